@@ -17,11 +17,16 @@ decode) runs underneath the VALU-bound front half of the next (cfa.EngineRing; a
 Every step still processes one whole batch; the windows are fenced by a synchronize of every context.
 `value_one_context` reports the same steps on a single context.
 
-Timing: W warm-up steps, then `--repeats` windows of EXACTLY K steps, each bracketed by barrier +
-synchronize on both sides, max over ranks per window; `value` comes from the MEDIAN window, min / max are
-reported next to it (`windows`).
+Timing: untimed set-up steps (every context x input buffer pair twice, at least 192 steps), W warm-up steps, then
+`--repeats` windows of EXACTLY K steps (default: one window, so a plain run times exactly K steps; 25 windows with --full),
+each bracketed by barrier + synchronize on both sides, max over ranks per window; `value` and `ms_per_step` come from the
+MEDIAN window, min / max are reported next to it (`windows`).
 
-Extra objects in the line:
+--dump-outputs DIR: after the timed windows, rank 0 writes what the last timed step returned to a caller as DIR/<name>.npy
+(float32; integer indices as float64): dets / lms / inds, or `records` (the gathered boxes) when N > 1 or with
+--exercise-gather-path.  Inputs and weights are seeded, so two builds run with the same arguments compare output for output.
+
+A plain run measures the headline only.  Extra objects in the line, with --full:
   roofline       -- dominant kernel symbol of the forward: algorithmic bytes per launch / average
                     launch duration, measured here with HIP events on the stream the kernels run on.
   cpu_baseline   -- the oracle (a torch-CPU restatement of the reference path, oracle/) timed on this
@@ -54,7 +59,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=25, help="timed windows of --steps steps; value = median window")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed windows of --steps steps; value = median window (default: 1, or 25 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline / per-kernel profile, value_with_h2d, value_one_context, "
+                         "parity, other_configs, standalone_depthwise, tolerance_mode, exact_fp32_mode, cpu_baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--batch", type=int, default=64, help="images per GPU per step")
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--topk", type=int, default=100)
@@ -62,8 +73,8 @@ def parse(argv=None):
                     help="contexts per GPU used round-robin (batches in flight); 1 = a single context, every step on one stream chain; "
                          "0 = automatic: 2, or 3 (decodes on the main streams) when a step is small (batch x size^2 <= 8 M pixels, e.g. four 1280x1280 images)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp32_split"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_with_h2d / tolerance_mode / exact_fp32_mode / parity (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip value_with_h2d / tolerance_mode / exact_fp32_mode / parity (profiling runs)")
     ap.add_argument("--gather", default="auto", choices=["auto", "cf", "torch"],
                     help="N > 1 gather of the final boxes: cf = cf_gather_topk (C ABI, RCCL), torch = torch.distributed; "
                          "auto = cf, falling back to torch if the communicator cannot be created")
@@ -84,7 +95,10 @@ def parse(argv=None):
     ap.add_argument("--traffic-json", default=None,
                     help="per-kernel HBM bytes from rocprofv3 PMC passes (tools/summarize_prof.py); "
                          "default: the newest profiles/traffic_*.json")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 25 if args.full else 1
+    return args
 
 
 def _host_core_set():
@@ -260,7 +274,29 @@ def make_step(cfa, engs, d_in_ptr, B, K, outs, gather="none", comms=None):   # d
             return out["all"]
         eng.decode_topk_device(K, out["dets"].data_ptr(), out["lms"].data_ptr(), out["inds"].data_ptr())
         return None
+    step.last_out = lambda: outs[(k[0] - 1) % depth]          # the output dict of the most recent step
     return step
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, gather):
+    """What the last step returned to a caller, as path/<name>.npy: the decoded dets / lms / inds, or the gathered records
+    when the step gathers.  float32; the int64 indices as float64 (exact).  Over DUMP_LIMIT_BYTES in all, a fixed seeded
+    sample of the images (leading axis) is kept, the same images in every array.  The caller has fenced the step."""
+    names = ("dets", "lms", "inds") if gather == "none" else ("records",)
+    arrays = {n: out["all" if n == "records" else n].cpu().numpy() for n in names}
+    arrays = {n: a.astype(np.float64 if a.dtype.kind in "iu" else np.float32) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = len(next(iter(arrays.values())))
+        keep = max(1, n * DUMP_LIMIT_BYTES // total)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(path, n + ".npy"), np.ascontiguousarray(a))
 
 
 def time_windows(step, fence, steps, repeats, reduce_max=None):
@@ -542,6 +578,88 @@ def tolerance_block(cfa, host_imgs, d_in_ptr, B, S, K, dev_index, aux, profile_r
     return out, vs_oracle, box_match, roof
 
 
+def roofline_block(cfa, eng, d_in_ptr, B, S, K, args):
+    """--full: the roofline of the dominant kernel symbol of the benchmarked forward (one context, HIP events around every launch,
+    `--profile-reps` forwards) and the VALU-issue bound of the forward's kernels from the committed instruction counts."""
+    # ---- per-kernel profile (HIP events on the ctx stream around every launch)
+    agg, tot_ms, dom_name, dom = kernel_profile(eng, cfa, d_in_ptr, B, K, args.profile_reps)
+    avg_ms = dom["ms"] / dom["launches"]
+    avg_bytes = dom["bytes"] / dom["launches"]
+    achieved = avg_bytes / (avg_ms * 1e-3) / 1e9
+    traffic = None
+    try:
+        import glob
+        tj = args.traffic_json or sorted(glob.glob(os.path.join(REPO, "profiles", "traffic_*.json")))[-1]
+        with open(tj) as f:
+            traffic = json.load(f).get(dom_name, {}).get("hbm_bytes_per_launch")
+    except Exception:
+        traffic = None
+    kinds = {}
+    for a in agg.values():
+        k = kinds.setdefault(a["kind"], dict(ms=0.0, bytes=0.0))
+        k["ms"] += a["ms"] / args.profile_reps; k["bytes"] += a["bytes"] / args.profile_reps
+    # ---- the roof that actually binds the fused kernels: VALU instruction issue.  Dynamic instruction counts per launch
+    # (rocprofv3 --pmc SQ_INSTS_*, committed as profiles/*_valu_counts.json by tools/valu_bound.py for THIS workload) x the
+    # committed issue costs, against this run's launch durations (HIP events) and the committed rocprofv3 durations.
+    valu_issue = None
+    try:
+        import glob
+        vj = sorted(glob.glob(os.path.join(REPO, "profiles", "*_valu_counts.json")))[-1]
+        vc = json.load(open(vj))
+        if (B, S, args.dtype) == (64, 640, "bf16"):
+            per, sb, sm, sr, sh = [], 0.0, 0.0, 0.0, 0.0
+            have_hw = True
+            for name, a in agg.items():
+                kc = vc["kernels"].get(name)
+                if kc is None:
+                    continue
+                n = a["launches"] // args.profile_reps
+                ms = a["ms"] / args.profile_reps
+                sb += kc["bound_us"] * n * 1e-3; sm += ms; sr += kc["rocprof_avg_us"] * n * 1e-3
+                hw = kc.get("bound_hw_us")
+                have_hw = have_hw and hw is not None
+                sh += (hw or 0.0) * n * 1e-3
+                per.append({"kernel": name, "launches": n, "bound_ms": round(kc["bound_us"] * n * 1e-3, 4), "measured_ms": round(ms, 4),
+                            "rocprof_ms": round(kc["rocprof_avg_us"] * n * 1e-3, 4), "frac": round(kc["bound_us"] * n * 1e-3 / ms, 3) if ms > 0 else None,
+                            "bound_hw_ms": round(hw * n * 1e-3, 4) if hw is not None else None,
+                            "frac_hw": round(hw * n * 1e-3 / ms, 3) if (hw is not None and ms > 0) else None})
+            per.sort(key=lambda r: -r["measured_ms"])
+            valu_issue = {"bound_ms": round(sb, 4), "measured_ms": round(sm, 4), "rocprof_ms": round(sr, 4),
+                          "frac": round(sb / sm, 4) if sm > 0 else None, "frac_vs_rocprof": round(sb / sr, 4) if sr > 0 else None,
+                          "bound_hw_ms": round(sh, 4) if have_hw else None, "frac_hw": round(sh / sm, 4) if (have_hw and sm > 0) else None,
+                          "frac_hw_vs_rocprof": round(sh / sr, 4) if (have_hw and sr > 0) else None,
+                          "cost_table": vc.get("cost_cycles_per_wave_instruction"), "cost_table_hw": vc.get("cost_hw_cycles_per_wave_instruction"),
+                          "counts": os.path.basename(vj), "counts_are": "committed dynamic instruction counts of this workload (a constant of the repo, not of this run); the measured_ms they are divided by are this run's",
+                          "per_kernel": per[:12],
+                          "note": "TWO cost tables.  bound_ms: sum over the forward's kernels of (wave-instruction counts x MEASURED issue cost, wall time of a dense "
+                                  "stream of that class expressed in cycles of a nominal 2.4 GHz: transcendental 9.45, packed 5.65, dot2c 4.53, VOP3 4.5, plain 3.1; "
+                                  "LDS / VMEM / MFMA issue slots) / 1024 SIMDs / 2.4 GHz -- what this instruction mix costs in wall time.  bound_hw_ms: VALU "
+                                  "instructions only at ARCHITECTURAL rates (transcendental 8, packed / dot2 4, everything else 2 shader cycles at 2.4 GHz): the "
+                                  "hardware guide's floor, which no sustained stream reaches (tools/ub_clock_probe.hip: dense v_fma_f32 = 2.28 shader cycles at a "
+                                  "power-capped 1.94 GHz).  measured = HIP events of this run (one context), rocprof = committed rocprofv3 --kernel-trace averages"}
+    except Exception:                                   # noqa: BLE001
+        valu_issue = None
+    dom_valu = None
+    if valu_issue:
+        dom_valu = next((r["frac"] for r in valu_issue["per_kernel"] if r["kernel"] == dom_name), None)
+    hbm_frac = achieved / HBM_PEAK_GBS
+    roofline = {
+        "bound": "valu_issue" if (dom_valu is not None and dom_valu > hbm_frac) else "hbm", "kernel": dom_name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+        "avg_launch_ms": round(avg_ms, 4), "algo_bytes_per_launch": avg_bytes,
+        "launches_per_forward": dom["launches"] // args.profile_reps, "layers": sorted(dom["layers"]),
+        "valu_issue_frac": dom_valu, "valu_issue": valu_issue,
+        "forward_ms_sum_of_kernels": round(tot_ms, 3),
+        # the fused kernels are VALU-issue bound (Swish: two transcendentals per expanded element), not HBM- or
+        # MFMA-bound: DESIGN.md section 4, profiles/r01_valu_microbench.md; whole-forward algorithmic rate:
+        "forward_algo_GBps": round(sum(a["bytes"] for a in agg.values()) / args.profile_reps / (tot_ms * 1e-3) / 1e9, 1),
+        "forward_TFLOPs": round(sum(a["flops"] for a in agg.values()) / args.profile_reps / (tot_ms * 1e-3) / 1e12, 1),
+        "by_kind": {k: {"ms": round(v["ms"], 3), "GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None}
+                    for k, v in kinds.items()},
+    }
+    return roofline
+
+
 def main():
     args = parse()
     if args.cpu_baseline_child:
@@ -681,6 +799,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    # untimed set-up.  A context captures its forward graph on the SECOND sighting of an input buffer, so every (context, input
+    # buffer) pair the steps rotate through runs at least twice here -- otherwise up to depth x buffers captures land in the timed
+    # window.  And the chip reaches the rate it sustains only after some load: on MI355X a window timed right after 5 warm-up steps ran
+    # 1-4 % slower than the later windows of the same process; ~0.25 s of fenced 8-step batches first brings that to about 1 %.
+    # A fixed count (not a time) so that every rank runs the same steps and barriers.
+    for i in range(max(2 * int(np.lcm(len(engs), len(d_in_ptrs))), 192)):
+        step()
+        if i % 8 == 7:
+            fence()
     for _ in range(args.warmup):
         step()
     wins = time_windows(step, fence, args.steps, max(1, args.repeats), reduce_max)
@@ -688,84 +815,10 @@ def main():
 
     result = None
     parity_aux = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step.last_out(), gather)
     if rank == 0:
         value = world * B * args.steps / med
-        # ---- per-kernel profile (HIP events on the ctx stream around every launch)
-        agg, tot_ms, dom_name, dom = kernel_profile(eng, cfa, d_in.data_ptr(), B, K, args.profile_reps)
-        avg_ms = dom["ms"] / dom["launches"]
-        avg_bytes = dom["bytes"] / dom["launches"]
-        achieved = avg_bytes / (avg_ms * 1e-3) / 1e9
-        traffic = None
-        try:
-            import glob
-            tj = args.traffic_json or sorted(glob.glob(os.path.join(REPO, "profiles", "traffic_*.json")))[-1]
-            with open(tj) as f:
-                traffic = json.load(f).get(dom_name, {}).get("hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
-        kinds = {}
-        for a in agg.values():
-            k = kinds.setdefault(a["kind"], dict(ms=0.0, bytes=0.0))
-            k["ms"] += a["ms"] / args.profile_reps; k["bytes"] += a["bytes"] / args.profile_reps
-        # ---- the roof that actually binds the fused kernels: VALU instruction issue.  Dynamic instruction counts per launch
-        # (rocprofv3 --pmc SQ_INSTS_*, committed as profiles/*_valu_counts.json by tools/valu_bound.py for THIS workload) x the
-        # committed issue costs, against this run's launch durations (HIP events) and the committed rocprofv3 durations.
-        valu_issue = None
-        try:
-            import glob
-            vj = sorted(glob.glob(os.path.join(REPO, "profiles", "*_valu_counts.json")))[-1]
-            vc = json.load(open(vj))
-            if (B, S, args.dtype) == (64, 640, "bf16"):
-                per, sb, sm, sr, sh = [], 0.0, 0.0, 0.0, 0.0
-                have_hw = True
-                for name, a in agg.items():
-                    kc = vc["kernels"].get(name)
-                    if kc is None:
-                        continue
-                    n = a["launches"] // args.profile_reps
-                    ms = a["ms"] / args.profile_reps
-                    sb += kc["bound_us"] * n * 1e-3; sm += ms; sr += kc["rocprof_avg_us"] * n * 1e-3
-                    hw = kc.get("bound_hw_us")
-                    have_hw = have_hw and hw is not None
-                    sh += (hw or 0.0) * n * 1e-3
-                    per.append({"kernel": name, "launches": n, "bound_ms": round(kc["bound_us"] * n * 1e-3, 4), "measured_ms": round(ms, 4),
-                                "rocprof_ms": round(kc["rocprof_avg_us"] * n * 1e-3, 4), "frac": round(kc["bound_us"] * n * 1e-3 / ms, 3) if ms > 0 else None,
-                                "bound_hw_ms": round(hw * n * 1e-3, 4) if hw is not None else None,
-                                "frac_hw": round(hw * n * 1e-3 / ms, 3) if (hw is not None and ms > 0) else None})
-                per.sort(key=lambda r: -r["measured_ms"])
-                valu_issue = {"bound_ms": round(sb, 4), "measured_ms": round(sm, 4), "rocprof_ms": round(sr, 4),
-                              "frac": round(sb / sm, 4) if sm > 0 else None, "frac_vs_rocprof": round(sb / sr, 4) if sr > 0 else None,
-                              "bound_hw_ms": round(sh, 4) if have_hw else None, "frac_hw": round(sh / sm, 4) if (have_hw and sm > 0) else None,
-                              "frac_hw_vs_rocprof": round(sh / sr, 4) if (have_hw and sr > 0) else None,
-                              "cost_table": vc.get("cost_cycles_per_wave_instruction"), "cost_table_hw": vc.get("cost_hw_cycles_per_wave_instruction"),
-                              "counts": os.path.basename(vj), "counts_are": "committed dynamic instruction counts of this workload (a constant of the repo, not of this run); the measured_ms they are divided by are this run's",
-                              "per_kernel": per[:12],
-                              "note": "TWO cost tables.  bound_ms: sum over the forward's kernels of (wave-instruction counts x MEASURED issue cost, wall time of a dense "
-                                      "stream of that class expressed in cycles of a nominal 2.4 GHz: transcendental 9.45, packed 5.65, dot2c 4.53, VOP3 4.5, plain 3.1; "
-                                      "LDS / VMEM / MFMA issue slots) / 1024 SIMDs / 2.4 GHz -- what this instruction mix costs in wall time.  bound_hw_ms: VALU "
-                                      "instructions only at ARCHITECTURAL rates (transcendental 8, packed / dot2 4, everything else 2 shader cycles at 2.4 GHz): the "
-                                      "hardware guide's floor, which no sustained stream reaches (tools/ub_clock_probe.hip: dense v_fma_f32 = 2.28 shader cycles at a "
-                                      "power-capped 1.94 GHz).  measured = HIP events of this run (one context), rocprof = committed rocprofv3 --kernel-trace averages"}
-        except Exception:                                   # noqa: BLE001
-            valu_issue = None
-        dom_valu = None
-        if valu_issue:
-            dom_valu = next((r["frac"] for r in valu_issue["per_kernel"] if r["kernel"] == dom_name), None)
-        hbm_frac = achieved / HBM_PEAK_GBS
-        roofline = {
-            "bound": "valu_issue" if (dom_valu is not None and dom_valu > hbm_frac) else "hbm", "kernel": dom_name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-            "avg_launch_ms": round(avg_ms, 4), "algo_bytes_per_launch": avg_bytes,
-            "launches_per_forward": dom["launches"] // args.profile_reps, "layers": sorted(dom["layers"]),
-            "valu_issue_frac": dom_valu, "valu_issue": valu_issue,
-            "forward_ms_sum_of_kernels": round(tot_ms, 3),
-            # the fused kernels are VALU-issue bound (Swish: two transcendentals per expanded element), not HBM- or
-            # MFMA-bound: DESIGN.md section 4, profiles/r01_valu_microbench.md; whole-forward algorithmic rate:
-            "forward_algo_GBps": round(sum(a["bytes"] for a in agg.values()) / args.profile_reps / (tot_ms * 1e-3) / 1e9, 1),
-            "forward_TFLOPs": round(sum(a["flops"] for a in agg.values()) / args.profile_reps / (tot_ms * 1e-3) / 1e12, 1),
-            "by_kind": {k: {"ms": round(v["ms"], 3), "GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None}
-                        for k, v in kinds.items()},
-        }
         result = {
             "metric": "images/sec at 640x640 batch inference", "value": round(value, 1), "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * med / args.steps, 4),
@@ -786,9 +839,10 @@ def main():
             "windows": {"n": len(wins), "steps_each": args.steps, "median_ms": round(1e3 * med, 5),
                         "min_ms": round(1e3 * min(wins), 5), "max_ms": round(1e3 * max(wins), 5),
                         "value_min": round(world * B * args.steps / max(wins), 1), "value_max": round(world * B * args.steps / min(wins), 1)},
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_extras:
+        if args.full:
+            result["roofline"] = roofline_block(cfa, eng, d_in.data_ptr(), B, S, K, args)
+        if args.full and world == 1 and not args.no_extras:
             # ---- PCIe-inclusive: the batch starts in pinned host memory every step (H2D on the copy stream, overlapped)
             pinned = torch.from_numpy(host_imgs).pin_memory()
             hview = pinned.numpy()
@@ -812,7 +866,7 @@ def main():
                                                "note": "the same steps on a single context (one batch in flight); median of 7 windows"}
             parity_aux, result["parity"] = parity_block(cfa, eng, host_imgs, d_in.data_ptr(), B, S, K, local_rank)
     eng_closed = False
-    if rank == 0 and world == 1 and not args.no_extras and args.dtype == "bf16":
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.dtype == "bf16":
         close_comms()
         for e in engs:
             e.close()
@@ -869,10 +923,9 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline:                # rank 0, every N: the other ranks have left by now and the host cores are idle
-            result["cpu_baseline"] = cpu_baseline(args.cpu_seconds, S, K, host_imgs)
-        else:
-            result["cpu_baseline"] = None
+        if args.full:
+            # rank 0, every N: the other ranks have left by now and the host cores are idle
+            result["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(args.cpu_seconds, S, K, host_imgs)
         flush_c_stdio()
         print(json.dumps(result), flush=True)       # the one JSON line, last on stdout
     if hard_exit:                                   # a thread is still blocked inside ncclCommInitRank: skip interpreter teardown

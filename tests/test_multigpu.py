@@ -540,11 +540,11 @@ def test_bench_standalone_depthwise_block_runs():
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    """bench.py as the driver runs it (small workload): exactly one line on stdout, the contract's fields, roofline and
+    """bench.py --full (small workload): exactly one line on stdout, the contract's fields, roofline and
     the per-run consistency the judge checks (value = images of the median window / its time)."""
     import json
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--repeats", "3",
-                          "--batch", "4", "--size", "160", "--topk", "20", "--no-cpu-baseline", "--no-extras", "--profile-reps", "1"],
+                          "--batch", "4", "--size", "160", "--topk", "20", "--full", "--no-cpu-baseline", "--no-extras", "--profile-reps", "1"],
                          capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]

@@ -72,7 +72,7 @@ def main():
              "Note: the decode kernels (`peak_collect_kernel`, `topk_select_kernel`) run on the context's second stream "
              "underneath the next forward (device-output decode in bench.py), so their durations here are stretched by "
              "sharing the chip; timed alone they are in the per-launch table below.", "",
-             "Source: `rocprofv3 --kernel-trace --stats -- python bench.py --depth 1 --steps 10 --warmup 3 --repeats 3 --no-cpu-baseline --no-extras` "
+             "Source: `rocprofv3 --kernel-trace --stats -- python bench.py --full --depth 1 --steps 10 --warmup 3 --repeats 3 --no-cpu-baseline --no-extras` "
              "(ONE context, as bench.py's roofline block times the kernels; with the default ring of two contexts kernels of two "
              "batches share the chip and every duration stretches -- second table) "
              "(kernel durations) and two `--pmc` passes over `tools/profile_ops.py` (FETCH_SIZE, WRITE_SIZE; "

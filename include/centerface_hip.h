@@ -132,7 +132,29 @@ int cf_forward_images(cf_ctx* ctx, const void* const* imgs, int B, int h, int w)
  * that the copy queue never stands behind a forward (CenterFaceBuckets: 5 contexts, 128 VGA images, profiles/r05_vga_pipeline.md). */
 int cf_upload_images(cf_ctx* ctx, const void* const* imgs, int B, int h, int w);
 int cf_forward_uploaded(cf_ctx* ctx);
-/* the resized uint8 [B,H,W,3] batch of the last cf_forward_resized (tests) */
+/* ---- 4:2:0 video frames: cv2.cvtColor(frame, COLOR_YUV2BGR_<fmt>) on the device, then the network ------------------- */
+#define CF_YUV_NV12 0            /* Y plane, then one interleaved U,V plane (what hardware decoders emit) */
+#define CF_YUV_NV21 1            /* Y plane, then one interleaved V,U plane */
+#define CF_YUV_I420 2            /* Y, U, V planes (yuv420p: what software decoders emit) */
+#define CF_YUV_YV12 3            /* Y, V, U planes */
+typedef struct cf_yuv_planes {
+    const void* y;               /* h rows of y_pitch bytes */
+    const void* c0;              /* first chroma plane in the format's order: NV12 / NV21 the interleaved plane, I420 U, YV12 V
+                                    (h/2 rows of c_pitch bytes) */
+    const void* c1;              /* second chroma plane (I420 V, YV12 U); NULL for NV12 / NV21 */
+} cf_yuv_planes;
+/* B frames of h x w (both even, >= 2) in format yuv_format (CF_YUV_*), frames[b] = the planes of frame b: converted to uint8 BGR
+ * with OpenCV's fixed-point BT.601 limited-range arithmetic (COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12; restated in csrc/cf_yuv.hip
+ * from the published algorithm, not pinned to a cv2 binary), stretch-resized to the ctx's (H, W) like cf_forward_resized when
+ * (h, w) differs, and fed to the network: every result equals that of the BGR frames through cf_forward / cf_forward_resized.
+ * y_pitch >= w, c_pitch >= w (NV12 / NV21) or w/2 (I420 / YV12), in bytes.  Host frames (in_on_device = 0) are copied into a
+ * device staging buffer: ONE DMA when the batch is one dense block of OpenCV's [h*3/2, w] frames (y_pitch = w, c_pitch = the
+ * chroma row), else one pitched 2-D copy per plane per frame; keep them unchanged until a blocking call on ctx has returned.
+ * Device frames (in_on_device = 1) are read in place; their plane addresses and pitches must be multiples of 4.  CF_EINVAL for
+ * any bad argument, before anything is enqueued.  Asynchronous. */
+int cf_forward_yuv(cf_ctx* ctx, int yuv_format, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w,
+                   int y_pitch, int c_pitch);
+/* the uint8 [B,H,W,3] BGR batch the network read in the last cf_forward_resized or cf_forward_yuv (resized / converted; tests) */
 int cf_get_resized_input(cf_ctx* ctx, void* out_u8, int B);
 /* copies the four head maps of the last forward to host as NCHW float32: hm [B,1,h,w] raw logits
  * (what net() returns), wh [B,2,h,w], lm [B,10,h,w], reg [B,2,h,w]; h=H/4, w=W/4 (model/centernet.py
@@ -422,6 +444,10 @@ int cf_op_decode_threshold_ex(int device, int mode, const float* hm, const float
 /* ctdet_post_process's coordinate part on explicit detections dets [B,K,dim] (in place, host array) */
 int cf_op_ctdet_post_process(int device, float* dets, const float* centers, const float* scales, int B, int K,
                              int dim, int out_w, int out_h);
+/* The conversion kernel of cf_forward_yuv alone, on host arrays: dense frames [B][h*3/2][w] (OpenCV's single-buffer layout, what
+ * cv2.cvtColor(bgr, COLOR_BGR2YUV_I420) returns) -> bgr [B][H][W][3].  (H, W) == (h, w): the conversion only; otherwise followed
+ * by cv2.resize to (H, W).  h, w, W even. */
+int cf_op_yuv_to_bgr(int device, int yuv_format, const uint8_t* frames, uint8_t* bgr, int B, int h, int w, int H, int W);
 /* CenterFace.nms alone (centerface.py:111-151): keep[] receives kept indices in keep order. */
 int cf_op_nms(int device, const float* boxes, const float* scores, int n, float nms_thresh,
               int32_t* keep, int32_t* n_keep);

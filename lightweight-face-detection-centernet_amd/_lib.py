@@ -16,15 +16,19 @@ CF_F32, CF_BF16, CF_F32_SPLIT = 0, 1, 2
 CF_IN_U8_HWC_BGR, CF_IN_F32_NCHW = 0, 1
 CF_FLAG_COLLAPSE_HEADS, CF_FLAG_NO_GRAPH, CF_FLAG_NO_FUSE, CF_FLAG_NO_UPHEAD, CF_FLAG_NO_NECK, CF_FLAG_NO_DECODE_STREAM, CF_FLAG_STREAM_HIGH = 1, 2, 4, 8, 16, 32, 64
 CF_EOVERFLOW = -6
+# 4:2:0 video frame formats of cf_forward_yuv / cf_op_yuv_to_bgr (cv2.COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12)
+CF_YUV_NV12, CF_YUV_NV21, CF_YUV_I420, CF_YUV_YV12 = 0, 1, 2, 3
+YUV_FORMATS = {"nv12": CF_YUV_NV12, "nv21": CF_YUV_NV21, "i420": CF_YUV_I420, "yuv420p": CF_YUV_I420, "yv12": CF_YUV_YV12}
 
 # every symbol include/centerface_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
     "cf_version", "cf_strerror", "cf_last_error", "cf_device_count", "cf_create", "cf_destroy",
-    "cf_load_weights", "cf_forward", "cf_forward_resized", "cf_forward_images", "cf_upload_images", "cf_forward_uploaded", "cf_get_resized_input", "cf_get_heads", "cf_decode_topk", "cf_decode_topk_post", "cf_affine_from_center_scale", "cf_decode_threshold", "cf_decode_threshold_ex", "cf_decode_threshold_sized", "cf_decode_threshold_enqueue", "cf_set_rescale",
+    "cf_load_weights", "cf_forward", "cf_forward_resized", "cf_forward_yuv", "cf_forward_images", "cf_upload_images", "cf_forward_uploaded", "cf_get_resized_input", "cf_get_heads", "cf_decode_topk", "cf_decode_topk_post", "cf_affine_from_center_scale", "cf_decode_threshold", "cf_decode_threshold_ex", "cf_decode_threshold_sized", "cf_decode_threshold_enqueue", "cf_set_rescale",
     "cf_detect_topk", "cf_synchronize", "cf_event_record", "cf_event_elapsed_ms",
     "cf_profile_forward", "cf_plan_size", "cf_plan_op", "cf_forward_trace", "cf_graph_stats", "cf_get_streams", "cf_streams_share_queue", "cf_streams_share_queue_ex", "cf_spread_streams", "cf_reroll_streams", "cf_ctdet_loss", "cf_comm_unique_id", "cf_comm_create", "cf_comm_create_all", "cf_comm_create_loopback", "cf_comm_loopback_rank", "cf_comm_destroy", "cf_comm_abort", "cf_comm_query", "cf_comm_synchronize", "cf_comm_last_error", "cf_comm_debug", "cf_comm_set_shard", "cf_comm_stream", "cf_gather_topk", "cf_host_alloc", "cf_host_free", "cf_pinned_alloc", "cf_pinned_free", "cf_host_register", "cf_host_unregister", "cf_device_alloc", "cf_device_free", "cf_memcpy_h2d", "cf_memcpy_d2h",
     "cf_op_last_error", "cf_op_shufflev2", "cf_op_mbconv", "cf_op_expand_dw", "cf_op_ctdet_loss", "cf_op_encode_targets", "cf_op_dwconv", "cf_op_pwconv", "cf_op_stem", "cf_op_idaup", "cf_op_heads",
     "cf_op_ctdet_decode", "cf_op_ctdet_post_process", "cf_op_decode_threshold", "cf_op_decode_threshold_ex", "cf_op_nms", "cf_op_box_match",
+    "cf_op_yuv_to_bgr",
 )
 
 
@@ -41,6 +45,28 @@ class OpTime(C.Structure):
 class OpInfo(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("kind", C.c_char * 16), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("fused_away", C.c_int32)]
+
+
+class YuvPlanes(C.Structure):
+    """cf_yuv_planes: the planes of one frame (c0 / c1 = the chroma planes in the format's order; c1 NULL for NV12 / NV21)."""
+    _fields_ = [("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p)]
+
+
+def yuv_format(fmt):
+    """CF_YUV_* code of a format name ('nv12', 'nv21', 'i420' / 'yuv420p', 'yv12'); integer codes pass through unchanged (the
+    library validates them)."""
+    if isinstance(fmt, str):
+        if fmt.lower() not in YUV_FORMATS:
+            raise ValueError("unknown YUV format %r (one of %s)" % (fmt, sorted(YUV_FORMATS)))
+        return YUV_FORMATS[fmt.lower()]
+    return int(fmt)
+
+
+def yuv_dense_geometry(fmt, h, w):
+    """(plane offsets (y, c0, c1 or None), c_pitch) of one frame in OpenCV's single-buffer [h*3/2, w] layout."""
+    if fmt in (CF_YUV_NV12, CF_YUV_NV21):
+        return (0, h * w, None), w
+    return (0, h * w, h * w + (h // 2) * (w // 2)), w // 2
 
 
 def build(force=False, verbose=False):
@@ -79,6 +105,8 @@ def lib():
             L.cf_forward_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
             L.cf_forward_lanes_flush.argtypes = [C.c_void_p]
         L.cf_forward_resized.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.cf_forward_yuv.argtypes = [C.c_void_p, C.c_int, C.POINTER(YuvPlanes), C.c_int] + [C.c_int] * 5
+        L.cf_op_yuv_to_bgr.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
         L.cf_get_resized_input.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.cf_get_heads.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.cf_decode_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

@@ -148,6 +148,58 @@ class Engine(object):
         self._chk(self._L.cf_forward_resized(self._h, _lib.ptr(x), 0, x.shape[0], x.shape[1], x.shape[2]))
         self.last_B = x.shape[0]
 
+    def forward_yuv_enqueue(self, frames, fmt="nv12", *, on_device=False, h=None, w=None, y_pitch=None, c_pitch=None):
+        """4:2:0 video frames -> BGR on the device -> forward (``cf_forward_yuv``): the same results as the frames'
+        ``cv2.cvtColor(frame, cv2.COLOR_YUV2BGR_<fmt>)`` through ``forward_enqueue`` (or ``forward_resized_enqueue`` when (h, w) is
+        not the network size), at half the bytes of BGR over the link.  ``fmt``: 'nv12', 'nv21', 'i420' ('yuv420p') or 'yv12'.
+        ``frames``: uint8 [B, h*3//2, w] (OpenCV's single-buffer layout: one DMA), or a list of [h*3//2, w] arrays of one size (one
+        descriptor per frame, no host stacking; page-locked arrays -- ``pinned_empty`` -- are DMA'd directly).  ``on_device=True``:
+        a list of (y, c0, c1) device addresses, chroma planes in the format's order (c1 None for NV12 / NV21), with ``h``, ``w`` and
+        the row pitches in bytes (default: dense rows; addresses and pitches multiples of 4)."""
+        f = _lib.yuv_format(fmt)
+        if on_device:
+            if h is None or w is None:
+                raise ValueError("forward_yuv_enqueue(on_device=True) needs h and w")
+            h, w = int(h), int(w)
+            addrs = [(tuple(t) + (None, None))[:3] for t in frames]
+            keep = None
+        else:
+            if isinstance(frames, np.ndarray):
+                x = np.ascontiguousarray(frames)
+                if x.dtype != np.uint8 or x.ndim != 3:
+                    raise ValueError("frames must be uint8 [B, h*3//2, w], got %s %s" % (x.dtype, x.shape))
+                arrs, shp, bases = x, x.shape[1:], [x.ctypes.data + b * x[0].nbytes for b in range(x.shape[0])]
+            else:
+                arrs = [np.asarray(a) for a in frames]
+                if not arrs:
+                    raise ValueError("forward_yuv_enqueue needs at least one frame")
+                shp = arrs[0].shape
+                for a in arrs:
+                    if a.dtype != np.uint8 or a.ndim != 2 or a.shape != shp:
+                        raise ValueError("frames must be uint8 [h*3//2, w] arrays of one size, got %s %s (first: %s)" % (a.dtype, a.shape, shp))
+                arrs = [a if a.flags["C_CONTIGUOUS"] else np.ascontiguousarray(a) for a in arrs]
+                bases = [a.ctypes.data for a in arrs]
+            rows, fw = int(shp[0]), int(shp[1])
+            fh = rows * 2 // 3
+            if fh * 3 // 2 != rows or (h is not None and int(h) != fh) or (w is not None and int(w) != fw):
+                raise ValueError("a 4:2:0 frame of h x w is [h*3//2, w] with h even; got %s (h=%s, w=%s)" % (shp, h, w))
+            h, w = fh, fw
+            offs, cp = _lib.yuv_dense_geometry(f, h, w)
+            if (y_pitch is not None and int(y_pitch) != w) or (c_pitch is not None and int(c_pitch) != cp):
+                raise ValueError("host frames are dense [h*3//2, w] arrays: y_pitch = w, c_pitch = the chroma row")
+            addrs = [tuple(None if o is None else a + o for o in offs) for a in bases]
+            keep = arrs
+        il = f in (_lib.CF_YUV_NV12, _lib.CF_YUV_NV21)
+        y_pitch = w if y_pitch is None else int(y_pitch)
+        c_pitch = (w if il else w // 2) if c_pitch is None else int(c_pitch)
+        descs = (_lib.YuvPlanes * max(len(addrs), 1))()
+        for b, (y, c0, c1) in enumerate(addrs):
+            descs[b].y, descs[b].c0, descs[b].c1 = y or None, c0 or None, c1 or None
+        if keep is not None:
+            self._keep_in = keep
+        self._chk(self._L.cf_forward_yuv(self._h, f, descs, 1 if on_device else 0, len(addrs), h, w, y_pitch, c_pitch))
+        self.last_B = len(addrs)
+
     def forward_images_enqueue(self, images, upload_only=False):
         """The batch as a LIST of uint8 [h,w,3] BGR arrays of one common size (``cf_forward_images``): one asynchronous DMA per
         image, resize on the device when (h, w) is not the network size.  With page-locked arrays (``pinned_empty`` / ``pin``)
@@ -190,7 +242,7 @@ class Engine(object):
         self._chk(self._L.cf_set_rescale(self._h, float(scale_h), float(scale_w)))
 
     def resized_input(self):
-        """The resized uint8 [B,H,W,3] batch of the last forward_resized_enqueue (for tests)."""
+        """The uint8 [B,H,W,3] BGR batch the network read in the last forward_resized_enqueue / forward_yuv_enqueue (for tests)."""
         out = np.empty((self.last_B, self.H, self.W, 3), np.uint8)
         self._chk(self._L.cf_get_resized_input(self._h, _lib.ptr(out), self.last_B))
         return out
@@ -517,6 +569,7 @@ class CenterFace(object):
     def __init__(self, height, width, landmarks=True, *, weights=None, dtype="fp32", device=0,
                  max_batch=1, collapse_heads=None, nms_thresh=0.3, max_dets=1024):
         self.landmarks = landmarks
+        self.src_hw = (int(height), int(width))                                  # the frame size detect_yuv takes
         self.img_h_new, self.img_w_new, self.scale_h, self.scale_w = self.transform(height, width)
         self.nms_thresh = nms_thresh
         self.max_dets = max_dets
@@ -612,11 +665,45 @@ class CenterFace(object):
             self.engine.set_rescale(0.0, 0.0)
         return out
 
-    def detect_stream(self, imgs, threshold=0.2):
+    def _yuv_frames(self, frames):
+        """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]
+        array as it is, anything else as a list of [height*3//2, width] arrays."""
+        want = (self.src_hw[0] * 3 // 2, self.src_hw[1])
+        if isinstance(frames, np.ndarray) and frames.ndim == 3:
+            if frames.dtype != np.uint8 or frames.shape[1:] != want:
+                raise ValueError("frames must be uint8 [B, %d, %d] (4:2:0 frames of %dx%d), got %s %s"
+                                 % (want + self.src_hw + (frames.dtype, frames.shape)))
+            return frames
+        frames = [np.asarray(f) for f in frames]
+        for f in frames:
+            if f.dtype != np.uint8 or f.shape != want:
+                raise ValueError("frames must be uint8 [%d, %d] arrays (4:2:0 frames of %dx%d), got %s %s"
+                                 % (want + self.src_hw + (f.dtype, f.shape)))
+        return frames
+
+    def detect_yuv(self, frames, fmt="nv12"):
+        """``detect_batch`` for 4:2:0 video frames -- NV12 / NV21 from hardware decoders, I420 (yuv420p) / YV12 from software ones:
+        the same results as ``detect_batch([cv2.cvtColor(f, cv2.COLOR_YUV2BGR_<fmt>) for f in frames])``, with the conversion on the
+        device and half the bytes of BGR over the link.  ``frames``: uint8 [B, height*3//2, width] or a list of [height*3//2, width]
+        arrays, (height, width) = the size this instance was built for (ValueError otherwise)."""
+        frames = self._yuv_frames(frames)
+        out = []
+        self.engine.set_rescale(self.scale_h, self.scale_w)                  # centerface.py:55-62 inside the decode kernel
+        try:
+            for i in range(0, len(frames), self.engine.max_batch):
+                self.engine.forward_yuv_enqueue(frames[i:i + self.engine.max_batch], fmt)
+                out.extend(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True))
+        finally:
+            self.engine.set_rescale(0.0, 0.0)
+        return out
+
+    def detect_stream(self, imgs, threshold=0.2, *, fmt=None):
         """``__call__`` over an iterable of same-sized images, results yielded in order (the loop of demo.py:30-38 /
         eval_widerface.py:76-90).  The reference runs one synchronous call per image; here two contexts alternate, the
         forward of chunk i+1 (``max_batch`` images) is enqueued before the host waits for the decode of chunk i, so the GPU
-        works on one chunk while the host decodes and rescales the other.  Same results as ``__call__`` (tests)."""
+        works on one chunk while the host decodes and rescales the other.  Same results as ``__call__`` (tests).
+        ``fmt`` ('nv12', 'nv21', 'i420', 'yv12'): the items are 4:2:0 video frames of the instance's size, as ``detect_yuv`` takes
+        them -- a decoder's output, converted on the device."""
         del threshold
         if self._engine2 is None:
             self._engine2 = Engine(self.img_h_new, self.img_w_new, **self._engine_kw)
@@ -630,6 +717,8 @@ class CenterFace(object):
             chunk = [np.asarray(im, dtype=np.uint8) for im in chunk]
             e.set_rescale(self.scale_h, self.scale_w)
             try:
+                if fmt is not None:
+                    return e.forward_yuv_enqueue(self._yuv_frames(chunk), fmt)
                 if all(is_pinned(im) for im in chunk):
                     return e.forward_images_enqueue(chunk)
                 batch = np.stack(chunk)

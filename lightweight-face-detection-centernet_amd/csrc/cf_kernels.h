@@ -320,6 +320,11 @@ hipError_t launch_box_match(hipStream_t s, const OverlapParams& p);
 hipError_t launch_resize_u8(hipStream_t s, const uint8_t* src, uint8_t* dst, int B, int h, int w, int H, int W);
 // B page-locked host images (device-visible addresses, 16-byte aligned, `bytes` each) -> dst [B][bytes], read over PCIe by a kernel
 hipError_t launch_upload_images(hipStream_t s, const void* const* imgs, uint8_t* dst, int B, long long bytes);
+// 4:2:0 frames (fmt = CF_YUV_*; planes = B x {y, c0, c1} device addresses, c1 unused for NV12 / NV21) -> uint8 BGR dst [B][H][W][3]:
+// cv2.cvtColor(COLOR_YUV2BGR_<fmt>), then cv2.resize to (H, W) when (H, W) != (h, w) (cf_yuv.hip).  h, w, W even; plane addresses
+// and pitches multiples of 4
+hipError_t launch_yuv_to_bgr(hipStream_t s, int fmt, const void* const* planes, int B, int h, int w, int y_pitch, int c_pitch,
+                             uint8_t* dst, int H, int W);
 
 // layout converters used by cf_get_heads and the per-op test entry points
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*T NHWC*/,

@@ -624,4 +624,27 @@ int cf_op_box_match(int device, int n_img, const float* boxes, int box_stride, c
     return sc.result("cf_op_box_match");
 }
 
+// The conversion kernel of cf_forward_yuv on dense host frames [B][h*3/2][w] -> bgr [B][H][W][3] ((H, W) != (h, w): convert + resize).
+int cf_op_yuv_to_bgr(int device, int yuv_format, const uint8_t* frames, uint8_t* bgr, int B, int h, int w, int H, int W) {
+    if (!frames || !bgr || B < 1 || yuv_format < CF_YUV_NV12 || yuv_format > CF_YUV_YV12 || h < 2 || w < 2 || (h & 1) || (w & 1) ||
+        H < 1 || W < 2 || (W & 1)) {
+        g_op_error = "cf_op_yuv_to_bgr: null buffer, B < 1, unknown format, or h / w / W not even and at least 2";
+        return CF_EINVAL;
+    }
+    const bool il = yuv_format == CF_YUV_NV12 || yuv_format == CF_YUV_NV21;
+    const int cw = il ? w : w / 2;
+    const size_t ybytes = (size_t)h * w, cbytes = (size_t)(h / 2) * cw, one = ybytes + (il ? cbytes : 2 * cbytes);
+    Scope sc(device);
+    const uint8_t* src = (const uint8_t*)sc.up(frames, one * B);
+    uint8_t* out = (uint8_t*)sc.alloc((size_t)B * H * W * 3);
+    std::vector<const void*> planes((size_t)3 * B);
+    for (int b = 0; b < B && src; ++b) {
+        const uint8_t* f = src + b * one;
+        planes[3 * b] = f; planes[3 * b + 1] = f + ybytes; planes[3 * b + 2] = il ? nullptr : f + ybytes + cbytes;
+    }
+    if (sc.err == hipSuccess) sc.chk(launch_yuv_to_bgr(sc.s, yuv_format, planes.data(), B, h, w, w, cw, out, H, W));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(bgr, out, (size_t)B * H * W * 3, hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_yuv_to_bgr");
+}
+
 }  // extern "C"

@@ -1292,6 +1292,71 @@ int cf_forward_images(cf_ctx* c, const void* const* imgs, int B, int h, int w) {
     return r ? r : cf_forward_uploaded(c);
 }
 
+// 4:2:0 video frames -> BGR (cf_yuv.hip) -> the network.  The conversion writes input_resized, so the plan and its graphs are those of
+// cf_forward_resized.  Host frames land in src_stage under the protocol above (small batches on the main stream; large ones on the
+// copy stream, waiting only for the conversion of the batch before to have read the buffer): one DMA for a dense block, else one
+// pitched 2-D copy per plane per frame.  Device frames are read in place.
+int cf_forward_yuv(cf_ctx* c, int fmt, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w, int y_pitch, int c_pitch) {
+    if (!c) return CF_EINVAL;
+    if (!c->weights_loaded) return c->fail(CF_ESTATE, "cf_forward_yuv before cf_load_weights");
+    if (fmt < CF_YUV_NV12 || fmt > CF_YUV_YV12) return c->fail(CF_EINVAL, "cf_forward_yuv: unknown format %d (0..3: NV12, NV21, I420, YV12)", fmt);
+    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return c->fail(CF_EINVAL, "cf_forward_yuv: h=%d, w=%d must be even and at least 2", h, w);
+    if (B < 1 || B > c->max_batch) return c->fail(CF_EINVAL, "cf_forward_yuv: B=%d outside [1, %d]", B, c->max_batch);
+    if (!frames) return c->fail(CF_EINVAL, "cf_forward_yuv: null frame table");
+    const bool il = fmt == CF_YUV_NV12 || fmt == CF_YUV_NV21;
+    const int cw = il ? w : w / 2;                                       // chroma bytes per row
+    if (y_pitch < w || c_pitch < cw)
+        return c->fail(CF_EINVAL, "cf_forward_yuv: pitches %d (luma) / %d (chroma) below the row sizes %d / %d", y_pitch, c_pitch, w, cw);
+    if (in_on_device && ((y_pitch | c_pitch) & 3))
+        return c->fail(CF_EINVAL, "cf_forward_yuv: device pitches must be multiples of 4 (got %d, %d)", y_pitch, c_pitch);
+    for (int b = 0; b < B; ++b) {
+        const cf_yuv_planes& f = frames[b];
+        if (!f.y || !f.c0 || (!il && !f.c1)) return c->fail(CF_EINVAL, "cf_forward_yuv: frame %d has a null plane", b);
+        const uintptr_t a = reinterpret_cast<uintptr_t>(f.y) | reinterpret_cast<uintptr_t>(f.c0) | (il ? 0 : reinterpret_cast<uintptr_t>(f.c1));
+        if (in_on_device && (a & 3)) return c->fail(CF_EINVAL, "cf_forward_yuv: the device planes of frame %d must be 4-byte aligned", b);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    CF_FLUSH_LANE(c);
+    uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
+    const size_t ybytes = (size_t)h * w, cbytes = (size_t)(h / 2) * cw, one = ybytes + (il ? cbytes : 2 * cbytes);     // = h * w * 3 / 2
+    std::vector<const void*> planes((size_t)3 * B);
+    if (!in_on_device) {
+        const size_t bytes = one * B;
+        int r = src_stage_begin(c, bytes); if (r) return r;
+        const hipStream_t cs = src_stage_stream(c, bytes);
+        const uint8_t* base = (const uint8_t*)frames[0].y;
+        bool dense = y_pitch == w && c_pitch == cw;                      // the whole batch is one [B][h*3/2][w] block
+        for (int b = 0; dense && b < B; ++b) {
+            const uint8_t* f = base + b * one;
+            dense = frames[b].y == f && frames[b].c0 == f + ybytes && (il || frames[b].c1 == f + ybytes + cbytes);
+        }
+        if (dense) HIPCHK(c, hipMemcpyAsync(c->src_stage, base, bytes, hipMemcpyHostToDevice, cs));
+        for (int b = 0; b < B; ++b) {
+            uint8_t* f = c->src_stage + b * one;
+            if (!dense) {
+                HIPCHK(c, hipMemcpy2DAsync(f, w, frames[b].y, y_pitch, w, h, hipMemcpyHostToDevice, cs));
+                HIPCHK(c, hipMemcpy2DAsync(f + ybytes, cw, frames[b].c0, c_pitch, cw, h / 2, hipMemcpyHostToDevice, cs));
+                if (!il) HIPCHK(c, hipMemcpy2DAsync(f + ybytes + cbytes, cw, frames[b].c1, c_pitch, cw, h / 2, hipMemcpyHostToDevice, cs));
+            }
+            planes[3 * b] = f; planes[3 * b + 1] = f + ybytes; planes[3 * b + 2] = il ? nullptr : f + ybytes + cbytes;
+        }
+        if (cs != c->stream) {
+            HIPCHK(c, hipEventRecord(c->ev_src_copy, cs));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_src_copy, 0));
+        }
+        HIPCHK(c, launch_yuv_to_bgr(c->stream, fmt, planes.data(), B, h, w, w, cw, dst, c->H, c->W));
+        HIPCHK(c, hipEventRecord(c->ev_src_free, c->stream));
+        c->src_busy = true;
+    } else {
+        for (int b = 0; b < B; ++b) { planes[3 * b] = frames[b].y; planes[3 * b + 1] = frames[b].c0; planes[3 * b + 2] = il ? nullptr : frames[b].c1; }
+        HIPCHK(c, launch_yuv_to_bgr(c->stream, fmt, planes.data(), B, h, w, y_pitch, c_pitch, dst, c->H, c->W));
+    }
+    int r = launch_all_ops(c, dst, CF_IN_U8_HWC_BGR, B);
+    if (r) return r;
+    c->last_B = B;
+    return CF_OK;
+}
+
 
 // centerface.py:55-62 on the device: the threshold decode writes floor(x / scale_w), floor(y / scale_h) for the four box corners and
 // the five landmark points (numpy's float32 `//` by a python float: the exact floor of the quotient -- evaluated here as the floor of

@@ -2,6 +2,7 @@
 // the test boundary (cf_get_heads / cf_op_*).
 #include "cf_common.h"
 #include "cf_kernels.h"
+#include "cf_cvresize.h"
 #include <cstdarg>
 #include <cstdio>
 
@@ -14,35 +15,7 @@ void set_kernel_tag(const char* fmt, ...) {
 }
 
 // ---------------------------------------------------------------- bilinear resize (centerface.py:30)
-// cv2.resize(img, (W, H)) with the default INTER_LINEAR on uint8 is FIXED-POINT in OpenCV (third-party code, not
-// under /root/reference and not installable here; algorithm restated from OpenCV 4.x modules/imgproc/src/resize.cpp,
-// the generic path all SIMD paths are bit-exact with):
-//   * per destination column: fx = (float)((dx + 0.5) * scale_x - 0.5) with scale_x = 1.0 / ((double)W / w),
-//     sx = floor(fx), fx -= sx; sx < 0 -> (sx, fx) = (0, 0); sx >= w - 1 -> (w - 1, 0);
-//     coefficients as shorts with 11 fractional bits: a0 = cvRound((1.f - fx) * 2048), a1 = cvRound(fx * 2048);
-//   * rows likewise (fy, sy, b0, b1), except that out-of-range rows are CLAMPED (sy + k -> [0, h - 1]) and the
-//     coefficients kept;
-//   * horizontal pass in int32: r = S[sx] * a0 + S[sx + 1] * a1;
-//   * vertical pass (VResizeLinear<uchar, int, short, FixedPtCast<int, uchar, 22>>):
-//     dst = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2.
-// cvRound = round-half-to-even (rintf).  Parity with an actual cv2 build is UNPINNED (no cv2 anywhere we can run);
-// the oracle restates the same published algorithm and the known answers in the tests (identity, exact 2x
-// patterns) are derived by hand from it.
-__device__ __forceinline__ void cv_linear_coeffs(int d, int src, int dst, bool clamp_coeff, int& s0, int& s1, int& c0, int& c1) {
-    const double scale = 1.0 / ((double)dst / (double)src);
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int si = (int)floorf(f);
-    f -= (float)si;
-    if (clamp_coeff) {                                   // columns: coefficient reset at the borders
-        if (si < 0) { f = 0.0f; si = 0; }
-        if (si >= src - 1) { f = 0.0f; si = src - 1; }
-        s0 = si; s1 = min(si + 1, src - 1);
-    } else {                                             // rows: indices clamped, coefficients kept
-        s0 = min(max(si, 0), src - 1); s1 = min(max(si + 1, 0), src - 1);
-    }
-    c0 = (int)rintf((1.0f - f) * 2048.0f);
-    c1 = (int)rintf(f * 2048.0f);
-}
+// cv2.resize's fixed-point INTER_LINEAR for uint8: the coefficients and the vertical pass are stated once, in cf_cvresize.h
 __global__ void resize_u8_kernel(const uint8_t* src, uint8_t* dst, int B, int h, int w, int H, int W) {
     const long long n = (long long)B * H * W;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,8 +34,7 @@ __global__ void resize_u8_kernel(const uint8_t* src, uint8_t* dst, int B, int h,
     for (int c = 0; c < 3; ++c) {
         const int r0 = (int)p00[c] * a0 + (int)p01[c] * a1;
         const int r1 = (int)p10[c] * a0 + (int)p11[c] * a1;
-        const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-        d[c] = (uint8_t)min(max(v, 0), 255);
+        d[c] = (uint8_t)cv_linear_vpass(b0, b1, r0, r1);
     }
 }
 // ---- host images -> HBM by a kernel (zero-copy reads of page-locked host memory over PCIe) -------------------------------------

@@ -144,6 +144,26 @@ def shuffle_v2_block(x, sd, inp, oup, mid, ksize, stride, prefix="", dtype="fp32
     return y
 
 
+def yuv_to_bgr(frames, fmt="nv12", size=None, device=0):
+    """cv2.cvtColor(frame, cv2.COLOR_YUV2BGR_<fmt>) on the device (``cf_op_yuv_to_bgr``), followed by cv2.resize to ``size`` = (H, W)
+    when given and different: frames uint8 [B, h*3//2, w] or one [h*3//2, w] frame (OpenCV's single-buffer 4:2:0 layout);
+    fmt 'nv12', 'nv21', 'i420' ('yuv420p') or 'yv12'.  Returns uint8 [B, H, W, 3] (or [H, W, 3] for one frame)."""
+    x = np.ascontiguousarray(frames, dtype=np.uint8)
+    one = x.ndim == 2
+    if one:
+        x = x[None]
+    if x.ndim != 3:
+        raise ValueError("frames must be uint8 [B, h*3//2, w] or [h*3//2, w], got %s" % (x.shape,))
+    B, rows, w = x.shape
+    h = rows * 2 // 3
+    if h * 3 // 2 != rows:
+        raise ValueError("a 4:2:0 frame has h*3//2 rows for an even h; got %d rows" % rows)
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    out = np.empty((B, H, W, 3), np.uint8)
+    _lib.check(_lib.lib().cf_op_yuv_to_bgr(device, _lib.yuv_format(fmt), ptr(x), ptr(out), B, h, w, H, W), op=True)
+    return out[0] if one else out
+
+
 def ctdet_decode(heat, wh, reg=None, K=100, lm=None, device=0):
     """ctdet_decode (centerface_ext.py:52-82): (dets [B,K,6], lms [B,K,10]|None, inds [B,K] int64)."""
     heat, wh, reg, lm = f32(heat), f32(wh), f32(reg), f32(lm)

@@ -331,6 +331,39 @@ static inline int cf_ab_int(const char* name, int dflt) { return cf_env_int(name
 static inline int cf_ab_int(const char*, int dflt) { return dflt; }
 #endif
 
+// host: launch kernel KFN with `lds` bytes of dynamic LDS.  More than 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize raised first.
+// Function attributes are per kernel and per device, so what was set is remembered per kernel (= per instantiation of this template), device
+// and thread -- as a size, so that a kernel whose LDS size is a run-time value raises it again when a launch needs more.  A failed
+// attribute call is returned and not remembered.
+template <auto KFN, typename... A>
+static inline hipError_t launch_lds(dim3 grid, dim3 blk, size_t lds, hipStream_t s, const A&... args) {
+    if (lds > 64 * 1024) {
+        static thread_local size_t raised_dev[32] = {};
+        int dev = 0; (void)hipGetDevice(&dev);
+        size_t& raised = raised_dev[dev & 31];
+        if (raised < lds) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KFN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            raised = lds;
+        }
+    }
+    hipLaunchKernelGGL(KFN, grid, blk, lds, s, args...);
+    return hipGetLastError();
+}
+
+// host: the row of a kernel-variant table that serves a key: the row `match` accepts whose `var` is `want` (the family's A/B switch), else
+// the accepted default row (var 0), else nullptr
+template <typename E, size_t N, typename Match>
+static inline const E* pick_variant(const E (&table)[N], int want, Match&& match) {
+    const E* base = nullptr;
+    for (const E& e : table)
+        if (match(e)) {
+            if (e.var == want) return &e;
+            if (e.var == 0) base = &e;
+        }
+    return base;
+}
+
 // host-side fp32 -> bf16 (RNE), identical rounding to the device instruction for finite values
 static inline uint16_t host_f32_to_bf16(float f) {
     uint32_t u; __builtin_memcpy(&u, &f, 4);

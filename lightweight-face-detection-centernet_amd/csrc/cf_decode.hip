@@ -769,36 +769,24 @@ hipError_t launch_box_match(hipStream_t s, const OverlapParams& p) {
 
 // dynamic LDS of the sweep: removed / kept bitmaps and kept bases
 static size_t sweep_lds_bytes(int words) { return ((size_t)2 * words + (words + 1) / 2) * sizeof(unsigned long long); }
-static hipError_t sweep_configure() {                      // > 64 KB of dynamic LDS needs the function attribute, once per device
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    if (configured_dev[dev & 31]) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(thresh_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) configured_dev[dev & 31] = true;
-    return e;
-}
 
 hipError_t launch_nms_stages(hipStream_t s, const ThreshParams& p) {
     if (p.B <= 0) return hipSuccess;
     const int words = (p.cap + 63) >> 6;
-    { hipError_t e = sweep_configure(); if (e != hipSuccess) return e; }
     if (sweep_lds_bytes(words) > 160 * 1024) return hipErrorInvalidValue;   // > ~520 k candidates per image
     hipLaunchKernelGGL(thresh_rank_kernel, dim3((p.cap + 255) / 256, p.B), dim3(256), 0, s, p);
     hipLaunchKernelGGL(thresh_mask_kernel, dim3(128, p.B), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(thresh_sweep_kernel, dim3(p.B), dim3(64), sweep_lds_bytes(words), s, p);
-    return hipGetLastError();
+    return launch_lds<thresh_sweep_kernel>(dim3(p.B), dim3(64), sweep_lds_bytes(words), s, p);      // (> 64 KB of dynamic LDS: the function attribute)
 }
 
 hipError_t launch_decode_threshold(hipStream_t s, const ThreshParams& p) {
     if (p.B <= 0) return hipSuccess;
     const int words = (p.cap + 63) >> 6;
-    { hipError_t e = sweep_configure(); if (e != hipSuccess) return e; }
     if (sweep_lds_bytes(words) > 160 * 1024) return hipErrorInvalidValue;   // > ~520 k candidates per image
     hipLaunchKernelGGL(thresh_collect_kernel, dim3(p.B), dim3(1024), 0, s, p);
     hipLaunchKernelGGL(thresh_rank_kernel, dim3((p.cap + 255) / 256, p.B), dim3(256), 0, s, p);
     hipLaunchKernelGGL(thresh_mask_kernel, dim3(128, p.B), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(thresh_sweep_kernel, dim3(p.B), dim3(64), sweep_lds_bytes(words), s, p);
-    return hipGetLastError();
+    return launch_lds<thresh_sweep_kernel>(dim3(p.B), dim3(64), sweep_lds_bytes(words), s, p);      // (> 64 KB of dynamic LDS: the function attribute)
 }
 
 }  // namespace cf

@@ -329,14 +329,7 @@ __global__ __launch_bounds__(256) void dw_strip_kernel(DwParams p, DwLdsGeom g, 
 struct DwTileCfg { int th, tw; };
 template <typename T, int KS, int S, int TH, int TW>
 static hipError_t dw_strip_launch(hipStream_t s, const DwParams& p, const DwLdsGeom& g, int threads) {
-    auto kfn = dw_strip_kernel<T, KS, S, TH, TW>;
-    static thread_local bool big[64] = {};
     int dev = 0; (void)hipGetDevice(&dev);
-    if (!big[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        if (e != hipSuccess) return e;
-        big[dev & 63] = true;
-    }
     const int ntx = (p.Wo + TW - 1) / TW, nty = (p.Ho + TH - 1) / TH;
     const long long nt = (long long)p.B * g.nchunk * nty * ntx;
     if (nt > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -349,8 +342,7 @@ static hipError_t dw_strip_launch(hipStream_t s, const DwParams& p, const DwLdsG
     const int nwg = persist ? ncu * per_cu : (int)nt;
     set_kernel_tag("void cf::dw_strip_kernel<%s, %d, %d, %d, %d>(cf::DwParams, cf::DwLdsGeom, int, int, int)", type_tag<T>(), KS, S, TH, TW);
     DwLdsGeom gs = g; dw_set_step(gs, threads);
-    hipLaunchKernelGGL(kfn, dim3(nwg), dim3(threads), (persist ? 2 : 1) * g.lds_bytes, s, p, gs, ntx, nty, (int)nt);
-    return hipGetLastError();
+    return launch_lds<dw_strip_kernel<T, KS, S, TH, TW>>(dim3(nwg), dim3(threads), (persist ? 2 : 1) * g.lds_bytes, s, p, gs, ntx, nty, (int)nt);
 }
 
 // geometry of one candidate tile: the largest channel chunk (a divisor of C, whole 16-byte groups) whose tile + tap weights fit `cap`

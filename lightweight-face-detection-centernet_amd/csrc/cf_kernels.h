@@ -65,12 +65,32 @@ void dw_pack_weights(const float* w /*[C][1][k][k]*/, int C, int k, float* out_h
 hipError_t launch_dw(hipStream_t s, int dtype, const DwParams& p);
 
 // ------------------------------------------------------------------ fused MBConv block
+// The kernel families.  The values are kernel arguments (MbParams::kind) and appear in tool output: they never change (3 is unused).
+// A family = one row of kMbFamilies (cf_mbconv.hip: how it packs and launches) + its place in mb_geometry / expdw_geometry (when it is
+// chosen) + an answer to each predicate below.
+enum MbKind : int {
+    MB_TILE = 0,          // cf_mbconv.hip: E tile in LDS as bf16 / fp32, every dtype
+    MB_PX = 1,            // cf_mbconv2.hip: fp16 pixel-pair tile, bf16 storage only
+    XD_PX = 2,            // cf_mbconv2.hip: expand + depthwise only (project stays a GEMM launch), bf16
+    XD_MX = 4,            // cf_mbconv3.hip: expand + depthwise on the matrix cores, stride 1, bf16
+    MB_MX = 5,            // cf_mbconv3.hip: fully fused block, matrix-core depthwise, stride 1, bf16
+    MB_MX2 = 6,           // cf_mbconv3.hip: the same for the stride-2 blocks
+    MB_F32 = 7,           // cf_mbconv4.hip: the fp32-storage modes' fused block, second generation
+    XD_F32 = 8,           // cf_mbconv5.hip: expand + depthwise for the fp32-storage modes
+    MB_SP = 9,            // cf_mbconv6.hip: the split mode's fused block for Cout <= 32
+    MB_SP_DIRECT = 10,    // experiments/cf_mbconv7.hip (experiments build only)
+};
+// can the family write its block output in pixel-block order (MbParams::yblock)?  The bf16 fused kernels, and cf_mbconv.hip's fp32-tile
+// kernel (layer3.1 in the split mode)
+inline bool mb_writes_blocked(MbKind kind, int dtype) {
+    return kind == MB_PX || kind == MB_MX || kind == MB_MX2 || (kind == MB_TILE && dtype != 1);
+}
 struct MbGeom {
     bool ok;              // false: this block shape is not supported by the fused kernel
     int HC, nq;           // hidden-channel chunk and number of chunks (hid = HC * nq)
     int NBE, JX, HALF, NBO, rowb;
     size_t lds_bytes, wexp_bytes, wdw_floats, wproj_bytes;
-    int kind, S;          // kind 0: cf_mbconv.hip, 1: cf_mbconv2.hip (fp16 pixel-pair tile, bf16 storage only)
+    MbKind kind; int S;   // kind: the kernel family that serves the block (MbKind above)
     int KG;               // k-groups of the project loop (fp32 / split kernels: the wave groups that split a hidden chunk's k-steps);
                           // the split mode packs the project fragments in pairs per k-group (split_pairs_inplace)
 };
@@ -87,63 +107,32 @@ struct MbParams {
     int HC, nq, NBE, JX, HALF, rowb;
     size_t lds_bytes;
     int nw;               // mbconv_px_kernel: 1 = XCD-aware tile order (set by the launcher)
-    int kind;             // MbGeom::kind
+    MbKind kind;          // MbGeom::kind
     int yblock;           // y (expdw: the depthwise tensor; mbconv_px: the block output) in pixel-block order
                           // [m / 32][C / 8][m % 32][8], m = linear pixel index over the batch (PwParams::xblock)
     int xblock;           // expdw_px_kernel: x in pixel-block order
     void* dbg;            // -DCF_X5_TIMING builds only: per-wave phase cycle sums (tools/x5_timing.py); nullptr otherwise
 };
 hipError_t launch_mbconv(hipStream_t s, int dtype, const MbParams& p);
-// cf_mbconv2.hip
-bool mb2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s);
-void mb2_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
-                      void* wexp_host, float* wdw_host, void* wproj_host);
-hipError_t mb2_launch(hipStream_t s, const MbParams& p);
-// expand + depthwise only (MbGeom::kind == 2): y = depthwise output [B][Hout][Wout][hid]; packs with mb_pack_weights(wproj = nullptr)
+// the MbParams fields that come from the geometry
+inline void mb_fill(MbParams& p, const MbGeom& g) {
+    p.HC = g.HC; p.nq = g.nq; p.NBE = g.NBE; p.JX = g.JX; p.HALF = g.HALF; p.rowb = g.rowb; p.lds_bytes = g.lds_bytes; p.kind = g.kind;
+}
+// expand + depthwise only (XD_PX [2], XD_MX [4], XD_F32 [8]): y = depthwise output [B][Hout][Wout][hid]; packs with mb_pack_weights(wproj = nullptr)
 MbGeom expdw_geometry(int dtype, int Cin, int hid, int k, int s);
-hipError_t expdw_launch(hipStream_t s, const MbParams& p);
-
-// cf_mbconv4.hip: the fp32 parity mode's fused block, second generation (MbGeom::kind = 7): wave = 64 pixels, SGPR taps, permlane32
-// swap into the project MFMA; expand fragments as cf_mbconv.hip, taps and project fragments repacked by mb4_repack
-bool mb4_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s);
-void mb4_repack(int dtype, const MbGeom& g, int hid, int Cout, int k, const float* wd, const float* wp, float* wdw_host, void* wproj_host);
-hipError_t mb4_launch(hipStream_t s, int dtype, const MbParams& p);
-
-// cf_mbconv5.hip: expand + depthwise for the fp32-storage modes (MbGeom::kind = 8, split-bf16 tolerance mode): register-window
+// What one family's translation unit calls of another's (everything else of a family is reached through kMbFamilies and mb_geometry,
+// cf_mbconv.hip, and declared there):
+// cf_mbconv3.hip: depthwise on the matrix cores (v_mfma_f32_4x4x4_16b_f16, Toeplitz operands), stride 1, bf16 storage.
+// XD_MX [4] = expand + depthwise (project stays a GEMM launch)
+MbGeom expdw_mx_geometry(int dtype, int Cin, int hid, int k, int s);
+// cf_mbconv5.hip: expand + depthwise for the fp32-storage modes (XD_F32 [8], split-bf16 tolerance mode): register-window
 // depthwise on an x-quad-cell tile, packed taps; y = depthwise output in NHWC or pixel-block order; MbGeom::HALF = hidden chunks
 // per workgroup.  Expand fragments as cf_mbconv.hip, taps [chunk][group of 4 channels][tap][4] (mb_pack_weights)
 MbGeom expdw_f32_geometry(int dtype, int Cin, int hid, int k, int s);
-hipError_t expdw_f32_launch(hipStream_t s, int dtype, const MbParams& p);
-
-// cf_mbconv6.hip: the split mode's fused block for Cout <= 32 (MbGeom::kind = 9): cf_mbconv5.hip's register-window depthwise + project
-// MFMAs from an LDS tile of the depthwise output
-bool mb6_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s);
-void mb6_pack(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+// cf_mbconv6.hip: the split mode's fused block for Cout <= 32 (MB_SP [9]): cf_mbconv5.hip's register-window depthwise + project
+// MFMAs from an LDS tile of the depthwise output (experiments/cf_mbconv7.hip packs its expand fragments and taps with it)
+void mb6_pack(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
               void* wexp_host, float* wdw_host, void* wproj_host);
-hipError_t mb6_launch(hipStream_t s, const MbParams& p);
-
-// experiments/cf_mbconv7.hip (experiments build only): as cf_mbconv6.hip, the depthwise feeding the project MFMAs directly (MbGeom::kind = 10; experiments switch CF_M7)
-bool mb7_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s);
-void mb7_pack(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
-              void* wexp_host, float* wdw_host, void* wproj_host);
-hipError_t mb7_launch(hipStream_t s, const MbParams& p);
-
-// cf_mbconv3.hip: depthwise on the matrix cores (v_mfma_f32_4x4x4_16b_f16, Toeplitz operands), stride 1, bf16 storage.
-// MbGeom::kind 4 = expand + depthwise (project stays a GEMM launch)
-MbGeom expdw_mx_geometry(int dtype, int Cin, int hid, int k, int s);
-void mx_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
-                     void* wexp_host, float* wdw_host, void* wproj_host);
-hipError_t mx_launch(hipStream_t s, const MbParams& p);
-// MbGeom::kind 5 = fully fused block (expand -> matrix-core depthwise -> project (+residual)), MbGeom::HALF = 1: last round of 16
-bool mx_fused_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s);
-void mx_fused_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
-                           void* wexp_host, float* wdw_host, void* wproj_host);
-hipError_t mx_fused_launch(hipStream_t s, const MbParams& p);
-// MbGeom::kind 6 = the same for the stride-2 blocks (two sets per tile, waves = (set, channel half))
-bool mx_fused2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s);
-void mx_fused2_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
-                            void* wexp_host, float* wdw_host, void* wproj_host);
-hipError_t mx_fused2_launch(hipStream_t s, const MbParams& p);
 
 // ------------------------------------------------------------------ stem 3x3 s2 3->32 + Swish
 struct StemParams {
@@ -167,14 +156,20 @@ struct Stem0Params {
     const void* wproj;    // stem0_pack_proj
     void* y;              // [B][H/2][W/2][16] T
     int B, H, W;
-    int kind;             // 0: stem0_kernel; 1: stem0_px_kernel (bf16 storage; weights from stem0px_pack)
+    int kind;             // 0: stem0_kernel; else a set of the bits below
+};
+// bits of Stem0Params::kind (kernel argument: the values never change)
+enum : int {
+    STEM0_PX = 1,         // stem0_px_kernel (bf16 storage; weights from stem0px_pack)
+    STEM0_XCD = 2,        // XCD-aware tile order
+    STEM0_MX = 4,         // depthwise on the matrix cores (weights from stem0mx_pack)
 };
 size_t stem0px_wstem_bytes();
 size_t stem0px_wdw_dwords();
 void stem0px_pack(const float* ws /*[32][3][3][3]*/, const float* wd /*[32][9]*/, const float* wp /*[16][32]*/,
                   void* wstem_out, uint32_t* wdw_out, void* wproj_out);
 size_t stem0mx_wdw_dwords();
-void stem0mx_pack(const float* ws, const float* wd, const float* wp, void* wstem_out, uint32_t* wdw_out, void* wproj_out);     // Stem0Params::kind bit 2
+void stem0mx_pack(const float* ws, const float* wd, const float* wp, void* wstem_out, uint32_t* wdw_out, void* wproj_out);     // STEM0_MX
 void stem0_lut(float* lut /*[3][256]*/);
 size_t stem0_proj_bytes(int dtype);
 void stem0_pack_proj(int dtype, const float* wp /*[16][32]*/, void* out_host);

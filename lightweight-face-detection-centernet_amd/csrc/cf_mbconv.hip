@@ -43,33 +43,8 @@ template <typename T> using MbMma = CfMma<T>;
 
 // ---------------------------------------------------------------- host: packing (geometry: mb_geometry below the kernel table)
 // we [hid][Cin], wd [hid][k*k], wp [Cout][hid]
-void mb_pack_weights(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we,
-                     const float* wd, const float* wp, void* wexp_host, float* wdw_host, void* wproj_host) {
-    if (g.kind == 1 || g.kind == 2) { mb2_pack_weights(g, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, wproj_host); return; }
-    if (g.kind == 4) { mx_pack_weights(g, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, wproj_host); return; }
-    if (g.kind == 5) { mx_fused_pack_weights(g, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, wproj_host); return; }
-    if (g.kind == 6) { mx_fused2_pack_weights(g, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, wproj_host); return; }
-#include CF_EXP_INC(cf_mbconv_m7_pack)
-    if (g.kind == 9) { mb6_pack(g, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, wproj_host); return; }
-    if (g.kind == 8) {                       // cf_mbconv5.hip: this file's expand fragments, taps as [chunk][group of 4 channels][tap][4]
-        MbGeom g0 = g; g0.kind = 0; g0.NBO = 0; g0.HALF = 0; g0.wproj_bytes = 0;
-        std::vector<float> generic(g.wdw_floats);
-        mb_pack_weights(dtype, g0, Cin, hid, Cout, k, we, wd, nullptr, wexp_host, generic.data(), nullptr);
-        for (int q = 0; q < g.nq; ++q)
-            for (int grp = 0; grp < g.HC / 4; ++grp)
-                for (int t = 0; t < k * k; ++t)
-                    for (int c = 0; c < 4; ++c)
-                        wdw_host[(((size_t)q * (g.HC / 4) + grp) * k * k + t) * 4 + c] = wd[(size_t)(q * g.HC + grp * 4 + c) * k * k + t];
-        return;
-    }
-    if (g.kind == 7) {                       // cf_mbconv4.hip: this file's expand fragments, its own tap table and project fragments
-        MbGeom g0 = g; g0.kind = 0;
-        mb_pack_weights(dtype, g0, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, wproj_host);      // (its project fragments are overwritten)
-        std::vector<float> wp7;
-        if (dtype == 2) { wp7.assign(wp, wp + (size_t)Cout * hid); for (float& v : wp7) v *= kCfNegLn2; wp = wp7.data(); }   // as the recursive call did for its own copy
-        mb4_repack(dtype, g, hid, Cout, k, wd, wp, wdw_host, wproj_host);
-        return;
-    }
+static void mb_tile_pack(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we,
+                         const float* wd, const float* wp, void* wexp_host, float* wdw_host, void* wproj_host) {
     // split mode: -log2(e) folded into the expand weights, the leftover -ln 2 into the project weights (swish2_sel<true>, cf_common.h);
     // the depthwise taps stay as they are (their input and their output both carry the -log2(e) factor)
     std::vector<float> we_s, wp_s;
@@ -396,21 +371,10 @@ struct MbEntry {
 
 template <typename T, int KS, int S, int NBO, bool RESID, int NW, int JX, int HC, int TOH, int TOW, bool EF>
 static hipError_t mb_launch(hipStream_t s, const MbParams& p) {
-    auto kfn = mbconv_kernel<T, KS, S, NBO, RESID, NW, JX, HC, TOH, TOW, EF>;
-    // function attributes are per device: remember what was set for each
-    static thread_local size_t configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    size_t& configured = configured_dev[dev & 31];
-    if (p.lds_bytes > 64 * 1024 && configured < p.lds_bytes) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-        if (e != hipSuccess) return e;
-        configured = p.lds_bytes;
-    }
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(NW * 64);
     set_kernel_tag("void cf::mbconv_kernel<%s, %d, %d, %d, %s, %d, %d, %d, %d, %d, %s>(cf::MbParams)", type_tag<T>(), KS, S, NBO,
                    RESID ? "true" : "false", NW, JX, HC, TOH, TOW, EF ? "true" : "false");
-    hipLaunchKernelGGL(kfn, grid, blk, p.lds_bytes, s, p);
-    return hipGetLastError();
+    return launch_lds<mbconv_kernel<T, KS, S, NBO, RESID, NW, JX, HC, TOH, TOW, EF>>(grid, blk, p.lds_bytes, s, p);
 }
 
 template <typename T, int KS, int S, int JX, int HC, int TOH, int TOW, bool EF, int NBO, int NW>
@@ -467,14 +431,30 @@ static const MbEntry kMbTable[] = {
 
 static const MbEntry* mb_find(int dtype, int k, int s, int jx, int nbo, int res) {
     static const int want = cf_ab_int("CF_MB_VARIANT", 0);
-    const MbEntry* base = nullptr;
-    for (const MbEntry& e : kMbTable)
-        if (e.dtype == dtype && e.k == k && e.s == s && e.jx == jx && e.nbo == nbo && e.res == res) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kMbTable, want, [&](const MbEntry& e) { return e.dtype == dtype && e.k == k && e.s == s && e.jx == jx && e.nbo == nbo && e.res == res; });
 }
+
+// ---------------------------------------------------------------- the families
+// What the other families' translation units give this one: when a family serves a block (geometry), how it packs, how it launches.
+// cf_mbconv2.hip: fp16 pixel-pair tile, bf16 storage only: MB_PX [1], and its expand + depthwise kernel XD_PX [2] (geometry: expdw_geometry)
+bool mb2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s);
+// cf_mbconv3.hip: MB_MX [5] = fully fused block (expand -> matrix-core depthwise -> project (+residual)), MbGeom::HALF = 1: last round of 16
+bool mx_fused_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s);
+// MB_MX2 [6] = the same for the stride-2 blocks (two sets per tile, waves = (set, channel half))
+bool mx_fused2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s);
+// cf_mbconv4.hip: the fp32 parity mode's fused block, second generation (MB_F32 [7]): wave = 64 pixels, SGPR taps, permlane32
+// swap into the project MFMA; expand fragments as this file's, taps and project fragments repacked by mb4_repack
+bool mb4_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s);
+void mb4_repack(int dtype, const MbGeom& g, int hid, int Cout, int k, const float* wd, const float* wp, float* wdw_host, void* wproj_host);
+// cf_mbconv6.hip: MB_SP [9]
+bool mb6_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s);
+// experiments/cf_mbconv7.hip (experiments build only): as cf_mbconv6.hip, the depthwise feeding the project MFMAs directly (MB_SP_DIRECT [10]; experiments switch CF_M7)
+bool mb7_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s);
+typedef void MbPackFn(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+                      void* wexp_host, float* wdw_host, void* wproj_host);
+typedef hipError_t MbLaunchFn(hipStream_t s, int dtype, const MbParams& p);
+MbPackFn mb2_pack_weights, mx_pack_weights, mx_fused_pack_weights, mx_fused2_pack_weights, mb7_pack;      // (mb6_pack: cf_kernels.h)
+MbLaunchFn mb2_launch, expdw_launch, mx_launch, mx_fused_launch, mx_fused2_launch, mb4_launch, expdw_f32_launch, mb6_launch, mb7_launch;
 
 MbGeom mb_geometry(int dtype, int Cin, int hid, int Cout, int k, int s) {
     MbGeom g{};
@@ -503,20 +483,64 @@ MbGeom mb_geometry(int dtype, int Cin, int hid, int Cout, int k, int s) {
     return g;
 }
 
-hipError_t launch_mbconv(hipStream_t s, int dtype, const MbParams& p) {
-    if (p.B <= 0) return hipSuccess;
-    if (p.kind == 1) return dtype == 1 ? mb2_launch(s, p) : hipErrorInvalidValue;
-    if (p.kind == 2) return dtype == 1 ? expdw_launch(s, p) : hipErrorInvalidValue;
-    if (p.kind == 4) return dtype == 1 ? mx_launch(s, p) : hipErrorInvalidValue;
-    if (p.kind == 5) return dtype == 1 ? mx_fused_launch(s, p) : hipErrorInvalidValue;
-    if (p.kind == 6) return dtype == 1 ? mx_fused2_launch(s, p) : hipErrorInvalidValue;
-    if (p.kind == 7) return dtype != 1 ? mb4_launch(s, dtype, p) : hipErrorInvalidValue;
-    if (p.kind == 8) return expdw_f32_launch(s, dtype, p);
-    if (p.kind == 9) return dtype == 2 ? mb6_launch(s, p) : hipErrorInvalidValue;
-#include CF_EXP_INC(cf_mbconv_m7_launch)
+static hipError_t mb_tile_launch(hipStream_t s, int dtype, const MbParams& p) {
     const MbEntry* e = mb_find(dtype, p.k, p.s, p.JX, (p.Cout + 31) / 32, p.residual ? 1 : 0);
     if (!e || e->hc != p.HC) return hipErrorInvalidValue;
     return e->fn(s, p);
+}
+
+// cf_mbconv4.hip: this file's expand fragments, its own tap table and project fragments
+static void mb_f32_pack(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+                        void* wexp_host, float* wdw_host, void* wproj_host) {
+    mb_tile_pack(dtype, g, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, wproj_host);      // (its project fragments are overwritten)
+    std::vector<float> wp7;
+    if (dtype == 2) { wp7.assign(wp, wp + (size_t)Cout * hid); for (float& v : wp7) v *= kCfNegLn2; wp = wp7.data(); }   // as mb_tile_pack did for its own copy
+    mb4_repack(dtype, g, hid, Cout, k, wd, wp, wdw_host, wproj_host);
+}
+// cf_mbconv5.hip: this file's expand fragments, taps as [chunk][group of 4 channels][tap][4]
+static void xd_f32_pack(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float*,
+                        void* wexp_host, float* wdw_host, void*) {
+    MbGeom g0 = g; g0.NBO = 0; g0.HALF = 0; g0.wproj_bytes = 0;
+    std::vector<float> generic(g.wdw_floats);
+    mb_tile_pack(dtype, g0, Cin, hid, Cout, k, we, wd, nullptr, wexp_host, generic.data(), nullptr);
+    for (int q = 0; q < g.nq; ++q)
+        for (int grp = 0; grp < g.HC / 4; ++grp)
+            for (int t = 0; t < k * k; ++t)
+                for (int c = 0; c < 4; ++c)
+                    wdw_host[(((size_t)q * (g.HC / 4) + grp) * k * k + t) * 4 + c] = wd[(size_t)(q * g.HC + grp * 4 + c) * k * k + t];
+}
+
+// One row per family: the storage types it serves (launch_mbconv refuses the others), its weight packer, its launcher.  WHEN a family
+// serves a block is decided by mb_geometry / expdw_geometry.
+enum : unsigned { DT_F32 = 1u << 0, DT_BF16 = 1u << 1, DT_SPLIT = 1u << 2 };      // bit = 1 << dtype
+struct MbFamily { MbKind kind; unsigned dtypes; MbPackFn* pack; MbLaunchFn* launch; };
+static const MbFamily kMbFamilies[] = {
+    {MB_TILE, DT_F32 | DT_BF16 | DT_SPLIT, mb_tile_pack, mb_tile_launch},
+    {MB_PX, DT_BF16, mb2_pack_weights, mb2_launch},
+    {XD_PX, DT_BF16, mb2_pack_weights, expdw_launch},
+    {XD_MX, DT_BF16, mx_pack_weights, mx_launch},
+    {MB_MX, DT_BF16, mx_fused_pack_weights, mx_fused_launch},
+    {MB_MX2, DT_BF16, mx_fused2_pack_weights, mx_fused2_launch},
+    {MB_F32, DT_F32 | DT_SPLIT, mb_f32_pack, mb4_launch},
+    {XD_F32, DT_F32 | DT_SPLIT, xd_f32_pack, expdw_f32_launch},
+    {MB_SP, DT_SPLIT, mb6_pack, mb6_launch},
+#include CF_EXP_INC(cf_mbconv_m7_family)
+};
+static const MbFamily* mb_family(MbKind kind) {
+    for (const MbFamily& f : kMbFamilies) if (f.kind == kind) return &f;
+    return nullptr;
+}
+
+void mb_pack_weights(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we,
+                     const float* wd, const float* wp, void* wexp_host, float* wdw_host, void* wproj_host) {
+    if (const MbFamily* f = mb_family(g.kind)) f->pack(dtype, g, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, wproj_host);
+}
+
+hipError_t launch_mbconv(hipStream_t s, int dtype, const MbParams& p) {
+    if (p.B <= 0) return hipSuccess;
+    const MbFamily* f = mb_family(p.kind);
+    if (!f || (unsigned)dtype > 2u || !(f->dtypes & (1u << dtype))) return hipErrorInvalidValue;
+    return f->launch(s, dtype, p);
 }
 
 }  // namespace cf

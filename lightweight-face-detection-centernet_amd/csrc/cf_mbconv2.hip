@@ -650,19 +650,9 @@ struct XdEntry {
 template <int KS, int S, int JX, int HC, int TOH, int TOW>
 static hipError_t xd_launch_t(hipStream_t s, const MbParams& p) {
     typedef Xd<KS, S, HC, TOH, TOW, JX> G;
-    auto kfn = expdw_px_kernel<KS, S, JX, HC, TOH, TOW>;
-    static thread_local bool configured_dev[32] = {};               // function attributes are per device
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid(((p.Wout + TOW - 1) / TOW) * ((p.Hout + TOH - 1) / TOH), p.hid / HC, p.B), blk(G::NW * 64);
     set_kernel_tag("void cf::expdw_px_kernel<%d, %d, %d, %d, %d, %d>(cf::MbParams)", KS, S, JX, HC, TOH, TOW);
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<expdw_px_kernel<KS, S, JX, HC, TOH, TOW>>(grid, blk, G::LDS, s, p);
 }
 #define XD(V, KS, S, JX, HC, TOH, TOW)                                                                             \
     {KS, S, JX, HC, TOH, TOW, V, Xd<KS, S, HC, TOH, TOW, JX>::LDS, Xd<KS, S, HC, TOH, TOW, JX>::NT, Xd<KS, S, HC, TOH, TOW, JX>::NPARW, \
@@ -679,18 +669,12 @@ static const XdEntry kXdTable[] = {
 #undef XD
 static const XdEntry* xd_find(int k, int s, int jx) {
     static const int want = cf_ab_int("CF_XD_VARIANT", 0);
-    const XdEntry* base = nullptr;
-    for (const XdEntry& e : kXdTable)
-        if (e.k == k && e.s == s && e.jx == jx) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kXdTable, want, [&](const XdEntry& e) { return e.k == k && e.s == s && e.jx == jx; });
 }
 
-// geometry of the expand+depthwise kernel for a block (bf16 storage): MbGeom with kind = 2
+// geometry of the expand+depthwise kernel for a block (bf16 storage): MbGeom with kind = XD_PX [2]
 MbGeom expdw_geometry(int dtype, int Cin, int hid, int k, int s) {
-    if (dtype != 1) return expdw_f32_geometry(dtype, Cin, hid, k, s);   // fp32 storage: cf_mbconv5.hip (kind 8)
+    if (dtype != 1) return expdw_f32_geometry(dtype, Cin, hid, k, s);   // fp32 storage: cf_mbconv5.hip (XD_F32 [8])
     MbGeom g = expdw_mx_geometry(dtype, Cin, hid, k, s);          // stride 1: depthwise on the matrix cores (cf_mbconv3.hip)
     if (g.ok) return g;
     static const bool off = cf_ab_int("CF_XD_KIND", 1) == 0;
@@ -698,7 +682,7 @@ MbGeom expdw_geometry(int dtype, int Cin, int hid, int k, int s) {
     const int jx = (Cin * 2 / 16 + 1) / 2;
     const XdEntry* e = xd_find(k, s, jx);
     if (!e || hid % e->hc) return g;
-    g.ok = true; g.kind = 2; g.S = s;
+    g.ok = true; g.kind = XD_PX; g.S = s;
     g.JX = jx; g.NBO = 0; g.HC = e->hc; g.nq = hid / e->hc; g.NBE = e->hc / 32; g.HALF = 0;
     g.rowb = e->hc * 4 + 16;
     g.lds_bytes = (size_t)e->lds_bytes;
@@ -707,7 +691,7 @@ MbGeom expdw_geometry(int dtype, int Cin, int hid, int k, int s) {
     g.wproj_bytes = 0;
     return g;
 }
-hipError_t expdw_launch(hipStream_t s, const MbParams& p) {
+hipError_t expdw_launch(hipStream_t s, int, const MbParams& p) {
     const XdEntry* e = xd_find(p.k, p.s, p.JX);
     if (!e || e->hc != p.HC) return hipErrorInvalidValue;
     return e->fn(s, p);
@@ -723,16 +707,7 @@ struct Mb2Entry {
 #endif  // !CF_ILP_TU
 template <int KS, int S, int NBO, bool RESID, int NW, int JX, int HC, int TOH, int TOW>
 hipError_t mb2_launch_t(hipStream_t s, const MbParams& p) {
-    auto kfn = mbconv_px_kernel<KS, S, NBO, RESID, NW, JX, HC, TOH, TOW>;
     constexpr int LDS = Px<KS, S, HC, TOH, TOW, JX, NW>::LDS;
-    static thread_local bool configured_dev[32] = {};               // function attributes are per device
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(NW * 64);
     // XCD-aware tile order: measured neutral-to-slower on these VALU-bound kernels (layer1.0 0.234 -> 0.237-0.244 ms; their
     // PMC traffic is already 1.0-1.13x algorithmic), so it stays off here (CF_MB2_XCD=1 switches it on in an experiments build);
@@ -740,8 +715,7 @@ hipError_t mb2_launch_t(hipStream_t s, const MbParams& p) {
     static const bool xcd_on = cf_ab_int("CF_MB2_XCD", 0) == 1;
     MbParams q = p; q.nw = xcd_on ? 1 : 0;
     set_kernel_tag("void cf::mbconv_px_kernel<%d, %d, %d, %s, %d, %d, %d, %d, %d>(cf::MbParams)", KS, S, NBO, RESID ? "true" : "false", NW, JX, HC, TOH, TOW);
-    hipLaunchKernelGGL(kfn, grid, blk, LDS, s, q);
-    return hipGetLastError();
+    return launch_lds<mbconv_px_kernel<KS, S, NBO, RESID, NW, JX, HC, TOH, TOW>>(grid, blk, LDS, s, q);
 }
 
 // Two instances are compiled in their own translation unit (cf_mbconv2_ilp.hip = this file with CF_ILP_TU defined) under
@@ -782,13 +756,7 @@ static const Mb2Entry kMb2Table[] = {
 
 static const Mb2Entry* mb2_find(int k, int s, int jx, int nbo, int res) {
     static const int want = cf_ab_int("CF_MB2_VARIANT", 0);
-    const Mb2Entry* base = nullptr;
-    for (const Mb2Entry& e : kMb2Table)
-        if (e.k == k && e.s == s && e.jx == jx && e.nbo == nbo && e.res == res) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kMb2Table, want, [&](const Mb2Entry& e) { return e.k == k && e.s == s && e.jx == jx && e.nbo == nbo && e.res == res; });
 }
 
 bool mb2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
@@ -797,7 +765,7 @@ bool mb2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
     const int jx = (Cin * 2 / 16 + 1) / 2, nbo = (Cout + 31) / 32;
     const Mb2Entry* e = mb2_find(k, s, jx, nbo, (Cin == Cout && s == 1) ? 1 : 0);
     if (!e || hid % e->hc) return false;
-    g.ok = true; g.kind = 1; g.S = s;
+    g.ok = true; g.kind = MB_PX; g.S = s;
     g.JX = jx; g.NBO = nbo; g.HC = e->hc; g.nq = hid / e->hc; g.NBE = e->nbe; g.HALF = e->half;
     g.rowb = e->hc * 4 + 16;
     g.lds_bytes = (size_t)e->lds_bytes;
@@ -808,7 +776,7 @@ bool mb2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
 }
 
 // we [hid][Cin], wd [hid][k*k], wp [Cout][hid]
-void mb2_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+void mb2_pack_weights(int, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
                       void* wexp_host, float* wdw_host, void* wproj_host) {
     const int NCx = Cin * 2 / 16, NT = (k + 1) / 2, NPARW = g.S == 1 ? 2 : 1;
     __builtin_memset(wexp_host, 0, g.wexp_bytes);
@@ -816,8 +784,8 @@ void mb2_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const 
     uint32_t* wt = reinterpret_cast<uint32_t*>(wdw_host);
     for (int q = 0; q < g.nq; ++q) {
         // expand, MFMA B operand: lane (n = channel, half h) holds Cin chunk h*JX + j of hidden channel q*HC + nbl*32 + n;
-        // a trailing 16-channel half block (kind 1 only) is one 16x16x32 fragment: lane (n = channel, kg = Cin chunk)
-        const bool part = g.kind == 1 && (g.HC % 32 == 16);
+        // a trailing 16-channel half block (MB_PX [1] only) is one 16x16x32 fragment: lane (n = channel, kg = Cin chunk)
+        const bool part = g.kind == MB_PX && (g.HC % 32 == 16);
         const int nbf = part ? g.HC / 32 : g.NBE;
         const size_t wxb = ((size_t)nbf * g.JX + (part ? 1 : 0)) * 1024;
         for (int nbl = 0; nbl < nbf; ++nbl)
@@ -862,7 +830,7 @@ void mb2_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const 
     }
 }
 
-hipError_t mb2_launch(hipStream_t s, const MbParams& p) {
+hipError_t mb2_launch(hipStream_t s, int, const MbParams& p) {
     const Mb2Entry* e = mb2_find(p.k, p.s, p.JX, (p.Cout + 31) / 32, p.residual ? 1 : 0);
     if (!e || e->hc != p.HC) return hipErrorInvalidValue;
     return e->fn(s, p);

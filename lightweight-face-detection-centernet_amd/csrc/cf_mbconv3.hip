@@ -794,21 +794,11 @@ struct MxEntry {
 template <int KS, int JX, int TOH, int TOW, int NW, bool ALDS>
 static hipError_t xmx_launch_t(hipStream_t s, const MbParams& p) {
     typedef Mx<KS, JX, TOH, TOW, NW, ALDS> G;
-    auto kfn = expdw_mx_kernel<KS, JX, TOH, TOW, NW, ALDS>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid(((p.Wout + TOW - 1) / TOW) * ((p.Hout + TOH - 1) / TOH), p.hid / 32, p.B), blk(NW * 64);
     set_kernel_tag("void cf::expdw_mx_kernel<%d, %d, %d, %d, %d, %s>(cf::MbParams)", KS, JX, TOH, TOW, NW, ALDS ? "true" : "false");
     static const int abl = cf_ab_int("CF_MX_ABL", 0);      // timing experiments only: results invalid
     MbParams q = p; q.nw = abl;
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, q);
-    return hipGetLastError();
+    return launch_lds<expdw_mx_kernel<KS, JX, TOH, TOW, NW, ALDS>>(grid, blk, G::LDS, s, q);
 }
 #include CF_EXP_INC(cf_mbconv3_2)
 #include CF_EXP_INC(cf_mbconv3_3)
@@ -828,16 +818,10 @@ static const MxEntry kXmxTable[] = {
 #undef XMR
 static const MxEntry* xmx_find(int k, int jx) {
     static const int want = cf_ab_int("CF_MX_VARIANT", 0);
-    const MxEntry* base = nullptr;
-    for (const MxEntry& e : kXmxTable)
-        if (e.k == k && e.jx == jx) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kXmxTable, want, [&](const MxEntry& e) { return e.k == k && e.jx == jx; });
 }
 
-// geometry of the matrix-core expand+depthwise kernel (MbGeom::kind = 4); stride 1 only
+// geometry of the matrix-core expand+depthwise kernel (XD_MX [4]); stride 1 only
 MbGeom expdw_mx_geometry(int dtype, int Cin, int hid, int k, int s) {
     MbGeom g{};
     static const bool off = cf_env_int("CF_DW_MATRIX", 1) == 0 || cf_ab_int("CF_MX", 1) == 0;      // product switch: the v_dot2c family instead
@@ -845,7 +829,7 @@ MbGeom expdw_mx_geometry(int dtype, int Cin, int hid, int k, int s) {
     const int jx = (Cin * 2 / 16 + 1) / 2;
     const MxEntry* e = xmx_find(k, jx);
     if (!e) return g;
-    g.ok = true; g.kind = 4; g.S = 1;
+    g.ok = true; g.kind = XD_MX; g.S = 1;
     g.JX = jx; g.NBO = 0; g.HC = 32; g.nq = hid / 32; g.NBE = 1; g.HALF = 0;
     g.rowb = 32 * 8 + 16;
     g.lds_bytes = (size_t)e->lds_bytes;
@@ -877,7 +861,7 @@ void mx_pack_taps(int nq, int k, const float* wd /*[hid][k*k]*/, uint32_t* out, 
 }
 
 // we [hid][Cin], wd [hid][k*k]; expand fragments as cf_mbconv2.hip (MFMA B operand: lane (n = channel, half) holds Cin chunk)
-void mx_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+void mx_pack_weights(int, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
                      void* wexp_host, float* wdw_host, void* wproj_host) {
     (void)hid; (void)Cout; (void)wp; (void)wproj_host;
     const int NCx = Cin * 2 / 16;
@@ -893,14 +877,14 @@ void mx_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const f
     mx_pack_taps(g.nq, k, wd, reinterpret_cast<uint32_t*>(wdw_host));
 }
 
-hipError_t mx_launch(hipStream_t s, const MbParams& p) {
+hipError_t mx_launch(hipStream_t s, int, const MbParams& p) {
     const MxEntry* e = xmx_find(p.k, p.JX);
     if (!e || p.s != 1) return hipErrorInvalidValue;
     return e->fn(s, p);
 }
 
 
-// ---------------------------------------------------------------- fused block, host side (MbGeom::kind = 5)
+// ---------------------------------------------------------------- fused block, host side (MB_MX [5])
 #endif  // !CF_ILP_TU
 struct FxEntry {
     int k, jx, nmb, res, tail, toh, tow, nw, var, lds_bytes;
@@ -909,23 +893,13 @@ struct FxEntry {
 template <int KS, int JX, int NMB, bool RESID, int TOH, int TOW, int NW, bool TAIL16, bool XRELOAD, bool ALDS, bool SB = false>
 hipError_t fx_launch_t(hipStream_t s, const MbParams& p) {
     typedef Fx<KS, JX, NMB, TOH, TOW, NW, TAIL16, ALDS> G;
-    auto kfn = mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(NW * 64);
     static const int abl = cf_ab_int("CF_FX_ABL", 0);      // timing experiments only: results invalid
     MbParams q = p; q.nw = abl;
     set_kernel_tag(SB ? "void cf::mbconv_mx_kernel<%d, %d, %d, %s, %d, %d, %d, %s, %s, %s, true>(cf::MbParams)"
                       : "void cf::mbconv_mx_kernel<%d, %d, %d, %s, %d, %d, %d, %s, %s, %s, false>(cf::MbParams)", KS, JX, NMB, RESID ? "true" : "false",
                    TOH, TOW, NW, TAIL16 ? "true" : "false", XRELOAD ? "true" : "false", ALDS ? "true" : "false");
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, q);
-    return hipGetLastError();
+    return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB>>(grid, blk, G::LDS, s, q);
 }
 // layer2.1 is compiled in its own translation unit (cf_mbconv3_ilp.hip = this file with CF_ILP_TU defined) under
 // `-mllvm -amdgpu-sched-strategy=max-ilp`: 0.0806 -> 0.0792 ms (same box, two runs each); layer1.1 is unchanged by it (0.1799 / 0.1805) and
@@ -958,13 +932,7 @@ static const FxEntry kFxTable[] = {
 #undef FXE
 static const FxEntry* fx_find(int k, int jx, int nmb, int res, int tail) {
     static const int want = cf_ab_int("CF_FX_VARIANT", 0);
-    const FxEntry* base = nullptr;
-    for (const FxEntry& e : kFxTable)
-        if (e.k == k && e.jx == jx && e.nmb == nmb && e.res == res && e.tail == tail) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kFxTable, want, [&](const FxEntry& e) { return e.k == k && e.jx == jx && e.nmb == nmb && e.res == res && e.tail == tail; });
 }
 
 bool mx_fused_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
@@ -974,7 +942,7 @@ bool mx_fused_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
     const FxEntry* e = fx_find(k, jx, nmb, (Cin == Cout) ? 1 : 0, tail);
     if (!e) return false;
     g = MbGeom{};
-    g.ok = true; g.kind = 5; g.S = 1;
+    g.ok = true; g.kind = MB_MX; g.S = 1;
     g.JX = jx; g.NBO = nmb; g.HC = 32; g.nq = hid / 32; g.NBE = 1; g.HALF = tail;
     g.rowb = 32 * 8 + 16;
     g.lds_bytes = (size_t)e->lds_bytes;
@@ -986,7 +954,7 @@ bool mx_fused_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
 
 static inline int fx_out_channel(int mb, int m) { return 32 * (mb >> 1) + 8 * (m >> 2) + 4 * (mb & 1) + (m & 3); }
 
-void mx_fused_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+void mx_fused_pack_weights(int, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
                            void* wexp_host, float* wdw_host, void* wproj_host) {
     const int NCx = Cin * 2 / 16, nq = g.nq, tail = g.HALF, nmb = g.NBO;
     __builtin_memset(wexp_host, 0, g.wexp_bytes);
@@ -1042,14 +1010,14 @@ void mx_fused_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, c
     }
 }
 
-hipError_t mx_fused_launch(hipStream_t s, const MbParams& p) {
+hipError_t mx_fused_launch(hipStream_t s, int, const MbParams& p) {
     const FxEntry* e = fx_find(p.k, p.JX, 2 * ((p.Cout + 31) / 32), p.residual ? 1 : 0, (p.hid % 32) ? 1 : 0);
     if (!e || p.s != 1) return hipErrorInvalidValue;
     return e->fn(s, p);
 }
 
 
-// ---------------------------------------------------------------- fused block, stride 2, host side (MbGeom::kind = 6)
+// ---------------------------------------------------------------- fused block, stride 2, host side (MB_MX2 [6])
 struct FsEntry {
     int k, jx, nmb, tail, toh, tow, xr, var, lds_bytes;
     hipError_t (*fn)(hipStream_t, const MbParams&);
@@ -1057,20 +1025,10 @@ struct FsEntry {
 template <int KS, int JX, int NMB, int TOH, int TOW, bool TAIL16, bool XRELOAD, bool ALDS>
 static hipError_t fs_launch_t(hipStream_t s, const MbParams& p) {
     typedef Fs<KS, JX, NMB, TOH, TOW, TAIL16, ALDS> G;
-    auto kfn = mbconv_mx2_kernel<KS, JX, NMB, TOH, TOW, TAIL16, XRELOAD, ALDS>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(256);
     set_kernel_tag("void cf::mbconv_mx2_kernel<%d, %d, %d, %d, %d, %s, %s, %s>(cf::MbParams)", KS, JX, NMB, TOH, TOW,
                    TAIL16 ? "true" : "false", XRELOAD ? "true" : "false", ALDS ? "true" : "false");
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<mbconv_mx2_kernel<KS, JX, NMB, TOH, TOW, TAIL16, XRELOAD, ALDS>>(grid, blk, G::LDS, s, p);
 }
 #define FSE(V, KS, JX, NMB, TAIL, TOH, TOW, XR, AL) \
     {KS, JX, NMB, TAIL, TOH, TOW, XR, V, Fs<KS, JX, NMB, TOH, TOW, (TAIL != 0), (AL != 0)>::LDS, &fs_launch_t<KS, JX, NMB, TOH, TOW, (TAIL != 0), (XR != 0), (AL != 0)>}
@@ -1084,13 +1042,7 @@ static const FsEntry kFsTable[] = {
 #undef FSE
 static const FsEntry* fs_find(int k, int jx, int nmb, int tail) {
     static const int want = cf_ab_int("CF_FS_VARIANT", 0);
-    const FsEntry* base = nullptr;
-    for (const FsEntry& e : kFsTable)
-        if (e.k == k && e.jx == jx && e.nmb == nmb && e.tail == tail) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kFsTable, want, [&](const FsEntry& e) { return e.k == k && e.jx == jx && e.nmb == nmb && e.tail == tail; });
 }
 
 bool mx_fused2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
@@ -1100,7 +1052,7 @@ bool mx_fused2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
     const FsEntry* e = fs_find(k, jx, nmb, tail);
     if (!e) return false;
     g = MbGeom{};
-    g.ok = true; g.kind = 6; g.S = 2;
+    g.ok = true; g.kind = MB_MX2; g.S = 2;
     g.JX = jx; g.NBO = nmb; g.HC = 32; g.nq = hid / 32; g.NBE = 1; g.HALF = tail;
     g.rowb = 32 * 8 + 16;
     g.lds_bytes = (size_t)e->lds_bytes;
@@ -1110,7 +1062,7 @@ bool mx_fused2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
     return true;
 }
 
-void mx_fused2_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+void mx_fused2_pack_weights(int, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
                             void* wexp_host, float* wdw_host, void* wproj_host) {
     const int NCx = Cin * 2 / 16, nq = g.nq, tail = g.HALF, nmb = g.NBO;
     __builtin_memset(wexp_host, 0, g.wexp_bytes);
@@ -1169,7 +1121,7 @@ void mx_fused2_pack_weights(const MbGeom& g, int Cin, int hid, int Cout, int k, 
     }
 }
 
-hipError_t mx_fused2_launch(hipStream_t s, const MbParams& p) {
+hipError_t mx_fused2_launch(hipStream_t s, int, const MbParams& p) {
     const FsEntry* e = fs_find(p.k, p.JX, 2 * ((p.Cout + 31) / 32), (p.hid % 32) ? 1 : 0);
     if (!e || p.s != 2) return hipErrorInvalidValue;
     return e->fn(s, p);

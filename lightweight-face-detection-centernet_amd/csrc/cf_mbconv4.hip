@@ -1,4 +1,4 @@
-// Fused MBConv block for the fp32 PARITY MODE, second generation (MbGeom::kind = 7): expand 1x1 (+Swish) -> depthwise k x k
+// Fused MBConv block for the fp32 PARITY MODE, second generation (MB_F32 [7]): expand 1x1 (+Swish) -> depthwise k x k
 // (+Swish) -> project 1x1 (+residual), MBConvBlock.forward (model/centernet.py:89-140), everything in fp32 on the exact
 // v_mfma_f32_32x32x2_f32 -- the only mode that meets north_star's 1e-3 against the reference.
 //
@@ -341,20 +341,10 @@ struct F4Entry {
 template <int KS, int S, int NBO, bool RESID, int NW, int JX, int HC, int TOH, int TOW, bool SP, bool XR>
 static hipError_t f4_launch_t(hipStream_t s, const MbParams& p) {
     typedef F4<KS, S, HC, TOH, TOW, JX, NW> G;
-    auto kfn = mbconv_f32_kernel<KS, S, NBO, RESID, NW, JX, HC, TOH, TOW, XR, SP>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(NW * 64);
     set_kernel_tag("void cf::mbconv_f32_kernel<%d, %d, %d, %s, %d, %d, %d, %d, %d, %s, %s>(cf::MbParams)", KS, S, NBO, RESID ? "true" : "false", NW, JX, HC, TOH, TOW,
                    XR ? "true" : "false", SP ? "true" : "false");
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<mbconv_f32_kernel<KS, S, NBO, RESID, NW, JX, HC, TOH, TOW, XR, SP>>(grid, blk, G::LDS, s, p);
 }
 #define F4X(V, KS, S, JX, HC, NBO, RES, TOH, TOW, NW, XR) \
     {KS, S, JX, HC, NBO, RES, V, F4<KS, S, HC, TOH, TOW, JX, NW>::LDS, F4<KS, S, HC, TOH, TOW, JX, NW>::KG, &f4_launch_t<KS, S, NBO, (RES != 0), NW, JX, HC, TOH, TOW, false, (XR != 0)>, \
@@ -421,7 +411,7 @@ bool mb4_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s
     const F4Entry* e = f4_find(dtype, k, s, jx, nbo, (Cin == Cout && s == 1) ? 1 : 0);
     if (!e || hid % e->hc) return false;
     g = MbGeom{};
-    g.ok = true; g.kind = 7; g.S = s;
+    g.ok = true; g.kind = MB_F32; g.S = s;
     g.JX = jx; g.NBO = nbo; g.HC = e->hc; g.nq = hid / e->hc;
     g.NBE = (g.HC + 31) / 32; g.HALF = g.HC / 8; g.rowb = g.HC * 4 + 16; g.KG = e->kg;
     g.lds_bytes = (size_t)e->lds_bytes;

@@ -1,4 +1,4 @@
-// Expand 1x1 (+Swish) -> depthwise k x k (+Swish) for the fp32-STORAGE modes (the split-bf16 tolerance mode, MbGeom::kind = 8):
+// Expand 1x1 (+Swish) -> depthwise k x k (+Swish) for the fp32-STORAGE modes (the split-bf16 tolerance mode, XD_F32 [8]):
 // the first two convolutions of MBConvBlock.forward (model/centernet.py:89-140) in one launch, the 6x tensor only in LDS, the
 // depthwise output written once to HBM for the project GEMM (pw_wlds_kernel) -- the wide blocks layer4.0 ... 6.0, whose project
 // accumulators (pixels x Cout fp32) do not fit next to a useful tile.  Round 4 ran those blocks either fully fused on 8x16 tiles
@@ -355,21 +355,11 @@ struct X5Entry {
 template <int KS, int S, int HC, int TOH, int TOW, int JX, int NW, bool PIPE, bool SP, bool RES, int MW>
 static hipError_t x5_launch_t(hipStream_t s, const MbParams& p) {
     typedef X5<KS, S, HC, TOH, TOW, JX, NW> G;
-    auto kfn = expdw_f32_kernel<KS, S, HC, TOH, TOW, JX, NW, PIPE, SP, RES, MW>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     const int ntx = (p.Wout + TOW - 1) / TOW, nty = (p.Hout + TOH - 1) / TOH;
     dim3 grid(ntx * nty, (p.nq + p.HALF - 1) / p.HALF, p.B), blk(NW * 64);
     set_kernel_tag("void cf::expdw_f32_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %s, %s, %d>(cf::MbParams)", KS, S, HC, TOH, TOW, JX, NW, PIPE ? "true" : "false", SP ? "true" : "false",
                    RES ? "true" : "false", MW);
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<expdw_f32_kernel<KS, S, HC, TOH, TOW, JX, NW, PIPE, SP, RES, MW>>(grid, blk, G::LDS, s, p);
 }
 #define X5M(V, KS, S, JX, HC, TOH, TOW, NW, PIPE, RES, MW, QPW) \
     {V, KS, S, JX, HC, TOH, TOW, QPW, X5<KS, S, HC, TOH, TOW, JX, NW>::LDS, &x5_launch_t<KS, S, HC, TOH, TOW, JX, NW, (PIPE != 0), false, (RES != 0), MW>, \
@@ -402,16 +392,10 @@ static const X5Entry kX5Table[] = {
 
 static const X5Entry* x5_find(int k, int s, int jx) {
     static const int want = cf_ab_int("CF_X5_VARIANT", 0);
-    const X5Entry* base = nullptr;
-    for (const X5Entry& e : kX5Table)
-        if (e.k == k && e.s == s && e.jx == jx) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kX5Table, want, [&](const X5Entry& e) { return e.k == k && e.s == s && e.jx == jx; });
 }
 
-// geometry of the fp32-storage expand+depthwise kernel for a block: MbGeom with kind = 8 (HALF = hidden chunks per workgroup)
+// geometry of the fp32-storage expand+depthwise kernel for a block: MbGeom with kind = XD_F32 [8] (HALF = hidden chunks per workgroup)
 MbGeom expdw_f32_geometry(int dtype, int Cin, int hid, int k, int s) {
     MbGeom g{};
     static const bool on = cf_ab_int("CF_X5", 1) != 0;      // A/B: 0 = round 4's fused 4.x / three-launch 5.x, 6.0
@@ -419,7 +403,7 @@ MbGeom expdw_f32_geometry(int dtype, int Cin, int hid, int k, int s) {
     const int jx = (Cin * 4 / 16 + 1) / 2;
     const X5Entry* e = x5_find(k, s, jx);
     if (!e || hid % e->hc) return g;
-    g.ok = true; g.kind = 8; g.S = s;
+    g.ok = true; g.kind = XD_F32; g.S = s;
     g.JX = jx; g.NBO = 0; g.HC = e->hc; g.nq = hid / e->hc; g.NBE = (e->hc + 31) / 32; g.HALF = e->qpw;
     g.rowb = 0; g.KG = 1;
     g.lds_bytes = (size_t)e->lds_bytes;

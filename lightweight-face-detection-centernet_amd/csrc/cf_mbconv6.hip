@@ -1,4 +1,4 @@
-// Fused MBConv block for the split-bf16 TOLERANCE MODE, third generation (MbGeom::kind = 9): expand 1x1 (+Swish) -> depthwise
+// Fused MBConv block for the split-bf16 TOLERANCE MODE, third generation (MB_SP [9]): expand 1x1 (+Swish) -> depthwise
 // k x k (+Swish) -> project 1x1 (+residual), MBConvBlock.forward (model/centernet.py:89-140), for the narrow early blocks
 // (Cout <= 32: layer1.0 ... 2.1) where the depthwise dominates.
 //
@@ -299,19 +299,9 @@ struct M6Entry {
 template <int KS, int S, int HC, int TOH, int TOW, int JX, int NW, bool RESID, int MW>
 static hipError_t m6_launch_t(hipStream_t s, const MbParams& p) {
     typedef M6<KS, S, HC, TOH, TOW, JX, NW> G;
-    auto kfn = mbconv6_kernel<KS, S, HC, TOH, TOW, JX, NW, RESID, MW>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(NW * 64);
     set_kernel_tag("void cf::mbconv6_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %d>(cf::MbParams)", KS, S, HC, TOH, TOW, JX, NW, RESID ? "true" : "false", MW);
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<mbconv6_kernel<KS, S, HC, TOH, TOW, JX, NW, RESID, MW>>(grid, blk, G::LDS, s, p);
 }
 #define M6E(V, KS, S, JX, HC, RES, TOH, TOW, NW, MW) \
     {V, KS, S, JX, HC, RES, M6<KS, S, HC, TOH, TOW, JX, NW>::KG, M6<KS, S, HC, TOH, TOW, JX, NW>::HALF, M6<KS, S, HC, TOH, TOW, JX, NW>::LDS, \
@@ -331,13 +321,7 @@ static const M6Entry kM6Table[] = {
 
 static const M6Entry* m6_find(int k, int s, int jx, int res) {
     static const int want = cf_ab_int("CF_M6_VARIANT", 0);
-    const M6Entry* base = nullptr;
-    for (const M6Entry& e : kM6Table)
-        if (e.k == k && e.s == s && e.jx == jx && e.res == res) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kM6Table, want, [&](const M6Entry& e) { return e.k == k && e.s == s && e.jx == jx && e.res == res; });
 }
 
 // JX is padded to an even chunk count per lane half (chunk pairs): Cin = 24 has three 16-byte chunks per half, the fourth is zero
@@ -351,7 +335,7 @@ bool mb6_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s
     const M6Entry* e = m6_find(k, s, jx, (Cin == Cout && s == 1) ? 1 : 0);
     if (!e || hid % e->hc) return false;
     g = MbGeom{};
-    g.ok = true; g.kind = 9; g.S = s;
+    g.ok = true; g.kind = MB_SP; g.S = s;
     g.JX = jx; g.NBO = 1; g.HC = e->hc; g.nq = hid / e->hc;
     g.NBE = (g.HC + 31) / 32; g.HALF = e->half; g.rowb = 0; g.KG = e->kg;
     g.lds_bytes = (size_t)e->lds_bytes;
@@ -364,7 +348,7 @@ bool mb6_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s
 // expand fragments [chunk][n-block][JX][lane] x 16 B (split pairs; -log2 e folded), taps [chunk][group][tap][4], project fragments
 // [chunk][k-group][JS][lane] x 16 B (-ln 2 folded; split pairs within a k-group): lane (row slot i -> output channel, half h) holds
 // w[co][chunk base + (h HALF + kg JS + js) 4 + e]
-void mb6_pack(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+void mb6_pack(int, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
               void* wexp_host, float* wdw_host, void* wproj_host) {
     const int NCx = Cin * 4 / 16;                                  // real 16-byte chunks of an input row
     const int JH = (NCx + 1) / 2;                                  // real chunks per lane half
@@ -407,7 +391,7 @@ void mb6_pack(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* w
     split_pairs_inplace(wproj_host, (size_t)g.nq * g.KG, JS);
 }
 
-hipError_t mb6_launch(hipStream_t s, const MbParams& p) {
+hipError_t mb6_launch(hipStream_t s, int, const MbParams& p) {
     const M6Entry* e = m6_find(p.k, p.s, p.JX, p.residual ? 1 : 0);
     if (!e || e->hc != p.HC) return hipErrorInvalidValue;
     return e->fn(s, p);

@@ -207,8 +207,8 @@ int cf_op_mbconv(int device, int dtype, const float* x, const float* w_exp, cons
     p.wexp = sc.up(we.data(), we.size()); p.wdw = sc.upv(wd); p.wproj = sc.up(wp.data(), wp.size());
     p.B = B; p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.Cin = Cin; p.hid = hid; p.Cout = Cout;
     p.k = k; p.s = stride; p.pad_lo = pd / 2; p.residual = (Cin == Cout && stride == 1) ? 1 : 0;
-    p.HC = g.HC; p.nq = g.nq; p.NBE = g.NBE; p.JX = g.JX; p.HALF = g.HALF; p.rowb = g.rowb; p.lds_bytes = g.lds_bytes; p.kind = g.kind;
-#ifdef CF_X5_TIMING      // A/B build only: per-wave phase cycle sums of mbconv_f32_kernel (kind 7), printed to stderr
+    mb_fill(p, g);
+#ifdef CF_X5_TIMING      // A/B build only: per-wave phase cycle sums of mbconv_f32_kernel (MB_F32 [7]), printed to stderr
     const size_t tn = (size_t)1 << 22;
     unsigned long long* tdev = (unsigned long long*)sc.alloc(tn * 8);
     (void)hipMemsetAsync(tdev, 0, tn * 8, sc.s); p.dbg = tdev;
@@ -248,11 +248,11 @@ int cf_op_expand_dw(int device, int dtype, const float* x, const float* w_exp, c
     p.wexp = sc.up(we.data(), we.size()); p.wdw = sc.upv(wd);
     p.B = B; p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.Cin = Cin; p.hid = hid; p.Cout = hid;
     p.k = k; p.s = stride; p.pad_lo = pd / 2;
-    p.HC = g.HC; p.nq = g.nq; p.NBE = g.NBE; p.JX = g.JX; p.HALF = g.HALF; p.rowb = g.rowb; p.lds_bytes = g.lds_bytes; p.kind = g.kind;
+    mb_fill(p, g);
 #ifdef CF_X5_TIMING      // A/B build only (tools/ab_build.sh): per-wave phase cycle sums of expdw_f32_kernel, printed to stderr
     const size_t tn = (size_t)1 << 20;
     unsigned long long* tdev = (unsigned long long*)sc.alloc(tn * 8);
-    if (g.kind == 8) { (void)hipMemsetAsync(tdev, 0, tn * 8, sc.s); p.wproj = tdev; }
+    if (g.kind == XD_F32) { (void)hipMemsetAsync(tdev, 0, tn * 8, sc.s); p.wproj = tdev; }
     for (int rep = 0; rep < 3 && sc.err == hipSuccess; ++rep) sc.chk(launch_mbconv(sc.s, dtype, p));
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, sc.s);
@@ -261,7 +261,7 @@ int cf_op_expand_dw(int device, int dtype, const float* x, const float* w_exp, c
 #ifdef CF_X5_TIMING
     (void)hipEventRecord(e1, sc.s); (void)hipStreamSynchronize(sc.s);
     float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-    if (g.kind == 8) {
+    if (g.kind == XD_F32) {
         std::vector<unsigned long long> th(tn);
         (void)hipMemcpy(th.data(), tdev, tn * 8, hipMemcpyDeviceToHost);
         double sum[4] = {0, 0, 0, 0}; size_t nw = 0;

@@ -57,6 +57,7 @@ struct Op {
     // fused MBConv (OP_MB): Cin -> hid -> Cout
     int hid = 0; bool residual = false; std::string wkey_dw, wkey_proj;
     MbGeom geo{}; void* wexp = nullptr; float* wdw = nullptr; void* wproj = nullptr;
+    int stem0_kind = 0;                               // OP_STEM0: Stem0Params::kind (STEM0_* bits), set when the weights are packed
     double macs = 0;                                  // per image
     // IDAUp stage 3 fused into the head kernel (cf_uphead.hip): the OP_PW op keeps its weights but is not
     // launched (fused_away); the OP_HEAD op launches the fused kernel with its partner's operands
@@ -157,8 +158,7 @@ void layout_pass(cf_ctx* c) {
         if (j < 0) continue;
         Op& pr = ops[j];
         const bool can_write = !pr.fused_away && pr.low < 0 &&
-                               ((pr.kind == OP_PW && pr.bnkey.empty()) || (pr.kind == OP_MB && (pr.geo.kind == 1 || pr.geo.kind == 5 || pr.geo.kind == 6)) ||
-                                (pr.kind == OP_MB && c->dtype != CF_BF16 && pr.geo.kind == 0));      // cf_mbconv.hip's fp32-tile kernel (layer3.1 in the split mode)
+                               ((pr.kind == OP_PW && pr.bnkey.empty()) || (pr.kind == OP_MB && mb_writes_blocked(pr.geo.kind, c->dtype)));
         if (!can_write) continue;
         bool ok = true;
         size_t end = j + 1;
@@ -227,7 +227,7 @@ void build_plan(cf_ctx* c) {
             // in one kernel (no accumulators: 6 waves per SIMD) + the LDS-weight GEMM for the project conv is faster although
             // the depthwise output makes a round trip through HBM: 0.111 -> 0.095 ms and 0.166 -> 0.141 ms.  CF_SPLIT_WIDE=0: A/B.
             static const bool fuse_wide = cf_ab_int("CF_SPLIT_WIDE", 1) == 0;
-            if (!fuse_wide && c->dtype == CF_BF16 && cout > 64 && geo.kind == 1) geo.ok = false;
+            if (!fuse_wide && c->dtype == CF_BF16 && cout > 64 && geo.kind == MB_PX) geo.ok = false;
             // fp32-storage modes, round 5: the same split for Cout = 96 (layer4.x) wherever cf_mbconv5.hip has the shape -- the fused
             // kernel's three accumulator blocks hold it to 8x16 tiles (1.9x halo recompute) and two waves per SIMD
             if (!fuse_wide && c->dtype != CF_BF16 && cout > 64 && expdw_geometry(c->dtype, cin, hid, k, s).ok) geo.ok = false;
@@ -711,7 +711,7 @@ int cf_load_weights(cf_ctx* c, const cf_tensor_desc* tensors, int n) {
             static const bool swz_on = cf_env_int("CF_XCD_ORDER", 1) >= 1;      // product switch
             static const bool mx_off = cf_env_int("CF_DW_MATRIX", 1) == 0 || cf_ab_int("CF_STEM_MX", 1) == 0;      // product switch: depthwise on the matrix cores
             const bool mx = px && !mx_off;
-            op.geo.kind = px ? ((swz_on ? 3 : 1) | (mx ? 4 : 0)) : 0;
+            op.stem0_kind = px ? (STEM0_PX | (swz_on ? STEM0_XCD : 0) | (mx ? STEM0_MX : 0)) : 0;
             std::vector<char> w(px ? stem0px_wstem_bytes() : stem_packed_bytes(dt)), wp(stem0_proj_bytes(dt));
             std::vector<float> wd(mx ? stem0mx_wdw_dwords() : px ? stem0px_wdw_dwords() : 9 * 32), lut(768);
             if (mx) {
@@ -870,7 +870,7 @@ hipError_t launch_op(cf_ctx* c, const Op& op, const void* net_in, int in_format,
         }
         case OP_STEM0: {
             Stem0Params p{}; p.x = net_in; p.in_format = in_format; p.lut = op.upw; p.wstem = op.wp; p.wdw = op.wdw;
-            p.wproj = op.wproj; p.y = bp(op.out); p.B = B; p.H = op.Hin; p.W = op.Win; p.kind = op.geo.kind;
+            p.wproj = op.wproj; p.y = bp(op.out); p.B = B; p.H = op.Hin; p.W = op.Win; p.kind = op.stem0_kind;
             return launch_stem0(c->stream, c->dtype, p);
         }
         case OP_EXPDW:
@@ -879,8 +879,7 @@ hipError_t launch_op(cf_ctx* c, const Op& op, const void* net_in, int in_format,
             if (img0) p.x = at(op.in, op.Hin, op.Win, op.Cin);                                                              // y: the depthwise tensor, from its start
             p.B = B; p.Hin = op.Hin; p.Win = op.Win; p.Hout = op.Hout; p.Wout = op.Wout; p.Cin = op.Cin; p.hid = op.hid; p.Cout = op.Cout;
             p.k = op.k; p.s = op.s; p.pad_lo = op.pad_lo; p.residual = op.residual ? 1 : 0;
-            p.HC = op.geo.HC; p.nq = op.geo.nq; p.NBE = op.geo.NBE; p.JX = op.geo.JX; p.HALF = op.geo.HALF; p.rowb = op.geo.rowb;
-            p.lds_bytes = op.geo.lds_bytes; p.kind = op.geo.kind; p.yblock = op.out_blk ? 1 : 0; p.xblock = op.in_blk ? 1 : 0;
+            mb_fill(p, op.geo); p.yblock = op.out_blk ? 1 : 0; p.xblock = op.in_blk ? 1 : 0;
             return launch_mbconv(c->stream, c->dtype, p);
         }
         case OP_HEAD: {
@@ -1799,13 +1798,6 @@ static hipStream_t pick_stream(cf_ctx* c, int which) {
 // for the first.  One timing sample can be fooled by anything else using the GPU: three probes, majority decides.  Both streams idle.
 static int streams_share(cf_ctx* a, hipStream_t sa, hipStream_t sb, int* shared, bool fat = false) {
     if (sa == sb) { *shared = 1; return CF_OK; }
-    if (fat) {
-        static thread_local bool configured_dev[64] = {};
-        if (!configured_dev[a->device & 63]) {
-            HIPCHK(a, hipFuncSetAttribute(reinterpret_cast<const void*>(cf_fat_spin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            configured_dev[a->device & 63] = true;
-        }
-    }
     HIPCHK(a, hipStreamSynchronize(sa));
     HIPCHK(a, hipStreamSynchronize(sb));
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -1815,9 +1807,8 @@ static int streams_share(cf_ctx* a, hipStream_t sa, hipStream_t sb, int* shared,
     for (int rep = 0; rep < 3 && err == hipSuccess; ++rep) {
         auto step = [&](hipError_t e) { if (err == hipSuccess) err = e; };
         step(hipEventRecord(ev[0], sa));
-        if (fat) hipLaunchKernelGGL(cf_fat_spin_kernel, dim3(2560), dim3(64), 64 * 1024, sa, (long long)6000);       // 5 rounds of 60 us
-        else hipLaunchKernelGGL(cf_spin_kernel, dim3(1), dim3(64), 0, sa, (long long)30000);
-        step(hipGetLastError());
+        if (fat) step(launch_lds<cf_fat_spin_kernel>(dim3(2560), dim3(64), 64 * 1024, sa, (long long)6000));       // 5 rounds of 60 us
+        else step(launch_lds<cf_spin_kernel>(dim3(1), dim3(64), 0, sa, (long long)30000));
         step(hipEventRecord(ev[1], sa));
         hipLaunchKernelGGL(cf_spin_kernel, dim3(1), dim3(64), 0, sb, (long long)0);
         step(hipGetLastError());

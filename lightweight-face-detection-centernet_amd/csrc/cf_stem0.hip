@@ -421,7 +421,7 @@ __global__ __launch_bounds__(S0P_NT) void stem0_px_kernel(Stem0Params p) {
     const int pl = lane & 31, h = lane >> 5;
     const int Ho = p.H >> 1, Wo = p.W >> 1;
     unsigned tbx = blockIdx.x, tby = blockIdx.y, tbz = blockIdx.z;
-    if (p.kind & 2) xcd_tile_order(tbx, tby, tbz);
+    if (p.kind & STEM0_XCD) xcd_tile_order(tbx, tby, tbz);
     const int ox0 = tbx * S0_TOW, oy0 = tby * S0_TOH, b = tbz;
 
     // ---- stage the normalised image patch
@@ -680,7 +680,7 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
     const int pl = lane & 31, h = lane >> 5;
     const int Ho = p.H >> 1, Wo = p.W >> 1;
     unsigned tbx = blockIdx.x, tby = blockIdx.y, tbz = blockIdx.z;
-    if (p.kind & 2) xcd_tile_order(tbx, tby, tbz);
+    if (p.kind & STEM0_XCD) xcd_tile_order(tbx, tby, tbz);
     const int ox0 = tbx * S0_TOW, oy0 = tby * S0_TOH, b = tbz;
 
     // ---- stage the normalised image patch
@@ -872,7 +872,7 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
 hipError_t launch_stem0(hipStream_t s, int dtype, const Stem0Params& p) {
     if (p.B <= 0) return hipSuccess;
     const int Ho = p.H / 2, Wo = p.W / 2;
-    if (p.kind & 4) {                      // matrix-core depthwise (bf16 storage)
+    if (p.kind & STEM0_MX) {                      // matrix-core depthwise (bf16 storage)
         if (dtype != 1) return hipErrorInvalidValue;
         dim3 grid((Wo + S0_TOW - 1) / S0_TOW, (Ho + S0_TOH - 1) / S0_TOH, p.B), blk(S0P_NT);
         set_kernel_tag("void cf::stem0_mx_kernel<%d>(cf::Stem0Params)", p.in_format);
@@ -880,7 +880,7 @@ hipError_t launch_stem0(hipStream_t s, int dtype, const Stem0Params& p) {
         else hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_F32_NCHW>), grid, blk, 0, s, p);
         return hipGetLastError();
     }
-    if (p.kind & 1) {
+    if (p.kind & STEM0_PX) {
         if (dtype != 1) return hipErrorInvalidValue;
         dim3 grid((Wo + S0_TOW - 1) / S0_TOW, (Ho + S0_TOH - 1) / S0_TOH, p.B), blk(S0P_NT);
         set_kernel_tag("void cf::stem0_px_kernel<%d>(cf::Stem0Params)", p.in_format);

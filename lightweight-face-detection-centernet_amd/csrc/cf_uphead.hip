@@ -174,19 +174,9 @@ __global__ __launch_bounds__(NW * 64) void uphead_kernel(UpHeadParams p) {
 template <typename T, bool CO, int TH, int NW, bool NT>
 static hipError_t uphead_launch_t(hipStream_t s, const UpHeadParams& q) {
     typedef Uh<T, TH, NW> U;
-    auto kfn = uphead_kernel<T, CO, TH, NW, NT>;
-    static thread_local bool configured_dev[32] = {};               // function attributes are per device
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (U::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, U::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid((q.w + UH_TW - 1) / UH_TW, (q.h + TH - 1) / TH, q.B), blk(NW * 64);
     set_kernel_tag("void cf::uphead_kernel<%s, %s, %d, %d, %s>(cf::UpHeadParams)", type_tag<T>(), CO ? "true" : "false", TH, NW, NT ? "true" : "false");
-    hipLaunchKernelGGL(kfn, grid, blk, U::LDS, s, q);
-    return hipGetLastError();
+    return launch_lds<uphead_kernel<T, CO, TH, NW, NT>>(grid, blk, U::LDS, s, q);
 }
 
 hipError_t launch_uphead(hipStream_t s, int dtype, const UpHeadParams& p) {

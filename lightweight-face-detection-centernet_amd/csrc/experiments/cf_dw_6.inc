@@ -3,16 +3,8 @@
         static const int band = cf_ab_int("CF_DW_BAND", 0);
         const int nitem = TH * (TW / 4) * g.cpp, nitemA = (TH / 2) * (TW / 4) * g.cpp;
         if (band && nitemA <= threads && nitem - nitemA <= threads && ((size_t)g.nch + 63) / 64 <= 16 * (size_t)(threads / 64)) {
-            auto bfn = dw_band_kernel<T, KS, S, TH, TW>;
-            static thread_local bool bigb[64] = {};
-            if (!bigb[dev & 63]) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bfn), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-                if (e != hipSuccess) return e;
-                bigb[dev & 63] = true;
-            }
             DwLdsGeom gb = g; dw_set_step(gb, threads);
             set_kernel_tag("void cf::dw_band_kernel<%s, %d, %d, %d, %d>(cf::DwParams, cf::DwLdsGeom, int, int, int)", type_tag<T>(), KS, S, TH, TW);
-            hipLaunchKernelGGL(bfn, dim3((unsigned)nt), dim3(threads), g.lds_bytes, s, p, gb, ntx, nty, (int)nt);
-            return hipGetLastError();
+            return launch_lds<dw_band_kernel<T, KS, S, TH, TW>>(dim3((unsigned)nt), dim3(threads), g.lds_bytes, s, p, gb, ntx, nty, (int)nt);
         }
     }

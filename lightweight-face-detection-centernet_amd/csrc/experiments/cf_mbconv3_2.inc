@@ -3,18 +3,8 @@ template <int KS, int JX, int TOH, int TOW, int NW, int R>
 static hipError_t xmxr_launch_t(hipStream_t s, const MbParams& p) {
     typedef Mx<KS, JX, TOH, TOW, NW, true> G;
     constexpr int LDS = G::EBYTES + 2 * (G::WXB + G::ATB);
-    auto kfn = expdw_mxr_kernel<KS, JX, TOH, TOW, NW, R>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     if ((p.hid / 32) % R) return hipErrorInvalidValue;
     dim3 grid(((p.Wout + TOW - 1) / TOW) * ((p.Hout + TOH - 1) / TOH), p.hid / 32 / R, p.B), blk(NW * 64);
     set_kernel_tag("void cf::expdw_mxr_kernel<%d, %d, %d, %d, %d, %d>(cf::MbParams)", KS, JX, TOH, TOW, NW, R);
-    hipLaunchKernelGGL(kfn, grid, blk, LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<expdw_mxr_kernel<KS, JX, TOH, TOW, NW, R>>(grid, blk, LDS, s, p);
 }

@@ -2,18 +2,8 @@
 template <int KS, int JX, int TOH, int TOW, int NW, int T>
 static hipError_t xmxt_launch_t(hipStream_t s, const MbParams& p) {
     typedef Mx<KS, JX, TOH, TOW, NW, true> G;
-    auto kfn = expdw_mxt_kernel<KS, JX, TOH, TOW, NW, T>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     const int units = ((p.Wout + TOW - 1) / TOW) * ((p.Hout + TOH - 1) / TOH) * p.B;
     dim3 grid((units + T - 1) / T, p.hid / 32, 1), blk(NW * 64);
     set_kernel_tag("void cf::expdw_mxt_kernel<%d, %d, %d, %d, %d, %d>(cf::MbParams)", KS, JX, TOH, TOW, NW, T);
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<expdw_mxt_kernel<KS, JX, TOH, TOW, NW, T>>(grid, blk, G::LDS, s, p);
 }

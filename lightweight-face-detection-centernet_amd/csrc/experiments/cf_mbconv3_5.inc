@@ -2,18 +2,8 @@
 template <int KS, int JX, int NMB, bool RESID, int TOH, int TOW, bool TAIL16>
 static hipError_t fz_launch_t(hipStream_t s, const MbParams& p) {
     typedef Fz<KS, JX, NMB, TOH, TOW, TAIL16> G;
-    auto kfn = mbconv_mxs_kernel<KS, JX, NMB, RESID, TOH, TOW, TAIL16>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(512);
     set_kernel_tag("void cf::mbconv_mxs_kernel<%d, %d, %d, %s, %d, %d, %s>(cf::MbParams)", KS, JX, NMB, RESID ? "true" : "false", TOH, TOW,
                    TAIL16 ? "true" : "false");
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<mbconv_mxs_kernel<KS, JX, NMB, RESID, TOH, TOW, TAIL16>>(grid, blk, G::LDS, s, p);
 }

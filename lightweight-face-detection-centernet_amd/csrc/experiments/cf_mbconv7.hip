@@ -1,5 +1,5 @@
 // Fused MBConv block for the split-bf16 tolerance mode, register-window depthwise feeding the project MFMAs DIRECTLY
-// (MbGeom::kind = 10; cf_mbconv6.hip without its second LDS tile): MBConvBlock.forward (model/centernet.py:89-140), Cout <= 32.
+// (MB_SP_DIRECT [10]; cf_mbconv6.hip without its second LDS tile): MBConvBlock.forward (model/centernet.py:89-140), Cout <= 32.
 //
 // cf_mbconv6.hip sends the depthwise output of a chunk through a second LDS tile so that the project MFMAs can read lane = pixel
 // fragments: a round trip and a barrier per chunk, and it lost to cf_mbconv4.hip on every 3x3 block.  The strip layout does not
@@ -306,19 +306,9 @@ struct M7Entry {
 template <int KS, int S, int HC, int TOH, int TOW, int JX, int NW, bool RESID, int MW>
 static hipError_t m7_launch_t(hipStream_t s, const MbParams& p) {
     typedef M7<KS, S, HC, TOH, TOW, JX, NW> G;
-    auto kfn = mbconv7_kernel<KS, S, HC, TOH, TOW, JX, NW, RESID, MW>;
-    static thread_local bool configured_dev[32] = {};
-    int dev = 0; (void)hipGetDevice(&dev);
-    bool& configured = configured_dev[dev & 31];
-    if (G::LDS > 64 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(NW * 64);
     set_kernel_tag("void cf::mbconv7_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %d>(cf::MbParams)", KS, S, HC, TOH, TOW, JX, NW, RESID ? "true" : "false", MW);
-    hipLaunchKernelGGL(kfn, grid, blk, G::LDS, s, p);
-    return hipGetLastError();
+    return launch_lds<mbconv7_kernel<KS, S, HC, TOH, TOW, JX, NW, RESID, MW>>(grid, blk, G::LDS, s, p);
 }
 #define M7E(V, KS, S, JX, HC, RES, TOH, TOW, NW, MW) \
     {V, KS, S, JX, HC, RES, M7<KS, S, HC, TOH, TOW, JX, NW>::LDS, &m7_launch_t<KS, S, HC, TOH, TOW, JX, NW, (RES != 0), MW>}
@@ -343,13 +333,7 @@ static const M7Entry kM7Table[] = {
 
 static const M7Entry* m7_find(int k, int s, int jx, int res) {
     static const int want = cf_ab_int("CF_M7_VARIANT", 0);
-    const M7Entry* base = nullptr;
-    for (const M7Entry& e : kM7Table)
-        if (e.k == k && e.s == s && e.jx == jx && e.res == res) {
-            if (e.var == want) return &e;
-            if (e.var == 0) base = &e;
-        }
-    return base;
+    return pick_variant(kM7Table, want, [&](const M7Entry& e) { return e.k == k && e.s == s && e.jx == jx && e.res == res; });
 }
 
 // JX is padded to an even chunk count per lane half (chunk pairs): Cin = 24 has three 16-byte chunks per half, the fourth is zero
@@ -363,7 +347,7 @@ bool mb7_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s
     const M7Entry* e = m7_find(k, s, jx, (Cin == Cout && s == 1) ? 1 : 0);
     if (!e || hid % e->hc) return false;
     g = MbGeom{};
-    g.ok = true; g.kind = 10; g.S = s;
+    g.ok = true; g.kind = MB_SP_DIRECT; g.S = s;
     g.JX = jx; g.NBO = 1; g.HC = e->hc; g.nq = hid / e->hc;
     g.NBE = (g.HC + 31) / 32; g.HALF = g.HC / 8; g.rowb = 0; g.KG = 1;
     g.lds_bytes = (size_t)e->lds_bytes;
@@ -375,11 +359,11 @@ bool mb7_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s
 
 // expand fragments and taps as mb6_pack; project fragments [chunk][group pair gp][lane] x 16 B ([4 x hi | 4 x lo]; -ln 2 folded): lane (row
 // slot i -> output channel, half h) holds w[co][chunk base + (2 gp + h) 4 + e] -- k-slots 0-3 = group 2 gp, 4-7 = group 2 gp + 1
-void mb7_pack(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
+void mb7_pack(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, const float* we, const float* wd, const float* wp,
               void* wexp_host, float* wdw_host, void* wproj_host) {
     MbGeom g6 = g; g6.KG = 1;
     std::vector<char> scratch(g.wproj_bytes);
-    mb6_pack(g6, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, scratch.data());       // (its project fragments are not used)
+    mb6_pack(dtype, g6, Cin, hid, Cout, k, we, wd, wp, wexp_host, wdw_host, scratch.data());       // (its project fragments are not used)
     __builtin_memset(wproj_host, 0, g.wproj_bytes);
     const int NGP = g.HC / 8;
     for (int q = 0; q < g.nq; ++q)
@@ -395,7 +379,7 @@ void mb7_pack(const MbGeom& g, int Cin, int hid, int Cout, int k, const float* w
     split_pairs_inplace(wproj_host, (size_t)g.nq * NGP, 1);
 }
 
-hipError_t mb7_launch(hipStream_t s, const MbParams& p) {
+hipError_t mb7_launch(hipStream_t s, int, const MbParams& p) {
     const M7Entry* e = m7_find(p.k, p.s, p.JX, p.residual ? 1 : 0);
     if (!e || e->hc != p.HC) return hipErrorInvalidValue;
     return e->fn(s, p);

@@ -215,6 +215,39 @@ int cf_set_rescale(cf_ctx* ctx, float scale_h, float scale_w);
  * in flight and collect them later (CenterFaceBuckets): the decode runs when the forward finishes, not when the host gets there. */
 int cf_decode_threshold_enqueue(cf_ctx* ctx, int mode, float score_thresh, float nms_thresh, int img_h, int img_w, int max_out);
 
+/* ---- aligned face chips: the similarity warp of the frame onto a chip template, on the device ---------------------------- */
+/* The next stage of a face pipeline (recognition, quality, attributes) takes an aligned crop: the least-squares similarity that maps
+ * the detector's five landmarks onto a template (what SimilarityTransform.estimate + cv2.warpAffine do on the host), sampled
+ * bilinearly.  Here one kernel writes the chips of every kept face of the batch from data that is still on the device.  The
+ * arithmetic is this library's own statement (csrc/cf_align.hip, restated in tests/test_align.py): float64 estimate in a fixed
+ * operation order, fixed-point warp (1/32-pixel positions, weights out of 1024, constant border 0 per neighbour).  It is NOT claimed
+ * bit-identical to cv2.warpAffine, whose weight table is rounded to 15 bits. */
+#define CF_CHIP_U8_HWC_BGR 0     /* uint8 [N,S,S,3] BGR */
+#define CF_CHIP_F32_NCHW   1     /* float [N,3,S,S], value ((float)u8 - mean) * scale; planes B,G,R, or R,G,B when rgb != 0 */
+typedef struct cf_align_opts {
+    int32_t size;                /* S: chip side, a multiple of 4 in [16, 512] */
+    int32_t format;              /* CF_CHIP_* */
+    int32_t rgb;                 /* CF_CHIP_F32_NCHW only: channel order R,G,B */
+    float   mean, scale;         /* CF_CHIP_F32_NCHW only */
+    const float* tmpl;           /* [5][2] template points (x, y) in chip pixels, or NULL: the ArcFace 112 x 112 points times S / 112 */
+    int32_t max_per_image;       /* at most this many faces per image, in keep order; 0 = all */
+} cf_align_opts;
+/* Chips of the faces kept by the LAST THRESHOLD DECODE of the last forward of ctx (cf_decode_threshold[_ex | _sized | _enqueue]),
+ * sampled from the uint8 BGR batch the network read in that forward -- whichever entry point put it there (cf_forward with
+ * CF_IN_U8_HWC_BGR from host or device, cf_forward_resized, cf_forward_images / _uploaded, cf_forward_yuv); a device input of
+ * cf_forward must still be unchanged.  Landmarks are taken in NETWORK coordinates whatever cf_set_rescale says, so the chips are
+ * cut from the network-sized batch (sampling a full-resolution source behind cf_forward_resized is not offered).  Face
+ * n = offsets[b] + i is keep position i of image b; offsets [B + 1] = exclusive prefix sum of min(counts[b], the decode's max_out,
+ * max_per_image).  Only faces n < cap_faces are written; offsets[B] is the number WANTED, so offsets[B] > cap_faces tells the
+ * caller of the truncation (call again with more room).  chips: [cap_faces] chips in opts->format; matrices (may be NULL):
+ * [cap_faces][6] float64, the row-major 2x3 chip -> source map that was sampled (all zero for a face that cannot be aligned:
+ * non-finite or coincident landmarks, or a scale beyond the fixed-point range; its chip is that of an all-zero source).
+ * out_on_device = 1: chips / matrices / offsets are device buffers (chips 16-byte aligned), the call is asynchronous on the stream
+ * that carried the decode and reads no count on the host; 0: host buffers, blocking.  CF_EINVAL for any bad argument before any GPU
+ * work; CF_ESTATE without a threshold decode behind the last forward, after a CF_IN_F32_NCHW forward, or once another upload or
+ * forward was started on ctx. */
+int cf_align_faces(cf_ctx* ctx, const cf_align_opts* opts, void* chips, double* matrices, int32_t* offsets, int cap_faces, int out_on_device);
+
 /* ---- fused convenience: forward + D3 decode in one enqueue (eval_widerface.py:76-90 shape) -- */
 int cf_detect_topk(cf_ctx* ctx, const void* in, int in_format, int in_on_device, int B, int K,
                    float* dets, float* lms, int64_t* inds, int out_on_device);
@@ -448,6 +481,10 @@ int cf_op_ctdet_post_process(int device, float* dets, const float* centers, cons
  * cv2.cvtColor(bgr, COLOR_BGR2YUV_I420) returns) -> bgr [B][H][W][3].  (H, W) == (h, w): the conversion only; otherwise followed
  * by cv2.resize to (H, W).  h, w, W even. */
 int cf_op_yuv_to_bgr(int device, int yuv_format, const uint8_t* frames, uint8_t* bgr, int B, int h, int w, int H, int W);
+/* The kernel of cf_align_faces alone, on host arrays: imgs uint8 [B,h,w,3] BGR (w >= 2), lms [N,10] landmark rows in image pixels,
+ * image after image, counts [B] (>= 0, N = their sum): chips [N] in opts->format, matrices [N,6] float64 (may be NULL). */
+int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, const float* lms, const int32_t* counts,
+                      const cf_align_opts* opts, void* chips, double* matrices);
 /* CenterFace.nms alone (centerface.py:111-151): keep[] receives kept indices in keep order. */
 int cf_op_nms(int device, const float* boxes, const float* scores, int n, float nms_thresh,
               int32_t* keep, int32_t* n_keep);

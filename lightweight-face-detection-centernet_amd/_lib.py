@@ -18,6 +18,10 @@ CF_FLAG_COLLAPSE_HEADS, CF_FLAG_NO_GRAPH, CF_FLAG_NO_FUSE, CF_FLAG_NO_UPHEAD, CF
 CF_EOVERFLOW = -6
 # 4:2:0 video frame formats of cf_forward_yuv / cf_op_yuv_to_bgr (cv2.COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12)
 CF_YUV_NV12, CF_YUV_NV21, CF_YUV_I420, CF_YUV_YV12 = 0, 1, 2, 3
+# chip formats of cf_align_faces / cf_op_align_faces
+CF_CHIP_U8_HWC_BGR, CF_CHIP_F32_NCHW = 0, 1
+CHIP_FORMATS = {"u8": CF_CHIP_U8_HWC_BGR, "uint8": CF_CHIP_U8_HWC_BGR, "f32": CF_CHIP_F32_NCHW, "float32": CF_CHIP_F32_NCHW}
+CF_ESTATE = -4
 YUV_FORMATS = {"nv12": CF_YUV_NV12, "nv21": CF_YUV_NV21, "i420": CF_YUV_I420, "yuv420p": CF_YUV_I420, "yv12": CF_YUV_YV12}
 
 # every symbol include/centerface_hip.h declares (checked by tests/test_abi.py)
@@ -28,7 +32,7 @@ EXPORTS = (
     "cf_profile_forward", "cf_plan_size", "cf_plan_op", "cf_forward_trace", "cf_graph_stats", "cf_get_streams", "cf_streams_share_queue", "cf_streams_share_queue_ex", "cf_spread_streams", "cf_reroll_streams", "cf_ctdet_loss", "cf_comm_unique_id", "cf_comm_create", "cf_comm_create_all", "cf_comm_create_loopback", "cf_comm_loopback_rank", "cf_comm_destroy", "cf_comm_abort", "cf_comm_query", "cf_comm_synchronize", "cf_comm_last_error", "cf_comm_debug", "cf_comm_set_shard", "cf_comm_stream", "cf_gather_topk", "cf_host_alloc", "cf_host_free", "cf_pinned_alloc", "cf_pinned_free", "cf_host_register", "cf_host_unregister", "cf_device_alloc", "cf_device_free", "cf_memcpy_h2d", "cf_memcpy_d2h",
     "cf_op_last_error", "cf_op_shufflev2", "cf_op_mbconv", "cf_op_expand_dw", "cf_op_ctdet_loss", "cf_op_encode_targets", "cf_op_dwconv", "cf_op_pwconv", "cf_op_stem", "cf_op_idaup", "cf_op_heads",
     "cf_op_ctdet_decode", "cf_op_ctdet_post_process", "cf_op_decode_threshold", "cf_op_decode_threshold_ex", "cf_op_nms", "cf_op_box_match",
-    "cf_op_yuv_to_bgr",
+    "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces",
 )
 
 
@@ -50,6 +54,33 @@ class OpInfo(C.Structure):
 class YuvPlanes(C.Structure):
     """cf_yuv_planes: the planes of one frame (c0 / c1 = the chroma planes in the format's order; c1 NULL for NV12 / NV21)."""
     _fields_ = [("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p)]
+
+
+class AlignOpts(C.Structure):
+    """cf_align_opts: chip size / format / channel order / normalisation / template / per-image limit."""
+    _fields_ = [("size", C.c_int32), ("format", C.c_int32), ("rgb", C.c_int32), ("mean", C.c_float), ("scale", C.c_float),
+                ("tmpl", C.c_void_p), ("max_per_image", C.c_int32)]
+
+
+def align_opts(size=112, out="u8", rgb=False, mean=0.0, scale=1.0, template=None, max_per_image=0):
+    """(AlignOpts, the template array it points to or None -- keep it alive for the call, chip shape, chip dtype).  ``out``: 'u8'
+    (uint8 [S,S,3] BGR) or 'f32' (float32 [3,S,S], ``(u8 - mean) * scale``, RGB planes with ``rgb``); integer codes pass through (the
+    library validates them, like the size)."""
+    if isinstance(out, str):
+        if out.lower() not in CHIP_FORMATS:
+            raise ValueError("unknown chip format %r (one of %s)" % (out, sorted(CHIP_FORMATS)))
+        fmt = CHIP_FORMATS[out.lower()]
+    else:
+        fmt = int(out)
+    tm = None
+    if template is not None:
+        tm = np.ascontiguousarray(template, dtype=np.float32)
+        if tm.shape != (5, 2):
+            raise ValueError("template must be [5][2] (x, y) points in chip pixels, got %s" % (tm.shape,))
+    S = int(size)
+    o = AlignOpts(S, fmt, 1 if rgb else 0, float(mean), float(scale), tm.ctypes.data if tm is not None else None, int(max_per_image))
+    shape, dtype = ((3, S, S), np.float32) if fmt == CF_CHIP_F32_NCHW else ((S, S, 3), np.uint8)
+    return o, tm, shape, dtype
 
 
 def yuv_format(fmt):
@@ -107,6 +138,8 @@ def lib():
         L.cf_forward_resized.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.cf_forward_yuv.argtypes = [C.c_void_p, C.c_int, C.POINTER(YuvPlanes), C.c_int] + [C.c_int] * 5
         L.cf_op_yuv_to_bgr.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
+        L.cf_align_faces.argtypes = [C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.cf_op_align_faces.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p]
         L.cf_get_resized_input.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.cf_get_heads.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.cf_decode_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

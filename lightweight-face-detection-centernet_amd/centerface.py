@@ -314,7 +314,39 @@ class Engine(object):
             if int(counts.max(initial=0)) <= max_out:
                 break
             max_out = int(counts.max())          # more survivors than rows: the reference keeps them all, so do we
+        self._last_kept = int(counts.sum())      # align_faces sizes its buffers from it
         return [(dets[b, :counts[b]].copy(), lms[b, :counts[b]].copy()) for b in range(B)]
+
+    # -- aligned face chips -------------------------------------------------------------------
+    def align_faces(self, size=112, *, max_faces=None, out="u8", rgb=False, mean=0.0, scale=1.0, template=None, max_per_image=0):
+        """Aligned chips of the faces the preceding ``decode_threshold`` kept (``cf_align_faces``): every face is warped from the
+        uint8 batch the network read onto ``template`` ([5][2] chip points; default the ArcFace 112 x 112 points times size / 112) by
+        the least-squares similarity of its five landmarks -- in network coordinates, whatever ``set_rescale`` says.  Returns
+        (chips [N,size,size,3] uint8 BGR, or [N,3,size,size] float32 = ``(u8 - mean) * scale`` with ``out='f32'``; offsets [B+1]:
+        the faces of image b are rows offsets[b]:offsets[b+1], in the decode's keep order; matrices [N,6] float64: the 2x3 chip ->
+        network-input maps, zero where a face could not be aligned).  ``max_faces`` caps N (offsets[-1] still tells the number
+        wanted); by default the buffers are sized from the decode's counts and grown if that was short."""
+        o, tm, shape, dtype = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
+        B = self.last_B
+        cap = int(getattr(self, "_last_kept", 0)) if max_faces is None else int(max_faces)
+        while True:
+            chips = np.empty((max(cap, 1),) + shape, dtype)
+            mats = np.empty((max(cap, 1), 6), np.float64)
+            offs = np.zeros((B + 1,), np.int32)
+            self._chk(self._L.cf_align_faces(self._h, C.byref(o), _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
+            if max_faces is not None or int(offs[-1]) <= cap:
+                break
+            cap = int(offs[-1])
+        n = min(int(offs[-1]), cap)
+        return chips[:n], offs, mats[:n]
+
+    def align_faces_device(self, chips_ptr, offsets_ptr, cap_faces, matrices_ptr=None, size=112, *, out="u8", rgb=False, mean=0.0,
+                           scale=1.0, template=None, max_per_image=0):
+        """Same, writing into caller-owned DEVICE buffers (chips for ``cap_faces`` faces, 16-byte aligned; offsets [B+1] int32;
+        matrices [cap_faces,6] float64 or None): asynchronous on the engine's main stream, no host read of the counts."""
+        o, tm, _, _ = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
+        self._chk(self._L.cf_align_faces(self._h, C.byref(o), C.c_void_p(int(chips_ptr)), C.c_void_p(int(matrices_ptr)) if matrices_ptr else None,
+                                         C.c_void_p(int(offsets_ptr)), int(cap_faces), 1))      # (the template is read during the call)
 
     # -- launch plan / layer trace (parity tests) ---------------------------------------------
     def plan(self):
@@ -645,6 +677,11 @@ class CenterFace(object):
         """Batched ``__call__`` (the shape of eval_widerface.get_detections, :76-90).  The reference's
         decode ignores ``threshold`` and uses 0.3 (centerface.py:77); so does this."""
         del threshold
+        return self._detect_chunks(imgs, lambda results: results)
+
+    def _detect_chunks(self, imgs, per_chunk):
+        """Forward + threshold decode of ``imgs`` in chunks of ``max_batch``; ``per_chunk(results)`` turns the postprocessed results of
+        a chunk (whose forward and decode are still the engine's last) into the items returned for it."""
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         direct = all(is_pinned(im) for im in imgs)                           # page-locked images: one DMA each, no host copy
         batch = imgs if direct else np.stack(imgs)                           # one common (h, w) per instance
@@ -660,10 +697,23 @@ class CenterFace(object):
                     self.engine.forward_enqueue(chunk)
                 else:
                     self.engine.forward_resized_enqueue(chunk)               # cv2.resize stand-in, on the device
-                out.extend(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True))
+                out.extend(per_chunk(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)))
         finally:
             self.engine.set_rescale(0.0, 0.0)
         return out
+
+    def detect_aligned(self, imgs, size=112, **chip_options):
+        """``detect_batch`` plus the aligned chip of every detection: one (dets, lms, chips) per image, dets / lms exactly those of
+        ``detect_batch`` (rescale included), chips[k] = the face of dets[k] warped onto the chip template from the network-sized
+        frame on the device (``Engine.align_faces``; ``chip_options``: out, rgb, mean, scale, template).  An image without
+        detections gives an empty [0, ...] chip array."""
+        if not self.landmarks:
+            raise ValueError("detect_aligned needs the landmarks: construct CenterFace(..., landmarks=True)")
+
+        def with_chips(results):
+            chips, offs, _ = self.engine.align_faces(size, **chip_options)
+            return [(d, l, chips[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(results)]
+        return self._detect_chunks(imgs, with_chips)
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]

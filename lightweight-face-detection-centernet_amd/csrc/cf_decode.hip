@@ -679,6 +679,11 @@ __global__ __launch_bounds__(64) void thresh_sweep_kernel(ThreshParams p) {
         const float c[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
         float* d = p.dets + ((size_t)b * p.max_out + pos) * 5;
         float* l = p.lms ? p.lms + ((size_t)b * p.max_out + pos) * 10 : nullptr;
+        if (p.lms_net) {
+            float* ln = p.lms_net + ((size_t)b * p.max_out + pos) * 10;
+#pragma unroll
+            for (int j = 0; j < 10; ++j) ln[j] = c[5 + j];
+        }
         if (p.rs_w > 0.f) {                        // centerface.py:55-62: x // scale_w, y // scale_h (exact floor of the quotient)
             const double sw = (double)p.rs_w, sh = (double)p.rs_h;
 #pragma unroll

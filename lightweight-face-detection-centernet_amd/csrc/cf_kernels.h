@@ -285,6 +285,7 @@ struct ThreshParams {
     int max_out;
     float* dets;          // [B][max_out][5]
     float* lms;           // [B][max_out][10] or nullptr
+    float* lms_net;       // optional [B][max_out][10]: the same rows in network coordinates whatever rs_h / rs_w say (cf_align_faces reads them)
     int* counts;          // [B]
     int* overflow;        // [1] largest candidate count seen when some image exceeded cap (else untouched)
     float rs_h, rs_w;     // > 0: emit floor(y / rs_h), floor(x / rs_w) (centerface.py:55-62); 0 = network coordinates
@@ -320,6 +321,33 @@ hipError_t launch_upload_images(hipStream_t s, const void* const* imgs, uint8_t*
 // and pitches multiples of 4
 hipError_t launch_yuv_to_bgr(hipStream_t s, int fmt, const void* const* planes, int B, int h, int w, int y_pitch, int c_pitch,
                              uint8_t* dst, int H, int W);
+
+// Aligned face chips (cf_align.hip): similarity estimate from five landmarks + fixed-point bilinear warp of the uint8 BGR batch,
+// one launch for every kept face of the batch.  Face n = off[b] + i (image b, keep position i), off = exclusive prefix sum of
+// min(counts[b], rows_cap, max_per_image); its landmark row is lms[b * lms_stride + i], or -- lms_stride == 0 -- row
+// (prefix sum of counts)[b] + i of a packed table.  Only faces n < cap_faces are written; offsets[B] = the number wanted.
+struct AlignParams {
+    const uint8_t* img;   // [B][H][W][3] uint8 BGR, 4-byte aligned
+    size_t img_dwords;    // readable dwords at img (>= B*H*W*3 / 4, rounded up)
+    int B, H, W;
+    const float* lms;     // landmark rows of 10 floats, network-input pixels
+    int lms_stride;       // rows per image, or 0 = packed
+    const int* counts;    // [B]
+    int rows_cap;         // rows the producer wrote per image at most
+    int max_per_image;    // 0 = all
+    int S, format, rgb;   // chip size; 0 = uint8 [N,S,S,3] BGR, 1 = float32 [N,3,S,S] ((u8 - mean) * scale; RGB planes when rgb)
+    float mean, scale;
+    double tmpl[10];      // template points in chip pixels
+    void* chips;          // 4-byte (uint8) / 16-byte (float) aligned
+    double* mats;         // [cap_faces][6] chip -> source, or nullptr
+    int* offsets;         // [B + 1] or nullptr
+    int cap_faces;
+};
+// chip options -> p (size, format, rgb, mean, scale, template: [5][2] floats or nullptr = ArcFace 112 points * S / 112); host only,
+// returns nullptr or what is wrong
+const char* align_params_set(AlignParams& p, int size, int format, int rgb, float mean, float scale, const float* tmpl, int max_per_image);
+size_t align_chip_bytes(int size, int format);
+hipError_t launch_align_faces(hipStream_t s, const AlignParams& p);
 
 // layout converters used by cf_get_heads and the per-op test entry points
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*T NHWC*/,

@@ -3,6 +3,8 @@
 // kernel in isolation against the oracle / the reference's golden vectors.  Layout conversion
 // NCHW<->NHWC happens on the device around the kernel; there is no CPU compute path here.
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -645,6 +647,41 @@ int cf_op_yuv_to_bgr(int device, int yuv_format, const uint8_t* frames, uint8_t*
     if (sc.err == hipSuccess) sc.chk(launch_yuv_to_bgr(sc.s, yuv_format, planes.data(), B, h, w, w, cw, out, H, W));
     if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(bgr, out, (size_t)B * H * W * 3, hipMemcpyDeviceToHost, sc.s));
     return sc.result("cf_op_yuv_to_bgr");
+}
+
+int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, const float* lms, const int32_t* counts,
+                      const cf_align_opts* o, void* chips, double* matrices) {
+    if (!imgs || !counts || !o || !chips || B < 1 || h < 1 || w < 2) {
+        g_op_error = "cf_op_align_faces: null images, counts, options or chips, B < 1, h < 1 or w < 2";
+        return CF_EINVAL;
+    }
+    AlignParams p{};
+    if (const char* why = align_params_set(p, o->size, o->format, o->rgb, o->mean, o->scale, o->tmpl, o->max_per_image)) {
+        g_op_error = std::string("cf_op_align_faces: ") + why;
+        return CF_EINVAL;
+    }
+    long long N = 0;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] < 0) { g_op_error = "cf_op_align_faces: negative count"; return CF_EINVAL; }
+        N += counts[b];
+    }
+    if (N > 0 && !lms) { g_op_error = "cf_op_align_faces: null landmarks"; return CF_EINVAL; }
+    if (N > (1 << 24)) { g_op_error = "cf_op_align_faces: more than 2^24 faces"; return CF_EINVAL; }
+    if (N == 0) return CF_OK;
+    Scope sc(device);
+    const size_t img_bytes = (size_t)B * h * w * 3, one = align_chip_bytes(o->size, o->format);
+    p.img = (const uint8_t*)sc.up(imgs, img_bytes); p.img_dwords = (img_bytes + 3) / 4;      // (Scope pads every allocation)
+    p.B = B; p.H = h; p.W = w;
+    p.lms = (const float*)sc.up(lms, (size_t)N * 10 * sizeof(float)); p.lms_stride = 0; p.rows_cap = INT_MAX;
+    p.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int));
+    p.chips = sc.alloc(one * N);
+    p.mats = matrices ? (double*)sc.alloc((size_t)N * 6 * sizeof(double)) : nullptr;
+    p.offsets = nullptr; p.cap_faces = (int)N;
+    if (sc.err == hipSuccess) sc.chk(launch_align_faces(sc.s, p));
+    const size_t n = o->max_per_image > 0 ? [&] { size_t t = 0; for (int b = 0; b < B; ++b) t += std::min(counts[b], o->max_per_image); return t; }() : (size_t)N;
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(chips, p.chips, one * n, hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess && matrices) sc.chk(hipMemcpyAsync(matrices, p.mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_align_faces");
 }
 
 }  // extern "C"

@@ -115,6 +115,12 @@ struct cf_ctx {
     bool thr_pending = false; int thr_mode = 0, thr_h = 0, thr_w = 0, thr_maxout = 0, thr_B = 0; float thr_score = 0.f, thr_nms = 0.f, thr_rs_h = 0.f, thr_rs_w = 0.f;
     int prio = 0;                      // stream priority class of the context's main / decode streams: -1 lowest, 0 normal, +1 highest
     float rs_h = 0.f, rs_w = 0.f;      // cf_set_rescale: the threshold decode floor-divides x by rs_w and y by rs_h (0 = off)
+    // cf_align_faces: what the last forward read (al_in: device address of the network input, al_fmt its format, al_slot the host-input
+    // staging slot it sits in or -1; al_in = nullptr once an upload may have replaced it), the network-coordinate landmark rows of the
+    // last threshold decode ([max_batch][t_maxout][10], written by the sweep kernel beside its outputs; al_rows = that decode's max_out,
+    // 0 = no decode behind the last forward) and the scratch of the host-output form
+    const void* al_in = nullptr; int al_fmt = -1, al_slot = -1, al_rows = 0; float* t_lmsnet = nullptr;
+    uint8_t* al_chips = nullptr; size_t al_chips_bytes = 0; double* al_mats = nullptr; int al_mats_cap = 0; int* al_off = nullptr;
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
     // input format, batch): the second forward with a key captures it, later ones replay it
     struct FwdGraph { const void* in; int fmt, B; hipGraphExec_t exec; bool broken; unsigned long long used; };
@@ -610,7 +616,8 @@ int cf_destroy(cf_ctx* c) {
     for (auto& b : c->bufs) if (b.p) hipFree(b.p);
     for (void* p : c->owned) hipFree(p);
     for (void* p : {(void*)c->src_stage, (void*)c->d_trans, (void*)c->hm_plane, (void*)c->keys, (void*)c->key_count, (void*)c->big, (void*)c->d_slot, (void*)c->d_dets, (void*)c->d_lms, (void*)c->d_inds, (void*)c->t_cand, (void*)c->t_count,
-                    (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow})
+                    (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow,
+                    (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off})
         if (p) hipFree(p);
     if (c->h_thr) hipHostFree(c->h_thr);
     if (c->ev_thr) hipEventDestroy(c->ev_thr);
@@ -1086,6 +1093,7 @@ hipError_t launch_plan_at(cf_ctx* c, size_t i, const void* net_in, int in_format
 int launch_all_ops(cf_ctx* c, const void* net_in, int in_format, int B) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
+    c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in_slot_used; c->al_rows = 0;      // what cf_align_faces samples
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -1191,6 +1199,7 @@ int cf_upload_images(cf_ctx* c, const void* const* imgs, int B, int h, int w) {
     for (int b = 0; b < B; ++b) if (!imgs[b]) return c->fail(CF_EINVAL, "cf_upload_images: image %d is a null pointer", b);
     HIPCHK(c, hipSetDevice(c->device));
     CF_FLUSH_LANE(c);
+    c->al_in = nullptr;                                     // the copies below may land in the slot the last forward read
     const size_t one = (size_t)h * w * 3;
     // page-locked images (device-visible, 16-byte aligned): ONE kernel reads them all over PCIe instead of one DMA command each
     std::vector<const void*> dev;
@@ -1466,10 +1475,12 @@ int cf_detect_topk(cf_ctx* c, const void* in, int in_format, int in_on_device, i
     return cf_decode_topk(c, K, 1, dets, lms, inds, out_on_device);
 }
 
-static void free_thresh_ws(cf_ctx* c) {
-    for (void* p : {(void*)c->t_cand, (void*)c->t_count, (void*)c->t_order, (void*)c->t_mask, (void*)c->t_counts, (void*)c->t_overflow})
+// keep_results: the per-image counts of the decode that just finished stay (cf_align_faces reads them beside the landmark rows)
+static void free_thresh_ws(cf_ctx* c, bool keep_results = false) {
+    for (void* p : {(void*)c->t_cand, (void*)c->t_count, (void*)c->t_order, (void*)c->t_mask, (void*)(keep_results ? nullptr : c->t_counts), (void*)c->t_overflow})
         if (p) hipFree(p);
-    c->t_cand = nullptr; c->t_count = nullptr; c->t_order = nullptr; c->t_mask = nullptr; c->t_counts = nullptr; c->t_overflow = nullptr;
+    c->t_cand = nullptr; c->t_count = nullptr; c->t_order = nullptr; c->t_mask = nullptr; c->t_overflow = nullptr;
+    if (!keep_results) { c->t_counts = nullptr; c->al_rows = 0; }
     c->t_cap = 0; c->t_B = 0;
 }
 // The suppression matrix is dense: cap x cap / 64 words per image.  The workspace is sized for the batch of the CURRENT call
@@ -1483,7 +1494,7 @@ static size_t thr_host_head(cf_ctx* c) { return (256 + (size_t)c->max_batch * si
 static int ensure_thresh_ws(cf_ctx* c, int max_out, int cap, int B) {
     if (c->t_cap < cap || c->t_B < B) {
         cap = std::max(cap, c->t_cap); B = std::max(B, c->t_B);
-        free_thresh_ws(c);
+        free_thresh_ws(c);                              // (also the counts an oversized decode left behind)
         const size_t mb = B, words = (cap + 63) / 64;
         hipError_t e = hipMalloc((void**)&c->t_cand, mb * cap * 16 * sizeof(float));
         if (e == hipSuccess) e = hipMalloc((void**)&c->t_count, mb * sizeof(int));
@@ -1502,6 +1513,8 @@ static int ensure_thresh_ws(cf_ctx* c, int max_out, int cap, int B) {
     if (c->t_maxout < max_out) {
         if (!c->t_host && c->t_dets) hipFree(c->t_dets);
         if (!c->t_host && c->t_lms) hipFree(c->t_lms);
+        if (c->t_lmsnet) hipFree(c->t_lmsnet);
+        c->t_lmsnet = nullptr; c->al_rows = 0;
         if (c->h_thr) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipHostFree(c->h_thr); }
         c->t_dets = nullptr; c->t_lms = nullptr; c->h_thr = nullptr; c->t_host = false; c->t_maxout = 0;
         const size_t nd = (size_t)c->max_batch * max_out * 5 * sizeof(float), nl = 2 * nd, head = thr_host_head(c);
@@ -1517,6 +1530,7 @@ static int ensure_thresh_ws(cf_ctx* c, int max_out, int cap, int B) {
             HIPCHK(c, hipMalloc((void**)&c->t_dets, nd));
             HIPCHK(c, hipMalloc((void**)&c->t_lms, nl));
         }
+        HIPCHK(c, hipMalloc((void**)&c->t_lmsnet, nl));
         c->t_maxout = max_out;
     }
     if (!c->ev_thr) HIPCHK(c, hipEventCreateWithFlags(&c->ev_thr, hipEventDisableTiming));
@@ -1543,11 +1557,12 @@ static int thresh_launch(cf_ctx* c, int mode, float score_thresh, float nms_thre
     p.img_h = img_h; p.img_w = img_w; p.score_thresh = score_thresh; p.nms_thresh = nms_thresh; p.cap = c->t_cap; p.mode = mode;
     p.cand = c->t_cand; p.cand_count = c->t_count; p.order = c->t_order; p.mask = c->t_mask;
     p.max_out = max_out; p.dets = c->t_dets; p.lms = c->t_lms; p.counts = c->t_counts; p.overflow = c->t_overflow;
-    p.rs_h = c->rs_h; p.rs_w = c->rs_w;
+    p.rs_h = c->rs_h; p.rs_w = c->rs_w; p.lms_net = c->t_lmsnet;
     if (c->t_host) { p.host_overflow = (int*)c->h_thr; p.host_counts = (int*)(c->h_thr + 256); }
     HIPCHK(c, hipMemsetAsync(c->t_overflow, 0, sizeof(int), c->stream));
     HIPCHK(c, launch_decode_threshold(c->stream, p));
     HIPCHK(c, hipEventRecord(c->ev_thr, c->stream));
+    c->al_rows = max_out;
     return CF_OK;
 }
 
@@ -1618,7 +1633,60 @@ int cf_decode_threshold_sized(cf_ctx* c, int mode, float score_thresh, float nms
                                             (size_t)rows * 10 * sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    if (thresh_mask_bytes(c->t_B, c->t_cap) > kThreshKeepBytes) free_thresh_ws(c);      // an oversized decode does not keep its workspace
+    if (thresh_mask_bytes(c->t_B, c->t_cap) > kThreshKeepBytes) free_thresh_ws(c, true);      // an oversized decode does not keep its workspace
+    return CF_OK;
+}
+
+// Aligned chips of the faces the last threshold decode kept (cf_align.hip): one launch on the stream that carried the decode, reading
+// the decode's device-side counts and network-coordinate landmark rows and the uint8 batch the forward read.
+int cf_align_faces(cf_ctx* c, const cf_align_opts* o, void* chips, double* matrices, int32_t* offsets, int cap_faces, int out_on_device) {
+    if (!c) return CF_EINVAL;
+    if (!o || !chips || !offsets) return c->fail(CF_EINVAL, "cf_align_faces: null options, chips or offsets");
+    if (cap_faces < 0) return c->fail(CF_EINVAL, "cf_align_faces: cap_faces=%d is negative", cap_faces);
+    AlignParams p{};
+    if (const char* why = align_params_set(p, o->size, o->format, o->rgb, o->mean, o->scale, o->tmpl, o->max_per_image))
+        return c->fail(CF_EINVAL, "cf_align_faces: %s", why);
+    if (out_on_device && (reinterpret_cast<uintptr_t>(chips) & 15)) return c->fail(CF_EINVAL, "cf_align_faces: device chips must be 16-byte aligned");
+    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_align_faces before cf_forward");
+    if (c->al_fmt != CF_IN_U8_HWC_BGR) return c->fail(CF_ESTATE, "cf_align_faces: the last forward read a float tensor, there is no uint8 batch to sample");
+    if (!c->al_in) return c->fail(CF_ESTATE, "cf_align_faces: an upload was started after the last forward, its input is gone");
+    if (c->al_rows < 1 || !c->t_lmsnet || !c->t_counts) return c->fail(CF_ESTATE, "cf_align_faces without a threshold decode of the last forward");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int B = c->last_B;
+    p.img = (const uint8_t*)c->al_in; p.img_dwords = (size_t)B * c->H * c->W * 3 / 4; p.B = B; p.H = c->H; p.W = c->W;     // H, W multiples of 32
+    p.lms = c->t_lmsnet; p.lms_stride = c->al_rows; p.rows_cap = c->al_rows; p.counts = c->t_counts; p.cap_faces = cap_faces;
+    const size_t one = align_chip_bytes(o->size, o->format);
+    if (out_on_device) {
+        p.chips = chips; p.mats = matrices; p.offsets = offsets;
+    } else {
+        const size_t need_bytes = std::max<size_t>(one * cap_faces, 16);
+        if (c->al_chips_bytes < need_bytes) {
+            if (c->al_chips) hipFree(c->al_chips);
+            c->al_chips = nullptr; c->al_chips_bytes = 0;
+            const hipError_t e = hipMalloc((void**)&c->al_chips, need_bytes);
+            if (e != hipSuccess) { (void)hipGetLastError(); return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_align_faces: %zu bytes of chips: %s", need_bytes, hipGetErrorString(e)); }
+            c->al_chips_bytes = need_bytes;
+        }
+        if (c->al_mats_cap < std::max(cap_faces, 1)) {
+            if (c->al_mats) hipFree(c->al_mats);
+            c->al_mats = nullptr; c->al_mats_cap = 0;
+            HIPCHK(c, hipMalloc((void**)&c->al_mats, (size_t)std::max(cap_faces, 1) * 6 * sizeof(double)));
+            c->al_mats_cap = std::max(cap_faces, 1);
+        }
+        if (!c->al_off) HIPCHK(c, hipMalloc((void**)&c->al_off, ((size_t)c->max_batch + 1) * sizeof(int)));
+        p.chips = c->al_chips; p.mats = matrices ? c->al_mats : nullptr; p.offsets = c->al_off;
+    }
+    HIPCHK(c, launch_align_faces(c->stream, p));
+    if (c->al_slot >= 0) HIPCHK(c, hipEventRecord(c->ev_slot_free[c->al_slot], c->stream));      // the staging slot has one more reader
+    if (out_on_device) return CF_OK;
+    HIPCHK(c, hipMemcpyAsync(offsets, c->al_off, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)std::min((int)offsets[B], cap_faces);
+    if (n > 0) {
+        HIPCHK(c, hipMemcpyAsync(chips, c->al_chips, n * one, hipMemcpyDeviceToHost, c->stream));
+        if (matrices) HIPCHK(c, hipMemcpyAsync(matrices, c->al_mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return CF_OK;
 }
 

@@ -164,6 +164,28 @@ def yuv_to_bgr(frames, fmt="nv12", size=None, device=0):
     return out[0] if one else out
 
 
+def align_faces(imgs, lms, counts, size=112, template=None, out="u8", rgb=False, mean=0.0, scale=1.0, device=0):
+    """Aligned face chips (``cf_op_align_faces``): imgs uint8 [B,h,w,3] BGR, lms [N,10] landmark rows (x0,y0,...,x4,y4 in image pixels),
+    image after image, counts [B] (N = their sum).  Every face is warped onto ``template`` ([5][2] chip points; default the ArcFace
+    112 x 112 points times size / 112) by the least-squares similarity of its landmarks.  Returns (chips, matrices): chips uint8
+    [N,size,size,3] BGR (``out='u8'``) or float32 [N,3,size,size] = ``(u8 - mean) * scale`` (``out='f32'``; RGB planes with ``rgb``),
+    matrices float64 [N,6] = the row-major 2x3 chip -> image maps (zero for faces that cannot be aligned)."""
+    x = np.ascontiguousarray(imgs, dtype=np.uint8)
+    if x.ndim != 4 or x.shape[3] != 3:
+        raise ValueError("images must be uint8 [B,h,w,3], got %s" % (x.shape,))
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    lms = np.ascontiguousarray(lms, dtype=np.float32).reshape(-1, 10)
+    if counts.shape[0] != x.shape[0] or (counts < 0).any() or int(counts.sum()) != lms.shape[0]:
+        raise ValueError("counts must be [B] non-negative and sum to the number of landmark rows")
+    o, tm, shape, dtype = _lib.align_opts(size, out, rgb, mean, scale, template)
+    N = lms.shape[0]
+    chips = np.zeros((N,) + shape, dtype)
+    mats = np.zeros((N, 6), np.float64)
+    _lib.check(_lib.lib().cf_op_align_faces(device, ptr(x), x.shape[0], x.shape[1], x.shape[2], ptr(lms), ptr(counts), C.byref(o),
+                                            ptr(chips), ptr(mats)), op=True)
+    return chips, mats
+
+
 def ctdet_decode(heat, wh, reg=None, K=100, lm=None, device=0):
     """ctdet_decode (centerface_ext.py:52-82): (dets [B,K,6], lms [B,K,10]|None, inds [B,K] int64)."""
     heat, wh, reg, lm = f32(heat), f32(wh), f32(reg), f32(lm)

@@ -405,6 +405,9 @@ int cf_memcpy_d2h(cf_ctx* ctx, void* dst, const void* src, uint64_t bytes);
 
 /* ---- per-op entry points (tests; host pointers; NCHW float32 like the torch ops they replace) */
 const char* cf_op_last_error(void);      /* text of the last failing cf_op_* call on this thread */
+/* Demangled symbol (as rocprofv3 prints it) of the kernel the last cf_op_* call on this thread selected; the layout converters
+ * around it set none, so after cf_op_pwconv it names the GEMM instance.  Lets a test assert WHICH variant it checked. */
+const char* cf_op_last_kernel(void);
 /* ConvReLU depthwise / ShuffleV2 dw: pad -> conv2d(groups=C, bias=False) -> act.
  * x [B,C,H,W], w [C,1,k,k], y [B,C,Ho,Wo]; pad_lo/pad_hi as ZeroPad2d (model/centernet.py:63,68-70;
  * model/blocks.py:28); act: 0 none, 1 swish.  bias may be NULL (folded BN shift, blocks.py:29).
@@ -415,6 +418,13 @@ int cf_op_dwconv(int device, int dtype, const float* x, const float* w, const fl
  * (model/centernet.py:109-110,117-118,134-137,179-184; blocks.py:22-24,31-33). act 0/1 swish/2 relu */
 int cf_op_pwconv(int device, int dtype, const float* x, const float* w, const float* bias,
                  const float* residual, float* y, int B, int Cin, int Cout, int H, int W, int act);
+/* The same with the kernel's pixel-block addressing ([m / 32][C / P][m % 32][P], P channels per 16 bytes, buffers padded to whole
+ * 32-pixel blocks as the engine's are) switched on per operand: layout bit 0 = x, bit 1 = y, bit 2 = residual.  The caller still
+ * passes and receives NCHW float32; the reordering happens on the device around the kernel.  layout = 0 is cf_op_pwconv.
+ * Unknown bits, or bit 2 without a residual: CF_EINVAL before any GPU work.  The output is filled with 0xFF bytes before the
+ * launch, so an element the kernel does not write comes back as NaN. */
+int cf_op_pwconv_ex(int device, int dtype, const float* x, const float* w, const float* bias,
+                    const float* residual, float* y, int B, int Cin, int Cout, int H, int W, int act, int layout);
 /* MBConvBlock.forward, se=False (model/centernet.py:89-140) as ONE fused kernel: x [B,Cin,H,W],
  * w_exp [hid,Cin], w_dw [hid,1,k,k], w_proj [Cout,hid]; residual when Cin==Cout and stride==1.
  * Returns CF_EINVAL for shapes the fused kernel does not cover (t == 1, Cout > 96). */

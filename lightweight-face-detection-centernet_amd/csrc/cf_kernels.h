@@ -353,6 +353,7 @@ hipError_t launch_align_faces(hipStream_t s, const AlignParams& p);
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*T NHWC*/,
                                int B, int C, int H, int W);
 hipError_t launch_blocked_to_nchw(hipStream_t s, int dtype, const void* src /*pixel-block order*/, float* dst /*f32 NCHW*/, int B, int C, int H, int W);
+hipError_t launch_nchw_to_blocked(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*pixel-block order, whole 32-pixel blocks*/, int B, int C, int H, int W);
 hipError_t launch_nhwc_to_nchw(hipStream_t s, int dtype, const void* src /*T NHWC*/, float* dst /*f32 NCHW*/,
                                int B, int C, int H, int W);
 

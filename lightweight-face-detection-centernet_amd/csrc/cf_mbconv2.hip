@@ -208,9 +208,12 @@ __global__ __launch_bounds__(NW * 64) void mbconv_px_kernel(MbParams p) {
         const unsigned off = ((unsigned)cy * (unsigned)p.Win + (unsigned)cx) * rowbytes + (unsigned)(h * JX * 16);
 #pragma unroll
         for (int j = 0; j < JX; ++j) {
+            // Cin = 24: the upper half's second chunk lies past the pixel's row (the next pixel's, or past x for the last one); its
+            // weights are zero, but 0 * NaN is NaN, so whatever was read there is dropped like a padding pixel's
+            const bool vj = valid && (h * JX + j) * 8 < p.Cin;
             const u32x4 v = ld16(xbase + off + j * 16);
-            xf[t][j].x = valid ? v.x : 0u; xf[t][j].y = valid ? v.y : 0u;
-            xf[t][j].z = valid ? v.z : 0u; xf[t][j].w = valid ? v.w : 0u;
+            xf[t][j].x = vj ? v.x : 0u; xf[t][j].y = vj ? v.y : 0u;
+            xf[t][j].z = vj ? v.z : 0u; xf[t][j].w = vj ? v.w : 0u;
         }
     }
 

@@ -36,7 +36,9 @@ struct Scope {
         if (err != hipSuccess) return nullptr;
         void* p = nullptr;
         err = hipMalloc(&p, bytes + 256);
-        if (err == hipSuccess) { ptrs.push_back(p); hipMemsetAsync(p, 0, bytes + 256, s); }
+        // zeroed body; the tail pad (kernels with clamped loads may read a few bytes past a buffer) holds 0xFF bytes, a NaN in every
+        // storage type, so that a read past the end shows in the result instead of meeting whatever the allocator held
+        if (err == hipSuccess) { ptrs.push_back(p); if (bytes) hipMemsetAsync(p, 0, bytes, s); hipMemsetAsync((char*)p + bytes, 0xFF, 256, s); }
         return p;
     }
     void* up(const void* host, size_t bytes) {
@@ -53,6 +55,25 @@ struct Scope {
         void* dst = alloc(n * elem_size(dtype));
         if (err == hipSuccess) chk(launch_nchw_to_nhwc(s, dtype, src, dst, B, C, H, W));
         return dst;
+    }
+    // host f32 NCHW -> device T in pixel-block order [m / 32][C / P][m % 32][P], padded to whole 32-pixel blocks as the engine's buffers are
+    void* to_blocked(int dtype, const float* host, int B, int C, int H, int W) {
+        size_t n = (size_t)B * C * H * W;
+        float* src = (float*)up(host, n * 4);
+        void* dst = alloc(blocked_bytes(dtype, B, C, H, W));
+        if (err == hipSuccess) chk(launch_nchw_to_blocked(s, dtype, src, dst, B, C, H, W));
+        return dst;
+    }
+    static size_t blocked_bytes(int dtype, int B, int C, int H, int W) {
+        return (((size_t)B * H * W + 31) / 32 * 32) * C * elem_size(dtype);
+    }
+    // device T pixel-block order -> host f32 NCHW
+    void blocked_to_host_nchw(int dtype, const void* dev, float* host, int B, int C, int H, int W) {
+        size_t n = (size_t)B * C * H * W;
+        float* tmp = (float*)alloc(n * 4);
+        if (err == hipSuccess) chk(launch_blocked_to_nchw(s, dtype, dev, tmp, B, C, H, W));
+        if (err == hipSuccess) chk(hipMemcpyAsync(host, tmp, n * 4, hipMemcpyDeviceToHost, s));
+        if (err == hipSuccess) chk(hipStreamSynchronize(s));
     }
     // device T NHWC -> host f32 NCHW
     void to_host_nchw(int dtype, const void* dev, float* host, int B, int C, int H, int W) {
@@ -100,6 +121,7 @@ std::vector<float> make_records(const float* hm, const float* wh, const float* r
 extern "C" {
 
 const char* cf_op_last_error(void) { return g_op_error.c_str(); }
+const char* cf_op_last_kernel(void) { return last_kernel_tag(); }
 
 // Page-locked host memory without a context (hipHostMalloc, portable: every device may DMA from it): what cfa.pinned_empty hands out.
 int cf_pinned_alloc(uint64_t bytes, void** hptr) {
@@ -174,22 +196,32 @@ int cf_op_dwconv(int device, int dtype, const float* x, const float* w, const fl
     return sc.result("cf_op_dwconv");
 }
 
-int cf_op_pwconv(int device, int dtype, const float* x, const float* w, const float* bias,
-                 const float* residual, float* y, int B, int Cin, int Cout, int H, int W, int act) {
-    if (bad_dtype(dtype) || !x || !w || !y || (Cin % 8) || (Cout % 8) || act < 0 || act > 2) return CF_EINVAL;
+int cf_op_pwconv_ex(int device, int dtype, const float* x, const float* w, const float* bias,
+                    const float* residual, float* y, int B, int Cin, int Cout, int H, int W, int act, int layout) {
+    if (bad_dtype(dtype) || !x || !w || !y || act < 0 || act > 2) return CF_EINVAL;
+    if ((Cin % 8) || (Cout % 8)) { g_op_error = "cf_op_pwconv: Cin and Cout must be multiples of 8"; return CF_EINVAL; }
+    if ((layout & ~7) || ((layout & 4) && !residual)) { g_op_error = "cf_op_pwconv_ex: unknown layout bits, or a pixel-block residual without a residual"; return CF_EINVAL; }
     Scope sc(device);
     std::vector<char> packed(pw_packed_bytes(dtype, Cin, Cout));
     pw_pack_weights(dtype, w, Cin, Cout, packed.data());
     PwParams p{};
-    p.x = sc.to_nhwc(dtype, x, B, Cin, H, W);
+    p.xblock = layout & 1; p.yblock = (layout >> 1) & 1; p.resblock = (layout >> 2) & 1;
+    p.x = p.xblock ? sc.to_blocked(dtype, x, B, Cin, H, W) : sc.to_nhwc(dtype, x, B, Cin, H, W);
     p.wp = sc.up(packed.data(), packed.size());
     p.bias = bias ? (const float*)sc.up(bias, (size_t)Cout * 4) : nullptr;
-    p.res = residual ? sc.to_nhwc(dtype, residual, B, Cout, H, W) : nullptr;
-    p.y = sc.alloc((size_t)B * H * W * Cout * elem_size(dtype));
+    p.res = !residual ? nullptr : p.resblock ? sc.to_blocked(dtype, residual, B, Cout, H, W) : sc.to_nhwc(dtype, residual, B, Cout, H, W);
+    const size_t ybytes = p.yblock ? Scope::blocked_bytes(dtype, B, Cout, H, W) : (size_t)B * H * W * Cout * elem_size(dtype);
+    p.y = sc.alloc(ybytes);
+    if (sc.err == hipSuccess) sc.chk(hipMemsetAsync(p.y, 0xFF, ybytes, sc.s));      // an element the kernel skips comes back as NaN
     p.M = (long long)B * H * W; p.K = Cin; p.N = Cout; p.act = act; p.Ho = H; p.Wo = W;      // the map size picks the kernel (cf_pw.hip)
     if (sc.err == hipSuccess) sc.chk(launch_pw(sc.s, dtype, p));
-    sc.to_host_nchw(dtype, p.y, y, B, Cout, H, W);
+    if (p.yblock) sc.blocked_to_host_nchw(dtype, p.y, y, B, Cout, H, W);
+    else sc.to_host_nchw(dtype, p.y, y, B, Cout, H, W);
     return sc.result("cf_op_pwconv");
+}
+int cf_op_pwconv(int device, int dtype, const float* x, const float* w, const float* bias,
+                 const float* residual, float* y, int B, int Cin, int Cout, int H, int W, int act) {
+    return cf_op_pwconv_ex(device, dtype, x, w, bias, residual, y, B, Cin, Cout, H, W, act, 0);
 }
 
 int cf_op_mbconv(int device, int dtype, const float* x, const float* w_exp, const float* w_dw,

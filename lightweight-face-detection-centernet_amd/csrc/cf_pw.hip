@@ -84,10 +84,13 @@ __global__ __launch_bounds__(256) void pw_kernel(PwParams p) {
     // x rows [m][K], or pixel-block order [m / 32][K / 8][m % 32][8] (xblock): consecutive 16-byte chunks of a pixel are then
     // 512 bytes apart and the 32 lanes of a wave half read one contiguous 512-byte run
     const size_t xs = p.xblock ? 512 : 16;
-    const char* xrow = p.xblock ? (const char*)p.x + (((size_t)pb * NC + (size_t)h * NCh) * 32 + pl) * 16
-                                : (const char*)p.x + (size_t)mr * p.K * sizeof(T) + (size_t)h * NCh * 16;
-    const char* wbase = (const char*)p.wp + ((size_t)nb0 * NCh * 64 + lane) * 16;
     const int jmax = (h == 0) ? NCh : NC - NCh;               // valid chunks of this half
+    // a half that owns no chunk at all (NC = 1: bf16 with K = 8) starts at chunk 0 as well: the clamped index below keeps every
+    // load inside this half's share only if the share is not empty, and h * NCh is then past the pixel's row (past x for the last one)
+    const size_t c0 = jmax > 0 ? (size_t)h * NCh : 0;
+    const char* xrow = p.xblock ? (const char*)p.x + (((size_t)pb * NC + c0) * 32 + pl) * 16
+                                : (const char*)p.x + (size_t)mr * p.K * sizeof(T) + c0 * 16;
+    const char* wbase = (const char*)p.wp + ((size_t)nb0 * NCh * 64 + lane) * 16;
 
     f32x16 acc[NBW];
 #pragma unroll

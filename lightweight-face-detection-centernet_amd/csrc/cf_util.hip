@@ -128,6 +128,23 @@ __global__ void blocked_to_nchw_kernel(const T* src, float* dst, int B, int C, i
         else dst[i] = bf16_to_f32(v);
     }
 }
+// NCHW float32 -> pixel-block order (the inverse of blocked_to_nchw_kernel); dst holds whole 32-pixel blocks, the pixels past
+// B H W of the last one are left as the caller filled them
+template <typename T>
+__global__ void nchw_to_blocked_kernel(const float* src, T* dst, int B, int C, int H, int W) {
+    constexpr int P = 16 / (int)sizeof(T);
+    const long long n = (long long)B * C * H * W;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        int x = (int)(i % W); long long t = i / W;
+        int y = (int)(t % H); t /= H;
+        int c = (int)(t % C); int b = (int)(t / C);
+        const size_t m = ((size_t)b * H + y) * W + x;
+        const float v = src[i];
+        T* d = dst + (((m >> 5) * (size_t)(C / P) + (size_t)(c / P)) * 32 + (m & 31)) * P + (c % P);
+        if constexpr (sizeof(T) == 4) *d = v;
+        else *d = (T)(pack_bf16x2(v, 0.0f) & 0xffffu);
+    }
+}
 static unsigned conv_grid(long long n) { long long g = (n + 255) / 256; return (unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
 
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src, void* dst, int B, int C, int H, int W) {
@@ -142,6 +159,13 @@ hipError_t launch_blocked_to_nchw(hipStream_t s, int dtype, const void* src, flo
     if (n == 0) return hipSuccess;
     if (dtype != 1) hipLaunchKernelGGL(blocked_to_nchw_kernel<float>, dim3(conv_grid(n)), dim3(256), 0, s, (const float*)src, dst, B, C, H, W);
     else hipLaunchKernelGGL(blocked_to_nchw_kernel<bf16_t>, dim3(conv_grid(n)), dim3(256), 0, s, (const bf16_t*)src, dst, B, C, H, W);
+    return hipGetLastError();
+}
+hipError_t launch_nchw_to_blocked(hipStream_t s, int dtype, const float* src, void* dst, int B, int C, int H, int W) {
+    long long n = (long long)B * C * H * W;
+    if (n == 0) return hipSuccess;
+    if (dtype != 1) hipLaunchKernelGGL(nchw_to_blocked_kernel<float>, dim3(conv_grid(n)), dim3(256), 0, s, src, (float*)dst, B, C, H, W);
+    else hipLaunchKernelGGL(nchw_to_blocked_kernel<bf16_t>, dim3(conv_grid(n)), dim3(256), 0, s, src, (bf16_t*)dst, B, C, H, W);
     return hipGetLastError();
 }
 hipError_t launch_nhwc_to_nchw(hipStream_t s, int dtype, const void* src, float* dst, int B, int C, int H, int W) {

@@ -27,15 +27,21 @@ def conv_dw(x, w, k, stride, pad=None, act="swish", bias=None, dtype="fp32", dev
     return y
 
 
-def conv_pw(x, w, act="none", bias=None, residual=None, dtype="fp32", device=0):
-    """1x1 Conv2d [+bias] [+act] [+residual] (model/centernet.py:109-110,117-118,134-137)."""
+def last_kernel():
+    """Demangled symbol of the kernel the last op call on this thread selected (cf_op_last_kernel)."""
+    return (_lib.lib().cf_op_last_kernel() or b"").decode()
+
+
+def conv_pw(x, w, act="none", bias=None, residual=None, dtype="fp32", device=0, layout=0):
+    """1x1 Conv2d [+bias] [+act] [+residual] (model/centernet.py:109-110,117-118,134-137).  ``layout``: bit 0 / 1 / 2 = the
+    kernel addresses x / y / the residual in pixel-block order (cf_op_pwconv_ex; arrays here stay NCHW either way)."""
     x = f32(x)
     w = f32(np.asarray(w).reshape(w.shape[0], -1))
     B, Cin, H, W = x.shape
     Cout = w.shape[0]
     y = np.empty((B, Cout, H, W), np.float32)
-    _lib.check(_lib.lib().cf_op_pwconv(device, _DT[dtype], ptr(x), ptr(w), ptr(f32(bias)), ptr(f32(residual)),
-                                       ptr(y), B, Cin, Cout, H, W, {"none": 0, "swish": 1, "relu": 2}[act]), op=True)
+    _lib.check(_lib.lib().cf_op_pwconv_ex(device, _DT[dtype], ptr(x), ptr(w), ptr(f32(bias)), ptr(f32(residual)),
+                                          ptr(y), B, Cin, Cout, H, W, {"none": 0, "swish": 1, "relu": 2}[act], int(layout)), op=True)
     return y
 
 

@@ -50,6 +50,25 @@ def test_argument_validation_happens_before_any_gpu_work():
     assert L.cf_create(0, 1, 64, 64, 7, 0, ctypes.byref(h)) == -1         # unknown dtype
 
 
+def test_pwconv_test_hooks_are_declared_exported_and_validate_first():
+    """The hooks tests/test_pw_sweep.py stands on: ``cf_op_last_kernel`` (which instance ran) and ``cf_op_pwconv_ex`` (pixel-block
+    addressing per operand); unknown layout bits, or a pixel-block residual without a residual, are CF_EINVAL before any GPU work."""
+    L = cfa._lib.lib()
+    declared = _declared_symbols()
+    for name in ("cf_op_last_kernel", "cf_op_pwconv_ex"):
+        assert name in declared and name in cfa._lib.EXPORTS and hasattr(L, name), name
+    assert isinstance(cfa.ops.last_kernel(), str)
+    x, w, y = np.zeros((1, 8, 4, 4), np.float32), np.zeros((8, 8), np.float32), np.zeros((1, 8, 4, 4), np.float32)
+    p = cfa._lib.ptr
+    for layout in (8, -1, 4, 5, 1 << 20):                  # 4 / 5: residual bit, no residual
+        assert L.cf_op_pwconv_ex(0, 0, p(x), p(w), None, None, p(y), 1, 8, 8, 4, 4, 0, layout) == -1, layout
+        assert L.cf_op_last_error()
+    assert L.cf_op_pwconv_ex(0, 0, p(x), p(w), None, None, p(y), 1, 12, 8, 4, 4, 0, 0) == -1      # Cin % 8
+    with pytest.raises(ValueError) as e:
+        cfa.ops.conv_pw(x, w, layout=8)
+    assert isinstance(e.value, cfa._lib.CenterFaceError) and e.value.code == -1 and "layout" in str(e.value)
+
+
 def test_schema_matches_reference_checkpoint_layout():
     sch = cfa.schema.state_dict_schema()
     assert len(sch) == 94

@@ -427,10 +427,18 @@ int cf_op_pwconv_ex(int device, int dtype, const float* x, const float* w, const
                     const float* residual, float* y, int B, int Cin, int Cout, int H, int W, int act, int layout);
 /* MBConvBlock.forward, se=False (model/centernet.py:89-140) as ONE fused kernel: x [B,Cin,H,W],
  * w_exp [hid,Cin], w_dw [hid,1,k,k], w_proj [Cout,hid]; residual when Cin==Cout and stride==1.
- * Returns CF_EINVAL for shapes the fused kernel does not cover (t == 1, Cout > 96). */
+ * Returns CF_EINVAL for shapes the fused kernel does not cover (t == 1, Cout > 96, Cin > 96, a hid no serving family's hidden
+ * chunk divides -- in bf16 that includes hid = 32 / 96 at Cin >= 56: cf_op_mbconv_pick tells), before any GPU work.  Like cf_op_pwconv_ex,
+ * cf_op_mbconv / cf_op_expand_dw / cf_op_dwconv fill the output with 0xFF bytes before the launch: a skipped element is a NaN. */
 int cf_op_mbconv(int device, int dtype, const float* x, const float* w_exp, const float* w_dw,
                  const float* w_proj, float* y, int B, int Cin, int hid, int Cout, int H, int W,
                  int k, int stride);
+/* Which kernel family and table row cf_op_mbconv / cf_op_expand_dw (and the engine) would pick for a block shape: the geometry
+ * function only, no device, no launch.  out = {ok, kind (MbKind: 0 tile, 1 px, 2 expdw px, 4 expdw mx, 5 mx, 6 mx2, 7 f32,
+ * 8 expdw f32, 9 sp), HC, nq, JX, NBO, HALF, KG}; ok = 0 (and CF_OK) for a shape the entry point refuses.  CF_EINVAL only for an
+ * unknown dtype or a null out. */
+int cf_op_mbconv_pick(int dtype, int Cin, int hid, int Cout, int k, int stride, int out[8]);
+int cf_op_expand_dw_pick(int dtype, int Cin, int hid, int k, int stride, int out[8]);
 /* The first two thirds of MBConvBlock.forward (model/centernet.py:109-114): expand 1x1 + Swish, depthwise
  * k x k (stride, `_get_padding`) + Swish, as ONE kernel (bf16 storage only; the path the engine uses for
  * the blocks whose Cout is too wide to fuse the project conv as well).  y [B,hid,Ho,Wo].

@@ -165,9 +165,9 @@ __global__ __launch_bounds__(NW * 64) void mbconv_kernel(MbParams p) {
     // This wave's input-tile pixel blocks (ib = wave + NW * t) -> X fragments, loaded ONCE: the input
     // tile is the same for every hidden chunk.  Branch-free: always load from a clamped (valid)
     // address, then zero what lies outside the image (= ZeroPad2d) -- predicated loads would each
-    // end in a full vmcnt(0) wait.  A row whose 16-byte chunk count is odd is over-read by one chunk
-    // on the h = 1 half: the matching weight fragment is zero and activation buffers are
-    // zero-initialised with slack, so it is inert.
+    // end in a full vmcnt(0) wait.  A row whose 16-byte chunk count is odd (bf16 only) is over-read by one
+    // chunk on the h = 1 half: the matching weight fragment is zero and the chunk is zeroed with the
+    // padding pixels (what lies there may be a NaN, and 0 * NaN is NaN).
     constexpr int MAXI = (NIB + NW - 1) / NW;
     u32x4 xf[MAXI][JX];
 #pragma unroll
@@ -183,8 +183,10 @@ __global__ __launch_bounds__(NW * 64) void mbconv_kernel(MbParams p) {
 #pragma unroll
         for (int j = 0; j < JX; ++j) {
             const u32x4 v = ld16(xbase + off + j * 16);
-            xf[t][j].x = valid ? v.x : 0u; xf[t][j].y = valid ? v.y : 0u;
-            xf[t][j].z = valid ? v.z : 0u; xf[t][j].w = valid ? v.w : 0u;
+            bool vj = valid;
+            if constexpr (sizeof(T) == 2) vj = valid && (h * JX + j) * 8 < p.Cin;      // bf16, odd chunk count: the over-read chunk is dropped (0 * NaN is NaN)
+            xf[t][j].x = vj ? v.x : 0u; xf[t][j].y = vj ? v.y : 0u;
+            xf[t][j].z = vj ? v.z : 0u; xf[t][j].w = vj ? v.w : 0u;
         }
         // split mode (round 5): split into bf16 (hi, lo) ONCE, here, not once per hidden chunk inside the MFMA chain (a chunk pair ->
         // [8 x hi], [8 x lo]; an odd last chunk -> [4 x hi | 4 x lo]): the same products in the same order
@@ -466,6 +468,11 @@ MbGeom mb_geometry(int dtype, int Cin, int hid, int Cout, int k, int s) {
 #include CF_EXP_INC(cf_mbconv_m7_geometry)
     if (dtype == 2 && mb6_geometry(dtype, g, Cin, hid, Cout, k, s)) return g;     // round 5: register-window depthwise (cf_mbconv6.hip)
     if (dtype != 1 && mb4_geometry(dtype, g, Cin, hid, Cout, k, s)) return g;
+    // bf16 storage: this file's own instances keep the expanded tile as bf16 / fp32 and the taps as fp32 -- other rounding points than the
+    // bf16 mode's (fp16 tile, fp16 taps: oracle/bf16_emulation.py), up to 4.7 bounds off the emulation (profiles/mbconv_sweep_parity.md).  They
+    // are the A/B baseline of an experiments build (CF_MB_KIND=0), not a silent fallback for a hid the fp16-tile families' HC does not divide:
+    // no network block has such a hid, and the shape is refused (the engine would run it as expand+dw + GEMM or as three launches)
+    if (dtype == 1 && cf_ab_int("CF_MB_KIND", 1) != 0) return g;
     g.JX = (Cin * sz / 16 + 1) / 2;
     g.NBO = (Cout + 31) / 32;
     const MbEntry* e = mb_find(dtype, k, s, g.JX, g.NBO, (Cin == Cout && s == 1) ? 1 : 0);

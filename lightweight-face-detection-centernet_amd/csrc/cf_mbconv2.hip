@@ -543,10 +543,14 @@ __global__ __launch_bounds__((Xd<KS, S, HC, TOH, TOW, JX>::NW) * 64) void expdw_
         }
         return ip < IPX && (unsigned)gy < (unsigned)p.Hin && (unsigned)gx < (unsigned)p.Win;
     };
+    // an odd chunk count (Cin = 56, 88, 152): the upper half's last chunk lies past the pixel's row (the next pixel's, or past x for the
+    // last one); its weights are zero, but 0 * NaN is NaN, so it is dropped like a padding pixel's
+    const bool last_in = (h * JX + JX - 1) * 8 < p.Cin;
     auto mask_x = [&](u32x4* xf, bool valid) {
 #pragma unroll
         for (int j = 0; j < JX; ++j) {
-            xf[j].x = valid ? xf[j].x : 0u; xf[j].y = valid ? xf[j].y : 0u; xf[j].z = valid ? xf[j].z : 0u; xf[j].w = valid ? xf[j].w : 0u;
+            const bool vj = j == JX - 1 ? (valid && last_in) : valid;
+            xf[j].x = vj ? xf[j].x : 0u; xf[j].y = vj ? xf[j].y : 0u; xf[j].z = vj ? xf[j].z : 0u; xf[j].w = vj ? xf[j].w : 0u;
         }
     };
     u32x4 xa[JX];

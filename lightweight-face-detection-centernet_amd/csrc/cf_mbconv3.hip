@@ -114,10 +114,14 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
         }
         return ip < IPX && (unsigned)gy < (unsigned)p.Hin && (unsigned)gx < (unsigned)p.Win;
     };
+    // an odd chunk count (Cin = 56, 88, 152): the upper half's last chunk lies past the pixel's row (the next pixel's, or past x for the
+    // last one); its weights are zero, but 0 * NaN is NaN, so it is dropped like a padding pixel's
+    const bool last_in = (h * JX + JX - 1) * 8 < p.Cin;
     auto mask_x = [&](u32x4* xf, bool valid) {
 #pragma unroll
         for (int j = 0; j < JX; ++j) {
-            xf[j].x = valid ? xf[j].x : 0u; xf[j].y = valid ? xf[j].y : 0u; xf[j].z = valid ? xf[j].z : 0u; xf[j].w = valid ? xf[j].w : 0u;
+            const bool vj = j == JX - 1 ? (valid && last_in) : valid;
+            xf[j].x = vj ? xf[j].x : 0u; xf[j].y = vj ? xf[j].y : 0u; xf[j].z = vj ? xf[j].z : 0u; xf[j].w = vj ? xf[j].w : 0u;
         }
     };
 #ifdef CF_ABLATION
@@ -953,6 +957,7 @@ bool mx_fused_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
     g.rowb = 32 * 8 + 16;
     g.lds_bytes = (size_t)e->lds_bytes;
     g.wexp_bytes = (size_t)g.nq * g.JX * 1024 + (tail ? 1024 : 0);
+    if (g.nq == 0) g.wexp_bytes = (size_t)g.JX * 1024;      // hid = 16, the tail round alone: the kernel still prefetches one full round's worth
     g.wdw_floats = ((size_t)g.nq * 2 + (tail ? 1 : 0)) * k * 2 * 64 * 2;
     g.wproj_bytes = (size_t)g.nq * nmb * 1024 + (tail ? (size_t)nmb * 512 : 0);
     return true;
@@ -1063,6 +1068,7 @@ bool mx_fused2_geometry(MbGeom& g, int Cin, int hid, int Cout, int k, int s) {
     g.rowb = 32 * 8 + 16;
     g.lds_bytes = (size_t)e->lds_bytes;
     g.wexp_bytes = (size_t)g.nq * g.JX * 1024 + (tail ? 1024 : 0);
+    if (g.nq == 0) g.wexp_bytes = (size_t)g.JX * 1024;      // hid = 16, the tail round alone: the kernel still prefetches one full round's worth
     g.wdw_floats = ((size_t)g.nq * 2 + (tail ? 1 : 0)) * k * 3 * 64 * 2;
     g.wproj_bytes = (size_t)g.nq * 2 * nmb * 512 + (tail ? (size_t)nmb * 512 : 0);
     return true;

@@ -106,11 +106,18 @@ __global__ __launch_bounds__(NW * 64, MW) void mbconv6_kernel(MbParams p) {
             const int gy = oy0 * S - p.pad_lo + iy, gx = ox0 * S - p.pad_lo + ix;
             xsv[t] = ip < IPX && (unsigned)gy < (unsigned)p.Hin && (unsigned)gx < (unsigned)p.Win;
             const int cy = min(max(gy, 0), p.Hin - 1), cx = min(max(gx, 0), p.Win - 1);
-            // half h reads the row's chunks h JH .. h JH + JX - 1 (JH = real chunks per half; a padded slot meets zero weights)
-            const unsigned off = ((unsigned)cy * (unsigned)p.Win + (unsigned)cx) * rowbytes + (unsigned)(h * ((p.Cin / 4 + 1) / 2) * 16);
+            // half h reads the row's chunks h JH .. h JH + JX - 1 (JH = real chunks per half).  A padded slot (Cin = 24: j = 3) meets zero
+            // weights, but what it read is the other half's chunk or, on the upper half, lies past the row (past x for the last pixel),
+            // and 0 * NaN is NaN: it is dropped
+            const int JH = (p.Cin / 4 + 1) / 2;
+            const unsigned off = ((unsigned)cy * (unsigned)p.Win + (unsigned)cx) * rowbytes + (unsigned)(h * JH * 16);
             u32x4 raw[JX];
 #pragma unroll
-            for (int j = 0; j < JX; ++j) raw[j] = ld16(xbase + off + j * 16);
+            for (int j = 0; j < JX; ++j) {
+                const u32x4 v = ld16(xbase + off + j * 16);
+                const bool pj = j < JH;
+                raw[j].x = pj ? v.x : 0u; raw[j].y = pj ? v.y : 0u; raw[j].z = pj ? v.z : 0u; raw[j].w = pj ? v.w : 0u;
+            }
 #pragma unroll
             for (int j = 0; j < JX; j += 2) { const SplitPair sp2 = split8(raw[j], raw[j + 1]); xs[t][j] = sp2.hi; xs[t][j + 1] = sp2.lo; }
         }
@@ -325,7 +332,7 @@ static const M6Entry* m6_find(int k, int s, int jx, int res) {
 }
 
 // JX is padded to an even chunk count per lane half (chunk pairs): Cin = 24 has three 16-byte chunks per half, the fourth is zero
-// weights against a clamped re-read (mb6_pack zeroes the fragment)
+// weights (mb6_pack zeroes the fragment) against a zeroed operand (the kernel drops what the padded slot read)
 static int m6_jx(int Cin) { const int j = (Cin * 4 / 16 + 1) / 2; return (j + 1) & ~1; }
 
 bool mb6_geometry(int dtype, MbGeom& g, int Cin, int hid, int Cout, int k, int s) {

@@ -189,7 +189,9 @@ int cf_op_dwconv(int device, int dtype, const float* x, const float* w, const fl
     p.x = sc.to_nhwc(dtype, x, B, C, H, W);
     p.w = sc.upv(wp);
     p.bias = bias ? (const float*)sc.up(bias, (size_t)C * 4) : nullptr;
-    p.y = sc.alloc((size_t)B * Ho * Wo * C * elem_size(dtype));
+    const size_t ybytes = (size_t)B * Ho * Wo * C * elem_size(dtype);
+    p.y = sc.alloc(ybytes);
+    if (sc.err == hipSuccess) sc.chk(hipMemsetAsync(p.y, 0xFF, ybytes, sc.s));      // an element the kernel skips comes back as NaN
     p.B = B; p.C = C; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.k = k; p.s = stride; p.pad_lo = pad_lo; p.act = act;
     if (sc.err == hipSuccess) sc.chk(launch_dw(sc.s, dtype, p));
     sc.to_host_nchw(dtype, p.y, y, B, C, Ho, Wo);
@@ -237,7 +239,9 @@ int cf_op_mbconv(int device, int dtype, const float* x, const float* w_exp, cons
     mb_pack_weights(dtype, g, Cin, hid, Cout, k, w_exp, w_dw, w_proj, we.data(), wd.data(), wp.data());
     MbParams p{};
     p.x = sc.to_nhwc(dtype, x, B, Cin, H, W);
-    p.y = sc.alloc((size_t)B * Ho * Wo * Cout * elem_size(dtype));
+    const size_t ybytes = (size_t)B * Ho * Wo * Cout * elem_size(dtype);
+    p.y = sc.alloc(ybytes);
+    if (sc.err == hipSuccess) sc.chk(hipMemsetAsync(p.y, 0xFF, ybytes, sc.s));      // an element the kernel skips comes back as NaN
     p.wexp = sc.up(we.data(), we.size()); p.wdw = sc.upv(wd); p.wproj = sc.up(wp.data(), wp.size());
     p.B = B; p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.Cin = Cin; p.hid = hid; p.Cout = Cout;
     p.k = k; p.s = stride; p.pad_lo = pd / 2; p.residual = (Cin == Cout && stride == 1) ? 1 : 0;
@@ -265,6 +269,23 @@ int cf_op_mbconv(int device, int dtype, const float* x, const float* w_exp, cons
     return sc.result("cf_op_mbconv");
 }
 
+// The geometry functions alone (no device, no launch): which family and table row a block shape lands on.
+static int pick_out(const MbGeom& g, int out[8]) {
+    const int v[8] = {g.ok ? 1 : 0, (int)g.kind, g.HC, g.nq, g.JX, g.NBO, g.HALF, g.KG};
+    for (int i = 0; i < 8; ++i) out[i] = g.ok ? v[i] : 0;
+    return CF_OK;
+}
+int cf_op_mbconv_pick(int dtype, int Cin, int hid, int Cout, int k, int stride, int out[8]) {
+    if (bad_dtype(dtype) || !out) return CF_EINVAL;
+    MbGeom g = mb_geometry(dtype, Cin, hid, Cout, k, stride);
+    if (hid == Cin) g.ok = false;
+    return pick_out(g, out);
+}
+int cf_op_expand_dw_pick(int dtype, int Cin, int hid, int k, int stride, int out[8]) {
+    if (bad_dtype(dtype) || !out) return CF_EINVAL;
+    return pick_out(expdw_geometry(dtype, Cin, hid, k, stride), out);
+}
+
 int cf_op_expand_dw(int device, int dtype, const float* x, const float* w_exp, const float* w_dw, float* y,
                     int B, int Cin, int hid, int H, int W, int k, int stride) {
     if (bad_dtype(dtype) || !x || !w_exp || !w_dw || !y || B < 1) return CF_EINVAL;
@@ -278,7 +299,9 @@ int cf_op_expand_dw(int device, int dtype, const float* x, const float* w_exp, c
     mb_pack_weights(dtype, g, Cin, hid, hid, k, w_exp, w_dw, nullptr, we.data(), wd.data(), nullptr);
     MbParams p{};
     p.x = sc.to_nhwc(dtype, x, B, Cin, H, W);
-    p.y = sc.alloc((size_t)B * Ho * Wo * hid * elem_size(dtype));
+    const size_t ybytes = (size_t)B * Ho * Wo * hid * elem_size(dtype);
+    p.y = sc.alloc(ybytes);
+    if (sc.err == hipSuccess) sc.chk(hipMemsetAsync(p.y, 0xFF, ybytes, sc.s));      // an element the kernel skips comes back as NaN
     p.wexp = sc.up(we.data(), we.size()); p.wdw = sc.upv(wd);
     p.B = B; p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.Cin = Cin; p.hid = hid; p.Cout = hid;
     p.k = k; p.s = stride; p.pad_lo = pd / 2;

@@ -78,6 +78,31 @@ def expand_dw(x, w_exp, w_dw, k, stride, dtype="bf16", device=0):
     return y
 
 
+_PICK = ("ok", "kind", "HC", "nq", "JX", "NBO", "HALF", "KG")
+MB_KINDS = {0: "MB_TILE", 1: "MB_PX", 2: "XD_PX", 4: "XD_MX", 5: "MB_MX", 6: "MB_MX2", 7: "MB_F32", 8: "XD_F32", 9: "MB_SP"}
+
+
+def _pick(code, out):
+    _lib.check(code, op=True)
+    d = dict(zip(_PICK, (int(v) for v in out)))
+    d["ok"] = bool(d["ok"])
+    d["kind"] = MB_KINDS.get(d["kind"], d["kind"]) if d["ok"] else None
+    return d
+
+
+def mbconv_pick(Cin, hid, Cout, k, stride, dtype="fp32"):
+    """What ``mbconv`` would run for a block shape, from the geometry function alone (cf_op_mbconv_pick: no GPU needed):
+    {ok, kind (family name), HC, nq, JX, NBO, HALF, KG}; ok = False for a shape ``mbconv`` refuses."""
+    out = (C.c_int * 8)()
+    return _pick(_lib.lib().cf_op_mbconv_pick(_DT[dtype], Cin, hid, Cout, k, stride, out), out)
+
+
+def expand_dw_pick(Cin, hid, k, stride, dtype="bf16"):
+    """The same for ``expand_dw`` (cf_op_expand_dw_pick)."""
+    out = (C.c_int * 8)()
+    return _pick(_lib.lib().cf_op_expand_dw_pick(_DT[dtype], Cin, hid, k, stride, out), out)
+
+
 def stem(x, w, dtype="fp32", device=0):
     """first_conv (model/centernet.py:224): x uint8 [B,H,W,3] BGR (normalisation fused) or float32 [B,3,H,W]."""
     x = np.ascontiguousarray(x)

@@ -10,6 +10,8 @@ import pytest
 
 import centerface_amd as cfa
 
+import mbconv_cases as M
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -67,6 +69,159 @@ def test_pwconv_test_hooks_are_declared_exported_and_validate_first():
     with pytest.raises(ValueError) as e:
         cfa.ops.conv_pw(x, w, layout=8)
     assert isinstance(e.value, cfa._lib.CenterFaceError) and e.value.code == -1 and "layout" in str(e.value)
+
+
+# ------------------------------------------------------------------------------- the MBConv sweep's GPU-less half
+_HIDS = (16, 32, 48, 64, 96, 144, 192, 384, 576, 960)
+_DTYPES = ("fp32", "fp32_split", "bf16")
+
+
+def _pick(c):
+    _, dtype, Cin, hid, Cout, k, s = c[:7]
+    return cfa.ops.expand_dw_pick(Cin, hid, k, s, dtype) if Cout == 0 else cfa.ops.mbconv_pick(Cin, hid, Cout, k, s, dtype)
+
+
+def _assert_lands_where_claimed(c, short, g):
+    """The geometry's answer for case c against what the tag ``short`` says about its table row."""
+    _, dtype, Cin, hid, Cout, k, s = c[:7]
+    if short == "REFUSED":
+        assert not g["ok"], (c[0], g)
+        return
+    assert g["ok"], (c[0], "refused")
+    claim = M.claimed(short)
+    have = dict(kind=g["kind"], k=k, s=s, JX=g["JX"], HC=g["HC"], nbo=(Cout + 31) // 32, res=int(Cin == Cout and s == 1), tail=int(hid % 32 == 16))
+    wrong = {n: (v, have[n]) for n, v in claim.items() if have[n] != v}
+    assert not wrong, (c[0], short, wrong)
+    assert g["nq"] == hid // g["HC"] and (hid % g["HC"] == 0 or (claim.get("tail") and hid % 32 == 16)), (c[0], g)
+
+
+def test_mbconv_pick_hooks_are_declared_exported_and_need_no_gpu():
+    """``cf_op_mbconv_pick`` / ``cf_op_expand_dw_pick``: the geometry functions alone.  Production shapes land where DESIGN.md says."""
+    L = cfa._lib.lib()
+    declared = _declared_symbols()
+    for name in ("cf_op_mbconv_pick", "cf_op_expand_dw_pick"):
+        assert name in declared and name in cfa._lib.EXPORTS and hasattr(L, name), name
+    out = (ctypes.c_int * 8)()
+    assert L.cf_op_mbconv_pick(7, 16, 96, 24, 3, 2, out) == -1 and L.cf_op_mbconv_pick(0, 16, 96, 24, 3, 2, None) == -1
+    assert L.cf_op_expand_dw_pick(-1, 96, 576, 5, 2, out) == -1
+    g = cfa.ops.mbconv_pick(16, 96, 24, 3, 2, "bf16")
+    assert g == dict(ok=True, kind="MB_PX", HC=32, nq=3, JX=1, NBO=1, HALF=g["HALF"], KG=g["KG"])
+    assert cfa.ops.mbconv_pick(32, 192, 32, 5, 1, "fp32_split")["kind"] == "MB_SP"
+    assert cfa.ops.expand_dw_pick(160, 960, 3, 1, "bf16")["kind"] == "XD_MX" and cfa.ops.expand_dw_pick(96, 576, 5, 2, "fp32_split")["HALF"] == 18
+    assert cfa.ops.mbconv_pick(32, 32, 32, 5, 1, "fp32") == dict(ok=False, kind=None, HC=0, nq=0, JX=0, NBO=0, HALF=0, KG=0)
+
+
+def test_mbconv_sweep_table_is_well_formed():
+    assert len(set(M.IDS)) == len(M.IDS) >= 150
+    for c in M.CASES:
+        cid, dtype, Cin, hid, Cout, k, s, H, W, tag, alt = c
+        assert dtype in _DTYPES and 1 <= M.out_size(H, k, s) <= 45 and 1 <= M.out_size(W, k, s) <= 45, cid
+        for t in (tag, alt):
+            if t not in (None, "REFUSED"):
+                assert M.family(t) in cfa.ops.MB_KINDS.values() and (Cout == 0) == M.family(t).startswith("XD_"), cid
+                assert M.full_tag(t, dtype).startswith("void cf::") and " T," not in M.full_tag(t, dtype), cid
+
+
+def test_mbconv_sweep_covers_every_group_of_accepted_shapes():
+    """Every block shape the two geometry functions accept, grouped by the table row that serves it -- (dtype, family, k, s, JX,
+    n-blocks, residual, tail, HC): each group has a case in the sweep's table, and each case is accepted and lands on the row its
+    tag names.  A new table row, or a retuned HC, without cases of its own fails here, without a GPU."""
+    groups = {}
+    for dtype in _DTYPES:
+        for k in (3, 5):
+            for s in (1, 2):
+                for Cin in range(8, 161, 8):
+                    for hid in _HIDS:
+                        g = cfa.ops.expand_dw_pick(Cin, hid, k, s, dtype)
+                        if g["ok"]:
+                            groups.setdefault(M.group_key(dtype, g, Cin, hid, 0, k, s), (Cin, hid, 0))
+                        for Cout in range(8, 97, 8):
+                            g = cfa.ops.mbconv_pick(Cin, hid, Cout, k, s, dtype)
+                            if g["ok"]:
+                                groups.setdefault(M.group_key(dtype, g, Cin, hid, Cout, k, s), (Cin, hid, Cout))
+    assert len(groups) >= 40
+    covered = set()
+    for c in M.CASES:
+        g = _pick(c)
+        _assert_lands_where_claimed(c, c[9], g)
+        if g["ok"]:
+            covered.add(M.group_key(c[1], g, c[2], c[3], c[4], c[5], c[6]))
+    missing = {key: first for key, first in groups.items() if key not in covered}
+    assert not missing, "groups of accepted shapes without a sweep case (key: first member (Cin, hid, Cout)): %s" % missing
+    assert {key[1] for key in covered} == set(cfa.ops.MB_KINDS.values())          # all nine families
+
+
+@pytest.mark.parametrize("name,value", [("CF_DW_MATRIX", "0"), ("CF_F4_VARIANT", "1")])
+def test_mbconv_sweep_switch_column_matches_the_geometry(name, value):
+    """The switches are read once per process: a child asks the geometry functions with the switch set, and every case must land
+    where the table's last column says (None: where it lands without the switch)."""
+    import json
+    import subprocess
+    import sys
+    code = ("import json, sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_abi as T, mbconv_cases as M; "
+            "print(json.dumps([T._pick(c) for c in M.CASES]))" % (REPO, os.path.join(REPO, "tests")))
+    env = dict(os.environ)
+    env[name] = value
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    picks = json.loads(r.stdout.strip().splitlines()[-1])
+    moved = 0
+    for c, g in zip(M.CASES, picks):
+        if M.SWITCH[c[1]] != (name, value):
+            continue
+        _assert_lands_where_claimed(c, M.short_tag(c, {name: value}), g)
+        moved += c[10] is not None
+    assert moved >= 20
+    families = {M.family(c[10]) for c in M.CASES if M.SWITCH[c[1]] == (name, value) and c[10] not in (None, "REFUSED")}
+    assert families >= ({"MB_PX", "XD_PX"} if name == "CF_DW_MATRIX" else {"MB_F32"})
+
+
+def test_mbconv_refusals_need_no_gpu():
+    """Shapes no family serves are CF_EINVAL before a device is opened (this machine may have none), with a message, and the
+    output buffer is not touched."""
+    L, p = cfa._lib.lib(), cfa._lib.ptr
+    rng = np.random.default_rng(0)
+    for what, (dtype, Cin, hid, Cout, k, s) in M.REFUSED.items():
+        x = rng.standard_normal((1, Cin, 5, 6)).astype(np.float32)
+        we, wd, wp = M.weights(rng, Cin, hid, Cout, k)
+        y = np.full((1, Cout or hid, 5, 6), 7.0, np.float32)
+        dt = cfa.ops._DT[dtype]
+        if Cout == 0:
+            assert not cfa.ops.expand_dw_pick(Cin, hid, k, s, dtype)["ok"], what
+            code = L.cf_op_expand_dw(0, dt, p(x), p(we), p(wd), p(y), 1, Cin, hid, 5, 6, k, s)
+        else:
+            assert not cfa.ops.mbconv_pick(Cin, hid, Cout, k, s, dtype)["ok"], what
+            code = L.cf_op_mbconv(0, dt, p(x), p(we), p(wd), p(wp), p(y), 1, Cin, hid, Cout, 5, 6, k, s)
+        assert code == -1 and L.cf_op_last_error() and (y == 7.0).all(), what
+        with pytest.raises(cfa._lib.CenterFaceValueError):
+            cfa.ops.expand_dw(x, we, wd, k, s, dtype=dtype) if Cout == 0 else cfa.ops.mbconv(x, we, wd, wp, k, s, dtype=dtype)
+
+
+def test_float64_mbconv_restatement_matches_the_oracle_on_the_production_shapes():
+    """``mbconv_cases.ref64`` (the sweep's fp32 / fp32_split reference) against ``O.mbconv``, the pinned float32 oracle, on the
+    eight fused block shapes (hid = 6 Cin, production Cout): float32 round-off of the oracle's own sums and nothing else."""
+    import torch
+    from oracle import centerface_oracle as O
+    done = 0
+    for prefix, cin, cout, t, k, s in O.blocks_table():
+        if t == 1 or cout > 96:
+            continue
+        rng = np.random.default_rng(cin * 100 + cout)
+        we, wd, wp = M.weights(rng, cin, cin * t, cout, k)
+        x = rng.standard_normal((2, cin, 9, 12)).astype(np.float32)
+        sd = {prefix + ".conv.0.1.weight": torch.from_numpy(we.reshape(cin * t, cin, 1, 1)), prefix + ".conv.1.1.weight": torch.from_numpy(wd),
+              prefix + ".conv.2.weight": torch.from_numpy(wp.reshape(cout, cin * t, 1, 1))}
+        ref = O.mbconv(torch.from_numpy(x), sd, prefix, cin, cout, t, k, s).numpy()
+        got = M.ref64(x, we, wd, wp, k, s)
+        assert got.shape == ref.shape == (2, cout, M.out_size(9, k, s), M.out_size(12, k, s))
+        # the oracle's float32 sums: <= 576 terms of O(1/sqrt(n)) each, eps 6e-8 -> a few 1e-6 on O(1) outputs
+        np.testing.assert_allclose(ref, got, rtol=2e-5, atol=2e-5, err_msg=prefix)
+        d = M.ref64(x, we, wd, None, k, s)
+        assert d.shape == (2, cin * t, ref.shape[2], ref.shape[3])
+        dref = O.conv_swish(O.conv_swish(torch.from_numpy(x), sd[prefix + ".conv.0.1.weight"], 1, 1), sd[prefix + ".conv.1.1.weight"], k, s, groups=cin * t).numpy()
+        np.testing.assert_allclose(dref, d, rtol=2e-5, atol=2e-5, err_msg=prefix + " expand+dw")
+        done += 1
+    assert done == 8
 
 
 def test_schema_matches_reference_checkpoint_layout():

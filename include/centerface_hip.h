@@ -137,6 +137,7 @@ int cf_forward_uploaded(cf_ctx* ctx);
 #define CF_YUV_NV21 1            /* Y plane, then one interleaved V,U plane */
 #define CF_YUV_I420 2            /* Y, U, V planes (yuv420p: what software decoders emit) */
 #define CF_YUV_YV12 3            /* Y, V, U planes */
+#define CF_FRAME_BGR 4           /* uint8 [h,w,3] BGR rows: with CF_YUV_* the one `format` integer of cf_redact_faces (not a cf_forward_yuv format) */
 typedef struct cf_yuv_planes {
     const void* y;               /* h rows of y_pitch bytes */
     const void* c0;              /* first chroma plane in the format's order: NV12 / NV21 the interleaved plane, I420 U, YV12 V
@@ -247,6 +248,58 @@ typedef struct cf_align_opts {
  * work; CF_ESTATE without a threshold decode behind the last forward, after a CF_IN_F32_NCHW forward, or once another upload or
  * forward was started on ctx. */
 int cf_align_faces(cf_ctx* ctx, const cf_align_opts* opts, void* chips, double* matrices, int32_t* offsets, int cap_faces, int out_on_device);
+
+/* ---- face redaction: blank or pixelate every kept face IN THE SOURCE FRAME, on the device ------------------------------------ */
+/* Anonymising video: every face the detector kept is covered in the full-resolution frame -- BGR or 4:2:0, a decoder's surface in
+ * place -- and the frame goes on to an encoder; no box and no pixel crosses to the host.  The arithmetic is this library's own
+ * statement (csrc/cf_redact.hip, restated in tests/test_redact.py; device and restatement are equal bit for bit).  Integers
+ * throughout, except the box mapping: float64 in the order written, no FMA contraction.
+ *   Per face: box (x1, y1, x2, y2) float32 in NETWORK coordinates (as the threshold decode computed it, BEFORE cf_set_rescale),
+ *   frame h x w, context H x W, options below.
+ *   1. Box to frame.  cx = ((double)x1 + (double)x2) * 0.5;  hw = ((double)x2 - (double)x1) * 0.5 * (double)scale;
+ *      fx = (double)w / (double)W;  X1 = floor((cx - hw) * fx), X2 = ceil((cx + hw) * fx); likewise y with h / H.  The face is
+ *      skipped when one of the four inputs is not finite or hw / hh is not > 0.  Each result is clamped to [-8192, 16384] as a
+ *      double, converted to int, then X1, Y1 are rounded DOWN to even and X2, Y2 UP to even (every format: a mask means the same
+ *      pixels in BGR and in 4:2:0).  Frames are at most 8192 a side, so no int64 product below overflows.
+ *   2. Coverage, in half-pixel units: a BGR pixel / luma sample (x, y) has the point (U, V) = (2x+1, 2y+1), a chroma sample (i, j)
+ *      the point (4i+2, 4j+2).  RECT: 2*X1 <= U < 2*X2 and 2*Y1 <= V < 2*Y2.  ELLIPSE: A = X2-X1, Bv = Y2-Y1, du = U-(X1+X2),
+ *      dv = V-(Y1+Y2): (du*Bv)^2 + (dv*A)^2 <= (A*Bv)^2 in int64.  Only samples inside the frame are written; a sample is redacted
+ *      when ANY face of its image covers it.
+ *   3. Value.  SOLID: fill[channel].  MOSAIC: the grid is anchored at the FRAME origin: cell (gx, gy) of a BGR / luma plane is
+ *      [gx*m, min((gx+1)*m, w)) x [gy*m, min((gy+1)*m, h)), of a chroma plane the same index with m/2, w/2, h/2 (the two interleaved
+ *      channels of NV12 / NV21 separately); its value is (sum + n/2) / n over ALL n samples of the cell in the frame AS IT WAS BEFORE
+ *      THE CALL, per channel, and a covered sample takes its cell's value -- so the result depends neither on the order of the faces
+ *      nor on their overlap.  On the device: one launch that only reads the frame writes the means of every cell a face's clipped
+ *      box touches into a scratch of one entry per cell, a second launch only writes covered samples.
+ * Bytes outside the masks -- pitch padding, the corners of an ELLIPSE box -- are not written at all. */
+#define CF_REDACT_SOLID   0
+#define CF_REDACT_MOSAIC  1
+#define CF_REDACT_RECT    0
+#define CF_REDACT_ELLIPSE 1
+typedef struct cf_planes_rw {
+    void* p0;                    /* BGR: the [h][pitch0] pixel rows; 4:2:0: the Y plane */
+    void* p1;                    /* 4:2:0: first chroma plane in the format's order (as cf_yuv_planes.c0), h/2 rows of pitch1 bytes; BGR: unused */
+    void* p2;                    /* I420 / YV12: second chroma plane; otherwise unused */
+} cf_planes_rw;
+typedef struct cf_redact_opts {
+    int32_t mode;                /* CF_REDACT_SOLID | CF_REDACT_MOSAIC */
+    int32_t shape;               /* CF_REDACT_RECT | CF_REDACT_ELLIPSE */
+    int32_t cell;                /* MOSAIC: m, even, 2 <= m <= 256 (ignored for SOLID) */
+    float   scale;               /* the box is grown about its centre by this factor, 0.25 <= scale <= 4 */
+    uint8_t fill[4];             /* SOLID: bytes in the frame's own channel order (B,G,R or Y,U,V); [3] unused */
+} cf_redact_opts;
+/* Redacts, in frames[b] (b < B, all h x w in `format`: CF_YUV_* or CF_FRAME_BGR), the faces that the LAST THRESHOLD DECODE of the last
+ * forward of ctx kept for image b: rows i < min(counts[b], the decode's max_out), as cf_align_faces.  The frames are named by the
+ * caller, so it does not matter which entry point fed the forward (a CF_IN_F32_NCHW forward is fine: the input batch is not read).
+ * pitch0 >= 3w (BGR) or >= w (Y), pitch1 as c_pitch of cf_forward_yuv (ignored for BGR), in bytes.
+ * on_device = 1: in place on the caller's device planes (addresses and pitches multiples of 4), asynchronous on the stream that
+ * carried the decode, no count is read on the host; on_device = 0: host frames are copied up, redacted and copied back, blocking.
+ * B must equal the last forward's batch.  CF_EINVAL, before any GPU work, for: format / mode / shape out of range, an odd or
+ * out-of-range cell (MOSAIC), scale out of range or not finite, odd h or w for 4:2:0, h or w of 0 or above 8192, a pitch that is too
+ * small, a misaligned device plane or pitch, a NULL required plane.  CF_ESTATE without a threshold decode behind the last forward, or
+ * once another upload or forward was started on ctx. */
+int cf_redact_faces(cf_ctx* ctx, const cf_redact_opts* opts, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
+                    int pitch0, int pitch1);
 
 /* ---- fused convenience: forward + D3 decode in one enqueue (eval_widerface.py:76-90 shape) -- */
 int cf_detect_topk(cf_ctx* ctx, const void* in, int in_format, int in_on_device, int B, int K,
@@ -503,6 +556,10 @@ int cf_op_yuv_to_bgr(int device, int yuv_format, const uint8_t* frames, uint8_t*
  * image after image, counts [B] (>= 0, N = their sum): chips [N] in opts->format, matrices [N,6] float64 (may be NULL). */
 int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, const float* lms, const int32_t* counts,
                       const cf_align_opts* opts, void* chips, double* matrices);
+/* The kernels of cf_redact_faces alone, on host frames (modified in place): boxes [sum counts][4] x1,y1,x2,y2 in the coordinates of an
+ * H x W network input, image after image, counts [B] (>= 0).  The same validation as cf_redact_faces, before any device is touched. */
+int cf_op_redact(int device, const cf_redact_opts* opts, int format, const cf_planes_rw* host_frames, int B, int h, int w, int pitch0,
+                 int pitch1, const float* boxes, const int32_t* counts, int H, int W);
 /* CenterFace.nms alone (centerface.py:111-151): keep[] receives kept indices in keep order. */
 int cf_op_nms(int device, const float* boxes, const float* scores, int n, float nms_thresh,
               int32_t* keep, int32_t* n_keep);

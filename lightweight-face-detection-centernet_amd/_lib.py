@@ -22,6 +22,12 @@ CF_YUV_NV12, CF_YUV_NV21, CF_YUV_I420, CF_YUV_YV12 = 0, 1, 2, 3
 CF_CHIP_U8_HWC_BGR, CF_CHIP_F32_NCHW = 0, 1
 CHIP_FORMATS = {"u8": CF_CHIP_U8_HWC_BGR, "uint8": CF_CHIP_U8_HWC_BGR, "f32": CF_CHIP_F32_NCHW, "float32": CF_CHIP_F32_NCHW}
 CF_ESTATE = -4
+# cf_redact_faces / cf_op_redact: CF_FRAME_BGR continues the CF_YUV_* numbering (one `format` integer for both families)
+CF_FRAME_BGR = 4
+CF_REDACT_SOLID, CF_REDACT_MOSAIC = 0, 1
+CF_REDACT_RECT, CF_REDACT_ELLIPSE = 0, 1
+REDACT_MODES = {"solid": CF_REDACT_SOLID, "mosaic": CF_REDACT_MOSAIC}
+REDACT_SHAPES = {"rect": CF_REDACT_RECT, "ellipse": CF_REDACT_ELLIPSE}
 YUV_FORMATS = {"nv12": CF_YUV_NV12, "nv21": CF_YUV_NV21, "i420": CF_YUV_I420, "yuv420p": CF_YUV_I420, "yv12": CF_YUV_YV12}
 
 # every symbol include/centerface_hip.h declares (checked by tests/test_abi.py)
@@ -32,7 +38,7 @@ EXPORTS = (
     "cf_profile_forward", "cf_plan_size", "cf_plan_op", "cf_forward_trace", "cf_graph_stats", "cf_get_streams", "cf_streams_share_queue", "cf_streams_share_queue_ex", "cf_spread_streams", "cf_reroll_streams", "cf_ctdet_loss", "cf_comm_unique_id", "cf_comm_create", "cf_comm_create_all", "cf_comm_create_loopback", "cf_comm_loopback_rank", "cf_comm_destroy", "cf_comm_abort", "cf_comm_query", "cf_comm_synchronize", "cf_comm_last_error", "cf_comm_debug", "cf_comm_set_shard", "cf_comm_stream", "cf_gather_topk", "cf_host_alloc", "cf_host_free", "cf_pinned_alloc", "cf_pinned_free", "cf_host_register", "cf_host_unregister", "cf_device_alloc", "cf_device_free", "cf_memcpy_h2d", "cf_memcpy_d2h",
     "cf_op_last_error", "cf_op_last_kernel", "cf_op_shufflev2", "cf_op_mbconv", "cf_op_expand_dw", "cf_op_mbconv_pick", "cf_op_expand_dw_pick", "cf_op_ctdet_loss", "cf_op_encode_targets", "cf_op_dwconv", "cf_op_pwconv", "cf_op_pwconv_ex", "cf_op_stem", "cf_op_idaup", "cf_op_heads",
     "cf_op_ctdet_decode", "cf_op_ctdet_post_process", "cf_op_decode_threshold", "cf_op_decode_threshold_ex", "cf_op_nms", "cf_op_box_match",
-    "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces",
+    "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces", "cf_redact_faces", "cf_op_redact",
 )
 
 
@@ -81,6 +87,127 @@ def align_opts(size=112, out="u8", rgb=False, mean=0.0, scale=1.0, template=None
     o = AlignOpts(S, fmt, 1 if rgb else 0, float(mean), float(scale), tm.ctypes.data if tm is not None else None, int(max_per_image))
     shape, dtype = ((3, S, S), np.float32) if fmt == CF_CHIP_F32_NCHW else ((S, S, 3), np.uint8)
     return o, tm, shape, dtype
+
+
+class PlanesRW(C.Structure):
+    """cf_planes_rw: the writable planes of one frame (BGR: p0 only; 4:2:0: Y, then the chroma planes in the format's order)."""
+    _fields_ = [("p0", C.c_void_p), ("p1", C.c_void_p), ("p2", C.c_void_p)]
+
+
+class RedactOpts(C.Structure):
+    """cf_redact_opts: mode / shape / mosaic cell / box scale / fill bytes in the frame's channel order."""
+    _fields_ = [("mode", C.c_int32), ("shape", C.c_int32), ("cell", C.c_int32), ("scale", C.c_float), ("fill", C.c_uint8 * 4)]
+
+
+def redact_opts(mode="mosaic", shape="ellipse", cell=20, scale=1.3, fill=(0, 0, 0)):
+    """RedactOpts from names ('solid' | 'mosaic', 'rect' | 'ellipse'); integer codes pass through (the library validates them, like
+    the cell and the scale).  ``fill``: three bytes in the frame's own channel order (B,G,R or Y,U,V)."""
+    def code(v, table, what):
+        if isinstance(v, str):
+            if v.lower() not in table:
+                raise ValueError("unknown redaction %s %r (one of %s)" % (what, v, sorted(table)))
+            return table[v.lower()]
+        return int(v)
+    fill = [int(v) for v in fill]
+    if len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
+        raise ValueError("fill must be three bytes in the frame's channel order, got %r" % (fill,))
+    return RedactOpts(code(mode, REDACT_MODES, "mode"), code(shape, REDACT_SHAPES, "shape"), int(cell), float(scale), (C.c_uint8 * 4)(*fill, 0))
+
+
+def frame_format(fmt):
+    """The `format` integer of cf_redact_faces: 'bgr' -> CF_FRAME_BGR, otherwise as ``yuv_format``."""
+    if isinstance(fmt, str) and fmt.lower() == "bgr":
+        return CF_FRAME_BGR
+    return yuv_format(fmt)
+
+
+def frame_planes(frames, fmt):
+    """Host frames of ``Engine.redact_faces`` / ``ops.redact_faces`` as (PlanesRW table, B, h, w, pitch0, pitch1, arrays to keep alive):
+    BGR uint8 [B,h,w,3]; 4:2:0 uint8 [B, h*3//2, w] (OpenCV's dense layout) or a list of such [h*3//2, w] frames; or a list of per-frame
+    plane tuples of uint8 2-D arrays (rows of bytes; one common shape and row stride per plane; BGR: one [h, 3w] or [h,w,3] array).  The arrays are written in place,
+    so nothing is copied here: a frame that is not writable or whose rows are not contiguous is refused."""
+    f = frame_format(fmt)
+    bgr, il = f == CF_FRAME_BGR, f in (CF_YUV_NV12, CF_YUV_NV21)
+
+    def rows_of(a, what):
+        a = a if isinstance(a, np.ndarray) else np.asarray(a)
+        if a.dtype != np.uint8 or a.ndim < 2 or not a.flags["WRITEABLE"]:
+            raise ValueError("%s must be a writable uint8 array, got %s %s" % (what, a.dtype, a.shape))
+        if a.ndim == 3:
+            if a.strides[1:] != (a.shape[2], 1):
+                raise ValueError("%s: the pixels of a row must be contiguous" % what)
+            return a, a.shape[0], a.shape[1] * a.shape[2], a.strides[0]
+        if a.ndim != 2 or a.strides[1] != 1:
+            raise ValueError("%s: the bytes of a row must be contiguous" % what)
+        return a, a.shape[0], a.shape[1], a.strides[0]
+    if isinstance(frames, np.ndarray):
+        x = frames
+        if x.dtype != np.uint8 or not x.flags["C_CONTIGUOUS"] or not x.flags["WRITEABLE"]:
+            raise ValueError("frames must be a writable C-contiguous uint8 array")
+        if bgr:
+            if x.ndim != 4 or x.shape[3] != 3:
+                raise ValueError("BGR frames must be uint8 [B,h,w,3], got %s" % (x.shape,))
+            B, h, w = x.shape[:3]
+            tab = (PlanesRW * max(B, 1))()
+            for b in range(B):
+                tab[b].p0 = x.ctypes.data + b * h * w * 3
+            return tab, B, h, w, 3 * w, 0, x
+        if x.ndim != 3 or (x.shape[1] * 2 // 3) * 3 // 2 != x.shape[1]:
+            raise ValueError("4:2:0 frames must be uint8 [B, h*3//2, w] with h even, got %s" % (x.shape,))
+        B, rows, w = x.shape
+        h = rows * 2 // 3
+        offs, cp = yuv_dense_geometry(f, h, w)
+        tab = (PlanesRW * max(B, 1))()
+        for b in range(B):
+            base = x.ctypes.data + b * rows * w
+            tab[b].p0, tab[b].p1, tab[b].p2 = base, base + offs[1], (base + offs[2]) if offs[2] is not None else None
+        return tab, B, h, w, w, cp, x
+    frames = list(frames)
+    if not bgr and frames and all(isinstance(t, np.ndarray) and t.ndim == 2 for t in frames):
+        # a list of dense [h*3//2, w] frames, as forward_yuv_enqueue takes them
+        rows, w = frames[0].shape
+        h = rows * 2 // 3
+        offs, cp = yuv_dense_geometry(f, h, w)
+        tab = (PlanesRW * len(frames))()
+        for b, x in enumerate(frames):
+            if x.dtype != np.uint8 or x.shape != (rows, w) or h * 3 // 2 != rows or not x.flags["C_CONTIGUOUS"] or not x.flags["WRITEABLE"]:
+                raise ValueError("frames must be writable C-contiguous uint8 [h*3//2, w] arrays of one size, got %s %s" % (x.dtype, x.shape))
+            base = x.ctypes.data
+            tab[b].p0, tab[b].p1, tab[b].p2 = base, base + offs[1], (base + offs[2]) if offs[2] is not None else None
+        return tab, len(frames), h, w, w, cp, frames
+    frames = [t if isinstance(t, (tuple, list)) else (t,) for t in frames]
+    need = 1 if bgr else 2 if il else 3
+    B = len(frames)
+    if B == 0:
+        raise ValueError("redact_faces needs at least one frame")
+    tab = (PlanesRW * B)()
+    keep, geo = [], None
+    for b, t in enumerate(frames):
+        t = [p for p in t if p is not None]
+        if len(t) != need:
+            raise ValueError("frame %d has %d planes, format %r takes %d" % (b, len(t), fmt, need))
+        g = []
+        for k, a in enumerate(t):
+            a, rows, rowbytes, pitch = rows_of(a, "plane %d of frame %d" % (k, b))
+            keep.append(a)
+            g.append((rows, rowbytes, pitch))
+            setattr(tab[b], "p%d" % k, a.ctypes.data)
+        if geo is None:
+            geo = g
+        elif g != geo:
+            raise ValueError("frame %d differs from frame 0 in a plane's shape or row stride" % b)
+    h, row0, pitch0 = geo[0]
+    if bgr and row0 % 3:
+        raise ValueError("a BGR plane has 3w bytes per row, got %d" % row0)
+    w = row0 // 3 if bgr else row0
+    pitch1 = 0
+    if not bgr:
+        want = (h // 2, w if il else w // 2)
+        for g in geo[1:]:
+            if (g[0], g[1]) != want or g[2] != geo[1][2]:
+                raise ValueError("chroma planes must be [%d, %d] with one row stride, got %s" % (want + (geo[1:],)))
+        pitch1 = geo[1][2]
+    return tab, B, h, w, pitch0, pitch1, keep
 
 
 def yuv_format(fmt):
@@ -142,6 +269,8 @@ def lib():
         L.cf_op_yuv_to_bgr.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
         L.cf_align_faces.argtypes = [C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.cf_op_align_faces.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p]
+        L.cf_redact_faces.argtypes = [C.c_void_p, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 6
+        L.cf_op_redact.argtypes = [C.c_int, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.cf_get_resized_input.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.cf_get_heads.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.cf_decode_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

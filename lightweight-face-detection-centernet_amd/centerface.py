@@ -348,6 +348,36 @@ class Engine(object):
         self._chk(self._L.cf_align_faces(self._h, C.byref(o), C.c_void_p(int(chips_ptr)), C.c_void_p(int(matrices_ptr)) if matrices_ptr else None,
                                          C.c_void_p(int(offsets_ptr)), int(cap_faces), 1))      # (the template is read during the call)
 
+    # -- face redaction in the source frame ------------------------------------------------------
+    def redact_faces(self, frames, fmt="bgr", *, mode="mosaic", shape="ellipse", cell=20, scale=1.3, fill=(0, 0, 0)):
+        """Blank or pixelate, in ``frames``, the faces the preceding ``decode_threshold`` kept (``cf_redact_faces``, blocking form): the
+        host arrays are copied up, redacted on the device and copied back IN PLACE, and returned.  ``frames``: BGR uint8 [B,h,w,3]
+        (``fmt='bgr'``), OpenCV's dense 4:2:0 uint8 [B, h*3//2, w] ('nv12', 'nv21', 'i420', 'yv12'), or a list of per-frame plane tuples
+        of 2-D uint8 arrays (pitched rows; chroma planes in the format's order) -- of ANY size: the boxes are taken in network
+        coordinates, whatever ``set_rescale`` says, and mapped to the frame by w / W, h / H.  B must be the last forward's batch.
+        A face's box is grown about its centre by ``scale``; ``shape`` 'rect' covers it, 'ellipse' the ellipse inscribed in it;
+        ``mode`` 'solid' writes ``fill`` (bytes in the frame's channel order), 'mosaic' the mean of the ``cell`` x ``cell`` cell of a
+        grid anchored at the frame origin, taken from the untouched frame."""
+        tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
+        o = _lib.redact_opts(mode, shape, cell, scale, fill)
+        self._chk(self._L.cf_redact_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1))
+        del keep
+        return frames
+
+    def redact_faces_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1=0, *, mode="mosaic", shape="ellipse", cell=20, scale=1.3,
+                            fill=(0, 0, 0)):
+        """Same, in place on DEVICE planes -- a decoder's surfaces: ``plane_ptrs`` = B tuples (p0, p1, p2) of device addresses (BGR: p0
+        only; NV12 / NV21: Y and the interleaved plane; I420 / YV12: three planes), addresses and pitches multiples of 4.  Asynchronous
+        on the engine's main stream behind the decode; no count is read on the host."""
+        tab = (_lib.PlanesRW * max(len(plane_ptrs), 1))()
+        for b, t in enumerate(plane_ptrs):
+            t = (tuple(t) if isinstance(t, (tuple, list)) else (t,)) + (None, None)
+            tab[b].p0, tab[b].p1, tab[b].p2 = (int(v) if v else None for v in t[:3])
+        o = _lib.redact_opts(mode, shape, cell, scale, fill)
+        if int(B) != len(plane_ptrs):
+            raise ValueError("redact_faces_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
+        self._chk(self._L.cf_redact_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1)))
+
     # -- launch plan / layer trace (parity tests) ---------------------------------------------
     def plan(self):
         """The context's launch plan: list of dicts name/kind/C/H/W/fused_away."""
@@ -714,6 +744,38 @@ class CenterFace(object):
             chips, offs, _ = self.engine.align_faces(size, **chip_options)
             return [(d, l, chips[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(results)]
         return self._detect_chunks(imgs, with_chips)
+
+    def anonymize(self, imgs, **options):
+        """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
+        ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
+        cell, scale, fill), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
+        without detections comes back byte for byte."""
+        imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
+        out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
+        k = [0]
+
+        def redact(results):
+            self.engine.redact_faces(out[k[0]:k[0] + len(results)], "bgr", **options)
+            k[0] += len(results)
+            return results
+        return out, self._detect_chunks(imgs, redact)
+
+    def anonymize_yuv(self, frames, fmt="nv12", **options):
+        """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
+        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes."""
+        frames = self._yuv_frames(frames)
+        out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
+        dets = []
+        self.engine.set_rescale(self.scale_h, self.scale_w)
+        try:
+            for i in range(0, len(out), self.engine.max_batch):
+                chunk = out[i:i + self.engine.max_batch]
+                self.engine.forward_yuv_enqueue(frames[i:i + self.engine.max_batch], fmt)
+                dets.extend(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True))
+                self.engine.redact_faces(chunk, fmt, **options)
+        finally:
+            self.engine.set_rescale(0.0, 0.0)
+        return out, dets
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]

@@ -684,6 +684,11 @@ __global__ __launch_bounds__(64) void thresh_sweep_kernel(ThreshParams p) {
 #pragma unroll
             for (int j = 0; j < 10; ++j) ln[j] = c[5 + j];
         }
+        if (p.dets_net) {
+            float* dn = p.dets_net + ((size_t)b * p.max_out + pos) * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dn[j] = c[j];
+        }
         if (p.rs_w > 0.f) {                        // centerface.py:55-62: x // scale_w, y // scale_h (exact floor of the quotient)
             const double sw = (double)p.rs_w, sh = (double)p.rs_h;
 #pragma unroll

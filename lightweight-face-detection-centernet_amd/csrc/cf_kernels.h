@@ -286,6 +286,7 @@ struct ThreshParams {
     float* dets;          // [B][max_out][5]
     float* lms;           // [B][max_out][10] or nullptr
     float* lms_net;       // optional [B][max_out][10]: the same rows in network coordinates whatever rs_h / rs_w say (cf_align_faces reads them)
+    float* dets_net;      // optional [B][max_out][4]: the box corners likewise, before the rescale (cf_redact_faces reads them)
     int* counts;          // [B]
     int* overflow;        // [1] largest candidate count seen when some image exceeded cap (else untouched)
     float rs_h, rs_w;     // > 0: emit floor(y / rs_h), floor(x / rs_w) (centerface.py:55-62); 0 = network coordinates
@@ -348,6 +349,39 @@ struct AlignParams {
 const char* align_params_set(AlignParams& p, int size, int format, int rgb, float mean, float scale, const float* tmpl, int max_per_image);
 size_t align_chip_bytes(int size, int format);
 hipError_t launch_align_faces(hipStream_t s, const AlignParams& p);
+
+// Face redaction in the source frame (cf_redact.hip): every sample of a BGR or 4:2:0 frame that the scaled box (RECT) or its inscribed
+// ellipse of some kept face covers is overwritten, by a fill colour (SOLID) or by the mean of its frame-anchored mosaic cell (MOSAIC: a
+// first launch writes the cell means of the untouched frame to `cells`, a second one writes the samples).  Image b uses box rows
+// boxes[b * box_stride + i], i < min(counts[b], rows_cap); the launches are sized for B x faces_cap faces and read counts on the device.
+constexpr int kRedactMaxSide = 8192;
+struct RedactParams {
+    int format;           // CF_YUV_NV12 .. CF_YUV_YV12, CF_FRAME_BGR
+    int mode, shape, cell;   // CF_REDACT_SOLID / _MOSAIC, CF_REDACT_RECT / _ELLIPSE, the mosaic cell m
+    float scale;
+    uint8_t fill[3];      // in the frame's channel order (B,G,R or Y,U,V)
+    const void* const* planes;   // HOST table, B x {p0, p1, p2} DEVICE addresses (p1 / p2 as the format needs), all 4-byte aligned
+    int B, h, w, pitch0, pitch1;   // pitches in bytes, multiples of 4
+    int H, W;             // the size the boxes are expressed in (the network input)
+    const float* boxes;   // rows of 4 floats x1,y1,x2,y2
+    int box_stride;       // rows per image
+    const int* counts;    // [B]
+    int rows_cap;         // rows the producer wrote per image at most
+    int faces_cap;        // faces per image the launches are sized for (>= 1)
+    uint32_t* cells;      // MOSAIC: [B][ceil(h / m)][ceil(w / m)] cell means, one dword each (else unused)
+};
+// nullptr, or what is wrong with the options / geometry (host only; no device is touched)
+const char* redact_check(int format, int mode, int shape, int cell, float scale, int B, int h, int w, int pitch0, int pitch1);
+// the same for a B x {p0, p1, p2} plane table: required planes present; device planes and pitches multiples of 4
+const char* redact_check_planes(int format, const void* const* planes, int B, int on_device, int pitch0, int pitch1);
+size_t redact_cells(int B, int h, int w, int cell);      // dwords of RedactParams::cells
+// Host frames of the blocking forms: B frames back to back in one device buffer of B * one bytes, every plane at a 4-byte aligned
+// offset with a pitch rounded up to 4; the copies move the row bytes only, so the host's own padding is neither read nor written
+struct RedactStage { int row0, row1, pitch0, pitch1, rows1; size_t off1, off2, one; };
+RedactStage redact_stage_layout(int format, int h, int w);
+hipError_t redact_stage_copy(hipStream_t s, const RedactStage& st, int format, void* const* host_planes, int B, int h, int pitch0, int pitch1,
+                             uint8_t* dev, bool to_device);
+hipError_t launch_redact_faces(hipStream_t s, const RedactParams& p);
 
 // layout converters used by cf_get_heads and the per-op test entry points
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*T NHWC*/,

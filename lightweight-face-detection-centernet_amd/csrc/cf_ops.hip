@@ -739,4 +739,50 @@ int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, cons
     return sc.result("cf_op_align_faces");
 }
 
+// The kernels of cf_redact_faces on host frames (in place).  The packed box rows are spread to [B][max count][4] on the host, the
+// layout the decode leaves behind, so that the launches address them exactly as the engine's do.
+int cf_op_redact(int device, const cf_redact_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
+                 const float* boxes, const int32_t* counts, int H, int W) {
+    if (!o) { g_op_error = "cf_op_redact: null options"; return CF_EINVAL; }
+    static_assert(sizeof(cf_planes_rw) == 3 * sizeof(void*), "cf_planes_rw is a table of three addresses");
+    const char* why = redact_check(format, o->mode, o->shape, o->cell, o->scale, B, h, w, pitch0, pitch1);
+    if (!why) why = redact_check_planes(format, reinterpret_cast<const void* const*>(frames), B, 0, pitch0, pitch1);
+    if (!why && (!counts || H < 1 || W < 1)) why = "null counts, or H / W below 1";
+    int rows = 1;
+    long long N = 0;
+    for (int b = 0; !why && b < B; ++b) {
+        if (counts[b] < 0 || counts[b] > (1 << 20)) why = "a count is negative or above 2^20";
+        else { rows = std::max(rows, (int)counts[b]); N += counts[b]; }
+    }
+    if (!why && N > 0 && !boxes) why = "null boxes";
+    if (why) { g_op_error = std::string("cf_op_redact: ") + why; return CF_EINVAL; }
+    if (N == 0) return CF_OK;
+    std::vector<float> spread((size_t)B * rows * 4, 0.0f);
+    for (long long b = 0, at = 0; b < B; at += counts[b], ++b)
+        if (counts[b]) memcpy(&spread[(size_t)b * rows * 4], boxes + at * 4, (size_t)counts[b] * 4 * sizeof(float));
+    Scope sc(device);
+    RedactParams p{};
+    p.format = format; p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
+    p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
+    p.B = B; p.h = h; p.w = w; p.H = H; p.W = W;
+    p.boxes = sc.upv(spread); p.box_stride = rows; p.rows_cap = rows; p.faces_cap = rows;
+    p.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int));
+    if (o->mode == CF_REDACT_MOSAIC) p.cells = (uint32_t*)sc.alloc(redact_cells(B, h, w, o->cell) * sizeof(uint32_t));
+    const RedactStage st = redact_stage_layout(format, h, w);
+    uint8_t* stage = (uint8_t*)sc.alloc(st.one * B);
+    std::vector<const void*> dev((size_t)3 * B, nullptr);
+    for (int b = 0; b < B && stage; ++b) {
+        uint8_t* f = stage + (size_t)b * st.one;
+        dev[3 * b] = f;
+        if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
+        if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
+    }
+    p.planes = dev.data(); p.pitch0 = st.pitch0; p.pitch1 = st.pitch1;
+    void* const* host_planes = reinterpret_cast<void* const*>(frames);
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, true));
+    if (sc.err == hipSuccess) sc.chk(launch_redact_faces(sc.s, p));
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, false));
+    return sc.result("cf_op_redact");
+}
+
 }  // extern "C"

@@ -121,6 +121,9 @@ struct cf_ctx {
     // 0 = no decode behind the last forward) and the scratch of the host-output form
     const void* al_in = nullptr; int al_fmt = -1, al_slot = -1, al_rows = 0; float* t_lmsnet = nullptr;
     uint8_t* al_chips = nullptr; size_t al_chips_bytes = 0; double* al_mats = nullptr; int al_mats_cap = 0; int* al_off = nullptr;
+    // cf_redact_faces: the network-coordinate box corners of the last threshold decode ([max_batch][t_maxout][4], beside t_lmsnet), the
+    // mosaic's cell means (one dword per grid cell, grown to the largest grid seen) and the frames of the host form
+    float* t_detsnet = nullptr; uint32_t* rd_cells = nullptr; size_t rd_cells_n = 0; uint8_t* rd_stage = nullptr; size_t rd_stage_bytes = 0;
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
     // input format, batch): the second forward with a key captures it, later ones replay it
     struct FwdGraph { const void* in; int fmt, B; hipGraphExec_t exec; bool broken; unsigned long long used; };
@@ -617,7 +620,7 @@ int cf_destroy(cf_ctx* c) {
     for (void* p : c->owned) hipFree(p);
     for (void* p : {(void*)c->src_stage, (void*)c->d_trans, (void*)c->hm_plane, (void*)c->keys, (void*)c->key_count, (void*)c->big, (void*)c->d_slot, (void*)c->d_dets, (void*)c->d_lms, (void*)c->d_inds, (void*)c->t_cand, (void*)c->t_count,
                     (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow,
-                    (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off})
+                    (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off, (void*)c->t_detsnet, (void*)c->rd_cells, (void*)c->rd_stage})
         if (p) hipFree(p);
     if (c->h_thr) hipHostFree(c->h_thr);
     if (c->ev_thr) hipEventDestroy(c->ev_thr);
@@ -1514,7 +1517,8 @@ static int ensure_thresh_ws(cf_ctx* c, int max_out, int cap, int B) {
         if (!c->t_host && c->t_dets) hipFree(c->t_dets);
         if (!c->t_host && c->t_lms) hipFree(c->t_lms);
         if (c->t_lmsnet) hipFree(c->t_lmsnet);
-        c->t_lmsnet = nullptr; c->al_rows = 0;
+        if (c->t_detsnet) hipFree(c->t_detsnet);
+        c->t_lmsnet = nullptr; c->t_detsnet = nullptr; c->al_rows = 0;
         if (c->h_thr) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipHostFree(c->h_thr); }
         c->t_dets = nullptr; c->t_lms = nullptr; c->h_thr = nullptr; c->t_host = false; c->t_maxout = 0;
         const size_t nd = (size_t)c->max_batch * max_out * 5 * sizeof(float), nl = 2 * nd, head = thr_host_head(c);
@@ -1531,6 +1535,7 @@ static int ensure_thresh_ws(cf_ctx* c, int max_out, int cap, int B) {
             HIPCHK(c, hipMalloc((void**)&c->t_lms, nl));
         }
         HIPCHK(c, hipMalloc((void**)&c->t_lmsnet, nl));
+        HIPCHK(c, hipMalloc((void**)&c->t_detsnet, (size_t)c->max_batch * max_out * 4 * sizeof(float)));
         c->t_maxout = max_out;
     }
     if (!c->ev_thr) HIPCHK(c, hipEventCreateWithFlags(&c->ev_thr, hipEventDisableTiming));
@@ -1557,7 +1562,7 @@ static int thresh_launch(cf_ctx* c, int mode, float score_thresh, float nms_thre
     p.img_h = img_h; p.img_w = img_w; p.score_thresh = score_thresh; p.nms_thresh = nms_thresh; p.cap = c->t_cap; p.mode = mode;
     p.cand = c->t_cand; p.cand_count = c->t_count; p.order = c->t_order; p.mask = c->t_mask;
     p.max_out = max_out; p.dets = c->t_dets; p.lms = c->t_lms; p.counts = c->t_counts; p.overflow = c->t_overflow;
-    p.rs_h = c->rs_h; p.rs_w = c->rs_w; p.lms_net = c->t_lmsnet;
+    p.rs_h = c->rs_h; p.rs_w = c->rs_w; p.lms_net = c->t_lmsnet; p.dets_net = c->t_detsnet;
     if (c->t_host) { p.host_overflow = (int*)c->h_thr; p.host_counts = (int*)(c->h_thr + 256); }
     HIPCHK(c, hipMemsetAsync(c->t_overflow, 0, sizeof(int), c->stream));
     HIPCHK(c, launch_decode_threshold(c->stream, p));
@@ -1687,6 +1692,69 @@ int cf_align_faces(cf_ctx* c, const cf_align_opts* o, void* chips, double* matri
         if (matrices) HIPCHK(c, hipMemcpyAsync(matrices, c->al_mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return CF_OK;
+}
+
+// Redaction of the faces the last threshold decode kept, in frames the caller names (cf_redact.hip): the launches go on the stream that
+// carried the decode and read its device-side counts and network-coordinate box rows.  Host frames are staged in rd_stage and copied
+// back; the scratch of the mosaic's cell means grows to the largest grid seen, like the decode workspace.
+static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char* what) {
+    if (*have >= need_bytes) return CF_OK;
+    if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(*p); }        // earlier launches may still use it
+    *p = nullptr; *have = 0;
+    const hipError_t e = hipMalloc(p, need_bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_redact_faces: %zu bytes of %s: %s", need_bytes, what, hipGetErrorString(e)); }
+    *have = need_bytes;
+    return CF_OK;
+}
+
+int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
+                    int pitch0, int pitch1) {
+    if (!c) return CF_EINVAL;
+    if (!o) return c->fail(CF_EINVAL, "cf_redact_faces: null options");
+    static_assert(sizeof(cf_planes_rw) == 3 * sizeof(void*), "cf_planes_rw is a table of three addresses");
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    if (const char* why = redact_check(format, o->mode, o->shape, o->cell, o->scale, B, h, w, pitch0, pitch1))
+        return c->fail(CF_EINVAL, "cf_redact_faces: %s", why);
+    if (const char* why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1))
+        return c->fail(CF_EINVAL, "cf_redact_faces: %s", why);
+    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_redact_faces before cf_forward");
+    if (!c->al_in) return c->fail(CF_ESTATE, "cf_redact_faces: an upload was started after the last forward");
+    if (c->al_rows < 1 || !c->t_detsnet || !c->t_counts) return c->fail(CF_ESTATE, "cf_redact_faces without a threshold decode of the last forward");
+    if (B != c->last_B) return c->fail(CF_EINVAL, "cf_redact_faces: B=%d, the last forward had %d images", B, c->last_B);
+    HIPCHK(c, hipSetDevice(c->device));
+    RedactParams p{};
+    p.format = format; p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
+    p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
+    p.B = B; p.h = h; p.w = w; p.H = c->H; p.W = c->W;
+    p.boxes = c->t_detsnet; p.box_stride = c->al_rows; p.rows_cap = c->al_rows; p.faces_cap = c->al_rows; p.counts = c->t_counts;
+    if (o->mode == CF_REDACT_MOSAIC) {
+        size_t have = c->rd_cells_n * sizeof(uint32_t);
+        int r = grow(c, (void**)&c->rd_cells, &have, redact_cells(B, h, w, o->cell) * sizeof(uint32_t), "mosaic cell means");
+        c->rd_cells_n = have / sizeof(uint32_t);
+        if (r) return r;
+        p.cells = c->rd_cells;
+    }
+    if (on_device) {
+        p.planes = planes; p.pitch0 = pitch0; p.pitch1 = pitch1;
+        HIPCHK(c, launch_redact_faces(c->stream, p));
+        return CF_OK;
+    }
+    const RedactStage st = redact_stage_layout(format, h, w);
+    int r = grow(c, (void**)&c->rd_stage, &c->rd_stage_bytes, st.one * B, "frame staging"); if (r) return r;
+    void* const* host_planes = reinterpret_cast<void* const*>(frames);
+    std::vector<const void*> dev((size_t)3 * B, nullptr);
+    for (int b = 0; b < B; ++b) {
+        uint8_t* f = c->rd_stage + (size_t)b * st.one;
+        dev[3 * b] = f;
+        if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
+        if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
+    }
+    p.planes = dev.data(); p.pitch0 = st.pitch0; p.pitch1 = st.pitch1;
+    HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, true));
+    HIPCHK(c, launch_redact_faces(c->stream, p));
+    HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, false));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return CF_OK;
 }
 

@@ -53,3 +53,45 @@ def dump_event(detector, images, im_dir, names, save_path):
         dets = res[0] if isinstance(res, tuple) else res
         paths.append(write_wider_result(save_path, im_dir, name, dets))
     return paths
+
+
+def anonymize_file(path, out_path, **options):
+    """Read one image file, redact every detected face on the device (``CenterFace.anonymize``; ``options``: mode, shape, cell,
+    scale, fill) and write the result to ``out_path`` (format from its extension).  Returns the detections."""
+    from PIL import Image
+    from .centerface import CenterFace
+    frame = imread(path)
+    detector = CenterFace(frame.shape[0], frame.shape[1], dtype=options.pop("dtype", "bf16"))
+    try:
+        frames, results = detector.anonymize([frame], **options)
+    finally:
+        detector.close()
+    Image.fromarray(np.ascontiguousarray(frames[0][:, :, ::-1])).save(out_path)
+    return results[0]
+
+
+def main(argv=None):
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT]``: print the detections of one image file; with ``--anonymize`` also
+    write the image with every face pixelated (or blanked: ``--mode solid``)."""
+    import argparse
+    ap = argparse.ArgumentParser(description=main.__doc__)
+    ap.add_argument("image")
+    ap.add_argument("--anonymize", metavar="OUT", help="write the image with every detected face redacted to OUT")
+    ap.add_argument("--mode", default="mosaic", choices=("mosaic", "solid"))
+    ap.add_argument("--shape", default="ellipse", choices=("ellipse", "rect"))
+    ap.add_argument("--cell", type=int, default=20)
+    ap.add_argument("--scale", type=float, default=1.3)
+    args = ap.parse_args(argv)
+    if args.anonymize:
+        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale)
+    else:
+        from .centerface import CenterFace
+        frame = imread(args.image)
+        detector = CenterFace(frame.shape[0], frame.shape[1], dtype="bf16")
+        dets, _ = detector(frame)
+        detector.close()
+    print(format_wider_result(args.image, dets), end="")
+
+
+if __name__ == "__main__":
+    main()

@@ -217,6 +217,24 @@ def align_faces(imgs, lms, counts, size=112, template=None, out="u8", rgb=False,
     return chips, mats
 
 
+def redact_faces(frames, boxes, counts, net_hw, fmt="bgr", mode="mosaic", shape="ellipse", cell=20, scale=1.3, fill=(0, 0, 0), device=0):
+    """Face redaction in the frame (``cf_op_redact``): ``frames`` -- BGR uint8 [B,h,w,3], dense 4:2:0 uint8 [B, h*3//2, w], or a list of
+    per-frame plane tuples (pitched rows) -- are modified IN PLACE and returned.  boxes [N,4] x1,y1,x2,y2 in the coordinates of a
+    network input of ``net_hw`` = (H, W), image after image, counts [B] (N = their sum).  Every sample that the box grown by ``scale``
+    (``shape='rect'``) or the ellipse inscribed in it covers becomes ``fill`` (``mode='solid'``; bytes in the frame's channel order) or
+    the mean of its ``cell`` x ``cell`` mosaic cell, a grid anchored at the frame origin."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+    if counts.shape[0] != B or (counts < 0).any() or int(counts.sum()) != boxes.shape[0]:
+        raise ValueError("counts must be [B] non-negative and sum to the number of box rows")
+    o = _lib.redact_opts(mode, shape, cell, scale, fill)
+    _lib.check(_lib.lib().cf_op_redact(device, C.byref(o), _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, ptr(boxes), ptr(counts),
+                                       int(net_hw[0]), int(net_hw[1])), op=True)
+    del keep
+    return frames
+
+
 def ctdet_decode(heat, wh, reg=None, K=100, lm=None, device=0):
     """ctdet_decode (centerface_ext.py:52-82): (dets [B,K,6], lms [B,K,10]|None, inds [B,K] int64)."""
     heat, wh, reg, lm = f32(heat), f32(wh), f32(reg), f32(lm)

@@ -301,6 +301,54 @@ typedef struct cf_redact_opts {
 int cf_redact_faces(cf_ctx* ctx, const cf_redact_opts* opts, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
                     int pitch0, int pitch1);
 
+/* ---- tiled detection of large frames (sliced inference) ------------------------------------
+ * A frame much larger than the network input loses its small faces in the stretch-resize of every other entry point.  Here the frame
+ * is cut into overlapping rectangles at or near native resolution, the rectangles run as one batch, and the per-tile detections are
+ * mapped back into frame pixels and de-duplicated, all on the device:
+ *   cf_tile_grid (host) -> cf_forward_tiles -> cf_decode_threshold* (unchanged, per tile image) -> cf_merge_tiles [-> cf_redact_faces]
+ * The defaults the Python layer uses (IoS 0.5, edge 2) are this project's choices, not the reference's; no accuracy claim is made. */
+typedef struct cf_tile_rect { int32_t x0, y0, w, h; } cf_tile_rect;
+#define CF_MERGE_IOU 0           /* suppress when inter / union >= thresh (the decode's own measure) */
+#define CF_MERGE_IOS 1           /* suppress when inter / min(area, area) >= thresh: removes a partial box lying inside a full one */
+typedef struct cf_merge_opts {
+    int32_t metric;              /* CF_MERGE_IOU | CF_MERGE_IOS */
+    float   thresh;
+    float   edge;                /* network pixels; 0 = no edge rule */
+} cf_merge_opts;
+/* The rectangles of an h x w frame for tiles of tile_h x tile_w with at least `overlap` pixels shared by neighbours (all even,
+ * 0 <= overlap < min(tile_h, tile_w)); host only.  Per axis: rw = min(tile_w, w); nx = 1 when rw == w, else
+ * ceil((w - overlap) / (rw - overlap)); x0_i = ((i * (w - rw)) / (nx - 1)) & ~1 (integer division).  Row-major, y outer; the
+ * whole-frame rectangle (0, 0, w, h) is appended when with_full and nx * ny > 1.  The rectangles cover the frame, the last one ends
+ * at w / h.  *n = the number wanted; only the first `cap` are written.  1920 x 1080, tile 640, overlap 128: 4 x 2 + 1 = 9. */
+int cf_tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, cf_tile_rect* rects, int cap, int* n);
+/* Bf frames of h x w in `format` (CF_YUV_* with the planes of cf_yuv_planes, or CF_FRAME_BGR with the [h][pitch0] pixel rows in .y)
+ * and T rectangles shared by the frames -> the network batch of Bf * T images, image f * T + t = resize(bgr(frame f)[rectangle t],
+ * (H, W)) with the conversion of cf_forward_yuv and the resize of cf_forward_resized applied to the crop (taps clamp at the
+ * rectangle's edges) -> forward.  x0, y0, w, h of every rectangle even, w, h >= 2, inside the frame; frame h, w even, <= 8192;
+ * 1 <= T, Bf * T <= max_batch.  pitch0 >= 3w (BGR) or w (Y), pitch1 as c_pitch of cf_forward_yuv.  in_on_device = 1: the planes
+ * are read in place (addresses and pitches multiples of 4); 0: host frames, copied up first (only the row bytes are read).
+ * CF_EINVAL before anything is enqueued, the offending rectangle named in cf_last_error.  The context remembers the rectangles and
+ * the frame size for cf_merge_tiles; every other forward or upload forgets them.  cf_get_resized_input returns the tile batch;
+ * cf_align_faces works per tile image. */
+int cf_forward_tiles(cf_ctx* ctx, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w,
+                     int pitch0, int pitch1, const cf_tile_rect* rects, int T);
+/* Merges the rows the LAST THRESHOLD DECODE kept for the Bf * T tile images of the last cf_forward_tiles, per frame.  Per tile the rows
+ * i < min(counts, the decode's max_out), in network coordinates whatever cf_set_rescale says:
+ *   * a row is dropped when a corner is not finite, or when the box comes within opts->edge network pixels of a side of its rectangle
+ *     that is not on the frame border (x1 < edge, x2 > W - edge, y1 < edge, y2 > H - edge; float32);
+ *   * the others are mapped, X = (float)((double)x * ((double)rw / (double)W) + (double)x0), y likewise (corners and landmarks);
+ *   * greedy NMS over the frame's candidates in (tile, row) order with opts->metric and opts->thresh: score descending, the higher
+ *     candidate index first among equals, float32 "+1" areas as the decode's.
+ * dets [Bf][max_out][5], lms [Bf][max_out][10] in frame pixels, counts [Bf] (may exceed max_out: only max_out rows are written),
+ * flags [Bf] (bit 0: a tile of the frame had more rows than the decode's max_out).  Any of the four may be NULL; the context's own
+ * merged rows are written in any case (cf_redact_faces reads them).  out_on_device = 1: device buffers, asynchronous on the decode's
+ * stream, no count read on the host; 0: host buffers, blocking.  CF_ESTATE unless the last forward was cf_forward_tiles with a
+ * threshold decode behind it; CF_ENOMEM, before any launch, when the suppression bits of Bf x (T * the decode's max_out) candidates
+ * would exceed 256 MiB.  After a merge, cf_redact_faces takes the merged boxes: its B must be Bf and its (h, w) the frame's
+ * (CF_EINVAL otherwise); after a tiled forward without a merge it returns CF_ESTATE. */
+int cf_merge_tiles(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags,
+                   int out_on_device);
+
 /* ---- fused convenience: forward + D3 decode in one enqueue (eval_widerface.py:76-90 shape) -- */
 int cf_detect_topk(cf_ctx* ctx, const void* in, int in_format, int in_on_device, int B, int K,
                    float* dets, float* lms, int64_t* inds, int out_on_device);
@@ -560,6 +608,17 @@ int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, cons
  * H x W network input, image after image, counts [B] (>= 0).  The same validation as cf_redact_faces, before any device is touched. */
 int cf_op_redact(int device, const cf_redact_opts* opts, int format, const cf_planes_rw* host_frames, int B, int h, int w, int pitch0,
                  int pitch1, const float* boxes, const int32_t* counts, int H, int W);
+/* The tile cutter of cf_forward_tiles alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up, so the
+ * padding bytes are on the device beside the pixels): tiles [Bf * T][H][W][3].  W % 4 == 0.  The same validation, before any device is
+ * touched. */
+int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1,
+                    const cf_tile_rect* rects, int T, int H, int W, uint8_t* tiles);
+/* The merge of cf_merge_tiles alone, on host tables: dets_net [Bf * T][rows][4], scores [Bf * T][rows], lms_net [Bf * T][rows][10],
+ * counts [Bf * T] -> dets [Bf][max_out][5], lms [Bf][max_out][10], out_counts [Bf], flags [Bf].  dets and lms are copied up first, so
+ * rows the kernels do not write come back as the caller filled them. */
+int cf_op_merge_tiles(int device, const cf_merge_opts* opts, const cf_tile_rect* rects, int T, int Bf, int h, int w, int H, int W,
+                      const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                      float* dets, float* lms, int32_t* out_counts, int32_t* flags);
 /* CenterFace.nms alone (centerface.py:111-151): keep[] receives kept indices in keep order. */
 int cf_op_nms(int device, const float* boxes, const float* scores, int n, float nms_thresh,
               int32_t* keep, int32_t* n_keep);

@@ -28,6 +28,10 @@ CF_REDACT_SOLID, CF_REDACT_MOSAIC = 0, 1
 CF_REDACT_RECT, CF_REDACT_ELLIPSE = 0, 1
 REDACT_MODES = {"solid": CF_REDACT_SOLID, "mosaic": CF_REDACT_MOSAIC}
 REDACT_SHAPES = {"rect": CF_REDACT_RECT, "ellipse": CF_REDACT_ELLIPSE}
+# cf_merge_tiles / cf_op_merge_tiles
+CF_ENOMEM = -2
+CF_MERGE_IOU, CF_MERGE_IOS = 0, 1
+MERGE_METRICS = {"iou": CF_MERGE_IOU, "ios": CF_MERGE_IOS}
 YUV_FORMATS = {"nv12": CF_YUV_NV12, "nv21": CF_YUV_NV21, "i420": CF_YUV_I420, "yuv420p": CF_YUV_I420, "yv12": CF_YUV_YV12}
 
 # every symbol include/centerface_hip.h declares (checked by tests/test_abi.py)
@@ -39,6 +43,7 @@ EXPORTS = (
     "cf_op_last_error", "cf_op_last_kernel", "cf_op_shufflev2", "cf_op_mbconv", "cf_op_expand_dw", "cf_op_mbconv_pick", "cf_op_expand_dw_pick", "cf_op_ctdet_loss", "cf_op_encode_targets", "cf_op_dwconv", "cf_op_pwconv", "cf_op_pwconv_ex", "cf_op_stem", "cf_op_idaup", "cf_op_heads",
     "cf_op_ctdet_decode", "cf_op_ctdet_post_process", "cf_op_decode_threshold", "cf_op_decode_threshold_ex", "cf_op_nms", "cf_op_box_match",
     "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces", "cf_redact_faces", "cf_op_redact",
+    "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
 )
 
 
@@ -114,6 +119,34 @@ def redact_opts(mode="mosaic", shape="ellipse", cell=20, scale=1.3, fill=(0, 0, 
     return RedactOpts(code(mode, REDACT_MODES, "mode"), code(shape, REDACT_SHAPES, "shape"), int(cell), float(scale), (C.c_uint8 * 4)(*fill, 0))
 
 
+class TileRect(C.Structure):
+    """cf_tile_rect: one rectangle of a frame, in frame pixels (all four values even)."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class MergeOpts(C.Structure):
+    """cf_merge_opts: suppression measure / threshold / edge margin in network pixels."""
+    _fields_ = [("metric", C.c_int32), ("thresh", C.c_float), ("edge", C.c_float)]
+
+
+def merge_opts(metric="ios", thresh=0.5, edge=2.0):
+    """MergeOpts from a name ('iou' | 'ios'); integer codes pass through (the library validates them, like the numbers)."""
+    if isinstance(metric, str):
+        if metric.lower() not in MERGE_METRICS:
+            raise ValueError("unknown merge metric %r (one of %s)" % (metric, sorted(MERGE_METRICS)))
+        metric = MERGE_METRICS[metric.lower()]
+    return MergeOpts(int(metric), float(thresh), float(edge))
+
+
+def tile_rects(rects):
+    """(TileRect table, T) of an int array-like [T][4] of (x0, y0, w, h) rows."""
+    r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 4)
+    tab = (TileRect * max(len(r), 1))()
+    for t, (x0, y0, w, h) in enumerate(r.tolist()):
+        tab[t].x0, tab[t].y0, tab[t].w, tab[t].h = x0, y0, w, h
+    return tab, len(r)
+
+
 def frame_format(fmt):
     """The `format` integer of cf_redact_faces: 'bgr' -> CF_FRAME_BGR, otherwise as ``yuv_format``."""
     if isinstance(fmt, str) and fmt.lower() == "bgr":
@@ -121,17 +154,18 @@ def frame_format(fmt):
     return yuv_format(fmt)
 
 
-def frame_planes(frames, fmt):
+def frame_planes(frames, fmt, writable=True):
     """Host frames of ``Engine.redact_faces`` / ``ops.redact_faces`` as (PlanesRW table, B, h, w, pitch0, pitch1, arrays to keep alive):
     BGR uint8 [B,h,w,3]; 4:2:0 uint8 [B, h*3//2, w] (OpenCV's dense layout) or a list of such [h*3//2, w] frames; or a list of per-frame
     plane tuples of uint8 2-D arrays (rows of bytes; one common shape and row stride per plane; BGR: one [h, 3w] or [h,w,3] array).  The arrays are written in place,
-    so nothing is copied here: a frame that is not writable or whose rows are not contiguous is refused."""
+    so nothing is copied here: a frame that is not writable or whose rows are not contiguous is refused (``writable=False``: the
+    caller only reads them -- the tile cutter -- and read-only arrays pass)."""
     f = frame_format(fmt)
     bgr, il = f == CF_FRAME_BGR, f in (CF_YUV_NV12, CF_YUV_NV21)
 
     def rows_of(a, what):
         a = a if isinstance(a, np.ndarray) else np.asarray(a)
-        if a.dtype != np.uint8 or a.ndim < 2 or not a.flags["WRITEABLE"]:
+        if a.dtype != np.uint8 or a.ndim < 2 or (writable and not a.flags["WRITEABLE"]):
             raise ValueError("%s must be a writable uint8 array, got %s %s" % (what, a.dtype, a.shape))
         if a.ndim == 3:
             if a.strides[1:] != (a.shape[2], 1):
@@ -142,7 +176,7 @@ def frame_planes(frames, fmt):
         return a, a.shape[0], a.shape[1], a.strides[0]
     if isinstance(frames, np.ndarray):
         x = frames
-        if x.dtype != np.uint8 or not x.flags["C_CONTIGUOUS"] or not x.flags["WRITEABLE"]:
+        if x.dtype != np.uint8 or not x.flags["C_CONTIGUOUS"] or (writable and not x.flags["WRITEABLE"]):
             raise ValueError("frames must be a writable C-contiguous uint8 array")
         if bgr:
             if x.ndim != 4 or x.shape[3] != 3:
@@ -170,7 +204,7 @@ def frame_planes(frames, fmt):
         offs, cp = yuv_dense_geometry(f, h, w)
         tab = (PlanesRW * len(frames))()
         for b, x in enumerate(frames):
-            if x.dtype != np.uint8 or x.shape != (rows, w) or h * 3 // 2 != rows or not x.flags["C_CONTIGUOUS"] or not x.flags["WRITEABLE"]:
+            if x.dtype != np.uint8 or x.shape != (rows, w) or h * 3 // 2 != rows or not x.flags["C_CONTIGUOUS"] or (writable and not x.flags["WRITEABLE"]):
                 raise ValueError("frames must be writable C-contiguous uint8 [h*3//2, w] arrays of one size, got %s %s" % (x.dtype, x.shape))
             base = x.ctypes.data
             tab[b].p0, tab[b].p1, tab[b].p2 = base, base + offs[1], (base + offs[2]) if offs[2] is not None else None
@@ -271,6 +305,11 @@ def lib():
         L.cf_op_align_faces.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p]
         L.cf_redact_faces.argtypes = [C.c_void_p, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 6
         L.cf_op_redact.argtypes = [C.c_int, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.cf_tile_grid.argtypes = [C.c_int] * 6 + [C.POINTER(TileRect), C.c_int, C.POINTER(C.c_int)]
+        L.cf_forward_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(TileRect), C.c_int]
+        L.cf_merge_tiles.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.cf_op_cut_tiles.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(TileRect)] + [C.c_int] * 3 + [C.c_void_p]
+        L.cf_op_merge_tiles.argtypes = [C.c_int, C.POINTER(MergeOpts), C.POINTER(TileRect)] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
         L.cf_get_resized_input.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.cf_get_heads.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.cf_decode_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

@@ -378,6 +378,65 @@ class Engine(object):
             raise ValueError("redact_faces_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
         self._chk(self._L.cf_redact_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1)))
 
+    # -- tiled detection of large frames ---------------------------------------------------------
+    def forward_tiles_enqueue(self, frames, rects, fmt="bgr", *, on_device=False, h=None, w=None, pitch0=None, pitch1=None):
+        """Cut ``rects`` ([T][4] rows (x0, y0, w, h), all even, inside the frame) out of every frame at native resolution, resize each to
+        the network size and run the Bf * T tiles as one batch (``cf_forward_tiles``); image f * T + t is tile t of frame f.  ``frames``:
+        host arrays as ``redact_faces`` takes them (BGR uint8 [B,h,w,3], dense 4:2:0 uint8 [B, h*3//2, w], or per-frame plane tuples of
+        pitched rows) -- only read -- or, with ``on_device=True``, Bf tuples (p0, p1, p2) of device addresses with ``h``, ``w`` and the
+        pitches in bytes (default: dense rows; addresses and pitches multiples of 4), read in place.  A ``decode_threshold`` then gives
+        the per-tile results and ``merge_tiles`` the per-frame ones."""
+        f = _lib.frame_format(fmt)
+        rt, T = _lib.tile_rects(rects)
+        if on_device:
+            if h is None or w is None:
+                raise ValueError("forward_tiles_enqueue(on_device=True) needs h and w")
+            h, w = int(h), int(w)
+            tab = (_lib.PlanesRW * max(len(frames), 1))()
+            for b, t in enumerate(frames):
+                t = (tuple(t) if isinstance(t, (tuple, list)) else (t,)) + (None, None)
+                tab[b].p0, tab[b].p1, tab[b].p2 = (int(v) if v else None for v in t[:3])
+            B, keep = len(frames), None
+            il = f in (_lib.CF_YUV_NV12, _lib.CF_YUV_NV21)
+            pitch0 = (3 * w if f == _lib.CF_FRAME_BGR else w) if pitch0 is None else int(pitch0)
+            pitch1 = (0 if f == _lib.CF_FRAME_BGR else w if il else w // 2) if pitch1 is None else int(pitch1)
+        else:
+            tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+            self._keep_in = keep
+        self._chk(self._L.cf_forward_tiles(self._h, f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, rt, T))
+        self.last_B = B * T
+        self._tiles = (B, T)
+
+    def merge_tiles(self, metric="ios", thresh=0.5, edge=2.0, max_out=1024):
+        """Per-frame detections of the last tiled forward (``cf_merge_tiles``, host form): the rows the preceding ``decode_threshold``
+        kept for every tile -- in network coordinates, whatever ``set_rescale`` says -- are mapped into frame pixels and de-duplicated
+        on the device.  A row whose box comes within ``edge`` network pixels of a tile side that is not on the frame border is dropped
+        first (a face cut by the seam; the neighbouring tile or the whole-frame tile sees it whole); the others go through greedy NMS
+        with ``metric`` 'ios' (intersection over the smaller box) or 'iou' at ``thresh``.  Returns (results, flags): a list of (dets
+        [n,5], lms [n,10]) per frame and int32 [Bf], bit 0 set where a tile's decode was truncated by its ``max_out``.  IoS 0.5 and
+        edge 2 are this project's defaults, not the reference's."""
+        Bf = getattr(self, "_tiles", (1, 1))[0]                          # (without a tiled forward the library refuses: CF_ESTATE)
+        o = _lib.merge_opts(metric, thresh, edge)
+        max_out = int(max_out)
+        while True:
+            dets = np.empty((Bf, max_out, 5), np.float32)
+            lms = np.empty((Bf, max_out, 10), np.float32)
+            counts = np.empty((Bf,), np.int32)
+            flags = np.empty((Bf,), np.int32)
+            self._chk(self._L.cf_merge_tiles(self._h, C.byref(o), max_out, _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts), _lib.ptr(flags), 0))
+            if int(counts.max(initial=0)) <= max_out:
+                break
+            max_out = int(counts.max())          # more survivors than rows: keep them all, as decode_threshold does
+        return [(dets[b, :counts[b]].copy(), lms[b, :counts[b]].copy()) for b in range(Bf)], flags
+
+    def merge_tiles_device(self, max_out, dets_ptr=None, lms_ptr=None, counts_ptr=None, flags_ptr=None, *, metric="ios", thresh=0.5, edge=2.0):
+        """Same, writing into caller-owned DEVICE buffers (dets [Bf,max_out,5], lms [Bf,max_out,10] float32, counts / flags [Bf] int32;
+        any may be None): asynchronous on the engine's main stream behind the decode, no count is read on the host.  The context keeps
+        the merged rows either way: a following ``redact_faces`` / ``redact_faces_device`` on the full frames uses them."""
+        o = _lib.merge_opts(metric, thresh, edge)
+        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
+        self._chk(self._L.cf_merge_tiles(self._h, C.byref(o), int(max_out), vp(dets_ptr), vp(lms_ptr), vp(counts_ptr), vp(flags_ptr), 1))
+
     # -- launch plan / layer trace (parity tests) ---------------------------------------------
     def plan(self):
         """The context's launch plan: list of dicts name/kind/C/H/W/fused_away."""
@@ -745,13 +804,51 @@ class CenterFace(object):
             return [(d, l, chips[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(results)]
         return self._detect_chunks(imgs, with_chips)
 
-    def anonymize(self, imgs, **options):
+    def _tile_geometry(self, h, w, tile, overlap, with_full):
+        th, tw = (self.img_h_new, self.img_w_new) if tile is None else (int(tile), int(tile)) if np.isscalar(tile) else (int(tile[0]), int(tile[1]))
+        if overlap is None:
+            overlap = (min(th, tw) // 4) & ~1
+        from . import ops
+        rects = ops.tile_grid(h, w, (th, tw), overlap, with_full)
+        per = self.engine.max_batch // len(rects)
+        if per < 1:
+            raise ValueError("%d tiles per frame need max_batch >= %d (this instance has %d)" % (len(rects), len(rects), self.engine.max_batch))
+        return rects, per
+
+    def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None):
+        """Sliced inference for frames much larger than the network input, whose small faces the stretch-resize of ``detect_batch``
+        loses: every frame is cut on the device into overlapping tiles of ``tile`` (default: the network's (H, W)) that share at
+        least ``overlap`` pixels (default: a quarter of the tile, rounded down to even), plus the whole frame as one more tile; the
+        tiles run as one batch, and the per-tile detections are mapped back and de-duplicated on the device (``Engine.merge_tiles``:
+        ``metric``, ``thresh``, ``edge``).  ``frames``: BGR uint8 [B,h,w,3] (``fmt='bgr'``), dense 4:2:0 uint8 [B, h*3//2, w], or
+        per-frame plane tuples -- of any even size; ``max_batch`` must hold the tiles of one frame.  Returns (dets [n,5], lms [n,10]) per
+        frame (``dets`` alone without landmarks), in FRAME pixels, not floor-divided.  The defaults are this project's choices; no
+        accuracy claim is made for them.  ``redact``: options of ``Engine.redact_faces``; the frames are then redacted IN PLACE with the
+        merged boxes."""
+        tab, B, h, w, _, _, keep = _lib.frame_planes(frames, fmt, writable=redact is not None)
+        del tab, keep
+        rects, per = self._tile_geometry(h, w, tile, overlap, with_full)
+        out = []
+        for i in range(0, B, per):
+            chunk = frames[i:i + per]
+            self.engine.forward_tiles_enqueue(chunk, rects, fmt)
+            self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets)
+            res, _ = self.engine.merge_tiles(metric, thresh, edge, self.max_dets)
+            if redact is not None:
+                self.engine.redact_faces(chunk, fmt, **redact)
+            out.extend((d, l) if self.landmarks else d for d, l in res)
+        return out
+
+    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
         cell, scale, fill), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
-        without detections comes back byte for byte."""
+        without detections comes back byte for byte.  ``tiled=True``: detection by ``detect_tiled`` (``tile``, ``overlap``) on frames of
+        any even size, redaction with the merged boxes; the detections are then in frame pixels."""
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
+        if tiled:
+            return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options)
         k = [0]
 
         def redact(results):
@@ -760,9 +857,13 @@ class CenterFace(object):
             return results
         return out, self._detect_chunks(imgs, redact)
 
-    def anonymize_yuv(self, frames, fmt="nv12", **options):
+    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
-        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes."""
+        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``: as
+        ``anonymize``."""
+        if tiled:                                                       # frames of any even size: [B, h*3//2, w]
+            out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
+            return out, self.detect_tiled(out, tile, overlap, fmt, redact=options)
         frames = self._yuv_frames(frames)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
         dets = []

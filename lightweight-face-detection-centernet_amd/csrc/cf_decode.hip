@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void thresh_mask_kernel(ThreshParams p) {
             const float xx2 = fminf(a[2], q[2]), yy2 = fminf(a[3], q[3]);
             const float w = fmaxf(0.0f, xx2 - xx1 + 1.0f), h = fmaxf(0.0f, yy2 - yy1 + 1.0f);
             const float inter = w * h;
-            const float ovr = inter / (ia + qa - inter);
+            const float ovr = inter / (p.metric == 1 ? fminf(ia, qa) : ia + qa - inter);      // 1 = IoS: the smaller box's share (the tile merge)
             sup = ovr >= p.nms_thresh;
         }
         const unsigned long long bal = __ballot(sup);

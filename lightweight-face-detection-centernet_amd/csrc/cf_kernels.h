@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string>
+#include "centerface_hip.h"
 
 struct sp32_t;
 
@@ -292,6 +294,7 @@ struct ThreshParams {
     float rs_h, rs_w;     // > 0: emit floor(y / rs_h), floor(x / rs_w) (centerface.py:55-62); 0 = network coordinates
     int* host_counts;     // optional page-locked HOST mirrors, written by the sweep kernel over PCIe ([B] counts, [1] the final overflow word):
     int* host_overflow;   // with dets / lms in page-locked memory too the host needs no copy command at all, only an event wait
+    int metric;           // suppression measure of the mask stage: 0 = IoU (inter / union), 1 = IoS (inter / the smaller area; cf_tiles.hip)
 };
 hipError_t launch_decode_threshold(hipStream_t s, const ThreshParams& p);
 // apply per-image 2x3 affines to the (x1,y1),(x2,y2) corners of dets [B][K][stride] in place (utils/post_process.py:83-90)
@@ -382,6 +385,39 @@ RedactStage redact_stage_layout(int format, int h, int w);
 hipError_t redact_stage_copy(hipStream_t s, const RedactStage& st, int format, void* const* host_planes, int B, int h, int pitch0, int pitch1,
                              uint8_t* dev, bool to_device);
 hipError_t launch_redact_faces(hipStream_t s, const RedactParams& p);
+
+// Tiled detection (cf_tiles.hip).  The cutter writes dst [Bf * T][H][W][3] uint8 BGR: image f * T + t = the rectangle rects[t] of frame f,
+// converted (4:2:0) and resized to (H, W) as launch_yuv_to_bgr / launch_resize_u8 would the cropped frame.  planes: HOST table of
+// Bf x {p0, p1, p2} DEVICE addresses as RedactParams::planes (read only); rects: T rectangles on the DEVICE.
+// tile_grid: the rectangles of cf_tile_grid (host only).  tiles_check: nullptr, or what is wrong (the text lives in `why`; host only).
+int tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, cf_tile_rect* rects, int cap, int* n);
+const char* tiles_check(std::string& why, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_tile_rect* rects, int T, int H, int W);
+hipError_t launch_cut_tiles(hipStream_t s, int format, const void* const* planes, int Bf, int pitch0, int pitch1, const cf_tile_rect* rects,
+                            int T, uint8_t* dst, int H, int W);
+// The merge of the per-tile results of a threshold decode over Bf * T images of H x W: rows i < min(counts[img], rows) of dets_net
+// [Bf * T][rows][4], scores[(img * rows + i) * score_stride], lms_net [Bf * T][rows][10] are filtered (edge rule, non-finite corners),
+// mapped into the h x w frame and collected per frame in (tile, row) order; then rank / mask / sweep with `metric` and `thresh`.
+struct MergeParams {
+    const cf_tile_rect* rects;   // [T], device
+    int T, Bf, h, w, H, W;
+    const float* dets_net; const float* scores; int score_stride; const float* lms_net; const int* counts; int rows;
+    int metric; float thresh, edge;
+    // workspace (device), cap = T * rows candidates per frame
+    float* cand;          // [Bf][cap][16]
+    int* cand_count;      // [Bf]
+    int* order;           // [Bf][cap]
+    unsigned long long* mask;    // [Bf][cap][ceil(cap / 64)]: merge_mask_bytes
+    // outputs (device), frame pixels
+    int max_out;
+    float* dets;          // [Bf][max_out][5]
+    float* lms;           // [Bf][max_out][10]
+    float* corners;       // [Bf][max_out][4]: the box rows RedactParams::boxes takes with (H, W) = (h, w)
+    int* out_counts;      // [Bf], may exceed max_out
+    int* flags;           // [Bf]: bit 0 = some tile of the frame had counts > rows
+};
+size_t merge_mask_bytes(int Bf, int T, int rows);
+constexpr size_t kMergeMaskLimit = (size_t)256 << 20;      // refused with CF_ENOMEM above this, before any launch
+hipError_t launch_merge_tiles(hipStream_t s, const MergeParams& p);
 
 // layout converters used by cf_get_heads and the per-op test entry points
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*T NHWC*/,

@@ -785,4 +785,74 @@ int cf_op_redact(int device, const cf_redact_opts* o, int format, const cf_plane
     return sc.result("cf_op_redact");
 }
 
+int cf_tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, cf_tile_rect* rects, int cap, int* n) {
+    const int r = tile_grid(h, w, tile_h, tile_w, overlap, with_full, rects, cap, n);
+    if (r) g_op_error = "cf_tile_grid: h, w, tile_h, tile_w, overlap must be even, the sizes at least 2, 0 <= overlap < min(tile_h, tile_w); n not null";
+    return r;
+}
+
+// The cutter of cf_forward_tiles on host frames.  Every plane is copied up whole (rows x pitch bytes), each into its own allocation, so
+// the caller's padding bytes sit beside the pixels on the device and Scope's 0xFF pad follows every plane.
+int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1,
+                    const cf_tile_rect* rects, int T, int H, int W, uint8_t* tiles) {
+    static_assert(sizeof(cf_yuv_planes) == 3 * sizeof(void*), "cf_yuv_planes is a table of three addresses");
+    std::string why;
+    const char* bad = tiles_check(why, format, Bf, h, w, pitch0, pitch1, rects, T, H, W);
+    if (!bad) bad = redact_check_planes(format, reinterpret_cast<const void* const*>(host_frames), Bf, 0, pitch0, pitch1);
+    if (!bad && !tiles) bad = "null output";
+    if (!bad && (long long)Bf * T * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
+    if (bad) { g_op_error = std::string("cf_op_cut_tiles: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    const int np = format == CF_FRAME_BGR ? 1 : (format == CF_YUV_NV12 || format == CF_YUV_NV21) ? 2 : 3;
+    const void* const* hp = reinterpret_cast<const void* const*>(host_frames);
+    std::vector<const void*> dev((size_t)3 * Bf, nullptr);
+    for (int b = 0; b < Bf; ++b)
+        for (int k = 0; k < np; ++k) dev[3 * b + k] = sc.up(hp[3 * b + k], k == 0 ? (size_t)h * pitch0 : (size_t)(h / 2) * pitch1);
+    const cf_tile_rect* drects = (const cf_tile_rect*)sc.up(rects, (size_t)T * sizeof(cf_tile_rect));
+    const size_t out_bytes = (size_t)Bf * T * H * W * 3;
+    uint8_t* out = (uint8_t*)sc.alloc(out_bytes);
+    if (sc.err == hipSuccess) sc.chk(launch_cut_tiles(sc.s, format, dev.data(), Bf, pitch0, pitch1, drects, T, out, H, W));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(tiles, out, out_bytes, hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_cut_tiles");
+}
+
+int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* rects, int T, int Bf, int h, int w, int H, int W,
+                      const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                      float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+    std::string why;
+    const char* bad = nullptr;
+    if (!o || !dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags) bad = "null argument";
+    else if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) bad = "unknown metric (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)";
+    else if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) bad = "thresh and edge must be finite and not negative";
+    else if (rows < 1 || max_out < 1 || H < 1 || W < 1) bad = "rows, max_out, H and W must be at least 1";
+    else bad = tiles_check(why, CF_FRAME_BGR, Bf, h, w, 3 * w, 0, rects, T, H, 4);      // the geometry part: frame and rectangles
+    if (bad) { g_op_error = std::string("cf_op_merge_tiles: ") + bad; return CF_EINVAL; }
+    if ((long long)T * rows > (1 << 24) || merge_mask_bytes(Bf, T, rows) > kMergeMaskLimit) {
+        g_op_error = "cf_op_merge_tiles: the suppression bits of Bf x (T * rows) candidates exceed 256 MiB";
+        return CF_ENOMEM;
+    }
+    Scope sc(device);
+    const size_t n = (size_t)Bf * T * rows, cap = (size_t)T * rows, mo = (size_t)Bf * max_out;
+    MergeParams p{};
+    p.rects = (const cf_tile_rect*)sc.up(rects, (size_t)T * sizeof(cf_tile_rect));
+    p.T = T; p.Bf = Bf; p.h = h; p.w = w; p.H = H; p.W = W;
+    p.dets_net = (const float*)sc.up(dets_net, n * 4 * sizeof(float));
+    p.scores = (const float*)sc.up(scores, n * sizeof(float)); p.score_stride = 1;
+    p.lms_net = (const float*)sc.up(lms_net, n * 10 * sizeof(float));
+    p.counts = (const int*)sc.up(counts, (size_t)Bf * T * sizeof(int)); p.rows = rows;
+    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
+    p.cand = (float*)sc.alloc(Bf * cap * 16 * sizeof(float)); p.cand_count = (int*)sc.alloc(Bf * sizeof(int));
+    p.order = (int*)sc.alloc(Bf * cap * sizeof(int)); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, T, rows));
+    p.max_out = max_out;
+    p.dets = (float*)sc.up(dets, mo * 5 * sizeof(float)); p.lms = (float*)sc.up(lms, mo * 10 * sizeof(float));
+    p.corners = (float*)sc.alloc(mo * 4 * sizeof(float));
+    p.out_counts = (int*)sc.alloc(Bf * sizeof(int)); p.flags = (int*)sc.alloc(Bf * sizeof(int));
+    if (sc.err == hipSuccess) sc.chk(launch_merge_tiles(sc.s, p));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, p.dets, mo * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, p.lms, mo * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out_counts, p.out_counts, Bf * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(flags, p.flags, Bf * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_merge_tiles");
+}
+
 }  // extern "C"

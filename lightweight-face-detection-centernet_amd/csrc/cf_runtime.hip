@@ -124,6 +124,13 @@ struct cf_ctx {
     // cf_redact_faces: the network-coordinate box corners of the last threshold decode ([max_batch][t_maxout][4], beside t_lmsnet), the
     // mosaic's cell means (one dword per grid cell, grown to the largest grid seen) and the frames of the host form
     float* t_detsnet = nullptr; uint32_t* rd_cells = nullptr; size_t rd_cells_n = 0; uint8_t* rd_stage = nullptr; size_t rd_stage_bytes = 0;
+    // cf_forward_tiles / cf_merge_tiles: the rectangles of the last forward when it was a tiled one (tl_T = 0: it was not; host copy and
+    // device table, uploaded when they change), the frame geometry, and the merge's workspace and merged rows (tl_buf, grown on demand:
+    // cand, cand_count, order, mask | dets, lms, corners, counts, flags); tl_merged: a merge of the last decode is behind us, with
+    // tl_maxout rows per frame
+    std::vector<cf_tile_rect> tl_rects; cf_tile_rect* tl_rects_dev = nullptr; size_t tl_rects_bytes = 0; int tl_rects_up = 0;
+    int tl_T = 0, tl_Bf = 0, tl_h = 0, tl_w = 0, tl_maxout = 0; bool tl_merged = false;
+    void* tl_buf[9] = {}; size_t tl_have[9] = {};
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
     // input format, batch): the second forward with a key captures it, later ones replay it
     struct FwdGraph { const void* in; int fmt, B; hipGraphExec_t exec; bool broken; unsigned long long used; };
@@ -620,8 +627,9 @@ int cf_destroy(cf_ctx* c) {
     for (void* p : c->owned) hipFree(p);
     for (void* p : {(void*)c->src_stage, (void*)c->d_trans, (void*)c->hm_plane, (void*)c->keys, (void*)c->key_count, (void*)c->big, (void*)c->d_slot, (void*)c->d_dets, (void*)c->d_lms, (void*)c->d_inds, (void*)c->t_cand, (void*)c->t_count,
                     (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow,
-                    (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off, (void*)c->t_detsnet, (void*)c->rd_cells, (void*)c->rd_stage})
+                    (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off, (void*)c->t_detsnet, (void*)c->rd_cells, (void*)c->rd_stage, (void*)c->tl_rects_dev})
         if (p) hipFree(p);
+    for (void* p : c->tl_buf) if (p) hipFree(p);
     if (c->h_thr) hipHostFree(c->h_thr);
     if (c->ev_thr) hipEventDestroy(c->ev_thr);
     for (auto& ev : c->events) if (ev) hipEventDestroy(ev);
@@ -1097,6 +1105,7 @@ int launch_all_ops(cf_ctx* c, const void* net_in, int in_format, int B) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in_slot_used; c->al_rows = 0;      // what cf_align_faces samples
+    c->tl_T = 0; c->tl_merged = false;                    // (cf_forward_tiles sets its state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -1567,7 +1576,7 @@ static int thresh_launch(cf_ctx* c, int mode, float score_thresh, float nms_thre
     HIPCHK(c, hipMemsetAsync(c->t_overflow, 0, sizeof(int), c->stream));
     HIPCHK(c, launch_decode_threshold(c->stream, p));
     HIPCHK(c, hipEventRecord(c->ev_thr, c->stream));
-    c->al_rows = max_out;
+    c->al_rows = max_out; c->tl_merged = false;
     return CF_OK;
 }
 
@@ -1698,12 +1707,12 @@ int cf_align_faces(cf_ctx* c, const cf_align_opts* o, void* chips, double* matri
 // Redaction of the faces the last threshold decode kept, in frames the caller names (cf_redact.hip): the launches go on the stream that
 // carried the decode and read its device-side counts and network-coordinate box rows.  Host frames are staged in rd_stage and copied
 // back; the scratch of the mosaic's cell means grows to the largest grid seen, like the decode workspace.
-static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char* what) {
+static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char* what, const char* who = "cf_redact_faces") {
     if (*have >= need_bytes) return CF_OK;
     if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(*p); }        // earlier launches may still use it
     *p = nullptr; *have = 0;
     const hipError_t e = hipMalloc(p, need_bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_redact_faces: %zu bytes of %s: %s", need_bytes, what, hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "%s: %zu bytes of %s: %s", who, need_bytes, what, hipGetErrorString(e)); }
     *have = need_bytes;
     return CF_OK;
 }
@@ -1721,13 +1730,22 @@ int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_pla
     if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_redact_faces before cf_forward");
     if (!c->al_in) return c->fail(CF_ESTATE, "cf_redact_faces: an upload was started after the last forward");
     if (c->al_rows < 1 || !c->t_detsnet || !c->t_counts) return c->fail(CF_ESTATE, "cf_redact_faces without a threshold decode of the last forward");
-    if (B != c->last_B) return c->fail(CF_EINVAL, "cf_redact_faces: B=%d, the last forward had %d images", B, c->last_B);
+    const bool tiled = c->tl_T > 0;                                          // the boxes are the merged ones, in frame pixels
+    if (tiled) {
+        if (!c->tl_merged) return c->fail(CF_ESTATE, "cf_redact_faces after cf_forward_tiles without a cf_merge_tiles of the last decode");
+        if (B != c->tl_Bf) return c->fail(CF_EINVAL, "cf_redact_faces: B=%d, the tiled forward had %d frames", B, c->tl_Bf);
+        if (h != c->tl_h || w != c->tl_w) return c->fail(CF_EINVAL, "cf_redact_faces: %d x %d frames, the tiled forward had %d x %d", w, h, c->tl_w, c->tl_h);
+    } else if (B != c->last_B) return c->fail(CF_EINVAL, "cf_redact_faces: B=%d, the last forward had %d images", B, c->last_B);
     HIPCHK(c, hipSetDevice(c->device));
     RedactParams p{};
     p.format = format; p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
     p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
     p.B = B; p.h = h; p.w = w; p.H = c->H; p.W = c->W;
     p.boxes = c->t_detsnet; p.box_stride = c->al_rows; p.rows_cap = c->al_rows; p.faces_cap = c->al_rows; p.counts = c->t_counts;
+    if (tiled) {
+        p.H = h; p.W = w;
+        p.boxes = (const float*)c->tl_buf[6]; p.box_stride = c->tl_maxout; p.rows_cap = c->tl_maxout; p.faces_cap = c->tl_maxout; p.counts = (const int*)c->tl_buf[7];
+    }
     if (o->mode == CF_REDACT_MOSAIC) {
         size_t have = c->rd_cells_n * sizeof(uint32_t);
         int r = grow(c, (void**)&c->rd_cells, &have, redact_cells(B, h, w, o->cell) * sizeof(uint32_t), "mosaic cell means");
@@ -1755,6 +1773,129 @@ int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_pla
     HIPCHK(c, launch_redact_faces(c->stream, p));
     HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, false));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CF_OK;
+}
+
+// Tiled forward: the cutter (cf_tiles.hip) writes the Bf * T tile images to input_resized, so the plan and its graphs are those of
+// cf_forward_resized.  Host frames -- BGR ones too -- land in src_stage under its protocol, in the layout of the redaction's staging
+// (pitches rounded up to 4): one DMA for a dense block, else one pitched 2-D copy per plane per frame.  Device frames are read in place.
+int cf_forward_tiles(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0, int pitch1,
+                     const cf_tile_rect* rects, int T) {
+    if (!c) return CF_EINVAL;
+    if (!c->weights_loaded) return c->fail(CF_ESTATE, "cf_forward_tiles before cf_load_weights");
+    static_assert(sizeof(cf_yuv_planes) == 3 * sizeof(void*), "cf_yuv_planes is a table of three addresses");
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    std::string why;
+    if (tiles_check(why, format, Bf, h, w, pitch0, pitch1, rects, T, c->H, c->W)) return c->fail(CF_EINVAL, "cf_forward_tiles: %s", why.c_str());
+    if ((long long)Bf * T > c->max_batch) return c->fail(CF_EINVAL, "cf_forward_tiles: Bf * T = %d x %d exceeds max_batch %d", Bf, T, c->max_batch);
+    if (const char* bad = redact_check_planes(format, planes, Bf, in_on_device, pitch0, pitch1)) return c->fail(CF_EINVAL, "cf_forward_tiles: %s", bad);
+    HIPCHK(c, hipSetDevice(c->device));
+    CF_FLUSH_LANE(c);
+    const size_t rbytes = (size_t)T * sizeof(cf_tile_rect);
+    if (!c->tl_rects_up || c->tl_rects.size() != (size_t)T || memcmp(c->tl_rects.data(), rects, rbytes) != 0) {
+        c->tl_rects_up = 0;
+        int r = grow(c, (void**)&c->tl_rects_dev, &c->tl_rects_bytes, rbytes, "rectangles", "cf_forward_tiles"); if (r) return r;
+        c->tl_rects.assign(rects, rects + T);
+        HIPCHK(c, hipMemcpyAsync(c->tl_rects_dev, c->tl_rects.data(), rbytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));                      // (only when the table changes: the host copy may be replaced next call)
+        c->tl_rects_up = 1;
+    }
+    uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
+    if (!in_on_device) {
+        const RedactStage st = redact_stage_layout(format, h, w);
+        const size_t bytes = st.one * Bf;
+        int r = src_stage_begin(c, bytes); if (r) return r;
+        const hipStream_t cs = src_stage_stream(c, bytes);
+        const bool bgr = format == CF_FRAME_BGR, three = format == CF_YUV_I420 || format == CF_YUV_YV12;
+        const uint8_t* base = (const uint8_t*)frames[0].y;
+        bool dense = pitch0 == st.row0 && st.pitch0 == st.row0 && (bgr || (pitch1 == st.row1 && st.pitch1 == st.row1));
+        std::vector<const void*> dev((size_t)3 * Bf, nullptr);
+        for (int b = 0; b < Bf; ++b) {
+            const uint8_t* hf = base + b * st.one;
+            if (dense) dense = frames[b].y == hf && (bgr || frames[b].c0 == hf + st.off1) && (!three || frames[b].c1 == hf + st.off2);
+            uint8_t* f = c->src_stage + (size_t)b * st.one;
+            dev[3 * b] = f;
+            if (!bgr) dev[3 * b + 1] = f + st.off1;
+            if (three) dev[3 * b + 2] = f + st.off2;
+        }
+        if (dense) HIPCHK(c, hipMemcpyAsync(c->src_stage, base, bytes, hipMemcpyHostToDevice, cs));
+        else HIPCHK(c, redact_stage_copy(cs, st, format, reinterpret_cast<void* const*>(const_cast<cf_yuv_planes*>(frames)), Bf, h, pitch0, pitch1, c->src_stage, true));
+        if (cs != c->stream) {
+            HIPCHK(c, hipEventRecord(c->ev_src_copy, cs));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_src_copy, 0));
+        }
+        HIPCHK(c, launch_cut_tiles(c->stream, format, dev.data(), Bf, st.pitch0, st.pitch1, c->tl_rects_dev, T, dst, c->H, c->W));
+        HIPCHK(c, hipEventRecord(c->ev_src_free, c->stream));
+        c->src_busy = true;
+    } else {
+        HIPCHK(c, launch_cut_tiles(c->stream, format, planes, Bf, pitch0, pitch1, c->tl_rects_dev, T, dst, c->H, c->W));
+    }
+    int r = launch_all_ops(c, dst, CF_IN_U8_HWC_BGR, Bf * T);
+    if (r) return r;
+    c->last_B = Bf * T;
+    c->tl_T = T; c->tl_Bf = Bf; c->tl_h = h; c->tl_w = w;
+    return CF_OK;
+}
+
+// The merge of the last threshold decode's per-tile rows (cf_tiles.hip) on the stream that carried the decode: it reads the decode's
+// device-side counts, network-coordinate corners and landmarks and the score column of its dets (device memory, or the page-locked
+// host rows the sweep kernel wrote: device-visible either way).
+int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
+    if (!c) return CF_EINVAL;
+    if (!o) return c->fail(CF_EINVAL, "cf_merge_tiles: null options");
+    if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) return c->fail(CF_EINVAL, "cf_merge_tiles: unknown metric %d (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)", o->metric);
+    if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge))
+        return c->fail(CF_EINVAL, "cf_merge_tiles: thresh and edge must be finite and not negative");
+    if (max_out < 1) return c->fail(CF_EINVAL, "cf_merge_tiles: max_out=%d must be at least 1", max_out);
+    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_merge_tiles before cf_forward_tiles");
+    if (c->tl_T < 1) return c->fail(CF_ESTATE, "cf_merge_tiles: the last forward was not cf_forward_tiles");
+    if (!c->al_in) return c->fail(CF_ESTATE, "cf_merge_tiles: an upload was started after the last forward");
+    if (c->al_rows < 1 || !c->t_detsnet || !c->t_lmsnet || !c->t_counts || !c->t_dets) return c->fail(CF_ESTATE, "cf_merge_tiles without a threshold decode of the last forward");
+    const int Bf = c->tl_Bf, T = c->tl_T, rows = c->al_rows;
+    if ((long long)T * rows > (1 << 24) || merge_mask_bytes(Bf, T, rows) > kMergeMaskLimit)
+        return c->fail(CF_ENOMEM, "cf_merge_tiles: %d frames x %d tiles x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
+                       Bf, T, rows, merge_mask_bytes(Bf, T, rows) / 1e6);
+    HIPCHK(c, hipSetDevice(c->device));
+    c->tl_merged = false;
+    const size_t cap = (size_t)T * rows, mo = (size_t)Bf * max_out;
+    const size_t need[9] = {Bf * cap * 16 * sizeof(float), Bf * sizeof(int), Bf * cap * sizeof(int), merge_mask_bytes(Bf, T, rows),
+                            mo * 5 * sizeof(float), mo * 10 * sizeof(float), mo * 4 * sizeof(float), Bf * sizeof(int), Bf * sizeof(int)};
+    static const char* const what[9] = {"candidates", "candidate counts", "sort order", "suppression bits", "merged dets", "merged landmarks", "merged corners", "merged counts", "flags"};
+    for (int k = 0; k < 9; ++k) { int r = grow(c, &c->tl_buf[k], &c->tl_have[k], need[k], what[k], "cf_merge_tiles"); if (r) return r; }
+    MergeParams p{};
+    p.rects = c->tl_rects_dev; p.T = T; p.Bf = Bf; p.h = c->tl_h; p.w = c->tl_w; p.H = c->H; p.W = c->W;
+    p.dets_net = c->t_detsnet; p.scores = c->t_dets + 4; p.score_stride = 5; p.lms_net = c->t_lmsnet; p.counts = c->t_counts; p.rows = rows;
+    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
+    p.cand = (float*)c->tl_buf[0]; p.cand_count = (int*)c->tl_buf[1]; p.order = (int*)c->tl_buf[2]; p.mask = (unsigned long long*)c->tl_buf[3];
+    p.max_out = max_out; p.dets = (float*)c->tl_buf[4]; p.lms = (float*)c->tl_buf[5]; p.corners = (float*)c->tl_buf[6];
+    p.out_counts = (int*)c->tl_buf[7]; p.flags = (int*)c->tl_buf[8];
+    HIPCHK(c, launch_merge_tiles(c->stream, p));
+    c->tl_merged = true; c->tl_maxout = max_out;
+    if (out_on_device) {
+        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, need[4], hipMemcpyDeviceToDevice, c->stream));
+        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms, need[5], hipMemcpyDeviceToDevice, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, need[7], hipMemcpyDeviceToDevice, c->stream));
+        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, need[8], hipMemcpyDeviceToDevice, c->stream));
+        return CF_OK;
+    }
+    std::vector<int> hc((size_t)2 * Bf);
+    {   // hc lives on this stack frame: never return while a copy into it may still be in flight
+        const hipError_t e1 = hipMemcpyAsync(hc.data(), p.out_counts, need[7], hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipMemcpyAsync(hc.data() + Bf, p.flags, need[8], hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e3 = hipStreamSynchronize(c->stream);
+        HIPCHK(c, e1); HIPCHK(c, e2); HIPCHK(c, e3);
+    }
+    int nrows = 0;
+    for (int f = 0; f < Bf; ++f) nrows = std::max(nrows, std::min(hc[f], max_out));
+    if (nrows > 0 && (dets || lms)) {                    // only the rows that exist, as cf_decode_threshold_sized
+        if (dets) HIPCHK(c, hipMemcpy2DAsync(dets, (size_t)max_out * 5 * sizeof(float), p.dets, (size_t)max_out * 5 * sizeof(float),
+                                             (size_t)nrows * 5 * sizeof(float), Bf, hipMemcpyDeviceToHost, c->stream));
+        if (lms) HIPCHK(c, hipMemcpy2DAsync(lms, (size_t)max_out * 10 * sizeof(float), p.lms, (size_t)max_out * 10 * sizeof(float),
+                                            (size_t)nrows * 10 * sizeof(float), Bf, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (counts) memcpy(counts, hc.data(), need[7]);
+    if (flags) memcpy(flags, hc.data() + Bf, need[8]);
     return CF_OK;
 }
 

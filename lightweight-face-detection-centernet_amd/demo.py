@@ -57,11 +57,22 @@ def dump_event(detector, images, im_dir, names, save_path):
 
 def anonymize_file(path, out_path, **options):
     """Read one image file, redact every detected face on the device (``CenterFace.anonymize``; ``options``: mode, shape, cell,
-    scale, fill) and write the result to ``out_path`` (format from its extension).  Returns the detections."""
+    scale, fill) and write the result to ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``: sliced
+    inference with N x N tiles at native resolution (``CenterFace.detect_tiled``; the image is cropped to even sides), for images much
+    larger than N whose small faces a whole-frame resize would lose; the detections are then in image pixels."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
-    detector = CenterFace(frame.shape[0], frame.shape[1], dtype=options.pop("dtype", "bf16"))
+    tiled = int(options.pop("tiled", 0) or 0)
+    dtype = options.pop("dtype", "bf16")
+    if tiled:
+        from . import ops
+        frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
+        T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
+        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T)
+        options["tiled"] = True
+    else:
+        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype)
     try:
         frames, results = detector.anonymize([frame], **options)
     finally:
@@ -71,8 +82,9 @@ def anonymize_file(path, out_path, **options):
 
 
 def main(argv=None):
-    """``python -m centerface_amd.demo IMAGE [--anonymize OUT]``: print the detections of one image file; with ``--anonymize`` also
-    write the image with every face pixelated (or blanked: ``--mode solid``)."""
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT [--tiled N]]``: print the detections of one image file; with
+    ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``); with ``--tiled N`` beside it the
+    faces are found by sliced inference over N x N tiles at native resolution."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("image")
@@ -81,9 +93,12 @@ def main(argv=None):
     ap.add_argument("--shape", default="ellipse", choices=("ellipse", "rect"))
     ap.add_argument("--cell", type=int, default=20)
     ap.add_argument("--scale", type=float, default=1.3)
+    ap.add_argument("--tiled", type=int, default=0, metavar="N", help="with --anonymize: detect on overlapping N x N tiles (N a multiple of 32)")
     args = ap.parse_args(argv)
+    if args.tiled and not args.anonymize:
+        ap.error("--tiled goes with --anonymize")
     if args.anonymize:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled)
     else:
         from .centerface import CenterFace
         frame = imread(args.image)

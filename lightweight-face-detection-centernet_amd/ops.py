@@ -235,6 +235,58 @@ def redact_faces(frames, boxes, counts, net_hw, fmt="bgr", mode="mosaic", shape=
     return frames
 
 
+def tile_grid(h, w, tile, overlap, with_full=True):
+    """The rectangles of sliced inference (``cf_tile_grid``; host only): int32 [T][4] rows (x0, y0, w, h) covering an h x w frame with
+    tiles of ``tile`` = (tile_h, tile_w) or one int, neighbours sharing at least ``overlap`` pixels, row-major; the whole frame is
+    appended when ``with_full`` and there is more than one tile.  All values even."""
+    th, tw = (int(tile), int(tile)) if np.isscalar(tile) else (int(tile[0]), int(tile[1]))
+    n = C.c_int(0)
+    L = _lib.lib()
+    _lib.check(L.cf_tile_grid(int(h), int(w), th, tw, int(overlap), 1 if with_full else 0, None, 0, C.byref(n)), op=True)
+    tab = (_lib.TileRect * max(n.value, 1))()
+    _lib.check(L.cf_tile_grid(int(h), int(w), th, tw, int(overlap), 1 if with_full else 0, tab, n.value, C.byref(n)), op=True)
+    return np.array([[r.x0, r.y0, r.w, r.h] for r in tab[:n.value]], np.int32).reshape(-1, 4)
+
+
+def cut_tiles(frames, rects, size, fmt="bgr", device=0):
+    """The tile cutter (``cf_op_cut_tiles``): uint8 [Bf, T, H, W, 3] BGR, tile (f, t) = the rectangle ``rects[t]`` = (x0, y0, w, h) of
+    frame f, converted to BGR (4:2:0 formats) and resized to ``size`` = (H, W) with the taps clamped at the rectangle's edges.
+    ``frames`` as ``redact_faces`` takes them (BGR [B,h,w,3], dense 4:2:0 [B, h*3//2, w], or per-frame plane tuples of pitched rows: a
+    plane's buffer must hold rows x pitch bytes); they are only read."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    rt, T = _lib.tile_rects(rects)
+    H, W = int(size[0]), int(size[1])
+    out = np.empty((B, T, H, W, 3), np.uint8)
+    _lib.check(_lib.lib().cf_op_cut_tiles(device, _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, rt, T, H, W, ptr(out)), op=True)
+    del keep
+    return out
+
+
+def merge_tiles(rects, frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, metric="ios", thresh=0.5, edge=2.0, dets=None, lms=None,
+                device=0):
+    """The merge of per-tile detections (``cf_op_merge_tiles``): dets_net [Bf, T, rows, 4] box corners, scores [Bf, T, rows], lms_net
+    [Bf, T, rows, 10] in the coordinates of a ``net_hw`` = (H, W) network input, counts [Bf, T]; per tile the rows below min(count, rows)
+    are filtered by the edge rule, mapped into the ``frame_hw`` = (h, w) frame and de-duplicated per frame by greedy NMS with ``metric``
+    ('iou' | 'ios') and ``thresh``.  Returns (dets [Bf, max_out, 5], lms [Bf, max_out, 10], counts [Bf], flags [Bf]); rows at and past
+    a frame's count keep the bytes of the ``dets`` / ``lms`` arrays passed in (zeros by default)."""
+    rt, T = _lib.tile_rects(rects)
+    d = np.ascontiguousarray(dets_net, dtype=np.float32)
+    if d.ndim != 4 or d.shape[1] != T or d.shape[3] != 4:
+        raise ValueError("dets_net must be [Bf, T=%d, rows, 4], got %s" % (T, d.shape))
+    Bf, _, rows, _ = d.shape
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(Bf, T, rows)
+    lm = np.ascontiguousarray(lms_net, dtype=np.float32).reshape(Bf, T, rows, 10)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(Bf, T)
+    max_out = int(max_out)
+    od = np.zeros((Bf, max_out, 5), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(Bf, max_out, 5)
+    ol = np.zeros((Bf, max_out, 10), np.float32) if lms is None else np.ascontiguousarray(lms, dtype=np.float32).reshape(Bf, max_out, 10)
+    oc, fl = np.zeros((Bf,), np.int32), np.zeros((Bf,), np.int32)
+    o = _lib.merge_opts(metric, thresh, edge)
+    _lib.check(_lib.lib().cf_op_merge_tiles(device, C.byref(o), rt, T, Bf, int(frame_hw[0]), int(frame_hw[1]), int(net_hw[0]), int(net_hw[1]),
+                                            ptr(d), ptr(sc), ptr(lm), ptr(cn), rows, max_out, ptr(od), ptr(ol), ptr(oc), ptr(fl)), op=True)
+    return od, ol, oc, fl
+
+
 def ctdet_decode(heat, wh, reg=None, K=100, lm=None, device=0):
     """ctdet_decode (centerface_ext.py:52-82): (dets [B,K,6], lms [B,K,10]|None, inds [B,K] int64)."""
     heat, wh, reg, lm = f32(heat), f32(wh), f32(reg), f32(lm)

@@ -284,3 +284,137 @@ def test_fast_floor_division_equals_numpy_floor_divide():
                             np.nextafter(near, np.float32(-np.inf)), -near[:500], np.array([0.0, -0.0], np.float32)])
         ref, got = a // s, cfa.CenterFace._floordiv(a, s)
         assert got.dtype == np.float32 and np.array_equal(ref, got) and np.array_equal(np.signbit(ref), np.signbit(got)), s
+
+
+# ------------------------------------------------------------------------------- the exact-mode layer check's GPU-less half
+import exact_cases as X
+
+
+def _oracle_record(sd, img, defect=None):
+    """The float32 oracle run launch by launch, as an engine whose every entry is its own launch would record it (the unfused plan
+    + the head record), in the keys of ``exact_cases.engine_record``.  ``defect``: one deliberately wrong step --
+    "dw_tap" (layer3.1: the centre tap of the last output column reads the column to its left), "k_chunk" (layer5.1's project GEMM
+    without its last 8 input channels) or "stem_pad" (the stem's right / bottom zero pad replaced by edge replication)."""
+    import torch
+    import torch.nn.functional as F
+    from oracle import centerface_oracle as O
+    g = {"img_u8": img}
+    x = torch.from_numpy(np.concatenate([O.preprocess(im) for im in img]))
+    w = sd["first_conv.0.1.weight"]
+    cur = O.swish(F.conv2d(F.pad(x, [0, 1, 0, 1], mode="replicate"), w, None, 2)) if defect == "stem_pad" else O.conv_swish(x, w, 3, 2)
+    g["first_conv"] = cur
+    for prefix, cin, cout, t, k, s in X.BLOCKS:
+        src, j = cur, int(t != 1)
+        if t != 1:
+            src = g[prefix + ".expand"] = O.conv_swish(cur, sd[prefix + ".conv.0.1.weight"], 1, 1)
+        wd = sd["%s.conv.%d.1.weight" % (prefix, j)]
+        if defect == "dw_tap" and prefix == "layer3.1":
+            pre = F.conv2d(O.same_pad(src, k, s), wd, None, s, 0, 1, cin * t)
+            pre[..., -1] += wd[:, 0, k // 2, k // 2].reshape(1, -1, 1) * (src[..., -2] - src[..., -1])
+            d = O.swish(pre)
+        else:
+            d = O.conv_swish(src, wd, k, s, groups=cin * t)
+        g[prefix + ".dw"] = d
+        wp = sd["%s.conv.%d.weight" % (prefix, j + 1)]
+        y = F.conv2d(d[:, :-8], wp[:, :-8]) if (defect == "k_chunk" and prefix == "layer5.1") else F.conv2d(d, wp)
+        cur = g[prefix] = cur + y if (cin == cout and s == 1) else y
+    g["conv_last"] = O.conv_1x1_bn(cur, sd)
+    g["up1"] = O.idaup(g["conv_last"], g["layer4.1"], sd, "up1")
+    g["up2"] = O.idaup(g["up1"], g["layer2.1"], sd, "up2")
+    g["up3"] = O.idaup(g["up2"], g["layer1.1"], sd, "up3")
+    for name in ("hm", "wh", "lm", "reg"):
+        g[name] = O.head(g["up3"], sd, name)
+    g["hm_sigmoid"] = O.sigmoid_clamp(g["hm"])
+    return {k2: (v.numpy() if hasattr(v, "numpy") else v) for k2, v in g.items()}
+
+
+def _as_fused(g, dtype):
+    """The same tensors as the DEFAULT plan of ``dtype`` would record them: what a fused launch keeps on chip is left out."""
+    names = X.plan_entries(dtype)
+    keep = {"img_u8", "hm", "wh", "lm", "reg", "hm_sigmoid", "layer0.0"}
+    for n in names:
+        if n.endswith(".mbconv") or n.endswith(".project"):
+            keep.add(n.rsplit(".", 1)[0])
+        elif n.endswith(".expand+dw"):
+            keep.add(n.rsplit(".", 1)[0] + ".dw")
+        elif n in g:
+            keep.add(n)
+    out = {k2: v for k2, v in g.items() if k2 in keep}
+    if "conv_last+up1+up2" in names:
+        out["up2"], out["neck_fused"] = g["up2"], True
+    if "up3+heads" in names:
+        out["uphead_fused"] = True
+    return out, names
+
+
+@pytest.fixture(scope="module")
+def exact_oracle_records():
+    import torch
+    from oracle import centerface_oracle as O
+    torch.manual_seed(0)
+    sd = O.to_torch_sd(cfa.weights.synthetic_state_dict(0))
+    rng = np.random.default_rng(96 + 3 * 128)
+    img = rng.integers(0, 256, (2, 96, 128, 3), dtype=np.uint8)
+    return sd, img, _oracle_record(sd, img)
+
+
+def test_exact_layer_check_is_tied_to_the_pinned_oracle(exact_oracle_records):
+    """``exact_cases.check_layers64`` on the pinned float32 oracle's own features (two random uint8 images, 96x128), fed in as if they
+    were an engine's: float32 round-off is all that separates them from the float64 restatement, <= 0.25 of every bound (measured
+    <= 0.08).  The launch-by-launch float32 run that supplies the tensors ``O.forward`` does not expose (up1, up2, the expanded and
+    depthwise tensors) reproduces every feature ``O.forward`` does expose bit for bit, so each entry ends in a pinned tensor; the
+    fused entries of both default plans are checked on the same tensors."""
+    import torch
+    from oracle import centerface_oracle as O
+    sd, img, g = exact_oracle_records
+    out, feats = O.forward(sd, torch.from_numpy(np.concatenate([O.preprocess(im) for im in img])), return_features=True)
+    for k2, v in list(feats.items()) + list(out.items()):
+        assert np.array_equal(v.numpy(), g["first_conv" if k2 == "stem" else k2]), k2
+    ratios = X.check_layers64(sd, g, "fp32")
+    assert sorted(ratios) == sorted(X.plan_entries("fp32", fuse=False) + ["hm_sigmoid"]) and len(ratios) == 3 + 33 + 5 + 1
+    for dtype in X.DTYPES:
+        gf, names = _as_fused(g, dtype)
+        r = X.check_layers64(sd, gf, dtype)
+        assert sorted(r) == sorted(names + ["hm_sigmoid"]), sorted(r)
+        ratios.update({"%s/%s" % (dtype, k2): v for k2, v in r.items() if k2 not in ratios})
+    for k2, v in ratios.items():
+        print("EXACTLAYERS oracle 96x128 %s %.4f" % (k2, v))
+    assert max(ratios.values()) <= 0.25, {k2: v for k2, v in ratios.items() if v > 0.25}
+
+
+@pytest.mark.parametrize("defect,entry", [("dw_tap", "layer3.1.mbconv"), ("k_chunk", "layer5.1.project"), ("stem_pad", "first_conv+layer0.0")])
+def test_exact_layer_check_sees_one_injected_defect(exact_oracle_records, defect, entry):
+    """One wrong step in an otherwise correct float32 network -- a depthwise tap taken from the neighbouring column on the last
+    output column only, the last 8 input channels of a project GEMM dropped, the stem's zero pad replaced by edge replication --
+    puts the entry that holds it (a fused block, a single GEMM, the fused stem) more than 100 bounds out.  Teacher forcing keeps it
+    there: every entry upstream keeps its ratio to the bit, every entry downstream (whose inputs are now the defective network's
+    tensors) stays within the 0.25 of a correct one."""
+    sd, img, good = exact_oracle_records
+    dtype = "fp32_split" if entry.endswith(".project") else "fp32"           # (the default plan that runs the entry as a launch of its own)
+    gf, _ = _as_fused(_oracle_record(sd, img[:1], defect), dtype)
+    ref, _ = _as_fused(_oracle_record(sd, img[:1]), dtype)
+    r, r0 = X.check_layers64(sd, gf, dtype), X.check_layers64(sd, ref, dtype)
+    assert r[entry] > 100.0 and r0[entry] <= 0.25, (entry, r[entry], r0[entry])
+    names = list(r)
+    assert names == list(r0)
+    for n in names[:names.index(entry)]:
+        assert r[n] == r0[n], (n, r[n], r0[n])
+    others = {n: v for n, v in r.items() if n != entry}
+    assert max(others.values()) <= 0.25, {n: v for n, v in others.items() if v > 0.25}
+    print("EXACTLAYERS defect %s %s %.1f" % (defect, entry, r[entry]))
+
+
+def test_exact_plans_pick_the_expected_family_per_block():
+    """Which kernel family serves each of the 11 backbone blocks behind the fused stem, in both modes (``exact_cases.PLAN``, from which
+    tests/test_exact_layers.py takes the plan entries and kernel names it expects): the fused pick, and the engine's rule for
+    splitting a block -- no fused family, or Cout > 64 where the expand+depthwise family has the shape."""
+    for dtype in X.DTYPES:
+        assert [p for p, _ in X.PLAN[dtype]] == [b[0] for b in X.BLOCKS[1:]]
+        for (prefix, cin, cout, t, k, s), (_, fam) in zip(X.BLOCKS[1:], X.PLAN[dtype]):
+            mb = cfa.ops.mbconv_pick(cin, cin * t, cout, k, s, dtype)
+            xd = cfa.ops.expand_dw_pick(cin, cin * t, k, s, dtype)
+            assert xd["ok"] == (dtype == "fp32_split" and cout > 64) and (not xd["ok"] or xd["kind"] == "XD_F32"), (dtype, prefix, xd)
+            have = "XD_F32" if (xd["ok"] and (cout > 64 or not mb["ok"])) else mb["kind"]
+            assert have == fam and mb["ok"] == (cout <= 96), (dtype, prefix, mb, xd)
+    assert len(X.plan_entries("fp32")) == 1 + 8 + 9 + 5 and len(X.plan_entries("fp32_split")) == 1 + 6 + 10 + 2
+    assert len(X.plan_entries("fp32_split", neck=False, uphead=False)) == 1 + 6 + 10 + 5

@@ -1194,11 +1194,11 @@ def test_fused_neck_bit_equal_to_three_kernels(size, B, dtype):
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp32_split"])
-@pytest.mark.parametrize("size", [(96, 128), (160, 224), (352, 640)])
+@pytest.mark.parametrize("size", [(96, 128), (160, 224), (352, 640), (32, 32), (64, 416)])
 def test_fused_up3_heads_bit_equal_to_two_kernels(size, dtype):
     """cf_uphead.hip (last IDAUp stage + collapsed heads, neck output only in LDS) performs the same arithmetic
     in the same order as cf_pw.hip's IDAUp epilogue followed by cf_head.hip: bit-identical head maps, on map
-    sizes with partial tiles in both directions."""
+    sizes with partial tiles in both directions, an 8x8 map and a wide, low one (the sizes of its neck twin)."""
     H, W = size
     rng = np.random.default_rng(H + W)
     x = rng.integers(0, 256, (3, H, W, 3), dtype=np.uint8)

@@ -53,8 +53,21 @@ struct Mx {
 
 // ================================================================== expand + depthwise (project stays a GEMM launch)
 // grid = (tiles, hid / 32, batch); one round of 32 hidden channels per workgroup; only the depthwise output reaches HBM
-template <int KS, int JX, int TOH, int TOW, int NW, bool ALDS>
+//
+// MODE picks how pixels are addressed (profiles/r07_loop_overhead.md: a workgroup runs only ceil(NIB / NW) = 3 expand iterations and
+// one or two depthwise sets, so per-pixel bookkeeping is never amortised and was 40 % of the kernel's non-transcendental VALU):
+//   0       any size: 64-bit addresses, the layouts (MbParams::xblock / yblock) tested at run time, ZeroPad2d = clamped address +
+//           a zero select on every loaded dword (4 JX selects per pixel block)
+//   1 + XB + 2 YB + 4 ODD   x and y below 4 GiB and 2^24 pixels (checked by the launcher): 32-bit byte offsets, the layouts
+//           compile-time, and ZeroPad2d by ADDRESS -- a padded or out-of-tile pixel reads kXmxZeros instead of x: one pointer select
+//           per pixel block.  Only ODD, an odd chunk count (Cin = 56, 88, 152), keeps a data select, on the one chunk past the
+//           pixel's row.
+static __device__ __attribute__((aligned(16))) uint32_t kXmxZeros[10 * 512 / 4];      // JX <= 10 chunks, 512 bytes apart in pixel-block order
+
+template <int KS, int JX, int TOH, int TOW, int NW, bool ALDS, int MODE = 0>
 __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
+    constexpr bool FAST = MODE != 0, XB = FAST && ((MODE - 1) & 1), YB = FAST && ((MODE - 1) & 2), ODD = FAST && ((MODE - 1) & 4);
+    static_assert(JX <= 10, "kXmxZeros");
     typedef Mx<KS, JX, TOH, TOW, NW, ALDS> G;
     constexpr int IWQ = G::IWQ, IWP = G::IWP, IPX = G::IPX, NIB = G::NIB, CP = G::CP, NSET = G::NSET, WXB = G::WXB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -97,8 +110,30 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
     asm volatile("" ::: "memory");
     const char* xbase = (const char*)p.x + (size_t)b * p.Hin * p.Win * p.Cin * 2;
     const unsigned rowbytes = (unsigned)p.Cin * 2;
+    // FAST: pixel index of halo pixel (0, 0) over the batch (wraps below zero at the top / left edge: only pixels inside the map are
+    // addressed with it) and the lane half's chunk offset
+    const int gy0 = oy0 - p.pad_lo, gx0h = ox0 - p.pad_lo;
+    const unsigned pix00 = ((unsigned)b * (unsigned)p.Hin + (unsigned)gy0) * (unsigned)p.Win;
+    const unsigned lanec = (unsigned)(h * JX) * (XB ? 512u : 16u);
+    const unsigned blkrow = (unsigned)(p.Cin / 8) * 512u;
+    typedef const __attribute__((address_space(1))) char* gptr_t;
+    gptr_t zeros = (gptr_t)kXmxZeros;
+    asm volatile("" : "+s"(zeros));                     // one address for the kernel: not fetched again per pixel block
+    // a pixel block past the halo tile (ip >= IPX) lies at iy >= IH: folded into the row test
+    const unsigned hlim = (unsigned)min(p.Hin, gy0 + G::IH);
     auto load_x = [&](int ib, u32x4* xf) -> bool {
         const int ip = ib * 32 + pl;
+        if constexpr (FAST) {
+            const int iy = ip / IWP, ix = ip - iy * IWP;
+            const int gy = gy0 + iy, gx = gx0h + ix;
+            const bool valid = (unsigned)gy < hlim && (unsigned)gx < (unsigned)p.Win;
+            const unsigned pix = __umul24((unsigned)iy, (unsigned)p.Win) + (unsigned)gx + pix00;
+            const unsigned off = XB ? __umul24(pix >> 5, blkrow) + ((pix & 31u) << 4) + lanec : __umul24(pix, rowbytes) + lanec;
+            gptr_t xb = valid ? (gptr_t)p.x + off : zeros;
+#pragma unroll
+            for (int j = 0; j < JX; ++j) xf[j] = *(const __attribute__((address_space(1))) u32x4*)(xb + j * (XB ? 512 : 16));
+            return valid;
+        } else {
         const int ipc = ip < IPX ? ip : IPX - 1;
         const int iy = ipc / IWP, ix = ipc - iy * IWP;
         const int gy = oy0 - p.pad_lo + iy, gx = ox0 - p.pad_lo + ix;
@@ -113,15 +148,24 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
             for (int j = 0; j < JX; ++j) xf[j] = ld16(xbase + off + j * 16);
         }
         return ip < IPX && (unsigned)gy < (unsigned)p.Hin && (unsigned)gx < (unsigned)p.Win;
+        }
     };
     // an odd chunk count (Cin = 56, 88, 152): the upper half's last chunk lies past the pixel's row (the next pixel's, or past x for the
     // last one); its weights are zero, but 0 * NaN is NaN, so it is dropped like a padding pixel's
     const bool last_in = (h * JX + JX - 1) * 8 < p.Cin;
     auto mask_x = [&](u32x4* xf, bool valid) {
+        if constexpr (FAST) {
+            // a padded pixel already read zeros; last_in is false exactly for the upper half of an odd chunk count
+            if constexpr (ODD) {
+                u32x4& v = xf[JX - 1];
+                v.x = h ? 0u : v.x; v.y = h ? 0u : v.y; v.z = h ? 0u : v.z; v.w = h ? 0u : v.w;
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < JX; ++j) {
             const bool vj = j == JX - 1 ? (valid && last_in) : valid;
             xf[j].x = vj ? xf[j].x : 0u; xf[j].y = vj ? xf[j].y : 0u; xf[j].z = vj ? xf[j].z : 0u; xf[j].w = vj ? xf[j].w : 0u;
+        }
         }
     };
 #ifdef CF_ABLATION
@@ -129,17 +173,24 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
 #else
     constexpr int abl = 0;           // (the run-time tests cost the production kernel 4-7 %: compiled out)
 #endif
-    u32x4 xa[JX];
+    // the wave's pixel blocks wave, wave + NW, ...: unrolled, the X fragments of the next block in flight under the Swish of this
+    // one, in two register sets that swap by name (a rolled loop copies the prefetched set: 2 JX v_mov_b64 per iteration)
+    constexpr int MAXI = (NIB + NW - 1) / NW;
+    u32x4 xq[2][JX];
     bool va = false;
-    if (wave < NIB) va = load_x(wave, xa);
+    if (wave < NIB) va = load_x(wave, xq[0]);
     static_assert(NIB >= NW, "every wave issues the X loads the wait below keeps in flight");
     cf_sync_lds_dma_keep<(ALDS ? 0 : 2 * KS * 2) + JX>();      // expand weights / operand table (DMA, issued first) landed for every wave
-    mask_x(xa, va);
+    mask_x(xq[0], va);
 
     // ---- phase 1: expand + Swish -> quad cells.  D rows (r & 3) + 8 (r >> 2) + 4 h: register quad t = halo quad ib*8 + 2t + h
-    for (int ib = wave; ib < NIB; ib += NW) {
-        u32x4 xn[JX];
-        const bool more = ib + NW < NIB;
+#pragma unroll
+    for (int it = 0; it < MAXI; ++it) {
+        const int ib = wave + NW * it;
+        if (ib >= NIB) break;
+        u32x4* xa = xq[it & 1];
+        u32x4* xn = xq[(it + 1) & 1];
+        const bool more = it + 1 < MAXI && ib + NW < NIB;
         bool vn = false;
         if (more) { if (abl & 8) { for (int j = 0; j < JX; ++j) xn[j] = xa[j]; vn = va; } else vn = load_x(ib + NW, xn); }
         f32x16 a;
@@ -163,11 +214,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
             d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
             *reinterpret_cast<u32x2*>(ecell + 2 * t * CP) = d;
         }
-        if (more) {
-#pragma unroll
-            for (int j = 0; j < JX; ++j) xa[j] = xn[j];
-            mask_x(xa, vn);
-        }
+        if (more) mask_x(xn, vn);
     }
     __syncthreads();
 
@@ -199,8 +246,38 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
             }
         const int gy = oy0 + oy, gx0 = ox0 + 4 * oxq;
         if (!live || gy >= p.Hout || ((abl & 16) && acc[0][0] != 123.0f)) continue;
-        const size_t opix0 = ((size_t)b * p.Hout + gy) * p.Wout + gx0;
         const int chunk = grp * 4 + kg;                               // 8-channel chunk of the depthwise tensor
+        if constexpr (FAST) {
+            // one 32-bit offset per output quad.  Wout % 4 == 0 (wave-uniform): a quad never straddles the right edge, and in
+            // pixel-block order its four pixels are four consecutive 16-byte slots of one block (opix0 % 4 == 0)
+            if (gx0 >= p.Wout) continue;
+            const bool q4 = (p.Wout & 3) == 0;
+            const unsigned opix0 = __umul24((unsigned)b * (unsigned)p.Hout + (unsigned)gy, (unsigned)p.Wout) + (unsigned)gx0;
+            const unsigned yrow = (unsigned)p.hid * 2u, yblk = (unsigned)(p.hid / 8) * 512u;
+            char* yb = (char*)p.y;
+            if (YB && q4) {
+                const unsigned off = __umul24(opix0 >> 5, yblk) + ((opix0 & 31u) << 4) + (unsigned)chunk * 512u;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    u32x4 o;
+                    o.x = packb(acc[0][i], acc[1][i]); o.y = packb(acc[2][i], acc[3][i]);
+                    o.z = packb(acc[4][i], acc[5][i]); o.w = packb(acc[6][i], acc[7][i]);
+                    st16(yb + off + 16 * i, o);
+                }
+            } else {
+                const unsigned off0 = YB ? (unsigned)chunk * 512u : __umul24(opix0, yrow) + (unsigned)chunk * 16u;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (!q4 && gx0 + i >= p.Wout) break;
+                    u32x4 o;
+                    o.x = packb(acc[0][i], acc[1][i]); o.y = packb(acc[2][i], acc[3][i]);
+                    o.z = packb(acc[4][i], acc[5][i]); o.w = packb(acc[6][i], acc[7][i]);
+                    const unsigned opix = opix0 + i;
+                    st16(yb + (YB ? off0 + __umul24(opix >> 5, yblk) + ((opix & 31u) << 4) : off0 + (unsigned)i * yrow), o);
+                }
+            }
+        } else {
+        const size_t opix0 = ((size_t)b * p.Hout + gy) * p.Wout + gx0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (gx0 + i >= p.Wout) break;
@@ -214,6 +291,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
                 continue;
             }
             st16((char*)p.y + (p.yblock ? blk_off(opix, p.hid / 8, chunk) : (opix * p.hid + (size_t)chunk * 8) * 2), o);
+        }
         }
     }
 }
@@ -808,7 +886,18 @@ static hipError_t xmx_launch_t(hipStream_t s, const MbParams& p) {
     set_kernel_tag("void cf::expdw_mx_kernel<%d, %d, %d, %d, %d, %s>(cf::MbParams)", KS, JX, TOH, TOW, NW, ALDS ? "true" : "false");
     static const int abl = cf_ab_int("CF_MX_ABL", 0);      // timing experiments only: results invalid
     MbParams q = p; q.nw = abl;
-    return launch_lds<expdw_mx_kernel<KS, JX, TOH, TOW, NW, ALDS>>(grid, blk, G::LDS, s, q);
+    // 32-bit offsets: both tensors (pixel-block order pads the pixel count to 32; an odd chunk count reads 16 bytes past a row) below
+    // 4 GiB, pixel indices below 2^24 (24-bit multiplies); the timing experiments stay on the general kernel
+    const size_t mx = ((size_t)p.B * p.Hin * p.Win + 31) & ~(size_t)31, my = ((size_t)p.B * p.Hout * p.Wout + 31) & ~(size_t)31;
+    const bool small = abl == 0 && mx < ((size_t)1 << 24) && my < ((size_t)1 << 24) && mx * p.Cin * 2 + 16 < ((size_t)1 << 32) &&
+                       my * p.hid * 2 < ((size_t)1 << 32) && (size_t)p.Win < ((size_t)1 << 20);
+    if (!small) return launch_lds<expdw_mx_kernel<KS, JX, TOH, TOW, NW, ALDS, 0>>(grid, blk, G::LDS, s, q);
+    switch ((p.xblock ? 1 : 0) + (p.yblock ? 2 : 0) + ((p.Cin & 8) ? 4 : 0)) {
+#define CF_XMX_MODE(M) case M: return launch_lds<expdw_mx_kernel<KS, JX, TOH, TOW, NW, ALDS, M + 1>>(grid, blk, G::LDS, s, q);
+    CF_XMX_MODE(0) CF_XMX_MODE(1) CF_XMX_MODE(2) CF_XMX_MODE(3) CF_XMX_MODE(4) CF_XMX_MODE(5) CF_XMX_MODE(6) CF_XMX_MODE(7)
+#undef CF_XMX_MODE
+    }
+    return hipErrorInvalidValue;
 }
 #include CF_EXP_INC(cf_mbconv3_2)
 #include CF_EXP_INC(cf_mbconv3_3)

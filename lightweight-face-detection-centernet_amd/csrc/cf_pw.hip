@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void pw_wlds_kernel(PwParams p) {
     constexpr int KT = 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];      // [NBW][KT][1 KiB]
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: the DMA addresses below are scalar work
     const int pl = lane & 31, h = lane >> 5;
     const long long pb = (long long)blockIdx.x * 4 + wave;
     const long long m = pb * 32 + pl;
@@ -227,24 +227,42 @@ __global__ __launch_bounds__(256) void pw_wlds_kernel(PwParams p) {
         // outstanding-instruction count per tile is a compile-time constant
 #pragma unroll
         for (int q = 0; q < NBW * KT / 4; ++q) {                 // straight-line: the compiler must be able to count vm ops
-            const int c = wave + 4 * q;
-            const int i = c / KT, jj = c - i * KT;
+            static_assert(KT == 4, "fragment c = wave + 4 q of the tile is (n-block q, k-step wave)");
+            const int i = q, jj = wave;
             const int ii = nb0 + i < NB ? nb0 + i : NB - 1, jc = j0 + jj < NCh ? j0 + jj : NCh - 1;
-            const char* src = (const char*)p.wp + ((((size_t)ii * NCh + jc) * 64) + lane) * 16;
+            const char* src = (const char*)p.wp + (((size_t)ii * NCh + jc) * 64) * 16 + lane * 16;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(stage + (i * KT + jj) * 1024), 16, 0, 0);
         }
         // no select on the loaded value here (it would force the wait at issue time): a chunk past this
         // half's share is read from a clamped address and meets ZERO weights (pw_pack_weights leaves the
-        // fragment of a missing chunk zero); whole k-steps past NCh are skipped at consumption
+        // fragment of a missing chunk zero); whole k-steps past NCh are skipped at consumption.
+        // Every tile but the last lies inside both halves' shares (wave-uniform test): its four chunks are the tile pointer plus
+        // constants, no per-chunk clamp
+        if (j0 + KT <= NC - NCh) {
+            const char* xt = xrow + (size_t)j0 * xs;
+            if (p.xblock) {
 #pragma unroll
-        for (int jj = 0; jj < KT; ++jj) xn[jj] = ld16(xrow + (size_t)(j0 + jj < jmax ? j0 + jj : 0) * xs);
+                for (int jj = 0; jj < KT; ++jj) xn[jj] = ld16(xt + jj * 512);
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < KT; ++jj) xn[jj] = ld16(xt + jj * 16);
+            }
+        } else {
+#pragma unroll
+            for (int jj = 0; jj < KT; ++jj) xn[jj] = ld16(xrow + (size_t)(j0 + jj < jmax ? j0 + jj : 0) * xs);
+        }
     };
     const int nbv = NB - nb0 < NBW ? NB - nb0 : NBW;
     u32x4 xr[NST][KT];
 #pragma unroll
     for (int s0 = 0; s0 < NST - 1; ++s0)
         if (s0 < NT) prefetch(s0, smem + s0 * STAGE, xr[s0]);
+    // The K loop exists twice: ALLNB = every n-block of this workgroup exists (wave-uniform; every workgroup but the last n-group of a
+    // layer whose N is no multiple of 32 NBW) runs without a test around its MFMAs.  With both forms in ONE loop the accumulators of
+    // the two paths lived in different registers and two whole blocks were copied after every tile (16 v_mov_b64).
+    auto kloop = [&](auto allnb) {
+    constexpr bool ALLNB = decltype(allnb)::value;
     for (int t0 = 0; t0 < NT; t0 += NST) {
 #pragma unroll
         for (int u = 0; u < NST; ++u) {
@@ -265,34 +283,28 @@ __global__ __launch_bounds__(256) void pw_wlds_kernel(PwParams p) {
                     if (jj + 1 < kt) {
 #pragma unroll
                         for (int i = 0; i < NBW; ++i)
-                            if (i < nbv) Mma<T>::run2(acc[i], ld16(st + (i * KT + jj) * 1024 + lane * 16), ld16(st + (i * KT + jj + 1) * 1024 + lane * 16),
-                                                      xr[u][jj], xr[u][jj + 1]);
+                            if (ALLNB || i < nbv) Mma<T>::run2(acc[i], ld16(st + (i * KT + jj) * 1024 + lane * 16), ld16(st + (i * KT + jj + 1) * 1024 + lane * 16),
+                                                               xr[u][jj], xr[u][jj + 1]);
                     } else if (jj < kt) {
 #pragma unroll
                         for (int i = 0; i < NBW; ++i)
-                            if (i < nbv) Mma<T>::run(acc[i], ld16(st + (i * KT + jj) * 1024 + lane * 16), xr[u][jj]);
+                            if (ALLNB || i < nbv) Mma<T>::run(acc[i], ld16(st + (i * KT + jj) * 1024 + lane * 16), xr[u][jj]);
                     }
                 }
-            } else if (nbv == NBW) {                              // wave-uniform: all n-blocks of this workgroup exist
-#pragma unroll
-                for (int jj = 0; jj < KT; ++jj) {
-                    if (jj < kt) {
-#pragma unroll
-                        for (int i = 0; i < NBW; ++i) Mma<T>::run(acc[i], ld16(st + (i * KT + jj) * 1024 + lane * 16), xr[u][jj]);
-                    }
-                }
-            } else {                                       // last n-group of a layer whose N is not a multiple of 32 NBW
+            } else {
 #pragma unroll
                 for (int jj = 0; jj < KT; ++jj) {
                     if (jj < kt) {
 #pragma unroll
                         for (int i = 0; i < NBW; ++i)
-                            if (i < nbv) Mma<T>::run(acc[i], ld16(st + (i * KT + jj) * 1024 + lane * 16), xr[u][jj]);
+                            if (ALLNB || i < nbv) Mma<T>::run(acc[i], ld16(st + (i * KT + jj) * 1024 + lane * 16), xr[u][jj]);
                     }
                 }
             }
         }
     }
+    };
+    if (nbv == NBW) kloop(std::true_type{}); else kloop(std::false_type{});
     if (!mvalid) return;
 #pragma unroll
     for (int i = 0; i < NBW; ++i) {

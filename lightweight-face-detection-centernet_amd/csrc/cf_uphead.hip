@@ -13,6 +13,8 @@
 #include "cf_exp.h"
 #include "cf_common.h"
 #include "cf_kernels.h"
+#include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 namespace cf {
@@ -171,6 +173,233 @@ __global__ __launch_bounds__(NW * 64) void uphead_kernel(UpHeadParams p) {
     }
 }
 
+// ---- bf16 (the benchmarked mode): a workgroup walks a RUN of 16 x 32 tiles instead of one.  Tiles are numbered image -> tile column ->
+// tile row, workgroup w of G owns tiles [w T / G, (w + 1) T / G): consecutive tiles of a run are vertically adjacent except where a
+// column or an image ends.  Once per workgroup: the head-weight DMA, the 1x1 conv fragments, the per-lane tile coordinates (tile origins
+// are multiples of 16 / 32, so a lane's (ty, tx), its deconv tap and its LDS cell are the same for every tile) and the bias / tap / shift
+// tables, which live in LDS (as neck_kernel's Tb) instead of being read from global memory behind the MFMA.  Per tile: the global loads of
+// tile k + 1 are issued before phase B of tile k and consumed by phase A of tile k + 1, so the memory round trip runs under the head conv
+// and its record stores; where tile k + 1 lies directly below tile k, its halo rows 0-1 are tile k's rows 16-17 and are copied inside LDS
+// instead of being fetched and computed again.  The arithmetic of a pixel is that of uphead_kernel<bf16_t, true, 16, 8, true>, operation
+// for operation.
+struct UhRuns {
+    typedef Uh<bf16_t, 16, 8> U;
+    static constexpr int NW = 8, TH = 16, IH = TH + 2;
+    static constexpr int TBF = 24 + 96 + 24 + 16;                  // floats: bias | upw[4][24] | upb | b0
+    static constexpr int TB_OFF = U::LDS, WC_OFF = TB_OFF + TBF * 4, LDS = WC_OFF + 2048;          // the tables; the 1x1 conv fragments
+    static constexpr int ROW_B = UH_IW * U::PIT;                   // one tile row in LDS
+    static constexpr int SHARED_CHUNKS = 2 * ROW_B / 16;           // rows 16-17 -> rows 0-1
+    static_assert(U::MAXB == 3 && U::NIB == 20 && U::NCH == 2 && U::G == 2 && U::SPD == 5 && U::CPD == 9, "written out for this geometry");
+    static_assert(SHARED_CHUNKS <= NW * 64 && WC_OFF % 16 == 0 && TB_OFF % 16 == 0, "one chunk per thread; 16-byte LDS reads");
+};
+
+// LDS-only barrier: every LDS access of this wave has completed, then s_barrier.  (The workgroup fence of __syncthreads() may also wait
+// for the vector-memory counter, and the prefetch loads and record stores are exactly what must stay in flight across the barrier.)
+__device__ __forceinline__ void uh_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Buffer access with the hardware range check as the predicate: an offset at or past the descriptor's byte count reads zeros / stores
+// nothing, and the instruction is issued all the same (uphead_runs_kernel relies on fixed instruction counts per tile).
+typedef __amdgpu_buffer_rsrc_t uh_rsrc_t;
+constexpr unsigned UH_OOB = 0x80000000u;
+__device__ __forceinline__ uh_rsrc_t uh_rsrc(const void* base, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
+}
+typedef __attribute__((ext_vector_type(4))) unsigned int uh_v4u;
+__device__ __forceinline__ u32x4 uh_bload(uh_rsrc_t r, unsigned off) {
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+}
+__device__ __forceinline__ void uh_bstore_nt(const u32x4& v, uh_rsrc_t r, unsigned off) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uh_v4u, v), r, (int)off, 0, 2);      // aux 2 = nt
+}
+__device__ __forceinline__ void uh_bstore32(unsigned v, uh_rsrc_t r, unsigned off) {
+    __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)off, 0, 0);
+}
+
+__global__ __launch_bounds__(UhRuns::NW * 64) __attribute__((amdgpu_waves_per_eu(4)))
+void uphead_runs_kernel(UpHeadParams p, int TX, int TY, unsigned tq, unsigned tr) {
+    typedef UhRuns R;
+    typedef R::U U;
+    typedef bf16_t T;
+    constexpr int PIT = U::PIT, NW = R::NW, UH_TH = R::TH;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* T3 = smem;
+    char* Wh = smem + U::T3B;
+    char* Rs = Wh + U::WHB;
+    float* Tb = reinterpret_cast<float*>(smem + R::TB_OFF);
+    char* Wc = smem + R::WC_OFF;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int pl = lane & 31, h = lane >> 5;
+
+    // this workgroup's run: tiles [t, t1) = [floor(w T / G), floor((w + 1) T / G)) with T = tq G + tr
+    const unsigned G = gridDim.x, wg = blockIdx.x;
+    unsigned t = wg * tq + wg * tr / G;
+    const unsigned t1 = (wg + 1) * tq + (wg + 1) * tr / G;
+    int b, col, row;
+    { const unsigned per = (unsigned)(TX * TY), bi = t / per, rem = t - bi * per, ci = rem / (unsigned)TY;
+      b = (int)bi; col = (int)ci; row = (int)(rem - ci * (unsigned)TY); }
+
+    // per lane, the same for every tile: halo pixel (ty, tx) of its three blocks (a block past the tile gets ty >= 18: never valid); its
+    // offsets from the pixel above-left of the tile origin in skip and in low and its deconv tap follow from it
+    int tyx[3];
+    const int wl = p.w >> 1;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int ip = (wave + NW * k) * 32 + pl;
+        const int ty = ip / UH_IW, tx = ip - ty * UH_IW;
+        tyx[k] = (ty << 8) | tx;
+    }
+    const int cell0 = (wave * 32 + pl) * PIT;                      // block k: + k * NW * 32 * PIT
+    const char* brow = T3 + (wave * UH_IW + pl) * PIT + h * (U::SPD * 16);       // phase B: output row `wave` (+ 8), lane half's chunks
+
+    u32x4 xs[3][2], lw[3][2];
+    // the halo rows / columns of tile (col, row) that lie inside the map
+    auto bounds = [&](int col_, int row_, int& ylo, int& ynum, int& xlo, int& xnum) {
+        const int oy0 = row_ * UH_TH, ox0 = col_ * UH_TW;
+        ylo = oy0 == 0 ? 1 : 0; ynum = min(R::IH, p.h - oy0 + 1) - ylo;
+        xlo = ox0 == 0 ? 1 : 0; xnum = min(UH_IW, p.w - ox0 + 1) - xlo;
+    };
+    // All global loads of a tile, as buffer loads through a descriptor of the tile's window: a lane with nothing to fetch (a pixel outside
+    // the map, the chunk past the row, a block the previous tile already holds, no tile at all) gets an offset past the window, which
+    // the range check answers with zeros without touching memory.  Every wave therefore issues the same twelve instructions for every
+    // tile and the compiler's vmcnt waits in phase A are exact counts that leave the record stores behind them in flight.
+    // `shared`: rows 0-1 come from the previous tile (blocks 0 and 1 are those rows only)
+    auto issue = [&](int b_, int col_, int row_, bool shared, bool any) {
+        int ylo, ynum, xlo, xnum; bounds(col_, row_, ylo, ynum, xlo, xnum);
+        const int oy0 = row_ * UH_TH, ox0 = col_ * UH_TW;
+        // the window starts at the pixel above-left of the tile origin; that may lie before the tensor, a valid lane's offset leads inside
+        const long long sb = (((long long)b_ * p.h + oy0 - 1) * p.w + ox0 - 1) * PIT;
+        const long long lb = (((long long)b_ * (p.h >> 1) + (oy0 >> 1) - 1) * wl + (ox0 >> 1) - 1) * PIT;
+        const uh_rsrc_t sk = uh_rsrc((const char*)p.skip + sb, any ? (R::IH * p.w + UH_IW) * PIT : 0);
+        const uh_rsrc_t lo = uh_rsrc((const char*)p.low + lb, any ? ((R::IH / 2 + 1) * wl + UH_IW / 2 + 1) * PIT : 0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int ty = tyx[k] >> 8, tx = tyx[k] & 255;
+            const bool ok = (unsigned)(ty - ylo) < (unsigned)ynum && (unsigned)(tx - xlo) < (unsigned)xnum && !(shared && wave + NW * k < 2);
+            // lane half h: chunks 2h, 2h + 1 (chunk 3 does not exist)
+            const unsigned xo = ok ? (unsigned)((ty * p.w + tx) * PIT + h * 32) : UH_OOB;
+            const unsigned lo_ = ok ? (unsigned)((((ty + 1) >> 1) * wl + ((tx + 1) >> 1)) * PIT + h * 32) : UH_OOB;
+            xs[k][0] = uh_bload(sk, xo); lw[k][0] = uh_bload(lo, lo_);
+            xs[k][1] = uh_bload(sk, h == 0 ? xo + 16 : UH_OOB); lw[k][1] = uh_bload(lo, h == 0 ? lo_ + 16 : UH_OOB);
+        }
+    };
+    // ---- phase A (uphead_kernel's, from the prefetched registers and the LDS tables)
+    auto phase_a = [&](int col_, int row_, bool shared) {
+        int ylo, ynum, xlo, xnum; bounds(col_, row_, ylo, ynum, xlo, xnum);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int ib = wave + NW * k;
+            if (ib >= U::NIB) break;
+            if (shared && ib < 2) continue;
+            const int ty = tyx[k] >> 8, tx = tyx[k] & 255;
+            const bool valid = (unsigned)(ty - ylo) < (unsigned)ynum && (unsigned)(tx - xlo) < (unsigned)xnum;
+            const bool keep = !(shared && ty < 2);             // block 2 holds four pixels of row 1
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+            mma_chain<T, 2>(acc, [&](int j) { return ld16(Wc + (j * 64 + lane) * 16); }, [&](int j) { return xs[k][j]; });
+            const int tap = (((ty + 1) & 1) << 1) | ((tx + 1) & 1);       // parity of the map row / column (origins are even)
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                const int ch = h * 16 + g * 8;
+                if (ch >= 24) break;
+                float v[8], r[8];
+                unpack16<T>(lw[k][g], r);
+#pragma unroll
+                for (int q = 0; q < 8; q += 4) {               // the tables four channels at a time: twelve registers, not twenty-four
+                    float bs[4], uw[4], ub[4];
+                    unpack16<float>(ld16(Tb + ch + q), bs);
+                    unpack16<float>(ld16(Tb + 24 + tap * 24 + ch + q), uw);
+                    unpack16<float>(ld16(Tb + 120 + ch + q), ub);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[q + e] = relu_f(acc[g * 8 + q + e] + bs[e]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[q + e] += relu_f(r[q + e] * uw[e] + ub[e]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                u32x4 o = pack16<T>(v);
+                if (!valid) o = zero16();
+                if (keep) st16(T3 + cell0 + k * (NW * 32 * PIT) + ch * (int)sizeof(T), o);
+            }
+        }
+    };
+
+    // the first tile's loads go out first, the once-per-workgroup pieces behind them: head weights and conv fragments by LDS-DMA, the tables
+    issue(b, col, row, false, true);
+    for (int c = wave; c < U::WHB / 1024; c += NW)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)p.w0p + c * 1024 + lane * 16),
+                                         (__attribute__((address_space(3))) void*)(Wh + c * 1024), 16, 0, 0);
+    if (wave < 2)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)p.wcv + wave * 1024 + lane * 16),
+                                         (__attribute__((address_space(3))) void*)(Wc + wave * 1024), 16, 0, 0);
+    if (tid < R::TBF) Tb[tid] = tid < 24 ? p.bias[tid] : tid < 120 ? p.upw[tid - 24] : tid < 144 ? p.upb[tid - 120] : p.b0[tid - 144];
+
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this wave's LDS-DMAs have landed (phase A is about to wait for the loads anyway)
+    uh_lds_barrier();
+    phase_a(col, row, false);
+    for (;;) {
+        uh_lds_barrier();                                          // the tile is complete
+
+        // ---- the next tile of the run: its loads go out now and come back under phase B
+        const bool more = t + 1 < t1;
+        int nb = b, ncol = col, nrow = row + 1;
+        bool nshared = more;
+        if (nrow == TY) { nrow = 0; nshared = false; if (++ncol == TX) { ncol = 0; ++nb; } }
+        issue(nb, ncol, nrow, nshared, more);
+
+        // ---- phase B (uphead_kernel's): output rows `wave` and `wave + 8` of the tile, one block of 32 cells each
+        const int ox0 = col * UH_TW, oy0 = row * UH_TH;
+        const int wcells = min(UH_TW, p.w - ox0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int oy = wave + NW * i;
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+                const char* rp = brow + (NW * i + dy) * R::ROW_B;
+                // the tenth chunk (upper lane half, j = 4) does not exist: what is read there (inside T3) is replaced by zeros
+                mma_chain<T, 5>(acc, [&](int j) { return ld16(Wh + ((dy * 5 + j) * 64 + lane) * 16); },
+                                [&](int j) { u32x4 xc = ld16(rp + j * 16); if (j == 4 && h) xc = zero16(); return xc; });
+            }
+            const int gy = oy0 + oy;
+            float b0a[4], b0b[4], out[8];
+            unpack16<float>(ld16(Tb + 144 + h * 4), b0a); unpack16<float>(ld16(Tb + 152 + h * 4), b0b);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { out[r] = acc[r] + b0a[r]; out[4 + r] = acc[4 + r] + b0b[r]; }
+            if (h == 0) {
+                float sg = 1.0f / (1.0f + expf(-out[0]));
+                sg = fminf(fmaxf(sg, 1e-4f), 1.0f - 1e-4f);
+                out[0] = sg;
+            }
+            // the stores go through descriptors of this map row's cells inside the tile (none when the row is below the map): the range
+            // check drops the rest, and the store count per tile is the same for every wave
+            const size_t mrow = ((size_t)b * p.h + gy) * p.w + ox0;
+            const int ncell = gy < p.h ? wcells : 0;
+            uh_bstore32(__float_as_uint(out[0]), uh_rsrc(p.hm_plane + mrow, p.hm_plane ? ncell * 4 : 0), h == 0 ? (unsigned)(pl * 4) : UH_OOB);
+            char* rs = Rs + wave * 2048;
+            st16(rs + pl * 64 + h * 16, pack16<float>(&out[0]));
+            st16(rs + pl * 64 + 32 + h * 16, pack16<float>(&out[4]));
+            __builtin_amdgcn_wave_barrier();
+            const uh_rsrc_t hr = uh_rsrc(p.heads + mrow * 16, ncell * 64);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int q = lane + 64 * k;                                // 16-byte piece q of the row: record q / 4
+                uh_bstore_nt(ld16(rs + q * 16), hr, (unsigned)(q * 16));
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (!more) break;
+        u32x4 keep2 = zero16();
+        const bool copies = nshared && tid < R::SHARED_CHUNKS;
+        if (copies) keep2 = ld16(T3 + (R::IH - 2) * R::ROW_B + tid * 16);
+        uh_lds_barrier();                                          // every wave is done reading the tile
+        if (copies) st16(T3 + tid * 16, keep2);
+        b = nb; col = ncol; row = nrow; ++t;
+        phase_a(col, row, nshared);
+    }
+}
+
 template <typename T, bool CO, int TH, int NW, bool NT>
 static hipError_t uphead_launch_t(hipStream_t s, const UpHeadParams& q) {
     typedef Uh<T, TH, NW> U;
@@ -179,15 +408,44 @@ static hipError_t uphead_launch_t(hipStream_t s, const UpHeadParams& q) {
     return launch_lds<uphead_kernel<T, CO, TH, NW, NT>>(grid, blk, U::LDS, s, q);
 }
 
+// Workgroups of uphead_runs_kernel the device holds at once: two per CU (61.6 KB of LDS and 8 waves of <= 128 VGPRs each).  The CU count
+// is asked once per device.
+static int uphead_slots() {
+    static std::atomic<int> cus[32];
+    int dev = 0; (void)hipGetDevice(&dev);
+    std::atomic<int>& slot = cus[dev & 31];
+    int n = slot.load(std::memory_order_relaxed);
+    if (n <= 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 1;
+        slot.store(n, std::memory_order_relaxed);
+    }
+    return 2 * std::min(n, 16384);
+}
+
+// G = min(T, slots) workgroups, workgroup w walks tiles [w T / G, (w + 1) T / G): with T <= slots every workgroup has one tile and every
+// tile its own workgroup (single images and small batches lose no CUs), above that the runs differ by at most one tile.
+static hipError_t uphead_runs_launch(hipStream_t s, const UpHeadParams& q) {
+    const int TX = (q.w + UH_TW - 1) / UH_TW, TY = (q.h + UhRuns::TH - 1) / UhRuns::TH;
+    const long long T = (long long)TX * TY * q.B;
+    if (T > 0x7fffffffLL) return hipErrorInvalidValue;
+    const unsigned G = (unsigned)std::min<long long>(T, uphead_slots());
+    set_kernel_tag("cf::uphead_runs_kernel(cf::UpHeadParams, int, int, unsigned int, unsigned int)");
+    return launch_lds<uphead_runs_kernel>(dim3(G), dim3(UhRuns::NW * 64), UhRuns::LDS, s, q, TX, TY, (unsigned)(T / G), (unsigned)(T % G));
+}
+
 hipError_t launch_uphead(hipStream_t s, int dtype, const UpHeadParams& p) {
     if (p.B <= 0) return hipSuccess;
     static const bool xcd_on = cf_ab_int("CF_UH_XCD", 0) >= 1;      // A/B only: 0.090 -> 0.094 ms with it
     UpHeadParams q = p; q.xcd = xcd_on ? 1 : 0;
 #include CF_EXP_INC(cf_uphead_0)
-    // bf16: 16 x 32 tiles on eight waves, non-temporal record stores: halo rows 2 / 8 -> 2 / 16 of the skip / low fetch (B = 64, 640x640,
-    // HIP events, same box: 8x32 / 4 waves 79.0 us, + non-temporal 78.1, 16x32 / 8 waves 73.2, + non-temporal 72.3; 16x32 / 4 waves 84.9,
-    // 32x32 / 8 waves 86.4, 8x32 / 8 waves 91.4); every variant is bit-identical to the two-kernel path (test_fused_up3_heads_...)
-    if (dtype == 1) return uphead_launch_t<bf16_t, true, 16, 8, true>(s, q);
+    // bf16: 16 x 32 tiles on eight waves, non-temporal record stores, a run of tiles per workgroup (uphead_runs_kernel: 115 VGPRs, no
+    // scratch, 65,152 B of LDS, two workgroups per CU).  B = 64, 640x640, same box and session, parent build against this one: rocprofv3
+    // 72.7 -> 58.5 us per launch (23 launches each), HIP events 76.1 -> 61.9 us, bench step 1.1714 / 1.1714 -> 1.1619 / 1.1606 ms
+    // (profiles/r08_uphead_runs.md).  The one-tile geometry before it was chosen on HIP events: 8x32 / 4 waves 79.0 us, + non-temporal
+    // 78.1, 16x32 / 8 waves 73.2, + non-temporal 72.3; 16x32 / 4 waves 84.9, 32x32 / 8 waves 86.4, 8x32 / 8 waves 91.4.  Every variant is
+    // bit-identical to the two-kernel path (test_fused_up3_heads_..., tests/test_uphead_runs.py).  XCD-aware tile order of the one-tile
+    // kernel was measured slower (0.090 -> 0.094 ms) and is not offered for the runs.
+    if (dtype == 1) return uphead_runs_launch(s, q);
     // fp32 tile (twice the LDS per pixel): 8 x 32 tiles on eight waves, 77.8 KB = two workgroups per CU.  B = 64, 640x640: 0.132 ms
     // (four waves 0.154, 16x32 / 8 waves 0.159, 4x32 / 4 waves 0.187) against 0.103 + 0.149 for the two launches
     if (dtype == 2) return uphead_launch_t<sp32_t, true, 8, 8, true>(s, q);

@@ -1,6 +1,7 @@
 // experiments build only (make EXP=1): cut out of cf_uphead.hip
     static const int var = cf_ab_int("CF_UH_VARIANT", 0);           // A/B sweep of tile height / waves / non-temporal record stores
     if (dtype == 1) {
+        if (cf_ab_int("CF_UH_RUNS", 1) == 0) return uphead_launch_t<bf16_t, true, 16, 8, true>(s, q);     // one tile per workgroup
         if (cf_ab_int("CF_UH_COALESCE", 1) == 0) return uphead_launch_t<bf16_t, false, 8, 4, false>(s, q);
         switch (var) {
             case 1: return uphead_launch_t<bf16_t, true, 8, 4, true>(s, q);

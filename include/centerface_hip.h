@@ -237,7 +237,7 @@ typedef struct cf_align_opts {
  * sampled from the uint8 BGR batch the network read in that forward -- whichever entry point put it there (cf_forward with
  * CF_IN_U8_HWC_BGR from host or device, cf_forward_resized, cf_forward_images / _uploaded, cf_forward_yuv); a device input of
  * cf_forward must still be unchanged.  Landmarks are taken in NETWORK coordinates whatever cf_set_rescale says, so the chips are
- * cut from the network-sized batch (sampling a full-resolution source behind cf_forward_resized is not offered).  Face
+ * cut from the network-sized batch (cf_align_faces_frame below samples the full-resolution source instead).  Face
  * n = offsets[b] + i is keep position i of image b; offsets [B + 1] = exclusive prefix sum of min(counts[b], the decode's max_out,
  * max_per_image).  Only faces n < cap_faces are written; offsets[B] is the number WANTED, so offsets[B] > cap_faces tells the
  * caller of the truncation (call again with more room).  chips: [cap_faces] chips in opts->format; matrices (may be NULL):
@@ -248,6 +248,32 @@ typedef struct cf_align_opts {
  * work; CF_ESTATE without a threshold decode behind the last forward, after a CF_IN_F32_NCHW forward, or once another upload or
  * forward was started on ctx. */
 int cf_align_faces(cf_ctx* ctx, const cf_align_opts* opts, void* chips, double* matrices, int32_t* offsets, int cap_faces, int out_on_device);
+/* The same chips cut from the SOURCE FRAMES instead of the network-sized batch: the read-side twin of cf_redact_faces.  A 1080p frame
+ * behind a 640 x 640 context keeps three times the resolution of the face that cf_align_faces would upscale.  frames[b] (b < B, all
+ * h x w in `format`: CF_YUV_* with the planes of cf_yuv_planes, or CF_FRAME_BGR with the [h][pitch0] pixel rows in .y), pitches and
+ * in_on_device exactly as for cf_forward_tiles, except that BGR frames may have odd sides: sides 2..8192, even for 4:2:0; device
+ * planes and pitches multiples of 4, read in place; host frames are copied up first (row bytes only).  The frames are named by the
+ * caller, so it does not matter which entry point fed the forward (a CF_IN_F32_NCHW forward is fine: the network batch is not read).
+ * Which faces -- as cf_redact_faces:
+ *   * after cf_forward_tiles: the merged rows of the last cf_merge_tiles, whose landmarks are in frame pixels already; B must be Bf and
+ *     (h, w) the tiled frame's (CF_EINVAL otherwise); CF_ESTATE without a merge;
+ *   * otherwise: the rows the last threshold decode kept, in NETWORK coordinates whatever cf_set_rescale says; every value is mapped
+ *     X = (double)x * ((double)w / (double)W), Y = (double)y * ((double)h / (double)H) and kept as a double, and the similarity is
+ *     fitted to the mapped points (the map is anisotropic when h / H != w / W); B must equal the last forward's batch.
+ * The source pixel at (sy, sx) is the three bytes at p0 + sy * pitch0 + 3 * sx (BGR), or the BT.601 conversion of cf_forward_yuv
+ * applied to Y[sy][sx] and the chroma sample at (sy >> 1, sx >> 1): the chip equals, bit for bit, the chip cf_op_align_faces cuts
+ * from the frame converted by cf_op_yuv_to_bgr at (H, W) = (h, w).  Estimate, fixed-point warp, border rule, the alignable rule and
+ * the all-zero matrix / all-zero-source chip of an unalignable face are those of cf_align_faces (restated in tests/test_align.py);
+ * `matrices` are chip -> FRAME pixel maps.  Sampling is bilinear at a point: a face much larger than the chip is not area-filtered
+ * (neither is cv2.warpAffine's).  opts, chips, matrices, offsets ([B + 1]; offsets[B] = the number wanted), cap_faces,
+ * max_per_image and out_on_device are exactly as for cf_align_faces.  With device frames and device outputs nothing is read on the
+ * host and the call is asynchronous on the stream that carried the decode or the merge; with host frames or host outputs it blocks.
+ * CF_EINVAL for every bad argument before any GPU work (ctx == NULL: the arguments are still checked, cf_op_last_error names the
+ * cause); CF_ESTATE without a threshold decode behind the last forward, or once another upload or forward was started on ctx.  The
+ * call changes no state of ctx: a cf_redact_faces, cf_align_faces or second cf_align_faces_frame behind it behaves as before. */
+int cf_align_faces_frame(cf_ctx* ctx, const cf_align_opts* opts, int format, const cf_yuv_planes* frames, int in_on_device,
+                         int B, int h, int w, int pitch0, int pitch1,
+                         void* chips, double* matrices, int32_t* offsets, int cap_faces, int out_on_device);
 
 /* ---- face redaction: blank or pixelate every kept face IN THE SOURCE FRAME, on the device ------------------------------------ */
 /* Anonymising video: every face the detector kept is covered in the full-resolution frame -- BGR or 4:2:0, a decoder's surface in
@@ -329,7 +355,7 @@ int cf_tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_ful
  * are read in place (addresses and pitches multiples of 4); 0: host frames, copied up first (only the row bytes are read).
  * CF_EINVAL before anything is enqueued, the offending rectangle named in cf_last_error.  The context remembers the rectangles and
  * the frame size for cf_merge_tiles; every other forward or upload forgets them.  cf_get_resized_input returns the tile batch;
- * cf_align_faces works per tile image. */
+ * cf_align_faces works per tile image; cf_align_faces_frame, after cf_merge_tiles, per frame on the merged rows. */
 int cf_forward_tiles(cf_ctx* ctx, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w,
                      int pitch0, int pitch1, const cf_tile_rect* rects, int T);
 /* Merges the rows the LAST THRESHOLD DECODE kept for the Bf * T tile images of the last cf_forward_tiles, per frame.  Per tile the rows
@@ -604,6 +630,12 @@ int cf_op_yuv_to_bgr(int device, int yuv_format, const uint8_t* frames, uint8_t*
  * image after image, counts [B] (>= 0, N = their sum): chips [N] in opts->format, matrices [N,6] float64 (may be NULL). */
 int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, const float* lms, const int32_t* counts,
                       const cf_align_opts* opts, void* chips, double* matrices);
+/* The kernel of cf_align_faces_frame alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up, so the
+ * padding bytes are on the device beside the pixels; pitches multiples of 4): lms [N,10] float32 landmark rows in FRAME pixels, image
+ * after image, counts [B] (>= 0, N = their sum): chips [N] in opts->format, matrices [N,6] float64 (may be NULL).  The same validation
+ * as cf_align_faces_frame, before any device is touched. */
+int cf_op_align_frame(int device, int format, const cf_yuv_planes* host_frames, int B, int h, int w, int pitch0, int pitch1,
+                      const float* lms, const int32_t* counts, const cf_align_opts* opts, void* chips, double* matrices);
 /* The kernels of cf_redact_faces alone, on host frames (modified in place): boxes [sum counts][4] x1,y1,x2,y2 in the coordinates of an
  * H x W network input, image after image, counts [B] (>= 0).  The same validation as cf_redact_faces, before any device is touched. */
 int cf_op_redact(int device, const cf_redact_opts* opts, int format, const cf_planes_rw* host_frames, int B, int h, int w, int pitch0,

@@ -42,7 +42,7 @@ EXPORTS = (
     "cf_profile_forward", "cf_plan_size", "cf_plan_op", "cf_forward_trace", "cf_graph_stats", "cf_get_streams", "cf_streams_share_queue", "cf_streams_share_queue_ex", "cf_spread_streams", "cf_reroll_streams", "cf_ctdet_loss", "cf_comm_unique_id", "cf_comm_create", "cf_comm_create_all", "cf_comm_create_loopback", "cf_comm_loopback_rank", "cf_comm_destroy", "cf_comm_abort", "cf_comm_query", "cf_comm_synchronize", "cf_comm_last_error", "cf_comm_debug", "cf_comm_set_shard", "cf_comm_stream", "cf_gather_topk", "cf_host_alloc", "cf_host_free", "cf_pinned_alloc", "cf_pinned_free", "cf_host_register", "cf_host_unregister", "cf_device_alloc", "cf_device_free", "cf_memcpy_h2d", "cf_memcpy_d2h",
     "cf_op_last_error", "cf_op_last_kernel", "cf_op_shufflev2", "cf_op_mbconv", "cf_op_expand_dw", "cf_op_mbconv_pick", "cf_op_expand_dw_pick", "cf_op_ctdet_loss", "cf_op_encode_targets", "cf_op_dwconv", "cf_op_pwconv", "cf_op_pwconv_ex", "cf_op_stem", "cf_op_idaup", "cf_op_heads",
     "cf_op_ctdet_decode", "cf_op_ctdet_post_process", "cf_op_decode_threshold", "cf_op_decode_threshold_ex", "cf_op_nms", "cf_op_box_match",
-    "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces", "cf_redact_faces", "cf_op_redact",
+    "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces", "cf_align_faces_frame", "cf_op_align_frame", "cf_redact_faces", "cf_op_redact",
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
 )
 
@@ -244,6 +244,36 @@ def frame_planes(frames, fmt, writable=True):
     return tab, B, h, w, pitch0, pitch1, keep
 
 
+def device_planes(plane_ptrs):
+    """PlanesRW table of B tuples (p0, p1, p2) of device addresses (missing planes None)."""
+    tab = (PlanesRW * max(len(plane_ptrs), 1))()
+    for b, t in enumerate(plane_ptrs):
+        t = (tuple(t) if isinstance(t, (tuple, list)) else (t,)) + (None, None)
+        tab[b].p0, tab[b].p1, tab[b].p2 = (int(v) if v else None for v in t[:3])
+    return tab
+
+
+def frames_pitch4(tab, fmt, B, h, w, pitch0, pitch1):
+    """The host frames of a ``frame_planes`` table with every pitch a multiple of 4: the table as it is when they are, else a new table
+    over padded copies (zero padding).  Returns (table, pitch0, pitch1, arrays to keep alive)."""
+    f = frame_format(fmt)
+    bgr, il = f == CF_FRAME_BGR, f in (CF_YUV_NV12, CF_YUV_NV21)
+    if pitch0 % 4 == 0 and (bgr or pitch1 % 4 == 0):
+        return tab, pitch0, pitch1, None
+    geo = [(h, 3 * w if bgr else w, pitch0)] + ([] if bgr else [(h // 2, w if il else w // 2, pitch1)] * (1 if il else 2))
+    out, keep = (PlanesRW * max(B, 1))(), []
+    for b in range(B):
+        for k, (rows, rowbytes, pitch) in enumerate(geo):
+            src = getattr(tab[b], "p%d" % k)
+            n = (rows - 1) * pitch + rowbytes
+            flat = np.frombuffer((C.c_uint8 * n).from_address(src), np.uint8)
+            dst = np.zeros((rows, (rowbytes + 3) & ~3), np.uint8)
+            dst[:, :rowbytes] = np.lib.stride_tricks.as_strided(flat, (rows, rowbytes), (pitch, 1))
+            keep.append(dst)
+            setattr(out[b], "p%d" % k, dst.ctypes.data)
+    return out, (geo[0][1] + 3) & ~3, 0 if bgr else (geo[1][1] + 3) & ~3, keep
+
+
 def yuv_format(fmt):
     """CF_YUV_* code of a format name ('nv12', 'nv21', 'i420' / 'yuv420p', 'yv12'); integer codes pass through unchanged (the
     library validates them)."""
@@ -303,6 +333,8 @@ def lib():
         L.cf_op_yuv_to_bgr.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
         L.cf_align_faces.argtypes = [C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.cf_op_align_faces.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p]
+        L.cf_align_faces_frame.argtypes = [C.c_void_p, C.POINTER(AlignOpts), C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int] * 2
+        L.cf_op_align_frame.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p]
         L.cf_redact_faces.argtypes = [C.c_void_p, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 6
         L.cf_op_redact.argtypes = [C.c_int, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.cf_tile_grid.argtypes = [C.c_int] * 6 + [C.POINTER(TileRect), C.c_int, C.POINTER(C.c_int)]

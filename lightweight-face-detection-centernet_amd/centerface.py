@@ -348,6 +348,45 @@ class Engine(object):
         self._chk(self._L.cf_align_faces(self._h, C.byref(o), C.c_void_p(int(chips_ptr)), C.c_void_p(int(matrices_ptr)) if matrices_ptr else None,
                                          C.c_void_p(int(offsets_ptr)), int(cap_faces), 1))      # (the template is read during the call)
 
+    def align_faces_frame(self, frames, fmt="bgr", size=112, *, max_faces=None, out="u8", rgb=False, mean=0.0, scale=1.0, template=None,
+                          max_per_image=0):
+        """Aligned chips cut from the SOURCE frames (``cf_align_faces_frame``, host form): as ``align_faces``, but every face is sampled
+        at the resolution it has in ``frames`` -- host arrays as ``redact_faces`` takes them (BGR uint8 [B,h,w,3], dense 4:2:0 uint8
+        [B, h*3//2, w], or per-frame plane tuples of pitched rows), only read -- instead of the network-sized batch.  Behind a plain
+        forward the faces are those the preceding ``decode_threshold`` kept, their network-coordinate landmarks mapped to the frame by
+        w / W, h / H in float64 (whatever ``set_rescale`` says), B the forward's batch; behind ``forward_tiles_enqueue`` +
+        ``merge_tiles`` they are the merged rows, B the number of frames.  Returns (chips, offsets [B+1], matrices [N,6] chip -> frame
+        pixel maps)."""
+        tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+        o, tm, shape, dtype = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
+        cap = int(getattr(self, "_last_kept", 0)) if max_faces is None else int(max_faces)
+        while True:
+            chips = np.empty((max(cap, 1),) + shape, dtype)
+            mats = np.empty((max(cap, 1), 6), np.float64)
+            offs = np.zeros((B + 1,), np.int32)
+            self._chk(self._L.cf_align_faces_frame(self._h, C.byref(o), _lib.frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1,
+                                                   _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
+            if max_faces is not None or int(offs[-1]) <= cap:
+                break
+            cap = int(offs[-1])
+        del keep
+        n = min(int(offs[-1]), cap)
+        return chips[:n], offs, mats[:n]
+
+    def align_faces_frame_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1, chips_ptr, offsets_ptr, cap_faces, matrices_ptr=None,
+                                 size=112, *, out="u8", rgb=False, mean=0.0, scale=1.0, template=None, max_per_image=0):
+        """Same, reading DEVICE planes in place -- a decoder's surfaces: ``plane_ptrs`` = B tuples (p0, p1, p2) of device addresses as
+        ``redact_faces_device`` takes them (addresses and pitches multiples of 4) -- and writing caller-owned DEVICE buffers as
+        ``align_faces_device`` does.  Asynchronous on the engine's main stream behind the decode or the merge; no count is read on
+        the host."""
+        if int(B) != len(plane_ptrs):
+            raise ValueError("align_faces_frame_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
+        tab = _lib.device_planes(plane_ptrs)
+        o, tm, _, _ = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
+        self._chk(self._L.cf_align_faces_frame(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1),
+                                               C.c_void_p(int(chips_ptr)), C.c_void_p(int(matrices_ptr)) if matrices_ptr else None,
+                                               C.c_void_p(int(offsets_ptr)), int(cap_faces), 1))      # (the template is read during the call)
+
     # -- face redaction in the source frame ------------------------------------------------------
     def redact_faces(self, frames, fmt="bgr", *, mode="mosaic", shape="ellipse", cell=20, scale=1.3, fill=(0, 0, 0)):
         """Blank or pixelate, in ``frames``, the faces the preceding ``decode_threshold`` kept (``cf_redact_faces``, blocking form): the
@@ -803,6 +842,50 @@ class CenterFace(object):
             chips, offs, _ = self.engine.align_faces(size, **chip_options)
             return [(d, l, chips[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(results)]
         return self._detect_chunks(imgs, with_chips)
+
+    def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, **chip_options):
+        """Detection plus the aligned chip of every detection cut from the FRAME ITSELF (``Engine.align_faces_frame``), not from the
+        network-sized batch: one (dets, lms, chips) per frame, dets / lms in frame pixels.  ``frames``: BGR uint8 [B,h,w,3]
+        (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] ('nv12', 'nv21', 'i420', 'yv12') of the (height, width) this instance was
+        built for; they go through ``forward_resized`` / ``forward_yuv`` and the results are those of ``detect_batch`` /
+        ``detect_yuv`` (floor-divided to frame pixels).  ``tiled=True``: frames of any even size, detected by ``detect_tiled``'s path
+        (``tile``, ``overlap``); the chips are those of the merged detections, which are in frame pixels and not floor-divided.
+        ``chip_options``: out, rgb, mean, scale, template."""
+        if not self.landmarks:
+            raise ValueError("detect_aligned_frames needs the landmarks: construct CenterFace(..., landmarks=True)")
+        bgr = _lib.frame_format(fmt) == _lib.CF_FRAME_BGR
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != (4 if bgr else 3):
+            raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (frames.shape,))
+        eng, out = self.engine, []
+
+        def with_chips(chunk, results):
+            chips, offs, _ = eng.align_faces_frame(chunk, fmt, size, **chip_options)
+            return [(d, l, chips[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(results)]
+        if tiled:
+            _, B, h, w, _, _, _ = _lib.frame_planes(frames, fmt, writable=False)
+            rects, per = self._tile_geometry(h, w, tile, overlap, True)
+            for i in range(0, B, per):
+                chunk = frames[i:i + per]
+                eng.forward_tiles_enqueue(chunk, rects, fmt)
+                eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
+                res, _ = eng.merge_tiles(max_out=self.max_dets)
+                eng._last_kept = sum(len(d) for d, _ in res)
+                out.extend(with_chips(chunk, res))
+            return out
+        want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
+        if frames.shape[1:] != want:
+            raise ValueError("frames must be %s per frame (this instance was built for %dx%d), got %s" % ((want,) + self.src_hw + (frames.shape[1:],)))
+        eng.set_rescale(self.scale_h, self.scale_w)                          # centerface.py:55-62 inside the decode kernel
+        try:
+            for i in range(0, len(frames), eng.max_batch):
+                chunk = frames[i:i + eng.max_batch]
+                eng.forward_resized_enqueue(chunk) if bgr else eng.forward_yuv_enqueue(chunk, fmt)
+                res = self._postprocess_many(eng.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)
+                out.extend(with_chips(chunk, res))
+        finally:
+            eng.set_rescale(0.0, 0.0)
+        return out
 
     def _tile_geometry(self, h, w, tile, overlap, with_full):
         th, tw = (self.img_h_new, self.img_w_new) if tile is None else (int(tile), int(tile)) if np.isscalar(tile) else (int(tile[0]), int(tile[1]))

@@ -386,6 +386,25 @@ hipError_t redact_stage_copy(hipStream_t s, const RedactStage& st, int format, v
                              uint8_t* dev, bool to_device);
 hipError_t launch_redact_faces(hipStream_t s, const RedactParams& p);
 
+// Aligned face chips cut from the caller's frames (cf_align_frame.hip): the estimate, warp and outputs of AlignParams (a.img, a.img_dwords,
+// a.H, a.W unused; a.B = the number of frames), sampling B pitched frames of h x w in `format` instead of the network batch.  A landmark
+// value x (y) of a.lms is taken as (double)x * sx ((double)y * sy): sx = w / W, sy = h / H for network-coordinate rows, 1.0 for rows
+// that are in frame pixels already.  4:2:0 pixels are converted by cf_yuvmath.h as they are read.
+struct AlignFrameParams {
+    AlignParams a;
+    int format;                  // CF_YUV_NV12 .. CF_YUV_YV12, CF_FRAME_BGR
+    const void* const* planes;   // HOST table of B x {p0, p1, p2} DEVICE addresses as RedactParams::planes (read only), 4-byte aligned
+    int h, w, pitch0, pitch1;    // pitches in bytes, multiples of 4
+    double sx, sy;
+};
+// geometry and chip options of cf_align_faces_frame / cf_op_align_frame: nullptr, or what is wrong (host only; fills p.a's options,
+// the format and the geometry).  on_device: the planes are read where they are (alignment rules), else they will be staged.
+const char* align_frame_check(AlignFrameParams& p, int size, int chip_format, int rgb, float mean, float scale, const float* tmpl,
+                              int max_per_image, int format, const void* const* planes, int on_device, int B, int h, int w, int pitch0, int pitch1);
+hipError_t launch_align_frame(hipStream_t s, const AlignFrameParams& p);
+// sets the text cf_op_last_error returns (cf_ops.hip): for a refusal that has no context to carry it
+void op_error_set(const char* text);
+
 // Tiled detection (cf_tiles.hip).  The cutter writes dst [Bf * T][H][W][3] uint8 BGR: image f * T + t = the rectangle rects[t] of frame f,
 // converted (4:2:0) and resized to (H, W) as launch_yuv_to_bgr / launch_resize_u8 would the cropped frame.  planes: HOST table of
 // Bf x {p0, p1, p2} DEVICE addresses as RedactParams::planes (read only); rects: T rectangles on the DEVICE.

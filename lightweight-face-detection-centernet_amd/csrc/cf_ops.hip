@@ -118,6 +118,11 @@ std::vector<float> make_records(const float* hm, const float* wh, const float* r
 
 }  // namespace
 
+namespace cf {
+// what cf_op_last_error reports, for an entry point of cf_runtime.hip that was called without a context
+void op_error_set(const char* text) { g_op_error = text; }
+}  // namespace cf
+
 extern "C" {
 
 const char* cf_op_last_error(void) { return g_op_error.c_str(); }
@@ -737,6 +742,46 @@ int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, cons
     if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(chips, p.chips, one * n, hipMemcpyDeviceToHost, sc.s));
     if (sc.err == hipSuccess && matrices) sc.chk(hipMemcpyAsync(matrices, p.mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
     return sc.result("cf_op_align_faces");
+}
+
+// The kernel of cf_align_faces_frame on host frames.  Every plane is copied up whole (rows x pitch bytes), each into its own allocation,
+// so the caller's padding bytes sit beside the pixels on the device and Scope's 0xFF pad follows every plane.
+int cf_op_align_frame(int device, int format, const cf_yuv_planes* host_frames, int B, int h, int w, int pitch0, int pitch1,
+                      const float* lms, const int32_t* counts, const cf_align_opts* o, void* chips, double* matrices) {
+    static_assert(sizeof(cf_yuv_planes) == 3 * sizeof(void*), "cf_yuv_planes is a table of three addresses");
+    const void* const* hp = reinterpret_cast<const void* const*>(host_frames);
+    AlignFrameParams p{};
+    const char* why = nullptr;
+    if (!o || !chips || !counts) why = "null options, chips or counts";
+    if (!why) why = align_frame_check(p, o->size, o->format, o->rgb, o->mean, o->scale, o->tmpl, o->max_per_image, format, hp, 0, B, h, w, pitch0, pitch1);
+    if (!why && ((pitch0 & 3) || (format != CF_FRAME_BGR && (pitch1 & 3)))) why = "pitches must be multiples of 4 (the planes are read on the device as they are)";
+    long long N = 0;
+    for (int b = 0; !why && b < B; ++b) {
+        if (counts[b] < 0) why = "negative count";
+        else N += counts[b];
+    }
+    if (!why && N > 0 && !lms) why = "null landmarks";
+    if (!why && N > (1 << 24)) why = "more than 2^24 faces";
+    if (why) { g_op_error = std::string("cf_op_align_frame: ") + why; return CF_EINVAL; }
+    if (N == 0) return CF_OK;
+    Scope sc(device);
+    const int np = format == CF_FRAME_BGR ? 1 : (format == CF_YUV_NV12 || format == CF_YUV_NV21) ? 2 : 3;
+    std::vector<const void*> dev((size_t)3 * B, nullptr);
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < np; ++k) dev[3 * b + k] = sc.up(hp[3 * b + k], k == 0 ? (size_t)h * pitch0 : (size_t)(h / 2) * pitch1);
+    const size_t one = align_chip_bytes(o->size, o->format);
+    p.planes = dev.data(); p.sx = 1.0; p.sy = 1.0;
+    p.a.lms = (const float*)sc.up(lms, (size_t)N * 10 * sizeof(float)); p.a.lms_stride = 0; p.a.rows_cap = INT_MAX;
+    p.a.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int));
+    p.a.chips = sc.alloc(one * N);
+    p.a.mats = matrices ? (double*)sc.alloc((size_t)N * 6 * sizeof(double)) : nullptr;
+    p.a.offsets = nullptr; p.a.cap_faces = (int)N;
+    if (sc.err == hipSuccess) sc.chk(launch_align_frame(sc.s, p));
+    size_t n = (size_t)N;
+    if (o->max_per_image > 0) { n = 0; for (int b = 0; b < B; ++b) n += std::min(counts[b], o->max_per_image); }
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(chips, p.a.chips, one * n, hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess && matrices) sc.chk(hipMemcpyAsync(matrices, p.a.mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_align_frame");
 }
 
 // The kernels of cf_redact_faces on host frames (in place).  The packed box rows are spread to [B][max count][4] on the host, the

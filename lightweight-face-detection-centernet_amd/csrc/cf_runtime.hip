@@ -1776,6 +1776,91 @@ int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_pla
     return CF_OK;
 }
 
+// Aligned chips cut from the frames the caller names (cf_align_frame.hip): the faces are cf_redact_faces' -- the rows the last threshold
+// decode kept (network coordinates, mapped by w / W, h / H inside the kernel) or, after a tiled forward, the merged rows (frame pixels) --
+// and the outputs cf_align_faces'.  One launch on the stream that carried the decode or the merge; host frames are staged in rd_stage
+// (row bytes only), host outputs come back through the scratch of cf_align_faces.  No state of the context is changed.
+int cf_align_faces_frame(cf_ctx* c, const cf_align_opts* o, int format, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w,
+                         int pitch0, int pitch1, void* chips, double* matrices, int32_t* offsets, int cap_faces, int out_on_device) {
+    static_assert(sizeof(cf_yuv_planes) == 3 * sizeof(void*), "cf_yuv_planes is a table of three addresses");
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    AlignFrameParams p{};
+    const char* why = nullptr;
+    if (!o || !chips || !offsets) why = "null options, chips or offsets";
+    else if (cap_faces < 0) why = "cap_faces is negative";
+    else why = align_frame_check(p, o->size, o->format, o->rgb, o->mean, o->scale, o->tmpl, o->max_per_image, format, planes, in_on_device, B, h, w, pitch0, pitch1);
+    if (!why && out_on_device && (reinterpret_cast<uintptr_t>(chips) & 15)) why = "device chips must be 16-byte aligned";
+    if (!c) {                                                                // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_align_faces_frame: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_align_faces_frame: %s", why);
+    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_align_faces_frame before cf_forward");
+    if (!c->al_in) return c->fail(CF_ESTATE, "cf_align_faces_frame: an upload was started after the last forward");
+    if (c->al_rows < 1 || !c->t_lmsnet || !c->t_counts) return c->fail(CF_ESTATE, "cf_align_faces_frame without a threshold decode of the last forward");
+    const bool tiled = c->tl_T > 0;                                          // the landmarks are the merged ones, in frame pixels
+    if (tiled) {
+        if (!c->tl_merged) return c->fail(CF_ESTATE, "cf_align_faces_frame after cf_forward_tiles without a cf_merge_tiles of the last decode");
+        if (B != c->tl_Bf) return c->fail(CF_EINVAL, "cf_align_faces_frame: B=%d, the tiled forward had %d frames", B, c->tl_Bf);
+        if (h != c->tl_h || w != c->tl_w) return c->fail(CF_EINVAL, "cf_align_faces_frame: %d x %d frames, the tiled forward had %d x %d", w, h, c->tl_w, c->tl_h);
+    } else if (B != c->last_B) return c->fail(CF_EINVAL, "cf_align_faces_frame: B=%d, the last forward had %d images", B, c->last_B);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (tiled) {
+        p.a.lms = (const float*)c->tl_buf[5]; p.a.lms_stride = c->tl_maxout; p.a.rows_cap = c->tl_maxout; p.a.counts = (const int*)c->tl_buf[7];
+        p.sx = 1.0; p.sy = 1.0;
+    } else {
+        p.a.lms = c->t_lmsnet; p.a.lms_stride = c->al_rows; p.a.rows_cap = c->al_rows; p.a.counts = c->t_counts;
+        p.sx = (double)w / (double)c->W; p.sy = (double)h / (double)c->H;
+    }
+    p.a.cap_faces = cap_faces;
+    const size_t one = align_chip_bytes(o->size, o->format);
+    if (out_on_device) {
+        p.a.chips = chips; p.a.mats = matrices; p.a.offsets = offsets;
+    } else {
+        size_t have = c->al_chips_bytes;
+        int r = grow(c, (void**)&c->al_chips, &have, std::max<size_t>(one * cap_faces, 16), "chips", "cf_align_faces_frame");
+        c->al_chips_bytes = have;
+        if (r) return r;
+        have = (size_t)c->al_mats_cap * 6 * sizeof(double);
+        r = grow(c, (void**)&c->al_mats, &have, (size_t)std::max(cap_faces, 1) * 6 * sizeof(double), "matrices", "cf_align_faces_frame");
+        c->al_mats_cap = (int)(have / (6 * sizeof(double)));
+        if (r) return r;
+        if (!c->al_off) HIPCHK(c, hipMalloc((void**)&c->al_off, ((size_t)c->max_batch + 1) * sizeof(int)));      // (B <= max_batch)
+        p.a.chips = c->al_chips; p.a.mats = matrices ? c->al_mats : nullptr; p.a.offsets = c->al_off;
+    }
+    std::vector<const void*> dev;
+    if (in_on_device) {
+        p.planes = planes;
+    } else {
+        const RedactStage st = redact_stage_layout(format, h, w);
+        int r = grow(c, (void**)&c->rd_stage, &c->rd_stage_bytes, st.one * B, "frame staging", "cf_align_faces_frame"); if (r) return r;
+        dev.assign((size_t)3 * B, nullptr);
+        for (int b = 0; b < B; ++b) {
+            uint8_t* f = c->rd_stage + (size_t)b * st.one;
+            dev[3 * b] = f;
+            if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
+            if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
+        }
+        p.planes = dev.data(); p.pitch0 = st.pitch0; p.pitch1 = st.pitch1;
+        HIPCHK(c, redact_stage_copy(c->stream, st, format, reinterpret_cast<void* const*>(const_cast<cf_yuv_planes*>(frames)), B, h, pitch0, pitch1,
+                                    c->rd_stage, true));
+    }
+    HIPCHK(c, launch_align_frame(c->stream, p));
+    if (out_on_device) {
+        if (!in_on_device) HIPCHK(c, hipStreamSynchronize(c->stream));       // the host form blocks: the caller's frames have been read
+        return CF_OK;
+    }
+    HIPCHK(c, hipMemcpyAsync(offsets, c->al_off, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)std::min((int)offsets[B], cap_faces);
+    if (n > 0) {
+        HIPCHK(c, hipMemcpyAsync(chips, c->al_chips, n * one, hipMemcpyDeviceToHost, c->stream));
+        if (matrices) HIPCHK(c, hipMemcpyAsync(matrices, c->al_mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return CF_OK;
+}
+
 // Tiled forward: the cutter (cf_tiles.hip) writes the Bf * T tile images to input_resized, so the plan and its graphs are those of
 // cf_forward_resized.  Host frames -- BGR ones too -- land in src_stage under its protocol, in the layout of the redaction's staging
 // (pitches rounded up to 4): one DMA for a dense block, else one pitched 2-D copy per plane per frame.  Device frames are read in place.

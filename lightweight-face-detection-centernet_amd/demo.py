@@ -81,9 +81,37 @@ def anonymize_file(path, out_path, **options):
     return results[0]
 
 
+def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16"):
+    """Read one image file and write the aligned chip of every detected face, cut from the image at its own resolution
+    (``CenterFace.detect_aligned_frames``), to ``out_dir``/<image name>_<k>.png.  Returns (detections, the paths written).
+    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides)."""
+    from PIL import Image
+    from .centerface import CenterFace
+    frame = imread(path)
+    tiled = int(tiled or 0)
+    if tiled:
+        from . import ops
+        frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
+        T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
+        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T)
+    else:
+        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype)
+    try:
+        dets, lms, chips = detector.detect_aligned_frames(frame[None], "bgr", size, tiled=bool(tiled))[0]
+    finally:
+        detector.close()
+    os.makedirs(out_dir, exist_ok=True)
+    stem, paths = os.path.splitext(os.path.basename(path))[0], []
+    for k, chip in enumerate(chips):
+        paths.append(os.path.join(out_dir, "%s_%d.png" % (stem, k)))
+        Image.fromarray(np.ascontiguousarray(chip[:, :, ::-1])).save(paths[-1])
+    return (dets, lms), paths
+
+
 def main(argv=None):
-    """``python -m centerface_amd.demo IMAGE [--anonymize OUT [--tiled N]]``: print the detections of one image file; with
-    ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``); with ``--tiled N`` beside it the
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR] [--tiled N]``: print the detections of one image file; with
+    ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``); with ``--chips`` write one aligned
+    ``--size`` x ``--size`` chip per face, cut from the image at its own resolution, into DIR; with ``--tiled N`` beside either the
     faces are found by sliced inference over N x N tiles at native resolution."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -93,11 +121,17 @@ def main(argv=None):
     ap.add_argument("--shape", default="ellipse", choices=("ellipse", "rect"))
     ap.add_argument("--cell", type=int, default=20)
     ap.add_argument("--scale", type=float, default=1.3)
-    ap.add_argument("--tiled", type=int, default=0, metavar="N", help="with --anonymize: detect on overlapping N x N tiles (N a multiple of 32)")
+    ap.add_argument("--tiled", type=int, default=0, metavar="N", help="with --anonymize / --chips: detect on overlapping N x N tiles (N a multiple of 32)")
+    ap.add_argument("--chips", metavar="DIR", help="write the aligned chip of every detected face, cut from the image itself, into DIR")
+    ap.add_argument("--size", type=int, default=112, help="with --chips: the chip side (a multiple of 4 in [16, 512])")
     args = ap.parse_args(argv)
-    if args.tiled and not args.anonymize:
-        ap.error("--tiled goes with --anonymize")
-    if args.anonymize:
+    if args.tiled and not (args.anonymize or args.chips):
+        ap.error("--tiled goes with --anonymize or --chips")
+    if args.anonymize and args.chips:
+        ap.error("--anonymize and --chips are separate runs")
+    if args.chips:
+        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled)
+    elif args.anonymize:
         dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled)
     else:
         from .centerface import CenterFace

@@ -217,6 +217,30 @@ def align_faces(imgs, lms, counts, size=112, template=None, out="u8", rgb=False,
     return chips, mats
 
 
+def align_frame(frames, lms, counts, fmt="bgr", size=112, template=None, out="u8", rgb=False, mean=0.0, scale=1.0, max_per_image=0, device=0):
+    """Aligned face chips cut from full-resolution frames (``cf_op_align_frame``): ``frames`` as ``cut_tiles`` takes them (BGR uint8
+    [B,h,w,3], dense 4:2:0 uint8 [B, h*3//2, w], or per-frame plane tuples of pitched rows: a plane's buffer must hold rows x pitch
+    bytes); they are only read, 4:2:0 pixels are converted as ``yuv_to_bgr`` converts them.  lms [N,10] landmark rows in FRAME pixels,
+    image after image, counts [B] (N = their sum).  Chip options and the result (chips, matrices) as ``align_faces``; the matrices are
+    chip -> frame maps.  The kernel reads dwords: planes whose pitch is not a multiple of 4 are copied into padded rows first."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    lms = np.ascontiguousarray(lms, dtype=np.float32)
+    if lms.ndim != 2 or lms.shape[1] != 10:
+        raise ValueError("landmarks must be [N,10] rows, got %s" % (lms.shape,))
+    if counts.shape[0] != B or (counts < 0).any() or int(counts.sum()) != lms.shape[0]:
+        raise ValueError("counts must be [B] non-negative and sum to the number of landmark rows")
+    tab, pitch0, pitch1, keep4 = _lib.frames_pitch4(tab, fmt, B, h, w, pitch0, pitch1)
+    o, tm, shape, dtype = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
+    N = int(np.minimum(counts, max_per_image).sum()) if max_per_image > 0 else lms.shape[0]
+    chips = np.zeros((N,) + shape, dtype)
+    mats = np.zeros((N, 6), np.float64)
+    _lib.check(_lib.lib().cf_op_align_frame(device, _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, ptr(lms), ptr(counts), C.byref(o),
+                                            ptr(chips), ptr(mats)), op=True)
+    del keep, keep4
+    return chips, mats
+
+
 def redact_faces(frames, boxes, counts, net_hw, fmt="bgr", mode="mosaic", shape="ellipse", cell=20, scale=1.3, fill=(0, 0, 0), device=0):
     """Face redaction in the frame (``cf_op_redact``): ``frames`` -- BGR uint8 [B,h,w,3], dense 4:2:0 uint8 [B, h*3//2, w], or a list of
     per-frame plane tuples (pitched rows) -- are modified IN PLACE and returned.  boxes [N,4] x1,y1,x2,y2 in the coordinates of a

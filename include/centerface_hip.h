@@ -327,6 +327,42 @@ typedef struct cf_redact_opts {
 int cf_redact_faces(cf_ctx* ctx, const cf_redact_opts* opts, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
                     int pitch0, int pitch1);
 
+/* ---- blur redaction: the same faces covered with a Gaussian-like blur of the frame ---------------------------------------------- */
+/* The third look of a face anonymiser beside SOLID and MOSAIC, as its own entry point with its own options (cf_redact_opts and its
+ * modes stay as they are).  The arithmetic is this library's own statement (csrc/cf_blur.hip, restated in tests/test_blur.py; device
+ * and restatement are equal bit for bit).  Integers throughout, except the box mapping, which is cf_redact_faces'.
+ *   1. Faces, boxes, coverage: steps 1 and 2 of cf_redact_faces, exactly -- the kept rows of the last threshold decode or the merged
+ *      rows after cf_merge_tiles, the box grown by `scale`, X1, Y1 snapped down and X2, Y2 up to even, the RECT / ELLIPSE half-pixel
+ *      point tests with chroma samples at (4i+2, 4j+2).
+ *   2. Filter of strength r, 1 <= r <= 24.  b = 2r+1; the 1-D taps t are the integer sequence box_b * box_b * box_b (three discrete
+ *      convolutions of b ones): 6r+1 taps, radius R = 3r, sum b^3, variance r(r+1), so sigma is about r; r = 1: 1 3 6 7 6 3 1.  The
+ *      taps come from integer convolution, never from exp.  For a sample (x, y) of a plane of cw x ch samples, per channel:
+ *        S = sum_j sum_i t[j] * t[i] * src[clamp(y+j-R, 0, ch-1)][clamp(x+i-R, 0, cw-1)]
+ *        value = (S + D/2) / D,  D = b^6, in 64-bit integers  (S <= 255 * 49^6; the row sums fit int32)
+ *      One rounding only, so a separable evaluation equals the 2-D one.  src is the plane AS IT WAS BEFORE THE CALL; border samples
+ *      replicate.  The three bytes of BGR are filtered separately, as are the two interleaved channels of NV12 / NV21 (stride 2
+ *      bytes).  Chroma planes use r_c = (r+1)/2 (integer division) on their w/2 x h/2 grid.
+ *   3. Which r.  radius in 1..24: that r for every face.  radius == 0: per face, with A = X2-X1 and Bv = Y2-Y1 of the snapped,
+ *      unclipped box, r_f = clamp(min(A, Bv) / 8, 1, 24) (integer division); a covered sample takes the value computed with
+ *      r* = max r_f over the faces of its image that cover THAT sample (the sample's own point test: the chroma one for chroma;
+ *      (r+1)/2 is monotonic, so the chroma radius is that of r*).  The value depends only on (plane, x, y, r*) and the untouched
+ *      frame, so the result depends neither on the order of the faces nor on their overlap.
+ *   4. Writes.  Only covered samples inside the frame, never by read-modify-write; pitch padding, the corners of an ELLIPSE box and
+ *      uncovered bytes are not touched.  On the device: one launch that only reads the frame writes the value of every covered
+ *      sample into a context-owned scratch that mirrors the planes, a second launch only writes covered samples -- so the call runs
+ *      in place on a decoder's surface. */
+typedef struct cf_blur_opts {
+    int32_t shape;               /* CF_REDACT_RECT | CF_REDACT_ELLIPSE */
+    int32_t radius;              /* r, 1..24; 0 = per face from the box size */
+    float   scale;               /* the box is grown about its centre by this factor, 0.25 <= scale <= 4 */
+} cf_blur_opts;
+/* Frames, formats, pitches, alignment, on_device, the faces (after cf_merge_tiles: the merged rows), B and the state rules are those
+ * of cf_redact_faces.  CF_EINVAL, before any GPU work, for: format / shape out of range, radius outside 0..24, scale out of range or
+ * not finite, odd h or w for 4:2:0, h or w of 0 or above 8192, a pitch that is too small, a misaligned device plane or pitch, a NULL
+ * required plane.  CF_ESTATE as cf_redact_faces.  The scratch grows to the largest B x frame seen (outside any graph). */
+int cf_blur_faces(cf_ctx* ctx, const cf_blur_opts* opts, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
+                  int pitch0, int pitch1);
+
 /* ---- tiled detection of large frames (sliced inference) ------------------------------------
  * A frame much larger than the network input loses its small faces in the stretch-resize of every other entry point.  Here the frame
  * is cut into overlapping rectangles at or near native resolution, the rectangles run as one batch, and the per-tile detections are
@@ -640,6 +676,9 @@ int cf_op_align_frame(int device, int format, const cf_yuv_planes* host_frames, 
  * H x W network input, image after image, counts [B] (>= 0).  The same validation as cf_redact_faces, before any device is touched. */
 int cf_op_redact(int device, const cf_redact_opts* opts, int format, const cf_planes_rw* host_frames, int B, int h, int w, int pitch0,
                  int pitch1, const float* boxes, const int32_t* counts, int H, int W);
+/* The kernels of cf_blur_faces alone, on host frames (modified in place): boxes, counts, H, W and the validation as cf_op_redact. */
+int cf_op_blur(int device, const cf_blur_opts* opts, int format, const cf_planes_rw* host_frames, int B, int h, int w, int pitch0,
+               int pitch1, const float* boxes, const int32_t* counts, int H, int W);
 /* The tile cutter of cf_forward_tiles alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up, so the
  * padding bytes are on the device beside the pixels): tiles [Bf * T][H][W][3].  W % 4 == 0.  The same validation, before any device is
  * touched. */

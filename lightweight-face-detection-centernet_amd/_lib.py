@@ -43,6 +43,7 @@ EXPORTS = (
     "cf_op_last_error", "cf_op_last_kernel", "cf_op_shufflev2", "cf_op_mbconv", "cf_op_expand_dw", "cf_op_mbconv_pick", "cf_op_expand_dw_pick", "cf_op_ctdet_loss", "cf_op_encode_targets", "cf_op_dwconv", "cf_op_pwconv", "cf_op_pwconv_ex", "cf_op_stem", "cf_op_idaup", "cf_op_heads",
     "cf_op_ctdet_decode", "cf_op_ctdet_post_process", "cf_op_decode_threshold", "cf_op_decode_threshold_ex", "cf_op_nms", "cf_op_box_match",
     "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces", "cf_align_faces_frame", "cf_op_align_frame", "cf_redact_faces", "cf_op_redact",
+    "cf_blur_faces", "cf_op_blur",
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
 )
 
@@ -117,6 +118,36 @@ def redact_opts(mode="mosaic", shape="ellipse", cell=20, scale=1.3, fill=(0, 0, 
     if len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
         raise ValueError("fill must be three bytes in the frame's channel order, got %r" % (fill,))
     return RedactOpts(code(mode, REDACT_MODES, "mode"), code(shape, REDACT_SHAPES, "shape"), int(cell), float(scale), (C.c_uint8 * 4)(*fill, 0))
+
+
+class BlurOpts(C.Structure):
+    """cf_blur_opts: shape / filter strength r (0 = per face, from the box size) / box scale."""
+    _fields_ = [("shape", C.c_int32), ("radius", C.c_int32), ("scale", C.c_float)]
+
+
+def blur_opts(shape="ellipse", radius=0, scale=1.3):
+    """BlurOpts from a shape name ('rect' | 'ellipse'); integer codes pass through (the library validates them, like the radius and
+    the scale)."""
+    if isinstance(shape, str):
+        if shape.lower() not in REDACT_SHAPES:
+            raise ValueError("unknown redaction shape %r (one of %s)" % (shape, sorted(REDACT_SHAPES)))
+        shape = REDACT_SHAPES[shape.lower()]
+    return BlurOpts(int(shape), int(radius), float(scale))
+
+
+def split_redact_options(options):
+    """Options of ``CenterFace.anonymize`` and its kin -> ('blur', blur_faces keywords) when ``mode`` is 'blur', else ('redact', the
+    options as they are).  Blur takes shape, radius and scale; ``cell`` and ``fill`` belong to the other modes and are refused here,
+    before RedactOpts is ever built."""
+    mode = options.get("mode")
+    if not (isinstance(mode, str) and mode.lower() == "blur"):
+        if "radius" in options:
+            raise ValueError("radius belongs to mode='blur'")
+        return "redact", options
+    extra = sorted(set(options) - {"mode", "shape", "radius", "scale"})
+    if extra:
+        raise ValueError("mode='blur' takes shape, radius and scale, not %s" % ", ".join(extra))
+    return "blur", {k: v for k, v in options.items() if k != "mode"}
 
 
 class TileRect(C.Structure):
@@ -337,6 +368,8 @@ def lib():
         L.cf_op_align_frame.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p]
         L.cf_redact_faces.argtypes = [C.c_void_p, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 6
         L.cf_op_redact.argtypes = [C.c_int, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.cf_blur_faces.argtypes = [C.c_void_p, C.POINTER(BlurOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 6
+        L.cf_op_blur.argtypes = [C.c_int, C.POINTER(BlurOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.cf_tile_grid.argtypes = [C.c_int] * 6 + [C.POINTER(TileRect), C.c_int, C.POINTER(C.c_int)]
         L.cf_forward_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(TileRect), C.c_int]
         L.cf_merge_tiles.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

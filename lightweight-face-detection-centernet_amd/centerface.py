@@ -417,6 +417,31 @@ class Engine(object):
             raise ValueError("redact_faces_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
         self._chk(self._L.cf_redact_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1)))
 
+    def blur_faces(self, frames, fmt="bgr", *, shape="ellipse", radius=0, scale=1.3):
+        """Blur, in ``frames``, the faces the preceding ``decode_threshold`` kept (``cf_blur_faces``, blocking form): frames, formats and
+        faces as ``redact_faces``; copied up, blurred on the device and copied back IN PLACE, and returned.  A covered sample becomes the
+        box * box * box filtered value (width 2r+1 each, sigma about r) of the untouched frame; ``radius`` = r in 1..24, or 0 for a
+        per-face r of an eighth of the box's smaller side (at most 24)."""
+        tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
+        o = _lib.blur_opts(shape, radius, scale)
+        self._chk(self._L.cf_blur_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1))
+        del keep
+        return frames
+
+    def blur_faces_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1=0, *, shape="ellipse", radius=0, scale=1.3):
+        """Same, in place on DEVICE planes as ``redact_faces_device`` takes them: asynchronous on the engine's main stream behind the
+        decode; no count is read on the host."""
+        tab = _lib.device_planes(plane_ptrs)
+        o = _lib.blur_opts(shape, radius, scale)
+        if int(B) != len(plane_ptrs):
+            raise ValueError("blur_faces_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
+        self._chk(self._L.cf_blur_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1)))
+
+    def cover_faces(self, frames, fmt="bgr", **options):
+        """``blur_faces`` when ``options`` say ``mode='blur'`` (shape, radius, scale), otherwise ``redact_faces``."""
+        kind, kw = _lib.split_redact_options(options)
+        return self.blur_faces(frames, fmt, **kw) if kind == "blur" else self.redact_faces(frames, fmt, **kw)
+
     # -- tiled detection of large frames ---------------------------------------------------------
     def forward_tiles_enqueue(self, frames, rects, fmt="bgr", *, on_device=False, h=None, w=None, pitch0=None, pitch1=None):
         """Cut ``rects`` ([T][4] rows (x0, y0, w, h), all even, inside the frame) out of every frame at native resolution, resize each to
@@ -906,8 +931,10 @@ class CenterFace(object):
         ``metric``, ``thresh``, ``edge``).  ``frames``: BGR uint8 [B,h,w,3] (``fmt='bgr'``), dense 4:2:0 uint8 [B, h*3//2, w], or
         per-frame plane tuples -- of any even size; ``max_batch`` must hold the tiles of one frame.  Returns (dets [n,5], lms [n,10]) per
         frame (``dets`` alone without landmarks), in FRAME pixels, not floor-divided.  The defaults are this project's choices; no
-        accuracy claim is made for them.  ``redact``: options of ``Engine.redact_faces``; the frames are then redacted IN PLACE with the
-        merged boxes."""
+        accuracy claim is made for them.  ``redact``: options of ``Engine.redact_faces``, or ``mode='blur'`` with those of
+        ``Engine.blur_faces``; the frames are then redacted IN PLACE with the merged boxes."""
+        if redact is not None:
+            _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         tab, B, h, w, _, _, keep = _lib.frame_planes(frames, fmt, writable=redact is not None)
         del tab, keep
         rects, per = self._tile_geometry(h, w, tile, overlap, with_full)
@@ -918,16 +945,17 @@ class CenterFace(object):
             self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets)
             res, _ = self.engine.merge_tiles(metric, thresh, edge, self.max_dets)
             if redact is not None:
-                self.engine.redact_faces(chunk, fmt, **redact)
+                self.engine.cover_faces(chunk, fmt, **redact)
             out.extend((d, l) if self.landmarks else d for d, l in res)
         return out
 
     def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
-        cell, scale, fill), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
+        cell, scale, fill) or, with ``mode='blur'``, blurred (``Engine.blur_faces``; shape, radius, scale), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
         without detections comes back byte for byte.  ``tiled=True``: detection by ``detect_tiled`` (``tile``, ``overlap``) on frames of
         any even size, redaction with the merged boxes; the detections are then in frame pixels."""
+        _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         if tiled:
@@ -935,7 +963,7 @@ class CenterFace(object):
         k = [0]
 
         def redact(results):
-            self.engine.redact_faces(out[k[0]:k[0] + len(results)], "bgr", **options)
+            self.engine.cover_faces(out[k[0]:k[0] + len(results)], "bgr", **options)
             k[0] += len(results)
             return results
         return out, self._detect_chunks(imgs, redact)
@@ -944,6 +972,7 @@ class CenterFace(object):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
         [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``: as
         ``anonymize``."""
+        _lib.split_redact_options(options)
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
             return out, self.detect_tiled(out, tile, overlap, fmt, redact=options)
@@ -956,7 +985,7 @@ class CenterFace(object):
                 chunk = out[i:i + self.engine.max_batch]
                 self.engine.forward_yuv_enqueue(frames[i:i + self.engine.max_batch], fmt)
                 dets.extend(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True))
-                self.engine.redact_faces(chunk, fmt, **options)
+                self.engine.cover_faces(chunk, fmt, **options)
         finally:
             self.engine.set_rescale(0.0, 0.0)
         return out, dets

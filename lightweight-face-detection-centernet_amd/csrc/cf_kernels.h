@@ -386,6 +386,25 @@ hipError_t redact_stage_copy(hipStream_t s, const RedactStage& st, int format, v
                              uint8_t* dev, bool to_device);
 hipError_t launch_redact_faces(hipStream_t s, const RedactParams& p);
 
+// Blur redaction in the source frame (cf_blur.hip): every sample that a kept face covers (boxes, coverage and faces as RedactParams)
+// becomes the box_b * box_b * box_b filtered value of the untouched frame.  A first launch only reads the frame and writes the value of
+// every covered sample into `scratch`, which mirrors the planes in the layout of redact_stage_layout (B * one bytes); a second launch
+// only writes the frame.
+constexpr int kBlurMaxRadius = 24;
+struct BlurParams {
+    int format, shape;
+    int radius;           // 1..24: that r for every face; 0: per face, clamp(min(A, Bv) / 8, 1, 24)
+    float scale;
+    const void* const* planes;   // as RedactParams::planes
+    int B, h, w, pitch0, pitch1, H, W;
+    const float* boxes; int box_stride; const int* counts; int rows_cap, faces_cap;      // as RedactParams
+    uint8_t* scratch;     // blur_scratch_bytes(format, B, h, w) bytes on the device
+};
+// nullptr, or what is wrong with the options / geometry (host only): redact_check's words plus the radius
+const char* blur_check(int format, int shape, int radius, float scale, int B, int h, int w, int pitch0, int pitch1);
+size_t blur_scratch_bytes(int format, int B, int h, int w);
+hipError_t launch_blur_faces(hipStream_t s, const BlurParams& p);
+
 // Aligned face chips cut from the caller's frames (cf_align_frame.hip): the estimate, warp and outputs of AlignParams (a.img, a.img_dwords,
 // a.H, a.W unused; a.B = the number of frames), sampling B pitched frames of h x w in `format` instead of the network batch.  A landmark
 // value x (y) of a.lms is taken as (double)x * sx ((double)y * sy): sx = w / W, sy = h / H for network-coordinate rows, 1.0 for rows

@@ -830,6 +830,49 @@ int cf_op_redact(int device, const cf_redact_opts* o, int format, const cf_plane
     return sc.result("cf_op_redact");
 }
 
+// The kernels of cf_blur_faces on host frames (in place): cf_op_redact's validation, box rows and staging.
+int cf_op_blur(int device, const cf_blur_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
+               const float* boxes, const int32_t* counts, int H, int W) {
+    if (!o) { g_op_error = "cf_op_blur: null options"; return CF_EINVAL; }
+    const char* why = blur_check(format, o->shape, o->radius, o->scale, B, h, w, pitch0, pitch1);
+    if (!why) why = redact_check_planes(format, reinterpret_cast<const void* const*>(frames), B, 0, pitch0, pitch1);
+    if (!why && (!counts || H < 1 || W < 1)) why = "null counts, or H / W below 1";
+    int rows = 1;
+    long long N = 0;
+    for (int b = 0; !why && b < B; ++b) {
+        if (counts[b] < 0 || counts[b] > (1 << 20)) why = "a count is negative or above 2^20";
+        else { rows = std::max(rows, (int)counts[b]); N += counts[b]; }
+    }
+    if (!why && N > 0 && !boxes) why = "null boxes";
+    if (why) { g_op_error = std::string("cf_op_blur: ") + why; return CF_EINVAL; }
+    if (N == 0) return CF_OK;
+    std::vector<float> spread((size_t)B * rows * 4, 0.0f);
+    for (long long b = 0, at = 0; b < B; at += counts[b], ++b)
+        if (counts[b]) memcpy(&spread[(size_t)b * rows * 4], boxes + at * 4, (size_t)counts[b] * 4 * sizeof(float));
+    Scope sc(device);
+    BlurParams p{};
+    p.format = format; p.shape = o->shape; p.radius = o->radius; p.scale = o->scale;
+    p.B = B; p.h = h; p.w = w; p.H = H; p.W = W;
+    p.boxes = sc.upv(spread); p.box_stride = rows; p.rows_cap = rows; p.faces_cap = rows;
+    p.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int));
+    p.scratch = (uint8_t*)sc.alloc(blur_scratch_bytes(format, B, h, w));
+    const RedactStage st = redact_stage_layout(format, h, w);
+    uint8_t* stage = (uint8_t*)sc.alloc(st.one * B);
+    std::vector<const void*> dev((size_t)3 * B, nullptr);
+    for (int b = 0; b < B && stage; ++b) {
+        uint8_t* f = stage + (size_t)b * st.one;
+        dev[3 * b] = f;
+        if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
+        if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
+    }
+    p.planes = dev.data(); p.pitch0 = st.pitch0; p.pitch1 = st.pitch1;
+    void* const* host_planes = reinterpret_cast<void* const*>(frames);
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, true));
+    if (sc.err == hipSuccess) sc.chk(launch_blur_faces(sc.s, p));
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, false));
+    return sc.result("cf_op_blur");
+}
+
 int cf_tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, cf_tile_rect* rects, int cap, int* n) {
     const int r = tile_grid(h, w, tile_h, tile_w, overlap, with_full, rects, cap, n);
     if (r) g_op_error = "cf_tile_grid: h, w, tile_h, tile_w, overlap must be even, the sizes at least 2, 0 <= overlap < min(tile_h, tile_w); n not null";

@@ -41,14 +41,12 @@
 #include "centerface_hip.h"
 #include "cf_common.h"
 #include "cf_kernels.h"
+#include "cf_redactmath.h"
 
 namespace cf {
 namespace {
 
-constexpr int kRedactFrames = 32;                     // frames per launch: 3 x 32 plane addresses by value = 768 bytes of kernel arguments
-constexpr int kRedactGridTarget = 32768;              // workgroups per launch aimed at when choosing the slices per face
 constexpr int kRedactMaxSlices = 64;
-struct RedactPtrs { uint8_t* p0[kRedactFrames]; uint8_t* p1[kRedactFrames]; uint8_t* p2[kRedactFrames]; };
 
 struct RedactArgs {
     int format, mode, shape, m;
@@ -60,25 +58,6 @@ struct RedactArgs {
     uint32_t* cells; int gw, gh;
     int group;            // lanes that share one cell in the means launch: 4, 16 or 64
 };
-
-struct FaceBox { int X1, Y1, X2, Y2; bool ok; };
-
-__device__ __forceinline__ int snap(double v) { return (int)fmin(fmax(v, -8192.0), 16384.0); }
-
-__device__ __forceinline__ FaceBox face_box(const float* bx, float scale, int h, int w, int H, int W) {
-    const double x1 = (double)bx[0], y1 = (double)bx[1], x2 = (double)bx[2], y2 = (double)bx[3], s = (double)scale;
-    const double cx = (x1 + x2) * 0.5, cy = (y1 + y2) * 0.5;
-    const double hw = (x2 - x1) * 0.5 * s, hh = (y2 - y1) * 0.5 * s;
-    const double fx = (double)w / (double)W, fy = (double)h / (double)H;
-    FaceBox f;
-    f.ok = isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && hw > 0.0 && hh > 0.0;
-    if (!f.ok) { f.X1 = f.Y1 = f.X2 = f.Y2 = 0; return f; }
-    f.X1 = snap(floor((cx - hw) * fx)) & ~1;
-    f.Y1 = snap(floor((cy - hh) * fy)) & ~1;
-    f.X2 = (snap(ceil((cx + hw) * fx)) + 1) & ~1;
-    f.Y2 = (snap(ceil((cy + hh) * fy)) + 1) & ~1;
-    return f;
-}
 
 // the face of this workgroup (blockIdx.x = image * faces_cap + keep position) and its box clipped to the frame; false = nothing to do.
 // Uniform over the workgroup.

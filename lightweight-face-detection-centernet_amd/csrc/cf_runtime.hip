@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <mutex>
@@ -124,6 +125,7 @@ struct cf_ctx {
     // cf_redact_faces: the network-coordinate box corners of the last threshold decode ([max_batch][t_maxout][4], beside t_lmsnet), the
     // mosaic's cell means (one dword per grid cell, grown to the largest grid seen) and the frames of the host form
     float* t_detsnet = nullptr; uint32_t* rd_cells = nullptr; size_t rd_cells_n = 0; uint8_t* rd_stage = nullptr; size_t rd_stage_bytes = 0;
+    uint8_t* bl_scratch = nullptr; size_t bl_scratch_bytes = 0;      // cf_blur_faces: the blurred values of the covered samples, laid out like rd_stage
     // cf_forward_tiles / cf_merge_tiles: the rectangles of the last forward when it was a tiled one (tl_T = 0: it was not; host copy and
     // device table, uploaded when they change), the frame geometry, and the merge's workspace and merged rows (tl_buf, grown on demand:
     // cand, cand_count, order, mask | dets, lms, corners, counts, flags); tl_merged: a merge of the last decode is behind us, with
@@ -627,7 +629,7 @@ int cf_destroy(cf_ctx* c) {
     for (void* p : c->owned) hipFree(p);
     for (void* p : {(void*)c->src_stage, (void*)c->d_trans, (void*)c->hm_plane, (void*)c->keys, (void*)c->key_count, (void*)c->big, (void*)c->d_slot, (void*)c->d_dets, (void*)c->d_lms, (void*)c->d_inds, (void*)c->t_cand, (void*)c->t_count,
                     (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow,
-                    (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off, (void*)c->t_detsnet, (void*)c->rd_cells, (void*)c->rd_stage, (void*)c->tl_rects_dev})
+                    (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off, (void*)c->t_detsnet, (void*)c->rd_cells, (void*)c->rd_stage, (void*)c->bl_scratch, (void*)c->tl_rects_dev})
         if (p) hipFree(p);
     for (void* p : c->tl_buf) if (p) hipFree(p);
     if (c->h_thr) hipHostFree(c->h_thr);
@@ -1717,6 +1719,52 @@ static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char
     return CF_OK;
 }
 
+// What cf_redact_faces and cf_blur_faces share: the state rules and the face rows (the last threshold decode's, or the merged rows of a
+// tiled forward), and the frames -- the caller's device planes as they are, or host frames staged in rd_stage around the launches.
+struct FaceRows { const float* boxes; const int* counts; int box_stride, rows_cap, faces_cap, H, W; };
+static int face_rows(cf_ctx* c, const char* who, int B, int h, int w, FaceRows& f) {
+    if (c->last_B < 1) return c->fail(CF_ESTATE, "%s before cf_forward", who);
+    if (!c->al_in) return c->fail(CF_ESTATE, "%s: an upload was started after the last forward", who);
+    if (c->al_rows < 1 || !c->t_detsnet || !c->t_counts) return c->fail(CF_ESTATE, "%s without a threshold decode of the last forward", who);
+    const bool tiled = c->tl_T > 0;                                          // the boxes are the merged ones, in frame pixels
+    if (tiled) {
+        if (!c->tl_merged) return c->fail(CF_ESTATE, "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
+        if (B != c->tl_Bf) return c->fail(CF_EINVAL, "%s: B=%d, the tiled forward had %d frames", who, B, c->tl_Bf);
+        if (h != c->tl_h || w != c->tl_w) return c->fail(CF_EINVAL, "%s: %d x %d frames, the tiled forward had %d x %d", who, w, h, c->tl_w, c->tl_h);
+    } else if (B != c->last_B) return c->fail(CF_EINVAL, "%s: B=%d, the last forward had %d images", who, B, c->last_B);
+    f.H = c->H; f.W = c->W;
+    f.boxes = c->t_detsnet; f.box_stride = c->al_rows; f.rows_cap = c->al_rows; f.faces_cap = c->al_rows; f.counts = c->t_counts;
+    if (tiled) {
+        f.H = h; f.W = w;
+        f.boxes = (const float*)c->tl_buf[6]; f.box_stride = c->tl_maxout; f.rows_cap = c->tl_maxout; f.faces_cap = c->tl_maxout; f.counts = (const int*)c->tl_buf[7];
+    }
+    return CF_OK;
+}
+
+// launch(planes, pitch0, pitch1) -> hipError_t enqueues the kernels on c->stream
+static int on_frames(cf_ctx* c, const char* who, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w, int pitch0, int pitch1,
+                     const std::function<hipError_t(const void* const*, int, int)>& launch) {
+    if (on_device) {
+        HIPCHK(c, launch(reinterpret_cast<const void* const*>(frames), pitch0, pitch1));
+        return CF_OK;
+    }
+    const RedactStage st = redact_stage_layout(format, h, w);
+    int r = grow(c, (void**)&c->rd_stage, &c->rd_stage_bytes, st.one * B, "frame staging", who); if (r) return r;
+    void* const* host_planes = reinterpret_cast<void* const*>(frames);
+    std::vector<const void*> dev((size_t)3 * B, nullptr);
+    for (int b = 0; b < B; ++b) {
+        uint8_t* f = c->rd_stage + (size_t)b * st.one;
+        dev[3 * b] = f;
+        if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
+        if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
+    }
+    HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, true));
+    HIPCHK(c, launch(dev.data(), st.pitch0, st.pitch1));
+    HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, false));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CF_OK;
+}
+
 int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
                     int pitch0, int pitch1) {
     if (!c) return CF_EINVAL;
@@ -1727,25 +1775,14 @@ int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_pla
         return c->fail(CF_EINVAL, "cf_redact_faces: %s", why);
     if (const char* why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1))
         return c->fail(CF_EINVAL, "cf_redact_faces: %s", why);
-    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_redact_faces before cf_forward");
-    if (!c->al_in) return c->fail(CF_ESTATE, "cf_redact_faces: an upload was started after the last forward");
-    if (c->al_rows < 1 || !c->t_detsnet || !c->t_counts) return c->fail(CF_ESTATE, "cf_redact_faces without a threshold decode of the last forward");
-    const bool tiled = c->tl_T > 0;                                          // the boxes are the merged ones, in frame pixels
-    if (tiled) {
-        if (!c->tl_merged) return c->fail(CF_ESTATE, "cf_redact_faces after cf_forward_tiles without a cf_merge_tiles of the last decode");
-        if (B != c->tl_Bf) return c->fail(CF_EINVAL, "cf_redact_faces: B=%d, the tiled forward had %d frames", B, c->tl_Bf);
-        if (h != c->tl_h || w != c->tl_w) return c->fail(CF_EINVAL, "cf_redact_faces: %d x %d frames, the tiled forward had %d x %d", w, h, c->tl_w, c->tl_h);
-    } else if (B != c->last_B) return c->fail(CF_EINVAL, "cf_redact_faces: B=%d, the last forward had %d images", B, c->last_B);
+    FaceRows f{};
+    if (int r = face_rows(c, "cf_redact_faces", B, h, w, f)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     RedactParams p{};
     p.format = format; p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
     p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
-    p.B = B; p.h = h; p.w = w; p.H = c->H; p.W = c->W;
-    p.boxes = c->t_detsnet; p.box_stride = c->al_rows; p.rows_cap = c->al_rows; p.faces_cap = c->al_rows; p.counts = c->t_counts;
-    if (tiled) {
-        p.H = h; p.W = w;
-        p.boxes = (const float*)c->tl_buf[6]; p.box_stride = c->tl_maxout; p.rows_cap = c->tl_maxout; p.faces_cap = c->tl_maxout; p.counts = (const int*)c->tl_buf[7];
-    }
+    p.B = B; p.h = h; p.w = w; p.H = f.H; p.W = f.W;
+    p.boxes = f.boxes; p.box_stride = f.box_stride; p.rows_cap = f.rows_cap; p.faces_cap = f.faces_cap; p.counts = f.counts;
     if (o->mode == CF_REDACT_MOSAIC) {
         size_t have = c->rd_cells_n * sizeof(uint32_t);
         int r = grow(c, (void**)&c->rd_cells, &have, redact_cells(B, h, w, o->cell) * sizeof(uint32_t), "mosaic cell means");
@@ -1753,27 +1790,35 @@ int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_pla
         if (r) return r;
         p.cells = c->rd_cells;
     }
-    if (on_device) {
-        p.planes = planes; p.pitch0 = pitch0; p.pitch1 = pitch1;
-        HIPCHK(c, launch_redact_faces(c->stream, p));
-        return CF_OK;
-    }
-    const RedactStage st = redact_stage_layout(format, h, w);
-    int r = grow(c, (void**)&c->rd_stage, &c->rd_stage_bytes, st.one * B, "frame staging"); if (r) return r;
-    void* const* host_planes = reinterpret_cast<void* const*>(frames);
-    std::vector<const void*> dev((size_t)3 * B, nullptr);
-    for (int b = 0; b < B; ++b) {
-        uint8_t* f = c->rd_stage + (size_t)b * st.one;
-        dev[3 * b] = f;
-        if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
-        if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
-    }
-    p.planes = dev.data(); p.pitch0 = st.pitch0; p.pitch1 = st.pitch1;
-    HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, true));
-    HIPCHK(c, launch_redact_faces(c->stream, p));
-    HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, false));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CF_OK;
+    return on_frames(c, "cf_redact_faces", format, frames, on_device, B, h, w, pitch0, pitch1, [&](const void* const* pl, int p0, int p1) {
+        p.planes = pl; p.pitch0 = p0; p.pitch1 = p1;
+        return launch_redact_faces(c->stream, p);
+    });
+}
+
+// Blur redaction (cf_blur.hip): cf_redact_faces' faces, frames and state rules; the scratch that mirrors the planes grows to the largest
+// B x frame seen, outside any graph, like the mosaic's cell means.
+int cf_blur_faces(cf_ctx* c, const cf_blur_opts* o, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
+                  int pitch0, int pitch1) {
+    if (!c) return CF_EINVAL;
+    if (!o) return c->fail(CF_EINVAL, "cf_blur_faces: null options");
+    if (const char* why = blur_check(format, o->shape, o->radius, o->scale, B, h, w, pitch0, pitch1))
+        return c->fail(CF_EINVAL, "cf_blur_faces: %s", why);
+    if (const char* why = redact_check_planes(format, reinterpret_cast<const void* const*>(frames), B, on_device, pitch0, pitch1))
+        return c->fail(CF_EINVAL, "cf_blur_faces: %s", why);
+    FaceRows f{};
+    if (int r = face_rows(c, "cf_blur_faces", B, h, w, f)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    BlurParams p{};
+    p.format = format; p.shape = o->shape; p.radius = o->radius; p.scale = o->scale;
+    p.B = B; p.h = h; p.w = w; p.H = f.H; p.W = f.W;
+    p.boxes = f.boxes; p.box_stride = f.box_stride; p.rows_cap = f.rows_cap; p.faces_cap = f.faces_cap; p.counts = f.counts;
+    if (int r = grow(c, (void**)&c->bl_scratch, &c->bl_scratch_bytes, blur_scratch_bytes(format, B, h, w), "blur scratch", "cf_blur_faces")) return r;
+    p.scratch = c->bl_scratch;
+    return on_frames(c, "cf_blur_faces", format, frames, on_device, B, h, w, pitch0, pitch1, [&](const void* const* pl, int p0, int p1) {
+        p.planes = pl; p.pitch0 = p0; p.pitch1 = p1;
+        return launch_blur_faces(c->stream, p);
+    });
 }
 
 // Aligned chips cut from the frames the caller names (cf_align_frame.hip): the faces are cf_redact_faces' -- the rows the last threshold

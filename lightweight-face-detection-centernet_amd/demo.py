@@ -57,7 +57,7 @@ def dump_event(detector, images, im_dir, names, save_path):
 
 def anonymize_file(path, out_path, **options):
     """Read one image file, redact every detected face on the device (``CenterFace.anonymize``; ``options``: mode, shape, cell,
-    scale, fill) and write the result to ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``: sliced
+    scale, fill, or mode='blur' with shape, radius, scale) and write the result to ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``: sliced
     inference with N x N tiles at native resolution (``CenterFace.detect_tiled``; the image is cropped to even sides), for images much
     larger than N whose small faces a whole-frame resize would lose; the detections are then in image pixels."""
     from PIL import Image
@@ -110,7 +110,8 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16"):
 
 def main(argv=None):
     """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR] [--tiled N]``: print the detections of one image file; with
-    ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``); with ``--chips`` write one aligned
+    ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``; or blurred: ``--blur [R]``, R = the
+    filter strength 1..24, without it or 0 an eighth of each face's smaller side); with ``--chips`` write one aligned
     ``--size`` x ``--size`` chip per face, cut from the image at its own resolution, into DIR; with ``--tiled N`` beside either the
     faces are found by sliced inference over N x N tiles at native resolution."""
     import argparse
@@ -121,16 +122,22 @@ def main(argv=None):
     ap.add_argument("--shape", default="ellipse", choices=("ellipse", "rect"))
     ap.add_argument("--cell", type=int, default=20)
     ap.add_argument("--scale", type=float, default=1.3)
+    ap.add_argument("--blur", type=int, nargs="?", const=0, default=None, metavar="R",
+                    help="with --anonymize: blur the faces instead (R in 1..24; 0 or no value: per face, from its size)")
     ap.add_argument("--tiled", type=int, default=0, metavar="N", help="with --anonymize / --chips: detect on overlapping N x N tiles (N a multiple of 32)")
     ap.add_argument("--chips", metavar="DIR", help="write the aligned chip of every detected face, cut from the image itself, into DIR")
     ap.add_argument("--size", type=int, default=112, help="with --chips: the chip side (a multiple of 4 in [16, 512])")
     args = ap.parse_args(argv)
     if args.tiled and not (args.anonymize or args.chips):
         ap.error("--tiled goes with --anonymize or --chips")
+    if args.blur is not None and not args.anonymize:
+        ap.error("--blur goes with --anonymize")
     if args.anonymize and args.chips:
         ap.error("--anonymize and --chips are separate runs")
     if args.chips:
         (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled)
+    elif args.anonymize and args.blur is not None:
+        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled)
     elif args.anonymize:
         dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled)
     else:

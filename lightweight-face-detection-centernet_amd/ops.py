@@ -259,6 +259,23 @@ def redact_faces(frames, boxes, counts, net_hw, fmt="bgr", mode="mosaic", shape=
     return frames
 
 
+def blur_faces(frames, boxes, counts, net_hw, fmt="bgr", shape="ellipse", radius=0, scale=1.3, device=0):
+    """Blur redaction in the frame (``cf_op_blur``): ``frames``, ``boxes``, ``counts`` and ``net_hw`` as ``redact_faces`` takes them; the
+    frames are modified IN PLACE and returned.  Every sample that the box grown by ``scale`` (``shape='rect'``) or the ellipse inscribed
+    in it covers becomes the box * box * box filtered value (width 2r+1 each, sigma about r) of the untouched frame; ``radius`` = r in
+    1..24, or 0 for a per-face r of an eighth of the box's smaller side."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+    if counts.shape[0] != B or (counts < 0).any() or int(counts.sum()) != boxes.shape[0]:
+        raise ValueError("counts must be [B] non-negative and sum to the number of box rows")
+    o = _lib.blur_opts(shape, radius, scale)
+    _lib.check(_lib.lib().cf_op_blur(device, C.byref(o), _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, ptr(boxes), ptr(counts),
+                                     int(net_hw[0]), int(net_hw[1])), op=True)
+    del keep
+    return frames
+
+
 def tile_grid(h, w, tile, overlap, with_full=True):
     """The rectangles of sliced inference (``cf_tile_grid``; host only): int32 [T][4] rows (x0, y0, w, h) covering an h x w frame with
     tiles of ``tile`` = (tile_h, tile_w) or one int, neighbours sharing at least ``overlap`` pixels, row-major; the whole frame is

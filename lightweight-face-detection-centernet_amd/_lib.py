@@ -284,6 +284,15 @@ def device_planes(plane_ptrs):
     return tab
 
 
+def box_rows(boxes, counts, B):
+    """(boxes float32 [N,4], counts int32 [B]) of the packed box rows of B images, N = the sum of the counts."""
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+    if counts.shape[0] != B or (counts < 0).any() or int(counts.sum()) != boxes.shape[0]:
+        raise ValueError("counts must be [B] non-negative and sum to the number of box rows")
+    return boxes, counts
+
+
 def frames_pitch4(tab, fmt, B, h, w, pitch0, pitch1):
     """The host frames of a ``frame_planes`` table with every pitch a multiple of 4: the table as it is when they are, else a new table
     over padded copies (zero padding).  Returns (table, pitch0, pitch1, arrays to keep alive)."""

@@ -327,13 +327,18 @@ class Engine(object):
         network-input maps, zero where a face could not be aligned).  ``max_faces`` caps N (offsets[-1] still tells the number
         wanted); by default the buffers are sized from the decode's counts and grown if that was short."""
         o, tm, shape, dtype = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
-        B = self.last_B
+        return self._align_grow(self.last_B, shape, dtype, max_faces, lambda chips, mats, offs, cap: self._L.cf_align_faces(
+            self._h, C.byref(o), _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
+
+    def _align_grow(self, B, shape, dtype, max_faces, call):
+        """(chips, offsets, matrices) of ``call(chips, mats, offs, cap)``: host buffers for ``max_faces`` faces, or sized from the
+        decode's counts and grown once the offsets tell that this was short."""
         cap = int(getattr(self, "_last_kept", 0)) if max_faces is None else int(max_faces)
         while True:
             chips = np.empty((max(cap, 1),) + shape, dtype)
             mats = np.empty((max(cap, 1), 6), np.float64)
             offs = np.zeros((B + 1,), np.int32)
-            self._chk(self._L.cf_align_faces(self._h, C.byref(o), _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
+            self._chk(call(chips, mats, offs, cap))
             if max_faces is not None or int(offs[-1]) <= cap:
                 break
             cap = int(offs[-1])
@@ -359,19 +364,10 @@ class Engine(object):
         pixel maps)."""
         tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
         o, tm, shape, dtype = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
-        cap = int(getattr(self, "_last_kept", 0)) if max_faces is None else int(max_faces)
-        while True:
-            chips = np.empty((max(cap, 1),) + shape, dtype)
-            mats = np.empty((max(cap, 1), 6), np.float64)
-            offs = np.zeros((B + 1,), np.int32)
-            self._chk(self._L.cf_align_faces_frame(self._h, C.byref(o), _lib.frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1,
-                                                   _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
-            if max_faces is not None or int(offs[-1]) <= cap:
-                break
-            cap = int(offs[-1])
+        res = self._align_grow(B, shape, dtype, max_faces, lambda chips, mats, offs, cap: self._L.cf_align_faces_frame(
+            self._h, C.byref(o), _lib.frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1, _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
         del keep
-        n = min(int(offs[-1]), cap)
-        return chips[:n], offs, mats[:n]
+        return res
 
     def align_faces_frame_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1, chips_ptr, offsets_ptr, cap_faces, matrices_ptr=None,
                                  size=112, *, out="u8", rgb=False, mean=0.0, scale=1.0, template=None, max_per_image=0):
@@ -408,13 +404,10 @@ class Engine(object):
         """Same, in place on DEVICE planes -- a decoder's surfaces: ``plane_ptrs`` = B tuples (p0, p1, p2) of device addresses (BGR: p0
         only; NV12 / NV21: Y and the interleaved plane; I420 / YV12: three planes), addresses and pitches multiples of 4.  Asynchronous
         on the engine's main stream behind the decode; no count is read on the host."""
-        tab = (_lib.PlanesRW * max(len(plane_ptrs), 1))()
-        for b, t in enumerate(plane_ptrs):
-            t = (tuple(t) if isinstance(t, (tuple, list)) else (t,)) + (None, None)
-            tab[b].p0, tab[b].p1, tab[b].p2 = (int(v) if v else None for v in t[:3])
-        o = _lib.redact_opts(mode, shape, cell, scale, fill)
         if int(B) != len(plane_ptrs):
             raise ValueError("redact_faces_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
+        tab = _lib.device_planes(plane_ptrs)
+        o = _lib.redact_opts(mode, shape, cell, scale, fill)
         self._chk(self._L.cf_redact_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1)))
 
     def blur_faces(self, frames, fmt="bgr", *, shape="ellipse", radius=0, scale=1.3):

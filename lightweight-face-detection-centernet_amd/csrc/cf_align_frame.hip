@@ -37,7 +37,7 @@ namespace cf {
 namespace {
 
 constexpr int kAlignFrames = 64;                     // frames per launch: 3 x 64 plane addresses by value = 1.5 KB of kernel arguments
-struct AlignFramePtrs { const uint8_t* p0[kAlignFrames]; const uint8_t* p1[kAlignFrames]; const uint8_t* p2[kAlignFrames]; };
+using AlignFramePtrs = FramePtrs<kAlignFrames>;
 struct AlignFrameGeo { int f0, nb, h, w, pitch0, pitch1; double sx, sy; };
 
 // SRC: 0 = BGR rows, 1 = one interleaved chroma plane (NV12 / NV21), 2 = two chroma planes (I420; YV12 on a swapped table);
@@ -114,16 +114,12 @@ __global__ void __launch_bounds__(256) align_frame_kernel(AlignParams p, AlignFr
     }
 }
 
-inline bool is_il(int format) { return format == CF_YUV_NV12 || format == CF_YUV_NV21; }
-
 }  // namespace
 
 const char* align_frame_check(AlignFrameParams& p, int size, int chip_format, int rgb, float mean, float scale, const float* tmpl,
                               int max_per_image, int format, const void* const* planes, int on_device, int B, int h, int w, int pitch0, int pitch1) {
     if (const char* why = align_params_set(p.a, size, chip_format, rgb, mean, scale, tmpl, max_per_image)) return why;
-    if (format < CF_YUV_NV12 || format > CF_FRAME_BGR) return "unknown format (0..3: NV12, NV21, I420, YV12; 4: BGR)";
-    if (h < 2 || w < 2 || h > kRedactMaxSide || w > kRedactMaxSide) return "h and w must be in [2, 8192]";
-    if (const char* why = redact_check(format, CF_REDACT_SOLID, CF_REDACT_RECT, 2, 1.0f, B, h, w, pitch0, pitch1)) return why;
+    if (const char* why = frame_geometry_check(FrameGeo{format, B, h, w, pitch0, pitch1}, 2, false)) return why;
     if (const char* why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1)) return why;
     p.format = format; p.a.B = B; p.h = h; p.w = w; p.pitch0 = pitch0; p.pitch1 = pitch1;
     return nullptr;
@@ -131,31 +127,19 @@ const char* align_frame_check(AlignFrameParams& p, int size, int chip_format, in
 
 hipError_t launch_align_frame(hipStream_t s, const AlignFrameParams& p) {
     const AlignParams& a = p.a;
-    const bool bgr = p.format == CF_FRAME_BGR;
-    if (p.format < CF_YUV_NV12 || p.format > CF_FRAME_BGR || !p.planes || a.B < 1 || p.h < 2 || p.w < 2 || p.h > kRedactMaxSide ||
-        p.w > kRedactMaxSide || (!bgr && ((p.h | p.w) & 1)) || (p.pitch0 & 3) || (!bgr && (p.pitch1 & 3)) ||
-        p.pitch0 < (bgr ? 3 * p.w : p.w) || (!bgr && p.pitch1 < (is_il(p.format) ? p.w : p.w / 2)) || !a.counts || a.cap_faces < 0 ||
+    if (frame_geometry_check(FrameGeo{p.format, a.B, p.h, p.w, p.pitch0, p.pitch1}, 2, false) ||
+        redact_check_planes(p.format, p.planes, a.B, 1, p.pitch0, p.pitch1) || !a.counts || a.cap_faces < 0 ||
         a.S < 16 || a.S > kAlignMaxS || (a.S & 3) || (reinterpret_cast<uintptr_t>(a.chips) & (a.format == 0 ? 3 : 15)) ||
         !(p.sx > 0.0) || !(p.sy > 0.0))
         return hipErrorInvalidValue;
-    const int np = bgr ? 1 : is_il(p.format) ? 2 : 3;
-    for (int b = 0; b < a.B; ++b)
-        for (int k = 0; k < np; ++k)
-            if (!p.planes[3 * b + k] || (reinterpret_cast<uintptr_t>(p.planes[3 * b + k]) & 3)) return hipErrorInvalidValue;
     const long long bands = ((long long)a.S * (a.S >> 2) + kAlignItems - 1) / kAlignItems;
     const long long grid = (long long)(a.cap_faces > 0 ? a.cap_faces : 1) * bands;      // one workgroup at least: it writes the offsets
     if (grid > INT_MAX) return hipErrorInvalidValue;
-    const bool swap = p.format == CF_YUV_YV12;             // I420 with the chroma planes swapped (as launch_cut_tiles)
     for (int f0 = 0; f0 < a.B; f0 += kAlignFrames) {
-        AlignFramePtrs tab{};
         AlignFrameGeo g{};
         g.f0 = f0; g.nb = a.B - f0 < kAlignFrames ? a.B - f0 : kAlignFrames;
         g.h = p.h; g.w = p.w; g.pitch0 = p.pitch0; g.pitch1 = p.pitch1; g.sx = p.sx; g.sy = p.sy;
-        for (int k = 0; k < g.nb; ++k) {
-            tab.p0[k] = (const uint8_t*)p.planes[3 * (f0 + k)];
-            tab.p1[k] = (const uint8_t*)p.planes[3 * (f0 + k) + (swap ? 2 : 1)];
-            tab.p2[k] = (const uint8_t*)p.planes[3 * (f0 + k) + (swap ? 1 : 2)];
-        }
+        const AlignFramePtrs tab = frame_ptrs<kAlignFrames>(p.planes, p.format, f0, g.nb, true);      // YV12: the I420 kernel on swapped planes
         AlignParams q = a;
         if (f0 > 0) q.offsets = nullptr;                    // the first launch has written them
         const dim3 gr((unsigned)grid);

@@ -85,11 +85,10 @@ static_assert(kHostTaps.t[7] == 1 && kHostTaps.t[7 + 6] == 19 && kHostTaps.t[kTa
 __constant__ BlurTaps g_taps = make_taps();
 
 struct BlurArgs {
-    int format, shape, radius;
+    int shape, radius;
     float scale;
-    int B, h, w, pitch0, pitch1, H, W;
-    const float* boxes; int box_stride;
-    const int* counts; int rows_cap, faces_cap;
+    FrameGeo g;                                        // g.B: the frames of this launch
+    FaceList f;
     uint8_t* scratch;                                  // first frame of this launch
     unsigned long long sone, soff1, soff2;             // bytes per frame, offsets of the chroma planes
     int spitch0, spitch1;
@@ -97,21 +96,6 @@ struct BlurArgs {
 
 __device__ __forceinline__ int face_r(const FaceBox& f, int radius) {
     return radius ? radius : min(max(min(f.X2 - f.X1, f.Y2 - f.Y1) / 8, 1), kBlurMaxRadius);
-}
-
-// the face of this workgroup (blockIdx.x = image * faces_cap + keep position) and its box clipped to the frame; false = nothing to do.
-// Uniform over the workgroup.
-struct Clip { int b, X1, Y1, X2, Y2, cx1, cy1, cx2, cy2; };
-__device__ __forceinline__ bool face_clip(const BlurArgs& a, Clip& c) {
-    const int n = (int)blockIdx.x;
-    c.b = n / a.faces_cap;
-    const int i = n - c.b * a.faces_cap;
-    if (c.b >= a.B || i >= min(a.counts[c.b], a.rows_cap)) return false;
-    const FaceBox f = face_box(a.boxes + ((size_t)c.b * a.box_stride + i) * 4, a.scale, a.h, a.w, a.H, a.W);
-    if (!f.ok) return false;
-    c.X1 = f.X1; c.Y1 = f.Y1; c.X2 = f.X2; c.Y2 = f.Y2;
-    c.cx1 = max(f.X1, 0); c.cy1 = max(f.Y1, 0); c.cx2 = min(f.X2, a.w); c.cy2 = min(f.Y2, a.h);
-    return c.cx1 < c.cx2 && c.cy1 < c.cy2;
 }
 
 // First launch: reads the frame, writes a.scratch only.
@@ -122,23 +106,20 @@ __global__ void __launch_bounds__(256) blur_compute_kernel(BlurArgs a, RedactPtr
     __shared__ int s_face[kFaceChunk][4];
     __shared__ int s_face_on[kFaceChunk];
     Clip c;
-    if (!face_clip(a, c)) return;
-    const bool bgr = a.format == CF_FRAME_BGR, il = a.format == CF_YUV_NV12 || a.format == CF_YUV_NV21;
+    if (!face_clip(a.g, a.f, a.scale, c)) return;
     const bool ellipse = a.shape == CF_REDACT_ELLIPSE;
-    const int passes = bgr ? 1 : il ? 2 : 3;
     const int tid = (int)threadIdx.x;
     FaceBox me; me.X1 = c.X1; me.Y1 = c.Y1; me.X2 = c.X2; me.Y2 = c.Y2; me.ok = true;
     const int r_me = face_r(me, a.radius);
-    const int nfaces = a.radius ? 0 : min(a.counts[c.b], a.rows_cap);           // the skip rule only matters when r varies
-    for (int ps = 0; ps < passes; ++ps) {
+    const int nfaces = a.radius ? 0 : min(a.f.counts[c.b], a.f.rows_cap);       // the skip rule only matters when r varies
+    for (int ps = 0; ps < frame_planes(a.g.format); ++ps) {
         const uint8_t* base = ps == 0 ? t.p0[c.b] : ps == 1 ? t.p1[c.b] : t.p2[c.b];
         uint8_t* sbase = a.scratch + (size_t)c.b * a.sone + (ps == 0 ? 0 : ps == 1 ? a.soff1 : a.soff2);
-        const bool chroma = ps > 0;
-        const int bps = bgr ? 3 : (il && ps == 1) ? 2 : 1;
-        const int pitch = chroma ? a.pitch1 : a.pitch0, spitch = chroma ? a.spitch1 : a.spitch0;
-        const int cw = chroma ? a.w >> 1 : a.w, ch = chroma ? a.h >> 1 : a.h;
-        const int sx0 = chroma ? c.cx1 >> 1 : c.cx1, sx1 = chroma ? c.cx2 >> 1 : c.cx2;       // 4:2:0: the clipped box is even on every side
-        const int sy0 = chroma ? c.cy1 >> 1 : c.cy1, sy1 = chroma ? c.cy2 >> 1 : c.cy2;
+        const PlanePass pp = plane_pass(a.g, ps, c);
+        const bool chroma = pp.chroma;
+        const int bps = pp.bps, pitch = pp.pitch, spitch = chroma ? a.spitch1 : a.spitch0;
+        const int cw = chroma ? a.g.w >> 1 : a.g.w, ch = chroma ? a.g.h >> 1 : a.g.h;
+        const int sx0 = pp.sx0, sx1 = pp.sx1, sy0 = pp.sy0, sy1 = pp.sy1;
         const int r = chroma ? (r_me + 1) >> 1 : r_me, R = 3 * r, ntaps = 2 * R + 1, bb = 2 * r + 1;
         const unsigned long long D = (unsigned long long)(bb * bb * bb) * (unsigned long long)(bb * bb * bb);
         const int ntx = (sx1 - sx0 + kTile - 1) / kTile, ntiles = ntx * ((sy1 - sy0 + kTile - 1) / kTile);
@@ -154,7 +135,7 @@ __global__ void __launch_bounds__(256) blur_compute_kernel(BlurArgs a, RedactPtr
                 const int k = tid + 256 * q, ly = k >> 5, lx = k & (kTile - 1);
                 if (lx < tw && ly < th) {
                     const int x = tx0 + lx, y = ty0 + ly;
-                    if (face_covers(c.X1, c.Y1, c.X2, c.Y2, ellipse, chroma ? 4 * x + 2 : 2 * x + 1, chroma ? 4 * y + 2 : 2 * y + 1)) mask |= 1 << q;
+                    if (face_covers(c.X1, c.Y1, c.X2, c.Y2, ellipse, pp.point(x), pp.point(y))) mask |= 1 << q;
                 }
             }
             // the skip rule: samples that a face of larger r covers belong to that face's workgroup
@@ -164,7 +145,7 @@ __global__ void __launch_bounds__(256) blur_compute_kernel(BlurArgs a, RedactPtr
                 const int nf = min(kFaceChunk, nfaces - f0);
                 __syncthreads();                                               // the previous round's list is no longer read
                 if (tid < nf) {
-                    const FaceBox f = face_box(a.boxes + ((size_t)c.b * a.box_stride + f0 + tid) * 4, a.scale, a.h, a.w, a.H, a.W);
+                    const FaceBox f = face_box(a.f.boxes + ((size_t)c.b * a.f.box_stride + f0 + tid) * 4, a.scale, a.g.h, a.g.w, a.f.H, a.f.W);
                     const bool on = f.ok && face_r(f, 0) > r_me && max(f.X1, lx0) < min(f.X2, lx1) && max(f.Y1, ly0) < min(f.Y2, ly1);
                     s_face[tid][0] = f.X1; s_face[tid][1] = f.Y1; s_face[tid][2] = f.X2; s_face[tid][3] = f.Y2;
                     s_face_on[tid] = on ? 1 : 0;
@@ -177,7 +158,7 @@ __global__ void __launch_bounds__(256) blur_compute_kernel(BlurArgs a, RedactPtr
                     for (int q = 0; q < 4; ++q) {
                         if (!(mask & (1 << q))) continue;
                         const int k = tid + 256 * q, x = tx0 + (k & (kTile - 1)), y = ty0 + (k >> 5);
-                        if (face_covers(X1, Y1, X2, Y2, ellipse, chroma ? 4 * x + 2 : 2 * x + 1, chroma ? 4 * y + 2 : 2 * y + 1)) mask &= ~(1 << q);
+                        if (face_covers(X1, Y1, X2, Y2, ellipse, pp.point(x), pp.point(y))) mask &= ~(1 << q);
                     }
                 }
             }
@@ -216,43 +197,29 @@ __global__ void __launch_bounds__(256) blur_compute_kernel(BlurArgs a, RedactPtr
 }
 
 // Second launch: writes the covered samples of one face, plane after plane, from the scratch; never reads the frame.  Item = one aligned
-// dword of a plane row inside the clipped box (the scratch rows hold the same bytes at the same offsets).
+// dword of a plane row inside the clipped box (the scratch rows hold the same bytes at the same offsets, in whole dwords).
 __global__ void __launch_bounds__(256) blur_write_kernel(BlurArgs a, RedactPtrs t) {
     Clip c;
-    if (!face_clip(a, c)) return;
-    const bool bgr = a.format == CF_FRAME_BGR, il = a.format == CF_YUV_NV12 || a.format == CF_YUV_NV21;
-    const int passes = bgr ? 1 : il ? 2 : 3;
+    if (!face_clip(a.g, a.f, a.scale, c)) return;
     const bool ellipse = a.shape == CF_REDACT_ELLIPSE;
     const int first = (int)blockIdx.y * 256 + (int)threadIdx.x, stride = (int)gridDim.y * 256;
-    for (int ps = 0; ps < passes; ++ps) {
+    for (int ps = 0; ps < frame_planes(a.g.format); ++ps) {
         uint8_t* base = ps == 0 ? t.p0[c.b] : ps == 1 ? t.p1[c.b] : t.p2[c.b];
         const uint8_t* sbase = a.scratch + (size_t)c.b * a.sone + (ps == 0 ? 0 : ps == 1 ? a.soff1 : a.soff2);
-        const bool chroma = ps > 0;
-        const int bps = bgr ? 3 : (il && ps == 1) ? 2 : 1;
-        const int pitch = chroma ? a.pitch1 : a.pitch0, spitch = chroma ? a.spitch1 : a.spitch0;
-        const int sx0 = chroma ? c.cx1 >> 1 : c.cx1, sx1 = chroma ? c.cx2 >> 1 : c.cx2;
-        const int sy0 = chroma ? c.cy1 >> 1 : c.cy1, sy1 = chroma ? c.cy2 >> 1 : c.cy2;
-        const int d0 = (bps * sx0) >> 2, nd = ((bps * sx1 + 3) >> 2) - d0, items = nd * (sy1 - sy0);
+        const PlanePass pp = plane_pass(a.g, ps, c);
+        const int bps = pp.bps, spitch = pp.chroma ? a.spitch1 : a.spitch0, items = pp.nd * (pp.sy1 - pp.sy0);
         for (int item = first; item < items; item += stride) {
-            const int row = sy0 + item / nd, d = d0 + (item - (item / nd) * nd);
-            const int V = chroma ? 4 * row + 2 : 2 * row + 1;
+            const int row = pp.sy0 + item / pp.nd, d = pp.d0 + (item - (item / pp.nd) * pp.nd);
             int mask = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int byte = 4 * d + k;
                 const int s = bps == 3 ? byte / 3 : bps == 2 ? byte >> 1 : byte;
-                if (s < sx0 || s >= sx1) continue;
-                if (face_covers(c.X1, c.Y1, c.X2, c.Y2, ellipse, chroma ? 4 * s + 2 : 2 * s + 1, V)) mask |= 1 << k;
+                if (s < pp.sx0 || s >= pp.sx1) continue;
+                if (face_covers(c.X1, c.Y1, c.X2, c.Y2, ellipse, pp.point(s), pp.point(row))) mask |= 1 << k;
             }
-            const uint8_t* src = sbase + (size_t)row * spitch + (size_t)d * 4;
-            uint8_t* q = base + (size_t)row * pitch + (size_t)d * 4;
-            if (mask == 15) {
-                *reinterpret_cast<uint32_t*>(q) = *reinterpret_cast<const uint32_t*>(src);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (mask & (1 << k)) q[k] = src[k];
-            }
+            if (mask) store_masked_dword(base + (size_t)row * pp.pitch + (size_t)d * 4,
+                                         *reinterpret_cast<const uint32_t*>(sbase + (size_t)row * spitch + (size_t)d * 4), mask);
         }
     }
 }
@@ -268,39 +235,33 @@ const char* blur_check(int format, int shape, int radius, float scale, int B, in
 size_t blur_scratch_bytes(int format, int B, int h, int w) { return redact_stage_layout(format, h, w).one * (size_t)B; }
 
 hipError_t launch_blur_faces(hipStream_t s, const BlurParams& p) {
-    if (blur_check(p.format, p.shape, p.radius, p.scale, p.B, p.h, p.w, p.pitch0, p.pitch1) ||
-        redact_check_planes(p.format, p.planes, p.B, 1, p.pitch0, p.pitch1) || p.H < 1 || p.W < 1 || !p.boxes || !p.counts ||
-        p.box_stride < 1 || p.rows_cap < 1 || p.faces_cap < 1 || !p.scratch)
+    const FrameGeo& g = p.g;
+    if (blur_check(g.format, p.shape, p.radius, p.scale, g.B, g.h, g.w, g.pitch0, g.pitch1) ||
+        redact_check_planes(g.format, p.planes, g.B, 1, g.pitch0, g.pitch1) || p.f.H < 1 || p.f.W < 1 || !p.f.boxes || !p.f.counts ||
+        p.f.box_stride < 1 || p.f.rows_cap < 1 || p.f.faces_cap < 1 || !p.scratch)
         return hipErrorInvalidValue;
-    const RedactStage st = redact_stage_layout(p.format, p.h, p.w);
+    const RedactStage st = redact_stage_layout(g.format, g.h, g.w);
     BlurArgs a{};
-    a.format = p.format; a.shape = p.shape; a.radius = p.radius; a.scale = p.scale;
-    a.h = p.h; a.w = p.w; a.pitch0 = p.pitch0; a.pitch1 = p.pitch1; a.H = p.H; a.W = p.W;
-    a.box_stride = p.box_stride; a.rows_cap = p.rows_cap; a.faces_cap = p.faces_cap;
+    a.g = g; a.f = p.f; a.shape = p.shape; a.radius = p.radius; a.scale = p.scale;
     a.sone = st.one; a.soff1 = st.off1; a.soff2 = st.off2; a.spitch0 = st.pitch0; a.spitch1 = st.pitch1;
-    for (int f0 = 0; f0 < p.B; f0 += kRedactFrames) {
-        const int nb = p.B - f0 < kRedactFrames ? p.B - f0 : kRedactFrames;
-        RedactPtrs tab{};
-        for (int k = 0; k < nb; ++k) {
-            tab.p0[k] = (uint8_t*)p.planes[3 * (f0 + k)];
-            tab.p1[k] = (uint8_t*)p.planes[3 * (f0 + k) + 1];
-            tab.p2[k] = (uint8_t*)p.planes[3 * (f0 + k) + 2];
-        }
-        a.B = nb;
-        a.boxes = p.boxes + (size_t)f0 * p.box_stride * 4;
-        a.counts = p.counts + f0;
+    for (int f0 = 0; f0 < g.B; f0 += kRedactFrames) {
+        const int nb = std::min(g.B - f0, kRedactFrames);
+        const RedactPtrs tab = frame_ptrs<kRedactFrames>(p.planes, g.format, f0, nb, false);
+        a.g.B = nb;
+        a.f.boxes = p.f.boxes + (size_t)f0 * p.f.box_stride * 4;
+        a.f.counts = p.f.counts + f0;
         a.scratch = p.scratch + (size_t)f0 * st.one;
-        const long long faces = (long long)nb * p.faces_cap;
+        const long long faces = (long long)nb * p.f.faces_cap;
         if (faces > INT_MAX) return hipErrorInvalidValue;
         // slices per face: one per tile of a frame-sized face, as long as the launch stays near kRedactGridTarget workgroups (most of
         // which belong to faces that do not exist and leave at once); a workgroup walks the tiles beyond its slice
         const long long room = std::max<long long>(kRedactGridTarget / faces, 1);
-        const long long tiles = (long long)((p.w + kTile - 1) / kTile) * ((p.h + kTile - 1) / kTile);
+        const long long tiles = (long long)((g.w + kTile - 1) / kTile) * ((g.h + kTile - 1) / kTile);
         const long long cs = std::min<long long>(std::min(tiles, room), kBlurMaxSlices);
         hipLaunchKernelGGL(blur_compute_kernel, dim3((unsigned)faces, (unsigned)cs), dim3(256), 0, s, a, tab);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        const long long dwords = (long long)p.h * (p.pitch0 / 4 + 1);
+        const long long dwords = (long long)g.h * (g.pitch0 / 4 + 1);
         const long long ws = std::min<long long>(std::min<long long>((dwords + 256 * 32 - 1) / (256 * 32), room), 64);
         hipLaunchKernelGGL(blur_write_kernel, dim3((unsigned)faces, (unsigned)std::max<long long>(ws, 1)), dim3(256), 0, s, a, tab);
         e = hipGetLastError();

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <string>
 #include "centerface_hip.h"
+#include "cf_frame.h"
 
 struct sp32_t;
 
@@ -355,22 +356,15 @@ hipError_t launch_align_faces(hipStream_t s, const AlignParams& p);
 
 // Face redaction in the source frame (cf_redact.hip): every sample of a BGR or 4:2:0 frame that the scaled box (RECT) or its inscribed
 // ellipse of some kept face covers is overwritten, by a fill colour (SOLID) or by the mean of its frame-anchored mosaic cell (MOSAIC: a
-// first launch writes the cell means of the untouched frame to `cells`, a second one writes the samples).  Image b uses box rows
-// boxes[b * box_stride + i], i < min(counts[b], rows_cap); the launches are sized for B x faces_cap faces and read counts on the device.
-constexpr int kRedactMaxSide = 8192;
+// first launch writes the cell means of the untouched frame to `cells`, a second one writes the samples).  Frames, plane table and faces:
+// cf_frame.h; the launches are sized for B x faces_cap faces and read counts on the device.
 struct RedactParams {
-    int format;           // CF_YUV_NV12 .. CF_YUV_YV12, CF_FRAME_BGR
+    FrameGeo g;           // pitches multiples of 4
+    FaceList f;
     int mode, shape, cell;   // CF_REDACT_SOLID / _MOSAIC, CF_REDACT_RECT / _ELLIPSE, the mosaic cell m
     float scale;
     uint8_t fill[3];      // in the frame's channel order (B,G,R or Y,U,V)
-    const void* const* planes;   // HOST table, B x {p0, p1, p2} DEVICE addresses (p1 / p2 as the format needs), all 4-byte aligned
-    int B, h, w, pitch0, pitch1;   // pitches in bytes, multiples of 4
-    int H, W;             // the size the boxes are expressed in (the network input)
-    const float* boxes;   // rows of 4 floats x1,y1,x2,y2
-    int box_stride;       // rows per image
-    const int* counts;    // [B]
-    int rows_cap;         // rows the producer wrote per image at most
-    int faces_cap;        // faces per image the launches are sized for (>= 1)
+    const void* const* planes;   // HOST table of B x {p0, p1, p2} DEVICE addresses (cf_frame.h), all 4-byte aligned
     uint32_t* cells;      // MOSAIC: [B][ceil(h / m)][ceil(w / m)] cell means, one dword each (else unused)
 };
 // nullptr, or what is wrong with the options / geometry (host only; no device is touched)
@@ -378,26 +372,20 @@ const char* redact_check(int format, int mode, int shape, int cell, float scale,
 // the same for a B x {p0, p1, p2} plane table: required planes present; device planes and pitches multiples of 4
 const char* redact_check_planes(int format, const void* const* planes, int B, int on_device, int pitch0, int pitch1);
 size_t redact_cells(int B, int h, int w, int cell);      // dwords of RedactParams::cells
-// Host frames of the blocking forms: B frames back to back in one device buffer of B * one bytes, every plane at a 4-byte aligned
-// offset with a pitch rounded up to 4; the copies move the row bytes only, so the host's own padding is neither read nor written
-struct RedactStage { int row0, row1, pitch0, pitch1, rows1; size_t off1, off2, one; };
-RedactStage redact_stage_layout(int format, int h, int w);
-hipError_t redact_stage_copy(hipStream_t s, const RedactStage& st, int format, void* const* host_planes, int B, int h, int pitch0, int pitch1,
-                             uint8_t* dev, bool to_device);
 hipError_t launch_redact_faces(hipStream_t s, const RedactParams& p);
 
-// Blur redaction in the source frame (cf_blur.hip): every sample that a kept face covers (boxes, coverage and faces as RedactParams)
+// Blur redaction in the source frame (cf_blur.hip): every sample that a kept face covers (frames, faces and coverage as RedactParams)
 // becomes the box_b * box_b * box_b filtered value of the untouched frame.  A first launch only reads the frame and writes the value of
 // every covered sample into `scratch`, which mirrors the planes in the layout of redact_stage_layout (B * one bytes); a second launch
 // only writes the frame.
 constexpr int kBlurMaxRadius = 24;
 struct BlurParams {
-    int format, shape;
+    FrameGeo g;
+    FaceList f;
+    int shape;
     int radius;           // 1..24: that r for every face; 0: per face, clamp(min(A, Bv) / 8, 1, 24)
     float scale;
     const void* const* planes;   // as RedactParams::planes
-    int B, h, w, pitch0, pitch1, H, W;
-    const float* boxes; int box_stride; const int* counts; int rows_cap, faces_cap;      // as RedactParams
     uint8_t* scratch;     // blur_scratch_bytes(format, B, h, w) bytes on the device
 };
 // nullptr, or what is wrong with the options / geometry (host only): redact_check's words plus the radius
@@ -412,7 +400,7 @@ hipError_t launch_blur_faces(hipStream_t s, const BlurParams& p);
 struct AlignFrameParams {
     AlignParams a;
     int format;                  // CF_YUV_NV12 .. CF_YUV_YV12, CF_FRAME_BGR
-    const void* const* planes;   // HOST table of B x {p0, p1, p2} DEVICE addresses as RedactParams::planes (read only), 4-byte aligned
+    const void* const* planes;   // HOST table of B x {p0, p1, p2} DEVICE addresses (cf_frame.h; read only), 4-byte aligned
     int h, w, pitch0, pitch1;    // pitches in bytes, multiples of 4
     double sx, sy;
 };
@@ -426,7 +414,7 @@ void op_error_set(const char* text);
 
 // Tiled detection (cf_tiles.hip).  The cutter writes dst [Bf * T][H][W][3] uint8 BGR: image f * T + t = the rectangle rects[t] of frame f,
 // converted (4:2:0) and resized to (H, W) as launch_yuv_to_bgr / launch_resize_u8 would the cropped frame.  planes: HOST table of
-// Bf x {p0, p1, p2} DEVICE addresses as RedactParams::planes (read only); rects: T rectangles on the DEVICE.
+// Bf x {p0, p1, p2} DEVICE addresses (cf_frame.h; read only); rects: T rectangles on the DEVICE.
 // tile_grid: the rectangles of cf_tile_grid (host only).  tiles_check: nullptr, or what is wrong (the text lives in `why`; host only).
 int tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, cf_tile_rect* rects, int cap, int* n);
 const char* tiles_check(std::string& why, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_tile_rect* rects, int T, int H, int W);
@@ -449,7 +437,7 @@ struct MergeParams {
     int max_out;
     float* dets;          // [Bf][max_out][5]
     float* lms;           // [Bf][max_out][10]
-    float* corners;       // [Bf][max_out][4]: the box rows RedactParams::boxes takes with (H, W) = (h, w)
+    float* corners;       // [Bf][max_out][4]: the box rows FaceList::boxes takes with (H, W) = (h, w)
     int* out_counts;      // [Bf], may exceed max_out
     int* flags;           // [Bf]: bit 0 = some tile of the frame had counts > rows
 };

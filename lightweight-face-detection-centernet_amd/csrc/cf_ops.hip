@@ -7,6 +7,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -744,8 +745,16 @@ int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, cons
     return sc.result("cf_op_align_faces");
 }
 
-// The kernel of cf_align_faces_frame on host frames.  Every plane is copied up whole (rows x pitch bytes), each into its own allocation,
-// so the caller's padding bytes sit beside the pixels on the device and Scope's 0xFF pad follows every plane.
+// Host frames of cf_op_align_frame and cf_op_cut_tiles -> their device plane table.  Every plane is copied up whole (rows x pitch bytes),
+// each into its own allocation, so the caller's padding bytes sit beside the pixels on the device and Scope's 0xFF pad follows every plane.
+static std::vector<const void*> up_planes(Scope& sc, int format, const void* const* hp, int B, int h, int pitch0, int pitch1) {
+    std::vector<const void*> dev((size_t)3 * B, nullptr);
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < frame_planes(format); ++k) dev[3 * b + k] = sc.up(hp[3 * b + k], k == 0 ? (size_t)h * pitch0 : (size_t)(h / 2) * pitch1);
+    return dev;
+}
+
+// The kernel of cf_align_faces_frame on host frames.
 int cf_op_align_frame(int device, int format, const cf_yuv_planes* host_frames, int B, int h, int w, int pitch0, int pitch1,
                       const float* lms, const int32_t* counts, const cf_align_opts* o, void* chips, double* matrices) {
     static_assert(sizeof(cf_yuv_planes) == 3 * sizeof(void*), "cf_yuv_planes is a table of three addresses");
@@ -765,10 +774,7 @@ int cf_op_align_frame(int device, int format, const cf_yuv_planes* host_frames, 
     if (why) { g_op_error = std::string("cf_op_align_frame: ") + why; return CF_EINVAL; }
     if (N == 0) return CF_OK;
     Scope sc(device);
-    const int np = format == CF_FRAME_BGR ? 1 : (format == CF_YUV_NV12 || format == CF_YUV_NV21) ? 2 : 3;
-    std::vector<const void*> dev((size_t)3 * B, nullptr);
-    for (int b = 0; b < B; ++b)
-        for (int k = 0; k < np; ++k) dev[3 * b + k] = sc.up(hp[3 * b + k], k == 0 ? (size_t)h * pitch0 : (size_t)(h / 2) * pitch1);
+    const std::vector<const void*> dev = up_planes(sc, format, hp, B, h, pitch0, pitch1);
     const size_t one = align_chip_bytes(o->size, o->format);
     p.planes = dev.data(); p.sx = 1.0; p.sy = 1.0;
     p.a.lms = (const float*)sc.up(lms, (size_t)N * 10 * sizeof(float)); p.a.lms_stride = 0; p.a.rows_cap = INT_MAX;
@@ -784,93 +790,67 @@ int cf_op_align_frame(int device, int format, const cf_yuv_planes* host_frames, 
     return sc.result("cf_op_align_frame");
 }
 
-// The kernels of cf_redact_faces on host frames (in place).  The packed box rows are spread to [B][max count][4] on the host, the
-// layout the decode leaves behind, so that the launches address them exactly as the engine's do.
-int cf_op_redact(int device, const cf_redact_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
-                 const float* boxes, const int32_t* counts, int H, int W) {
-    if (!o) { g_op_error = "cf_op_redact: null options"; return CF_EINVAL; }
+// What cf_op_redact and cf_op_blur share, on host frames (in place): the rest of the validation (`why`: what the entry point's own check
+// found), the packed box rows spread to [B][max count][4] on the host -- the layout the decode leaves behind, so that the launches
+// address them exactly as the engine's do --, the staging of the frames, and launch(sc, staged geometry, staged planes, faces) between
+// the copy up and the copy down.
+static int op_on_faces(const char* who, const char* why, int device, const FrameGeo& g, const cf_planes_rw* frames, const float* boxes,
+                       const int32_t* counts, int H, int W,
+                       const std::function<hipError_t(Scope&, const FrameGeo&, const void* const*, const FaceList&)>& launch) {
     static_assert(sizeof(cf_planes_rw) == 3 * sizeof(void*), "cf_planes_rw is a table of three addresses");
-    const char* why = redact_check(format, o->mode, o->shape, o->cell, o->scale, B, h, w, pitch0, pitch1);
-    if (!why) why = redact_check_planes(format, reinterpret_cast<const void* const*>(frames), B, 0, pitch0, pitch1);
+    const void* const* host_planes = reinterpret_cast<const void* const*>(frames);
+    if (!why) why = redact_check_planes(g.format, host_planes, g.B, 0, g.pitch0, g.pitch1);
     if (!why && (!counts || H < 1 || W < 1)) why = "null counts, or H / W below 1";
     int rows = 1;
     long long N = 0;
-    for (int b = 0; !why && b < B; ++b) {
+    for (int b = 0; !why && b < g.B; ++b) {
         if (counts[b] < 0 || counts[b] > (1 << 20)) why = "a count is negative or above 2^20";
         else { rows = std::max(rows, (int)counts[b]); N += counts[b]; }
     }
     if (!why && N > 0 && !boxes) why = "null boxes";
-    if (why) { g_op_error = std::string("cf_op_redact: ") + why; return CF_EINVAL; }
+    if (why) { g_op_error = std::string(who) + ": " + why; return CF_EINVAL; }
     if (N == 0) return CF_OK;
-    std::vector<float> spread((size_t)B * rows * 4, 0.0f);
-    for (long long b = 0, at = 0; b < B; at += counts[b], ++b)
+    std::vector<float> spread((size_t)g.B * rows * 4, 0.0f);
+    for (long long b = 0, at = 0; b < g.B; at += counts[b], ++b)
         if (counts[b]) memcpy(&spread[(size_t)b * rows * 4], boxes + at * 4, (size_t)counts[b] * 4 * sizeof(float));
     Scope sc(device);
-    RedactParams p{};
-    p.format = format; p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
-    p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
-    p.B = B; p.h = h; p.w = w; p.H = H; p.W = W;
-    p.boxes = sc.upv(spread); p.box_stride = rows; p.rows_cap = rows; p.faces_cap = rows;
-    p.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int));
-    if (o->mode == CF_REDACT_MOSAIC) p.cells = (uint32_t*)sc.alloc(redact_cells(B, h, w, o->cell) * sizeof(uint32_t));
-    const RedactStage st = redact_stage_layout(format, h, w);
-    uint8_t* stage = (uint8_t*)sc.alloc(st.one * B);
-    std::vector<const void*> dev((size_t)3 * B, nullptr);
-    for (int b = 0; b < B && stage; ++b) {
-        uint8_t* f = stage + (size_t)b * st.one;
-        dev[3 * b] = f;
-        if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
-        if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
-    }
-    p.planes = dev.data(); p.pitch0 = st.pitch0; p.pitch1 = st.pitch1;
-    void* const* host_planes = reinterpret_cast<void* const*>(frames);
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, true));
-    if (sc.err == hipSuccess) sc.chk(launch_redact_faces(sc.s, p));
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, false));
-    return sc.result("cf_op_redact");
+    const FaceList f{sc.upv(spread), rows, (const int*)sc.up(counts, (size_t)g.B * sizeof(int)), rows, rows, H, W};
+    const RedactStage st = redact_stage_layout(g.format, g.h, g.w);
+    uint8_t* stage = (uint8_t*)sc.alloc(st.one * g.B);
+    const std::vector<const void*> dev = stage_table(st, stage, g.format, g.B);
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, g.format, host_planes, g.B, g.h, g.pitch0, g.pitch1, stage, true));
+    if (sc.err == hipSuccess) sc.chk(launch(sc, FrameGeo{g.format, g.B, g.h, g.w, st.pitch0, st.pitch1}, dev.data(), f));
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, g.format, host_planes, g.B, g.h, g.pitch0, g.pitch1, stage, false));
+    return sc.result(who);
 }
 
-// The kernels of cf_blur_faces on host frames (in place): cf_op_redact's validation, box rows and staging.
+// The kernels of cf_redact_faces on host frames (in place).
+int cf_op_redact(int device, const cf_redact_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
+                 const float* boxes, const int32_t* counts, int H, int W) {
+    if (!o) { g_op_error = "cf_op_redact: null options"; return CF_EINVAL; }
+    const char* why = redact_check(format, o->mode, o->shape, o->cell, o->scale, B, h, w, pitch0, pitch1);
+    return op_on_faces("cf_op_redact", why, device, FrameGeo{format, B, h, w, pitch0, pitch1}, frames, boxes, counts, H, W,
+                       [&](Scope& sc, const FrameGeo& g, const void* const* planes, const FaceList& f) {
+        RedactParams p{};
+        p.g = g; p.f = f; p.planes = planes; p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
+        p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
+        if (o->mode == CF_REDACT_MOSAIC) p.cells = (uint32_t*)sc.alloc(redact_cells(B, h, w, o->cell) * sizeof(uint32_t));
+        return sc.err == hipSuccess ? launch_redact_faces(sc.s, p) : sc.err;
+    });
+}
+
+// The kernels of cf_blur_faces on host frames (in place).
 int cf_op_blur(int device, const cf_blur_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
                const float* boxes, const int32_t* counts, int H, int W) {
     if (!o) { g_op_error = "cf_op_blur: null options"; return CF_EINVAL; }
     const char* why = blur_check(format, o->shape, o->radius, o->scale, B, h, w, pitch0, pitch1);
-    if (!why) why = redact_check_planes(format, reinterpret_cast<const void* const*>(frames), B, 0, pitch0, pitch1);
-    if (!why && (!counts || H < 1 || W < 1)) why = "null counts, or H / W below 1";
-    int rows = 1;
-    long long N = 0;
-    for (int b = 0; !why && b < B; ++b) {
-        if (counts[b] < 0 || counts[b] > (1 << 20)) why = "a count is negative or above 2^20";
-        else { rows = std::max(rows, (int)counts[b]); N += counts[b]; }
-    }
-    if (!why && N > 0 && !boxes) why = "null boxes";
-    if (why) { g_op_error = std::string("cf_op_blur: ") + why; return CF_EINVAL; }
-    if (N == 0) return CF_OK;
-    std::vector<float> spread((size_t)B * rows * 4, 0.0f);
-    for (long long b = 0, at = 0; b < B; at += counts[b], ++b)
-        if (counts[b]) memcpy(&spread[(size_t)b * rows * 4], boxes + at * 4, (size_t)counts[b] * 4 * sizeof(float));
-    Scope sc(device);
-    BlurParams p{};
-    p.format = format; p.shape = o->shape; p.radius = o->radius; p.scale = o->scale;
-    p.B = B; p.h = h; p.w = w; p.H = H; p.W = W;
-    p.boxes = sc.upv(spread); p.box_stride = rows; p.rows_cap = rows; p.faces_cap = rows;
-    p.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int));
-    p.scratch = (uint8_t*)sc.alloc(blur_scratch_bytes(format, B, h, w));
-    const RedactStage st = redact_stage_layout(format, h, w);
-    uint8_t* stage = (uint8_t*)sc.alloc(st.one * B);
-    std::vector<const void*> dev((size_t)3 * B, nullptr);
-    for (int b = 0; b < B && stage; ++b) {
-        uint8_t* f = stage + (size_t)b * st.one;
-        dev[3 * b] = f;
-        if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
-        if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
-    }
-    p.planes = dev.data(); p.pitch0 = st.pitch0; p.pitch1 = st.pitch1;
-    void* const* host_planes = reinterpret_cast<void* const*>(frames);
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, true));
-    if (sc.err == hipSuccess) sc.chk(launch_blur_faces(sc.s, p));
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, false));
-    return sc.result("cf_op_blur");
+    return op_on_faces("cf_op_blur", why, device, FrameGeo{format, B, h, w, pitch0, pitch1}, frames, boxes, counts, H, W,
+                       [&](Scope& sc, const FrameGeo& g, const void* const* planes, const FaceList& f) {
+        BlurParams p{};
+        p.g = g; p.f = f; p.planes = planes; p.shape = o->shape; p.radius = o->radius; p.scale = o->scale;
+        p.scratch = (uint8_t*)sc.alloc(blur_scratch_bytes(format, B, h, w));
+        return sc.err == hipSuccess ? launch_blur_faces(sc.s, p) : sc.err;
+    });
 }
 
 int cf_tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, cf_tile_rect* rects, int cap, int* n) {
@@ -879,8 +859,7 @@ int cf_tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_ful
     return r;
 }
 
-// The cutter of cf_forward_tiles on host frames.  Every plane is copied up whole (rows x pitch bytes), each into its own allocation, so
-// the caller's padding bytes sit beside the pixels on the device and Scope's 0xFF pad follows every plane.
+// The cutter of cf_forward_tiles on host frames.
 int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1,
                     const cf_tile_rect* rects, int T, int H, int W, uint8_t* tiles) {
     static_assert(sizeof(cf_yuv_planes) == 3 * sizeof(void*), "cf_yuv_planes is a table of three addresses");
@@ -891,11 +870,7 @@ int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, in
     if (!bad && (long long)Bf * T * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
     if (bad) { g_op_error = std::string("cf_op_cut_tiles: ") + bad; return CF_EINVAL; }
     Scope sc(device);
-    const int np = format == CF_FRAME_BGR ? 1 : (format == CF_YUV_NV12 || format == CF_YUV_NV21) ? 2 : 3;
-    const void* const* hp = reinterpret_cast<const void* const*>(host_frames);
-    std::vector<const void*> dev((size_t)3 * Bf, nullptr);
-    for (int b = 0; b < Bf; ++b)
-        for (int k = 0; k < np; ++k) dev[3 * b + k] = sc.up(hp[3 * b + k], k == 0 ? (size_t)h * pitch0 : (size_t)(h / 2) * pitch1);
+    const std::vector<const void*> dev = up_planes(sc, format, reinterpret_cast<const void* const*>(host_frames), Bf, h, pitch0, pitch1);
     const cf_tile_rect* drects = (const cf_tile_rect*)sc.up(rects, (size_t)T * sizeof(cf_tile_rect));
     const size_t out_bytes = (size_t)Bf * T * H * W * 3;
     uint8_t* out = (uint8_t*)sc.alloc(out_bytes);

@@ -49,42 +49,26 @@ namespace {
 constexpr int kRedactMaxSlices = 64;
 
 struct RedactArgs {
-    int format, mode, shape, m;
+    FrameGeo g;           // g.B: the frames of this launch
+    FaceList f;
+    int mode, shape, m;
     float scale;
     uint32_t fill;        // SOLID: the three bytes in PLANE order (BGR; Y, first chroma channel in memory order, second)
-    int B, h, w, pitch0, pitch1, H, W;
-    const float* boxes; int box_stride;
-    const int* counts; int rows_cap, faces_cap;
     uint32_t* cells; int gw, gh;
     int group;            // lanes that share one cell in the means launch: 4, 16 or 64
 };
-
-// the face of this workgroup (blockIdx.x = image * faces_cap + keep position) and its box clipped to the frame; false = nothing to do.
-// Uniform over the workgroup.
-struct Clip { int b, X1, Y1, X2, Y2, cx1, cy1, cx2, cy2; };
-__device__ __forceinline__ bool face_clip(const RedactArgs& a, Clip& c) {
-    const int n = (int)blockIdx.x;
-    c.b = n / a.faces_cap;
-    const int i = n - c.b * a.faces_cap;
-    if (c.b >= a.B || i >= min(a.counts[c.b], a.rows_cap)) return false;
-    const FaceBox f = face_box(a.boxes + ((size_t)c.b * a.box_stride + i) * 4, a.scale, a.h, a.w, a.H, a.W);
-    if (!f.ok) return false;
-    c.X1 = f.X1; c.Y1 = f.Y1; c.X2 = f.X2; c.Y2 = f.Y2;
-    c.cx1 = max(f.X1, 0); c.cy1 = max(f.Y1, 0); c.cx2 = min(f.X2, a.w); c.cy2 = min(f.Y2, a.h);
-    return c.cx1 < c.cx2 && c.cy1 < c.cy2;
-}
 
 // MOSAIC, first launch: the means of the cells a face's clipped box touches.  A group of a.group lanes shares one cell (its lanes stride
 // over the cell's samples, a shuffle reduction adds them up, the group's first lane stores the dword); the cells of a face are spread
 // over the groups of its gridDim.y slices.  Reads the frame, writes a.cells only.
 __global__ void __launch_bounds__(256) redact_means_kernel(RedactArgs a, RedactPtrs t) {
     Clip c;
-    if (!face_clip(a, c)) return;
-    const int m = a.m, G = a.group;
+    if (!face_clip(a.g, a.f, a.scale, c)) return;
+    const int m = a.m, G = a.group, w = a.g.w, h = a.g.h, pitch0 = a.g.pitch0, pitch1 = a.g.pitch1;
     const int gx0 = c.cx1 / m, gy0 = c.cy1 / m, ncx = (c.cx2 - 1) / m - gx0 + 1, ncells = ncx * ((c.cy2 - 1) / m - gy0 + 1);
     const int tid = (int)threadIdx.x, sub = tid & (G - 1);
     const int grp = ((int)blockIdx.y * 256 + tid) / G, ngrp = (int)gridDim.y * 256 / G;
-    const bool bgr = a.format == CF_FRAME_BGR, il = a.format == CF_YUV_NV12 || a.format == CF_YUV_NV21;
+    const bool bgr = a.g.format == CF_FRAME_BGR, il = frame_is_il(a.g.format);
     const uint8_t* p0 = t.p0[c.b];
     const uint8_t* p1 = t.p1[c.b];
     const uint8_t* p2 = t.p2[c.b];
@@ -95,29 +79,29 @@ __global__ void __launch_bounds__(256) redact_means_kernel(RedactArgs a, RedactP
         int n0 = 1, n1 = 1, gx = 0, gy = 0;
         if (valid) {
             gy = gy0 + cell / ncx; gx = gx0 + (cell - (cell / ncx) * ncx);
-            const int xa = gx * m, ya = gy * m, cw = min(xa + m, a.w) - xa, ch = min(ya + m, a.h) - ya;
+            const int xa = gx * m, ya = gy * m, cw = min(xa + m, w) - xa, ch = min(ya + m, h) - ya;
             n0 = cw * ch;
             if (bgr) {
                 for (int k = sub; k < n0; k += G) {
                     const int y = k / cw, x = k - y * cw;
-                    const uint8_t* q = p0 + (size_t)(ya + y) * a.pitch0 + (size_t)(xa + x) * 3;
+                    const uint8_t* q = p0 + (size_t)(ya + y) * pitch0 + (size_t)(xa + x) * 3;
                     s0 += q[0]; s1 += q[1]; s2 += q[2];
                 }
                 n1 = n0;
             } else {
                 for (int k = sub; k < n0; k += G) {
                     const int y = k / cw, x = k - y * cw;
-                    s0 += p0[(size_t)(ya + y) * a.pitch0 + (xa + x)];
+                    s0 += p0[(size_t)(ya + y) * pitch0 + (xa + x)];
                 }
-                const int mc = m >> 1, xc = gx * mc, yc = gy * mc, cwc = min(xc + mc, a.w >> 1) - xc, chc = min(yc + mc, a.h >> 1) - yc;
+                const int mc = m >> 1, xc = gx * mc, yc = gy * mc, cwc = min(xc + mc, w >> 1) - xc, chc = min(yc + mc, h >> 1) - yc;
                 n1 = cwc * chc;
                 for (int k = sub; k < n1; k += G) {
                     const int j = k / cwc, i = k - j * cwc;
                     if (il) {
-                        const uint8_t* q = p1 + (size_t)(yc + j) * a.pitch1 + (size_t)(xc + i) * 2;
+                        const uint8_t* q = p1 + (size_t)(yc + j) * pitch1 + (size_t)(xc + i) * 2;
                         s1 += q[0]; s2 += q[1];
                     } else {
-                        const size_t o = (size_t)(yc + j) * a.pitch1 + (xc + i);
+                        const size_t o = (size_t)(yc + j) * pitch1 + (xc + i);
                         s1 += p1[o]; s2 += p2[o];
                     }
                 }
@@ -133,79 +117,59 @@ __global__ void __launch_bounds__(256) redact_means_kernel(RedactArgs a, RedactP
     }
 }
 
-// Second launch (the only one of SOLID): writes the covered samples of one face, plane after plane.  A plane pass is described by its
-// bytes per sample position (3 BGR, 1 planar, 2 interleaved chroma), whether its samples are chroma samples, and the plane-order
-// channel of its first byte.  Item = one aligned dword of a plane row inside the clipped box.  Reads a.cells, never the frame.
+// Second launch (the only one of SOLID): writes the covered samples of one face, plane after plane (PlanePass; the plane-order channel
+// of a pass's first byte is its number).  Item = one aligned dword of a plane row inside the clipped box.  Reads a.cells, never the frame.
 __global__ void __launch_bounds__(256) redact_write_kernel(RedactArgs a, RedactPtrs t) {
     Clip c;
-    if (!face_clip(a, c)) return;
-    const bool bgr = a.format == CF_FRAME_BGR, il = a.format == CF_YUV_NV12 || a.format == CF_YUV_NV21;
-    const int passes = bgr ? 1 : il ? 2 : 3;
+    if (!face_clip(a.g, a.f, a.scale, c)) return;
+    // the point test is written out, not face_covers: RECT is the clipped sample range itself, and face_covers' four bounds cost 6 SGPRs
     const long long A = c.X2 - c.X1, Bv = c.Y2 - c.Y1, R2 = (A * Bv) * (A * Bv);
     const int sumx = c.X1 + c.X2, sumy = c.Y1 + c.Y2;
     const bool ellipse = a.shape == CF_REDACT_ELLIPSE, mosaic = a.mode == CF_REDACT_MOSAIC;
     const int first = (int)blockIdx.y * 256 + (int)threadIdx.x, stride = (int)gridDim.y * 256;
-    for (int ps = 0; ps < passes; ++ps) {
+    for (int ps = 0; ps < frame_planes(a.g.format); ++ps) {
         uint8_t* base = ps == 0 ? t.p0[c.b] : ps == 1 ? t.p1[c.b] : t.p2[c.b];
-        const bool chroma = ps > 0;
-        const int bps = bgr ? 3 : (il && ps == 1) ? 2 : 1, ch0 = ps;
-        const int pitch = chroma ? a.pitch1 : a.pitch0;
-        const int sx0 = chroma ? c.cx1 >> 1 : c.cx1, sx1 = chroma ? c.cx2 >> 1 : c.cx2;       // 4:2:0: the clipped box is even on every side
-        const int sy0 = chroma ? c.cy1 >> 1 : c.cy1, sy1 = chroma ? c.cy2 >> 1 : c.cy2;
-        const int cs = chroma ? a.m >> 1 : a.m;
-        const int d0 = (bps * sx0) >> 2, nd = ((bps * sx1 + 3) >> 2) - d0, items = nd * (sy1 - sy0);
+        const PlanePass pp = plane_pass(a.g, ps, c);
+        const int bps = pp.bps, cs = pp.chroma ? a.m >> 1 : a.m, items = pp.nd * (pp.sy1 - pp.sy0);
         for (int item = first; item < items; item += stride) {
-            const int r = sy0 + item / nd, d = d0 + (item - (item / nd) * nd);
-            const long long dv = (chroma ? 4 * r + 2 : 2 * r + 1) - sumy, tv = dv * A, tv2 = tv * tv;
+            const int r = pp.sy0 + item / pp.nd, d = pp.d0 + (item - (item / pp.nd) * pp.nd);
+            const long long dv = pp.point(r) - sumy, tv = dv * A, tv2 = tv * tv;
             const uint32_t* cellrow = mosaic ? a.cells + ((size_t)c.b * a.gh + r / cs) * a.gw : nullptr;
             uint32_t val = 0;
             int mask = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int byte = 4 * d + k;
-                const int s = bps == 3 ? byte / 3 : bps == 2 ? byte >> 1 : byte, ch = ch0 + (byte - s * bps);
-                if (s < sx0 || s >= sx1) continue;
+                const int s = bps == 3 ? byte / 3 : bps == 2 ? byte >> 1 : byte, ch = ps + (byte - s * bps);
+                if (s < pp.sx0 || s >= pp.sx1) continue;
                 if (ellipse) {
-                    const long long tu = (long long)((chroma ? 4 * s + 2 : 2 * s + 1) - sumx) * Bv;
+                    const long long tu = (long long)(pp.point(s) - sumx) * Bv;
                     if (tu * tu + tv2 > R2) continue;
                 }
                 const uint32_t src = mosaic ? cellrow[s / cs] : a.fill;
                 val |= ((src >> (8 * ch)) & 255u) << (8 * k);
                 mask |= 1 << k;
             }
-            uint8_t* q = base + (size_t)r * pitch + (size_t)d * 4;
-            if (mask == 15) {
-                *reinterpret_cast<uint32_t*>(q) = val;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (mask & (1 << k)) q[k] = (uint8_t)(val >> (8 * k));
-            }
+            store_masked_dword(base + (size_t)r * pp.pitch + (size_t)d * 4, val, mask);
         }
     }
 }
 
-inline bool is_il(int format) { return format == CF_YUV_NV12 || format == CF_YUV_NV21; }
-
 }  // namespace
 
 const char* redact_check(int format, int mode, int shape, int cell, float scale, int B, int h, int w, int pitch0, int pitch1) {
-    if (format < CF_YUV_NV12 || format > CF_FRAME_BGR) return "unknown format (0..3: NV12, NV21, I420, YV12; 4: BGR)";
+    const char* geo = frame_geometry_check(FrameGeo{format, B, h, w, pitch0, pitch1}, 1, false);
+    if (format < CF_YUV_NV12 || format > CF_FRAME_BGR) return geo;             // the format is refused first, then the options
     if (mode != CF_REDACT_SOLID && mode != CF_REDACT_MOSAIC) return "unknown mode (0 = CF_REDACT_SOLID, 1 = CF_REDACT_MOSAIC)";
     if (shape != CF_REDACT_RECT && shape != CF_REDACT_ELLIPSE) return "unknown shape (0 = CF_REDACT_RECT, 1 = CF_REDACT_ELLIPSE)";
     if (mode == CF_REDACT_MOSAIC && (cell < 2 || cell > 256 || (cell & 1))) return "cell must be even and in [2, 256]";
     if (!(scale >= 0.25f && scale <= 4.0f)) return "scale must be in [0.25, 4]";
-    if (B < 1) return "B must be at least 1";
-    if (h < 1 || w < 1 || h > kRedactMaxSide || w > kRedactMaxSide) return "h and w must be in [1, 8192]";
-    if (format != CF_FRAME_BGR && ((h | w) & 1)) return "a 4:2:0 frame has even h and w";
-    if (format == CF_FRAME_BGR ? pitch0 < 3 * w : pitch0 < w) return "pitch0 is below the row size (3w bytes for BGR, w for a Y plane)";
-    if (format != CF_FRAME_BGR && pitch1 < (is_il(format) ? w : w / 2)) return "pitch1 is below the chroma row size (w bytes for NV12 / NV21, w/2 for I420 / YV12)";
-    return nullptr;
+    return geo;
 }
 
 const char* redact_check_planes(int format, const void* const* planes, int B, int on_device, int pitch0, int pitch1) {
     if (!planes) return "null frame table";
-    const int need = format == CF_FRAME_BGR ? 1 : is_il(format) ? 2 : 3;
+    const int need = frame_planes(format);
     for (int b = 0; b < B; ++b)
         for (int k = 0; k < need; ++k) {
             if (!planes[3 * b + k]) return "a frame has a null plane";
@@ -219,63 +183,30 @@ size_t redact_cells(int B, int h, int w, int cell) {
     return (size_t)B * ((h + cell - 1) / cell) * ((w + cell - 1) / cell);
 }
 
-RedactStage redact_stage_layout(int format, int h, int w) {
-    RedactStage st{};
-    const bool bgr = format == CF_FRAME_BGR, il = is_il(format);
-    st.row0 = bgr ? 3 * w : w; st.row1 = bgr ? 0 : il ? w : w / 2;
-    st.pitch0 = (st.row0 + 3) & ~3; st.pitch1 = (st.row1 + 3) & ~3;
-    st.rows1 = bgr ? 0 : h / 2;
-    st.off1 = (size_t)st.pitch0 * h; st.off2 = st.off1 + (size_t)st.pitch1 * st.rows1;
-    st.one = bgr ? st.off1 : il ? st.off2 : st.off2 + (size_t)st.pitch1 * st.rows1;
-    return st;
-}
-
-hipError_t redact_stage_copy(hipStream_t s, const RedactStage& st, int format, void* const* host_planes, int B, int h, int pitch0, int pitch1,
-                             uint8_t* dev, bool to_device) {
-    const int np = format == CF_FRAME_BGR ? 1 : is_il(format) ? 2 : 3;
-    for (int b = 0; b < B; ++b)
-        for (int k = 0; k < np; ++k) {
-            uint8_t* d = dev + (size_t)b * st.one + (k == 0 ? 0 : k == 1 ? st.off1 : st.off2);
-            void* hp = host_planes[3 * b + k];
-            const size_t dp = k == 0 ? st.pitch0 : st.pitch1, hpitch = k == 0 ? pitch0 : pitch1, row = k == 0 ? st.row0 : st.row1;
-            const size_t rows = k == 0 ? h : st.rows1;
-            const hipError_t e = to_device ? hipMemcpy2DAsync(d, dp, hp, hpitch, row, rows, hipMemcpyHostToDevice, s)
-                                           : hipMemcpy2DAsync(hp, hpitch, d, dp, row, rows, hipMemcpyDeviceToHost, s);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
-
 hipError_t launch_redact_faces(hipStream_t s, const RedactParams& p) {
-    if (redact_check(p.format, p.mode, p.shape, p.cell, p.scale, p.B, p.h, p.w, p.pitch0, p.pitch1) ||
-        redact_check_planes(p.format, p.planes, p.B, 1, p.pitch0, p.pitch1) || p.H < 1 || p.W < 1 || !p.boxes || !p.counts ||
-        p.box_stride < 1 || p.rows_cap < 1 || p.faces_cap < 1 || (p.mode == CF_REDACT_MOSAIC && !p.cells))
+    const FrameGeo& g = p.g;
+    if (redact_check(g.format, p.mode, p.shape, p.cell, p.scale, g.B, g.h, g.w, g.pitch0, g.pitch1) ||
+        redact_check_planes(g.format, p.planes, g.B, 1, g.pitch0, g.pitch1) || p.f.H < 1 || p.f.W < 1 || !p.f.boxes || !p.f.counts ||
+        p.f.box_stride < 1 || p.f.rows_cap < 1 || p.f.faces_cap < 1 || (p.mode == CF_REDACT_MOSAIC && !p.cells))
         return hipErrorInvalidValue;
-    const bool swap = p.format == CF_YUV_NV21 || p.format == CF_YUV_YV12;      // memory order V, U
+    const bool swap = frame_swaps_chroma(g.format);
     RedactArgs a{};
-    a.format = p.format; a.mode = p.mode; a.shape = p.shape; a.m = p.mode == CF_REDACT_MOSAIC ? p.cell : 2; a.scale = p.scale;
+    a.g = g; a.f = p.f; a.mode = p.mode; a.shape = p.shape; a.m = p.mode == CF_REDACT_MOSAIC ? p.cell : 2; a.scale = p.scale;
     a.fill = (uint32_t)p.fill[0] | ((uint32_t)p.fill[swap ? 2 : 1] << 8) | ((uint32_t)p.fill[swap ? 1 : 2] << 16);
-    a.h = p.h; a.w = p.w; a.pitch0 = p.pitch0; a.pitch1 = p.pitch1; a.H = p.H; a.W = p.W;
-    a.box_stride = p.box_stride; a.rows_cap = p.rows_cap; a.faces_cap = p.faces_cap;
-    a.gw = (p.w + a.m - 1) / a.m; a.gh = (p.h + a.m - 1) / a.m;
+    a.gw = (g.w + a.m - 1) / a.m; a.gh = (g.h + a.m - 1) / a.m;
     a.group = a.m <= 4 ? 4 : a.m <= 16 ? 16 : 64;
-    for (int f0 = 0; f0 < p.B; f0 += kRedactFrames) {
-        const int nb = p.B - f0 < kRedactFrames ? p.B - f0 : kRedactFrames;
-        RedactPtrs tab{};
-        for (int k = 0; k < nb; ++k) {
-            tab.p0[k] = (uint8_t*)p.planes[3 * (f0 + k)];
-            tab.p1[k] = (uint8_t*)p.planes[3 * (f0 + k) + 1];
-            tab.p2[k] = (uint8_t*)p.planes[3 * (f0 + k) + 2];
-        }
-        a.B = nb;
-        a.boxes = p.boxes + (size_t)f0 * p.box_stride * 4;
-        a.counts = p.counts + f0;
+    for (int f0 = 0; f0 < g.B; f0 += kRedactFrames) {
+        const int nb = std::min(g.B - f0, kRedactFrames);
+        const RedactPtrs tab = frame_ptrs<kRedactFrames>(p.planes, g.format, f0, nb, false);
+        a.g.B = nb;
+        a.f.boxes = p.f.boxes + (size_t)f0 * p.f.box_stride * 4;
+        a.f.counts = p.f.counts + f0;
         a.cells = p.cells ? p.cells + (size_t)f0 * a.gh * a.gw : nullptr;
-        const long long faces = (long long)nb * p.faces_cap;
+        const long long faces = (long long)nb * p.f.faces_cap;
         if (faces > INT_MAX) return hipErrorInvalidValue;
         // slices per face: enough that one thread of a frame-sized face handles at most ~32 dwords, as long as the launch stays
         // near kRedactGridTarget workgroups (most of which belong to faces that do not exist and leave at once)
-        const long long dwords = (long long)p.h * (p.pitch0 / 4 + 1);
+        const long long dwords = (long long)g.h * (g.pitch0 / 4 + 1);
         long long slices = (dwords + 256 * 32 - 1) / (256 * 32);
         slices = std::min<long long>(slices, std::max<long long>(kRedactGridTarget / faces, 1));
         slices = std::min<long long>(std::max<long long>(slices, 1), kRedactMaxSlices);

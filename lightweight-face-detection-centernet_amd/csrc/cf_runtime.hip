@@ -1653,6 +1653,20 @@ int cf_decode_threshold_sized(cf_ctx* c, int mode, float score_thresh, float nms
     return CF_OK;
 }
 
+// The host-output tail of cf_align_faces and cf_align_faces_frame: the offsets, then the chips and matrices they announce, from the
+// context's scratch
+static int align_copy_out(cf_ctx* c, int B, size_t one, int cap_faces, void* chips, double* matrices, int32_t* offsets) {
+    HIPCHK(c, hipMemcpyAsync(offsets, c->al_off, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)std::min((int)offsets[B], cap_faces);
+    if (n > 0) {
+        HIPCHK(c, hipMemcpyAsync(chips, c->al_chips, n * one, hipMemcpyDeviceToHost, c->stream));
+        if (matrices) HIPCHK(c, hipMemcpyAsync(matrices, c->al_mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return CF_OK;
+}
+
 // Aligned chips of the faces the last threshold decode kept (cf_align.hip): one launch on the stream that carried the decode, reading
 // the decode's device-side counts and network-coordinate landmark rows and the uint8 batch the forward read.
 int cf_align_faces(cf_ctx* c, const cf_align_opts* o, void* chips, double* matrices, int32_t* offsets, int cap_faces, int out_on_device) {
@@ -1695,21 +1709,13 @@ int cf_align_faces(cf_ctx* c, const cf_align_opts* o, void* chips, double* matri
     HIPCHK(c, launch_align_faces(c->stream, p));
     if (c->al_slot >= 0) HIPCHK(c, hipEventRecord(c->ev_slot_free[c->al_slot], c->stream));      // the staging slot has one more reader
     if (out_on_device) return CF_OK;
-    HIPCHK(c, hipMemcpyAsync(offsets, c->al_off, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t n = (size_t)std::min((int)offsets[B], cap_faces);
-    if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(chips, c->al_chips, n * one, hipMemcpyDeviceToHost, c->stream));
-        if (matrices) HIPCHK(c, hipMemcpyAsync(matrices, c->al_mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return CF_OK;
+    return align_copy_out(c, B, one, cap_faces, chips, matrices, offsets);
 }
 
 // Redaction of the faces the last threshold decode kept, in frames the caller names (cf_redact.hip): the launches go on the stream that
 // carried the decode and read its device-side counts and network-coordinate box rows.  Host frames are staged in rd_stage and copied
 // back; the scratch of the mosaic's cell means grows to the largest grid seen, like the decode workspace.
-static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char* what, const char* who = "cf_redact_faces") {
+static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char* what, const char* who) {
     if (*have >= need_bytes) return CF_OK;
     if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(*p); }        // earlier launches may still use it
     *p = nullptr; *have = 0;
@@ -1719,48 +1725,43 @@ static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char
     return CF_OK;
 }
 
-// What cf_redact_faces and cf_blur_faces share: the state rules and the face rows (the last threshold decode's, or the merged rows of a
-// tiled forward), and the frames -- the caller's device planes as they are, or host frames staged in rd_stage around the launches.
-struct FaceRows { const float* boxes; const int* counts; int box_stride, rows_cap, faces_cap, H, W; };
-static int face_rows(cf_ctx* c, const char* who, int B, int h, int w, FaceRows& f) {
+// What cf_redact_faces, cf_blur_faces and cf_align_faces_frame share: the state rules and the face rows (the last threshold decode's, in
+// network coordinates, or the merged rows of a tiled forward, in frame pixels), and the frames -- the caller's device planes as they are,
+// or host frames staged in rd_stage around the launches.  want_lms: the caller reads the landmark rows, not the boxes.
+struct FaceRows { FaceList f; const float* lms; bool tiled; };
+static int face_rows(cf_ctx* c, const char* who, int B, int h, int w, bool want_lms, FaceRows& r) {
     if (c->last_B < 1) return c->fail(CF_ESTATE, "%s before cf_forward", who);
     if (!c->al_in) return c->fail(CF_ESTATE, "%s: an upload was started after the last forward", who);
-    if (c->al_rows < 1 || !c->t_detsnet || !c->t_counts) return c->fail(CF_ESTATE, "%s without a threshold decode of the last forward", who);
-    const bool tiled = c->tl_T > 0;                                          // the boxes are the merged ones, in frame pixels
-    if (tiled) {
+    if (c->al_rows < 1 || !(want_lms ? c->t_lmsnet : c->t_detsnet) || !c->t_counts) return c->fail(CF_ESTATE, "%s without a threshold decode of the last forward", who);
+    r.tiled = c->tl_T > 0;
+    if (r.tiled) {
         if (!c->tl_merged) return c->fail(CF_ESTATE, "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
         if (B != c->tl_Bf) return c->fail(CF_EINVAL, "%s: B=%d, the tiled forward had %d frames", who, B, c->tl_Bf);
         if (h != c->tl_h || w != c->tl_w) return c->fail(CF_EINVAL, "%s: %d x %d frames, the tiled forward had %d x %d", who, w, h, c->tl_w, c->tl_h);
-    } else if (B != c->last_B) return c->fail(CF_EINVAL, "%s: B=%d, the last forward had %d images", who, B, c->last_B);
-    f.H = c->H; f.W = c->W;
-    f.boxes = c->t_detsnet; f.box_stride = c->al_rows; f.rows_cap = c->al_rows; f.faces_cap = c->al_rows; f.counts = c->t_counts;
-    if (tiled) {
-        f.H = h; f.W = w;
-        f.boxes = (const float*)c->tl_buf[6]; f.box_stride = c->tl_maxout; f.rows_cap = c->tl_maxout; f.faces_cap = c->tl_maxout; f.counts = (const int*)c->tl_buf[7];
+        r.f = FaceList{(const float*)c->tl_buf[6], c->tl_maxout, (const int*)c->tl_buf[7], c->tl_maxout, c->tl_maxout, h, w};
+        r.lms = (const float*)c->tl_buf[5];
+    } else {
+        if (B != c->last_B) return c->fail(CF_EINVAL, "%s: B=%d, the last forward had %d images", who, B, c->last_B);
+        r.f = FaceList{c->t_detsnet, c->al_rows, c->t_counts, c->al_rows, c->al_rows, c->H, c->W};
+        r.lms = c->t_lmsnet;
     }
     return CF_OK;
 }
 
-// launch(planes, pitch0, pitch1) -> hipError_t enqueues the kernels on c->stream
-static int on_frames(cf_ctx* c, const char* who, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w, int pitch0, int pitch1,
+// launch(planes, pitch0, pitch1) -> hipError_t enqueues the kernels on c->stream.  Host frames: the call blocks until they have been
+// read and -- write_back -- written.  g is a copy: launch may rewrite the caller's geometry with the staged pitches, the copy back
+// needs the host's.
+static int on_frames(cf_ctx* c, const char* who, const FrameGeo g, const void* const* planes, int on_device, bool write_back,
                      const std::function<hipError_t(const void* const*, int, int)>& launch) {
     if (on_device) {
-        HIPCHK(c, launch(reinterpret_cast<const void* const*>(frames), pitch0, pitch1));
+        HIPCHK(c, launch(planes, g.pitch0, g.pitch1));
         return CF_OK;
     }
-    const RedactStage st = redact_stage_layout(format, h, w);
-    int r = grow(c, (void**)&c->rd_stage, &c->rd_stage_bytes, st.one * B, "frame staging", who); if (r) return r;
-    void* const* host_planes = reinterpret_cast<void* const*>(frames);
-    std::vector<const void*> dev((size_t)3 * B, nullptr);
-    for (int b = 0; b < B; ++b) {
-        uint8_t* f = c->rd_stage + (size_t)b * st.one;
-        dev[3 * b] = f;
-        if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
-        if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
-    }
-    HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, true));
-    HIPCHK(c, launch(dev.data(), st.pitch0, st.pitch1));
-    HIPCHK(c, redact_stage_copy(c->stream, st, format, host_planes, B, h, pitch0, pitch1, c->rd_stage, false));
+    const RedactStage st = redact_stage_layout(g.format, g.h, g.w);
+    int r = grow(c, (void**)&c->rd_stage, &c->rd_stage_bytes, st.one * g.B, "frame staging", who); if (r) return r;
+    HIPCHK(c, redact_stage_copy(c->stream, st, g.format, planes, g.B, g.h, g.pitch0, g.pitch1, c->rd_stage, true));
+    HIPCHK(c, launch(stage_table(st, c->rd_stage, g.format, g.B).data(), st.pitch0, st.pitch1));
+    if (write_back) HIPCHK(c, redact_stage_copy(c->stream, st, g.format, planes, g.B, g.h, g.pitch0, g.pitch1, c->rd_stage, false));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CF_OK;
 }
@@ -1775,23 +1776,22 @@ int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_pla
         return c->fail(CF_EINVAL, "cf_redact_faces: %s", why);
     if (const char* why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1))
         return c->fail(CF_EINVAL, "cf_redact_faces: %s", why);
-    FaceRows f{};
-    if (int r = face_rows(c, "cf_redact_faces", B, h, w, f)) return r;
+    FaceRows rows{};
+    if (int r = face_rows(c, "cf_redact_faces", B, h, w, false, rows)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     RedactParams p{};
-    p.format = format; p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
+    p.g = FrameGeo{format, B, h, w, pitch0, pitch1}; p.f = rows.f;
+    p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
     p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
-    p.B = B; p.h = h; p.w = w; p.H = f.H; p.W = f.W;
-    p.boxes = f.boxes; p.box_stride = f.box_stride; p.rows_cap = f.rows_cap; p.faces_cap = f.faces_cap; p.counts = f.counts;
     if (o->mode == CF_REDACT_MOSAIC) {
         size_t have = c->rd_cells_n * sizeof(uint32_t);
-        int r = grow(c, (void**)&c->rd_cells, &have, redact_cells(B, h, w, o->cell) * sizeof(uint32_t), "mosaic cell means");
+        int r = grow(c, (void**)&c->rd_cells, &have, redact_cells(B, h, w, o->cell) * sizeof(uint32_t), "mosaic cell means", "cf_redact_faces");
         c->rd_cells_n = have / sizeof(uint32_t);
         if (r) return r;
         p.cells = c->rd_cells;
     }
-    return on_frames(c, "cf_redact_faces", format, frames, on_device, B, h, w, pitch0, pitch1, [&](const void* const* pl, int p0, int p1) {
-        p.planes = pl; p.pitch0 = p0; p.pitch1 = p1;
+    return on_frames(c, "cf_redact_faces", p.g, planes, on_device, true, [&](const void* const* pl, int p0, int p1) {
+        p.planes = pl; p.g.pitch0 = p0; p.g.pitch1 = p1;
         return launch_redact_faces(c->stream, p);
     });
 }
@@ -1802,21 +1802,21 @@ int cf_blur_faces(cf_ctx* c, const cf_blur_opts* o, int format, const cf_planes_
                   int pitch0, int pitch1) {
     if (!c) return CF_EINVAL;
     if (!o) return c->fail(CF_EINVAL, "cf_blur_faces: null options");
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
     if (const char* why = blur_check(format, o->shape, o->radius, o->scale, B, h, w, pitch0, pitch1))
         return c->fail(CF_EINVAL, "cf_blur_faces: %s", why);
-    if (const char* why = redact_check_planes(format, reinterpret_cast<const void* const*>(frames), B, on_device, pitch0, pitch1))
+    if (const char* why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1))
         return c->fail(CF_EINVAL, "cf_blur_faces: %s", why);
-    FaceRows f{};
-    if (int r = face_rows(c, "cf_blur_faces", B, h, w, f)) return r;
+    FaceRows rows{};
+    if (int r = face_rows(c, "cf_blur_faces", B, h, w, false, rows)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     BlurParams p{};
-    p.format = format; p.shape = o->shape; p.radius = o->radius; p.scale = o->scale;
-    p.B = B; p.h = h; p.w = w; p.H = f.H; p.W = f.W;
-    p.boxes = f.boxes; p.box_stride = f.box_stride; p.rows_cap = f.rows_cap; p.faces_cap = f.faces_cap; p.counts = f.counts;
+    p.g = FrameGeo{format, B, h, w, pitch0, pitch1}; p.f = rows.f;
+    p.shape = o->shape; p.radius = o->radius; p.scale = o->scale;
     if (int r = grow(c, (void**)&c->bl_scratch, &c->bl_scratch_bytes, blur_scratch_bytes(format, B, h, w), "blur scratch", "cf_blur_faces")) return r;
     p.scratch = c->bl_scratch;
-    return on_frames(c, "cf_blur_faces", format, frames, on_device, B, h, w, pitch0, pitch1, [&](const void* const* pl, int p0, int p1) {
-        p.planes = pl; p.pitch0 = p0; p.pitch1 = p1;
+    return on_frames(c, "cf_blur_faces", p.g, planes, on_device, true, [&](const void* const* pl, int p0, int p1) {
+        p.planes = pl; p.g.pitch0 = p0; p.g.pitch1 = p1;
         return launch_blur_faces(c->stream, p);
     });
 }
@@ -1840,23 +1840,11 @@ int cf_align_faces_frame(cf_ctx* c, const cf_align_opts* o, int format, const cf
         return CF_EINVAL;
     }
     if (why) return c->fail(CF_EINVAL, "cf_align_faces_frame: %s", why);
-    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_align_faces_frame before cf_forward");
-    if (!c->al_in) return c->fail(CF_ESTATE, "cf_align_faces_frame: an upload was started after the last forward");
-    if (c->al_rows < 1 || !c->t_lmsnet || !c->t_counts) return c->fail(CF_ESTATE, "cf_align_faces_frame without a threshold decode of the last forward");
-    const bool tiled = c->tl_T > 0;                                          // the landmarks are the merged ones, in frame pixels
-    if (tiled) {
-        if (!c->tl_merged) return c->fail(CF_ESTATE, "cf_align_faces_frame after cf_forward_tiles without a cf_merge_tiles of the last decode");
-        if (B != c->tl_Bf) return c->fail(CF_EINVAL, "cf_align_faces_frame: B=%d, the tiled forward had %d frames", B, c->tl_Bf);
-        if (h != c->tl_h || w != c->tl_w) return c->fail(CF_EINVAL, "cf_align_faces_frame: %d x %d frames, the tiled forward had %d x %d", w, h, c->tl_w, c->tl_h);
-    } else if (B != c->last_B) return c->fail(CF_EINVAL, "cf_align_faces_frame: B=%d, the last forward had %d images", B, c->last_B);
+    FaceRows rows{};
+    if (int r = face_rows(c, "cf_align_faces_frame", B, h, w, true, rows)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    if (tiled) {
-        p.a.lms = (const float*)c->tl_buf[5]; p.a.lms_stride = c->tl_maxout; p.a.rows_cap = c->tl_maxout; p.a.counts = (const int*)c->tl_buf[7];
-        p.sx = 1.0; p.sy = 1.0;
-    } else {
-        p.a.lms = c->t_lmsnet; p.a.lms_stride = c->al_rows; p.a.rows_cap = c->al_rows; p.a.counts = c->t_counts;
-        p.sx = (double)w / (double)c->W; p.sy = (double)h / (double)c->H;
-    }
+    p.a.lms = rows.lms; p.a.lms_stride = rows.f.box_stride; p.a.rows_cap = rows.f.rows_cap; p.a.counts = rows.f.counts;
+    p.sx = (double)w / (double)rows.f.W; p.sy = (double)h / (double)rows.f.H;      // merged rows are in frame pixels: 1.0
     p.a.cap_faces = cap_faces;
     const size_t one = align_chip_bytes(o->size, o->format);
     if (out_on_device) {
@@ -1873,37 +1861,14 @@ int cf_align_faces_frame(cf_ctx* c, const cf_align_opts* o, int format, const cf
         if (!c->al_off) HIPCHK(c, hipMalloc((void**)&c->al_off, ((size_t)c->max_batch + 1) * sizeof(int)));      // (B <= max_batch)
         p.a.chips = c->al_chips; p.a.mats = matrices ? c->al_mats : nullptr; p.a.offsets = c->al_off;
     }
-    std::vector<const void*> dev;
-    if (in_on_device) {
-        p.planes = planes;
-    } else {
-        const RedactStage st = redact_stage_layout(format, h, w);
-        int r = grow(c, (void**)&c->rd_stage, &c->rd_stage_bytes, st.one * B, "frame staging", "cf_align_faces_frame"); if (r) return r;
-        dev.assign((size_t)3 * B, nullptr);
-        for (int b = 0; b < B; ++b) {
-            uint8_t* f = c->rd_stage + (size_t)b * st.one;
-            dev[3 * b] = f;
-            if (format != CF_FRAME_BGR) dev[3 * b + 1] = f + st.off1;
-            if (format == CF_YUV_I420 || format == CF_YUV_YV12) dev[3 * b + 2] = f + st.off2;
-        }
-        p.planes = dev.data(); p.pitch0 = st.pitch0; p.pitch1 = st.pitch1;
-        HIPCHK(c, redact_stage_copy(c->stream, st, format, reinterpret_cast<void* const*>(const_cast<cf_yuv_planes*>(frames)), B, h, pitch0, pitch1,
-                                    c->rd_stage, true));
-    }
-    HIPCHK(c, launch_align_frame(c->stream, p));
-    if (out_on_device) {
-        if (!in_on_device) HIPCHK(c, hipStreamSynchronize(c->stream));       // the host form blocks: the caller's frames have been read
-        return CF_OK;
-    }
-    HIPCHK(c, hipMemcpyAsync(offsets, c->al_off, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t n = (size_t)std::min((int)offsets[B], cap_faces);
-    if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(chips, c->al_chips, n * one, hipMemcpyDeviceToHost, c->stream));
-        if (matrices) HIPCHK(c, hipMemcpyAsync(matrices, c->al_mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return CF_OK;
+    // host frames are only read: staged, not copied back
+    const int r = on_frames(c, "cf_align_faces_frame", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, in_on_device, false,
+                            [&](const void* const* pl, int p0, int p1) {
+        p.planes = pl; p.pitch0 = p0; p.pitch1 = p1;
+        return launch_align_frame(c->stream, p);
+    });
+    if (r || out_on_device) return r;
+    return align_copy_out(c, B, one, cap_faces, chips, matrices, offsets);
 }
 
 // Tiled forward: the cutter (cf_tiles.hip) writes the Bf * T tile images to input_resized, so the plan and its graphs are those of
@@ -1936,20 +1901,16 @@ int cf_forward_tiles(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_
         const size_t bytes = st.one * Bf;
         int r = src_stage_begin(c, bytes); if (r) return r;
         const hipStream_t cs = src_stage_stream(c, bytes);
-        const bool bgr = format == CF_FRAME_BGR, three = format == CF_YUV_I420 || format == CF_YUV_YV12;
+        const bool bgr = format == CF_FRAME_BGR, three = frame_planes(format) == 3;
         const uint8_t* base = (const uint8_t*)frames[0].y;
         bool dense = pitch0 == st.row0 && st.pitch0 == st.row0 && (bgr || (pitch1 == st.row1 && st.pitch1 == st.row1));
-        std::vector<const void*> dev((size_t)3 * Bf, nullptr);
-        for (int b = 0; b < Bf; ++b) {
+        for (int b = 0; b < Bf && dense; ++b) {
             const uint8_t* hf = base + b * st.one;
-            if (dense) dense = frames[b].y == hf && (bgr || frames[b].c0 == hf + st.off1) && (!three || frames[b].c1 == hf + st.off2);
-            uint8_t* f = c->src_stage + (size_t)b * st.one;
-            dev[3 * b] = f;
-            if (!bgr) dev[3 * b + 1] = f + st.off1;
-            if (three) dev[3 * b + 2] = f + st.off2;
+            dense = frames[b].y == hf && (bgr || frames[b].c0 == hf + st.off1) && (!three || frames[b].c1 == hf + st.off2);
         }
+        const std::vector<const void*> dev = stage_table(st, c->src_stage, format, Bf);
         if (dense) HIPCHK(c, hipMemcpyAsync(c->src_stage, base, bytes, hipMemcpyHostToDevice, cs));
-        else HIPCHK(c, redact_stage_copy(cs, st, format, reinterpret_cast<void* const*>(const_cast<cf_yuv_planes*>(frames)), Bf, h, pitch0, pitch1, c->src_stage, true));
+        else HIPCHK(c, redact_stage_copy(cs, st, format, planes, Bf, h, pitch0, pitch1, c->src_stage, true));
         if (cs != c->stream) {
             HIPCHK(c, hipEventRecord(c->ev_src_copy, cs));
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_src_copy, 0));

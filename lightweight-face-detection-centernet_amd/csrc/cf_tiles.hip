@@ -30,7 +30,7 @@ namespace {
 
 constexpr int kCutFrames = 64;                       // frames per launch: 3 x 64 pointers = 1.5 KB of kernel arguments
 constexpr int kCutRows = 8;                          // output rows per lane (one set of column coefficients)
-struct CutPtrs { const uint8_t* p0[kCutFrames]; const uint8_t* p1[kCutFrames]; const uint8_t* p2[kCutFrames]; };
+using CutPtrs = FramePtrs<kCutFrames>;
 
 // SRC: 0 = BGR rows, 1 = one interleaved chroma plane (NV12 / NV21), 2 = two chroma planes (I420; YV12 on a swapped table);
 // VF: V first in the interleaved pairs (NV21).  One source pixel -> B | G << 8 | R << 16
@@ -155,8 +155,6 @@ __global__ void __launch_bounds__(1024) merge_collect_kernel(MergeParams p) {
     if (tid == 0) { p.cand_count[f] = (int)base; p.flags[f] = truncated; }
 }
 
-bool is_il(int format) { return format == CF_YUV_NV12 || format == CF_YUV_NV21; }
-
 }  // namespace
 
 int tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, cf_tile_rect* rects, int cap, int* n) {
@@ -181,12 +179,9 @@ int tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, 
 
 const char* tiles_check(std::string& why, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_tile_rect* rects, int T, int H, int W) {
     auto say = [&](const std::string& s) { why = s; return why.c_str(); };
-    if (format < CF_YUV_NV12 || format > CF_FRAME_BGR) return say("unknown format (0..4: NV12, NV21, I420, YV12, BGR)");
     if (Bf < 1 || T < 1) return say("Bf and T must be at least 1");
-    if (h < 2 || w < 2 || ((h | w) & 1) || h > kRedactMaxSide || w > kRedactMaxSide) return say("h and w must be even and in [2, 8192]");
     if (H < 1 || W < 4 || (W & 3)) return say("W must be a multiple of 4 and H at least 1");
-    if (format == CF_FRAME_BGR ? pitch0 < 3 * w : pitch0 < w) return say("pitch0 is below the row size (3w bytes for BGR, w for a Y plane)");
-    if (format != CF_FRAME_BGR && pitch1 < (is_il(format) ? w : w / 2)) return say("pitch1 is below the chroma row size (w bytes for NV12 / NV21, w/2 for I420 / YV12)");
+    if (const char* geo = frame_geometry_check(FrameGeo{format, Bf, h, w, pitch0, pitch1}, 2, true)) return say(geo);
     if (!rects) return say("null rectangle table");
     for (int t = 0; t < T; ++t) {
         const cf_tile_rect& r = rects[t];
@@ -209,15 +204,9 @@ hipError_t launch_cut_tiles(hipStream_t s, int format, const void* const* planes
     if (format < CF_YUV_NV12 || format > CF_FRAME_BGR || !planes || !rects || !dst || Bf < 1 || T < 1 || T > 65535 || H < 1 || W < 4 || (W & 3))
         return hipErrorInvalidValue;
     const long long n = (long long)((H + kCutRows - 1) / kCutRows) * (W >> 2);
-    const bool swap = format == CF_YUV_YV12;             // I420 with the chroma planes swapped (as launch_yuv_to_bgr)
     for (int f0 = 0; f0 < Bf; f0 += kCutFrames) {
         const int nb = Bf - f0 < kCutFrames ? Bf - f0 : kCutFrames;
-        CutPtrs tab{};
-        for (int k = 0; k < nb; ++k) {
-            tab.p0[k] = (const uint8_t*)planes[3 * (f0 + k)];
-            tab.p1[k] = (const uint8_t*)planes[3 * (f0 + k) + (swap ? 2 : 1)];
-            tab.p2[k] = (const uint8_t*)planes[3 * (f0 + k) + (swap ? 1 : 2)];
-        }
+        const CutPtrs tab = frame_ptrs<kCutFrames>(planes, format, f0, nb, true);      // YV12: the I420 kernel on swapped planes (as launch_yuv_to_bgr)
         const dim3 grid((unsigned)((n + 255) / 256), (unsigned)T, (unsigned)nb);
         uint8_t* out = dst + (size_t)f0 * T * H * W * 3;
         switch (format) {

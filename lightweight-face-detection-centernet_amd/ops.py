@@ -248,10 +248,7 @@ def redact_faces(frames, boxes, counts, net_hw, fmt="bgr", mode="mosaic", shape=
     (``shape='rect'``) or the ellipse inscribed in it covers becomes ``fill`` (``mode='solid'``; bytes in the frame's channel order) or
     the mean of its ``cell`` x ``cell`` mosaic cell, a grid anchored at the frame origin."""
     tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
-    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
-    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
-    if counts.shape[0] != B or (counts < 0).any() or int(counts.sum()) != boxes.shape[0]:
-        raise ValueError("counts must be [B] non-negative and sum to the number of box rows")
+    boxes, counts = _lib.box_rows(boxes, counts, B)
     o = _lib.redact_opts(mode, shape, cell, scale, fill)
     _lib.check(_lib.lib().cf_op_redact(device, C.byref(o), _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, ptr(boxes), ptr(counts),
                                        int(net_hw[0]), int(net_hw[1])), op=True)
@@ -265,10 +262,7 @@ def blur_faces(frames, boxes, counts, net_hw, fmt="bgr", shape="ellipse", radius
     in it covers becomes the box * box * box filtered value (width 2r+1 each, sigma about r) of the untouched frame; ``radius`` = r in
     1..24, or 0 for a per-face r of an eighth of the box's smaller side."""
     tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
-    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
-    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
-    if counts.shape[0] != B or (counts < 0).any() or int(counts.sum()) != boxes.shape[0]:
-        raise ValueError("counts must be [B] non-negative and sum to the number of box rows")
+    boxes, counts = _lib.box_rows(boxes, counts, B)
     o = _lib.blur_opts(shape, radius, scale)
     _lib.check(_lib.lib().cf_op_blur(device, C.byref(o), _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, ptr(boxes), ptr(counts),
                                      int(net_hw[0]), int(net_hw[1])), op=True)

@@ -106,6 +106,25 @@ def test_op_align_frame_bit_exact(fmt):
     assert c0.shape == (0, 16, 16, 3) and m0.shape == (0, 6)
 
 
+@pytest.mark.parametrize("fmt", ("i420", "bgr"))
+def test_op_align_frame_more_frames_than_one_launch(fmt):
+    """65 frames of 32 x 32 (one launch takes 64): two faces in frame 0, one in frame 63 (the first launch's last) and two in frame 64
+    (the second launch's only frame, at table entry 0).  The face numbering runs over all 65 counts in both launches: chips and
+    matrices equal the restatement bit for bit, so they come in frame order -- every frame holds other noise."""
+    B, h, w, S = 65, 32, 32, 16
+    rng = np.random.default_rng(80 + FORMATS.index(fmt))
+    dense = rng.integers(0, 256, (B, h, w, 3) if fmt == "bgr" else (B, h * 3 // 2, w), dtype=np.uint8)
+    counts = np.zeros(B, np.int32)
+    counts[[0, 63, 64]] = 2, 1, 2
+    lms = pose_landmarks(rng, 5, h, w, S, scale=(0.1, 0.2), margin=0.2)   # faces of 11..22 pixels, centred inside the frame
+    want_c, want_m = frame_align_ref(bgr_of(dense, fmt), lms.astype(np.float64), counts, S)
+    assert len(want_m) == 5 and want_m.any(1).all() and all(c.any() for c in want_c)
+    assert len({c.tobytes() for c in want_c}) == 5
+    gc, gm = ops.align_frame(dense, lms, counts, fmt, size=S)
+    assert bits_equal(gm, want_m), np.argwhere(gm != want_m)[:5]
+    assert bits_equal(gc, want_c), np.argwhere(gc != want_c)[:5]
+
+
 # ------------------------------------------------------------------------------------------ the engine, not tiled
 ENG_HW, SRC_HW = (96, 128), (150, 202)
 

@@ -13,7 +13,7 @@ import pytest
 import centerface_amd as cfa
 from centerface_amd import ops
 from test_redact import (FORMATS, Frames, face_box, coverage, plane_passes, pitches_for, source_frames, BOXES, COUNTS, NET, _reversed_rows,
-                         _feed_until_faces, _net_boxes)
+                         _feed_until_faces, _net_boxes, chunk_case)
 
 
 # ------------------------------------------------------------------------------------------ the restatement
@@ -236,6 +236,14 @@ def test_op_blur_small_then_large_frame():
         _op_case(fmt, 128, 256, fmt == "nv12", boxes, counts, NET)                       # the defaults: ellipse, per-face radius, 1.3
     _op_case("nv12", 128, 256, False, boxes, counts, NET, shape="rect", radius=8, scale=4.0)
     _op_case("yv12", 128, 256, False, boxes, counts, NET, shape="ellipse", radius=2, scale=0.25)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", ("nv12", "bgr"))
+def test_op_blur_more_frames_than_one_launch(fmt):
+    """test_redact's 33 frames with the per-face radius: frame 32 is the second launch's, which reads its face list (the skip rule
+    walks it) and its scratch at the launch's offsets."""
+    chunk_case(_op_case, fmt, shape="ellipse", radius=0, scale=1.0)
 
 
 # ------------------------------------------------------------------------------------------ on the GPU: the engine

@@ -352,6 +352,28 @@ def test_op_redact_small_then_large_grid():
     _op_case("bgr", 37, 51, False, BOXES, COUNTS, NET, mode="mosaic", shape="ellipse", cell=6)        # BGR frames may be odd
 
 
+# More frames than one launch takes (32): a face in frame 0 and in frame 31 (the first launch's last), two in frame 32 (the second
+# launch's only frame: its boxes, counts and mosaic cells sit at the launch's offsets), one of them overhanging the right and bottom
+# edges; frames 1..30 have none.  Frame = network = 16 x 16.
+CHUNK_COUNTS = np.array([1] + [0] * 30 + [1, 2], np.int32)
+CHUNK_BOXES = np.float32([(2, 3, 9, 11), (5, 1, 13, 8), (1, 2, 7, 9), (10, 9, 19, 18)])
+
+
+def chunk_case(case, fmt, **opt):
+    """``case`` = this module's or test_blur's _op_case on the 33 frames: every byte equals the restatement, and exactly the frames
+    0, 31 and 32 change."""
+    fr, before = case(fmt, 16, 16, False, CHUNK_BOXES, CHUNK_COUNTS, (16, 16), **opt)
+    n = len(fr.geo)
+    changed = [b for b in range(33) if not all(np.array_equal(x, y) for x, y in zip(fr.bufs[b * n:(b + 1) * n], before.bufs[b * n:(b + 1) * n]))]
+    assert changed == [0, 31, 32], changed
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", ("nv12", "bgr"))
+def test_op_redact_more_frames_than_one_launch(fmt):
+    chunk_case(_op_case, fmt, mode="mosaic", shape="ellipse", cell=4, scale=1.0)
+
+
 # ------------------------------------------------------------------------------------------ on the GPU: the engine
 def source_frames(rng, kind, shape):
     """uint8 frames: uniform noise, noise of the two extreme levels, or 4-pixel runs of one noise value along axes 1 and 2 (coarse noise

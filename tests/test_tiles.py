@@ -92,6 +92,21 @@ def test_op_cut_tiles_bit_exact(fmt):
     assert np.array_equal(want[:, 2], bgr_of(dense, fmt)[:, 20:52, 10:74])
 
 
+@pytest.mark.parametrize("fmt", ("yv12", "bgr"))
+def test_op_cut_tiles_more_frames_than_one_launch(fmt):
+    """Bf = 65 frames of 8 x 8 (one launch takes 64), two rectangles, (H, W) = (4, 8), rows with padding: frame 64 is the second launch's
+    only frame -- its planes (YV12: swapped) at table entry 0, its tiles behind those of the 64 before it."""
+    rng = np.random.default_rng(90 + FORMATS.index(fmt))
+    dense = rng.integers(0, 256, (65, 8, 8, 3) if fmt == "bgr" else (65, 12, 8), dtype=np.uint8)
+    rects = [(0, 2, 8, 4), (2, 0, 6, 8)]
+    want = tiles_ref(bgr_of(dense, fmt), rects, (4, 8))
+    views, _, _, _ = pitched_frames(dense, fmt, 0xFF)
+    got = ops.cut_tiles(views, rects, (4, 8), fmt)
+    assert got.shape == want.shape == (65, 2, 4, 8, 3)
+    bad = np.argwhere(got != want)
+    assert len(bad) == 0, (fmt, len(bad), bad[:4].tolist())
+
+
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_engine_forward_tiles_writes_the_restated_tiles(fmt):
     """cf_forward_tiles, host-staged (padded rows, and one dense block) and in place on device planes: cf_get_resized_input returns the

@@ -411,6 +411,67 @@ int cf_forward_tiles(cf_ctx* ctx, int format, const cf_yuv_planes* frames, int i
 int cf_merge_tiles(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags,
                    int out_on_device);
 
+/* ---- face tracks across video frames: cover faces through detection dropouts -----------------
+ * Every entry point above treats a frame as if it were the only one: the frame in which a face scores just under the threshold goes out
+ * uncovered.  A cf_tracker associates the rows of each frame with the tracks of the frames before, on the device, and hands the
+ * redaction the detections of the frame PLUS the tracks that were seen min_hits times running and then missed at most max_age frames:
+ *   cf_forward* -> cf_decode_threshold* [-> cf_merge_tiles] -> cf_track_update -> cf_redact_faces | cf_blur_faces | cf_align_faces_frame
+ * The defaults the Python layer uses are this project's choices; no accuracy claim is made for them.
+ *
+ * A tracker holds n_streams independent video streams on one device; stream s has max_tracks slots.  A slot holds: alive, id, hits,
+ * misses, box[4], score, lms[10] (float32); the stream holds next_id (starts at 1, never reused).  One update of stream s with the rows
+ * i < n = min(count, rows the decode / the merge wrote per image), in row order (the keep order):
+ *   1. A row with a non-finite corner is skipped: it neither matches nor is born.
+ *   2. Match.  For each remaining row in row order, over the slots that were alive when the update began and are not yet matched in this
+ *      update: the decode's float32 "+1" IoU (areas (x2-x1+1)*(y2-y1+1), inter / (area_t + area_d - inter), float32 throughout, no
+ *      FMA contraction).  The largest wins, ties go to the lowest slot, a NaN never wins.  A winner >= iou_thresh takes the row's box,
+ *      score and landmarks as they are, hits = min(hits + 1, 1 << 30), misses = 0.  Otherwise the row is new.
+ *   3. Age.  Every slot alive at the start and unmatched: hits < min_hits -> freed at once (a tentative track is never held);
+ *      otherwise misses += 1, freed when misses > max_age.
+ *   4. Birth.  New rows, in row order, take the lowest free slot (free after step 3): id = next_id++, hits = 1, misses = 0.  With no
+ *      free slot the row is DROPPED and bit 0 of flags[s] is set: THAT FACE IS NOT IN THE OUTPUT AND WILL NOT BE COVERED.  Size
+ *      max_tracks for the most faces a frame can show plus the tracks held through dropouts (80 bytes of device state per slot).
+ *   5. Output.  The alive slots in ascending slot order are rows k < counts[s] <= max_tracks: dets[k] = box, score; lms[k]; info[k] =
+ *      id, hits, misses (int32).  misses == 0: the box bit for bit.  misses > 0 (held): the box grown about its centre, in float64:
+ *      cx = ((double)x1 + (double)x2) * 0.5; hw = ((double)x2 - (double)x1) * 0.5 * (1.0 + (double)hold_grow * (double)misses);
+ *      x1' = (float)(cx - hw), x2' = (float)(cx + hw); y likewise.  THE LANDMARKS OF A HELD ROW ARE THE LAST ONES SEEN (not grown, not
+ *      moved): chips cut from them by cf_align_faces_frame show whatever is at that place now.
+ * Coordinates are whatever the rows are in: network coordinates after an ordinary forward (whatever cf_set_rescale says), frame pixels
+ * after cf_merge_tiles.  The tracker latches that space -- (not tiled, H, W), or (tiled, h, w) -- on its first update and refuses
+ * another with CF_EINVAL. */
+typedef struct cf_tracker cf_tracker;
+typedef struct cf_track_opts {
+    float   iou_thresh;   /* finite, in (0, 1] */
+    int32_t max_age;      /* 0..1000 frames a confirmed track is held */
+    int32_t min_hits;     /* 1..1000 */
+    int32_t max_tracks;   /* 1..1024 per stream */
+    float   hold_grow;    /* finite, 0..1 per missed frame */
+} cf_track_opts;
+/* ctx names the device (and carries the error text); 1..4096 streams.  CF_EINVAL for a bad option or count before any GPU work (ctx ==
+ * NULL: the arguments are still checked first, cf_op_last_error names the cause).  *out is written on success only. */
+int cf_track_create(cf_ctx* ctx, int n_streams, const cf_track_opts* opts, cf_tracker** out);
+/* Waits for the tracker's last update, then frees it.  NULL: CF_OK. */
+int cf_track_destroy(cf_tracker* trk);
+/* A scene cut: frees every track of `stream` (-1: of all streams), ordered behind the updates issued so far and before those issued
+ * later.  ids are not reused; the latched coordinate space stays.  CF_EINVAL for a stream outside -1 .. n_streams - 1. */
+int cf_track_reset(cf_tracker* trk, int stream);
+/* One update with the rows of the LAST THRESHOLD DECODE of the last forward of ctx (network coordinates); after cf_forward_tiles, with
+ * the merged rows of the last cf_merge_tiles (frame pixels).  Image (frame) b is the next frame of stream stream0 + b; stream0 + B <=
+ * n_streams.  dets [B][max_tracks][5], lms [B][max_tracks][10], info [B][max_tracks][3], counts [B], flags [B]; any may be NULL.
+ * out_on_device as for cf_merge_tiles: device buffers are asynchronous on the stream that carried the decode or the merge, host buffers
+ * block (rows at and past the largest count of the batch are not written).
+ * CF_ESTATE without a decode (or, tiled, without a merge), once another upload or forward was started on ctx, and on a second update
+ * behind the same decode / merge (time would advance twice).  CF_EINVAL, before any GPU work, for a stream range outside the tracker, a
+ * tracker of another device, or a changed coordinate space.
+ * The output rows live in buffers owned by the CONTEXT, the state in the tracker: a ring of contexts can share one tracker.  The
+ * tracker keeps one event; every update first makes its stream wait for the previous update's event, then records a new one, so the
+ * updates of one tracker are ordered across contexts in call order.
+ * After a successful update, and until the next forward, upload, threshold decode or merge on ctx, cf_redact_faces, cf_blur_faces and
+ * cf_align_faces_frame take the TRACKED rows (held ones included) instead of the decode's or the merge's; their B and (h, w) rules
+ * are those of the rows the update consumed.  Without an update they do exactly what they did before. */
+int cf_track_update(cf_ctx* ctx, cf_tracker* trk, int stream0, float* dets, float* lms, int32_t* info,
+                    int32_t* counts, int32_t* flags, int out_on_device);
+
 /* ---- fused convenience: forward + D3 decode in one enqueue (eval_widerface.py:76-90 shape) -- */
 int cf_detect_topk(cf_ctx* ctx, const void* in, int in_format, int in_on_device, int B, int K,
                    float* dets, float* lms, int64_t* inds, int out_on_device);
@@ -690,6 +751,15 @@ int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, in
 int cf_op_merge_tiles(int device, const cf_merge_opts* opts, const cf_tile_rect* rects, int T, int Bf, int h, int w, int H, int W,
                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
                       float* dets, float* lms, int32_t* out_counts, int32_t* flags);
+/* The update kernel of cf_track_update over a whole sequence, on host tables, with a fresh tracker of n_streams streams: frame f of
+ * stream s has the rows i < min(counts_in[f][s], rows) of boxes [F][S][rows][4], scores [F][S][rows], lms_in [F][S][rows][10] ->
+ * dets [F][S][max_tracks][5], lms [F][S][max_tracks][10], info [F][S][max_tracks][3], counts [F][S], flags [F][S] after each frame.
+ * dets, lms and info are copied up first, so rows the kernel does not write come back as the caller filled them.  No pointer may be
+ * NULL; n_frames, rows >= 1, n_frames * n_streams * max(rows, max_tracks) <= 2^24; counts_in >= 0.  The same option checks as
+ * cf_track_create, before any device is touched. */
+int cf_op_track(int device, const cf_track_opts* opts, int n_streams, int n_frames, int rows, const float* boxes,
+                const float* scores, const float* lms_in, const int32_t* counts_in,
+                float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags);
 /* CenterFace.nms alone (centerface.py:111-151): keep[] receives kept indices in keep order. */
 int cf_op_nms(int device, const float* boxes, const float* scores, int n, float nms_thresh,
               int32_t* keep, int32_t* n_keep);

@@ -45,6 +45,7 @@ EXPORTS = (
     "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces", "cf_align_faces_frame", "cf_op_align_frame", "cf_redact_faces", "cf_op_redact",
     "cf_blur_faces", "cf_op_blur",
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
+    "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
 )
 
 
@@ -167,6 +168,17 @@ def merge_opts(metric="ios", thresh=0.5, edge=2.0):
             raise ValueError("unknown merge metric %r (one of %s)" % (metric, sorted(MERGE_METRICS)))
         metric = MERGE_METRICS[metric.lower()]
     return MergeOpts(int(metric), float(thresh), float(edge))
+
+
+class TrackOpts(C.Structure):
+    """cf_track_opts: match threshold / frames a confirmed track is held / detections that confirm a track / slots per stream / growth of
+    a held box per missed frame."""
+    _fields_ = [("iou_thresh", C.c_float), ("max_age", C.c_int32), ("min_hits", C.c_int32), ("max_tracks", C.c_int32), ("hold_grow", C.c_float)]
+
+
+def track_opts(iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0):
+    """TrackOpts (the library validates the numbers).  The defaults are this project's choices; no accuracy claim is made for them."""
+    return TrackOpts(float(iou), int(max_age), int(min_hits), int(max_tracks), float(hold_grow))
 
 
 def tile_rects(rects):
@@ -384,6 +396,11 @@ def lib():
         L.cf_merge_tiles.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.cf_op_cut_tiles.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(TileRect)] + [C.c_int] * 3 + [C.c_void_p]
         L.cf_op_merge_tiles.argtypes = [C.c_int, C.POINTER(MergeOpts), C.POINTER(TileRect)] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
+        L.cf_track_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(TrackOpts), C.POINTER(C.c_void_p)]
+        L.cf_track_destroy.argtypes = [C.c_void_p]
+        L.cf_track_reset.argtypes = [C.c_void_p, C.c_int]
+        L.cf_track_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
+        L.cf_op_track.argtypes = [C.c_int, C.POINTER(TrackOpts)] + [C.c_int] * 3 + [C.c_void_p] * 9
         L.cf_get_resized_input.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.cf_get_heads.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.cf_decode_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

@@ -79,6 +79,16 @@ class Engine(object):
     def _chk(self, code):
         _lib.check(code, self._h)
 
+    @property
+    def last_B(self):
+        """The batch of the last forward (tile images after ``forward_tiles_enqueue``)."""
+        return self._last_B
+
+    @last_B.setter
+    def last_B(self, B):
+        self._last_B = B
+        self._tiled_last = False              # (forward_tiles_enqueue sets it again behind this)
+
     def load_state_dict(self, sd):
         """Strict load (centerface.py:24)."""
         sd = _weights.validate_state_dict(sd)
@@ -463,6 +473,7 @@ class Engine(object):
         self._chk(self._L.cf_forward_tiles(self._h, f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, rt, T))
         self.last_B = B * T
         self._tiles = (B, T)
+        self._tiled_last = True
 
     def merge_tiles(self, metric="ios", thresh=0.5, edge=2.0, max_out=1024):
         """Per-frame detections of the last tiled forward (``cf_merge_tiles``, host form): the rows the preceding ``decode_threshold``
@@ -493,6 +504,34 @@ class Engine(object):
         o = _lib.merge_opts(metric, thresh, edge)
         vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
         self._chk(self._L.cf_merge_tiles(self._h, C.byref(o), int(max_out), vp(dets_ptr), vp(lms_ptr), vp(counts_ptr), vp(flags_ptr), 1))
+
+    # -- face tracks across video frames -----------------------------------------------------------
+    def track_update(self, tracker, stream0=0):
+        """Advance ``tracker`` by one frame with the rows the preceding ``decode_threshold`` kept -- after ``forward_tiles_enqueue``, the
+        rows of the preceding ``merge_tiles`` -- (``cf_track_update``, host form): image b is the next frame of stream ``stream0 + b``.
+        Returns (results, flags): per image (dets [n,5], lms [n,10], ids [n], hits [n], misses [n]) -- every detection of the frame plus
+        the tracks held through a dropout (``misses`` > 0: box grown by ``hold_grow`` per missed frame, last-seen landmarks), in slot
+        order -- and int32 [B], bit 0 set where a new face found no free slot and was dropped.  Until the next forward, decode or
+        merge, ``redact_faces`` / ``blur_faces`` / ``align_faces_frame`` of this engine use these rows."""
+        B = self._tiles[0] if self._tiled_last else self.last_B
+        M = tracker.max_tracks
+        dets = np.empty((B, M, 5), np.float32)
+        lms = np.empty((B, M, 10), np.float32)
+        info = np.empty((B, M, 3), np.int32)
+        counts = np.zeros((B,), np.int32)
+        flags = np.zeros((B,), np.int32)
+        self._chk(self._L.cf_track_update(self._h, tracker._handle(self), int(stream0), _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(info),
+                                          _lib.ptr(counts), _lib.ptr(flags), 0))
+        return [(dets[b, :counts[b]].copy(), lms[b, :counts[b]].copy(), info[b, :counts[b], 0].copy(), info[b, :counts[b], 1].copy(),
+                 info[b, :counts[b], 2].copy()) for b in range(B)], flags
+
+    def track_update_device(self, tracker, stream0=0, dets_ptr=None, lms_ptr=None, info_ptr=None, counts_ptr=None, flags_ptr=None):
+        """Same, writing into caller-owned DEVICE buffers (dets [B,max_tracks,5], lms [B,max_tracks,10] float32, info [B,max_tracks,3],
+        counts / flags [B] int32; any may be None): asynchronous on the engine's main stream behind the decode or the merge, nothing is
+        read on the host.  The context keeps the tracked rows either way."""
+        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
+        self._chk(self._L.cf_track_update(self._h, tracker._handle(self), int(stream0), vp(dets_ptr), vp(lms_ptr), vp(info_ptr), vp(counts_ptr),
+                                          vp(flags_ptr), 1))
 
     # -- launch plan / layer trace (parity tests) ---------------------------------------------
     def plan(self):
@@ -616,6 +655,61 @@ class Engine(object):
         if not arr.flags["C_CONTIGUOUS"]:
             raise ValueError("memcpy_d2h needs a C-contiguous destination")
         self._chk(self._L.cf_memcpy_d2h(self._h, _lib.ptr(arr), C.c_void_p(int(dptr)), arr.nbytes))
+
+
+class Tracker(object):
+    """One cf_tracker: ``streams`` independent video streams on one GPU, ``max_tracks`` slots each (``include/centerface_hip.h`` states
+    the update).  ``engine_or_device``: an ``Engine`` (the tracker is created at once on its GPU) or a device index (created by the first
+    ``Engine.track_update`` that uses it, which must be on that GPU).  A face that matches a track (IoU >= ``iou``) keeps its id; a track
+    seen ``min_hits`` times running is held for up to ``max_age`` frames without a detection, its box growing by ``hold_grow`` of its
+    size per missed frame.  A frame with more faces and held tracks than ``max_tracks`` DROPS the surplus new faces (flag bit 0): they are
+    not covered.  The defaults are this project's choices; no accuracy claim is made for them.  Engines of one GPU may share a tracker:
+    its updates are ordered in call order."""
+
+    def __init__(self, engine_or_device, streams, iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0):
+        self._L = _lib.lib()
+        self._o = _lib.track_opts(iou, max_age, min_hits, max_tracks, hold_grow)
+        self.streams, self.max_tracks = int(streams), int(max_tracks)
+        self._h = None
+        if isinstance(engine_or_device, Engine):
+            self.device = engine_or_device.device
+            self._handle(engine_or_device)
+        else:
+            self.device = int(engine_or_device)
+            # refuse bad options now, not at the first update (no context: the library checks the arguments and tells)
+            out = C.c_void_p()
+            self._L.cf_track_create(None, self.streams, C.byref(self._o), C.byref(out))
+            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
+            if "null context" not in why:
+                raise _lib.CenterFaceValueError(-1, why)
+
+    def _handle(self, engine):
+        """The cf_tracker, created with ``engine``'s context on first use."""
+        if self._h is None:
+            if engine.device != self.device:
+                raise ValueError("the tracker was made for device %d, the engine runs on device %d" % (self.device, engine.device))
+            out = C.c_void_p()
+            _lib.check(self._L.cf_track_create(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
+            self._h = out
+        return self._h
+
+    def reset(self, stream=-1):
+        """A scene cut: drop every track of ``stream`` (-1: of all streams).  ids are not reused."""
+        if not -1 <= int(stream) < self.streams:
+            raise ValueError("stream %d of a tracker with %d" % (stream, self.streams))
+        if self._h is not None:
+            _lib.check(self._L.cf_track_reset(self._h, int(stream)), op=True)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.cf_track_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class EngineRing(object):
@@ -916,7 +1010,8 @@ class CenterFace(object):
             raise ValueError("%d tiles per frame need max_batch >= %d (this instance has %d)" % (len(rects), len(rects), self.engine.max_batch))
         return rects, per
 
-    def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None):
+    def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None,
+                     tracker=None):
         """Sliced inference for frames much larger than the network input, whose small faces the stretch-resize of ``detect_batch``
         loses: every frame is cut on the device into overlapping tiles of ``tile`` (default: the network's (H, W)) that share at
         least ``overlap`` pixels (default: a quarter of the tile, rounded down to even), plus the whole frame as one more tile; the
@@ -925,7 +1020,10 @@ class CenterFace(object):
         per-frame plane tuples -- of any even size; ``max_batch`` must hold the tiles of one frame.  Returns (dets [n,5], lms [n,10]) per
         frame (``dets`` alone without landmarks), in FRAME pixels, not floor-divided.  The defaults are this project's choices; no
         accuracy claim is made for them.  ``redact``: options of ``Engine.redact_faces``, or ``mode='blur'`` with those of
-        ``Engine.blur_faces``; the frames are then redacted IN PLACE with the merged boxes."""
+        ``Engine.blur_faces``; the frames are then redacted IN PLACE with the merged boxes.  ``tracker``: a ``Tracker`` whose
+        stream k the k-th frame of this call continues (frame pixels): it is advanced behind the merge, and the redaction then covers
+        the tracked rows -- the merged detections plus the tracks held through a dropout; the detections returned stay the frame's
+        own."""
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         tab, B, h, w, _, _, keep = _lib.frame_planes(frames, fmt, writable=redact is not None)
@@ -937,38 +1035,45 @@ class CenterFace(object):
             self.engine.forward_tiles_enqueue(chunk, rects, fmt)
             self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets)
             res, _ = self.engine.merge_tiles(metric, thresh, edge, self.max_dets)
+            if tracker is not None:
+                self.engine.track_update_device(tracker, i)
             if redact is not None:
                 self.engine.cover_faces(chunk, fmt, **redact)
             out.extend((d, l) if self.landmarks else d for d, l in res)
         return out
 
-    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, **options):
+    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
         cell, scale, fill) or, with ``mode='blur'``, blurred (``Engine.blur_faces``; shape, radius, scale), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
         without detections comes back byte for byte.  ``tiled=True``: detection by ``detect_tiled`` (``tile``, ``overlap``) on frames of
-        any even size, redaction with the merged boxes; the detections are then in frame pixels."""
+        any even size, redaction with the merged boxes; the detections are then in frame pixels.  ``tracker``: a ``Tracker`` (default none: every
+        call stands alone) whose stream k the k-th image of this call continues -- a video is fed one call per frame, n cameras n images per
+        call; it is advanced between the decode (the merge) and the redaction, which then covers the detections of this frame AND the
+        tracks held through a dropout.  The detections returned stay the frame's own."""
         _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         if tiled:
-            return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options)
+            return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker)
         k = [0]
 
         def redact(results):
+            if tracker is not None:
+                self.engine.track_update_device(tracker, k[0])
             self.engine.cover_faces(out[k[0]:k[0] + len(results)], "bgr", **options)
             k[0] += len(results)
             return results
         return out, self._detect_chunks(imgs, redact)
 
-    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, **options):
+    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
-        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``: as
+        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True`` and ``tracker``: as
         ``anonymize``."""
         _lib.split_redact_options(options)
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            return out, self.detect_tiled(out, tile, overlap, fmt, redact=options)
+            return out, self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker)
         frames = self._yuv_frames(frames)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
         dets = []
@@ -978,6 +1083,8 @@ class CenterFace(object):
                 chunk = out[i:i + self.engine.max_batch]
                 self.engine.forward_yuv_enqueue(frames[i:i + self.engine.max_batch], fmt)
                 dets.extend(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True))
+                if tracker is not None:
+                    self.engine.track_update_device(tracker, i)
                 self.engine.cover_faces(chunk, fmt, **options)
         finally:
             self.engine.set_rescale(0.0, 0.0)

@@ -445,6 +445,30 @@ size_t merge_mask_bytes(int Bf, int T, int rows);
 constexpr size_t kMergeMaskLimit = (size_t)256 << 20;      // refused with CF_ENOMEM above this, before any launch
 hipError_t launch_merge_tiles(hipStream_t s, const MergeParams& p);
 
+// Face tracks across video frames (cf_track.hip; the statement is that file's header).  One update of the streams stream0 .. stream0 + B - 1
+// with the rows i < min(counts[b], rows) of image b: boxes [B][rows][4], scores[(b * rows + i) * score_stride], lms [B][rows][10].
+// All pointers are device-visible; boxes rows are 16-byte aligned.
+constexpr int kTrackMaxSlots = 1024, kTrackMaxStreams = 4096;
+struct TrackParams {
+    const float* boxes; const float* scores; int score_stride; const float* lms; const int* counts; int rows, B;
+    float iou_thresh; int max_age, min_hits, max_tracks; float hold_grow;
+    // state (device), owned by the tracker: n_streams x max_tracks slots
+    int stream0;
+    int* meta;            // [S][max_tracks][4]: alive, id, hits, misses
+    float* rec;           // [S][max_tracks][16]: box, score, lms[10], 0
+    int* next_id;         // [S]
+    // outputs (device): the alive slots of every stream, compacted in slot order
+    float* dets;          // [B][max_tracks][5]
+    float* lms_out;       // [B][max_tracks][10]
+    int* info;            // [B][max_tracks][3]: id, hits, misses
+    float* corners;       // [B][max_tracks][4]: the box rows FaceList::boxes takes, as MergeParams::corners
+    int* out_counts;      // [B], <= max_tracks
+    int* flags;           // [B]: bit 0 = a new row found no free slot and was dropped
+};
+// nullptr, or what is wrong with the options / the number of streams (host only)
+const char* track_check(const cf_track_opts* o, int n_streams);
+hipError_t launch_track_update(hipStream_t s, const TrackParams& p);
+
 // layout converters used by cf_get_heads and the per-op test entry points
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*T NHWC*/,
                                int B, int C, int H, int W);

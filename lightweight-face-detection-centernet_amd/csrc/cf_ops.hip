@@ -918,4 +918,45 @@ int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* re
     return sc.result("cf_op_merge_tiles");
 }
 
+// The update of cf_track_update, frame after frame on one stream, with the state of a fresh tracker (no slot alive, next_id = 1).
+int cf_op_track(int device, const cf_track_opts* o, int n_streams, int n_frames, int rows, const float* boxes, const float* scores,
+                const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags) {
+    const char* bad = track_check(o, n_streams);
+    if (!bad && (!boxes || !scores || !lms_in || !counts_in || !dets || !lms || !info || !counts || !flags)) bad = "null argument";
+    if (!bad && (n_frames < 1 || rows < 1)) bad = "n_frames and rows must be at least 1";
+    if (!bad && (long long)n_frames * n_streams * std::max(rows, o->max_tracks) > (1 << 24)) bad = "more than 2^24 rows";
+    if (!bad) for (long long k = 0; k < (long long)n_frames * n_streams; ++k) if (counts_in[k] < 0) { bad = "negative count"; break; }
+    if (bad) { g_op_error = std::string("cf_op_track: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    const size_t S = n_streams, F = n_frames, M = o->max_tracks, nin = F * S * rows, nout = F * S * M;
+    TrackParams p{};
+    p.boxes = (const float*)sc.up(boxes, nin * 4 * sizeof(float));
+    p.scores = (const float*)sc.up(scores, nin * sizeof(float)); p.score_stride = 1;
+    p.lms = (const float*)sc.up(lms_in, nin * 10 * sizeof(float));
+    p.counts = (const int*)sc.up(counts_in, F * S * sizeof(int));
+    p.rows = rows; p.B = n_streams; p.stream0 = 0;
+    p.iou_thresh = o->iou_thresh; p.max_age = o->max_age; p.min_hits = o->min_hits; p.max_tracks = o->max_tracks; p.hold_grow = o->hold_grow;
+    p.meta = (int*)sc.alloc(S * M * 4 * sizeof(int)); p.rec = (float*)sc.alloc(S * M * 16 * sizeof(float));
+    const std::vector<int> ones(S, 1);
+    p.next_id = (int*)sc.upv(ones);
+    p.dets = (float*)sc.up(dets, nout * 5 * sizeof(float)); p.lms_out = (float*)sc.up(lms, nout * 10 * sizeof(float));
+    p.info = (int*)sc.up(info, nout * 3 * sizeof(int));
+    p.corners = (float*)sc.alloc(S * M * 4 * sizeof(float));
+    p.out_counts = (int*)sc.alloc(F * S * sizeof(int)); p.flags = (int*)sc.alloc(F * S * sizeof(int));
+    const TrackParams first = p;
+    for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
+        p.boxes = first.boxes + f * S * rows * 4; p.scores = first.scores + f * S * rows; p.lms = first.lms + f * S * rows * 10;
+        p.counts = first.counts + f * S;
+        p.dets = first.dets + f * S * M * 5; p.lms_out = first.lms_out + f * S * M * 10; p.info = first.info + f * S * M * 3;
+        p.out_counts = first.out_counts + f * S; p.flags = first.flags + f * S;
+        sc.chk(launch_track_update(sc.s, p));
+    }
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, first.dets, nout * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, first.lms_out, nout * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(info, first.info, nout * 3 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(counts, first.out_counts, F * S * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(flags, first.flags, F * S * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_track");
+}
+
 }  // extern "C"

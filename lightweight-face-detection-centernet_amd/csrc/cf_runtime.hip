@@ -133,6 +133,9 @@ struct cf_ctx {
     std::vector<cf_tile_rect> tl_rects; cf_tile_rect* tl_rects_dev = nullptr; size_t tl_rects_bytes = 0; int tl_rects_up = 0;
     int tl_T = 0, tl_Bf = 0, tl_h = 0, tl_w = 0, tl_maxout = 0; bool tl_merged = false;
     void* tl_buf[9] = {}; size_t tl_have[9] = {};
+    // cf_track_update: the tracked rows of the last update (tk_buf, grown on demand: dets, lms, info, corners, counts, flags; tk_M rows
+    // per image).  tk_on: they stand in for the decode's / the merge's rows in face_rows; tk_done: an update consumed those rows
+    void* tk_buf[6] = {}; size_t tk_have[6] = {}; int tk_M = 0; bool tk_on = false, tk_done = false;
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
     // input format, batch): the second forward with a key captures it, later ones replay it
     struct FwdGraph { const void* in; int fmt, B; hipGraphExec_t exec; bool broken; unsigned long long used; };
@@ -632,6 +635,7 @@ int cf_destroy(cf_ctx* c) {
                     (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off, (void*)c->t_detsnet, (void*)c->rd_cells, (void*)c->rd_stage, (void*)c->bl_scratch, (void*)c->tl_rects_dev})
         if (p) hipFree(p);
     for (void* p : c->tl_buf) if (p) hipFree(p);
+    for (void* p : c->tk_buf) if (p) hipFree(p);
     if (c->h_thr) hipHostFree(c->h_thr);
     if (c->ev_thr) hipEventDestroy(c->ev_thr);
     for (auto& ev : c->events) if (ev) hipEventDestroy(ev);
@@ -1108,6 +1112,7 @@ int launch_all_ops(cf_ctx* c, const void* net_in, int in_format, int B) {
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in_slot_used; c->al_rows = 0;      // what cf_align_faces samples
     c->tl_T = 0; c->tl_merged = false;                    // (cf_forward_tiles sets its state again behind this call)
+    c->tk_on = false; c->tk_done = false;
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -1578,7 +1583,7 @@ static int thresh_launch(cf_ctx* c, int mode, float score_thresh, float nms_thre
     HIPCHK(c, hipMemsetAsync(c->t_overflow, 0, sizeof(int), c->stream));
     HIPCHK(c, launch_decode_threshold(c->stream, p));
     HIPCHK(c, hipEventRecord(c->ev_thr, c->stream));
-    c->al_rows = max_out; c->tl_merged = false;
+    c->al_rows = max_out; c->tl_merged = false; c->tk_on = false; c->tk_done = false;
     return CF_OK;
 }
 
@@ -1726,7 +1731,7 @@ static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char
 }
 
 // What cf_redact_faces, cf_blur_faces and cf_align_faces_frame share: the state rules and the face rows (the last threshold decode's, in
-// network coordinates, or the merged rows of a tiled forward, in frame pixels), and the frames -- the caller's device planes as they are,
+// network coordinates, or the merged rows of a tiled forward, in frame pixels, or -- behind a cf_track_update -- the tracked rows), and the frames -- the caller's device planes as they are,
 // or host frames staged in rd_stage around the launches.  want_lms: the caller reads the landmark rows, not the boxes.
 struct FaceRows { FaceList f; const float* lms; bool tiled; };
 static int face_rows(cf_ctx* c, const char* who, int B, int h, int w, bool want_lms, FaceRows& r) {
@@ -1744,6 +1749,11 @@ static int face_rows(cf_ctx* c, const char* who, int B, int h, int w, bool want_
         if (B != c->last_B) return c->fail(CF_EINVAL, "%s: B=%d, the last forward had %d images", who, B, c->last_B);
         r.f = FaceList{c->t_detsnet, c->al_rows, c->t_counts, c->al_rows, c->al_rows, c->H, c->W};
         r.lms = c->t_lmsnet;
+    }
+    if (c->tk_on) {                                      // cf_track_update stood behind those rows: the tracked rows, in the same coordinates
+        r.f.boxes = (const float*)c->tk_buf[3]; r.f.counts = (const int*)c->tk_buf[4];
+        r.f.box_stride = r.f.rows_cap = r.f.faces_cap = c->tk_M;
+        r.lms = (const float*)c->tk_buf[1];
     }
     return CF_OK;
 }
@@ -1947,7 +1957,7 @@ int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
         return c->fail(CF_ENOMEM, "cf_merge_tiles: %d frames x %d tiles x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
                        Bf, T, rows, merge_mask_bytes(Bf, T, rows) / 1e6);
     HIPCHK(c, hipSetDevice(c->device));
-    c->tl_merged = false;
+    c->tl_merged = false; c->tk_on = false; c->tk_done = false;
     const size_t cap = (size_t)T * rows, mo = (size_t)Bf * max_out;
     const size_t need[9] = {Bf * cap * 16 * sizeof(float), Bf * sizeof(int), Bf * cap * sizeof(int), merge_mask_bytes(Bf, T, rows),
                             mo * 5 * sizeof(float), mo * 10 * sizeof(float), mo * 4 * sizeof(float), Bf * sizeof(int), Bf * sizeof(int)};
@@ -1987,6 +1997,136 @@ int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
     }
     if (counts) memcpy(counts, hc.data(), need[7]);
     if (flags) memcpy(flags, hc.data() + Bf, need[8]);
+    return CF_OK;
+}
+
+// ---- face tracks across frames (cf_track.hip).  The tracker owns the state of its streams, one event that orders its updates across
+// the contexts that issue them, and a stream of its own for what no context carries (the initial state, cf_track_reset).
+}  // extern "C"
+struct cf_tracker {
+    int device = 0, S = 0;
+    cf_track_opts o{};
+    int* meta = nullptr; float* rec = nullptr; int* next_id = nullptr;
+    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
+    bool latched = false, sp_tiled = false; int sp_h = 0, sp_w = 0;      // the coordinate space of the first update
+};
+extern "C" {
+
+int cf_track_destroy(cf_tracker* t) {
+    if (!t) return CF_OK;
+    hipSetDevice(t->device);
+    if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
+    if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
+    for (void* p : {(void*)t->meta, (void*)t->rec, (void*)t->next_id}) if (p) hipFree(p);
+    delete t;
+    return CF_OK;
+}
+
+int cf_track_create(cf_ctx* c, int n_streams, const cf_track_opts* o, cf_tracker** out) {
+    const char* why = track_check(o, n_streams);
+    if (!why && !out) why = "null out";
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_track_create: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_track_create: %s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    cf_tracker* t = new cf_tracker();
+    t->device = c->device; t->S = n_streams; t->o = *o;
+    const size_t slots = (size_t)n_streams * o->max_tracks;
+    hipError_t e = hipStreamCreateWithFlags(&t->ts, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->meta, slots * 4 * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&t->rec, slots * 16 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&t->next_id, (size_t)n_streams * sizeof(int));
+    if (e == hipSuccess) e = hipMemsetAsync(t->meta, 0, slots * 4 * sizeof(int), t->ts);
+    if (e == hipSuccess) e = hipMemsetAsync(t->rec, 0, slots * 16 * sizeof(float), t->ts);
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)t->next_id, 1, (size_t)n_streams, t->ts);
+    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        cf_track_destroy(t);
+        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_track_create: %d streams x %d tracks: %s", n_streams, o->max_tracks, hipGetErrorString(e));
+    }
+    *out = t;
+    return CF_OK;
+}
+
+int cf_track_reset(cf_tracker* t, int stream) {
+    if (!t || stream < -1 || stream >= t->S) { op_error_set("cf_track_reset: null tracker, or a stream outside -1 .. n_streams - 1"); return CF_EINVAL; }
+    const size_t M = t->o.max_tracks, first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)t->S : 1;
+    hipError_t e = hipSetDevice(t->device);
+    if (e == hipSuccess) e = hipStreamWaitEvent(t->ts, t->ev, 0);
+    if (e == hipSuccess) e = hipMemsetAsync(t->meta + first * M * 4, 0, n * M * 4 * sizeof(int), t->ts);
+    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
+    if (e != hipSuccess) { op_error_set((std::string("cf_track_reset: ") + hipGetErrorString(e)).c_str()); return CF_EHIP; }
+    return CF_OK;
+}
+
+int cf_track_update(cf_ctx* c, cf_tracker* t, int stream0, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags,
+                    int out_on_device) {
+    if (!c) return CF_EINVAL;
+    if (!t) return c->fail(CF_EINVAL, "cf_track_update: null tracker");
+    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_track_update: the tracker lives on device %d, the context on device %d", t->device, c->device);
+    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_track_update before cf_forward");
+    if (!c->al_in) return c->fail(CF_ESTATE, "cf_track_update: an upload was started after the last forward");
+    if (c->al_rows < 1 || !c->t_detsnet || !c->t_lmsnet || !c->t_counts || !c->t_dets) return c->fail(CF_ESTATE, "cf_track_update without a threshold decode of the last forward");
+    const bool tiled = c->tl_T > 0;
+    if (tiled && !c->tl_merged) return c->fail(CF_ESTATE, "cf_track_update after cf_forward_tiles without a cf_merge_tiles of the last decode");
+    if (c->tk_done) return c->fail(CF_ESTATE, "cf_track_update: these rows went through an update already (time would advance twice)");
+    const int B = tiled ? c->tl_Bf : c->last_B, M = t->o.max_tracks;
+    const int sh = tiled ? c->tl_h : c->H, sw = tiled ? c->tl_w : c->W;
+    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_track_update: streams %d .. %d of a tracker with %d", stream0, stream0 + B - 1, t->S);
+    if (t->latched && (t->sp_tiled != tiled || t->sp_h != sh || t->sp_w != sw))
+        return c->fail(CF_EINVAL, "cf_track_update: the tracker's rows are in %s %d x %d coordinates, these in %s %d x %d", t->sp_tiled ? "frame" : "network", t->sp_w, t->sp_h,
+                       tiled ? "frame" : "network", sw, sh);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bm = (size_t)B * M;
+    const size_t need[6] = {bm * 5 * sizeof(float), bm * 10 * sizeof(float), bm * 3 * sizeof(int), bm * 4 * sizeof(float), B * sizeof(int), B * sizeof(int)};
+    static const char* const what[6] = {"tracked dets", "tracked landmarks", "track info", "tracked corners", "tracked counts", "track flags"};
+    for (int k = 0; k < 6; ++k) { int r = grow(c, &c->tk_buf[k], &c->tk_have[k], need[k], what[k], "cf_track_update"); if (r) return r; }
+    TrackParams p{};
+    if (tiled) {
+        p.boxes = (const float*)c->tl_buf[6]; p.scores = (const float*)c->tl_buf[4] + 4; p.lms = (const float*)c->tl_buf[5];
+        p.counts = (const int*)c->tl_buf[7]; p.rows = c->tl_maxout;
+    } else {
+        p.boxes = c->t_detsnet; p.scores = c->t_dets + 4; p.lms = c->t_lmsnet; p.counts = c->t_counts; p.rows = c->al_rows;
+    }
+    p.score_stride = 5; p.B = B; p.stream0 = stream0;
+    p.iou_thresh = t->o.iou_thresh; p.max_age = t->o.max_age; p.min_hits = t->o.min_hits; p.max_tracks = M; p.hold_grow = t->o.hold_grow;
+    p.meta = t->meta; p.rec = t->rec; p.next_id = t->next_id;
+    p.dets = (float*)c->tk_buf[0]; p.lms_out = (float*)c->tk_buf[1]; p.info = (int*)c->tk_buf[2]; p.corners = (float*)c->tk_buf[3];
+    p.out_counts = (int*)c->tk_buf[4]; p.flags = (int*)c->tk_buf[5];
+    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the update before this one, on whichever context's stream
+    HIPCHK(c, launch_track_update(c->stream, p));
+    HIPCHK(c, hipEventRecord(t->ev, c->stream));
+    t->latched = true; t->sp_tiled = tiled; t->sp_h = sh; t->sp_w = sw;
+    c->tk_on = true; c->tk_done = true; c->tk_M = M;
+    if (out_on_device) {
+        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, need[0], hipMemcpyDeviceToDevice, c->stream));
+        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, need[1], hipMemcpyDeviceToDevice, c->stream));
+        if (info) HIPCHK(c, hipMemcpyAsync(info, p.info, need[2], hipMemcpyDeviceToDevice, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, need[4], hipMemcpyDeviceToDevice, c->stream));
+        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, need[5], hipMemcpyDeviceToDevice, c->stream));
+        return CF_OK;
+    }
+    std::vector<int> hc((size_t)2 * B);
+    {   // hc lives on this stack frame: never return while a copy into it may still be in flight
+        const hipError_t e1 = hipMemcpyAsync(hc.data(), p.out_counts, need[4], hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipMemcpyAsync(hc.data() + B, p.flags, need[5], hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e3 = hipStreamSynchronize(c->stream);
+        HIPCHK(c, e1); HIPCHK(c, e2); HIPCHK(c, e3);
+    }
+    int nrows = 0;
+    for (int b = 0; b < B; ++b) nrows = std::max(nrows, std::min(hc[b], M));
+    if (nrows > 0 && (dets || lms || info)) {            // only the rows that exist, as cf_merge_tiles
+        if (dets) HIPCHK(c, hipMemcpy2DAsync(dets, (size_t)M * 5 * sizeof(float), p.dets, (size_t)M * 5 * sizeof(float), (size_t)nrows * 5 * sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
+        if (lms) HIPCHK(c, hipMemcpy2DAsync(lms, (size_t)M * 10 * sizeof(float), p.lms_out, (size_t)M * 10 * sizeof(float), (size_t)nrows * 10 * sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
+        if (info) HIPCHK(c, hipMemcpy2DAsync(info, (size_t)M * 3 * sizeof(int), p.info, (size_t)M * 3 * sizeof(int), (size_t)nrows * 3 * sizeof(int), B, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (counts) memcpy(counts, hc.data(), need[4]);
+    if (flags) memcpy(flags, hc.data() + B, need[5]);
     return CF_OK;
 }
 

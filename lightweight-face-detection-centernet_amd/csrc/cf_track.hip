@@ -1,0 +1,189 @@
+// Face tracks across the frames of a video stream (cf_track_update / cf_op_track): the association of the current frame's detection rows
+// with the tracks of the frames before, and the rows -- detections and held tracks -- that the redaction of this frame covers.
+//
+// THE STATEMENT (tests/track_cases.py restates it in numpy; the two agree bit for bit)
+// A tracker holds n_streams independent streams; stream s has max_tracks slots.  A slot holds: alive, id, hits, misses, box[4] f32,
+// score f32, lms[10] f32.  The stream holds next_id (starts at 1, never reused).  One update of stream s with the rows
+// i < n = min(count, rows written per image), in row order (the decode's / the merge's keep order):
+//   1. A row with a non-finite corner is skipped: it neither matches nor is born.
+//   2. Match.  For each remaining row in row order, over the slots that were alive WHEN THE UPDATE BEGAN and are not yet matched in this
+//      update, the measure is the decode's float32 "+1" IoU of the slot's box t and the row's box d:
+//        at = (t.x2 - t.x1 + 1) * (t.y2 - t.y1 + 1), ad likewise; w = max(0, min(t.x2, d.x2) - max(t.x1, d.x1) + 1), h likewise;
+//        inter = w * h; iou = inter / (at + ad - inter)            (float32 throughout, every operation rounded, no FMA contraction)
+//      The largest measure wins, ties go to the lowest slot; a slot whose measure is NaN (or -inf) never wins.  A winner with
+//      iou >= iou_thresh takes the row's box, score and landmarks as they are, hits = min(hits + 1, 1 << 30), misses = 0.  Otherwise
+//      (or without a winner) the row is NEW.
+//   3. Age.  Every slot that was alive at the start and is unmatched: hits < min_hits -> freed at once (a tentative track is never
+//      held); otherwise misses += 1, and it is freed when misses > max_age.
+//   4. Birth.  New rows, in row order, take the lowest free slot (free after step 3) with id = next_id++, hits = 1, misses = 0.  With no
+//      free slot the row is DROPPED -- that face is not covered -- and bit 0 of flags[s] is set.
+//   5. Output.  The alive slots in ascending slot order become rows k < counts[s] <= max_tracks: dets[k] = box, score; lms[k];
+//      info[k] = id, hits, misses.  misses == 0: the box bit for bit.  misses > 0 (a held track): the box grown about its centre in
+//      float64, cx = ((double)x1 + (double)x2) * 0.5, hw = ((double)x2 - (double)x1) * 0.5 * (1.0 + (double)hold_grow * (double)misses),
+//      x1' = (float)(cx - hw), x2' = (float)(cx + hw), y likewise; its landmarks are the last ones seen.
+//
+// THE KERNEL
+// One launch per update, one workgroup of ONE wave per stream.  The loop over the rows is sequential by definition; per row only an
+// arg-max over the slots is needed.  Lane l owns the slots j * 64 + l (j < ceil(max_tracks / 64) <= 16): it keeps their start-of-update
+// boxes and a flag in LDS words that no other lane touches, takes the best of its own slots in ascending order, and a six-step
+// xor butterfly over (measure, slot) leaves the winner in every lane.  No workgroup barrier in the loop.  The owner of the winning slot
+// writes the slot.  Free-slot ranks (birth) and alive-slot ranks (compaction) are prefix sums: one ballot per 64 slots plus a running
+// base, in slot order because slot = j * 64 + lane.  The state lives in device memory the tracker owns; nothing is read on the host.
+#include <climits>
+#include <cmath>
+
+#include "cf_common.h"
+#include "cf_kernels.h"
+
+namespace cf {
+
+namespace {
+
+constexpr int F_START = 1, F_MATCHED = 2, F_ALIVE = 4;      // s_flag: alive when the update began | matched in this update | alive after it
+
+__global__ __launch_bounds__(64) void track_update_kernel(TrackParams p) {
+    __shared__ float4 s_box[kTrackMaxSlots];      // start-of-update boxes (lane-owned words)
+    __shared__ int s_flag[kTrackMaxSlots];
+    __shared__ int s_new[kTrackMaxSlots];         // the first max_tracks new rows: no more can be born
+    const int b = blockIdx.x, lane = threadIdx.x, M = p.max_tracks, per = (M + 63) >> 6;
+    const size_t so = (size_t)(p.stream0 + b) * M;
+    int* meta = p.meta + so * 4;
+    float* rec = p.rec + so * 16;
+    for (int j = 0; j < per; ++j) {
+        const int k = j * 64 + lane;
+        if (k >= M) continue;
+        const int alive = meta[k * 4];
+        s_flag[k] = alive ? F_START : 0;
+        if (alive) s_box[k] = *reinterpret_cast<const float4*>(rec + (size_t)k * 16);
+    }
+    const int cnt = p.counts[b];
+    const int n = cnt < 0 ? 0 : cnt < p.rows ? cnt : p.rows;
+    const float* boxes = p.boxes + (size_t)b * p.rows * 4;
+    const float* scores = p.scores + (size_t)b * p.rows * p.score_stride;
+    const float* lms = p.lms + (size_t)b * p.rows * 10;
+    int n_new = 0;
+    for (int i = 0; i < n; ++i) {
+        const float4 d = *reinterpret_cast<const float4*>(boxes + (size_t)i * 4);
+        if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.z) && isfinite(d.w))) continue;
+        const float ad = (d.z - d.x + 1.0f) * (d.w - d.y + 1.0f);
+        float bv = -INFINITY;
+        int bk = INT_MAX;
+        for (int j = 0; j < per; ++j) {
+            const int k = j * 64 + lane;
+            if (k >= M || s_flag[k] != F_START) continue;
+            const float4 t = s_box[k];
+            const float at = (t.z - t.x + 1.0f) * (t.w - t.y + 1.0f);
+            const float w = fmaxf(0.0f, fminf(t.z, d.z) - fmaxf(t.x, d.x) + 1.0f), h = fmaxf(0.0f, fminf(t.w, d.w) - fmaxf(t.y, d.y) + 1.0f);
+            const float inter = w * h;
+            const float v = inter / (at + ad - inter);
+            if (v > bv) { bv = v; bk = k; }            // ascending k: the lowest slot among equals; a NaN never passes
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(bv, off);
+            const int ok = __shfl_xor(bk, off);
+            if (ov > bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
+        }
+        if (bk != INT_MAX && bv >= p.iou_thresh) {
+            if ((bk & 63) == lane) {
+                s_flag[bk] = F_START | F_MATCHED;
+                float* r = rec + (size_t)bk * 16;
+                r[0] = d.x; r[1] = d.y; r[2] = d.z; r[3] = d.w; r[4] = scores[(size_t)i * p.score_stride];
+                for (int q = 0; q < 10; ++q) r[5 + q] = lms[(size_t)i * 10 + q];
+                const int hits = meta[bk * 4 + 2];
+                meta[bk * 4 + 2] = hits < (1 << 30) ? hits + 1 : (1 << 30);
+                meta[bk * 4 + 3] = 0;
+            }
+        } else {
+            if (lane == 0 && n_new < M) s_new[n_new] = i;
+            ++n_new;
+        }
+    }
+    __syncthreads();                                   // s_new: written by lane 0, read by the owners of the free slots
+    // age the unmatched, then give the free slots to the new rows in slot order
+    const int next = p.next_id[p.stream0 + b];
+    int base = 0;
+    for (int j = 0; j < per; ++j) {
+        const int k = j * 64 + lane;
+        bool is_free = false;
+        if (k < M) {
+            const int f = s_flag[k];
+            bool alive = (f & F_MATCHED) != 0;
+            if (f == F_START) {
+                const int hits = meta[k * 4 + 2], misses = meta[k * 4 + 3] + 1;
+                alive = hits >= p.min_hits && misses <= p.max_age;
+                if (alive) meta[k * 4 + 3] = misses; else meta[k * 4] = 0;
+            }
+            s_flag[k] = alive ? F_ALIVE : 0;
+            is_free = !alive;
+        }
+        const unsigned long long bal = __ballot(is_free);
+        const int r = base + __popcll(bal & ((1ull << lane) - 1ull));
+        if (is_free && r < n_new) {
+            const int i = s_new[r];                    // r < the free slots <= max_tracks: written
+            float* q = rec + (size_t)k * 16;
+            for (int c = 0; c < 4; ++c) q[c] = boxes[(size_t)i * 4 + c];
+            q[4] = scores[(size_t)i * p.score_stride];
+            for (int c = 0; c < 10; ++c) q[5 + c] = lms[(size_t)i * 10 + c];
+            meta[k * 4] = 1; meta[k * 4 + 1] = next + r; meta[k * 4 + 2] = 1; meta[k * 4 + 3] = 0;
+            s_flag[k] = F_ALIVE;
+        }
+        base += __popcll(bal);
+    }
+    if (lane == 0) {
+        p.next_id[p.stream0 + b] = next + (n_new < base ? n_new : base);
+        p.flags[b] = n_new > base ? 1 : 0;
+    }
+    // the alive slots, compacted in slot order (every lane reads back only what it wrote itself)
+    float* odets = p.dets + (size_t)b * M * 5;
+    float* olms = p.lms_out + (size_t)b * M * 10;
+    int* oinfo = p.info + (size_t)b * M * 3;
+    float* ocorn = p.corners + (size_t)b * M * 4;
+    base = 0;
+    for (int j = 0; j < per; ++j) {
+        const int k = j * 64 + lane;
+        const bool alive = k < M && s_flag[k] == F_ALIVE;
+        const unsigned long long bal = __ballot(alive);
+        if (alive) {
+            const int r = base + __popcll(bal & ((1ull << lane) - 1ull));
+            const float* q = rec + (size_t)k * 16;
+            const int misses = meta[k * 4 + 3];
+            float x1 = q[0], y1 = q[1], x2 = q[2], y2 = q[3];
+            if (misses > 0) {
+                const double g = 1.0 + (double)p.hold_grow * (double)misses;
+                const double cx = ((double)x1 + (double)x2) * 0.5, hw = ((double)x2 - (double)x1) * 0.5 * g;
+                const double cy = ((double)y1 + (double)y2) * 0.5, hh = ((double)y2 - (double)y1) * 0.5 * g;
+                x1 = (float)(cx - hw); x2 = (float)(cx + hw); y1 = (float)(cy - hh); y2 = (float)(cy + hh);
+            }
+            float* od = odets + (size_t)r * 5;
+            od[0] = x1; od[1] = y1; od[2] = x2; od[3] = y2; od[4] = q[4];
+            float* oc = ocorn + (size_t)r * 4;
+            oc[0] = x1; oc[1] = y1; oc[2] = x2; oc[3] = y2;
+            for (int c = 0; c < 10; ++c) olms[(size_t)r * 10 + c] = q[5 + c];
+            oinfo[r * 3] = meta[k * 4 + 1]; oinfo[r * 3 + 1] = meta[k * 4 + 2]; oinfo[r * 3 + 2] = misses;
+        }
+        base += __popcll(bal);
+    }
+    if (lane == 0) p.out_counts[b] = base;
+}
+
+}  // namespace
+
+const char* track_check(const cf_track_opts* o, int n_streams) {
+    if (!o) return "null options";
+    if (!std::isfinite(o->iou_thresh) || !(o->iou_thresh > 0.f) || !(o->iou_thresh <= 1.f)) return "iou_thresh must be finite and in (0, 1]";
+    if (o->max_age < 0 || o->max_age > 1000) return "max_age must be in 0..1000";
+    if (o->min_hits < 1 || o->min_hits > 1000) return "min_hits must be in 1..1000";
+    if (o->max_tracks < 1 || o->max_tracks > kTrackMaxSlots) return "max_tracks must be in 1..1024";
+    if (!std::isfinite(o->hold_grow) || !(o->hold_grow >= 0.f) || !(o->hold_grow <= 1.f)) return "hold_grow must be finite and in 0..1";
+    if (n_streams < 1 || n_streams > kTrackMaxStreams) return "n_streams must be in 1..4096";
+    return nullptr;
+}
+
+hipError_t launch_track_update(hipStream_t s, const TrackParams& p) {
+    if (p.B < 1 || p.rows < 1 || p.max_tracks < 1 || p.max_tracks > kTrackMaxSlots || p.stream0 < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(track_update_kernel, dim3(p.B), dim3(64), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace cf

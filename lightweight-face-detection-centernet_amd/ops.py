@@ -322,6 +322,30 @@ def merge_tiles(rects, frame_hw, net_hw, dets_net, scores, lms_net, counts, max_
     return od, ol, oc, fl
 
 
+def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=None, device=0, **opts):
+    """The tracker's update over a whole sequence (``cf_op_track``) with a fresh tracker: boxes [F, S, rows, 4], scores [F, S, rows], lms
+    [F, S, rows, 10], counts [F, S] -- frame f of stream s has the rows below min(count, rows), in whatever coordinates they are.
+    ``opts``: iou, max_age, min_hits, max_tracks, hold_grow (``_lib.track_opts``).  Returns (dets [F, S, max_tracks, 5], lms
+    [F, S, max_tracks, 10], info [F, S, max_tracks, 3] = id, hits, misses, counts [F, S], flags [F, S]) after every frame; rows at and
+    past a count keep the bytes of the ``dets`` / ``lms_out`` / ``info`` arrays passed in (zeros by default)."""
+    o = _lib.track_opts(**opts)
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    if b.ndim != 4 or b.shape[3] != 4:
+        raise ValueError("boxes must be [F, S, rows, 4], got %s" % (b.shape,))
+    F, S, rows, _ = b.shape
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(F, S, rows)
+    lm = np.ascontiguousarray(lms, dtype=np.float32).reshape(F, S, rows, 10)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(F, S)
+    M = max(int(o.max_tracks), 1)
+    od = np.zeros((F, S, M, 5), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(F, S, M, 5)
+    ol = np.zeros((F, S, M, 10), np.float32) if lms_out is None else np.ascontiguousarray(lms_out, dtype=np.float32).reshape(F, S, M, 10)
+    oi = np.zeros((F, S, M, 3), np.int32) if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(F, S, M, 3)
+    oc, fl = np.zeros((F, S), np.int32), np.zeros((F, S), np.int32)
+    _lib.check(_lib.lib().cf_op_track(device, C.byref(o), S, F, rows, ptr(b), ptr(sc), ptr(lm), ptr(cn), ptr(od), ptr(ol), ptr(oi), ptr(oc), ptr(fl)),
+               op=True)
+    return od, ol, oi, oc, fl
+
+
 def ctdet_decode(heat, wh, reg=None, K=100, lm=None, device=0):
     """ctdet_decode (centerface_ext.py:52-82): (dets [B,K,6], lms [B,K,10]|None, inds [B,K] int64)."""
     heat, wh, reg, lm = f32(heat), f32(wh), f32(reg), f32(lm)

@@ -74,6 +74,14 @@ struct Op {
 
 struct Buf { std::string name; size_t elems = 0; bool f32 = false; void* p = nullptr; };
 
+struct DevBuf { void* p = nullptr; size_t bytes = 0; };      // device scratch that grow() enlarges on demand
+
+// The face rows a consumer reads, whichever producer wrote them: dets [.][stride][5] (the score column is dets + 4, stride 5), corners
+// [.][stride][4], lms [.][stride][10], counts [B]; in the pixels of an H x W network input or -- frame_space -- of the H x W frames of a
+// tiled forward.  RowStage: the newest producer behind the last forward.
+struct RowSet { const float* corners; const float* dets; const float* lms; const int* counts; int stride, B, H, W; bool frame_space; };
+enum RowStage { ROWS_NONE = 0, ROWS_DECODED, ROWS_MERGED, ROWS_TRACKED };
+
 }  // namespace
 
 struct cf_ctx {
@@ -116,26 +124,21 @@ struct cf_ctx {
     bool thr_pending = false; int thr_mode = 0, thr_h = 0, thr_w = 0, thr_maxout = 0, thr_B = 0; float thr_score = 0.f, thr_nms = 0.f, thr_rs_h = 0.f, thr_rs_w = 0.f;
     int prio = 0;                      // stream priority class of the context's main / decode streams: -1 lowest, 0 normal, +1 highest
     float rs_h = 0.f, rs_w = 0.f;      // cf_set_rescale: the threshold decode floor-divides x by rs_w and y by rs_h (0 = off)
-    // cf_align_faces: what the last forward read (al_in: device address of the network input, al_fmt its format, al_slot the host-input
-    // staging slot it sits in or -1; al_in = nullptr once an upload may have replaced it), the network-coordinate landmark rows of the
-    // last threshold decode ([max_batch][t_maxout][10], written by the sweep kernel beside its outputs; al_rows = that decode's max_out,
-    // 0 = no decode behind the last forward) and the scratch of the host-output form
-    const void* al_in = nullptr; int al_fmt = -1, al_slot = -1, al_rows = 0; float* t_lmsnet = nullptr;
-    uint8_t* al_chips = nullptr; size_t al_chips_bytes = 0; double* al_mats = nullptr; int al_mats_cap = 0; int* al_off = nullptr;
-    // cf_redact_faces: the network-coordinate box corners of the last threshold decode ([max_batch][t_maxout][4], beside t_lmsnet), the
-    // mosaic's cell means (one dword per grid cell, grown to the largest grid seen) and the frames of the host form
-    float* t_detsnet = nullptr; uint32_t* rd_cells = nullptr; size_t rd_cells_n = 0; uint8_t* rd_stage = nullptr; size_t rd_stage_bytes = 0;
-    uint8_t* bl_scratch = nullptr; size_t bl_scratch_bytes = 0;      // cf_blur_faces: the blurred values of the covered samples, laid out like rd_stage
-    // cf_forward_tiles / cf_merge_tiles: the rectangles of the last forward when it was a tiled one (tl_T = 0: it was not; host copy and
-    // device table, uploaded when they change), the frame geometry, and the merge's workspace and merged rows (tl_buf, grown on demand:
-    // cand, cand_count, order, mask | dets, lms, corners, counts, flags); tl_merged: a merge of the last decode is behind us, with
-    // tl_maxout rows per frame
-    std::vector<cf_tile_rect> tl_rects; cf_tile_rect* tl_rects_dev = nullptr; size_t tl_rects_bytes = 0; int tl_rects_up = 0;
-    int tl_T = 0, tl_Bf = 0, tl_h = 0, tl_w = 0, tl_maxout = 0; bool tl_merged = false;
-    void* tl_buf[9] = {}; size_t tl_have[9] = {};
-    // cf_track_update: the tracked rows of the last update (tk_buf, grown on demand: dets, lms, info, corners, counts, flags; tk_M rows
-    // per image).  tk_on: they stand in for the decode's / the merge's rows in face_rows; tk_done: an update consumed those rows
-    void* tk_buf[6] = {}; size_t tk_have[6] = {}; int tk_M = 0; bool tk_on = false, tk_done = false;
+    // What the last forward read (al_in: device address of the network input, al_fmt its format, al_slot the host-input staging slot it
+    // sits in or -1; al_in = nullptr once an upload may have replaced it) and the newest face rows behind it (rows_for): the threshold
+    // decode's (t_detsnet [max_batch][t_maxout][4] corners and t_lmsnet [.][.][10] landmarks in network coordinates, written by the sweep
+    // kernel beside t_dets and t_counts; al_rows = that decode's max_out), then cf_merge_tiles', then cf_track_update's
+    const void* al_in = nullptr; int al_fmt = -1, al_slot = -1, al_rows = 0; float* t_lmsnet = nullptr; float* t_detsnet = nullptr;
+    RowStage stage = ROWS_NONE;
+    // scratch, grown to the largest need seen: chips and matrices of the host-output align forms (al_off: their [max_batch + 1] offsets),
+    // the mosaic's cell means (one dword per grid cell), the frames of the host forms and the blur's mirror of them
+    DevBuf al_chips, al_mats, rd_cells, rd_stage, bl_scratch; int* al_off = nullptr;
+    // cf_forward_tiles: the rectangles of the last forward when it was a tiled one (tl_T = 0: it was not; host copy and device table,
+    // uploaded when they change) and the frame geometry.  cf_merge_tiles: its workspace and the merged rows, tl_maxout per frame
+    std::vector<cf_tile_rect> tl_rects; DevBuf tl_rects_dev; int tl_rects_up = 0;
+    int tl_T = 0, tl_Bf = 0, tl_h = 0, tl_w = 0, tl_maxout = 0;
+    struct { DevBuf cand, cand_count, order, mask, dets, lms, corners, counts, flags; } tl;
+    struct { DevBuf dets, lms, info, corners, counts, flags; } tk; int tk_M = 0;      // cf_track_update: the tracked rows, tk_M per image
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
     // input format, batch): the second forward with a key captures it, later ones replay it
     struct FwdGraph { const void* in; int fmt, B; hipGraphExec_t exec; bool broken; unsigned long long used; };
@@ -632,10 +635,12 @@ int cf_destroy(cf_ctx* c) {
     for (void* p : c->owned) hipFree(p);
     for (void* p : {(void*)c->src_stage, (void*)c->d_trans, (void*)c->hm_plane, (void*)c->keys, (void*)c->key_count, (void*)c->big, (void*)c->d_slot, (void*)c->d_dets, (void*)c->d_lms, (void*)c->d_inds, (void*)c->t_cand, (void*)c->t_count,
                     (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow,
-                    (void*)c->t_lmsnet, (void*)c->al_chips, (void*)c->al_mats, (void*)c->al_off, (void*)c->t_detsnet, (void*)c->rd_cells, (void*)c->rd_stage, (void*)c->bl_scratch, (void*)c->tl_rects_dev})
+                    (void*)c->t_lmsnet, (void*)c->al_off, (void*)c->t_detsnet})
         if (p) hipFree(p);
-    for (void* p : c->tl_buf) if (p) hipFree(p);
-    for (void* p : c->tk_buf) if (p) hipFree(p);
+    for (const DevBuf* b : {&c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->tl_rects_dev,
+                            &c->tl.cand, &c->tl.cand_count, &c->tl.order, &c->tl.mask, &c->tl.dets, &c->tl.lms, &c->tl.corners, &c->tl.counts, &c->tl.flags,
+                            &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags})
+        if (b->p) hipFree(b->p);
     if (c->h_thr) hipHostFree(c->h_thr);
     if (c->ev_thr) hipEventDestroy(c->ev_thr);
     for (auto& ev : c->events) if (ev) hipEventDestroy(ev);
@@ -1110,9 +1115,8 @@ hipError_t launch_plan_at(cf_ctx* c, size_t i, const void* net_in, int in_format
 int launch_all_ops(cf_ctx* c, const void* net_in, int in_format, int B) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
-    c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in_slot_used; c->al_rows = 0;      // what cf_align_faces samples
-    c->tl_T = 0; c->tl_merged = false;                    // (cf_forward_tiles sets its state again behind this call)
-    c->tk_on = false; c->tk_done = false;
+    c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in_slot_used;      // what cf_align_faces samples
+    c->stage = ROWS_NONE; c->tl_T = 0;                    // (cf_forward_tiles sets its state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -1494,12 +1498,77 @@ int cf_detect_topk(cf_ctx* c, const void* in, int in_format, int in_on_device, i
     return cf_decode_topk(c, K, 1, dets, lms, inds, out_on_device);
 }
 
+// Device scratch that only grows: b holds at least need_bytes afterwards, or nothing (CF_ENOMEM / CF_EHIP)
+static int grow(cf_ctx* c, DevBuf& b, size_t need_bytes, const char* what, const char* who) {
+    if (b.bytes >= need_bytes) return CF_OK;
+    if (b.p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(b.p); }        // earlier launches may still use it
+    b = DevBuf{};
+    const hipError_t e = hipMalloc(&b.p, need_bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "%s: %zu bytes of %s: %s", who, need_bytes, what, hipGetErrorString(e)); }
+    b.bytes = need_bytes;
+    return CF_OK;
+}
+
+// The host read-out tail of the threshold decode, the merge and the tracker: the counts (and flags) of B images, then only the rows that
+// exist -- [B][rows][.] out of [B][stride][.], one pitched copy per column with a destination (the rows past an image's count are never
+// read by the caller) -- and one wait.  d_counts = nullptr: the caller has the counts on the host already, in `counts`; otherwise
+// counts and flags may be null.
+struct RowCopy { void* dst; const void* src; size_t row_bytes; };
+static int read_out(cf_ctx* c, int B, int stride, const int* d_counts, const int* d_flags, int32_t* counts, int32_t* flags, std::initializer_list<RowCopy> cols) {
+    const size_t nb = (size_t)B * sizeof(int);
+    std::vector<int> hc;
+    if (d_counts) {     // hc lives on this stack frame: never return while a copy into it may still be in flight
+        hc.resize((size_t)2 * B);
+        const hipError_t e1 = hipMemcpyAsync(hc.data(), d_counts, nb, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = d_flags ? hipMemcpyAsync(hc.data() + B, d_flags, nb, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+        const hipError_t e3 = hipStreamSynchronize(c->stream);
+        HIPCHK(c, e1); HIPCHK(c, e2); HIPCHK(c, e3);
+    }
+    const int* n = d_counts ? hc.data() : counts;
+    int rows = 0, copies = 0;
+    for (int b = 0; b < B; ++b) rows = std::max(rows, std::min(n[b], stride));
+    for (const RowCopy& col : cols) {
+        if (rows < 1 || !col.dst) continue;
+        HIPCHK(c, hipMemcpy2DAsync(col.dst, stride * col.row_bytes, col.src, stride * col.row_bytes, rows * col.row_bytes, B, hipMemcpyDeviceToHost, c->stream));
+        ++copies;
+    }
+    if (copies) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (d_counts && counts) memcpy(counts, hc.data(), nb);
+    if (d_flags && flags) memcpy(flags, hc.data() + B, nb);
+    return CF_OK;
+}
+
+// Every state rule of the consumers of face rows, once: which rows `who` gets behind the last forward.
+enum RowsWanted {
+    ROWS_OF_DECODE,          // the threshold decode's, whatever came after (cf_align_faces)
+    ROWS_OF_TILED_DECODE,    // the same, of a tiled forward (cf_merge_tiles)
+    ROWS_UNTRACKED,          // the newest that no cf_track_update has consumed: the merged rows of a tiled forward, else the decode's
+    ROWS_NEWEST              // the tracked rows behind an update, else those (cf_redact_faces, cf_blur_faces, cf_align_faces_frame)
+};
+static int rows_for(cf_ctx* c, const char* who, RowsWanted want, RowSet& r) {
+    if (c->last_B < 1) return c->fail(CF_ESTATE, "%s before cf_forward", who);
+    if (want == ROWS_OF_TILED_DECODE && c->tl_T < 1) return c->fail(CF_ESTATE, "%s: the last forward was not cf_forward_tiles", who);
+    if (!c->al_in) return c->fail(CF_ESTATE, "%s: an upload was started after the last forward, its input is gone", who);
+    if (c->stage == ROWS_NONE || !c->t_detsnet || !c->t_dets || !c->t_lmsnet || !c->t_counts) return c->fail(CF_ESTATE, "%s without a threshold decode of the last forward", who);
+    r = RowSet{c->t_detsnet, c->t_dets, c->t_lmsnet, c->t_counts, c->al_rows, c->last_B, c->H, c->W, false};
+    if (want == ROWS_OF_DECODE || want == ROWS_OF_TILED_DECODE) return CF_OK;
+    if (c->tl_T > 0) {
+        if (c->stage < ROWS_MERGED) return c->fail(CF_ESTATE, "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
+        r = RowSet{(const float*)c->tl.corners.p, (const float*)c->tl.dets.p, (const float*)c->tl.lms.p, (const int*)c->tl.counts.p, c->tl_maxout, c->tl_Bf, c->tl_h, c->tl_w, true};
+    }
+    if (c->stage < ROWS_TRACKED) return CF_OK;
+    if (want == ROWS_UNTRACKED) return c->fail(CF_ESTATE, "%s: these rows went through an update already (time would advance twice)", who);
+    r.corners = (const float*)c->tk.corners.p; r.dets = (const float*)c->tk.dets.p; r.lms = (const float*)c->tk.lms.p;      // the same images and coordinates
+    r.counts = (const int*)c->tk.counts.p; r.stride = c->tk_M;
+    return CF_OK;
+}
+
 // keep_results: the per-image counts of the decode that just finished stay (cf_align_faces reads them beside the landmark rows)
 static void free_thresh_ws(cf_ctx* c, bool keep_results = false) {
     for (void* p : {(void*)c->t_cand, (void*)c->t_count, (void*)c->t_order, (void*)c->t_mask, (void*)(keep_results ? nullptr : c->t_counts), (void*)c->t_overflow})
         if (p) hipFree(p);
     c->t_cand = nullptr; c->t_count = nullptr; c->t_order = nullptr; c->t_mask = nullptr; c->t_overflow = nullptr;
-    if (!keep_results) { c->t_counts = nullptr; c->al_rows = 0; }
+    if (!keep_results) { c->t_counts = nullptr; c->stage = ROWS_NONE; }
     c->t_cap = 0; c->t_B = 0;
 }
 // The suppression matrix is dense: cap x cap / 64 words per image.  The workspace is sized for the batch of the CURRENT call
@@ -1534,7 +1603,7 @@ static int ensure_thresh_ws(cf_ctx* c, int max_out, int cap, int B) {
         if (!c->t_host && c->t_lms) hipFree(c->t_lms);
         if (c->t_lmsnet) hipFree(c->t_lmsnet);
         if (c->t_detsnet) hipFree(c->t_detsnet);
-        c->t_lmsnet = nullptr; c->t_detsnet = nullptr; c->al_rows = 0;
+        c->t_lmsnet = nullptr; c->t_detsnet = nullptr; c->stage = ROWS_NONE;
         if (c->h_thr) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipHostFree(c->h_thr); }
         c->t_dets = nullptr; c->t_lms = nullptr; c->h_thr = nullptr; c->t_host = false; c->t_maxout = 0;
         const size_t nd = (size_t)c->max_batch * max_out * 5 * sizeof(float), nl = 2 * nd, head = thr_host_head(c);
@@ -1583,7 +1652,7 @@ static int thresh_launch(cf_ctx* c, int mode, float score_thresh, float nms_thre
     HIPCHK(c, hipMemsetAsync(c->t_overflow, 0, sizeof(int), c->stream));
     HIPCHK(c, launch_decode_threshold(c->stream, p));
     HIPCHK(c, hipEventRecord(c->ev_thr, c->stream));
-    c->al_rows = max_out; c->tl_merged = false; c->tk_on = false; c->tk_done = false;
+    c->al_rows = max_out; c->stage = ROWS_DECODED;
     return CF_OK;
 }
 
@@ -1637,40 +1706,39 @@ int cf_decode_threshold_sized(cf_ctx* c, int mode, float score_thresh, float nms
         if (overflow > c->t_cap) return c->fail(CF_EOVERFLOW, "more than %d cells above the score threshold in one image", c->t_cap);
         break;
     }
-    // only the rows that exist: [B][rows][5 | 10] out of [B][max_out][.] (the rows past an image's count are never read by the caller)
-    int rows = 0;
-    for (int b = 0; b < B; ++b) rows = std::max(rows, std::min((int)counts[b], max_out));
-    if (rows > 0 && c->t_host) {
+    if (c->t_host) {                               // only the rows that exist, as read_out
         for (int b = 0; b < B; ++b) {
             const size_t n = (size_t)std::min((int)counts[b], max_out);
             if (!n) continue;
             memcpy(dets + (size_t)b * max_out * 5, c->t_dets + (size_t)b * max_out * 5, n * 5 * sizeof(float));
             if (lms) memcpy(lms + (size_t)b * max_out * 10, c->t_lms + (size_t)b * max_out * 10, n * 10 * sizeof(float));
         }
-    } else if (rows > 0) {
-        HIPCHK(c, hipMemcpy2DAsync(dets, (size_t)max_out * 5 * sizeof(float), c->t_dets, (size_t)max_out * 5 * sizeof(float),
-                                   (size_t)rows * 5 * sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
-        if (lms) HIPCHK(c, hipMemcpy2DAsync(lms, (size_t)max_out * 10 * sizeof(float), c->t_lms, (size_t)max_out * 10 * sizeof(float),
-                                            (size_t)rows * 10 * sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    } else if (int r = read_out(c, B, max_out, nullptr, nullptr, counts, nullptr, {{dets, c->t_dets, 5 * sizeof(float)}, {lms, c->t_lms, 10 * sizeof(float)}})) return r;
     if (thresh_mask_bytes(c->t_B, c->t_cap) > kThreshKeepBytes) free_thresh_ws(c, true);      // an oversized decode does not keep its workspace
     return CF_OK;
 }
 
-// The host-output tail of cf_align_faces and cf_align_faces_frame: the offsets, then the chips and matrices they announce, from the
-// context's scratch
+// The host-output form of cf_align_faces and cf_align_faces_frame: the kernel writes to the context's scratch (align_scratch), then the
+// offsets and the chips and matrices they announce come back from it (align_copy_out)
+static int align_scratch(cf_ctx* c, const char* who, size_t one, int cap_faces, bool want_mats, AlignParams& a) {
+    if (int r = grow(c, c->al_chips, std::max<size_t>(one * cap_faces, 16), "chips", who)) return r;
+    if (int r = grow(c, c->al_mats, (size_t)std::max(cap_faces, 1) * 6 * sizeof(double), "matrices", who)) return r;
+    if (!c->al_off) HIPCHK(c, hipMalloc((void**)&c->al_off, ((size_t)c->max_batch + 1) * sizeof(int)));      // (B <= max_batch)
+    a.chips = c->al_chips.p; a.mats = want_mats ? (double*)c->al_mats.p : nullptr; a.offsets = c->al_off;
+    return CF_OK;
+}
 static int align_copy_out(cf_ctx* c, int B, size_t one, int cap_faces, void* chips, double* matrices, int32_t* offsets) {
     HIPCHK(c, hipMemcpyAsync(offsets, c->al_off, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)std::min((int)offsets[B], cap_faces);
     if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(chips, c->al_chips, n * one, hipMemcpyDeviceToHost, c->stream));
-        if (matrices) HIPCHK(c, hipMemcpyAsync(matrices, c->al_mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(chips, c->al_chips.p, n * one, hipMemcpyDeviceToHost, c->stream));
+        if (matrices) HIPCHK(c, hipMemcpyAsync(matrices, c->al_mats.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return CF_OK;
 }
+static void align_rows_set(AlignParams& a, const RowSet& r) { a.lms = r.lms; a.lms_stride = a.rows_cap = r.stride; a.counts = r.counts; }
 
 // Aligned chips of the faces the last threshold decode kept (cf_align.hip): one launch on the stream that carried the decode, reading
 // the decode's device-side counts and network-coordinate landmark rows and the uint8 batch the forward read.
@@ -1682,81 +1750,32 @@ int cf_align_faces(cf_ctx* c, const cf_align_opts* o, void* chips, double* matri
     if (const char* why = align_params_set(p, o->size, o->format, o->rgb, o->mean, o->scale, o->tmpl, o->max_per_image))
         return c->fail(CF_EINVAL, "cf_align_faces: %s", why);
     if (out_on_device && (reinterpret_cast<uintptr_t>(chips) & 15)) return c->fail(CF_EINVAL, "cf_align_faces: device chips must be 16-byte aligned");
-    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_align_faces before cf_forward");
-    if (c->al_fmt != CF_IN_U8_HWC_BGR) return c->fail(CF_ESTATE, "cf_align_faces: the last forward read a float tensor, there is no uint8 batch to sample");
-    if (!c->al_in) return c->fail(CF_ESTATE, "cf_align_faces: an upload was started after the last forward, its input is gone");
-    if (c->al_rows < 1 || !c->t_lmsnet || !c->t_counts) return c->fail(CF_ESTATE, "cf_align_faces without a threshold decode of the last forward");
+    if (c->last_B >= 1 && c->al_fmt != CF_IN_U8_HWC_BGR) return c->fail(CF_ESTATE, "cf_align_faces: the last forward read a float tensor, there is no uint8 batch to sample");
+    RowSet rows{};
+    if (int r = rows_for(c, "cf_align_faces", ROWS_OF_DECODE, rows)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    const int B = c->last_B;
+    const int B = rows.B;
     p.img = (const uint8_t*)c->al_in; p.img_dwords = (size_t)B * c->H * c->W * 3 / 4; p.B = B; p.H = c->H; p.W = c->W;     // H, W multiples of 32
-    p.lms = c->t_lmsnet; p.lms_stride = c->al_rows; p.rows_cap = c->al_rows; p.counts = c->t_counts; p.cap_faces = cap_faces;
+    align_rows_set(p, rows); p.cap_faces = cap_faces;
     const size_t one = align_chip_bytes(o->size, o->format);
-    if (out_on_device) {
-        p.chips = chips; p.mats = matrices; p.offsets = offsets;
-    } else {
-        const size_t need_bytes = std::max<size_t>(one * cap_faces, 16);
-        if (c->al_chips_bytes < need_bytes) {
-            if (c->al_chips) hipFree(c->al_chips);
-            c->al_chips = nullptr; c->al_chips_bytes = 0;
-            const hipError_t e = hipMalloc((void**)&c->al_chips, need_bytes);
-            if (e != hipSuccess) { (void)hipGetLastError(); return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_align_faces: %zu bytes of chips: %s", need_bytes, hipGetErrorString(e)); }
-            c->al_chips_bytes = need_bytes;
-        }
-        if (c->al_mats_cap < std::max(cap_faces, 1)) {
-            if (c->al_mats) hipFree(c->al_mats);
-            c->al_mats = nullptr; c->al_mats_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->al_mats, (size_t)std::max(cap_faces, 1) * 6 * sizeof(double)));
-            c->al_mats_cap = std::max(cap_faces, 1);
-        }
-        if (!c->al_off) HIPCHK(c, hipMalloc((void**)&c->al_off, ((size_t)c->max_batch + 1) * sizeof(int)));
-        p.chips = c->al_chips; p.mats = matrices ? c->al_mats : nullptr; p.offsets = c->al_off;
-    }
+    if (out_on_device) { p.chips = chips; p.mats = matrices; p.offsets = offsets; }
+    else if (int r = align_scratch(c, "cf_align_faces", one, cap_faces, matrices != nullptr, p)) return r;
     HIPCHK(c, launch_align_faces(c->stream, p));
     if (c->al_slot >= 0) HIPCHK(c, hipEventRecord(c->ev_slot_free[c->al_slot], c->stream));      // the staging slot has one more reader
     if (out_on_device) return CF_OK;
     return align_copy_out(c, B, one, cap_faces, chips, matrices, offsets);
 }
 
-// Redaction of the faces the last threshold decode kept, in frames the caller names (cf_redact.hip): the launches go on the stream that
-// carried the decode and read its device-side counts and network-coordinate box rows.  Host frames are staged in rd_stage and copied
-// back; the scratch of the mosaic's cell means grows to the largest grid seen, like the decode workspace.
-static int grow(cf_ctx* c, void** p, size_t* have, size_t need_bytes, const char* what, const char* who) {
-    if (*have >= need_bytes) return CF_OK;
-    if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(*p); }        // earlier launches may still use it
-    *p = nullptr; *have = 0;
-    const hipError_t e = hipMalloc(p, need_bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "%s: %zu bytes of %s: %s", who, need_bytes, what, hipGetErrorString(e)); }
-    *have = need_bytes;
+// What cf_redact_faces, cf_blur_faces and cf_align_faces_frame share: the newest face rows (rows_for) with the B, h, w of the frames they
+// belong to, and the frames -- the caller's device planes as they are, or host frames staged in rd_stage around the launches.
+static int frame_rows(cf_ctx* c, const char* who, int B, int h, int w, RowSet& r) {
+    if (int e = rows_for(c, who, ROWS_NEWEST, r)) return e;
+    if (!r.frame_space) return B == r.B ? CF_OK : c->fail(CF_EINVAL, "%s: B=%d, the last forward had %d images", who, B, r.B);
+    if (B != r.B) return c->fail(CF_EINVAL, "%s: B=%d, the tiled forward had %d frames", who, B, r.B);
+    if (h != r.H || w != r.W) return c->fail(CF_EINVAL, "%s: %d x %d frames, the tiled forward had %d x %d", who, w, h, r.W, r.H);
     return CF_OK;
 }
-
-// What cf_redact_faces, cf_blur_faces and cf_align_faces_frame share: the state rules and the face rows (the last threshold decode's, in
-// network coordinates, or the merged rows of a tiled forward, in frame pixels, or -- behind a cf_track_update -- the tracked rows), and the frames -- the caller's device planes as they are,
-// or host frames staged in rd_stage around the launches.  want_lms: the caller reads the landmark rows, not the boxes.
-struct FaceRows { FaceList f; const float* lms; bool tiled; };
-static int face_rows(cf_ctx* c, const char* who, int B, int h, int w, bool want_lms, FaceRows& r) {
-    if (c->last_B < 1) return c->fail(CF_ESTATE, "%s before cf_forward", who);
-    if (!c->al_in) return c->fail(CF_ESTATE, "%s: an upload was started after the last forward", who);
-    if (c->al_rows < 1 || !(want_lms ? c->t_lmsnet : c->t_detsnet) || !c->t_counts) return c->fail(CF_ESTATE, "%s without a threshold decode of the last forward", who);
-    r.tiled = c->tl_T > 0;
-    if (r.tiled) {
-        if (!c->tl_merged) return c->fail(CF_ESTATE, "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
-        if (B != c->tl_Bf) return c->fail(CF_EINVAL, "%s: B=%d, the tiled forward had %d frames", who, B, c->tl_Bf);
-        if (h != c->tl_h || w != c->tl_w) return c->fail(CF_EINVAL, "%s: %d x %d frames, the tiled forward had %d x %d", who, w, h, c->tl_w, c->tl_h);
-        r.f = FaceList{(const float*)c->tl_buf[6], c->tl_maxout, (const int*)c->tl_buf[7], c->tl_maxout, c->tl_maxout, h, w};
-        r.lms = (const float*)c->tl_buf[5];
-    } else {
-        if (B != c->last_B) return c->fail(CF_EINVAL, "%s: B=%d, the last forward had %d images", who, B, c->last_B);
-        r.f = FaceList{c->t_detsnet, c->al_rows, c->t_counts, c->al_rows, c->al_rows, c->H, c->W};
-        r.lms = c->t_lmsnet;
-    }
-    if (c->tk_on) {                                      // cf_track_update stood behind those rows: the tracked rows, in the same coordinates
-        r.f.boxes = (const float*)c->tk_buf[3]; r.f.counts = (const int*)c->tk_buf[4];
-        r.f.box_stride = r.f.rows_cap = r.f.faces_cap = c->tk_M;
-        r.lms = (const float*)c->tk_buf[1];
-    }
-    return CF_OK;
-}
+static FaceList face_list(const RowSet& r) { return FaceList{r.corners, r.stride, r.counts, r.stride, r.stride, r.H, r.W}; }
 
 // launch(planes, pitch0, pitch1) -> hipError_t enqueues the kernels on c->stream.  Host frames: the call blocks until they have been
 // read and -- write_back -- written.  g is a copy: launch may rewrite the caller's geometry with the staged pitches, the copy back
@@ -1768,14 +1787,17 @@ static int on_frames(cf_ctx* c, const char* who, const FrameGeo g, const void* c
         return CF_OK;
     }
     const RedactStage st = redact_stage_layout(g.format, g.h, g.w);
-    int r = grow(c, (void**)&c->rd_stage, &c->rd_stage_bytes, st.one * g.B, "frame staging", who); if (r) return r;
-    HIPCHK(c, redact_stage_copy(c->stream, st, g.format, planes, g.B, g.h, g.pitch0, g.pitch1, c->rd_stage, true));
-    HIPCHK(c, launch(stage_table(st, c->rd_stage, g.format, g.B).data(), st.pitch0, st.pitch1));
-    if (write_back) HIPCHK(c, redact_stage_copy(c->stream, st, g.format, planes, g.B, g.h, g.pitch0, g.pitch1, c->rd_stage, false));
+    int r = grow(c, c->rd_stage, st.one * g.B, "frame staging", who); if (r) return r;
+    uint8_t* stage = (uint8_t*)c->rd_stage.p;
+    HIPCHK(c, redact_stage_copy(c->stream, st, g.format, planes, g.B, g.h, g.pitch0, g.pitch1, stage, true));
+    HIPCHK(c, launch(stage_table(st, stage, g.format, g.B).data(), st.pitch0, st.pitch1));
+    if (write_back) HIPCHK(c, redact_stage_copy(c->stream, st, g.format, planes, g.B, g.h, g.pitch0, g.pitch1, stage, false));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CF_OK;
 }
 
+// Redaction of the newest face rows, in frames the caller names (cf_redact.hip): the launches go on the stream that carried the rows'
+// producer and read its device-side counts and box corners.  The scratch of the mosaic's cell means grows to the largest grid seen.
 int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
                     int pitch0, int pitch1) {
     if (!c) return CF_EINVAL;
@@ -1786,19 +1808,16 @@ int cf_redact_faces(cf_ctx* c, const cf_redact_opts* o, int format, const cf_pla
         return c->fail(CF_EINVAL, "cf_redact_faces: %s", why);
     if (const char* why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1))
         return c->fail(CF_EINVAL, "cf_redact_faces: %s", why);
-    FaceRows rows{};
-    if (int r = face_rows(c, "cf_redact_faces", B, h, w, false, rows)) return r;
+    RowSet rows{};
+    if (int r = frame_rows(c, "cf_redact_faces", B, h, w, rows)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     RedactParams p{};
-    p.g = FrameGeo{format, B, h, w, pitch0, pitch1}; p.f = rows.f;
+    p.g = FrameGeo{format, B, h, w, pitch0, pitch1}; p.f = face_list(rows);
     p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
     p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
     if (o->mode == CF_REDACT_MOSAIC) {
-        size_t have = c->rd_cells_n * sizeof(uint32_t);
-        int r = grow(c, (void**)&c->rd_cells, &have, redact_cells(B, h, w, o->cell) * sizeof(uint32_t), "mosaic cell means", "cf_redact_faces");
-        c->rd_cells_n = have / sizeof(uint32_t);
-        if (r) return r;
-        p.cells = c->rd_cells;
+        if (int r = grow(c, c->rd_cells, redact_cells(B, h, w, o->cell) * sizeof(uint32_t), "mosaic cell means", "cf_redact_faces")) return r;
+        p.cells = (uint32_t*)c->rd_cells.p;
     }
     return on_frames(c, "cf_redact_faces", p.g, planes, on_device, true, [&](const void* const* pl, int p0, int p1) {
         p.planes = pl; p.g.pitch0 = p0; p.g.pitch1 = p1;
@@ -1817,14 +1836,14 @@ int cf_blur_faces(cf_ctx* c, const cf_blur_opts* o, int format, const cf_planes_
         return c->fail(CF_EINVAL, "cf_blur_faces: %s", why);
     if (const char* why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1))
         return c->fail(CF_EINVAL, "cf_blur_faces: %s", why);
-    FaceRows rows{};
-    if (int r = face_rows(c, "cf_blur_faces", B, h, w, false, rows)) return r;
+    RowSet rows{};
+    if (int r = frame_rows(c, "cf_blur_faces", B, h, w, rows)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     BlurParams p{};
-    p.g = FrameGeo{format, B, h, w, pitch0, pitch1}; p.f = rows.f;
+    p.g = FrameGeo{format, B, h, w, pitch0, pitch1}; p.f = face_list(rows);
     p.shape = o->shape; p.radius = o->radius; p.scale = o->scale;
-    if (int r = grow(c, (void**)&c->bl_scratch, &c->bl_scratch_bytes, blur_scratch_bytes(format, B, h, w), "blur scratch", "cf_blur_faces")) return r;
-    p.scratch = c->bl_scratch;
+    if (int r = grow(c, c->bl_scratch, blur_scratch_bytes(format, B, h, w), "blur scratch", "cf_blur_faces")) return r;
+    p.scratch = (uint8_t*)c->bl_scratch.p;
     return on_frames(c, "cf_blur_faces", p.g, planes, on_device, true, [&](const void* const* pl, int p0, int p1) {
         p.planes = pl; p.g.pitch0 = p0; p.g.pitch1 = p1;
         return launch_blur_faces(c->stream, p);
@@ -1850,27 +1869,14 @@ int cf_align_faces_frame(cf_ctx* c, const cf_align_opts* o, int format, const cf
         return CF_EINVAL;
     }
     if (why) return c->fail(CF_EINVAL, "cf_align_faces_frame: %s", why);
-    FaceRows rows{};
-    if (int r = face_rows(c, "cf_align_faces_frame", B, h, w, true, rows)) return r;
+    RowSet rows{};
+    if (int r = frame_rows(c, "cf_align_faces_frame", B, h, w, rows)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    p.a.lms = rows.lms; p.a.lms_stride = rows.f.box_stride; p.a.rows_cap = rows.f.rows_cap; p.a.counts = rows.f.counts;
-    p.sx = (double)w / (double)rows.f.W; p.sy = (double)h / (double)rows.f.H;      // merged rows are in frame pixels: 1.0
-    p.a.cap_faces = cap_faces;
+    align_rows_set(p.a, rows); p.a.cap_faces = cap_faces;
+    p.sx = (double)w / (double)rows.W; p.sy = (double)h / (double)rows.H;      // merged rows are in frame pixels: 1.0
     const size_t one = align_chip_bytes(o->size, o->format);
-    if (out_on_device) {
-        p.a.chips = chips; p.a.mats = matrices; p.a.offsets = offsets;
-    } else {
-        size_t have = c->al_chips_bytes;
-        int r = grow(c, (void**)&c->al_chips, &have, std::max<size_t>(one * cap_faces, 16), "chips", "cf_align_faces_frame");
-        c->al_chips_bytes = have;
-        if (r) return r;
-        have = (size_t)c->al_mats_cap * 6 * sizeof(double);
-        r = grow(c, (void**)&c->al_mats, &have, (size_t)std::max(cap_faces, 1) * 6 * sizeof(double), "matrices", "cf_align_faces_frame");
-        c->al_mats_cap = (int)(have / (6 * sizeof(double)));
-        if (r) return r;
-        if (!c->al_off) HIPCHK(c, hipMalloc((void**)&c->al_off, ((size_t)c->max_batch + 1) * sizeof(int)));      // (B <= max_batch)
-        p.a.chips = c->al_chips; p.a.mats = matrices ? c->al_mats : nullptr; p.a.offsets = c->al_off;
-    }
+    if (out_on_device) { p.a.chips = chips; p.a.mats = matrices; p.a.offsets = offsets; }
+    else if (int r = align_scratch(c, "cf_align_faces_frame", one, cap_faces, matrices != nullptr, p.a)) return r;
     // host frames are only read: staged, not copied back
     const int r = on_frames(c, "cf_align_faces_frame", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, in_on_device, false,
                             [&](const void* const* pl, int p0, int p1) {
@@ -1899,9 +1905,9 @@ int cf_forward_tiles(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_
     const size_t rbytes = (size_t)T * sizeof(cf_tile_rect);
     if (!c->tl_rects_up || c->tl_rects.size() != (size_t)T || memcmp(c->tl_rects.data(), rects, rbytes) != 0) {
         c->tl_rects_up = 0;
-        int r = grow(c, (void**)&c->tl_rects_dev, &c->tl_rects_bytes, rbytes, "rectangles", "cf_forward_tiles"); if (r) return r;
+        int r = grow(c, c->tl_rects_dev, rbytes, "rectangles", "cf_forward_tiles"); if (r) return r;
         c->tl_rects.assign(rects, rects + T);
-        HIPCHK(c, hipMemcpyAsync(c->tl_rects_dev, c->tl_rects.data(), rbytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->tl_rects_dev.p, c->tl_rects.data(), rbytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));                      // (only when the table changes: the host copy may be replaced next call)
         c->tl_rects_up = 1;
     }
@@ -1925,11 +1931,11 @@ int cf_forward_tiles(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_
             HIPCHK(c, hipEventRecord(c->ev_src_copy, cs));
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_src_copy, 0));
         }
-        HIPCHK(c, launch_cut_tiles(c->stream, format, dev.data(), Bf, st.pitch0, st.pitch1, c->tl_rects_dev, T, dst, c->H, c->W));
+        HIPCHK(c, launch_cut_tiles(c->stream, format, dev.data(), Bf, st.pitch0, st.pitch1, (const cf_tile_rect*)c->tl_rects_dev.p, T, dst, c->H, c->W));
         HIPCHK(c, hipEventRecord(c->ev_src_free, c->stream));
         c->src_busy = true;
     } else {
-        HIPCHK(c, launch_cut_tiles(c->stream, format, planes, Bf, pitch0, pitch1, c->tl_rects_dev, T, dst, c->H, c->W));
+        HIPCHK(c, launch_cut_tiles(c->stream, format, planes, Bf, pitch0, pitch1, (const cf_tile_rect*)c->tl_rects_dev.p, T, dst, c->H, c->W));
     }
     int r = launch_all_ops(c, dst, CF_IN_U8_HWC_BGR, Bf * T);
     if (r) return r;
@@ -1948,56 +1954,39 @@ int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
     if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge))
         return c->fail(CF_EINVAL, "cf_merge_tiles: thresh and edge must be finite and not negative");
     if (max_out < 1) return c->fail(CF_EINVAL, "cf_merge_tiles: max_out=%d must be at least 1", max_out);
-    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_merge_tiles before cf_forward_tiles");
-    if (c->tl_T < 1) return c->fail(CF_ESTATE, "cf_merge_tiles: the last forward was not cf_forward_tiles");
-    if (!c->al_in) return c->fail(CF_ESTATE, "cf_merge_tiles: an upload was started after the last forward");
-    if (c->al_rows < 1 || !c->t_detsnet || !c->t_lmsnet || !c->t_counts || !c->t_dets) return c->fail(CF_ESTATE, "cf_merge_tiles without a threshold decode of the last forward");
-    const int Bf = c->tl_Bf, T = c->tl_T, rows = c->al_rows;
+    RowSet in{};
+    if (int r = rows_for(c, "cf_merge_tiles", ROWS_OF_TILED_DECODE, in)) return r;
+    const int Bf = c->tl_Bf, T = c->tl_T, rows = in.stride;
     if ((long long)T * rows > (1 << 24) || merge_mask_bytes(Bf, T, rows) > kMergeMaskLimit)
         return c->fail(CF_ENOMEM, "cf_merge_tiles: %d frames x %d tiles x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
                        Bf, T, rows, merge_mask_bytes(Bf, T, rows) / 1e6);
     HIPCHK(c, hipSetDevice(c->device));
-    c->tl_merged = false; c->tk_on = false; c->tk_done = false;
-    const size_t cap = (size_t)T * rows, mo = (size_t)Bf * max_out;
-    const size_t need[9] = {Bf * cap * 16 * sizeof(float), Bf * sizeof(int), Bf * cap * sizeof(int), merge_mask_bytes(Bf, T, rows),
-                            mo * 5 * sizeof(float), mo * 10 * sizeof(float), mo * 4 * sizeof(float), Bf * sizeof(int), Bf * sizeof(int)};
-    static const char* const what[9] = {"candidates", "candidate counts", "sort order", "suppression bits", "merged dets", "merged landmarks", "merged corners", "merged counts", "flags"};
-    for (int k = 0; k < 9; ++k) { int r = grow(c, &c->tl_buf[k], &c->tl_have[k], need[k], what[k], "cf_merge_tiles"); if (r) return r; }
+    c->stage = ROWS_DECODED;                              // the merged (and tracked) rows of an earlier call are gone from here on
+    const size_t cap = (size_t)T * rows, mo = (size_t)Bf * max_out, nb = (size_t)Bf * sizeof(int);
+    const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
+    auto& ws = c->tl;
+    const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
+        {ws.cand, Bf * cap * 16 * sizeof(float), "candidates"}, {ws.cand_count, nb, "candidate counts"}, {ws.order, Bf * cap * sizeof(int), "sort order"},
+        {ws.mask, merge_mask_bytes(Bf, T, rows), "suppression bits"}, {ws.dets, nd, "merged dets"}, {ws.lms, nl, "merged landmarks"},
+        {ws.corners, mo * 4 * sizeof(float), "merged corners"}, {ws.counts, nb, "merged counts"}, {ws.flags, nb, "flags"}};
+    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_merge_tiles")) return r;
     MergeParams p{};
-    p.rects = c->tl_rects_dev; p.T = T; p.Bf = Bf; p.h = c->tl_h; p.w = c->tl_w; p.H = c->H; p.W = c->W;
-    p.dets_net = c->t_detsnet; p.scores = c->t_dets + 4; p.score_stride = 5; p.lms_net = c->t_lmsnet; p.counts = c->t_counts; p.rows = rows;
+    p.rects = (const cf_tile_rect*)c->tl_rects_dev.p; p.T = T; p.Bf = Bf; p.h = c->tl_h; p.w = c->tl_w; p.H = in.H; p.W = in.W;
+    p.dets_net = in.corners; p.scores = in.dets + 4; p.score_stride = 5; p.lms_net = in.lms; p.counts = in.counts; p.rows = rows;
     p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
-    p.cand = (float*)c->tl_buf[0]; p.cand_count = (int*)c->tl_buf[1]; p.order = (int*)c->tl_buf[2]; p.mask = (unsigned long long*)c->tl_buf[3];
-    p.max_out = max_out; p.dets = (float*)c->tl_buf[4]; p.lms = (float*)c->tl_buf[5]; p.corners = (float*)c->tl_buf[6];
-    p.out_counts = (int*)c->tl_buf[7]; p.flags = (int*)c->tl_buf[8];
+    p.cand = (float*)ws.cand.p; p.cand_count = (int*)ws.cand_count.p; p.order = (int*)ws.order.p; p.mask = (unsigned long long*)ws.mask.p;
+    p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
+    p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
     HIPCHK(c, launch_merge_tiles(c->stream, p));
-    c->tl_merged = true; c->tl_maxout = max_out;
+    c->stage = ROWS_MERGED; c->tl_maxout = max_out;
     if (out_on_device) {
-        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, need[4], hipMemcpyDeviceToDevice, c->stream));
-        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms, need[5], hipMemcpyDeviceToDevice, c->stream));
-        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, need[7], hipMemcpyDeviceToDevice, c->stream));
-        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, need[8], hipMemcpyDeviceToDevice, c->stream));
+        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
+        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms, nl, hipMemcpyDeviceToDevice, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, nb, hipMemcpyDeviceToDevice, c->stream));
+        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, nb, hipMemcpyDeviceToDevice, c->stream));
         return CF_OK;
     }
-    std::vector<int> hc((size_t)2 * Bf);
-    {   // hc lives on this stack frame: never return while a copy into it may still be in flight
-        const hipError_t e1 = hipMemcpyAsync(hc.data(), p.out_counts, need[7], hipMemcpyDeviceToHost, c->stream);
-        const hipError_t e2 = hipMemcpyAsync(hc.data() + Bf, p.flags, need[8], hipMemcpyDeviceToHost, c->stream);
-        const hipError_t e3 = hipStreamSynchronize(c->stream);
-        HIPCHK(c, e1); HIPCHK(c, e2); HIPCHK(c, e3);
-    }
-    int nrows = 0;
-    for (int f = 0; f < Bf; ++f) nrows = std::max(nrows, std::min(hc[f], max_out));
-    if (nrows > 0 && (dets || lms)) {                    // only the rows that exist, as cf_decode_threshold_sized
-        if (dets) HIPCHK(c, hipMemcpy2DAsync(dets, (size_t)max_out * 5 * sizeof(float), p.dets, (size_t)max_out * 5 * sizeof(float),
-                                             (size_t)nrows * 5 * sizeof(float), Bf, hipMemcpyDeviceToHost, c->stream));
-        if (lms) HIPCHK(c, hipMemcpy2DAsync(lms, (size_t)max_out * 10 * sizeof(float), p.lms, (size_t)max_out * 10 * sizeof(float),
-                                            (size_t)nrows * 10 * sizeof(float), Bf, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (counts) memcpy(counts, hc.data(), need[7]);
-    if (flags) memcpy(flags, hc.data() + Bf, need[8]);
-    return CF_OK;
+    return read_out(c, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }
 
 // ---- face tracks across frames (cf_track.hip).  The tracker owns the state of its streams, one event that orders its updates across
@@ -2068,66 +2057,44 @@ int cf_track_update(cf_ctx* c, cf_tracker* t, int stream0, float* dets, float* l
     if (!c) return CF_EINVAL;
     if (!t) return c->fail(CF_EINVAL, "cf_track_update: null tracker");
     if (t->device != c->device) return c->fail(CF_EINVAL, "cf_track_update: the tracker lives on device %d, the context on device %d", t->device, c->device);
-    if (c->last_B < 1) return c->fail(CF_ESTATE, "cf_track_update before cf_forward");
-    if (!c->al_in) return c->fail(CF_ESTATE, "cf_track_update: an upload was started after the last forward");
-    if (c->al_rows < 1 || !c->t_detsnet || !c->t_lmsnet || !c->t_counts || !c->t_dets) return c->fail(CF_ESTATE, "cf_track_update without a threshold decode of the last forward");
-    const bool tiled = c->tl_T > 0;
-    if (tiled && !c->tl_merged) return c->fail(CF_ESTATE, "cf_track_update after cf_forward_tiles without a cf_merge_tiles of the last decode");
-    if (c->tk_done) return c->fail(CF_ESTATE, "cf_track_update: these rows went through an update already (time would advance twice)");
-    const int B = tiled ? c->tl_Bf : c->last_B, M = t->o.max_tracks;
-    const int sh = tiled ? c->tl_h : c->H, sw = tiled ? c->tl_w : c->W;
+    RowSet in{};
+    if (int r = rows_for(c, "cf_track_update", ROWS_UNTRACKED, in)) return r;
+    const bool tiled = in.frame_space;
+    const int B = in.B, M = t->o.max_tracks;
     if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_track_update: streams %d .. %d of a tracker with %d", stream0, stream0 + B - 1, t->S);
-    if (t->latched && (t->sp_tiled != tiled || t->sp_h != sh || t->sp_w != sw))
+    if (t->latched && (t->sp_tiled != tiled || t->sp_h != in.H || t->sp_w != in.W))
         return c->fail(CF_EINVAL, "cf_track_update: the tracker's rows are in %s %d x %d coordinates, these in %s %d x %d", t->sp_tiled ? "frame" : "network", t->sp_w, t->sp_h,
-                       tiled ? "frame" : "network", sw, sh);
+                       tiled ? "frame" : "network", in.W, in.H);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bm = (size_t)B * M;
-    const size_t need[6] = {bm * 5 * sizeof(float), bm * 10 * sizeof(float), bm * 3 * sizeof(int), bm * 4 * sizeof(float), B * sizeof(int), B * sizeof(int)};
-    static const char* const what[6] = {"tracked dets", "tracked landmarks", "track info", "tracked corners", "tracked counts", "track flags"};
-    for (int k = 0; k < 6; ++k) { int r = grow(c, &c->tk_buf[k], &c->tk_have[k], need[k], what[k], "cf_track_update"); if (r) return r; }
+    const size_t bm = (size_t)B * M, nb = (size_t)B * sizeof(int);
+    const size_t nd = bm * 5 * sizeof(float), nl = bm * 10 * sizeof(float), ni = bm * 3 * sizeof(int);
+    auto& ws = c->tk;
+    const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
+        {ws.dets, nd, "tracked dets"}, {ws.lms, nl, "tracked landmarks"}, {ws.info, ni, "track info"},
+        {ws.corners, bm * 4 * sizeof(float), "tracked corners"}, {ws.counts, nb, "tracked counts"}, {ws.flags, nb, "track flags"}};
+    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_track_update")) return r;
     TrackParams p{};
-    if (tiled) {
-        p.boxes = (const float*)c->tl_buf[6]; p.scores = (const float*)c->tl_buf[4] + 4; p.lms = (const float*)c->tl_buf[5];
-        p.counts = (const int*)c->tl_buf[7]; p.rows = c->tl_maxout;
-    } else {
-        p.boxes = c->t_detsnet; p.scores = c->t_dets + 4; p.lms = c->t_lmsnet; p.counts = c->t_counts; p.rows = c->al_rows;
-    }
-    p.score_stride = 5; p.B = B; p.stream0 = stream0;
+    p.boxes = in.corners; p.scores = in.dets + 4; p.score_stride = 5; p.lms = in.lms; p.counts = in.counts; p.rows = in.stride;
+    p.B = B; p.stream0 = stream0;
     p.iou_thresh = t->o.iou_thresh; p.max_age = t->o.max_age; p.min_hits = t->o.min_hits; p.max_tracks = M; p.hold_grow = t->o.hold_grow;
     p.meta = t->meta; p.rec = t->rec; p.next_id = t->next_id;
-    p.dets = (float*)c->tk_buf[0]; p.lms_out = (float*)c->tk_buf[1]; p.info = (int*)c->tk_buf[2]; p.corners = (float*)c->tk_buf[3];
-    p.out_counts = (int*)c->tk_buf[4]; p.flags = (int*)c->tk_buf[5];
+    p.dets = (float*)ws.dets.p; p.lms_out = (float*)ws.lms.p; p.info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
+    p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
     HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the update before this one, on whichever context's stream
     HIPCHK(c, launch_track_update(c->stream, p));
     HIPCHK(c, hipEventRecord(t->ev, c->stream));
-    t->latched = true; t->sp_tiled = tiled; t->sp_h = sh; t->sp_w = sw;
-    c->tk_on = true; c->tk_done = true; c->tk_M = M;
+    t->latched = true; t->sp_tiled = tiled; t->sp_h = in.H; t->sp_w = in.W;
+    c->stage = ROWS_TRACKED; c->tk_M = M;
     if (out_on_device) {
-        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, need[0], hipMemcpyDeviceToDevice, c->stream));
-        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, need[1], hipMemcpyDeviceToDevice, c->stream));
-        if (info) HIPCHK(c, hipMemcpyAsync(info, p.info, need[2], hipMemcpyDeviceToDevice, c->stream));
-        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, need[4], hipMemcpyDeviceToDevice, c->stream));
-        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, need[5], hipMemcpyDeviceToDevice, c->stream));
+        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
+        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, nl, hipMemcpyDeviceToDevice, c->stream));
+        if (info) HIPCHK(c, hipMemcpyAsync(info, p.info, ni, hipMemcpyDeviceToDevice, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, nb, hipMemcpyDeviceToDevice, c->stream));
+        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, nb, hipMemcpyDeviceToDevice, c->stream));
         return CF_OK;
     }
-    std::vector<int> hc((size_t)2 * B);
-    {   // hc lives on this stack frame: never return while a copy into it may still be in flight
-        const hipError_t e1 = hipMemcpyAsync(hc.data(), p.out_counts, need[4], hipMemcpyDeviceToHost, c->stream);
-        const hipError_t e2 = hipMemcpyAsync(hc.data() + B, p.flags, need[5], hipMemcpyDeviceToHost, c->stream);
-        const hipError_t e3 = hipStreamSynchronize(c->stream);
-        HIPCHK(c, e1); HIPCHK(c, e2); HIPCHK(c, e3);
-    }
-    int nrows = 0;
-    for (int b = 0; b < B; ++b) nrows = std::max(nrows, std::min(hc[b], M));
-    if (nrows > 0 && (dets || lms || info)) {            // only the rows that exist, as cf_merge_tiles
-        if (dets) HIPCHK(c, hipMemcpy2DAsync(dets, (size_t)M * 5 * sizeof(float), p.dets, (size_t)M * 5 * sizeof(float), (size_t)nrows * 5 * sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
-        if (lms) HIPCHK(c, hipMemcpy2DAsync(lms, (size_t)M * 10 * sizeof(float), p.lms_out, (size_t)M * 10 * sizeof(float), (size_t)nrows * 10 * sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
-        if (info) HIPCHK(c, hipMemcpy2DAsync(info, (size_t)M * 3 * sizeof(int), p.info, (size_t)M * 3 * sizeof(int), (size_t)nrows * 3 * sizeof(int), B, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (counts) memcpy(counts, hc.data(), need[4]);
-    if (flags) memcpy(flags, hc.data() + B, need[5]);
-    return CF_OK;
+    return read_out(c, B, M, p.out_counts, p.flags, counts, flags,
+                    {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)}});
 }
 
 int cf_event_record(cf_ctx* c, int slot) {

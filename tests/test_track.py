@@ -151,6 +151,83 @@ def _state_error(call):
     assert e.value.code == cfa._lib.CF_ESTATE
 
 
+OK, STATE, VALUE = "ok", "CF_ESTATE", "ValueError"
+
+
+def _outcome(call):
+    try:
+        call()
+    except ValueError:
+        return VALUE
+    except cfa._lib.CenterFaceError as e:
+        assert e.code == cfa._lib.CF_ESTATE, e
+        return STATE
+    return OK
+
+
+def _expect(state, eng, trk, frames, **want):
+    """Calls the named consumers of the current face rows, in the order given, and compares the outcome class of each; a refused call
+    must leave its host frames as they were.  (A merge or an update that succeeds moves the context on: name it last.)"""
+    keep = frames.copy()
+    calls = dict(align=lambda: eng.align_faces(size=16),
+                 align_frame=lambda: eng.align_faces_frame(keep, "bgr", size=16),
+                 redact=lambda: eng.redact_faces(keep, "bgr", mode="solid", fill=(1, 2, 3)),
+                 blur=lambda: eng.blur_faces(keep, "bgr", radius=2),
+                 merge=lambda: eng.merge_tiles(max_out=64),
+                 update=lambda: eng.track_update(trk))
+    for name, outcome in want.items():
+        keep[...] = frames
+        assert _outcome(calls[name]) == outcome, (state, name)
+        if outcome != OK:
+            assert np.array_equal(keep, frames), (state, name)
+
+
+def test_row_sources_state_table():
+    """Which consumer accepts the context in which state: the decode's, the merge's and the tracker's rows, walked through a plain and a
+    tiled forward.  Only the outcome class is asserted (random frames: every call is legal with any number of rows)."""
+    rng = np.random.default_rng(5)
+    eng = cfa.Engine(64, 96, max_batch=4, dtype="bf16")
+    frames = rng.integers(0, 256, (2, 76, 102, 3), dtype=np.uint8)
+    four = rng.integers(0, 256, (4, 76, 102, 3), dtype=np.uint8)
+    decode = lambda: eng.decode_threshold(0.3, 0.3, 64)                     # noqa: E731
+    everything = lambda o: dict(align=o, align_frame=o, redact=o, blur=o, merge=o, update=o)      # noqa: E731
+    chips = lambda o: dict(align=OK, align_frame=o, redact=o, blur=o)       # noqa: E731
+    # ---- a plain forward
+    trk = cfa.Tracker(eng, 2, max_tracks=8)
+    _expect("fresh", eng, trk, frames, **everything(STATE))
+    eng.forward_resized_enqueue(frames)
+    _expect("forward", eng, trk, frames, **everything(STATE))
+    decode()
+    _expect("decode", eng, trk, frames, **chips(OK), merge=STATE, update=OK)
+    _expect("update", eng, trk, frames, **chips(OK), merge=STATE, update=STATE)
+    decode()
+    _expect("decode again", eng, trk, frames, **chips(OK), merge=STATE, update=OK)
+    _expect("update again", eng, trk, frames, **chips(OK), merge=STATE, update=STATE)
+    eng.upload_images(list(frames))
+    _expect("upload", eng, trk, frames, **everything(STATE))
+    eng.forward_enqueue(rng.standard_normal((2, 3, 64, 96)).astype(np.float32))
+    _expect("float forward", eng, trk, frames, **everything(STATE))
+    decode()
+    _expect("float decode", eng, trk, frames, align=STATE, align_frame=OK, redact=OK, blur=OK, merge=STATE, update=OK)
+    _expect("float update", eng, trk, frames, align=STATE, align_frame=OK, redact=OK, blur=OK, merge=STATE, update=STATE)
+    trk.close()
+    # ---- a tiled forward: 2 frames x 2 rectangles, rows in frame pixels (another coordinate space: another tracker)
+    trk = cfa.Tracker(eng, 2, max_tracks=8)
+    eng.forward_tiles_enqueue(frames, [(0, 0, 64, 48), (38, 28, 64, 48)], "bgr")
+    _expect("tiles", eng, trk, frames, **everything(STATE))
+    decode()
+    _expect("tiles decode", eng, trk, frames, **chips(STATE), update=STATE, merge=OK)
+    _expect("merge", eng, trk, frames, **chips(OK))
+    _expect("merge, B = Bf * T", eng, trk, four, align_frame=VALUE, redact=VALUE, blur=VALUE)
+    _expect("merge", eng, trk, frames, update=OK)
+    _expect("tiles update", eng, trk, frames, **chips(OK), update=STATE, merge=OK)
+    _expect("merge again", eng, trk, frames, **chips(OK), update=OK)
+    _expect("tiles update again", eng, trk, frames, **chips(OK), update=STATE)
+    decode()
+    _expect("tiles decode again", eng, trk, frames, **chips(STATE), update=STATE, merge=OK)
+    trk.close(), eng.close()
+
+
 def test_engine_update_holds_tracks_and_the_redaction_covers_them():
     rng = np.random.default_rng(3)
     eng = cfa.Engine(64, 96, max_batch=3, dtype="bf16")

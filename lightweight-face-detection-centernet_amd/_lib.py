@@ -231,26 +231,16 @@ def frame_planes(frames, fmt, writable=True):
             return tab, B, h, w, 3 * w, 0, x
         if x.ndim != 3 or (x.shape[1] * 2 // 3) * 3 // 2 != x.shape[1]:
             raise ValueError("4:2:0 frames must be uint8 [B, h*3//2, w] with h even, got %s" % (x.shape,))
-        B, rows, w = x.shape
-        h = rows * 2 // 3
-        offs, cp = yuv_dense_geometry(f, h, w)
-        tab = (PlanesRW * max(B, 1))()
-        for b in range(B):
-            base = x.ctypes.data + b * rows * w
-            tab[b].p0, tab[b].p1, tab[b].p2 = base, base + offs[1], (base + offs[2]) if offs[2] is not None else None
-        return tab, B, h, w, w, cp, x
+        tab, h, w, cp = dense_planes(f, x)
+        return tab, x.shape[0], h, w, w, cp, x
     frames = list(frames)
     if not bgr and frames and all(isinstance(t, np.ndarray) and t.ndim == 2 for t in frames):
         # a list of dense [h*3//2, w] frames, as forward_yuv_enqueue takes them
         rows, w = frames[0].shape
-        h = rows * 2 // 3
-        offs, cp = yuv_dense_geometry(f, h, w)
-        tab = (PlanesRW * len(frames))()
-        for b, x in enumerate(frames):
-            if x.dtype != np.uint8 or x.shape != (rows, w) or h * 3 // 2 != rows or not x.flags["C_CONTIGUOUS"] or (writable and not x.flags["WRITEABLE"]):
+        for x in frames:
+            if x.dtype != np.uint8 or x.shape != (rows, w) or (rows * 2 // 3) * 3 // 2 != rows or not x.flags["C_CONTIGUOUS"] or (writable and not x.flags["WRITEABLE"]):
                 raise ValueError("frames must be writable C-contiguous uint8 [h*3//2, w] arrays of one size, got %s %s" % (x.dtype, x.shape))
-            base = x.ctypes.data
-            tab[b].p0, tab[b].p1, tab[b].p2 = base, base + offs[1], (base + offs[2]) if offs[2] is not None else None
+        tab, h, w, cp = dense_planes(f, frames)
         return tab, len(frames), h, w, w, cp, frames
     frames = [t if isinstance(t, (tuple, list)) else (t,) for t in frames]
     need = 1 if bgr else 2 if il else 3
@@ -287,8 +277,35 @@ def frame_planes(frames, fmt, writable=True):
     return tab, B, h, w, pitch0, pitch1, keep
 
 
+def dense_planes(f, frames):
+    """(PlanesRW table, h, w, chroma pitch) of dense 4:2:0 host frames the caller has validated: a C-contiguous uint8 [B, h*3//2, w] array
+    or a list of C-contiguous [h*3//2, w] arrays."""
+    rows, w = frames.shape[1:] if isinstance(frames, np.ndarray) else frames[0].shape
+    h = rows * 2 // 3
+    offs, cp = yuv_dense_geometry(f, h, w)
+    bases = [frames.ctypes.data + b * rows * w for b in range(len(frames))] if isinstance(frames, np.ndarray) else [a.ctypes.data for a in frames]
+    tab = (PlanesRW * max(len(bases), 1))()
+    for b, base in enumerate(bases):
+        tab[b].p0, tab[b].p1, tab[b].p2 = base, base + offs[1], (base + offs[2]) if offs[2] is not None else None
+    return tab, h, w, cp
+
+
+def host_frame_args(frames, fmt, writable=True):
+    """The frame arguments of cf_redact_faces / cf_blur_faces / cf_align_faces_frame / cf_forward_tiles for host ``frames`` as ``frame_planes``
+    takes them: ((format, table, in_on_device = 0, B, h, w, pitch0, pitch1), the arrays to keep alive for the call)."""
+    tab, B, h, w, pitch0, pitch1, keep = frame_planes(frames, fmt, writable)
+    return (frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1), keep
+
+
+def device_frame_args(who, plane_ptrs, fmt, B, h, w, pitch0, pitch1):
+    """The same arguments for B tuples of device addresses (in_on_device = 1); ``who`` names the caller in the refusal."""
+    if int(B) != len(plane_ptrs):
+        raise ValueError("%s: %d plane tuples for B=%d" % (who, len(plane_ptrs), B))
+    return frame_format(fmt), device_planes(plane_ptrs), 1, int(B), int(h), int(w), int(pitch0), int(pitch1)
+
+
 def device_planes(plane_ptrs):
-    """PlanesRW table of B tuples (p0, p1, p2) of device addresses (missing planes None)."""
+    """PlanesRW table of B tuples (p0, p1, p2) of device addresses (missing planes None); cf_yuv_planes has the same layout."""
     tab = (PlanesRW * max(len(plane_ptrs), 1))()
     for b, t in enumerate(plane_ptrs):
         t = (tuple(t) if isinstance(t, (tuple, list)) else (t,)) + (None, None)
@@ -381,7 +398,7 @@ def lib():
             L.cf_forward_lanes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
             L.cf_forward_lanes_flush.argtypes = [C.c_void_p]
         L.cf_forward_resized.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.cf_forward_yuv.argtypes = [C.c_void_p, C.c_int, C.POINTER(YuvPlanes), C.c_int] + [C.c_int] * 5
+        L.cf_forward_yuv.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 5      # (a YuvPlanes or a PlanesRW table: one layout)
         L.cf_op_yuv_to_bgr.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
         L.cf_align_faces.argtypes = [C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.cf_op_align_faces.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(AlignOpts), C.c_void_p, C.c_void_p]

@@ -16,6 +16,7 @@ import bisect
 import ctypes as C
 import os
 import threading
+import types
 import weakref
 
 import numpy as np
@@ -27,6 +28,16 @@ _DTYPES = {"fp32": _lib.CF_F32, "float32": _lib.CF_F32, "f32": _lib.CF_F32,
            "bf16": _lib.CF_BF16, "bfloat16": _lib.CF_BF16,
            # tolerance mode: fp32 storage, split-bf16 ("bf16x3") GEMM products -- within 1e-3 of the reference like "fp32"
            "fp32_split": _lib.CF_F32_SPLIT, "bf16x3": _lib.CF_F32_SPLIT}
+
+
+def _grown(cap, run):
+    """``run(cap)`` fills buffers of ``cap`` rows and returns (result, rows wanted): the result of the first run whose buffers held all
+    it wanted -- when more rows survive than there is room for, the reference keeps them all, so the run is repeated with that many."""
+    while True:
+        res, want = run(cap)
+        if want <= cap:
+            return res
+        cap = want
 
 
 class Engine(object):
@@ -53,7 +64,9 @@ class Engine(object):
         _lib.check(L.cf_create(self.device, self.max_batch, self.H, self.W, _DTYPES[dtype], flags, C.byref(handle)))
         self._h = handle
         self._L = L
-        self.last_B = 0
+        # what the last forward was: its batch (last_B), (frames, tiles per frame) when it was tiled, the batches waiting in an upload or
+        # in a lane, the rows the last decode or merge kept (the align forms size their buffers from it), the host arrays kept alive
+        self._last = types.SimpleNamespace(B=0, tiles=None, uploaded_B=0, lane_B=0, kept=0, keep=None)
         if weights is None:
             weights = _weights.synthetic_state_dict(0)
         elif isinstance(weights, str):
@@ -82,12 +95,11 @@ class Engine(object):
     @property
     def last_B(self):
         """The batch of the last forward (tile images after ``forward_tiles_enqueue``)."""
-        return self._last_B
+        return self._last.B
 
     @last_B.setter
     def last_B(self, B):
-        self._last_B = B
-        self._tiled_last = False              # (forward_tiles_enqueue sets it again behind this)
+        self._last.B, self._last.tiles = B, None          # (forward_tiles_enqueue sets the tiles again behind this)
 
     def load_state_dict(self, sd):
         """Strict load (centerface.py:24)."""
@@ -123,7 +135,7 @@ class Engine(object):
                     raise ValueError("float input must be [B,3,%d,%d], got %s" % (self.H, self.W, x.shape))
                 in_format = _lib.CF_IN_F32_NCHW
             B = x.shape[0]
-            self._keep_in = x
+            self._last.keep = x
             p = _lib.ptr(x)
         self._chk(self._L.cf_forward(self._h, p, int(in_format), 1 if on_device else 0, int(B)))
         self.last_B = int(B)
@@ -139,14 +151,14 @@ class Engine(object):
             raise RuntimeError("cf_forward_lanes exists only in an experiments build of the library (make -C csrc EXP=1)")
         self._chk(self._L.cf_forward_lanes(self._h, prev._h if prev is not None else None, C.c_void_p(int(x)), fmt, 1, int(B)))
         self.last_B = 0
-        if prev is not None and getattr(prev, "_lane_B", 0):
-            prev.last_B, prev._lane_B = prev._lane_B, 0
-        self._lane_B = int(B)
+        if prev is not None and prev._last.lane_B:
+            prev.last_B, prev._last.lane_B = prev._last.lane_B, 0
+        self._last.lane_B = int(B)
 
     def forward_lanes_flush(self):
         self._chk(self._L.cf_forward_lanes_flush(self._h))
-        if getattr(self, "_lane_B", 0):
-            self.last_B, self._lane_B = self._lane_B, 0
+        if self._last.lane_B:
+            self.last_B, self._last.lane_B = self._last.lane_B, 0
 
     def forward_resized_enqueue(self, imgs_u8):
         """cv2.resize + forward (centerface.py:30-41): uint8 [B,h,w,3] BGR images of any (common) size are
@@ -154,7 +166,7 @@ class Engine(object):
         x = np.ascontiguousarray(imgs_u8, dtype=np.uint8)
         if x.ndim != 4 or x.shape[3] != 3:
             raise ValueError("images must be uint8 [B,h,w,3], got %s" % (x.shape,))
-        self._keep_in = x
+        self._last.keep = x
         self._chk(self._L.cf_forward_resized(self._h, _lib.ptr(x), 0, x.shape[0], x.shape[1], x.shape[2]))
         self.last_B = x.shape[0]
 
@@ -171,14 +183,13 @@ class Engine(object):
             if h is None or w is None:
                 raise ValueError("forward_yuv_enqueue(on_device=True) needs h and w")
             h, w = int(h), int(w)
-            addrs = [(tuple(t) + (None, None))[:3] for t in frames]
-            keep = None
+            tab, B, cp = _lib.device_planes(frames), len(frames), _lib.yuv_dense_geometry(f, h, w)[1]
         else:
             if isinstance(frames, np.ndarray):
-                x = np.ascontiguousarray(frames)
-                if x.dtype != np.uint8 or x.ndim != 3:
-                    raise ValueError("frames must be uint8 [B, h*3//2, w], got %s %s" % (x.dtype, x.shape))
-                arrs, shp, bases = x, x.shape[1:], [x.ctypes.data + b * x[0].nbytes for b in range(x.shape[0])]
+                arrs = np.ascontiguousarray(frames)
+                if arrs.dtype != np.uint8 or arrs.ndim != 3:
+                    raise ValueError("frames must be uint8 [B, h*3//2, w], got %s %s" % (arrs.dtype, arrs.shape))
+                shp = arrs.shape[1:]
             else:
                 arrs = [np.asarray(a) for a in frames]
                 if not arrs:
@@ -188,27 +199,15 @@ class Engine(object):
                     if a.dtype != np.uint8 or a.ndim != 2 or a.shape != shp:
                         raise ValueError("frames must be uint8 [h*3//2, w] arrays of one size, got %s %s (first: %s)" % (a.dtype, a.shape, shp))
                 arrs = [a if a.flags["C_CONTIGUOUS"] else np.ascontiguousarray(a) for a in arrs]
-                bases = [a.ctypes.data for a in arrs]
-            rows, fw = int(shp[0]), int(shp[1])
-            fh = rows * 2 // 3
-            if fh * 3 // 2 != rows or (h is not None and int(h) != fh) or (w is not None and int(w) != fw):
+            if (shp[0] * 2 // 3) * 3 // 2 != shp[0] or (h is not None and int(h) != shp[0] * 2 // 3) or (w is not None and int(w) != shp[1]):
                 raise ValueError("a 4:2:0 frame of h x w is [h*3//2, w] with h even; got %s (h=%s, w=%s)" % (shp, h, w))
-            h, w = fh, fw
-            offs, cp = _lib.yuv_dense_geometry(f, h, w)
+            tab, h, w, cp = _lib.dense_planes(f, arrs)
             if (y_pitch is not None and int(y_pitch) != w) or (c_pitch is not None and int(c_pitch) != cp):
                 raise ValueError("host frames are dense [h*3//2, w] arrays: y_pitch = w, c_pitch = the chroma row")
-            addrs = [tuple(None if o is None else a + o for o in offs) for a in bases]
-            keep = arrs
-        il = f in (_lib.CF_YUV_NV12, _lib.CF_YUV_NV21)
-        y_pitch = w if y_pitch is None else int(y_pitch)
-        c_pitch = (w if il else w // 2) if c_pitch is None else int(c_pitch)
-        descs = (_lib.YuvPlanes * max(len(addrs), 1))()
-        for b, (y, c0, c1) in enumerate(addrs):
-            descs[b].y, descs[b].c0, descs[b].c1 = y or None, c0 or None, c1 or None
-        if keep is not None:
-            self._keep_in = keep
-        self._chk(self._L.cf_forward_yuv(self._h, f, descs, 1 if on_device else 0, len(addrs), h, w, y_pitch, c_pitch))
-        self.last_B = len(addrs)
+            B, self._last.keep = len(arrs), arrs
+        self._chk(self._L.cf_forward_yuv(self._h, f, tab, 1 if on_device else 0, B, h, w, w if y_pitch is None else int(y_pitch),
+                                         cp if c_pitch is None else int(c_pitch)))
+        self.last_B = B
 
     def forward_images_enqueue(self, images, upload_only=False):
         """The batch as a LIST of uint8 [h,w,3] BGR arrays of one common size (``cf_forward_images``): one asynchronous DMA per
@@ -223,19 +222,19 @@ class Engine(object):
                 raise ValueError("images must be uint8 [h,w,3] arrays of one common size, got %s %s (first: %s)" % (a.dtype, a.shape, shp))
         arrs = [a if a.flags["C_CONTIGUOUS"] else np.ascontiguousarray(a) for a in arrs]
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        self._keep_in = arrs
+        self._last.keep = arrs
         self._chk((self._L.cf_upload_images if upload_only else self._L.cf_forward_images)(self._h, ptrs, len(arrs), int(shp[0]), int(shp[1])))
         if upload_only:
-            self._uploaded_B = len(arrs)
+            self._last.uploaded_B = len(arrs)
         else:
             self.last_B = len(arrs)
 
     def _upload_addrs(self, addrs, h, w, keep):
         """``upload_images`` for callers that have validated the batch already (CenterFaceBuckets: one raw size per chunk, page-locked
         uint8 arrays): the host addresses go straight into the pointer table."""
-        self._keep_in = keep
+        self._last.keep = keep
         self._chk(self._L.cf_upload_images(self._h, (C.c_void_p * len(addrs))(*addrs), len(addrs), int(h), int(w)))
-        self._uploaded_B = len(addrs)
+        self._last.uploaded_B = len(addrs)
 
     def upload_images(self, images):
         """First half of ``forward_images_enqueue`` (``cf_upload_images``): only the host -> device copies are enqueued."""
@@ -244,7 +243,7 @@ class Engine(object):
     def forward_uploaded(self):
         """Second half (``cf_forward_uploaded``): resize + forward on what the last ``upload_images`` brought over."""
         self._chk(self._L.cf_forward_uploaded(self._h))
-        self.last_B = self._uploaded_B
+        self.last_B = self._last.uploaded_B
 
     def set_rescale(self, scale_h=0.0, scale_w=0.0):
         """centerface.py:55-62 on the device (``cf_set_rescale``): the threshold decodes of this engine return
@@ -314,17 +313,18 @@ class Engine(object):
         mode "d2" = eval_widerface.decode (eval_widerface.py:92-110): threshold honoured, offsets used.
         ``size`` = (h, w) the boxes are clamped to (default: the engine's input size)."""
         ih, iw = (self.H, self.W) if size is None else (int(size[0]), int(size[1]))
-        B = self.last_B
-        while True:
-            dets = np.empty((B, max_out, 5), np.float32)
-            lms = np.empty((B, max_out, 10), np.float32)
-            counts = np.empty((B,), np.int32)
-            self._chk(self._L.cf_decode_threshold_sized(self._h, {"d1": 0, "d2": 1}[mode], float(score_thresh), float(nms_thresh),
-                                                        ih, iw, int(max_out), _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts)))
-            if int(counts.max(initial=0)) <= max_out:
-                break
-            max_out = int(counts.max())          # more survivors than rows: the reference keeps them all, so do we
-        self._last_kept = int(counts.sum())      # align_faces sizes its buffers from it
+        return self._rows(self.last_B, max_out, lambda cap, dets, lms, counts: self._L.cf_decode_threshold_sized(
+            self._h, {"d1": 0, "d2": 1}[mode], float(score_thresh), float(nms_thresh), ih, iw, cap, _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts)))
+
+    def _rows(self, B, max_out, call):
+        """Per-image (dets [n,5], lms [n,10]) of ``call(cap, dets, lms, counts)`` -- the threshold decode or the tile merge -- on host
+        buffers of ``max_out`` rows per image, grown until every image's rows fit; remembers how many rows were kept."""
+        def run(cap):
+            dets, lms, counts = np.empty((B, cap, 5), np.float32), np.empty((B, cap, 10), np.float32), np.empty((B,), np.int32)
+            self._chk(call(cap, dets, lms, counts))
+            return (dets, lms, counts), int(counts.max(initial=0))
+        dets, lms, counts = _grown(int(max_out), run)
+        self._last.kept = int(counts.sum())
         return [(dets[b, :counts[b]].copy(), lms[b, :counts[b]].copy()) for b in range(B)]
 
     # -- aligned face chips -------------------------------------------------------------------
@@ -337,23 +337,18 @@ class Engine(object):
         network-input maps, zero where a face could not be aligned).  ``max_faces`` caps N (offsets[-1] still tells the number
         wanted); by default the buffers are sized from the decode's counts and grown if that was short."""
         o, tm, shape, dtype = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
-        return self._align_grow(self.last_B, shape, dtype, max_faces, lambda chips, mats, offs, cap: self._L.cf_align_faces(
+        return self._chips(self.last_B, shape, dtype, max_faces, lambda chips, mats, offs, cap: self._L.cf_align_faces(
             self._h, C.byref(o), _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
 
-    def _align_grow(self, B, shape, dtype, max_faces, call):
-        """(chips, offsets, matrices) of ``call(chips, mats, offs, cap)``: host buffers for ``max_faces`` faces, or sized from the
-        decode's counts and grown once the offsets tell that this was short."""
-        cap = int(getattr(self, "_last_kept", 0)) if max_faces is None else int(max_faces)
-        while True:
-            chips = np.empty((max(cap, 1),) + shape, dtype)
-            mats = np.empty((max(cap, 1), 6), np.float64)
-            offs = np.zeros((B + 1,), np.int32)
+    def _chips(self, B, shape, dtype, max_faces, call):
+        """(chips, offsets, matrices) of ``call(chips, mats, offs, cap)``: host buffers for ``max_faces`` faces, or sized from the rows
+        the last decode or merge kept and grown once the offsets tell that this was short."""
+        def run(cap):
+            chips, mats, offs = np.empty((max(cap, 1),) + shape, dtype), np.empty((max(cap, 1), 6), np.float64), np.zeros((B + 1,), np.int32)
             self._chk(call(chips, mats, offs, cap))
-            if max_faces is not None or int(offs[-1]) <= cap:
-                break
-            cap = int(offs[-1])
-        n = min(int(offs[-1]), cap)
-        return chips[:n], offs, mats[:n]
+            n = min(int(offs[-1]), cap)
+            return (chips[:n], offs, mats[:n]), 0 if max_faces is not None else int(offs[-1])
+        return _grown(self._last.kept if max_faces is None else int(max_faces), run)
 
     def align_faces_device(self, chips_ptr, offsets_ptr, cap_faces, matrices_ptr=None, size=112, *, out="u8", rgb=False, mean=0.0,
                            scale=1.0, template=None, max_per_image=0):
@@ -372,12 +367,10 @@ class Engine(object):
         w / W, h / H in float64 (whatever ``set_rescale`` says), B the forward's batch; behind ``forward_tiles_enqueue`` +
         ``merge_tiles`` they are the merged rows, B the number of frames.  Returns (chips, offsets [B+1], matrices [N,6] chip -> frame
         pixel maps)."""
-        tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+        args, keep = _lib.host_frame_args(frames, fmt, writable=False)
         o, tm, shape, dtype = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
-        res = self._align_grow(B, shape, dtype, max_faces, lambda chips, mats, offs, cap: self._L.cf_align_faces_frame(
-            self._h, C.byref(o), _lib.frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1, _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
-        del keep
-        return res
+        return self._chips(args[3], shape, dtype, max_faces, lambda chips, mats, offs, cap: self._L.cf_align_faces_frame(
+            self._h, C.byref(o), *args, _lib.ptr(chips), _lib.ptr(mats), _lib.ptr(offs), cap, 0))
 
     def align_faces_frame_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1, chips_ptr, offsets_ptr, cap_faces, matrices_ptr=None,
                                  size=112, *, out="u8", rgb=False, mean=0.0, scale=1.0, template=None, max_per_image=0):
@@ -385,12 +378,9 @@ class Engine(object):
         ``redact_faces_device`` takes them (addresses and pitches multiples of 4) -- and writing caller-owned DEVICE buffers as
         ``align_faces_device`` does.  Asynchronous on the engine's main stream behind the decode or the merge; no count is read on
         the host."""
-        if int(B) != len(plane_ptrs):
-            raise ValueError("align_faces_frame_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
-        tab = _lib.device_planes(plane_ptrs)
+        args = _lib.device_frame_args("align_faces_frame_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1)
         o, tm, _, _ = _lib.align_opts(size, out, rgb, mean, scale, template, max_per_image)
-        self._chk(self._L.cf_align_faces_frame(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1),
-                                               C.c_void_p(int(chips_ptr)), C.c_void_p(int(matrices_ptr)) if matrices_ptr else None,
+        self._chk(self._L.cf_align_faces_frame(self._h, C.byref(o), *args, C.c_void_p(int(chips_ptr)), C.c_void_p(int(matrices_ptr)) if matrices_ptr else None,
                                                C.c_void_p(int(offsets_ptr)), int(cap_faces), 1))      # (the template is read during the call)
 
     # -- face redaction in the source frame ------------------------------------------------------
@@ -403,42 +393,35 @@ class Engine(object):
         A face's box is grown about its centre by ``scale``; ``shape`` 'rect' covers it, 'ellipse' the ellipse inscribed in it;
         ``mode`` 'solid' writes ``fill`` (bytes in the frame's channel order), 'mosaic' the mean of the ``cell`` x ``cell`` cell of a
         grid anchored at the frame origin, taken from the untouched frame."""
-        tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
-        o = _lib.redact_opts(mode, shape, cell, scale, fill)
-        self._chk(self._L.cf_redact_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1))
-        del keep
-        return frames
+        return self._cover(self._L.cf_redact_faces, _lib.host_frame_args(frames, fmt), lambda: _lib.redact_opts(mode, shape, cell, scale, fill), frames)
 
     def redact_faces_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1=0, *, mode="mosaic", shape="ellipse", cell=20, scale=1.3,
                             fill=(0, 0, 0)):
         """Same, in place on DEVICE planes -- a decoder's surfaces: ``plane_ptrs`` = B tuples (p0, p1, p2) of device addresses (BGR: p0
         only; NV12 / NV21: Y and the interleaved plane; I420 / YV12: three planes), addresses and pitches multiples of 4.  Asynchronous
         on the engine's main stream behind the decode; no count is read on the host."""
-        if int(B) != len(plane_ptrs):
-            raise ValueError("redact_faces_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
-        tab = _lib.device_planes(plane_ptrs)
-        o = _lib.redact_opts(mode, shape, cell, scale, fill)
-        self._chk(self._L.cf_redact_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1)))
+        self._cover(self._L.cf_redact_faces, (_lib.device_frame_args("redact_faces_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1), None),
+                    lambda: _lib.redact_opts(mode, shape, cell, scale, fill))
+
+    def _cover(self, fn, frame_args, opts, frames=None):
+        """The body of the redact and blur pairs: ``frame_args`` = (the frame arguments, what to keep alive) of the host or the device
+        planes, then the options struct of ``opts()``, then the one ABI call; returns ``frames``."""
+        o = opts()
+        self._chk(fn(self._h, C.byref(o), *frame_args[0]))
+        return frames
 
     def blur_faces(self, frames, fmt="bgr", *, shape="ellipse", radius=0, scale=1.3):
         """Blur, in ``frames``, the faces the preceding ``decode_threshold`` kept (``cf_blur_faces``, blocking form): frames, formats and
         faces as ``redact_faces``; copied up, blurred on the device and copied back IN PLACE, and returned.  A covered sample becomes the
         box * box * box filtered value (width 2r+1 each, sigma about r) of the untouched frame; ``radius`` = r in 1..24, or 0 for a
         per-face r of an eighth of the box's smaller side (at most 24)."""
-        tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
-        o = _lib.blur_opts(shape, radius, scale)
-        self._chk(self._L.cf_blur_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 0, B, h, w, pitch0, pitch1))
-        del keep
-        return frames
+        return self._cover(self._L.cf_blur_faces, _lib.host_frame_args(frames, fmt), lambda: _lib.blur_opts(shape, radius, scale), frames)
 
     def blur_faces_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1=0, *, shape="ellipse", radius=0, scale=1.3):
         """Same, in place on DEVICE planes as ``redact_faces_device`` takes them: asynchronous on the engine's main stream behind the
         decode; no count is read on the host."""
-        tab = _lib.device_planes(plane_ptrs)
-        o = _lib.blur_opts(shape, radius, scale)
-        if int(B) != len(plane_ptrs):
-            raise ValueError("blur_faces_device: %d plane tuples for B=%d" % (len(plane_ptrs), B))
-        self._chk(self._L.cf_blur_faces(self._h, C.byref(o), _lib.frame_format(fmt), tab, 1, int(B), int(h), int(w), int(pitch0), int(pitch1)))
+        self._cover(self._L.cf_blur_faces, (_lib.device_frame_args("blur_faces_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1), None),
+                    lambda: _lib.blur_opts(shape, radius, scale))
 
     def cover_faces(self, frames, fmt="bgr", **options):
         """``blur_faces`` when ``options`` say ``mode='blur'`` (shape, radius, scale), otherwise ``redact_faces``."""
@@ -459,21 +442,14 @@ class Engine(object):
             if h is None or w is None:
                 raise ValueError("forward_tiles_enqueue(on_device=True) needs h and w")
             h, w = int(h), int(w)
-            tab = (_lib.PlanesRW * max(len(frames), 1))()
-            for b, t in enumerate(frames):
-                t = (tuple(t) if isinstance(t, (tuple, list)) else (t,)) + (None, None)
-                tab[b].p0, tab[b].p1, tab[b].p2 = (int(v) if v else None for v in t[:3])
-            B, keep = len(frames), None
-            il = f in (_lib.CF_YUV_NV12, _lib.CF_YUV_NV21)
+            tab, B = _lib.device_planes(frames), len(frames)
             pitch0 = (3 * w if f == _lib.CF_FRAME_BGR else w) if pitch0 is None else int(pitch0)
-            pitch1 = (0 if f == _lib.CF_FRAME_BGR else w if il else w // 2) if pitch1 is None else int(pitch1)
+            pitch1 = (0 if f == _lib.CF_FRAME_BGR else _lib.yuv_dense_geometry(f, h, w)[1]) if pitch1 is None else int(pitch1)
         else:
-            tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
-            self._keep_in = keep
+            tab, B, h, w, pitch0, pitch1, self._last.keep = _lib.frame_planes(frames, fmt, writable=False)
         self._chk(self._L.cf_forward_tiles(self._h, f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, rt, T))
         self.last_B = B * T
-        self._tiles = (B, T)
-        self._tiled_last = True
+        self._last.tiles = (B, T)
 
     def merge_tiles(self, metric="ios", thresh=0.5, edge=2.0, max_out=1024):
         """Per-frame detections of the last tiled forward (``cf_merge_tiles``, host form): the rows the preceding ``decode_threshold``
@@ -483,19 +459,11 @@ class Engine(object):
         with ``metric`` 'ios' (intersection over the smaller box) or 'iou' at ``thresh``.  Returns (results, flags): a list of (dets
         [n,5], lms [n,10]) per frame and int32 [Bf], bit 0 set where a tile's decode was truncated by its ``max_out``.  IoS 0.5 and
         edge 2 are this project's defaults, not the reference's."""
-        Bf = getattr(self, "_tiles", (1, 1))[0]                          # (without a tiled forward the library refuses: CF_ESTATE)
+        Bf = (self._last.tiles or (1, 1))[0]                             # (without a tiled forward the library refuses: CF_ESTATE)
         o = _lib.merge_opts(metric, thresh, edge)
-        max_out = int(max_out)
-        while True:
-            dets = np.empty((Bf, max_out, 5), np.float32)
-            lms = np.empty((Bf, max_out, 10), np.float32)
-            counts = np.empty((Bf,), np.int32)
-            flags = np.empty((Bf,), np.int32)
-            self._chk(self._L.cf_merge_tiles(self._h, C.byref(o), max_out, _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts), _lib.ptr(flags), 0))
-            if int(counts.max(initial=0)) <= max_out:
-                break
-            max_out = int(counts.max())          # more survivors than rows: keep them all, as decode_threshold does
-        return [(dets[b, :counts[b]].copy(), lms[b, :counts[b]].copy()) for b in range(Bf)], flags
+        flags = np.empty((Bf,), np.int32)
+        return self._rows(Bf, max_out, lambda cap, dets, lms, counts: self._L.cf_merge_tiles(
+            self._h, C.byref(o), cap, _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts), _lib.ptr(flags), 0)), flags
 
     def merge_tiles_device(self, max_out, dets_ptr=None, lms_ptr=None, counts_ptr=None, flags_ptr=None, *, metric="ios", thresh=0.5, edge=2.0):
         """Same, writing into caller-owned DEVICE buffers (dets [Bf,max_out,5], lms [Bf,max_out,10] float32, counts / flags [Bf] int32;
@@ -513,7 +481,7 @@ class Engine(object):
         the tracks held through a dropout (``misses`` > 0: box grown by ``hold_grow`` per missed frame, last-seen landmarks), in slot
         order -- and int32 [B], bit 0 set where a new face found no free slot and was dropped.  Until the next forward, decode or
         merge, ``redact_faces`` / ``blur_faces`` / ``align_faces_frame`` of this engine use these rows."""
-        B = self._tiles[0] if self._tiled_last else self.last_B
+        B = self._last.tiles[0] if self._last.tiles else self.last_B
         M = tracker.max_tracks
         dets = np.empty((B, M, 5), np.float32)
         lms = np.empty((B, M, 10), np.float32)
@@ -917,29 +885,54 @@ class CenterFace(object):
         """Batched ``__call__`` (the shape of eval_widerface.get_detections, :76-90).  The reference's
         decode ignores ``threshold`` and uses 0.3 (centerface.py:77); so does this."""
         del threshold
-        return self._detect_chunks(imgs, lambda results: results)
+        return self._drive(*self._input_form(self.engine, imgs))
 
-    def _detect_chunks(self, imgs, per_chunk):
-        """Forward + threshold decode of ``imgs`` in chunks of ``max_batch``; ``per_chunk(results)`` turns the postprocessed results of
-        a chunk (whose forward and decode are still the engine's last) into the items returned for it."""
+    def _input_form(self, eng, imgs, fmt=None):
+        """(frames, forward): the form in which ``eng`` takes ``imgs`` and the enqueue that takes any slice of them -- 4:2:0 frames
+        (``fmt``) are converted on the device, page-locked images go up as they are (one DMA each, no host copy), a network-sized batch
+        runs as it is, and anything else passes the device's cv2.resize stand-in."""
+        if fmt is not None:
+            return self._yuv_frames(imgs), lambda chunk: eng.forward_yuv_enqueue(chunk, fmt)
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
-        direct = all(is_pinned(im) for im in imgs)                           # page-locked images: one DMA each, no host copy
+        direct = all(is_pinned(im) for im in imgs)
         batch = imgs if direct else np.stack(imgs)                           # one common (h, w) per instance
         identity = batch[0].shape[:2] == (self.img_h_new, self.img_w_new)
-        out = []
-        self.engine.set_rescale(self.scale_h, self.scale_w)                  # centerface.py:55-62 inside the decode kernel
+        return batch, eng.forward_images_enqueue if direct else eng.forward_enqueue if identity else eng.forward_resized_enqueue
+
+    def _decode(self, eng):
+        """The results of the forward last enqueued on ``eng``; the rescale (centerface.py:55-62) was done by the decode kernel."""
+        return self._postprocess_many(eng.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)
+
+    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None):
+        """The chunk loop of every product path: ``forward`` enqueues ``frames`` in slices of ``per`` (default ``max_batch``), each is
+        decoded, and while the engine still holds it the steps that were asked for run in this order: ``tracker`` is advanced -- image b
+        of the chunk that starts at frame i continues its stream i + b --, ``cover`` = (array, fmt, options) has the chunk's slice of
+        the array covered, ``chips(i, j)`` cuts the chips of frames i:j, which join the results.  ``merge`` = (metric, thresh, edge) says
+        that the forward is a tiled one: the tiles' rows are merged, in frame pixels; otherwise the decode rescales, and the rescale is
+        switched off again whatever happens.  Returns the per-frame results."""
+        eng, out = self.engine, []
+        per = per or eng.max_batch
+        if merge is None:
+            eng.set_rescale(self.scale_h, self.scale_w)                      # centerface.py:55-62 inside the decode kernel
         try:
-            for i in range(0, len(batch), self.engine.max_batch):
-                chunk = batch[i:i + self.engine.max_batch]
-                if direct:
-                    self.engine.forward_images_enqueue(chunk)
-                elif identity:
-                    self.engine.forward_enqueue(chunk)
+            for i in range(0, len(frames), per):
+                forward(frames[i:i + per])
+                if merge is None:
+                    res = self._decode(eng)
                 else:
-                    self.engine.forward_resized_enqueue(chunk)               # cv2.resize stand-in, on the device
-                out.extend(per_chunk(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)))
+                    eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
+                    res = self._postprocess_many(eng.merge_tiles(*merge, self.max_dets)[0], rescaled=True)
+                if tracker is not None:
+                    eng.track_update_device(tracker, i)
+                if cover is not None:
+                    eng.cover_faces(cover[0][i:i + per], cover[1], **cover[2])
+                if chips is not None:
+                    cut, offs, _ = chips(i, i + per)
+                    res = [(d, l, cut[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(res)]
+                out.extend(res)
         finally:
-            self.engine.set_rescale(0.0, 0.0)
+            if merge is None:
+                eng.set_rescale(0.0, 0.0)
         return out
 
     def detect_aligned(self, imgs, size=112, **chip_options):
@@ -949,11 +942,7 @@ class CenterFace(object):
         detections gives an empty [0, ...] chip array."""
         if not self.landmarks:
             raise ValueError("detect_aligned needs the landmarks: construct CenterFace(..., landmarks=True)")
-
-        def with_chips(results):
-            chips, offs, _ = self.engine.align_faces(size, **chip_options)
-            return [(d, l, chips[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(results)]
-        return self._detect_chunks(imgs, with_chips)
+        return self._drive(*self._input_form(self.engine, imgs), chips=lambda i, j: self.engine.align_faces(size, **chip_options))
 
     def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, **chip_options):
         """Detection plus the aligned chip of every detection cut from the FRAME ITSELF (``Engine.align_faces_frame``), not from the
@@ -969,37 +958,18 @@ class CenterFace(object):
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         if frames.ndim != (4 if bgr else 3):
             raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (frames.shape,))
-        eng, out = self.engine, []
-
-        def with_chips(chunk, results):
-            chips, offs, _ = eng.align_faces_frame(chunk, fmt, size, **chip_options)
-            return [(d, l, chips[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(results)]
+        eng = self.engine
+        chips = lambda i, j: eng.align_faces_frame(frames[i:j], fmt, size, **chip_options)      # noqa: E731
         if tiled:
-            _, B, h, w, _, _, _ = _lib.frame_planes(frames, fmt, writable=False)
-            rects, per = self._tile_geometry(h, w, tile, overlap, True)
-            for i in range(0, B, per):
-                chunk = frames[i:i + per]
-                eng.forward_tiles_enqueue(chunk, rects, fmt)
-                eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
-                res, _ = eng.merge_tiles(max_out=self.max_dets)
-                eng._last_kept = sum(len(d) for d, _ in res)
-                out.extend(with_chips(chunk, res))
-            return out
+            return self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, True, False), merge=("ios", 0.5, 2.0), chips=chips)
         want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
         if frames.shape[1:] != want:
             raise ValueError("frames must be %s per frame (this instance was built for %dx%d), got %s" % ((want,) + self.src_hw + (frames.shape[1:],)))
-        eng.set_rescale(self.scale_h, self.scale_w)                          # centerface.py:55-62 inside the decode kernel
-        try:
-            for i in range(0, len(frames), eng.max_batch):
-                chunk = frames[i:i + eng.max_batch]
-                eng.forward_resized_enqueue(chunk) if bgr else eng.forward_yuv_enqueue(chunk, fmt)
-                res = self._postprocess_many(eng.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)
-                out.extend(with_chips(chunk, res))
-        finally:
-            eng.set_rescale(0.0, 0.0)
-        return out
+        return self._drive(frames, eng.forward_resized_enqueue if bgr else lambda chunk: eng.forward_yuv_enqueue(chunk, fmt), chips=chips)
 
-    def _tile_geometry(self, h, w, tile, overlap, with_full):
+    def _tiled_form(self, frames, fmt, tile, overlap, with_full, writable):
+        """(forward, frames per chunk) of the tiled paths: the enqueue that cuts any slice of ``frames`` into the tiles of their size."""
+        h, w = _lib.frame_planes(frames, fmt, writable=writable)[2:4]
         th, tw = (self.img_h_new, self.img_w_new) if tile is None else (int(tile), int(tile)) if np.isscalar(tile) else (int(tile[0]), int(tile[1]))
         if overlap is None:
             overlap = (min(th, tw) // 4) & ~1
@@ -1008,7 +978,7 @@ class CenterFace(object):
         per = self.engine.max_batch // len(rects)
         if per < 1:
             raise ValueError("%d tiles per frame need max_batch >= %d (this instance has %d)" % (len(rects), len(rects), self.engine.max_batch))
-        return rects, per
+        return lambda chunk: self.engine.forward_tiles_enqueue(chunk, rects, fmt), per
 
     def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None,
                      tracker=None):
@@ -1026,21 +996,8 @@ class CenterFace(object):
         own."""
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
-        tab, B, h, w, _, _, keep = _lib.frame_planes(frames, fmt, writable=redact is not None)
-        del tab, keep
-        rects, per = self._tile_geometry(h, w, tile, overlap, with_full)
-        out = []
-        for i in range(0, B, per):
-            chunk = frames[i:i + per]
-            self.engine.forward_tiles_enqueue(chunk, rects, fmt)
-            self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets)
-            res, _ = self.engine.merge_tiles(metric, thresh, edge, self.max_dets)
-            if tracker is not None:
-                self.engine.track_update_device(tracker, i)
-            if redact is not None:
-                self.engine.cover_faces(chunk, fmt, **redact)
-            out.extend((d, l) if self.landmarks else d for d, l in res)
-        return out
+        return self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, with_full, redact is not None), merge=(metric, thresh, edge),
+                           tracker=tracker, cover=None if redact is None else (frames, fmt, redact))
 
     def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
@@ -1056,15 +1013,7 @@ class CenterFace(object):
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         if tiled:
             return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker)
-        k = [0]
-
-        def redact(results):
-            if tracker is not None:
-                self.engine.track_update_device(tracker, k[0])
-            self.engine.cover_faces(out[k[0]:k[0] + len(results)], "bgr", **options)
-            k[0] += len(results)
-            return results
-        return out, self._detect_chunks(imgs, redact)
+        return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, cover=(out, "bgr", options))
 
     def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
@@ -1074,21 +1023,9 @@ class CenterFace(object):
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
             return out, self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker)
-        frames = self._yuv_frames(frames)
+        frames, forward = self._input_form(self.engine, frames, fmt)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
-        dets = []
-        self.engine.set_rescale(self.scale_h, self.scale_w)
-        try:
-            for i in range(0, len(out), self.engine.max_batch):
-                chunk = out[i:i + self.engine.max_batch]
-                self.engine.forward_yuv_enqueue(frames[i:i + self.engine.max_batch], fmt)
-                dets.extend(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True))
-                if tracker is not None:
-                    self.engine.track_update_device(tracker, i)
-                self.engine.cover_faces(chunk, fmt, **options)
-        finally:
-            self.engine.set_rescale(0.0, 0.0)
-        return out, dets
+        return out, self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options))
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]
@@ -1111,16 +1048,7 @@ class CenterFace(object):
         the same results as ``detect_batch([cv2.cvtColor(f, cv2.COLOR_YUV2BGR_<fmt>) for f in frames])``, with the conversion on the
         device and half the bytes of BGR over the link.  ``frames``: uint8 [B, height*3//2, width] or a list of [height*3//2, width]
         arrays, (height, width) = the size this instance was built for (ValueError otherwise)."""
-        frames = self._yuv_frames(frames)
-        out = []
-        self.engine.set_rescale(self.scale_h, self.scale_w)                  # centerface.py:55-62 inside the decode kernel
-        try:
-            for i in range(0, len(frames), self.engine.max_batch):
-                self.engine.forward_yuv_enqueue(frames[i:i + self.engine.max_batch], fmt)
-                out.extend(self._postprocess_many(self.engine.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True))
-        finally:
-            self.engine.set_rescale(0.0, 0.0)
-        return out
+        return self._drive(*self._input_form(self.engine, frames, fmt))
 
     def detect_stream(self, imgs, threshold=0.2, *, fmt=None):
         """``__call__`` over an iterable of same-sized images, results yielded in order (the loop of demo.py:30-38 /
@@ -1142,22 +1070,15 @@ class CenterFace(object):
             chunk = [np.asarray(im, dtype=np.uint8) for im in chunk]
             e.set_rescale(self.scale_h, self.scale_w)
             try:
-                if fmt is not None:
-                    return e.forward_yuv_enqueue(self._yuv_frames(chunk), fmt)
-                if all(is_pinned(im) for im in chunk):
-                    return e.forward_images_enqueue(chunk)
-                batch = np.stack(chunk)
-                if batch.shape[1:3] == (self.img_h_new, self.img_w_new):
-                    e.forward_enqueue(batch)
-                else:
-                    e.forward_resized_enqueue(batch)
+                frames, forward = self._input_form(e, chunk, fmt)
+                forward(frames)
             except BaseException:
                 e.set_rescale(0.0, 0.0)                  # the rescale is per-context state: a failed enqueue must not leave it behind
                 raise
 
         def finish(e):
             try:
-                return self._postprocess_many(e.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)
+                return self._decode(e)
             finally:
                 e.set_rescale(0.0, 0.0)
         it, k, pending = iter(imgs), 0, None
@@ -1191,18 +1112,13 @@ class CenterFace(object):
         h, w = hm.shape[2:]
         wh = _lib.f32(scale)
         lm = _lib.f32(landmark) if landmark is not None else np.zeros((1, 10, h, w), np.float32)
-        cap = max(1, min(h * w, 4096))
-        while True:
-            dets = np.empty((1, cap, 5), np.float32)
-            lms = np.empty((1, cap, 10), np.float32)
-            cnt = np.zeros((1,), np.int32)
+        def run(cap):
+            dets, lms, cnt = np.empty((1, cap, 5), np.float32), np.empty((1, cap, 10), np.float32), np.zeros((1,), np.int32)
             _lib.check(L.cf_op_decode_threshold(self.device, _lib.ptr(hm), _lib.ptr(wh), _lib.ptr(lm), 1, h, w,
                                                 int(size[0]), int(size[1]), 0.3, float(self.nms_thresh), cap,
                                                 _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(cnt)), op=True)
-            if int(cnt[0]) <= cap:
-                break
-            cap = int(cnt[0])
-        n = int(cnt[0])
+            return (dets, lms, int(cnt[0])), int(cnt[0])
+        dets, lms, n = _grown(max(1, min(h * w, 4096)), run)
         if n == 0:
             return ([], []) if self.landmarks else []
         return (dets[0, :n].copy(), lms[0, :n].copy()) if self.landmarks else dets[0, :n].copy()

@@ -441,3 +441,60 @@ def test_two_engines_share_one_tracker():
     trk.close()
     for e in engs:
         e.close()
+
+
+def _chunked_by_hand(face, trk, frames, fmt, opt):
+    """anonymize / anonymize_yuv of five frames at max_batch = 2, restated from public Engine calls: image b of the chunk that starts at
+    frame i continues tracker stream i + b."""
+    eng, out, dets = face.engine, np.stack(list(frames)), []
+    eng.set_rescale(face.scale_h, face.scale_w)
+    for i in range(0, len(out), 2):
+        if fmt == "bgr":
+            eng.forward_resized_enqueue(np.stack(list(frames[i:i + 2])))
+        else:
+            eng.forward_yuv_enqueue(frames[i:i + 2], fmt)
+        dets.extend(eng.decode_threshold(0.3, face.nms_thresh, face.max_dets))
+        eng.track_update_device(trk, i)
+        eng.cover_faces(out[i:i + 2], fmt, **opt)
+    eng.set_rescale(0.0, 0.0)
+    return out, dets
+
+
+def test_chunked_anonymize_continues_tracker_stream_i_plus_b():
+    """Five frames through max_batch = 2 (chunks at 0, 2, 4) with a tracker, twice: byte for byte the hand-written chunk loop on a second
+    CenterFace and a second Tracker.  min_hits = 1 holds every face at once, so a chunk fed to the wrong streams would cover other boxes.
+    BGR frames through anonymize, then NV12 frames of 76 x 102 through anonymize_yuv."""
+    for fmt in ("bgr", "nv12"):
+        _check_chunked_anonymize(fmt)
+
+
+def _check_chunked_anonymize(fmt):
+    rng = np.random.default_rng(17)
+    face, face2 = (cfa.CenterFace(75, 101, dtype="bf16", max_batch=2) if fmt == "bgr" else cfa.CenterFace(76, 102, dtype="bf16", max_batch=2) for _ in range(2))
+    tried = []
+    for kind, hw in SOURCES:
+        if fmt == "bgr":
+            frames = list(source_frames(rng, kind, (5,) + hw + (3,)))
+            n = [len(d) for d, _ in face.detect_batch(frames)]
+        else:
+            frames = source_frames(rng, kind, (5, 76 * 3 // 2, 102))
+            n = [len(d) for d, _ in face.detect_yuv(frames, fmt)]
+        tried.append((kind, hw, n))
+        if sum(n) >= 2 and sum(n[2:]) >= 1:
+            break
+    else:
+        raise AssertionError("no source holds two faces, one of them behind the first chunk, with the default weights: %s" % tried)
+    before = np.stack(list(frames))
+    opts = dict(min_hits=1, max_age=3, hold_grow=0.1)
+    trk, trk2 = cfa.Tracker(face.engine, 5, **opts), cfa.Tracker(face2.engine, 5, **opts)
+    opt = dict(mode="solid", shape="rect")
+    for call in range(2):
+        out, dets = face.anonymize(frames, tracker=trk, **opt) if fmt == "bgr" else face.anonymize_yuv(frames, fmt, tracker=trk, **opt)
+        want, want_dets = _chunked_by_hand(face2, trk2, frames, fmt, opt)
+        assert np.array_equal(out, want), call
+        assert len(dets) == len(want_dets) == 5
+        for (d, l), (wd, wl) in zip(dets, want_dets):
+            assert d.shape == wd.shape and l.shape == wl.shape and d.tobytes() == wd.tobytes() and l.tobytes() == wl.tobytes(), call
+        assert np.array_equal(np.stack(list(frames)), before)
+    assert (out[2:] != before[2:]).any()                                     # the second call covered a box behind the first chunk
+    trk.close(), trk2.close(), face.close(), face2.close()

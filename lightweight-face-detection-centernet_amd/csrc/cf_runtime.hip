@@ -76,6 +76,29 @@ struct Buf { std::string name; size_t elems = 0; bool f32 = false; void* p = nul
 
 struct DevBuf { void* p = nullptr; size_t bytes = 0; };      // device scratch that grow() enlarges on demand
 
+// Host inputs.  A call whose copies add up to kCopyStreamBytes or more puts them on the device's copy stream, so that the copy of batch
+// i+1 overlaps the forward of batch i (PCIe-inclusive rate ~ max(copy, compute), not their sum).  Smaller ones (single-image calls: 1.2
+// MB) go on the context's MAIN stream: there is nothing to overlap them with, and the copy stream's event round trip costs 0.3 ms of
+// latency (CenterFace(640,640)(img): 0.81 -> 0.5 ms).
+constexpr size_t kCopyStreamBytes = (size_t)8 << 20;
+inline bool on_copy_stream(size_t bytes) { return bytes >= kCopyStreamBytes; }
+
+// The two network-sized input slots (in_slot_begin ... in_slot_done): buf = their entries in cf_ctx::bufs ("input": u8 HWC or f32 NCHW;
+// "input2": u8 only), ev_copy[i] = behind the copy-stream copies into slot i, ev_free[i] = behind the last reader of slot i (a forward's
+// stem, cf_align_faces) once busy[i]; next alternates the slot of the copy-stream batches, used = the slot the coming forward reads or -1.
+struct InSlots {
+    int buf[2] = {-1, -1}, next = 0, used = -1;
+    hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}; bool busy[2] = {false, false};
+};
+// Where one host batch goes (in_slot_begin): the slot, its address, the stream of the copies and whether that is the copy stream; after =
+// ev_free[slot] while the slot has a reader in flight (cs waits for it already; a second copy stream has to as well), else nullptr
+struct InSlotUse { int slot; void* dst; hipStream_t cs; bool on_copy; hipEvent_t after; };
+
+// Source frames of the host forms that do not feed the network as they are (another size, 4:2:0, tiles): filled by the copies, read by
+// ONE kernel on the main stream that writes input_resized (src_stage_begin ... src_stage_read).  ev_copy = behind the copy-stream
+// copies, ev_free = behind the last reader once busy.
+struct SrcStage { DevBuf buf; hipEvent_t ev_copy = nullptr, ev_free = nullptr; bool busy = false; };
+
 // The face rows a consumer reads, whichever producer wrote them: dets [.][stride][5] (the score column is dets + 4, stride 5), corners
 // [.][stride][4], lms [.][stride][10], counts [B]; in the pixels of an H x W network input or -- frame_space -- of the H x W frames of a
 // tiled forward.  RowStage: the newest producer behind the last forward.
@@ -94,13 +117,14 @@ struct cf_ctx {
     std::vector<Buf> bufs;
     std::vector<Op> ops;
     std::vector<void*> owned;                 // device allocations to free
-    int buf_in = -1, buf_heads = -1, buf_resized = -1;
-    // host inputs: H2D copies run on their own stream into two alternating staging buffers, so the copy of
-    // batch i+1 overlaps the forward of batch i (PCIe-inclusive rate ~ max(copy, compute), not their sum)
-    hipStream_t stream_in = nullptr, stream_in2 = nullptr; hipEvent_t ev_copy2 = nullptr; int buf_in2 = -1; int in_slot = 0; int in_slot_used = -1;
-    struct Upload { bool pending; int B, h, w, slot; bool small, dual; } up = {false, 0, 0, 0, 0, false, false};      // cf_upload_images -> cf_forward_uploaded
-    hipEvent_t ev_src_copy = nullptr, ev_src_free = nullptr; bool src_busy = false;     // src_stage: filled on stream_in, read by the resize on stream
-    hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_slot_free[2] = {nullptr, nullptr}; bool slot_busy[2] = {false, false};
+    int buf_heads = -1, buf_resized = -1;
+    // host inputs (kCopyStreamBytes): the device's copy stream -- and its second one, with the event behind ITS copies (cf_upload_images) --
+    // the two network-sized slots and the source-frame staging buffer
+    hipStream_t stream_in = nullptr, stream_in2 = nullptr; hipEvent_t ev_copy2 = nullptr;
+    InSlots in; SrcStage src;
+    // cf_upload_images -> cf_forward_uploaded: slot = the input slot the images sit in, -1 = in src; on_copy / dual: their copies went on the
+    // copy stream / on both copy streams
+    struct Upload { bool pending; int B, h, w, slot; bool on_copy, dual; } up = {false, 0, 0, 0, 0, false, false};
     bool weights_loaded = false;
     int last_B = 0;
     std::string err;
@@ -113,7 +137,7 @@ struct cf_ctx {
     hipEvent_t ev_seg1 = nullptr, ev_seg2 = nullptr; bool seg2_recorded = false;
     bool lane_pending = false; const void* lane_in = nullptr; int lane_fmt = 0, lane_B = 0; int lane_cut1 = -1, lane_cut2 = -1;
     hipEvent_t ev_gather = nullptr; bool gather_pending = false;       // the last all-gather still reads d_rec (communicator's stream)
-    float* hm_plane = nullptr; double* d_trans = nullptr; uint8_t* src_stage = nullptr; size_t src_stage_bytes = 0;
+    float* hm_plane = nullptr; double* d_trans = nullptr;
     float* d_dets = nullptr; float* d_lms = nullptr; long long* d_inds = nullptr; int decK = 0;
     float* t_cand = nullptr; int* t_count = nullptr; int* t_order = nullptr; unsigned long long* t_mask = nullptr; int t_B = 0;
     float* t_dets = nullptr; float* t_lms = nullptr; int* t_counts = nullptr; int* t_overflow = nullptr;
@@ -585,18 +609,18 @@ int cf_create(int device, int max_batch, int H, int W, int dtype, uint32_t flags
     if ((e = hipEventCreateWithFlags(&c->ev_fwd, hipEventDisableTiming)) != hipSuccess) return bail(CF_EHIP, "hipEventCreate", e);
     if ((e = acquire_copy_stream(c->device, &c->stream_in)) != hipSuccess) return bail(CF_EHIP, "hipStreamCreate", e);
     for (int i = 0; i < 2; ++i) {
-        if ((e = hipEventCreateWithFlags(&c->ev_copy[i], hipEventDisableTiming)) != hipSuccess) return bail(CF_EHIP, "hipEventCreate", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_slot_free[i], hipEventDisableTiming)) != hipSuccess) return bail(CF_EHIP, "hipEventCreate", e);
+        if ((e = hipEventCreateWithFlags(&c->in.ev_copy[i], hipEventDisableTiming)) != hipSuccess) return bail(CF_EHIP, "hipEventCreate", e);
+        if ((e = hipEventCreateWithFlags(&c->in.ev_free[i], hipEventDisableTiming)) != hipSuccess) return bail(CF_EHIP, "hipEventCreate", e);
     }
     if ((e = hipEventCreateWithFlags(&c->ev_dec, hipEventDisableTiming)) != hipSuccess) return bail(CF_EHIP, "hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&c->ev_main_dec, hipEventDisableTiming)) != hipSuccess) return bail(CF_EHIP, "hipEventCreate", e);
     for (auto& ev : c->events) if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(CF_EHIP, "hipEventCreate", e);
     build_plan(c);
     // input staging: the larger of u8 HWC and f32 NCHW
-    c->buf_in = add_buf(c, "input", true);
-    need(c, c->buf_in, (size_t)3 * H * W);
-    c->buf_in2 = add_buf(c, "input2", false);
-    need(c, c->buf_in2, ((size_t)3 * H * W + elem_size(dtype) - 1) / elem_size(dtype));     // 3*H*W BYTES per image (u8 only)
+    c->in.buf[0] = add_buf(c, "input", true);
+    need(c, c->in.buf[0], (size_t)3 * H * W);
+    c->in.buf[1] = add_buf(c, "input2", false);
+    need(c, c->in.buf[1], ((size_t)3 * H * W + elem_size(dtype) - 1) / elem_size(dtype));     // 3*H*W BYTES per image (u8 only)
     // cf_forward_resized writes here (not into a host-input staging slot: those belong to the copy stream's protocol)
     c->buf_resized = add_buf(c, "input_resized", false);
     need(c, c->buf_resized, ((size_t)3 * H * W + elem_size(dtype) - 1) / elem_size(dtype));
@@ -622,10 +646,8 @@ int cf_destroy(cf_ctx* c) {
     if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); }
     if (c->ev_fwd) hipEventDestroy(c->ev_fwd);
     if (c->stream_in) { hipStreamSynchronize(c->stream_in); if (c->stream_in2) hipStreamSynchronize(c->stream_in2); release_copy_stream(c->device); }
-    for (int i = 0; i < 2; ++i) { if (c->ev_copy[i]) hipEventDestroy(c->ev_copy[i]); if (c->ev_slot_free[i]) hipEventDestroy(c->ev_slot_free[i]); }
-    if (c->ev_copy2) hipEventDestroy(c->ev_copy2);
-    if (c->ev_src_copy) hipEventDestroy(c->ev_src_copy);
-    if (c->ev_src_free) hipEventDestroy(c->ev_src_free);
+    for (hipEvent_t ev : {c->in.ev_copy[0], c->in.ev_copy[1], c->in.ev_free[0], c->in.ev_free[1], c->ev_copy2, c->src.ev_copy, c->src.ev_free})
+        if (ev) hipEventDestroy(ev);
     if (c->ev_dec) hipEventDestroy(c->ev_dec);
     if (c->ev_gather) { hipEventSynchronize(c->ev_gather); hipEventDestroy(c->ev_gather); }
     if (c->ev_main_dec) hipEventDestroy(c->ev_main_dec);
@@ -633,11 +655,11 @@ int cf_destroy(cf_ctx* c) {
     if (c->ev_seg2) hipEventDestroy(c->ev_seg2);
     for (auto& b : c->bufs) if (b.p) hipFree(b.p);
     for (void* p : c->owned) hipFree(p);
-    for (void* p : {(void*)c->src_stage, (void*)c->d_trans, (void*)c->hm_plane, (void*)c->keys, (void*)c->key_count, (void*)c->big, (void*)c->d_slot, (void*)c->d_dets, (void*)c->d_lms, (void*)c->d_inds, (void*)c->t_cand, (void*)c->t_count,
+    for (void* p : {(void*)c->d_trans, (void*)c->hm_plane, (void*)c->keys, (void*)c->key_count, (void*)c->big, (void*)c->d_slot, (void*)c->d_dets, (void*)c->d_lms, (void*)c->d_inds, (void*)c->t_cand, (void*)c->t_count,
                     (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow,
                     (void*)c->t_lmsnet, (void*)c->al_off, (void*)c->t_detsnet})
         if (p) hipFree(p);
-    for (const DevBuf* b : {&c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->tl_rects_dev,
+    for (const DevBuf* b : {&c->src.buf, &c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->tl_rects_dev,
                             &c->tl.cand, &c->tl.cand_count, &c->tl.order, &c->tl.mask, &c->tl.dets, &c->tl.lms, &c->tl.corners, &c->tl.counts, &c->tl.flags,
                             &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags})
         if (b->p) hipFree(b->p);
@@ -940,40 +962,44 @@ double op_bytes(const cf_ctx* c, const Op& op, int in_format, int B) {
     return (in_b + out_b) * B;
 }
 
-int stage_input(cf_ctx* c, const void* in, int in_format, int in_on_device, int B, const void** net_in) {
-    if (!c->weights_loaded) return c->fail(CF_ESTATE, "cf_forward before cf_load_weights");
-    if (!in || B < 1 || B > c->max_batch) return c->fail(CF_EINVAL, "cf_forward: B=%d outside [1, %d] or null input", B, c->max_batch);
-    if (in_format != CF_IN_U8_HWC_BGR && in_format != CF_IN_F32_NCHW) return c->fail(CF_EINVAL, "unknown input format %d", in_format);
-    HIPCHK(c, hipSetDevice(c->device));
-    *net_in = in;
-    if (in_on_device && (reinterpret_cast<uintptr_t>(in) & 3))
-        return c->fail(CF_EINVAL, "cf_forward: device input must be 4-byte aligned (the stem reads it as dwords)");
-    if (!in_on_device) {
-        size_t bytes = (size_t)B * 3 * c->H * c->W * (in_format == CF_IN_U8_HWC_BGR ? 1 : 4);
-        // only the u8 format fits the second staging buffer; f32 NCHW input (tests) keeps the single buffer
-        const bool two = in_format == CF_IN_U8_HWC_BGR;
-        if (bytes < ((size_t)8 << 20)) {
-            // small batches (single-image calls: 1.2 MB): the copy goes on the MAIN stream into slot 0 -- there is nothing to
-            // overlap it with, and the copy stream's event round trip costs 0.3 ms of latency (CenterFace(640,640)(img):
-            // 0.81 -> 0.5 ms).  Stream order covers earlier forwards; a later copy-stream transfer into slot 0 waits for
-            // ev_slot_free[0] like after any other forward.
-            void* dst = c->bufs[c->buf_in].p;
-            if (c->slot_busy[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_slot_free[0], 0));
-            HIPCHK(c, hipMemcpyAsync(dst, in, bytes, hipMemcpyHostToDevice, c->stream));
-            c->in_slot_used = 0;
-            *net_in = dst;
-            return CF_OK;
-        }
-        const int slot = two ? (c->in_slot ^= 1) : 0;
-        void* dst = c->bufs[slot == 0 ? c->buf_in : c->buf_in2].p;
-        if (c->slot_busy[slot]) HIPCHK(c, hipStreamWaitEvent(c->stream_in, c->ev_slot_free[slot], 0));   // its last reader (a stem) is done
-        HIPCHK(c, hipMemcpyAsync(dst, in, bytes, hipMemcpyHostToDevice, c->stream_in));
-        HIPCHK(c, hipEventRecord(c->ev_copy[slot], c->stream_in));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy[slot], 0));
-        c->in_slot_used = slot;
-        *net_in = dst;
-    }
+// The network-sized input slots, one function per half of their protocol.  Producer: where a host batch of `bytes` goes and on which
+// stream -- below the rule slot 0 on the main stream (stream order covers earlier forwards; a later copy-stream transfer into slot 0
+// waits for ev_free[0] like after any other forward), from it on the copy stream and, when the format fits both slots (`two`: u8; f32
+// NCHW input -- tests -- keeps the single buffer), the slot the copy-stream batch before did not take -- and that stream waits for the
+// slot's last reader.  main_only: A/B, every batch on the main stream.
+int in_slot_begin(cf_ctx* c, size_t bytes, bool two, bool main_only, InSlotUse& u) {
+    InSlots& s = c->in;
+    u.on_copy = !main_only && on_copy_stream(bytes);
+    u.slot = u.on_copy && two ? (s.next ^= 1) : 0;
+    u.dst = c->bufs[s.buf[u.slot]].p;
+    u.cs = u.on_copy ? c->stream_in : c->stream;
+    u.after = s.busy[u.slot] ? s.ev_free[u.slot] : nullptr;
+    if (u.after) HIPCHK(c, hipStreamWaitEvent(u.cs, u.after, 0));
     return CF_OK;
+}
+// ... and behind its copies
+int in_slot_copied(cf_ctx* c, const InSlotUse& u) {
+    if (u.on_copy) HIPCHK(c, hipEventRecord(c->in.ev_copy[u.slot], u.cs));
+    return CF_OK;
+}
+// Consumer: the coming forward reads `slot`; the main stream waits for copies that went on the copy stream.  Returns the slot's address.
+int in_slot_consume(cf_ctx* c, int slot, bool on_copy, const void** net_in) {
+    if (on_copy) HIPCHK(c, hipStreamWaitEvent(c->stream, c->in.ev_copy[slot], 0));
+    c->in.used = slot;
+    *net_in = c->bufs[c->in.buf[slot]].p;
+    return CF_OK;
+}
+// Release: the main stream has one more reader of `slot` in it ...
+int in_slot_release(cf_ctx* c, int slot) {
+    HIPCHK(c, hipEventRecord(c->in.ev_free[slot], c->stream));
+    c->in.busy[slot] = true;
+    return CF_OK;
+}
+// ... the stem of the forward that in_slot_consume announced, if one did
+int in_slot_done(cf_ctx* c) {
+    const int slot = c->in.used;
+    c->in.used = -1;
+    return slot >= 0 ? in_slot_release(c, slot) : CF_OK;
 }
 
 // get_affine_transform(center, scale, rot=0, output_size=(out_w, out_h), inv=1) (utils/image.py:27-60):
@@ -1112,10 +1138,11 @@ hipError_t launch_plan_at(cf_ctx* c, size_t i, const void* net_in, int in_format
     return launch_op(c, op, net_in, in_format, B);
 }
 
-int launch_all_ops(cf_ctx* c, const void* net_in, int in_format, int B) {
+// The tail of every forward entry point: the plan on the main stream, reading B images of in_format at net_in
+int forward_run(cf_ctx* c, const void* net_in, int in_format, int B) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
-    c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in_slot_used;      // what cf_align_faces samples
+    c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in.used;      // what cf_align_faces samples
     c->stage = ROWS_NONE; c->tl_T = 0;                    // (cf_forward_tiles sets its state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
@@ -1130,12 +1157,84 @@ int launch_all_ops(cf_ctx* c, const void* net_in, int in_format, int B) {
         i += used;
     }
     HIPCHK(c, hipEventRecord(c->ev_fwd, c->stream));
-    if (c->in_slot_used >= 0) {                     // this forward read a host-input staging slot: mark when it is free again
-        HIPCHK(c, hipEventRecord(c->ev_slot_free[c->in_slot_used], c->stream));
-        c->slot_busy[c->in_slot_used] = true;
-        c->in_slot_used = -1;
-    }
+    if (int r = in_slot_done(c)) return r;          // this forward read a host-input slot: mark when it is free again
+    c->last_B = B;
     return CF_OK;
+}
+
+// Device scratch that only grows: b holds at least need_bytes afterwards, or nothing (CF_ENOMEM / CF_EHIP)
+int grow(cf_ctx* c, DevBuf& b, size_t need_bytes, const char* what, const char* who) {
+    if (b.bytes >= need_bytes) return CF_OK;
+    if (b.p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(b.p); }        // earlier launches may still use it
+    b = DevBuf{};
+    const hipError_t e = hipMalloc(&b.p, need_bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "%s: %zu bytes of %s: %s", who, need_bytes, what, hipGetErrorString(e)); }
+    b.bytes = need_bytes;
+    return CF_OK;
+}
+
+// The source-frame staging buffer, one function per half of its protocol.  Its copies follow the rule of the input slots, and the large
+// ones go on the device's ONE copy stream like theirs: with several contexts in flight (CenterFaceBuckets: one per network shape) copies
+// issued on each context's own stream share the PCIe link, ALL finish late and no forward can start under them; queued on one stream
+// the first chunk is complete after 1/n of the time and its forward runs under the other copies.
+// Producer: src holds `bytes` and u.cs, the stream of the copies, waits for the buffer's last reader; u.after = that reader's event
+// where a second copy stream has to wait for it as well.  (A main-stream copy stands behind the reader in stream order.)
+struct SrcUse { hipStream_t cs; bool on_copy; hipEvent_t after; };
+int src_stage_begin(cf_ctx* c, const char* who, size_t bytes, SrcUse& u) {
+    SrcStage& s = c->src;
+    if (!s.ev_copy) HIPCHK(c, hipEventCreateWithFlags(&s.ev_copy, hipEventDisableTiming));
+    if (!s.ev_free) HIPCHK(c, hipEventCreateWithFlags(&s.ev_free, hipEventDisableTiming));
+    if (s.buf.bytes < bytes) {
+        // grow() waits for the main stream -- the readers -- before it frees.  The copy streams may still be WRITING the buffer (an upload
+        // nobody ran), so they are drained first; they are the device's, this waits for other contexts' copies too, as hipFree does.
+        if (s.buf.p) {
+            HIPCHK(c, hipStreamSynchronize(c->stream_in));
+            if (c->stream_in2) HIPCHK(c, hipStreamSynchronize(c->stream_in2));
+        }
+        s.busy = false;
+        if (int r = grow(c, s.buf, bytes, "source-frame staging", who)) return r;
+    }
+    u.on_copy = on_copy_stream(bytes);
+    u.cs = u.on_copy ? c->stream_in : c->stream;
+    u.after = s.busy && u.on_copy ? s.ev_free : nullptr;
+    if (u.after) HIPCHK(c, hipStreamWaitEvent(u.cs, u.after, 0));
+    return CF_OK;
+}
+// ... and behind its copies
+int src_stage_copied(cf_ctx* c, const SrcUse& u) {
+    if (u.on_copy) HIPCHK(c, hipEventRecord(c->src.ev_copy, u.cs));
+    return CF_OK;
+}
+// Consumer: the copies are in; reader() -> hipError_t launches the one kernel that reads the buffer, on the main stream
+template <class F> int src_stage_read(cf_ctx* c, bool on_copy, F&& reader) {
+    if (on_copy) HIPCHK(c, hipStreamWaitEvent(c->stream, c->src.ev_copy, 0));
+    HIPCHK(c, reader());
+    HIPCHK(c, hipEventRecord(c->src.ev_free, c->stream));
+    c->src.busy = true;
+    return CF_OK;
+}
+int src_stage_resize(cf_ctx* c, bool on_copy, uint8_t* dst, int B, int h, int w) {
+    return src_stage_read(c, on_copy, [&] { return launch_resize_u8(c->stream, (const uint8_t*)c->src.buf.p, dst, B, h, w, c->H, c->W); });
+}
+// Both halves for pitched host frames of any format (planes: g.B x {p0, p1, p2} host addresses): they land in the staging layout of
+// cf_frame.h (every pitch rounded up to 4) -- one DMA when the batch is one dense block in that layout already, else one pitched 2-D copy
+// per plane per frame -- and reader(table of their device planes, pitch0, pitch1) -> hipError_t launches the kernel that reads them.
+template <class F> int src_stage_frames(cf_ctx* c, const char* who, const FrameGeo& g, const void* const* planes, F&& reader) {
+    const RedactStage st = redact_stage_layout(g.format, g.h, g.w);
+    const size_t bytes = st.one * g.B, off[3] = {0, st.off1, st.off2};
+    SrcUse u;
+    if (int r = src_stage_begin(c, who, bytes, u)) return r;
+    uint8_t* stage = (uint8_t*)c->src.buf.p;
+    const int np = frame_planes(g.format);
+    const uint8_t* base = (const uint8_t*)planes[0];
+    bool dense = g.pitch0 == st.row0 && st.pitch0 == st.row0 && (np == 1 || (g.pitch1 == st.row1 && st.pitch1 == st.row1));
+    for (int b = 0; b < g.B && dense; ++b)
+        for (int k = 0; k < np; ++k) dense = dense && planes[3 * b + k] == base + b * st.one + off[k];
+    if (dense) HIPCHK(c, hipMemcpyAsync(stage, base, bytes, hipMemcpyHostToDevice, u.cs));
+    else HIPCHK(c, redact_stage_copy(u.cs, st, g.format, planes, g.B, g.h, g.pitch0, g.pitch1, stage, true));
+    if (int r = src_stage_copied(c, u)) return r;
+    const std::vector<const void*> dev = stage_table(st, stage, g.format, g.B);
+    return src_stage_read(c, u.on_copy, [&] { return reader(dev.data(), st.pitch0, st.pitch1); });
 }
 
 }  // namespace
@@ -1147,67 +1246,59 @@ extern "C" {
 #define CF_FLUSH_LANE(c) do { } while (0)
 #endif
 
-// Host images of a size other than the network's land in src_stage first (the resize kernel reads them from there).  The copies go
-// on the device's ONE copy stream, like the network-sized batches of stage_input: with several contexts in flight (CenterFaceBuckets:
-// one per network shape) copies issued on each context's own stream share the PCIe link, ALL finish late and no forward can start
-// under them; queued on one stream the first chunk is complete after 1/n of the time and its forward runs under the other copies.
-// Small batches (single-image calls) stay on the main stream: nothing to overlap, and the event round trip costs 0.3 ms of latency.
-static hipStream_t src_stage_stream(cf_ctx* c, size_t bytes) { return bytes < ((size_t)8 << 20) ? c->stream : c->stream_in; }
-static int src_stage_begin(cf_ctx* c, size_t bytes) {
-    if (!c->ev_src_copy) HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_copy, hipEventDisableTiming));
-    if (!c->ev_src_free) HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_free, hipEventDisableTiming));
-    if (c->src_stage_bytes < bytes) {
-        if (c->src_stage) HIPCHK(c, hipFree(c->src_stage));        // (a device-wide synchronisation: no reader is left)
-        c->src_stage = nullptr; c->src_stage_bytes = 0; c->src_busy = false;
-        HIPCHK(c, hipMalloc((void**)&c->src_stage, bytes));
-        c->src_stage_bytes = bytes;
-    }
-    hipStream_t cs = src_stage_stream(c, bytes);
-    if (c->src_busy && cs != c->stream) HIPCHK(c, hipStreamWaitEvent(cs, c->ev_src_free, 0));      // the resize of the batch before has read it
+// The head of every forward entry point, under the caller's name: the state and batch-range checks, the device and (experiments build)
+// a lane still pending.  in_ok / tail: cf_forward folds its null-input check into the range message.
+static int forward_begin(cf_ctx* c, const char* who, int B, bool in_ok = true, const char* tail = "") {
+    if (!c->weights_loaded) return c->fail(CF_ESTATE, "%s before cf_load_weights", who);
+    if (!in_ok || B < 1 || B > c->max_batch) return c->fail(CF_EINVAL, "%s: B=%d outside [1, %d]%s", who, B, c->max_batch, tail);
+    HIPCHK(c, hipSetDevice(c->device));
+    CF_FLUSH_LANE(c);
     return CF_OK;
 }
-static int src_stage_resize(cf_ctx* c, size_t bytes, uint8_t* dst, int B, int h, int w) {
-    if (src_stage_stream(c, bytes) != c->stream) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_src_copy, 0));      // recorded behind the copies
-    HIPCHK(c, launch_resize_u8(c->stream, c->src_stage, dst, B, h, w, c->H, c->W));
-    HIPCHK(c, hipEventRecord(c->ev_src_free, c->stream));
-    c->src_busy = true;
-    return CF_OK;
+
+// cf_forward's input, also under the profile, trace and lane entry points: a device tensor is read in place, a host batch goes through
+// an input slot
+static int stage_input(cf_ctx* c, const void* in, int in_format, int in_on_device, int B, const void** net_in) {
+    if (int r = forward_begin(c, "cf_forward", B, in != nullptr, " or null input")) return r;
+    if (in_format != CF_IN_U8_HWC_BGR && in_format != CF_IN_F32_NCHW) return c->fail(CF_EINVAL, "unknown input format %d", in_format);
+    *net_in = in;
+    if (in_on_device) {
+        if (reinterpret_cast<uintptr_t>(in) & 3) return c->fail(CF_EINVAL, "cf_forward: device input must be 4-byte aligned (the stem reads it as dwords)");
+        return CF_OK;
+    }
+    const size_t bytes = (size_t)B * 3 * c->H * c->W * (in_format == CF_IN_U8_HWC_BGR ? 1 : 4);
+    InSlotUse u;
+    if (int r = in_slot_begin(c, bytes, in_format == CF_IN_U8_HWC_BGR, false, u)) return r;
+    HIPCHK(c, hipMemcpyAsync(u.dst, in, bytes, hipMemcpyHostToDevice, u.cs));
+    if (int r = in_slot_copied(c, u)) return r;
+    return in_slot_consume(c, u.slot, u.on_copy, net_in);
 }
 
 int cf_forward(cf_ctx* c, const void* in, int in_format, int in_on_device, int B) {
     if (!c) return CF_EINVAL;
-    CF_FLUSH_LANE(c);
     const void* net_in = nullptr;
-    int r = stage_input(c, in, in_format, in_on_device, B, &net_in);
-    if (r) return r;
-    r = launch_all_ops(c, net_in, in_format, B);
-    if (r) return r;
-    c->last_B = B;
-    return CF_OK;
+    if (int r = stage_input(c, in, in_format, in_on_device, B, &net_in)) return r;
+    return forward_run(c, net_in, in_format, B);
 }
 
 #include CF_EXP_INC(cf_runtime_2)   // measured 2-8 % slower than the free-running pair of contexts: not in the release library
 
+// Host images of a size other than the network's land in src first (the resize kernel reads them from there)
 int cf_forward_resized(cf_ctx* c, const void* imgs, int in_on_device, int B, int h, int w) {
     if (!c || !imgs || h < 1 || w < 1) return CF_EINVAL;
-    if (!c->weights_loaded) return c->fail(CF_ESTATE, "cf_forward_resized before cf_load_weights");
-    if (B < 1 || B > c->max_batch) return c->fail(CF_EINVAL, "cf_forward_resized: B=%d outside [1, %d]", B, c->max_batch);
-    HIPCHK(c, hipSetDevice(c->device));
-    CF_FLUSH_LANE(c);
+    if (int r = forward_begin(c, "cf_forward_resized", B)) return r;
     uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
     if (!in_on_device) {
         const size_t bytes = (size_t)B * h * w * 3;
-        int r = src_stage_begin(c, bytes); if (r) return r;
-        HIPCHK(c, hipMemcpyAsync(c->src_stage, imgs, bytes, hipMemcpyHostToDevice, src_stage_stream(c, bytes)));
-        if (src_stage_stream(c, bytes) != c->stream) HIPCHK(c, hipEventRecord(c->ev_src_copy, c->stream_in));
-        r = src_stage_resize(c, bytes, dst, B, h, w); if (r) return r;
+        SrcUse u;
+        if (int r = src_stage_begin(c, "cf_forward_resized", bytes, u)) return r;
+        HIPCHK(c, hipMemcpyAsync(c->src.buf.p, imgs, bytes, hipMemcpyHostToDevice, u.cs));
+        if (int r = src_stage_copied(c, u)) return r;
+        if (int r = src_stage_resize(c, u.on_copy, dst, B, h, w)) return r;
     } else {
         HIPCHK(c, launch_resize_u8(c->stream, (const uint8_t*)imgs, dst, B, h, w, c->H, c->W));
     }
-    int r = launch_all_ops(c, dst, CF_IN_U8_HWC_BGR, B);
-    if (r) return r;
-    c->last_B = B;
-    return CF_OK;
+    return forward_run(c, dst, CF_IN_U8_HWC_BGR, B);
 }
 
 // The batch as B separate host images (one pointer each) instead of one [B,h,w,3] block: what a caller holds after B cv2.imread calls
@@ -1217,11 +1308,8 @@ int cf_forward_resized(cf_ctx* c, const void* imgs, int in_on_device, int B, int
 // then returns only when the copies have left the caller's memory).
 int cf_upload_images(cf_ctx* c, const void* const* imgs, int B, int h, int w) {
     if (!c || !imgs || h < 1 || w < 1) return CF_EINVAL;
-    if (!c->weights_loaded) return c->fail(CF_ESTATE, "cf_upload_images before cf_load_weights");
-    if (B < 1 || B > c->max_batch) return c->fail(CF_EINVAL, "cf_upload_images: B=%d outside [1, %d]", B, c->max_batch);
+    if (int r = forward_begin(c, "cf_upload_images", B)) return r;
     for (int b = 0; b < B; ++b) if (!imgs[b]) return c->fail(CF_EINVAL, "cf_upload_images: image %d is a null pointer", b);
-    HIPCHK(c, hipSetDevice(c->device));
-    CF_FLUSH_LANE(c);
     c->al_in = nullptr;                                     // the copies below may land in the slot the last forward read
     const size_t one = (size_t)h * w * 3;
     // page-locked images (device-visible, 16-byte aligned): ONE kernel reads them all over PCIe instead of one DMA command each
@@ -1242,12 +1330,12 @@ int cf_upload_images(cf_ctx* c, const void* const* imgs, int B, int h, int w) {
     }
     // One DMA command per run of images that are adjacent in host memory (a caller's frame pool often is).  A command costs the engine
     // 8-10 us of idle link on top of ~22 us per VGA image, so large batches alternate between the device's two copy streams (two
-    // engines): one's set-up hides under the other's transfer.  Both streams wait for `after` (the buffer's last reader), each records
-    // its own event behind its copies, and the forward waits for both -- no stream waits for the other (every such hop costs ~0.1 ms).
+    // engines): one's set-up hides under the other's transfer.  Both streams wait for `after` (the buffer's last reader; cs does
+    // already), each records its own event behind its copies, and the forward waits for both -- no stream waits for the other (every
+    // such hop costs ~0.1 ms).
     bool dual = false;
     auto copy_in = [&](uint8_t* dst, hipStream_t cs, hipEvent_t after) -> hipError_t {
         hipError_t e = hipSuccess;
-        if (after && (e = hipStreamWaitEvent(cs, after, 0)) != hipSuccess) return e;
         if (!dev.empty()) return launch_upload_images(cs, dev.data(), dst, B, (long long)one);
         static const bool dual_ok = cf_ab_int("CF_COPY_DUAL", 1) != 0;
         dual = dual_ok && cs == c->stream_in && B > 1;
@@ -1268,54 +1356,36 @@ int cf_upload_images(cf_ctx* c, const void* const* imgs, int B, int h, int w) {
         if (dual && (e = hipEventRecord(c->ev_copy2, c->stream_in2)) != hipSuccess) return e;
         return hipSuccess;
     };
-    if (h == c->H && w == c->W) {                           // network-sized: straight into an input slot, on the copy stream
+    if (h == c->H && w == c->W) {                           // network-sized: straight into an input slot
         static const bool own_stream = cf_ab_int("CF_UPLOAD_STREAM", 1) == 0;      // A/B: uploads on the context's main stream
-        const bool small = own_stream || one * B < ((size_t)8 << 20);             // as in stage_input: slot 0 on the main stream, no event round trip
-        const int slot = small ? 0 : (c->in_slot ^= 1);
-        hipStream_t cs = small ? c->stream : c->stream_in;
-        uint8_t* dst = (uint8_t*)c->bufs[slot == 0 ? c->buf_in : c->buf_in2].p;
-        HIPCHK(c, copy_in(dst, cs, c->slot_busy[slot] ? c->ev_slot_free[slot] : nullptr));
-        if (!small) HIPCHK(c, hipEventRecord(c->ev_copy[slot], cs));
-        c->up = {true, B, h, w, slot, small, dual};
+        InSlotUse u;
+        if (int r = in_slot_begin(c, one * B, true, own_stream, u)) return r;
+        HIPCHK(c, copy_in((uint8_t*)u.dst, u.cs, u.after));
+        if (int r = in_slot_copied(c, u)) return r;
+        c->up = {true, B, h, w, u.slot, u.on_copy, dual};
         return CF_OK;
     }
-    const size_t bytes = one * B;
-    if (!c->ev_src_copy) HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_copy, hipEventDisableTiming));
-    if (!c->ev_src_free) HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_free, hipEventDisableTiming));
-    if (c->src_stage_bytes < bytes) {
-        if (c->src_stage) HIPCHK(c, hipFree(c->src_stage));        // (a device-wide synchronisation: no reader is left)
-        c->src_stage = nullptr; c->src_stage_bytes = 0; c->src_busy = false;
-        HIPCHK(c, hipMalloc((void**)&c->src_stage, bytes));
-        c->src_stage_bytes = bytes;
-    }
-    hipStream_t cs = src_stage_stream(c, bytes);
-    HIPCHK(c, copy_in(c->src_stage, cs, c->src_busy && cs != c->stream ? c->ev_src_free : nullptr));
-    if (cs != c->stream) HIPCHK(c, hipEventRecord(c->ev_src_copy, cs));
-    c->up = {true, B, h, w, -1, false, dual};
+    SrcUse u;
+    if (int r = src_stage_begin(c, "cf_upload_images", one * B, u)) return r;
+    HIPCHK(c, copy_in((uint8_t*)c->src.buf.p, u.cs, u.after));
+    if (int r = src_stage_copied(c, u)) return r;
+    c->up = {true, B, h, w, -1, u.on_copy, dual};
     return CF_OK;
 }
 
+// The consumer halves of what cf_upload_images began
 int cf_forward_uploaded(cf_ctx* c) {
     if (!c) return CF_EINVAL;
     if (!c->up.pending) return c->fail(CF_ESTATE, "cf_forward_uploaded without a cf_upload_images before it");
-    HIPCHK(c, hipSetDevice(c->device));
     const cf_ctx::Upload u = c->up;
+    if (int r = forward_begin(c, "cf_forward_uploaded", u.B)) return r;
     c->up.pending = false;
-    const uint8_t* net_in;
+    uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
+    const void* net_in = dst;
     if (u.dual) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy2, 0));
-    if (u.slot >= 0) {
-        if (!u.small) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy[u.slot], 0));
-        c->in_slot_used = u.slot;
-        net_in = (const uint8_t*)c->bufs[u.slot == 0 ? c->buf_in : c->buf_in2].p;
-    } else {
-        uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
-        int r = src_stage_resize(c, (size_t)u.B * u.h * u.w * 3, dst, u.B, u.h, u.w); if (r) return r;
-        net_in = dst;
-    }
-    int r = launch_all_ops(c, net_in, CF_IN_U8_HWC_BGR, u.B);
-    if (r) return r;
-    c->last_B = u.B;
-    return CF_OK;
+    if (u.slot >= 0) { if (int r = in_slot_consume(c, u.slot, u.on_copy, &net_in)) return r; }
+    else if (int r = src_stage_resize(c, u.on_copy, dst, u.B, u.h, u.w)) return r;
+    return forward_run(c, net_in, CF_IN_U8_HWC_BGR, u.B);
 }
 
 int cf_forward_images(cf_ctx* c, const void* const* imgs, int B, int h, int w) {
@@ -1324,15 +1394,12 @@ int cf_forward_images(cf_ctx* c, const void* const* imgs, int B, int h, int w) {
 }
 
 // 4:2:0 video frames -> BGR (cf_yuv.hip) -> the network.  The conversion writes input_resized, so the plan and its graphs are those of
-// cf_forward_resized.  Host frames land in src_stage under the protocol above (small batches on the main stream; large ones on the
-// copy stream, waiting only for the conversion of the batch before to have read the buffer): one DMA for a dense block, else one
-// pitched 2-D copy per plane per frame.  Device frames are read in place.
+// cf_forward_resized.  Host frames land in src (src_stage_frames); device frames are read in place.
 int cf_forward_yuv(cf_ctx* c, int fmt, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w, int y_pitch, int c_pitch) {
     if (!c) return CF_EINVAL;
-    if (!c->weights_loaded) return c->fail(CF_ESTATE, "cf_forward_yuv before cf_load_weights");
+    if (int r = forward_begin(c, "cf_forward_yuv", B)) return r;
     if (fmt < CF_YUV_NV12 || fmt > CF_YUV_YV12) return c->fail(CF_EINVAL, "cf_forward_yuv: unknown format %d (0..3: NV12, NV21, I420, YV12)", fmt);
     if (h < 2 || w < 2 || (h & 1) || (w & 1)) return c->fail(CF_EINVAL, "cf_forward_yuv: h=%d, w=%d must be even and at least 2", h, w);
-    if (B < 1 || B > c->max_batch) return c->fail(CF_EINVAL, "cf_forward_yuv: B=%d outside [1, %d]", B, c->max_batch);
     if (!frames) return c->fail(CF_EINVAL, "cf_forward_yuv: null frame table");
     const bool il = fmt == CF_YUV_NV12 || fmt == CF_YUV_NV21;
     const int cw = il ? w : w / 2;                                       // chroma bytes per row
@@ -1346,46 +1413,13 @@ int cf_forward_yuv(cf_ctx* c, int fmt, const cf_yuv_planes* frames, int in_on_de
         const uintptr_t a = reinterpret_cast<uintptr_t>(f.y) | reinterpret_cast<uintptr_t>(f.c0) | (il ? 0 : reinterpret_cast<uintptr_t>(f.c1));
         if (in_on_device && (a & 3)) return c->fail(CF_EINVAL, "cf_forward_yuv: the device planes of frame %d must be 4-byte aligned", b);
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    CF_FLUSH_LANE(c);
+    static_assert(sizeof(cf_yuv_planes) == 3 * sizeof(void*), "cf_yuv_planes is a table of three addresses");
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
     uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
-    const size_t ybytes = (size_t)h * w, cbytes = (size_t)(h / 2) * cw, one = ybytes + (il ? cbytes : 2 * cbytes);     // = h * w * 3 / 2
-    std::vector<const void*> planes((size_t)3 * B);
-    if (!in_on_device) {
-        const size_t bytes = one * B;
-        int r = src_stage_begin(c, bytes); if (r) return r;
-        const hipStream_t cs = src_stage_stream(c, bytes);
-        const uint8_t* base = (const uint8_t*)frames[0].y;
-        bool dense = y_pitch == w && c_pitch == cw;                      // the whole batch is one [B][h*3/2][w] block
-        for (int b = 0; dense && b < B; ++b) {
-            const uint8_t* f = base + b * one;
-            dense = frames[b].y == f && frames[b].c0 == f + ybytes && (il || frames[b].c1 == f + ybytes + cbytes);
-        }
-        if (dense) HIPCHK(c, hipMemcpyAsync(c->src_stage, base, bytes, hipMemcpyHostToDevice, cs));
-        for (int b = 0; b < B; ++b) {
-            uint8_t* f = c->src_stage + b * one;
-            if (!dense) {
-                HIPCHK(c, hipMemcpy2DAsync(f, w, frames[b].y, y_pitch, w, h, hipMemcpyHostToDevice, cs));
-                HIPCHK(c, hipMemcpy2DAsync(f + ybytes, cw, frames[b].c0, c_pitch, cw, h / 2, hipMemcpyHostToDevice, cs));
-                if (!il) HIPCHK(c, hipMemcpy2DAsync(f + ybytes + cbytes, cw, frames[b].c1, c_pitch, cw, h / 2, hipMemcpyHostToDevice, cs));
-            }
-            planes[3 * b] = f; planes[3 * b + 1] = f + ybytes; planes[3 * b + 2] = il ? nullptr : f + ybytes + cbytes;
-        }
-        if (cs != c->stream) {
-            HIPCHK(c, hipEventRecord(c->ev_src_copy, cs));
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_src_copy, 0));
-        }
-        HIPCHK(c, launch_yuv_to_bgr(c->stream, fmt, planes.data(), B, h, w, w, cw, dst, c->H, c->W));
-        HIPCHK(c, hipEventRecord(c->ev_src_free, c->stream));
-        c->src_busy = true;
-    } else {
-        for (int b = 0; b < B; ++b) { planes[3 * b] = frames[b].y; planes[3 * b + 1] = frames[b].c0; planes[3 * b + 2] = il ? nullptr : frames[b].c1; }
-        HIPCHK(c, launch_yuv_to_bgr(c->stream, fmt, planes.data(), B, h, w, y_pitch, c_pitch, dst, c->H, c->W));
-    }
-    int r = launch_all_ops(c, dst, CF_IN_U8_HWC_BGR, B);
-    if (r) return r;
-    c->last_B = B;
-    return CF_OK;
+    auto convert = [&](const void* const* pl, int p0, int p1) { return launch_yuv_to_bgr(c->stream, fmt, pl, B, h, w, p0, p1, dst, c->H, c->W); };
+    if (in_on_device) HIPCHK(c, convert(planes, y_pitch, c_pitch));
+    else if (int r = src_stage_frames(c, "cf_forward_yuv", FrameGeo{fmt, B, h, w, y_pitch, c_pitch}, planes, convert)) return r;
+    return forward_run(c, dst, CF_IN_U8_HWC_BGR, B);
 }
 
 
@@ -1496,17 +1530,6 @@ int cf_detect_topk(cf_ctx* c, const void* in, int in_format, int in_on_device, i
     int r = cf_forward(c, in, in_format, in_on_device, B);
     if (r) return r;
     return cf_decode_topk(c, K, 1, dets, lms, inds, out_on_device);
-}
-
-// Device scratch that only grows: b holds at least need_bytes afterwards, or nothing (CF_ENOMEM / CF_EHIP)
-static int grow(cf_ctx* c, DevBuf& b, size_t need_bytes, const char* what, const char* who) {
-    if (b.bytes >= need_bytes) return CF_OK;
-    if (b.p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(b.p); }        // earlier launches may still use it
-    b = DevBuf{};
-    const hipError_t e = hipMalloc(&b.p, need_bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "%s: %zu bytes of %s: %s", who, need_bytes, what, hipGetErrorString(e)); }
-    b.bytes = need_bytes;
-    return CF_OK;
 }
 
 // The host read-out tail of the threshold decode, the merge and the tracker: the counts (and flags) of B images, then only the rows that
@@ -1761,7 +1784,7 @@ int cf_align_faces(cf_ctx* c, const cf_align_opts* o, void* chips, double* matri
     if (out_on_device) { p.chips = chips; p.mats = matrices; p.offsets = offsets; }
     else if (int r = align_scratch(c, "cf_align_faces", one, cap_faces, matrices != nullptr, p)) return r;
     HIPCHK(c, launch_align_faces(c->stream, p));
-    if (c->al_slot >= 0) HIPCHK(c, hipEventRecord(c->ev_slot_free[c->al_slot], c->stream));      // the staging slot has one more reader
+    if (c->al_slot >= 0) { if (int r = in_slot_release(c, c->al_slot)) return r; }      // the input slot has one more reader
     if (out_on_device) return CF_OK;
     return align_copy_out(c, B, one, cap_faces, chips, matrices, offsets);
 }
@@ -1888,20 +1911,16 @@ int cf_align_faces_frame(cf_ctx* c, const cf_align_opts* o, int format, const cf
 }
 
 // Tiled forward: the cutter (cf_tiles.hip) writes the Bf * T tile images to input_resized, so the plan and its graphs are those of
-// cf_forward_resized.  Host frames -- BGR ones too -- land in src_stage under its protocol, in the layout of the redaction's staging
-// (pitches rounded up to 4): one DMA for a dense block, else one pitched 2-D copy per plane per frame.  Device frames are read in place.
+// cf_forward_resized.  Host frames -- BGR ones too -- land in src (src_stage_frames); device frames are read in place.
 int cf_forward_tiles(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0, int pitch1,
                      const cf_tile_rect* rects, int T) {
     if (!c) return CF_EINVAL;
-    if (!c->weights_loaded) return c->fail(CF_ESTATE, "cf_forward_tiles before cf_load_weights");
-    static_assert(sizeof(cf_yuv_planes) == 3 * sizeof(void*), "cf_yuv_planes is a table of three addresses");
     const void* const* planes = reinterpret_cast<const void* const*>(frames);
     std::string why;
     if (tiles_check(why, format, Bf, h, w, pitch0, pitch1, rects, T, c->H, c->W)) return c->fail(CF_EINVAL, "cf_forward_tiles: %s", why.c_str());
     if ((long long)Bf * T > c->max_batch) return c->fail(CF_EINVAL, "cf_forward_tiles: Bf * T = %d x %d exceeds max_batch %d", Bf, T, c->max_batch);
     if (const char* bad = redact_check_planes(format, planes, Bf, in_on_device, pitch0, pitch1)) return c->fail(CF_EINVAL, "cf_forward_tiles: %s", bad);
-    HIPCHK(c, hipSetDevice(c->device));
-    CF_FLUSH_LANE(c);
+    if (int r = forward_begin(c, "cf_forward_tiles", Bf * T)) return r;
     const size_t rbytes = (size_t)T * sizeof(cf_tile_rect);
     if (!c->tl_rects_up || c->tl_rects.size() != (size_t)T || memcmp(c->tl_rects.data(), rects, rbytes) != 0) {
         c->tl_rects_up = 0;
@@ -1912,34 +1931,12 @@ int cf_forward_tiles(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_
         c->tl_rects_up = 1;
     }
     uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
-    if (!in_on_device) {
-        const RedactStage st = redact_stage_layout(format, h, w);
-        const size_t bytes = st.one * Bf;
-        int r = src_stage_begin(c, bytes); if (r) return r;
-        const hipStream_t cs = src_stage_stream(c, bytes);
-        const bool bgr = format == CF_FRAME_BGR, three = frame_planes(format) == 3;
-        const uint8_t* base = (const uint8_t*)frames[0].y;
-        bool dense = pitch0 == st.row0 && st.pitch0 == st.row0 && (bgr || (pitch1 == st.row1 && st.pitch1 == st.row1));
-        for (int b = 0; b < Bf && dense; ++b) {
-            const uint8_t* hf = base + b * st.one;
-            dense = frames[b].y == hf && (bgr || frames[b].c0 == hf + st.off1) && (!three || frames[b].c1 == hf + st.off2);
-        }
-        const std::vector<const void*> dev = stage_table(st, c->src_stage, format, Bf);
-        if (dense) HIPCHK(c, hipMemcpyAsync(c->src_stage, base, bytes, hipMemcpyHostToDevice, cs));
-        else HIPCHK(c, redact_stage_copy(cs, st, format, planes, Bf, h, pitch0, pitch1, c->src_stage, true));
-        if (cs != c->stream) {
-            HIPCHK(c, hipEventRecord(c->ev_src_copy, cs));
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_src_copy, 0));
-        }
-        HIPCHK(c, launch_cut_tiles(c->stream, format, dev.data(), Bf, st.pitch0, st.pitch1, (const cf_tile_rect*)c->tl_rects_dev.p, T, dst, c->H, c->W));
-        HIPCHK(c, hipEventRecord(c->ev_src_free, c->stream));
-        c->src_busy = true;
-    } else {
-        HIPCHK(c, launch_cut_tiles(c->stream, format, planes, Bf, pitch0, pitch1, (const cf_tile_rect*)c->tl_rects_dev.p, T, dst, c->H, c->W));
-    }
-    int r = launch_all_ops(c, dst, CF_IN_U8_HWC_BGR, Bf * T);
-    if (r) return r;
-    c->last_B = Bf * T;
+    auto cut = [&](const void* const* pl, int p0, int p1) {
+        return launch_cut_tiles(c->stream, format, pl, Bf, p0, p1, (const cf_tile_rect*)c->tl_rects_dev.p, T, dst, c->H, c->W);
+    };
+    if (in_on_device) HIPCHK(c, cut(planes, pitch0, pitch1));
+    else if (int r = src_stage_frames(c, "cf_forward_tiles", FrameGeo{format, Bf, h, w, pitch0, pitch1}, planes, cut)) return r;
+    if (int r = forward_run(c, dst, CF_IN_U8_HWC_BGR, Bf * T)) return r;
     c->tl_T = T; c->tl_Bf = Bf; c->tl_h = h; c->tl_w = w;
     return CF_OK;
 }
@@ -2194,10 +2191,7 @@ int cf_forward_trace(cf_ctx* c, const void* in, int in_format, int in_on_device,
     if (r) return r;
     if (c->dec_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_dec, 0)); c->dec_pending = false; }
     for (int i = 0; i <= op_index; ++i) HIPCHK(c, launch_op(c, c->ops[i], net_in, in_format, B));
-    if (c->in_slot_used >= 0) {
-        HIPCHK(c, hipEventRecord(c->ev_slot_free[c->in_slot_used], c->stream));
-        c->slot_busy[c->in_slot_used] = true; c->in_slot_used = -1;
-    }
+    if (int r2 = in_slot_done(c)) return r2;
     const Op& op = c->ops[op_index];
     const bool head = op.kind == OP_HEAD;
     const int C = head ? 16 : op.Cout;
@@ -2365,7 +2359,7 @@ int cf_spread_streams(cf_ctx** ctxs, int n, int window, int* n_distinct) {
         if (slot) hipStreamDestroy(slot);
         slot = chosen[k];
         c->dec_pending = false; c->main_dec_pending = false;
-        for (int i = 0; i < 2; ++i) c->slot_busy[i] = false;
+        c->in.busy[0] = c->in.busy[1] = false;
     }
     if (n_distinct) *n_distinct = (int)chosen.size();
     return CF_OK;
@@ -2389,7 +2383,7 @@ int cf_reroll_streams(cf_ctx* c) {
     if (c->stream2) hipStreamDestroy(c->stream2);
     c->stream = s1; c->stream2 = s2;
     c->dec_pending = false; c->main_dec_pending = false;               // everything was drained above
-    for (int i = 0; i < 2; ++i) c->slot_busy[i] = false;
+    c->in.busy[0] = c->in.busy[1] = false;
     return CF_OK;
 }
 

@@ -57,11 +57,7 @@ int cf_forward_lanes(cf_ctx* cur, cf_ctx* prev, const void* in, int in_format, i
     if (alone && prev && prev->seg2_recorded) HIPCHK(cur, hipStreamWaitEvent(cur->stream, prev->ev_seg2, 0));
     r = launch_range(cur, 0, cur->lane_cut1, net_in, in_format, B); if (r) return r;
     HIPCHK(cur, hipEventRecord(cur->ev_seg1, cur->stream));
-    if (cur->in_slot_used >= 0) {                       // the stem has read the host-input staging slot
-        HIPCHK(cur, hipEventRecord(cur->ev_slot_free[cur->in_slot_used], cur->stream));
-        cur->slot_busy[cur->in_slot_used] = true;
-        cur->in_slot_used = -1;
-    }
+    r = in_slot_done(cur); if (r) return r;             // the stem has read the host-input slot
     if (prev && prev->lane_pending) {
         HIPCHK(prev, hipSetDevice(prev->device));
         HIPCHK(prev, hipStreamWaitEvent(prev->stream, cur->ev_seg1, 0));

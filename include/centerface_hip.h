@@ -472,6 +472,72 @@ int cf_track_reset(cf_tracker* trk, int stream);
 int cf_track_update(cf_ctx* ctx, cf_tracker* trk, int stream0, float* dets, float* lms, int32_t* info,
                     int32_t* counts, int32_t* flags, int out_on_device);
 
+/* ---- annotation: box outlines, landmark dots and a numeric label IN THE SOURCE FRAME, on the device --------------------------- */
+/* What demo.py:15-23, 40-51 does with a detection -- cv2.rectangle(frame, .., (2, 255, 0), 1) per box, cv2.circle(frame, .., 2,
+ * (0, 0, 255), -1) per landmark -- for frames that stay on the device: BGR or 4:2:0, pitched, a decoder's surface in place, behind the
+ * decode, the merge or the tracker, whose work it makes visible (held tracks in their own colour, dashed, with their id).  The
+ * arithmetic is this library's own statement (csrc/cf_drawmath.h, shared by the host and the kernels of csrc/cf_draw.hip; restated in
+ * tests/draw_cases.py; device and restatement are equal bit for bit).  Integers throughout, except the point mapping: float64 in the
+ * order written, no FMA contraction.
+ *   Frame h x w, the rows' coordinate space H x W, fx = (double)w / (double)W, fy = (double)h / (double)H (after a merge H x W is the
+ *   frame itself: fx = fy = 1).  Options t = thickness, r = radius, k = label_scale.
+ *   1. Points.  P(v, f) = (int)min(max(floor(v * f), -8192.0), 16384.0) for a double v.
+ *      Box: cx = ((double)x1 + (double)x2) * 0.5, hw = ((double)x2 - (double)x1) * 0.5 * (double)scale, X1 = P(cx - hw, fx),
+ *      X2 = P(cx + hw, fx); y likewise.  A row is skipped entirely when a corner is not finite or hw / hh is not > 0, as in the
+ *      redaction.  Both corners are inclusive: the box is [X1..X2] x [Y1..Y2].  There is no snapping to even.
+ *      Landmark j: (Lx, Ly) = (P((double)lx, fx), P((double)ly, fy)); skipped when either value is not finite.
+ *   2. Primitives of a row, as sets of frame pixels (x, y), clipped to the frame:
+ *      Outline (CF_DRAW_BOX): pixels inside the box with x < X1 + t || x > X2 - t || y < Y1 + t || y > Y2 - t.  With t = 1 these are
+ *        exactly the pixels cv2.rectangle(.., thickness=1) names for the same integer corners.  A held row (misses > 0) with dash_held
+ *        keeps only pixels with ((x + y) % (8 * t)) < 4 * t: x, y >= 0 inside the frame, so the pattern is anchored at the frame origin.
+ *      Dot (CF_DRAW_LANDMARKS): pixels with dx*dx + dy*dy <= r*r + r about each of the five (Lx, Ly), live rows only (a held row's
+ *        landmarks are the last ones seen and are not drawn).  r = 2 is the 5 x 5 square without its corners, 21 pixels; r = 0 one pixel.
+ *      Label (label != NONE).  SCORE: value p = (int)floor((double)score * 100.0) clamped to [0, 100]; no label when score is not
+ *        finite.  ID: the row's track id; no label when id <= 0.  Digits: the decimal digits of the value without leading zeros, n of
+ *        them (1..10).  Plate: Pw = k * (6n + 1), Ph = 9k, x0 = X1, y0 = Y1 - Ph when that is >= 0, else Y1 + t; the plate is
+ *        [x0, x0 + Pw) x [y0, y0 + Ph).  Ink: with u = (x - x0) / k, v = (y - y0) / k, the pixel is ink when 1 <= v <= 7, u >= 1,
+ *        q = (u - 1) / 6 < n, col = (u - 1) % 6 < 5 and bit 4 - col of GLYPH[digit q][v - 1] is set.
+ *        GLYPH, rows top to bottom, 5 bits each, MSB = left column:
+ *          0: 0E 11 13 15 19 11 0E    1: 04 0C 04 04 04 04 0E    2: 0E 11 01 02 04 08 1F    3: 1F 02 04 02 01 11 0E
+ *          4: 02 06 0A 12 1F 02 02    5: 1F 10 1E 01 01 11 0E    6: 06 08 10 1E 11 11 0E    7: 1F 01 02 04 08 08 08
+ *          8: 0E 11 11 0E 11 11 0E    9: 0E 11 11 0F 01 02 0C
+ *   3. Layers.  Each primitive pixel has a layer, and the layer fixes the colour: 1 held_color: outline and plate of held rows;
+ *      2 box_color: outline and plate of live rows; 3 text_color: ink; 4 lm_color: dots.  A frame pixel takes the colour of the HIGHEST
+ *      layer that any row of its image puts on it and is not written at all when there is none -- so the result depends neither on the
+ *      order of the rows nor on their overlap.
+ *   4. Planes.  BGR: the three bytes of the pixel.  4:2:0: the luma sample takes byte 0 of the colour; a chroma sample (i, j) takes
+ *      bytes 1 and 2 of the colour of the highest layer over its four luma pixels (2i..2i+1, 2j..2j+1) and is untouched when none of
+ *      the four is drawn; chroma is in memory order for NV21 / YV12, as cf_redact_faces places `fill`.  No byte that is not drawn is
+ *      ever read-modify-written: pitch padding and every undrawn byte keep their values.
+ * On the device this is a gather (one launch writes a record per row, one launch of a workgroup per 64 x 16 tile paints): every byte
+ * has one writer, the frame is never read. */
+#define CF_DRAW_BOX        1     /* `what` bits */
+#define CF_DRAW_LANDMARKS  2
+#define CF_DRAW_LABEL_NONE  0    /* `label` */
+#define CF_DRAW_LABEL_SCORE 1
+#define CF_DRAW_LABEL_ID    2
+typedef struct cf_draw_opts {
+    int32_t what;                /* CF_DRAW_BOX | CF_DRAW_LANDMARKS; what == 0 with label == 0 is CF_EINVAL */
+    int32_t thickness;           /* t, 1..16: the outline grows INWARDS from the box */
+    int32_t radius;              /* r, 0..16: landmark dot */
+    int32_t label;               /* CF_DRAW_LABEL_* */
+    int32_t label_scale;         /* k, 1..8: pixels per glyph cell */
+    int32_t dash_held;           /* 0 | 1: outlines of held rows (misses > 0) are dashed */
+    float   scale;               /* box grown about its centre, 0.25..4 (1 = the detection itself) */
+    uint8_t box_color[4], held_color[4], lm_color[4], text_color[4];   /* bytes in the frame's own channel order (B,G,R or Y,U,V), [3] unused -- as cf_redact_opts.fill */
+} cf_draw_opts;                  /* 44 bytes */
+/* Which rows, B, (h, w), pitches, alignment, on_device, the stream and the CF_ESTATE / CF_EINVAL rules are those of cf_redact_faces:
+ * the tracked rows behind a cf_track_update, else the merged rows of a tiled forward, else the decode's, in network coordinates
+ * whatever cf_set_rescale says.  misses and id come from the tracked rows' info; untracked rows are all live, and CF_DRAW_LABEL_ID on
+ * them is CF_ESTATE.  The call changes no state of ctx, as cf_align_faces_frame promises: a redact, blur, align or second draw behind it
+ * behaves as before (draw-after-redact is the expected order).  BGR frames may have odd sides (h, w in 1..8192).  on_device = 1: in
+ * place, asynchronous on the stream that carried the rows' producer, no count is read on the host.  CF_EINVAL, before any GPU work,
+ * for: `what` outside 0..3 or `label` outside 0..2, nothing to draw, thickness, radius or label_scale out of range, dash_held not
+ * 0 / 1, scale out of range or not finite, and every geometry and plane error of the redaction.  A scratch of one record per row
+ * grows to the largest B x rows seen (outside any graph). */
+int cf_draw_faces(cf_ctx* ctx, const cf_draw_opts* opts, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
+                  int pitch0, int pitch1);
+
 /* ---- fused convenience: forward + D3 decode in one enqueue (eval_widerface.py:76-90 shape) -- */
 int cf_detect_topk(cf_ctx* ctx, const void* in, int in_format, int in_on_device, int B, int K,
                    float* dets, float* lms, int64_t* inds, int out_on_device);
@@ -760,6 +826,21 @@ int cf_op_merge_tiles(int device, const cf_merge_opts* opts, const cf_tile_rect*
 int cf_op_track(int device, const cf_track_opts* opts, int n_streams, int n_frames, int rows, const float* boxes,
                 const float* scores, const float* lms_in, const int32_t* counts_in,
                 float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags);
+/* The kernels of cf_draw_faces alone, on host frames (modified in place): boxes [N][4] x1,y1,x2,y2 in the coordinates of an H x W
+ * network input, scores [N], lms [N][10] or NULL, info [N][3] = id, hits, misses or NULL (all live), image after image, counts [B]
+ * (>= 0, N = their sum).  The same validation as cf_draw_faces, before any device is touched; NULL lms with CF_DRAW_LANDMARKS and
+ * NULL info with CF_DRAW_LABEL_ID are CF_EINVAL. */
+int cf_op_draw(int device, const cf_draw_opts* opts, int format, const cf_planes_rw* host_frames, int B, int h, int w, int pitch0,
+               int pitch1, const float* boxes, const float* scores, const float* lms, const int32_t* info, const int32_t* counts,
+               int H, int W);
+/* HOST ONLY: the integer geometry of one row in an h x w frame, computed by the code the kernels run (csrc/cf_drawmath.h), so that
+ * the shared statement can be checked with no GPU.  lms [10] and info [3] may be NULL.  out[32]:
+ *   [0] ok (0 = the row is skipped; every other value is then 0)   [1..4] X1, Y1, X2, Y2   [5] held (misses > 0)
+ *   [6..9] plate x0, y0, Pw, Ph (0 without a label)   [10] n, the digits of the label (0 = none)   [11..20] the digits, most
+ *   significant first, 0 past n   [21] bit j set: landmark j is finite   [22..31] Lx0, Ly0 .. Lx4, Ly4 (0 where not finite).
+ * Returns CF_EINVAL for options cf_draw_faces refuses, NULL opts / box / out, or h, w, H, W outside 1..8192 (H, W: below 1). */
+int cf_draw_layout(const cf_draw_opts* opts, const float* box, float score, const float* lms, const int32_t* info, int h, int w,
+                   int H, int W, int32_t* out);
 /* CenterFace.nms alone (centerface.py:111-151): keep[] receives kept indices in keep order. */
 int cf_op_nms(int device, const float* boxes, const float* scores, int n, float nms_thresh,
               int32_t* keep, int32_t* n_keep);

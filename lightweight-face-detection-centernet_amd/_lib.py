@@ -28,6 +28,10 @@ CF_REDACT_SOLID, CF_REDACT_MOSAIC = 0, 1
 CF_REDACT_RECT, CF_REDACT_ELLIPSE = 0, 1
 REDACT_MODES = {"solid": CF_REDACT_SOLID, "mosaic": CF_REDACT_MOSAIC}
 REDACT_SHAPES = {"rect": CF_REDACT_RECT, "ellipse": CF_REDACT_ELLIPSE}
+# cf_draw_faces / cf_op_draw
+CF_DRAW_BOX, CF_DRAW_LANDMARKS = 1, 2
+CF_DRAW_LABEL_NONE, CF_DRAW_LABEL_SCORE, CF_DRAW_LABEL_ID = 0, 1, 2
+DRAW_LABELS = {"none": CF_DRAW_LABEL_NONE, "score": CF_DRAW_LABEL_SCORE, "id": CF_DRAW_LABEL_ID}
 # cf_merge_tiles / cf_op_merge_tiles
 CF_ENOMEM = -2
 CF_MERGE_IOU, CF_MERGE_IOS = 0, 1
@@ -44,6 +48,7 @@ EXPORTS = (
     "cf_op_ctdet_decode", "cf_op_ctdet_post_process", "cf_op_decode_threshold", "cf_op_decode_threshold_ex", "cf_op_nms", "cf_op_box_match",
     "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces", "cf_align_faces_frame", "cf_op_align_frame", "cf_redact_faces", "cf_op_redact",
     "cf_blur_faces", "cf_op_blur",
+    "cf_draw_faces", "cf_op_draw", "cf_draw_layout",
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
 )
@@ -134,6 +139,37 @@ def blur_opts(shape="ellipse", radius=0, scale=1.3):
             raise ValueError("unknown redaction shape %r (one of %s)" % (shape, sorted(REDACT_SHAPES)))
         shape = REDACT_SHAPES[shape.lower()]
     return BlurOpts(int(shape), int(radius), float(scale))
+
+
+class DrawOpts(C.Structure):
+    """cf_draw_opts: what to draw / outline thickness / dot radius / label kind and scale / dashed held outlines / box scale / the four
+    colours in the frame's channel order."""
+    _fields_ = [("what", C.c_int32), ("thickness", C.c_int32), ("radius", C.c_int32), ("label", C.c_int32), ("label_scale", C.c_int32),
+                ("dash_held", C.c_int32), ("scale", C.c_float), ("box_color", C.c_uint8 * 4), ("held_color", C.c_uint8 * 4),
+                ("lm_color", C.c_uint8 * 4), ("text_color", C.c_uint8 * 4)]
+
+
+def draw_opts(boxes=True, landmarks=True, thickness=1, radius=2, label="score", label_scale=2, dash_held=True, scale=1.0,
+              box_color=(2, 255, 0), held_color=(0, 255, 255), lm_color=(0, 0, 255), text_color=(0, 0, 0), what=None):
+    """DrawOpts: ``boxes`` / ``landmarks`` switch the outlines and the dots (``what``: the bits themselves, passed through), ``label``
+    'none' | 'score' | 'id' (integer codes pass through; the library validates them, like the numbers).  The colours are three bytes
+    in the frame's own channel order (B,G,R or Y,U,V; ``ops.bgr_to_yuv_color`` converts)."""
+    if isinstance(label, str):
+        if label.lower() not in DRAW_LABELS:
+            raise ValueError("unknown label %r (one of %s)" % (label, sorted(DRAW_LABELS)))
+        label = DRAW_LABELS[label.lower()]
+    elif label is None:
+        label = CF_DRAW_LABEL_NONE
+    if what is None:
+        what = (CF_DRAW_BOX if boxes else 0) | (CF_DRAW_LANDMARKS if landmarks else 0)
+
+    def color(v, name):
+        v = [int(x) for x in v]
+        if len(v) != 3 or min(v) < 0 or max(v) > 255:
+            raise ValueError("%s must be three bytes in the frame's channel order, got %r" % (name, v))
+        return (C.c_uint8 * 4)(*v, 0)
+    return DrawOpts(int(what), int(thickness), int(radius), int(label), int(label_scale), int(dash_held), float(scale),
+                    color(box_color, "box_color"), color(held_color, "held_color"), color(lm_color, "lm_color"), color(text_color, "text_color"))
 
 
 def split_redact_options(options):
@@ -408,6 +444,9 @@ def lib():
         L.cf_op_redact.argtypes = [C.c_int, C.POINTER(RedactOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.cf_blur_faces.argtypes = [C.c_void_p, C.POINTER(BlurOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 6
         L.cf_op_blur.argtypes = [C.c_int, C.POINTER(BlurOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.cf_draw_faces.argtypes = [C.c_void_p, C.POINTER(DrawOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 6
+        L.cf_op_draw.argtypes = [C.c_int, C.POINTER(DrawOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_int, C.c_int]
+        L.cf_draw_layout.argtypes = [C.POINTER(DrawOpts), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
         L.cf_tile_grid.argtypes = [C.c_int] * 6 + [C.POINTER(TileRect), C.c_int, C.POINTER(C.c_int)]
         L.cf_forward_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(TileRect), C.c_int]
         L.cf_merge_tiles.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

@@ -423,6 +423,22 @@ class Engine(object):
         self._cover(self._L.cf_blur_faces, (_lib.device_frame_args("blur_faces_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1), None),
                     lambda: _lib.blur_opts(shape, radius, scale))
 
+    def draw_faces(self, frames, fmt="bgr", **options):
+        """Draw, in ``frames``, the newest face rows -- those ``redact_faces`` would cover: the preceding ``decode_threshold``'s, the
+        merged ones, or the tracked ones behind ``track_update`` -- (``cf_draw_faces``, blocking form): box outlines, landmark dots
+        and a numeric label, copied up, painted on the device and copied back IN PLACE, and returned.  Frames and formats as
+        ``redact_faces``.  ``options``: those of ``_lib.draw_opts`` -- boxes, landmarks, thickness, radius, label ('none' | 'score' |
+        'id': the track id, tracked rows only), label_scale, dash_held, scale, box_color, held_color, lm_color, text_color (bytes in
+        the frame's own channel order; ``ops.bgr_to_yuv_color`` converts).  Held tracks are drawn in ``held_color``, dashed, without
+        dots.  No state of the engine changes: draw after redact."""
+        return self._cover(self._L.cf_draw_faces, _lib.host_frame_args(frames, fmt), lambda: _lib.draw_opts(**options), frames)
+
+    def draw_faces_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1=0, **options):
+        """Same, in place on DEVICE planes as ``redact_faces_device`` takes them: asynchronous on the engine's main stream behind the
+        rows' producer; no count is read on the host."""
+        self._cover(self._L.cf_draw_faces, (_lib.device_frame_args("draw_faces_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1), None),
+                    lambda: _lib.draw_opts(**options))
+
     def cover_faces(self, frames, fmt="bgr", **options):
         """``blur_faces`` when ``options`` say ``mode='blur'`` (shape, radius, scale), otherwise ``redact_faces``."""
         kind, kw = _lib.split_redact_options(options)
@@ -903,11 +919,12 @@ class CenterFace(object):
         """The results of the forward last enqueued on ``eng``; the rescale (centerface.py:55-62) was done by the decode kernel."""
         return self._postprocess_many(eng.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)
 
-    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None):
+    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None):
         """The chunk loop of every product path: ``forward`` enqueues ``frames`` in slices of ``per`` (default ``max_batch``), each is
         decoded, and while the engine still holds it the steps that were asked for run in this order: ``tracker`` is advanced -- image b
         of the chunk that starts at frame i continues its stream i + b --, ``cover`` = (array, fmt, options) has the chunk's slice of
-        the array covered, ``chips(i, j)`` cuts the chips of frames i:j, which join the results.  ``merge`` = (metric, thresh, edge) says
+        the array covered, ``draw`` = (array, fmt, options) has it annotated (``Engine.draw_faces``), ``chips(i, j)`` cuts the chips of
+        frames i:j, which join the results.  ``merge`` = (metric, thresh, edge) says
         that the forward is a tiled one: the tiles' rows are merged, in frame pixels; otherwise the decode rescales, and the rescale is
         switched off again whatever happens.  Returns the per-frame results."""
         eng, out = self.engine, []
@@ -926,6 +943,8 @@ class CenterFace(object):
                     eng.track_update_device(tracker, i)
                 if cover is not None:
                     eng.cover_faces(cover[0][i:i + per], cover[1], **cover[2])
+                if draw is not None:
+                    eng.draw_faces(draw[0][i:i + per], draw[1], **draw[2])
                 if chips is not None:
                     cut, offs, _ = chips(i, i + per)
                     res = [(d, l, cut[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(res)]
@@ -1026,6 +1045,45 @@ class CenterFace(object):
         frames, forward = self._input_form(self.engine, frames, fmt)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
         return out, self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options))
+
+    def _draw_options(self, options, tracker, yuv):
+        """The options of ``annotate`` / ``annotate_yuv`` -> those of ``Engine.draw_faces``: the reference's look (demo.py:15-23: green
+        boxes of thickness 1, red dots of radius 2) by default, the track id as the label when there is a tracker, else the score;
+        colours are BGR triples, converted for 4:2:0 frames."""
+        from . import ops
+        o = dict(box_color=(2, 255, 0), lm_color=(0, 0, 255), held_color=(0, 255, 255), text_color=(0, 0, 0), thickness=1, radius=2,
+                 label="id" if tracker is not None else "score", label_scale=2, dash_held=True, scale=1.0, landmarks=bool(self.landmarks))
+        o.update(options)
+        if yuv:
+            for k in ("box_color", "lm_color", "held_color", "text_color"):
+                o[k] = ops.bgr_to_yuv_color(o[k])
+        _lib.draw_opts(**o)                                                   # refuse bad names and colours before any work
+        return o
+
+    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, **options):
+        """``detect_batch`` plus the drawing of every detection, what demo.py:15-23 does with cv2 on the host: (frames_out, [(dets, lms),
+        ...]) -- frames_out a uint8 [B,h,w,3] COPY of ``imgs`` with box outlines, landmark dots and a label painted on the device
+        (``Engine.draw_faces``; ``options`` as there, colours as BGR triples).  ``tiled``, ``tile``, ``overlap`` and ``tracker`` as
+        ``anonymize``: with a tracker the label is the track id and the tracks held through a dropout are drawn too, dashed, in
+        ``held_color``."""
+        imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
+        out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
+        draw = (out, "bgr", self._draw_options(options, tracker, False))
+        if tiled:
+            return out, self._drive(out, *self._tiled_form(out, "bgr", tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker, draw=draw)
+        return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, draw=draw)
+
+    def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, **options):
+        """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
+        in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``."""
+        o = self._draw_options(options, tracker, True)
+        if tiled:                                                       # frames of any even size: [B, h*3//2, w]
+            out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
+            return out, self._drive(out, *self._tiled_form(out, fmt, tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker,
+                                    draw=(out, fmt, o))
+        frames, forward = self._input_form(self.engine, frames, fmt)
+        out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
+        return out, self._drive(frames, forward, tracker=tracker, draw=(out, fmt, o))
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]

@@ -393,6 +393,28 @@ const char* blur_check(int format, int shape, int radius, float scale, int B, in
 size_t blur_scratch_bytes(int format, int B, int h, int w);
 hipError_t launch_blur_faces(hipStream_t s, const BlurParams& p);
 
+// Annotation of the source frame (cf_draw.hip): outlines, landmark dots and a numeric label of every face row, painted by a gather -- a
+// prep launch writes one record per (image, row) to `recs`, a paint launch of one workgroup per 64 x 16 tile takes, per pixel, the highest
+// layer over the records that touch its tile.  The arithmetic: cf_drawmath.h.
+struct DrawRec;
+struct DrawGeoOpts;
+// the rows of B images: image b has the rows b * stride + i, i < min(counts[b], rows_cap) (rows_cap <= stride), of boxes [.][4] (the
+// coordinates of an H x W network input), scores[row * score_step], lms [.][10] (nullptr: none) and info [.][3] = id, hits, misses
+// (nullptr: untracked rows, all live)
+struct DrawRows { const float* boxes; const float* scores; int score_step; const float* lms; const int32_t* info; const int* counts; int stride, rows_cap, H, W; };
+struct DrawParams {
+    FrameGeo g;           // pitches multiples of 4
+    DrawRows r;
+    cf_draw_opts o;
+    const void* const* planes;   // as RedactParams::planes
+    DrawRec* recs;        // draw_scratch_bytes(B, rows_cap) bytes on the device
+};
+// nullptr, or what is wrong with the options / geometry (host only; no device is touched)
+const char* draw_check(const cf_draw_opts* o, int format, int B, int h, int w, int pitch0, int pitch1);
+DrawGeoOpts draw_geo_opts(const cf_draw_opts* o);
+size_t draw_scratch_bytes(int B, int rows_cap);
+hipError_t launch_draw_faces(hipStream_t s, const DrawParams& p);
+
 // Aligned face chips cut from the caller's frames (cf_align_frame.hip): the estimate, warp and outputs of AlignParams (a.img, a.img_dwords,
 // a.H, a.W unused; a.B = the number of frames), sampling B pitched frames of h x w in `format` instead of the network batch.  A landmark
 // value x (y) of a.lms is taken as (double)x * sx ((double)y * sy): sx = w / W, sy = h / H for network-coordinate rows, 1.0 for rows

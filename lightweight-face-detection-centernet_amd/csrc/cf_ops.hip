@@ -853,6 +853,52 @@ int cf_op_blur(int device, const cf_blur_opts* o, int format, const cf_planes_rw
     });
 }
 
+// The kernels of cf_draw_faces on host frames (in place).  The packed rows are spread to [B][max count] like op_on_faces' boxes.
+int cf_op_draw(int device, const cf_draw_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
+               const float* boxes, const float* scores, const float* lms, const int32_t* info, const int32_t* counts, int H, int W) {
+    if (!o) { g_op_error = "cf_op_draw: null options"; return CF_EINVAL; }
+    const void* const* host_planes = reinterpret_cast<const void* const*>(frames);
+    const char* why = draw_check(o, format, B, h, w, pitch0, pitch1);
+    if (!why) why = redact_check_planes(format, host_planes, B, 0, pitch0, pitch1);
+    if (!why && (!counts || H < 1 || W < 1)) why = "null counts, or H / W below 1";
+    if (!why && (o->what & CF_DRAW_LANDMARKS) && !lms) why = "CF_DRAW_LANDMARKS without landmark rows";
+    if (!why && o->label == CF_DRAW_LABEL_ID && !info) why = "CF_DRAW_LABEL_ID without info rows";
+    int rows = 1;
+    long long N = 0;
+    for (int b = 0; !why && b < B; ++b) {
+        if (counts[b] < 0 || counts[b] > (1 << 20)) why = "a count is negative or above 2^20";
+        else { rows = std::max(rows, (int)counts[b]); N += counts[b]; }
+    }
+    if (!why && N > 0 && (!boxes || !scores)) why = "null boxes or scores";
+    if (why) { g_op_error = std::string("cf_op_draw: ") + why; return CF_EINVAL; }
+    if (N == 0) return CF_OK;
+    const size_t cap = (size_t)B * rows;
+    std::vector<float> sb(cap * 4, 0.0f), ss(cap, 0.0f), sl(lms ? cap * 10 : 0, 0.0f);
+    std::vector<int32_t> si(info ? cap * 3 : 0, 0);
+    for (long long b = 0, at = 0; b < B; at += counts[b], ++b) {
+        const size_t n = (size_t)counts[b], to = (size_t)b * rows;
+        if (!n) continue;
+        memcpy(&sb[to * 4], boxes + at * 4, n * 4 * sizeof(float));
+        memcpy(&ss[to], scores + at, n * sizeof(float));
+        if (lms) memcpy(&sl[to * 10], lms + at * 10, n * 10 * sizeof(float));
+        if (info) memcpy(&si[to * 3], info + at * 3, n * 3 * sizeof(int32_t));
+    }
+    Scope sc(device);
+    DrawParams p{};
+    p.o = *o;
+    p.r = DrawRows{sc.upv(sb), sc.upv(ss), 1, lms ? sc.upv(sl) : nullptr, info ? (const int32_t*)sc.up(si.data(), si.size() * sizeof(int32_t)) : nullptr,
+                   (const int*)sc.up(counts, (size_t)B * sizeof(int)), rows, rows, H, W};
+    const RedactStage st = redact_stage_layout(format, h, w);
+    uint8_t* stage = (uint8_t*)sc.alloc(st.one * B);
+    const std::vector<const void*> dev = stage_table(st, stage, format, B);
+    p.g = FrameGeo{format, B, h, w, st.pitch0, st.pitch1}; p.planes = dev.data();
+    p.recs = (DrawRec*)sc.alloc(draw_scratch_bytes(B, rows));
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, true));
+    if (sc.err == hipSuccess) sc.chk(launch_draw_faces(sc.s, p));
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, false));
+    return sc.result("cf_op_draw");
+}
+
 int cf_tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, cf_tile_rect* rects, int cap, int* n) {
     const int r = tile_grid(h, w, tile_h, tile_w, overlap, with_full, rects, cap, n);
     if (r) g_op_error = "cf_tile_grid: h, w, tile_h, tile_w, overlap must be even, the sizes at least 2, 0 <= overlap < min(tile_h, tile_w); n not null";

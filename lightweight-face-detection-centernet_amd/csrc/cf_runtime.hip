@@ -156,7 +156,7 @@ struct cf_ctx {
     RowStage stage = ROWS_NONE;
     // scratch, grown to the largest need seen: chips and matrices of the host-output align forms (al_off: their [max_batch + 1] offsets),
     // the mosaic's cell means (one dword per grid cell), the frames of the host forms and the blur's mirror of them
-    DevBuf al_chips, al_mats, rd_cells, rd_stage, bl_scratch; int* al_off = nullptr;
+    DevBuf al_chips, al_mats, rd_cells, rd_stage, bl_scratch, dr_recs; int* al_off = nullptr;
     // cf_forward_tiles: the rectangles of the last forward when it was a tiled one (tl_T = 0: it was not; host copy and device table,
     // uploaded when they change) and the frame geometry.  cf_merge_tiles: its workspace and the merged rows, tl_maxout per frame
     std::vector<cf_tile_rect> tl_rects; DevBuf tl_rects_dev; int tl_rects_up = 0;
@@ -659,7 +659,7 @@ int cf_destroy(cf_ctx* c) {
                     (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow,
                     (void*)c->t_lmsnet, (void*)c->al_off, (void*)c->t_detsnet})
         if (p) hipFree(p);
-    for (const DevBuf* b : {&c->src.buf, &c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->tl_rects_dev,
+    for (const DevBuf* b : {&c->src.buf, &c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->dr_recs, &c->tl_rects_dev,
                             &c->tl.cand, &c->tl.cand_count, &c->tl.order, &c->tl.mask, &c->tl.dets, &c->tl.lms, &c->tl.corners, &c->tl.counts, &c->tl.flags,
                             &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags})
         if (b->p) hipFree(b->p);
@@ -1870,6 +1870,34 @@ int cf_blur_faces(cf_ctx* c, const cf_blur_opts* o, int format, const cf_planes_
     return on_frames(c, "cf_blur_faces", p.g, planes, on_device, true, [&](const void* const* pl, int p0, int p1) {
         p.planes = pl; p.g.pitch0 = p0; p.g.pitch1 = p1;
         return launch_blur_faces(c->stream, p);
+    });
+}
+
+// Annotation (cf_draw.hip): cf_redact_faces' rows, frames and state rules, plus each row's score, landmarks and -- behind an update --
+// track info.  The scratch of one record per (image, row) grows to the largest B x rows seen, outside any graph, like the mosaic's
+// cell means.  No state of the context is changed.
+int cf_draw_faces(cf_ctx* c, const cf_draw_opts* o, int format, const cf_planes_rw* frames, int on_device, int B, int h, int w,
+                  int pitch0, int pitch1) {
+    if (!c) return CF_EINVAL;
+    if (!o) return c->fail(CF_EINVAL, "cf_draw_faces: null options");
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    if (const char* why = draw_check(o, format, B, h, w, pitch0, pitch1))
+        return c->fail(CF_EINVAL, "cf_draw_faces: %s", why);
+    if (const char* why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1))
+        return c->fail(CF_EINVAL, "cf_draw_faces: %s", why);
+    RowSet rows{};
+    if (int r = frame_rows(c, "cf_draw_faces", B, h, w, rows)) return r;
+    const bool tracked = c->stage >= ROWS_TRACKED;
+    if (o->label == CF_DRAW_LABEL_ID && !tracked) return c->fail(CF_ESTATE, "cf_draw_faces: CF_DRAW_LABEL_ID without a cf_track_update behind the last decode");
+    HIPCHK(c, hipSetDevice(c->device));
+    DrawParams p{};
+    p.g = FrameGeo{format, B, h, w, pitch0, pitch1}; p.o = *o;
+    p.r = DrawRows{rows.corners, rows.dets + 4, 5, rows.lms, tracked ? (const int32_t*)c->tk.info.p : nullptr, rows.counts, rows.stride, rows.stride, rows.H, rows.W};
+    if (int r = grow(c, c->dr_recs, draw_scratch_bytes(B, rows.stride), "draw records", "cf_draw_faces")) return r;
+    p.recs = (DrawRec*)c->dr_recs.p;
+    return on_frames(c, "cf_draw_faces", p.g, planes, on_device, true, [&](const void* const* pl, int p0, int p1) {
+        p.planes = pl; p.g.pitch0 = p0; p.g.pitch1 = p1;
+        return launch_draw_faces(c->stream, p);
     });
 }
 

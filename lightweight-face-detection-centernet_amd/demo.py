@@ -81,6 +81,31 @@ def anonymize_file(path, out_path, **options):
     return results[0]
 
 
+def annotate_file(path, out_path, **options):
+    """demo.py:30-51 (``test_image`` with its drawing loop): read one image file, draw every detection on the device
+    (``CenterFace.annotate``: green boxes, red landmark dots, the score as a label; ``options`` as there) and write the result to
+    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``: sliced inference as ``anonymize_file``."""
+    from PIL import Image
+    from .centerface import CenterFace
+    frame = imread(path)
+    tiled = int(options.pop("tiled", 0) or 0)
+    dtype = options.pop("dtype", "bf16")
+    if tiled:
+        from . import ops
+        frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
+        T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
+        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T)
+        options["tiled"] = True
+    else:
+        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype)
+    try:
+        frames, results = detector.annotate([frame], **options)
+    finally:
+        detector.close()
+    Image.fromarray(np.ascontiguousarray(frames[0][:, :, ::-1])).save(out_path)
+    return results[0]
+
+
 def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16"):
     """Read one image file and write the aligned chip of every detected face, cut from the image at its own resolution
     (``CenterFace.detect_aligned_frames``), to ``out_dir``/<image name>_<k>.png.  Returns (detections, the paths written).
@@ -109,7 +134,9 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16"):
 
 
 def main(argv=None):
-    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR] [--tiled N]``: print the detections of one image file; with
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N]``: print the detections of one image
+    file; with ``--draw`` also write the image with every detection drawn into it (boxes, landmark dots and, unless ``--label none``,
+    the score); with
     ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``; or blurred: ``--blur [R]``, R = the
     filter strength 1..24, without it or 0 an eighth of each face's smaller side); with ``--chips`` write one aligned
     ``--size`` x ``--size`` chip per face, cut from the image at its own resolution, into DIR; with ``--tiled N`` beside either the
@@ -127,14 +154,20 @@ def main(argv=None):
     ap.add_argument("--tiled", type=int, default=0, metavar="N", help="with --anonymize / --chips: detect on overlapping N x N tiles (N a multiple of 32)")
     ap.add_argument("--chips", metavar="DIR", help="write the aligned chip of every detected face, cut from the image itself, into DIR")
     ap.add_argument("--size", type=int, default=112, help="with --chips: the chip side (a multiple of 4 in [16, 512])")
+    ap.add_argument("--draw", metavar="OUT", help="write the image with every detection drawn into it to OUT")
+    ap.add_argument("--label", default="score", choices=("score", "none"), help="with --draw: the number above each box")
     args = ap.parse_args(argv)
-    if args.tiled and not (args.anonymize or args.chips):
-        ap.error("--tiled goes with --anonymize or --chips")
+    if args.tiled and not (args.anonymize or args.chips or args.draw):
+        ap.error("--tiled goes with --anonymize, --chips or --draw")
+    if args.draw and (args.anonymize or args.chips):
+        ap.error("--draw, --anonymize and --chips are separate runs")
     if args.blur is not None and not args.anonymize:
         ap.error("--blur goes with --anonymize")
     if args.anonymize and args.chips:
         ap.error("--anonymize and --chips are separate runs")
-    if args.chips:
+    if args.draw:
+        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled)
+    elif args.chips:
         (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled)
     elif args.anonymize and args.blur is not None:
         dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled)

@@ -270,6 +270,54 @@ def blur_faces(frames, boxes, counts, net_hw, fmt="bgr", shape="ellipse", radius
     return frames
 
 
+def bgr_to_yuv_color(bgr):
+    """(Y, U, V) of a (B, G, R) byte triple: integer BT.601 limited range, ``>> 8`` as floor division.  White -> (235, 128, 128),
+    black -> (16, 128, 128), the reference's box green (2, 255, 0) -> (145, 55, 34)."""
+    b, g, r = (int(v) for v in bgr)
+    return (((66 * r + 129 * g + 25 * b + 128) >> 8) + 16, ((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128,
+            ((112 * r - 94 * g - 18 * b + 128) >> 8) + 128)
+
+
+def _draw_rows(boxes, scores, counts, B, lms, info):
+    boxes, counts = _lib.box_rows(boxes, counts, B)
+    N = boxes.shape[0]
+    scores = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
+    lms = None if lms is None else np.ascontiguousarray(lms, dtype=np.float32).reshape(-1, 10)
+    info = None if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(-1, 3)
+    for a, what in ((scores, "scores"), (lms, "lms"), (info, "info")):
+        if a is not None and a.shape[0] != N:
+            raise ValueError("%s has %d rows, boxes %d" % (what, a.shape[0], N))
+    return boxes, scores, counts, lms, info
+
+
+def draw_faces(frames, boxes, scores, counts, net_hw, fmt="bgr", lms=None, info=None, device=0, **opts):
+    """Annotation in the frame (``cf_op_draw``): ``frames`` as ``redact_faces`` takes them are modified IN PLACE and returned.  boxes
+    [N,4] x1,y1,x2,y2 and lms [N,10] in the coordinates of a network input of ``net_hw`` = (H, W), scores [N], info [N,3] = id, hits,
+    misses (``None``: all rows live), image after image, counts [B].  ``opts``: those of ``_lib.draw_opts`` -- boxes, landmarks,
+    thickness, radius, label ('none' | 'score' | 'id'), label_scale, dash_held, scale and the four colours, bytes in the frame's own
+    channel order."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt)
+    boxes, scores, counts, lms, info = _draw_rows(boxes, scores, counts, B, lms, info)
+    o = _lib.draw_opts(**opts)
+    _lib.check(_lib.lib().cf_op_draw(device, C.byref(o), _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, ptr(boxes), ptr(scores), ptr(lms),
+                                     ptr(info), ptr(counts), int(net_hw[0]), int(net_hw[1])), op=True)
+    del keep
+    return frames
+
+
+def draw_layout(box, score, frame_hw, net_hw, lms=None, info=None, **opts):
+    """One row's integer geometry (``cf_draw_layout``; host only, the code the kernels run): int32 [32] = ok, X1, Y1, X2, Y2, held, plate
+    x0, y0, Pw, Ph, n, ten digits, the landmarks' valid bits, Lx0, Ly0 .. Lx4, Ly4."""
+    box = np.ascontiguousarray(box, dtype=np.float32).reshape(4)
+    lms = None if lms is None else np.ascontiguousarray(lms, dtype=np.float32).reshape(10)
+    info = None if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(3)
+    out = np.zeros((32,), np.int32)
+    o = _lib.draw_opts(**opts)
+    _lib.check(_lib.lib().cf_draw_layout(C.byref(o), ptr(box), float(np.float32(score)), ptr(lms), ptr(info), int(frame_hw[0]), int(frame_hw[1]),
+                                         int(net_hw[0]), int(net_hw[1]), ptr(out)), op=True)
+    return out
+
+
 def tile_grid(h, w, tile, overlap, with_full=True):
     """The rectangles of sliced inference (``cf_tile_grid``; host only): int32 [T][4] rows (x0, y0, w, h) covering an h x w frame with
     tiles of ``tile`` = (tile_h, tile_w) or one int, neighbours sharing at least ``overlap`` pixels, row-major; the whole frame is

@@ -435,7 +435,7 @@ int cf_merge_tiles(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* d
  *      id, hits, misses (int32).  misses == 0: the box bit for bit.  misses > 0 (held): the box grown about its centre, in float64:
  *      cx = ((double)x1 + (double)x2) * 0.5; hw = ((double)x2 - (double)x1) * 0.5 * (1.0 + (double)hold_grow * (double)misses);
  *      x1' = (float)(cx - hw), x2' = (float)(cx + hw); y likewise.  THE LANDMARKS OF A HELD ROW ARE THE LAST ONES SEEN (not grown, not
- *      moved): chips cut from them by cf_align_faces_frame show whatever is at that place now.
+ *      moved): chips cut from them by cf_align_faces_frame show whatever is at that place now.  (cf_track_follow, below, moves both.)
  * Coordinates are whatever the rows are in: network coordinates after an ordinary forward (whatever cf_set_rescale says), frame pixels
  * after cf_merge_tiles.  The tracker latches that space -- (not tiled, H, W), or (tiled, h, w) -- on its first update and refuses
  * another with CF_EINVAL. */
@@ -471,6 +471,72 @@ int cf_track_reset(cf_tracker* trk, int stream);
  * are those of the rows the update consumed.  Without an update they do exactly what they did before. */
 int cf_track_update(cf_ctx* ctx, cf_tracker* trk, int stream0, float* dets, float* lms, int32_t* info,
                     int32_t* counts, int32_t* flags, int out_on_device);
+
+/* ---- follow tracked faces between detections: block matching in the frame, on the device -----
+ * cf_track_update leaves two holes: a held track does not move (hold_grow only inflates its box blindly, and its landmarks stay where
+ * the face was), and every frame needs a forward, because the tracker advances only behind a decode.  cf_track_follow measures, from
+ * the pixels of a new frame and WITHOUT A FORWARD, where every tracked face went, and moves the tracker's state there:
+ *   key frame:       cf_forward* -> cf_decode_threshold* [-> cf_merge_tiles] -> cf_track_update -> cf_track_follow -> cf_redact_faces | ...
+ *   frames between:                                                                                cf_track_follow -> cf_redact_faces | ...
+ * The arithmetic is this library's own statement (csrc/cf_follow.hip; restated in tests/follow_cases.py; device and restatement are
+ * equal bit for bit).  Integers throughout, except the box geometry and the move: float64 in the order written, no FMA contraction.
+ * The defaults the Python layer uses (search 4, max_sad 4096) are this project's choices; no accuracy claim is made for them.
+ *
+ * P = 16 is the template side in cells, R = opts->search.  A tracker that was followed at least once holds, per slot, a follower record
+ * (allocated by the first follow, 280 bytes per slot, all zero at first): tpl[16][16] uint8, tpl_c, tpl_id, tpl_box[4] = the bit
+ * patterns of the slot's box as the follower last left it.
+ *   Luma.  Of a 4:2:0 frame: the sample's Y byte.  Of a BGR frame: (29*B + 150*G + 77*R + 128) >> 8.
+ *   Geometry.  Frames of h x w; the tracker's latched row space is H x W.  Network space: fx = (double)w / (double)W, fy = (double)h /
+ *   (double)H.  Frame space (rows of cf_merge_tiles): fx = fy = 1, and (h, w) must be the latched size.  For every alive slot of the
+ *   streams stream0 .. stream0 + B - 1, with the slot's box (x1, y1, x2, y2) as the state holds it (not grown):
+ *     side = max(((double)x2 - (double)x1) * fx, ((double)y2 - (double)y1) * fy).  The slot is skipped, code NONE, when a corner is not
+ *     finite or side is not > 0.
+ *     cx = ((double)x1 + (double)x2) * 0.5 * fx clamped to [-8192, 16384], CX = (int)floor(cx); CY likewise with y and fy.
+ *     S = (int)ceil(side clamped to [1, 8192]); cell size c = (S + 15) / 16 (integer division; 1..512).
+ *   Cell (i, j) about (CX, CY), i and j possibly negative, covers the pixels [CX + i*c, CX + (i+1)*c) x [CY + j*c, CY + (j+1)*c), their
+ *   coordinates clamped into the frame (the border replicates); its value is (sum of luma + c*c/2) / (c*c) (the sum fits int32).
+ *   Learn or follow, decided per slot on the device:
+ *     LEARN when tpl_id != id or the box differs in any bit from tpl_box -- the slot is new, or an update matched a detection into it.
+ *       tpl = the cells i, j in [-8, 8) of this frame, tpl_c = c, tpl_id = id, tpl_box = the box.  Code LEARNED, moves 0, 0, 0.
+ *     FOLLOW otherwise, with c = tpl_c.  Window: the cells i, j in [-8-R, 8+R) about the CURRENT (CX, CY).  For every (dx, dy) in
+ *       [-R, R]^2: SAD = sum over the 256 template cells of |win[j+dy][i+dx] - tpl[j][i]|.  The best displacement has the smallest SAD,
+ *       then the smallest dx*dx + dy*dy, then the smallest dy, then the smallest dx; px = dx*c, py = dy*c.
+ *       SAD > max_sad: code LOST, nothing moves (moves = px, py, SAD of the best displacement all the same).
+ *       Otherwise every x of the box and of the ten landmarks becomes (float)((double)x + (double)px / fx), every y
+ *       (float)((double)y + (double)py / fy); the state and tpl_box take the new box; code MOVED.
+ *       THE TEMPLATE IS NOT REFRESHED BY A FOLLOW: it stays that of the last detection, so the quantisation to c pixels does not add up.
+ *   hits, misses, ids and flags are untouched: a followed frame is not a detection opportunity, max_age keeps counting detections.
+ *   Output.  The context's tracked rows are written again from the state by step 5 of cf_track_update (alive slots in slot order, held
+ *   boxes grown by hold_grow, info = id, hits, misses), and moves[B][max_tracks][4] int32 = px, py, SAD, code in the same row order.
+ * So: at a key frame (update, then follow) the matched and the newborn slots learn and the held slots move with their face; between
+ * key frames every slot moves; a slot reused under a new id learns again; cf_track_reset needs no word about the follower.
+ * On the device: one workgroup per (slot, stream) and a second launch of one wave per stream for the rows.  THE COST GROWS WITH THE
+ * FACE'S AREA: c*c pixels per cell, (16 + 2R)^2 cells per followed face. */
+#define CF_FOLLOW_NONE    0
+#define CF_FOLLOW_LEARNED 1
+#define CF_FOLLOW_MOVED   2
+#define CF_FOLLOW_LOST    3
+typedef struct cf_follow_opts {
+    int32_t search;       /* R, 1..8 cells */
+    int32_t max_sad;      /* 0..65280: a best match above it is LOST */
+} cf_follow_opts;
+/* Follows the streams stream0 .. stream0 + B - 1 of trk in frames[b] (b < B; frame b is the current frame of stream stream0 + b).
+ * Frames, formats, pitches, alignment and on_device are those of cf_redact_faces; the frames are only read (host frames are copied up,
+ * never back).  IT NEEDS NO FORWARD ON ctx: everything comes from the tracker, so a chunk loop or a ring of contexts can follow any
+ * streams on any context of the tracker's device.  The call orders itself on the tracker's event exactly as cf_track_update does.
+ * dets [B][max_tracks][5], lms [B][max_tracks][10], info [B][max_tracks][3], counts [B], moves [B][max_tracks][4]; any may be NULL;
+ * out_on_device as for cf_track_update.
+ * CF_ESTATE when the tracker was never updated (it has no row space yet).  CF_EINVAL, before any GPU work, for: bad options, a stream
+ * range outside the tracker, B outside 1..max_batch, a tracker of another device, in frame space an (h, w) that is not the latched one,
+ * and every geometry and plane error of the redaction (ctx == NULL: the options and the geometry are still checked first,
+ * cf_op_last_error names the cause).  CF_ENOMEM, before any launch, when the follower records do not fit.
+ * Afterwards, and until the next forward, threshold decode, merge or update on ctx, cf_redact_faces, cf_blur_faces,
+ * cf_align_faces_frame and cf_draw_faces (CF_DRAW_LABEL_ID included) take THESE rows: their B is the follow's B, their coordinates the
+ * tracker's space.  Calls that name the decode's own rows -- cf_align_faces, cf_merge_tiles -- and the refusal of a second
+ * cf_track_update behave as before. */
+int cf_track_follow(cf_ctx* ctx, cf_tracker* trk, int stream0, int B, const cf_follow_opts* opts, int format, const cf_planes_rw* frames,
+                    int on_device, int h, int w, int pitch0, int pitch1, float* dets, float* lms, int32_t* info, int32_t* counts,
+                    int32_t* moves, int out_on_device);
 
 /* ---- annotation: box outlines, landmark dots and a numeric label IN THE SOURCE FRAME, on the device --------------------------- */
 /* What demo.py:15-23, 40-51 does with a detection -- cv2.rectangle(frame, .., (2, 255, 0), 1) per box, cv2.circle(frame, .., 2,
@@ -826,6 +892,19 @@ int cf_op_merge_tiles(int device, const cf_merge_opts* opts, const cf_tile_rect*
 int cf_op_track(int device, const cf_track_opts* opts, int n_streams, int n_frames, int rows, const float* boxes,
                 const float* scores, const float* lms_in, const int32_t* counts_in,
                 float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags);
+/* The kernels of cf_track_update and cf_track_follow over a whole sequence, on host tables and host frames, with a fresh tracker of
+ * n_streams streams whose row space is space_h x space_w (tiled = 0: network space, fx = w / space_w, fy = h / space_h; tiled = 1:
+ * frame space, (space_h, space_w) must be (h, w)).  Frame f of stream s: where detect[f] is not 0 the update with the rows
+ * i < min(counts_in[f][s], rows) of boxes [F][S][rows][4], scores [F][S][rows], lms_in [F][S][rows][10] (as cf_op_track) runs first;
+ * then the follow on frames[f * S + s] (F * S host frames of h x w in `format`, pitches as cf_redact_faces; only read).  Outputs after
+ * each frame: dets [F][S][max_tracks][5], lms [F][S][max_tracks][10], info [F][S][max_tracks][3], counts [F][S], flags [F][S] (0 where
+ * no update ran), moves [F][S][max_tracks][4]; rows at and past a count keep the caller's bytes.  All pointers host, none NULL.  The
+ * option checks of cf_track_create and cf_track_follow, the geometry and plane checks of cf_redact_faces and the limits of cf_op_track,
+ * before any device is touched; nothing is written on refusal. */
+int cf_op_follow(int device, const cf_track_opts* opts, const cf_follow_opts* fopts, int n_streams, int n_frames, int rows,
+                 const float* boxes, const float* scores, const float* lms_in, const int32_t* counts_in, const uint8_t* detect,
+                 int format, const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h, int space_w, int tiled,
+                 float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, int32_t* moves);
 /* The kernels of cf_draw_faces alone, on host frames (modified in place): boxes [N][4] x1,y1,x2,y2 in the coordinates of an H x W
  * network input, scores [N], lms [N][10] or NULL, info [N][3] = id, hits, misses or NULL (all live), image after image, counts [B]
  * (>= 0, N = their sum).  The same validation as cf_draw_faces, before any device is touched; NULL lms with CF_DRAW_LANDMARKS and

@@ -51,6 +51,7 @@ EXPORTS = (
     "cf_draw_faces", "cf_op_draw", "cf_draw_layout",
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
+    "cf_track_follow", "cf_op_follow",
 )
 
 
@@ -215,6 +216,19 @@ class TrackOpts(C.Structure):
 def track_opts(iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0):
     """TrackOpts (the library validates the numbers).  The defaults are this project's choices; no accuracy claim is made for them."""
     return TrackOpts(float(iou), int(max_age), int(min_hits), int(max_tracks), float(hold_grow))
+
+
+CF_FOLLOW_NONE, CF_FOLLOW_LEARNED, CF_FOLLOW_MOVED, CF_FOLLOW_LOST = 0, 1, 2, 3
+
+
+class FollowOpts(C.Structure):
+    """cf_follow_opts: search radius R in cells / the largest SAD of a match that still moves the track."""
+    _fields_ = [("search", C.c_int32), ("max_sad", C.c_int32)]
+
+
+def follow_opts(search=4, max_sad=4096):
+    """FollowOpts (the library validates the numbers).  The defaults are this project's choices; no accuracy claim is made for them."""
+    return FollowOpts(int(search), int(max_sad))
 
 
 def tile_rects(rects):
@@ -457,6 +471,10 @@ def lib():
         L.cf_track_reset.argtypes = [C.c_void_p, C.c_int]
         L.cf_track_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         L.cf_op_track.argtypes = [C.c_int, C.POINTER(TrackOpts)] + [C.c_int] * 3 + [C.c_void_p] * 9
+        L.cf_track_follow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(FollowOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + \
+            [C.c_void_p] * 5 + [C.c_int]
+        L.cf_op_follow.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(FollowOpts)] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.POINTER(PlanesRW)] + \
+            [C.c_int] * 7 + [C.c_void_p] * 6
         L.cf_get_resized_input.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.cf_get_heads.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.cf_decode_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

@@ -517,6 +517,38 @@ class Engine(object):
         self._chk(self._L.cf_track_update(self._h, tracker._handle(self), int(stream0), vp(dets_ptr), vp(lms_ptr), vp(info_ptr), vp(counts_ptr),
                                           vp(flags_ptr), 1))
 
+    def track_follow(self, frames, fmt, tracker, stream0=0, *, search=4, max_sad=4096):
+        """Follow the faces ``tracker`` holds into ``frames`` by block matching, WITHOUT a forward (``cf_track_follow``, host form): frame b
+        is the current frame of stream ``stream0 + b`` -- host frames as ``redact_faces`` takes them, only read, of any size when the
+        tracker's rows are in network coordinates (mapped by w / W, h / H), of the tiled frames' size when they are in frame pixels.  A
+        slot that an update has just filled or matched learns a 16 x 16 cell template of its face; any other is searched within
+        ``search`` cells of where it was and, with a best sum of absolute differences of at most ``max_sad``, moved there -- box and
+        landmarks, in the tracker's state.  ``search=4`` and ``max_sad=4096`` are this project's choices; no accuracy claim is made for
+        them.  Needs one ``track_update`` on the tracker before the first call, and none on this engine.  Returns (dets [B,M,5], lms
+        [B,M,10], info [B,M,3] = id, hits, misses, counts [B], moves [B,M,4] = px, py, SAD, code (``_lib.CF_FOLLOW_*``)), M =
+        ``max_tracks``, rows below counts[b] valid.  Until the next forward, decode, merge or update on this engine, ``redact_faces`` /
+        ``blur_faces`` / ``align_faces_frame`` / ``draw_faces`` use these rows."""
+        args, keep = _lib.host_frame_args(frames, fmt, writable=False)
+        f, tab, dev, B, h, w, pitch0, pitch1 = args
+        M = tracker.max_tracks
+        dets, lms = np.zeros((B, M, 5), np.float32), np.zeros((B, M, 10), np.float32)
+        info, moves, counts = np.zeros((B, M, 3), np.int32), np.zeros((B, M, 4), np.int32), np.zeros((B,), np.int32)
+        o = _lib.follow_opts(search, max_sad)
+        self._chk(self._L.cf_track_follow(self._h, tracker._handle(self), int(stream0), B, C.byref(o), f, tab, dev, h, w, pitch0, pitch1,
+                                          _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(info), _lib.ptr(counts), _lib.ptr(moves), 0))
+        return dets, lms, info, counts, moves
+
+    def track_follow_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1, tracker, stream0=0, *, search=4, max_sad=4096, dets_ptr=None,
+                            lms_ptr=None, info_ptr=None, counts_ptr=None, moves_ptr=None):
+        """Same, reading DEVICE planes in place as ``redact_faces_device`` takes them and writing caller-owned DEVICE buffers (any may
+        be None): asynchronous on the engine's main stream behind the tracker's last update or follow; nothing is read on the host.
+        The context keeps the followed rows either way."""
+        f, tab, dev, B, h, w, pitch0, pitch1 = _lib.device_frame_args("track_follow_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1)
+        o = _lib.follow_opts(search, max_sad)
+        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
+        self._chk(self._L.cf_track_follow(self._h, tracker._handle(self), int(stream0), B, C.byref(o), f, tab, dev, h, w, pitch0, pitch1,
+                                          vp(dets_ptr), vp(lms_ptr), vp(info_ptr), vp(counts_ptr), vp(moves_ptr), 1))
+
     # -- launch plan / layer trace (parity tests) ---------------------------------------------
     def plan(self):
         """The context's launch plan: list of dicts name/kind/C/H/W/fused_away."""
@@ -919,28 +951,64 @@ class CenterFace(object):
         """The results of the forward last enqueued on ``eng``; the rescale (centerface.py:55-62) was done by the decode kernel."""
         return self._postprocess_many(eng.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)
 
-    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None):
+    def _follow(self, follow, detect, tracker, frames, fmt):
+        """The ``follow`` / ``detect`` arguments of the product paths -> the ``follow`` of ``_drive``: None, or (frames, fmt, options
+        of ``Engine.track_follow``).  ``follow``: None / False, True (the defaults) or a dict with search and / or max_sad;
+        ``detect=False`` follows in any case.  Both need a tracker."""
+        if detect and not follow:
+            return None
+        if tracker is None:
+            raise ValueError("follow= and detect=False need tracker=")
+        o = dict(follow) if isinstance(follow, dict) else {}
+        if set(o) - {"search", "max_sad"}:
+            raise ValueError("follow takes search and max_sad, got %s" % sorted(o))
+        return frames, fmt, o
+
+    def _followed(self, dets, lms, counts, hw, tiled):
+        """The per-frame results of a chunk that was only followed: the tracked rows mapped from the tracker's space to frame pixels in
+        float64 (w / W, h / H of the network input; rows of a tiled path are in frame pixels already), not floored."""
+        fx, fy = (1.0, 1.0) if tiled else (float(hw[1]) / float(self.img_w_new), float(hw[0]) / float(self.img_h_new))
+        out = []
+        for b, n in enumerate(counts):
+            d, l = dets[b, :n].astype(np.float64), lms[b, :n].astype(np.float64)
+            d[:, 0:4:2] *= fx
+            d[:, 1:4:2] *= fy
+            l[:, 0::2] *= fx
+            l[:, 1::2] *= fy
+            out.append((d, l) if self.landmarks else d)
+        return out
+
+    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None, follow=None, detect=True):
         """The chunk loop of every product path: ``forward`` enqueues ``frames`` in slices of ``per`` (default ``max_batch``), each is
         decoded, and while the engine still holds it the steps that were asked for run in this order: ``tracker`` is advanced -- image b
         of the chunk that starts at frame i continues its stream i + b --, ``cover`` = (array, fmt, options) has the chunk's slice of
         the array covered, ``draw`` = (array, fmt, options) has it annotated (``Engine.draw_faces``), ``chips(i, j)`` cuts the chips of
-        frames i:j, which join the results.  ``merge`` = (metric, thresh, edge) says
+        frames i:j, which join the results.  ``follow`` = (array, fmt, options) has the tracker's faces followed in the chunk's slice of
+        the array right behind the update (``Engine.track_follow``), before anything is covered or drawn; with ``detect=False`` there is no
+        forward, decode or update at all -- each chunk is followed, then covered or drawn, and its results are the followed rows
+        (``_followed``).  ``merge`` = (metric, thresh, edge) says
         that the forward is a tiled one: the tiles' rows are merged, in frame pixels; otherwise the decode rescales, and the rescale is
         switched off again whatever happens.  Returns the per-frame results."""
         eng, out = self.engine, []
         per = per or eng.max_batch
-        if merge is None:
+        if merge is None and detect:
             eng.set_rescale(self.scale_h, self.scale_w)                      # centerface.py:55-62 inside the decode kernel
         try:
             for i in range(0, len(frames), per):
-                forward(frames[i:i + per])
-                if merge is None:
-                    res = self._decode(eng)
-                else:
-                    eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
-                    res = self._postprocess_many(eng.merge_tiles(*merge, self.max_dets)[0], rescaled=True)
-                if tracker is not None:
-                    eng.track_update_device(tracker, i)
+                if detect:
+                    forward(frames[i:i + per])
+                    if merge is None:
+                        res = self._decode(eng)
+                    else:
+                        eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
+                        res = self._postprocess_many(eng.merge_tiles(*merge, self.max_dets)[0], rescaled=True)
+                    if tracker is not None:
+                        eng.track_update_device(tracker, i)
+                if follow is not None:
+                    part = follow[0][i:i + per]
+                    d, l, _, n, _ = eng.track_follow(part, follow[1], tracker, i, **follow[2])
+                    if not detect:
+                        res = self._followed(d, l, n, _lib.frame_planes(part, follow[1], writable=False)[2:4], merge is not None)
                 if cover is not None:
                     eng.cover_faces(cover[0][i:i + per], cover[1], **cover[2])
                 if draw is not None:
@@ -950,7 +1018,7 @@ class CenterFace(object):
                     res = [(d, l, cut[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(res)]
                 out.extend(res)
         finally:
-            if merge is None:
+            if merge is None and detect:
                 eng.set_rescale(0.0, 0.0)
         return out
 
@@ -1000,7 +1068,7 @@ class CenterFace(object):
         return lambda chunk: self.engine.forward_tiles_enqueue(chunk, rects, fmt), per
 
     def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None,
-                     tracker=None):
+                     tracker=None, follow=None, detect=True):
         """Sliced inference for frames much larger than the network input, whose small faces the stretch-resize of ``detect_batch``
         loses: every frame is cut on the device into overlapping tiles of ``tile`` (default: the network's (H, W)) that share at
         least ``overlap`` pixels (default: a quarter of the tile, rounded down to even), plus the whole frame as one more tile; the
@@ -1012,13 +1080,14 @@ class CenterFace(object):
         ``Engine.blur_faces``; the frames are then redacted IN PLACE with the merged boxes.  ``tracker``: a ``Tracker`` whose
         stream k the k-th frame of this call continues (frame pixels): it is advanced behind the merge, and the redaction then covers
         the tracked rows -- the merged detections plus the tracks held through a dropout; the detections returned stay the frame's
-        own."""
+        own.  ``follow`` and ``detect``: as ``anonymize`` (``redact=`` only; the frames are followed as they are before the redaction)."""
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         return self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, with_full, redact is not None), merge=(metric, thresh, edge),
-                           tracker=tracker, cover=None if redact is None else (frames, fmt, redact))
+                           tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
+                           follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect)
 
-    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, **options):
+    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
         cell, scale, fill) or, with ``mode='blur'``, blurred (``Engine.blur_faces``; shape, radius, scale), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
@@ -1026,25 +1095,33 @@ class CenterFace(object):
         any even size, redaction with the merged boxes; the detections are then in frame pixels.  ``tracker``: a ``Tracker`` (default none: every
         call stands alone) whose stream k the k-th image of this call continues -- a video is fed one call per frame, n cameras n images per
         call; it is advanced between the decode (the merge) and the redaction, which then covers the detections of this frame AND the
-        tracks held through a dropout.  The detections returned stay the frame's own."""
+        tracks held through a dropout.  The detections returned stay the frame's own.  ``follow`` (needs ``tracker``): True, or a dict with
+        ``search`` and / or ``max_sad`` (``Engine.track_follow``; the defaults 4 and 4096 are this project's choices, no accuracy claim is
+        made): right behind the update the tracker's faces are followed in the frame by block matching, so a track held through a dropout
+        moves with its face instead of staying where it was last detected.  ``detect=False`` (needs ``tracker``, which a call with
+        detection has advanced before): NO FORWARD -- the faces are only followed from where the tracker has them, then covered; the
+        results are then the tracked rows (held ones included) mapped to frame pixels in float64, not floored.  Detecting every Nth
+        frame and following in between is the throughput lever for video.  With the defaults every call does what it did without them."""
         _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         if tiled:
-            return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker)
-        return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, cover=(out, "bgr", options))
+            return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker, follow=follow, detect=detect)
+        return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, cover=(out, "bgr", options),
+                                follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect)
 
-    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, **options):
+    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
-        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True`` and ``tracker``: as
-        ``anonymize``."""
+        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow`` and
+        ``detect``: as ``anonymize``."""
         _lib.split_redact_options(options)
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            return out, self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker)
+            return out, self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker, follow=follow, detect=detect)
         frames, forward = self._input_form(self.engine, frames, fmt)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
-        return out, self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options))
+        return out, self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options),
+                                follow=self._follow(follow, detect, tracker, out, fmt), detect=detect)
 
     def _draw_options(self, options, tracker, yuv):
         """The options of ``annotate`` / ``annotate_yuv`` -> those of ``Engine.draw_faces``: the reference's look (demo.py:15-23: green
@@ -1060,30 +1137,31 @@ class CenterFace(object):
         _lib.draw_opts(**o)                                                   # refuse bad names and colours before any work
         return o
 
-    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, **options):
+    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, **options):
         """``detect_batch`` plus the drawing of every detection, what demo.py:15-23 does with cv2 on the host: (frames_out, [(dets, lms),
         ...]) -- frames_out a uint8 [B,h,w,3] COPY of ``imgs`` with box outlines, landmark dots and a label painted on the device
         (``Engine.draw_faces``; ``options`` as there, colours as BGR triples).  ``tiled``, ``tile``, ``overlap`` and ``tracker`` as
         ``anonymize``: with a tracker the label is the track id and the tracks held through a dropout are drawn too, dashed, in
-        ``held_color``."""
+        ``held_color``.  ``follow`` and ``detect``: as ``anonymize``."""
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         draw = (out, "bgr", self._draw_options(options, tracker, False))
+        fo = dict(follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect)
         if tiled:
-            return out, self._drive(out, *self._tiled_form(out, "bgr", tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker, draw=draw)
-        return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, draw=draw)
+            return out, self._drive(out, *self._tiled_form(out, "bgr", tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker, draw=draw, **fo)
+        return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, draw=draw, **fo)
 
-    def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, **options):
+    def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, **options):
         """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
         in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``."""
         o = self._draw_options(options, tracker, True)
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
             return out, self._drive(out, *self._tiled_form(out, fmt, tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker,
-                                    draw=(out, fmt, o))
+                                    draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect)
         frames, forward = self._input_form(self.engine, frames, fmt)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
-        return out, self._drive(frames, forward, tracker=tracker, draw=(out, fmt, o))
+        return out, self._drive(frames, forward, tracker=tracker, draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect)
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]

@@ -491,6 +491,28 @@ struct TrackParams {
 const char* track_check(const cf_track_opts* o, int n_streams);
 hipError_t launch_track_update(hipStream_t s, const TrackParams& p);
 
+// The follower (cf_follow.hip; the statement is in include/centerface_hip.h): block matching of every alive slot of the streams
+// stream0 .. stream0 + g.B - 1 in the luma of the g.B frames, then the rows of TrackParams' step 5 again, from the moved state.
+constexpr int kFollowSide = 16, kFollowMaxSearch = 8, kFollowMaxSad = 255 * kFollowSide * kFollowSide;
+constexpr size_t kFollowSlotBytes = kFollowSide * kFollowSide + 6 * sizeof(int);      // tpl | tpl_c, tpl_id, tpl_box[4]
+struct FollowParams {
+    FrameGeo g;                  // pitch0 a multiple of 4; only plane 0 (BGR rows or the Y plane) is read
+    const void* const* planes;   // HOST table of g.B x {p0, p1, p2} DEVICE addresses (cf_frame.h), p0 4-byte aligned
+    int search, max_sad;
+    double fx, fy;               // frame pixels per unit of the rows' space: w / W, h / H, or 1.0 for rows in frame pixels
+    int stream0, max_tracks; float hold_grow;
+    // state (device), owned by the tracker: TrackParams' meta and rec, and the follower records of all n_streams x max_tracks slots
+    int* meta; float* rec;
+    uint8_t* tpl;                // [S][max_tracks][16][16]
+    int* tmeta;                  // [S][max_tracks][6]: tpl_c, tpl_id, the bits of tpl_box
+    int* slot_moves;             // scratch [g.B][max_tracks][4]: px, py, SAD, code per SLOT
+    // outputs (device), as TrackParams', plus moves [g.B][max_tracks][4] in the same row order
+    float* dets; float* lms_out; int* info; float* corners; int* out_counts; int* moves;
+};
+// nullptr, or what is wrong with the options / geometry (host only; no device is touched)
+const char* follow_check(const cf_follow_opts* o, int format, int B, int h, int w, int pitch0, int pitch1);
+hipError_t launch_track_follow(hipStream_t s, const FollowParams& p);
+
 // layout converters used by cf_get_heads and the per-op test entry points
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*T NHWC*/,
                                int B, int C, int H, int W);

@@ -964,15 +964,30 @@ int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* re
     return sc.result("cf_op_merge_tiles");
 }
 
-// The update of cf_track_update, frame after frame on one stream, with the state of a fresh tracker (no slot alive, next_id = 1).
-int cf_op_track(int device, const cf_track_opts* o, int n_streams, int n_frames, int rows, const float* boxes, const float* scores,
-                const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags) {
+}  // extern "C"
+
+namespace {
+
+// What cf_op_follow adds to cf_op_track's sequence: the follow of cf_track_follow behind every frame, the update only where `detect` says so
+struct OpFollow {
+    const cf_follow_opts* o; const uint8_t* detect; int format; const void* const* host_planes; int h, w, pitch0, pitch1, space_h, space_w, tiled;
+    int32_t* moves;
+};
+
+// The update of cf_track_update, frame after frame, with the state of a fresh tracker (no slot alive, next_id = 1); fw: each frame is then
+// followed in its host frames, staged as cf_op_redact stages them.
+int op_track_sequence(const char* who, int device, const cf_track_opts* o, int n_streams, int n_frames, int rows, const float* boxes, const float* scores,
+                      const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, const OpFollow* fw) {
     const char* bad = track_check(o, n_streams);
-    if (!bad && (!boxes || !scores || !lms_in || !counts_in || !dets || !lms || !info || !counts || !flags)) bad = "null argument";
+    if (!bad && fw) bad = follow_check(fw->o, fw->format, n_streams, fw->h, fw->w, fw->pitch0, fw->pitch1);
+    if (!bad && (!boxes || !scores || !lms_in || !counts_in || !dets || !lms || !info || !counts || !flags || (fw && (!fw->detect || !fw->moves)))) bad = "null argument";
     if (!bad && (n_frames < 1 || rows < 1)) bad = "n_frames and rows must be at least 1";
     if (!bad && (long long)n_frames * n_streams * std::max(rows, o->max_tracks) > (1 << 24)) bad = "more than 2^24 rows";
+    if (!bad && fw) bad = redact_check_planes(fw->format, fw->host_planes, n_frames * n_streams, 0, fw->pitch0, fw->pitch1);
+    if (!bad && fw && (fw->space_h < 1 || fw->space_w < 1 || (fw->tiled != 0 && fw->tiled != 1))) bad = "space_h and space_w must be at least 1, tiled 0 or 1";
+    if (!bad && fw && fw->tiled && (fw->space_h != fw->h || fw->space_w != fw->w)) bad = "rows in frame space need space_h x space_w = h x w";
     if (!bad) for (long long k = 0; k < (long long)n_frames * n_streams; ++k) if (counts_in[k] < 0) { bad = "negative count"; break; }
-    if (bad) { g_op_error = std::string("cf_op_track: ") + bad; return CF_EINVAL; }
+    if (bad) { g_op_error = std::string(who) + ": " + bad; return CF_EINVAL; }
     Scope sc(device);
     const size_t S = n_streams, F = n_frames, M = o->max_tracks, nin = F * S * rows, nout = F * S * M;
     TrackParams p{};
@@ -989,20 +1004,58 @@ int cf_op_track(int device, const cf_track_opts* o, int n_streams, int n_frames,
     p.info = (int*)sc.up(info, nout * 3 * sizeof(int));
     p.corners = (float*)sc.alloc(S * M * 4 * sizeof(float));
     p.out_counts = (int*)sc.alloc(F * S * sizeof(int)); p.flags = (int*)sc.alloc(F * S * sizeof(int));
+    FollowParams q{};
+    int* moves_dev = nullptr;
+    std::vector<const void*> dev;
+    if (fw) {
+        q.search = fw->o->search; q.max_sad = fw->o->max_sad;
+        q.fx = fw->tiled ? 1.0 : (double)fw->w / (double)fw->space_w; q.fy = fw->tiled ? 1.0 : (double)fw->h / (double)fw->space_h;
+        q.stream0 = 0; q.max_tracks = o->max_tracks; q.hold_grow = o->hold_grow; q.meta = p.meta; q.rec = p.rec; q.corners = p.corners;
+        q.tpl = (uint8_t*)sc.alloc(S * M * kFollowSlotBytes); q.tmeta = (int*)(q.tpl + S * M * kFollowSide * kFollowSide);
+        q.slot_moves = (int*)sc.alloc(S * M * 4 * sizeof(int));
+        moves_dev = (int*)sc.up(fw->moves, nout * 4 * sizeof(int));
+        const RedactStage st = redact_stage_layout(fw->format, fw->h, fw->w);
+        uint8_t* stage = (uint8_t*)sc.alloc(st.one * F * S);
+        dev = stage_table(st, stage, fw->format, (int)(F * S));
+        q.g = FrameGeo{fw->format, n_streams, fw->h, fw->w, st.pitch0, st.pitch1};
+        if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, fw->format, fw->host_planes, (int)(F * S), fw->h, fw->pitch0, fw->pitch1, stage, true));
+    }
     const TrackParams first = p;
     for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
         p.boxes = first.boxes + f * S * rows * 4; p.scores = first.scores + f * S * rows; p.lms = first.lms + f * S * rows * 10;
         p.counts = first.counts + f * S;
         p.dets = first.dets + f * S * M * 5; p.lms_out = first.lms_out + f * S * M * 10; p.info = first.info + f * S * M * 3;
         p.out_counts = first.out_counts + f * S; p.flags = first.flags + f * S;
-        sc.chk(launch_track_update(sc.s, p));
+        if (!fw || fw->detect[f]) sc.chk(launch_track_update(sc.s, p));
+        if (!fw) continue;
+        q.planes = dev.data() + 3 * f * S;
+        q.dets = p.dets; q.lms_out = p.lms_out; q.info = p.info; q.out_counts = p.out_counts; q.moves = moves_dev + f * S * M * 4;
+        if (sc.err == hipSuccess) sc.chk(launch_track_follow(sc.s, q));
     }
     if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, first.dets, nout * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
     if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, first.lms_out, nout * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
     if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(info, first.info, nout * 3 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
     if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(counts, first.out_counts, F * S * sizeof(int), hipMemcpyDeviceToHost, sc.s));
     if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(flags, first.flags, F * S * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    return sc.result("cf_op_track");
+    if (sc.err == hipSuccess && fw) sc.chk(hipMemcpyAsync(fw->moves, moves_dev, nout * 4 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    return sc.result(who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cf_op_track(int device, const cf_track_opts* o, int n_streams, int n_frames, int rows, const float* boxes, const float* scores,
+                const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags) {
+    return op_track_sequence("cf_op_track", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, nullptr);
+}
+
+int cf_op_follow(int device, const cf_track_opts* o, const cf_follow_opts* fo, int n_streams, int n_frames, int rows, const float* boxes,
+                 const float* scores, const float* lms_in, const int32_t* counts_in, const uint8_t* detect, int format,
+                 const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h, int space_w, int tiled, float* dets,
+                 float* lms, int32_t* info, int32_t* counts, int32_t* flags, int32_t* moves) {
+    const OpFollow fw{fo, detect, format, reinterpret_cast<const void* const*>(frames), h, w, pitch0, pitch1, space_h, space_w, tiled, moves};
+    return op_track_sequence("cf_op_follow", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, &fw);
 }
 
 }  // extern "C"

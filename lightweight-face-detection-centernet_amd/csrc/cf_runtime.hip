@@ -102,7 +102,8 @@ struct SrcStage { DevBuf buf; hipEvent_t ev_copy = nullptr, ev_free = nullptr; b
 // The face rows a consumer reads, whichever producer wrote them: dets [.][stride][5] (the score column is dets + 4, stride 5), corners
 // [.][stride][4], lms [.][stride][10], counts [B]; in the pixels of an H x W network input or -- frame_space -- of the H x W frames of a
 // tiled forward.  RowStage: the newest producer behind the last forward.
-struct RowSet { const float* corners; const float* dets; const float* lms; const int* counts; int stride, B, H, W; bool frame_space; };
+// info [.][stride][3] = id, hits, misses: tracked rows only, else nullptr.
+struct RowSet { const float* corners; const float* dets; const float* lms; const int* counts; int stride, B, H, W; bool frame_space; const int32_t* info = nullptr; };
 enum RowStage { ROWS_NONE = 0, ROWS_DECODED, ROWS_MERGED, ROWS_TRACKED };
 
 }  // namespace
@@ -163,6 +164,9 @@ struct cf_ctx {
     int tl_T = 0, tl_Bf = 0, tl_h = 0, tl_w = 0, tl_maxout = 0;
     struct { DevBuf cand, cand_count, order, mask, dets, lms, corners, counts, flags; } tl;
     struct { DevBuf dets, lms, info, corners, counts, flags; } tk; int tk_M = 0;      // cf_track_update: the tracked rows, tk_M per image
+    // cf_track_follow: B > 0 = the rows in tk are the follow's, of B frames in the tracker's space (H x W network input, or -- tiled -- H x W
+    // frames), and the newest whatever `stage` says; any forward, threshold decode, merge or update ends that (B = 0)
+    struct { DevBuf slot_moves, moves; int B = 0, H = 0, W = 0; bool tiled = false; } fo;
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
     // input format, batch): the second forward with a key captures it, later ones replay it
     struct FwdGraph { const void* in; int fmt, B; hipGraphExec_t exec; bool broken; unsigned long long used; };
@@ -1143,7 +1147,7 @@ int forward_run(cf_ctx* c, const void* net_in, int in_format, int B) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in.used;      // what cf_align_faces samples
-    c->stage = ROWS_NONE; c->tl_T = 0;                    // (cf_forward_tiles sets its state again behind this call)
+    c->stage = ROWS_NONE; c->tl_T = 0; c->fo.B = 0;       // (cf_forward_tiles sets its state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -1566,9 +1570,15 @@ enum RowsWanted {
     ROWS_OF_DECODE,          // the threshold decode's, whatever came after (cf_align_faces)
     ROWS_OF_TILED_DECODE,    // the same, of a tiled forward (cf_merge_tiles)
     ROWS_UNTRACKED,          // the newest that no cf_track_update has consumed: the merged rows of a tiled forward, else the decode's
-    ROWS_NEWEST              // the tracked rows behind an update, else those (cf_redact_faces, cf_blur_faces, cf_align_faces_frame)
+    ROWS_NEWEST              // the followed rows behind a follow, else the tracked rows behind an update, else those (cf_redact_faces, cf_blur_faces,
+                             // cf_align_faces_frame, cf_draw_faces)
 };
 static int rows_for(cf_ctx* c, const char* who, RowsWanted want, RowSet& r) {
+    if (want == ROWS_NEWEST && c->fo.B > 0) {            // behind cf_track_follow, which needs no forward: the followed rows, in the tracker's space
+        r = RowSet{(const float*)c->tk.corners.p, (const float*)c->tk.dets.p, (const float*)c->tk.lms.p, (const int*)c->tk.counts.p, c->tk_M, c->fo.B, c->fo.H, c->fo.W,
+                   c->fo.tiled, (const int32_t*)c->tk.info.p};
+        return CF_OK;
+    }
     if (c->last_B < 1) return c->fail(CF_ESTATE, "%s before cf_forward", who);
     if (want == ROWS_OF_TILED_DECODE && c->tl_T < 1) return c->fail(CF_ESTATE, "%s: the last forward was not cf_forward_tiles", who);
     if (!c->al_in) return c->fail(CF_ESTATE, "%s: an upload was started after the last forward, its input is gone", who);
@@ -1582,7 +1592,7 @@ static int rows_for(cf_ctx* c, const char* who, RowsWanted want, RowSet& r) {
     if (c->stage < ROWS_TRACKED) return CF_OK;
     if (want == ROWS_UNTRACKED) return c->fail(CF_ESTATE, "%s: these rows went through an update already (time would advance twice)", who);
     r.corners = (const float*)c->tk.corners.p; r.dets = (const float*)c->tk.dets.p; r.lms = (const float*)c->tk.lms.p;      // the same images and coordinates
-    r.counts = (const int*)c->tk.counts.p; r.stride = c->tk_M;
+    r.counts = (const int*)c->tk.counts.p; r.stride = c->tk_M; r.info = (const int32_t*)c->tk.info.p;
     return CF_OK;
 }
 
@@ -1675,7 +1685,7 @@ static int thresh_launch(cf_ctx* c, int mode, float score_thresh, float nms_thre
     HIPCHK(c, hipMemsetAsync(c->t_overflow, 0, sizeof(int), c->stream));
     HIPCHK(c, launch_decode_threshold(c->stream, p));
     HIPCHK(c, hipEventRecord(c->ev_thr, c->stream));
-    c->al_rows = max_out; c->stage = ROWS_DECODED;
+    c->al_rows = max_out; c->stage = ROWS_DECODED; c->fo.B = 0;
     return CF_OK;
 }
 
@@ -1793,9 +1803,10 @@ int cf_align_faces(cf_ctx* c, const cf_align_opts* o, void* chips, double* matri
 // belong to, and the frames -- the caller's device planes as they are, or host frames staged in rd_stage around the launches.
 static int frame_rows(cf_ctx* c, const char* who, int B, int h, int w, RowSet& r) {
     if (int e = rows_for(c, who, ROWS_NEWEST, r)) return e;
-    if (!r.frame_space) return B == r.B ? CF_OK : c->fail(CF_EINVAL, "%s: B=%d, the last forward had %d images", who, B, r.B);
-    if (B != r.B) return c->fail(CF_EINVAL, "%s: B=%d, the tiled forward had %d frames", who, B, r.B);
-    if (h != r.H || w != r.W) return c->fail(CF_EINVAL, "%s: %d x %d frames, the tiled forward had %d x %d", who, w, h, r.W, r.H);
+    const char* by = c->fo.B > 0 ? "follow" : "forward";                 // (the producer the B and the size are those of)
+    if (!r.frame_space) return B == r.B ? CF_OK : c->fail(CF_EINVAL, "%s: B=%d, the last %s had %d images", who, B, by, r.B);
+    if (B != r.B) return c->fail(CF_EINVAL, "%s: B=%d, the tiled %s had %d frames", who, B, by, r.B);
+    if (h != r.H || w != r.W) return c->fail(CF_EINVAL, "%s: %d x %d frames, the tiled %s had %d x %d", who, w, h, by, r.W, r.H);
     return CF_OK;
 }
 static FaceList face_list(const RowSet& r) { return FaceList{r.corners, r.stride, r.counts, r.stride, r.stride, r.H, r.W}; }
@@ -1887,12 +1898,11 @@ int cf_draw_faces(cf_ctx* c, const cf_draw_opts* o, int format, const cf_planes_
         return c->fail(CF_EINVAL, "cf_draw_faces: %s", why);
     RowSet rows{};
     if (int r = frame_rows(c, "cf_draw_faces", B, h, w, rows)) return r;
-    const bool tracked = c->stage >= ROWS_TRACKED;
-    if (o->label == CF_DRAW_LABEL_ID && !tracked) return c->fail(CF_ESTATE, "cf_draw_faces: CF_DRAW_LABEL_ID without a cf_track_update behind the last decode");
+    if (o->label == CF_DRAW_LABEL_ID && !rows.info) return c->fail(CF_ESTATE, "cf_draw_faces: CF_DRAW_LABEL_ID without a cf_track_update behind the last decode");
     HIPCHK(c, hipSetDevice(c->device));
     DrawParams p{};
     p.g = FrameGeo{format, B, h, w, pitch0, pitch1}; p.o = *o;
-    p.r = DrawRows{rows.corners, rows.dets + 4, 5, rows.lms, tracked ? (const int32_t*)c->tk.info.p : nullptr, rows.counts, rows.stride, rows.stride, rows.H, rows.W};
+    p.r = DrawRows{rows.corners, rows.dets + 4, 5, rows.lms, rows.info, rows.counts, rows.stride, rows.stride, rows.H, rows.W};
     if (int r = grow(c, c->dr_recs, draw_scratch_bytes(B, rows.stride), "draw records", "cf_draw_faces")) return r;
     p.recs = (DrawRec*)c->dr_recs.p;
     return on_frames(c, "cf_draw_faces", p.g, planes, on_device, true, [&](const void* const* pl, int p0, int p1) {
@@ -1986,7 +1996,7 @@ int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
         return c->fail(CF_ENOMEM, "cf_merge_tiles: %d frames x %d tiles x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
                        Bf, T, rows, merge_mask_bytes(Bf, T, rows) / 1e6);
     HIPCHK(c, hipSetDevice(c->device));
-    c->stage = ROWS_DECODED;                              // the merged (and tracked) rows of an earlier call are gone from here on
+    c->stage = ROWS_DECODED; c->fo.B = 0;                 // the merged (and tracked, and followed) rows of an earlier call are gone from here on
     const size_t cap = (size_t)T * rows, mo = (size_t)Bf * max_out, nb = (size_t)Bf * sizeof(int);
     const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
     auto& ws = c->tl;
@@ -2021,6 +2031,7 @@ struct cf_tracker {
     int device = 0, S = 0;
     cf_track_opts o{};
     int* meta = nullptr; float* rec = nullptr; int* next_id = nullptr;
+    uint8_t* fol = nullptr;                                             // the follower records (cf_track_follow), allocated by the first follow
     hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
     bool latched = false, sp_tiled = false; int sp_h = 0, sp_w = 0;      // the coordinate space of the first update
 };
@@ -2031,7 +2042,7 @@ int cf_track_destroy(cf_tracker* t) {
     hipSetDevice(t->device);
     if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
     if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
-    for (void* p : {(void*)t->meta, (void*)t->rec, (void*)t->next_id}) if (p) hipFree(p);
+    for (void* p : {(void*)t->meta, (void*)t->rec, (void*)t->next_id, (void*)t->fol}) if (p) hipFree(p);
     delete t;
     return CF_OK;
 }
@@ -2109,7 +2120,7 @@ int cf_track_update(cf_ctx* c, cf_tracker* t, int stream0, float* dets, float* l
     HIPCHK(c, launch_track_update(c->stream, p));
     HIPCHK(c, hipEventRecord(t->ev, c->stream));
     t->latched = true; t->sp_tiled = tiled; t->sp_h = in.H; t->sp_w = in.W;
-    c->stage = ROWS_TRACKED; c->tk_M = M;
+    c->stage = ROWS_TRACKED; c->tk_M = M; c->fo.B = 0;
     if (out_on_device) {
         if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
         if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, nl, hipMemcpyDeviceToDevice, c->stream));
@@ -2120,6 +2131,70 @@ int cf_track_update(cf_ctx* c, cf_tracker* t, int stream0, float* dets, float* l
     }
     return read_out(c, B, M, p.out_counts, p.flags, counts, flags,
                     {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)}});
+}
+
+// The follow (cf_follow.hip) of the streams stream0 .. stream0 + B - 1 in the caller's frames: ordered on the tracker's event like an update,
+// it reads and moves the tracker's state and writes the context's tracked rows again; no forward of the context is involved.
+int cf_track_follow(cf_ctx* c, cf_tracker* t, int stream0, int B, const cf_follow_opts* o, int format, const cf_planes_rw* frames, int on_device,
+                    int h, int w, int pitch0, int pitch1, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* moves, int out_on_device) {
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    const char* why = follow_check(o, format, B, h, w, pitch0, pitch1);
+    if (!why) why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1);
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_track_follow: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_track_follow: %s", why);
+    if (!t) return c->fail(CF_EINVAL, "cf_track_follow: null tracker");
+    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_track_follow: the tracker lives on device %d, the context on device %d", t->device, c->device);
+    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_track_follow: B=%d exceeds max_batch %d", B, c->max_batch);
+    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_track_follow: streams %d .. %d of a tracker with %d", stream0, stream0 + B - 1, t->S);
+    if (!t->latched) return c->fail(CF_ESTATE, "cf_track_follow before the tracker's first cf_track_update: its rows have no coordinate space yet");
+    if (t->sp_tiled && (h != t->sp_h || w != t->sp_w))
+        return c->fail(CF_EINVAL, "cf_track_follow: %d x %d frames, the tracker's rows are in frame %d x %d coordinates", w, h, t->sp_w, t->sp_h);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int M = t->o.max_tracks;
+    const size_t slots = (size_t)t->S * M, bm = (size_t)B * M, nb = (size_t)B * sizeof(int);
+    const size_t nd = bm * 5 * sizeof(float), nl = bm * 10 * sizeof(float), ni = bm * 3 * sizeof(int), nm = bm * 4 * sizeof(int);
+    auto& ws = c->tk;
+    const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
+        {ws.dets, nd, "tracked dets"}, {ws.lms, nl, "tracked landmarks"}, {ws.info, ni, "track info"},
+        {ws.corners, bm * 4 * sizeof(float), "tracked corners"}, {ws.counts, nb, "tracked counts"}, {c->fo.slot_moves, nm, "moves per slot"}, {c->fo.moves, nm, "moves"}};
+    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_track_follow")) return r;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the update or follow before this one, on whichever context's stream
+    if (!t->fol) {
+        const hipError_t e = hipMalloc((void**)&t->fol, slots * kFollowSlotBytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError(); t->fol = nullptr;
+            return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_track_follow: %zu bytes of follower records: %s", slots * kFollowSlotBytes, hipGetErrorString(e));
+        }
+        HIPCHK(c, hipMemsetAsync(t->fol, 0, slots * kFollowSlotBytes, c->stream));      // tpl_id 0 is no track's id: every slot learns first
+    }
+    FollowParams p{};
+    p.search = o->search; p.max_sad = o->max_sad;
+    p.fx = t->sp_tiled ? 1.0 : (double)w / (double)t->sp_w; p.fy = t->sp_tiled ? 1.0 : (double)h / (double)t->sp_h;
+    p.stream0 = stream0; p.max_tracks = M; p.hold_grow = t->o.hold_grow; p.meta = t->meta; p.rec = t->rec;
+    p.tpl = t->fol; p.tmeta = (int*)(t->fol + slots * kFollowSide * kFollowSide); p.slot_moves = (int*)c->fo.slot_moves.p;
+    p.dets = (float*)ws.dets.p; p.lms_out = (float*)ws.lms.p; p.info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
+    p.out_counts = (int*)ws.counts.p; p.moves = (int*)c->fo.moves.p;
+    c->fo.B = 0;                                                          // (a failure below leaves no followed rows behind)
+    // host frames are only read: staged, not copied back
+    if (int r = on_frames(c, "cf_track_follow", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, on_device, false, [&](const void* const* pl, int p0, int p1) {
+            p.g = FrameGeo{format, B, h, w, p0, p1}; p.planes = pl;
+            const hipError_t e = launch_track_follow(c->stream, p);
+            return e != hipSuccess ? e : hipEventRecord(t->ev, c->stream);
+        })) return r;
+    c->tk_M = M; c->fo.B = B; c->fo.H = t->sp_h; c->fo.W = t->sp_w; c->fo.tiled = t->sp_tiled;
+    if (out_on_device) {
+        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
+        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, nl, hipMemcpyDeviceToDevice, c->stream));
+        if (info) HIPCHK(c, hipMemcpyAsync(info, p.info, ni, hipMemcpyDeviceToDevice, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, nb, hipMemcpyDeviceToDevice, c->stream));
+        if (moves) HIPCHK(c, hipMemcpyAsync(moves, p.moves, nm, hipMemcpyDeviceToDevice, c->stream));
+        return CF_OK;
+    }
+    return read_out(c, B, M, p.out_counts, nullptr, counts, nullptr,
+                    {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)}, {moves, p.moves, 4 * sizeof(int)}});
 }
 
 int cf_event_record(cf_ctx* c, int slot) {

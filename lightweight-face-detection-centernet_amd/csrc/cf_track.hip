@@ -34,6 +34,7 @@
 
 #include "cf_common.h"
 #include "cf_kernels.h"
+#include "cf_trackemit.h"
 
 namespace cf {
 
@@ -134,36 +135,9 @@ __global__ __launch_bounds__(64) void track_update_kernel(TrackParams p) {
         p.next_id[p.stream0 + b] = next + (n_new < base ? n_new : base);
         p.flags[b] = n_new > base ? 1 : 0;
     }
-    // the alive slots, compacted in slot order (every lane reads back only what it wrote itself)
-    float* odets = p.dets + (size_t)b * M * 5;
-    float* olms = p.lms_out + (size_t)b * M * 10;
-    int* oinfo = p.info + (size_t)b * M * 3;
-    float* ocorn = p.corners + (size_t)b * M * 4;
-    base = 0;
-    for (int j = 0; j < per; ++j) {
-        const int k = j * 64 + lane;
-        const bool alive = k < M && s_flag[k] == F_ALIVE;
-        const unsigned long long bal = __ballot(alive);
-        if (alive) {
-            const int r = base + __popcll(bal & ((1ull << lane) - 1ull));
-            const float* q = rec + (size_t)k * 16;
-            const int misses = meta[k * 4 + 3];
-            float x1 = q[0], y1 = q[1], x2 = q[2], y2 = q[3];
-            if (misses > 0) {
-                const double g = 1.0 + (double)p.hold_grow * (double)misses;
-                const double cx = ((double)x1 + (double)x2) * 0.5, hw = ((double)x2 - (double)x1) * 0.5 * g;
-                const double cy = ((double)y1 + (double)y2) * 0.5, hh = ((double)y2 - (double)y1) * 0.5 * g;
-                x1 = (float)(cx - hw); x2 = (float)(cx + hw); y1 = (float)(cy - hh); y2 = (float)(cy + hh);
-            }
-            float* od = odets + (size_t)r * 5;
-            od[0] = x1; od[1] = y1; od[2] = x2; od[3] = y2; od[4] = q[4];
-            float* oc = ocorn + (size_t)r * 4;
-            oc[0] = x1; oc[1] = y1; oc[2] = x2; oc[3] = y2;
-            for (int c = 0; c < 10; ++c) olms[(size_t)r * 10 + c] = q[5 + c];
-            oinfo[r * 3] = meta[k * 4 + 1]; oinfo[r * 3 + 1] = meta[k * 4 + 2]; oinfo[r * 3 + 2] = misses;
-        }
-        base += __popcll(bal);
-    }
+    // the alive slots, compacted in slot order (every lane reads back only what it wrote itself): step 5, cf_trackemit.h
+    const TrackRows o{p.dets + (size_t)b * M * 5, p.lms_out + (size_t)b * M * 10, p.info + (size_t)b * M * 3, p.corners + (size_t)b * M * 4};
+    base = track_emit_rows(lane, M, p.hold_grow, meta, rec, o, [&](int k) { return s_flag[k] == F_ALIVE; }, [](int, int) {});
     if (lane == 0) p.out_counts[b] = base;
 }
 

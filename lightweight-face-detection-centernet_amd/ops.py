@@ -394,6 +394,41 @@ def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=Non
     return od, ol, oi, oc, fl
 
 
+def follow_sequence(boxes, scores, lms, counts, frames, fmt="bgr", space_hw=None, detect=None, *, tiled=False, search=4, max_sad=4096,
+                    dets=None, lms_out=None, info=None, moves=None, device=0, **opts):
+    """``track_sequence`` with the follower behind every frame (``cf_op_follow``): frame f of stream s is ``frames[f * S + s]`` -- F * S host
+    frames of one size as ``redact_faces`` takes them (BGR uint8 [F*S,h,w,3], dense 4:2:0 uint8 [F*S, h*3//2, w], or per-frame plane
+    tuples of pitched rows), only read.  ``detect`` [F] (default: all): where it is set the update with the frame's rows runs first,
+    then the faces are followed in the frame -- block matching of a 16 x 16 cell template within ``search`` cells, a best match above
+    ``max_sad`` moves nothing; the two defaults are this project's choices, no accuracy claim is made for them.  ``space_hw``: the (H, W)
+    the rows are in, mapped to the frame by w / W, h / H; ``tiled=True``: the rows are in frame pixels (``space_hw`` is the frame's size).
+    ``opts`` as ``track_sequence``.  Returns (dets, lms, info, counts, flags, moves [F, S, max_tracks, 4] = px, py, SAD, code
+    (``_lib.CF_FOLLOW_*``)) after every frame; rows at and past a count keep the bytes of the arrays passed in (zeros by default)."""
+    o, fo = _lib.track_opts(**opts), _lib.follow_opts(search, max_sad)
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    if b.ndim != 4 or b.shape[3] != 4:
+        raise ValueError("boxes must be [F, S, rows, 4], got %s" % (b.shape,))
+    F, S, rows, _ = b.shape
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(F, S, rows)
+    lm = np.ascontiguousarray(lms, dtype=np.float32).reshape(F, S, rows, 10)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(F, S)
+    dt = np.ones((F,), np.uint8) if detect is None else np.ascontiguousarray(np.asarray(detect).astype(bool), dtype=np.uint8).reshape(F)
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    if B != F * S:
+        raise ValueError("%d frames for F x S = %d x %d" % (B, F, S))
+    H, W = (h, w) if space_hw is None else (int(space_hw[0]), int(space_hw[1]))
+    M = max(int(o.max_tracks), 1)
+    od = np.zeros((F, S, M, 5), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(F, S, M, 5)
+    ol = np.zeros((F, S, M, 10), np.float32) if lms_out is None else np.ascontiguousarray(lms_out, dtype=np.float32).reshape(F, S, M, 10)
+    oi = np.zeros((F, S, M, 3), np.int32) if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(F, S, M, 3)
+    om = np.zeros((F, S, M, 4), np.int32) if moves is None else np.ascontiguousarray(moves, dtype=np.int32).reshape(F, S, M, 4)
+    oc, fl = np.zeros((F, S), np.int32), np.zeros((F, S), np.int32)
+    _lib.check(_lib.lib().cf_op_follow(device, C.byref(o), C.byref(fo), S, F, rows, ptr(b), ptr(sc), ptr(lm), ptr(cn), ptr(dt), _lib.frame_format(fmt), tab,
+                                       h, w, pitch0, pitch1, H, W, 1 if tiled else 0, ptr(od), ptr(ol), ptr(oi), ptr(oc), ptr(fl), ptr(om)), op=True)
+    del keep
+    return od, ol, oi, oc, fl, om
+
+
 def ctdet_decode(heat, wh, reg=None, K=100, lm=None, device=0):
     """ctdet_decode (centerface_ext.py:52-82): (dets [B,K,6], lms [B,K,10]|None, inds [B,K] int64)."""
     heat, wh, reg, lm = f32(heat), f32(wh), f32(reg), f32(lm)

@@ -538,6 +538,105 @@ int cf_track_follow(cf_ctx* ctx, cf_tracker* trk, int stream0, int B, const cf_f
                     int on_device, int h, int w, int pitch0, int pitch1, float* dets, float* lms, int32_t* info, int32_t* counts,
                     int32_t* moves, int out_on_device);
 
+/* ---- best-shot selection: each track's sharpest chip, kept on the device -----------------------------------------------------
+ * cf_track_update / cf_track_follow give every face an identity, cf_align_faces_frame cuts a chip of every tracked row: a track that
+ * lives 200 frames yields 200 chips.  A cf_bestshot table is offered the chips of each frame, scores them, and keeps PER TRACK ID the
+ * chip with the highest quality; when the id disappears from the tracked rows the entry is finished, and cf_bestshot_collect hands the
+ * finished entries out in finishing order -- one chip per appearance of a person.  In the device form no chip, box or count crosses to
+ * the host:
+ *   ... -> cf_track_update [-> cf_track_follow] -> cf_align_faces_frame (chips, offsets) -> cf_bestshot_offer ...  cf_bestshot_collect
+ * The arithmetic is this library's own statement (csrc/cf_bestshot.hip; restated in tests/bestshot_cases.py; device and restatement are
+ * equal bit for bit): integers throughout, except a few float64 terms in the order written, no FMA contraction.  THE QUALITY FORMULA IS
+ * THIS PROJECT'S CHOICE; no accuracy claim is made for it.
+ *
+ * Quality of one chip.  Inputs: a uint8 [S][S][3] BGR chip, its row (x1, y1, x2, y2), score, lms[10] (float32), and fx, fy (float64).
+ *   1. Luma.  L = (29*B + 150*G + 77*R + 128) >> 8 (the follower's luma).
+ *   2. Sharpness.  The window is the central half: a = S/4, b = 3*S/4, pixels a <= x, y < b, N = (S/2)*(S/2).
+ *      lap = 4*L[y][x] - L[y-1][x] - L[y+1][x] - L[y][x-1] - L[y][x+1] (the neighbours exist because a >= 4).
+ *      S1 = sum lap, S2 = sum lap*lap (int64); V = N*S2 - S1*S1; sharp = V / (N*N).  V >= 0: the division needs no sign rule.  Range
+ *      0 .. 1 040 400; at S = 512, N*S2 <= 4.5e15 and S1*S1 <= 4.5e15 fit int64.  This is the variance of the 4-neighbour Laplacian; it
+ *      leaves out the chip border, where the warp's zero border would count as an edge.
+ *   3. size_w: 256 when CF_BEST_SIZE is off.  wx = ((double)x2 - (double)x1) * fx, wy = ((double)y2 - (double)y1) * fy.
+ *      !(wx > 0) || !(wy > 0): 0.  Otherwise side = wx < wy ? wx : wy, side_i = side >= (double)S ? S : (int)floor(side),
+ *      size_w = side_i * 256 / S.  (A face larger than the chip gains nothing more: the chip is point-sampled.)
+ *   4. pose_w: 256 when CF_BEST_POSE is off; 0 when any of the ten landmark values is not finite.
+ *      Pj = ((double)lms[2j] * fx, (double)lms[2j+1] * fy); ex = (P0x + P1x) * 0.5, ey = (P0y + P1y) * 0.5; mx = (P3x + P4x) * 0.5,
+ *      my = (P3y + P4y) * 0.5; ax = mx - ex, ay = my - ey; dx = P2x - ex, dy = P2y - ey; cr = ax*dy - ay*dx; len2 = ax*ax + ay*ay.
+ *      !(len2 > 0): 0.  Otherwise t = fabs(cr) / len2 * 512.0, pose_w = !(t < 256.0) ? 0 : 256 - (int)floor(t).  (The nose's sideways
+ *      offset from the eye-mouth axis, in units of that axis: 0.5 or more gives 0.)
+ *   5. score_w: 256 when CF_BEST_SCORE is off.  t = (double)score * 256.0; score_w = !(t > 0) ? 0 : (t >= 256.0 ? 256 : (int)floor(t)).
+ *   6. Q = (int64)sharp * size_w * pose_w * score_w (at most 1.8e13); parts = sharp, size_w, pose_w, score_w.
+ *   (A flat chip gives sharp 0; grey columns alternating 100 / 110 give 400; a grey 0 / 255 checkerboard gives 1 040 400.)
+ *
+ * The table.  Each stream has E entries, each FREE, LIVE or DONE.  An entry holds id, Q, parts, best_t, first_t, last_t, n_offered,
+ * done_seq, det[5] and lms[10] (the row of the best frame, bit for bit) and the chip.  Each stream also holds an offer counter t and a
+ * finish counter seq, both starting at 0, and sticky flags.
+ *
+ * One offer of stream s.  The rows are the context's newest TRACKED rows of image b: i < n = min(count, rows per image), with
+ * info = id, hits, misses.  The caller's chips and offsets[B+1] are as cf_align_faces_frame writes them.  Row i has chip
+ * c = offsets[b] + i iff 0 <= offsets[b] <= offsets[b+1], i < offsets[b+1] - offsets[b] and c < cap_faces; anything else is "no chip",
+ * never an out-of-range read.  (Offsets as the align calls write them never name a chip twice; should malformed ones do, the chip is
+ * that of the lowest image naming it and the others' rows have no chip.)
+ *   1. A row COUNTS if id >= 1 and no earlier row of the image has the same id.
+ *   2. Every LIVE entry, in ascending entry order: its id is among the counted rows -> last_t = t; otherwise the entry becomes DONE
+ *      with done_seq = seq++.
+ *   3. Counted rows in row order.  A row is eligible iff misses == 0 && hits >= min_hits and it has a chip.  (A row held through a
+ *      dropout shows whatever is at that place now, so it is never offered; its id is still present, so its entry stays alive.)  For an
+ *      eligible row, compute Q:
+ *        a LIVE entry holds the id: n_offered = min(n_offered + 1, 1 << 30); if Q > entry.Q (strictly: the earlier frame wins a tie)
+ *          the entry takes Q, parts, best_t = t, det, lms and the chip.
+ *        no entry holds it: the lowest FREE entry (DONE entries are not free) becomes LIVE with first_t = best_t = last_t = t,
+ *          n_offered = 1, and Q, parts, det, lms and the chip.
+ *        there is none: the row is not entered; bit 0 is set in this offer's flags and in the stream's sticky flags.  It may enter on
+ *          a later frame.
+ *   4. t += 1.
+ *
+ * Collect of stream s with cap and flush.
+ *   1. flush: every LIVE entry becomes DONE, in ascending entry order with consecutive seqs (the end of the video).
+ *   2. The DONE entries in ascending done_seq: the first min(n_done, cap) are output as rows k and become FREE.
+ *   3. counts[s] is that number, pending[s] what stays DONE.  4. flags[s] = the sticky flags, which are then cleared.
+ *   5. records[k] = id, best_t, first_t, last_t, n_offered, sharp, size_w | pose_w << 10 | score_w << 20, done_seq (int32).
+ *   6. Rows at and past counts[s] are not written.
+ *
+ * On the device an offer is three launches (score: one workgroup per chip; decide: one per stream; copy) and a collect two. */
+#define CF_BEST_SIZE  1
+#define CF_BEST_POSE  2
+#define CF_BEST_SCORE 4
+typedef struct cf_bestshot_opts {
+    int32_t size;      /* S: chip side, a multiple of 4 in [16, 512]; chips are CF_CHIP_U8_HWC_BGR */
+    int32_t entries;   /* E: 1..2048 table entries per stream (live tracks + finished ones not yet collected) */
+    int32_t min_hits;  /* 1..1000: a row is offered only with hits >= min_hits */
+    int32_t terms;     /* 0..7: which of the three weights take part (CF_BEST_*); sharpness always does */
+} cf_bestshot_opts;   /* 16 bytes */
+typedef struct cf_bestshot cf_bestshot;
+/* A table of n_streams (1..4096) streams on ctx's device: n_streams * E * (3*S*S + 128) bytes of device state.  CF_EINVAL for bad options
+ * or a NULL out, before any GPU work (ctx == NULL: the options are still checked first, cf_op_last_error names the cause, as
+ * cf_track_create does); CF_ENOMEM, before anything is allocated, when the state does not fit the device's free memory. */
+int cf_bestshot_create(cf_ctx* ctx, int n_streams, const cf_bestshot_opts* opts, cf_bestshot** out);
+/* Waits for the table's last call, then frees it.  NULL gives CF_OK. */
+int cf_bestshot_destroy(cf_bestshot* bs);
+/* One offer of the streams stream0 .. stream0 + B - 1: image b of ctx's newest tracked rows is stream stream0 + b; B must be the B of
+ * those rows.  chips [cap_faces][S][S][3] uint8 and offsets [B+1] as cf_align_faces / cf_align_faces_frame wrote them (on_device: device
+ * addresses, chips 16-byte aligned; otherwise host arrays, which are copied up, and the call blocks).  (h, w) is the frame the chips were
+ * cut from: rows in network space, any 2..8192, fx = (double)w / (double)W, fy = (double)h / (double)H (chips of cf_align_faces: pass
+ * (H, W)); rows in frame space (after cf_merge_tiles), (h, w) must be the tiled frame's and fx = fy = 1.
+ * quality [cap_faces] (Q of the chip of an eligible row, -1 otherwise) and flags [B] may be NULL; out_on_device says where they are.
+ * With device chips and device outputs the call is asynchronous on the context's main stream behind the align, and reads nothing on
+ * the host.  It changes no state of ctx.
+ * CF_ESTATE when the newest rows of ctx are not tracked rows (no cf_track_update / cf_track_follow behind them), or once another
+ * forward or upload was started.  CF_EINVAL, before any GPU work, for: a stream range outside the table, B outside 1..max_batch or not
+ * the rows' B, cap_faces < 0, bad h / w, device chips not 16-byte aligned, a table on another device, NULL chips / offsets / table
+ * (ctx == NULL: the arguments are still checked first, cf_op_last_error names the cause).
+ * Ordering: the table keeps one event, used exactly as the tracker uses its own -- every offer or collect first makes its stream wait
+ * for the previous call's event, then records a new one -- so a ring of contexts can share one table in call order. */
+int cf_bestshot_offer(cf_ctx* ctx, cf_bestshot* bs, int stream0, int B, const void* chips, const int32_t* offsets, int cap_faces,
+                      int on_device, int h, int w, int64_t* quality, int32_t* flags, int out_on_device);
+/* Collect of the streams stream0 .. stream0 + B - 1 (any range inside the table, cap in 0..E).  Outputs, any may be NULL (entries are freed all
+ * the same): chips [B][cap][S][S][3] (16-byte aligned on the device), quality [B][cap], records [B][cap][8], dets [B][cap][5],
+ * lms [B][cap][10], counts [B], pending [B], flags [B].  It needs no forward on ctx.  The host form blocks. */
+int cf_bestshot_collect(cf_ctx* ctx, cf_bestshot* bs, int stream0, int B, int cap, int flush, void* chips, int64_t* quality,
+                        int32_t* records, float* dets, float* lms, int32_t* counts, int32_t* pending, int32_t* flags, int out_on_device);
+
 /* ---- annotation: box outlines, landmark dots and a numeric label IN THE SOURCE FRAME, on the device --------------------------- */
 /* What demo.py:15-23, 40-51 does with a detection -- cv2.rectangle(frame, .., (2, 255, 0), 1) per box, cv2.circle(frame, .., 2,
  * (0, 0, 255), -1) per landmark -- for frames that stay on the device: BGR or 4:2:0, pitched, a decoder's surface in place, behind the
@@ -905,6 +1004,26 @@ int cf_op_follow(int device, const cf_track_opts* opts, const cf_follow_opts* fo
                  const float* boxes, const float* scores, const float* lms_in, const int32_t* counts_in, const uint8_t* detect,
                  int format, const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h, int space_w, int tiled,
                  float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, int32_t* moves);
+/* The scoring kernel of cf_bestshot_offer alone, on host tables: chips [n][S][S][3] uint8, boxes [n][4], scores [n], lms [n][10]
+ * (n in 1..65536; every row counts and is eligible) -> quality [n] int64, parts [n][4] int32 = sharp, size_w, pose_w, score_w.  fx, fy
+ * finite and > 0.  Every bad argument is CF_EINVAL with a cf_op_last_error that names it, before any device is touched. */
+int cf_op_chip_quality(int device, const cf_bestshot_opts* opts, const uint8_t* chips, const float* boxes, const float* scores,
+                       const float* lms, int n, double fx, double fy, int64_t* quality, int32_t* parts);
+/* The kernels of cf_bestshot_offer and cf_bestshot_collect over a whole scripted sequence on host tables, with a fresh table of n_streams
+ * streams and no engine and no tracker.  Frame f of stream s is offered the rows i < min(counts[f][s], rows) of boxes [F][S][rows][4],
+ * scores [F][S][rows], lms [F][S][rows][10], info [F][S][rows][3] = id, hits, misses; the leading min(chip_counts[f][s], rows) rows
+ * have a chip (as max_per_image truncates), chips [F][S][rows][Sz][Sz][3].  collect [F] uint8: 0 none, 1 collect, 2 collect with flush,
+ * of all streams with `cap` (0..entries), after that frame's offer.  Outputs per frame: out_chips [F][S][cap][Sz][Sz][3], out_quality
+ * [F][S][cap], out_records [F][S][cap][8], out_dets [F][S][cap][5], out_lms [F][S][cap][10] (rows at and past a count keep the caller's
+ * bytes), out_counts, out_pending, out_flags [F][S] (zero on frames without a collect), offer_flags [F][S], offer_quality [F][S][rows]
+ * (-1 for a row without a chip).  All pointers host, none NULL.  rows in 1..1024, n_frames >= 1, counts and chip_counts >= 0, fx, fy
+ * finite and > 0, and the option checks of cf_bestshot_create; every bad argument is CF_EINVAL with a cf_op_last_error that names it,
+ * before any device is touched; nothing is written on refusal. */
+int cf_op_bestshot(int device, const cf_bestshot_opts* opts, int n_streams, int n_frames, int rows, const float* boxes,
+                   const float* scores, const float* lms, const int32_t* info, const int32_t* counts, const int32_t* chip_counts,
+                   const uint8_t* chips, const uint8_t* collect, int cap, double fx, double fy, uint8_t* out_chips,
+                   int64_t* out_quality, int32_t* out_records, float* out_dets, float* out_lms, int32_t* out_counts,
+                   int32_t* out_pending, int32_t* out_flags, int32_t* offer_flags, int64_t* offer_quality);
 /* The kernels of cf_draw_faces alone, on host frames (modified in place): boxes [N][4] x1,y1,x2,y2 in the coordinates of an H x W
  * network input, scores [N], lms [N][10] or NULL, info [N][3] = id, hits, misses or NULL (all live), image after image, counts [B]
  * (>= 0, N = their sum).  The same validation as cf_draw_faces, before any device is touched; NULL lms with CF_DRAW_LANDMARKS and

@@ -52,6 +52,7 @@ EXPORTS = (
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_follow", "cf_op_follow",
+    "cf_bestshot_create", "cf_bestshot_destroy", "cf_bestshot_offer", "cf_bestshot_collect", "cf_op_chip_quality", "cf_op_bestshot",
 )
 
 
@@ -229,6 +230,28 @@ class FollowOpts(C.Structure):
 def follow_opts(search=4, max_sad=4096):
     """FollowOpts (the library validates the numbers).  The defaults are this project's choices; no accuracy claim is made for them."""
     return FollowOpts(int(search), int(max_sad))
+
+
+CF_BEST_SIZE, CF_BEST_POSE, CF_BEST_SCORE = 1, 2, 4
+_BEST_TERMS = {"size": CF_BEST_SIZE, "pose": CF_BEST_POSE, "score": CF_BEST_SCORE}
+
+
+class BestShotOpts(C.Structure):
+    """cf_bestshot_opts: chip side / table entries per stream / hits a row needs to be offered / the CF_BEST_* weights that take part."""
+    _fields_ = [("size", C.c_int32), ("entries", C.c_int32), ("min_hits", C.c_int32), ("terms", C.c_int32)]
+
+
+def bestshot_opts(size=112, entries=320, min_hits=2, terms=("size", "pose", "score")):
+    """BestShotOpts (the library validates the numbers).  ``terms``: an int mask of CF_BEST_*, or names out of size / pose / score.  The
+    quality formula and the defaults are this project's choices; no accuracy claim is made for them."""
+    if isinstance(terms, (int, np.integer)):
+        mask = int(terms)
+    else:
+        unknown = [t for t in terms if t not in _BEST_TERMS]
+        if unknown:
+            raise ValueError("terms must be out of %s, got %s" % (sorted(_BEST_TERMS), unknown))
+        mask = sum(set(_BEST_TERMS[t] for t in terms))
+    return BestShotOpts(int(size), int(entries), int(min_hits), mask)
 
 
 def tile_rects(rects):
@@ -475,6 +498,12 @@ def lib():
             [C.c_void_p] * 5 + [C.c_int]
         L.cf_op_follow.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(FollowOpts)] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.POINTER(PlanesRW)] + \
             [C.c_int] * 7 + [C.c_void_p] * 6
+        L.cf_bestshot_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(BestShotOpts), C.POINTER(C.c_void_p)]
+        L.cf_bestshot_destroy.argtypes = [C.c_void_p]
+        L.cf_bestshot_offer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int]
+        L.cf_bestshot_collect.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 8 + [C.c_int]
+        L.cf_op_chip_quality.argtypes = [C.c_int, C.POINTER(BestShotOpts)] + [C.c_void_p] * 4 + [C.c_int, C.c_double, C.c_double] + [C.c_void_p] * 2
+        L.cf_op_bestshot.argtypes = [C.c_int, C.POINTER(BestShotOpts)] + [C.c_int] * 3 + [C.c_void_p] * 8 + [C.c_int, C.c_double, C.c_double] + [C.c_void_p] * 10
         L.cf_get_resized_input.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.cf_get_heads.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.cf_decode_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

@@ -549,6 +549,60 @@ class Engine(object):
         self._chk(self._L.cf_track_follow(self._h, tracker._handle(self), int(stream0), B, C.byref(o), f, tab, dev, h, w, pitch0, pitch1,
                                           vp(dets_ptr), vp(lms_ptr), vp(info_ptr), vp(counts_ptr), vp(moves_ptr), 1))
 
+    # -- best-shot selection: each track's sharpest chip ---------------------------------------------
+    def bestshot_offer(self, shots, chips, offsets, hw, stream0=0):
+        """Offer ``shots`` (a ``BestShots``) the chips of this frame (``cf_bestshot_offer``, host form): ``chips`` uint8 [N, size, size, 3]
+        and ``offsets`` [B+1] as ``align_faces_frame`` (or ``align_faces``) returned them for the tracked rows this engine holds -- behind a
+        ``track_update`` or ``track_follow`` --, image b being the next frame of stream ``stream0 + b``; ``hw`` = (h, w) of the frames the
+        chips were cut from (the network's (H, W) for ``align_faces``).  Every row with ``misses == 0`` and ``hits >= min_hits`` that has
+        a chip is scored, and the table keeps per track id the chip with the highest quality; an id that is gone from the rows finishes
+        its entry.  Returns (quality int64 [N]: Q of the chip of an eligible row, -1 otherwise; flags int32 [B]: bit 0 = a new track
+        found no free entry).  No state of the engine changes."""
+        ch = np.ascontiguousarray(chips, dtype=np.uint8)
+        if ch.ndim != 4 or ch.shape[1:] != (shots.size, shots.size, 3):
+            raise ValueError("chips must be [N, %d, %d, 3], got %s" % (shots.size, shots.size, ch.shape))
+        offs = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        B, N = offs.size - 1, ch.shape[0]
+        if N == 0:
+            ch = np.zeros((1,) + ch.shape[1:], np.uint8)                      # (an address to name; cap_faces = 0 reads none of it)
+        quality, flags = np.full((N,), -1, np.int64), np.zeros((max(B, 0),), np.int32)
+        self._chk(self._L.cf_bestshot_offer(self._h, shots._handle(self), int(stream0), B, _lib.ptr(ch), _lib.ptr(offs), N, 0, int(hw[0]), int(hw[1]),
+                                            _lib.ptr(quality) if N else None, _lib.ptr(flags), 0))
+        return quality, flags
+
+    def bestshot_offer_device(self, shots, chips_ptr, offsets_ptr, cap_faces, B, hw, stream0=0, quality_ptr=None, flags_ptr=None):
+        """Same, reading the DEVICE chips and offsets an ``align_faces_frame_device`` wrote (chips for ``cap_faces`` faces, 16-byte
+        aligned) and writing caller-owned DEVICE outputs (quality [cap_faces] int64, flags [B] int32; either may be None): asynchronous
+        on the engine's main stream behind the align; nothing is read on the host."""
+        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
+        self._chk(self._L.cf_bestshot_offer(self._h, shots._handle(self), int(stream0), int(B), vp(chips_ptr), vp(offsets_ptr), int(cap_faces), 1,
+                                            int(hw[0]), int(hw[1]), vp(quality_ptr), vp(flags_ptr), 1))
+
+    def bestshot_collect(self, shots, stream0=0, B=None, cap=None, flush=False):
+        """The finished entries of the streams ``stream0 .. stream0 + B - 1`` of ``shots`` (default: all from ``stream0`` on), at most
+        ``cap`` per stream (default: every entry), in finishing order (``cf_bestshot_collect``, host form); ``flush=True`` first finishes
+        every live entry -- the end of the video.  Returns (chips [B, cap, size, size, 3], quality int64 [B, cap], records int32
+        [B, cap, 8] = id, best_t, first_t, last_t, n_offered, sharp, size_w | pose_w << 10 | score_w << 20, done_seq; dets [B, cap, 5]
+        and lms [B, cap, 10] = the row of the best frame; counts [B]: the valid rows; pending [B]: finished entries that did not fit;
+        flags [B]: bit 0 = since the last collect a new track found no free entry).  Needs no forward on this engine."""
+        B = shots.streams - int(stream0) if B is None else int(B)
+        cap = shots.entries if cap is None else int(cap)
+        k, S = max(cap, 0), shots.size
+        chips, quality, records = np.zeros((max(B, 0), k, S, S, 3), np.uint8), np.zeros((max(B, 0), k), np.int64), np.zeros((max(B, 0), k, 8), np.int32)
+        dets, lms = np.zeros((max(B, 0), k, 5), np.float32), np.zeros((max(B, 0), k, 10), np.float32)
+        counts, pending, flags = (np.zeros((max(B, 0),), np.int32) for _ in range(3))
+        self._chk(self._L.cf_bestshot_collect(self._h, shots._handle(self), int(stream0), B, cap, 1 if flush else 0, _lib.ptr(chips), _lib.ptr(quality),
+                                              _lib.ptr(records), _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts), _lib.ptr(pending), _lib.ptr(flags), 0))
+        return chips, quality, records, dets, lms, counts, pending, flags
+
+    def bestshot_collect_device(self, shots, stream0, B, cap, flush=False, chips_ptr=None, quality_ptr=None, records_ptr=None, dets_ptr=None,
+                                lms_ptr=None, counts_ptr=None, pending_ptr=None, flags_ptr=None):
+        """Same, writing caller-owned DEVICE buffers ([B, cap, ...] as above, chips 16-byte aligned; any may be None -- the entries are
+        freed all the same): asynchronous on the engine's main stream behind the table's last call."""
+        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
+        self._chk(self._L.cf_bestshot_collect(self._h, shots._handle(self), int(stream0), int(B), int(cap), 1 if flush else 0, vp(chips_ptr), vp(quality_ptr),
+                                              vp(records_ptr), vp(dets_ptr), vp(lms_ptr), vp(counts_ptr), vp(pending_ptr), vp(flags_ptr), 1))
+
     # -- launch plan / layer trace (parity tests) ---------------------------------------------
     def plan(self):
         """The context's launch plan: list of dicts name/kind/C/H/W/fused_away."""
@@ -719,6 +773,57 @@ class Tracker(object):
     def close(self):
         if getattr(self, "_h", None):
             self._L.cf_track_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BestShots(object):
+    """One cf_bestshot table: ``streams`` independent video streams on one GPU, ``entries`` entries each -- live tracks plus finished ones
+    not yet collected (``include/centerface_hip.h`` states the quality, the offer and the collect).  ``engine_or_device``: an ``Engine``
+    (the table is created at once on its GPU) or a device index (created by the first ``Engine.bestshot_offer`` / ``bestshot_collect``
+    that uses it, which must be on that GPU).  Per track id the table keeps the chip -- ``size`` x ``size`` uint8 BGR, as
+    ``align_faces_frame(size=size)`` cuts it -- with the highest quality: the variance of the Laplacian of its central half, times the
+    weights named in ``terms`` ('size': the face's side in the frame against the chip's; 'pose': the nose's offset from the eye-mouth
+    axis; 'score': the detector's).  Only rows with ``misses == 0`` and ``hits >= min_hits`` are offered.  A stream with more live
+    and uncollected tracks than ``entries`` does NOT ENTER the surplus (flag bit 0) until an entry is free.  The formula and the defaults
+    are this project's choices; no accuracy claim is made for them.  Engines of one GPU may share a table: its calls are ordered in call
+    order."""
+
+    def __init__(self, engine_or_device, streams, size=112, entries=320, min_hits=2, terms=("size", "pose", "score")):
+        self._L = _lib.lib()
+        self._o = _lib.bestshot_opts(size, entries, min_hits, terms)
+        self.streams, self.size, self.entries = int(streams), int(size), int(entries)
+        self._h = None
+        if isinstance(engine_or_device, Engine):
+            self.device = engine_or_device.device
+            self._handle(engine_or_device)
+        else:
+            self.device = int(engine_or_device)
+            # refuse bad options now, not at the first offer (no context: the library checks the arguments and tells)
+            out = C.c_void_p()
+            self._L.cf_bestshot_create(None, self.streams, C.byref(self._o), C.byref(out))
+            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
+            if "null context" not in why:
+                raise _lib.CenterFaceValueError(-1, why)
+
+    def _handle(self, engine):
+        """The cf_bestshot, created with ``engine``'s context on first use."""
+        if self._h is None:
+            if engine.device != self.device:
+                raise ValueError("the table was made for device %d, the engine runs on device %d" % (self.device, engine.device))
+            out = C.c_void_p()
+            _lib.check(self._L.cf_bestshot_create(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
+            self._h = out
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.cf_bestshot_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -978,7 +1083,7 @@ class CenterFace(object):
             out.append((d, l) if self.landmarks else d)
         return out
 
-    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None, follow=None, detect=True):
+    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None, follow=None, detect=True, best=None):
         """The chunk loop of every product path: ``forward`` enqueues ``frames`` in slices of ``per`` (default ``max_batch``), each is
         decoded, and while the engine still holds it the steps that were asked for run in this order: ``tracker`` is advanced -- image b
         of the chunk that starts at frame i continues its stream i + b --, ``cover`` = (array, fmt, options) has the chunk's slice of
@@ -988,7 +1093,10 @@ class CenterFace(object):
         forward, decode or update at all -- each chunk is followed, then covered or drawn, and its results are the followed rows
         (``_followed``).  ``merge`` = (metric, thresh, edge) says
         that the forward is a tiled one: the tiles' rows are merged, in frame pixels; otherwise the decode rescales, and the rescale is
-        switched off again whatever happens.  Returns the per-frame results."""
+        switched off again whatever happens.  ``best`` = (shots, array, fmt, template, flush, sink): behind the update and the follow the
+        chips of the tracked rows are cut from the chunk's slice of the array (``Engine.align_faces_frame`` at ``shots.size``) and offered
+        to ``shots`` (``Engine.bestshot_offer``); after the loop ONE ``Engine.bestshot_collect`` over the call's streams (``flush``) is
+        appended to ``sink``.  Returns the per-frame results."""
         eng, out = self.engine, []
         per = per or eng.max_batch
         if merge is None and detect:
@@ -1009,6 +1117,10 @@ class CenterFace(object):
                     d, l, _, n, _ = eng.track_follow(part, follow[1], tracker, i, **follow[2])
                     if not detect:
                         res = self._followed(d, l, n, _lib.frame_planes(part, follow[1], writable=False)[2:4], merge is not None)
+                if best is not None:
+                    part = best[1][i:i + per]
+                    cut, offs, _ = eng.align_faces_frame(part, best[2], best[0].size, template=best[3])
+                    eng.bestshot_offer(best[0], cut, offs, _lib.frame_planes(part, best[2], writable=False)[2:4], i)
                 if cover is not None:
                     eng.cover_faces(cover[0][i:i + per], cover[1], **cover[2])
                 if draw is not None:
@@ -1017,6 +1129,8 @@ class CenterFace(object):
                     cut, offs, _ = chips(i, i + per)
                     res = [(d, l, cut[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(res)]
                 out.extend(res)
+            if best is not None and len(frames):
+                best[5].append(eng.bestshot_collect(best[0], 0, len(frames), flush=best[4]))
         finally:
             if merge is None and detect:
                 eng.set_rescale(0.0, 0.0)
@@ -1122,6 +1236,44 @@ class CenterFace(object):
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
         return out, self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options),
                                 follow=self._follow(follow, detect, tracker, out, fmt), detect=detect)
+
+    def best_shots(self, frames, fmt="bgr", *, tracker, shots, tiled=False, tile=None, overlap=None, follow=None, detect=True, flush=False,
+                   template=None):
+        """One chip per appearance of a person: detection, tracking and best-shot selection of ``frames`` -- BGR uint8 [B,h,w,3]
+        (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] -- where image k of a call is the next frame of stream k of ``tracker`` (a
+        ``Tracker``) and of ``shots`` (a ``BestShots``), as in ``anonymize(tracker=)``: a video is fed one call per frame, n cameras n
+        images per call.  Per chunk: forward, decode (``tiled=True``: ``detect_tiled``'s path with ``tile``, ``overlap``, on frames of any
+        even size), ``track_update``, the follow if asked for (``follow``, ``detect``: as ``anonymize``), then the aligned chips of the
+        tracked rows are cut from the frames at ``shots.size`` (``template``: as ``Engine.align_faces_frame``) and offered to the table;
+        after the last chunk the finished entries of the call's streams are collected -- ``flush=True`` finishes every live track first
+        (the end of the video).  Returns, per stream, the list of finished shots in finishing order: dicts with ``id``, ``quality``,
+        ``chip`` [size, size, 3], ``det`` [5], ``lms`` [10] (the row of the best frame, in the tracker's space) and ``record`` (the eight
+        int32 of ``Engine.bestshot_collect``).  The quality formula is this project's choice; no accuracy claim is made for it."""
+        if not self.landmarks:
+            raise ValueError("best_shots needs the landmarks: construct CenterFace(..., landmarks=True)")
+        if tracker is None or shots is None:
+            raise ValueError("best_shots needs tracker= and shots=")
+        bgr = _lib.frame_format(fmt) == _lib.CF_FRAME_BGR
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != (4 if bgr else 3):
+            raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (frames.shape,))
+        eng, sink = self.engine, []
+        best = (shots, frames, fmt, template, bool(flush), sink)
+        fol = self._follow(follow, detect, tracker, frames, fmt)
+        if tiled:
+            self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, True, False), merge=("ios", 0.5, 2.0), tracker=tracker, follow=fol,
+                        detect=detect, best=best)
+        else:
+            want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
+            if frames.shape[1:] != want:
+                raise ValueError("frames must be %s per frame (this instance was built for %dx%d), got %s" % ((want,) + self.src_hw + (frames.shape[1:],)))
+            self._drive(frames, eng.forward_resized_enqueue if bgr else lambda chunk: eng.forward_yuv_enqueue(chunk, fmt), tracker=tracker, follow=fol,
+                        detect=detect, best=best)
+        if not sink:
+            return []
+        chips, quality, records, dets, lms, counts = sink[0][:6]
+        return [[{"id": int(records[s, k, 0]), "quality": int(quality[s, k]), "chip": chips[s, k].copy(), "det": dets[s, k].copy(), "lms": lms[s, k].copy(),
+                  "record": records[s, k].copy()} for k in range(int(counts[s]))] for s in range(len(frames))]
 
     def _draw_options(self, options, tracker, yuv):
         """The options of ``annotate`` / ``annotate_yuv`` -> those of ``Engine.draw_faces``: the reference's look (demo.py:15-23: green

@@ -513,6 +513,38 @@ struct FollowParams {
 const char* follow_check(const cf_follow_opts* o, int format, int B, int h, int w, int pitch0, int pitch1);
 hipError_t launch_track_follow(hipStream_t s, const FollowParams& p);
 
+// Best-shot selection (cf_bestshot.hip; the statement is in include/centerface_hip.h).  The table's device state, per stream and entry:
+// erec kBestRecInts int32 (state, id, best_t, first_t, last_t, n_offered, done_seq, parts[4], -, Q as int64, -, -), erow kBestRowFloats
+// float32 (det[5], lms[10], -), the chip; per stream smeta kBestStreamInts int32 (t, seq, sticky flags, -).  All zero at first.
+constexpr int kBestMaxEntries = 2048, kBestMaxRows = kTrackMaxSlots, kBestRecInts = 16, kBestRowFloats = 16, kBestStreamInts = 4, kBestScratchInts = 6;
+struct BestTable { int size, entries, min_hits, terms; int32_t* erec; float* erow; uint8_t* chips; int32_t* smeta; };
+// the rows of B images: boxes [B][rows][4], scores (stride score_stride floats per row), lms [B][rows][10], info [B][rows][3], counts [B]
+struct BestRows { const float* boxes; const float* scores; int score_stride; const float* lms; const int32_t* info; const int* counts; int rows; };
+struct BestOffer {
+    BestTable t; BestRows r;
+    int stream0, B;
+    const uint8_t* chips;        // [cap_faces][S][S][3], 16-byte aligned
+    const int* offsets;          // [B + 1]
+    int cap_faces;
+    double fx, fy;
+    long long* q;                // [cap_faces]: Q of the chip of an eligible row, else -1 (the caller's `quality`, or scratch)
+    int32_t* sc;                 // scratch [cap_faces][kBestScratchInts]: parts[4], the row b * rows + i whose image names the chip or -1, -
+    int32_t* jobs;               // scratch [B][rows][2]: chip -> entry (of all streams), or -1
+    int32_t* flags;              // [B] or nullptr
+};
+struct BestCollect {
+    BestTable t;
+    int stream0, B, cap, flush;
+    void* chips; long long* quality; int32_t* records; float* dets; float* lms; int32_t* counts; int32_t* pending; int32_t* flags;      // [B][cap]... / [B]; any may be nullptr
+    int32_t* jobs;               // scratch [B][cap][2]
+};
+// nullptr, or what is wrong with the options / the number of streams (host only)
+const char* best_check(const cf_bestshot_opts* o, int n_streams);
+size_t best_chip_bytes(int size);
+hipError_t launch_best_score(hipStream_t s, const BestOffer& p);       // the score kernel alone: t.size, t.min_hits, t.terms, r, chips, offsets, q, sc
+hipError_t launch_best_offer(hipStream_t s, const BestOffer& p);       // score, decide, copy
+hipError_t launch_best_collect(hipStream_t s, const BestCollect& p);   // collect, copy
+
 // layout converters used by cf_get_heads and the per-op test entry points
 hipError_t launch_nchw_to_nhwc(hipStream_t s, int dtype, const float* src /*f32 NCHW*/, void* dst /*T NHWC*/,
                                int B, int C, int H, int W);

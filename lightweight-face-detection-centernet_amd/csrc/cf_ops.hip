@@ -1058,4 +1058,117 @@ int cf_op_follow(int device, const cf_track_opts* o, const cf_follow_opts* fo, i
     return op_track_sequence("cf_op_follow", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, &fw);
 }
 
+// The score kernel of cf_bestshot_offer alone: one image whose n rows all count and are eligible (ids 1 .. n, hits 1000, misses 0).
+int cf_op_chip_quality(int device, const cf_bestshot_opts* o, const uint8_t* chips, const float* boxes, const float* scores, const float* lms,
+                       int n, double fx, double fy, int64_t* quality, int32_t* parts) {
+    const char* bad = best_check(o, 1);
+    if (!bad && (!chips || !boxes || !scores || !lms || !quality || !parts)) bad = "null argument";
+    if (!bad && (n < 1 || n > 65536)) bad = "n must be in 1..65536";
+    if (!bad && (!std::isfinite(fx) || !std::isfinite(fy) || !(fx > 0) || !(fy > 0))) bad = "fx and fy must be finite and greater than 0";
+    if (bad) { g_op_error = std::string("cf_op_chip_quality: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    std::vector<int32_t> info((size_t)n * 3);
+    for (int i = 0; i < n; ++i) { info[(size_t)i * 3] = i + 1; info[(size_t)i * 3 + 1] = 1000; info[(size_t)i * 3 + 2] = 0; }
+    const int offs[2] = {0, n};
+    BestOffer p{};
+    p.t.size = o->size; p.t.entries = o->entries; p.t.min_hits = o->min_hits; p.t.terms = o->terms;
+    p.r = BestRows{(const float*)sc.up(boxes, (size_t)n * 4 * sizeof(float)), (const float*)sc.up(scores, (size_t)n * sizeof(float)), 1,
+                   (const float*)sc.up(lms, (size_t)n * 10 * sizeof(float)), (const int32_t*)sc.upv(info), (const int*)sc.up(&offs[1], sizeof(int)), n};
+    p.B = 1; p.cap_faces = n; p.fx = fx; p.fy = fy;
+    p.chips = (const uint8_t*)sc.up(chips, (size_t)n * best_chip_bytes(o->size));
+    p.offsets = (const int*)sc.up(offs, sizeof(offs));
+    p.q = (long long*)sc.alloc((size_t)n * sizeof(long long)); p.sc = (int32_t*)sc.alloc((size_t)n * kBestScratchInts * sizeof(int32_t));
+    if (sc.err == hipSuccess) sc.chk(hipStreamSynchronize(sc.s));       // (offs and info are on this stack frame)
+    if (sc.err == hipSuccess) sc.chk(launch_best_score(sc.s, p));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(quality, p.q, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpy2DAsync(parts, 4 * sizeof(int32_t), p.sc, kBestScratchInts * sizeof(int32_t), 4 * sizeof(int32_t), n, hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_chip_quality");
+}
+
+// cf_bestshot_offer and cf_bestshot_collect, frame after frame, with the state of a fresh table (every entry FREE, t = seq = 0)
+int cf_op_bestshot(int device, const cf_bestshot_opts* o, int n_streams, int n_frames, int rows, const float* boxes, const float* scores,
+                   const float* lms, const int32_t* info, const int32_t* counts, const int32_t* chip_counts, const uint8_t* chips,
+                   const uint8_t* collect, int cap, double fx, double fy, uint8_t* out_chips, int64_t* out_quality, int32_t* out_records,
+                   float* out_dets, float* out_lms, int32_t* out_counts, int32_t* out_pending, int32_t* out_flags, int32_t* offer_flags,
+                   int64_t* offer_quality) {
+    const char* bad = best_check(o, n_streams);
+    if (!bad && (!boxes || !scores || !lms || !info || !counts || !chip_counts || !chips || !collect || !out_chips || !out_quality || !out_records ||
+                 !out_dets || !out_lms || !out_counts || !out_pending || !out_flags || !offer_flags || !offer_quality)) bad = "null argument";
+    if (!bad && n_frames < 1) bad = "n_frames must be at least 1";
+    if (!bad && (rows < 1 || rows > kBestMaxRows)) bad = "rows must be in 1..1024";
+    if (!bad && (cap < 0 || cap > o->entries)) bad = "cap must be in 0..entries";
+    if (!bad && (!std::isfinite(fx) || !std::isfinite(fy) || !(fx > 0) || !(fy > 0))) bad = "fx and fy must be finite and greater than 0";
+    if (!bad && (long long)n_frames * n_streams * std::max(rows, std::max(cap, 1)) > (1 << 24)) bad = "more than 2^24 rows";
+    const size_t S = bad ? 0 : n_streams, F = bad ? 0 : n_frames, one = bad ? 0 : best_chip_bytes(o->size), E = bad ? 0 : o->entries;
+    if (!bad) for (size_t k = 0; k < F * S; ++k) if (counts[k] < 0 || chip_counts[k] < 0) { bad = "negative count"; break; }
+    if (!bad) for (size_t f = 0; f < F; ++f) if (collect[f] > 2) { bad = "collect must be 0, 1 or 2"; break; }
+    // the chips of every frame, packed as an align call packs them: offsets [F][S + 1] within the frame, base[f] chips before frame f
+    std::vector<int> offs(F * (S + 1)), base(F + 1, 0);
+    if (!bad) {
+        for (size_t f = 0; f < F; ++f) {
+            int off = 0;
+            for (size_t s = 0; s < S; ++s) { offs[f * (S + 1) + s] = off; off += std::min(chip_counts[f * S + s], rows); }
+            offs[f * (S + 1) + S] = off; base[f + 1] = base[f] + off;
+        }
+        if ((double)base[F] * (double)one > 1073741824.0 || (double)S * E * (double)one > 1073741824.0 || (double)F * S * std::max(cap, 1) * (double)one > 1073741824.0)
+            bad = "more than 1 GiB of chips";
+    }
+    if (bad) { g_op_error = std::string("cf_op_bestshot: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    std::vector<uint8_t> packed(std::max<size_t>((size_t)base[F] * one, 16));
+    for (size_t f = 0; f < F; ++f)
+        for (size_t s = 0; s < S; ++s) {
+            const size_t m = (size_t)(offs[f * (S + 1) + s + 1] - offs[f * (S + 1) + s]);
+            if (m) memcpy(packed.data() + ((size_t)base[f] + offs[f * (S + 1) + s]) * one, chips + (f * S + s) * rows * one, m * one);
+        }
+    const size_t nin = F * S * rows, nout = F * S * cap, nq = std::max<size_t>(base[F], 1);
+    BestOffer p{};
+    p.t = BestTable{o->size, o->entries, o->min_hits, o->terms, (int32_t*)sc.alloc(S * E * kBestRecInts * sizeof(int32_t)),
+                    (float*)sc.alloc(S * E * kBestRowFloats * sizeof(float)), (uint8_t*)sc.alloc(S * E * one), (int32_t*)sc.alloc(S * kBestStreamInts * sizeof(int32_t))};
+    p.r = BestRows{(const float*)sc.up(boxes, nin * 4 * sizeof(float)), (const float*)sc.up(scores, nin * sizeof(float)), 1, (const float*)sc.up(lms, nin * 10 * sizeof(float)),
+                   (const int32_t*)sc.up(info, nin * 3 * sizeof(int32_t)), (const int*)sc.up(counts, F * S * sizeof(int)), rows};
+    p.stream0 = 0; p.B = n_streams; p.fx = fx; p.fy = fy;
+    p.chips = (const uint8_t*)sc.upv(packed); p.offsets = (const int*)sc.upv(offs);
+    p.q = (long long*)sc.alloc(nq * sizeof(long long)); p.sc = (int32_t*)sc.alloc(nq * kBestScratchInts * sizeof(int32_t));
+    p.jobs = (int32_t*)sc.alloc(S * rows * 2 * sizeof(int32_t)); p.flags = (int32_t*)sc.alloc(F * S * sizeof(int32_t));
+    BestCollect c{};
+    c.t = p.t; c.stream0 = 0; c.B = n_streams; c.cap = cap;
+    c.chips = sc.up(out_chips, nout * one); c.quality = (long long*)sc.up(out_quality, nout * sizeof(long long));
+    c.records = (int32_t*)sc.up(out_records, nout * 8 * sizeof(int32_t)); c.dets = (float*)sc.up(out_dets, nout * 5 * sizeof(float));
+    c.lms = (float*)sc.up(out_lms, nout * 10 * sizeof(float));
+    c.counts = (int32_t*)sc.alloc(F * S * sizeof(int32_t)); c.pending = (int32_t*)sc.alloc(F * S * sizeof(int32_t)); c.flags = (int32_t*)sc.alloc(F * S * sizeof(int32_t));
+    c.jobs = (int32_t*)sc.alloc(S * std::max(cap, 1) * 2 * sizeof(int32_t));
+    const BestOffer p0 = p;
+    const BestCollect c0 = c;
+    for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
+        p.r.boxes = p0.r.boxes + f * S * rows * 4; p.r.scores = p0.r.scores + f * S * rows; p.r.lms = p0.r.lms + f * S * rows * 10;
+        p.r.info = p0.r.info + f * S * rows * 3; p.r.counts = p0.r.counts + f * S;
+        p.chips = p0.chips + (size_t)base[f] * one; p.offsets = p0.offsets + f * (S + 1); p.cap_faces = base[f + 1] - base[f];
+        p.q = p0.q + base[f]; p.sc = p0.sc + (size_t)base[f] * kBestScratchInts; p.flags = p0.flags + f * S;
+        sc.chk(launch_best_offer(sc.s, p));
+        if (!collect[f]) continue;
+        c.flush = collect[f] == 2;
+        c.chips = (uint8_t*)c0.chips + f * S * cap * one; c.quality = c0.quality + f * S * cap; c.records = c0.records + f * S * cap * 8;
+        c.dets = c0.dets + f * S * cap * 5; c.lms = c0.lms + f * S * cap * 10;
+        c.counts = c0.counts + f * S; c.pending = c0.pending + f * S; c.flags = c0.flags + f * S;
+        if (sc.err == hipSuccess) sc.chk(launch_best_collect(sc.s, c));
+    }
+    std::vector<long long> q(nq);
+    auto down = [&](void* dst, const void* src, size_t bytes) { if (bytes && sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc.s)); };
+    if (sc.err == hipSuccess) sc.chk(hipStreamSynchronize(sc.s));         // nothing is written unless the whole sequence ran
+    down(out_chips, c0.chips, nout * one); down(out_quality, c0.quality, nout * sizeof(long long)); down(out_records, c0.records, nout * 8 * sizeof(int32_t));
+    down(out_dets, c0.dets, nout * 5 * sizeof(float)); down(out_lms, c0.lms, nout * 10 * sizeof(float));
+    down(out_counts, c0.counts, F * S * sizeof(int32_t)); down(out_pending, c0.pending, F * S * sizeof(int32_t)); down(out_flags, c0.flags, F * S * sizeof(int32_t));
+    down(offer_flags, p0.flags, F * S * sizeof(int32_t)); down(q.data(), p0.q, (size_t)base[F] * sizeof(long long));
+    const int r = sc.result("cf_op_bestshot");
+    if (r != CF_OK) return r;
+    for (size_t k = 0; k < nin; ++k) offer_quality[k] = -1;
+    for (size_t f = 0; f < F; ++f)
+        for (size_t s = 0; s < S; ++s) {
+            const int o0 = offs[f * (S + 1) + s], m = offs[f * (S + 1) + s + 1] - o0;
+            for (int i = 0; i < m; ++i) offer_quality[(f * S + s) * rows + i] = q[(size_t)base[f] + o0 + i];
+        }
+    return CF_OK;
+}
+
 }  // extern "C"

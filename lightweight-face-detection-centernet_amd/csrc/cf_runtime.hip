@@ -167,6 +167,7 @@ struct cf_ctx {
     // cf_track_follow: B > 0 = the rows in tk are the follow's, of B frames in the tracker's space (H x W network input, or -- tiled -- H x W
     // frames), and the newest whatever `stage` says; any forward, threshold decode, merge or update ends that (B = 0)
     struct { DevBuf slot_moves, moves; int B = 0, H = 0, W = 0; bool tiled = false; } fo;
+    struct { DevBuf q, sc, jobs, flags, chips, off, out; } bs;          // cf_bestshot_offer / cf_bestshot_collect: per-call scratch and the staging of their host forms
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
     // input format, batch): the second forward with a key captures it, later ones replay it
     struct FwdGraph { const void* in; int fmt, B; hipGraphExec_t exec; bool broken; unsigned long long used; };
@@ -665,7 +666,8 @@ int cf_destroy(cf_ctx* c) {
         if (p) hipFree(p);
     for (const DevBuf* b : {&c->src.buf, &c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->dr_recs, &c->tl_rects_dev,
                             &c->tl.cand, &c->tl.cand_count, &c->tl.order, &c->tl.mask, &c->tl.dets, &c->tl.lms, &c->tl.corners, &c->tl.counts, &c->tl.flags,
-                            &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags})
+                            &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags, &c->fo.slot_moves, &c->fo.moves,
+                            &c->bs.q, &c->bs.sc, &c->bs.jobs, &c->bs.flags, &c->bs.chips, &c->bs.off, &c->bs.out})
         if (b->p) hipFree(b->p);
     if (c->h_thr) hipHostFree(c->h_thr);
     if (c->ev_thr) hipEventDestroy(c->ev_thr);
@@ -2195,6 +2197,176 @@ int cf_track_follow(cf_ctx* c, cf_tracker* t, int stream0, int B, const cf_follo
     }
     return read_out(c, B, M, p.out_counts, nullptr, counts, nullptr,
                     {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)}, {moves, p.moves, 4 * sizeof(int)}});
+}
+
+// Best-shot selection (cf_bestshot.hip): the table's state lives in device memory the table owns and is advanced only by kernels, on the
+// stream of the context that issues the call; the calls are ordered on the table's event exactly as a tracker's are.
+}  // extern "C"
+struct cf_bestshot {
+    int device = 0, S = 0;
+    cf_bestshot_opts o{};
+    int32_t* erec = nullptr; float* erow = nullptr; uint8_t* chips = nullptr; int32_t* smeta = nullptr;
+    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
+    BestTable table() const { return BestTable{o.size, o.entries, o.min_hits, o.terms, erec, erow, chips, smeta}; }
+};
+extern "C" {
+
+int cf_bestshot_destroy(cf_bestshot* t) {
+    if (!t) return CF_OK;
+    hipSetDevice(t->device);
+    if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
+    if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
+    for (void* p : {(void*)t->erec, (void*)t->erow, (void*)t->chips, (void*)t->smeta}) if (p) hipFree(p);
+    delete t;
+    return CF_OK;
+}
+
+int cf_bestshot_create(cf_ctx* c, int n_streams, const cf_bestshot_opts* o, cf_bestshot** out) {
+    const char* why = best_check(o, n_streams);
+    if (!why && !out) why = "null out";
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_bestshot_create: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_bestshot_create: %s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t slots = (size_t)n_streams * o->entries, one = best_chip_bytes(o->size);
+    const size_t nrec = slots * kBestRecInts * sizeof(int32_t), nrow = slots * kBestRowFloats * sizeof(float), nmeta = (size_t)n_streams * kBestStreamInts * sizeof(int32_t);
+    const double need = (double)slots * (double)one + (double)nrec + (double)nrow + (double)nmeta;
+    size_t mem_free = 0, mem_total = 0;
+    HIPCHK(c, hipMemGetInfo(&mem_free, &mem_total));
+    if (need > (double)mem_free)                         // before anything is allocated
+        return c->fail(CF_ENOMEM, "cf_bestshot_create: %d streams x %d entries of %d x %d chips need %.1f MB, the device has %.1f MB free", n_streams, o->entries,
+                       o->size, o->size, need / 1e6, (double)mem_free / 1e6);
+    cf_bestshot* t = new cf_bestshot();
+    t->device = c->device; t->S = n_streams; t->o = *o;
+    hipError_t e = hipStreamCreateWithFlags(&t->ts, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->erec, nrec);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->erow, nrow);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->chips, slots * one);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->smeta, nmeta);
+    if (e == hipSuccess) e = hipMemsetAsync(t->erec, 0, nrec, t->ts);       // every entry FREE
+    if (e == hipSuccess) e = hipMemsetAsync(t->erow, 0, nrow, t->ts);
+    if (e == hipSuccess) e = hipMemsetAsync(t->smeta, 0, nmeta, t->ts);     // t = seq = 0, no flag
+    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        cf_bestshot_destroy(t);
+        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_bestshot_create: %d streams x %d entries: %s", n_streams, o->entries, hipGetErrorString(e));
+    }
+    *out = t;
+    return CF_OK;
+}
+
+int cf_bestshot_offer(cf_ctx* c, cf_bestshot* t, int stream0, int B, const void* chips, const int32_t* offsets, int cap_faces, int on_device,
+                      int h, int w, int64_t* quality, int32_t* flags, int out_on_device) {
+    const char* why = nullptr;
+    if (!t) why = "null table";
+    else if (!chips || !offsets) why = "null chips or offsets";
+    else if (cap_faces < 0) why = "cap_faces is negative";
+    else if (B < 1) why = "B must be at least 1";
+    else if (h < 2 || h > 8192 || w < 2 || w > 8192) why = "h and w must be in 2..8192";
+    else if (on_device && (reinterpret_cast<uintptr_t>(chips) & 15)) why = "device chips must be 16-byte aligned";
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_bestshot_offer: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_bestshot_offer: %s", why);
+    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_bestshot_offer: the table lives on device %d, the context on device %d", t->device, c->device);
+    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_bestshot_offer: B=%d exceeds max_batch %d", B, c->max_batch);
+    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_bestshot_offer: streams %d .. %d of a table with %d", stream0, stream0 + B - 1, t->S);
+    RowSet rows{};
+    if (int r = rows_for(c, "cf_bestshot_offer", ROWS_NEWEST, rows)) return r;
+    if (!rows.info) return c->fail(CF_ESTATE, "cf_bestshot_offer without a cf_track_update or cf_track_follow behind the last decode: the rows have no ids");
+    if (B != rows.B) return c->fail(CF_EINVAL, "cf_bestshot_offer: B=%d, the tracked rows are of %d images", B, rows.B);
+    if (rows.frame_space && (h != rows.H || w != rows.W))
+        return c->fail(CF_EINVAL, "cf_bestshot_offer: %d x %d frames, the rows are in frame %d x %d coordinates", w, h, rows.W, rows.H);
+    if (rows.stride > kBestMaxRows) return c->fail(CF_EINVAL, "cf_bestshot_offer: %d rows per image exceed %d", rows.stride, kBestMaxRows);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t one = best_chip_bytes(t->o.size), ncap = (size_t)std::max(cap_faces, 1);
+    auto& ws = c->bs;
+    if (int r = grow(c, ws.sc, ncap * kBestScratchInts * sizeof(int32_t), "scores", "cf_bestshot_offer")) return r;
+    if (int r = grow(c, ws.jobs, (size_t)B * rows.stride * 2 * sizeof(int32_t), "jobs", "cf_bestshot_offer")) return r;
+    if (int r = grow(c, ws.flags, (size_t)B * sizeof(int32_t), "flags", "cf_bestshot_offer")) return r;
+    if (!(out_on_device && quality)) if (int r = grow(c, ws.q, ncap * sizeof(long long), "qualities", "cf_bestshot_offer")) return r;
+    if (!on_device) {
+        if (int r = grow(c, ws.chips, ncap * one, "chips", "cf_bestshot_offer")) return r;
+        if (int r = grow(c, ws.off, ((size_t)B + 1) * sizeof(int32_t), "offsets", "cf_bestshot_offer")) return r;
+    }
+    BestOffer p{};
+    p.t = t->table();
+    p.r = BestRows{rows.corners, rows.dets + 4, 5, rows.lms, rows.info, rows.counts, rows.stride};
+    p.stream0 = stream0; p.B = B; p.cap_faces = cap_faces;
+    p.fx = rows.frame_space ? 1.0 : (double)w / (double)rows.W; p.fy = rows.frame_space ? 1.0 : (double)h / (double)rows.H;
+    p.chips = (const uint8_t*)(on_device ? chips : ws.chips.p); p.offsets = on_device ? (const int*)offsets : (const int*)ws.off.p;
+    p.q = out_on_device && quality ? (long long*)quality : (long long*)ws.q.p;
+    p.sc = (int32_t*)ws.sc.p; p.jobs = (int32_t*)ws.jobs.p; p.flags = out_on_device ? flags : (int32_t*)ws.flags.p;
+    if (!on_device) {
+        if (cap_faces > 0) HIPCHK(c, hipMemcpyAsync(ws.chips.p, chips, (size_t)cap_faces * one, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ws.off.p, offsets, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the offer or collect before this one, on whichever context's stream
+    HIPCHK(c, launch_best_offer(c->stream, p));
+    HIPCHK(c, hipEventRecord(t->ev, c->stream));
+    if (!out_on_device) {
+        if (quality && cap_faces > 0) HIPCHK(c, hipMemcpyAsync(quality, p.q, (size_t)cap_faces * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!on_device || !out_on_device) HIPCHK(c, hipStreamSynchronize(c->stream));      // host chips have been read, host outputs are there
+    return CF_OK;
+}
+
+int cf_bestshot_collect(cf_ctx* c, cf_bestshot* t, int stream0, int B, int cap, int flush, void* chips, int64_t* quality, int32_t* records,
+                        float* dets, float* lms, int32_t* counts, int32_t* pending, int32_t* flags, int out_on_device) {
+    if (!c) return CF_EINVAL;
+    if (!t) return c->fail(CF_EINVAL, "cf_bestshot_collect: null table");
+    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_bestshot_collect: the table lives on device %d, the context on device %d", t->device, c->device);
+    if (B < 1) return c->fail(CF_EINVAL, "cf_bestshot_collect: B=%d is less than 1", B);      // (no rows of ctx are involved: max_batch does not bound it)
+    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_bestshot_collect: streams %d .. %d of a table with %d", stream0, stream0 + B - 1, t->S);
+    if (cap < 0 || cap > t->o.entries) return c->fail(CF_EINVAL, "cf_bestshot_collect: cap=%d outside 0..entries %d", cap, t->o.entries);
+    if (out_on_device && chips && (reinterpret_cast<uintptr_t>(chips) & 15)) return c->fail(CF_EINVAL, "cf_bestshot_collect: device chips must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t one = best_chip_bytes(t->o.size), bc = (size_t)B * cap, nb = (size_t)B * sizeof(int32_t);
+    auto& ws = c->bs;
+    if (int r = grow(c, ws.jobs, std::max<size_t>(bc, 1) * 2 * sizeof(int32_t), "jobs", "cf_bestshot_collect")) return r;
+    BestCollect p{};
+    p.t = t->table(); p.stream0 = stream0; p.B = B; p.cap = cap; p.flush = flush ? 1 : 0; p.jobs = (int32_t*)ws.jobs.p;
+    // host outputs: the kernels write one scratch -- chips | quality | records | dets | lms | counts, pending, flags -- and the rows that exist come back
+    const size_t o_q = bc * one, o_rec = o_q + bc * sizeof(long long), o_det = o_rec + bc * 8 * sizeof(int32_t), o_lm = o_det + bc * 5 * sizeof(float),
+                 o_cnt = o_lm + bc * 10 * sizeof(float);
+    if (out_on_device) {
+        p.chips = chips; p.quality = (long long*)quality; p.records = records; p.dets = dets; p.lms = lms; p.counts = counts; p.pending = pending; p.flags = flags;
+    } else {
+        if (int r = grow(c, ws.out, o_cnt + 3 * nb, "collected rows", "cf_bestshot_collect")) return r;
+        uint8_t* base = (uint8_t*)ws.out.p;
+        p.chips = chips ? base : nullptr; p.quality = quality ? (long long*)(base + o_q) : nullptr; p.records = records ? (int32_t*)(base + o_rec) : nullptr;
+        p.dets = dets ? (float*)(base + o_det) : nullptr; p.lms = lms ? (float*)(base + o_lm) : nullptr;
+        p.counts = (int32_t*)(base + o_cnt); p.pending = p.counts + B; p.flags = p.counts + 2 * B;
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the offer or collect before this one, on whichever context's stream
+    HIPCHK(c, launch_best_collect(c->stream, p));
+    HIPCHK(c, hipEventRecord(t->ev, c->stream));
+    if (out_on_device) return CF_OK;
+    std::vector<int32_t> hc((size_t)3 * B);          // on this stack frame: never return while a copy into it may still be in flight
+    const hipError_t e1 = hipMemcpyAsync(hc.data(), p.counts, 3 * nb, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e1); HIPCHK(c, e2);
+    const struct { void* dst; const void* src; size_t row; } cols[] = {{chips, p.chips, one}, {quality, p.quality, sizeof(long long)}, {records, p.records, 8 * sizeof(int32_t)},
+                                                                       {dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}};
+    hipError_t e = hipSuccess;
+    for (int b = 0; b < B; ++b) {
+        const size_t n = (size_t)std::min(std::max(hc[b], 0), cap);
+        for (const auto& col : cols)
+            if (n && col.dst && e == hipSuccess)
+                e = hipMemcpyAsync((uint8_t*)col.dst + (size_t)b * cap * col.row, (const uint8_t*)col.src + (size_t)b * cap * col.row, n * col.row, hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t e3 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e); HIPCHK(c, e3);
+    if (counts) memcpy(counts, hc.data(), nb);
+    if (pending) memcpy(pending, hc.data() + B, nb);
+    if (flags) memcpy(flags, hc.data() + 2 * B, nb);
+    return CF_OK;
 }
 
 int cf_event_record(cf_ctx* c, int slot) {

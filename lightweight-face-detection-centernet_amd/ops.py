@@ -429,6 +429,62 @@ def follow_sequence(boxes, scores, lms, counts, frames, fmt="bgr", space_hw=None
     return od, ol, oi, oc, fl, om
 
 
+def chip_quality(chips, boxes, scores, lms, fx=1.0, fy=1.0, *, min_hits=2, terms=("size", "pose", "score"), device=0):
+    """The scoring kernel of the best-shot table alone (``cf_op_chip_quality``): chips uint8 [n, S, S, 3] BGR, their rows boxes [n, 4],
+    scores [n], lms [n, 10] and the frame pixels per unit of the rows' space ``fx``, ``fy`` -> (quality int64 [n], parts int32 [n, 4] =
+    sharp, size_w, pose_w, score_w).  The formula (``include/centerface_hip.h``) is this project's choice; no accuracy claim is made."""
+    ch = np.ascontiguousarray(chips, dtype=np.uint8)
+    if ch.ndim != 4 or ch.shape[1] != ch.shape[2] or ch.shape[3] != 3:
+        raise ValueError("chips must be [n, S, S, 3], got %s" % (ch.shape,))
+    n = ch.shape[0]
+    o = _lib.bestshot_opts(ch.shape[1], 1, min_hits, terms)
+    b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(n, 4)
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(n)
+    lm = np.ascontiguousarray(lms, dtype=np.float32).reshape(n, 10)
+    q, parts = np.zeros((n,), np.int64), np.zeros((n, 4), np.int32)
+    _lib.check(_lib.lib().cf_op_chip_quality(device, C.byref(o), ptr(ch), ptr(b), ptr(sc), ptr(lm), n, float(fx), float(fy), ptr(q), ptr(parts)), op=True)
+    return q, parts
+
+
+def bestshot_sequence(boxes, scores, lms, info, counts, chips, collect, cap=None, fx=1.0, fy=1.0, chip_counts=None, *, entries=320, min_hits=2,
+                      terms=("size", "pose", "score"), out=None, device=0):
+    """A whole scripted sequence of offers and collects on a fresh best-shot table (``cf_op_bestshot``), no engine and no tracker: frame f
+    of stream s is offered the rows i < counts[f, s] of boxes [F, S, rows, 4], scores [F, S, rows], lms [F, S, rows, 10], info
+    [F, S, rows, 3] = id, hits, misses with the chips [F, S, rows, Sz, Sz, 3]; the leading ``chip_counts[f, s]`` rows have a chip (default:
+    all rows).  ``collect`` [F]: 0 none, 1 collect, 2 collect with flush, after that frame's offer, ``cap`` rows per stream (default
+    ``entries``).  Returns a dict: chips [F, S, cap, Sz, Sz, 3], quality [F, S, cap] int64, records [F, S, cap, 8], dets [F, S, cap, 5],
+    lms [F, S, cap, 10], counts / pending / flags [F, S] (zero on frames without a collect), offer_flags [F, S], offer_quality
+    [F, S, rows] int64.  ``out``: a dict of arrays for chips / quality / records / dets / lms whose bytes rows at and past a count keep
+    (zeros by default)."""
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    if b.ndim != 4 or b.shape[3] != 4:
+        raise ValueError("boxes must be [F, S, rows, 4], got %s" % (b.shape,))
+    F, S, rows, _ = b.shape
+    ch = np.ascontiguousarray(chips, dtype=np.uint8)
+    if ch.ndim != 6 or ch.shape[:3] != (F, S, rows) or ch.shape[3] != ch.shape[4] or ch.shape[5] != 3:
+        raise ValueError("chips must be [F, S, rows, Sz, Sz, 3], got %s" % (ch.shape,))
+    Sz = ch.shape[3]
+    o = _lib.bestshot_opts(Sz, entries, min_hits, terms)
+    cap = int(o.entries if cap is None else cap)
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(F, S, rows)
+    lm = np.ascontiguousarray(lms, dtype=np.float32).reshape(F, S, rows, 10)
+    nf = np.ascontiguousarray(info, dtype=np.int32).reshape(F, S, rows, 3)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(F, S)
+    cc = np.full((F, S), rows, np.int32) if chip_counts is None else np.ascontiguousarray(chip_counts, dtype=np.int32).reshape(F, S)
+    co = np.ascontiguousarray(collect, dtype=np.uint8).reshape(F)
+    kc = max(cap, 0)
+    shapes = {"chips": ((F, S, kc, Sz, Sz, 3), np.uint8), "quality": ((F, S, kc), np.int64), "records": ((F, S, kc, 8), np.int32),
+              "dets": ((F, S, kc, 5), np.float32), "lms": ((F, S, kc, 10), np.float32)}
+    r = {k: np.zeros(sh, dt) if out is None or k not in out else np.ascontiguousarray(out[k], dtype=dt).reshape(sh) for k, (sh, dt) in shapes.items()}
+    for k in ("counts", "pending", "flags", "offer_flags"):
+        r[k] = np.zeros((F, S), np.int32)
+    r["offer_quality"] = np.zeros((F, S, rows), np.int64)
+    _lib.check(_lib.lib().cf_op_bestshot(device, C.byref(o), S, F, rows, ptr(b), ptr(sc), ptr(lm), ptr(nf), ptr(cn), ptr(cc), ptr(ch), ptr(co), cap,
+                                         float(fx), float(fy), ptr(r["chips"]), ptr(r["quality"]), ptr(r["records"]), ptr(r["dets"]), ptr(r["lms"]),
+                                         ptr(r["counts"]), ptr(r["pending"]), ptr(r["flags"]), ptr(r["offer_flags"]), ptr(r["offer_quality"])), op=True)
+    return r
+
+
 def ctdet_decode(heat, wh, reg=None, K=100, lm=None, device=0):
     """ctdet_decode (centerface_ext.py:52-82): (dets [B,K,6], lms [B,K,10]|None, inds [B,K] int64)."""
     heat, wh, reg, lm = f32(heat), f32(wh), f32(reg), f32(lm)

@@ -538,6 +538,70 @@ int cf_track_follow(cf_ctx* ctx, cf_tracker* trk, int stream0, int B, const cf_f
                     int on_device, int h, int w, int pitch0, int pitch1, float* dets, float* lms, int32_t* info, int32_t* counts,
                     int32_t* moves, int out_on_device);
 
+/* ---- scene cuts: found in the luma on the device, the cut streams' tracks reset without a host round trip -------------------------
+ * Tracks, the follower, the best shots and the annotation all assume that frame n + 1 continues frame n.  At an edit point of a video it
+ * does not: held tracks keep covering the places where the previous scene's faces stood, the follower matches old templates against
+ * unrelated pixels, and follow-only frames cover nothing that is new.  cf_track_reset is the remedy, but a host call the caller has to
+ * time by hand.  cf_scene_check measures whether a frame continues its stream and, where it does not, frees the stream's tracks on the
+ * device:
+ *   frame -> cf_scene_check [resets the cut streams' tracks] -> (cf_forward* -> decode -> cf_track_update)? -> cf_track_follow -> ...
+ * CALL IT BEFORE THE FRAME'S UPDATE OR FOLLOW.  The arithmetic is this library's own statement (csrc/cf_scene.hip; restated in
+ * tests/scene_cases.py; device and restatement are equal bit for bit).  All integers.  The defaults the Python layer uses (hist 350,
+ * grid 640) are this project's choices: there is no labelled video here, nobody has measured them, and no accuracy claim is made.
+ *
+ *   Luma.  The follower's: of a 4:2:0 frame the sample's Y byte, of a BGR frame (29*B + 150*G + 77*R + 128) >> 8.
+ *   Signature of an h x w frame, 128 int32:
+ *     bins[k], k < 64: the number of pixels with luma >> 2 == k.
+ *     mean[8*j + i], i, j < 8: cell (i, j) covers x in [(i*w)/8, ((i+1)*w)/8) and y in [(j*h)/8, ((j+1)*h)/8) (integer division; the
+ *       cells differ in size when 8 does not divide the side).  With n pixels in the cell the value is (sum of luma + n/2) / n.  A cell
+ *       sum stays below 2^31 for every allowed frame size.
+ *     Pitch padding bytes never count.
+ *   State per stream of a cf_scene: the last signature, the (h, w) it was taken at, valid, run; all zero at first.
+ *   One check of stream s with a frame, N = h*w:
+ *     FIRST when the state is not valid or its (h, w) differ from the frame's: hist = grid = 0, run = 0.  Nothing is reset.
+ *     Otherwise A = sum_k |bins[k] - prev.bins[k]| (int64), hist = (A * 1000) / (2 * N), in 0..1000: the per mille of pixels that
+ *       changed bin; grid = sum_k |mean[k] - prev.mean[k]|, in 0..16320.
+ *       CUT when hist >= hist_thresh && grid >= grid_thresh; run = 0.
+ *       SAME otherwise; run = min(run + 1, 1 << 30).
+ *     After any code the state takes the frame's signature and (h, w), valid = 1.
+ *     Output: out[b][4] int32 = code, hist, grid, run.
+ *     On CUT with a tracker given every slot of stream s is freed exactly as cf_track_reset(trk, s) frees it: the slots' meta words
+ *     become zero, next_id is untouched (ids are not reused), the latched space stays, the follower records need no word.  This is
+ *     decided and done by the kernel; no count or code is read on the host.
+ * Both conditions must hold: a pan changes the cell means but not the histogram, a face-sized object entering changes neither much.
+ * TWO LIMITS.  A full-frame brightness jump (a flash) changes both measures and is reported as a cut; the cost is lost held tracks, not
+ * uncovered detections.  A dissolve is not one cut: no pair of neighbouring frames differs enough.
+ * On the device: one bandwidth-bound pass over the luma (many workgroups per frame, each leaving 72 int32 partials) and one wave per
+ * stream that finishes the sums, decides, resets and stores the signature. */
+#define CF_SCENE_FIRST 0
+#define CF_SCENE_SAME  1
+#define CF_SCENE_CUT   2
+typedef struct cf_scene cf_scene;
+typedef struct cf_scene_opts {
+    int32_t hist_thresh;  /* 0..1000 per mille */
+    int32_t grid_thresh;  /* 0..16320 */
+} cf_scene_opts;
+/* ctx names the device (and carries the error text); 1..4096 streams.  CF_EINVAL for a bad option or count before any GPU work (ctx ==
+ * NULL: the arguments are still checked first, cf_op_last_error names the cause).  *out is written on success only. */
+int cf_scene_create(cf_ctx* ctx, int n_streams, const cf_scene_opts* opts, cf_scene** out);
+/* Waits for the object's last check, then frees it.  NULL: CF_OK. */
+int cf_scene_destroy(cf_scene* scn);
+/* The next check of `stream` (-1: of every stream) is FIRST; ordered behind the checks issued so far and before those issued later.
+ * CF_EINVAL for a stream outside -1 .. n_streams - 1. */
+int cf_scene_forget(cf_scene* scn, int stream);
+/* Checks the streams stream0 .. stream0 + B - 1 of scn with frames[b] (frame b is the current frame of stream stream0 + b) and, with trk
+ * not NULL, resets the tracks of the streams that are CUT.  Frames, formats, pitches, alignment, on_device and the h / w rules are those
+ * of cf_track_follow (h and w even, at most 8192; the frames are only read, host frames are copied up, never back); in addition h, w >=
+ * 8, so that every cell holds a pixel.  IT NEEDS NO FORWARD ON ctx, does not touch the rows ctx holds and does not change which rows the
+ * redaction, the blur, the chips or the annotation take.  A cf_scene owns its state, a stream and an event, like a cf_tracker: a check
+ * makes the context's stream wait for the event of the check before it and records a new one, and with trk does the same on the tracker's
+ * event, so a ring of contexts can share both objects in call order.  out [B][4] (may be NULL); out_on_device = 1: a device buffer,
+ * asynchronous on the context's stream, nothing is read on the host; 0: a host buffer, the call blocks.
+ * CF_EINVAL, before any GPU work, for: a stream range outside scn or trk, B outside 1..max_batch, an object of another device, and every
+ * geometry and plane error of the follower (ctx == NULL: the geometry is still checked first, cf_op_last_error names the cause). */
+int cf_scene_check(cf_ctx* ctx, cf_scene* scn, cf_tracker* trk, int stream0, int B, int format, const cf_planes_rw* frames,
+                   int on_device, int h, int w, int pitch0, int pitch1, int32_t* out, int out_on_device);
+
 /* ---- best-shot selection: each track's sharpest chip, kept on the device -----------------------------------------------------
  * cf_track_update / cf_track_follow give every face an identity, cf_align_faces_frame cuts a chip of every tracked row: a track that
  * lives 200 frames yields 200 chips.  A cf_bestshot table is offered the chips of each frame, scores them, and keeps PER TRACK ID the
@@ -1004,6 +1068,13 @@ int cf_op_follow(int device, const cf_track_opts* opts, const cf_follow_opts* fo
                  const float* boxes, const float* scores, const float* lms_in, const int32_t* counts_in, const uint8_t* detect,
                  int format, const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h, int space_w, int tiled,
                  float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, int32_t* moves);
+/* The kernels of cf_scene_check over a whole sequence of host frames, with a fresh cf_scene of n_streams streams and no tracker: frame
+ * f of stream s is frames[f * S + s] (F * S host frames of h x w in `format`, pitches as cf_redact_faces; only read).  out [F][S][4] =
+ * code, hist, grid, run of every check; sigs [F][S][128] (or NULL) = the signature of every frame.  The option and count checks of
+ * cf_scene_create, the geometry and plane checks of cf_scene_check, n_frames >= 1 and at most 2^24 frames, before any device is touched;
+ * nothing is written on refusal. */
+int cf_op_scene(int device, const cf_scene_opts* opts, int n_streams, int n_frames, int format, const cf_planes_rw* frames, int h, int w,
+                int pitch0, int pitch1, int32_t* out, int32_t* sigs);
 /* The scoring kernel of cf_bestshot_offer alone, on host tables: chips [n][S][S][3] uint8, boxes [n][4], scores [n], lms [n][10]
  * (n in 1..65536; every row counts and is eligible) -> quality [n] int64, parts [n][4] int32 = sharp, size_w, pose_w, score_w.  fx, fy
  * finite and > 0.  Every bad argument is CF_EINVAL with a cf_op_last_error that names it, before any device is touched. */

@@ -52,6 +52,7 @@ EXPORTS = (
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_follow", "cf_op_follow",
+    "cf_scene_create", "cf_scene_destroy", "cf_scene_forget", "cf_scene_check", "cf_op_scene",
     "cf_bestshot_create", "cf_bestshot_destroy", "cf_bestshot_offer", "cf_bestshot_collect", "cf_op_chip_quality", "cf_op_bestshot",
 )
 
@@ -230,6 +231,20 @@ class FollowOpts(C.Structure):
 def follow_opts(search=4, max_sad=4096):
     """FollowOpts (the library validates the numbers).  The defaults are this project's choices; no accuracy claim is made for them."""
     return FollowOpts(int(search), int(max_sad))
+
+
+CF_SCENE_FIRST, CF_SCENE_SAME, CF_SCENE_CUT = 0, 1, 2
+
+
+class SceneOpts(C.Structure):
+    """cf_scene_opts: the per mille of pixels that must change histogram bin / the sum of cell-mean differences, both needed for a cut."""
+    _fields_ = [("hist_thresh", C.c_int32), ("grid_thresh", C.c_int32)]
+
+
+def scene_opts(hist=350, grid=640):
+    """SceneOpts (the library validates the numbers).  The defaults are this project's choices: there is no labelled video here, nobody
+    has measured them, and no accuracy claim is made for them."""
+    return SceneOpts(int(hist), int(grid))
 
 
 CF_BEST_SIZE, CF_BEST_POSE, CF_BEST_SCORE = 1, 2, 4
@@ -498,6 +513,11 @@ def lib():
             [C.c_void_p] * 5 + [C.c_int]
         L.cf_op_follow.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(FollowOpts)] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.POINTER(PlanesRW)] + \
             [C.c_int] * 7 + [C.c_void_p] * 6
+        L.cf_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(SceneOpts), C.POINTER(C.c_void_p)]
+        L.cf_scene_destroy.argtypes = [C.c_void_p]
+        L.cf_scene_forget.argtypes = [C.c_void_p, C.c_int]
+        L.cf_scene_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_int]
+        L.cf_op_scene.argtypes = [C.c_int, C.POINTER(SceneOpts), C.c_int, C.c_int, C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 4 + [C.c_void_p] * 2
         L.cf_bestshot_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(BestShotOpts), C.POINTER(C.c_void_p)]
         L.cf_bestshot_destroy.argtypes = [C.c_void_p]
         L.cf_bestshot_offer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int]

@@ -549,6 +549,31 @@ class Engine(object):
         self._chk(self._L.cf_track_follow(self._h, tracker._handle(self), int(stream0), B, C.byref(o), f, tab, dev, h, w, pitch0, pitch1,
                                           vp(dets_ptr), vp(lms_ptr), vp(info_ptr), vp(counts_ptr), vp(moves_ptr), 1))
 
+    # -- scene cuts --------------------------------------------------------------------------------
+    def scene_check(self, frames, fmt, scenes, tracker=None, stream0=0, *, codes=True):
+        """Does frame b continue stream ``stream0 + b`` of ``scenes`` (a ``SceneCuts``)?  (``cf_scene_check``, host form; the statement is
+        in ``include/centerface_hip.h``.)  Host frames as ``redact_faces`` takes them, only read, of an even size of at least 8 x 8; no
+        forward is needed and the rows this engine holds stay as they are.  With ``tracker`` the tracks of every stream that is CUT are
+        freed on the device, as ``Tracker.reset`` frees them: CALL IT BEFORE the frame's ``track_update`` or ``track_follow``.  Returns
+        int32 [B, 4] = code (``_lib.CF_SCENE_FIRST`` / ``_SAME`` / ``_CUT``), hist (per mille of pixels that changed luma bin), grid (sum
+        of the 64 cell-mean differences), run (SAME checks in a row) and blocks; ``codes=False`` reads nothing back and returns None.
+        A flash is reported as a cut, a dissolve is not one cut; the thresholds are this project's choices, no accuracy claim is made."""
+        args, keep = _lib.host_frame_args(frames, fmt, writable=False)
+        f, tab, dev, B, h, w, pitch0, pitch1 = args
+        out = np.zeros((B, 4), np.int32) if codes else None
+        self._chk(self._L.cf_scene_check(self._h, scenes._handle(self), tracker._handle(self) if tracker is not None else None, int(stream0), B, f, tab,
+                                         dev, h, w, pitch0, pitch1, _lib.ptr(out), 0))
+        del keep
+        return out
+
+    def scene_check_device(self, plane_ptrs, fmt, B, h, w, pitch0, pitch1, scenes, tracker=None, stream0=0, out_ptr=None):
+        """Same, reading DEVICE planes in place as ``redact_faces_device`` takes them and writing the caller-owned DEVICE buffer ``out_ptr``
+        (int32 [B, 4], or None): asynchronous on the engine's main stream behind the last check of ``scenes`` and the last update, follow
+        or reset of ``tracker``; nothing is read on the host -- the cut is decided and the tracks are freed by the kernel."""
+        f, tab, dev, B, h, w, pitch0, pitch1 = _lib.device_frame_args("scene_check_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1)
+        self._chk(self._L.cf_scene_check(self._h, scenes._handle(self), tracker._handle(self) if tracker is not None else None, int(stream0), B, f, tab,
+                                         dev, h, w, pitch0, pitch1, C.c_void_p(int(out_ptr)) if out_ptr else None, 1))
+
     # -- best-shot selection: each track's sharpest chip ---------------------------------------------
     def bestshot_offer(self, shots, chips, offsets, hw, stream0=0):
         """Offer ``shots`` (a ``BestShots``) the chips of this frame (``cf_bestshot_offer``, host form): ``chips`` uint8 [N, size, size, 3]
@@ -773,6 +798,60 @@ class Tracker(object):
     def close(self):
         if getattr(self, "_h", None):
             self._L.cf_track_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SceneCuts(object):
+    """One cf_scene: the last frame signature of ``streams`` independent video streams on one GPU (``include/centerface_hip.h`` states the
+    signature and the check).  ``engine_or_device``: an ``Engine`` (created at once on its GPU) or a device index (created by the first
+    ``Engine.scene_check`` that uses it, which must be on that GPU).  A frame is a CUT when at least ``hist`` per mille of its pixels
+    changed luma bin AND the 64 cell means moved by ``grid`` in sum.  A full-frame flash is reported as a cut (the cost: held tracks are
+    lost); a dissolve is not one cut.  The defaults are this project's choices: there is no labelled video here, nobody has measured
+    them, and no accuracy claim is made.  Engines of one GPU may share an object: its checks are ordered in call order."""
+
+    def __init__(self, engine_or_device, streams, hist=350, grid=640):
+        self._L = _lib.lib()
+        self._o = _lib.scene_opts(hist, grid)
+        self.streams = int(streams)
+        self._h = None
+        if isinstance(engine_or_device, Engine):
+            self.device = engine_or_device.device
+            self._handle(engine_or_device)
+        else:
+            self.device = int(engine_or_device)
+            # refuse bad options now, not at the first check (no context: the library checks the arguments and tells)
+            out = C.c_void_p()
+            self._L.cf_scene_create(None, self.streams, C.byref(self._o), C.byref(out))
+            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
+            if "null context" not in why:
+                raise _lib.CenterFaceValueError(-1, why)
+
+    def _handle(self, engine):
+        """The cf_scene, created with ``engine``'s context on first use."""
+        if self._h is None:
+            if engine.device != self.device:
+                raise ValueError("the scene object was made for device %d, the engine runs on device %d" % (self.device, engine.device))
+            out = C.c_void_p()
+            _lib.check(self._L.cf_scene_create(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
+            self._h = out
+        return self._h
+
+    def forget(self, stream=-1):
+        """The next check of ``stream`` (-1: of every stream) is FIRST: a new video begins there."""
+        if not -1 <= int(stream) < self.streams:
+            raise ValueError("stream %d of a scene object with %d" % (stream, self.streams))
+        if self._h is not None:
+            _lib.check(self._L.cf_scene_forget(self._h, int(stream)), op=True)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.cf_scene_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -1083,7 +1162,16 @@ class CenterFace(object):
             out.append((d, l) if self.landmarks else d)
         return out
 
-    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None, follow=None, detect=True, best=None):
+    def _scene(self, scenes, tracker, frames, fmt):
+        """The ``scenes`` argument of the product paths -> the ``scene`` of ``_drive``: None, or (scenes, frames, fmt).  Needs a tracker."""
+        if scenes is None:
+            return None
+        if tracker is None:
+            raise ValueError("scenes= needs tracker=")
+        return scenes, frames, fmt
+
+    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None, follow=None, detect=True, best=None,
+               scene=None):
         """The chunk loop of every product path: ``forward`` enqueues ``frames`` in slices of ``per`` (default ``max_batch``), each is
         decoded, and while the engine still holds it the steps that were asked for run in this order: ``tracker`` is advanced -- image b
         of the chunk that starts at frame i continues its stream i + b --, ``cover`` = (array, fmt, options) has the chunk's slice of
@@ -1096,22 +1184,37 @@ class CenterFace(object):
         switched off again whatever happens.  ``best`` = (shots, array, fmt, template, flush, sink): behind the update and the follow the
         chips of the tracked rows are cut from the chunk's slice of the array (``Engine.align_faces_frame`` at ``shots.size``) and offered
         to ``shots`` (``Engine.bestshot_offer``); after the loop ONE ``Engine.bestshot_collect`` over the call's streams (``flush``) is
-        appended to ``sink``.  Returns the per-frame results."""
+        appended to ``sink``.  ``scene`` = (scenes, array, fmt): per chunk, before anything else, the chunk's slice of the array is checked
+        for scene cuts (``Engine.scene_check`` with the tracker, stream i + b), which frees the tracks of the cut streams on the device.
+        With ``detect=True`` no code is read on the host.  With ``detect=False`` the codes are read (B x 4 ints per chunk), and a chunk in
+        which any frame is FIRST or CUT becomes a key frame: forward, decode (merge), update, then the follow it would have had -- the new
+        scene's faces are detected and covered in that same frame; its results are still the followed rows.  Returns the per-frame
+        results."""
         eng, out = self.engine, []
         per = per or eng.max_batch
         if merge is None and detect:
             eng.set_rescale(self.scale_h, self.scale_w)                      # centerface.py:55-62 inside the decode kernel
         try:
             for i in range(0, len(frames), per):
-                if detect:
-                    forward(frames[i:i + per])
-                    if merge is None:
-                        res = self._decode(eng)
-                    else:
-                        eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
-                        res = self._postprocess_many(eng.merge_tiles(*merge, self.max_dets)[0], rescaled=True)
-                    if tracker is not None:
-                        eng.track_update_device(tracker, i)
+                key = detect
+                if scene is not None:
+                    codes = eng.scene_check(scene[1][i:i + per], scene[2], scene[0], tracker, i, codes=not detect)
+                    key = detect or bool((codes[:, 0] != _lib.CF_SCENE_SAME).any())
+                if key:
+                    if merge is None and not detect:
+                        eng.set_rescale(self.scale_h, self.scale_w)
+                    try:
+                        forward(frames[i:i + per])
+                        if merge is None:
+                            res = self._decode(eng)
+                        else:
+                            eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
+                            res = self._postprocess_many(eng.merge_tiles(*merge, self.max_dets)[0], rescaled=True)
+                        if tracker is not None:
+                            eng.track_update_device(tracker, i)
+                    finally:
+                        if merge is None and not detect:
+                            eng.set_rescale(0.0, 0.0)
                 if follow is not None:
                     part = follow[0][i:i + per]
                     d, l, _, n, _ = eng.track_follow(part, follow[1], tracker, i, **follow[2])
@@ -1182,7 +1285,7 @@ class CenterFace(object):
         return lambda chunk: self.engine.forward_tiles_enqueue(chunk, rects, fmt), per
 
     def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None,
-                     tracker=None, follow=None, detect=True):
+                     tracker=None, follow=None, detect=True, scenes=None):
         """Sliced inference for frames much larger than the network input, whose small faces the stretch-resize of ``detect_batch``
         loses: every frame is cut on the device into overlapping tiles of ``tile`` (default: the network's (H, W)) that share at
         least ``overlap`` pixels (default: a quarter of the tile, rounded down to even), plus the whole frame as one more tile; the
@@ -1194,14 +1297,16 @@ class CenterFace(object):
         ``Engine.blur_faces``; the frames are then redacted IN PLACE with the merged boxes.  ``tracker``: a ``Tracker`` whose
         stream k the k-th frame of this call continues (frame pixels): it is advanced behind the merge, and the redaction then covers
         the tracked rows -- the merged detections plus the tracks held through a dropout; the detections returned stay the frame's
-        own.  ``follow`` and ``detect``: as ``anonymize`` (``redact=`` only; the frames are followed as they are before the redaction)."""
+        own.  ``follow``, ``detect`` and ``scenes``: as ``anonymize`` (``redact=`` only; the frames are checked and followed as they are before the
+        redaction)."""
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         return self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, with_full, redact is not None), merge=(metric, thresh, edge),
                            tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
-                           follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect)
+                           follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
+                           scene=self._scene(scenes, tracker, frames, fmt))
 
-    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, **options):
+    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, scenes=None, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
         cell, scale, fill) or, with ``mode='blur'``, blurred (``Engine.blur_faces``; shape, radius, scale), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
@@ -1215,30 +1320,36 @@ class CenterFace(object):
         moves with its face instead of staying where it was last detected.  ``detect=False`` (needs ``tracker``, which a call with
         detection has advanced before): NO FORWARD -- the faces are only followed from where the tracker has them, then covered; the
         results are then the tracked rows (held ones included) mapped to frame pixels in float64, not floored.  Detecting every Nth
-        frame and following in between is the throughput lever for video.  With the defaults every call does what it did without them."""
+        frame and following in between is the throughput lever for video.  ``scenes`` (needs ``tracker``): a ``SceneCuts`` whose stream k the
+        k-th image continues; every chunk is first checked for scene cuts on the device (``Engine.scene_check``) and the tracks of a cut
+        stream are freed there, so nothing of the previous scene is held, followed or covered.  With ``detect=False`` a chunk in which a
+        frame is a stream's first or a cut is detected after all (forward, decode, update, then the follow): ``detect=False`` then means
+        "detect only where a scene starts".  A flash counts as a cut, a dissolve is not one; the thresholds are this project's choices, no
+        accuracy claim is made.  With the defaults every call does what it did without them."""
         _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         if tiled:
-            return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker, follow=follow, detect=detect)
+            return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
         return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, cover=(out, "bgr", options),
-                                follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect)
+                                follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"))
 
-    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, **options):
+    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, scenes=None,
+                      **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
-        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow`` and
-        ``detect``: as ``anonymize``."""
+        [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow``,
+        ``detect`` and ``scenes``: as ``anonymize``."""
         _lib.split_redact_options(options)
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            return out, self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker, follow=follow, detect=detect)
+            return out, self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
         frames, forward = self._input_form(self.engine, frames, fmt)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
         return out, self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options),
-                                follow=self._follow(follow, detect, tracker, out, fmt), detect=detect)
+                                follow=self._follow(follow, detect, tracker, out, fmt), detect=detect, scene=self._scene(scenes, tracker, out, fmt))
 
     def best_shots(self, frames, fmt="bgr", *, tracker, shots, tiled=False, tile=None, overlap=None, follow=None, detect=True, flush=False,
-                   template=None):
+                   template=None, scenes=None):
         """One chip per appearance of a person: detection, tracking and best-shot selection of ``frames`` -- BGR uint8 [B,h,w,3]
         (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] -- where image k of a call is the next frame of stream k of ``tracker`` (a
         ``Tracker``) and of ``shots`` (a ``BestShots``), as in ``anonymize(tracker=)``: a video is fed one call per frame, n cameras n
@@ -1248,7 +1359,7 @@ class CenterFace(object):
         after the last chunk the finished entries of the call's streams are collected -- ``flush=True`` finishes every live track first
         (the end of the video).  Returns, per stream, the list of finished shots in finishing order: dicts with ``id``, ``quality``,
         ``chip`` [size, size, 3], ``det`` [5], ``lms`` [10] (the row of the best frame, in the tracker's space) and ``record`` (the eight
-        int32 of ``Engine.bestshot_collect``).  The quality formula is this project's choice; no accuracy claim is made for it."""
+        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  The quality formula is this project's choice; no accuracy claim is made for it."""
         if not self.landmarks:
             raise ValueError("best_shots needs the landmarks: construct CenterFace(..., landmarks=True)")
         if tracker is None or shots is None:
@@ -1260,15 +1371,16 @@ class CenterFace(object):
         eng, sink = self.engine, []
         best = (shots, frames, fmt, template, bool(flush), sink)
         fol = self._follow(follow, detect, tracker, frames, fmt)
+        scn = self._scene(scenes, tracker, frames, fmt)
         if tiled:
             self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, True, False), merge=("ios", 0.5, 2.0), tracker=tracker, follow=fol,
-                        detect=detect, best=best)
+                        detect=detect, best=best, scene=scn)
         else:
             want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
             if frames.shape[1:] != want:
                 raise ValueError("frames must be %s per frame (this instance was built for %dx%d), got %s" % ((want,) + self.src_hw + (frames.shape[1:],)))
             self._drive(frames, eng.forward_resized_enqueue if bgr else lambda chunk: eng.forward_yuv_enqueue(chunk, fmt), tracker=tracker, follow=fol,
-                        detect=detect, best=best)
+                        detect=detect, best=best, scene=scn)
         if not sink:
             return []
         chips, quality, records, dets, lms, counts = sink[0][:6]
@@ -1289,31 +1401,34 @@ class CenterFace(object):
         _lib.draw_opts(**o)                                                   # refuse bad names and colours before any work
         return o
 
-    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, **options):
+    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, scenes=None, **options):
         """``detect_batch`` plus the drawing of every detection, what demo.py:15-23 does with cv2 on the host: (frames_out, [(dets, lms),
         ...]) -- frames_out a uint8 [B,h,w,3] COPY of ``imgs`` with box outlines, landmark dots and a label painted on the device
         (``Engine.draw_faces``; ``options`` as there, colours as BGR triples).  ``tiled``, ``tile``, ``overlap`` and ``tracker`` as
         ``anonymize``: with a tracker the label is the track id and the tracks held through a dropout are drawn too, dashed, in
-        ``held_color``.  ``follow`` and ``detect``: as ``anonymize``."""
+        ``held_color``.  ``follow``, ``detect`` and ``scenes``: as ``anonymize``."""
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         draw = (out, "bgr", self._draw_options(options, tracker, False))
-        fo = dict(follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect)
+        fo = dict(follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"))
         if tiled:
             return out, self._drive(out, *self._tiled_form(out, "bgr", tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker, draw=draw, **fo)
         return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, draw=draw, **fo)
 
-    def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, **options):
+    def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, scenes=None,
+                     **options):
         """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
-        in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``."""
+        in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``scenes``: as ``anonymize``."""
         o = self._draw_options(options, tracker, True)
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
             return out, self._drive(out, *self._tiled_form(out, fmt, tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker,
-                                    draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect)
+                                    draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
+                                    scene=self._scene(scenes, tracker, out, fmt))
         frames, forward = self._input_form(self.engine, frames, fmt)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
-        return out, self._drive(frames, forward, tracker=tracker, draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect)
+        return out, self._drive(frames, forward, tracker=tracker, draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
+                                scene=self._scene(scenes, tracker, out, fmt))
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]

@@ -513,6 +513,27 @@ struct FollowParams {
 const char* follow_check(const cf_follow_opts* o, int format, int B, int h, int w, int pitch0, int pitch1);
 hipError_t launch_track_follow(hipStream_t s, const FollowParams& p);
 
+// Scene cuts (cf_scene.hip; the statement is in include/centerface_hip.h): the signature of g.B frames, the check of the streams
+// stream0 .. stream0 + g.B - 1 against their last signature and, on CUT with `meta`, the reset of the stream's track slots.
+constexpr int kSceneSig = 128, kScenePart = 72, kSceneRows = 16;      // int32 of a signature / of a workgroup's partials; rows of a workgroup
+struct SceneParams {
+    FrameGeo g;                  // pitch0 a multiple of 4; only plane 0 (BGR rows or the Y plane) is read
+    const void* const* planes;   // HOST table of g.B x {p0, p1, p2} DEVICE addresses (cf_frame.h), p0 4-byte aligned
+    int hist_thresh, grid_thresh, stream0;
+    // state (device), owned by the scene object
+    int* sig;                    // [S][128]: bins, cell means
+    int* st;                     // [S][4]: h, w, valid, run
+    // the tracker's TrackParams::meta (max_tracks slots per stream), or nullptr: nothing is reset
+    int* meta; int max_tracks;
+    int* part;                   // scratch, scene_part_bytes(g.B, g.h)
+    int* out;                    // [g.B][4] (device): code, hist, grid, run
+    int* sig_out;                // [g.B][128] (device) or nullptr: the frames' signatures
+};
+// nullptr, or what is wrong with the options / geometry (host only; no device is touched)
+const char* scene_check(const cf_scene_opts* o, int format, int B, int h, int w, int pitch0, int pitch1);
+size_t scene_part_bytes(int B, int h);
+hipError_t launch_scene_check(hipStream_t s, const SceneParams& p);
+
 // Best-shot selection (cf_bestshot.hip; the statement is in include/centerface_hip.h).  The table's device state, per stream and entry:
 // erec kBestRecInts int32 (state, id, best_t, first_t, last_t, n_offered, done_seq, parts[4], -, Q as int64, -, -), erow kBestRowFloats
 // float32 (det[5], lms[10], -), the chip; per stream smeta kBestStreamInts int32 (t, seq, sticky flags, -).  All zero at first.

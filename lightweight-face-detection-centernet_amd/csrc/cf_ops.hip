@@ -1058,6 +1058,40 @@ int cf_op_follow(int device, const cf_track_opts* o, const cf_follow_opts* fo, i
     return op_track_sequence("cf_op_follow", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, &fw);
 }
 
+// The kernels of cf_scene_check over a sequence of host frames, with the state of a fresh cf_scene (nothing valid) and no tracker.
+int cf_op_scene(int device, const cf_scene_opts* o, int n_streams, int n_frames, int format, const cf_planes_rw* frames, int h, int w, int pitch0,
+                int pitch1, int32_t* out, int32_t* sigs) {
+    const void* const* host_planes = reinterpret_cast<const void* const*>(frames);
+    const char* bad = !o ? "null options" : nullptr;
+    if (!bad && (n_streams < 1 || n_streams > kTrackMaxStreams)) bad = "n_streams must be in 1..4096";
+    if (!bad && n_frames < 1) bad = "n_frames must be at least 1";
+    if (!bad) bad = scene_check(o, format, n_streams, h, w, pitch0, pitch1);
+    if (!bad && (long long)n_frames * n_streams > (1 << 24)) bad = "more than 2^24 frames";
+    if (!bad) bad = redact_check_planes(format, host_planes, n_frames * n_streams, 0, pitch0, pitch1);
+    if (!bad && !out) bad = "null out";
+    if (bad) { g_op_error = std::string("cf_op_scene: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    const size_t S = n_streams, F = n_frames;
+    SceneParams p{};
+    p.hist_thresh = o->hist_thresh; p.grid_thresh = o->grid_thresh; p.stream0 = 0;
+    p.sig = (int*)sc.alloc(S * kSceneSig * sizeof(int)); p.st = (int*)sc.alloc(S * 4 * sizeof(int));
+    p.part = (int*)sc.alloc(scene_part_bytes(n_streams, h));
+    int* out_dev = (int*)sc.alloc(F * S * 4 * sizeof(int));
+    int* sig_dev = sigs ? (int*)sc.alloc(F * S * kSceneSig * sizeof(int)) : nullptr;
+    const RedactStage st = redact_stage_layout(format, h, w);
+    uint8_t* stage = (uint8_t*)sc.alloc(st.one * F * S);
+    const std::vector<const void*> dev = stage_table(st, stage, format, (int)(F * S));
+    p.g = FrameGeo{format, n_streams, h, w, st.pitch0, st.pitch1};
+    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, (int)(F * S), h, pitch0, pitch1, stage, true));
+    for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
+        p.planes = dev.data() + 3 * f * S; p.out = out_dev + f * S * 4; p.sig_out = sig_dev ? sig_dev + f * S * kSceneSig : nullptr;
+        sc.chk(launch_scene_check(sc.s, p));
+    }
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out, out_dev, F * S * 4 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess && sigs) sc.chk(hipMemcpyAsync(sigs, sig_dev, F * S * kSceneSig * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_scene");
+}
+
 // The score kernel of cf_bestshot_offer alone: one image whose n rows all count and are eligible (ids 1 .. n, hits 1000, misses 0).
 int cf_op_chip_quality(int device, const cf_bestshot_opts* o, const uint8_t* chips, const float* boxes, const float* scores, const float* lms,
                        int n, double fx, double fy, int64_t* quality, int32_t* parts) {

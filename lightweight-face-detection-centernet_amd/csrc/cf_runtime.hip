@@ -167,6 +167,7 @@ struct cf_ctx {
     // cf_track_follow: B > 0 = the rows in tk are the follow's, of B frames in the tracker's space (H x W network input, or -- tiled -- H x W
     // frames), and the newest whatever `stage` says; any forward, threshold decode, merge or update ends that (B = 0)
     struct { DevBuf slot_moves, moves; int B = 0, H = 0, W = 0; bool tiled = false; } fo;
+    struct { DevBuf part, out; } sn;                                    // cf_scene_check: the workgroups' partial sums, out [B][4] of a host-output call
     struct { DevBuf q, sc, jobs, flags, chips, off, out; } bs;          // cf_bestshot_offer / cf_bestshot_collect: per-call scratch and the staging of their host forms
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
     // input format, batch): the second forward with a key captures it, later ones replay it
@@ -666,7 +667,7 @@ int cf_destroy(cf_ctx* c) {
         if (p) hipFree(p);
     for (const DevBuf* b : {&c->src.buf, &c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->dr_recs, &c->tl_rects_dev,
                             &c->tl.cand, &c->tl.cand_count, &c->tl.order, &c->tl.mask, &c->tl.dets, &c->tl.lms, &c->tl.corners, &c->tl.counts, &c->tl.flags,
-                            &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags, &c->fo.slot_moves, &c->fo.moves,
+                            &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags, &c->fo.slot_moves, &c->fo.moves, &c->sn.part, &c->sn.out,
                             &c->bs.q, &c->bs.sc, &c->bs.jobs, &c->bs.flags, &c->bs.chips, &c->bs.off, &c->bs.out})
         if (b->p) hipFree(b->p);
     if (c->h_thr) hipHostFree(c->h_thr);
@@ -2197,6 +2198,114 @@ int cf_track_follow(cf_ctx* c, cf_tracker* t, int stream0, int B, const cf_follo
     }
     return read_out(c, B, M, p.out_counts, nullptr, counts, nullptr,
                     {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)}, {moves, p.moves, 4 * sizeof(int)}});
+}
+
+// ---- scene cuts (cf_scene.hip).  The object owns the state of its streams, one event that orders its checks across the contexts that
+// issue them, and a stream of its own for what no context carries (the initial state, cf_scene_forget).
+}  // extern "C"
+struct cf_scene {
+    int device = 0, S = 0;
+    cf_scene_opts o{};
+    int* sig = nullptr; int* st = nullptr;
+    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
+};
+static const char* scene_create_check(const cf_scene_opts* o, int n_streams) {
+    if (const char* why = scene_check(o, CF_FRAME_BGR, 1, 8, 8, 24, 0)) return why;      // the options alone
+    if (n_streams < 1 || n_streams > kTrackMaxStreams) return "n_streams must be in 1..4096";
+    return nullptr;
+}
+extern "C" {
+
+int cf_scene_destroy(cf_scene* t) {
+    if (!t) return CF_OK;
+    hipSetDevice(t->device);
+    if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
+    if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
+    for (void* p : {(void*)t->sig, (void*)t->st}) if (p) hipFree(p);
+    delete t;
+    return CF_OK;
+}
+
+int cf_scene_create(cf_ctx* c, int n_streams, const cf_scene_opts* o, cf_scene** out) {
+    const char* why = scene_create_check(o, n_streams);
+    if (!why && !out) why = "null out";
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_scene_create: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_scene_create: %s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    cf_scene* t = new cf_scene();
+    t->device = c->device; t->S = n_streams; t->o = *o;
+    const size_t nsig = (size_t)n_streams * kSceneSig * sizeof(int), nst = (size_t)n_streams * 4 * sizeof(int);
+    hipError_t e = hipStreamCreateWithFlags(&t->ts, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->sig, nsig);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->st, nst);
+    if (e == hipSuccess) e = hipMemsetAsync(t->sig, 0, nsig, t->ts);
+    if (e == hipSuccess) e = hipMemsetAsync(t->st, 0, nst, t->ts);
+    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        cf_scene_destroy(t);
+        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_scene_create: %d streams: %s", n_streams, hipGetErrorString(e));
+    }
+    *out = t;
+    return CF_OK;
+}
+
+int cf_scene_forget(cf_scene* t, int stream) {
+    if (!t || stream < -1 || stream >= t->S) { op_error_set("cf_scene_forget: null object, or a stream outside -1 .. n_streams - 1"); return CF_EINVAL; }
+    const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)t->S : 1;
+    hipError_t e = hipSetDevice(t->device);
+    if (e == hipSuccess) e = hipStreamWaitEvent(t->ts, t->ev, 0);
+    if (e == hipSuccess) e = hipMemsetAsync(t->st + first * 4, 0, n * 4 * sizeof(int), t->ts);
+    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
+    if (e != hipSuccess) { op_error_set((std::string("cf_scene_forget: ") + hipGetErrorString(e)).c_str()); return CF_EHIP; }
+    return CF_OK;
+}
+
+// The check of the streams stream0 .. stream0 + B - 1 in the caller's frames: ordered on the scene object's event and, with a tracker,
+// on the tracker's; it reads and writes the object's state and the tracker's meta words, and nothing of the rows the context holds.
+int cf_scene_check(cf_ctx* c, cf_scene* t, cf_tracker* trk, int stream0, int B, int format, const cf_planes_rw* frames, int on_device,
+                   int h, int w, int pitch0, int pitch1, int32_t* out, int out_on_device) {
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    const cf_scene_opts any{0, 0};                       // the options were checked when the object was made
+    const char* why = scene_check(t ? &t->o : &any, format, B, h, w, pitch0, pitch1);
+    if (!why) why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1);
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_scene_check: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_scene_check: %s", why);
+    if (!t) return c->fail(CF_EINVAL, "cf_scene_check: null scene object");
+    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_scene_check: the scene object lives on device %d, the context on device %d", t->device, c->device);
+    if (trk && trk->device != c->device) return c->fail(CF_EINVAL, "cf_scene_check: the tracker lives on device %d, the context on device %d", trk->device, c->device);
+    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_scene_check: B=%d exceeds max_batch %d", B, c->max_batch);
+    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_scene_check: streams %d .. %d of a scene object with %d", stream0, stream0 + B - 1, t->S);
+    if (trk && (long long)stream0 + B > trk->S) return c->fail(CF_EINVAL, "cf_scene_check: streams %d .. %d of a tracker with %d", stream0, stream0 + B - 1, trk->S);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t no = (size_t)B * 4 * sizeof(int);
+    if (int r = grow(c, c->sn.part, scene_part_bytes(B, h), "scene partial sums", "cf_scene_check")) return r;
+    if (int r = grow(c, c->sn.out, no, "scene codes", "cf_scene_check")) return r;
+    SceneParams p{};
+    p.hist_thresh = t->o.hist_thresh; p.grid_thresh = t->o.grid_thresh; p.stream0 = stream0; p.sig = t->sig; p.st = t->st;
+    p.meta = trk ? trk->meta : nullptr; p.max_tracks = trk ? trk->o.max_tracks : 0;
+    p.part = (int*)c->sn.part.p; p.out = out_on_device && out ? out : (int*)c->sn.out.p;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the check before this one, on whichever context's stream
+    if (trk) HIPCHK(c, hipStreamWaitEvent(c->stream, trk->ev, 0));       // and the tracker's last update, follow or reset
+    // host frames are only read: staged, not copied back
+    if (int r = on_frames(c, "cf_scene_check", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, on_device, false, [&](const void* const* pl, int p0, int p1) {
+            p.g = FrameGeo{format, B, h, w, p0, p1}; p.planes = pl;
+            hipError_t e = launch_scene_check(c->stream, p);
+            if (e == hipSuccess) e = hipEventRecord(t->ev, c->stream);
+            if (e == hipSuccess && trk) e = hipEventRecord(trk->ev, c->stream);
+            return e;
+        })) return r;
+    if (out_on_device || !out) return CF_OK;
+    HIPCHK(c, hipMemcpyAsync(out, p.out, no, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CF_OK;
 }
 
 // Best-shot selection (cf_bestshot.hip): the table's state lives in device memory the table owns and is advanced only by kernels, on the

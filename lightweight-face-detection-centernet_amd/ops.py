@@ -429,6 +429,32 @@ def follow_sequence(boxes, scores, lms, counts, frames, fmt="bgr", space_hw=None
     return od, ol, oi, oc, fl, om
 
 
+def scene_sequence(frames, fmt, streams, hist=350, grid=640, sigs=False, device=0):
+    """The scene check of ``Engine.scene_check`` over a whole sequence, with a fresh ``SceneCuts`` and no tracker (``cf_op_scene``): frame f
+    of stream s is ``frames[f * S + s]`` -- F * S host frames of one even size, at least 8 x 8, as ``redact_faces`` takes them (BGR uint8
+    [F*S,h,w,3], dense 4:2:0 uint8 [F*S, h*3//2, w], or per-frame plane tuples of pitched rows), only read.  Returns out int32 [F, S, 4] =
+    code (``_lib.CF_SCENE_*``), hist, grid, run of every check; with ``sigs`` also the signatures int32 [F, S, 128] (64 bins, 64 cell
+    means).  ``hist=350`` and ``grid=640`` are this project's choices; no accuracy claim is made for them."""
+    o = _lib.scene_opts(hist, grid)
+    S = int(streams)
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    if S < 1 or B % S:
+        raise ValueError("%d frames for %d streams" % (B, S))
+    F = B // S
+    out = np.zeros((F, S, 4), np.int32)
+    sg = np.zeros((F, S, 128), np.int32) if sigs else None
+    _lib.check(_lib.lib().cf_op_scene(device, C.byref(o), S, F, _lib.frame_format(fmt), tab, h, w, pitch0, pitch1, ptr(out), ptr(sg)), op=True)
+    del keep
+    return (out, sg) if sigs else out
+
+
+def scene_signature(frame, fmt, device=0):
+    """The 128 int32 of one frame's signature (``include/centerface_hip.h``: 64 luma bins, 8 x 8 cell means), computed on the device:
+    ``frame`` is one BGR uint8 [h,w,3], one dense 4:2:0 uint8 [h*3//2, w], or one plane tuple."""
+    one = np.ascontiguousarray(frame)[None] if isinstance(frame, np.ndarray) else [frame]
+    return scene_sequence(one, fmt, 1, sigs=True, device=device)[1][0, 0]
+
+
 def chip_quality(chips, boxes, scores, lms, fx=1.0, fy=1.0, *, min_hits=2, terms=("size", "pose", "score"), device=0):
     """The scoring kernel of the best-shot table alone (``cf_op_chip_quality``): chips uint8 [n, S, S, 3] BGR, their rows boxes [n, 4],
     scores [n], lms [n, 10] and the frame pixels per unit of the rows' space ``fx``, ``fy`` -> (quality int64 [n], parts int32 [n, 4] =

@@ -411,6 +411,61 @@ int cf_forward_tiles(cf_ctx* ctx, int format, const cf_yuv_planes* frames, int i
 int cf_merge_tiles(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags,
                    int out_on_device);
 
+/* ---- aspect-preserving (letterbox) input: fit frames on the device, map rows back ------------
+ * cf_forward_resized, cf_forward_yuv and the whole-frame tile of a tiled forward STRETCH a frame of another size to (H, W): a 1920 x 1080
+ * frame behind a 640 x 640 context reaches the network with every face squashed to 56 % of its width.  The reference's data pipeline
+ * fits the image with its aspect ratio kept and the border left black (dataset/dataset.py:114-134: s = max(h, w), get_affine_transform,
+ * cv2.warpAffine with the zero border), and its CenterFace(h, w) builds the network for the frame's size, so neither distorts.  Here
+ * the frame is resized with its aspect ratio kept, pasted into a filled (H, W) canvas, and the decode's rows are mapped back into frame
+ * pixels, all on the device:
+ *   cf_forward_fit -> cf_decode_threshold* (unchanged, per canvas) -> cf_unfit_rows [-> cf_track_update | cf_redact_faces | ...]
+ * No trained weights and no labelled set are on hand: no accuracy claim is made for cf_forward_fit; the argument is geometric.
+ *
+ * Geometry of an h x w frame in an H x W canvas (integers, 64-bit products):
+ *   upscale == 0 and h <= H and w <= W:   rw = w, rh = h
+ *   else w * H <= h * W (height-limited): rh = H, rw = max(1, (2 * w * H + h) / (2 * h))
+ *   else:                                 rw = W, rh = max(1, (2 * h * W + w) / (2 * w))
+ *   CF_FIT_CENTER: dx = (W - rw) / 2, dy = (H - rh) / 2;  CF_FIT_TOPLEFT: dx = dy = 0.
+ *   1080 x 1920 in 640 x 640: rw 640, rh 360, dy 140.  40 x 120 in 64 x 96: rw 96, rh 32, dy 16.  120 x 40 in 64 x 96: rh 64, rw 21, dx 37.
+ * Canvas: image b = fill everywhere, except canvas[dy : dy + rh, dx : dx + rw] = resize(bgr(frame b), (rh, rw)) with the conversion of
+ * cf_forward_yuv (the identity for CF_FRAME_BGR) and the resize of cf_forward_resized from (h, w) to (rh, rw): "resize, then pad".
+ * rw == w and rh == h reproduce the source bytes.  rw, rh, dx, dy may be odd. */
+#define CF_FIT_CENTER  0
+#define CF_FIT_TOPLEFT 1
+typedef struct cf_fit_opts {
+    int32_t anchor;              /* CF_FIT_CENTER | CF_FIT_TOPLEFT */
+    int32_t upscale;             /* 1: a frame smaller than the canvas is enlarged until one side fills it; 0: it keeps its size */
+    uint8_t fill[4];             /* B, G, R of the padding, unused */
+} cf_fit_opts;                   /* 12 bytes */
+typedef struct cf_fit_geom { int32_t rw, rh, dx, dy; } cf_fit_geom;
+/* The geometry above; host only.  CF_EINVAL (cf_op_last_error names the value) for NULL opts or g, an anchor or upscale outside {0, 1},
+ * h or w outside 2..8192, H or W below 1; *g is written on success only. */
+int cf_fit_geometry(const cf_fit_opts* opts, int h, int w, int H, int W, cf_fit_geom* g);
+/* B frames of h x w in `format` -> the network batch of B canvases as stated above -> forward.  Formats, planes, pitches, in_on_device
+ * and the alignment rule of device planes exactly as for cf_forward_tiles, except that BGR frames may have odd sides: sides 2..8192,
+ * even for 4:2:0.  The fit is one launch (per 64 frames); every tap lies inside the frame, pitch padding is never read; the frames are
+ * not modified.  CF_EINVAL before any GPU work, the offending value named in cf_last_error, for: NULL opts, frame table or required
+ * plane, an anchor or upscale outside {0, 1}, a bad format, side, pitch or alignment, B < 1 or B > max_batch (ctx == NULL: the arguments
+ * are still checked first, cf_op_last_error names the cause).  The context remembers the geometry and the frame size for cf_unfit_rows
+ * until any other forward or upload.  cf_get_resized_input returns the padded batch; cf_align_faces works per image on the padded
+ * batch; cf_merge_tiles behind it is CF_ESTATE (it is not a tiled forward). */
+int cf_forward_fit(cf_ctx* ctx, const cf_fit_opts* opts, int format, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w,
+                   int pitch0, int pitch1);
+/* Maps the rows the LAST THRESHOLD DECODE kept for the B images of the last cf_forward_fit back into frame pixels.  Per image the rows
+ * i < min(count, the decode's max_out), in keep order, in network coordinates whatever cf_set_rescale says:
+ *   * a row is dropped when a corner is not finite, or when its centre cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f (float32) lies
+ *     outside the content: it is kept iff dx <= cx < dx + rw and dy <= cy < dy + rh;
+ *   * the others are mapped, X = (float)(((double)x - (double)dx) * ((double)w / (double)rw)), Y likewise with dy and h / rh (the four
+ *     corners and the ten landmark values; float64 in this order, no contraction); the score is copied.  No clamping, no second NMS.
+ * The kept rows are compacted in order (a prefix sum: deterministic).  dets [B][max_out][5], lms [B][max_out][10] in frame pixels,
+ * counts [B] (may exceed max_out: only max_out rows are written), flags [B] (bit 0: the image had more rows than the decode's max_out).
+ * Any of the four may be NULL; out_on_device as for cf_merge_tiles.  The context's own frame-space rows are written in any case and the
+ * context is left in the state behind a merge: cf_track_update, cf_track_follow, cf_redact_faces, cf_blur_faces, cf_draw_faces,
+ * cf_align_faces_frame and the best-shot offer take them with B frames of (h, w), as after cf_merge_tiles; before cf_unfit_rows they
+ * return CF_ESTATE.  CF_EINVAL for max_out < 1 (ctx == NULL: checked first, cf_op_last_error names the cause); CF_ESTATE unless the
+ * last forward was cf_forward_fit with a threshold decode behind it. */
+int cf_unfit_rows(cf_ctx* ctx, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device);
+
 /* ---- face tracks across video frames: cover faces through detection dropouts -----------------
  * Every entry point above treats a frame as if it were the only one: the frame in which a face scores just under the threshold goes out
  * uncovered.  A cf_tracker associates the rows of each frame with the tracks of the frames before, on the device, and hands the
@@ -1046,6 +1101,19 @@ int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, in
 int cf_op_merge_tiles(int device, const cf_merge_opts* opts, const cf_tile_rect* rects, int T, int Bf, int h, int w, int H, int W,
                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
                       float* dets, float* lms, int32_t* out_counts, int32_t* flags);
+/* The fit kernel of cf_forward_fit alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up, so the
+ * padding bytes are on the device beside the pixels): canvas [B][H][W][3] uint8.  W % 4 == 0, B * H * W * 3 < 2^31.  The same
+ * validation, before any device is touched; nothing is written on refusal. */
+int cf_op_fit(int device, const cf_fit_opts* opts, int format, const cf_yuv_planes* host_frames, int B, int h, int w, int pitch0,
+              int pitch1, int H, int W, uint8_t* canvas);
+/* The mapper of cf_unfit_rows alone, on host tables, with the geometry of (opts, h, w, H, W): dets_net [B][rows][4], scores [B][rows],
+ * lms_net [B][rows][10], counts [B] -> dets [B][max_out][5], lms [B][max_out][10], out_counts [B], flags [B].  dets and lms are copied
+ * up first, so rows the kernel does not write come back as the caller filled them.  No pointer may be NULL; B, rows, max_out >= 1,
+ * B * max(rows, max_out) <= 2^24; the option and size checks of cf_fit_geometry, before any device is touched; nothing is written on
+ * refusal. */
+int cf_op_unfit(int device, const cf_fit_opts* opts, int B, int h, int w, int H, int W, const float* dets_net, const float* scores,
+                const float* lms_net, const int32_t* counts, int rows, int max_out, float* dets, float* lms, int32_t* out_counts,
+                int32_t* flags);
 /* The update kernel of cf_track_update over a whole sequence, on host tables, with a fresh tracker of n_streams streams: frame f of
  * stream s has the rows i < min(counts_in[f][s], rows) of boxes [F][S][rows][4], scores [F][S][rows], lms_in [F][S][rows][10] ->
  * dets [F][S][max_tracks][5], lms [F][S][max_tracks][10], info [F][S][max_tracks][3], counts [F][S], flags [F][S] after each frame.

@@ -36,6 +36,9 @@ DRAW_LABELS = {"none": CF_DRAW_LABEL_NONE, "score": CF_DRAW_LABEL_SCORE, "id": C
 CF_ENOMEM = -2
 CF_MERGE_IOU, CF_MERGE_IOS = 0, 1
 MERGE_METRICS = {"iou": CF_MERGE_IOU, "ios": CF_MERGE_IOS}
+# cf_forward_fit / cf_op_fit
+CF_FIT_CENTER, CF_FIT_TOPLEFT = 0, 1
+FIT_ANCHORS = {"center": CF_FIT_CENTER, "centre": CF_FIT_CENTER, "topleft": CF_FIT_TOPLEFT}
 YUV_FORMATS = {"nv12": CF_YUV_NV12, "nv21": CF_YUV_NV21, "i420": CF_YUV_I420, "yuv420p": CF_YUV_I420, "yv12": CF_YUV_YV12}
 
 # every symbol include/centerface_hip.h declares (checked by tests/test_abi.py)
@@ -50,6 +53,7 @@ EXPORTS = (
     "cf_blur_faces", "cf_op_blur",
     "cf_draw_faces", "cf_op_draw", "cf_draw_layout",
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
+    "cf_fit_geometry", "cf_forward_fit", "cf_unfit_rows", "cf_op_fit", "cf_op_unfit",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_follow", "cf_op_follow",
     "cf_scene_create", "cf_scene_destroy", "cf_scene_forget", "cf_scene_check", "cf_op_scene",
@@ -207,6 +211,29 @@ def merge_opts(metric="ios", thresh=0.5, edge=2.0):
             raise ValueError("unknown merge metric %r (one of %s)" % (metric, sorted(MERGE_METRICS)))
         metric = MERGE_METRICS[metric.lower()]
     return MergeOpts(int(metric), float(thresh), float(edge))
+
+
+class FitOpts(C.Structure):
+    """cf_fit_opts: where the content sits in the canvas / whether a small frame is enlarged / the B, G, R bytes of the padding."""
+    _fields_ = [("anchor", C.c_int32), ("upscale", C.c_int32), ("fill", C.c_uint8 * 4)]
+
+
+class FitGeom(C.Structure):
+    """cf_fit_geom: the content is rw x rh canvas pixels at (dx, dy)."""
+    _fields_ = [("rw", C.c_int32), ("rh", C.c_int32), ("dx", C.c_int32), ("dy", C.c_int32)]
+
+
+def fit_opts(anchor="center", upscale=True, fill=(0, 0, 0)):
+    """FitOpts from an anchor name ('center' | 'topleft'); integer codes pass through (the library validates them, like ``upscale``).
+    ``fill``: the three bytes B, G, R of the padding."""
+    if isinstance(anchor, str):
+        if anchor.lower() not in FIT_ANCHORS:
+            raise ValueError("unknown fit anchor %r (one of %s)" % (anchor, sorted(FIT_ANCHORS)))
+        anchor = FIT_ANCHORS[anchor.lower()]
+    fill = [int(v) for v in fill]
+    if len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
+        raise ValueError("fill must be three bytes B, G, R, got %r" % (fill,))
+    return FitOpts(int(anchor), int(upscale), (C.c_uint8 * 4)(*fill, 0))
 
 
 class TrackOpts(C.Structure):
@@ -504,6 +531,11 @@ def lib():
         L.cf_merge_tiles.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.cf_op_cut_tiles.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(TileRect)] + [C.c_int] * 3 + [C.c_void_p]
         L.cf_op_merge_tiles.argtypes = [C.c_int, C.POINTER(MergeOpts), C.POINTER(TileRect)] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
+        L.cf_fit_geometry.argtypes = [C.POINTER(FitOpts)] + [C.c_int] * 4 + [C.POINTER(FitGeom)]
+        L.cf_forward_fit.argtypes = [C.c_void_p, C.POINTER(FitOpts), C.c_int, C.c_void_p] + [C.c_int] * 6
+        L.cf_unfit_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.cf_op_fit.argtypes = [C.c_int, C.POINTER(FitOpts), C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+        L.cf_op_unfit.argtypes = [C.c_int, C.POINTER(FitOpts)] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
         L.cf_track_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(TrackOpts), C.POINTER(C.c_void_p)]
         L.cf_track_destroy.argtypes = [C.c_void_p]
         L.cf_track_reset.argtypes = [C.c_void_p, C.c_int]

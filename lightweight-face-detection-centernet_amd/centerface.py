@@ -489,6 +489,47 @@ class Engine(object):
         vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
         self._chk(self._L.cf_merge_tiles(self._h, C.byref(o), int(max_out), vp(dets_ptr), vp(lms_ptr), vp(counts_ptr), vp(flags_ptr), 1))
 
+    # -- aspect-preserving (letterbox) input -------------------------------------------------------
+    def forward_fit_enqueue(self, frames, fmt="bgr", *, anchor="center", upscale=True, fill=(0, 0, 0), on_device=False, h=None, w=None,
+                            pitch0=None, pitch1=None):
+        """Fit every frame into the network's (H, W) canvas with its aspect ratio kept -- resized to (rh, rw) = ``ops.fit_geometry``,
+        pasted at the centre (``anchor='topleft'``: at the origin), ``fill`` (B, G, R) around it -- and run the B canvases as one batch
+        (``cf_forward_fit``).  ``upscale=False`` leaves a frame that is smaller than the canvas at its size.  ``frames`` and the
+        ``on_device`` form as ``forward_tiles_enqueue`` takes them, except that BGR frames may have odd sides; they are only read.  A
+        ``decode_threshold`` then gives the rows in canvas coordinates and ``unfit_rows`` those in frame pixels.  No accuracy claim is
+        made for letterboxed input: the argument is geometric (the reference's data pipeline fits and pads, dataset/dataset.py:114-134)."""
+        f = _lib.frame_format(fmt)
+        o = _lib.fit_opts(anchor, upscale, fill)
+        if on_device:
+            if h is None or w is None:
+                raise ValueError("forward_fit_enqueue(on_device=True) needs h and w")
+            h, w = int(h), int(w)
+            tab, B = _lib.device_planes(frames), len(frames)
+            pitch0 = (3 * w if f == _lib.CF_FRAME_BGR else w) if pitch0 is None else int(pitch0)
+            pitch1 = (0 if f == _lib.CF_FRAME_BGR else _lib.yuv_dense_geometry(f, h, w)[1]) if pitch1 is None else int(pitch1)
+        else:
+            tab, B, h, w, pitch0, pitch1, self._last.keep = _lib.frame_planes(frames, fmt, writable=False)
+        self._chk(self._L.cf_forward_fit(self._h, C.byref(o), f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1))
+        self.last_B = B
+
+    def unfit_rows(self, max_out=1024):
+        """Per-frame detections of the last fitted forward in frame pixels (``cf_unfit_rows``, host form): the rows the preceding
+        ``decode_threshold`` kept -- in canvas coordinates, whatever ``set_rescale`` says -- whose corners are finite and whose centre
+        lies in the content, mapped back on the device, in the decode's order.  Returns (results, flags): a list of (dets [n,5], lms
+        [n,10]) per frame and int32 [B], bit 0 set where the decode was truncated by its ``max_out``.  Until the next forward or decode,
+        ``track_update``, ``redact_faces`` / ``blur_faces`` / ``draw_faces`` / ``align_faces_frame`` of this engine use these rows."""
+        B = self.last_B
+        flags = np.empty((B,), np.int32)
+        return self._rows(B, max_out, lambda cap, dets, lms, counts: self._L.cf_unfit_rows(
+            self._h, cap, _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts), _lib.ptr(flags), 0)), flags
+
+    def unfit_rows_device(self, max_out, dets_ptr=None, lms_ptr=None, counts_ptr=None, flags_ptr=None):
+        """Same, writing into caller-owned DEVICE buffers (dets [B,max_out,5], lms [B,max_out,10] float32, counts / flags [B] int32; any
+        may be None): asynchronous on the engine's main stream behind the decode, no count is read on the host.  The context keeps the
+        mapped rows either way."""
+        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
+        self._chk(self._L.cf_unfit_rows(self._h, int(max_out), vp(dets_ptr), vp(lms_ptr), vp(counts_ptr), vp(flags_ptr), 1))
+
     # -- face tracks across video frames -----------------------------------------------------------
     def track_update(self, tracker, stream0=0):
         """Advance ``tracker`` by one frame with the rows the preceding ``decode_threshold`` kept -- after ``forward_tiles_enqueue``, the
@@ -1180,7 +1221,8 @@ class CenterFace(object):
         the array right behind the update (``Engine.track_follow``), before anything is covered or drawn; with ``detect=False`` there is no
         forward, decode or update at all -- each chunk is followed, then covered or drawn, and its results are the followed rows
         (``_followed``).  ``merge`` = (metric, thresh, edge) says
-        that the forward is a tiled one: the tiles' rows are merged, in frame pixels; otherwise the decode rescales, and the rescale is
+        that the forward is a tiled one: the tiles' rows are merged, in frame pixels; ``merge='unfit'`` that it is a fitted one: the
+        rows are mapped back into frame pixels (``Engine.unfit_rows``); otherwise the decode rescales, and the rescale is
         switched off again whatever happens.  ``best`` = (shots, array, fmt, template, flush, sink): behind the update and the follow the
         chips of the tracked rows are cut from the chunk's slice of the array (``Engine.align_faces_frame`` at ``shots.size``) and offered
         to ``shots`` (``Engine.bestshot_offer``); after the loop ONE ``Engine.bestshot_collect`` over the call's streams (``flush``) is
@@ -1209,7 +1251,8 @@ class CenterFace(object):
                             res = self._decode(eng)
                         else:
                             eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
-                            res = self._postprocess_many(eng.merge_tiles(*merge, self.max_dets)[0], rescaled=True)
+                            rows = eng.unfit_rows(self.max_dets) if merge == "unfit" else eng.merge_tiles(*merge, self.max_dets)
+                            res = self._postprocess_many(rows[0], rescaled=True)
                         if tracker is not None:
                             eng.track_update_device(tracker, i)
                     finally:
@@ -1248,14 +1291,16 @@ class CenterFace(object):
             raise ValueError("detect_aligned needs the landmarks: construct CenterFace(..., landmarks=True)")
         return self._drive(*self._input_form(self.engine, imgs), chips=lambda i, j: self.engine.align_faces(size, **chip_options))
 
-    def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, **chip_options):
+    def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, fit=None, **chip_options):
         """Detection plus the aligned chip of every detection cut from the FRAME ITSELF (``Engine.align_faces_frame``), not from the
         network-sized batch: one (dets, lms, chips) per frame, dets / lms in frame pixels.  ``frames``: BGR uint8 [B,h,w,3]
         (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] ('nv12', 'nv21', 'i420', 'yv12') of the (height, width) this instance was
         built for; they go through ``forward_resized`` / ``forward_yuv`` and the results are those of ``detect_batch`` /
         ``detect_yuv`` (floor-divided to frame pixels).  ``tiled=True``: frames of any even size, detected by ``detect_tiled``'s path
         (``tile``, ``overlap``); the chips are those of the merged detections, which are in frame pixels and not floor-divided.
-        ``chip_options``: out, rgb, mean, scale, template."""
+        ``fit``: True, or a dict with anchor, upscale and / or fill: frames of any size, detected by ``detect_fit``'s path instead
+        (frame pixels, not floor-divided); not together with ``tiled``.  ``chip_options``: out, rgb, mean, scale, template."""
+        fit = self._fit_options(fit, tiled)
         if not self.landmarks:
             raise ValueError("detect_aligned_frames needs the landmarks: construct CenterFace(..., landmarks=True)")
         bgr = _lib.frame_format(fmt) == _lib.CF_FRAME_BGR
@@ -1264,8 +1309,9 @@ class CenterFace(object):
             raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (frames.shape,))
         eng = self.engine
         chips = lambda i, j: eng.align_faces_frame(frames[i:j], fmt, size, **chip_options)      # noqa: E731
-        if tiled:
-            return self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, True, False), merge=("ios", 0.5, 2.0), chips=chips)
+        if tiled or fit is not None:
+            forward, per, merge = self._frame_form(frames, fmt, tile, overlap, fit, False)
+            return self._drive(frames, forward, per, merge=merge, chips=chips)
         want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
         if frames.shape[1:] != want:
             raise ValueError("frames must be %s per frame (this instance was built for %dx%d), got %s" % ((want,) + self.src_hw + (frames.shape[1:],)))
@@ -1283,6 +1329,43 @@ class CenterFace(object):
         if per < 1:
             raise ValueError("%d tiles per frame need max_batch >= %d (this instance has %d)" % (len(rects), len(rects), self.engine.max_batch))
         return lambda chunk: self.engine.forward_tiles_enqueue(chunk, rects, fmt), per
+
+    def _fit_options(self, fit, tiled=False):
+        """The ``fit`` argument of the product paths -> None, or the options of ``Engine.forward_fit_enqueue``: ``fit`` None / False,
+        True (the defaults) or a dict with anchor, upscale and / or fill.  ``fit`` and ``tiled=True`` exclude each other."""
+        if fit is None or fit is False:
+            return None
+        if tiled:
+            raise ValueError("fit= and tiled=True exclude each other: a frame is either letterboxed or cut into tiles")
+        o = dict(fit) if isinstance(fit, dict) else {}
+        if set(o) - {"anchor", "upscale", "fill"}:
+            raise ValueError("fit takes anchor, upscale and fill, got %s" % sorted(o))
+        _lib.fit_opts(**o)                                                    # refuse bad names and bytes before any work
+        return o
+
+    def _frame_form(self, frames, fmt, tile, overlap, fit, writable):
+        """(forward, frames per chunk, merge) of the paths whose rows are in frame pixels: the fitted forward when ``fit`` (the options
+        of ``_fit_options``) is not None, else the tiled one with the default merge."""
+        if fit is not None:
+            return lambda chunk: self.engine.forward_fit_enqueue(chunk, fmt, **fit), None, "unfit"
+        return self._tiled_form(frames, fmt, tile, overlap, True, writable) + (("ios", 0.5, 2.0),)
+
+    def detect_fit(self, frames, fmt="bgr", *, anchor="center", upscale=True, fill=(0, 0, 0), redact=None, tracker=None, follow=None, detect=True,
+                   scenes=None):
+        """Detection of frames of another size -- or shape -- than the network input WITHOUT the stretch of ``detect_batch``: every frame
+        is resized on the device with its aspect ratio kept and pasted into the network's canvas (``Engine.forward_fit_enqueue``:
+        ``anchor``, ``upscale``, ``fill``), and the rows whose centre lies in the content are mapped back (``Engine.unfit_rows``).
+        ``frames``: BGR uint8 [B,h,w,3] (``fmt='bgr'``; odd sides allowed), dense 4:2:0 uint8 [B, h*3//2, w], or per-frame plane tuples.
+        Returns (dets [n,5], lms [n,10]) per frame (``dets`` alone without landmarks), in FRAME pixels, not floor-divided.  No accuracy
+        claim is made: there are no trained weights and no labelled set here; the reference's data pipeline fits and pads likewise
+        (dataset/dataset.py:114-134).  ``redact``, ``tracker``, ``follow``, ``detect`` and ``scenes``: as ``detect_tiled``."""
+        if redact is not None:
+            _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
+        fit = self._fit_options(dict(anchor=anchor, upscale=upscale, fill=fill))
+        forward, per, merge = self._frame_form(frames, fmt, None, None, fit, redact is not None)
+        return self._drive(frames, forward, per, merge=merge, tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
+                           follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
+                           scene=self._scene(scenes, tracker, frames, fmt))
 
     def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None,
                      tracker=None, follow=None, detect=True, scenes=None):
@@ -1306,7 +1389,7 @@ class CenterFace(object):
                            follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
                            scene=self._scene(scenes, tracker, frames, fmt))
 
-    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, scenes=None, **options):
+    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
         cell, scale, fill) or, with ``mode='blur'``, blurred (``Engine.blur_faces``; shape, radius, scale), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
@@ -1325,21 +1408,30 @@ class CenterFace(object):
         stream are freed there, so nothing of the previous scene is held, followed or covered.  With ``detect=False`` a chunk in which a
         frame is a stream's first or a cut is detected after all (forward, decode, update, then the follow): ``detect=False`` then means
         "detect only where a scene starts".  A flash counts as a cut, a dissolve is not one; the thresholds are this project's choices, no
-        accuracy claim is made.  With the defaults every call does what it did without them."""
+        accuracy claim is made.  ``fit``: True, or a dict with anchor, upscale and / or fill: detection by ``detect_fit`` on frames of
+        any size -- letterboxed instead of stretched --, redaction with the rows mapped back, which are in frame pixels; not together
+        with ``tiled``; no accuracy claim is made for it either.  With the defaults every call does what it did without them."""
         _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
+        fit = self._fit_options(fit, tiled)
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
+        if fit is not None:
+            return out, self.detect_fit(out, "bgr", **fit, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
         if tiled:
             return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
         return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, cover=(out, "bgr", options),
                                 follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"))
 
-    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, scenes=None,
-                      **options):
+    def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
+                      scenes=None, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
         [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow``,
-        ``detect`` and ``scenes``: as ``anonymize``."""
+        ``fit``, ``detect`` and ``scenes``: as ``anonymize``."""
         _lib.split_redact_options(options)
+        fit = self._fit_options(fit, tiled)
+        if fit is not None:                                             # frames of any even size: [B, h*3//2, w]
+            out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
+            return out, self.detect_fit(out, fmt, **fit, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
             return out, self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
@@ -1348,8 +1440,8 @@ class CenterFace(object):
         return out, self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options),
                                 follow=self._follow(follow, detect, tracker, out, fmt), detect=detect, scene=self._scene(scenes, tracker, out, fmt))
 
-    def best_shots(self, frames, fmt="bgr", *, tracker, shots, tiled=False, tile=None, overlap=None, follow=None, detect=True, flush=False,
-                   template=None, scenes=None):
+    def best_shots(self, frames, fmt="bgr", *, tracker, shots, tiled=False, tile=None, overlap=None, fit=None, follow=None, detect=True,
+                   flush=False, template=None, scenes=None):
         """One chip per appearance of a person: detection, tracking and best-shot selection of ``frames`` -- BGR uint8 [B,h,w,3]
         (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] -- where image k of a call is the next frame of stream k of ``tracker`` (a
         ``Tracker``) and of ``shots`` (a ``BestShots``), as in ``anonymize(tracker=)``: a video is fed one call per frame, n cameras n
@@ -1359,7 +1451,8 @@ class CenterFace(object):
         after the last chunk the finished entries of the call's streams are collected -- ``flush=True`` finishes every live track first
         (the end of the video).  Returns, per stream, the list of finished shots in finishing order: dicts with ``id``, ``quality``,
         ``chip`` [size, size, 3], ``det`` [5], ``lms`` [10] (the row of the best frame, in the tracker's space) and ``record`` (the eight
-        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  The quality formula is this project's choice; no accuracy claim is made for it."""
+        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  ``fit``: as ``anonymize`` (``detect_fit``'s path).  The quality formula is this project's choice; no accuracy claim is made for it."""
+        fit = self._fit_options(fit, tiled)
         if not self.landmarks:
             raise ValueError("best_shots needs the landmarks: construct CenterFace(..., landmarks=True)")
         if tracker is None or shots is None:
@@ -1372,9 +1465,9 @@ class CenterFace(object):
         best = (shots, frames, fmt, template, bool(flush), sink)
         fol = self._follow(follow, detect, tracker, frames, fmt)
         scn = self._scene(scenes, tracker, frames, fmt)
-        if tiled:
-            self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, True, False), merge=("ios", 0.5, 2.0), tracker=tracker, follow=fol,
-                        detect=detect, best=best, scene=scn)
+        if tiled or fit is not None:
+            forward, per, merge = self._frame_form(frames, fmt, tile, overlap, fit, False)
+            self._drive(frames, forward, per, merge=merge, tracker=tracker, follow=fol, detect=detect, best=best, scene=scn)
         else:
             want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
             if frames.shape[1:] != want:
@@ -1401,28 +1494,32 @@ class CenterFace(object):
         _lib.draw_opts(**o)                                                   # refuse bad names and colours before any work
         return o
 
-    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, scenes=None, **options):
+    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, **options):
         """``detect_batch`` plus the drawing of every detection, what demo.py:15-23 does with cv2 on the host: (frames_out, [(dets, lms),
         ...]) -- frames_out a uint8 [B,h,w,3] COPY of ``imgs`` with box outlines, landmark dots and a label painted on the device
         (``Engine.draw_faces``; ``options`` as there, colours as BGR triples).  ``tiled``, ``tile``, ``overlap`` and ``tracker`` as
         ``anonymize``: with a tracker the label is the track id and the tracks held through a dropout are drawn too, dashed, in
-        ``held_color``.  ``follow``, ``detect`` and ``scenes``: as ``anonymize``."""
+        ``held_color``.  ``fit``, ``follow``, ``detect`` and ``scenes``: as ``anonymize``."""
+        fit = self._fit_options(fit, tiled)
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         draw = (out, "bgr", self._draw_options(options, tracker, False))
         fo = dict(follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"))
-        if tiled:
-            return out, self._drive(out, *self._tiled_form(out, "bgr", tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker, draw=draw, **fo)
+        if tiled or fit is not None:
+            forward, per, merge = self._frame_form(out, "bgr", tile, overlap, fit, True)
+            return out, self._drive(out, forward, per, merge=merge, tracker=tracker, draw=draw, **fo)
         return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, draw=draw, **fo)
 
-    def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, tracker=None, follow=None, detect=True, scenes=None,
-                     **options):
+    def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
+                     scenes=None, **options):
         """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
-        in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``scenes``: as ``anonymize``."""
+        in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``fit`` and ``scenes``: as ``anonymize``."""
+        fit = self._fit_options(fit, tiled)
         o = self._draw_options(options, tracker, True)
-        if tiled:                                                       # frames of any even size: [B, h*3//2, w]
+        if tiled or fit is not None:                                    # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            return out, self._drive(out, *self._tiled_form(out, fmt, tile, overlap, True, True), merge=("ios", 0.5, 2.0), tracker=tracker,
+            forward, per, merge = self._frame_form(out, fmt, tile, overlap, fit, True)
+            return out, self._drive(out, forward, per, merge=merge, tracker=tracker,
                                     draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
                                     scene=self._scene(scenes, tracker, out, fmt))
         frames, forward = self._input_form(self.engine, frames, fmt)

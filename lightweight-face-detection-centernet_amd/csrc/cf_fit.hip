@@ -1,0 +1,231 @@
+// Aspect-preserving (letterbox) input: the fit of source frames into the network's canvas and the mapping of the decode's rows back
+// into frame pixels.
+//
+// GEOMETRY (fit_geometry; integers, 64-bit products).  An h x w frame in an H x W canvas keeps its size when upscale == 0 and it fits
+// (rw = w, rh = h); else, height-limited (w * H <= h * W): rh = H, rw = max(1, (2 * w * H + h) / (2 * h)); else rw = W,
+// rh = max(1, (2 * h * W + w) / (2 * w)).  CF_FIT_CENTER: dx = (W - rw) / 2, dy = (H - rh) / 2; CF_FIT_TOPLEFT: dx = dy = 0.
+//
+// FIT.  One launch writes the network's uint8 input batch [B][H][W][3] BGR from B full-resolution frames (BGR rows or 4:2:0 planes,
+// pitched, read in place):
+//   canvas_b[dy : dy + rh, dx : dx + rw] = resize(bgr(frame_b), (rh, rw)),   every other pixel = fill
+// with bgr() the fixed-point BT.601 conversion of cf_yuvmath.h (the identity for BGR frames) and resize the fixed-point INTER_LINEAR of
+// cf_cvresize.h from (h, w) to (rh, rw): "resize, then pad".  rw == w and rh == h give the coefficients 2048 / 0: the source bytes.
+// A lane owns four adjacent CANVAS columns -- each of them content or padding on its own, dx and dx + rw are no multiples of 4 -- whose
+// taps and coefficients are computed once and serve kFitRows canvas rows, each row going out as three dword stores (W % 4 == 0),
+// lane-contiguous.  Rows wholly in the padding, and lanes whose four columns are, are written as fill without touching the source; a
+// padding column beside content computes the edge column's taps and drops them.  The taps are byte loads; every tap lies inside the
+// frame, pitch padding is never read.
+//
+// UNFIT.  One workgroup per image walks the rows the threshold decode kept, i < min(count, rows), in keep order:
+//   * dropped when a corner is not finite, or when its centre cx = (x1 + x2) * 0.5f, cy likewise (float32) lies outside the content:
+//     kept iff dx <= cx < dx + rw and dy <= cy < dy + rh;
+//   * else X = (float)(((double)x - (double)dx) * ((double)w / (double)rw)), Y likewise with dy and h / rh, for the four corners and the
+//     ten landmark values (float64 in this order, no contraction: the file is built with -ffp-contract=off); the score is copied.
+// The compaction is a prefix sum, never an atomic: the order is the decode's.
+#include "cf_common.h"
+#include "cf_kernels.h"
+#include "cf_cvresize.h"
+#include "cf_yuvmath.h"
+#include <string>
+
+namespace cf {
+namespace {
+
+constexpr int kFitFrames = 64;                       // frames per launch: 3 x 64 pointers = 1.5 KB of kernel arguments
+// canvas rows per lane (one set of column coefficients).  The cutter's 8 left 16 frames of 1080p with 3 waves per SIMD, 44 % of them
+// storing fill only: 35 / 55 us (NV12 / BGR) against 23 / 32 us with 4; 2 and 1 measured the same as 4 (profiles/fit.md)
+constexpr int kFitRows = 4;
+using FitPtrs = FramePtrs<kFitFrames>;
+
+// SRC: 0 = BGR rows, 1 = one interleaved chroma plane (NV12 / NV21), 2 = two chroma planes (I420; YV12 on a swapped table);
+// VF: V first in the interleaved pairs (NV21).  One source pixel -> B | G << 8 | R << 16
+template <int SRC, bool VF>
+__device__ __forceinline__ uint32_t fit_tap(const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, int pitch0, int pitch1, int y, int x) {
+    if constexpr (SRC == 0) {
+        const uint8_t* q = p0 + (size_t)y * pitch0 + 3 * x;
+        return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+    } else {
+        return yuv_px(p0[(size_t)y * pitch0 + x], chroma_at<SRC == 1, VF>(p1, p2, pitch1, y >> 1, x >> 1));
+    }
+}
+
+// Three values 0..255 -> B | G << 8 | R << 16 by byte selection from whole dwords (two v_perm_b32).  Written as shifts and ORs, the
+// clamp of cv_linear_vpass next to the packing is selected as gfx950's v_ashr_pk_u8_i32, whose result came back from the device with
+// foreign bits above bit 15 in this kernel (they reach R and the next pixel's B); a byte selection takes bits 7:0 of each value and
+// nothing else.
+__device__ __forceinline__ uint32_t pack_bgr(uint32_t b, uint32_t g, uint32_t r) {
+    const uint32_t bg = __builtin_amdgcn_perm(g, b, 0x0c0c0400u);       // byte 0 = b[7:0], byte 1 = g[7:0], bytes 2, 3 = 0
+    return __builtin_amdgcn_perm(r, bg, 0x0c040100u);                   // bytes 0, 1 = bg[15:0], byte 2 = r[7:0], byte 3 = 0
+}
+
+__device__ __forceinline__ void fit_store(uint8_t* row, const uint32_t (&p)[4]) {
+    uint32_t* o = reinterpret_cast<uint32_t*>(row);
+    o[0] = p[0] | (p[1] << 24);
+    o[1] = (p[1] >> 8) | (p[2] << 16);
+    o[2] = (p[2] >> 16) | (p[3] << 8);
+}
+
+template <int SRC, bool VF>
+__global__ void __launch_bounds__(256) fit_frames_kernel(FitPtrs tab, uint8_t* dst, cf_fit_geom g, uint32_t fill, int h, int w, int pitch0,
+                                                         int pitch1, int H, int W) {
+    const int f = blockIdx.y;
+    const int gw = W >> 2, ng = (H + kFitRows - 1) / kFitRows;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ng * gw) return;
+    const int grp = i / gw, X0 = (i - grp * gw) << 2;
+    uint8_t* out = dst + ((size_t)f * H * W + X0) * 3;
+    const int Y0 = grp * kFitRows, Yend = min(H, Y0 + kFitRows);
+    const uint32_t pad[4] = {fill, fill, fill, fill};
+    bool in[4];
+    int x0[4], x1[4], a0[4], a1[4];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = X0 + k - g.dx;
+        in[k] = x >= 0 && x < g.rw;
+        cv_linear_coeffs(min(max(x, 0), g.rw - 1), w, g.rw, true, x0[k], x1[k], a0[k], a1[k]);      // a padding column beside content: the edge's taps, not used
+        any = any || in[k];
+    }
+    if (!any || Yend <= g.dy || Y0 >= g.dy + g.rh) {     // the lane's columns, or all of its rows, are padding: the source is not touched
+        for (int Y = Y0; Y < Yend; ++Y) fit_store(out + (size_t)Y * W * 3, pad);
+        return;
+    }
+    const uint8_t* p0 = tab.p0[f];
+    const uint8_t* p1 = tab.p1[f];
+    const uint8_t* p2 = tab.p2[f];
+    for (int Y = Y0; Y < Yend; ++Y) {
+        const int y = Y - g.dy;
+        if (y < 0 || y >= g.rh) { fit_store(out + (size_t)Y * W * 3, pad); continue; }
+        int y0, y1, b0, b1;
+        cv_linear_coeffs(y, h, g.rh, false, y0, y1, b0, b1);
+        uint32_t p[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t t00 = fit_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x0[k]);
+            const uint32_t t01 = fit_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x1[k]);
+            const uint32_t t10 = fit_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x0[k]);
+            const uint32_t t11 = fit_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x1[k]);
+            uint32_t ch[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int s = 8 * c;
+                const int h0 = (int)((t00 >> s) & 255) * a0[k] + (int)((t01 >> s) & 255) * a1[k];
+                const int h1 = (int)((t10 >> s) & 255) * a0[k] + (int)((t11 >> s) & 255) * a1[k];
+                ch[c] = (uint32_t)cv_linear_vpass(b0, b1, h0, h1);
+            }
+            p[k] = in[k] ? pack_bgr(ch[0], ch[1], ch[2]) : fill;
+        }
+        fit_store(out + (size_t)Y * W * 3, p);
+    }
+}
+
+// One workgroup per image walks its rows in order, 1024 at a time: keep flag, ballot, the 16 wave counts through LDS, write at
+// base + prefix (as merge_collect_kernel).
+__global__ void __launch_bounds__(1024) unfit_rows_kernel(UnfitParams p) {
+    __shared__ uint32_t wave_cnt[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int count = p.counts[b], n = min(max(count, 0), p.rows);
+    const float xlo = (float)p.g.dx, xhi = (float)(p.g.dx + p.g.rw), ylo = (float)p.g.dy, yhi = (float)(p.g.dy + p.g.rh);
+    const double sx = (double)p.w / (double)p.g.rw, sy = (double)p.h / (double)p.g.rh;
+    const double ox = (double)p.g.dx, oy = (double)p.g.dy;
+    uint32_t base = 0;
+    for (int j0 = 0; j0 < n; j0 += 1024) {               // (n is uniform over the workgroup: so is the trip count)
+        const int row = j0 + tid;
+        bool keep = false;
+        float c[4] = {0.f, 0.f, 0.f, 0.f};
+        const size_t src = (size_t)b * p.rows + row;
+        if (row < n) {
+            const float4 q = *reinterpret_cast<const float4*>(p.dets_net + src * 4);
+            c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w;
+            keep = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]);
+            const float cx = (c[0] + c[2]) * 0.5f, cy = (c[1] + c[3]) * 0.5f;
+            if (!(cx >= xlo && cx < xhi && cy >= ylo && cy < yhi)) keep = false;
+        }
+        const unsigned long long bal = __ballot(keep);
+        __syncthreads();                                                  // the counts of the round before have been read
+        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = 0, total = 0;
+        for (int w2 = 0; w2 < 16; ++w2) { if (w2 < wave) off += wave_cnt[w2]; total += wave_cnt[w2]; }
+        const uint32_t pos = base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (keep && pos < (uint32_t)p.max_out) {
+            const size_t d = (size_t)b * p.max_out + pos;
+            float o[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = (float)(((double)c[k] - ((k & 1) ? oy : ox)) * ((k & 1) ? sy : sx));
+            *reinterpret_cast<float4*>(p.corners + d * 4) = make_float4(o[0], o[1], o[2], o[3]);
+            float* dd = p.dets + d * 5;
+            dd[0] = o[0]; dd[1] = o[1]; dd[2] = o[2]; dd[3] = o[3];
+            dd[4] = p.scores[src * p.score_stride];
+            const float* l = p.lms_net + src * 10;
+            float* dl = p.lms + d * 10;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) dl[k] = (float)(((double)l[k] - ((k & 1) ? oy : ox)) * ((k & 1) ? sy : sx));
+        }
+        base += total;
+    }
+    if (tid == 0) { p.out_counts[b] = (int)base; p.flags[b] = count > p.rows ? 1 : 0; }
+}
+
+}  // namespace
+
+int fit_geometry(int anchor, int upscale, int h, int w, int H, int W, cf_fit_geom* g) {
+    if (!g || (anchor != CF_FIT_CENTER && anchor != CF_FIT_TOPLEFT) || (upscale != 0 && upscale != 1) || h < 1 || w < 1 || H < 1 || W < 1) return CF_EINVAL;
+    long long rw, rh;
+    if (!upscale && h <= H && w <= W) { rw = w; rh = h; }
+    else if ((long long)w * H <= (long long)h * W) { rh = H; rw = std::max(1LL, (2LL * w * H + h) / (2LL * h)); }
+    else { rw = W; rh = std::max(1LL, (2LL * h * W + w) / (2LL * w)); }
+    g->rw = (int)rw; g->rh = (int)rh;
+    g->dx = anchor == CF_FIT_CENTER ? (W - (int)rw) / 2 : 0;
+    g->dy = anchor == CF_FIT_CENTER ? (H - (int)rh) / 2 : 0;
+    return CF_OK;
+}
+
+const char* fit_check(std::string& why, const cf_fit_opts* o, int format, int B, int h, int w, int pitch0, int pitch1, int H, int W) {
+    char b[224];
+    auto say = [&](const char* s) { why = s; return why.c_str(); };
+    if (!o) return say("null options");
+    if (o->anchor != CF_FIT_CENTER && o->anchor != CF_FIT_TOPLEFT) { snprintf(b, sizeof b, "unknown anchor %d (0 = CF_FIT_CENTER, 1 = CF_FIT_TOPLEFT)", o->anchor); return say(b); }
+    if (o->upscale != 0 && o->upscale != 1) { snprintf(b, sizeof b, "upscale=%d must be 0 or 1", o->upscale); return say(b); }
+    if (H < 1 || W < 4 || (W & 3)) { snprintf(b, sizeof b, "H=%d, W=%d: W must be a multiple of 4 and H at least 1", H, W); return say(b); }
+    if (const char* geo = frame_geometry_check(FrameGeo{format, B, h, w, pitch0, pitch1}, 2, false)) {
+        snprintf(b, sizeof b, "%s (format=%d, B=%d, h=%d, w=%d, pitch0=%d, pitch1=%d)", geo, format, B, h, w, pitch0, pitch1);
+        return say(b);
+    }
+    return nullptr;
+}
+
+// planes: B x {p0, p1, p2} device addresses (HOST table); the caller has run fit_check and fit_geometry
+hipError_t launch_fit_frames(hipStream_t s, int format, const void* const* planes, int B, int h, int w, int pitch0, int pitch1, const cf_fit_geom& g,
+                             const uint8_t* fill, uint8_t* dst, int H, int W) {
+    if (format < CF_YUV_NV12 || format > CF_FRAME_BGR || !planes || !dst || !fill || B < 1 || H < 1 || W < 4 || (W & 3) || h < 1 || w < 1 ||
+        g.rw < 1 || g.rh < 1 || g.dx < 0 || g.dy < 0 || g.dx > W - g.rw || g.dy > H - g.rh)
+        return hipErrorInvalidValue;
+    const uint32_t fv = (uint32_t)fill[0] | ((uint32_t)fill[1] << 8) | ((uint32_t)fill[2] << 16);
+    const long long n = (long long)((H + kFitRows - 1) / kFitRows) * (W >> 2);
+    for (int f0 = 0; f0 < B; f0 += kFitFrames) {
+        const int nb = B - f0 < kFitFrames ? B - f0 : kFitFrames;
+        const FitPtrs tab = frame_ptrs<kFitFrames>(planes, format, f0, nb, true);      // YV12: the I420 kernel on swapped planes (as launch_cut_tiles)
+        const dim3 grid((unsigned)((n + 255) / 256), (unsigned)nb);
+        uint8_t* out = dst + (size_t)f0 * H * W * 3;
+        switch (format) {
+            case CF_YUV_NV12: hipLaunchKernelGGL((fit_frames_kernel<1, false>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W); break;
+            case CF_YUV_NV21: hipLaunchKernelGGL((fit_frames_kernel<1, true>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W); break;
+            case CF_YUV_I420: case CF_YUV_YV12: hipLaunchKernelGGL((fit_frames_kernel<2, false>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W); break;
+            default: hipLaunchKernelGGL((fit_frames_kernel<0, false>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W); break;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_unfit_rows(hipStream_t s, const UnfitParams& p) {
+    if (p.B < 1 || p.rows < 1 || p.max_out < 1 || p.h < 1 || p.w < 1 || p.g.rw < 1 || p.g.rh < 1 || p.score_stride < 1 || !p.dets_net || !p.scores ||
+        !p.lms_net || !p.counts || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(unfit_rows_kernel, dim3(p.B), dim3(1024), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace cf

@@ -467,6 +467,31 @@ size_t merge_mask_bytes(int Bf, int T, int rows);
 constexpr size_t kMergeMaskLimit = (size_t)256 << 20;      // refused with CF_ENOMEM above this, before any launch
 hipError_t launch_merge_tiles(hipStream_t s, const MergeParams& p);
 
+// Aspect-preserving input (cf_fit.hip; the statement is that file's header).  fit_geometry: the placement of an h x w frame in an H x W
+// canvas (host only; CF_EINVAL for an unknown anchor / upscale, a null g or a size below 1).  fit_check: nullptr, or what is wrong with the
+// options and the frames (the text lives in `why`; host only).  The fit writes dst [B][H][W][3] uint8 BGR: the frame converted (4:2:0),
+// resized to (g.rh, g.rw) and pasted at (g.dy, g.dx), `fill` (B, G, R) elsewhere.  planes: HOST table of B x {p0, p1, p2} DEVICE addresses
+// (cf_frame.h; read only).
+int fit_geometry(int anchor, int upscale, int h, int w, int H, int W, cf_fit_geom* g);
+const char* fit_check(std::string& why, const cf_fit_opts* o, int format, int B, int h, int w, int pitch0, int pitch1, int H, int W);
+hipError_t launch_fit_frames(hipStream_t s, int format, const void* const* planes, int B, int h, int w, int pitch0, int pitch1, const cf_fit_geom& g,
+                             const uint8_t* fill, uint8_t* dst, int H, int W);
+// The rows of a threshold decode over B fitted images mapped back into the h x w frames: rows i < min(counts[b], rows) of dets_net
+// [B][rows][4], scores[(b * rows + i) * score_stride], lms_net [B][rows][10] are filtered (non-finite corners, centre outside the
+// content), mapped and compacted per image in order.
+struct UnfitParams {
+    cf_fit_geom g; int h, w, B;
+    const float* dets_net; const float* scores; int score_stride; const float* lms_net; const int* counts; int rows;
+    // outputs (device), frame pixels
+    int max_out;
+    float* dets;          // [B][max_out][5]
+    float* lms;           // [B][max_out][10]
+    float* corners;       // [B][max_out][4]: the box rows FaceList::boxes takes with (H, W) = (h, w)
+    int* out_counts;      // [B], may exceed max_out
+    int* flags;           // [B]: bit 0 = the image had counts > rows
+};
+hipError_t launch_unfit_rows(hipStream_t s, const UnfitParams& p);
+
 // Face tracks across video frames (cf_track.hip; the statement is that file's header).  One update of the streams stream0 .. stream0 + B - 1
 // with the rows i < min(counts[b], rows) of image b: boxes [B][rows][4], scores[(b * rows + i) * score_stride], lms [B][rows][10].
 // All pointers are device-visible; boxes rows are 16-byte aligned.

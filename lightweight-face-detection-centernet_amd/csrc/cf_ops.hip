@@ -964,6 +964,72 @@ int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* re
     return sc.result("cf_op_merge_tiles");
 }
 
+// nullptr, or what is wrong with the options and sizes of a fit geometry (the text lives in `why`)
+static const char* fit_geometry_check(std::string& why, const cf_fit_opts* o, int h, int w, int H, int W) {
+    if (const char* bad = fit_check(why, o, CF_FRAME_BGR, 1, h, w, 3 * w, 0, 4, 4)) return bad;      // the options and the frame's sides
+    if (H < 1 || W < 1) { why = "H=" + std::to_string(H) + ", W=" + std::to_string(W) + " must be at least 1"; return why.c_str(); }
+    return nullptr;
+}
+
+int cf_fit_geometry(const cf_fit_opts* o, int h, int w, int H, int W, cf_fit_geom* g) {
+    std::string why;
+    const char* bad = fit_geometry_check(why, o, h, w, H, W);
+    if (!bad && !g) bad = "null output";
+    if (bad) { g_op_error = std::string("cf_fit_geometry: ") + bad; return CF_EINVAL; }
+    return fit_geometry(o->anchor, o->upscale, h, w, H, W, g);
+}
+
+// The fit kernel of cf_forward_fit on host frames.
+int cf_op_fit(int device, const cf_fit_opts* o, int format, const cf_yuv_planes* host_frames, int B, int h, int w, int pitch0, int pitch1,
+              int H, int W, uint8_t* canvas) {
+    const void* const* hp = reinterpret_cast<const void* const*>(host_frames);
+    std::string why;
+    const char* bad = fit_check(why, o, format, B, h, w, pitch0, pitch1, H, W);
+    if (!bad) bad = redact_check_planes(format, hp, B, 0, pitch0, pitch1);
+    if (!bad && !canvas) bad = "null output";
+    if (!bad && (long long)B * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
+    cf_fit_geom g{};
+    if (!bad && fit_geometry(o->anchor, o->upscale, h, w, H, W, &g)) bad = "no geometry";
+    if (bad) { g_op_error = std::string("cf_op_fit: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    const std::vector<const void*> dev = up_planes(sc, format, hp, B, h, pitch0, pitch1);
+    const size_t out_bytes = (size_t)B * H * W * 3;
+    uint8_t* out = (uint8_t*)sc.alloc(out_bytes);
+    if (sc.err == hipSuccess) sc.chk(launch_fit_frames(sc.s, format, dev.data(), B, h, w, pitch0, pitch1, g, o->fill, out, H, W));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(canvas, out, out_bytes, hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_fit");
+}
+
+int cf_op_unfit(int device, const cf_fit_opts* o, int B, int h, int w, int H, int W, const float* dets_net, const float* scores,
+                const float* lms_net, const int32_t* counts, int rows, int max_out, float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+    std::string why;
+    const char* bad = fit_geometry_check(why, o, h, w, H, W);
+    if (!bad && (!dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags)) bad = "null argument";
+    if (!bad && (B < 1 || rows < 1 || max_out < 1)) bad = "B, rows and max_out must be at least 1";
+    if (!bad && (long long)B * std::max(rows, max_out) > (1 << 24)) bad = "more than 2^24 rows";
+    cf_fit_geom g{};
+    if (!bad && fit_geometry(o->anchor, o->upscale, h, w, H, W, &g)) bad = "no geometry";
+    if (bad) { g_op_error = std::string("cf_op_unfit: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    const size_t n = (size_t)B * rows, mo = (size_t)B * max_out;
+    UnfitParams p{};
+    p.g = g; p.h = h; p.w = w; p.B = B;
+    p.dets_net = (const float*)sc.up(dets_net, n * 4 * sizeof(float));
+    p.scores = (const float*)sc.up(scores, n * sizeof(float)); p.score_stride = 1;
+    p.lms_net = (const float*)sc.up(lms_net, n * 10 * sizeof(float));
+    p.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int)); p.rows = rows;
+    p.max_out = max_out;
+    p.dets = (float*)sc.up(dets, mo * 5 * sizeof(float)); p.lms = (float*)sc.up(lms, mo * 10 * sizeof(float));
+    p.corners = (float*)sc.alloc(mo * 4 * sizeof(float));
+    p.out_counts = (int*)sc.alloc(B * sizeof(int)); p.flags = (int*)sc.alloc(B * sizeof(int));
+    if (sc.err == hipSuccess) sc.chk(launch_unfit_rows(sc.s, p));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, p.dets, mo * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, p.lms, mo * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out_counts, p.out_counts, B * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(flags, p.flags, B * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_unfit");
+}
+
 }  // extern "C"
 
 namespace {

@@ -162,6 +162,9 @@ struct cf_ctx {
     // uploaded when they change) and the frame geometry.  cf_merge_tiles: its workspace and the merged rows, tl_maxout per frame
     std::vector<cf_tile_rect> tl_rects; DevBuf tl_rects_dev; int tl_rects_up = 0;
     int tl_T = 0, tl_Bf = 0, tl_h = 0, tl_w = 0, tl_maxout = 0;
+    // cf_forward_fit: ft_on = the last forward was a fitted one, of tl_Bf frames of tl_h x tl_w placed by ft_g; cf_unfit_rows leaves its
+    // rows where the merge leaves its own (tl, tl_maxout per frame)
+    bool ft_on = false; cf_fit_geom ft_g = {0, 0, 0, 0};
     struct { DevBuf cand, cand_count, order, mask, dets, lms, corners, counts, flags; } tl;
     struct { DevBuf dets, lms, info, corners, counts, flags; } tk; int tk_M = 0;      // cf_track_update: the tracked rows, tk_M per image
     // cf_track_follow: B > 0 = the rows in tk are the follow's, of B frames in the tracker's space (H x W network input, or -- tiled -- H x W
@@ -1150,7 +1153,7 @@ int forward_run(cf_ctx* c, const void* net_in, int in_format, int B) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in.used;      // what cf_align_faces samples
-    c->stage = ROWS_NONE; c->tl_T = 0; c->fo.B = 0;       // (cf_forward_tiles sets its state again behind this call)
+    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->fo.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -1572,7 +1575,9 @@ static int read_out(cf_ctx* c, int B, int stride, const int* d_counts, const int
 enum RowsWanted {
     ROWS_OF_DECODE,          // the threshold decode's, whatever came after (cf_align_faces)
     ROWS_OF_TILED_DECODE,    // the same, of a tiled forward (cf_merge_tiles)
-    ROWS_UNTRACKED,          // the newest that no cf_track_update has consumed: the merged rows of a tiled forward, else the decode's
+    ROWS_OF_FIT_DECODE,      // the same, of a fitted forward (cf_unfit_rows)
+    ROWS_UNTRACKED,          // the newest that no cf_track_update has consumed: the merged rows of a tiled forward, the mapped rows of a
+                             // fitted one, else the decode's
     ROWS_NEWEST              // the followed rows behind a follow, else the tracked rows behind an update, else those (cf_redact_faces, cf_blur_faces,
                              // cf_align_faces_frame, cf_draw_faces)
 };
@@ -1584,12 +1589,14 @@ static int rows_for(cf_ctx* c, const char* who, RowsWanted want, RowSet& r) {
     }
     if (c->last_B < 1) return c->fail(CF_ESTATE, "%s before cf_forward", who);
     if (want == ROWS_OF_TILED_DECODE && c->tl_T < 1) return c->fail(CF_ESTATE, "%s: the last forward was not cf_forward_tiles", who);
+    if (want == ROWS_OF_FIT_DECODE && !c->ft_on) return c->fail(CF_ESTATE, "%s: the last forward was not cf_forward_fit", who);
     if (!c->al_in) return c->fail(CF_ESTATE, "%s: an upload was started after the last forward, its input is gone", who);
     if (c->stage == ROWS_NONE || !c->t_detsnet || !c->t_dets || !c->t_lmsnet || !c->t_counts) return c->fail(CF_ESTATE, "%s without a threshold decode of the last forward", who);
     r = RowSet{c->t_detsnet, c->t_dets, c->t_lmsnet, c->t_counts, c->al_rows, c->last_B, c->H, c->W, false};
-    if (want == ROWS_OF_DECODE || want == ROWS_OF_TILED_DECODE) return CF_OK;
-    if (c->tl_T > 0) {
-        if (c->stage < ROWS_MERGED) return c->fail(CF_ESTATE, "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
+    if (want == ROWS_OF_DECODE || want == ROWS_OF_TILED_DECODE || want == ROWS_OF_FIT_DECODE) return CF_OK;
+    if (c->tl_T > 0 || c->ft_on) {
+        if (c->stage < ROWS_MERGED)
+            return c->fail(CF_ESTATE, c->ft_on ? "%s after cf_forward_fit without a cf_unfit_rows of the last decode" : "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
         r = RowSet{(const float*)c->tl.corners.p, (const float*)c->tl.dets.p, (const float*)c->tl.lms.p, (const int*)c->tl.counts.p, c->tl_maxout, c->tl_Bf, c->tl_h, c->tl_w, true};
     }
     if (c->stage < ROWS_TRACKED) return CF_OK;
@@ -2025,6 +2032,69 @@ int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
         return CF_OK;
     }
     return read_out(c, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
+}
+
+// Fitted forward: the fit kernel (cf_fit.hip) writes the B padded canvases to input_resized, so the plan and its graphs are those of
+// cf_forward_resized.  Host frames -- BGR ones too -- land in src (src_stage_frames); device frames are read in place.
+int cf_forward_fit(cf_ctx* c, const cf_fit_opts* o, int format, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w, int pitch0,
+                   int pitch1) {
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    std::string text;
+    const char* why = fit_check(text, o, format, B, h, w, pitch0, pitch1, c ? c->H : 4, c ? c->W : 4);
+    if (!why) why = redact_check_planes(format, planes, B, in_on_device, pitch0, pitch1);
+    if (!c) {                                                                // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_forward_fit: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_forward_fit: %s", why);
+    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_forward_fit: B=%d exceeds max_batch %d", B, c->max_batch);
+    cf_fit_geom g{};
+    if (fit_geometry(o->anchor, o->upscale, h, w, c->H, c->W, &g)) return c->fail(CF_EINVAL, "cf_forward_fit: no geometry for %d x %d in %d x %d", w, h, c->W, c->H);
+    if (int r = forward_begin(c, "cf_forward_fit", B)) return r;
+    uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
+    auto fit = [&](const void* const* pl, int p0, int p1) { return launch_fit_frames(c->stream, format, pl, B, h, w, p0, p1, g, o->fill, dst, c->H, c->W); };
+    if (in_on_device) HIPCHK(c, fit(planes, pitch0, pitch1));
+    else if (int r = src_stage_frames(c, "cf_forward_fit", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, fit)) return r;
+    if (int r = forward_run(c, dst, CF_IN_U8_HWC_BGR, B)) return r;
+    c->ft_on = true; c->ft_g = g; c->tl_Bf = B; c->tl_h = h; c->tl_w = w;
+    return CF_OK;
+}
+
+// The rows of the last threshold decode of a fitted forward, mapped back into frame pixels (cf_fit.hip) on the stream that carried the
+// decode; they land where the merge leaves its rows, and every consumer takes them from there.
+int cf_unfit_rows(cf_ctx* c, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
+    if (max_out < 1) {
+        if (!c) { op_error_set("cf_unfit_rows: max_out must be at least 1"); return CF_EINVAL; }
+        return c->fail(CF_EINVAL, "cf_unfit_rows: max_out=%d must be at least 1", max_out);
+    }
+    if (!c) { op_error_set("cf_unfit_rows: null context"); return CF_EINVAL; }
+    RowSet in{};
+    if (int r = rows_for(c, "cf_unfit_rows", ROWS_OF_FIT_DECODE, in)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->stage = ROWS_DECODED; c->fo.B = 0;                 // the mapped (and tracked, and followed) rows of an earlier call are gone from here on
+    const int B = c->tl_Bf;
+    const size_t mo = (size_t)B * max_out, nb = (size_t)B * sizeof(int);
+    const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
+    auto& ws = c->tl;
+    const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
+        {ws.dets, nd, "mapped dets"}, {ws.lms, nl, "mapped landmarks"}, {ws.corners, mo * 4 * sizeof(float), "mapped corners"},
+        {ws.counts, nb, "mapped counts"}, {ws.flags, nb, "flags"}};
+    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_unfit_rows")) return r;
+    UnfitParams p{};
+    p.g = c->ft_g; p.h = c->tl_h; p.w = c->tl_w; p.B = B;
+    p.dets_net = in.corners; p.scores = in.dets + 4; p.score_stride = 5; p.lms_net = in.lms; p.counts = in.counts; p.rows = in.stride;
+    p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
+    p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
+    HIPCHK(c, launch_unfit_rows(c->stream, p));
+    c->stage = ROWS_MERGED; c->tl_maxout = max_out;
+    if (out_on_device) {
+        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
+        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms, nl, hipMemcpyDeviceToDevice, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, nb, hipMemcpyDeviceToDevice, c->stream));
+        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, nb, hipMemcpyDeviceToDevice, c->stream));
+        return CF_OK;
+    }
+    return read_out(c, B, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }
 
 // ---- face tracks across frames (cf_track.hip).  The tracker owns the state of its streams, one event that orders its updates across

@@ -55,17 +55,29 @@ def dump_event(detector, images, im_dir, names, save_path):
     return paths
 
 
+def _fit_detector(fit, dtype):
+    """The detector of ``fit=N``: an N x N context that takes a frame of any size letterboxed (``CenterFace.detect_fit``: the aspect
+    ratio kept, black padding; no accuracy claim is made for it)."""
+    from .centerface import CenterFace
+    return CenterFace(fit, fit, dtype=dtype)
+
+
 def anonymize_file(path, out_path, **options):
     """Read one image file, redact every detected face on the device (``CenterFace.anonymize``; ``options``: mode, shape, cell,
     scale, fill, or mode='blur' with shape, radius, scale) and write the result to ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``: sliced
     inference with N x N tiles at native resolution (``CenterFace.detect_tiled``; the image is cropped to even sides), for images much
-    larger than N whose small faces a whole-frame resize would lose; the detections are then in image pixels."""
+    larger than N whose small faces a whole-frame resize would lose; the detections are then in image pixels.  ``fit=N``: the image
+    goes letterboxed through an N x N context instead of one built for its size; not together with ``tiled``."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
     tiled = int(options.pop("tiled", 0) or 0)
+    fit = int(options.pop("fit", 0) or 0)
     dtype = options.pop("dtype", "bf16")
-    if tiled:
+    if fit:
+        detector = _fit_detector(fit, dtype)
+        options["fit"], options["tiled"] = True, bool(tiled)
+    elif tiled:
         from . import ops
         frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
         T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
@@ -84,13 +96,17 @@ def anonymize_file(path, out_path, **options):
 def annotate_file(path, out_path, **options):
     """demo.py:30-51 (``test_image`` with its drawing loop): read one image file, draw every detection on the device
     (``CenterFace.annotate``: green boxes, red landmark dots, the score as a label; ``options`` as there) and write the result to
-    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``: sliced inference as ``anonymize_file``."""
+    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``, ``fit=N``: as ``anonymize_file``."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
     tiled = int(options.pop("tiled", 0) or 0)
+    fit = int(options.pop("fit", 0) or 0)
     dtype = options.pop("dtype", "bf16")
-    if tiled:
+    if fit:
+        detector = _fit_detector(fit, dtype)
+        options["fit"], options["tiled"] = True, bool(tiled)
+    elif tiled:
         from . import ops
         frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
         T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
@@ -106,15 +122,17 @@ def annotate_file(path, out_path, **options):
     return results[0]
 
 
-def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16"):
+def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0):
     """Read one image file and write the aligned chip of every detected face, cut from the image at its own resolution
     (``CenterFace.detect_aligned_frames``), to ``out_dir``/<image name>_<k>.png.  Returns (detections, the paths written).
-    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides)."""
+    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides).  ``fit=N``: as ``anonymize_file``."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
-    tiled = int(tiled or 0)
-    if tiled:
+    tiled, fit = int(tiled or 0), int(fit or 0)
+    if fit:
+        detector = _fit_detector(fit, dtype)
+    elif tiled:
         from . import ops
         frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
         T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
@@ -122,7 +140,7 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16"):
     else:
         detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype)
     try:
-        dets, lms, chips = detector.detect_aligned_frames(frame[None], "bgr", size, tiled=bool(tiled))[0]
+        dets, lms, chips = detector.detect_aligned_frames(frame[None], "bgr", size, tiled=bool(tiled), fit=bool(fit) or None)[0]
     finally:
         detector.close()
     os.makedirs(out_dir, exist_ok=True)
@@ -134,13 +152,15 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16"):
 
 
 def main(argv=None):
-    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N]``: print the detections of one image
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]]``: print the detections of one image
     file; with ``--draw`` also write the image with every detection drawn into it (boxes, landmark dots and, unless ``--label none``,
     the score); with
     ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``; or blurred: ``--blur [R]``, R = the
     filter strength 1..24, without it or 0 an eighth of each face's smaller side); with ``--chips`` write one aligned
     ``--size`` x ``--size`` chip per face, cut from the image at its own resolution, into DIR; with ``--tiled N`` beside either the
-    faces are found by sliced inference over N x N tiles at native resolution."""
+    faces are found by sliced inference over N x N tiles at native resolution; with ``--fit [N]`` (default 640) the image goes through an
+    N x N context letterboxed -- its aspect ratio kept, black padding, the detections mapped back into image pixels -- instead of a
+    context built for its size (no accuracy claim is made for it)."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("image")
@@ -152,6 +172,8 @@ def main(argv=None):
     ap.add_argument("--blur", type=int, nargs="?", const=0, default=None, metavar="R",
                     help="with --anonymize: blur the faces instead (R in 1..24; 0 or no value: per face, from its size)")
     ap.add_argument("--tiled", type=int, default=0, metavar="N", help="with --anonymize / --chips: detect on overlapping N x N tiles (N a multiple of 32)")
+    ap.add_argument("--fit", type=int, nargs="?", const=640, default=0, metavar="N",
+                    help="detect through an N x N context with the image letterboxed (N a multiple of 32; default 640)")
     ap.add_argument("--chips", metavar="DIR", help="write the aligned chip of every detected face, cut from the image itself, into DIR")
     ap.add_argument("--size", type=int, default=112, help="with --chips: the chip side (a multiple of 4 in [16, 512])")
     ap.add_argument("--draw", metavar="OUT", help="write the image with every detection drawn into it to OUT")
@@ -159,6 +181,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.tiled and not (args.anonymize or args.chips or args.draw):
         ap.error("--tiled goes with --anonymize, --chips or --draw")
+    if args.tiled and args.fit:
+        ap.error("--tiled and --fit exclude each other")
     if args.draw and (args.anonymize or args.chips):
         ap.error("--draw, --anonymize and --chips are separate runs")
     if args.blur is not None and not args.anonymize:
@@ -166,18 +190,22 @@ def main(argv=None):
     if args.anonymize and args.chips:
         ap.error("--anonymize and --chips are separate runs")
     if args.draw:
-        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled)
+        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit)
     elif args.chips:
-        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled)
+        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit)
     elif args.anonymize and args.blur is not None:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit)
     elif args.anonymize:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit)
     else:
         from .centerface import CenterFace
         frame = imread(args.image)
-        detector = CenterFace(frame.shape[0], frame.shape[1], dtype="bf16")
-        dets, _ = detector(frame)
+        if args.fit:
+            detector = _fit_detector(args.fit, "bf16")
+            dets, _ = detector.detect_fit(frame[None])[0]
+        else:
+            detector = CenterFace(frame.shape[0], frame.shape[1], dtype="bf16")
+            dets, _ = detector(frame)
         detector.close()
     print(format_wider_result(args.image, dets), end="")
 

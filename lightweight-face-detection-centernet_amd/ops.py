@@ -370,6 +370,49 @@ def merge_tiles(rects, frame_hw, net_hw, dets_net, scores, lms_net, counts, max_
     return od, ol, oc, fl
 
 
+def fit_geometry(h, w, H, W, anchor="center", upscale=True):
+    """The placement of an h x w frame in an H x W canvas with its aspect ratio kept (``cf_fit_geometry``, host only): (rw, rh, dx, dy)."""
+    o, g = _lib.fit_opts(anchor, upscale), _lib.FitGeom()
+    _lib.check(_lib.lib().cf_fit_geometry(C.byref(o), int(h), int(w), int(H), int(W), C.byref(g)), op=True)
+    return g.rw, g.rh, g.dx, g.dy
+
+
+def fit_frames(frames, size, fmt="bgr", anchor="center", upscale=True, fill=(0, 0, 0), device=0):
+    """The fit kernel (``cf_op_fit``): uint8 [B, H, W, 3] BGR canvases of ``size`` = (H, W), frame b converted to BGR (4:2:0 formats),
+    resized to (rh, rw) with its aspect ratio kept and pasted at (dy, dx), ``fill`` (B, G, R) elsewhere.  ``frames`` as ``cut_tiles``
+    takes them; they are only read.  No accuracy claim is made for letterboxed input."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    H, W = int(size[0]), int(size[1])
+    o = _lib.fit_opts(anchor, upscale, fill)
+    out = np.empty((B, H, W, 3), np.uint8)
+    _lib.check(_lib.lib().cf_op_fit(device, C.byref(o), _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, H, W, ptr(out)), op=True)
+    del keep
+    return out
+
+
+def unfit_rows(frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, anchor="center", upscale=True, dets=None, lms=None, device=0):
+    """The mapping of decoded rows back into frame pixels (``cf_op_unfit``): dets_net [B, rows, 4] box corners, scores [B, rows], lms_net
+    [B, rows, 10] in the coordinates of a ``net_hw`` = (H, W) canvas that holds a fitted ``frame_hw`` = (h, w) frame, counts [B]; the rows
+    below min(count, rows) whose corners are finite and whose centre lies in the content are mapped and compacted in order.  Returns
+    (dets [B, max_out, 5], lms [B, max_out, 10], counts [B], flags [B]); rows at and past an image's count keep the bytes of the
+    ``dets`` / ``lms`` arrays passed in (zeros by default)."""
+    d = np.ascontiguousarray(dets_net, dtype=np.float32)
+    if d.ndim != 3 or d.shape[2] != 4:
+        raise ValueError("dets_net must be [B, rows, 4], got %s" % (d.shape,))
+    B, rows, _ = d.shape
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(B, rows)
+    lm = np.ascontiguousarray(lms_net, dtype=np.float32).reshape(B, rows, 10)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(B)
+    max_out = int(max_out)
+    od = np.zeros((B, max_out, 5), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(B, max_out, 5)
+    ol = np.zeros((B, max_out, 10), np.float32) if lms is None else np.ascontiguousarray(lms, dtype=np.float32).reshape(B, max_out, 10)
+    oc, fl = np.zeros((B,), np.int32), np.zeros((B,), np.int32)
+    o = _lib.fit_opts(anchor, upscale)
+    _lib.check(_lib.lib().cf_op_unfit(device, C.byref(o), B, int(frame_hw[0]), int(frame_hw[1]), int(net_hw[0]), int(net_hw[1]),
+                                      ptr(d), ptr(sc), ptr(lm), ptr(cn), rows, max_out, ptr(od), ptr(ol), ptr(oc), ptr(fl)), op=True)
+    return od, ol, oc, fl
+
+
 def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=None, device=0, **opts):
     """The tracker's update over a whole sequence (``cf_op_track``) with a fresh tracker: boxes [F, S, rows, 4], scores [F, S, rows], lms
     [F, S, rows, 10], counts [F, S] -- frame f of stream s has the rows below min(count, rows), in whatever coordinates they are.

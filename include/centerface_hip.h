@@ -216,6 +216,54 @@ int cf_set_rescale(cf_ctx* ctx, float scale_h, float scale_w);
  * in flight and collect them later (CenterFaceBuckets): the decode runs when the forward finishes, not when the host gets there. */
 int cf_decode_threshold_enqueue(cf_ctx* ctx, int mode, float score_thresh, float nms_thresh, int img_h, int img_w, int max_out);
 
+/* ---- flip test: the batch and its mirror in one forward, the heads merged on the device ---------------------------------------- */
+/* The reference trains on mirrored images half of the time (dataset/dataset.py:125-128 mirrors the image, :166-174 the boxes and the
+ * landmark x values, and swaps the left and right points 0 <-> 1 and 3 <-> 4) and carries CenterNet's flip test for inference
+ * (centerface_ext.py:162-163 concatenates the batch with its mirror; model/losses.py:94-116 flip_tensor / flip_lr / flip_lr_off put the
+ * mirrored maps back).  cf_set_flip_test(ctx, 1) switches ctx to it; 0 (the default) switches it off; any other value is CF_EINVAL, as
+ * is 1 on a context with max_batch < 2.  No trained weights and no labelled set are on hand: no accuracy claim is made.  The cost is
+ * about one forward at 2B instead of one at B, plus the two kernels below.
+ *
+ * While it is on, every forward entry point -- cf_forward, cf_forward_resized, cf_forward_images / cf_upload_images /
+ * cf_forward_uploaded, cf_forward_yuv, cf_forward_tiles (B = the tile count Bf * T), cf_forward_fit, and the forward inside
+ * cf_detect_topk -- accepts B <= max_batch / 2 (CF_EINVAL above that, before anything is enqueued) and runs
+ *     mirror -> the plan over 2B images -> merge
+ * on the context's stream: image B + b of the network input is image b with its columns reversed (csrc/cf_flip.hip writes it on the
+ * device; there is no second host-to-device copy), and ONE kernel folds the two halves of the head records into the first before
+ * anything reads them.  The context then holds B images (cf_get_heads, every decode, cf_merge_tiles, cf_unfit_rows, the tracker,
+ * redact, blur, draw, chips and best shots work unchanged on the merged heads); cf_align_faces and cf_get_resized_input see the
+ * unmirrored images.  Results are the same with and without CF_FLAG_NO_GRAPH.  cf_forward_trace and cf_profile_forward (and the
+ * experiments build's cf_forward_lanes) return CF_ESTATE while it is on.  A context that never switches it on allocates nothing for it;
+ * the first flip forward of a caller's device tensor or a host batch of the network's size allocates a second input buffer.
+ *
+ * THE MERGE.  All arithmetic is float32, in the order written.  The head records are rec [.][h][w][16] float32:
+ *     r[0] = clamp(sigmoid(hm)), r[1..2] = wh, r[3..12] = lm as x, y of points 0 .. 4, r[13..14] = reg, r[15] = the raw hm logit,
+ * and hm_plane [.][h * w] is the dense copy of r[0] that the decodes scan.  For b < B and cell (y, x) let
+ *     a = rec[b][y][x],   m = rec[B + b][y][w - 1 - x],   p = (1, 0, 2, 4, 3).
+ * Then
+ *     out[0]      = (a[0] + m[0]) * 0.5f                      the heat, after sigmoid and clamp, as CenterNet averages it
+ *     out[1]      = (a[1] + m[1]) * 0.5f
+ *     out[2]      = (a[2] + m[2]) * 0.5f                      wh
+ *     out[3 + 2j] = (a[3 + 2j] - m[3 + 2 p[j]]) * 0.5f        x of point j = 0 .. 4
+ *     out[4 + 2j] = (a[4 + 2j] + m[4 + 2 p[j]]) * 0.5f        y of point j
+ *     out[13..14] = a[13..14]                                  reg of the unmirrored pass only, as CenterNet does
+ *     out[15]     = (a[15] + m[15]) * 0.5f                    the MEAN LOGIT of the two passes, NOT the logit of out[0]
+ * out overwrites rec[b][y][x], and hm_plane[b][y * w + x] = out[0].  A landmark x is an offset from the cell centre in map units: in
+ * the unmirrored frame the mirrored pass's point lies at x + 0.5 - lx', hence the minus; the pairs change places because the training
+ * data swaps them.
+ *
+ * Worked example, B = 1, h = 1, w = 2 (every value is exact in float32):
+ *     rec[0][0][0] = a  = ( 0.75, 4,  6,   1, -2,   3,  0.5,  -1, 2.5,  5, -3,  0.25,  8,  0.125, 0.875,  1.5)
+ *     rec[1][0][1] = m  = ( 0.25, 2, 10,  -3,  4,   2, -1,     7, 0.5,  1.5, -5,  3,   6,  0.5,   0.25,  -0.5)
+ *       -> rec[0][0][0] = ( 0.5,  3,  8,  -0.5, -1.5,  3, 2.25,  -4, 1.5,  1, 1.5,  -0.625, 1.5,  0.125, 0.875,  0.5)
+ *          e.g. out[3] = (a[3] - m[5]) / 2 = (1 - 2) / 2, out[4] = (a[4] + m[6]) / 2 = (-2 - 1) / 2, out[5] = (a[5] - m[3]) / 2 = (3 + 3) / 2,
+ *          out[9] = (a[9] - m[11]) / 2 = (5 - 3) / 2, out[11] = (a[11] - m[9]) / 2 = (0.25 - 1.5) / 2, out[12] = (a[12] + m[10]) / 2 = (8 - 5) / 2
+ *     rec[0][0][1] = a' = ( 0.5,  1,  1,   0,  0,   0,  0,   0,  0,   0,  0,   0,   0,  0.25, 0.75,  0)
+ *     rec[1][0][0] = m' = ( 0.5,  3,  5,   2,  4,   6,  8,  10, 12,  14, 16,  18,  20,  9,    9,     2)
+ *       -> rec[0][0][1] = ( 0.5,  2,  3,  -3,  4,  -1,  2,  -5,  6,  -9, 10,  -7,   8,  0.25, 0.75,  1)
+ *     hm_plane[0] = (0.5, 0.5). */
+int cf_set_flip_test(cf_ctx* ctx, int on);
+
 /* ---- aligned face chips: the similarity warp of the frame onto a chip template, on the device ---------------------------- */
 /* The next stage of a face pipeline (recognition, quality, attributes) takes an aligned crop: the least-squares similarity that maps
  * the detector's five landmarks onto a template (what SimilarityTransform.estimate + cv2.warpAffine do on the host), sampled
@@ -1114,6 +1162,16 @@ int cf_op_fit(int device, const cf_fit_opts* opts, int format, const cf_yuv_plan
 int cf_op_unfit(int device, const cf_fit_opts* opts, int B, int h, int w, int H, int W, const float* dets_net, const float* scores,
                 const float* lms_net, const int32_t* counts, int rows, int max_out, float* dets, float* lms, int32_t* out_counts,
                 int32_t* flags);
+/* The mirror kernel of the flip test alone (cf_set_flip_test), on a host batch: x holds B network inputs of in_format (CF_IN_U8_HWC_BGR:
+ * uint8 [B][H][W][3]; CF_IN_F32_NCHW: float32 [B][3][H][W]), out the same with the columns of every image reversed (whole pixels, not
+ * bytes).  The kernel runs as the flip forward of a caller's tensor runs it -- one launch that writes the unmirrored and the mirrored
+ * half of a 2B batch -- and the mirrored half comes back.  CF_EINVAL, before any device is touched, for a NULL pointer, B < 1, H < 1,
+ * W not a positive multiple of 32, an unknown format, or 2^31 bytes and more. */
+int cf_op_mirror(int device, int in_format, const void* x, int B, int H, int W, void* out);
+/* The merge kernel of the flip test alone, on host records: records_2B [2B][h][w][16] float32 (B unmirrored images, then the B
+ * mirrored passes) -> records_out [B][h][w][16] and hm_plane_out [B][h * w], by the statement under cf_set_flip_test.  CF_EINVAL, before
+ * any device is touched, for a NULL pointer, B, h or w below 1, or 2^31 bytes and more. */
+int cf_op_flip_heads(int device, const float* records_2B, int B, int h, int w, float* records_out, float* hm_plane_out);
 /* The update kernel of cf_track_update over a whole sequence, on host tables, with a fresh tracker of n_streams streams: frame f of
  * stream s has the rows i < min(counts_in[f][s], rows) of boxes [F][S][rows][4], scores [F][S][rows], lms_in [F][S][rows][10] ->
  * dets [F][S][max_tracks][5], lms [F][S][max_tracks][10], info [F][S][max_tracks][3], counts [F][S], flags [F][S] after each frame.

@@ -54,6 +54,7 @@ EXPORTS = (
     "cf_draw_faces", "cf_op_draw", "cf_draw_layout",
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
     "cf_fit_geometry", "cf_forward_fit", "cf_unfit_rows", "cf_op_fit", "cf_op_unfit",
+    "cf_set_flip_test", "cf_op_mirror", "cf_op_flip_heads",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_follow", "cf_op_follow",
     "cf_scene_create", "cf_scene_destroy", "cf_scene_forget", "cf_scene_check", "cf_op_scene",
@@ -536,6 +537,9 @@ def lib():
         L.cf_unfit_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.cf_op_fit.argtypes = [C.c_int, C.POINTER(FitOpts), C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
         L.cf_op_unfit.argtypes = [C.c_int, C.POINTER(FitOpts)] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
+        L.cf_set_flip_test.argtypes = [C.c_void_p, C.c_int]
+        L.cf_op_mirror.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]
+        L.cf_op_flip_heads.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2
         L.cf_track_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(TrackOpts), C.POINTER(C.c_void_p)]
         L.cf_track_destroy.argtypes = [C.c_void_p]
         L.cf_track_reset.argtypes = [C.c_void_p, C.c_int]

@@ -44,7 +44,11 @@ class Engine(object):
     """One cf_ctx: one GPU, one stream, fixed (H, W), batch up to ``max_batch``."""
 
     def __init__(self, height, width, max_batch=1, dtype="fp32", device=0, weights=None,
-                 collapse_heads=None, fuse=True, graph=True, uphead=True, neck=True, decode_stream=True, high_priority_streams=False):
+                 collapse_heads=None, fuse=True, graph=True, uphead=True, neck=True, decode_stream=True, high_priority_streams=False,
+                 flip_test=False):
+        """``flip_test=True``: CenterNet's flip test (``cf_set_flip_test``): every forward runs the batch and its mirror as one batch
+        of 2B and the heads are merged on the device before anything reads them -- about one forward at 2B instead of one at B.  The
+        context is created with room for ``2 * max_batch`` images; ``max_batch`` stays the caller's number.  No accuracy claim is made."""
         L = _lib.lib()
         if dtype not in _DTYPES:
             raise ValueError("dtype must be one of %s" % sorted(_DTYPES))
@@ -61,9 +65,12 @@ class Engine(object):
                  | (0 if neck else _lib.CF_FLAG_NO_NECK) | (0 if decode_stream else _lib.CF_FLAG_NO_DECODE_STREAM)
                  | (_lib.CF_FLAG_STREAM_HIGH if high_priority_streams else 0))
         handle = C.c_void_p()
-        _lib.check(L.cf_create(self.device, self.max_batch, self.H, self.W, _DTYPES[dtype], flags, C.byref(handle)))
+        self._flip_room, self._flip = bool(flip_test), False
+        _lib.check(L.cf_create(self.device, self.max_batch * (2 if self._flip_room else 1), self.H, self.W, _DTYPES[dtype], flags, C.byref(handle)))
         self._h = handle
         self._L = L
+        if self._flip_room:
+            self.set_flip_test(True)
         # what the last forward was: its batch (last_B), (frames, tiles per frame) when it was tiled, the batches waiting in an upload or
         # in a lane, the rows the last decode or merge kept (the align forms size their buffers from it), the host arrays kept alive
         self._last = types.SimpleNamespace(B=0, tiles=None, uploaded_B=0, lane_B=0, kept=0, keep=None)
@@ -249,6 +256,19 @@ class Engine(object):
         """centerface.py:55-62 on the device (``cf_set_rescale``): the threshold decodes of this engine return
         ``x // scale_w``, ``y // scale_h``; (0, 0) = off."""
         self._chk(self._L.cf_set_rescale(self._h, float(scale_h), float(scale_w)))
+
+    @property
+    def flip_test(self):
+        """Whether the forwards of this engine run the flip test (``set_flip_test``)."""
+        return self._flip
+
+    def set_flip_test(self, on):
+        """Switch CenterNet's flip test on or off for the forwards from now on (``cf_set_flip_test``); the results of the last forward
+        stay.  Only an engine built with ``flip_test=True`` has the room for the mirrored half."""
+        if not self._flip_room:
+            raise ValueError("set_flip_test needs an engine built with flip_test=True (its context holds 2 * max_batch images)")
+        self._chk(self._L.cf_set_flip_test(self._h, 1 if on else 0))
+        self._flip = bool(on)
 
     def resized_input(self):
         """The uint8 [B,H,W,3] BGR batch the network read in the last forward_resized_enqueue / forward_yuv_enqueue (for tests)."""
@@ -1080,7 +1100,9 @@ class CenterFace(object):
     std = np.array([0.289, 0.274, 0.278], dtype=np.float32).reshape(1, 1, 3)    # centerface.py:14-15
 
     def __init__(self, height, width, landmarks=True, *, weights=None, dtype="fp32", device=0,
-                 max_batch=1, collapse_heads=None, nms_thresh=0.3, max_dets=1024):
+                 max_batch=1, collapse_heads=None, nms_thresh=0.3, max_dets=1024, flip_test=False):
+        """``flip_test=True``: every forward of every path runs the batch and its mirror and merges the heads on the device
+        (``Engine(flip_test=True)``): about twice the network time; no accuracy claim is made."""
         self.landmarks = landmarks
         self.src_hw = (int(height), int(width))                                  # the frame size detect_yuv takes
         self.img_h_new, self.img_w_new, self.scale_h, self.scale_w = self.transform(height, width)
@@ -1088,7 +1110,8 @@ class CenterFace(object):
         self.max_dets = max_dets
         self.device = device
         # (threshold decodes run on the main stream: these contexts never need a decode stream of their own)
-        self._engine_kw = dict(max_batch=max_batch, dtype=dtype, device=device, weights=weights, collapse_heads=collapse_heads, decode_stream=False)
+        self._engine_kw = dict(max_batch=max_batch, dtype=dtype, device=device, weights=weights, collapse_heads=collapse_heads, decode_stream=False,
+                               flip_test=flip_test)
         self.engine = Engine(self.img_h_new, self.img_w_new, **self._engine_kw)
         self._engine2 = None                      # second context of detect_stream, created on first use
 
@@ -1849,8 +1872,9 @@ class CenterFaceBuckets(object):
     the order of ``imgs``; every image gets exactly what ``CenterFace(h, w)(img)`` returns for it."""
 
     def __init__(self, landmarks=True, *, weights=None, dtype="fp32", device=0, max_batch=32, max_buckets=8,
-                 nms_thresh=0.3, max_dets=1024, collapse_heads=None):
+                 nms_thresh=0.3, max_dets=1024, collapse_heads=None, flip_test=False):
         self.landmarks, self.dtype, self.device, self.max_batch, self.max_buckets = landmarks, dtype, device, max_batch, max_buckets
+        self.flip_test = bool(flip_test)        # every bucket's engine runs the flip test (Engine(flip_test=True))
         self.nms_thresh, self.max_dets, self.collapse_heads = nms_thresh, max_dets, collapse_heads
         self._weights = _weights.synthetic_state_dict(0) if weights is None else (
             _weights.load_checkpoint(weights) if isinstance(weights, str) else weights)
@@ -1865,7 +1889,7 @@ class CenterFaceBuckets(object):
                 old = next(iter(self._buckets))
                 self._buckets.pop(old).close()
             eng = Engine(H, W, max_batch=self.max_batch, dtype=self.dtype, device=self.device, weights=self._weights, decode_stream=False,
-                         collapse_heads=self.collapse_heads)
+                         collapse_heads=self.collapse_heads, flip_test=self.flip_test)
             self.created += 1
             self._placement_dirty = True
         self._buckets[key] = eng

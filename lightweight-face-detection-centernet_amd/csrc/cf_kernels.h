@@ -492,6 +492,16 @@ struct UnfitParams {
 };
 hipError_t launch_unfit_rows(hipStream_t s, const UnfitParams& p);
 
+// Flip test (cf_flip.hip; the statement is in include/centerface_hip.h).  mirror_check: nullptr, or what is wrong with the format and sizes
+// of a batch to mirror (the text lives in `why`; host only).  launch_mirror_batch: dst holds 2B network inputs of in_format (uint8
+// [.][H][W][3] or float32 [.][3][H][W]; 16-byte aligned); images B .. 2B-1 become images 0 .. B-1 of src with their columns reversed and,
+// when src != dst, images 0 .. B-1 of dst become those of src in the same launch.  src == dst mirrors the first half of dst into its
+// second.  src is 4-byte aligned at least.  launch_flip_heads: rec [2B][h][w][16] float32 -> the merged records in rec [0 .. B) and their
+// heat in hm_plane [B][h * w], in place.
+const char* mirror_check(std::string& why, int in_format, int B, int H, int W);
+hipError_t launch_mirror_batch(hipStream_t s, int in_format, const void* src, void* dst, int B, int H, int W);
+hipError_t launch_flip_heads(hipStream_t s, float* rec, float* hm_plane, int B, int h, int w);
+
 // Face tracks across video frames (cf_track.hip; the statement is that file's header).  One update of the streams stream0 .. stream0 + B - 1
 // with the rows i < min(counts[b], rows) of image b: boxes [B][rows][4], scores[(b * rows + i) * score_stride], lms [B][rows][10].
 // All pointers are device-visible; boxes rows are 16-byte aligned.

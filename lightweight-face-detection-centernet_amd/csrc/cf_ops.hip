@@ -1030,6 +1030,38 @@ int cf_op_unfit(int device, const cf_fit_opts* o, int B, int h, int w, int H, in
     return sc.result("cf_op_unfit");
 }
 
+// The mirror kernel of the flip test as the flip forward of a caller's tensor runs it: src -> a 2B batch, whose second half comes back.
+int cf_op_mirror(int device, int in_format, const void* x, int B, int H, int W, void* out) {
+    std::string why;
+    const char* bad = mirror_check(why, in_format, B, H, W);
+    if (!bad && (!x || !out)) bad = "null argument";
+    const long long one = bad ? 0 : (long long)B * 3 * H * W * (in_format == CF_IN_U8_HWC_BGR ? 1 : 4);
+    if (!bad && 2 * one > INT_MAX) bad = "2^31 bytes and more in the doubled batch";
+    if (bad) { g_op_error = std::string("cf_op_mirror: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    const void* src = sc.up(x, (size_t)one);
+    uint8_t* dst = (uint8_t*)sc.alloc(2 * (size_t)one);
+    if (sc.err == hipSuccess) sc.chk(launch_mirror_batch(sc.s, in_format, src, dst, B, H, W));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out, dst + one, (size_t)one, hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_mirror");
+}
+
+int cf_op_flip_heads(int device, const float* records_2B, int B, int h, int w, float* records_out, float* hm_plane_out) {
+    const char* bad = nullptr;
+    if (!records_2B || !records_out || !hm_plane_out) bad = "null argument";
+    else if (B < 1 || h < 1 || w < 1) bad = "B, h and w must be at least 1";
+    else if (2LL * B * h * w * 16 * (long long)sizeof(float) > INT_MAX) bad = "2^31 bytes and more of records";
+    if (bad) { g_op_error = std::string("cf_op_flip_heads: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    const size_t cells = (size_t)B * h * w;
+    float* rec = (float*)sc.up(records_2B, 2 * cells * 16 * sizeof(float));
+    float* plane = (float*)sc.alloc(cells * sizeof(float));
+    if (sc.err == hipSuccess) sc.chk(launch_flip_heads(sc.s, rec, plane, B, h, w));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(records_out, rec, cells * 16 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(hm_plane_out, plane, cells * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_flip_heads");
+}
+
 }  // extern "C"
 
 namespace {

@@ -149,6 +149,9 @@ struct cf_ctx {
     bool thr_pending = false; int thr_mode = 0, thr_h = 0, thr_w = 0, thr_maxout = 0, thr_B = 0; float thr_score = 0.f, thr_nms = 0.f, thr_rs_h = 0.f, thr_rs_w = 0.f;
     int prio = 0;                      // stream priority class of the context's main / decode streams: -1 lowest, 0 normal, +1 highest
     float rs_h = 0.f, rs_w = 0.f;      // cf_set_rescale: the threshold decode floor-divides x by rs_w and y by rs_h (0 = off)
+    // cf_set_flip_test: every forward runs B images and their mirrors as 2B (batch_cap) and folds the heads (forward_run); fl_in = the 2B
+    // input of the forwards whose source is not input_resized (a caller's tensor, a host-input slot), allocated by the first of them
+    bool flip = false; DevBuf fl_in;
     // What the last forward read (al_in: device address of the network input, al_fmt its format, al_slot the host-input staging slot it
     // sits in or -1; al_in = nullptr once an upload may have replaced it) and the newest face rows behind it (rows_for): the threshold
     // decode's (t_detsnet [max_batch][t_maxout][4] corners and t_lmsnet [.][.][10] landmarks in network coordinates, written by the sweep
@@ -671,7 +674,7 @@ int cf_destroy(cf_ctx* c) {
     for (const DevBuf* b : {&c->src.buf, &c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->dr_recs, &c->tl_rects_dev,
                             &c->tl.cand, &c->tl.cand_count, &c->tl.order, &c->tl.mask, &c->tl.dets, &c->tl.lms, &c->tl.corners, &c->tl.counts, &c->tl.flags,
                             &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags, &c->fo.slot_moves, &c->fo.moves, &c->sn.part, &c->sn.out,
-                            &c->bs.q, &c->bs.sc, &c->bs.jobs, &c->bs.flags, &c->bs.chips, &c->bs.off, &c->bs.out})
+                            &c->bs.q, &c->bs.sc, &c->bs.jobs, &c->bs.flags, &c->bs.chips, &c->bs.off, &c->bs.out, &c->fl_in})
         if (b->p) hipFree(b->p);
     if (c->h_thr) hipHostFree(c->h_thr);
     if (c->ev_thr) hipEventDestroy(c->ev_thr);
@@ -1148,8 +1151,30 @@ hipError_t launch_plan_at(cf_ctx* c, size_t i, const void* net_in, int in_format
     return launch_op(c, op, net_in, in_format, B);
 }
 
-// The tail of every forward entry point: the plan on the main stream, reading B images of in_format at net_in
-int forward_run(cf_ctx* c, const void* net_in, int in_format, int B) {
+int grow(cf_ctx* c, DevBuf& b, size_t need_bytes, const char* what, const char* who);
+
+// The largest batch a forward entry point takes: with flip test on, the mirrors need the other half of every buffer
+inline int batch_cap(const cf_ctx* c) { return c->flip ? c->max_batch / 2 : c->max_batch; }
+
+// The tail of every forward entry point: the plan on the main stream, reading B images of in_format at net_in.  Flip test: mirror ->
+// the plan over 2B images -> merge (cf_flip.hip).  input_resized has room for the mirrors behind its B images (B <= max_batch / 2); a
+// caller's tensor and a host-input slot are copied into fl_in by the launch that mirrors them.  The context's state speaks of the B
+// unmirrored images from here on.
+int forward_run(cf_ctx* c, const void* caller_in, int in_format, int Bcaller) {
+    const void* net_in = caller_in;
+    const int B = c->flip ? 2 * Bcaller : Bcaller;        // what the plan runs
+    if (c->flip) {
+        void* in2 = c->bufs[c->buf_resized].p;
+        const bool copied = caller_in != in2;
+        if (copied) {
+            const size_t bytes = (size_t)c->max_batch * 3 * c->H * c->W * (in_format == CF_IN_U8_HWC_BGR ? 1 : 4) + 256;      // + what the stem may over-read
+            if (int r = grow(c, c->fl_in, bytes, "flip-test input", "cf_forward")) return r;
+            in2 = c->fl_in.p;
+        }
+        HIPCHK(c, launch_mirror_batch(c->stream, in_format, caller_in, in2, Bcaller, c->H, c->W));
+        if (copied) { if (int r = in_slot_done(c)) return r; }      // a host-input slot has been read: it is free behind the mirror
+        net_in = in2;
+    }
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in.used;      // what cf_align_faces samples
@@ -1166,9 +1191,11 @@ int forward_run(cf_ctx* c, const void* net_in, int in_format, int B) {
         if (!(exec && op.kind != OP_HEAD)) HIPCHK(c, launch_plan_at(c, i, net_in, in_format, B, &used));
         i += used;
     }
+    // flip test: the two halves of the head records become the first half, before anything reads them (eager, as the heads are)
+    if (c->flip) HIPCHK(c, launch_flip_heads(c->stream, (float*)c->bufs[c->buf_heads].p, c->hm_plane, Bcaller, c->H / 4, c->W / 4));
     HIPCHK(c, hipEventRecord(c->ev_fwd, c->stream));
     if (int r = in_slot_done(c)) return r;          // this forward read a host-input slot: mark when it is free again
-    c->last_B = B;
+    c->last_B = Bcaller;
     return CF_OK;
 }
 
@@ -1260,7 +1287,8 @@ extern "C" {
 // a lane still pending.  in_ok / tail: cf_forward folds its null-input check into the range message.
 static int forward_begin(cf_ctx* c, const char* who, int B, bool in_ok = true, const char* tail = "") {
     if (!c->weights_loaded) return c->fail(CF_ESTATE, "%s before cf_load_weights", who);
-    if (!in_ok || B < 1 || B > c->max_batch) return c->fail(CF_EINVAL, "%s: B=%d outside [1, %d]%s", who, B, c->max_batch, tail);
+    if (!in_ok || B < 1 || B > batch_cap(c))
+        return c->fail(CF_EINVAL, "%s: B=%d outside [1, %d]%s%s", who, B, batch_cap(c), tail, c->flip ? " (flip test is on: half of max_batch)" : "");
     HIPCHK(c, hipSetDevice(c->device));
     CF_FLUSH_LANE(c);
     return CF_OK;
@@ -1441,6 +1469,19 @@ int cf_set_rescale(cf_ctx* c, float scale_h, float scale_w) {
     if (!(scale_h >= 0.f) || !(scale_w >= 0.f) || (scale_h == 0.f) != (scale_w == 0.f))
         return c->fail(CF_EINVAL, "cf_set_rescale: scales must both be positive, or both 0 (off); got %g, %g", (double)scale_h, (double)scale_w);
     c->rs_h = scale_h; c->rs_w = scale_w;
+    return CF_OK;
+}
+
+// Flip test on / off for the forwards from now on (forward_run); the results of the last forward stay as they are
+int cf_set_flip_test(cf_ctx* c, int on) {
+    if (!c) return CF_EINVAL;
+    if (on != 0 && on != 1) return c->fail(CF_EINVAL, "cf_set_flip_test: on=%d must be 0 or 1", on);
+    if (on && c->max_batch < 2) return c->fail(CF_EINVAL, "cf_set_flip_test: max_batch=%d leaves no room for the mirrored half (2 at least)", c->max_batch);
+    if (on && !c->flip) {
+        HIPCHK(c, hipSetDevice(c->device));
+        CF_FLUSH_LANE(c);                                 // (experiments build) the back half of a lane forward runs as it was begun
+    }
+    c->flip = on != 0;
     return CF_OK;
 }
 
@@ -1966,7 +2007,8 @@ int cf_forward_tiles(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_
     const void* const* planes = reinterpret_cast<const void* const*>(frames);
     std::string why;
     if (tiles_check(why, format, Bf, h, w, pitch0, pitch1, rects, T, c->H, c->W)) return c->fail(CF_EINVAL, "cf_forward_tiles: %s", why.c_str());
-    if ((long long)Bf * T > c->max_batch) return c->fail(CF_EINVAL, "cf_forward_tiles: Bf * T = %d x %d exceeds max_batch %d", Bf, T, c->max_batch);
+    if ((long long)Bf * T > batch_cap(c))
+        return c->fail(CF_EINVAL, "cf_forward_tiles: Bf * T = %d x %d exceeds max_batch %d%s", Bf, T, batch_cap(c), c->flip ? " (flip test is on: half of max_batch)" : "");
     if (const char* bad = redact_check_planes(format, planes, Bf, in_on_device, pitch0, pitch1)) return c->fail(CF_EINVAL, "cf_forward_tiles: %s", bad);
     if (int r = forward_begin(c, "cf_forward_tiles", Bf * T)) return r;
     const size_t rbytes = (size_t)T * sizeof(cf_tile_rect);
@@ -2047,7 +2089,8 @@ int cf_forward_fit(cf_ctx* c, const cf_fit_opts* o, int format, const cf_yuv_pla
         return CF_EINVAL;
     }
     if (why) return c->fail(CF_EINVAL, "cf_forward_fit: %s", why);
-    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_forward_fit: B=%d exceeds max_batch %d", B, c->max_batch);
+    if (B > batch_cap(c))
+        return c->fail(CF_EINVAL, "cf_forward_fit: B=%d exceeds max_batch %d%s", B, batch_cap(c), c->flip ? " (flip test is on: half of max_batch)" : "");
     cf_fit_geom g{};
     if (fit_geometry(o->anchor, o->upscale, h, w, c->H, c->W, &g)) return c->fail(CF_EINVAL, "cf_forward_fit: no geometry for %d x %d in %d x %d", w, h, c->W, c->H);
     if (int r = forward_begin(c, "cf_forward_fit", B)) return r;
@@ -2563,6 +2606,7 @@ int cf_event_elapsed_ms(cf_ctx* c, int a, int b, float* ms) {
 int cf_profile_forward(cf_ctx* c, const void* in, int in_format, int in_on_device, int B, int K,
                        cf_op_time* out, int cap, int* n_out) {
     if (!c || !out || !n_out) return CF_EINVAL;
+    if (c->flip) return c->fail(CF_ESTATE, "cf_profile_forward while flip test is on (cf_set_flip_test): it times the plan of one batch");
     const void* net_in = nullptr;
     int r = stage_input(c, in, in_format, in_on_device, B, &net_in);
     if (r) return r;
@@ -2638,6 +2682,7 @@ int cf_plan_op(cf_ctx* c, int i, cf_op_info* out) {
 
 int cf_forward_trace(cf_ctx* c, const void* in, int in_format, int in_on_device, int B, int op_index, float* out_nchw) {
     if (!c || !out_nchw) return CF_EINVAL;
+    if (c->flip) return c->fail(CF_ESTATE, "cf_forward_trace while flip test is on (cf_set_flip_test): it runs the plan of one batch");
     if (op_index < 0 || op_index >= (int)c->ops.size()) return c->fail(CF_EINVAL, "cf_forward_trace: op_index %d outside the plan", op_index);
     if (c->ops[op_index].fused_away) return c->fail(CF_EINVAL, "cf_forward_trace: plan entry %d is fused into the next one", op_index);
     const void* net_in = nullptr;

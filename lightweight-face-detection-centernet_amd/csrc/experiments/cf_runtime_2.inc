@@ -48,6 +48,7 @@ static int lane_back_half(cf_ctx* p) {
 int cf_forward_lanes(cf_ctx* cur, cf_ctx* prev, const void* in, int in_format, int in_on_device, int B) {
     if (!cur || cur == prev) return CF_EINVAL;
     if (prev && prev->device != cur->device) return cur->fail(CF_EINVAL, "cf_forward_lanes: both contexts must live on one device");
+    if (cur->flip) return cur->fail(CF_ESTATE, "cf_forward_lanes while flip test is on (cf_set_flip_test): it runs the plan of one batch");
     int r = lane_cuts(cur); if (r) return r;
     if (cur->lane_pending) { r = lane_back_half(cur); if (r) return r; }       // its own earlier batch never got a successor
     const void* net_in = nullptr;

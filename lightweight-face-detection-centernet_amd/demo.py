@@ -55,11 +55,11 @@ def dump_event(detector, images, im_dir, names, save_path):
     return paths
 
 
-def _fit_detector(fit, dtype):
+def _fit_detector(fit, dtype, flip=False):
     """The detector of ``fit=N``: an N x N context that takes a frame of any size letterboxed (``CenterFace.detect_fit``: the aspect
     ratio kept, black padding; no accuracy claim is made for it)."""
     from .centerface import CenterFace
-    return CenterFace(fit, fit, dtype=dtype)
+    return CenterFace(fit, fit, dtype=dtype, flip_test=flip)
 
 
 def anonymize_file(path, out_path, **options):
@@ -67,24 +67,26 @@ def anonymize_file(path, out_path, **options):
     scale, fill, or mode='blur' with shape, radius, scale) and write the result to ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``: sliced
     inference with N x N tiles at native resolution (``CenterFace.detect_tiled``; the image is cropped to even sides), for images much
     larger than N whose small faces a whole-frame resize would lose; the detections are then in image pixels.  ``fit=N``: the image
-    goes letterboxed through an N x N context instead of one built for its size; not together with ``tiled``."""
+    goes letterboxed through an N x N context instead of one built for its size; not together with ``tiled``.  ``flip=True``: the
+    detector runs CenterNet's flip test (``CenterFace(flip_test=True)``: about twice the network time; no accuracy claim is made)."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
     tiled = int(options.pop("tiled", 0) or 0)
     fit = int(options.pop("fit", 0) or 0)
     dtype = options.pop("dtype", "bf16")
+    flip = bool(options.pop("flip", False))
     if fit:
-        detector = _fit_detector(fit, dtype)
+        detector = _fit_detector(fit, dtype, flip)
         options["fit"], options["tiled"] = True, bool(tiled)
     elif tiled:
         from . import ops
         frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
         T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
-        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T)
+        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T, flip_test=flip)
         options["tiled"] = True
     else:
-        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype)
+        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype, flip_test=flip)
     try:
         frames, results = detector.anonymize([frame], **options)
     finally:
@@ -96,24 +98,25 @@ def anonymize_file(path, out_path, **options):
 def annotate_file(path, out_path, **options):
     """demo.py:30-51 (``test_image`` with its drawing loop): read one image file, draw every detection on the device
     (``CenterFace.annotate``: green boxes, red landmark dots, the score as a label; ``options`` as there) and write the result to
-    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``, ``fit=N``: as ``anonymize_file``."""
+    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``, ``fit=N``, ``flip=True``: as ``anonymize_file``."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
     tiled = int(options.pop("tiled", 0) or 0)
     fit = int(options.pop("fit", 0) or 0)
     dtype = options.pop("dtype", "bf16")
+    flip = bool(options.pop("flip", False))
     if fit:
-        detector = _fit_detector(fit, dtype)
+        detector = _fit_detector(fit, dtype, flip)
         options["fit"], options["tiled"] = True, bool(tiled)
     elif tiled:
         from . import ops
         frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
         T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
-        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T)
+        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T, flip_test=flip)
         options["tiled"] = True
     else:
-        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype)
+        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype, flip_test=flip)
     try:
         frames, results = detector.annotate([frame], **options)
     finally:
@@ -122,23 +125,23 @@ def annotate_file(path, out_path, **options):
     return results[0]
 
 
-def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0):
+def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False):
     """Read one image file and write the aligned chip of every detected face, cut from the image at its own resolution
     (``CenterFace.detect_aligned_frames``), to ``out_dir``/<image name>_<k>.png.  Returns (detections, the paths written).
-    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides).  ``fit=N``: as ``anonymize_file``."""
+    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides).  ``fit=N``, ``flip=True``: as ``anonymize_file``."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
     tiled, fit = int(tiled or 0), int(fit or 0)
     if fit:
-        detector = _fit_detector(fit, dtype)
+        detector = _fit_detector(fit, dtype, flip)
     elif tiled:
         from . import ops
         frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
         T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
-        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T)
+        detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T, flip_test=flip)
     else:
-        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype)
+        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype, flip_test=flip)
     try:
         dets, lms, chips = detector.detect_aligned_frames(frame[None], "bgr", size, tiled=bool(tiled), fit=bool(fit) or None)[0]
     finally:
@@ -152,7 +155,7 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0):
 
 
 def main(argv=None):
-    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]]``: print the detections of one image
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]] [--flip]``: print the detections of one image
     file; with ``--draw`` also write the image with every detection drawn into it (boxes, landmark dots and, unless ``--label none``,
     the score); with
     ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``; or blurred: ``--blur [R]``, R = the
@@ -160,7 +163,8 @@ def main(argv=None):
     ``--size`` x ``--size`` chip per face, cut from the image at its own resolution, into DIR; with ``--tiled N`` beside either the
     faces are found by sliced inference over N x N tiles at native resolution; with ``--fit [N]`` (default 640) the image goes through an
     N x N context letterboxed -- its aspect ratio kept, black padding, the detections mapped back into image pixels -- instead of a
-    context built for its size (no accuracy claim is made for it)."""
+    context built for its size (no accuracy claim is made for it); with ``--flip`` the detector runs CenterNet's flip test -- the image and
+    its mirror in one forward, the heads merged on the device -- at about twice the network time (no accuracy claim is made either)."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("image")
@@ -174,6 +178,7 @@ def main(argv=None):
     ap.add_argument("--tiled", type=int, default=0, metavar="N", help="with --anonymize / --chips: detect on overlapping N x N tiles (N a multiple of 32)")
     ap.add_argument("--fit", type=int, nargs="?", const=640, default=0, metavar="N",
                     help="detect through an N x N context with the image letterboxed (N a multiple of 32; default 640)")
+    ap.add_argument("--flip", action="store_true", help="flip test: run the image and its mirror and merge the heads on the device (about twice the network time)")
     ap.add_argument("--chips", metavar="DIR", help="write the aligned chip of every detected face, cut from the image itself, into DIR")
     ap.add_argument("--size", type=int, default=112, help="with --chips: the chip side (a multiple of 4 in [16, 512])")
     ap.add_argument("--draw", metavar="OUT", help="write the image with every detection drawn into it to OUT")
@@ -190,21 +195,21 @@ def main(argv=None):
     if args.anonymize and args.chips:
         ap.error("--anonymize and --chips are separate runs")
     if args.draw:
-        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit)
+        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit, flip=args.flip)
     elif args.chips:
-        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit)
+        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit, flip=args.flip)
     elif args.anonymize and args.blur is not None:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip)
     elif args.anonymize:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip)
     else:
         from .centerface import CenterFace
         frame = imread(args.image)
         if args.fit:
-            detector = _fit_detector(args.fit, "bf16")
+            detector = _fit_detector(args.fit, "bf16", args.flip)
             dets, _ = detector.detect_fit(frame[None])[0]
         else:
-            detector = CenterFace(frame.shape[0], frame.shape[1], dtype="bf16")
+            detector = CenterFace(frame.shape[0], frame.shape[1], dtype="bf16", flip_test=args.flip)
             dets, _ = detector(frame)
         detector.close()
     print(format_wider_result(args.image, dets), end="")

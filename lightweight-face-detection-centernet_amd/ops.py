@@ -413,6 +413,40 @@ def unfit_rows(frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, anc
     return od, ol, oc, fl
 
 
+def mirror_batch(x, device=0):
+    """The mirror kernel of the flip test (``cf_op_mirror``): ``x`` uint8 [B, H, W, 3] or float32 [B, 3, H, W] with W a multiple of 32 ->
+    the same batch with the columns of every image reversed (whole pixels), written on the device as the flip forward writes the
+    second half of its 2B input."""
+    x = np.ascontiguousarray(x)
+    if x.dtype == np.uint8:
+        if x.ndim != 4 or x.shape[3] != 3:
+            raise ValueError("uint8 input must be [B, H, W, 3], got %s" % (x.shape,))
+        fmt, (B, H, W) = _lib.CF_IN_U8_HWC_BGR, x.shape[:3]
+    else:
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 4 or x.shape[1] != 3:
+            raise ValueError("float input must be [B, 3, H, W], got %s" % (x.shape,))
+        fmt, (B, H, W) = _lib.CF_IN_F32_NCHW, (x.shape[0], x.shape[2], x.shape[3])
+    out = np.empty_like(x)
+    _lib.check(_lib.lib().cf_op_mirror(device, fmt, ptr(x), B, H, W, ptr(out)), op=True)
+    return out
+
+
+def flip_heads(records, B, device=0):
+    """The merge kernel of the flip test (``cf_op_flip_heads``): ``records`` float32 [2B, h, w, 16] head records, the B unmirrored
+    images first, then their mirrored passes -> (records [B, h, w, 16], hm_plane [B, h*w]) by the statement under ``cf_set_flip_test`` in
+    include/centerface_hip.h (heat and wh averaged, landmark x negated with the point pairs 0 <-> 1 and 3 <-> 4 swapped, reg of the
+    unmirrored pass)."""
+    r = np.ascontiguousarray(records, dtype=np.float32)
+    B = int(B)
+    if r.ndim != 4 or r.shape[3] != 16 or r.shape[0] != 2 * B:
+        raise ValueError("records must be [2B, h, w, 16] with B=%d, got %s" % (B, r.shape))
+    h, w = r.shape[1:3]
+    out, plane = np.empty((B, h, w, 16), np.float32), np.empty((B, h * w), np.float32)
+    _lib.check(_lib.lib().cf_op_flip_heads(device, ptr(r), B, h, w, ptr(out), ptr(plane)), op=True)
+    return out, plane
+
+
 def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=None, device=0, **opts):
     """The tracker's update over a whole sequence (``cf_op_track``) with a fresh tracker: boxes [F, S, rows, 4], scores [F, S, rows], lms
     [F, S, rows, 10], counts [F, S] -- frame f of stream s has the rows below min(count, rows), in whatever coordinates they are.

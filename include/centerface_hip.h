@@ -705,6 +705,78 @@ int cf_scene_forget(cf_scene* scn, int stream);
 int cf_scene_check(cf_ctx* ctx, cf_scene* scn, cf_tracker* trk, int stream0, int B, int format, const cf_planes_rw* frames,
                    int on_device, int h, int w, int pitch0, int pitch1, int32_t* out, int out_on_device);
 
+/* ---- lookback: cover faces in the frames BEFORE their first detection -----------------------------------------------------------
+ * cf_track_update, cf_track_follow and cf_scene_check close holes that lie behind a detection.  The hole in front of it is still open: a
+ * face that enters the picture, turns to the camera or comes into focus is visible for several frames before it first scores above the
+ * threshold, and those frames go out uncovered.  The tracker knows only the past, and a tentative track is never held (min_hits): an
+ * onset that flickers hit, miss, hit leaves the middle frame bare.  A cf_lookback delays the output by `depth` frames and paints a
+ * track's first box backwards: it keeps the last frames' tracked rows per stream on the device and hands out the rows of the frame
+ * `depth` steps back PLUS the first boxes of every track born since, grown by the distance:
+ *   ... -> cf_track_update [-> cf_track_follow] -> cf_lookback_step -> cf_redact_faces | cf_blur_faces | cf_draw_faces (ON THE FRAME OF
+ *   `depth` STEPS AGO, which the caller keeps)
+ * No row, count or code crosses to the host.  The defaults the Python layer uses (depth 8, grow 0.05, confirm 1) are this project's
+ * choices: there is no labelled video here, nobody has measured them, and no accuracy claim is made.
+ *
+ * A cf_lookback holds n_streams independent streams on one device.  A stream holds: a queue of at most depth + 1 entries, oldest first;
+ * max_id, seq_next, pending_cut, all 0 at first.  An entry holds seq, cut, n and n rows; a row holds box[4], score, lms[10] (float32),
+ * id, hits, misses (int32) and born.  One step of stream s (image b of the call):
+ *   1. Push, when push != 0.  n = min(max(count, 0), the stride of the pushed rows, rows).  A new entry takes the image's tracked rows
+ *      i < n bit for bit: dets, lms and info = id, hits, misses as step 5 of cf_track_update or cf_track_follow left them.  seq =
+ *      seq_next++.  cut = pending_cut || (scene codes given && code[b][0] != CF_SCENE_SAME); then pending_cut = 0.  born[i] = id[i] >
+ *      max_id with max_id as it was before this step; then max_id becomes the largest id seen.  The entry is appended.
+ *   2. Emit.  After a push: when the queue holds depth + 1 entries.  Without a push (a drain): when the queue is not empty.  Otherwise
+ *      nothing is emitted: counts[b] = 0 and state[b] = -1, 0, 0, 0.
+ *   3. An emit takes the oldest entry t out of the queue; e_1 .. e_m (m <= depth) are the entries that remain, oldest first.
+ *      Own rows.  The output rows k < n_t are t's rows, bit for bit, in order.
+ *      Back-filled rows.  For j = 1 .. m in order, STOPPING at the first e_j with cut set (it and everything behind it belong to another
+ *      scene; a cut on t itself stops nothing): the rows i of e_j in row order with born set are eligible when (a) their four corners
+ *      are finite and (b) their id occurs in at least `confirm` of the entries e_j .. e_m, counted up to but not including the next
+ *      entry with cut set.  While fewer than `rows` rows are written an eligible row is appended; otherwise it is DROPPED and bit 0 of
+ *      the flags is set: THAT FACE IS NOT COVERED IN THIS FRAME.  The appended row: the box grown about its centre in float64 by g = 1.0
+ *      + (double)grow * (double)j -- cx = ((double)x1 + (double)x2) * 0.5; hw = ((double)x2 - (double)x1) * 0.5 * g; x1' = (float)(cx -
+ *      hw), x2' = (float)(cx + hw); y likewise (the order of the tracker's held rows, no contraction) --, score and landmarks as
+ *      stored, info = id, 0, j.  THE LANDMARKS OF A BACK-FILLED ROW ARE THOSE OF THE TRACK'S FIRST FRAME (not grown, not moved), and so
+ *      is the box's place: the face is covered where it was FIRST SEEN, j frames later.  With hits = 0 and misses = j > 0
+ *      cf_draw_faces draws the row as a held one and the best-shot offer never scores it.
+ *      state[b] = seq_t, n_t, rows appended, flags.
+ * On the device: one launch per step, one workgroup per stream; the queue is a rotating array whose head and fill live in device
+ * memory (80 bytes per row, (depth + 1) * rows rows per stream). */
+typedef struct cf_lookback cf_lookback;
+typedef struct cf_lookback_opts {
+    int32_t depth;        /* 1..32 frames of delay */
+    int32_t rows;         /* 1..1024: capacity of an entry AND of an output image; the stride of every output table */
+    float   grow;         /* finite, 0..1 per frame of distance */
+    int32_t confirm;      /* 1..depth + 1 queued frames that must show a new id before it is back-filled (at most depth entries are
+                           * counted, e_j .. e_m: depth + 1 is never met and back-fills nothing) */
+} cf_lookback_opts;
+/* ctx names the device (and carries the error text); 1..4096 streams.  CF_EINVAL for a bad option or count before any GPU work (ctx ==
+ * NULL: the arguments are still checked first, cf_op_last_error names the cause); CF_ENOMEM when the queues do not fit.  *out is written
+ * on success only. */
+int cf_lookback_create(cf_ctx* ctx, int n_streams, const cf_lookback_opts* opts, cf_lookback** out);
+/* Waits for the object's last step, then frees it.  NULL: CF_OK. */
+int cf_lookback_destroy(cf_lookback* lb);
+/* Sets pending_cut of `stream` (-1: of every stream): nothing pushed later is painted back into what is queued now.  For callers that
+ * reset tracks themselves (cf_track_reset).  Ordered like cf_track_reset: behind the steps issued so far, before those issued later.
+ * CF_EINVAL for a stream outside -1 .. n_streams - 1. */
+int cf_lookback_forget(cf_lookback* lb, int stream);
+/* One step of the streams stream0 .. stream0 + B - 1 (image b is stream stream0 + b).  push != 0: ctx must hold tracked rows that no step
+ * has consumed -- the tracked rows behind a cf_track_update or the followed rows behind a cf_track_follow -- of B images, else CF_ESTATE;
+ * a second push behind the same rows is CF_ESTATE (time would advance twice).  push == 0 (a drain, the end of the video) needs no
+ * forward, only an object that was pushed into before (CF_ESTATE otherwise: its rows have no coordinate space yet).  scene: [B][4]
+ * exactly as cf_scene_check wrote it (scene_on_device: a device buffer, read on ctx's stream; else a host table, copied up before the call returns), or NULL.
+ * The object latches the row space -- (not tiled, H, W) or (tiled, h, w) -- and the stride of the pushed rows (<= rows) on its first push;
+ * another space or stride later is CF_EINVAL.  CF_EINVAL also, before any GPU work, for B outside 1..max_batch, a stream range outside
+ * the object and an object of another device (ctx == NULL: B is still checked first, cf_op_last_error names the cause).
+ * dets [B][rows][5], lms [B][rows][10], info [B][rows][3], counts [B], state [B][4]; any may be NULL; out_on_device as for
+ * cf_track_update (host buffers block; rows at and past the largest count of the batch are not written).
+ * After a successful step, and until the next forward, upload, threshold decode, merge, update or follow on ctx, cf_redact_faces,
+ * cf_blur_faces, cf_draw_faces and cf_align_faces_frame take the LOOKBACK ROWS, with the step's B and the latched space: GIVE THEM THE
+ * FRAMES OF `depth` STEPS AGO.  cf_align_faces, cf_merge_tiles, cf_unfit_rows and the refusal of a second cf_track_update behave as
+ * before.  The rows live in buffers owned by the CONTEXT, the queues in the object: a ring of contexts can share one object; it keeps one
+ * event and orders its steps across contexts exactly as a tracker orders its updates. */
+int cf_lookback_step(cf_ctx* ctx, cf_lookback* lb, int stream0, int B, int push, const int32_t* scene, int scene_on_device,
+                     float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* state, int out_on_device);
+
 /* ---- best-shot selection: each track's sharpest chip, kept on the device -----------------------------------------------------
  * cf_track_update / cf_track_follow give every face an identity, cf_align_faces_frame cuts a chip of every tracked row: a track that
  * lives 200 frames yields 200 chips.  A cf_bestshot table is offered the chips of each frame, scores them, and keeps PER TRACK ID the
@@ -1201,6 +1273,16 @@ int cf_op_follow(int device, const cf_track_opts* opts, const cf_follow_opts* fo
  * nothing is written on refusal. */
 int cf_op_scene(int device, const cf_scene_opts* opts, int n_streams, int n_frames, int format, const cf_planes_rw* frames, int h, int w,
                 int pitch0, int pitch1, int32_t* out, int32_t* sigs);
+/* The kernel of cf_lookback_step over a whole sequence of host tables, with a fresh cf_lookback of n_streams streams: step f is a push of
+ * the streams 0 .. S - 1 when push[f] != 0 -- the rows i < counts_in[f][s] of dets_in [F][S][rows_in][5], lms_in [F][S][rows_in][10],
+ * info_in [F][S][rows_in][3] --, else a drain.  cuts [F][S] (or NULL): bit 0 = the scene code of the pushed frame is CF_SCENE_CUT (else
+ * CF_SCENE_SAME), bit 1 = a cf_lookback_forget of the stream comes before the step.  After each step: dets [F][S][rows][5], lms
+ * [F][S][rows][10], info [F][S][rows][3], counts [F][S], state [F][S][4]; rows at and past a count keep the caller's bytes.  All other
+ * pointers host, none NULL.  The option and count checks of cf_lookback_create, n_steps >= 1, 1 <= rows_in <= opts->rows and
+ * n_steps * n_streams * rows <= 2^24, before any device is touched; nothing is written on refusal. */
+int cf_op_lookback(int device, const cf_lookback_opts* opts, int n_streams, int n_steps, int rows_in, const uint8_t* push,
+                   const float* dets_in, const float* lms_in, const int32_t* info_in, const int32_t* counts_in, const int32_t* cuts,
+                   float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* state);
 /* The scoring kernel of cf_bestshot_offer alone, on host tables: chips [n][S][S][3] uint8, boxes [n][4], scores [n], lms [n][10]
  * (n in 1..65536; every row counts and is eligible) -> quality [n] int64, parts [n][4] int32 = sharp, size_w, pose_w, score_w.  fx, fy
  * finite and > 0.  Every bad argument is CF_EINVAL with a cf_op_last_error that names it, before any device is touched. */

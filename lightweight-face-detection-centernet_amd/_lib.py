@@ -58,6 +58,7 @@ EXPORTS = (
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_follow", "cf_op_follow",
     "cf_scene_create", "cf_scene_destroy", "cf_scene_forget", "cf_scene_check", "cf_op_scene",
+    "cf_lookback_create", "cf_lookback_destroy", "cf_lookback_forget", "cf_lookback_step", "cf_op_lookback",
     "cf_bestshot_create", "cf_bestshot_destroy", "cf_bestshot_offer", "cf_bestshot_collect", "cf_op_chip_quality", "cf_op_bestshot",
 )
 
@@ -273,6 +274,18 @@ def scene_opts(hist=350, grid=640):
     """SceneOpts (the library validates the numbers).  The defaults are this project's choices: there is no labelled video here, nobody
     has measured them, and no accuracy claim is made for them."""
     return SceneOpts(int(hist), int(grid))
+
+
+class LookbackOpts(C.Structure):
+    """cf_lookback_opts: frames of delay / rows of an entry and of an output image / growth of a back-filled box per frame of distance /
+    queued frames that must show a new id before it is back-filled."""
+    _fields_ = [("depth", C.c_int32), ("rows", C.c_int32), ("grow", C.c_float), ("confirm", C.c_int32)]
+
+
+def lookback_opts(depth=8, rows=256, grow=0.05, confirm=1):
+    """LookbackOpts (the library validates the numbers).  The defaults are this project's choices: there is no labelled video here, nobody
+    has measured them, and no accuracy claim is made for them."""
+    return LookbackOpts(int(depth), int(rows), float(grow), int(confirm))
 
 
 CF_BEST_SIZE, CF_BEST_POSE, CF_BEST_SCORE = 1, 2, 4
@@ -554,6 +567,11 @@ def lib():
         L.cf_scene_forget.argtypes = [C.c_void_p, C.c_int]
         L.cf_scene_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + [C.c_void_p, C.c_int]
         L.cf_op_scene.argtypes = [C.c_int, C.POINTER(SceneOpts), C.c_int, C.c_int, C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 4 + [C.c_void_p] * 2
+        L.cf_lookback_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(LookbackOpts), C.POINTER(C.c_void_p)]
+        L.cf_lookback_destroy.argtypes = [C.c_void_p]
+        L.cf_lookback_forget.argtypes = [C.c_void_p, C.c_int]
+        L.cf_lookback_step.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
+        L.cf_op_lookback.argtypes = [C.c_int, C.POINTER(LookbackOpts)] + [C.c_int] * 3 + [C.c_void_p] * 11
         L.cf_bestshot_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(BestShotOpts), C.POINTER(C.c_void_p)]
         L.cf_bestshot_destroy.argtypes = [C.c_void_p]
         L.cf_bestshot_offer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int]

@@ -611,19 +611,20 @@ class Engine(object):
                                           vp(dets_ptr), vp(lms_ptr), vp(info_ptr), vp(counts_ptr), vp(moves_ptr), 1))
 
     # -- scene cuts --------------------------------------------------------------------------------
-    def scene_check(self, frames, fmt, scenes, tracker=None, stream0=0, *, codes=True):
+    def scene_check(self, frames, fmt, scenes, tracker=None, stream0=0, *, codes=True, out_ptr=None):
         """Does frame b continue stream ``stream0 + b`` of ``scenes`` (a ``SceneCuts``)?  (``cf_scene_check``, host form; the statement is
         in ``include/centerface_hip.h``.)  Host frames as ``redact_faces`` takes them, only read, of an even size of at least 8 x 8; no
         forward is needed and the rows this engine holds stay as they are.  With ``tracker`` the tracks of every stream that is CUT are
         freed on the device, as ``Tracker.reset`` frees them: CALL IT BEFORE the frame's ``track_update`` or ``track_follow``.  Returns
         int32 [B, 4] = code (``_lib.CF_SCENE_FIRST`` / ``_SAME`` / ``_CUT``), hist (per mille of pixels that changed luma bin), grid (sum
         of the 64 cell-mean differences), run (SAME checks in a row) and blocks; ``codes=False`` reads nothing back and returns None.
-        A flash is reported as a cut, a dissolve is not one cut; the thresholds are this project's choices, no accuracy claim is made."""
+        A flash is reported as a cut, a dissolve is not one cut; the thresholds are this project's choices, no accuracy claim is made.
+        ``out_ptr``: a DEVICE int32 [B, 4] buffer that takes the codes instead (for ``lookback_step``); nothing is read back, returns None."""
         args, keep = _lib.host_frame_args(frames, fmt, writable=False)
         f, tab, dev, B, h, w, pitch0, pitch1 = args
-        out = np.zeros((B, 4), np.int32) if codes else None
+        out = np.zeros((B, 4), np.int32) if codes and not out_ptr else None
         self._chk(self._L.cf_scene_check(self._h, scenes._handle(self), tracker._handle(self) if tracker is not None else None, int(stream0), B, f, tab,
-                                         dev, h, w, pitch0, pitch1, _lib.ptr(out), 0))
+                                         dev, h, w, pitch0, pitch1, C.c_void_p(int(out_ptr)) if out_ptr else _lib.ptr(out), 1 if out_ptr else 0))
         del keep
         return out
 
@@ -634,6 +635,38 @@ class Engine(object):
         f, tab, dev, B, h, w, pitch0, pitch1 = _lib.device_frame_args("scene_check_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1)
         self._chk(self._L.cf_scene_check(self._h, scenes._handle(self), tracker._handle(self) if tracker is not None else None, int(stream0), B, f, tab,
                                          dev, h, w, pitch0, pitch1, C.c_void_p(int(out_ptr)) if out_ptr else None, 1))
+
+    # -- lookback: cover faces in the frames before their first detection ---------------------------
+    def lookback_step(self, lb, stream0=0, B=None, push=True, scene=None):
+        """One step of the streams ``stream0 .. stream0 + B - 1`` of ``lb`` (a ``Lookback``; default: all from ``stream0`` on)
+        (``cf_lookback_step``, host form; the statement is in ``include/centerface_hip.h``).  ``push=True``: the tracked rows this engine
+        holds behind a ``track_update`` or ``track_follow`` of B images enter the delay line, image b as the next frame of stream
+        ``stream0 + b``; ``scene``: the int32 [B, 4] codes ``scene_check`` returned for these frames -- or the address of a DEVICE buffer
+        it wrote them to --, or None.  ``push=False``: a drain, for the end of the video; no forward is needed.  Returns (dets [B,R,5],
+        lms [B,R,10], info [B,R,3] = id, hits, misses, counts [B], state [B,4] = seq, own rows, back-filled rows, flags), R = ``lb.rows``,
+        rows below counts[b] valid: the tracked rows of the frame ``depth`` steps back plus the first boxes of the tracks born since (hits
+        0, misses = the distance, the box grown by ``grow`` per frame).  state[b, 0] == -1: the stream is still warming up (or drained)
+        and nothing is due.  Until the next forward, decode, merge, update or follow on this engine ``redact_faces`` / ``blur_faces`` /
+        ``draw_faces`` / ``align_faces_frame`` use these rows: GIVE THEM THE FRAMES OF ``depth`` STEPS AGO."""
+        B = lb.streams - int(stream0) if B is None else int(B)
+        n, R = max(B, 0), lb.rows
+        dets, lms, info = np.zeros((n, R, 5), np.float32), np.zeros((n, R, 10), np.float32), np.zeros((n, R, 3), np.int32)
+        counts, state = np.zeros((n,), np.int32), np.zeros((n, 4), np.int32)
+        on_dev = scene is not None and not isinstance(scene, np.ndarray)
+        sc = C.c_void_p(int(scene)) if on_dev else _lib.ptr(None if scene is None else np.ascontiguousarray(scene, dtype=np.int32).reshape(n, 4))
+        self._chk(self._L.cf_lookback_step(self._h, lb._handle(self), int(stream0), B, 1 if push else 0, sc, 1 if on_dev else 0, _lib.ptr(dets),
+                                           _lib.ptr(lms), _lib.ptr(info), _lib.ptr(counts), _lib.ptr(state), 0))
+        return dets, lms, info, counts, state
+
+    def lookback_step_device(self, lb, stream0, B, push=True, scene_ptr=None, dets_ptr=None, lms_ptr=None, info_ptr=None, counts_ptr=None,
+                             state_ptr=None):
+        """Same, reading the scene codes from the DEVICE buffer ``scene_check_device`` wrote (or None) and writing caller-owned DEVICE
+        buffers (dets [B,R,5], lms [B,R,10] float32, info [B,R,3], counts [B], state [B,4] int32; any may be None): asynchronous on the
+        engine's main stream behind the last step of ``lb``; no row, count or code is read on the host.  The context keeps the lookback
+        rows either way."""
+        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
+        self._chk(self._L.cf_lookback_step(self._h, lb._handle(self), int(stream0), int(B), 1 if push else 0, vp(scene_ptr), 1, vp(dets_ptr), vp(lms_ptr),
+                                           vp(info_ptr), vp(counts_ptr), vp(state_ptr), 1))
 
     # -- best-shot selection: each track's sharpest chip ---------------------------------------------
     def bestshot_offer(self, shots, chips, offsets, hw, stream0=0):
@@ -913,6 +946,86 @@ class SceneCuts(object):
     def close(self):
         if getattr(self, "_h", None):
             self._L.cf_scene_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Lookback(object):
+    """One cf_lookback: a delay line of ``depth`` frames for ``streams`` independent video streams on one GPU (``include/centerface_hip.h``
+    states the step).  ``engine_or_device``: an ``Engine`` (created at once on its GPU) or a device index (created by the first
+    ``Engine.lookback_step`` that uses it, which must be on that GPU).  A frame leaves the line ``depth`` steps after it entered, with its
+    own tracked rows plus the first box of every track born in the meantime -- seen in at least ``confirm`` of the queued frames --,
+    grown by ``grow`` of its size per frame of distance: the face is covered BEFORE its first detection, where it was first detected
+    (the box is not moved).  ``rows``: the most rows of a frame, pushed or emitted; a surplus of back-filled rows is DROPPED (state flag
+    bit 0): those faces are not covered in that frame.  A scene cut (``scene=`` of the step, or ``forget``) is never painted across.  The
+    defaults are this project's choices: there is no labelled video here, nobody has measured them, and no accuracy claim is made.
+    Engines of one GPU may share an object: its steps are ordered in call order.  For the product paths (``CenterFace.anonymize(...,
+    lookback=)``) the object also keeps, per stream, the host copies of the source frames that are still in the line."""
+
+    def __init__(self, engine_or_device, streams, depth=8, rows=256, grow=0.05, confirm=1):
+        self._L = _lib.lib()
+        self._o = _lib.lookback_opts(depth, rows, grow, confirm)
+        self.streams, self.depth, self.rows = int(streams), int(depth), int(rows)
+        self._h = None
+        self._frames = [[] for _ in range(max(self.streams, 0))]             # per stream: the retained source frames, oldest first
+        self._codes = None                                                    # (engine, device address): the scene codes of a chunk
+        if isinstance(engine_or_device, Engine):
+            self.device = engine_or_device.device
+            self._handle(engine_or_device)
+        else:
+            self.device = int(engine_or_device)
+            # refuse bad options now, not at the first step (no context: the library checks the arguments and tells)
+            out = C.c_void_p()
+            self._L.cf_lookback_create(None, self.streams, C.byref(self._o), C.byref(out))
+            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
+            if "null context" not in why:
+                raise _lib.CenterFaceValueError(-1, why)
+
+    def _handle(self, engine):
+        """The cf_lookback, created with ``engine``'s context on first use."""
+        if self._h is None:
+            if engine.device != self.device:
+                raise ValueError("the lookback object was made for device %d, the engine runs on device %d" % (self.device, engine.device))
+            out = C.c_void_p()
+            _lib.check(self._L.cf_lookback_create(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
+            self._h = out
+        return self._h
+
+    def fill(self, stream):
+        """The number of source frames of ``stream`` the product paths still hold (0 .. depth)."""
+        return len(self._frames[stream])
+
+    def _scene_codes(self, engine):
+        """A device buffer of this object for the scene codes of one chunk of ``engine`` (int32 [max_batch, 4])."""
+        if self._codes is None or self._codes[0] is not engine:
+            self._free_codes()
+            self._codes = (engine, engine.device_alloc(16 * engine.max_batch))
+        return self._codes[1]
+
+    def _free_codes(self):
+        if self._codes is not None:
+            engine, p = self._codes
+            self._codes = None
+            if getattr(engine, "_h", None):
+                engine.device_free(p)
+
+    def forget(self, stream=-1):
+        """Nothing pushed from now on is painted back into the frames of ``stream`` (-1: of every stream) that are queued now: for callers
+        that reset the tracks themselves (``Tracker.reset``).  The queued frames still come out."""
+        if not -1 <= int(stream) < self.streams:
+            raise ValueError("stream %d of a lookback object with %d" % (stream, self.streams))
+        if self._h is not None:
+            _lib.check(self._L.cf_lookback_forget(self._h, int(stream)), op=True)
+
+    def close(self):
+        self._free_codes()
+        if getattr(self, "_h", None):
+            self._L.cf_lookback_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -1234,8 +1347,47 @@ class CenterFace(object):
             raise ValueError("scenes= needs tracker=")
         return scenes, frames, fmt
 
+    def _lookback(self, lookback, flush, tracker, n):
+        """The ``lookback`` / ``flush`` arguments of the product paths -> the ``lookback`` of ``_drive``: None, or (lookback, flush, ready)
+        with ``ready`` the n lists the call returns.  Needs a tracker, and the n streams of the call at one fill level: otherwise one
+        step would be due for some of its images and not for others.  Refused before any engine call."""
+        if lookback is None:
+            if flush:
+                raise ValueError("flush= needs lookback=")
+            return None
+        if tracker is None:
+            raise ValueError("lookback= needs tracker=")
+        if n > lookback.streams:
+            raise ValueError("%d images for a lookback object with %d streams" % (n, lookback.streams))
+        fills = [lookback.fill(k) for k in range(n)]
+        if len(set(fills)) > 1:
+            raise ValueError("the streams of this call stand at different fill levels of the lookback object: %s" % (fills,))
+        return lookback, bool(flush), [[] for _ in range(n)]
+
+    def _lookback_redact(self, lookback, flush, tracker, redact, n):
+        """``_lookback`` for ``detect_tiled`` / ``detect_fit``, where it needs ``redact=``: without it there is nothing to delay."""
+        if lookback is not None and redact is None:
+            raise ValueError("lookback= needs redact=")
+        return self._lookback(lookback, flush, tracker, n)
+
+    def _lookback_out(self, eng, lb, i, rows, cover, draw, ready):
+        """Behind a step of the streams i .. i + B - 1: where a frame became due, the retained copies of those frames are covered or
+        drawn with the lookback rows the engine holds, and (frame, dets, lms, info) joins ``ready`` per stream."""
+        dets, lms, info, counts, state = rows
+        B = len(counts)
+        if not (state[:, 0] >= 0).any():
+            return
+        due = np.stack([lb._frames[i + b].pop(0) for b in range(B)])         # (the streams of a call stand at one fill level: all are due)
+        if cover is not None:
+            eng.cover_faces(due, cover[1], **cover[2])
+        if draw is not None:
+            eng.draw_faces(due, draw[1], **draw[2])
+        for b in range(B):
+            n = int(counts[b])
+            ready[i + b].append((due[b], dets[b, :n].copy(), lms[b, :n].copy(), info[b, :n].copy()))
+
     def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None, follow=None, detect=True, best=None,
-               scene=None):
+               scene=None, lookback=None):
         """The chunk loop of every product path: ``forward`` enqueues ``frames`` in slices of ``per`` (default ``max_batch``), each is
         decoded, and while the engine still holds it the steps that were asked for run in this order: ``tracker`` is advanced -- image b
         of the chunk that starts at frame i continues its stream i + b --, ``cover`` = (array, fmt, options) has the chunk's slice of
@@ -1253,8 +1405,12 @@ class CenterFace(object):
         for scene cuts (``Engine.scene_check`` with the tracker, stream i + b), which frees the tracks of the cut streams on the device.
         With ``detect=True`` no code is read on the host.  With ``detect=False`` the codes are read (B x 4 ints per chunk), and a chunk in
         which any frame is FIRST or CUT becomes a key frame: forward, decode (merge), update, then the follow it would have had -- the new
-        scene's faces are detected and covered in that same frame; its results are still the followed rows.  Returns the per-frame
-        results."""
+        scene's faces are detected and covered in that same frame; its results are still the followed rows.  ``lookback`` = (lookback,
+        flush, ready): behind the update and the follow the chunk's slice of the ``cover`` / ``draw`` array is retained by the
+        ``Lookback`` and its tracked rows are pushed (``Engine.lookback_step``, stream i + b; with ``scene`` and ``detect=True`` the
+        chunk's scene codes go from the check to the step in a device buffer); the frames that become due -- the retained ones of
+        ``depth`` calls ago, not this chunk's -- are covered or drawn instead of the chunk's and join ``ready``; with ``flush`` the streams
+        are drained after the loop.  Returns the per-frame results."""
         eng, out = self.engine, []
         per = per or eng.max_batch
         if merge is None and detect:
@@ -1262,7 +1418,10 @@ class CenterFace(object):
         try:
             for i in range(0, len(frames), per):
                 key = detect
-                if scene is not None:
+                if scene is not None and lookback is not None and detect:
+                    codes = lookback[0]._scene_codes(eng)
+                    eng.scene_check(scene[1][i:i + per], scene[2], scene[0], tracker, i, codes=False, out_ptr=codes)
+                elif scene is not None:
                     codes = eng.scene_check(scene[1][i:i + per], scene[2], scene[0], tracker, i, codes=not detect)
                     key = detect or bool((codes[:, 0] != _lib.CF_SCENE_SAME).any())
                 if key:
@@ -1290,16 +1449,29 @@ class CenterFace(object):
                     part = best[1][i:i + per]
                     cut, offs, _ = eng.align_faces_frame(part, best[2], best[0].size, template=best[3])
                     eng.bestshot_offer(best[0], cut, offs, _lib.frame_planes(part, best[2], writable=False)[2:4], i)
-                if cover is not None:
-                    eng.cover_faces(cover[0][i:i + per], cover[1], **cover[2])
-                if draw is not None:
-                    eng.draw_faces(draw[0][i:i + per], draw[1], **draw[2])
+                if lookback is not None:
+                    lb, part = lookback[0], (cover if cover is not None else draw)[0][i:i + per]
+                    for b in range(len(part)):
+                        lb._frames[i + b].append(part[b])
+                    rows = eng.lookback_step(lb, i, len(part), push=True, scene=codes if scene is not None else None)
+                    self._lookback_out(eng, lb, i, rows, cover, draw, lookback[2])
+                else:
+                    if cover is not None:
+                        eng.cover_faces(cover[0][i:i + per], cover[1], **cover[2])
+                    if draw is not None:
+                        eng.draw_faces(draw[0][i:i + per], draw[1], **draw[2])
                 if chips is not None:
                     cut, offs, _ = chips(i, i + per)
                     res = [(d, l, cut[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(res)]
                 out.extend(res)
             if best is not None and len(frames):
                 best[5].append(eng.bestshot_collect(best[0], 0, len(frames), flush=best[4]))
+            if lookback is not None and lookback[1]:
+                lb = lookback[0]
+                while len(frames) and lb.fill(0) > 0:                            # the end of the video: one drain per frame still in the line
+                    for i in range(0, len(frames), per):
+                        B = min(per, len(frames) - i)
+                        self._lookback_out(eng, lb, i, eng.lookback_step(lb, i, B, push=False), cover, draw, lookback[2])
         finally:
             if merge is None and detect:
                 eng.set_rescale(0.0, 0.0)
@@ -1374,24 +1546,27 @@ class CenterFace(object):
         return self._tiled_form(frames, fmt, tile, overlap, True, writable) + (("ios", 0.5, 2.0),)
 
     def detect_fit(self, frames, fmt="bgr", *, anchor="center", upscale=True, fill=(0, 0, 0), redact=None, tracker=None, follow=None, detect=True,
-                   scenes=None):
+                   scenes=None, lookback=None, flush=False):
         """Detection of frames of another size -- or shape -- than the network input WITHOUT the stretch of ``detect_batch``: every frame
         is resized on the device with its aspect ratio kept and pasted into the network's canvas (``Engine.forward_fit_enqueue``:
         ``anchor``, ``upscale``, ``fill``), and the rows whose centre lies in the content are mapped back (``Engine.unfit_rows``).
         ``frames``: BGR uint8 [B,h,w,3] (``fmt='bgr'``; odd sides allowed), dense 4:2:0 uint8 [B, h*3//2, w], or per-frame plane tuples.
         Returns (dets [n,5], lms [n,10]) per frame (``dets`` alone without landmarks), in FRAME pixels, not floor-divided.  No accuracy
         claim is made: there are no trained weights and no labelled set here; the reference's data pipeline fits and pads likewise
-        (dataset/dataset.py:114-134).  ``redact``, ``tracker``, ``follow``, ``detect`` and ``scenes``: as ``detect_tiled``."""
+        (dataset/dataset.py:114-134).  ``redact``, ``tracker``, ``follow``, ``detect``, ``scenes``, ``lookback`` and ``flush``: as
+        ``detect_tiled``."""
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         fit = self._fit_options(dict(anchor=anchor, upscale=upscale, fill=fill))
         forward, per, merge = self._frame_form(frames, fmt, None, None, fit, redact is not None)
-        return self._drive(frames, forward, per, merge=merge, tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
-                           follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
-                           scene=self._scene(scenes, tracker, frames, fmt))
+        look = self._lookback_redact(lookback, flush, tracker, redact, len(frames))
+        res = self._drive(frames, forward, per, merge=merge, tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
+                          follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
+                          scene=self._scene(scenes, tracker, frames, fmt), **({} if look is None else {"lookback": look}))
+        return res if look is None else look[2]
 
     def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None,
-                     tracker=None, follow=None, detect=True, scenes=None):
+                     tracker=None, follow=None, detect=True, scenes=None, lookback=None, flush=False):
         """Sliced inference for frames much larger than the network input, whose small faces the stretch-resize of ``detect_batch``
         loses: every frame is cut on the device into overlapping tiles of ``tile`` (default: the network's (H, W)) that share at
         least ``overlap`` pixels (default: a quarter of the tile, rounded down to even), plus the whole frame as one more tile; the
@@ -1404,15 +1579,19 @@ class CenterFace(object):
         stream k the k-th frame of this call continues (frame pixels): it is advanced behind the merge, and the redaction then covers
         the tracked rows -- the merged detections plus the tracks held through a dropout; the detections returned stay the frame's
         own.  ``follow``, ``detect`` and ``scenes``: as ``anonymize`` (``redact=`` only; the frames are checked and followed as they are before the
-        redaction)."""
+        redaction).  ``lookback`` and ``flush`` (``redact=`` and an array of frames only): as ``anonymize`` -- the frames are then NOT
+        redacted in place, the return is the lists of ``anonymize(lookback=)``."""
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
-        return self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, with_full, redact is not None), merge=(metric, thresh, edge),
-                           tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
-                           follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
-                           scene=self._scene(scenes, tracker, frames, fmt))
+        look = self._lookback_redact(lookback, flush, tracker, redact, len(frames))
+        res = self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, with_full, redact is not None), merge=(metric, thresh, edge),
+                          tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
+                          follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
+                          scene=self._scene(scenes, tracker, frames, fmt), **({} if look is None else {"lookback": look}))
+        return res if look is None else look[2]
 
-    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, **options):
+    def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None,
+                  flush=False, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
         cell, scale, fill) or, with ``mode='blur'``, blurred (``Engine.blur_faces``; shape, radius, scale), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
@@ -1433,35 +1612,56 @@ class CenterFace(object):
         "detect only where a scene starts".  A flash counts as a cut, a dissolve is not one; the thresholds are this project's choices, no
         accuracy claim is made.  ``fit``: True, or a dict with anchor, upscale and / or fill: detection by ``detect_fit`` on frames of
         any size -- letterboxed instead of stretched --, redaction with the rows mapped back, which are in frame pixels; not together
-        with ``tiled``; no accuracy claim is made for it either.  With the defaults every call does what it did without them."""
+        with ``tiled``; no accuracy claim is made for it either.  ``lookback`` (needs ``tracker``): a ``Lookback`` whose stream k the k-th
+        image continues: THE OUTPUT IS DELAYED by ``lookback.depth`` calls, and a face is covered in the frames BEFORE its first
+        detection too -- with the first box of its track, grown by the distance, where it was first detected (not moved; the defaults
+        are this project's choices, no accuracy claim is made).  Each chunk runs [scene check,] forward, decode, update[, follow], then
+        ``Engine.lookback_step``; the frame that becomes due -- the object's own copy of the image of ``depth`` calls ago -- is covered
+        with the lookback rows.  The return is then, per image k of the call, the LIST of (frame, dets [n,5], lms [n,10], info [n,3] = id,
+        hits, misses) that became ready: empty while stream k warms up, one item in the steady state, and with ``flush=True`` (the end of
+        the video: the stream is drained) up to ``depth + 1``; dets and lms are the covered rows, in the tracker's space, back-filled ones
+        with hits 0 and misses = the distance.  The streams of a call must stand at one fill level (ValueError).  With the defaults every
+        call does what it did without them."""
         _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
         fit = self._fit_options(fit, tiled)
+        look = self._lookback(lookback, flush, tracker, len(imgs))
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
+        late = {} if look is None else {"lookback": lookback, "flush": flush}
         if fit is not None:
-            return out, self.detect_fit(out, "bgr", **fit, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
+            res = self.detect_fit(out, "bgr", **fit, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes, **late)
+            return res if late else (out, res)
         if tiled:
-            return out, self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
-        return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, cover=(out, "bgr", options),
-                                follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"))
+            res = self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes, **late)
+            return res if late else (out, res)
+        res = self._drive(*self._input_form(self.engine, imgs), tracker=tracker, cover=(out, "bgr", options),
+                          follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"),
+                          **({} if look is None else {"lookback": look}))
+        return (out, res) if look is None else look[2]
 
     def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
-                      scenes=None, **options):
+                      scenes=None, lookback=None, flush=False, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
         [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow``,
-        ``fit``, ``detect`` and ``scenes``: as ``anonymize``."""
+        ``fit``, ``detect``, ``scenes``, ``lookback`` and ``flush``: as ``anonymize``."""
         _lib.split_redact_options(options)
         fit = self._fit_options(fit, tiled)
+        look = self._lookback(lookback, flush, tracker, len(frames))
+        late = {} if look is None else {"lookback": lookback, "flush": flush}
         if fit is not None:                                             # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            return out, self.detect_fit(out, fmt, **fit, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
+            res = self.detect_fit(out, fmt, **fit, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes, **late)
+            return res if late else (out, res)
         if tiled:                                                       # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            return out, self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
+            res = self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes, **late)
+            return res if late else (out, res)
         frames, forward = self._input_form(self.engine, frames, fmt)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
-        return out, self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options),
-                                follow=self._follow(follow, detect, tracker, out, fmt), detect=detect, scene=self._scene(scenes, tracker, out, fmt))
+        res = self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options),
+                          follow=self._follow(follow, detect, tracker, out, fmt), detect=detect, scene=self._scene(scenes, tracker, out, fmt),
+                          **({} if look is None else {"lookback": look}))
+        return (out, res) if look is None else look[2]
 
     def best_shots(self, frames, fmt="bgr", *, tracker, shots, tiled=False, tile=None, overlap=None, fit=None, follow=None, detect=True,
                    flush=False, template=None, scenes=None):
@@ -1517,38 +1717,50 @@ class CenterFace(object):
         _lib.draw_opts(**o)                                                   # refuse bad names and colours before any work
         return o
 
-    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, **options):
+    def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None,
+                 flush=False, **options):
         """``detect_batch`` plus the drawing of every detection, what demo.py:15-23 does with cv2 on the host: (frames_out, [(dets, lms),
         ...]) -- frames_out a uint8 [B,h,w,3] COPY of ``imgs`` with box outlines, landmark dots and a label painted on the device
         (``Engine.draw_faces``; ``options`` as there, colours as BGR triples).  ``tiled``, ``tile``, ``overlap`` and ``tracker`` as
         ``anonymize``: with a tracker the label is the track id and the tracks held through a dropout are drawn too, dashed, in
-        ``held_color``.  ``fit``, ``follow``, ``detect`` and ``scenes``: as ``anonymize``."""
+        ``held_color``.  ``fit``, ``follow``, ``detect`` and ``scenes``: as ``anonymize``.  ``lookback`` and ``flush``: as ``anonymize`` --
+        the delayed frames are drawn, a back-filled row as a held one (dashed, in ``held_color``), and the return is the lists."""
         fit = self._fit_options(fit, tiled)
+        look = self._lookback(lookback, flush, tracker, len(imgs))
         imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
         out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
         draw = (out, "bgr", self._draw_options(options, tracker, False))
         fo = dict(follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"))
+        if look is not None:
+            fo["lookback"] = look
         if tiled or fit is not None:
             forward, per, merge = self._frame_form(out, "bgr", tile, overlap, fit, True)
-            return out, self._drive(out, forward, per, merge=merge, tracker=tracker, draw=draw, **fo)
-        return out, self._drive(*self._input_form(self.engine, imgs), tracker=tracker, draw=draw, **fo)
+            res = self._drive(out, forward, per, merge=merge, tracker=tracker, draw=draw, **fo)
+        else:
+            res = self._drive(*self._input_form(self.engine, imgs), tracker=tracker, draw=draw, **fo)
+        return (out, res) if look is None else look[2]
 
     def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
-                     scenes=None, **options):
+                     scenes=None, lookback=None, flush=False, **options):
         """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
-        in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``fit`` and ``scenes``: as ``anonymize``."""
+        in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``fit``, ``scenes``, ``lookback`` and
+        ``flush``: as ``annotate``."""
         fit = self._fit_options(fit, tiled)
         o = self._draw_options(options, tracker, True)
+        look = self._lookback(lookback, flush, tracker, len(frames))
+        late = {} if look is None else {"lookback": look}
         if tiled or fit is not None:                                    # frames of any even size: [B, h*3//2, w]
             out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
             forward, per, merge = self._frame_form(out, fmt, tile, overlap, fit, True)
-            return out, self._drive(out, forward, per, merge=merge, tracker=tracker,
-                                    draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
-                                    scene=self._scene(scenes, tracker, out, fmt))
+            res = self._drive(out, forward, per, merge=merge, tracker=tracker,
+                              draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
+                              scene=self._scene(scenes, tracker, out, fmt), **late)
+            return (out, res) if look is None else look[2]
         frames, forward = self._input_form(self.engine, frames, fmt)
         out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
-        return out, self._drive(frames, forward, tracker=tracker, draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
-                                scene=self._scene(scenes, tracker, out, fmt))
+        res = self._drive(frames, forward, tracker=tracker, draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
+                          scene=self._scene(scenes, tracker, out, fmt), **late)
+        return (out, res) if look is None else look[2]
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]

@@ -569,6 +569,28 @@ const char* scene_check(const cf_scene_opts* o, int format, int B, int h, int w,
 size_t scene_part_bytes(int B, int h);
 hipError_t launch_scene_check(hipStream_t s, const SceneParams& p);
 
+// Lookback (cf_lookback.hip; the statement is in include/centerface_hip.h): one step of the streams stream0 .. stream0 + B - 1 -- with
+// push != 0 the tracked rows of image b (in_dets [B][in_stride][5], in_lms [.][.][10], in_info [.][.][3], in_counts [B]; scene [B][4] as
+// SceneParams::out, or nullptr) enter the queue of stream stream0 + b; then the due entry leaves it with the back-filled rows behind its own.
+constexpr int kLookbackMaxDepth = 32, kLookbackMaxRows = 1024;
+struct LookbackParams {
+    int depth, rows, confirm; float grow;
+    int stream0, B, push;
+    const float* in_dets; const float* in_lms; const int* in_info; const int* in_counts; int in_stride;
+    const int* scene;
+    // state (device), owned by the object: n_streams queues of depth + 1 entries of `rows` rows
+    int* qmeta;           // [S][4]: head, fill, max_id, seq_next
+    int* pend;            // [S]: pending_cut
+    int* emeta;           // [S][depth + 1][4]: seq, cut, n, 0
+    float* rec;           // [S][depth + 1][rows][16]: box, score, lms[10], 0
+    int* info;            // [S][depth + 1][rows][4]: id, hits, misses, born
+    // outputs (device), stride `rows` per image; corners may be nullptr
+    float* dets; float* lms; int* out_info; float* corners; int* counts; int* state;
+};
+// nullptr, or what is wrong with the options / the number of streams (host only)
+const char* lookback_check(const cf_lookback_opts* o, int n_streams);
+hipError_t launch_lookback_step(hipStream_t s, const LookbackParams& p);
+
 // Best-shot selection (cf_bestshot.hip; the statement is in include/centerface_hip.h).  The table's device state, per stream and entry:
 // erec kBestRecInts int32 (state, id, best_t, first_t, last_t, n_offered, done_seq, parts[4], -, Q as int64, -, -), erow kBestRowFloats
 // float32 (det[5], lms[10], -), the chip; per stream smeta kBestStreamInts int32 (t, seq, sticky flags, -).  All zero at first.

@@ -1190,6 +1190,53 @@ int cf_op_scene(int device, const cf_scene_opts* o, int n_streams, int n_frames,
     return sc.result("cf_op_scene");
 }
 
+// The kernel of cf_lookback_step over a sequence of host tables, with the state of a fresh cf_lookback (empty queues, max_id = seq_next = 0).
+int cf_op_lookback(int device, const cf_lookback_opts* o, int n_streams, int n_steps, int rows_in, const uint8_t* push, const float* dets_in,
+                   const float* lms_in, const int32_t* info_in, const int32_t* counts_in, const int32_t* cuts, float* dets, float* lms,
+                   int32_t* info, int32_t* counts, int32_t* state) {
+    const char* bad = lookback_check(o, n_streams);
+    if (!bad && (!push || !dets_in || !lms_in || !info_in || !counts_in || !dets || !lms || !info || !counts || !state)) bad = "null argument";
+    if (!bad && n_steps < 1) bad = "n_steps must be at least 1";
+    if (!bad && (rows_in < 1 || rows_in > o->rows)) bad = "rows_in must be in 1..rows";
+    if (!bad && (long long)n_steps * n_streams * o->rows > (1 << 24)) bad = "more than 2^24 rows";
+    if (bad) { g_op_error = std::string("cf_op_lookback: ") + bad; return CF_EINVAL; }
+    Scope sc(device);
+    const size_t S = n_streams, F = n_steps, R = o->rows, cap = (size_t)o->depth + 1, nin = F * S * rows_in, nout = F * S * R;
+    std::vector<int32_t> codes(F * S * 4, 0), ones(S, 1);
+    for (size_t k = 0; k < F * S; ++k) codes[k * 4] = cuts && (cuts[k] & 1) ? CF_SCENE_CUT : CF_SCENE_SAME;
+    LookbackParams p{};
+    p.depth = o->depth; p.rows = o->rows; p.confirm = o->confirm; p.grow = o->grow; p.stream0 = 0; p.B = n_streams;
+    const float* din = (const float*)sc.up(dets_in, nin * 5 * sizeof(float));
+    const float* lin = (const float*)sc.up(lms_in, nin * 10 * sizeof(float));
+    const int* iin = (const int*)sc.up(info_in, nin * 3 * sizeof(int));
+    const int* cin = (const int*)sc.up(counts_in, F * S * sizeof(int));
+    const int* scn = (const int*)sc.upv(codes);
+    const int* one = (const int*)sc.upv(ones);
+    p.in_stride = rows_in;
+    p.qmeta = (int*)sc.alloc(S * 4 * sizeof(int)); p.pend = (int*)sc.alloc(S * sizeof(int)); p.emeta = (int*)sc.alloc(S * cap * 4 * sizeof(int));
+    p.rec = (float*)sc.alloc(S * cap * R * 16 * sizeof(float)); p.info = (int*)sc.alloc(S * cap * R * 4 * sizeof(int));
+    float* d_dev = (float*)sc.up(dets, nout * 5 * sizeof(float));
+    float* l_dev = (float*)sc.up(lms, nout * 10 * sizeof(float));
+    int* i_dev = (int*)sc.up(info, nout * 3 * sizeof(int));
+    int* c_dev = (int*)sc.alloc(F * S * sizeof(int));
+    int* s_dev = (int*)sc.alloc(F * S * 4 * sizeof(int));
+    for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
+        for (size_t s = 0; cuts && s < S && sc.err == hipSuccess; ++s)      // cf_lookback_forget of stream s
+            if (cuts[f * S + s] & 2) sc.chk(hipMemcpyAsync(p.pend + s, one + s, sizeof(int), hipMemcpyDeviceToDevice, sc.s));
+        p.push = push[f] ? 1 : 0;
+        p.in_dets = din + f * S * rows_in * 5; p.in_lms = lin + f * S * rows_in * 10; p.in_info = iin + f * S * rows_in * 3; p.in_counts = cin + f * S;
+        p.scene = cuts ? scn + f * S * 4 : nullptr;
+        p.dets = d_dev + f * S * R * 5; p.lms = l_dev + f * S * R * 10; p.out_info = i_dev + f * S * R * 3; p.counts = c_dev + f * S; p.state = s_dev + f * S * 4;
+        if (sc.err == hipSuccess) sc.chk(launch_lookback_step(sc.s, p));
+    }
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, d_dev, nout * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, l_dev, nout * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(info, i_dev, nout * 3 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(counts, c_dev, F * S * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(state, s_dev, F * S * 4 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    return sc.result("cf_op_lookback");
+}
+
 // The score kernel of cf_bestshot_offer alone: one image whose n rows all count and are eligible (ids 1 .. n, hits 1000, misses 0).
 int cf_op_chip_quality(int device, const cf_bestshot_opts* o, const uint8_t* chips, const float* boxes, const float* scores, const float* lms,
                        int n, double fx, double fy, int64_t* quality, int32_t* parts) {

@@ -173,6 +173,9 @@ struct cf_ctx {
     // cf_track_follow: B > 0 = the rows in tk are the follow's, of B frames in the tracker's space (H x W network input, or -- tiled -- H x W
     // frames), and the newest whatever `stage` says; any forward, threshold decode, merge or update ends that (B = 0)
     struct { DevBuf slot_moves, moves; int B = 0, H = 0, W = 0; bool tiled = false; } fo;
+    // cf_lookback_step: B > 0 = the lookback rows (M per image, in the object's latched space) are the newest, until what ends a follow's
+    // rows or an upload; pushed = the tracked rows in tk went into a lookback queue already
+    struct { DevBuf dets, lms, info, corners, counts, state, scene; int B = 0, M = 0, H = 0, W = 0; bool tiled = false, pushed = false; } lb;
     struct { DevBuf part, out; } sn;                                    // cf_scene_check: the workgroups' partial sums, out [B][4] of a host-output call
     struct { DevBuf q, sc, jobs, flags, chips, off, out; } bs;          // cf_bestshot_offer / cf_bestshot_collect: per-call scratch and the staging of their host forms
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
@@ -1178,7 +1181,7 @@ int forward_run(cf_ctx* c, const void* caller_in, int in_format, int Bcaller) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in.used;      // what cf_align_faces samples
-    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->fo.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
+    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->fo.B = 0; c->lb.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -1348,7 +1351,7 @@ int cf_upload_images(cf_ctx* c, const void* const* imgs, int B, int h, int w) {
     if (!c || !imgs || h < 1 || w < 1) return CF_EINVAL;
     if (int r = forward_begin(c, "cf_upload_images", B)) return r;
     for (int b = 0; b < B; ++b) if (!imgs[b]) return c->fail(CF_EINVAL, "cf_upload_images: image %d is a null pointer", b);
-    c->al_in = nullptr;                                     // the copies below may land in the slot the last forward read
+    c->al_in = nullptr; c->lb.B = 0;                        // the copies below may land in the slot the last forward read; the lookback rows end here too
     const size_t one = (size_t)h * w * 3;
     // page-locked images (device-visible, 16-byte aligned): ONE kernel reads them all over PCIe instead of one DMA command each
     std::vector<const void*> dev;
@@ -1619,11 +1622,20 @@ enum RowsWanted {
     ROWS_OF_FIT_DECODE,      // the same, of a fitted forward (cf_unfit_rows)
     ROWS_UNTRACKED,          // the newest that no cf_track_update has consumed: the merged rows of a tiled forward, the mapped rows of a
                              // fitted one, else the decode's
-    ROWS_NEWEST              // the followed rows behind a follow, else the tracked rows behind an update, else those (cf_redact_faces, cf_blur_faces,
-                             // cf_align_faces_frame, cf_draw_faces)
+    ROWS_UNSTEPPED,          // the tracked rows that no cf_lookback_step has consumed: the followed rows behind a follow, else the tracked rows
+                             // behind an update (the push of cf_lookback_step)
+    ROWS_NEWEST              // the lookback rows behind a step, else the followed rows behind a follow, else the tracked rows behind an update, else
+                             // the untracked ones (cf_redact_faces, cf_blur_faces, cf_align_faces_frame, cf_draw_faces)
 };
 static int rows_for(cf_ctx* c, const char* who, RowsWanted want, RowSet& r) {
-    if (want == ROWS_NEWEST && c->fo.B > 0) {            // behind cf_track_follow, which needs no forward: the followed rows, in the tracker's space
+    if (want == ROWS_NEWEST && c->lb.B > 0) {            // behind cf_lookback_step, whose drain needs no forward: the lookback rows, in the object's latched space
+        r = RowSet{(const float*)c->lb.corners.p, (const float*)c->lb.dets.p, (const float*)c->lb.lms.p, (const int*)c->lb.counts.p, c->lb.M, c->lb.B, c->lb.H, c->lb.W,
+                   c->lb.tiled, (const int32_t*)c->lb.info.p};
+        return CF_OK;
+    }
+    if (want == ROWS_UNSTEPPED && c->lb.pushed && (c->fo.B > 0 || c->stage == ROWS_TRACKED))
+        return c->fail(CF_ESTATE, "%s: these rows went into a lookback queue already (time would advance twice)", who);
+    if ((want == ROWS_NEWEST || want == ROWS_UNSTEPPED) && c->fo.B > 0) {      // behind cf_track_follow, which needs no forward: the followed rows, in the tracker's space
         r = RowSet{(const float*)c->tk.corners.p, (const float*)c->tk.dets.p, (const float*)c->tk.lms.p, (const int*)c->tk.counts.p, c->tk_M, c->fo.B, c->fo.H, c->fo.W,
                    c->fo.tiled, (const int32_t*)c->tk.info.p};
         return CF_OK;
@@ -1640,7 +1652,7 @@ static int rows_for(cf_ctx* c, const char* who, RowsWanted want, RowSet& r) {
             return c->fail(CF_ESTATE, c->ft_on ? "%s after cf_forward_fit without a cf_unfit_rows of the last decode" : "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
         r = RowSet{(const float*)c->tl.corners.p, (const float*)c->tl.dets.p, (const float*)c->tl.lms.p, (const int*)c->tl.counts.p, c->tl_maxout, c->tl_Bf, c->tl_h, c->tl_w, true};
     }
-    if (c->stage < ROWS_TRACKED) return CF_OK;
+    if (c->stage < ROWS_TRACKED) return want == ROWS_UNSTEPPED ? c->fail(CF_ESTATE, "%s without a cf_track_update or cf_track_follow behind the last decode", who) : CF_OK;
     if (want == ROWS_UNTRACKED) return c->fail(CF_ESTATE, "%s: these rows went through an update already (time would advance twice)", who);
     r.corners = (const float*)c->tk.corners.p; r.dets = (const float*)c->tk.dets.p; r.lms = (const float*)c->tk.lms.p;      // the same images and coordinates
     r.counts = (const int*)c->tk.counts.p; r.stride = c->tk_M; r.info = (const int32_t*)c->tk.info.p;
@@ -1736,7 +1748,7 @@ static int thresh_launch(cf_ctx* c, int mode, float score_thresh, float nms_thre
     HIPCHK(c, hipMemsetAsync(c->t_overflow, 0, sizeof(int), c->stream));
     HIPCHK(c, launch_decode_threshold(c->stream, p));
     HIPCHK(c, hipEventRecord(c->ev_thr, c->stream));
-    c->al_rows = max_out; c->stage = ROWS_DECODED; c->fo.B = 0;
+    c->al_rows = max_out; c->stage = ROWS_DECODED; c->fo.B = 0; c->lb.B = 0;
     return CF_OK;
 }
 
@@ -2048,7 +2060,7 @@ int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
         return c->fail(CF_ENOMEM, "cf_merge_tiles: %d frames x %d tiles x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
                        Bf, T, rows, merge_mask_bytes(Bf, T, rows) / 1e6);
     HIPCHK(c, hipSetDevice(c->device));
-    c->stage = ROWS_DECODED; c->fo.B = 0;                 // the merged (and tracked, and followed) rows of an earlier call are gone from here on
+    c->stage = ROWS_DECODED; c->fo.B = 0; c->lb.B = 0;    // the merged (and tracked, and followed) rows of an earlier call are gone from here on
     const size_t cap = (size_t)T * rows, mo = (size_t)Bf * max_out, nb = (size_t)Bf * sizeof(int);
     const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
     auto& ws = c->tl;
@@ -2114,7 +2126,7 @@ int cf_unfit_rows(cf_ctx* c, int max_out, float* dets, float* lms, int32_t* coun
     RowSet in{};
     if (int r = rows_for(c, "cf_unfit_rows", ROWS_OF_FIT_DECODE, in)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    c->stage = ROWS_DECODED; c->fo.B = 0;                 // the mapped (and tracked, and followed) rows of an earlier call are gone from here on
+    c->stage = ROWS_DECODED; c->fo.B = 0; c->lb.B = 0;    // the mapped (and tracked, and followed) rows of an earlier call are gone from here on
     const int B = c->tl_Bf;
     const size_t mo = (size_t)B * max_out, nb = (size_t)B * sizeof(int);
     const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
@@ -2236,7 +2248,7 @@ int cf_track_update(cf_ctx* c, cf_tracker* t, int stream0, float* dets, float* l
     HIPCHK(c, launch_track_update(c->stream, p));
     HIPCHK(c, hipEventRecord(t->ev, c->stream));
     t->latched = true; t->sp_tiled = tiled; t->sp_h = in.H; t->sp_w = in.W;
-    c->stage = ROWS_TRACKED; c->tk_M = M; c->fo.B = 0;
+    c->stage = ROWS_TRACKED; c->tk_M = M; c->fo.B = 0; c->lb.B = 0; c->lb.pushed = false;
     if (out_on_device) {
         if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
         if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, nl, hipMemcpyDeviceToDevice, c->stream));
@@ -2293,14 +2305,14 @@ int cf_track_follow(cf_ctx* c, cf_tracker* t, int stream0, int B, const cf_follo
     p.tpl = t->fol; p.tmeta = (int*)(t->fol + slots * kFollowSide * kFollowSide); p.slot_moves = (int*)c->fo.slot_moves.p;
     p.dets = (float*)ws.dets.p; p.lms_out = (float*)ws.lms.p; p.info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
     p.out_counts = (int*)ws.counts.p; p.moves = (int*)c->fo.moves.p;
-    c->fo.B = 0;                                                          // (a failure below leaves no followed rows behind)
+    c->fo.B = 0; c->lb.B = 0;                                              // (a failure below leaves no followed rows behind)
     // host frames are only read: staged, not copied back
     if (int r = on_frames(c, "cf_track_follow", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, on_device, false, [&](const void* const* pl, int p0, int p1) {
             p.g = FrameGeo{format, B, h, w, p0, p1}; p.planes = pl;
             const hipError_t e = launch_track_follow(c->stream, p);
             return e != hipSuccess ? e : hipEventRecord(t->ev, c->stream);
         })) return r;
-    c->tk_M = M; c->fo.B = B; c->fo.H = t->sp_h; c->fo.W = t->sp_w; c->fo.tiled = t->sp_tiled;
+    c->tk_M = M; c->fo.B = B; c->fo.H = t->sp_h; c->fo.W = t->sp_w; c->fo.tiled = t->sp_tiled; c->lb.pushed = false;
     if (out_on_device) {
         if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
         if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, nl, hipMemcpyDeviceToDevice, c->stream));
@@ -2419,6 +2431,140 @@ int cf_scene_check(cf_ctx* c, cf_scene* t, cf_tracker* trk, int stream0, int B, 
     HIPCHK(c, hipMemcpyAsync(out, p.out, no, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CF_OK;
+}
+
+// ---- lookback (cf_lookback.hip).  The object owns the queues of its streams, one event that orders its steps across the contexts that
+// issue them, and a stream of its own for what no context carries (the initial state, cf_lookback_forget).
+}  // extern "C"
+struct cf_lookback {
+    int device = 0, S = 0;
+    cf_lookback_opts o{};
+    int* qmeta = nullptr; int* pend = nullptr; int* emeta = nullptr; float* rec = nullptr; int* info = nullptr;
+    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
+    bool latched = false, sp_tiled = false; int sp_h = 0, sp_w = 0, stride = 0;      // the row space and the stride of the first push
+};
+extern "C" {
+
+int cf_lookback_destroy(cf_lookback* t) {
+    if (!t) return CF_OK;
+    hipSetDevice(t->device);
+    if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
+    if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
+    for (void* p : {(void*)t->qmeta, (void*)t->pend, (void*)t->emeta, (void*)t->rec, (void*)t->info}) if (p) hipFree(p);
+    delete t;
+    return CF_OK;
+}
+
+int cf_lookback_create(cf_ctx* c, int n_streams, const cf_lookback_opts* o, cf_lookback** out) {
+    const char* why = lookback_check(o, n_streams);
+    if (!why && !out) why = "null out";
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_lookback_create: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_lookback_create: %s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    cf_lookback* t = new cf_lookback();
+    t->device = c->device; t->S = n_streams; t->o = *o;
+    const size_t S = (size_t)n_streams, entries = S * (o->depth + 1), rows = entries * o->rows;
+    hipError_t e = hipStreamCreateWithFlags(&t->ts, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->qmeta, S * 4 * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&t->pend, S * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&t->emeta, entries * 4 * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&t->rec, rows * 16 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&t->info, rows * 4 * sizeof(int));
+    if (e == hipSuccess) e = hipMemsetAsync(t->qmeta, 0, S * 4 * sizeof(int), t->ts);
+    if (e == hipSuccess) e = hipMemsetAsync(t->pend, 0, S * sizeof(int), t->ts);
+    if (e == hipSuccess) e = hipMemsetAsync(t->emeta, 0, entries * 4 * sizeof(int), t->ts);
+    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        cf_lookback_destroy(t);
+        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_lookback_create: %d streams x %d entries x %d rows: %s", n_streams, o->depth + 1, o->rows,
+                       hipGetErrorString(e));
+    }
+    *out = t;
+    return CF_OK;
+}
+
+int cf_lookback_forget(cf_lookback* t, int stream) {
+    if (!t || stream < -1 || stream >= t->S) { op_error_set("cf_lookback_forget: null object, or a stream outside -1 .. n_streams - 1"); return CF_EINVAL; }
+    const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)t->S : 1;
+    hipError_t e = hipSetDevice(t->device);
+    if (e == hipSuccess) e = hipStreamWaitEvent(t->ts, t->ev, 0);
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)(t->pend + first), 1, n, t->ts);
+    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
+    if (e != hipSuccess) { op_error_set((std::string("cf_lookback_forget: ") + hipGetErrorString(e)).c_str()); return CF_EHIP; }
+    return CF_OK;
+}
+
+// One step of the streams stream0 .. stream0 + B - 1: ordered on the object's event like a tracker's update; a push reads the context's
+// tracked rows (rows_for), and the context's lookback rows are written in any case.
+int cf_lookback_step(cf_ctx* c, cf_lookback* t, int stream0, int B, int push, const int32_t* scene, int scene_on_device, float* dets, float* lms,
+                     int32_t* info, int32_t* counts, int32_t* state, int out_on_device) {
+    const char* why = B < 1 ? "B must be at least 1" : nullptr;
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_lookback_step: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_lookback_step: %s", why);
+    if (!t) return c->fail(CF_EINVAL, "cf_lookback_step: null lookback object");
+    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_lookback_step: the lookback object lives on device %d, the context on device %d", t->device, c->device);
+    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_lookback_step: B=%d exceeds max_batch %d", B, c->max_batch);
+    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_lookback_step: streams %d .. %d of a lookback object with %d", stream0, stream0 + B - 1, t->S);
+    RowSet in{};
+    const int R = t->o.rows;
+    if (push) {
+        if (int r = rows_for(c, "cf_lookback_step", ROWS_UNSTEPPED, in)) return r;
+        if (in.B != B) return c->fail(CF_ESTATE, "cf_lookback_step: B=%d, the tracked rows are those of %d images", B, in.B);
+        if (t->latched && (t->sp_tiled != in.frame_space || t->sp_h != in.H || t->sp_w != in.W))
+            return c->fail(CF_EINVAL, "cf_lookback_step: the queued rows are in %s %d x %d coordinates, these in %s %d x %d", t->sp_tiled ? "frame" : "network", t->sp_w, t->sp_h,
+                           in.frame_space ? "frame" : "network", in.W, in.H);
+        if (t->latched ? in.stride != t->stride : in.stride > R)
+            return c->fail(CF_EINVAL, "cf_lookback_step: %d tracked rows per image, the object %s %d", in.stride, t->latched ? "was first given" : "holds at most", t->latched ? t->stride : R);
+    } else if (!t->latched) {
+        return c->fail(CF_ESTATE, "cf_lookback_step: a drain before the object's first push: its rows have no coordinate space yet");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bm = (size_t)B * R, nb = (size_t)B * sizeof(int), ns = (size_t)B * 4 * sizeof(int);
+    const size_t nd = bm * 5 * sizeof(float), nl = bm * 10 * sizeof(float), ni = bm * 3 * sizeof(int);
+    auto& ws = c->lb;
+    const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
+        {ws.dets, nd, "lookback dets"}, {ws.lms, nl, "lookback landmarks"}, {ws.info, ni, "lookback info"}, {ws.corners, bm * 4 * sizeof(float), "lookback corners"},
+        {ws.counts, nb, "lookback counts"}, {ws.state, ns, "lookback state"}, {ws.scene, ns, "scene codes"}};
+    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_lookback_step")) return r;
+    LookbackParams p{};
+    p.depth = t->o.depth; p.rows = R; p.confirm = t->o.confirm; p.grow = t->o.grow;
+    p.stream0 = stream0; p.B = B; p.push = push ? 1 : 0;
+    if (push) { p.in_dets = in.dets; p.in_lms = in.lms; p.in_info = (const int*)in.info; p.in_counts = in.counts; p.in_stride = in.stride; }
+    if (push && scene && !scene_on_device) {
+        HIPCHK(c, hipMemcpyAsync(ws.scene.p, scene, ns, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));                        // the caller's table is free when the call returns
+        p.scene = (const int*)ws.scene.p;
+    } else if (push) {
+        p.scene = (const int*)scene;
+    }
+    p.qmeta = t->qmeta; p.pend = t->pend; p.emeta = t->emeta; p.rec = t->rec; p.info = t->info;
+    p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.out_info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
+    p.counts = (int*)ws.counts.p; p.state = (int*)ws.state.p;
+    c->lb.B = 0;                                                          // (a failure below leaves no lookback rows behind)
+    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the step before this one, on whichever context's stream
+    HIPCHK(c, launch_lookback_step(c->stream, p));
+    HIPCHK(c, hipEventRecord(t->ev, c->stream));
+    if (push) { t->sp_tiled = in.frame_space; t->sp_h = in.H; t->sp_w = in.W; t->stride = in.stride; t->latched = true; c->lb.pushed = true; }
+    c->lb.B = B; c->lb.M = R; c->lb.H = t->sp_h; c->lb.W = t->sp_w; c->lb.tiled = t->sp_tiled;
+    if (out_on_device) {
+        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
+        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms, nl, hipMemcpyDeviceToDevice, c->stream));
+        if (info) HIPCHK(c, hipMemcpyAsync(info, p.out_info, ni, hipMemcpyDeviceToDevice, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.counts, nb, hipMemcpyDeviceToDevice, c->stream));
+        if (state) HIPCHK(c, hipMemcpyAsync(state, p.state, ns, hipMemcpyDeviceToDevice, c->stream));
+        return CF_OK;
+    }
+    if (state) HIPCHK(c, hipMemcpyAsync(state, p.state, ns, hipMemcpyDeviceToHost, c->stream));
+    return read_out(c, B, R, p.counts, nullptr, counts, nullptr,
+                    {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}, {info, p.out_info, 3 * sizeof(int)}});
 }
 
 // Best-shot selection (cf_bestshot.hip): the table's state lives in device memory the table owns and is advanced only by kernels, on the

@@ -525,6 +525,35 @@ def scene_sequence(frames, fmt, streams, hist=350, grid=640, sigs=False, device=
     return (out, sg) if sigs else out
 
 
+def lookback_sequence(dets_in, lms_in, info_in, counts_in, push=None, cuts=None, dets=None, lms_out=None, info=None, device=0, **opts):
+    """The lookback step of ``Engine.lookback_step`` over a whole sequence, with a fresh ``Lookback`` (``cf_op_lookback``): step f pushes,
+    for every stream s, the tracked rows below counts_in[f, s] of dets_in [F, S, rows_in, 5], lms_in [F, S, rows_in, 10] and info_in
+    [F, S, rows_in, 3] = id, hits, misses -- what ``track_sequence`` returns -- where ``push`` [F] is set (default: everywhere), and is a
+    drain elsewhere.  ``cuts`` [F, S] (default: none): bit 0 = the scene check called the pushed frame a cut, bit 1 = a
+    ``Lookback.forget`` of the stream comes before the step.  ``opts``: depth, rows, grow, confirm (``_lib.lookback_opts``; the defaults
+    are this project's choices, no accuracy claim is made for them).  Returns (dets [F, S, rows, 5], lms [F, S, rows, 10], info
+    [F, S, rows, 3], counts [F, S], state [F, S, 4] = seq, own rows, back-filled rows, flags -- seq -1 where nothing was emitted) after
+    every step; rows at and past a count keep the bytes of the ``dets`` / ``lms_out`` / ``info`` arrays passed in (zeros by default)."""
+    o = _lib.lookback_opts(**opts)
+    d = np.ascontiguousarray(dets_in, dtype=np.float32)
+    if d.ndim != 4 or d.shape[3] != 5:
+        raise ValueError("dets_in must be [F, S, rows_in, 5], got %s" % (d.shape,))
+    F, S, rows_in, _ = d.shape
+    lm = np.ascontiguousarray(lms_in, dtype=np.float32).reshape(F, S, rows_in, 10)
+    ii = np.ascontiguousarray(info_in, dtype=np.int32).reshape(F, S, rows_in, 3)
+    cn = np.ascontiguousarray(counts_in, dtype=np.int32).reshape(F, S)
+    pu = np.ones((F,), np.uint8) if push is None else np.ascontiguousarray(np.asarray(push) != 0, dtype=np.uint8).reshape(F)
+    cu = None if cuts is None else np.ascontiguousarray(cuts, dtype=np.int32).reshape(F, S)
+    R = max(int(o.rows), 1)
+    od = np.zeros((F, S, R, 5), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(F, S, R, 5)
+    ol = np.zeros((F, S, R, 10), np.float32) if lms_out is None else np.ascontiguousarray(lms_out, dtype=np.float32).reshape(F, S, R, 10)
+    oi = np.zeros((F, S, R, 3), np.int32) if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(F, S, R, 3)
+    oc, st = np.zeros((F, S), np.int32), np.zeros((F, S, 4), np.int32)
+    _lib.check(_lib.lib().cf_op_lookback(device, C.byref(o), S, F, rows_in, ptr(pu), ptr(d), ptr(lm), ptr(ii), ptr(cn), ptr(cu), ptr(od), ptr(ol), ptr(oi),
+                                         ptr(oc), ptr(st)), op=True)
+    return od, ol, oi, oc, st
+
+
 def scene_signature(frame, fmt, device=0):
     """The 128 int32 of one frame's signature (``include/centerface_hip.h``: 64 luma bins, 8 x 8 cell means), computed on the device:
     ``frame`` is one BGR uint8 [h,w,3], one dense 4:2:0 uint8 [h*3//2, w], or one plane tuple."""

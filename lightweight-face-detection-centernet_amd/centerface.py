@@ -846,7 +846,59 @@ class Engine(object):
         self._chk(self._L.cf_memcpy_d2h(self._h, _lib.ptr(arr), C.c_void_p(int(dptr)), arr.nbytes))
 
 
-class Tracker(object):
+class _StreamState(object):
+    """What ``Tracker``, ``SceneCuts``, ``Lookback`` and ``BestShots`` share: one object of the library that holds the state of ``streams``
+    video streams on one GPU.  A subclass names the library's functions (``_create``, ``_destroy`` and, where there is one, ``_clear``)
+    and the noun of the messages, and hands ``_open`` its options struct last in its ``__init__``."""
+
+    _create = _destroy = _clear = _noun = None
+
+    def _open(self, engine_or_device, streams, opts):
+        self._L = _lib.lib()
+        self._o = opts
+        self.streams = int(streams)
+        self._h = None
+        if isinstance(engine_or_device, Engine):
+            self.device = engine_or_device.device
+            self._handle(engine_or_device)
+        else:
+            self.device = int(engine_or_device)
+            # refuse bad options now, not at the first call (no context: the library checks the arguments and tells)
+            out = C.c_void_p()
+            getattr(self._L, self._create)(None, self.streams, C.byref(self._o), C.byref(out))
+            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
+            if "null context" not in why:
+                raise _lib.CenterFaceValueError(-1, why)
+
+    def _handle(self, engine):
+        """The library's object, created with ``engine``'s context on first use."""
+        if self._h is None:
+            if engine.device != self.device:
+                raise ValueError("the %s was made for device %d, the engine runs on device %d" % (self._noun, self.device, engine.device))
+            out = C.c_void_p()
+            _lib.check(getattr(self._L, self._create)(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
+            self._h = out
+        return self._h
+
+    def _clear_stream(self, stream):
+        if not -1 <= int(stream) < self.streams:
+            raise ValueError("stream %d of a %s with %d" % (stream, self._noun, self.streams))
+        if self._h is not None:
+            _lib.check(getattr(self._L, self._clear)(self._h, int(stream)), op=True)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Tracker(_StreamState):
     """One cf_tracker: ``streams`` independent video streams on one GPU, ``max_tracks`` slots each (``include/centerface_hip.h`` states
     the update).  ``engine_or_device``: an ``Engine`` (the tracker is created at once on its GPU) or a device index (created by the first
     ``Engine.track_update`` that uses it, which must be on that GPU).  A face that matches a track (IoU >= ``iou``) keeps its id; a track
@@ -855,53 +907,18 @@ class Tracker(object):
     not covered.  The defaults are this project's choices; no accuracy claim is made for them.  Engines of one GPU may share a tracker:
     its updates are ordered in call order."""
 
-    def __init__(self, engine_or_device, streams, iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0):
-        self._L = _lib.lib()
-        self._o = _lib.track_opts(iou, max_age, min_hits, max_tracks, hold_grow)
-        self.streams, self.max_tracks = int(streams), int(max_tracks)
-        self._h = None
-        if isinstance(engine_or_device, Engine):
-            self.device = engine_or_device.device
-            self._handle(engine_or_device)
-        else:
-            self.device = int(engine_or_device)
-            # refuse bad options now, not at the first update (no context: the library checks the arguments and tells)
-            out = C.c_void_p()
-            self._L.cf_track_create(None, self.streams, C.byref(self._o), C.byref(out))
-            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
-            if "null context" not in why:
-                raise _lib.CenterFaceValueError(-1, why)
+    _create, _destroy, _clear, _noun = "cf_track_create", "cf_track_destroy", "cf_track_reset", "tracker"
 
-    def _handle(self, engine):
-        """The cf_tracker, created with ``engine``'s context on first use."""
-        if self._h is None:
-            if engine.device != self.device:
-                raise ValueError("the tracker was made for device %d, the engine runs on device %d" % (self.device, engine.device))
-            out = C.c_void_p()
-            _lib.check(self._L.cf_track_create(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
-            self._h = out
-        return self._h
+    def __init__(self, engine_or_device, streams, iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0):
+        self.max_tracks = int(max_tracks)
+        self._open(engine_or_device, streams, _lib.track_opts(iou, max_age, min_hits, max_tracks, hold_grow))
 
     def reset(self, stream=-1):
         """A scene cut: drop every track of ``stream`` (-1: of all streams).  ids are not reused."""
-        if not -1 <= int(stream) < self.streams:
-            raise ValueError("stream %d of a tracker with %d" % (stream, self.streams))
-        if self._h is not None:
-            _lib.check(self._L.cf_track_reset(self._h, int(stream)), op=True)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.cf_track_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._clear_stream(stream)
 
 
-class SceneCuts(object):
+class SceneCuts(_StreamState):
     """One cf_scene: the last frame signature of ``streams`` independent video streams on one GPU (``include/centerface_hip.h`` states the
     signature and the check).  ``engine_or_device``: an ``Engine`` (created at once on its GPU) or a device index (created by the first
     ``Engine.scene_check`` that uses it, which must be on that GPU).  A frame is a CUT when at least ``hist`` per mille of its pixels
@@ -909,53 +926,17 @@ class SceneCuts(object):
     lost); a dissolve is not one cut.  The defaults are this project's choices: there is no labelled video here, nobody has measured
     them, and no accuracy claim is made.  Engines of one GPU may share an object: its checks are ordered in call order."""
 
-    def __init__(self, engine_or_device, streams, hist=350, grid=640):
-        self._L = _lib.lib()
-        self._o = _lib.scene_opts(hist, grid)
-        self.streams = int(streams)
-        self._h = None
-        if isinstance(engine_or_device, Engine):
-            self.device = engine_or_device.device
-            self._handle(engine_or_device)
-        else:
-            self.device = int(engine_or_device)
-            # refuse bad options now, not at the first check (no context: the library checks the arguments and tells)
-            out = C.c_void_p()
-            self._L.cf_scene_create(None, self.streams, C.byref(self._o), C.byref(out))
-            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
-            if "null context" not in why:
-                raise _lib.CenterFaceValueError(-1, why)
+    _create, _destroy, _clear, _noun = "cf_scene_create", "cf_scene_destroy", "cf_scene_forget", "scene object"
 
-    def _handle(self, engine):
-        """The cf_scene, created with ``engine``'s context on first use."""
-        if self._h is None:
-            if engine.device != self.device:
-                raise ValueError("the scene object was made for device %d, the engine runs on device %d" % (self.device, engine.device))
-            out = C.c_void_p()
-            _lib.check(self._L.cf_scene_create(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
-            self._h = out
-        return self._h
+    def __init__(self, engine_or_device, streams, hist=350, grid=640):
+        self._open(engine_or_device, streams, _lib.scene_opts(hist, grid))
 
     def forget(self, stream=-1):
         """The next check of ``stream`` (-1: of every stream) is FIRST: a new video begins there."""
-        if not -1 <= int(stream) < self.streams:
-            raise ValueError("stream %d of a scene object with %d" % (stream, self.streams))
-        if self._h is not None:
-            _lib.check(self._L.cf_scene_forget(self._h, int(stream)), op=True)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.cf_scene_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._clear_stream(stream)
 
 
-class Lookback(object):
+class Lookback(_StreamState):
     """One cf_lookback: a delay line of ``depth`` frames for ``streams`` independent video streams on one GPU (``include/centerface_hip.h``
     states the step).  ``engine_or_device``: an ``Engine`` (created at once on its GPU) or a device index (created by the first
     ``Engine.lookback_step`` that uses it, which must be on that GPU).  A frame leaves the line ``depth`` steps after it entered, with its
@@ -967,34 +948,13 @@ class Lookback(object):
     Engines of one GPU may share an object: its steps are ordered in call order.  For the product paths (``CenterFace.anonymize(...,
     lookback=)``) the object also keeps, per stream, the host copies of the source frames that are still in the line."""
 
-    def __init__(self, engine_or_device, streams, depth=8, rows=256, grow=0.05, confirm=1):
-        self._L = _lib.lib()
-        self._o = _lib.lookback_opts(depth, rows, grow, confirm)
-        self.streams, self.depth, self.rows = int(streams), int(depth), int(rows)
-        self._h = None
-        self._frames = [[] for _ in range(max(self.streams, 0))]             # per stream: the retained source frames, oldest first
-        self._codes = None                                                    # (engine, device address): the scene codes of a chunk
-        if isinstance(engine_or_device, Engine):
-            self.device = engine_or_device.device
-            self._handle(engine_or_device)
-        else:
-            self.device = int(engine_or_device)
-            # refuse bad options now, not at the first step (no context: the library checks the arguments and tells)
-            out = C.c_void_p()
-            self._L.cf_lookback_create(None, self.streams, C.byref(self._o), C.byref(out))
-            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
-            if "null context" not in why:
-                raise _lib.CenterFaceValueError(-1, why)
+    _create, _destroy, _clear, _noun = "cf_lookback_create", "cf_lookback_destroy", "cf_lookback_forget", "lookback object"
 
-    def _handle(self, engine):
-        """The cf_lookback, created with ``engine``'s context on first use."""
-        if self._h is None:
-            if engine.device != self.device:
-                raise ValueError("the lookback object was made for device %d, the engine runs on device %d" % (self.device, engine.device))
-            out = C.c_void_p()
-            _lib.check(self._L.cf_lookback_create(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
-            self._h = out
-        return self._h
+    def __init__(self, engine_or_device, streams, depth=8, rows=256, grow=0.05, confirm=1):
+        self.depth, self.rows = int(depth), int(rows)
+        self._frames = [[] for _ in range(max(int(streams), 0))]             # per stream: the retained source frames, oldest first
+        self._codes = None                                                    # (engine, device address): the scene codes of a chunk
+        self._open(engine_or_device, streams, _lib.lookback_opts(depth, rows, grow, confirm))
 
     def fill(self, stream):
         """The number of source frames of ``stream`` the product paths still hold (0 .. depth)."""
@@ -1017,25 +977,14 @@ class Lookback(object):
     def forget(self, stream=-1):
         """Nothing pushed from now on is painted back into the frames of ``stream`` (-1: of every stream) that are queued now: for callers
         that reset the tracks themselves (``Tracker.reset``).  The queued frames still come out."""
-        if not -1 <= int(stream) < self.streams:
-            raise ValueError("stream %d of a lookback object with %d" % (stream, self.streams))
-        if self._h is not None:
-            _lib.check(self._L.cf_lookback_forget(self._h, int(stream)), op=True)
+        self._clear_stream(stream)
 
     def close(self):
         self._free_codes()
-        if getattr(self, "_h", None):
-            self._L.cf_lookback_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _StreamState.close(self)
 
 
-class BestShots(object):
+class BestShots(_StreamState):
     """One cf_bestshot table: ``streams`` independent video streams on one GPU, ``entries`` entries each -- live tracks plus finished ones
     not yet collected (``include/centerface_hip.h`` states the quality, the offer and the collect).  ``engine_or_device``: an ``Engine``
     (the table is created at once on its GPU) or a device index (created by the first ``Engine.bestshot_offer`` / ``bestshot_collect``
@@ -1047,43 +996,11 @@ class BestShots(object):
     are this project's choices; no accuracy claim is made for them.  Engines of one GPU may share a table: its calls are ordered in call
     order."""
 
+    _create, _destroy, _noun = "cf_bestshot_create", "cf_bestshot_destroy", "table"      # (no clear: entries leave through the collect)
+
     def __init__(self, engine_or_device, streams, size=112, entries=320, min_hits=2, terms=("size", "pose", "score")):
-        self._L = _lib.lib()
-        self._o = _lib.bestshot_opts(size, entries, min_hits, terms)
-        self.streams, self.size, self.entries = int(streams), int(size), int(entries)
-        self._h = None
-        if isinstance(engine_or_device, Engine):
-            self.device = engine_or_device.device
-            self._handle(engine_or_device)
-        else:
-            self.device = int(engine_or_device)
-            # refuse bad options now, not at the first offer (no context: the library checks the arguments and tells)
-            out = C.c_void_p()
-            self._L.cf_bestshot_create(None, self.streams, C.byref(self._o), C.byref(out))
-            why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
-            if "null context" not in why:
-                raise _lib.CenterFaceValueError(-1, why)
-
-    def _handle(self, engine):
-        """The cf_bestshot, created with ``engine``'s context on first use."""
-        if self._h is None:
-            if engine.device != self.device:
-                raise ValueError("the table was made for device %d, the engine runs on device %d" % (self.device, engine.device))
-            out = C.c_void_p()
-            _lib.check(self._L.cf_bestshot_create(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
-            self._h = out
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.cf_bestshot_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.size, self.entries = int(size), int(entries)
+        self._open(engine_or_device, streams, _lib.bestshot_opts(size, entries, min_hits, terms))
 
 
 class EngineRing(object):

@@ -1615,6 +1615,19 @@ static int read_out(cf_ctx* c, int B, int stride, const int* d_counts, const int
     return CF_OK;
 }
 
+// The output tail of the calls that leave rows of stride `stride` for B images in the context: caller-owned DEVICE buffers take the
+// whole [B][stride][.] columns, the counts and the flags (any may be null), asynchronously; host buffers go through read_out.
+static int write_out(cf_ctx* c, int out_on_device, int B, int stride, const int* d_counts, const int* d_flags, int32_t* counts, int32_t* flags,
+                     std::initializer_list<RowCopy> cols) {
+    if (!out_on_device) return read_out(c, B, stride, d_counts, d_flags, counts, flags, cols);
+    const size_t nb = (size_t)B * sizeof(int);
+    for (const RowCopy& col : cols)
+        if (col.dst) HIPCHK(c, hipMemcpyAsync(col.dst, col.src, (size_t)B * stride * col.row_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts, d_counts, nb, hipMemcpyDeviceToDevice, c->stream));
+    if (flags && d_flags) HIPCHK(c, hipMemcpyAsync(flags, d_flags, nb, hipMemcpyDeviceToDevice, c->stream));
+    return CF_OK;
+}
+
 // Every state rule of the consumers of face rows, once: which rows `who` gets behind the last forward.
 enum RowsWanted {
     ROWS_OF_DECODE,          // the threshold decode's, whatever came after (cf_align_faces)
@@ -2078,14 +2091,7 @@ int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
     p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
     HIPCHK(c, launch_merge_tiles(c->stream, p));
     c->stage = ROWS_MERGED; c->tl_maxout = max_out;
-    if (out_on_device) {
-        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
-        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms, nl, hipMemcpyDeviceToDevice, c->stream));
-        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, nb, hipMemcpyDeviceToDevice, c->stream));
-        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, nb, hipMemcpyDeviceToDevice, c->stream));
-        return CF_OK;
-    }
-    return read_out(c, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
+    return write_out(c, out_on_device, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }
 
 // Fitted forward: the fit kernel (cf_fit.hip) writes the B padded canvases to input_resized, so the plan and its graphs are those of
@@ -2142,93 +2148,179 @@ int cf_unfit_rows(cf_ctx* c, int max_out, float* dets, float* lms, int32_t* coun
     p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
     HIPCHK(c, launch_unfit_rows(c->stream, p));
     c->stage = ROWS_MERGED; c->tl_maxout = max_out;
-    if (out_on_device) {
-        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
-        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms, nl, hipMemcpyDeviceToDevice, c->stream));
-        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, nb, hipMemcpyDeviceToDevice, c->stream));
-        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, nb, hipMemcpyDeviceToDevice, c->stream));
-        return CF_OK;
-    }
-    return read_out(c, B, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
+    return write_out(c, out_on_device, B, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }
 
-// ---- face tracks across frames (cf_track.hip).  The tracker owns the state of its streams, one event that orders its updates across
-// the contexts that issue them, and a stream of its own for what no context carries (the initial state, cf_track_reset).
+// ---- the objects that hold the state of N video streams between calls: cf_tracker (cf_track.hip, cf_follow.hip), cf_scene
+// (cf_scene.hip), cf_lookback (cf_lookback.hip) and cf_bestshot (cf_bestshot.hip).  One protocol for the four: the object owns its
+// device state, which only kernels advance, on the stream of the context that issues the call; one event orders its calls across those
+// contexts (each call waits for it on its own stream, launches there and records it again); and a stream of the object's own carries
+// what no context carries (the initial state, the clear of a range of streams).
 }  // extern "C"
-struct cf_tracker {
+struct StreamState {
     int device = 0, S = 0;
+    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
+    std::vector<void*> owned;                                           // every device allocation of the object, in the order made
+};
+// The coordinate space of the rows an object was first given; rows of another space are refused from then on.
+struct RowSpace {
+    bool latched = false, tiled = false; int h = 0, w = 0;
+    bool matches(const RowSet& r) const { return !latched || (tiled == r.frame_space && h == r.H && w == r.W); }
+    void latch(const RowSet& r) { latched = true; tiled = r.frame_space; h = r.H; w = r.W; }
+    int refuse(cf_ctx* c, const char* who, const char* whose, const RowSet& r) const {
+        return c->fail(CF_EINVAL, "%s: the %s rows are in %s %d x %d coordinates, these in %s %d x %d", who, whose, tiled ? "frame" : "network", w, h,
+                       r.frame_space ? "frame" : "network", r.W, r.H);
+    }
+};
+// (noun: what the messages call the object)
+struct cf_tracker : StreamState {
+    static constexpr const char* noun = "tracker";
     cf_track_opts o{};
     int* meta = nullptr; float* rec = nullptr; int* next_id = nullptr;
     uint8_t* fol = nullptr;                                             // the follower records (cf_track_follow), allocated by the first follow
-    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
-    bool latched = false, sp_tiled = false; int sp_h = 0, sp_w = 0;      // the coordinate space of the first update
+    RowSpace sp;                                                        // the coordinate space of the first update
 };
-extern "C" {
+struct cf_scene : StreamState {
+    static constexpr const char* noun = "scene object";
+    cf_scene_opts o{};
+    int* sig = nullptr; int* st = nullptr;
+};
+struct cf_lookback : StreamState {
+    static constexpr const char* noun = "lookback object";
+    cf_lookback_opts o{};
+    int* qmeta = nullptr; int* pend = nullptr; int* emeta = nullptr; float* rec = nullptr; int* info = nullptr;
+    RowSpace sp; int stride = 0;                                        // the row space and the stride of the first push
+};
+struct cf_bestshot : StreamState {
+    static constexpr const char* noun = "table";
+    cf_bestshot_opts o{};
+    int32_t* erec = nullptr; float* erow = nullptr; uint8_t* chips = nullptr; int32_t* smeta = nullptr;
+    BestTable table() const { return BestTable{o.size, o.entries, o.min_hits, o.terms, erec, erow, chips, smeta}; }
+};
 
-int cf_track_destroy(cf_tracker* t) {
+template <class T> static int state_destroy(T* t) {
     if (!t) return CF_OK;
     hipSetDevice(t->device);
     if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
     if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
-    for (void* p : {(void*)t->meta, (void*)t->rec, (void*)t->next_id, (void*)t->fol}) if (p) hipFree(p);
+    for (void* p : t->owned) hipFree(p);
     delete t;
     return CF_OK;
 }
 
-int cf_track_create(cf_ctx* c, int n_streams, const cf_track_opts* o, cf_tracker** out) {
-    const char* why = track_check(o, n_streams);
+// The refusals of a create, `why` being what the kind's own check found; a null context still tells why (cf_op_last_error).
+static int state_create_check(cf_ctx* c, const char* who, const char* why, const void* out) {
     if (!why && !out) why = "null out";
-    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
-        op_error_set((std::string("cf_track_create: ") + (why ? why : "null context")).c_str());
+    if (!c) {
+        op_error_set((std::string(who) + ": " + (why ? why : "null context")).c_str());
         return CF_EINVAL;
     }
-    if (why) return c->fail(CF_EINVAL, "cf_track_create: %s", why);
+    if (why) return c->fail(CF_EINVAL, "%s: %s", who, why);
     HIPCHK(c, hipSetDevice(c->device));
-    cf_tracker* t = new cf_tracker();
-    t->device = c->device; t->S = n_streams; t->o = *o;
-    const size_t slots = (size_t)n_streams * o->max_tracks;
+    return CF_OK;
+}
+
+// ... and the rest of it: the object's stream and event, every buffer of `bufs`, their initial values on the object's stream, the event
+// behind them.  Whatever fails, the object is destroyed again and the failure is told as fail_fmt (its last %s: the HIP error).
+constexpr int kNoInit = -1;
+struct StateBuf { void** slot; size_t bytes; int init; };              // init: kNoInit, 0 = zero bytes, else the value of every dword
+template <class T, class... A>
+static int state_create(cf_ctx* c, T* t, int n_streams, std::initializer_list<StateBuf> bufs, T** out, const char* fail_fmt, A... sizes) {
+    t->device = c->device; t->S = n_streams;
     hipError_t e = hipStreamCreateWithFlags(&t->ts, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->meta, slots * 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->rec, slots * 16 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->next_id, (size_t)n_streams * sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(t->meta, 0, slots * 4 * sizeof(int), t->ts);
-    if (e == hipSuccess) e = hipMemsetAsync(t->rec, 0, slots * 16 * sizeof(float), t->ts);
-    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)t->next_id, 1, (size_t)n_streams, t->ts);
+    for (const StateBuf& b : bufs)
+        if (e == hipSuccess && (e = hipMalloc(b.slot, b.bytes)) == hipSuccess) t->owned.push_back(*b.slot);
+    for (const StateBuf& b : bufs) {
+        if (e != hipSuccess || b.init == kNoInit) continue;
+        e = b.init ? hipMemsetD32Async((hipDeviceptr_t)*b.slot, b.init, b.bytes / sizeof(int), t->ts) : hipMemsetAsync(*b.slot, 0, b.bytes, t->ts);
+    }
     if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        cf_track_destroy(t);
-        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_track_create: %d streams x %d tracks: %s", n_streams, o->max_tracks, hipGetErrorString(e));
+        state_destroy(t);
+        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, fail_fmt, sizes..., hipGetErrorString(e));
     }
     *out = t;
     return CF_OK;
 }
 
-int cf_track_reset(cf_tracker* t, int stream) {
-    if (!t || stream < -1 || stream >= t->S) { op_error_set("cf_track_reset: null tracker, or a stream outside -1 .. n_streams - 1"); return CF_EINVAL; }
-    const size_t M = t->o.max_tracks, first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)t->S : 1;
+// cf_track_reset, cf_scene_forget, cf_lookback_forget: `per` words of `stream` (-1: of every stream) from `words` on take `value`, on
+// the object's own stream behind everything its event has seen.
+static int state_clear(StreamState* t, const char* who, const char* noun, int stream, int* words, size_t per, int value) {
+    if (!t || stream < -1 || stream >= t->S) {
+        op_error_set((std::string(who) + ": null " + noun + ", or a stream outside -1 .. n_streams - 1").c_str());
+        return CF_EINVAL;
+    }
+    int* at = words + (stream < 0 ? 0 : (size_t)stream) * per;
+    const size_t n = (stream < 0 ? (size_t)t->S : 1) * per;
     hipError_t e = hipSetDevice(t->device);
     if (e == hipSuccess) e = hipStreamWaitEvent(t->ts, t->ev, 0);
-    if (e == hipSuccess) e = hipMemsetAsync(t->meta + first * M * 4, 0, n * M * 4 * sizeof(int), t->ts);
+    if (e == hipSuccess) e = value ? hipMemsetD32Async((hipDeviceptr_t)at, value, n, t->ts) : hipMemsetAsync(at, 0, n * sizeof(int), t->ts);
     if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
-    if (e != hipSuccess) { op_error_set((std::string("cf_track_reset: ") + hipGetErrorString(e)).c_str()); return CF_EHIP; }
+    if (e != hipSuccess) { op_error_set((std::string(who) + ": " + hipGetErrorString(e)).c_str()); return CF_EHIP; }
     return CF_OK;
+}
+
+// The preamble of the per-frame calls, in the two parts between which some of them check something of their own: the object is there and
+// lives on the context's device; then B fits the context (bounded = false: no rows of the context are involved, or they are its own
+// forward's) and the streams stream0 .. stream0 + B - 1 are the object's.
+template <class T> static int state_here(cf_ctx* c, const char* who, const T* t) {
+    if (!t) return c->fail(CF_EINVAL, "%s: null %s", who, T::noun);
+    if (t->device != c->device) return c->fail(CF_EINVAL, "%s: the %s lives on device %d, the context on device %d", who, T::noun, t->device, c->device);
+    return CF_OK;
+}
+template <class T> static int state_range(cf_ctx* c, const char* who, const T* t, int stream0, int B, bool bounded = true) {
+    if (bounded && B > c->max_batch) return c->fail(CF_EINVAL, "%s: B=%d exceeds max_batch %d", who, B, c->max_batch);
+    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "%s: streams %d .. %d of a %s with %d", who, stream0, stream0 + B - 1, T::noun, t->S);
+    return CF_OK;
+}
+
+// The ordering bracket of a per-frame call on the context's stream: behind the last call of the object `a` (and of `b`, if any), on
+// whichever context's stream it was -- the launch -- and the events again behind it.  The halves stand alone where staging copies
+// lie between the wait and the launch (cf_track_follow, cf_scene_check: the launch and the records are in their on_frames lambda).
+static hipError_t order_wait(cf_ctx* c, const StreamState* a, const StreamState* b = nullptr) {
+    const hipError_t e = hipStreamWaitEvent(c->stream, a->ev, 0);
+    return e != hipSuccess || !b ? e : hipStreamWaitEvent(c->stream, b->ev, 0);
+}
+template <class F> static hipError_t order_launch(cf_ctx* c, const StreamState* a, const StreamState* b, F&& launch) {
+    hipError_t e = launch();
+    if (e == hipSuccess) e = hipEventRecord(a->ev, c->stream);
+    if (e == hipSuccess && b) e = hipEventRecord(b->ev, c->stream);
+    return e;
+}
+template <class F> static hipError_t ordered(cf_ctx* c, const StreamState* a, F&& launch) {
+    const hipError_t e = order_wait(c, a);
+    return e != hipSuccess ? e : order_launch(c, a, nullptr, launch);
+}
+extern "C" {
+
+// ---- face tracks across frames (cf_track.hip)
+int cf_track_destroy(cf_tracker* t) { return state_destroy(t); }
+
+int cf_track_create(cf_ctx* c, int n_streams, const cf_track_opts* o, cf_tracker** out) {
+    if (int r = state_create_check(c, "cf_track_create", track_check(o, n_streams), out)) return r;
+    cf_tracker* t = new cf_tracker();
+    t->o = *o;
+    const size_t slots = (size_t)n_streams * o->max_tracks;
+    return state_create(c, t, n_streams, {{(void**)&t->meta, slots * 4 * sizeof(int), 0}, {(void**)&t->rec, slots * 16 * sizeof(float), 0},
+                                          {(void**)&t->next_id, (size_t)n_streams * sizeof(int), 1}},
+                        out, "cf_track_create: %d streams x %d tracks: %s", n_streams, o->max_tracks);
+}
+
+int cf_track_reset(cf_tracker* t, int stream) {
+    return state_clear(t, "cf_track_reset", "tracker", stream, t ? t->meta : nullptr, t ? (size_t)t->o.max_tracks * 4 : 0, 0);
 }
 
 int cf_track_update(cf_ctx* c, cf_tracker* t, int stream0, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags,
                     int out_on_device) {
     if (!c) return CF_EINVAL;
-    if (!t) return c->fail(CF_EINVAL, "cf_track_update: null tracker");
-    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_track_update: the tracker lives on device %d, the context on device %d", t->device, c->device);
+    if (int r = state_here(c, "cf_track_update", t)) return r;
     RowSet in{};
     if (int r = rows_for(c, "cf_track_update", ROWS_UNTRACKED, in)) return r;
-    const bool tiled = in.frame_space;
     const int B = in.B, M = t->o.max_tracks;
-    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_track_update: streams %d .. %d of a tracker with %d", stream0, stream0 + B - 1, t->S);
-    if (t->latched && (t->sp_tiled != tiled || t->sp_h != in.H || t->sp_w != in.W))
-        return c->fail(CF_EINVAL, "cf_track_update: the tracker's rows are in %s %d x %d coordinates, these in %s %d x %d", t->sp_tiled ? "frame" : "network", t->sp_w, t->sp_h,
-                       tiled ? "frame" : "network", in.W, in.H);
+    if (int r = state_range(c, "cf_track_update", t, stream0, B, false)) return r;      // (B is the forward's: max_batch bounded it there)
+    if (!t->sp.matches(in)) return t->sp.refuse(c, "cf_track_update", "tracker's", in);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bm = (size_t)B * M, nb = (size_t)B * sizeof(int);
     const size_t nd = bm * 5 * sizeof(float), nl = bm * 10 * sizeof(float), ni = bm * 3 * sizeof(int);
@@ -2244,21 +2336,11 @@ int cf_track_update(cf_ctx* c, cf_tracker* t, int stream0, float* dets, float* l
     p.meta = t->meta; p.rec = t->rec; p.next_id = t->next_id;
     p.dets = (float*)ws.dets.p; p.lms_out = (float*)ws.lms.p; p.info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
     p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
-    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the update before this one, on whichever context's stream
-    HIPCHK(c, launch_track_update(c->stream, p));
-    HIPCHK(c, hipEventRecord(t->ev, c->stream));
-    t->latched = true; t->sp_tiled = tiled; t->sp_h = in.H; t->sp_w = in.W;
+    HIPCHK(c, ordered(c, t, [&] { return launch_track_update(c->stream, p); }));
+    t->sp.latch(in);
     c->stage = ROWS_TRACKED; c->tk_M = M; c->fo.B = 0; c->lb.B = 0; c->lb.pushed = false;
-    if (out_on_device) {
-        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
-        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, nl, hipMemcpyDeviceToDevice, c->stream));
-        if (info) HIPCHK(c, hipMemcpyAsync(info, p.info, ni, hipMemcpyDeviceToDevice, c->stream));
-        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, nb, hipMemcpyDeviceToDevice, c->stream));
-        if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, nb, hipMemcpyDeviceToDevice, c->stream));
-        return CF_OK;
-    }
-    return read_out(c, B, M, p.out_counts, p.flags, counts, flags,
-                    {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)}});
+    return write_out(c, out_on_device, B, M, p.out_counts, p.flags, counts, flags,
+                     {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)}});
 }
 
 // The follow (cf_follow.hip) of the streams stream0 .. stream0 + B - 1 in the caller's frames: ordered on the tracker's event like an update,
@@ -2273,13 +2355,12 @@ int cf_track_follow(cf_ctx* c, cf_tracker* t, int stream0, int B, const cf_follo
         return CF_EINVAL;
     }
     if (why) return c->fail(CF_EINVAL, "cf_track_follow: %s", why);
-    if (!t) return c->fail(CF_EINVAL, "cf_track_follow: null tracker");
-    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_track_follow: the tracker lives on device %d, the context on device %d", t->device, c->device);
-    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_track_follow: B=%d exceeds max_batch %d", B, c->max_batch);
-    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_track_follow: streams %d .. %d of a tracker with %d", stream0, stream0 + B - 1, t->S);
-    if (!t->latched) return c->fail(CF_ESTATE, "cf_track_follow before the tracker's first cf_track_update: its rows have no coordinate space yet");
-    if (t->sp_tiled && (h != t->sp_h || w != t->sp_w))
-        return c->fail(CF_EINVAL, "cf_track_follow: %d x %d frames, the tracker's rows are in frame %d x %d coordinates", w, h, t->sp_w, t->sp_h);
+    if (int r = state_here(c, "cf_track_follow", t)) return r;
+    if (int r = state_range(c, "cf_track_follow", t, stream0, B)) return r;
+    const RowSpace& sp = t->sp;
+    if (!sp.latched) return c->fail(CF_ESTATE, "cf_track_follow before the tracker's first cf_track_update: its rows have no coordinate space yet");
+    if (sp.tiled && (h != sp.h || w != sp.w))
+        return c->fail(CF_EINVAL, "cf_track_follow: %d x %d frames, the tracker's rows are in frame %d x %d coordinates", w, h, sp.w, sp.h);
     HIPCHK(c, hipSetDevice(c->device));
     const int M = t->o.max_tracks;
     const size_t slots = (size_t)t->S * M, bm = (size_t)B * M, nb = (size_t)B * sizeof(int);
@@ -2289,18 +2370,19 @@ int cf_track_follow(cf_ctx* c, cf_tracker* t, int stream0, int B, const cf_follo
         {ws.dets, nd, "tracked dets"}, {ws.lms, nl, "tracked landmarks"}, {ws.info, ni, "track info"},
         {ws.corners, bm * 4 * sizeof(float), "tracked corners"}, {ws.counts, nb, "tracked counts"}, {c->fo.slot_moves, nm, "moves per slot"}, {c->fo.moves, nm, "moves"}};
     for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_track_follow")) return r;
-    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the update or follow before this one, on whichever context's stream
+    HIPCHK(c, order_wait(c, t));
     if (!t->fol) {
         const hipError_t e = hipMalloc((void**)&t->fol, slots * kFollowSlotBytes);
         if (e != hipSuccess) {
             (void)hipGetLastError(); t->fol = nullptr;
             return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_track_follow: %zu bytes of follower records: %s", slots * kFollowSlotBytes, hipGetErrorString(e));
         }
+        t->owned.push_back(t->fol);
         HIPCHK(c, hipMemsetAsync(t->fol, 0, slots * kFollowSlotBytes, c->stream));      // tpl_id 0 is no track's id: every slot learns first
     }
     FollowParams p{};
     p.search = o->search; p.max_sad = o->max_sad;
-    p.fx = t->sp_tiled ? 1.0 : (double)w / (double)t->sp_w; p.fy = t->sp_tiled ? 1.0 : (double)h / (double)t->sp_h;
+    p.fx = sp.tiled ? 1.0 : (double)w / (double)sp.w; p.fy = sp.tiled ? 1.0 : (double)h / (double)sp.h;
     p.stream0 = stream0; p.max_tracks = M; p.hold_grow = t->o.hold_grow; p.meta = t->meta; p.rec = t->rec;
     p.tpl = t->fol; p.tmeta = (int*)(t->fol + slots * kFollowSide * kFollowSide); p.slot_moves = (int*)c->fo.slot_moves.p;
     p.dets = (float*)ws.dets.p; p.lms_out = (float*)ws.lms.p; p.info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
@@ -2309,31 +2391,19 @@ int cf_track_follow(cf_ctx* c, cf_tracker* t, int stream0, int B, const cf_follo
     // host frames are only read: staged, not copied back
     if (int r = on_frames(c, "cf_track_follow", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, on_device, false, [&](const void* const* pl, int p0, int p1) {
             p.g = FrameGeo{format, B, h, w, p0, p1}; p.planes = pl;
-            const hipError_t e = launch_track_follow(c->stream, p);
-            return e != hipSuccess ? e : hipEventRecord(t->ev, c->stream);
+            return order_launch(c, t, nullptr, [&] { return launch_track_follow(c->stream, p); });
         })) return r;
-    c->tk_M = M; c->fo.B = B; c->fo.H = t->sp_h; c->fo.W = t->sp_w; c->fo.tiled = t->sp_tiled; c->lb.pushed = false;
-    if (out_on_device) {
-        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
-        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms_out, nl, hipMemcpyDeviceToDevice, c->stream));
-        if (info) HIPCHK(c, hipMemcpyAsync(info, p.info, ni, hipMemcpyDeviceToDevice, c->stream));
-        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.out_counts, nb, hipMemcpyDeviceToDevice, c->stream));
-        if (moves) HIPCHK(c, hipMemcpyAsync(moves, p.moves, nm, hipMemcpyDeviceToDevice, c->stream));
-        return CF_OK;
-    }
-    return read_out(c, B, M, p.out_counts, nullptr, counts, nullptr,
-                    {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)}, {moves, p.moves, 4 * sizeof(int)}});
+    c->tk_M = M; c->fo.B = B; c->fo.H = sp.h; c->fo.W = sp.w; c->fo.tiled = sp.tiled; c->lb.pushed = false;
+    // (no flags; on the device the moves go behind the counts, so they are no column of that form)
+    if (int r = write_out(c, out_on_device, B, M, p.out_counts, nullptr, counts, nullptr,
+                          {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms_out, 10 * sizeof(float)}, {info, p.info, 3 * sizeof(int)},
+                           {out_on_device ? nullptr : moves, p.moves, 4 * sizeof(int)}})) return r;
+    if (out_on_device && moves) HIPCHK(c, hipMemcpyAsync(moves, p.moves, nm, hipMemcpyDeviceToDevice, c->stream));
+    return CF_OK;
 }
 
-// ---- scene cuts (cf_scene.hip).  The object owns the state of its streams, one event that orders its checks across the contexts that
-// issue them, and a stream of its own for what no context carries (the initial state, cf_scene_forget).
+// ---- scene cuts (cf_scene.hip)
 }  // extern "C"
-struct cf_scene {
-    int device = 0, S = 0;
-    cf_scene_opts o{};
-    int* sig = nullptr; int* st = nullptr;
-    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
-};
 static const char* scene_create_check(const cf_scene_opts* o, int n_streams) {
     if (const char* why = scene_check(o, CF_FRAME_BGR, 1, 8, 8, 24, 0)) return why;      // the options alone
     if (n_streams < 1 || n_streams > kTrackMaxStreams) return "n_streams must be in 1..4096";
@@ -2341,54 +2411,17 @@ static const char* scene_create_check(const cf_scene_opts* o, int n_streams) {
 }
 extern "C" {
 
-int cf_scene_destroy(cf_scene* t) {
-    if (!t) return CF_OK;
-    hipSetDevice(t->device);
-    if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
-    if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
-    for (void* p : {(void*)t->sig, (void*)t->st}) if (p) hipFree(p);
-    delete t;
-    return CF_OK;
-}
+int cf_scene_destroy(cf_scene* t) { return state_destroy(t); }
 
 int cf_scene_create(cf_ctx* c, int n_streams, const cf_scene_opts* o, cf_scene** out) {
-    const char* why = scene_create_check(o, n_streams);
-    if (!why && !out) why = "null out";
-    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
-        op_error_set((std::string("cf_scene_create: ") + (why ? why : "null context")).c_str());
-        return CF_EINVAL;
-    }
-    if (why) return c->fail(CF_EINVAL, "cf_scene_create: %s", why);
-    HIPCHK(c, hipSetDevice(c->device));
+    if (int r = state_create_check(c, "cf_scene_create", scene_create_check(o, n_streams), out)) return r;
     cf_scene* t = new cf_scene();
-    t->device = c->device; t->S = n_streams; t->o = *o;
-    const size_t nsig = (size_t)n_streams * kSceneSig * sizeof(int), nst = (size_t)n_streams * 4 * sizeof(int);
-    hipError_t e = hipStreamCreateWithFlags(&t->ts, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->sig, nsig);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->st, nst);
-    if (e == hipSuccess) e = hipMemsetAsync(t->sig, 0, nsig, t->ts);
-    if (e == hipSuccess) e = hipMemsetAsync(t->st, 0, nst, t->ts);
-    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        cf_scene_destroy(t);
-        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_scene_create: %d streams: %s", n_streams, hipGetErrorString(e));
-    }
-    *out = t;
-    return CF_OK;
+    t->o = *o;
+    return state_create(c, t, n_streams, {{(void**)&t->sig, (size_t)n_streams * kSceneSig * sizeof(int), 0}, {(void**)&t->st, (size_t)n_streams * 4 * sizeof(int), 0}},
+                        out, "cf_scene_create: %d streams: %s", n_streams);
 }
 
-int cf_scene_forget(cf_scene* t, int stream) {
-    if (!t || stream < -1 || stream >= t->S) { op_error_set("cf_scene_forget: null object, or a stream outside -1 .. n_streams - 1"); return CF_EINVAL; }
-    const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)t->S : 1;
-    hipError_t e = hipSetDevice(t->device);
-    if (e == hipSuccess) e = hipStreamWaitEvent(t->ts, t->ev, 0);
-    if (e == hipSuccess) e = hipMemsetAsync(t->st + first * 4, 0, n * 4 * sizeof(int), t->ts);
-    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
-    if (e != hipSuccess) { op_error_set((std::string("cf_scene_forget: ") + hipGetErrorString(e)).c_str()); return CF_EHIP; }
-    return CF_OK;
-}
+int cf_scene_forget(cf_scene* t, int stream) { return state_clear(t, "cf_scene_forget", "object", stream, t ? t->st : nullptr, 4, 0); }
 
 // The check of the streams stream0 .. stream0 + B - 1 in the caller's frames: ordered on the scene object's event and, with a tracker,
 // on the tracker's; it reads and writes the object's state and the tracker's meta words, and nothing of the rows the context holds.
@@ -2403,12 +2436,10 @@ int cf_scene_check(cf_ctx* c, cf_scene* t, cf_tracker* trk, int stream0, int B, 
         return CF_EINVAL;
     }
     if (why) return c->fail(CF_EINVAL, "cf_scene_check: %s", why);
-    if (!t) return c->fail(CF_EINVAL, "cf_scene_check: null scene object");
-    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_scene_check: the scene object lives on device %d, the context on device %d", t->device, c->device);
-    if (trk && trk->device != c->device) return c->fail(CF_EINVAL, "cf_scene_check: the tracker lives on device %d, the context on device %d", trk->device, c->device);
-    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_scene_check: B=%d exceeds max_batch %d", B, c->max_batch);
-    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_scene_check: streams %d .. %d of a scene object with %d", stream0, stream0 + B - 1, t->S);
-    if (trk && (long long)stream0 + B > trk->S) return c->fail(CF_EINVAL, "cf_scene_check: streams %d .. %d of a tracker with %d", stream0, stream0 + B - 1, trk->S);
+    if (int r = state_here(c, "cf_scene_check", t)) return r;
+    if (trk) if (int r = state_here(c, "cf_scene_check", trk)) return r;
+    if (int r = state_range(c, "cf_scene_check", t, stream0, B)) return r;
+    if (trk) if (int r = state_range(c, "cf_scene_check", trk, stream0, B, false)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t no = (size_t)B * 4 * sizeof(int);
     if (int r = grow(c, c->sn.part, scene_part_bytes(B, h), "scene partial sums", "cf_scene_check")) return r;
@@ -2417,15 +2448,11 @@ int cf_scene_check(cf_ctx* c, cf_scene* t, cf_tracker* trk, int stream0, int B, 
     p.hist_thresh = t->o.hist_thresh; p.grid_thresh = t->o.grid_thresh; p.stream0 = stream0; p.sig = t->sig; p.st = t->st;
     p.meta = trk ? trk->meta : nullptr; p.max_tracks = trk ? trk->o.max_tracks : 0;
     p.part = (int*)c->sn.part.p; p.out = out_on_device && out ? out : (int*)c->sn.out.p;
-    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the check before this one, on whichever context's stream
-    if (trk) HIPCHK(c, hipStreamWaitEvent(c->stream, trk->ev, 0));       // and the tracker's last update, follow or reset
+    HIPCHK(c, order_wait(c, t, trk));                                    // the check before this one, and the tracker's last update, follow or reset
     // host frames are only read: staged, not copied back
     if (int r = on_frames(c, "cf_scene_check", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, on_device, false, [&](const void* const* pl, int p0, int p1) {
             p.g = FrameGeo{format, B, h, w, p0, p1}; p.planes = pl;
-            hipError_t e = launch_scene_check(c->stream, p);
-            if (e == hipSuccess) e = hipEventRecord(t->ev, c->stream);
-            if (e == hipSuccess && trk) e = hipEventRecord(trk->ev, c->stream);
-            return e;
+            return order_launch(c, t, trk, [&] { return launch_scene_check(c->stream, p); });
         })) return r;
     if (out_on_device || !out) return CF_OK;
     HIPCHK(c, hipMemcpyAsync(out, p.out, no, hipMemcpyDeviceToHost, c->stream));
@@ -2433,71 +2460,21 @@ int cf_scene_check(cf_ctx* c, cf_scene* t, cf_tracker* trk, int stream0, int B, 
     return CF_OK;
 }
 
-// ---- lookback (cf_lookback.hip).  The object owns the queues of its streams, one event that orders its steps across the contexts that
-// issue them, and a stream of its own for what no context carries (the initial state, cf_lookback_forget).
-}  // extern "C"
-struct cf_lookback {
-    int device = 0, S = 0;
-    cf_lookback_opts o{};
-    int* qmeta = nullptr; int* pend = nullptr; int* emeta = nullptr; float* rec = nullptr; int* info = nullptr;
-    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
-    bool latched = false, sp_tiled = false; int sp_h = 0, sp_w = 0, stride = 0;      // the row space and the stride of the first push
-};
-extern "C" {
-
-int cf_lookback_destroy(cf_lookback* t) {
-    if (!t) return CF_OK;
-    hipSetDevice(t->device);
-    if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
-    if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
-    for (void* p : {(void*)t->qmeta, (void*)t->pend, (void*)t->emeta, (void*)t->rec, (void*)t->info}) if (p) hipFree(p);
-    delete t;
-    return CF_OK;
-}
+// ---- lookback (cf_lookback.hip)
+int cf_lookback_destroy(cf_lookback* t) { return state_destroy(t); }
 
 int cf_lookback_create(cf_ctx* c, int n_streams, const cf_lookback_opts* o, cf_lookback** out) {
-    const char* why = lookback_check(o, n_streams);
-    if (!why && !out) why = "null out";
-    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
-        op_error_set((std::string("cf_lookback_create: ") + (why ? why : "null context")).c_str());
-        return CF_EINVAL;
-    }
-    if (why) return c->fail(CF_EINVAL, "cf_lookback_create: %s", why);
-    HIPCHK(c, hipSetDevice(c->device));
+    if (int r = state_create_check(c, "cf_lookback_create", lookback_check(o, n_streams), out)) return r;
     cf_lookback* t = new cf_lookback();
-    t->device = c->device; t->S = n_streams; t->o = *o;
+    t->o = *o;
     const size_t S = (size_t)n_streams, entries = S * (o->depth + 1), rows = entries * o->rows;
-    hipError_t e = hipStreamCreateWithFlags(&t->ts, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->qmeta, S * 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->pend, S * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->emeta, entries * 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->rec, rows * 16 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->info, rows * 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(t->qmeta, 0, S * 4 * sizeof(int), t->ts);
-    if (e == hipSuccess) e = hipMemsetAsync(t->pend, 0, S * sizeof(int), t->ts);
-    if (e == hipSuccess) e = hipMemsetAsync(t->emeta, 0, entries * 4 * sizeof(int), t->ts);
-    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        cf_lookback_destroy(t);
-        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_lookback_create: %d streams x %d entries x %d rows: %s", n_streams, o->depth + 1, o->rows,
-                       hipGetErrorString(e));
-    }
-    *out = t;
-    return CF_OK;
+    return state_create(c, t, n_streams, {{(void**)&t->qmeta, S * 4 * sizeof(int), 0}, {(void**)&t->pend, S * sizeof(int), 0},
+                                          {(void**)&t->emeta, entries * 4 * sizeof(int), 0}, {(void**)&t->rec, rows * 16 * sizeof(float), kNoInit},
+                                          {(void**)&t->info, rows * 4 * sizeof(int), kNoInit}},
+                        out, "cf_lookback_create: %d streams x %d entries x %d rows: %s", n_streams, o->depth + 1, o->rows);
 }
 
-int cf_lookback_forget(cf_lookback* t, int stream) {
-    if (!t || stream < -1 || stream >= t->S) { op_error_set("cf_lookback_forget: null object, or a stream outside -1 .. n_streams - 1"); return CF_EINVAL; }
-    const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)t->S : 1;
-    hipError_t e = hipSetDevice(t->device);
-    if (e == hipSuccess) e = hipStreamWaitEvent(t->ts, t->ev, 0);
-    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)(t->pend + first), 1, n, t->ts);
-    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
-    if (e != hipSuccess) { op_error_set((std::string("cf_lookback_forget: ") + hipGetErrorString(e)).c_str()); return CF_EHIP; }
-    return CF_OK;
-}
+int cf_lookback_forget(cf_lookback* t, int stream) { return state_clear(t, "cf_lookback_forget", "object", stream, t ? t->pend : nullptr, 1, 1); }
 
 // One step of the streams stream0 .. stream0 + B - 1: ordered on the object's event like a tracker's update; a push reads the context's
 // tracked rows (rows_for), and the context's lookback rows are written in any case.
@@ -2509,21 +2486,18 @@ int cf_lookback_step(cf_ctx* c, cf_lookback* t, int stream0, int B, int push, co
         return CF_EINVAL;
     }
     if (why) return c->fail(CF_EINVAL, "cf_lookback_step: %s", why);
-    if (!t) return c->fail(CF_EINVAL, "cf_lookback_step: null lookback object");
-    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_lookback_step: the lookback object lives on device %d, the context on device %d", t->device, c->device);
-    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_lookback_step: B=%d exceeds max_batch %d", B, c->max_batch);
-    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_lookback_step: streams %d .. %d of a lookback object with %d", stream0, stream0 + B - 1, t->S);
+    if (int r = state_here(c, "cf_lookback_step", t)) return r;
+    if (int r = state_range(c, "cf_lookback_step", t, stream0, B)) return r;
     RowSet in{};
     const int R = t->o.rows;
+    RowSpace& sp = t->sp;
     if (push) {
         if (int r = rows_for(c, "cf_lookback_step", ROWS_UNSTEPPED, in)) return r;
         if (in.B != B) return c->fail(CF_ESTATE, "cf_lookback_step: B=%d, the tracked rows are those of %d images", B, in.B);
-        if (t->latched && (t->sp_tiled != in.frame_space || t->sp_h != in.H || t->sp_w != in.W))
-            return c->fail(CF_EINVAL, "cf_lookback_step: the queued rows are in %s %d x %d coordinates, these in %s %d x %d", t->sp_tiled ? "frame" : "network", t->sp_w, t->sp_h,
-                           in.frame_space ? "frame" : "network", in.W, in.H);
-        if (t->latched ? in.stride != t->stride : in.stride > R)
-            return c->fail(CF_EINVAL, "cf_lookback_step: %d tracked rows per image, the object %s %d", in.stride, t->latched ? "was first given" : "holds at most", t->latched ? t->stride : R);
-    } else if (!t->latched) {
+        if (!sp.matches(in)) return sp.refuse(c, "cf_lookback_step", "queued", in);
+        if (sp.latched ? in.stride != t->stride : in.stride > R)
+            return c->fail(CF_EINVAL, "cf_lookback_step: %d tracked rows per image, the object %s %d", in.stride, sp.latched ? "was first given" : "holds at most", sp.latched ? t->stride : R);
+    } else if (!sp.latched) {
         return c->fail(CF_ESTATE, "cf_lookback_step: a drain before the object's first push: its rows have no coordinate space yet");
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -2549,55 +2523,22 @@ int cf_lookback_step(cf_ctx* c, cf_lookback* t, int stream0, int B, int push, co
     p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.out_info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
     p.counts = (int*)ws.counts.p; p.state = (int*)ws.state.p;
     c->lb.B = 0;                                                          // (a failure below leaves no lookback rows behind)
-    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the step before this one, on whichever context's stream
-    HIPCHK(c, launch_lookback_step(c->stream, p));
-    HIPCHK(c, hipEventRecord(t->ev, c->stream));
-    if (push) { t->sp_tiled = in.frame_space; t->sp_h = in.H; t->sp_w = in.W; t->stride = in.stride; t->latched = true; c->lb.pushed = true; }
-    c->lb.B = B; c->lb.M = R; c->lb.H = t->sp_h; c->lb.W = t->sp_w; c->lb.tiled = t->sp_tiled;
-    if (out_on_device) {
-        if (dets) HIPCHK(c, hipMemcpyAsync(dets, p.dets, nd, hipMemcpyDeviceToDevice, c->stream));
-        if (lms) HIPCHK(c, hipMemcpyAsync(lms, p.lms, nl, hipMemcpyDeviceToDevice, c->stream));
-        if (info) HIPCHK(c, hipMemcpyAsync(info, p.out_info, ni, hipMemcpyDeviceToDevice, c->stream));
-        if (counts) HIPCHK(c, hipMemcpyAsync(counts, p.counts, nb, hipMemcpyDeviceToDevice, c->stream));
-        if (state) HIPCHK(c, hipMemcpyAsync(state, p.state, ns, hipMemcpyDeviceToDevice, c->stream));
-        return CF_OK;
-    }
-    if (state) HIPCHK(c, hipMemcpyAsync(state, p.state, ns, hipMemcpyDeviceToHost, c->stream));
-    return read_out(c, B, R, p.counts, nullptr, counts, nullptr,
-                    {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}, {info, p.out_info, 3 * sizeof(int)}});
-}
-
-// Best-shot selection (cf_bestshot.hip): the table's state lives in device memory the table owns and is advanced only by kernels, on the
-// stream of the context that issues the call; the calls are ordered on the table's event exactly as a tracker's are.
-}  // extern "C"
-struct cf_bestshot {
-    int device = 0, S = 0;
-    cf_bestshot_opts o{};
-    int32_t* erec = nullptr; float* erow = nullptr; uint8_t* chips = nullptr; int32_t* smeta = nullptr;
-    hipStream_t ts = nullptr; hipEvent_t ev = nullptr;
-    BestTable table() const { return BestTable{o.size, o.entries, o.min_hits, o.terms, erec, erow, chips, smeta}; }
-};
-extern "C" {
-
-int cf_bestshot_destroy(cf_bestshot* t) {
-    if (!t) return CF_OK;
-    hipSetDevice(t->device);
-    if (t->ev) { hipEventSynchronize(t->ev); hipEventDestroy(t->ev); }
-    if (t->ts) { hipStreamSynchronize(t->ts); hipStreamDestroy(t->ts); }
-    for (void* p : {(void*)t->erec, (void*)t->erow, (void*)t->chips, (void*)t->smeta}) if (p) hipFree(p);
-    delete t;
+    HIPCHK(c, ordered(c, t, [&] { return launch_lookback_step(c->stream, p); }));
+    if (push) { sp.latch(in); t->stride = in.stride; c->lb.pushed = true; }
+    c->lb.B = B; c->lb.M = R; c->lb.H = sp.h; c->lb.W = sp.w; c->lb.tiled = sp.tiled;
+    // the state words: ahead of the rows' wait on the host, behind the counts on the device
+    if (state && !out_on_device) HIPCHK(c, hipMemcpyAsync(state, p.state, ns, hipMemcpyDeviceToHost, c->stream));
+    if (int r = write_out(c, out_on_device, B, R, p.counts, nullptr, counts, nullptr,
+                          {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}, {info, p.out_info, 3 * sizeof(int)}})) return r;
+    if (state && out_on_device) HIPCHK(c, hipMemcpyAsync(state, p.state, ns, hipMemcpyDeviceToDevice, c->stream));
     return CF_OK;
 }
 
+// ---- best-shot selection (cf_bestshot.hip)
+int cf_bestshot_destroy(cf_bestshot* t) { return state_destroy(t); }
+
 int cf_bestshot_create(cf_ctx* c, int n_streams, const cf_bestshot_opts* o, cf_bestshot** out) {
-    const char* why = best_check(o, n_streams);
-    if (!why && !out) why = "null out";
-    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
-        op_error_set((std::string("cf_bestshot_create: ") + (why ? why : "null context")).c_str());
-        return CF_EINVAL;
-    }
-    if (why) return c->fail(CF_EINVAL, "cf_bestshot_create: %s", why);
-    HIPCHK(c, hipSetDevice(c->device));
+    if (int r = state_create_check(c, "cf_bestshot_create", best_check(o, n_streams), out)) return r;
     const size_t slots = (size_t)n_streams * o->entries, one = best_chip_bytes(o->size);
     const size_t nrec = slots * kBestRecInts * sizeof(int32_t), nrow = slots * kBestRowFloats * sizeof(float), nmeta = (size_t)n_streams * kBestStreamInts * sizeof(int32_t);
     const double need = (double)slots * (double)one + (double)nrec + (double)nrow + (double)nmeta;
@@ -2607,24 +2548,10 @@ int cf_bestshot_create(cf_ctx* c, int n_streams, const cf_bestshot_opts* o, cf_b
         return c->fail(CF_ENOMEM, "cf_bestshot_create: %d streams x %d entries of %d x %d chips need %.1f MB, the device has %.1f MB free", n_streams, o->entries,
                        o->size, o->size, need / 1e6, (double)mem_free / 1e6);
     cf_bestshot* t = new cf_bestshot();
-    t->device = c->device; t->S = n_streams; t->o = *o;
-    hipError_t e = hipStreamCreateWithFlags(&t->ts, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->erec, nrec);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->erow, nrow);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->chips, slots * one);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->smeta, nmeta);
-    if (e == hipSuccess) e = hipMemsetAsync(t->erec, 0, nrec, t->ts);       // every entry FREE
-    if (e == hipSuccess) e = hipMemsetAsync(t->erow, 0, nrow, t->ts);
-    if (e == hipSuccess) e = hipMemsetAsync(t->smeta, 0, nmeta, t->ts);     // t = seq = 0, no flag
-    if (e == hipSuccess) e = hipEventRecord(t->ev, t->ts);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        cf_bestshot_destroy(t);
-        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_bestshot_create: %d streams x %d entries: %s", n_streams, o->entries, hipGetErrorString(e));
-    }
-    *out = t;
-    return CF_OK;
+    t->o = *o;
+    // zeros: every entry FREE; t = seq = 0, no flag
+    return state_create(c, t, n_streams, {{(void**)&t->erec, nrec, 0}, {(void**)&t->erow, nrow, 0}, {(void**)&t->chips, slots * one, kNoInit}, {(void**)&t->smeta, nmeta, 0}},
+                        out, "cf_bestshot_create: %d streams x %d entries: %s", n_streams, o->entries);
 }
 
 int cf_bestshot_offer(cf_ctx* c, cf_bestshot* t, int stream0, int B, const void* chips, const int32_t* offsets, int cap_faces, int on_device,
@@ -2641,9 +2568,8 @@ int cf_bestshot_offer(cf_ctx* c, cf_bestshot* t, int stream0, int B, const void*
         return CF_EINVAL;
     }
     if (why) return c->fail(CF_EINVAL, "cf_bestshot_offer: %s", why);
-    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_bestshot_offer: the table lives on device %d, the context on device %d", t->device, c->device);
-    if (B > c->max_batch) return c->fail(CF_EINVAL, "cf_bestshot_offer: B=%d exceeds max_batch %d", B, c->max_batch);
-    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_bestshot_offer: streams %d .. %d of a table with %d", stream0, stream0 + B - 1, t->S);
+    if (int r = state_here(c, "cf_bestshot_offer", t)) return r;           // (a null table was refused above, ahead of the other arguments)
+    if (int r = state_range(c, "cf_bestshot_offer", t, stream0, B)) return r;
     RowSet rows{};
     if (int r = rows_for(c, "cf_bestshot_offer", ROWS_NEWEST, rows)) return r;
     if (!rows.info) return c->fail(CF_ESTATE, "cf_bestshot_offer without a cf_track_update or cf_track_follow behind the last decode: the rows have no ids");
@@ -2674,9 +2600,7 @@ int cf_bestshot_offer(cf_ctx* c, cf_bestshot* t, int stream0, int B, const void*
         if (cap_faces > 0) HIPCHK(c, hipMemcpyAsync(ws.chips.p, chips, (size_t)cap_faces * one, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(ws.off.p, offsets, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
-    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the offer or collect before this one, on whichever context's stream
-    HIPCHK(c, launch_best_offer(c->stream, p));
-    HIPCHK(c, hipEventRecord(t->ev, c->stream));
+    HIPCHK(c, ordered(c, t, [&] { return launch_best_offer(c->stream, p); }));
     if (!out_on_device) {
         if (quality && cap_faces > 0) HIPCHK(c, hipMemcpyAsync(quality, p.q, (size_t)cap_faces * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
         if (flags) HIPCHK(c, hipMemcpyAsync(flags, p.flags, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -2688,10 +2612,9 @@ int cf_bestshot_offer(cf_ctx* c, cf_bestshot* t, int stream0, int B, const void*
 int cf_bestshot_collect(cf_ctx* c, cf_bestshot* t, int stream0, int B, int cap, int flush, void* chips, int64_t* quality, int32_t* records,
                         float* dets, float* lms, int32_t* counts, int32_t* pending, int32_t* flags, int out_on_device) {
     if (!c) return CF_EINVAL;
-    if (!t) return c->fail(CF_EINVAL, "cf_bestshot_collect: null table");
-    if (t->device != c->device) return c->fail(CF_EINVAL, "cf_bestshot_collect: the table lives on device %d, the context on device %d", t->device, c->device);
-    if (B < 1) return c->fail(CF_EINVAL, "cf_bestshot_collect: B=%d is less than 1", B);      // (no rows of ctx are involved: max_batch does not bound it)
-    if (stream0 < 0 || (long long)stream0 + B > t->S) return c->fail(CF_EINVAL, "cf_bestshot_collect: streams %d .. %d of a table with %d", stream0, stream0 + B - 1, t->S);
+    if (int r = state_here(c, "cf_bestshot_collect", t)) return r;
+    if (B < 1) return c->fail(CF_EINVAL, "cf_bestshot_collect: B=%d is less than 1", B);
+    if (int r = state_range(c, "cf_bestshot_collect", t, stream0, B, false)) return r;      // (no rows of ctx are involved: max_batch does not bound it)
     if (cap < 0 || cap > t->o.entries) return c->fail(CF_EINVAL, "cf_bestshot_collect: cap=%d outside 0..entries %d", cap, t->o.entries);
     if (out_on_device && chips && (reinterpret_cast<uintptr_t>(chips) & 15)) return c->fail(CF_EINVAL, "cf_bestshot_collect: device chips must be 16-byte aligned");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2712,9 +2635,7 @@ int cf_bestshot_collect(cf_ctx* c, cf_bestshot* t, int stream0, int B, int cap, 
         p.dets = dets ? (float*)(base + o_det) : nullptr; p.lms = lms ? (float*)(base + o_lm) : nullptr;
         p.counts = (int32_t*)(base + o_cnt); p.pending = p.counts + B; p.flags = p.counts + 2 * B;
     }
-    HIPCHK(c, hipStreamWaitEvent(c->stream, t->ev, 0));                  // the offer or collect before this one, on whichever context's stream
-    HIPCHK(c, launch_best_collect(c->stream, p));
-    HIPCHK(c, hipEventRecord(t->ev, c->stream));
+    HIPCHK(c, ordered(c, t, [&] { return launch_best_collect(c->stream, p); }));
     if (out_on_device) return CF_OK;
     std::vector<int32_t> hc((size_t)3 * B);          // on this stack frame: never return while a copy into it may still be in flight
     const hipError_t e1 = hipMemcpyAsync(hc.data(), p.counts, 3 * nb, hipMemcpyDeviceToHost, c->stream);

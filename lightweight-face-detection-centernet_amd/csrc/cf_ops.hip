@@ -1,13 +1,16 @@
-// Per-op C-ABI entry points (cf_op_*): each runs ONE production kernel on host NCHW float32
-// arrays, exactly as the torch op it replaces would be called, so the parity tests can check every
-// kernel in isolation against the oracle / the reference's golden vectors.  Layout conversion
-// NCHW<->NHWC happens on the device around the kernel; there is no CPU compute path here.
+// Per-op C-ABI entry points (cf_op_*): each runs ONE production kernel, or one product sequence of them, on the caller's host arrays, so
+// the parity tests can check it in isolation against the oracle, the reference's golden vectors or a float64 restatement.  The layer ops take
+// host NCHW float32 tensors as the torch op they replace would (the layout conversion happens on the device around the kernel); the decode,
+// row and tile ops take the row tables of the ABI; the frame ops take pitched host frames, staged as the blocking product calls stage them;
+// the sequence ops (track, follow, scene, lookback, best shot) step one launch's pointers through the frames of a fresh state object.  There
+// is no CPU compute path here.  Every entry point reads the same way -- validation (before any device is touched), declarations (`Scope`'s
+// verbs below), launches, `result`.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -21,9 +24,28 @@ namespace {
 
 thread_local std::string g_op_error;
 
+// the refusal of entry point `who`
+int fail(const char* who, const char* why) { g_op_error = std::string(who) + ": " + why; return CF_EINVAL; }
+
+// Host frames staged by Scope::stage: n frames back to back in cf_frame.h's staging layout, and their device plane table
+struct Staged {
+    RedactStage st{};
+    int format = 0, n = 0, h = 0, w = 0, pitch0 = 0, pitch1 = 0;      // the host frames' own pitches
+    const void* const* host = nullptr;
+    uint8_t* base = nullptr;
+    std::vector<const void*> table;
+    // the geometry of a launch over B of the staged frames (the staged pitches), and the table from frame `first` on
+    FrameGeo geo(int B) const { return FrameGeo{format, B, h, w, st.pitch0, st.pitch1}; }
+    const void* const* planes(size_t first = 0) const { return table.data() + 3 * first; }
+};
+
+// The device side of one entry point: a stream, the allocations, the first error, and the result copies.  Nothing runs after an error
+// (`run`), and the caller's arrays are written only once every launch has completed (`result`).
 struct Scope {
     hipStream_t s = nullptr;
     std::vector<void*> ptrs;
+    struct Back { void* host; const void* dev; size_t bytes; };
+    std::vector<Back> backs;      // the result copies, in the order of their declaration
     hipError_t err = hipSuccess;
     explicit Scope(int device) {
         err = hipSetDevice(device);
@@ -33,6 +55,9 @@ struct Scope {
         if (s) { hipStreamSynchronize(s); hipStreamDestroy(s); }
         for (void* p : ptrs) hipFree(p);
     }
+    bool ok() const { return err == hipSuccess; }
+    // every launch and every HIP call of an entry point: f() runs only while nothing has failed, and its error is kept
+    template <typename F> void run(F&& f) { if (err == hipSuccess) err = f(); }
     void* alloc(size_t bytes) {
         if (err != hipSuccess) return nullptr;
         void* p = nullptr;
@@ -42,55 +67,109 @@ struct Scope {
         if (err == hipSuccess) { ptrs.push_back(p); if (bytes) hipMemsetAsync(p, 0, bytes, s); hipMemsetAsync((char*)p + bytes, 0xFF, 256, s); }
         return p;
     }
-    void* up(const void* host, size_t bytes) {
+    void* alloc_nan(size_t bytes) {
         void* p = alloc(bytes);
-        if (p && err == hipSuccess) err = hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, s);
+        run([&] { return hipMemsetAsync(p, 0xFF, bytes, s); });      // an element the kernel skips comes back as NaN
         return p;
     }
-    template <typename T> T* upv(const std::vector<T>& v) { return (T*)up(v.data(), v.size() * sizeof(T)); }
-    void chk(hipError_t e) { if (err == hipSuccess) err = e; }
+    void* up(const void* host, size_t bytes) {
+        void* p = alloc(bytes);
+        run([&] { return hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, s); });
+        return p;
+    }
+    // result() copies `bytes` at dev to host
+    void back(void* host, const void* dev, size_t bytes) { if (bytes) backs.push_back(Back{host, dev, bytes}); }
+    // n elements: scratch (zeroed), an input, an output (zeroed), an output that starts as the caller's buffer -- so that rows the kernel
+    // leaves alone come back with the caller's values.  A null output is scratch: nothing comes back.
+    template <typename T> T* make(size_t n) { return (T*)alloc(n * sizeof(T)); }
+    template <typename T> T* in(const T* host, size_t n) { return (T*)up(host, n * sizeof(T)); }
+    template <typename T> T* upv(const std::vector<T>& v) { return in(v.data(), v.size()); }
+    template <typename T> T* out(T* host, size_t n) {
+        T* p = make<T>(n);
+        if (host) back(host, p, n * sizeof(T));
+        return p;
+    }
+    template <typename T> T* inout(T* host, size_t n) {
+        T* p = host ? in(host, n) : make<T>(n);
+        if (host) back(host, p, n * sizeof(T));
+        return p;
+    }
     // host f32 NCHW -> device T NHWC
     void* to_nhwc(int dtype, const float* host, int B, int C, int H, int W) {
         size_t n = (size_t)B * C * H * W;
-        float* src = (float*)up(host, n * 4);
+        float* src = in(host, n);
         void* dst = alloc(n * elem_size(dtype));
-        if (err == hipSuccess) chk(launch_nchw_to_nhwc(s, dtype, src, dst, B, C, H, W));
+        run([&] { return launch_nchw_to_nhwc(s, dtype, src, dst, B, C, H, W); });
         return dst;
     }
     // host f32 NCHW -> device T in pixel-block order [m / 32][C / P][m % 32][P], padded to whole 32-pixel blocks as the engine's buffers are
     void* to_blocked(int dtype, const float* host, int B, int C, int H, int W) {
         size_t n = (size_t)B * C * H * W;
-        float* src = (float*)up(host, n * 4);
+        float* src = in(host, n);
         void* dst = alloc(blocked_bytes(dtype, B, C, H, W));
-        if (err == hipSuccess) chk(launch_nchw_to_blocked(s, dtype, src, dst, B, C, H, W));
+        run([&] { return launch_nchw_to_blocked(s, dtype, src, dst, B, C, H, W); });
         return dst;
     }
     static size_t blocked_bytes(int dtype, int B, int C, int H, int W) {
         return (((size_t)B * H * W + 31) / 32 * 32) * C * elem_size(dtype);
     }
-    // device T pixel-block order -> host f32 NCHW
+    // device T pixel-block order -> host f32 NCHW (an output like any other: result() copies the converted temporary)
     void blocked_to_host_nchw(int dtype, const void* dev, float* host, int B, int C, int H, int W) {
-        size_t n = (size_t)B * C * H * W;
-        float* tmp = (float*)alloc(n * 4);
-        if (err == hipSuccess) chk(launch_blocked_to_nchw(s, dtype, dev, tmp, B, C, H, W));
-        if (err == hipSuccess) chk(hipMemcpyAsync(host, tmp, n * 4, hipMemcpyDeviceToHost, s));
-        if (err == hipSuccess) chk(hipStreamSynchronize(s));
+        float* tmp = out(host, (size_t)B * C * H * W);
+        run([&] { return launch_blocked_to_nchw(s, dtype, dev, tmp, B, C, H, W); });
     }
-    // device T NHWC -> host f32 NCHW
+    // device T NHWC -> host f32 NCHW (likewise)
     void to_host_nchw(int dtype, const void* dev, float* host, int B, int C, int H, int W) {
-        size_t n = (size_t)B * C * H * W;
-        float* tmp = (float*)alloc(n * 4);
-        if (err == hipSuccess) chk(launch_nhwc_to_nchw(s, dtype, dev, tmp, B, C, H, W));
-        if (err == hipSuccess) chk(hipMemcpyAsync(host, tmp, n * 4, hipMemcpyDeviceToHost, s));
-        if (err == hipSuccess) chk(hipStreamSynchronize(s));
+        float* tmp = out(host, (size_t)B * C * H * W);
+        run([&] { return launch_nhwc_to_nchw(s, dtype, dev, tmp, B, C, H, W); });
     }
+    // n host frames -> the staging layout on the device, as cf_op_redact stages them (the row bytes only; pitches rounded up to 4)
+    Staged stage(int format, const void* const* host_planes, int n, int h, int w, int pitch0, int pitch1) {
+        Staged fr;
+        fr.st = redact_stage_layout(format, h, w);
+        fr.format = format; fr.n = n; fr.h = h; fr.w = w; fr.pitch0 = pitch0; fr.pitch1 = pitch1; fr.host = host_planes;
+        fr.base = (uint8_t*)alloc(fr.st.one * n);
+        fr.table = stage_table(fr.st, fr.base, format, n);
+        run([&] { return redact_stage_copy(s, fr.st, format, host_planes, n, h, pitch0, pitch1, fr.base, true); });
+        return fr;
+    }
+    // ... and back into the host frames, behind the launches that changed them
+    void unstage(const Staged& fr) {
+        run([&] { return redact_stage_copy(s, fr.st, fr.format, fr.host, fr.n, fr.h, fr.pitch0, fr.pitch1, fr.base, false); });
+    }
+    // The end of every entry point: the declared outputs come back once the whole sequence ran (nothing is written otherwise), and the list
+    // is cleared (cf_op_decode_threshold_ex comes here twice on one Scope).
     int result(const char* what) {
-        if (err == hipSuccess) err = hipStreamSynchronize(s);
+        run([&] { return hipStreamSynchronize(s); });
+        for (const Back& b : backs) run([&] { return hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, s); });
+        run([&] { return hipStreamSynchronize(s); });
+        backs.clear();
         if (err == hipSuccess) return CF_OK;
         g_op_error = std::string(what) + ": " + hipGetErrorString(err);
         return CF_EHIP;
     }
 };
+
+// Packed rows: image b owns the next counts[b] rows.  count_rows: nullptr with the largest count (at least 1) in *rows (may be null) and
+// the sum in *N, or `refusal` where a count is negative or above `limit`.
+const char* count_rows(const int32_t* counts, int B, int limit, const char* refusal, int* rows, long long* N) {
+    int most = 1;
+    *N = 0;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] < 0 || counts[b] > limit) return refusal;
+        most = std::max(most, (int)counts[b]); *N += counts[b];
+    }
+    if (rows) *rows = most;
+    return nullptr;
+}
+// ... spread to [B][rows][width] (zero where an image has fewer) -- the layout the decode leaves behind, so that the launches address the
+// rows exactly as the engine's do; no rows (src null): an empty vector
+template <typename T> std::vector<T> spread(const T* src, const int32_t* counts, int B, int rows, int width) {
+    std::vector<T> v(src ? (size_t)B * rows * width : 0, T(0));
+    for (long long b = 0, at = 0; src && b < B; at += counts[b], ++b)
+        if (counts[b]) memcpy(&v[(size_t)b * rows * width], src + at * width, (size_t)counts[b] * width * sizeof(T));
+    return v;
+}
 
 bool bad_dtype(int d) { return d != CF_F32 && d != CF_BF16 && d != CF_F32_SPLIT; }
 
@@ -115,6 +194,81 @@ std::vector<float> make_records(const float* hm, const float* wh, const float* r
             if (reg) { r[13] = reg[((size_t)b * 2 + 0) * HW + i]; r[14] = reg[((size_t)b * 2 + 1) * HW + i]; }
         }
     return rec;
+}
+
+// launch_mbconv(p).  An A/B build (-DCF_X5_TIMING, tools/ab_build.sh) launches `reps` times first and times one more launch with events;
+// with `counters` it points the kernel (*slot) at tn zeroed 64-bit counters, where every wave leaves four phase cycle sums, and hands the
+// time, the number of waves that wrote any and the four totals to print(ms, waves, sum), which writes them to stderr.
+template <typename Slot, typename Print>
+void launch_mbconv_timed(Scope& sc, int dtype, MbParams& p, Slot* slot, bool counters, size_t tn, int reps, Print print) {
+    auto launch = [&] { return launch_mbconv(sc.s, dtype, p); };
+#ifdef CF_X5_TIMING
+    unsigned long long* tdev = sc.make<unsigned long long>(tn);
+    if (counters) { (void)hipMemsetAsync(tdev, 0, tn * 8, sc.s); *slot = tdev; }
+    for (int rep = 0; rep < reps; ++rep) sc.run(launch);
+    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, sc.s);
+    sc.run(launch);
+    (void)hipEventRecord(e1, sc.s); (void)hipStreamSynchronize(sc.s);
+    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
+    if (!counters) return;
+    std::vector<unsigned long long> th(tn);
+    (void)hipMemcpy(th.data(), tdev, tn * 8, hipMemcpyDeviceToHost);
+    double sum[4] = {0, 0, 0, 0}; size_t nw = 0;
+    for (size_t i = 0; i + 3 < tn; i += 4) if (th[i] | th[i + 1] | th[i + 2] | th[i + 3]) { for (int k = 0; k < 4; ++k) sum[k] += (double)th[i + k]; ++nw; }
+    print(ms, nw, sum);
+#else
+    sc.run(launch);
+#endif
+}
+
+// Host frames of cf_op_align_frame, cf_op_cut_tiles and cf_op_fit -> their device plane table.  Every plane is copied up whole (rows x pitch
+// bytes), each into its own allocation, so the caller's padding bytes sit beside the pixels on the device and Scope's 0xFF pad follows every plane.
+std::vector<const void*> up_planes(Scope& sc, int format, const void* const* hp, int B, int h, int pitch0, int pitch1) {
+    std::vector<const void*> dev((size_t)3 * B, nullptr);
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < frame_planes(format); ++k) dev[3 * b + k] = sc.up(hp[3 * b + k], k == 0 ? (size_t)h * pitch0 : (size_t)(h / 2) * pitch1);
+    return dev;
+}
+
+// What the two align ops share: the N packed landmark rows and their counts as an align launch reads them, and its outputs, of which the
+// chips and matrices of the rows taken (all of them, or at most max_per_image of an image) come back
+void align_rows(Scope& sc, AlignParams& a, const float* lms, const int32_t* counts, int B, long long N, const cf_align_opts* o, void* chips, double* matrices) {
+    const size_t one = align_chip_bytes(o->size, o->format);
+    a.lms = sc.in(lms, (size_t)N * 10); a.lms_stride = 0; a.rows_cap = INT_MAX;
+    a.counts = sc.in(counts, B);
+    a.chips = sc.alloc(one * N);
+    a.mats = matrices ? sc.make<double>((size_t)N * 6) : nullptr;
+    a.offsets = nullptr; a.cap_faces = (int)N;
+    size_t n = (size_t)N;
+    if (o->max_per_image > 0) { n = 0; for (int b = 0; b < B; ++b) n += std::min(counts[b], o->max_per_image); }
+    sc.back(chips, a.chips, one * n);
+    if (matrices) sc.back(matrices, a.mats, n * 6 * sizeof(double));
+}
+
+// What cf_op_redact and cf_op_blur share, on host frames (in place): the rest of the validation (`why`: what the entry point's own check
+// found), the packed box rows spread on the host, the staging of the frames, and launch(sc, staged geometry, staged planes, faces) between
+// the copy up and the copy down.
+template <typename Launch>
+int op_on_faces(const char* who, const char* why, int device, const FrameGeo& g, const cf_planes_rw* frames, const float* boxes,
+                const int32_t* counts, int H, int W, Launch launch) {
+    static_assert(sizeof(cf_planes_rw) == 3 * sizeof(void*), "cf_planes_rw is a table of three addresses");
+    const void* const* host_planes = reinterpret_cast<const void* const*>(frames);
+    if (!why) why = redact_check_planes(g.format, host_planes, g.B, 0, g.pitch0, g.pitch1);
+    if (!why && (!counts || H < 1 || W < 1)) why = "null counts, or H / W below 1";
+    int rows = 1;
+    long long N = 0;
+    if (!why) why = count_rows(counts, g.B, 1 << 20, "a count is negative or above 2^20", &rows, &N);
+    if (!why && N > 0 && !boxes) why = "null boxes";
+    if (why) return fail(who, why);
+    if (N == 0) return CF_OK;
+    const std::vector<float> sb = spread(boxes, counts, g.B, rows, 4);
+    Scope sc(device);
+    const FaceList f{sc.upv(sb), rows, sc.in(counts, g.B), rows, rows, H, W};
+    const Staged fr = sc.stage(g.format, host_planes, g.B, g.h, g.w, g.pitch0, g.pitch1);
+    launch(sc, fr.geo(g.B), fr.planes(), f);
+    sc.unstage(fr);
+    return sc.result(who);
 }
 
 }  // namespace
@@ -194,12 +348,10 @@ int cf_op_dwconv(int device, int dtype, const float* x, const float* w, const fl
     DwParams p{};
     p.x = sc.to_nhwc(dtype, x, B, C, H, W);
     p.w = sc.upv(wp);
-    p.bias = bias ? (const float*)sc.up(bias, (size_t)C * 4) : nullptr;
-    const size_t ybytes = (size_t)B * Ho * Wo * C * elem_size(dtype);
-    p.y = sc.alloc(ybytes);
-    if (sc.err == hipSuccess) sc.chk(hipMemsetAsync(p.y, 0xFF, ybytes, sc.s));      // an element the kernel skips comes back as NaN
+    p.bias = bias ? sc.in(bias, C) : nullptr;
+    p.y = sc.alloc_nan((size_t)B * Ho * Wo * C * elem_size(dtype));
     p.B = B; p.C = C; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.k = k; p.s = stride; p.pad_lo = pad_lo; p.act = act;
-    if (sc.err == hipSuccess) sc.chk(launch_dw(sc.s, dtype, p));
+    sc.run([&] { return launch_dw(sc.s, dtype, p); });
     sc.to_host_nchw(dtype, p.y, y, B, C, Ho, Wo);
     return sc.result("cf_op_dwconv");
 }
@@ -207,8 +359,8 @@ int cf_op_dwconv(int device, int dtype, const float* x, const float* w, const fl
 int cf_op_pwconv_ex(int device, int dtype, const float* x, const float* w, const float* bias,
                     const float* residual, float* y, int B, int Cin, int Cout, int H, int W, int act, int layout) {
     if (bad_dtype(dtype) || !x || !w || !y || act < 0 || act > 2) return CF_EINVAL;
-    if ((Cin % 8) || (Cout % 8)) { g_op_error = "cf_op_pwconv: Cin and Cout must be multiples of 8"; return CF_EINVAL; }
-    if ((layout & ~7) || ((layout & 4) && !residual)) { g_op_error = "cf_op_pwconv_ex: unknown layout bits, or a pixel-block residual without a residual"; return CF_EINVAL; }
+    if ((Cin % 8) || (Cout % 8)) return fail("cf_op_pwconv", "Cin and Cout must be multiples of 8");
+    if ((layout & ~7) || ((layout & 4) && !residual)) return fail("cf_op_pwconv_ex", "unknown layout bits, or a pixel-block residual without a residual");
     Scope sc(device);
     std::vector<char> packed(pw_packed_bytes(dtype, Cin, Cout));
     pw_pack_weights(dtype, w, Cin, Cout, packed.data());
@@ -216,13 +368,11 @@ int cf_op_pwconv_ex(int device, int dtype, const float* x, const float* w, const
     p.xblock = layout & 1; p.yblock = (layout >> 1) & 1; p.resblock = (layout >> 2) & 1;
     p.x = p.xblock ? sc.to_blocked(dtype, x, B, Cin, H, W) : sc.to_nhwc(dtype, x, B, Cin, H, W);
     p.wp = sc.up(packed.data(), packed.size());
-    p.bias = bias ? (const float*)sc.up(bias, (size_t)Cout * 4) : nullptr;
+    p.bias = bias ? sc.in(bias, Cout) : nullptr;
     p.res = !residual ? nullptr : p.resblock ? sc.to_blocked(dtype, residual, B, Cout, H, W) : sc.to_nhwc(dtype, residual, B, Cout, H, W);
-    const size_t ybytes = p.yblock ? Scope::blocked_bytes(dtype, B, Cout, H, W) : (size_t)B * H * W * Cout * elem_size(dtype);
-    p.y = sc.alloc(ybytes);
-    if (sc.err == hipSuccess) sc.chk(hipMemsetAsync(p.y, 0xFF, ybytes, sc.s));      // an element the kernel skips comes back as NaN
+    p.y = sc.alloc_nan(p.yblock ? Scope::blocked_bytes(dtype, B, Cout, H, W) : (size_t)B * H * W * Cout * elem_size(dtype));
     p.M = (long long)B * H * W; p.K = Cin; p.N = Cout; p.act = act; p.Ho = H; p.Wo = W;      // the map size picks the kernel (cf_pw.hip)
-    if (sc.err == hipSuccess) sc.chk(launch_pw(sc.s, dtype, p));
+    sc.run([&] { return launch_pw(sc.s, dtype, p); });
     if (p.yblock) sc.blocked_to_host_nchw(dtype, p.y, y, B, Cout, H, W);
     else sc.to_host_nchw(dtype, p.y, y, B, Cout, H, W);
     return sc.result("cf_op_pwconv");
@@ -245,32 +395,16 @@ int cf_op_mbconv(int device, int dtype, const float* x, const float* w_exp, cons
     mb_pack_weights(dtype, g, Cin, hid, Cout, k, w_exp, w_dw, w_proj, we.data(), wd.data(), wp.data());
     MbParams p{};
     p.x = sc.to_nhwc(dtype, x, B, Cin, H, W);
-    const size_t ybytes = (size_t)B * Ho * Wo * Cout * elem_size(dtype);
-    p.y = sc.alloc(ybytes);
-    if (sc.err == hipSuccess) sc.chk(hipMemsetAsync(p.y, 0xFF, ybytes, sc.s));      // an element the kernel skips comes back as NaN
+    p.y = sc.alloc_nan((size_t)B * Ho * Wo * Cout * elem_size(dtype));
     p.wexp = sc.up(we.data(), we.size()); p.wdw = sc.upv(wd); p.wproj = sc.up(wp.data(), wp.size());
     p.B = B; p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.Cin = Cin; p.hid = hid; p.Cout = Cout;
     p.k = k; p.s = stride; p.pad_lo = pd / 2; p.residual = (Cin == Cout && stride == 1) ? 1 : 0;
     mb_fill(p, g);
-#ifdef CF_X5_TIMING      // A/B build only: per-wave phase cycle sums of mbconv_f32_kernel (MB_F32 [7]), printed to stderr
-    const size_t tn = (size_t)1 << 22;
-    unsigned long long* tdev = (unsigned long long*)sc.alloc(tn * 8);
-    (void)hipMemsetAsync(tdev, 0, tn * 8, sc.s); p.dbg = tdev;
-    for (int rep = 0; rep < 2 && sc.err == hipSuccess; ++rep) sc.chk(launch_mbconv(sc.s, dtype, p));
-    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, sc.s);
-#endif
-    if (sc.err == hipSuccess) sc.chk(launch_mbconv(sc.s, dtype, p));
-#ifdef CF_X5_TIMING
-    (void)hipEventRecord(e1, sc.s); (void)hipStreamSynchronize(sc.s);
-    { float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-      std::vector<unsigned long long> th(tn);
-      (void)hipMemcpy(th.data(), tdev, tn * 8, hipMemcpyDeviceToHost);
-      double sum[4] = {0, 0, 0, 0}; size_t nw = 0;
-      for (size_t i = 0; i + 3 < tn; i += 4) if (th[i] | th[i + 1] | th[i + 2] | th[i + 3]) { for (int k = 0; k < 4; ++k) sum[k] += (double)th[i + k]; ++nw; }
-      if (nw) fprintf(stderr, "mbconv timing (kind %d): %.1f us; %zu waves, %d chunks each; mean cycles per wave and chunk: wait-top %.0f  expand %.0f  barrier %.0f  dw+project %.0f  (sum %.0f)\n",
-                      g.kind, ms * 1e3, nw, g.nq, sum[0] / nw / g.nq, sum[1] / nw / g.nq, sum[2] / nw / g.nq, sum[3] / nw / g.nq, (sum[0] + sum[1] + sum[2] + sum[3]) / nw / g.nq); }
-#endif
+    // (A/B build: the phase cycle sums of mbconv_f32_kernel, MB_F32 [7])
+    launch_mbconv_timed(sc, dtype, p, &p.dbg, true, (size_t)1 << 22, 2, [&](float ms, size_t nw, const double* sum) {
+        if (nw) fprintf(stderr, "mbconv timing (kind %d): %.1f us; %zu waves, %d chunks each; mean cycles per wave and chunk: wait-top %.0f  expand %.0f  barrier %.0f  dw+project %.0f  (sum %.0f)\n",
+                        g.kind, ms * 1e3, nw, g.nq, sum[0] / nw / g.nq, sum[1] / nw / g.nq, sum[2] / nw / g.nq, sum[3] / nw / g.nq, (sum[0] + sum[1] + sum[2] + sum[3]) / nw / g.nq);
+    });
     sc.to_host_nchw(dtype, p.y, y, B, Cout, Ho, Wo);
     return sc.result("cf_op_mbconv");
 }
@@ -305,35 +439,17 @@ int cf_op_expand_dw(int device, int dtype, const float* x, const float* w_exp, c
     mb_pack_weights(dtype, g, Cin, hid, hid, k, w_exp, w_dw, nullptr, we.data(), wd.data(), nullptr);
     MbParams p{};
     p.x = sc.to_nhwc(dtype, x, B, Cin, H, W);
-    const size_t ybytes = (size_t)B * Ho * Wo * hid * elem_size(dtype);
-    p.y = sc.alloc(ybytes);
-    if (sc.err == hipSuccess) sc.chk(hipMemsetAsync(p.y, 0xFF, ybytes, sc.s));      // an element the kernel skips comes back as NaN
+    p.y = sc.alloc_nan((size_t)B * Ho * Wo * hid * elem_size(dtype));
     p.wexp = sc.up(we.data(), we.size()); p.wdw = sc.upv(wd);
     p.B = B; p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.Cin = Cin; p.hid = hid; p.Cout = hid;
     p.k = k; p.s = stride; p.pad_lo = pd / 2;
     mb_fill(p, g);
-#ifdef CF_X5_TIMING      // A/B build only (tools/ab_build.sh): per-wave phase cycle sums of expdw_f32_kernel, printed to stderr
-    const size_t tn = (size_t)1 << 20;
-    unsigned long long* tdev = (unsigned long long*)sc.alloc(tn * 8);
-    if (g.kind == XD_F32) { (void)hipMemsetAsync(tdev, 0, tn * 8, sc.s); p.wproj = tdev; }
-    for (int rep = 0; rep < 3 && sc.err == hipSuccess; ++rep) sc.chk(launch_mbconv(sc.s, dtype, p));
-    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, sc.s);
-#endif
-    if (sc.err == hipSuccess) sc.chk(launch_mbconv(sc.s, dtype, p));
-#ifdef CF_X5_TIMING
-    (void)hipEventRecord(e1, sc.s); (void)hipStreamSynchronize(sc.s);
-    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-    if (g.kind == XD_F32) {
-        std::vector<unsigned long long> th(tn);
-        (void)hipMemcpy(th.data(), tdev, tn * 8, hipMemcpyDeviceToHost);
-        double sum[4] = {0, 0, 0, 0}; size_t nw = 0;
-        for (size_t i = 0; i + 3 < tn; i += 4) if (th[i] | th[i + 1] | th[i + 2] | th[i + 3]) { for (int k = 0; k < 4; ++k) sum[k] += (double)th[i + k]; ++nw; }
+    // (A/B build: the phase cycle sums of expdw_f32_kernel, which finds its counters where a projection's weights would be)
+    launch_mbconv_timed(sc, dtype, p, &p.wproj, g.kind == XD_F32, (size_t)1 << 20, 3, [&](float ms, size_t nw, const double* sum) {
         const int chunks = g.HALF < g.nq ? g.HALF : g.nq;
         fprintf(stderr, "x5 timing: %.1f us; %zu waves, %d chunks each; mean cycles per wave and chunk: wait-top %.0f  phase1 %.0f  barrier %.0f  phase2 %.0f  (sum %.0f)\n",
                 ms * 1e3, nw, chunks, sum[0] / nw / chunks, sum[1] / nw / chunks, sum[2] / nw / chunks, sum[3] / nw / chunks, (sum[0] + sum[1] + sum[2] + sum[3]) / nw / chunks);
-    }
-#endif
+    });
     sc.to_host_nchw(dtype, p.y, y, B, hid, Ho, Wo);
     return sc.result("cf_op_expand_dw");
 }
@@ -347,20 +463,16 @@ int cf_op_ctdet_loss(int device, const float* hm_raw, const float* wh, const flo
     Scope sc(device);
     const size_t hw = (size_t)h * w, bm = (size_t)B * max_objs;
     LossParams p{};
-    p.hm_raw = (const float*)sc.up(hm_raw, B * hw * 4); p.wh = (const float*)sc.up(wh, B * 2 * hw * 4);
-    p.reg = (const float*)sc.up(reg, B * 2 * hw * 4); p.lm = (const float*)sc.up(lm, B * 10 * hw * 4);
-    p.gt_hm = (const float*)sc.up(gt_hm, B * hw * 4);
-    p.reg_mask = (const unsigned char*)sc.up(reg_mask, bm); p.ind = (const long long*)sc.up(ind, bm * 8);
-    p.wh_t = (const float*)sc.up(wh_t, bm * 8); p.reg_t = (const float*)sc.up(reg_t, bm * 8);
-    p.lm_mask = (const unsigned char*)sc.up(lm_mask, bm); p.lm_ind = (const long long*)sc.up(lm_ind, bm * 8);
-    p.lm_t = (const float*)sc.up(lm_t, bm * 40);
+    p.hm_raw = sc.in(hm_raw, B * hw); p.wh = sc.in(wh, B * 2 * hw); p.reg = sc.in(reg, B * 2 * hw); p.lm = sc.in(lm, B * 10 * hw);
+    p.gt_hm = sc.in(gt_hm, B * hw);
+    p.reg_mask = sc.in(reg_mask, bm); p.ind = (const long long*)sc.in(ind, bm); p.wh_t = sc.in(wh_t, bm * 2); p.reg_t = sc.in(reg_t, bm * 2);
+    p.lm_mask = sc.in(lm_mask, bm); p.lm_ind = (const long long*)sc.in(lm_ind, bm); p.lm_t = sc.in(lm_t, bm * 10);
     p.B = B; p.h = h; p.w = w; p.M = max_objs;
     p.hm_w = weights4[0]; p.wh_w = weights4[1]; p.off_w = weights4[2]; p.lm_w = weights4[3];
     const int nblocks = 256;
-    double* ws = (double*)sc.alloc((3 * nblocks + 6) * sizeof(double));
-    float* out = (float*)sc.alloc(5 * sizeof(float));
-    if (sc.err == hipSuccess) sc.chk(launch_ctdet_loss(sc.s, p, ws, nblocks, out));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out5, out, 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    double* ws = sc.make<double>(3 * nblocks + 6);
+    float* out = sc.out(out5, 5);
+    sc.run([&] { return launch_ctdet_loss(sc.s, p, ws, nblocks, out); });
     return sc.result("cf_op_ctdet_loss");
 }
 
@@ -373,15 +485,12 @@ int cf_op_encode_targets(int device, const float* boxes, const float* lms, const
     Scope sc(device);
     const size_t hw = (size_t)h * w, bm = (size_t)B * max_objs;
     EncodeParams p{};
-    p.boxes = (const float*)sc.up(boxes, bm * 16); p.lms = (const float*)sc.up(lms, bm * 40); p.counts = (const int*)sc.up(counts, (size_t)B * 4);
-    p.hm = (float*)sc.alloc(B * hw * 4); p.wh = (float*)sc.alloc(bm * 8); p.reg = (float*)sc.alloc(bm * 8);
-    p.ind = (long long*)sc.alloc(bm * 8); p.reg_mask = (unsigned char*)sc.alloc(bm);
-    p.landmarks = (float*)sc.alloc(bm * 40); p.lm_ind = (long long*)sc.alloc(bm * 8); p.lm_mask = (unsigned char*)sc.alloc(bm);
+    p.boxes = sc.in(boxes, bm * 4); p.lms = sc.in(lms, bm * 10); p.counts = sc.in(counts, B);
+    p.hm = sc.out(hm, B * hw); p.wh = sc.out(wh, bm * 2); p.reg = sc.out(reg, bm * 2);
+    p.ind = (long long*)sc.out(ind, bm); p.reg_mask = sc.out(reg_mask, bm);
+    p.landmarks = sc.out(landmarks, bm * 10); p.lm_ind = (long long*)sc.out(lm_ind, bm); p.lm_mask = sc.out(lm_mask, bm);
     p.B = B; p.h = h; p.w = w; p.M = max_objs;
-    if (sc.err == hipSuccess) sc.chk(launch_encode_targets(sc.s, p));
-    auto down = [&](void* dst, const void* src, size_t bytes) { if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc.s)); };
-    down(hm, p.hm, B * hw * 4); down(wh, p.wh, bm * 8); down(reg, p.reg, bm * 8); down(ind, p.ind, bm * 8);
-    down(reg_mask, p.reg_mask, bm); down(landmarks, p.landmarks, bm * 40); down(lm_ind, p.lm_ind, bm * 8); down(lm_mask, p.lm_mask, bm);
+    sc.run([&] { return launch_encode_targets(sc.s, p); });
     return sc.result("cf_op_encode_targets");
 }
 
@@ -396,7 +505,7 @@ int cf_op_stem(int device, int dtype, const void* x, int in_format, const float*
     p.in_format = in_format; p.w = sc.up(wp.data(), wp.size());
     p.y = sc.alloc((size_t)B * (H / 2) * (W / 2) * 32 * elem_size(dtype));
     p.B = B; p.H = H; p.W = W;
-    if (sc.err == hipSuccess) sc.chk(launch_stem(sc.s, dtype, p));
+    sc.run([&] { return launch_stem(sc.s, dtype, p); });
     sc.to_host_nchw(dtype, p.y, y, B, 32, H / 2, W / 2);
     return sc.result("cf_op_stem");
 }
@@ -426,7 +535,7 @@ int cf_op_idaup(int device, int dtype, const float* lo, const float* skip, const
     p.bias = sc.upv(bias); p.upw = sc.upv(uw); p.upb = sc.upv(ub);
     p.y = sc.alloc((size_t)B * Ho * Wo * C * elem_size(dtype));
     p.M = (long long)B * Ho * Wo; p.K = Cs; p.N = C; p.act = 2; p.Ho = Ho; p.Wo = Wo;
-    if (sc.err == hipSuccess) sc.chk(launch_pw(sc.s, dtype, p));
+    sc.run([&] { return launch_pw(sc.s, dtype, p); });
     sc.to_host_nchw(dtype, p.y, y, B, C, Ho, Wo);
     return sc.result("cf_op_idaup");
 }
@@ -443,11 +552,10 @@ int cf_op_heads(int device, int dtype, const float* x, const float* w0, const fl
     p.w0p = sc.up(packed.data(), packed.size());
     p.b0 = sc.upv(b0h); p.w1d = sc.upv(w1d); p.b1 = sc.upv(b1h);
     const size_t HW = (size_t)h * w;
-    p.heads = (float*)sc.alloc((size_t)B * HW * 16 * 4);
-    p.B = B; p.h = h; p.w = w; p.collapsed = collapse ? 1 : 0;
-    if (sc.err == hipSuccess) sc.chk(launch_heads(sc.s, dtype, p));
     std::vector<float> rec((size_t)B * HW * 16);
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(rec.data(), p.heads, rec.size() * 4, hipMemcpyDeviceToHost, sc.s));
+    p.heads = sc.out(rec.data(), rec.size());
+    p.B = B; p.h = h; p.w = w; p.collapsed = collapse ? 1 : 0;
+    sc.run([&] { return launch_heads(sc.s, dtype, p); });
     int r = sc.result("cf_op_heads");
     if (r) return r;
     for (int b = 0; b < B; ++b)
@@ -495,7 +603,7 @@ int cf_op_shufflev2(int device, int dtype, const float* x, float* y, int B, int 
         PwParams p{};
         p.x = src; p.wp = sc.up(packed.data(), packed.size()); p.bias = sc.upv(bias); p.y = dst;
         p.M = M; p.K = K; p.N = N; p.act = 2; p.ldy = ldy; p.yoff = yoff;
-        if (sc.err == hipSuccess) sc.chk(launch_pw(sc.s, dtype, p));
+        sc.run([&] { return launch_pw(sc.s, dtype, p); });
     };
     auto dw = [&](const void* src, int C, const float* w /*[C][1][k][k]*/, const float* bn) -> void* {
         std::vector<double> s1, h1;
@@ -510,7 +618,7 @@ int cf_op_shufflev2(int device, int dtype, const float* x, float* y, int B, int 
         p.x = src; p.w = sc.upv(wp); p.bias = sc.upv(bias);
         p.y = sc.alloc((size_t)Mout * C * elem_size(dtype));
         p.B = B; p.C = C; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.k = ksize; p.s = stride; p.pad_lo = pad; p.act = 0;
-        if (sc.err == hipSuccess) sc.chk(launch_dw(sc.s, dtype, p));
+        sc.run([&] { return launch_dw(sc.s, dtype, p); });
         return p.y;
     };
 
@@ -521,7 +629,7 @@ int cf_op_shufflev2(int device, int dtype, const float* x, float* y, int B, int 
     pw(t2, Mout, mid, outputs, m_w5, mid, false, m_bn6, out, oup, inp);
     if (stride == 1) {
         // x_proj = the even channels (:56-62), passed through into channels [0, inp)
-        if (sc.err == hipSuccess) sc.chk(launch_shuffle_copy(sc.s, dtype, xd, out, Min, inp, 0, oup, 0));
+        sc.run([&] { return launch_shuffle_copy(sc.s, dtype, xd, out, Min, inp, 0, oup, 0); });
     } else {
         // branch_proj (:36-45): dw + BN -> pw + BN + ReLU, into channels [0, inp)
         void* p1 = dw(xd, inp, p_wdw, p_bn1);
@@ -538,17 +646,14 @@ int cf_op_ctdet_decode(int device, const float* heat, const float* wh, const flo
     std::vector<float> rec = make_records(heat, wh, reg, lm, B, h, w);
     TopkParams p{};
     p.heads = sc.upv(rec);
-    p.scratch = (unsigned long long*)sc.alloc((size_t)B * h * w * 8);
-    p.count = (int*)sc.alloc((size_t)B * kTopkCountStride * 4);               // zero-initialised by Scope::alloc
-    if (K > 1024) { p.big_stride = topk_big_stride(K); p.big = (unsigned long long*)sc.alloc((size_t)B * p.big_stride * 8); }
+    p.scratch = sc.make<unsigned long long>((size_t)B * h * w);
+    p.count = sc.make<int>((size_t)B * kTopkCountStride);               // zero-initialised by Scope::alloc
+    if (K > 1024) { p.big_stride = topk_big_stride(K); p.big = sc.make<unsigned long long>((size_t)B * p.big_stride); }
     p.B = B; p.h = h; p.w = w; p.K = K; p.use_reg = reg ? 1 : 0;
-    p.dets = (float*)sc.alloc((size_t)B * K * 6 * 4);
-    p.lms = (lms && lm) ? (float*)sc.alloc((size_t)B * K * 10 * 4) : nullptr;
-    p.inds = inds ? (long long*)sc.alloc((size_t)B * K * 8) : nullptr;
-    if (sc.err == hipSuccess) sc.chk(launch_peak_topk(sc.s, p));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, p.dets, (size_t)B * K * 6 * 4, hipMemcpyDeviceToHost, sc.s));
-    if (p.lms && sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, p.lms, (size_t)B * K * 10 * 4, hipMemcpyDeviceToHost, sc.s));
-    if (p.inds && sc.err == hipSuccess) sc.chk(hipMemcpyAsync(inds, p.inds, (size_t)B * K * 8, hipMemcpyDeviceToHost, sc.s));
+    p.dets = sc.out(dets, (size_t)B * K * 6);
+    p.lms = (lms && lm) ? sc.out(lms, (size_t)B * K * 10) : nullptr;
+    p.inds = inds ? (long long*)sc.out(inds, (size_t)B * K) : nullptr;
+    sc.run([&] { return launch_peak_topk(sc.s, p); });
     return sc.result("cf_op_ctdet_decode");
 }
 
@@ -559,20 +664,16 @@ static int run_threshold(Scope& sc, int mode, const float* d_heads, int B, int h
     ThreshParams p{};
     p.heads = d_heads; p.B = B; p.h = h; p.w = w; p.img_h = img_h; p.img_w = img_w;
     p.score_thresh = score_thresh; p.nms_thresh = nms_thresh; p.cap = cap; p.mode = mode;
-    p.cand = (float*)sc.alloc((size_t)B * cap * 16 * 4);
-    p.cand_count = (int*)sc.alloc((size_t)B * 4);
-    p.order = (int*)sc.alloc((size_t)B * cap * 4);
-    p.mask = (unsigned long long*)sc.alloc((size_t)B * cap * words * 8);
+    p.cand = sc.make<float>((size_t)B * cap * 16);
+    p.cand_count = sc.make<int>(B);
+    p.order = sc.make<int>((size_t)B * cap);
+    p.mask = sc.make<unsigned long long>((size_t)B * cap * words);
     p.max_out = max_out;
-    p.dets = (float*)sc.alloc((size_t)B * max_out * 5 * 4);
-    p.lms = lms ? (float*)sc.alloc((size_t)B * max_out * 10 * 4) : nullptr;
-    p.counts = (int*)sc.alloc((size_t)B * 4);
-    p.overflow = (int*)sc.alloc(4);
-    if (sc.err == hipSuccess) sc.chk(launch_decode_threshold(sc.s, p));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, p.dets, (size_t)B * max_out * 5 * 4, hipMemcpyDeviceToHost, sc.s));
-    if (lms && sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, p.lms, (size_t)B * max_out * 10 * 4, hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(counts, p.counts, (size_t)B * 4, hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(overflow_out, p.overflow, 4, hipMemcpyDeviceToHost, sc.s));
+    p.dets = sc.out(dets, (size_t)B * max_out * 5);
+    p.lms = lms ? sc.out(lms, (size_t)B * max_out * 10) : nullptr;
+    p.counts = sc.out(counts, B);
+    p.overflow = sc.out(overflow_out, 1);
+    sc.run([&] { return launch_decode_threshold(sc.s, p); });
     return sc.result("decode_threshold");
 }
 
@@ -609,10 +710,9 @@ int cf_op_ctdet_post_process(int device, float* dets, const float* centers, cons
     Scope sc(device);
     std::vector<double> t((size_t)B * 6);
     for (int b = 0; b < B; ++b) cf_affine_from_center_scale(centers[2 * b], centers[2 * b + 1], scales[2 * b], out_w, out_h, &t[(size_t)b * 6]);
-    float* d = (float*)sc.up(dets, (size_t)B * K * dim * 4);
+    float* d = sc.inout(dets, (size_t)B * K * dim);
     double* dt = sc.upv(t);
-    if (sc.err == hipSuccess) sc.chk(launch_affine_boxes(sc.s, d, dt, B, K, dim));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, d, (size_t)B * K * dim * 4, hipMemcpyDeviceToHost, sc.s));
+    sc.run([&] { return launch_affine_boxes(sc.s, d, dt, B, K, dim); });
     return sc.result("cf_op_ctdet_post_process");
 }
 
@@ -633,19 +733,17 @@ int cf_op_nms(int device, const float* boxes, const float* scores, int n, float 
     ThreshParams p{};
     p.B = 1; p.cap = cap; p.nms_thresh = nms_thresh;
     p.cand = sc.upv(cand);
-    p.cand_count = (int*)sc.up(&n, 4);
-    p.order = (int*)sc.alloc((size_t)cap * 4);
-    p.mask = (unsigned long long*)sc.alloc((size_t)cap * words * 8);
+    p.cand_count = sc.in(&n, 1);
+    p.order = sc.make<int>(cap);
+    p.mask = sc.make<unsigned long long>((size_t)cap * words);
     p.max_out = n;
-    p.dets = (float*)sc.alloc((size_t)n * 5 * 4);
-    p.lms = (float*)sc.alloc((size_t)n * 10 * 4);
-    p.counts = (int*)sc.alloc(4);
-    p.overflow = (int*)sc.alloc(4);
-    if (sc.err == hipSuccess) sc.chk(launch_nms_stages(sc.s, p));
     std::vector<float> l((size_t)n * 10);
     int cnt = 0;
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(l.data(), p.lms, l.size() * 4, hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(&cnt, p.counts, 4, hipMemcpyDeviceToHost, sc.s));
+    p.dets = sc.make<float>((size_t)n * 5);
+    p.lms = sc.out(l.data(), l.size());
+    p.counts = sc.out(&cnt, 1);
+    p.overflow = sc.make<int>(1);
+    sc.run([&] { return launch_nms_stages(sc.s, p); });
     int r = sc.result("cf_op_nms");
     if (r) return r;
     for (int i = 0; i < cnt; ++i) keep[i] = (int32_t)l[(size_t)i * 10];
@@ -672,86 +770,58 @@ int cf_op_box_match(int device, int n_img, const float* boxes, int box_stride, c
     OverlapParams p{};
     p.n_img = n_img; p.box_stride = box_stride; p.query_stride = query_stride; p.thresh = thresh;
     float dummy[4] = {0, 0, 0, 0};
-    p.boxes = (const float*)sc.up(NB ? (const void*)boxes : (const void*)dummy, NB ? (size_t)NB * box_stride * 4 : 16);
-    p.query = (const float*)sc.up(NQ ? (const void*)query : (const void*)dummy, NQ ? (size_t)NQ * query_stride * 4 : 16);
-    p.box_off = (const int*)sc.up(box_off, (size_t)(n_img + 1) * 4);
-    p.query_off = (const int*)sc.up(query_off, (size_t)(n_img + 1) * 4);
+    p.boxes = sc.in(NB ? boxes : dummy, NB ? (size_t)NB * box_stride : 4);
+    p.query = sc.in(NQ ? query : dummy, NQ ? (size_t)NQ * query_stride : 4);
+    p.box_off = sc.in(box_off, (size_t)n_img + 1);
+    p.query_off = sc.in(query_off, (size_t)n_img + 1);
     if (overlaps && ooff[n_img] > 0) {
-        p.overlaps = (double*)sc.alloc((size_t)ooff[n_img] * 8);
-        p.overlaps_off = (const long long*)sc.up(ooff.data(), ooff.size() * 8);
+        p.overlaps = sc.out(overlaps, (size_t)ooff[n_img]);
+        p.overlaps_off = sc.upv(ooff);
     }
-    if (counts) p.counts = (int*)sc.alloc((size_t)n_img * 2 * 4);
-    if (sc.err == hipSuccess) sc.chk(launch_box_match(sc.s, p));
-    if (sc.err == hipSuccess && p.overlaps) sc.chk(hipMemcpyAsync(overlaps, p.overlaps, (size_t)ooff[n_img] * 8, hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess && counts) sc.chk(hipMemcpyAsync(counts, p.counts, (size_t)n_img * 2 * 4, hipMemcpyDeviceToHost, sc.s));
+    if (counts) p.counts = sc.out(counts, (size_t)n_img * 2);
+    sc.run([&] { return launch_box_match(sc.s, p); });
     return sc.result("cf_op_box_match");
 }
 
 // The conversion kernel of cf_forward_yuv on dense host frames [B][h*3/2][w] -> bgr [B][H][W][3] ((H, W) != (h, w): convert + resize).
 int cf_op_yuv_to_bgr(int device, int yuv_format, const uint8_t* frames, uint8_t* bgr, int B, int h, int w, int H, int W) {
     if (!frames || !bgr || B < 1 || yuv_format < CF_YUV_NV12 || yuv_format > CF_YUV_YV12 || h < 2 || w < 2 || (h & 1) || (w & 1) ||
-        H < 1 || W < 2 || (W & 1)) {
-        g_op_error = "cf_op_yuv_to_bgr: null buffer, B < 1, unknown format, or h / w / W not even and at least 2";
-        return CF_EINVAL;
-    }
+        H < 1 || W < 2 || (W & 1))
+        return fail("cf_op_yuv_to_bgr", "null buffer, B < 1, unknown format, or h / w / W not even and at least 2");
     const bool il = yuv_format == CF_YUV_NV12 || yuv_format == CF_YUV_NV21;
     const int cw = il ? w : w / 2;
     const size_t ybytes = (size_t)h * w, cbytes = (size_t)(h / 2) * cw, one = ybytes + (il ? cbytes : 2 * cbytes);
     Scope sc(device);
-    const uint8_t* src = (const uint8_t*)sc.up(frames, one * B);
-    uint8_t* out = (uint8_t*)sc.alloc((size_t)B * H * W * 3);
+    const uint8_t* src = sc.in(frames, one * B);
+    uint8_t* out = sc.out(bgr, (size_t)B * H * W * 3);
     std::vector<const void*> planes((size_t)3 * B);
     for (int b = 0; b < B && src; ++b) {
         const uint8_t* f = src + b * one;
         planes[3 * b] = f; planes[3 * b + 1] = f + ybytes; planes[3 * b + 2] = il ? nullptr : f + ybytes + cbytes;
     }
-    if (sc.err == hipSuccess) sc.chk(launch_yuv_to_bgr(sc.s, yuv_format, planes.data(), B, h, w, w, cw, out, H, W));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(bgr, out, (size_t)B * H * W * 3, hipMemcpyDeviceToHost, sc.s));
+    sc.run([&] { return launch_yuv_to_bgr(sc.s, yuv_format, planes.data(), B, h, w, w, cw, out, H, W); });
     return sc.result("cf_op_yuv_to_bgr");
 }
 
 int cf_op_align_faces(int device, const uint8_t* imgs, int B, int h, int w, const float* lms, const int32_t* counts,
                       const cf_align_opts* o, void* chips, double* matrices) {
-    if (!imgs || !counts || !o || !chips || B < 1 || h < 1 || w < 2) {
-        g_op_error = "cf_op_align_faces: null images, counts, options or chips, B < 1, h < 1 or w < 2";
-        return CF_EINVAL;
-    }
+    if (!imgs || !counts || !o || !chips || B < 1 || h < 1 || w < 2)
+        return fail("cf_op_align_faces", "null images, counts, options or chips, B < 1, h < 1 or w < 2");
     AlignParams p{};
-    if (const char* why = align_params_set(p, o->size, o->format, o->rgb, o->mean, o->scale, o->tmpl, o->max_per_image)) {
-        g_op_error = std::string("cf_op_align_faces: ") + why;
-        return CF_EINVAL;
-    }
+    const char* why = align_params_set(p, o->size, o->format, o->rgb, o->mean, o->scale, o->tmpl, o->max_per_image);
     long long N = 0;
-    for (int b = 0; b < B; ++b) {
-        if (counts[b] < 0) { g_op_error = "cf_op_align_faces: negative count"; return CF_EINVAL; }
-        N += counts[b];
-    }
-    if (N > 0 && !lms) { g_op_error = "cf_op_align_faces: null landmarks"; return CF_EINVAL; }
-    if (N > (1 << 24)) { g_op_error = "cf_op_align_faces: more than 2^24 faces"; return CF_EINVAL; }
+    if (!why) why = count_rows(counts, B, INT_MAX, "negative count", nullptr, &N);
+    if (!why && N > 0 && !lms) why = "null landmarks";
+    if (!why && N > (1 << 24)) why = "more than 2^24 faces";
+    if (why) return fail("cf_op_align_faces", why);
     if (N == 0) return CF_OK;
     Scope sc(device);
-    const size_t img_bytes = (size_t)B * h * w * 3, one = align_chip_bytes(o->size, o->format);
-    p.img = (const uint8_t*)sc.up(imgs, img_bytes); p.img_dwords = (img_bytes + 3) / 4;      // (Scope pads every allocation)
+    const size_t img_bytes = (size_t)B * h * w * 3;
+    p.img = sc.in(imgs, img_bytes); p.img_dwords = (img_bytes + 3) / 4;      // (Scope pads every allocation)
     p.B = B; p.H = h; p.W = w;
-    p.lms = (const float*)sc.up(lms, (size_t)N * 10 * sizeof(float)); p.lms_stride = 0; p.rows_cap = INT_MAX;
-    p.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int));
-    p.chips = sc.alloc(one * N);
-    p.mats = matrices ? (double*)sc.alloc((size_t)N * 6 * sizeof(double)) : nullptr;
-    p.offsets = nullptr; p.cap_faces = (int)N;
-    if (sc.err == hipSuccess) sc.chk(launch_align_faces(sc.s, p));
-    const size_t n = o->max_per_image > 0 ? [&] { size_t t = 0; for (int b = 0; b < B; ++b) t += std::min(counts[b], o->max_per_image); return t; }() : (size_t)N;
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(chips, p.chips, one * n, hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess && matrices) sc.chk(hipMemcpyAsync(matrices, p.mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
+    align_rows(sc, p, lms, counts, B, N, o, chips, matrices);
+    sc.run([&] { return launch_align_faces(sc.s, p); });
     return sc.result("cf_op_align_faces");
-}
-
-// Host frames of cf_op_align_frame and cf_op_cut_tiles -> their device plane table.  Every plane is copied up whole (rows x pitch bytes),
-// each into its own allocation, so the caller's padding bytes sit beside the pixels on the device and Scope's 0xFF pad follows every plane.
-static std::vector<const void*> up_planes(Scope& sc, int format, const void* const* hp, int B, int h, int pitch0, int pitch1) {
-    std::vector<const void*> dev((size_t)3 * B, nullptr);
-    for (int b = 0; b < B; ++b)
-        for (int k = 0; k < frame_planes(format); ++k) dev[3 * b + k] = sc.up(hp[3 * b + k], k == 0 ? (size_t)h * pitch0 : (size_t)(h / 2) * pitch1);
-    return dev;
 }
 
 // The kernel of cf_align_faces_frame on host frames.
@@ -765,98 +835,52 @@ int cf_op_align_frame(int device, int format, const cf_yuv_planes* host_frames, 
     if (!why) why = align_frame_check(p, o->size, o->format, o->rgb, o->mean, o->scale, o->tmpl, o->max_per_image, format, hp, 0, B, h, w, pitch0, pitch1);
     if (!why && ((pitch0 & 3) || (format != CF_FRAME_BGR && (pitch1 & 3)))) why = "pitches must be multiples of 4 (the planes are read on the device as they are)";
     long long N = 0;
-    for (int b = 0; !why && b < B; ++b) {
-        if (counts[b] < 0) why = "negative count";
-        else N += counts[b];
-    }
+    if (!why) why = count_rows(counts, B, INT_MAX, "negative count", nullptr, &N);
     if (!why && N > 0 && !lms) why = "null landmarks";
     if (!why && N > (1 << 24)) why = "more than 2^24 faces";
-    if (why) { g_op_error = std::string("cf_op_align_frame: ") + why; return CF_EINVAL; }
+    if (why) return fail("cf_op_align_frame", why);
     if (N == 0) return CF_OK;
     Scope sc(device);
     const std::vector<const void*> dev = up_planes(sc, format, hp, B, h, pitch0, pitch1);
-    const size_t one = align_chip_bytes(o->size, o->format);
     p.planes = dev.data(); p.sx = 1.0; p.sy = 1.0;
-    p.a.lms = (const float*)sc.up(lms, (size_t)N * 10 * sizeof(float)); p.a.lms_stride = 0; p.a.rows_cap = INT_MAX;
-    p.a.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int));
-    p.a.chips = sc.alloc(one * N);
-    p.a.mats = matrices ? (double*)sc.alloc((size_t)N * 6 * sizeof(double)) : nullptr;
-    p.a.offsets = nullptr; p.a.cap_faces = (int)N;
-    if (sc.err == hipSuccess) sc.chk(launch_align_frame(sc.s, p));
-    size_t n = (size_t)N;
-    if (o->max_per_image > 0) { n = 0; for (int b = 0; b < B; ++b) n += std::min(counts[b], o->max_per_image); }
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(chips, p.a.chips, one * n, hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess && matrices) sc.chk(hipMemcpyAsync(matrices, p.a.mats, n * 6 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
+    align_rows(sc, p.a, lms, counts, B, N, o, chips, matrices);
+    sc.run([&] { return launch_align_frame(sc.s, p); });
     return sc.result("cf_op_align_frame");
-}
-
-// What cf_op_redact and cf_op_blur share, on host frames (in place): the rest of the validation (`why`: what the entry point's own check
-// found), the packed box rows spread to [B][max count][4] on the host -- the layout the decode leaves behind, so that the launches
-// address them exactly as the engine's do --, the staging of the frames, and launch(sc, staged geometry, staged planes, faces) between
-// the copy up and the copy down.
-static int op_on_faces(const char* who, const char* why, int device, const FrameGeo& g, const cf_planes_rw* frames, const float* boxes,
-                       const int32_t* counts, int H, int W,
-                       const std::function<hipError_t(Scope&, const FrameGeo&, const void* const*, const FaceList&)>& launch) {
-    static_assert(sizeof(cf_planes_rw) == 3 * sizeof(void*), "cf_planes_rw is a table of three addresses");
-    const void* const* host_planes = reinterpret_cast<const void* const*>(frames);
-    if (!why) why = redact_check_planes(g.format, host_planes, g.B, 0, g.pitch0, g.pitch1);
-    if (!why && (!counts || H < 1 || W < 1)) why = "null counts, or H / W below 1";
-    int rows = 1;
-    long long N = 0;
-    for (int b = 0; !why && b < g.B; ++b) {
-        if (counts[b] < 0 || counts[b] > (1 << 20)) why = "a count is negative or above 2^20";
-        else { rows = std::max(rows, (int)counts[b]); N += counts[b]; }
-    }
-    if (!why && N > 0 && !boxes) why = "null boxes";
-    if (why) { g_op_error = std::string(who) + ": " + why; return CF_EINVAL; }
-    if (N == 0) return CF_OK;
-    std::vector<float> spread((size_t)g.B * rows * 4, 0.0f);
-    for (long long b = 0, at = 0; b < g.B; at += counts[b], ++b)
-        if (counts[b]) memcpy(&spread[(size_t)b * rows * 4], boxes + at * 4, (size_t)counts[b] * 4 * sizeof(float));
-    Scope sc(device);
-    const FaceList f{sc.upv(spread), rows, (const int*)sc.up(counts, (size_t)g.B * sizeof(int)), rows, rows, H, W};
-    const RedactStage st = redact_stage_layout(g.format, g.h, g.w);
-    uint8_t* stage = (uint8_t*)sc.alloc(st.one * g.B);
-    const std::vector<const void*> dev = stage_table(st, stage, g.format, g.B);
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, g.format, host_planes, g.B, g.h, g.pitch0, g.pitch1, stage, true));
-    if (sc.err == hipSuccess) sc.chk(launch(sc, FrameGeo{g.format, g.B, g.h, g.w, st.pitch0, st.pitch1}, dev.data(), f));
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, g.format, host_planes, g.B, g.h, g.pitch0, g.pitch1, stage, false));
-    return sc.result(who);
 }
 
 // The kernels of cf_redact_faces on host frames (in place).
 int cf_op_redact(int device, const cf_redact_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
                  const float* boxes, const int32_t* counts, int H, int W) {
-    if (!o) { g_op_error = "cf_op_redact: null options"; return CF_EINVAL; }
+    if (!o) return fail("cf_op_redact", "null options");
     const char* why = redact_check(format, o->mode, o->shape, o->cell, o->scale, B, h, w, pitch0, pitch1);
     return op_on_faces("cf_op_redact", why, device, FrameGeo{format, B, h, w, pitch0, pitch1}, frames, boxes, counts, H, W,
                        [&](Scope& sc, const FrameGeo& g, const void* const* planes, const FaceList& f) {
         RedactParams p{};
         p.g = g; p.f = f; p.planes = planes; p.mode = o->mode; p.shape = o->shape; p.cell = o->cell; p.scale = o->scale;
         p.fill[0] = o->fill[0]; p.fill[1] = o->fill[1]; p.fill[2] = o->fill[2];
-        if (o->mode == CF_REDACT_MOSAIC) p.cells = (uint32_t*)sc.alloc(redact_cells(B, h, w, o->cell) * sizeof(uint32_t));
-        return sc.err == hipSuccess ? launch_redact_faces(sc.s, p) : sc.err;
+        if (o->mode == CF_REDACT_MOSAIC) p.cells = sc.make<uint32_t>(redact_cells(B, h, w, o->cell));
+        sc.run([&] { return launch_redact_faces(sc.s, p); });
     });
 }
 
 // The kernels of cf_blur_faces on host frames (in place).
 int cf_op_blur(int device, const cf_blur_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
                const float* boxes, const int32_t* counts, int H, int W) {
-    if (!o) { g_op_error = "cf_op_blur: null options"; return CF_EINVAL; }
+    if (!o) return fail("cf_op_blur", "null options");
     const char* why = blur_check(format, o->shape, o->radius, o->scale, B, h, w, pitch0, pitch1);
     return op_on_faces("cf_op_blur", why, device, FrameGeo{format, B, h, w, pitch0, pitch1}, frames, boxes, counts, H, W,
                        [&](Scope& sc, const FrameGeo& g, const void* const* planes, const FaceList& f) {
         BlurParams p{};
         p.g = g; p.f = f; p.planes = planes; p.shape = o->shape; p.radius = o->radius; p.scale = o->scale;
         p.scratch = (uint8_t*)sc.alloc(blur_scratch_bytes(format, B, h, w));
-        return sc.err == hipSuccess ? launch_blur_faces(sc.s, p) : sc.err;
+        sc.run([&] { return launch_blur_faces(sc.s, p); });
     });
 }
 
 // The kernels of cf_draw_faces on host frames (in place).  The packed rows are spread to [B][max count] like op_on_faces' boxes.
 int cf_op_draw(int device, const cf_draw_opts* o, int format, const cf_planes_rw* frames, int B, int h, int w, int pitch0, int pitch1,
                const float* boxes, const float* scores, const float* lms, const int32_t* info, const int32_t* counts, int H, int W) {
-    if (!o) { g_op_error = "cf_op_draw: null options"; return CF_EINVAL; }
+    if (!o) return fail("cf_op_draw", "null options");
     const void* const* host_planes = reinterpret_cast<const void* const*>(frames);
     const char* why = draw_check(o, format, B, h, w, pitch0, pitch1);
     if (!why) why = redact_check_planes(format, host_planes, B, 0, pitch0, pitch1);
@@ -865,37 +889,21 @@ int cf_op_draw(int device, const cf_draw_opts* o, int format, const cf_planes_rw
     if (!why && o->label == CF_DRAW_LABEL_ID && !info) why = "CF_DRAW_LABEL_ID without info rows";
     int rows = 1;
     long long N = 0;
-    for (int b = 0; !why && b < B; ++b) {
-        if (counts[b] < 0 || counts[b] > (1 << 20)) why = "a count is negative or above 2^20";
-        else { rows = std::max(rows, (int)counts[b]); N += counts[b]; }
-    }
+    if (!why) why = count_rows(counts, B, 1 << 20, "a count is negative or above 2^20", &rows, &N);
     if (!why && N > 0 && (!boxes || !scores)) why = "null boxes or scores";
-    if (why) { g_op_error = std::string("cf_op_draw: ") + why; return CF_EINVAL; }
+    if (why) return fail("cf_op_draw", why);
     if (N == 0) return CF_OK;
-    const size_t cap = (size_t)B * rows;
-    std::vector<float> sb(cap * 4, 0.0f), ss(cap, 0.0f), sl(lms ? cap * 10 : 0, 0.0f);
-    std::vector<int32_t> si(info ? cap * 3 : 0, 0);
-    for (long long b = 0, at = 0; b < B; at += counts[b], ++b) {
-        const size_t n = (size_t)counts[b], to = (size_t)b * rows;
-        if (!n) continue;
-        memcpy(&sb[to * 4], boxes + at * 4, n * 4 * sizeof(float));
-        memcpy(&ss[to], scores + at, n * sizeof(float));
-        if (lms) memcpy(&sl[to * 10], lms + at * 10, n * 10 * sizeof(float));
-        if (info) memcpy(&si[to * 3], info + at * 3, n * 3 * sizeof(int32_t));
-    }
+    const std::vector<float> sb = spread(boxes, counts, B, rows, 4), ss = spread(scores, counts, B, rows, 1), sl = spread(lms, counts, B, rows, 10);
+    const std::vector<int32_t> si = spread(info, counts, B, rows, 3);
     Scope sc(device);
     DrawParams p{};
     p.o = *o;
-    p.r = DrawRows{sc.upv(sb), sc.upv(ss), 1, lms ? sc.upv(sl) : nullptr, info ? (const int32_t*)sc.up(si.data(), si.size() * sizeof(int32_t)) : nullptr,
-                   (const int*)sc.up(counts, (size_t)B * sizeof(int)), rows, rows, H, W};
-    const RedactStage st = redact_stage_layout(format, h, w);
-    uint8_t* stage = (uint8_t*)sc.alloc(st.one * B);
-    const std::vector<const void*> dev = stage_table(st, stage, format, B);
-    p.g = FrameGeo{format, B, h, w, st.pitch0, st.pitch1}; p.planes = dev.data();
+    p.r = DrawRows{sc.upv(sb), sc.upv(ss), 1, lms ? sc.upv(sl) : nullptr, info ? sc.upv(si) : nullptr, sc.in(counts, B), rows, rows, H, W};
+    const Staged fr = sc.stage(format, host_planes, B, h, w, pitch0, pitch1);
+    p.g = fr.geo(B); p.planes = fr.planes();
     p.recs = (DrawRec*)sc.alloc(draw_scratch_bytes(B, rows));
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, true));
-    if (sc.err == hipSuccess) sc.chk(launch_draw_faces(sc.s, p));
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, B, h, pitch0, pitch1, stage, false));
+    sc.run([&] { return launch_draw_faces(sc.s, p); });
+    sc.unstage(fr);
     return sc.result("cf_op_draw");
 }
 
@@ -914,14 +922,12 @@ int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, in
     if (!bad) bad = redact_check_planes(format, reinterpret_cast<const void* const*>(host_frames), Bf, 0, pitch0, pitch1);
     if (!bad && !tiles) bad = "null output";
     if (!bad && (long long)Bf * T * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
-    if (bad) { g_op_error = std::string("cf_op_cut_tiles: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_cut_tiles", bad);
     Scope sc(device);
     const std::vector<const void*> dev = up_planes(sc, format, reinterpret_cast<const void* const*>(host_frames), Bf, h, pitch0, pitch1);
-    const cf_tile_rect* drects = (const cf_tile_rect*)sc.up(rects, (size_t)T * sizeof(cf_tile_rect));
-    const size_t out_bytes = (size_t)Bf * T * H * W * 3;
-    uint8_t* out = (uint8_t*)sc.alloc(out_bytes);
-    if (sc.err == hipSuccess) sc.chk(launch_cut_tiles(sc.s, format, dev.data(), Bf, pitch0, pitch1, drects, T, out, H, W));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(tiles, out, out_bytes, hipMemcpyDeviceToHost, sc.s));
+    const cf_tile_rect* drects = sc.in(rects, T);
+    uint8_t* out = sc.out(tiles, (size_t)Bf * T * H * W * 3);
+    sc.run([&] { return launch_cut_tiles(sc.s, format, dev.data(), Bf, pitch0, pitch1, drects, T, out, H, W); });
     return sc.result("cf_op_cut_tiles");
 }
 
@@ -935,7 +941,7 @@ int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* re
     else if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) bad = "thresh and edge must be finite and not negative";
     else if (rows < 1 || max_out < 1 || H < 1 || W < 1) bad = "rows, max_out, H and W must be at least 1";
     else bad = tiles_check(why, CF_FRAME_BGR, Bf, h, w, 3 * w, 0, rects, T, H, 4);      // the geometry part: frame and rectangles
-    if (bad) { g_op_error = std::string("cf_op_merge_tiles: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_merge_tiles", bad);
     if ((long long)T * rows > (1 << 24) || merge_mask_bytes(Bf, T, rows) > kMergeMaskLimit) {
         g_op_error = "cf_op_merge_tiles: the suppression bits of Bf x (T * rows) candidates exceed 256 MiB";
         return CF_ENOMEM;
@@ -943,24 +949,20 @@ int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* re
     Scope sc(device);
     const size_t n = (size_t)Bf * T * rows, cap = (size_t)T * rows, mo = (size_t)Bf * max_out;
     MergeParams p{};
-    p.rects = (const cf_tile_rect*)sc.up(rects, (size_t)T * sizeof(cf_tile_rect));
+    p.rects = sc.in(rects, T);
     p.T = T; p.Bf = Bf; p.h = h; p.w = w; p.H = H; p.W = W;
-    p.dets_net = (const float*)sc.up(dets_net, n * 4 * sizeof(float));
-    p.scores = (const float*)sc.up(scores, n * sizeof(float)); p.score_stride = 1;
-    p.lms_net = (const float*)sc.up(lms_net, n * 10 * sizeof(float));
-    p.counts = (const int*)sc.up(counts, (size_t)Bf * T * sizeof(int)); p.rows = rows;
+    p.dets_net = sc.in(dets_net, n * 4);
+    p.scores = sc.in(scores, n); p.score_stride = 1;
+    p.lms_net = sc.in(lms_net, n * 10);
+    p.counts = sc.in(counts, (size_t)Bf * T); p.rows = rows;
     p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
-    p.cand = (float*)sc.alloc(Bf * cap * 16 * sizeof(float)); p.cand_count = (int*)sc.alloc(Bf * sizeof(int));
-    p.order = (int*)sc.alloc(Bf * cap * sizeof(int)); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, T, rows));
+    p.cand = sc.make<float>(Bf * cap * 16); p.cand_count = sc.make<int>(Bf);
+    p.order = sc.make<int>(Bf * cap); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, T, rows));
     p.max_out = max_out;
-    p.dets = (float*)sc.up(dets, mo * 5 * sizeof(float)); p.lms = (float*)sc.up(lms, mo * 10 * sizeof(float));
-    p.corners = (float*)sc.alloc(mo * 4 * sizeof(float));
-    p.out_counts = (int*)sc.alloc(Bf * sizeof(int)); p.flags = (int*)sc.alloc(Bf * sizeof(int));
-    if (sc.err == hipSuccess) sc.chk(launch_merge_tiles(sc.s, p));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, p.dets, mo * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, p.lms, mo * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out_counts, p.out_counts, Bf * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(flags, p.flags, Bf * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
+    p.corners = sc.make<float>(mo * 4);
+    p.out_counts = sc.out(out_counts, Bf); p.flags = sc.out(flags, Bf);
+    sc.run([&] { return launch_merge_tiles(sc.s, p); });
     return sc.result("cf_op_merge_tiles");
 }
 
@@ -975,7 +977,7 @@ int cf_fit_geometry(const cf_fit_opts* o, int h, int w, int H, int W, cf_fit_geo
     std::string why;
     const char* bad = fit_geometry_check(why, o, h, w, H, W);
     if (!bad && !g) bad = "null output";
-    if (bad) { g_op_error = std::string("cf_fit_geometry: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_fit_geometry", bad);
     return fit_geometry(o->anchor, o->upscale, h, w, H, W, g);
 }
 
@@ -990,13 +992,11 @@ int cf_op_fit(int device, const cf_fit_opts* o, int format, const cf_yuv_planes*
     if (!bad && (long long)B * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
     cf_fit_geom g{};
     if (!bad && fit_geometry(o->anchor, o->upscale, h, w, H, W, &g)) bad = "no geometry";
-    if (bad) { g_op_error = std::string("cf_op_fit: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_fit", bad);
     Scope sc(device);
     const std::vector<const void*> dev = up_planes(sc, format, hp, B, h, pitch0, pitch1);
-    const size_t out_bytes = (size_t)B * H * W * 3;
-    uint8_t* out = (uint8_t*)sc.alloc(out_bytes);
-    if (sc.err == hipSuccess) sc.chk(launch_fit_frames(sc.s, format, dev.data(), B, h, w, pitch0, pitch1, g, o->fill, out, H, W));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(canvas, out, out_bytes, hipMemcpyDeviceToHost, sc.s));
+    uint8_t* out = sc.out(canvas, (size_t)B * H * W * 3);
+    sc.run([&] { return launch_fit_frames(sc.s, format, dev.data(), B, h, w, pitch0, pitch1, g, o->fill, out, H, W); });
     return sc.result("cf_op_fit");
 }
 
@@ -1009,24 +1009,20 @@ int cf_op_unfit(int device, const cf_fit_opts* o, int B, int h, int w, int H, in
     if (!bad && (long long)B * std::max(rows, max_out) > (1 << 24)) bad = "more than 2^24 rows";
     cf_fit_geom g{};
     if (!bad && fit_geometry(o->anchor, o->upscale, h, w, H, W, &g)) bad = "no geometry";
-    if (bad) { g_op_error = std::string("cf_op_unfit: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_unfit", bad);
     Scope sc(device);
     const size_t n = (size_t)B * rows, mo = (size_t)B * max_out;
     UnfitParams p{};
     p.g = g; p.h = h; p.w = w; p.B = B;
-    p.dets_net = (const float*)sc.up(dets_net, n * 4 * sizeof(float));
-    p.scores = (const float*)sc.up(scores, n * sizeof(float)); p.score_stride = 1;
-    p.lms_net = (const float*)sc.up(lms_net, n * 10 * sizeof(float));
-    p.counts = (const int*)sc.up(counts, (size_t)B * sizeof(int)); p.rows = rows;
+    p.dets_net = sc.in(dets_net, n * 4);
+    p.scores = sc.in(scores, n); p.score_stride = 1;
+    p.lms_net = sc.in(lms_net, n * 10);
+    p.counts = sc.in(counts, B); p.rows = rows;
     p.max_out = max_out;
-    p.dets = (float*)sc.up(dets, mo * 5 * sizeof(float)); p.lms = (float*)sc.up(lms, mo * 10 * sizeof(float));
-    p.corners = (float*)sc.alloc(mo * 4 * sizeof(float));
-    p.out_counts = (int*)sc.alloc(B * sizeof(int)); p.flags = (int*)sc.alloc(B * sizeof(int));
-    if (sc.err == hipSuccess) sc.chk(launch_unfit_rows(sc.s, p));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, p.dets, mo * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, p.lms, mo * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out_counts, p.out_counts, B * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(flags, p.flags, B * sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
+    p.corners = sc.make<float>(mo * 4);
+    p.out_counts = sc.out(out_counts, B); p.flags = sc.out(flags, B);
+    sc.run([&] { return launch_unfit_rows(sc.s, p); });
     return sc.result("cf_op_unfit");
 }
 
@@ -1037,12 +1033,12 @@ int cf_op_mirror(int device, int in_format, const void* x, int B, int H, int W, 
     if (!bad && (!x || !out)) bad = "null argument";
     const long long one = bad ? 0 : (long long)B * 3 * H * W * (in_format == CF_IN_U8_HWC_BGR ? 1 : 4);
     if (!bad && 2 * one > INT_MAX) bad = "2^31 bytes and more in the doubled batch";
-    if (bad) { g_op_error = std::string("cf_op_mirror: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_mirror", bad);
     Scope sc(device);
     const void* src = sc.up(x, (size_t)one);
-    uint8_t* dst = (uint8_t*)sc.alloc(2 * (size_t)one);
-    if (sc.err == hipSuccess) sc.chk(launch_mirror_batch(sc.s, in_format, src, dst, B, H, W));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out, dst + one, (size_t)one, hipMemcpyDeviceToHost, sc.s));
+    uint8_t* dst = sc.make<uint8_t>(2 * (size_t)one);
+    sc.back(out, dst + one, (size_t)one);
+    sc.run([&] { return launch_mirror_batch(sc.s, in_format, src, dst, B, H, W); });
     return sc.result("cf_op_mirror");
 }
 
@@ -1051,14 +1047,13 @@ int cf_op_flip_heads(int device, const float* records_2B, int B, int h, int w, f
     if (!records_2B || !records_out || !hm_plane_out) bad = "null argument";
     else if (B < 1 || h < 1 || w < 1) bad = "B, h and w must be at least 1";
     else if (2LL * B * h * w * 16 * (long long)sizeof(float) > INT_MAX) bad = "2^31 bytes and more of records";
-    if (bad) { g_op_error = std::string("cf_op_flip_heads: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_flip_heads", bad);
     Scope sc(device);
     const size_t cells = (size_t)B * h * w;
-    float* rec = (float*)sc.up(records_2B, 2 * cells * 16 * sizeof(float));
-    float* plane = (float*)sc.alloc(cells * sizeof(float));
-    if (sc.err == hipSuccess) sc.chk(launch_flip_heads(sc.s, rec, plane, B, h, w));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(records_out, rec, cells * 16 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(hm_plane_out, plane, cells * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    float* rec = sc.in(records_2B, 2 * cells * 16);
+    sc.back(records_out, rec, cells * 16 * sizeof(float));      // the merge happens in place, in the first half
+    float* plane = sc.out(hm_plane_out, cells);
+    sc.run([&] { return launch_flip_heads(sc.s, rec, plane, B, h, w); });
     return sc.result("cf_op_flip_heads");
 }
 
@@ -1084,58 +1079,49 @@ int op_track_sequence(const char* who, int device, const cf_track_opts* o, int n
     if (!bad && fw) bad = redact_check_planes(fw->format, fw->host_planes, n_frames * n_streams, 0, fw->pitch0, fw->pitch1);
     if (!bad && fw && (fw->space_h < 1 || fw->space_w < 1 || (fw->tiled != 0 && fw->tiled != 1))) bad = "space_h and space_w must be at least 1, tiled 0 or 1";
     if (!bad && fw && fw->tiled && (fw->space_h != fw->h || fw->space_w != fw->w)) bad = "rows in frame space need space_h x space_w = h x w";
-    if (!bad) for (long long k = 0; k < (long long)n_frames * n_streams; ++k) if (counts_in[k] < 0) { bad = "negative count"; break; }
-    if (bad) { g_op_error = std::string(who) + ": " + bad; return CF_EINVAL; }
+    long long N = 0;
+    if (!bad) bad = count_rows(counts_in, n_frames * n_streams, INT_MAX, "negative count", nullptr, &N);
+    if (bad) return fail(who, bad);
     Scope sc(device);
     const size_t S = n_streams, F = n_frames, M = o->max_tracks, nin = F * S * rows, nout = F * S * M;
     TrackParams p{};
-    p.boxes = (const float*)sc.up(boxes, nin * 4 * sizeof(float));
-    p.scores = (const float*)sc.up(scores, nin * sizeof(float)); p.score_stride = 1;
-    p.lms = (const float*)sc.up(lms_in, nin * 10 * sizeof(float));
-    p.counts = (const int*)sc.up(counts_in, F * S * sizeof(int));
+    p.boxes = sc.in(boxes, nin * 4);
+    p.scores = sc.in(scores, nin); p.score_stride = 1;
+    p.lms = sc.in(lms_in, nin * 10);
+    p.counts = sc.in(counts_in, F * S);
     p.rows = rows; p.B = n_streams; p.stream0 = 0;
     p.iou_thresh = o->iou_thresh; p.max_age = o->max_age; p.min_hits = o->min_hits; p.max_tracks = o->max_tracks; p.hold_grow = o->hold_grow;
-    p.meta = (int*)sc.alloc(S * M * 4 * sizeof(int)); p.rec = (float*)sc.alloc(S * M * 16 * sizeof(float));
+    p.meta = sc.make<int>(S * M * 4); p.rec = sc.make<float>(S * M * 16);
     const std::vector<int> ones(S, 1);
-    p.next_id = (int*)sc.upv(ones);
-    p.dets = (float*)sc.up(dets, nout * 5 * sizeof(float)); p.lms_out = (float*)sc.up(lms, nout * 10 * sizeof(float));
-    p.info = (int*)sc.up(info, nout * 3 * sizeof(int));
-    p.corners = (float*)sc.alloc(S * M * 4 * sizeof(float));
-    p.out_counts = (int*)sc.alloc(F * S * sizeof(int)); p.flags = (int*)sc.alloc(F * S * sizeof(int));
+    p.next_id = sc.upv(ones);
+    p.dets = sc.inout(dets, nout * 5); p.lms_out = sc.inout(lms, nout * 10); p.info = sc.inout(info, nout * 3);
+    p.corners = sc.make<float>(S * M * 4);
+    p.out_counts = sc.out(counts, F * S); p.flags = sc.out(flags, F * S);
     FollowParams q{};
     int* moves_dev = nullptr;
-    std::vector<const void*> dev;
+    Staged fr;
     if (fw) {
         q.search = fw->o->search; q.max_sad = fw->o->max_sad;
         q.fx = fw->tiled ? 1.0 : (double)fw->w / (double)fw->space_w; q.fy = fw->tiled ? 1.0 : (double)fw->h / (double)fw->space_h;
         q.stream0 = 0; q.max_tracks = o->max_tracks; q.hold_grow = o->hold_grow; q.meta = p.meta; q.rec = p.rec; q.corners = p.corners;
         q.tpl = (uint8_t*)sc.alloc(S * M * kFollowSlotBytes); q.tmeta = (int*)(q.tpl + S * M * kFollowSide * kFollowSide);
-        q.slot_moves = (int*)sc.alloc(S * M * 4 * sizeof(int));
-        moves_dev = (int*)sc.up(fw->moves, nout * 4 * sizeof(int));
-        const RedactStage st = redact_stage_layout(fw->format, fw->h, fw->w);
-        uint8_t* stage = (uint8_t*)sc.alloc(st.one * F * S);
-        dev = stage_table(st, stage, fw->format, (int)(F * S));
-        q.g = FrameGeo{fw->format, n_streams, fw->h, fw->w, st.pitch0, st.pitch1};
-        if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, fw->format, fw->host_planes, (int)(F * S), fw->h, fw->pitch0, fw->pitch1, stage, true));
+        q.slot_moves = sc.make<int>(S * M * 4);
+        moves_dev = sc.inout(fw->moves, nout * 4);
+        fr = sc.stage(fw->format, fw->host_planes, (int)(F * S), fw->h, fw->w, fw->pitch0, fw->pitch1);      // read only: nothing to copy back
+        q.g = fr.geo(n_streams);
     }
     const TrackParams first = p;
-    for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
+    for (size_t f = 0; f < F && sc.ok(); ++f) {
         p.boxes = first.boxes + f * S * rows * 4; p.scores = first.scores + f * S * rows; p.lms = first.lms + f * S * rows * 10;
         p.counts = first.counts + f * S;
         p.dets = first.dets + f * S * M * 5; p.lms_out = first.lms_out + f * S * M * 10; p.info = first.info + f * S * M * 3;
         p.out_counts = first.out_counts + f * S; p.flags = first.flags + f * S;
-        if (!fw || fw->detect[f]) sc.chk(launch_track_update(sc.s, p));
+        if (!fw || fw->detect[f]) sc.run([&] { return launch_track_update(sc.s, p); });
         if (!fw) continue;
-        q.planes = dev.data() + 3 * f * S;
+        q.planes = fr.planes(f * S);
         q.dets = p.dets; q.lms_out = p.lms_out; q.info = p.info; q.out_counts = p.out_counts; q.moves = moves_dev + f * S * M * 4;
-        if (sc.err == hipSuccess) sc.chk(launch_track_follow(sc.s, q));
+        sc.run([&] { return launch_track_follow(sc.s, q); });
     }
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, first.dets, nout * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, first.lms_out, nout * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(info, first.info, nout * 3 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(counts, first.out_counts, F * S * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(flags, first.flags, F * S * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess && fw) sc.chk(hipMemcpyAsync(fw->moves, moves_dev, nout * 4 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
     return sc.result(who);
 }
 
@@ -1167,26 +1153,21 @@ int cf_op_scene(int device, const cf_scene_opts* o, int n_streams, int n_frames,
     if (!bad && (long long)n_frames * n_streams > (1 << 24)) bad = "more than 2^24 frames";
     if (!bad) bad = redact_check_planes(format, host_planes, n_frames * n_streams, 0, pitch0, pitch1);
     if (!bad && !out) bad = "null out";
-    if (bad) { g_op_error = std::string("cf_op_scene: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_scene", bad);
     Scope sc(device);
     const size_t S = n_streams, F = n_frames;
     SceneParams p{};
     p.hist_thresh = o->hist_thresh; p.grid_thresh = o->grid_thresh; p.stream0 = 0;
-    p.sig = (int*)sc.alloc(S * kSceneSig * sizeof(int)); p.st = (int*)sc.alloc(S * 4 * sizeof(int));
+    p.sig = sc.make<int>(S * kSceneSig); p.st = sc.make<int>(S * 4);
     p.part = (int*)sc.alloc(scene_part_bytes(n_streams, h));
-    int* out_dev = (int*)sc.alloc(F * S * 4 * sizeof(int));
-    int* sig_dev = sigs ? (int*)sc.alloc(F * S * kSceneSig * sizeof(int)) : nullptr;
-    const RedactStage st = redact_stage_layout(format, h, w);
-    uint8_t* stage = (uint8_t*)sc.alloc(st.one * F * S);
-    const std::vector<const void*> dev = stage_table(st, stage, format, (int)(F * S));
-    p.g = FrameGeo{format, n_streams, h, w, st.pitch0, st.pitch1};
-    if (sc.err == hipSuccess) sc.chk(redact_stage_copy(sc.s, st, format, host_planes, (int)(F * S), h, pitch0, pitch1, stage, true));
-    for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
-        p.planes = dev.data() + 3 * f * S; p.out = out_dev + f * S * 4; p.sig_out = sig_dev ? sig_dev + f * S * kSceneSig : nullptr;
-        sc.chk(launch_scene_check(sc.s, p));
+    int* out_dev = sc.out(out, F * S * 4);
+    int* sig_dev = sigs ? sc.out(sigs, F * S * kSceneSig) : nullptr;
+    const Staged fr = sc.stage(format, host_planes, (int)(F * S), h, w, pitch0, pitch1);      // read only: nothing to copy back
+    p.g = fr.geo(n_streams);
+    for (size_t f = 0; f < F && sc.ok(); ++f) {
+        p.planes = fr.planes(f * S); p.out = out_dev + f * S * 4; p.sig_out = sig_dev ? sig_dev + f * S * kSceneSig : nullptr;
+        sc.run([&] { return launch_scene_check(sc.s, p); });
     }
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(out, out_dev, F * S * 4 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess && sigs) sc.chk(hipMemcpyAsync(sigs, sig_dev, F * S * kSceneSig * sizeof(int), hipMemcpyDeviceToHost, sc.s));
     return sc.result("cf_op_scene");
 }
 
@@ -1199,41 +1180,33 @@ int cf_op_lookback(int device, const cf_lookback_opts* o, int n_streams, int n_s
     if (!bad && n_steps < 1) bad = "n_steps must be at least 1";
     if (!bad && (rows_in < 1 || rows_in > o->rows)) bad = "rows_in must be in 1..rows";
     if (!bad && (long long)n_steps * n_streams * o->rows > (1 << 24)) bad = "more than 2^24 rows";
-    if (bad) { g_op_error = std::string("cf_op_lookback: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_lookback", bad);
     Scope sc(device);
     const size_t S = n_streams, F = n_steps, R = o->rows, cap = (size_t)o->depth + 1, nin = F * S * rows_in, nout = F * S * R;
     std::vector<int32_t> codes(F * S * 4, 0), ones(S, 1);
     for (size_t k = 0; k < F * S; ++k) codes[k * 4] = cuts && (cuts[k] & 1) ? CF_SCENE_CUT : CF_SCENE_SAME;
     LookbackParams p{};
     p.depth = o->depth; p.rows = o->rows; p.confirm = o->confirm; p.grow = o->grow; p.stream0 = 0; p.B = n_streams;
-    const float* din = (const float*)sc.up(dets_in, nin * 5 * sizeof(float));
-    const float* lin = (const float*)sc.up(lms_in, nin * 10 * sizeof(float));
-    const int* iin = (const int*)sc.up(info_in, nin * 3 * sizeof(int));
-    const int* cin = (const int*)sc.up(counts_in, F * S * sizeof(int));
-    const int* scn = (const int*)sc.upv(codes);
-    const int* one = (const int*)sc.upv(ones);
+    p.in_dets = sc.in(dets_in, nin * 5); p.in_lms = sc.in(lms_in, nin * 10); p.in_info = sc.in(info_in, nin * 3); p.in_counts = sc.in(counts_in, F * S);
+    p.scene = sc.upv(codes);
+    const int* one = sc.upv(ones);
     p.in_stride = rows_in;
-    p.qmeta = (int*)sc.alloc(S * 4 * sizeof(int)); p.pend = (int*)sc.alloc(S * sizeof(int)); p.emeta = (int*)sc.alloc(S * cap * 4 * sizeof(int));
-    p.rec = (float*)sc.alloc(S * cap * R * 16 * sizeof(float)); p.info = (int*)sc.alloc(S * cap * R * 4 * sizeof(int));
-    float* d_dev = (float*)sc.up(dets, nout * 5 * sizeof(float));
-    float* l_dev = (float*)sc.up(lms, nout * 10 * sizeof(float));
-    int* i_dev = (int*)sc.up(info, nout * 3 * sizeof(int));
-    int* c_dev = (int*)sc.alloc(F * S * sizeof(int));
-    int* s_dev = (int*)sc.alloc(F * S * 4 * sizeof(int));
-    for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
-        for (size_t s = 0; cuts && s < S && sc.err == hipSuccess; ++s)      // cf_lookback_forget of stream s
-            if (cuts[f * S + s] & 2) sc.chk(hipMemcpyAsync(p.pend + s, one + s, sizeof(int), hipMemcpyDeviceToDevice, sc.s));
+    p.qmeta = sc.make<int>(S * 4); p.pend = sc.make<int>(S); p.emeta = sc.make<int>(S * cap * 4);
+    p.rec = sc.make<float>(S * cap * R * 16); p.info = sc.make<int>(S * cap * R * 4);
+    p.dets = sc.inout(dets, nout * 5); p.lms = sc.inout(lms, nout * 10); p.out_info = sc.inout(info, nout * 3);
+    p.counts = sc.out(counts, F * S); p.state = sc.out(state, F * S * 4);
+    const LookbackParams first = p;
+    for (size_t f = 0; f < F && sc.ok(); ++f) {
+        for (size_t s = 0; cuts && s < S; ++s)      // cf_lookback_forget of stream s
+            if (cuts[f * S + s] & 2) sc.run([&] { return hipMemcpyAsync(p.pend + s, one + s, sizeof(int), hipMemcpyDeviceToDevice, sc.s); });
         p.push = push[f] ? 1 : 0;
-        p.in_dets = din + f * S * rows_in * 5; p.in_lms = lin + f * S * rows_in * 10; p.in_info = iin + f * S * rows_in * 3; p.in_counts = cin + f * S;
-        p.scene = cuts ? scn + f * S * 4 : nullptr;
-        p.dets = d_dev + f * S * R * 5; p.lms = l_dev + f * S * R * 10; p.out_info = i_dev + f * S * R * 3; p.counts = c_dev + f * S; p.state = s_dev + f * S * 4;
-        if (sc.err == hipSuccess) sc.chk(launch_lookback_step(sc.s, p));
+        p.in_dets = first.in_dets + f * S * rows_in * 5; p.in_lms = first.in_lms + f * S * rows_in * 10; p.in_info = first.in_info + f * S * rows_in * 3;
+        p.in_counts = first.in_counts + f * S;
+        p.scene = cuts ? first.scene + f * S * 4 : nullptr;
+        p.dets = first.dets + f * S * R * 5; p.lms = first.lms + f * S * R * 10; p.out_info = first.out_info + f * S * R * 3;
+        p.counts = first.counts + f * S; p.state = first.state + f * S * 4;
+        sc.run([&] { return launch_lookback_step(sc.s, p); });
     }
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dets, d_dev, nout * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(lms, l_dev, nout * 10 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(info, i_dev, nout * 3 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(counts, c_dev, F * S * sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(state, s_dev, F * S * 4 * sizeof(int), hipMemcpyDeviceToHost, sc.s));
     return sc.result("cf_op_lookback");
 }
 
@@ -1244,23 +1217,22 @@ int cf_op_chip_quality(int device, const cf_bestshot_opts* o, const uint8_t* chi
     if (!bad && (!chips || !boxes || !scores || !lms || !quality || !parts)) bad = "null argument";
     if (!bad && (n < 1 || n > 65536)) bad = "n must be in 1..65536";
     if (!bad && (!std::isfinite(fx) || !std::isfinite(fy) || !(fx > 0) || !(fy > 0))) bad = "fx and fy must be finite and greater than 0";
-    if (bad) { g_op_error = std::string("cf_op_chip_quality: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_chip_quality", bad);
     Scope sc(device);
     std::vector<int32_t> info((size_t)n * 3);
     for (int i = 0; i < n; ++i) { info[(size_t)i * 3] = i + 1; info[(size_t)i * 3 + 1] = 1000; info[(size_t)i * 3 + 2] = 0; }
     const int offs[2] = {0, n};
     BestOffer p{};
     p.t.size = o->size; p.t.entries = o->entries; p.t.min_hits = o->min_hits; p.t.terms = o->terms;
-    p.r = BestRows{(const float*)sc.up(boxes, (size_t)n * 4 * sizeof(float)), (const float*)sc.up(scores, (size_t)n * sizeof(float)), 1,
-                   (const float*)sc.up(lms, (size_t)n * 10 * sizeof(float)), (const int32_t*)sc.upv(info), (const int*)sc.up(&offs[1], sizeof(int)), n};
+    p.r = BestRows{sc.in(boxes, (size_t)n * 4), sc.in(scores, n), 1, sc.in(lms, (size_t)n * 10), sc.upv(info), sc.in(&offs[1], 1), n};
     p.B = 1; p.cap_faces = n; p.fx = fx; p.fy = fy;
-    p.chips = (const uint8_t*)sc.up(chips, (size_t)n * best_chip_bytes(o->size));
-    p.offsets = (const int*)sc.up(offs, sizeof(offs));
-    p.q = (long long*)sc.alloc((size_t)n * sizeof(long long)); p.sc = (int32_t*)sc.alloc((size_t)n * kBestScratchInts * sizeof(int32_t));
-    if (sc.err == hipSuccess) sc.chk(hipStreamSynchronize(sc.s));       // (offs and info are on this stack frame)
-    if (sc.err == hipSuccess) sc.chk(launch_best_score(sc.s, p));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpyAsync(quality, p.q, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, sc.s));
-    if (sc.err == hipSuccess) sc.chk(hipMemcpy2DAsync(parts, 4 * sizeof(int32_t), p.sc, kBestScratchInts * sizeof(int32_t), 4 * sizeof(int32_t), n, hipMemcpyDeviceToHost, sc.s));
+    p.chips = sc.in(chips, (size_t)n * best_chip_bytes(o->size));
+    p.offsets = sc.in(offs, 2);
+    p.q = (long long*)sc.out(quality, n); p.sc = sc.make<int32_t>((size_t)n * kBestScratchInts);
+    sc.run([&] { return hipStreamSynchronize(sc.s); });       // (offs and info are on this stack frame)
+    sc.run([&] { return launch_best_score(sc.s, p); });
+    // the first four of a row's scratch ints (a strided read, not a declared output)
+    sc.run([&] { return hipMemcpy2DAsync(parts, 4 * sizeof(int32_t), p.sc, kBestScratchInts * sizeof(int32_t), 4 * sizeof(int32_t), n, hipMemcpyDeviceToHost, sc.s); });
     return sc.result("cf_op_chip_quality");
 }
 
@@ -1292,7 +1264,7 @@ int cf_op_bestshot(int device, const cf_bestshot_opts* o, int n_streams, int n_f
         if ((double)base[F] * (double)one > 1073741824.0 || (double)S * E * (double)one > 1073741824.0 || (double)F * S * std::max(cap, 1) * (double)one > 1073741824.0)
             bad = "more than 1 GiB of chips";
     }
-    if (bad) { g_op_error = std::string("cf_op_bestshot: ") + bad; return CF_EINVAL; }
+    if (bad) return fail("cf_op_bestshot", bad);
     Scope sc(device);
     std::vector<uint8_t> packed(std::max<size_t>((size_t)base[F] * one, 16));
     for (size_t f = 0; f < F; ++f)
@@ -1301,44 +1273,37 @@ int cf_op_bestshot(int device, const cf_bestshot_opts* o, int n_streams, int n_f
             if (m) memcpy(packed.data() + ((size_t)base[f] + offs[f * (S + 1) + s]) * one, chips + (f * S + s) * rows * one, m * one);
         }
     const size_t nin = F * S * rows, nout = F * S * cap, nq = std::max<size_t>(base[F], 1);
+    std::vector<long long> q(nq);
     BestOffer p{};
-    p.t = BestTable{o->size, o->entries, o->min_hits, o->terms, (int32_t*)sc.alloc(S * E * kBestRecInts * sizeof(int32_t)),
-                    (float*)sc.alloc(S * E * kBestRowFloats * sizeof(float)), (uint8_t*)sc.alloc(S * E * one), (int32_t*)sc.alloc(S * kBestStreamInts * sizeof(int32_t))};
-    p.r = BestRows{(const float*)sc.up(boxes, nin * 4 * sizeof(float)), (const float*)sc.up(scores, nin * sizeof(float)), 1, (const float*)sc.up(lms, nin * 10 * sizeof(float)),
-                   (const int32_t*)sc.up(info, nin * 3 * sizeof(int32_t)), (const int*)sc.up(counts, F * S * sizeof(int)), rows};
+    p.t = BestTable{o->size, o->entries, o->min_hits, o->terms, sc.make<int32_t>(S * E * kBestRecInts), sc.make<float>(S * E * kBestRowFloats),
+                    sc.make<uint8_t>(S * E * one), sc.make<int32_t>(S * kBestStreamInts)};
+    p.r = BestRows{sc.in(boxes, nin * 4), sc.in(scores, nin), 1, sc.in(lms, nin * 10), sc.in(info, nin * 3), sc.in(counts, F * S), rows};
     p.stream0 = 0; p.B = n_streams; p.fx = fx; p.fy = fy;
-    p.chips = (const uint8_t*)sc.upv(packed); p.offsets = (const int*)sc.upv(offs);
-    p.q = (long long*)sc.alloc(nq * sizeof(long long)); p.sc = (int32_t*)sc.alloc(nq * kBestScratchInts * sizeof(int32_t));
-    p.jobs = (int32_t*)sc.alloc(S * rows * 2 * sizeof(int32_t)); p.flags = (int32_t*)sc.alloc(F * S * sizeof(int32_t));
+    p.chips = sc.upv(packed); p.offsets = sc.upv(offs);
+    p.q = sc.make<long long>(nq); p.sc = sc.make<int32_t>(nq * kBestScratchInts);
+    sc.back(q.data(), p.q, (size_t)base[F] * sizeof(long long));      // the chips' qualities: scattered to offer_quality's rows below
+    p.jobs = sc.make<int32_t>(S * rows * 2); p.flags = sc.out(offer_flags, F * S);
     BestCollect c{};
     c.t = p.t; c.stream0 = 0; c.B = n_streams; c.cap = cap;
-    c.chips = sc.up(out_chips, nout * one); c.quality = (long long*)sc.up(out_quality, nout * sizeof(long long));
-    c.records = (int32_t*)sc.up(out_records, nout * 8 * sizeof(int32_t)); c.dets = (float*)sc.up(out_dets, nout * 5 * sizeof(float));
-    c.lms = (float*)sc.up(out_lms, nout * 10 * sizeof(float));
-    c.counts = (int32_t*)sc.alloc(F * S * sizeof(int32_t)); c.pending = (int32_t*)sc.alloc(F * S * sizeof(int32_t)); c.flags = (int32_t*)sc.alloc(F * S * sizeof(int32_t));
-    c.jobs = (int32_t*)sc.alloc(S * std::max(cap, 1) * 2 * sizeof(int32_t));
+    c.chips = sc.inout(out_chips, nout * one); c.quality = (long long*)sc.inout(out_quality, nout);
+    c.records = sc.inout(out_records, nout * 8); c.dets = sc.inout(out_dets, nout * 5); c.lms = sc.inout(out_lms, nout * 10);
+    c.counts = sc.out(out_counts, F * S); c.pending = sc.out(out_pending, F * S); c.flags = sc.out(out_flags, F * S);
+    c.jobs = sc.make<int32_t>(S * std::max(cap, 1) * 2);
     const BestOffer p0 = p;
     const BestCollect c0 = c;
-    for (size_t f = 0; f < F && sc.err == hipSuccess; ++f) {
+    for (size_t f = 0; f < F && sc.ok(); ++f) {
         p.r.boxes = p0.r.boxes + f * S * rows * 4; p.r.scores = p0.r.scores + f * S * rows; p.r.lms = p0.r.lms + f * S * rows * 10;
         p.r.info = p0.r.info + f * S * rows * 3; p.r.counts = p0.r.counts + f * S;
         p.chips = p0.chips + (size_t)base[f] * one; p.offsets = p0.offsets + f * (S + 1); p.cap_faces = base[f + 1] - base[f];
         p.q = p0.q + base[f]; p.sc = p0.sc + (size_t)base[f] * kBestScratchInts; p.flags = p0.flags + f * S;
-        sc.chk(launch_best_offer(sc.s, p));
+        sc.run([&] { return launch_best_offer(sc.s, p); });
         if (!collect[f]) continue;
         c.flush = collect[f] == 2;
         c.chips = (uint8_t*)c0.chips + f * S * cap * one; c.quality = c0.quality + f * S * cap; c.records = c0.records + f * S * cap * 8;
         c.dets = c0.dets + f * S * cap * 5; c.lms = c0.lms + f * S * cap * 10;
         c.counts = c0.counts + f * S; c.pending = c0.pending + f * S; c.flags = c0.flags + f * S;
-        if (sc.err == hipSuccess) sc.chk(launch_best_collect(sc.s, c));
+        sc.run([&] { return launch_best_collect(sc.s, c); });
     }
-    std::vector<long long> q(nq);
-    auto down = [&](void* dst, const void* src, size_t bytes) { if (bytes && sc.err == hipSuccess) sc.chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc.s)); };
-    if (sc.err == hipSuccess) sc.chk(hipStreamSynchronize(sc.s));         // nothing is written unless the whole sequence ran
-    down(out_chips, c0.chips, nout * one); down(out_quality, c0.quality, nout * sizeof(long long)); down(out_records, c0.records, nout * 8 * sizeof(int32_t));
-    down(out_dets, c0.dets, nout * 5 * sizeof(float)); down(out_lms, c0.lms, nout * 10 * sizeof(float));
-    down(out_counts, c0.counts, F * S * sizeof(int32_t)); down(out_pending, c0.pending, F * S * sizeof(int32_t)); down(out_flags, c0.flags, F * S * sizeof(int32_t));
-    down(offer_flags, p0.flags, F * S * sizeof(int32_t)); down(q.data(), p0.q, (size_t)base[F] * sizeof(long long));
     const int r = sc.result("cf_op_bestshot");
     if (r != CF_OK) return r;
     for (size_t k = 0; k < nin; ++k) offer_quality[k] = -1;

@@ -442,6 +442,16 @@ def device_planes(plane_ptrs):
     return tab
 
 
+def device_input_planes(who, plane_ptrs, f, h, w, pitch0=None, pitch1=None):
+    """The ``on_device=True`` form of the forwards that read frames of format code ``f`` in place: (table, B, h, w, pitch0, pitch1) of B
+    tuples of device addresses, the pitches dense rows by default; ``who`` names the caller in the refusal."""
+    if h is None or w is None:
+        raise ValueError("%s(on_device=True) needs h and w" % who)
+    h, w, bgr = int(h), int(w), f == CF_FRAME_BGR
+    return (device_planes(plane_ptrs), len(plane_ptrs), h, w, (3 * w if bgr else w) if pitch0 is None else int(pitch0),
+            (0 if bgr else yuv_dense_geometry(f, h, w)[1]) if pitch1 is None else int(pitch1))
+
+
 def box_rows(boxes, counts, B):
     """(boxes float32 [N,4], counts int32 [B]) of the packed box rows of B images, N = the sum of the counts."""
     counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
@@ -666,6 +676,11 @@ def ptr(a):
         return None
     assert a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(C.c_void_p)
+
+
+def vp(a):
+    """An optional device address as the ABI takes it: c_void_p, or None for 0 / None."""
+    return C.c_void_p(int(a)) if a else None
 
 
 def f32(a):

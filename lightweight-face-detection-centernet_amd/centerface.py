@@ -13,6 +13,8 @@ reference's ``weight/model_epoch_100.pt`` is not distributed), ``dtype=`` ('fp32
 ``detect_batch``, ``decode_topk`` (the ``ctdet_decode`` path of centerface_ext.py:52-82).
 """
 import bisect
+import collections
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -187,10 +189,7 @@ class Engine(object):
         the row pitches in bytes (default: dense rows; addresses and pitches multiples of 4)."""
         f = _lib.yuv_format(fmt)
         if on_device:
-            if h is None or w is None:
-                raise ValueError("forward_yuv_enqueue(on_device=True) needs h and w")
-            h, w = int(h), int(w)
-            tab, B, cp = _lib.device_planes(frames), len(frames), _lib.yuv_dense_geometry(f, h, w)[1]
+            tab, B, h, w, y_pitch, cp = _lib.device_input_planes("forward_yuv_enqueue", frames, f, h, w, y_pitch, c_pitch)
         else:
             if isinstance(frames, np.ndarray):
                 arrs = np.ascontiguousarray(frames)
@@ -475,12 +474,7 @@ class Engine(object):
         f = _lib.frame_format(fmt)
         rt, T = _lib.tile_rects(rects)
         if on_device:
-            if h is None or w is None:
-                raise ValueError("forward_tiles_enqueue(on_device=True) needs h and w")
-            h, w = int(h), int(w)
-            tab, B = _lib.device_planes(frames), len(frames)
-            pitch0 = (3 * w if f == _lib.CF_FRAME_BGR else w) if pitch0 is None else int(pitch0)
-            pitch1 = (0 if f == _lib.CF_FRAME_BGR else _lib.yuv_dense_geometry(f, h, w)[1]) if pitch1 is None else int(pitch1)
+            tab, B, h, w, pitch0, pitch1 = _lib.device_input_planes("forward_tiles_enqueue", frames, f, h, w, pitch0, pitch1)
         else:
             tab, B, h, w, pitch0, pitch1, self._last.keep = _lib.frame_planes(frames, fmt, writable=False)
         self._chk(self._L.cf_forward_tiles(self._h, f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, rt, T))
@@ -506,8 +500,7 @@ class Engine(object):
         any may be None): asynchronous on the engine's main stream behind the decode, no count is read on the host.  The context keeps
         the merged rows either way: a following ``redact_faces`` / ``redact_faces_device`` on the full frames uses them."""
         o = _lib.merge_opts(metric, thresh, edge)
-        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
-        self._chk(self._L.cf_merge_tiles(self._h, C.byref(o), int(max_out), vp(dets_ptr), vp(lms_ptr), vp(counts_ptr), vp(flags_ptr), 1))
+        self._chk(self._L.cf_merge_tiles(self._h, C.byref(o), int(max_out), _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(counts_ptr), _lib.vp(flags_ptr), 1))
 
     # -- aspect-preserving (letterbox) input -------------------------------------------------------
     def forward_fit_enqueue(self, frames, fmt="bgr", *, anchor="center", upscale=True, fill=(0, 0, 0), on_device=False, h=None, w=None,
@@ -521,12 +514,7 @@ class Engine(object):
         f = _lib.frame_format(fmt)
         o = _lib.fit_opts(anchor, upscale, fill)
         if on_device:
-            if h is None or w is None:
-                raise ValueError("forward_fit_enqueue(on_device=True) needs h and w")
-            h, w = int(h), int(w)
-            tab, B = _lib.device_planes(frames), len(frames)
-            pitch0 = (3 * w if f == _lib.CF_FRAME_BGR else w) if pitch0 is None else int(pitch0)
-            pitch1 = (0 if f == _lib.CF_FRAME_BGR else _lib.yuv_dense_geometry(f, h, w)[1]) if pitch1 is None else int(pitch1)
+            tab, B, h, w, pitch0, pitch1 = _lib.device_input_planes("forward_fit_enqueue", frames, f, h, w, pitch0, pitch1)
         else:
             tab, B, h, w, pitch0, pitch1, self._last.keep = _lib.frame_planes(frames, fmt, writable=False)
         self._chk(self._L.cf_forward_fit(self._h, C.byref(o), f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1))
@@ -547,8 +535,7 @@ class Engine(object):
         """Same, writing into caller-owned DEVICE buffers (dets [B,max_out,5], lms [B,max_out,10] float32, counts / flags [B] int32; any
         may be None): asynchronous on the engine's main stream behind the decode, no count is read on the host.  The context keeps the
         mapped rows either way."""
-        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
-        self._chk(self._L.cf_unfit_rows(self._h, int(max_out), vp(dets_ptr), vp(lms_ptr), vp(counts_ptr), vp(flags_ptr), 1))
+        self._chk(self._L.cf_unfit_rows(self._h, int(max_out), _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(counts_ptr), _lib.vp(flags_ptr), 1))
 
     # -- face tracks across video frames -----------------------------------------------------------
     def track_update(self, tracker, stream0=0):
@@ -574,9 +561,8 @@ class Engine(object):
         """Same, writing into caller-owned DEVICE buffers (dets [B,max_tracks,5], lms [B,max_tracks,10] float32, info [B,max_tracks,3],
         counts / flags [B] int32; any may be None): asynchronous on the engine's main stream behind the decode or the merge, nothing is
         read on the host.  The context keeps the tracked rows either way."""
-        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
-        self._chk(self._L.cf_track_update(self._h, tracker._handle(self), int(stream0), vp(dets_ptr), vp(lms_ptr), vp(info_ptr), vp(counts_ptr),
-                                          vp(flags_ptr), 1))
+        self._chk(self._L.cf_track_update(self._h, tracker._handle(self), int(stream0), _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(info_ptr), _lib.vp(counts_ptr),
+                                          _lib.vp(flags_ptr), 1))
 
     def track_follow(self, frames, fmt, tracker, stream0=0, *, search=4, max_sad=4096):
         """Follow the faces ``tracker`` holds into ``frames`` by block matching, WITHOUT a forward (``cf_track_follow``, host form): frame b
@@ -606,9 +592,8 @@ class Engine(object):
         The context keeps the followed rows either way."""
         f, tab, dev, B, h, w, pitch0, pitch1 = _lib.device_frame_args("track_follow_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1)
         o = _lib.follow_opts(search, max_sad)
-        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
         self._chk(self._L.cf_track_follow(self._h, tracker._handle(self), int(stream0), B, C.byref(o), f, tab, dev, h, w, pitch0, pitch1,
-                                          vp(dets_ptr), vp(lms_ptr), vp(info_ptr), vp(counts_ptr), vp(moves_ptr), 1))
+                                          _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(info_ptr), _lib.vp(counts_ptr), _lib.vp(moves_ptr), 1))
 
     # -- scene cuts --------------------------------------------------------------------------------
     def scene_check(self, frames, fmt, scenes, tracker=None, stream0=0, *, codes=True, out_ptr=None):
@@ -664,9 +649,8 @@ class Engine(object):
         buffers (dets [B,R,5], lms [B,R,10] float32, info [B,R,3], counts [B], state [B,4] int32; any may be None): asynchronous on the
         engine's main stream behind the last step of ``lb``; no row, count or code is read on the host.  The context keeps the lookback
         rows either way."""
-        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
-        self._chk(self._L.cf_lookback_step(self._h, lb._handle(self), int(stream0), int(B), 1 if push else 0, vp(scene_ptr), 1, vp(dets_ptr), vp(lms_ptr),
-                                           vp(info_ptr), vp(counts_ptr), vp(state_ptr), 1))
+        self._chk(self._L.cf_lookback_step(self._h, lb._handle(self), int(stream0), int(B), 1 if push else 0, _lib.vp(scene_ptr), 1, _lib.vp(dets_ptr), _lib.vp(lms_ptr),
+                                           _lib.vp(info_ptr), _lib.vp(counts_ptr), _lib.vp(state_ptr), 1))
 
     # -- best-shot selection: each track's sharpest chip ---------------------------------------------
     def bestshot_offer(self, shots, chips, offsets, hw, stream0=0):
@@ -693,9 +677,8 @@ class Engine(object):
         """Same, reading the DEVICE chips and offsets an ``align_faces_frame_device`` wrote (chips for ``cap_faces`` faces, 16-byte
         aligned) and writing caller-owned DEVICE outputs (quality [cap_faces] int64, flags [B] int32; either may be None): asynchronous
         on the engine's main stream behind the align; nothing is read on the host."""
-        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
-        self._chk(self._L.cf_bestshot_offer(self._h, shots._handle(self), int(stream0), int(B), vp(chips_ptr), vp(offsets_ptr), int(cap_faces), 1,
-                                            int(hw[0]), int(hw[1]), vp(quality_ptr), vp(flags_ptr), 1))
+        self._chk(self._L.cf_bestshot_offer(self._h, shots._handle(self), int(stream0), int(B), _lib.vp(chips_ptr), _lib.vp(offsets_ptr), int(cap_faces), 1,
+                                            int(hw[0]), int(hw[1]), _lib.vp(quality_ptr), _lib.vp(flags_ptr), 1))
 
     def bestshot_collect(self, shots, stream0=0, B=None, cap=None, flush=False):
         """The finished entries of the streams ``stream0 .. stream0 + B - 1`` of ``shots`` (default: all from ``stream0`` on), at most
@@ -718,9 +701,8 @@ class Engine(object):
                                 lms_ptr=None, counts_ptr=None, pending_ptr=None, flags_ptr=None):
         """Same, writing caller-owned DEVICE buffers ([B, cap, ...] as above, chips 16-byte aligned; any may be None -- the entries are
         freed all the same): asynchronous on the engine's main stream behind the table's last call."""
-        vp = lambda a: C.c_void_p(int(a)) if a else None                     # noqa: E731
-        self._chk(self._L.cf_bestshot_collect(self._h, shots._handle(self), int(stream0), int(B), int(cap), 1 if flush else 0, vp(chips_ptr), vp(quality_ptr),
-                                              vp(records_ptr), vp(dets_ptr), vp(lms_ptr), vp(counts_ptr), vp(pending_ptr), vp(flags_ptr), 1))
+        self._chk(self._L.cf_bestshot_collect(self._h, shots._handle(self), int(stream0), int(B), int(cap), 1 if flush else 0, _lib.vp(chips_ptr), _lib.vp(quality_ptr),
+                                              _lib.vp(records_ptr), _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(counts_ptr), _lib.vp(pending_ptr), _lib.vp(flags_ptr), 1))
 
     # -- launch plan / layer trace (parity tests) ---------------------------------------------
     def plan(self):
@@ -960,6 +942,15 @@ class Lookback(_StreamState):
         """The number of source frames of ``stream`` the product paths still hold (0 .. depth)."""
         return len(self._frames[stream])
 
+    def _retain(self, stream0, frames):
+        """The product paths': frame b of ``frames`` is the newest source frame of stream ``stream0 + b`` (kept as it is, not copied)."""
+        for b, frame in enumerate(frames):
+            self._frames[stream0 + b].append(frame)
+
+    def _due(self, stream0, B):
+        """The oldest retained frame of each of the streams ``stream0 .. stream0 + B - 1`` as one new array [B, ...]; they are let go."""
+        return np.stack([self._frames[stream0 + b].pop(0) for b in range(B)])
+
     def _scene_codes(self, engine):
         """A device buffer of this object for the scene codes of one chunk of ``engine`` (int32 [max_batch, 4])."""
         if self._codes is None or self._codes[0] is not engine:
@@ -1124,6 +1115,31 @@ class EngineRing(object):
             pass
 
 
+_RESCALE, _UNFIT, _MERGE = "rescale", "unfit", "merge"                 # how a plan's rows reach frame space: the three cases of ``_Plan.rows``
+_Frames = collections.namedtuple("_Frames", "array fmt options")        # the cover, draw and follow steps: the array a chunk's slice of which they work on
+_Scene = collections.namedtuple("_Scene", "scenes array fmt")           # the scene check: the ``SceneCuts`` and the array it looks at
+_Best = collections.namedtuple("_Best", "shots array fmt template flush sink")      # the best shots: where the chips are cut, where the collect goes
+_Late = collections.namedtuple("_Late", "lookback flush ready")         # the lookback: the ``Lookback``, drain at the end, the lists the call returns
+_Plan = collections.namedtuple("_Plan", (
+    "frames",        # the source the forward reads, sliced per chunk: an array or a list of frames
+    "forward",       # the enqueue that takes any slice of ``frames``
+    "per",           # frames per chunk
+    "rows",          # how the rows reach frame space: _RESCALE (the decode rescales), _UNFIT (``Engine.unfit_rows``) or _MERGE
+    "merge",         # (metric, thresh, edge) of ``Engine.merge_tiles`` for _MERGE
+    "out",           # the output copy that is returned with the results, or None
+    "tracker",       # the ``Tracker`` that every detected chunk advances, or None
+    "scene",         # _Scene: every chunk is first checked for scene cuts, which frees the tracks of a cut stream
+    "follow",        # _Frames: the tracker's faces are followed in the chunk right behind the update
+    "detect",        # False: no forward, decode or update except in a key chunk; the results are the followed rows
+    "cover",         # _Frames: the chunk's slice of the array is covered (``Engine.cover_faces``)
+    "draw",          # _Frames: the chunk's slice of the array is annotated (``Engine.draw_faces``)
+    "chips",         # chips(i, j) cuts the chips of frames i:j, which join the results
+    "best",          # _Best: the chips of the tracked rows are offered per chunk, ONE collect follows the last
+    "lookback",      # _Late: the chunk's frames are retained and its rows pushed; the frames that become due are covered or drawn instead
+), defaults=(_RESCALE, None, None, None, None, None, True, None, None, None, None, None))
+"""What one call asks of the chunk loop (``CenterFace._run``)."""
+
+
 class CenterFace(object):
     """Same construction and call surface as the reference class (centerface.py:11-66)."""
     mean = np.array([0.408, 0.447, 0.470], dtype=np.float32).reshape(1, 1, 3)   # centerface.py:12-13
@@ -1211,7 +1227,7 @@ class CenterFace(object):
         """Batched ``__call__`` (the shape of eval_widerface.get_detections, :76-90).  The reference's
         decode ignores ``threshold`` and uses 0.3 (centerface.py:77); so does this."""
         del threshold
-        return self._drive(*self._input_form(self.engine, imgs))
+        return self._run(self._plain(imgs))
 
     def _input_form(self, eng, imgs, fmt=None):
         """(frames, forward): the form in which ``eng`` takes ``imgs`` and the enqueue that takes any slice of them -- 4:2:0 frames
@@ -1230,8 +1246,8 @@ class CenterFace(object):
         return self._postprocess_many(eng.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)
 
     def _follow(self, follow, detect, tracker, frames, fmt):
-        """The ``follow`` / ``detect`` arguments of the product paths -> the ``follow`` of ``_drive``: None, or (frames, fmt, options
-        of ``Engine.track_follow``).  ``follow``: None / False, True (the defaults) or a dict with search and / or max_sad;
+        """The ``follow`` / ``detect`` arguments of the product paths -> the ``follow`` of a plan: None, or (array, fmt, options of
+        ``Engine.track_follow``).  ``follow``: None / False, True (the defaults) or a dict with search and / or max_sad;
         ``detect=False`` follows in any case.  Both need a tracker."""
         if detect and not follow:
             return None
@@ -1240,7 +1256,7 @@ class CenterFace(object):
         o = dict(follow) if isinstance(follow, dict) else {}
         if set(o) - {"search", "max_sad"}:
             raise ValueError("follow takes search and max_sad, got %s" % sorted(o))
-        return frames, fmt, o
+        return _Frames(frames, fmt, o)
 
     def _followed(self, dets, lms, counts, hw, tiled):
         """The per-frame results of a chunk that was only followed: the tracked rows mapped from the tracker's space to frame pixels in
@@ -1257,15 +1273,15 @@ class CenterFace(object):
         return out
 
     def _scene(self, scenes, tracker, frames, fmt):
-        """The ``scenes`` argument of the product paths -> the ``scene`` of ``_drive``: None, or (scenes, frames, fmt).  Needs a tracker."""
+        """The ``scenes`` argument of the product paths -> the ``scene`` of a plan: None, or (scenes, array, fmt).  Needs a tracker."""
         if scenes is None:
             return None
         if tracker is None:
             raise ValueError("scenes= needs tracker=")
-        return scenes, frames, fmt
+        return _Scene(scenes, frames, fmt)
 
     def _lookback(self, lookback, flush, tracker, n):
-        """The ``lookback`` / ``flush`` arguments of the product paths -> the ``lookback`` of ``_drive``: None, or (lookback, flush, ready)
+        """The ``lookback`` / ``flush`` arguments of the product paths -> the ``lookback`` of a plan: None, or (lookback, flush, ready)
         with ``ready`` the n lists the call returns.  Needs a tracker, and the n streams of the call at one fill level: otherwise one
         step would be due for some of its images and not for others.  Refused before any engine call."""
         if lookback is None:
@@ -1279,120 +1295,155 @@ class CenterFace(object):
         fills = [lookback.fill(k) for k in range(n)]
         if len(set(fills)) > 1:
             raise ValueError("the streams of this call stand at different fill levels of the lookback object: %s" % (fills,))
-        return lookback, bool(flush), [[] for _ in range(n)]
+        return _Late(lookback, bool(flush), [[] for _ in range(n)])
 
-    def _lookback_redact(self, lookback, flush, tracker, redact, n):
-        """``_lookback`` for ``detect_tiled`` / ``detect_fit``, where it needs ``redact=``: without it there is nothing to delay."""
-        if lookback is not None and redact is None:
-            raise ValueError("lookback= needs redact=")
-        return self._lookback(lookback, flush, tracker, n)
+    def _plan(self, frames, fmt, take, *, tiled=False, tile=None, overlap=None, with_full=True, merge=("ios", 0.5, 2.0), fit=None, tracker=None,
+              follow=None, detect=True, scenes=None, lookback=None, flush=False, cover=None, draw=None):
+        """The plan of a public product method from the keyword arguments they share (``fit``: what ``_fit_options`` made of it;
+        ``cover`` / ``draw``: the options of that step).  ``fmt`` None: BGR images.  ``take`` says what the steps in frame space work on:
+        'copy' -- a new array, which the call returns (the inputs stay untouched); 'array' -- the frames as one uint8 array of the size
+        this instance was built for, unless they are fitted or tiled; 'given' -- the frames as they are (fitted or tiled only).  The
+        forward reads that array too, except on the untiled path of 'copy', which takes the input in ``_input_form``.  Refuses, in this
+        order and before any engine call: what ``_lookback`` refuses, frames of the wrong form, a source that cannot be had (the
+        instance's size, ``max_batch`` below the tiles of a frame), what ``_follow`` and ``_scene`` refuse."""
+        eng = self.engine
+        late = self._lookback(lookback, flush, tracker, len(frames))
+        fmt_, plain, per, rows = "bgr" if fmt is None else fmt, not tiled and fit is None, eng.max_batch, _RESCALE
+        if take == "copy" and plain and fmt is not None:                          # 4:2:0 frames of the instance's size go up as they are
+            src, forward = self._input_form(eng, frames, fmt)
+            array = np.stack([np.asarray(f) for f in src])                        # a new array: the inputs stay untouched
+        elif take == "copy":
+            frames = [np.asarray(f, dtype=np.uint8) for f in frames]
+            array = np.stack(frames)                                              # a new array: the inputs stay untouched
+            # (the copy comes BEFORE the batch that ``_input_form`` stacks: with the two large blocks allocated the other way round the
+            # allocator handed out cold pages in every call, and anonymize of 8 VGA frames took 3.0 ms instead of 1.4)
+            src, forward = self._input_form(eng, frames) if plain else (array, None)
+        elif take == "array":
+            bgr, array = _lib.frame_format(fmt) == _lib.CF_FRAME_BGR, np.ascontiguousarray(frames, dtype=np.uint8)
+            if array.ndim != (4 if bgr else 3):
+                raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (array.shape,))
+        else:
+            array = frames
+        if fit is not None:
+            src, forward, rows = array, lambda chunk: eng.forward_fit_enqueue(chunk, fmt_, **fit), _UNFIT
+        elif tiled:
+            (forward, per), src, rows = self._tiled_form(array, fmt_, tile, overlap, with_full, cover is not None or draw is not None), array, _MERGE
+        elif take == "array":
+            want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
+            if array.shape[1:] != want:
+                raise ValueError("frames must be %s per frame (this instance was built for %dx%d), got %s" % ((want,) + self.src_hw + (array.shape[1:],)))
+            src, forward = array, eng.forward_resized_enqueue if bgr else lambda chunk: eng.forward_yuv_enqueue(chunk, fmt)
+        step = lambda options: None if options is None else _Frames(array, fmt_, options)      # noqa: E731
+        return _Plan(src, forward, per, rows, merge, array if take == "copy" else None, tracker, follow=self._follow(follow, detect, tracker, array, fmt_),
+                     scene=self._scene(scenes, tracker, array, fmt_), detect=detect, cover=step(cover), draw=step(draw), lookback=late)
 
-    def _lookback_out(self, eng, lb, i, rows, cover, draw, ready):
+    def _plain(self, imgs, fmt=None, **steps):
+        """The plan of the paths that only detect: the input in ``_input_form``, the decode rescales."""
+        return _Plan(*self._input_form(self.engine, imgs, fmt), self.engine.max_batch, **steps)
+
+    @contextlib.contextmanager
+    def _rescaled(self, plan, on):
+        """centerface.py:55-62 inside the decode kernel while the block runs -- where ``on`` and the plan's rows reach frame space that
+        way --, switched off again whatever happens in it."""
+        on = on and plan.rows == _RESCALE
+        if on:
+            self.engine.set_rescale(self.scale_h, self.scale_w)
+        try:
+            yield
+        finally:
+            if on:
+                self.engine.set_rescale(0.0, 0.0)
+
+    def _run(self, plan):
+        """The chunk loop of every product path.  Per chunk of ``plan.per`` frames, image b of the chunk at frame i being stream i + b:
+        the scene check; the detection (``_detect_chunk``) -- of every chunk with ``detect``, else of a key chunk, in which a frame is a
+        stream's FIRST or a CUT --; the steps behind it (``_chunk_steps``): follow, best-shot offer, lookback step, cover, draw, chips.
+        Behind the last chunk ``_finish``.  The decode rescales for the whole call with ``detect``, else around a key chunk's detection.
+        Returns the lookback's lists, (the output copy, the per-frame results) or the per-frame results."""
+        eng, res = self.engine, []
+        with self._rescaled(plan, plan.detect):
+            for i in range(0, len(plan.frames), plan.per):
+                codes, key, sc = None, plan.detect, plan.scene
+                if sc is not None and plan.lookback is not None and plan.detect:      # the codes go to the step in a device buffer
+                    codes = plan.lookback.lookback._scene_codes(eng)
+                    eng.scene_check(sc.array[i:i + plan.per], sc.fmt, sc.scenes, plan.tracker, i, codes=False, out_ptr=codes)
+                elif sc is not None:
+                    codes = eng.scene_check(sc.array[i:i + plan.per], sc.fmt, sc.scenes, plan.tracker, i, codes=not plan.detect)
+                    key = plan.detect or bool((codes[:, 0] != _lib.CF_SCENE_SAME).any())
+                res.extend(self._chunk_steps(plan, i, self._detect_chunk(plan, i) if key else None, codes))
+            self._finish(plan)
+        return plan.lookback.ready if plan.lookback is not None else res if plan.out is None else (plan.out, res)
+
+    def _detect_chunk(self, plan, i):
+        """The detection of the chunk at frame i: forward, decode, the rows to frame space, the tracker's update; the per-frame results."""
+        eng = self.engine
+        with self._rescaled(plan, not plan.detect):
+            plan.forward(plan.frames[i:i + plan.per])
+            if plan.rows == _RESCALE:
+                res = self._decode(eng)
+            else:
+                eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
+                rows = eng.unfit_rows(self.max_dets) if plan.rows == _UNFIT else eng.merge_tiles(*plan.merge, self.max_dets)
+                res = self._postprocess_many(rows[0], rescaled=True)
+            if plan.tracker is not None:
+                eng.track_update_device(plan.tracker, i)
+        return res
+
+    def _chunk_steps(self, plan, i, res, codes):
+        """The steps behind the detection of the chunk at frame i, while the engine still holds its rows: the follow (without ``detect``
+        its rows are the results); the chips of the tracked rows offered to the best shots; with a lookback its step -- the chunk's
+        frames are retained and the due ones covered and drawn (``_lookback_out``) --, else the chunk's frames covered and drawn; the
+        chips, which join the results.  ``codes``: what the scene check left for the lookback step.  Returns the chunk's results."""
+        eng, j, follow, best = self.engine, i + plan.per, plan.follow, plan.best
+        if follow is not None:
+            part = follow.array[i:j]
+            d, l, _, n, _ = eng.track_follow(part, follow.fmt, plan.tracker, i, **follow.options)
+            if not plan.detect:
+                res = self._followed(d, l, n, _lib.frame_planes(part, follow.fmt, writable=False)[2:4], plan.rows != _RESCALE)
+        if best is not None:
+            part = best.array[i:j]
+            cut, offs, _ = eng.align_faces_frame(part, best.fmt, best.shots.size, template=best.template)
+            eng.bestshot_offer(best.shots, cut, offs, _lib.frame_planes(part, best.fmt, writable=False)[2:4], i)
+        if plan.lookback is not None:
+            lb, part = plan.lookback.lookback, (plan.draw if plan.cover is None else plan.cover).array[i:j]
+            lb._retain(i, part)
+            self._lookback_out(plan, i, eng.lookback_step(lb, i, len(part), push=True, scene=codes))
+        else:
+            self._paint(plan, lambda array: array[i:j])
+        if plan.chips is not None:
+            cut, offs, _ = plan.chips(i, j)
+            res = [(d, l, cut[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(res)]
+        return res
+
+    def _paint(self, plan, frames_of):
+        """Cover, then draw, the faces of the rows the engine holds in ``frames_of(the step's array)``."""
+        if plan.cover is not None:
+            self.engine.cover_faces(frames_of(plan.cover.array), plan.cover.fmt, **plan.cover.options)
+        if plan.draw is not None:
+            self.engine.draw_faces(frames_of(plan.draw.array), plan.draw.fmt, **plan.draw.options)
+
+    def _lookback_out(self, plan, i, rows):
         """Behind a step of the streams i .. i + B - 1: where a frame became due, the retained copies of those frames are covered or
         drawn with the lookback rows the engine holds, and (frame, dets, lms, info) joins ``ready`` per stream."""
         dets, lms, info, counts, state = rows
-        B = len(counts)
         if not (state[:, 0] >= 0).any():
             return
-        due = np.stack([lb._frames[i + b].pop(0) for b in range(B)])         # (the streams of a call stand at one fill level: all are due)
-        if cover is not None:
-            eng.cover_faces(due, cover[1], **cover[2])
-        if draw is not None:
-            eng.draw_faces(due, draw[1], **draw[2])
-        for b in range(B):
-            n = int(counts[b])
-            ready[i + b].append((due[b], dets[b, :n].copy(), lms[b, :n].copy(), info[b, :n].copy()))
+        due = plan.lookback.lookback._due(i, len(counts))                    # (the streams of a call stand at one fill level: all are due)
+        self._paint(plan, lambda array: due)
+        for b, n in enumerate(counts):
+            plan.lookback.ready[i + b].append((due[b], dets[b, :n].copy(), lms[b, :n].copy(), info[b, :n].copy()))
 
-    def _drive(self, frames, forward, per=None, *, merge=None, tracker=None, cover=None, chips=None, draw=None, follow=None, detect=True, best=None,
-               scene=None, lookback=None):
-        """The chunk loop of every product path: ``forward`` enqueues ``frames`` in slices of ``per`` (default ``max_batch``), each is
-        decoded, and while the engine still holds it the steps that were asked for run in this order: ``tracker`` is advanced -- image b
-        of the chunk that starts at frame i continues its stream i + b --, ``cover`` = (array, fmt, options) has the chunk's slice of
-        the array covered, ``draw`` = (array, fmt, options) has it annotated (``Engine.draw_faces``), ``chips(i, j)`` cuts the chips of
-        frames i:j, which join the results.  ``follow`` = (array, fmt, options) has the tracker's faces followed in the chunk's slice of
-        the array right behind the update (``Engine.track_follow``), before anything is covered or drawn; with ``detect=False`` there is no
-        forward, decode or update at all -- each chunk is followed, then covered or drawn, and its results are the followed rows
-        (``_followed``).  ``merge`` = (metric, thresh, edge) says
-        that the forward is a tiled one: the tiles' rows are merged, in frame pixels; ``merge='unfit'`` that it is a fitted one: the
-        rows are mapped back into frame pixels (``Engine.unfit_rows``); otherwise the decode rescales, and the rescale is
-        switched off again whatever happens.  ``best`` = (shots, array, fmt, template, flush, sink): behind the update and the follow the
-        chips of the tracked rows are cut from the chunk's slice of the array (``Engine.align_faces_frame`` at ``shots.size``) and offered
-        to ``shots`` (``Engine.bestshot_offer``); after the loop ONE ``Engine.bestshot_collect`` over the call's streams (``flush``) is
-        appended to ``sink``.  ``scene`` = (scenes, array, fmt): per chunk, before anything else, the chunk's slice of the array is checked
-        for scene cuts (``Engine.scene_check`` with the tracker, stream i + b), which frees the tracks of the cut streams on the device.
-        With ``detect=True`` no code is read on the host.  With ``detect=False`` the codes are read (B x 4 ints per chunk), and a chunk in
-        which any frame is FIRST or CUT becomes a key frame: forward, decode (merge), update, then the follow it would have had -- the new
-        scene's faces are detected and covered in that same frame; its results are still the followed rows.  ``lookback`` = (lookback,
-        flush, ready): behind the update and the follow the chunk's slice of the ``cover`` / ``draw`` array is retained by the
-        ``Lookback`` and its tracked rows are pushed (``Engine.lookback_step``, stream i + b; with ``scene`` and ``detect=True`` the
-        chunk's scene codes go from the check to the step in a device buffer); the frames that become due -- the retained ones of
-        ``depth`` calls ago, not this chunk's -- are covered or drawn instead of the chunk's and join ``ready``; with ``flush`` the streams
-        are drained after the loop.  Returns the per-frame results."""
-        eng, out = self.engine, []
-        per = per or eng.max_batch
-        if merge is None and detect:
-            eng.set_rescale(self.scale_h, self.scale_w)                      # centerface.py:55-62 inside the decode kernel
-        try:
-            for i in range(0, len(frames), per):
-                key = detect
-                if scene is not None and lookback is not None and detect:
-                    codes = lookback[0]._scene_codes(eng)
-                    eng.scene_check(scene[1][i:i + per], scene[2], scene[0], tracker, i, codes=False, out_ptr=codes)
-                elif scene is not None:
-                    codes = eng.scene_check(scene[1][i:i + per], scene[2], scene[0], tracker, i, codes=not detect)
-                    key = detect or bool((codes[:, 0] != _lib.CF_SCENE_SAME).any())
-                if key:
-                    if merge is None and not detect:
-                        eng.set_rescale(self.scale_h, self.scale_w)
-                    try:
-                        forward(frames[i:i + per])
-                        if merge is None:
-                            res = self._decode(eng)
-                        else:
-                            eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
-                            rows = eng.unfit_rows(self.max_dets) if merge == "unfit" else eng.merge_tiles(*merge, self.max_dets)
-                            res = self._postprocess_many(rows[0], rescaled=True)
-                        if tracker is not None:
-                            eng.track_update_device(tracker, i)
-                    finally:
-                        if merge is None and not detect:
-                            eng.set_rescale(0.0, 0.0)
-                if follow is not None:
-                    part = follow[0][i:i + per]
-                    d, l, _, n, _ = eng.track_follow(part, follow[1], tracker, i, **follow[2])
-                    if not detect:
-                        res = self._followed(d, l, n, _lib.frame_planes(part, follow[1], writable=False)[2:4], merge is not None)
-                if best is not None:
-                    part = best[1][i:i + per]
-                    cut, offs, _ = eng.align_faces_frame(part, best[2], best[0].size, template=best[3])
-                    eng.bestshot_offer(best[0], cut, offs, _lib.frame_planes(part, best[2], writable=False)[2:4], i)
-                if lookback is not None:
-                    lb, part = lookback[0], (cover if cover is not None else draw)[0][i:i + per]
-                    for b in range(len(part)):
-                        lb._frames[i + b].append(part[b])
-                    rows = eng.lookback_step(lb, i, len(part), push=True, scene=codes if scene is not None else None)
-                    self._lookback_out(eng, lb, i, rows, cover, draw, lookback[2])
-                else:
-                    if cover is not None:
-                        eng.cover_faces(cover[0][i:i + per], cover[1], **cover[2])
-                    if draw is not None:
-                        eng.draw_faces(draw[0][i:i + per], draw[1], **draw[2])
-                if chips is not None:
-                    cut, offs, _ = chips(i, i + per)
-                    res = [(d, l, cut[offs[b]:offs[b + 1]]) for b, (d, l) in enumerate(res)]
-                out.extend(res)
-            if best is not None and len(frames):
-                best[5].append(eng.bestshot_collect(best[0], 0, len(frames), flush=best[4]))
-            if lookback is not None and lookback[1]:
-                lb = lookback[0]
-                while len(frames) and lb.fill(0) > 0:                            # the end of the video: one drain per frame still in the line
-                    for i in range(0, len(frames), per):
-                        B = min(per, len(frames) - i)
-                        self._lookback_out(eng, lb, i, eng.lookback_step(lb, i, B, push=False), cover, draw, lookback[2])
-        finally:
-            if merge is None and detect:
-                eng.set_rescale(0.0, 0.0)
-        return out
+    def _finish(self, plan):
+        """Behind the last chunk: ONE collect of the best shots over the call's streams; with ``flush`` the lookback's streams are
+        drained, one step per frame still in the line."""
+        eng, n = self.engine, len(plan.frames)
+        if plan.best is not None and n:
+            plan.best.sink.append(eng.bestshot_collect(plan.best.shots, 0, n, flush=plan.best.flush))
+        if plan.lookback is not None and plan.lookback.flush:
+            lb = plan.lookback.lookback
+            while n and lb.fill(0) > 0:                                           # the end of the video
+                for i in range(0, n, plan.per):
+                    self._lookback_out(plan, i, eng.lookback_step(lb, i, min(plan.per, n - i), push=False))
 
     def detect_aligned(self, imgs, size=112, **chip_options):
         """``detect_batch`` plus the aligned chip of every detection: one (dets, lms, chips) per image, dets / lms exactly those of
@@ -1401,7 +1452,7 @@ class CenterFace(object):
         detections gives an empty [0, ...] chip array."""
         if not self.landmarks:
             raise ValueError("detect_aligned needs the landmarks: construct CenterFace(..., landmarks=True)")
-        return self._drive(*self._input_form(self.engine, imgs), chips=lambda i, j: self.engine.align_faces(size, **chip_options))
+        return self._run(self._plain(imgs, chips=lambda i, j: self.engine.align_faces(size, **chip_options)))
 
     def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, fit=None, **chip_options):
         """Detection plus the aligned chip of every detection cut from the FRAME ITSELF (``Engine.align_faces_frame``), not from the
@@ -1415,19 +1466,8 @@ class CenterFace(object):
         fit = self._fit_options(fit, tiled)
         if not self.landmarks:
             raise ValueError("detect_aligned_frames needs the landmarks: construct CenterFace(..., landmarks=True)")
-        bgr = _lib.frame_format(fmt) == _lib.CF_FRAME_BGR
-        frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        if frames.ndim != (4 if bgr else 3):
-            raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (frames.shape,))
-        eng = self.engine
-        chips = lambda i, j: eng.align_faces_frame(frames[i:j], fmt, size, **chip_options)      # noqa: E731
-        if tiled or fit is not None:
-            forward, per, merge = self._frame_form(frames, fmt, tile, overlap, fit, False)
-            return self._drive(frames, forward, per, merge=merge, chips=chips)
-        want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
-        if frames.shape[1:] != want:
-            raise ValueError("frames must be %s per frame (this instance was built for %dx%d), got %s" % ((want,) + self.src_hw + (frames.shape[1:],)))
-        return self._drive(frames, eng.forward_resized_enqueue if bgr else lambda chunk: eng.forward_yuv_enqueue(chunk, fmt), chips=chips)
+        plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit)
+        return self._run(plan._replace(chips=lambda i, j: self.engine.align_faces_frame(plan.frames[i:j], fmt, size, **chip_options)))
 
     def _tiled_form(self, frames, fmt, tile, overlap, with_full, writable):
         """(forward, frames per chunk) of the tiled paths: the enqueue that cuts any slice of ``frames`` into the tiles of their size."""
@@ -1455,13 +1495,6 @@ class CenterFace(object):
         _lib.fit_opts(**o)                                                    # refuse bad names and bytes before any work
         return o
 
-    def _frame_form(self, frames, fmt, tile, overlap, fit, writable):
-        """(forward, frames per chunk, merge) of the paths whose rows are in frame pixels: the fitted forward when ``fit`` (the options
-        of ``_fit_options``) is not None, else the tiled one with the default merge."""
-        if fit is not None:
-            return lambda chunk: self.engine.forward_fit_enqueue(chunk, fmt, **fit), None, "unfit"
-        return self._tiled_form(frames, fmt, tile, overlap, True, writable) + (("ios", 0.5, 2.0),)
-
     def detect_fit(self, frames, fmt="bgr", *, anchor="center", upscale=True, fill=(0, 0, 0), redact=None, tracker=None, follow=None, detect=True,
                    scenes=None, lookback=None, flush=False):
         """Detection of frames of another size -- or shape -- than the network input WITHOUT the stretch of ``detect_batch``: every frame
@@ -1475,12 +1508,10 @@ class CenterFace(object):
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         fit = self._fit_options(dict(anchor=anchor, upscale=upscale, fill=fill))
-        forward, per, merge = self._frame_form(frames, fmt, None, None, fit, redact is not None)
-        look = self._lookback_redact(lookback, flush, tracker, redact, len(frames))
-        res = self._drive(frames, forward, per, merge=merge, tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
-                          follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
-                          scene=self._scene(scenes, tracker, frames, fmt), **({} if look is None else {"lookback": look}))
-        return res if look is None else look[2]
+        if lookback is not None and redact is None:
+            raise ValueError("lookback= needs redact=")                         # (without it there is nothing to delay)
+        return self._run(self._plan(frames, fmt, "given", fit=fit, tracker=tracker, follow=follow, detect=detect, scenes=scenes, lookback=lookback,
+                                    flush=flush, cover=redact))
 
     def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None,
                      tracker=None, follow=None, detect=True, scenes=None, lookback=None, flush=False):
@@ -1500,12 +1531,10 @@ class CenterFace(object):
         redacted in place, the return is the lists of ``anonymize(lookback=)``."""
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
-        look = self._lookback_redact(lookback, flush, tracker, redact, len(frames))
-        res = self._drive(frames, *self._tiled_form(frames, fmt, tile, overlap, with_full, redact is not None), merge=(metric, thresh, edge),
-                          tracker=tracker, cover=None if redact is None else (frames, fmt, redact),
-                          follow=self._follow(follow, detect, tracker, frames, fmt), detect=detect,
-                          scene=self._scene(scenes, tracker, frames, fmt), **({} if look is None else {"lookback": look}))
-        return res if look is None else look[2]
+        if lookback is not None and redact is None:
+            raise ValueError("lookback= needs redact=")                         # (without it there is nothing to delay)
+        return self._run(self._plan(frames, fmt, "given", tiled=True, tile=tile, overlap=overlap, with_full=with_full, merge=(metric, thresh, edge),
+                                    tracker=tracker, follow=follow, detect=detect, scenes=scenes, lookback=lookback, flush=flush, cover=redact))
 
     def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None,
                   flush=False, **options):
@@ -1539,46 +1568,21 @@ class CenterFace(object):
         the video: the stream is drained) up to ``depth + 1``; dets and lms are the covered rows, in the tracker's space, back-filled ones
         with hits 0 and misses = the distance.  The streams of a call must stand at one fill level (ValueError).  With the defaults every
         call does what it did without them."""
-        _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
-        fit = self._fit_options(fit, tiled)
-        look = self._lookback(lookback, flush, tracker, len(imgs))
-        imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
-        out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
-        late = {} if look is None else {"lookback": lookback, "flush": flush}
-        if fit is not None:
-            res = self.detect_fit(out, "bgr", **fit, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes, **late)
-            return res if late else (out, res)
-        if tiled:
-            res = self.detect_tiled(out, tile, overlap, "bgr", redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes, **late)
-            return res if late else (out, res)
-        res = self._drive(*self._input_form(self.engine, imgs), tracker=tracker, cover=(out, "bgr", options),
-                          follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"),
-                          **({} if look is None else {"lookback": look}))
-        return (out, res) if look is None else look[2]
+        return self._anonymize(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
+                               scenes=scenes, lookback=lookback, flush=flush)
 
     def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
                       scenes=None, lookback=None, flush=False, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
         [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow``,
         ``fit``, ``detect``, ``scenes``, ``lookback`` and ``flush``: as ``anonymize``."""
-        _lib.split_redact_options(options)
-        fit = self._fit_options(fit, tiled)
-        look = self._lookback(lookback, flush, tracker, len(frames))
-        late = {} if look is None else {"lookback": lookback, "flush": flush}
-        if fit is not None:                                             # frames of any even size: [B, h*3//2, w]
-            out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            res = self.detect_fit(out, fmt, **fit, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes, **late)
-            return res if late else (out, res)
-        if tiled:                                                       # frames of any even size: [B, h*3//2, w]
-            out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            res = self.detect_tiled(out, tile, overlap, fmt, redact=options, tracker=tracker, follow=follow, detect=detect, scenes=scenes, **late)
-            return res if late else (out, res)
-        frames, forward = self._input_form(self.engine, frames, fmt)
-        out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
-        res = self._drive(frames, forward, tracker=tracker, cover=(out, fmt, options),
-                          follow=self._follow(follow, detect, tracker, out, fmt), detect=detect, scene=self._scene(scenes, tracker, out, fmt),
-                          **({} if look is None else {"lookback": look}))
-        return (out, res) if look is None else look[2]
+        return self._anonymize(frames, fmt, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
+                               scenes=scenes, lookback=lookback, flush=flush)
+
+    def _anonymize(self, frames, fmt, options, *, tiled, fit, **shared):
+        """The body of ``anonymize`` (``fmt`` None: BGR images) and ``anonymize_yuv``: the copy of the frames is covered."""
+        _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
+        return self._run(self._plan(frames, fmt, "copy", tiled=tiled, fit=self._fit_options(fit, tiled), cover=options, **shared))
 
     def best_shots(self, frames, fmt="bgr", *, tracker, shots, tiled=False, tile=None, overlap=None, fit=None, follow=None, detect=True,
                    flush=False, template=None, scenes=None):
@@ -1597,28 +1601,14 @@ class CenterFace(object):
             raise ValueError("best_shots needs the landmarks: construct CenterFace(..., landmarks=True)")
         if tracker is None or shots is None:
             raise ValueError("best_shots needs tracker= and shots=")
-        bgr = _lib.frame_format(fmt) == _lib.CF_FRAME_BGR
-        frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        if frames.ndim != (4 if bgr else 3):
-            raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (frames.shape,))
-        eng, sink = self.engine, []
-        best = (shots, frames, fmt, template, bool(flush), sink)
-        fol = self._follow(follow, detect, tracker, frames, fmt)
-        scn = self._scene(scenes, tracker, frames, fmt)
-        if tiled or fit is not None:
-            forward, per, merge = self._frame_form(frames, fmt, tile, overlap, fit, False)
-            self._drive(frames, forward, per, merge=merge, tracker=tracker, follow=fol, detect=detect, best=best, scene=scn)
-        else:
-            want = self.src_hw + (3,) if bgr else (self.src_hw[0] * 3 // 2, self.src_hw[1])
-            if frames.shape[1:] != want:
-                raise ValueError("frames must be %s per frame (this instance was built for %dx%d), got %s" % ((want,) + self.src_hw + (frames.shape[1:],)))
-            self._drive(frames, eng.forward_resized_enqueue if bgr else lambda chunk: eng.forward_yuv_enqueue(chunk, fmt), tracker=tracker, follow=fol,
-                        detect=detect, best=best, scene=scn)
+        plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
+        sink = []
+        self._run(plan._replace(best=_Best(shots, plan.frames, fmt, template, bool(flush), sink)))
         if not sink:
             return []
         chips, quality, records, dets, lms, counts = sink[0][:6]
         return [[{"id": int(records[s, k, 0]), "quality": int(quality[s, k]), "chip": chips[s, k].copy(), "det": dets[s, k].copy(), "lms": lms[s, k].copy(),
-                  "record": records[s, k].copy()} for k in range(int(counts[s]))] for s in range(len(frames))]
+                  "record": records[s, k].copy()} for k in range(int(counts[s]))] for s in range(len(plan.frames))]
 
     def _draw_options(self, options, tracker, yuv):
         """The options of ``annotate`` / ``annotate_yuv`` -> those of ``Engine.draw_faces``: the reference's look (demo.py:15-23: green
@@ -1642,42 +1632,22 @@ class CenterFace(object):
         ``anonymize``: with a tracker the label is the track id and the tracks held through a dropout are drawn too, dashed, in
         ``held_color``.  ``fit``, ``follow``, ``detect`` and ``scenes``: as ``anonymize``.  ``lookback`` and ``flush``: as ``anonymize`` --
         the delayed frames are drawn, a back-filled row as a held one (dashed, in ``held_color``), and the return is the lists."""
-        fit = self._fit_options(fit, tiled)
-        look = self._lookback(lookback, flush, tracker, len(imgs))
-        imgs = [np.asarray(im, dtype=np.uint8) for im in imgs]
-        out = np.stack(imgs)                                                  # a new array: the inputs stay untouched
-        draw = (out, "bgr", self._draw_options(options, tracker, False))
-        fo = dict(follow=self._follow(follow, detect, tracker, out, "bgr"), detect=detect, scene=self._scene(scenes, tracker, out, "bgr"))
-        if look is not None:
-            fo["lookback"] = look
-        if tiled or fit is not None:
-            forward, per, merge = self._frame_form(out, "bgr", tile, overlap, fit, True)
-            res = self._drive(out, forward, per, merge=merge, tracker=tracker, draw=draw, **fo)
-        else:
-            res = self._drive(*self._input_form(self.engine, imgs), tracker=tracker, draw=draw, **fo)
-        return (out, res) if look is None else look[2]
+        return self._annotate(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
+                              scenes=scenes, lookback=lookback, flush=flush)
 
     def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
                      scenes=None, lookback=None, flush=False, **options):
         """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
         in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``fit``, ``scenes``, ``lookback`` and
         ``flush``: as ``annotate``."""
+        return self._annotate(frames, fmt, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
+                              scenes=scenes, lookback=lookback, flush=flush)
+
+    def _annotate(self, frames, fmt, options, *, tiled, fit, tracker, **shared):
+        """The body of ``annotate`` (``fmt`` None: BGR images) and ``annotate_yuv``: the copy of the frames is drawn into."""
         fit = self._fit_options(fit, tiled)
-        o = self._draw_options(options, tracker, True)
-        look = self._lookback(lookback, flush, tracker, len(frames))
-        late = {} if look is None else {"lookback": look}
-        if tiled or fit is not None:                                    # frames of any even size: [B, h*3//2, w]
-            out = np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
-            forward, per, merge = self._frame_form(out, fmt, tile, overlap, fit, True)
-            res = self._drive(out, forward, per, merge=merge, tracker=tracker,
-                              draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
-                              scene=self._scene(scenes, tracker, out, fmt), **late)
-            return (out, res) if look is None else look[2]
-        frames, forward = self._input_form(self.engine, frames, fmt)
-        out = np.stack([np.asarray(f) for f in frames])                 # a new array: the inputs stay untouched
-        res = self._drive(frames, forward, tracker=tracker, draw=(out, fmt, o), follow=self._follow(follow, detect, tracker, out, fmt), detect=detect,
-                          scene=self._scene(scenes, tracker, out, fmt), **late)
-        return (out, res) if look is None else look[2]
+        return self._run(self._plan(frames, fmt, "copy", tiled=tiled, fit=fit, tracker=tracker, draw=self._draw_options(options, tracker, fmt is not None),
+                                    **shared))
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]
@@ -1700,7 +1670,7 @@ class CenterFace(object):
         the same results as ``detect_batch([cv2.cvtColor(f, cv2.COLOR_YUV2BGR_<fmt>) for f in frames])``, with the conversion on the
         device and half the bytes of BGR over the link.  ``frames``: uint8 [B, height*3//2, width] or a list of [height*3//2, width]
         arrays, (height, width) = the size this instance was built for (ValueError otherwise)."""
-        return self._drive(*self._input_form(self.engine, frames, fmt))
+        return self._run(self._plain(frames, fmt))
 
     def detect_stream(self, imgs, threshold=0.2, *, fmt=None):
         """``__call__`` over an iterable of same-sized images, results yielded in order (the loop of demo.py:30-38 /

@@ -333,6 +333,35 @@ def test_best_shots_issues_exactly_these_calls_over_two_chunks(flush):
         face.best_shots(frames[:, :10], tracker=pp.TRK, shots=SHOTS)
 
 
+@pytest.mark.parametrize("how", ("tiled", "fit"))
+def test_best_shots_tiled_and_fitted_collect_once_after_the_last_chunk(how):
+    """The chips are cut from the frames behind the merge (the unfit) and the update of every chunk; ONE collect over streams 0 .. n stands
+    after the last chunk, and nothing rescales."""
+    script = pp.Script()
+    face = pp.make_face((pp.YH, pp.YW), BestEngine(script))
+    n, per = 3, pp.BGR_EVEN
+    frames = np.zeros((n,) + per, np.uint8)
+    got = face.best_shots(frames, tracker=pp.TRK, shots=SHOTS, **({"tiled": True} if how == "tiled" else {"fit": dict(anchor="topleft")}))
+    rects = tuple(map(tuple, pp.ops.tile_grid(pp.YH, pp.YW, (pp.NH, pp.NW), 24, True).tolist()))
+    step = pp.NB // len(rects) if how == "tiled" else pp.NB
+    want = []
+    for i in range(0, n, step):
+        b = min(step, n - i)
+        part, faces = pp.chunk(i, b, per, "frames"), list(pp.COUNTS[i:i + b])
+        if how == "tiled":
+            want += [("forward_tiles_enqueue", part, rects, "bgr"), ("decode_threshold", 0.3, pp.NMS, pp.MAXD), ("merge_tiles", "ios", 0.5, 2.0, pp.MAXD)]
+        else:
+            want += [("forward_fit_enqueue", part, "bgr", dict(pp.FIT, anchor="topleft")), ("decode_threshold", 0.3, pp.NMS, pp.MAXD), ("unfit_rows", pp.MAXD)]
+        ids = list(range(sum(pp.COUNTS[:i]), sum(pp.COUNTS[:i + b])))
+        want += [("track_update_device", True, i), ("align_faces_frame", part, "bgr", 16, dict(template=None)),
+                 ("bestshot_offer", True, (len(ids), 16, 16, 3), ids, np.concatenate([[0], np.cumsum(faces)]).tolist(), (pp.YH, pp.YW), i)]
+    want += [("bestshot_collect", True, 0, n, None, False)]
+    log = [e[1:] for e in pp.resolve(script.log, dict(frames=frames))]
+    assert log == want
+    assert [e[0] for e in log].count("bestshot_collect") == 1 and log[-1][0] == "bestshot_collect" and not frames.any()
+    assert [len(s) for s in got] == [1, 0, 2]
+
+
 def test_drive_without_best_issues_no_bestshot_call():
     script = pp.Script()
     face = pp.make_face((pp.H, pp.W), BestEngine(script))

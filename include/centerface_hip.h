@@ -777,6 +777,63 @@ int cf_lookback_forget(cf_lookback* lb, int stream);
 int cf_lookback_step(cf_ctx* ctx, cf_lookback* lb, int stream0, int B, int push, const int32_t* scene, int scene_on_device,
                      float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* state, int out_on_device);
 
+/* ---- lookback with a trace: the back-filled boxes follow the face through the queued frames (opt-in) ---------------------------------
+ * cf_lookback_step paints a back-filled box where the face was first detected.  A person who walks into the picture is not there in the
+ * frames before: at 12 pixels per frame the face is 96 pixels from its birth box at distance 8.  With cf_lookback_trace_enable the
+ * object also keeps the LUMA of every queued frame on the device, a pushing step matches every newborn face BACKWARDS through those
+ * planes with the follower's block matching (cell means, a 16 x 16 cell template, SAD search, one 64-bit min key: see "follow tracked
+ * faces between detections"), and the emit moves the back-filled box to where the walk found the face.  cf_follow_opts is the
+ * follower's (search R in 1..8, max_sad in 0..65280); the defaults the Python layer uses (4, 4096) are this project's choices:
+ * no accuracy claim is made.  WITHOUT THE CALL EVERYTHING ABOVE HOLDS AS IT STANDS, bit for bit.
+ *
+ * cf_lookback_trace_enable allocates, for an object nothing was pushed into yet, the luma ring -- per stream depth + 1 planes of h rows
+ * of (w + 15) & ~15 bytes: 16 streams, depth 8, 1920 x 1080: 298 MB -- and the trace table -- per queue entry rows x depth x 4 int32.
+ * CF_ESTATE when the object was pushed into already (an entry without luma cannot be traced through) or is enabled already.  CF_EINVAL,
+ * before any GPU work, for bad options (the follower's texts), h or w odd, below 2 or above 8192, and an object of another device (ctx
+ * == NULL: the arguments are still checked first, cf_op_last_error names the cause).  CF_ENOMEM when the ring does not fit.
+ *
+ * Once enabled: cf_lookback_step with push != 0 is CF_ESTATE (the frame is missing); with push == 0 it stays allowed and emits what
+ * cf_lookback_step_frames with push == 0 emits.  cf_lookback_step_frames on an object that is not enabled is CF_ESTATE; a pushed (h, w)
+ * other than the enabled one is CF_EINVAL.  Frames, formats, pitches, alignment and on_device are those of cf_track_follow (the frames
+ * are only read; host frames are copied up, never back); every state rule -- which rows a push takes, the refusal of a second push, which
+ * calls take the lookback rows afterwards, the ordering on the object's event -- is cf_lookback_step's.  With push == 0, frames may be
+ * NULL and the frame arguments are ignored.
+ *
+ * A step with push, per stream; frames[b] MUST be the frame the pushed rows belong to.
+ *   1. Retain.  The luma of frames[b] -- the follower's: the Y byte, or (29*B + 150*G + 77*R + 128) >> 8 -- is stored in the ring plane of
+ *      the entry the push fills, which is decided from the queue's words on the device: no head or fill is read on the host.
+ *   2. Push.  As step 1 of cf_lookback_step.
+ *   3. Trace.  After the push the queue is q_0 (oldest) .. q_m = E (the new entry), m <= depth; L_k is the retained luma of q_k.  Rows
+ *      in network space: fx = w / W, fy = h / H in float64; rows in frame space: fx = fy = 1 and (h, w) must be the latched size; which
+ *      of the two is what the object latched on its first push.  For every row i of E with born set and four finite corners:
+ *        Learn.  The follower's geometry from the row's box as stored: side, CX, CY, S, c = (S + 15) / 16.  When side is not > 0 the
+ *          row's trace is 0, 0, 0, CF_FOLLOW_NONE at every distance.  Otherwise tpl = the cells i, j in [-8, 8) about (CX, CY) in L_m,
+ *          and PX = PY = 0.
+ *        Walk, for d = 1 .. m:  (a) if q_(m-d+1) has cut set (for d = 1 that is E itself) the chain ends; those distances are never
+ *          read by an emit.  (b) Window = the cells [-8-R, 8+R) of size c about (CX + PX, CY + PY) in L_(m-d).  (c) The best (dx, dy) in
+ *          [-R, R]^2 by the follower's key: smallest SAD, then dx*dx + dy*dy, then dy, then dx.  (d) SAD > max_sad: T[i][d] = PX, PY,
+ *          SAD, CF_FOLLOW_LOST; the chain ends, and every further distance takes the same four words.  (e) Otherwise PX += dx*c, PY +=
+ *          dy*c and T[i][d] = PX, PY, SAD, CF_FOLLOW_MOVED.
+ *        The template is that of the birth frame throughout: nothing is refreshed, nothing is kept past the step.  Integers throughout.
+ *   4. Emit.  As steps 2 and 3 of cf_lookback_step -- eligibility, confirm, the stop at a cut, the `rows` capacity with its flag bit and
+ *      the order are unchanged -- except for the appended back-filled rows: a row of e_j at distance j reads (PX, PY, SAD, code) =
+ *      T[row][j] of e_j's table.  PX == 0 and PY == 0: the row is appended exactly as by cf_lookback_step.  Otherwise every x of the box
+ *      and of the ten landmarks becomes (float)((double)x + (double)PX / fx), every y (float)((double)y + (double)PY / fy) (the
+ *      follower's formula), and THEN the moved box is grown by g = 1 + grow * j in the order stated above.  info = id, 0, j as before.
+ *      moves[b][rows][4] = PX, PY, SAD, code for the back-filled rows and 0, 0, 0, CF_FOLLOW_NONE for own rows; rows at and past the
+ *      largest count of the batch are not written.
+ * So: on a sequence in which displacement 0 is always the best match -- identical frames, by the smallest-move tie rule -- the output
+ * equals that of cf_lookback_step bit for bit.  A LOST chain leaves the box where the walk last had the face.
+ * On the device: a bandwidth-bound retain pass per pushed frame (16-byte loads and stores; 48 BGR bytes give 16 lumas), one workgroup
+ * per (pushed row, stream) for the trace, which leaves at once for a row that is not born, and the one launch of cf_lookback_step. */
+int cf_lookback_trace_enable(cf_ctx* ctx, cf_lookback* lb, const cf_follow_opts* opts, int h, int w);
+/* dets [B][rows][5], lms [B][rows][10], info [B][rows][3], counts [B], state [B][4], moves [B][rows][4]; any may be NULL; out_on_device as
+ * for cf_lookback_step.  CF_EINVAL, before any GPU work, for B below 1 and, with push != 0, every geometry and plane error of
+ * cf_track_follow (ctx == NULL: these are still checked first, cf_op_last_error names the cause). */
+int cf_lookback_step_frames(cf_ctx* ctx, cf_lookback* lb, int stream0, int B, int push, const int32_t* scene, int scene_on_device,
+                            int format, const cf_planes_rw* frames, int on_device, int h, int w, int pitch0, int pitch1,
+                            float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* state, int32_t* moves, int out_on_device);
+
 /* ---- best-shot selection: each track's sharpest chip, kept on the device -----------------------------------------------------
  * cf_track_update / cf_track_follow give every face an identity, cf_align_faces_frame cuts a chip of every tracked row: a track that
  * lives 200 frames yields 200 chips.  A cf_bestshot table is offered the chips of each frame, scores them, and keeps PER TRACK ID the
@@ -1283,6 +1340,16 @@ int cf_op_scene(int device, const cf_scene_opts* opts, int n_streams, int n_fram
 int cf_op_lookback(int device, const cf_lookback_opts* opts, int n_streams, int n_steps, int rows_in, const uint8_t* push,
                    const float* dets_in, const float* lms_in, const int32_t* info_in, const int32_t* counts_in, const int32_t* cuts,
                    float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* state);
+/* cf_op_lookback with a fresh cf_lookback that is enabled for tracing (cf_lookback_trace_enable with fopts, h, w): every step has a frame,
+ * frames[f * S + s] (F * S host frames of h x w in `format`, pitches as cf_redact_faces; only read; the frame of a drain is ignored),
+ * and the rows are in the space space_h x space_w (tiled = 0: network space, fx = w / space_w, fy = h / space_h; tiled = 1: frame space,
+ * (space_h, space_w) must be (h, w)), as for cf_op_follow.  Adds moves [F][S][rows][4]; rows at and past a count keep the caller's bytes.
+ * The checks of cf_op_lookback, cf_lookback_trace_enable and cf_op_follow's frame table, before any device is touched; nothing is
+ * written on refusal. */
+int cf_op_lookback_trace(int device, const cf_lookback_opts* opts, const cf_follow_opts* fopts, int n_streams, int n_steps, int rows_in,
+                         const uint8_t* push, const float* dets_in, const float* lms_in, const int32_t* info_in, const int32_t* counts_in,
+                         const int32_t* cuts, int format, const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h,
+                         int space_w, int tiled, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* state, int32_t* moves);
 /* The scoring kernel of cf_bestshot_offer alone, on host tables: chips [n][S][S][3] uint8, boxes [n][4], scores [n], lms [n][10]
  * (n in 1..65536; every row counts and is eligible) -> quality [n] int64, parts [n][4] int32 = sharp, size_w, pose_w, score_w.  fx, fy
  * finite and > 0.  Every bad argument is CF_EINVAL with a cf_op_last_error that names it, before any device is touched. */

@@ -59,6 +59,7 @@ EXPORTS = (
     "cf_track_follow", "cf_op_follow",
     "cf_scene_create", "cf_scene_destroy", "cf_scene_forget", "cf_scene_check", "cf_op_scene",
     "cf_lookback_create", "cf_lookback_destroy", "cf_lookback_forget", "cf_lookback_step", "cf_op_lookback",
+    "cf_lookback_trace_enable", "cf_lookback_step_frames", "cf_op_lookback_trace",
     "cf_bestshot_create", "cf_bestshot_destroy", "cf_bestshot_offer", "cf_bestshot_collect", "cf_op_chip_quality", "cf_op_bestshot",
 )
 
@@ -582,6 +583,11 @@ def lib():
         L.cf_lookback_forget.argtypes = [C.c_void_p, C.c_int]
         L.cf_lookback_step.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         L.cf_op_lookback.argtypes = [C.c_int, C.POINTER(LookbackOpts)] + [C.c_int] * 3 + [C.c_void_p] * 11
+        L.cf_lookback_trace_enable.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FollowOpts), C.c_int, C.c_int]
+        L.cf_lookback_step_frames.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int] + [C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + \
+            [C.c_void_p] * 6 + [C.c_int]
+        L.cf_op_lookback_trace.argtypes = [C.c_int, C.POINTER(LookbackOpts), C.POINTER(FollowOpts)] + [C.c_int] * 3 + [C.c_void_p] * 6 + \
+            [C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 7 + [C.c_void_p] * 6
         L.cf_bestshot_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(BestShotOpts), C.POINTER(C.c_void_p)]
         L.cf_bestshot_destroy.argtypes = [C.c_void_p]
         L.cf_bestshot_offer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int]

@@ -652,6 +652,61 @@ class Engine(object):
         self._chk(self._L.cf_lookback_step(self._h, lb._handle(self), int(stream0), int(B), 1 if push else 0, _lib.vp(scene_ptr), 1, _lib.vp(dets_ptr), _lib.vp(lms_ptr),
                                            _lib.vp(info_ptr), _lib.vp(counts_ptr), _lib.vp(state_ptr), 1))
 
+    def _lookback_enable(self, lb, h, w):
+        """The library object of ``lb`` -- a ``Lookback`` with ``trace()`` set -- enabled for h x w frames on its first use."""
+        handle = lb._handle(self)
+        if lb._trace is not None and lb._traced_hw is None:
+            o = _lib.follow_opts(**lb._trace)
+            self._chk(self._L.cf_lookback_trace_enable(self._h, handle, C.byref(o), int(h), int(w)))
+            lb._traced_hw = (int(h), int(w))
+        return handle
+
+    def lookback_step_frames(self, lb, frames, fmt, stream0=0, B=None, push=True, scene=None):
+        """``lookback_step`` of a ``Lookback`` with ``trace()`` set (``cf_lookback_step_frames``, host form): ``frames`` -- host frames as
+        ``track_follow`` takes them, only read -- ARE THE FRAMES THE PUSHED ROWS BELONG TO, frame b that of stream ``stream0 + b``.  Their
+        luma is retained on the device, every newborn face is matched backwards through the queued frames' luma, and the back-filled
+        boxes and landmarks of the emitted frame stand where the walk found the face (then grown as before).  The first call enables
+        the library object for the frames' (h, w); every later push must have that size.  ``push=False``: a drain; ``frames`` may be
+        None and ``B`` defaults to all streams from ``stream0`` on.  Returns (dets, lms, info, counts, state) as ``lookback_step`` plus
+        moves int32 [B,R,4] = PX, PY, SAD, code (``_lib.CF_FOLLOW_*``) of the back-filled rows, zeros for the frame's own rows."""
+        if push:
+            args, keep = _lib.host_frame_args(frames, fmt, writable=False)
+            f, tab, dev, nB, h, w, pitch0, pitch1 = args
+            B = nB if B is None else int(B)
+            if B != nB:
+                raise ValueError("%d frames for B=%d" % (nB, B))
+            handle = self._lookback_enable(lb, h, w)
+        else:
+            f, tab, dev, h, w, pitch0, pitch1, keep = 0, None, 0, 0, 0, 0, 0, None
+            B = lb.streams - int(stream0) if B is None else int(B)
+            handle = lb._handle(self)
+        n, R = max(B, 0), lb.rows
+        dets, lms, info = np.zeros((n, R, 5), np.float32), np.zeros((n, R, 10), np.float32), np.zeros((n, R, 3), np.int32)
+        counts, state, moves = np.zeros((n,), np.int32), np.zeros((n, 4), np.int32), np.zeros((n, R, 4), np.int32)
+        on_dev = scene is not None and not isinstance(scene, np.ndarray)
+        sc = C.c_void_p(int(scene)) if on_dev else _lib.ptr(None if scene is None else np.ascontiguousarray(scene, dtype=np.int32).reshape(n, 4))
+        self._chk(self._L.cf_lookback_step_frames(self._h, handle, int(stream0), B, 1 if push else 0, sc, 1 if on_dev else 0, f, tab, dev, h, w, pitch0,
+                                                  pitch1, _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(info), _lib.ptr(counts), _lib.ptr(state),
+                                                  _lib.ptr(moves), 0))
+        del keep
+        return dets, lms, info, counts, state, moves
+
+    def lookback_step_frames_device(self, lb, plane_ptrs, fmt, B, h, w, pitch0, pitch1, stream0=0, push=True, scene_ptr=None, dets_ptr=None,
+                                    lms_ptr=None, info_ptr=None, counts_ptr=None, state_ptr=None, moves_ptr=None):
+        """Same, reading DEVICE planes in place as ``track_follow_device`` takes them (``plane_ptrs`` None with ``push=False``) and the
+        scene codes from a DEVICE buffer (or None), and writing caller-owned DEVICE buffers (as ``lookback_step_device``, plus moves
+        [B,R,4] int32; any may be None): asynchronous on the engine's main stream behind the last step of ``lb``; nothing is read on
+        the host.  The context keeps the lookback rows either way."""
+        if push:
+            f, tab, dev, B, h, w, pitch0, pitch1 = _lib.device_frame_args("lookback_step_frames_device", plane_ptrs, fmt, B, h, w, pitch0, pitch1)
+            handle = self._lookback_enable(lb, h, w)
+        else:
+            f, tab, dev, h, w, pitch0, pitch1 = 0, None, 1, 0, 0, 0, 0
+            handle = lb._handle(self)
+        self._chk(self._L.cf_lookback_step_frames(self._h, handle, int(stream0), int(B), 1 if push else 0, _lib.vp(scene_ptr), 1, f, tab, dev, h, w,
+                                                  pitch0, pitch1, _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(info_ptr), _lib.vp(counts_ptr),
+                                                  _lib.vp(state_ptr), _lib.vp(moves_ptr), 1))
+
     # -- best-shot selection: each track's sharpest chip ---------------------------------------------
     def bestshot_offer(self, shots, chips, offsets, hw, stream0=0):
         """Offer ``shots`` (a ``BestShots``) the chips of this frame (``cf_bestshot_offer``, host form): ``chips`` uint8 [N, size, size, 3]
@@ -928,7 +983,8 @@ class Lookback(_StreamState):
     bit 0): those faces are not covered in that frame.  A scene cut (``scene=`` of the step, or ``forget``) is never painted across.  The
     defaults are this project's choices: there is no labelled video here, nobody has measured them, and no accuracy claim is made.
     Engines of one GPU may share an object: its steps are ordered in call order.  For the product paths (``CenterFace.anonymize(...,
-    lookback=)``) the object also keeps, per stream, the host copies of the source frames that are still in the line."""
+    lookback=)``) the object also keeps, per stream, the host copies of the source frames that are still in the line.  ``trace()``
+    opts in to back-filled boxes that follow the face through the queued frames."""
 
     _create, _destroy, _clear, _noun = "cf_lookback_create", "cf_lookback_destroy", "cf_lookback_forget", "lookback object"
 
@@ -936,7 +992,26 @@ class Lookback(_StreamState):
         self.depth, self.rows = int(depth), int(rows)
         self._frames = [[] for _ in range(max(int(streams), 0))]             # per stream: the retained source frames, oldest first
         self._codes = None                                                    # (engine, device address): the scene codes of a chunk
+        self._trace, self._traced_hw = None, None                             # ``trace()``'s options; the (h, w) the library object is enabled for
         self._open(engine_or_device, streams, _lib.lookback_opts(depth, rows, grow, confirm))
+
+    def trace(self, search=4, max_sad=4096):
+        """Opt in, before the object's first use, to back-filled boxes that FOLLOW the face through the queued frames
+        (``include/centerface_hip.h``, "lookback with a trace"): the object then keeps the luma of every queued frame on the device
+        (``depth + 1`` planes per stream: 16 streams, depth 8, 1080p: 298 MB), and a newborn face is matched backwards through them
+        with the follower's block matching -- within ``search`` cells per frame, a best match above ``max_sad`` ends the chain.
+        Pushes then go through ``Engine.lookback_step_frames``, whose first call enables the library object for its frames' size; the
+        product paths do that by themselves.  The defaults are the follower's, this project's choices; no accuracy claim is made.
+        Returns the object."""
+        if self._traced_hw is not None or any(self._frames):
+            raise ValueError("trace() comes before the %s's first use" % self._noun)
+        # refuse bad options now, not at the first step (no context: the library checks the arguments and tells)
+        self._L.cf_lookback_trace_enable(None, None, C.byref(_lib.follow_opts(search, max_sad)), 2, 2)
+        why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
+        if "null context" not in why:
+            raise _lib.CenterFaceValueError(-1, why)
+        self._trace = dict(search=int(search), max_sad=int(max_sad))
+        return self
 
     def fill(self, stream):
         """The number of source frames of ``stream`` the product paths still hold (0 .. depth)."""
@@ -972,7 +1047,8 @@ class Lookback(_StreamState):
 
     def close(self):
         self._free_codes()
-        _StreamState.close(self)
+        _StreamState.close(self)                                              # (the luma ring and the trace table are the library object's)
+        self._traced_hw = None
 
 
 class BestShots(_StreamState):
@@ -1407,7 +1483,12 @@ class CenterFace(object):
         if plan.lookback is not None:
             lb, part = plan.lookback.lookback, (plan.draw if plan.cover is None else plan.cover).array[i:j]
             lb._retain(i, part)
-            self._lookback_out(plan, i, eng.lookback_step(lb, i, len(part), push=True, scene=codes))
+            if getattr(lb, "_trace", None) is not None:                          # the chunk's frames go along: their luma is retained and traced through
+                fmt_ = (plan.draw if plan.cover is None else plan.cover).fmt
+                rows = eng.lookback_step_frames(lb, part, fmt_, i, len(part), push=True, scene=codes)[:5]
+            else:
+                rows = eng.lookback_step(lb, i, len(part), push=True, scene=codes)
+            self._lookback_out(plan, i, rows)
         else:
             self._paint(plan, lambda array: array[i:j])
         if plan.chips is not None:
@@ -1563,7 +1644,8 @@ class CenterFace(object):
         detection too -- with the first box of its track, grown by the distance, where it was first detected (not moved; the defaults
         are this project's choices, no accuracy claim is made).  Each chunk runs [scene check,] forward, decode, update[, follow], then
         ``Engine.lookback_step``; the frame that becomes due -- the object's own copy of the image of ``depth`` calls ago -- is covered
-        with the lookback rows.  The return is then, per image k of the call, the LIST of (frame, dets [n,5], lms [n,10], info [n,3] = id,
+        with the lookback rows.  A ``Lookback`` with ``trace()`` set takes the chunk's frames too (``Engine.lookback_step_frames``; even
+        sides): the back-filled boxes then follow the face through the queued frames.  The return is then, per image k of the call, the LIST of (frame, dets [n,5], lms [n,10], info [n,3] = id,
         hits, misses) that became ready: empty while stream k warms up, one item in the steady state, and with ``flush=True`` (the end of
         the video: the stream is drained) up to ``depth + 1``; dets and lms are the covered rows, in the tracker's space, back-filled ones
         with hits 0 and misses = the distance.  The streams of a call must stand at one fill level (ValueError).  With the defaults every

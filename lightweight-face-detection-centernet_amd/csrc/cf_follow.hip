@@ -19,10 +19,12 @@
 // follow_emit_kernel: a second launch, one wave per stream: step 5 of the tracker's statement (cf_trackemit.h, the very function the
 // update kernel calls) from the moved state, plus the moves in the same row order.
 // The cost of phase 1 grows with the face's area: c * c pixels per cell, c = ceil(side / 16).
+// Phases 1 to 3 are device functions in cf_followmatch.h, which the lookback's backward trace (cf_lookback.hip) calls too.
 #include <algorithm>
 #include <cmath>
 
 #include "cf_common.h"
+#include "cf_followmatch.h"
 #include "cf_kernels.h"
 #include "cf_trackemit.h"
 
@@ -31,37 +33,7 @@ namespace cf {
 namespace {
 
 constexpr int kFollowFrames = 16;                                  // frames (= streams) of one launch: their plane-0 addresses go by value
-constexpr int kWin = kFollowSide + 2 * kFollowMaxSearch;          // 32 cells
-constexpr int kWinPitch = kWin / 4 + 1;                            // dwords per window row: the byte-aligning read names one dword past the 32 cells
 struct FollowPlanes { const uint8_t* p0[kFollowFrames]; };
-
-__device__ inline int luma_bgr(int b, int g, int r) { return (29 * b + 150 * g + 77 * r + 128) >> 8; }
-
-// the luma sum of the pixels x0 .. x0 + n - 1 of a Y row (4-byte aligned), all inside the frame
-__device__ inline int run_y(const uint8_t* row, int x0, int n) {
-    unsigned s = 0;
-    int x = x0;
-    const int e = x0 + n;
-    for (; x < e && (x & 3); ++x) s += row[x];
-    for (; x + 4 <= e; x += 4) s = __builtin_amdgcn_sad_u8(*reinterpret_cast<const uint32_t*>(row + x), 0u, s);
-    for (; x < e; ++x) s += row[x];
-    return (int)s;
-}
-// the same of a BGR row: the bytes 3 * x0 .. 3 * (x0 + n) - 1, each dword that holds some of them loaded once and no other
-__device__ inline int run_bgr(const uint8_t* row, int x0, int n) {
-    const uint32_t* d = reinterpret_cast<const uint32_t*>(row);
-    int s = 0, k = 3 * x0, have = -1;
-    uint32_t wd = 0;
-    for (int i = 0; i < n; ++i) {
-        int ch[3];
-        for (int q = 0; q < 3; ++q, ++k) {
-            if ((k >> 2) != have) { have = k >> 2; wd = d[have]; }
-            ch[q] = (int)((wd >> (8 * (k & 3))) & 255u);
-        }
-        s += luma_bgr(ch[0], ch[1], ch[2]);
-    }
-    return s;
-}
 
 __global__ __launch_bounds__(256) void follow_kernel(FollowParams p, FollowPlanes fr) {
     __shared__ int s_sum[kWin * kWin];
@@ -93,34 +65,8 @@ __global__ __launch_bounds__(256) void follow_kernel(FollowParams p, FollowPlane
     // (every thread has read the state by the first barrier below; thread 0 writes it behind the last one)
     const int c = learn ? (S + kFollowSide - 1) / kFollowSide : tm[0];
     const int R = learn ? 0 : p.search, n = kFollowSide + 2 * R, X0 = CX - (kFollowSide / 2 + R) * c, Y0 = CY - (kFollowSide / 2 + R) * c;
-    for (int i = t; i < kWin * kWin; i += 256) s_sum[i] = 0;
-    for (int i = t; i < kWin * kWinPitch; i += 256) s_win[i] = 0;
-    __syncthreads();
-    // 1. the cell sums: item = (window pixel row r, cell column ci)
-    const uint8_t* p0 = fr.p0[b];
-    const bool bgr = p.g.format == CF_FRAME_BGR;
-    const int h = p.g.h, w = p.g.w, items = n * c * n;             // <= 32 * 512 * 32
-    for (int it = t; it < items; it += 256) {
-        const int r = it / n, ci = it - r * n;
-        const int y = min(max(Y0 + r, 0), h - 1), x0 = X0 + ci * c;
-        const uint8_t* row = p0 + (size_t)y * p.g.pitch0;
-        int s = 0;
-        if (x0 >= 0 && x0 + c <= w) s = bgr ? run_bgr(row, x0, c) : run_y(row, x0, c);
-        else
-            for (int i = 0; i < c; ++i) {
-                const int x = min(max(x0 + i, 0), w - 1);
-                s += bgr ? luma_bgr(row[3 * x], row[3 * x + 1], row[3 * x + 2]) : row[x];
-            }
-        atomicAdd(&s_sum[(r / c) * kWin + ci], s);
-    }
-    __syncthreads();
-    uint8_t* wb = reinterpret_cast<uint8_t*>(s_win);
-    const int cc = c * c;
-    for (int i = t; i < n * n; i += 256) {
-        const int j = i / n, ci = i - j * n;
-        wb[j * (kWinPitch * 4) + ci] = (uint8_t)((s_sum[j * kWin + ci] + cc / 2) / cc);
-    }
-    __syncthreads();
+    // 1. the cell means of the window
+    match_cell_means<true>(t, fr.p0[b], p.g.pitch0, p.g.h, p.g.w, p.g.format == CF_FRAME_BGR, X0, Y0, n, c, s_sum, s_win);
     if (learn) {
         if (t < kFollowSide * kFollowSide / 4) tpl[t] = s_win[(t >> 2) * kWinPitch + (t & 3)];
         if (t == 0) {
@@ -133,38 +79,10 @@ __global__ __launch_bounds__(256) void follow_kernel(FollowParams p, FollowPlane
     // 2. + 3. the SADs and the best of them
     if (t < kFollowSide * kFollowSide / 4) s_tpl[t] = tpl[t];
     __syncthreads();
-    const int D = 2 * R + 1;
-    unsigned long long best = ~0ull;
-    for (int cand = t; cand < D * D; cand += 256) {
-        const int oy = cand / D, ox = cand - oy * D;               // dy + R, dx + R
-        const unsigned shift = ox & 3;
-        unsigned sad = 0;
-        for (int j = 0; j < kFollowSide; ++j) {
-            const uint32_t* wr = s_win + (j + oy) * kWinPitch + (ox >> 2);
-            uint32_t lo = wr[0];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t hi = wr[q + 1];                     // (ox >> 2) + 4 <= 8: the row's ninth dword, used only with shift 0, i.e. not at all
-                sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(hi, lo, shift), s_tpl[j * 4 + q], sad);
-                lo = hi;
-            }
-        }
-        const int dx = ox - R, dy = oy - R;
-        const unsigned long long key = ((unsigned long long)sad << 32) | ((unsigned long long)(dx * dx + dy * dy) << 16) | (unsigned)(oy << 8) | (unsigned)ox;
-        best = key < best ? key : best;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned ohi = __shfl_xor((unsigned)(best >> 32), off), olo = __shfl_xor((unsigned)best, off);
-        const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
-        best = o < best ? o : best;
-    }
-    if ((t & 63) == 0) s_key[t >> 6] = best;
-    __syncthreads();
+    const unsigned long long best = match_best_key(t, R, s_win, s_tpl, s_key);
     // 4. the state and the slot's result
     if (t == 0) {
-        for (int q = 1; q < 4; ++q) best = s_key[q] < best ? s_key[q] : best;
-        const int sad = (int)(best >> 32), px = ((int)(best & 255) - R) * c, py = ((int)((best >> 8) & 255) - R) * c;
+        const int sad = match_key_sad(best), px = match_key_dx(best, R) * c, py = match_key_dy(best, R) * c;
         const bool moved = sad <= p.max_sad;
         if (moved) {
             const double mx = (double)px / p.fx, my = (double)py / p.fy;

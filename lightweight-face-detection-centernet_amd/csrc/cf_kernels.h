@@ -586,10 +586,31 @@ struct LookbackParams {
     int* info;            // [S][depth + 1][rows][4]: id, hits, misses, born
     // outputs (device), stride `rows` per image; corners may be nullptr
     float* dets; float* lms; int* out_info; float* corners; int* counts; int* state;
+    // the trace of an enabled object (cf_lookback_trace_enable), nullptr otherwise: a back-filled row of e_j is moved by trace[e_j][row][j - 1]
+    const int* trace;     // [S][depth + 1][rows][depth][4]: PX, PY, SAD, code at the distances 1 .. depth
+    double fx, fy;        // frame pixels per unit of the rows' space (FollowParams)
+    int* moves;           // output [B][rows][4], or nullptr
 };
 // nullptr, or what is wrong with the options / the number of streams (host only)
 const char* lookback_check(const cf_lookback_opts* o, int n_streams);
 hipError_t launch_lookback_step(hipStream_t s, const LookbackParams& p);
+
+// The lookback's trace (cf_lookback.hip; the statement is in include/centerface_hip.h, "a step with push"): ahead of a pushing step of an
+// enabled object, the luma of the g.B frames goes into the ring plane of the entry the push will fill (retain), and every row the push
+// will call born is matched backwards through the retained planes of the queued entries (trace).  Both read the queue's words as the
+// step before left them; the step kernel behind them advances the queue and reads the trace.
+constexpr int kLookbackLumaAlign = 16;
+__host__ __device__ inline int lookback_luma_pitch(int w) { return (w + kLookbackLumaAlign - 1) & ~(kLookbackLumaAlign - 1); }
+struct LookbackTraceParams {
+    FrameGeo g;                  // pitch0 a multiple of 4; only plane 0 (BGR rows or the Y plane) is read
+    const void* const* planes;   // HOST table of g.B x {p0, p1, p2} DEVICE addresses (cf_frame.h), p0 4-byte aligned
+    int search, max_sad;
+    double fx, fy;
+    uint8_t* luma;               // [S][depth + 1][g.h][lookback_luma_pitch(g.w)]
+    int* trace;                  // as LookbackParams::trace
+    LookbackParams step;         // the step this goes ahead of (push != 0): its options, inputs and queue words
+};
+hipError_t launch_lookback_trace(hipStream_t s, const LookbackTraceParams& p);
 
 // Best-shot selection (cf_bestshot.hip; the statement is in include/centerface_hip.h).  The table's device state, per stream and entry:
 // erec kBestRecInts int32 (state, id, best_t, first_t, last_t, n_offered, done_seq, parts[4], -, Q as int64, -, -), erow kBestRowFloats

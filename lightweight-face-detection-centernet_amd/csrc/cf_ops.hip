@@ -1171,16 +1171,32 @@ int cf_op_scene(int device, const cf_scene_opts* o, int n_streams, int n_frames,
     return sc.result("cf_op_scene");
 }
 
-// The kernel of cf_lookback_step over a sequence of host tables, with the state of a fresh cf_lookback (empty queues, max_id = seq_next = 0).
-int cf_op_lookback(int device, const cf_lookback_opts* o, int n_streams, int n_steps, int rows_in, const uint8_t* push, const float* dets_in,
-                   const float* lms_in, const int32_t* info_in, const int32_t* counts_in, const int32_t* cuts, float* dets, float* lms,
-                   int32_t* info, int32_t* counts, int32_t* state) {
+}  // extern "C"
+
+namespace {
+
+// What cf_op_lookback_trace adds to cf_op_lookback's sequence: the object is enabled, and every push has its frame
+struct OpTrace {
+    const cf_follow_opts* o; int format; const void* const* host_planes; int h, w, pitch0, pitch1, space_h, space_w, tiled;
+    int32_t* moves;
+};
+
+// The kernel of cf_lookback_step over a sequence of host tables, with the state of a fresh cf_lookback (empty queues, max_id = seq_next = 0);
+// tr: of an enabled one, the frames staged as cf_op_redact stages them, retain and trace ahead of every push.
+int op_lookback_sequence(const char* who, int device, const cf_lookback_opts* o, int n_streams, int n_steps, int rows_in, const uint8_t* push, const float* dets_in,
+                         const float* lms_in, const int32_t* info_in, const int32_t* counts_in, const int32_t* cuts, float* dets, float* lms,
+                         int32_t* info, int32_t* counts, int32_t* state, const OpTrace* tr) {
     const char* bad = lookback_check(o, n_streams);
-    if (!bad && (!push || !dets_in || !lms_in || !info_in || !counts_in || !dets || !lms || !info || !counts || !state)) bad = "null argument";
+    if (!bad && tr) bad = follow_check(tr->o, tr->format, n_streams, tr->h, tr->w, tr->pitch0, tr->pitch1);
+    if (!bad && tr && (((tr->h | tr->w) & 1) || tr->h < 2 || tr->w < 2)) bad = "h and w must be even and in [2, 8192]";
+    if (!bad && (!push || !dets_in || !lms_in || !info_in || !counts_in || !dets || !lms || !info || !counts || !state || (tr && !tr->moves))) bad = "null argument";
     if (!bad && n_steps < 1) bad = "n_steps must be at least 1";
     if (!bad && (rows_in < 1 || rows_in > o->rows)) bad = "rows_in must be in 1..rows";
     if (!bad && (long long)n_steps * n_streams * o->rows > (1 << 24)) bad = "more than 2^24 rows";
-    if (bad) return fail("cf_op_lookback", bad);
+    if (!bad && tr) bad = redact_check_planes(tr->format, tr->host_planes, n_steps * n_streams, 0, tr->pitch0, tr->pitch1);
+    if (!bad && tr && (tr->space_h < 1 || tr->space_w < 1 || (tr->tiled != 0 && tr->tiled != 1))) bad = "space_h and space_w must be at least 1, tiled 0 or 1";
+    if (!bad && tr && tr->tiled && (tr->space_h != tr->h || tr->space_w != tr->w)) bad = "rows in frame space need space_h x space_w = h x w";
+    if (bad) return fail(who, bad);
     Scope sc(device);
     const size_t S = n_streams, F = n_steps, R = o->rows, cap = (size_t)o->depth + 1, nin = F * S * rows_in, nout = F * S * R;
     std::vector<int32_t> codes(F * S * 4, 0), ones(S, 1);
@@ -1195,6 +1211,17 @@ int cf_op_lookback(int device, const cf_lookback_opts* o, int n_streams, int n_s
     p.rec = sc.make<float>(S * cap * R * 16); p.info = sc.make<int>(S * cap * R * 4);
     p.dets = sc.inout(dets, nout * 5); p.lms = sc.inout(lms, nout * 10); p.out_info = sc.inout(info, nout * 3);
     p.counts = sc.out(counts, F * S); p.state = sc.out(state, F * S * 4);
+    LookbackTraceParams q{};
+    Staged fr;
+    if (tr) {
+        q.search = tr->o->search; q.max_sad = tr->o->max_sad;
+        q.fx = tr->tiled ? 1.0 : (double)tr->w / (double)tr->space_w; q.fy = tr->tiled ? 1.0 : (double)tr->h / (double)tr->space_h;
+        q.luma = (uint8_t*)sc.alloc(S * cap * tr->h * lookback_luma_pitch(tr->w));
+        q.trace = sc.make<int>(S * cap * R * o->depth * 4);
+        p.trace = q.trace; p.fx = q.fx; p.fy = q.fy; p.moves = sc.inout(tr->moves, nout * 4);
+        fr = sc.stage(tr->format, tr->host_planes, (int)(F * S), tr->h, tr->w, tr->pitch0, tr->pitch1);      // read only: nothing to copy back
+        q.g = fr.geo(n_streams);
+    }
     const LookbackParams first = p;
     for (size_t f = 0; f < F && sc.ok(); ++f) {
         for (size_t s = 0; cuts && s < S; ++s)      // cf_lookback_forget of stream s
@@ -1205,9 +1232,34 @@ int cf_op_lookback(int device, const cf_lookback_opts* o, int n_streams, int n_s
         p.scene = cuts ? first.scene + f * S * 4 : nullptr;
         p.dets = first.dets + f * S * R * 5; p.lms = first.lms + f * S * R * 10; p.out_info = first.out_info + f * S * R * 3;
         p.counts = first.counts + f * S; p.state = first.state + f * S * 4;
+        if (tr) p.moves = first.moves + f * S * R * 4;
+        if (tr && p.push) {
+            q.planes = fr.planes(f * S); q.step = p;
+            sc.run([&] { return launch_lookback_trace(sc.s, q); });
+        }
         sc.run([&] { return launch_lookback_step(sc.s, p); });
     }
-    return sc.result("cf_op_lookback");
+    return sc.result(who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cf_op_lookback(int device, const cf_lookback_opts* o, int n_streams, int n_steps, int rows_in, const uint8_t* push, const float* dets_in,
+                   const float* lms_in, const int32_t* info_in, const int32_t* counts_in, const int32_t* cuts, float* dets, float* lms,
+                   int32_t* info, int32_t* counts, int32_t* state) {
+    return op_lookback_sequence("cf_op_lookback", device, o, n_streams, n_steps, rows_in, push, dets_in, lms_in, info_in, counts_in, cuts, dets, lms, info, counts,
+                                state, nullptr);
+}
+
+int cf_op_lookback_trace(int device, const cf_lookback_opts* o, const cf_follow_opts* fo, int n_streams, int n_steps, int rows_in, const uint8_t* push,
+                         const float* dets_in, const float* lms_in, const int32_t* info_in, const int32_t* counts_in, const int32_t* cuts, int format,
+                         const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h, int space_w, int tiled, float* dets, float* lms,
+                         int32_t* info, int32_t* counts, int32_t* state, int32_t* moves) {
+    const OpTrace tr{fo, format, reinterpret_cast<const void* const*>(frames), h, w, pitch0, pitch1, space_h, space_w, tiled, moves};
+    return op_lookback_sequence("cf_op_lookback_trace", device, o, n_streams, n_steps, rows_in, push, dets_in, lms_in, info_in, counts_in, cuts, dets, lms, info,
+                                counts, state, &tr);
 }
 
 // The score kernel of cf_bestshot_offer alone: one image whose n rows all count and are eligible (ids 1 .. n, hits 1000, misses 0).

@@ -175,7 +175,7 @@ struct cf_ctx {
     struct { DevBuf slot_moves, moves; int B = 0, H = 0, W = 0; bool tiled = false; } fo;
     // cf_lookback_step: B > 0 = the lookback rows (M per image, in the object's latched space) are the newest, until what ends a follow's
     // rows or an upload; pushed = the tracked rows in tk went into a lookback queue already
-    struct { DevBuf dets, lms, info, corners, counts, state, scene; int B = 0, M = 0, H = 0, W = 0; bool tiled = false, pushed = false; } lb;
+    struct { DevBuf dets, lms, info, corners, counts, state, scene, moves; int B = 0, M = 0, H = 0, W = 0; bool tiled = false, pushed = false; } lb;
     struct { DevBuf part, out; } sn;                                    // cf_scene_check: the workgroups' partial sums, out [B][4] of a host-output call
     struct { DevBuf q, sc, jobs, flags, chips, off, out; } bs;          // cf_bestshot_offer / cf_bestshot_collect: per-call scratch and the staging of their host forms
     // hipGraph replay of the backbone + neck launches, one executable graph per (input pointer,
@@ -2190,6 +2190,8 @@ struct cf_lookback : StreamState {
     cf_lookback_opts o{};
     int* qmeta = nullptr; int* pend = nullptr; int* emeta = nullptr; float* rec = nullptr; int* info = nullptr;
     RowSpace sp; int stride = 0;                                        // the row space and the stride of the first push
+    // cf_lookback_trace_enable: the follower's options, the frame size, the luma ring and the trace table (cf_kernels.h: LookbackTraceParams)
+    bool traced = false; cf_follow_opts fo{}; int th = 0, tw = 0; uint8_t* luma = nullptr; int* trace = nullptr;
 };
 struct cf_bestshot : StreamState {
     static constexpr const char* noun = "table";
@@ -2476,38 +2478,67 @@ int cf_lookback_create(cf_ctx* c, int n_streams, const cf_lookback_opts* o, cf_l
 
 int cf_lookback_forget(cf_lookback* t, int stream) { return state_clear(t, "cf_lookback_forget", "object", stream, t ? t->pend : nullptr, 1, 1); }
 
-// One step of the streams stream0 .. stream0 + B - 1: ordered on the object's event like a tracker's update; a push reads the context's
-// tracked rows (rows_for), and the context's lookback rows are written in any case.
-int cf_lookback_step(cf_ctx* c, cf_lookback* t, int stream0, int B, int push, const int32_t* scene, int scene_on_device, float* dets, float* lms,
-                     int32_t* info, int32_t* counts, int32_t* state, int out_on_device) {
-    const char* why = B < 1 ? "B must be at least 1" : nullptr;
+// The luma ring and the trace table of an object nothing was pushed into yet (cf_lookback.hip: retain and trace).
+int cf_lookback_trace_enable(cf_ctx* c, cf_lookback* t, const cf_follow_opts* o, int h, int w) {
+    const char* why = follow_check(o, CF_YUV_NV12, 1, 2, 2, 4, 4);           // the options alone, in the follower's words
+    if (!why && (((h | w) & 1) || h < 2 || w < 2 || h > kRedactMaxSide || w > kRedactMaxSide)) why = "h and w must be even and in [2, 8192]";
     if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
-        op_error_set((std::string("cf_lookback_step: ") + (why ? why : "null context")).c_str());
+        op_error_set((std::string("cf_lookback_trace_enable: ") + (why ? why : "null context")).c_str());
         return CF_EINVAL;
     }
-    if (why) return c->fail(CF_EINVAL, "cf_lookback_step: %s", why);
-    if (int r = state_here(c, "cf_lookback_step", t)) return r;
-    if (int r = state_range(c, "cf_lookback_step", t, stream0, B)) return r;
+    if (why) return c->fail(CF_EINVAL, "cf_lookback_trace_enable: %s", why);
+    if (int r = state_here(c, "cf_lookback_trace_enable", t)) return r;
+    if (t->traced) return c->fail(CF_ESTATE, "cf_lookback_trace_enable: the object is enabled already");
+    if (t->sp.latched) return c->fail(CF_ESTATE, "cf_lookback_trace_enable after the object's first push: an entry without luma cannot be traced through");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t entries = (size_t)t->S * (t->o.depth + 1);
+    const size_t nl = entries * h * lookback_luma_pitch(w), nt = entries * t->o.rows * t->o.depth * 4 * sizeof(int);
+    void* bufs[2] = {nullptr, nullptr};
+    hipError_t e = hipMalloc(&bufs[0], nl);
+    if (e == hipSuccess) e = hipMalloc(&bufs[1], nt);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (bufs[0]) hipFree(bufs[0]);
+        return c->fail(e == hipErrorOutOfMemory ? CF_ENOMEM : CF_EHIP, "cf_lookback_trace_enable: %zu bytes of luma and %zu of trace for %d streams x %d entries of %d x %d: %s",
+                       nl, nt, t->S, t->o.depth + 1, w, h, hipGetErrorString(e));
+    }
+    t->owned.push_back(bufs[0]); t->owned.push_back(bufs[1]);
+    t->luma = (uint8_t*)bufs[0]; t->trace = (int*)bufs[1]; t->fo = *o; t->th = h; t->tw = w; t->traced = true;
+    return CF_OK;
+}
+
+}  // extern "C"
+// The frames of cf_lookback_step_frames (fr == nullptr: cf_lookback_step)
+struct LookbackFrames { int format; const void* const* planes; int on_device, h, w, pitch0, pitch1; };
+
+// One step of the streams stream0 .. stream0 + B - 1: ordered on the object's event like a tracker's update; a push reads the context's
+// tracked rows (rows_for), and the context's lookback rows are written in any case.  On an enabled object a push has its frames: retain
+// and trace go ahead of the step kernel on the same stream, inside the same ordering bracket.
+static int lookback_step(cf_ctx* c, const char* who, cf_lookback* t, int stream0, int B, int push, const int32_t* scene, int scene_on_device,
+                         const LookbackFrames* fr, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* state, int32_t* moves, int out_on_device) {
     RowSet in{};
     const int R = t->o.rows;
     RowSpace& sp = t->sp;
     if (push) {
-        if (int r = rows_for(c, "cf_lookback_step", ROWS_UNSTEPPED, in)) return r;
-        if (in.B != B) return c->fail(CF_ESTATE, "cf_lookback_step: B=%d, the tracked rows are those of %d images", B, in.B);
-        if (!sp.matches(in)) return sp.refuse(c, "cf_lookback_step", "queued", in);
+        if (int r = rows_for(c, who, ROWS_UNSTEPPED, in)) return r;
+        if (in.B != B) return c->fail(CF_ESTATE, "%s: B=%d, the tracked rows are those of %d images", who, B, in.B);
+        if (!sp.matches(in)) return sp.refuse(c, who, "queued", in);
         if (sp.latched ? in.stride != t->stride : in.stride > R)
-            return c->fail(CF_EINVAL, "cf_lookback_step: %d tracked rows per image, the object %s %d", in.stride, sp.latched ? "was first given" : "holds at most", sp.latched ? t->stride : R);
+            return c->fail(CF_EINVAL, "%s: %d tracked rows per image, the object %s %d", who, in.stride, sp.latched ? "was first given" : "holds at most", sp.latched ? t->stride : R);
+        if (fr && in.frame_space && (in.H != fr->h || in.W != fr->w))
+            return c->fail(CF_EINVAL, "%s: %d x %d frames, the tracked rows are in frame %d x %d coordinates", who, fr->w, fr->h, in.W, in.H);
     } else if (!sp.latched) {
-        return c->fail(CF_ESTATE, "cf_lookback_step: a drain before the object's first push: its rows have no coordinate space yet");
+        return c->fail(CF_ESTATE, "%s: a drain before the object's first push: its rows have no coordinate space yet", who);
     }
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bm = (size_t)B * R, nb = (size_t)B * sizeof(int), ns = (size_t)B * 4 * sizeof(int);
-    const size_t nd = bm * 5 * sizeof(float), nl = bm * 10 * sizeof(float), ni = bm * 3 * sizeof(int);
+    const size_t nd = bm * 5 * sizeof(float), nl = bm * 10 * sizeof(float), ni = bm * 3 * sizeof(int), nm = bm * 4 * sizeof(int);
     auto& ws = c->lb;
     const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
         {ws.dets, nd, "lookback dets"}, {ws.lms, nl, "lookback landmarks"}, {ws.info, ni, "lookback info"}, {ws.corners, bm * 4 * sizeof(float), "lookback corners"},
         {ws.counts, nb, "lookback counts"}, {ws.state, ns, "lookback state"}, {ws.scene, ns, "scene codes"}};
-    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_lookback_step")) return r;
+    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, who)) return r;
+    if (t->traced) if (int r = grow(c, ws.moves, nm, "lookback moves", who)) return r;
     LookbackParams p{};
     p.depth = t->o.depth; p.rows = R; p.confirm = t->o.confirm; p.grow = t->o.grow;
     p.stream0 = stream0; p.B = B; p.push = push ? 1 : 0;
@@ -2522,16 +2553,75 @@ int cf_lookback_step(cf_ctx* c, cf_lookback* t, int stream0, int B, int push, co
     p.qmeta = t->qmeta; p.pend = t->pend; p.emeta = t->emeta; p.rec = t->rec; p.info = t->info;
     p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.out_info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
     p.counts = (int*)ws.counts.p; p.state = (int*)ws.state.p;
+    if (t->traced) {                                                      // the space is the latched one, or the one this push latches
+        const bool tiled = sp.latched ? sp.tiled : in.frame_space;
+        const int sh = sp.latched ? sp.h : in.H, sw = sp.latched ? sp.w : in.W;
+        p.trace = t->trace; p.moves = (int*)ws.moves.p;
+        p.fx = tiled ? 1.0 : (double)t->tw / (double)sw; p.fy = tiled ? 1.0 : (double)t->th / (double)sh;
+    }
     c->lb.B = 0;                                                          // (a failure below leaves no lookback rows behind)
-    HIPCHK(c, ordered(c, t, [&] { return launch_lookback_step(c->stream, p); }));
+    if (push && fr) {
+        LookbackTraceParams q{};
+        q.search = t->fo.search; q.max_sad = t->fo.max_sad; q.fx = p.fx; q.fy = p.fy; q.luma = t->luma; q.trace = t->trace; q.step = p;
+        HIPCHK(c, order_wait(c, t));
+        // host frames are only read: staged, not copied back
+        if (int r = on_frames(c, who, FrameGeo{fr->format, B, fr->h, fr->w, fr->pitch0, fr->pitch1}, fr->planes, fr->on_device, false, [&](const void* const* pl, int p0, int p1) {
+                q.g = FrameGeo{fr->format, B, fr->h, fr->w, p0, p1}; q.planes = pl;
+                return order_launch(c, t, nullptr, [&] {
+                    const hipError_t e = launch_lookback_trace(c->stream, q);
+                    return e != hipSuccess ? e : launch_lookback_step(c->stream, p);
+                });
+            })) return r;
+    } else {
+        HIPCHK(c, ordered(c, t, [&] { return launch_lookback_step(c->stream, p); }));
+    }
     if (push) { sp.latch(in); t->stride = in.stride; c->lb.pushed = true; }
     c->lb.B = B; c->lb.M = R; c->lb.H = sp.h; c->lb.W = sp.w; c->lb.tiled = sp.tiled;
     // the state words: ahead of the rows' wait on the host, behind the counts on the device
     if (state && !out_on_device) HIPCHK(c, hipMemcpyAsync(state, p.state, ns, hipMemcpyDeviceToHost, c->stream));
     if (int r = write_out(c, out_on_device, B, R, p.counts, nullptr, counts, nullptr,
-                          {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}, {info, p.out_info, 3 * sizeof(int)}})) return r;
+                          {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}, {info, p.out_info, 3 * sizeof(int)},
+                           {out_on_device || !p.moves ? nullptr : moves, p.moves, 4 * sizeof(int)}})) return r;
     if (state && out_on_device) HIPCHK(c, hipMemcpyAsync(state, p.state, ns, hipMemcpyDeviceToDevice, c->stream));
+    if (moves && p.moves && out_on_device) HIPCHK(c, hipMemcpyAsync(moves, p.moves, nm, hipMemcpyDeviceToDevice, c->stream));
     return CF_OK;
+}
+extern "C" {
+
+int cf_lookback_step(cf_ctx* c, cf_lookback* t, int stream0, int B, int push, const int32_t* scene, int scene_on_device, float* dets, float* lms,
+                     int32_t* info, int32_t* counts, int32_t* state, int out_on_device) {
+    const char* why = B < 1 ? "B must be at least 1" : nullptr;
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_lookback_step: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_lookback_step: %s", why);
+    if (int r = state_here(c, "cf_lookback_step", t)) return r;
+    if (int r = state_range(c, "cf_lookback_step", t, stream0, B)) return r;
+    if (push && t->traced) return c->fail(CF_ESTATE, "cf_lookback_step: a push into an object with cf_lookback_trace_enable needs the frame (cf_lookback_step_frames)");
+    return lookback_step(c, "cf_lookback_step", t, stream0, B, push, scene, scene_on_device, nullptr, dets, lms, info, counts, state, nullptr, out_on_device);
+}
+
+int cf_lookback_step_frames(cf_ctx* c, cf_lookback* t, int stream0, int B, int push, const int32_t* scene, int scene_on_device, int format,
+                            const cf_planes_rw* frames, int on_device, int h, int w, int pitch0, int pitch1, float* dets, float* lms, int32_t* info,
+                            int32_t* counts, int32_t* state, int32_t* moves, int out_on_device) {
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    const cf_follow_opts any{1, 0};                      // the options were checked when the object was enabled
+    const char* why = B < 1 ? "B must be at least 1" : nullptr;
+    if (!why && push) why = follow_check(&any, format, B, h, w, pitch0, pitch1);
+    if (!why && push) why = redact_check_planes(format, planes, B, on_device, pitch0, pitch1);
+    if (!c) {                                            // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_lookback_step_frames: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_lookback_step_frames: %s", why);
+    if (int r = state_here(c, "cf_lookback_step_frames", t)) return r;
+    if (int r = state_range(c, "cf_lookback_step_frames", t, stream0, B)) return r;
+    if (!t->traced) return c->fail(CF_ESTATE, "cf_lookback_step_frames on an object without cf_lookback_trace_enable");
+    if (push && (h != t->th || w != t->tw)) return c->fail(CF_EINVAL, "cf_lookback_step_frames: %d x %d frames, the object was enabled for %d x %d", w, h, t->tw, t->th);
+    const LookbackFrames fr{format, planes, on_device, h, w, pitch0, pitch1};
+    return lookback_step(c, "cf_lookback_step_frames", t, stream0, B, push, scene, scene_on_device, push ? &fr : nullptr, dets, lms, info, counts, state, moves,
+                         out_on_device);
 }
 
 // ---- best-shot selection (cf_bestshot.hip)

@@ -554,6 +554,41 @@ def lookback_sequence(dets_in, lms_in, info_in, counts_in, push=None, cuts=None,
     return od, ol, oi, oc, st
 
 
+def lookback_trace_sequence(dets_in, lms_in, info_in, counts_in, frames, fmt, space_hw, push=None, cuts=None, *, tiled=False, search=4,
+                            max_sad=4096, dets=None, lms_out=None, info=None, moves=None, device=0, **opts):
+    """``lookback_sequence`` with a fresh ``Lookback`` that has ``trace(search, max_sad)`` set (``cf_op_lookback_trace``): step f of stream
+    s has the frame ``frames[f * S + s]`` -- F * S host frames of one even size as ``follow_sequence`` takes them, only read; the frame of a
+    drain is ignored --, whose luma is retained and through which the newborn faces are matched backwards.  ``space_hw``: the (H, W) the
+    rows are in, mapped to the frame by w / W, h / H; ``tiled=True``: the rows are in frame pixels (``space_hw`` is the frame's size).
+    Returns ``lookback_sequence``'s tuple plus moves [F, S, rows, 4] = PX, PY, SAD, code (``_lib.CF_FOLLOW_*``) of the back-filled rows
+    (zeros for own rows); rows at and past a count keep the bytes of the arrays passed in (zeros by default)."""
+    o, fo = _lib.lookback_opts(**opts), _lib.follow_opts(search, max_sad)
+    d = np.ascontiguousarray(dets_in, dtype=np.float32)
+    if d.ndim != 4 or d.shape[3] != 5:
+        raise ValueError("dets_in must be [F, S, rows_in, 5], got %s" % (d.shape,))
+    F, S, rows_in, _ = d.shape
+    lm = np.ascontiguousarray(lms_in, dtype=np.float32).reshape(F, S, rows_in, 10)
+    ii = np.ascontiguousarray(info_in, dtype=np.int32).reshape(F, S, rows_in, 3)
+    cn = np.ascontiguousarray(counts_in, dtype=np.int32).reshape(F, S)
+    pu = np.ones((F,), np.uint8) if push is None else np.ascontiguousarray(np.asarray(push) != 0, dtype=np.uint8).reshape(F)
+    cu = None if cuts is None else np.ascontiguousarray(cuts, dtype=np.int32).reshape(F, S)
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    if B != F * S:
+        raise ValueError("%d frames for F x S = %d x %d" % (B, F, S))
+    H, W = int(space_hw[0]), int(space_hw[1])
+    R = max(int(o.rows), 1)
+    od = np.zeros((F, S, R, 5), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(F, S, R, 5)
+    ol = np.zeros((F, S, R, 10), np.float32) if lms_out is None else np.ascontiguousarray(lms_out, dtype=np.float32).reshape(F, S, R, 10)
+    oi = np.zeros((F, S, R, 3), np.int32) if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(F, S, R, 3)
+    om = np.zeros((F, S, R, 4), np.int32) if moves is None else np.ascontiguousarray(moves, dtype=np.int32).reshape(F, S, R, 4)
+    oc, st = np.zeros((F, S), np.int32), np.zeros((F, S, 4), np.int32)
+    _lib.check(_lib.lib().cf_op_lookback_trace(device, C.byref(o), C.byref(fo), S, F, rows_in, ptr(pu), ptr(d), ptr(lm), ptr(ii), ptr(cn), ptr(cu),
+                                               _lib.frame_format(fmt), tab, h, w, pitch0, pitch1, H, W, 1 if tiled else 0, ptr(od), ptr(ol), ptr(oi),
+                                               ptr(oc), ptr(st), ptr(om)), op=True)
+    del keep
+    return od, ol, oi, oc, st, om
+
+
 def scene_signature(frame, fmt, device=0):
     """The 128 int32 of one frame's signature (``include/centerface_hip.h``: 64 luma bins, 8 x 8 cell means), computed on the device:
     ``frame`` is one BGR uint8 [h,w,3], one dense 4:2:0 uint8 [h*3//2, w], or one plane tuple."""

@@ -575,6 +575,42 @@ int cf_track_reset(cf_tracker* trk, int stream);
 int cf_track_update(cf_ctx* ctx, cf_tracker* trk, int stream0, float* dets, float* lms, int32_t* info,
                     int32_t* counts, int32_t* flags, int out_on_device);
 
+/* ---- two thresholds: a second association pass for low-score rows ----------------------------
+ * A held box is stale: the face that scored 0.29 instead of 0.31 was seen by the detector, box and landmarks at the right place, and the
+ * row was thrown away before the tracker could look at it.  A tracker created with two more numbers takes the rows of a decode at a
+ * LOWER score threshold, lets the low-score rows match tracks that already exist, and lets them do nothing else (the association of
+ * ByteTrack and its descendants; the defaults the Python layer uses are its customary values, nobody has measured them here and no
+ * accuracy claim is made):
+ *   birth_score: float32, finite, in (0, 1];   weak_iou: float32, finite, in (0, 1].
+ * A row is STRONG when score > birth_score -- strict and in float32, because the threshold decodes keep cells with hm > score_thresh:
+ * the strong rows of a decode at a lower threshold are then exactly the rows of a decode at birth_score (the NMS is greedy in descending
+ * score order and keeps that order, cf_unfit_rows is a filter, cf_merge_tiles removes duplicates greedily by score; this holds as long
+ * as no stage is cut by its max_out or its candidate limit).  Every other row is WEAK, a NaN score and score == birth_score included.
+ * One update of a stream becomes:
+ *   1.  Unchanged: a row with a non-finite corner is skipped, strong or weak.
+ *   2a. Strong pass.  Step 2 above over the strong rows only, in row order.  A strong row without a winner >= iou_thresh is NEW.
+ *   2b. Weak pass, after the strong pass has seen every strong row, over the weak rows in row order.  Eligible are the slots that were
+ *       alive when the update began, are not yet matched in this update by either pass, and had hits >= min_hits when the update began:
+ *       confirmed tracks, live or held; a tentative track is never matched by a weak row.  The measure, the arg-max, the tie rule (lowest
+ *       slot) and the NaN rule are step 2's.  A winner with iou >= weak_iou takes the row's box, score and landmarks as they are, hits =
+ *       min(hits + 1, 1 << 30), misses = 0 -- exactly what a strong match does.  Otherwise the row is DISCARDED: it is not new, it is
+ *       never born, and it never sets flag bit 0.
+ *   3 to 5. Unchanged, so a weak match stops the ageing and the row comes out ungrown, bit for bit.  Bit 1 (value 2) of flags[s] is set
+ *       for a stream in whose update at least one weak row matched; bit 0 keeps its meaning.
+ * A tracker created without the two numbers does what it did before, bit for bit.  What follows for the other objects:
+ *   * cf_track_follow LEARNS a new template behind a weak match, because the box changed.
+ *   * The lookback back-fills only strong births, because weak rows are never born.
+ *   * The best-shot offer sees a weak-matched row as any live row (misses == 0); its score term already weighs it down.
+ * The library never sees the threshold the caller decodes at; cf_track_update, cf_track_follow, cf_track_reset, the scene check and the
+ * lookback take such a tracker unchanged. */
+typedef struct cf_track_weak_opts {
+    float birth_score;    /* finite, in (0, 1]: a row is strong when score > birth_score */
+    float weak_iou;       /* finite, in (0, 1]: the match threshold of the weak pass */
+} cf_track_weak_opts;
+/* cf_track_create with the two numbers; weak == NULL is cf_track_create.  CF_EINVAL for a bad value before any GPU work, the cause in
+ * cf_last_error (ctx == NULL: the arguments are still checked first, cf_op_last_error names the cause). */
+int cf_track_create_weak(cf_ctx* ctx, int n_streams, const cf_track_opts* opts, const cf_track_weak_opts* weak, cf_tracker** out);
+
 /* ---- follow tracked faces between detections: block matching in the frame, on the device -----
  * cf_track_update leaves two holes: a held track does not move (hold_grow only inflates its box blindly, and its landmarks stay where
  * the face was), and every frame needs a forward, because the tracker advances only behind a decode.  cf_track_follow measures, from
@@ -1310,6 +1346,11 @@ int cf_op_flip_heads(int device, const float* records_2B, int B, int h, int w, f
 int cf_op_track(int device, const cf_track_opts* opts, int n_streams, int n_frames, int rows, const float* boxes,
                 const float* scores, const float* lms_in, const int32_t* counts_in,
                 float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags);
+/* cf_op_track with the tracker of cf_track_create_weak: the same tables, limits and checks, plus the option checks of
+ * cf_track_create_weak, before any device is touched.  flags [F][S] carry bit 1 where a weak row matched.  weak == NULL is cf_op_track. */
+int cf_op_track_weak(int device, const cf_track_opts* opts, const cf_track_weak_opts* weak, int n_streams, int n_frames, int rows,
+                     const float* boxes, const float* scores, const float* lms_in, const int32_t* counts_in,
+                     float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags);
 /* The kernels of cf_track_update and cf_track_follow over a whole sequence, on host tables and host frames, with a fresh tracker of
  * n_streams streams whose row space is space_h x space_w (tiled = 0: network space, fx = w / space_w, fy = h / space_h; tiled = 1:
  * frame space, (space_h, space_w) must be (h, w)).  Frame f of stream s: where detect[f] is not 0 the update with the rows

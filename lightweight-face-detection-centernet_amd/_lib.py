@@ -56,6 +56,7 @@ EXPORTS = (
     "cf_fit_geometry", "cf_forward_fit", "cf_unfit_rows", "cf_op_fit", "cf_op_unfit",
     "cf_set_flip_test", "cf_op_mirror", "cf_op_flip_heads",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
+    "cf_track_create_weak", "cf_op_track_weak",
     "cf_track_follow", "cf_op_follow",
     "cf_scene_create", "cf_scene_destroy", "cf_scene_forget", "cf_scene_check", "cf_op_scene",
     "cf_lookback_create", "cf_lookback_destroy", "cf_lookback_forget", "cf_lookback_step", "cf_op_lookback",
@@ -251,6 +252,17 @@ def track_opts(iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0):
 
 
 CF_FOLLOW_NONE, CF_FOLLOW_LEARNED, CF_FOLLOW_MOVED, CF_FOLLOW_LOST = 0, 1, 2, 3
+
+
+class TrackWeakOpts(C.Structure):
+    """cf_track_weak_opts: a row is strong when score > birth_score / the match threshold of the weak pass."""
+    _fields_ = [("birth_score", C.c_float), ("weak_iou", C.c_float)]
+
+
+def track_weak_opts(birth_score=0.3, weak_iou=0.5):
+    """TrackWeakOpts (the library validates the numbers).  0.5 is ByteTrack's customary value and this project's choice: nobody has
+    measured it here, and no accuracy claim is made."""
+    return TrackWeakOpts(float(birth_score), float(weak_iou))
 
 
 class FollowOpts(C.Structure):
@@ -569,6 +581,8 @@ def lib():
         L.cf_track_reset.argtypes = [C.c_void_p, C.c_int]
         L.cf_track_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         L.cf_op_track.argtypes = [C.c_int, C.POINTER(TrackOpts)] + [C.c_int] * 3 + [C.c_void_p] * 9
+        L.cf_track_create_weak.argtypes = [C.c_void_p, C.c_int, C.POINTER(TrackOpts), C.POINTER(TrackWeakOpts), C.POINTER(C.c_void_p)]
+        L.cf_op_track_weak.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(TrackWeakOpts)] + [C.c_int] * 3 + [C.c_void_p] * 9
         L.cf_track_follow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(FollowOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + \
             [C.c_void_p] * 5 + [C.c_int]
         L.cf_op_follow.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(FollowOpts)] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.POINTER(PlanesRW)] + \

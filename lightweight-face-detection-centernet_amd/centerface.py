@@ -902,10 +902,14 @@ class _StreamState(object):
             self.device = int(engine_or_device)
             # refuse bad options now, not at the first call (no context: the library checks the arguments and tells)
             out = C.c_void_p()
-            getattr(self._L, self._create)(None, self.streams, C.byref(self._o), C.byref(out))
+            self._make(None, out)
             why = (self._L.cf_op_last_error() or b"").decode(errors="replace")
             if "null context" not in why:
                 raise _lib.CenterFaceValueError(-1, why)
+
+    def _make(self, ctx, out):
+        """The library's create call with the context handle ``ctx`` (None: only the arguments are checked); returns its code."""
+        return getattr(self._L, self._create)(ctx, self.streams, C.byref(self._o), C.byref(out))
 
     def _handle(self, engine):
         """The library's object, created with ``engine``'s context on first use."""
@@ -913,7 +917,7 @@ class _StreamState(object):
             if engine.device != self.device:
                 raise ValueError("the %s was made for device %d, the engine runs on device %d" % (self._noun, self.device, engine.device))
             out = C.c_void_p()
-            _lib.check(getattr(self._L, self._create)(engine._h, self.streams, C.byref(self._o), C.byref(out)), engine._h)
+            _lib.check(self._make(engine._h, out), engine._h)
             self._h = out
         return self._h
 
@@ -942,13 +946,35 @@ class Tracker(_StreamState):
     seen ``min_hits`` times running is held for up to ``max_age`` frames without a detection, its box growing by ``hold_grow`` of its
     size per missed frame.  A frame with more faces and held tracks than ``max_tracks`` DROPS the surplus new faces (flag bit 0): they are
     not covered.  The defaults are this project's choices; no accuracy claim is made for them.  Engines of one GPU may share a tracker:
-    its updates are ordered in call order."""
+    its updates are ordered in call order.
+
+    ``weak_score`` (default None: the tracker above): two thresholds, ``0 < weak_score < birth_score <= 1``.  ``weak_score`` is the
+    score threshold the caller -- or the product paths of ``CenterFace``, which read it from here -- DECODES at; the library never sees
+    it.  Rows with ``score > birth_score`` associate, are born and are returned as before; the rows between the two thresholds may
+    only match a track that was already confirmed (``min_hits``), at IoU >= ``weak_iou``, and are otherwise discarded: the frame in
+    which a face scores 0.29 keeps its track alive with the box and the landmarks of THAT frame instead of a held, stale box (flag
+    bit 1 of the update says that it happened).  0.1 and 0.5 are ByteTrack's customary values and this project's choice: nobody has
+    measured them here, and no accuracy claim is made."""
 
     _create, _destroy, _clear, _noun = "cf_track_create", "cf_track_destroy", "cf_track_reset", "tracker"
 
-    def __init__(self, engine_or_device, streams, iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0):
+    def __init__(self, engine_or_device, streams, iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0, weak_score=None, birth_score=0.3,
+                 weak_iou=0.5):
         self.max_tracks = int(max_tracks)
+        self.weak_score, self.birth_score, self._wo = None, None, None
+        if weak_score is not None:
+            weak_score, birth_score, weak_iou = float(weak_score), float(birth_score), float(weak_iou)
+            if not 0.0 < weak_score < birth_score <= 1.0:                         # (a NaN fails every comparison)
+                raise ValueError("a weak tracker needs 0 < weak_score < birth_score <= 1, got weak_score=%r, birth_score=%r" % (weak_score, birth_score))
+            if not 0.0 < weak_iou <= 1.0:
+                raise ValueError("weak_iou must be in (0, 1], got %r" % (weak_iou,))
+            self.weak_score, self.birth_score, self._wo = weak_score, birth_score, _lib.track_weak_opts(birth_score, weak_iou)
         self._open(engine_or_device, streams, _lib.track_opts(iou, max_age, min_hits, max_tracks, hold_grow))
+
+    def _make(self, ctx, out):
+        if self._wo is None:
+            return _StreamState._make(self, ctx, out)
+        return self._L.cf_track_create_weak(ctx, self.streams, C.byref(self._o), C.byref(self._wo), C.byref(out))
 
     def reset(self, stream=-1):
         """A scene cut: drop every track of ``stream`` (-1: of all streams).  ids are not reused."""
@@ -1317,9 +1343,9 @@ class CenterFace(object):
         identity = batch[0].shape[:2] == (self.img_h_new, self.img_w_new)
         return batch, eng.forward_images_enqueue if direct else eng.forward_enqueue if identity else eng.forward_resized_enqueue
 
-    def _decode(self, eng):
+    def _decode(self, eng, score=0.3):
         """The results of the forward last enqueued on ``eng``; the rescale (centerface.py:55-62) was done by the decode kernel."""
-        return self._postprocess_many(eng.decode_threshold(0.3, self.nms_thresh, self.max_dets), rescaled=True)
+        return self._postprocess_many(eng.decode_threshold(score, self.nms_thresh, self.max_dets), rescaled=True)
 
     def _follow(self, follow, detect, tracker, frames, fmt):
         """The ``follow`` / ``detect`` arguments of the product paths -> the ``follow`` of a plan: None, or (array, fmt, options of
@@ -1453,17 +1479,30 @@ class CenterFace(object):
     def _detect_chunk(self, plan, i):
         """The detection of the chunk at frame i: forward, decode, the rows to frame space, the tracker's update; the per-frame results."""
         eng = self.engine
+        # a tracker with two thresholds: the decode keeps the rows above its weak_score for the update, and the results are the rows
+        # above its birth_score -- those a decode at birth_score keeps, in the same order (include/centerface_hip.h, "two thresholds")
+        weak = getattr(plan.tracker, "weak_score", None)
+        score = 0.3 if weak is None else weak
         with self._rescaled(plan, not plan.detect):
             plan.forward(plan.frames[i:i + plan.per])
             if plan.rows == _RESCALE:
-                res = self._decode(eng)
+                res = self._decode(eng, score)
             else:
-                eng.decode_threshold(0.3, self.nms_thresh, self.max_dets)
+                eng.decode_threshold(score, self.nms_thresh, self.max_dets)
                 rows = eng.unfit_rows(self.max_dets) if plan.rows == _UNFIT else eng.merge_tiles(*plan.merge, self.max_dets)
                 res = self._postprocess_many(rows[0], rescaled=True)
             if plan.tracker is not None:
                 eng.track_update_device(plan.tracker, i)
-        return res
+        return res if weak is None else self._strong(res, plan.tracker.birth_score)
+
+    def _strong(self, res, birth_score):
+        """The per-frame results with only the rows whose score is above ``birth_score`` (float32, strict: the decode's own compare)."""
+        out = []
+        for r in res:
+            d, l = r if self.landmarks else (r, None)
+            keep = d[:, 4] > np.float32(birth_score)
+            out.append((d[keep], l[keep]) if self.landmarks else d[keep])
+        return out
 
     def _chunk_steps(self, plan, i, res, codes):
         """The steps behind the detection of the chunk at frame i, while the engine still holds its rows: the follow (without ``detect``
@@ -1626,7 +1665,9 @@ class CenterFace(object):
         any even size, redaction with the merged boxes; the detections are then in frame pixels.  ``tracker``: a ``Tracker`` (default none: every
         call stands alone) whose stream k the k-th image of this call continues -- a video is fed one call per frame, n cameras n images per
         call; it is advanced between the decode (the merge) and the redaction, which then covers the detections of this frame AND the
-        tracks held through a dropout.  The detections returned stay the frame's own.  ``follow`` (needs ``tracker``): True, or a dict with
+        tracks held through a dropout.  The detections returned stay the frame's own.  A tracker with two thresholds
+        (``Tracker(weak_score=)``): every product path decodes at its ``weak_score`` instead of 0.3, so that the rows between the
+        thresholds reach the update, and returns the rows above its ``birth_score``.  ``follow`` (needs ``tracker``): True, or a dict with
         ``search`` and / or ``max_sad`` (``Engine.track_follow``; the defaults 4 and 4096 are this project's choices, no accuracy claim is
         made): right behind the update the tracker's faces are followed in the frame by block matching, so a track held through a dropout
         moves with its face instead of staying where it was last detected.  ``detect=False`` (needs ``tracker``, which a call with

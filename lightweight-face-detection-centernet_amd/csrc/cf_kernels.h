@@ -509,6 +509,9 @@ constexpr int kTrackMaxSlots = 1024, kTrackMaxStreams = 4096;
 struct TrackParams {
     const float* boxes; const float* scores; int score_stride; const float* lms; const int* counts; int rows, B;
     float iou_thresh; int max_age, min_hits, max_tracks; float hold_grow;
+    // two thresholds (cf_track_create_weak): weak != 0 runs the second pass for the rows with !(score > birth_score)
+    int weak; float birth_score, weak_iou;
+    void set_weak(const cf_track_weak_opts* w) { weak = w ? 1 : 0; birth_score = w ? w->birth_score : 0.f; weak_iou = w ? w->weak_iou : 0.f; }
     // state (device), owned by the tracker: n_streams x max_tracks slots
     int stream0;
     int* meta;            // [S][max_tracks][4]: alive, id, hits, misses
@@ -520,10 +523,11 @@ struct TrackParams {
     int* info;            // [B][max_tracks][3]: id, hits, misses
     float* corners;       // [B][max_tracks][4]: the box rows FaceList::boxes takes, as MergeParams::corners
     int* out_counts;      // [B], <= max_tracks
-    int* flags;           // [B]: bit 0 = a new row found no free slot and was dropped
+    int* flags;           // [B]: bit 0 = a new row found no free slot and was dropped; bit 1 = a weak row matched
 };
-// nullptr, or what is wrong with the options / the number of streams (host only)
+// nullptr, or what is wrong with the options / the number of streams (host only); the weak options may be null (a plain tracker)
 const char* track_check(const cf_track_opts* o, int n_streams);
+const char* track_weak_check(const cf_track_weak_opts* w);
 hipError_t launch_track_update(hipStream_t s, const TrackParams& p);
 
 // The follower (cf_follow.hip; the statement is in include/centerface_hip.h): block matching of every alive slot of the streams

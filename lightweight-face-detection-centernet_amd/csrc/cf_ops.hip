@@ -1070,8 +1070,10 @@ struct OpFollow {
 // The update of cf_track_update, frame after frame, with the state of a fresh tracker (no slot alive, next_id = 1); fw: each frame is then
 // followed in its host frames, staged as cf_op_redact stages them.
 int op_track_sequence(const char* who, int device, const cf_track_opts* o, int n_streams, int n_frames, int rows, const float* boxes, const float* scores,
-                      const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, const OpFollow* fw) {
+                      const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, const OpFollow* fw,
+                      const cf_track_weak_opts* wo = nullptr) {
     const char* bad = track_check(o, n_streams);
+    if (!bad) bad = track_weak_check(wo);
     if (!bad && fw) bad = follow_check(fw->o, fw->format, n_streams, fw->h, fw->w, fw->pitch0, fw->pitch1);
     if (!bad && (!boxes || !scores || !lms_in || !counts_in || !dets || !lms || !info || !counts || !flags || (fw && (!fw->detect || !fw->moves)))) bad = "null argument";
     if (!bad && (n_frames < 1 || rows < 1)) bad = "n_frames and rows must be at least 1";
@@ -1091,6 +1093,7 @@ int op_track_sequence(const char* who, int device, const cf_track_opts* o, int n
     p.counts = sc.in(counts_in, F * S);
     p.rows = rows; p.B = n_streams; p.stream0 = 0;
     p.iou_thresh = o->iou_thresh; p.max_age = o->max_age; p.min_hits = o->min_hits; p.max_tracks = o->max_tracks; p.hold_grow = o->hold_grow;
+    p.set_weak(wo);
     p.meta = sc.make<int>(S * M * 4); p.rec = sc.make<float>(S * M * 16);
     const std::vector<int> ones(S, 1);
     p.next_id = sc.upv(ones);
@@ -1132,6 +1135,12 @@ extern "C" {
 int cf_op_track(int device, const cf_track_opts* o, int n_streams, int n_frames, int rows, const float* boxes, const float* scores,
                 const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags) {
     return op_track_sequence("cf_op_track", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, nullptr);
+}
+
+int cf_op_track_weak(int device, const cf_track_opts* o, const cf_track_weak_opts* weak, int n_streams, int n_frames, int rows, const float* boxes,
+                     const float* scores, const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags) {
+    if (!weak) return cf_op_track(device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags);
+    return op_track_sequence("cf_op_track_weak", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, nullptr, weak);
 }
 
 int cf_op_follow(int device, const cf_track_opts* o, const cf_follow_opts* fo, int n_streams, int n_frames, int rows, const float* boxes,

@@ -22,6 +22,19 @@
 //      float64, cx = ((double)x1 + (double)x2) * 0.5, hw = ((double)x2 - (double)x1) * 0.5 * (1.0 + (double)hold_grow * (double)misses),
 //      x1' = (float)(cx - hw), x2' = (float)(cx + hw), y likewise; its landmarks are the last ones seen.
 //
+// TWO THRESHOLDS (cf_track_create_weak / cf_op_track_weak; tests/weak_cases.py restates it).  A tracker created with birth_score and
+// weak_iou, both float32, finite, in (0, 1], calls a row STRONG when score > birth_score (strict, float32: the threshold decodes keep
+// hm > score_thresh, so the strong rows of a decode at a lower threshold are the rows of a decode at birth_score) and WEAK otherwise -- a
+// NaN score and score == birth_score are weak.  Step 1 holds for both kinds.  Step 2 becomes
+//   2a. Strong pass: step 2 over the strong rows only, in row order; a strong row without a winner >= iou_thresh is NEW.
+//   2b. Weak pass, after every strong row: over the weak rows in row order, among the slots that were alive when the update began, are
+//       matched by neither pass so far, and had hits >= min_hits when the update began (confirmed tracks, live or held; a tentative
+//       track is never matched by a weak row).  Measure, arg-max, tie rule and NaN rule are step 2's.  A winner with iou >= weak_iou takes
+//       the row exactly as a strong match does (box, score, landmarks as they are, hits = min(hits + 1, 1 << 30), misses = 0).  Otherwise
+//       the row is DISCARDED: not new, never born, never the cause of flag bit 0.
+// Steps 3 to 5 are unchanged, so a weak match stops the ageing and its row comes out ungrown.  Bit 1 (value 2) of flags[s] is set when at
+// least one weak row matched in this update of stream s.  Without the two numbers the update is the one above, bit for bit.
+//
 // THE KERNEL
 // One launch per update, one workgroup of ONE wave per stream.  The loop over the rows is sequential by definition; per row only an
 // arg-max over the slots is needed.  Lane l owns the slots j * 64 + l (j < ceil(max_tracks / 64) <= 16): it keeps their start-of-update
@@ -29,6 +42,9 @@
 // xor butterfly over (measure, slot) leaves the winner in every lane.  No workgroup barrier in the loop.  The owner of the winning slot
 // writes the slot.  Free-slot ranks (birth) and alive-slot ranks (compaction) are prefix sums: one ballot per 64 slots plus a running
 // base, in slot order because slot = j * 64 + lane.  The state lives in device memory the tracker owns; nothing is read on the host.
+// A weak tracker is the same launch with the row loop run twice (a template parameter: the plain instance has no second loop, reads no
+// score in the loop and knows no fourth flag bit); the prologue that reads `alive` also reads `hits` once for the "confirmed at the
+// start" bit of the lane-owned flag word.
 #include <climits>
 #include <cmath>
 
@@ -40,8 +56,51 @@ namespace cf {
 
 namespace {
 
-constexpr int F_START = 1, F_MATCHED = 2, F_ALIVE = 4;      // s_flag: alive when the update began | matched in this update | alive after it
+// s_flag: alive when the update began | matched in this update | alive after it | (weak trackers) hits >= min_hits when it began
+constexpr int F_START = 1, F_MATCHED = 2, F_ALIVE = 4, F_CONF = 8;
 
+// The winner of row box d among the slots whose flag word, under MASK, equals WANT: each lane over its own slots in ascending order,
+// then the butterfly; every lane of the wave calls it and every lane returns the same (bv, bk), bk == INT_MAX without a winner.
+template <int MASK, int WANT>
+__device__ __forceinline__ void track_best(const float4 d, int lane, int M, int per, const int* s_flag, const float4* s_box, float& bv, int& bk) {
+    const float ad = (d.z - d.x + 1.0f) * (d.w - d.y + 1.0f);
+    bv = -INFINITY;
+    bk = INT_MAX;
+    for (int j = 0; j < per; ++j) {
+        const int k = j * 64 + lane;
+        if (k >= M || (s_flag[k] & MASK) != WANT) continue;
+        const float4 t = s_box[k];
+        const float at = (t.z - t.x + 1.0f) * (t.w - t.y + 1.0f);
+        const float w = fmaxf(0.0f, fminf(t.z, d.z) - fmaxf(t.x, d.x) + 1.0f), h = fmaxf(0.0f, fminf(t.w, d.w) - fmaxf(t.y, d.y) + 1.0f);
+        const float inter = w * h;
+        const float v = inter / (at + ad - inter);
+        if (v > bv) { bv = v; bk = k; }            // ascending k: the lowest slot among equals; a NaN never passes
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int ok = __shfl_xor(bk, off);
+        if (ov > bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
+    }
+}
+
+// The owner of the winning slot bk takes row i: the slot's flag word, its record and its counters (no other lane touches them).
+__device__ __forceinline__ void track_take(const TrackParams& p, int lane, int bk, int i, const float4 d, const float* scores, const float* lms, int* s_flag,
+                                           int* meta, float* rec) {
+    if ((bk & 63) != lane) return;
+    s_flag[bk] = F_START | F_MATCHED;
+    float* r = rec + (size_t)bk * 16;
+    r[0] = d.x; r[1] = d.y; r[2] = d.z; r[3] = d.w; r[4] = scores[(size_t)i * p.score_stride];
+    for (int q = 0; q < 10; ++q) r[5 + q] = lms[(size_t)i * 10 + q];
+    const int hits = meta[bk * 4 + 2];
+    meta[bk * 4 + 2] = hits < (1 << 30) ? hits + 1 : (1 << 30);
+    meta[bk * 4 + 3] = 0;
+}
+
+// WEAK = false is the plain tracker: one pass over every row, no score read in the loop, no F_CONF bit anywhere.  WEAK = true splits the
+// rows by score > birth_score (a wave-uniform test: every lane reads the same score) and walks them twice.  A lane reads and writes only
+// the flag words of its own slots in both passes, so the second pass needs no barrier either.
+template <bool WEAK>
 __global__ __launch_bounds__(64) void track_update_kernel(TrackParams p) {
     __shared__ float4 s_box[kTrackMaxSlots];      // start-of-update boxes (lane-owned words)
     __shared__ int s_flag[kTrackMaxSlots];
@@ -54,7 +113,9 @@ __global__ __launch_bounds__(64) void track_update_kernel(TrackParams p) {
         const int k = j * 64 + lane;
         if (k >= M) continue;
         const int alive = meta[k * 4];
-        s_flag[k] = alive ? F_START : 0;
+        int f = alive ? F_START : 0;
+        if constexpr (WEAK) { if (alive && meta[k * 4 + 2] >= p.min_hits) f |= F_CONF; }
+        s_flag[k] = f;
         if (alive) s_box[k] = *reinterpret_cast<const float4*>(rec + (size_t)k * 16);
     }
     const int cnt = p.counts[b];
@@ -62,42 +123,31 @@ __global__ __launch_bounds__(64) void track_update_kernel(TrackParams p) {
     const float* boxes = p.boxes + (size_t)b * p.rows * 4;
     const float* scores = p.scores + (size_t)b * p.rows * p.score_stride;
     const float* lms = p.lms + (size_t)b * p.rows * 10;
-    int n_new = 0;
+    int n_new = 0, n_weak = 0;
+    float bv;
+    int bk;
     for (int i = 0; i < n; ++i) {
         const float4 d = *reinterpret_cast<const float4*>(boxes + (size_t)i * 4);
         if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.z) && isfinite(d.w))) continue;
-        const float ad = (d.z - d.x + 1.0f) * (d.w - d.y + 1.0f);
-        float bv = -INFINITY;
-        int bk = INT_MAX;
-        for (int j = 0; j < per; ++j) {
-            const int k = j * 64 + lane;
-            if (k >= M || s_flag[k] != F_START) continue;
-            const float4 t = s_box[k];
-            const float at = (t.z - t.x + 1.0f) * (t.w - t.y + 1.0f);
-            const float w = fmaxf(0.0f, fminf(t.z, d.z) - fmaxf(t.x, d.x) + 1.0f), h = fmaxf(0.0f, fminf(t.w, d.w) - fmaxf(t.y, d.y) + 1.0f);
-            const float inter = w * h;
-            const float v = inter / (at + ad - inter);
-            if (v > bv) { bv = v; bk = k; }            // ascending k: the lowest slot among equals; a NaN never passes
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(bv, off);
-            const int ok = __shfl_xor(bk, off);
-            if (ov > bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
-        }
+        if constexpr (WEAK) { if (!(scores[(size_t)i * p.score_stride] > p.birth_score)) continue; }      // weak (a NaN too): the second pass
+        track_best<WEAK ? ~F_CONF : ~0, F_START>(d, lane, M, per, s_flag, s_box, bv, bk);      // alive at the start, not yet matched
         if (bk != INT_MAX && bv >= p.iou_thresh) {
-            if ((bk & 63) == lane) {
-                s_flag[bk] = F_START | F_MATCHED;
-                float* r = rec + (size_t)bk * 16;
-                r[0] = d.x; r[1] = d.y; r[2] = d.z; r[3] = d.w; r[4] = scores[(size_t)i * p.score_stride];
-                for (int q = 0; q < 10; ++q) r[5 + q] = lms[(size_t)i * 10 + q];
-                const int hits = meta[bk * 4 + 2];
-                meta[bk * 4 + 2] = hits < (1 << 30) ? hits + 1 : (1 << 30);
-                meta[bk * 4 + 3] = 0;
-            }
+            track_take(p, lane, bk, i, d, scores, lms, s_flag, meta, rec);
         } else {
             if (lane == 0 && n_new < M) s_new[n_new] = i;
             ++n_new;
+        }
+    }
+    if constexpr (WEAK) {
+        for (int i = 0; i < n; ++i) {
+            const float4 d = *reinterpret_cast<const float4*>(boxes + (size_t)i * 4);
+            if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.z) && isfinite(d.w))) continue;
+            if (scores[(size_t)i * p.score_stride] > p.birth_score) continue;
+            track_best<~0, F_START | F_CONF>(d, lane, M, per, s_flag, s_box, bv, bk);      // confirmed at the start, matched by neither pass
+            if (bk != INT_MAX && bv >= p.weak_iou) {
+                track_take(p, lane, bk, i, d, scores, lms, s_flag, meta, rec);
+                ++n_weak;
+            }                                          // otherwise DISCARDED: never new, never born
         }
     }
     __syncthreads();                                   // s_new: written by lane 0, read by the owners of the free slots
@@ -108,7 +158,7 @@ __global__ __launch_bounds__(64) void track_update_kernel(TrackParams p) {
         const int k = j * 64 + lane;
         bool is_free = false;
         if (k < M) {
-            const int f = s_flag[k];
+            const int f = WEAK ? s_flag[k] & ~F_CONF : s_flag[k];
             bool alive = (f & F_MATCHED) != 0;
             if (f == F_START) {
                 const int hits = meta[k * 4 + 2], misses = meta[k * 4 + 3] + 1;
@@ -133,7 +183,7 @@ __global__ __launch_bounds__(64) void track_update_kernel(TrackParams p) {
     }
     if (lane == 0) {
         p.next_id[p.stream0 + b] = next + (n_new < base ? n_new : base);
-        p.flags[b] = n_new > base ? 1 : 0;
+        p.flags[b] = (n_new > base ? 1 : 0) | (WEAK && n_weak > 0 ? 2 : 0);
     }
     // the alive slots, compacted in slot order (every lane reads back only what it wrote itself): step 5, cf_trackemit.h
     const TrackRows o{p.dets + (size_t)b * M * 5, p.lms_out + (size_t)b * M * 10, p.info + (size_t)b * M * 3, p.corners + (size_t)b * M * 4};
@@ -154,9 +204,17 @@ const char* track_check(const cf_track_opts* o, int n_streams) {
     return nullptr;
 }
 
+const char* track_weak_check(const cf_track_weak_opts* w) {
+    if (!w) return nullptr;                            // no weak options: the plain tracker
+    if (!std::isfinite(w->birth_score) || !(w->birth_score > 0.f) || !(w->birth_score <= 1.f)) return "birth_score must be finite and in (0, 1]";
+    if (!std::isfinite(w->weak_iou) || !(w->weak_iou > 0.f) || !(w->weak_iou <= 1.f)) return "weak_iou must be finite and in (0, 1]";
+    return nullptr;
+}
+
 hipError_t launch_track_update(hipStream_t s, const TrackParams& p) {
     if (p.B < 1 || p.rows < 1 || p.max_tracks < 1 || p.max_tracks > kTrackMaxSlots || p.stream0 < 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(track_update_kernel, dim3(p.B), dim3(64), 0, s, p);
+    if (p.weak) hipLaunchKernelGGL(track_update_kernel<true>, dim3(p.B), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL(track_update_kernel<false>, dim3(p.B), dim3(64), 0, s, p);
     return hipGetLastError();
 }
 

@@ -447,13 +447,18 @@ def flip_heads(records, B, device=0):
     return out, plane
 
 
-def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=None, device=0, **opts):
+def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=None, device=0, birth_score=None, weak_iou=None, **opts):
     """The tracker's update over a whole sequence (``cf_op_track``) with a fresh tracker: boxes [F, S, rows, 4], scores [F, S, rows], lms
     [F, S, rows, 10], counts [F, S] -- frame f of stream s has the rows below min(count, rows), in whatever coordinates they are.
-    ``opts``: iou, max_age, min_hits, max_tracks, hold_grow (``_lib.track_opts``).  Returns (dets [F, S, max_tracks, 5], lms
+    ``opts``: iou, max_age, min_hits, max_tracks, hold_grow (``_lib.track_opts``).  ``birth_score``: the tracker with two thresholds
+    (``cf_op_track_weak``) -- rows with score > birth_score associate as before, the others may only match a confirmed track, at IoU >=
+    ``weak_iou`` (0.5 unless given), and are never born; flag bit 1 says that one did.  Returns (dets [F, S, max_tracks, 5], lms
     [F, S, max_tracks, 10], info [F, S, max_tracks, 3] = id, hits, misses, counts [F, S], flags [F, S]) after every frame; rows at and
     past a count keep the bytes of the ``dets`` / ``lms_out`` / ``info`` arrays passed in (zeros by default)."""
     o = _lib.track_opts(**opts)
+    if birth_score is None and weak_iou is not None:
+        raise ValueError("weak_iou needs birth_score")
+    wo = None if birth_score is None else _lib.track_weak_opts(birth_score, 0.5 if weak_iou is None else weak_iou)
     b = np.ascontiguousarray(boxes, dtype=np.float32)
     if b.ndim != 4 or b.shape[3] != 4:
         raise ValueError("boxes must be [F, S, rows, 4], got %s" % (b.shape,))
@@ -466,8 +471,11 @@ def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=Non
     ol = np.zeros((F, S, M, 10), np.float32) if lms_out is None else np.ascontiguousarray(lms_out, dtype=np.float32).reshape(F, S, M, 10)
     oi = np.zeros((F, S, M, 3), np.int32) if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(F, S, M, 3)
     oc, fl = np.zeros((F, S), np.int32), np.zeros((F, S), np.int32)
-    _lib.check(_lib.lib().cf_op_track(device, C.byref(o), S, F, rows, ptr(b), ptr(sc), ptr(lm), ptr(cn), ptr(od), ptr(ol), ptr(oi), ptr(oc), ptr(fl)),
-               op=True)
+    tabs = (ptr(b), ptr(sc), ptr(lm), ptr(cn), ptr(od), ptr(ol), ptr(oi), ptr(oc), ptr(fl))
+    if wo is None:
+        _lib.check(_lib.lib().cf_op_track(device, C.byref(o), S, F, rows, *tabs), op=True)
+    else:
+        _lib.check(_lib.lib().cf_op_track_weak(device, C.byref(o), C.byref(wo), S, F, rows, *tabs), op=True)
     return od, ol, oi, oc, fl
 
 

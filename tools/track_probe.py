@@ -10,7 +10,17 @@ each fenced by the engine's events and a synchronize, after warming up every lau
 median and spread of 7 windows of each kind, taken alternately; update_us = the difference of the medians, update_share = update_us /
 decode_us: the update as a share of the decode it follows, from this one run.  The steady state is what is timed: the same 20 faces per
 stream match their tracks at IoU 1 in every update.  One JSON line.  --short: a few calls only, for a rocprofv3 --kernel-trace --stats
-run of its own (kernel: track_update_kernel)."""
+run of its own (kernel: track_update_kernel).
+
+--weak: the tracker with two thresholds (cf_track_create_weak) beside the plain one, in the same run and the same alternation.  Two
+more kinds of window on the SAME rows -- a weak tracker whose birth_score is the decode's threshold, so every row is strong and the
+second pass finds nothing to do:
+  decode_update_weak_us         10 x (the same decode + cf_track_update of the weak tracker)
+and three on a LARGER row count, a decode at a threshold lowered further until every image has 60 rows (max_out = 60):
+  decode60_us, decode60_update_us (a plain tracker: every row associates and is born), decode60_update_weak_us (birth_score = the
+  median over the images of the 21st row's score, so about 20 rows per image are strong and 40 weak: the weak rows only look for a
+  confirmed track, find none -- a weak row is never born -- and are discarded in every update)
+update_*_us are the differences to the decode of the same rows."""
 import json
 import os
 import sys
@@ -20,18 +30,26 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import centerface_amd as cfa
 
-short = "--short" in sys.argv
-B, H, W, MAXF, REP, WIN = 16, 544, 960, 20, 10, 7
+short, weak = "--short" in sys.argv, "--weak" in sys.argv
+B, H, W, MAXF, MAXW, REP, WIN = 16, 544, 960, 20, 60, 10, 7
 rng = np.random.default_rng(0)
 eng = cfa.Engine(H, W, max_batch=B, dtype="bf16", decode_stream=False)
 L, P = cfa._lib.lib(), cfa._lib.ptr
 small = rng.integers(0, 256, (B, H // 8, W // 8, 3), dtype=np.uint8)             # coarse noise: 8-pixel blocks
 eng.forward_enqueue(np.ascontiguousarray(np.repeat(np.repeat(small, 8, 1), 8, 2)))
-for thr in (0.3, 0.1, 0.03, 0.01, 0.001):
-    dets, lms, counts = np.zeros((B, MAXF, 5), np.float32), np.zeros((B, MAXF, 10), np.float32), np.zeros(B, np.int32)
-    eng._chk(L.cf_decode_threshold(eng._h, thr, 0.3, MAXF, P(dets), P(lms), P(counts)))
-    if int(np.minimum(counts, MAXF).min()) == MAXF:
-        break
+
+
+def lowered(ladder, max_out):
+    """The first threshold of ``ladder`` at which every image has ``max_out`` rows (else the last): (threshold, scores [B, max_out], counts)."""
+    for t in ladder:
+        dets, lms, counts = np.zeros((B, max_out, 5), np.float32), np.zeros((B, max_out, 10), np.float32), np.zeros(B, np.int32)
+        eng._chk(L.cf_decode_threshold(eng._h, t, 0.3, max_out, P(dets), P(lms), P(counts)))
+        if int(np.minimum(counts, max_out).min()) == max_out:
+            break
+    return t, dets[:, :, 4], counts
+
+
+thr, _, counts = lowered((0.3, 0.1, 0.03, 0.01, 0.001), MAXF)
 trk = cfa.Tracker(eng, B, max_tracks=256)
 d_counts = eng.device_alloc(4 * B)
 
@@ -45,18 +63,43 @@ def decode_update():
     eng.track_update_device(trk, 0, counts_ptr=d_counts)
 
 
+calls = [("decode", decode), ("decode_update", decode_update)]
+out = {"shape": "%d images %dx%d bf16, decode max_out %d, tracker %d streams x 256 slots" % (B, H, W, MAXF, B), "score_thresh": thr}
+trackers = [trk]
+if weak:
+    thr_w, scores_w, counts_w = lowered([thr * f for f in (0.5, 0.25, 0.1, 0.03, 0.01, 0.001)], MAXW)
+    n_w = np.minimum(counts_w, MAXW)
+    # max_out keeps the best rows, so all 60 may well lie above the first threshold: birth_score for them is the median over the images
+    # of the 21st row's score -- about 20 strong and 40 weak rows per image
+    birth60 = max(float(np.median(scores_w[:, MAXF])), float(np.nextafter(np.float32(thr_w), np.float32(1))))
+    strong = [int((scores_w[b, :n_w[b]] > np.float32(birth60)).sum()) for b in range(B)]
+    same, plain60, weak60 = (cfa.Tracker(eng, B, max_tracks=256, weak_score=thr_w, birth_score=thr), cfa.Tracker(eng, B, max_tracks=256),
+                             cfa.Tracker(eng, B, max_tracks=256, weak_score=thr_w, birth_score=birth60))
+    trackers += [same, plain60, weak60]
+
+    def update_of(t, score, max_out):
+        def call():
+            eng.decode_threshold_enqueue(score, 0.3, max_out)
+            eng.track_update_device(t, 0, counts_ptr=d_counts)
+        return call
+
+    calls += [("decode_update_weak", update_of(same, thr, MAXF)), ("decode60", lambda: eng.decode_threshold_enqueue(thr_w, 0.3, MAXW)),
+              ("decode60_update", update_of(plain60, thr_w, MAXW)), ("decode60_update_weak", update_of(weak60, thr_w, MAXW))]
+    out.update(weak_score_thresh=thr_w, birth_score60=birth60, rows60_per_image=[int(c) for c in n_w], strong_rows60_per_image=strong)
+
 for _ in range(3):                                                              # warm-up: code objects, the context's tracked rows
-    decode()
-    decode_update()
+    for _, call in calls:
+        call()
+eng.synchronize()
+decode_update()
 eng.synchronize()
 tracked = np.zeros(B, np.int32)
 eng.memcpy_d2h(tracked, d_counts)
-out = {"shape": "%d images %dx%d bf16, decode max_out %d, tracker %d streams x 256 slots" % (B, H, W, MAXF, B), "score_thresh": thr,
-       "rows_per_image": [int(c) for c in np.minimum(counts, MAXF)], "tracked_per_stream": tracked.tolist()}
+out.update(rows_per_image=[int(c) for c in np.minimum(counts, MAXF)], tracked_per_stream=tracked.tolist())
 if not short:
-    us = {"decode": [], "decode_update": []}
+    us = {name: [] for name, _ in calls}
     for _ in range(WIN):
-        for name, call in (("decode", decode), ("decode_update", decode_update)):
+        for name, call in calls:
             eng.event_record(0)
             for _ in range(REP):
                 call()
@@ -68,8 +111,13 @@ if not short:
         out["%s_us_min_max" % name] = [round(min(v), 2), round(max(v), 2)]
     out["update_us"] = round(out["decode_update_us"] - out["decode_us"], 2)
     out["update_share"] = round(out["update_us"] / out["decode_us"], 3)
+    if weak:
+        out["update_weak_us"] = round(out["decode_update_weak_us"] - out["decode_us"], 2)
+        out["update60_us"] = round(out["decode60_update_us"] - out["decode60_us"], 2)
+        out["update60_weak_us"] = round(out["decode60_update_weak_us"] - out["decode60_us"], 2)
 eng.synchronize()
 eng.device_free(d_counts)
-trk.close()
+for t in trackers:
+    t.close()
 eng.close()
 print(json.dumps(out))

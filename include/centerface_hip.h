@@ -1198,9 +1198,18 @@ const char* cf_op_last_kernel(void);
 /* ConvReLU depthwise / ShuffleV2 dw: pad -> conv2d(groups=C, bias=False) -> act.
  * x [B,C,H,W], w [C,1,k,k], y [B,C,Ho,Wo]; pad_lo/pad_hi as ZeroPad2d (model/centernet.py:63,68-70;
  * model/blocks.py:28); act: 0 none, 1 swish.  bias may be NULL (folded BN shift, blocks.py:29).
- * C a multiple of 8; one image (H x W x C in the storage type) smaller than 4 GiB (CF_EINVAL otherwise). */
+ * C a multiple of 8; k 3 or 5; stride 1 or 2; act 0 or 1; the padded input at least k x k (so Ho, Wo >= 1); one image (H x W x C in the
+ * storage type) smaller than 4 GiB (CF_EINVAL otherwise, before any GPU work: y is not written). */
 int cf_op_dwconv(int device, int dtype, const float* x, const float* w, const float* bias, float* y,
                  int B, int C, int H, int W, int k, int stride, int pad_lo, int pad_hi, int act);
+/* Which kernel instance cf_op_dwconv (and the engine's and the ShuffleV2 block's standalone depthwise) would launch for a shape, and
+ * with what: the host half of the launcher only, no device, no launch.  out = {ok, strip (1 dw_strip_kernel, 0 dw_lds_kernel), k,
+ * stride, tile rows, tile columns, Cc (channels per chunk), nchunk, cpp (16-byte groups per pixel of a chunk), threads per workgroup,
+ * dynamic LDS bytes, ntx, nty (tiles across / down one image), workgroups, Ho, Wo}; tag (may be NULL; tag_len bytes) receives the
+ * symbol cf_op_last_kernel reports after that launch.  ok = 0 (all zeros, empty tag, CF_OK) for a shape cf_op_dwconv refuses.
+ * CF_EINVAL only for an unknown dtype, B < 1, a null out or tag_len < 1 with a tag. */
+int cf_op_dw_pick(int dtype, int B, int C, int H, int W, int k, int stride, int pad_lo, int pad_hi, int act, int has_bias,
+                  int out[16], char* tag, int tag_len);
 /* 1x1 conv [+bias] [+act] [+residual]: x [B,Cin,H,W], w [Cout,Cin], y [B,Cout,H,W]
  * (model/centernet.py:109-110,117-118,134-137,179-184; blocks.py:22-24,31-33). act 0/1 swish/2 relu */
 int cf_op_pwconv(int device, int dtype, const float* x, const float* w, const float* bias,

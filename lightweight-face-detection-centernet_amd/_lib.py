@@ -47,7 +47,7 @@ EXPORTS = (
     "cf_load_weights", "cf_forward", "cf_forward_resized", "cf_forward_yuv", "cf_forward_images", "cf_upload_images", "cf_forward_uploaded", "cf_get_resized_input", "cf_get_heads", "cf_decode_topk", "cf_decode_topk_post", "cf_affine_from_center_scale", "cf_decode_threshold", "cf_decode_threshold_ex", "cf_decode_threshold_sized", "cf_decode_threshold_enqueue", "cf_set_rescale",
     "cf_detect_topk", "cf_synchronize", "cf_event_record", "cf_event_elapsed_ms",
     "cf_profile_forward", "cf_plan_size", "cf_plan_op", "cf_forward_trace", "cf_graph_stats", "cf_get_streams", "cf_streams_share_queue", "cf_streams_share_queue_ex", "cf_spread_streams", "cf_reroll_streams", "cf_ctdet_loss", "cf_comm_unique_id", "cf_comm_create", "cf_comm_create_all", "cf_comm_create_loopback", "cf_comm_loopback_rank", "cf_comm_destroy", "cf_comm_abort", "cf_comm_query", "cf_comm_synchronize", "cf_comm_last_error", "cf_comm_debug", "cf_comm_set_shard", "cf_comm_stream", "cf_gather_topk", "cf_host_alloc", "cf_host_free", "cf_pinned_alloc", "cf_pinned_free", "cf_host_register", "cf_host_unregister", "cf_device_alloc", "cf_device_free", "cf_memcpy_h2d", "cf_memcpy_d2h",
-    "cf_op_last_error", "cf_op_last_kernel", "cf_op_shufflev2", "cf_op_mbconv", "cf_op_expand_dw", "cf_op_mbconv_pick", "cf_op_expand_dw_pick", "cf_op_ctdet_loss", "cf_op_encode_targets", "cf_op_dwconv", "cf_op_pwconv", "cf_op_pwconv_ex", "cf_op_stem", "cf_op_idaup", "cf_op_heads",
+    "cf_op_last_error", "cf_op_last_kernel", "cf_op_shufflev2", "cf_op_mbconv", "cf_op_expand_dw", "cf_op_mbconv_pick", "cf_op_expand_dw_pick", "cf_op_ctdet_loss", "cf_op_encode_targets", "cf_op_dwconv", "cf_op_dw_pick", "cf_op_pwconv", "cf_op_pwconv_ex", "cf_op_stem", "cf_op_idaup", "cf_op_heads",
     "cf_op_ctdet_decode", "cf_op_ctdet_post_process", "cf_op_decode_threshold", "cf_op_decode_threshold_ex", "cf_op_nms", "cf_op_box_match",
     "cf_op_yuv_to_bgr", "cf_align_faces", "cf_op_align_faces", "cf_align_faces_frame", "cf_op_align_frame", "cf_redact_faces", "cf_op_redact",
     "cf_blur_faces", "cf_op_blur",
@@ -678,6 +678,7 @@ def lib():
         L.cf_op_shufflev2.argtypes = [i, i, fp, fp] + [i] * 8 + [fp] * 10
         L.cf_op_mbconv.argtypes = [i, i, fp, fp, fp, fp, fp] + [i] * 8
         L.cf_op_expand_dw.argtypes = [i, i, fp, fp, fp, fp] + [i] * 7
+        L.cf_op_dw_pick.argtypes = [i] * 11 + [C.POINTER(C.c_int), C.c_char_p, i]
         L.cf_op_mbconv_pick.argtypes = [i] * 6 + [C.POINTER(C.c_int)]
         L.cf_op_expand_dw_pick.argtypes = [i] * 5 + [C.POINTER(C.c_int)]
         L.cf_op_idaup.argtypes = [i, i, fp, fp, fp, fp, fp, fp, C.c_float, fp] + [i] * 5

@@ -20,6 +20,7 @@
 #include "cf_common.h"
 #include "cf_kernels.h"
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -46,6 +47,23 @@ struct DwLdsGeom { int Cc, nchunk, cpp, rc, nch, magic_rc, magic_cpp, nt, xcd; s
 static void dw_set_step(DwLdsGeom& g, int threads) {
     g.srow = threads / g.rc; const int r1 = threads - g.srow * g.rc;
     g.spx = r1 / g.cpp; g.spart = r1 - g.spx * g.cpp;
+}
+// What launch_dw does for one shape: the instance and its launch parameters (DwChoice, cf_kernels.h: what cf_op_dw_pick shows) and the geometry the
+// kernel receives.  dw_plan below is the ONE place that computes it; the launchers only read it.
+struct DwPlan { DwChoice c; DwLdsGeom g; };
+template <typename T>
+static bool dw_plan_finish(const DwParams& p, DwPlan& pl, bool strip, int th, int tw, int threads) {
+    DwChoice& c = pl.c; DwLdsGeom& g = pl.g;
+    dw_set_step(g, threads);
+    c.strip = strip ? 1 : 0; c.k = p.k; c.s = p.s; c.th = th; c.tw = tw; c.threads = threads;
+    c.Cc = g.Cc; c.nchunk = g.nchunk; c.cpp = g.cpp; c.lds_bytes = g.lds_bytes;
+    c.ntx = (p.Wo + tw - 1) / tw; c.nty = (p.Ho + th - 1) / th;
+    c.nwg = (long long)p.B * g.nchunk * c.nty * c.ntx;
+    if (c.nwg > 0x7fffffffLL) return false;
+    if (strip) snprintf(c.tag, sizeof c.tag, "void cf::dw_strip_kernel<%s, %d, %d, %d, %d>(cf::DwParams, cf::DwLdsGeom, int, int, int)", type_tag<T>(), p.k, p.s, th, tw);
+    else snprintf(c.tag, sizeof c.tag, "void cf::dw_lds_kernel<%s, %d, %d, %d, %d, %d, %s>(cf::DwParams, cf::DwLdsGeom)", type_tag<T>(), p.k, p.s, th, tw,
+                  p.act, p.bias ? "true" : "false");
+    return true;
 }
 // Workgroups are dealt to the eight XCDs round-robin by their linear id, and each XCD has an L2 of its own: with the plain order
 // the tile below (its first halo rows = this tile's last ones) and the other channel chunks of the same pixels (the other half of
@@ -159,30 +177,34 @@ __global__ __launch_bounds__(256) void dw_lds_kernel(DwParams p, DwLdsGeom g) {
 }
 
 
-template <typename T, int KS, int S, int TH, int TW>
-static hipError_t dw_lds_dispatch(hipStream_t s, const DwParams& p, int cap_default = 48) {
-    constexpr int IH = (TH - 1) * S + KS, IW = (TW - 1) * S + KS;
+// geometry of the one-vector form on a TH x TW tile: the channel chunk is the largest divisor of C (a multiple of one 16-byte group) whose tile fits the budget
+// (48 KiB unless the caller's table says otherwise: tile + tap weights stay under the 64 KiB default dynamic-LDS limit; a smaller budget = more workgroups per
+// CU, shorter DMA runs per pixel)
+template <typename T>
+static bool dw_lds_plan(const DwParams& p, int TH, int TW, int cap_default, DwPlan& pl) {
+    const int IH = (TH - 1) * p.s + p.k, IW = (TW - 1) * p.s + p.k;
     constexpr int P = 16 / (int)sizeof(T);
-    // channel chunk: largest divisor of C (multiple of one 16-byte group) whose tile fits the budget (48 KiB unless the caller's table says otherwise: tile +
-    // tap weights stay under the 64 KiB default dynamic-LDS limit; a smaller budget = more workgroups per CU, shorter DMA runs per pixel)
     int Cc = 0;
     static const int cap_env = cf_ab_int("CF_DW_CAP2", 0);           // A/B: LDS budget of the tile in KB
     const int cap_kb = cap_env > 0 ? cap_env : cap_default;
     for (int c = p.C; c >= P; c -= P)
         if (p.C % c == 0 && (size_t)IH * IW * c * sizeof(T) <= (size_t)cap_kb * 1024) { Cc = c; break; }
-    if (!Cc) return hipErrorInvalidValue;
-    DwLdsGeom g;
+    if (!Cc) return false;
+    DwLdsGeom& g = pl.g;
     g.Cc = Cc; g.nchunk = p.C / Cc; g.cpp = Cc / P; g.rc = IW * g.cpp; g.nch = IH * g.rc;
-    if (g.nch >= 65536) return hipErrorInvalidValue;
+    if (g.nch >= 65536) return false;
     g.magic_rc = magic_div(g.rc); g.magic_cpp = magic_div(g.cpp);
     g.nt = 0;          // (non-temporal DMA loads cost 8-35 %, non-temporal stores nothing: profiles/r01_dw_variants.md, r06_dw_xcd.md)
-    dw_set_step(g, 256);
     { static const int xcd_env = cf_ab_int("CF_DW_XCD", 1); g.xcd = xcd_env; }
-    g.lds_bytes = (((size_t)g.nch * 16 + 1023) / 1024) * 1024 + (size_t)KS * KS * Cc * 4;
-    dim3 grid((p.Wo + TW - 1) / TW, (p.Ho + TH - 1) / TH, p.B * g.nchunk), blk(256);
+    g.lds_bytes = (((size_t)g.nch * 16 + 1023) / 1024) * 1024 + (size_t)p.k * p.k * Cc * 4;
+    return dw_plan_finish<T>(p, pl, false, TH, TW, 256);
+}
+template <typename T, int KS, int S, int TH, int TW>
+static hipError_t dw_lds_launch(hipStream_t s, const DwParams& p, const DwPlan& pl) {
+    const DwLdsGeom& g = pl.g;
+    dim3 grid(pl.c.ntx, pl.c.nty, p.B * g.nchunk), blk(pl.c.threads);
     const bool bias = p.bias != nullptr;
-    set_kernel_tag("void cf::dw_lds_kernel<%s, %d, %d, %d, %d, %d, %s>(cf::DwParams, cf::DwLdsGeom)", type_tag<T>(), KS, S, TH, TW,
-                   p.act, bias ? "true" : "false");
+    set_kernel_tag("%s", pl.c.tag);
 #define CF_DW_LAUNCH(ACT, BIAS) \
     hipLaunchKernelGGL((dw_lds_kernel<T, KS, S, TH, TW, ACT, BIAS>), grid, blk, g.lds_bytes, s, p, g); return hipGetLastError();
     if (p.act == 1 && !bias) { CF_DW_LAUNCH(1, false) }
@@ -190,6 +212,13 @@ static hipError_t dw_lds_dispatch(hipStream_t s, const DwParams& p, int cap_defa
     if (p.act == 0 && !bias) { CF_DW_LAUNCH(0, false) }
     CF_DW_LAUNCH(1, true)
 #undef CF_DW_LAUNCH
+}
+// (the experiments build's tile sweeps name an instance themselves)
+template <typename T, int KS, int S, int TH, int TW>
+static hipError_t dw_lds_dispatch(hipStream_t s, const DwParams& p, int cap_default = 48) {
+    DwPlan pl{};
+    if (p.k != KS || p.s != S || !dw_lds_plan<T>(p, TH, TW, cap_default, pl)) return hipErrorInvalidValue;
+    return dw_lds_launch<T, KS, S, TH, TW>(s, p, pl);
 }
 
 
@@ -328,11 +357,11 @@ __global__ __launch_bounds__(256) void dw_strip_kernel(DwParams p, DwLdsGeom g, 
 #include CF_EXP_INC(cf_dw_5)   // the strip form in two row bands (dw_band_kernel): measured, +2-7 % on some layers, -7 % on others -- experiments build only
 struct DwTileCfg { int th, tw; };
 template <typename T, int KS, int S, int TH, int TW>
-static hipError_t dw_strip_launch(hipStream_t s, const DwParams& p, const DwLdsGeom& g, int threads) {
+static hipError_t dw_strip_launch(hipStream_t s, const DwParams& p, const DwPlan& pl) {
     int dev = 0; (void)hipGetDevice(&dev);
-    const int ntx = (p.Wo + TW - 1) / TW, nty = (p.Ho + TH - 1) / TH;
-    const long long nt = (long long)p.B * g.nchunk * nty * ntx;
-    if (nt > 0x7fffffffLL) return hipErrorInvalidValue;
+    const DwLdsGeom& g = pl.g;
+    const int threads = pl.c.threads, ntx = pl.c.ntx, nty = pl.c.nty;
+    const long long nt = pl.c.nwg;
 #include CF_EXP_INC(cf_dw_6)   // CF_DW_BAND=1: dw_band_kernel
     // CF_DW_WGS = n > 0: n PERSISTENT workgroups per CU, each walking tiles with two LDS buffers (the DMA of the next tile under the arithmetic of
     // this one); 0: one workgroup per tile, one buffer -- the overlap comes from the other workgroups of the CU
@@ -340,9 +369,8 @@ static hipError_t dw_strip_launch(hipStream_t s, const DwParams& p, const DwLdsG
     int ncu = 256; { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ncu = pr.multiProcessorCount; }
     const bool persist = per_cu > 0 && nt > (long long)ncu * per_cu;
     const int nwg = persist ? ncu * per_cu : (int)nt;
-    set_kernel_tag("void cf::dw_strip_kernel<%s, %d, %d, %d, %d>(cf::DwParams, cf::DwLdsGeom, int, int, int)", type_tag<T>(), KS, S, TH, TW);
-    DwLdsGeom gs = g; dw_set_step(gs, threads);
-    return launch_lds<dw_strip_kernel<T, KS, S, TH, TW>>(dim3(nwg), dim3(threads), (persist ? 2 : 1) * g.lds_bytes, s, p, gs, ntx, nty, (int)nt);
+    set_kernel_tag("%s", pl.c.tag);
+    return launch_lds<dw_strip_kernel<T, KS, S, TH, TW>>(dim3(nwg), dim3(threads), (persist ? 2 : 1) * g.lds_bytes, s, p, g, ntx, nty, (int)nt);
 }
 
 // geometry of one candidate tile: the largest channel chunk (a divisor of C, whole 16-byte groups) whose tile + tap weights fit `cap`
@@ -374,65 +402,99 @@ static bool dw_strip_geom(const DwParams& p, int TH, int TW, size_t cap, DwLdsGe
     return true;
 }
 
+// the instances: strip form (stride 1, k = 3 and 5 each) and one-vector form (stride 2) -- dw_run below instantiates exactly these
 #define CF_DW_TILES(X) X(4, 16) X(4, 32) X(8, 16) X(8, 32) X(16, 16) X(16, 32) X(8, 40) X(10, 20) X(20, 20)
+#define CF_DW2_TILES(X) X(3, 10, 20) X(3, 4, 32) X(3, 4, 16) X(5, 8, 16) X(5, 4, 32)
 // Tile and LDS budget per shape class: the best of an exhaustive sweep (nine tiles x five LDS caps per layer of the 640x640 network at B = 64,
 // tools/dw_sweep2.sh, profiles/r06_dw_strip.md); shapes the table does not fit fall back to the score of dw_strip_geom.
 static void dw_strip_table(int k, int s, int Wo, int& th, int& tw, int& cap_kb) {
-    (void)s;                                                         // (stride 1 only: dw_by_stride)
+    (void)s;                                                         // (stride 1 only: dw_plan)
     if (k == 3) { if (Wo >= 256) { th = 16; tw = 32; cap_kb = 60; } else if (Wo >= 96) { th = 8; tw = 40; cap_kb = 48; } else { th = 10; tw = 20; cap_kb = 48; } }
     else { if (Wo >= 64) { th = 16; tw = 16; cap_kb = 32; } else if (Wo >= 32) { th = 20; tw = 20; cap_kb = 48; } else { th = 10; tw = 20; cap_kb = 32; } }
 }
-template <typename T, int KS, int S>
-static hipError_t dw_strip_pick(hipStream_t s, const DwParams& p) {
+template <typename T>
+static bool dw_strip_plan(const DwParams& p, DwPlan& pl) {
     static const int force = cf_ab_int("CF_DW_TILE", -1);           // A/B: index into the tile list
     static const int cap_env = cf_ab_int("CF_DW_CAP", 0);           //      LDS budget of the tile buffer in KB
+    static const DwTileCfg tiles[] = {
+#define CF_DW_ROW(TH_, TW_) {TH_, TW_},
+        CF_DW_TILES(CF_DW_ROW)
+#undef CF_DW_ROW
+    };
+    const int ntile = (int)(sizeof tiles / sizeof tiles[0]);
     int tth = 0, ttw = 0, tcap = 48;
-    dw_strip_table(KS, S, p.Wo, tth, ttw, tcap);
-    int best = -1, bthreads = 0, idx = 0; double bscore = -1.0; DwLdsGeom bg{};
+    dw_strip_table(p.k, p.s, p.Wo, tth, ttw, tcap);
+    int best = -1, bthreads = 0; double bscore = -1.0; DwLdsGeom bg{};
     // first choice: the table's tile; otherwise (or when the table's tile cannot hold one 16-byte channel group) the best score
     for (int pass = 0; pass < 2 && best < 0; ++pass) {
         const size_t cap = (size_t)(cap_env > 0 ? cap_env : (pass == 0 ? tcap : 48)) * 1024;
-        idx = 0;
-#define CF_DW_TRY(TH_, TW_) { DwLdsGeom g{}; int th = 0; double sc = 0; \
-            const bool want = force >= 0 ? idx == force : (pass == 0 ? (TH_ == tth && TW_ == ttw) : true); \
-            if (want && dw_strip_geom<T>(p, TH_, TW_, cap, g, th, sc) && (force >= 0 || pass == 0 || sc > bscore)) { best = idx; bscore = sc; bg = g; bthreads = th; } ++idx; }
-        CF_DW_TILES(CF_DW_TRY)
-#undef CF_DW_TRY
+        for (int idx = 0; idx < ntile; ++idx) {
+            DwLdsGeom g{}; int th = 0; double sc = 0;
+            const bool want = force >= 0 ? idx == force : (pass == 0 ? (tiles[idx].th == tth && tiles[idx].tw == ttw) : true);
+            if (want && dw_strip_geom<T>(p, tiles[idx].th, tiles[idx].tw, cap, g, th, sc) && (force >= 0 || pass == 0 || sc > bscore)) { best = idx; bscore = sc; bg = g; bthreads = th; }
+        }
         if (force >= 0) break;
     }
-    if (best < 0) return hipErrorInvalidValue;
-    idx = 0;
-#define CF_DW_GO(TH_, TW_) if (idx++ == best) return dw_strip_launch<T, KS, S, TH_, TW_>(s, p, bg, bthreads);
-    CF_DW_TILES(CF_DW_GO)
-#undef CF_DW_GO
-    return hipErrorInvalidValue;
+    if (best < 0) return false;
+    pl.g = bg;
+    return dw_plan_finish<T>(p, pl, true, tiles[best].th, tiles[best].tw, bthreads);
 }
 // Stride 1: the strip form (3.3-4.2 TB/s at 3x3 against 2.5-3.8, 1.9-2.3 TB/s at 5x5 against 1.3-1.7).  Stride 2: round 1's one-vector form -- a strip of four
 // stride-2 outputs sits on 9 / 11 input columns per row, the reuse is small and the work items are four times fewer: measured 4.18 / 2.73 / 3.73 / 1.84 TB/s
 // (layer1.0 / 2.0 / 3.0 / 5.0, best of 45 tile x LDS-budget combinations each) against 4.63 / 2.70 / 3.97 / 1.98 (profiles/r06_dw_strip.md).
 template <typename T>
-static hipError_t dw_by_stride(hipStream_t s, const DwParams& p) {
-    if (p.k == 3 && p.s == 1) return dw_strip_pick<T, 3, 1>(s, p);
-    if (p.k == 5 && p.s == 1) return dw_strip_pick<T, 5, 1>(s, p);
-#include CF_EXP_INC(cf_dw_4)   // CF_DW2_TILE: tile sweep of the stride-2 form
+static bool dw_plan(const DwParams& p, DwPlan& pl) {
+    if ((p.k == 3 || p.k == 5) && p.s == 1) return dw_strip_plan<T>(p, pl);
     if (p.k == 3 && p.s == 2) {
-        if (p.Ho <= 20 && p.Wo <= 20 && p.Ho > 8) return dw_lds_dispatch<T, 3, 2, 10, 20>(s, p);      // small late maps: one tile = the whole map
+        if (p.Ho <= 20 && p.Wo <= 20 && p.Ho > 8) return dw_lds_plan<T>(p, 10, 20, 48, pl);      // small late maps: one tile = the whole map
         // (tile x LDS budget sweep with the XCD-contiguous order, gpurun_out/r06q_sweep_s2.txt: layer3.0 3.77 -> 4.33 TB/s at 24 KB)
-        return p.Wo >= 64 ? dw_lds_dispatch<T, 3, 2, 4, 32>(s, p, 48) : dw_lds_dispatch<T, 3, 2, 4, 16>(s, p, 24);
+        return p.Wo >= 64 ? dw_lds_plan<T>(p, 4, 32, 48, pl) : dw_lds_plan<T>(p, 4, 16, 24, pl);
     }
     // (same sweep: layer2.0 2.55 -> 2.93 TB/s on 8x16 tiles at 24 KB, layer5.0 1.94 -> 2.16 at 32 KB)
-    if (p.k == 5 && p.s == 2) return p.Wo >= 64 ? dw_lds_dispatch<T, 5, 2, 8, 16>(s, p, 24) : dw_lds_dispatch<T, 5, 2, 4, 32>(s, p, 32);
+    if (p.k == 5 && p.s == 2) return p.Wo >= 64 ? dw_lds_plan<T>(p, 8, 16, 24, pl) : dw_lds_plan<T>(p, 4, 32, 32, pl);
+    return false;
+}
+// the plan's instance, launched with the plan's parameters
+template <typename T>
+static hipError_t dw_run(hipStream_t s, const DwParams& p, const DwPlan& pl) {
+#include CF_EXP_INC(cf_dw_4)   // CF_DW2_TILE: tile sweep of the stride-2 form
+    const DwChoice& c = pl.c;
+    if (c.strip) {
+#define CF_DW_GO(TH_, TW_) if (c.th == TH_ && c.tw == TW_) return c.k == 3 ? dw_strip_launch<T, 3, 1, TH_, TW_>(s, p, pl) : dw_strip_launch<T, 5, 1, TH_, TW_>(s, p, pl);
+        CF_DW_TILES(CF_DW_GO)
+#undef CF_DW_GO
+        return hipErrorInvalidValue;
+    }
+#define CF_DW_GO(K_, TH_, TW_) if (c.k == K_ && c.th == TH_ && c.tw == TW_) return dw_lds_launch<T, K_, 2, TH_, TW_>(s, p, pl);
+    CF_DW2_TILES(CF_DW_GO)
+#undef CF_DW_GO
     return hipErrorInvalidValue;
 }
 
 #include CF_EXP_INC(cf_dw_2)   // ... and their per-shape dispatch
 
+// every shape question of the standalone depthwise is answered on the host alone: what launch_dw refuses outright, then the plan by storage type
+static bool dw_admits(int dtype, const DwParams& p) {
+    if (p.C % 8) return false;
+    return (unsigned long long)p.H * p.W * p.C * (dtype != 1 ? 4ull : 2ull) < (1ull << 32);       // 32-bit byte offsets inside an image (dw_stage_tile)
+}
+static bool dw_plan_any(int dtype, const DwParams& p, DwPlan& pl) {
+    return dtype != 1 ? dw_plan<float>(p, pl) : dw_plan<bf16_t>(p, pl);      // dtype 2: fp32 storage, no GEMM here
+}
+hipError_t dw_choose(int dtype, const DwParams& p, DwChoice& c) {
+    DwPlan pl{};
+    if (!dw_admits(dtype, p) || !dw_plan_any(dtype, p, pl)) return hipErrorInvalidValue;
+    c = pl.c;
+    return hipSuccess;
+}
+
 hipError_t launch_dw(hipStream_t s, int dtype, const DwParams& p) {
     if (p.B <= 0) return hipSuccess;
-    if (p.C % 8) return hipErrorInvalidValue;
-    if ((unsigned long long)p.H * p.W * p.C * (dtype != 1 ? 4ull : 2ull) >= (1ull << 32)) return hipErrorInvalidValue;       // 32-bit byte offsets inside an image (dw_stage_tile)
+    if (!dw_admits(dtype, p)) return hipErrorInvalidValue;
 #include CF_EXP_INC(cf_dw_3)   // CF_DW_MARCH=1 / CF_DW_STRIP=0: the older kernels, for A/B runs
-    return dtype != 1 ? dw_by_stride<float>(s, p) : dw_by_stride<bf16_t>(s, p);      // dtype 2: fp32 storage, no GEMM here
+    DwPlan pl{};
+    if (!dw_plan_any(dtype, p, pl)) return hipErrorInvalidValue;
+    return dtype != 1 ? dw_run<float>(s, p, pl) : dw_run<bf16_t>(s, p, pl);
 }
 
 }  // namespace cf

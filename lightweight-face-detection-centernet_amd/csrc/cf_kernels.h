@@ -66,6 +66,18 @@ struct DwParams {
 };
 void dw_pack_weights(const float* w /*[C][1][k][k]*/, int C, int k, float* out_host /*[k][k][C]*/);
 hipError_t launch_dw(hipStream_t s, int dtype, const DwParams& p);
+// What launch_dw does for p, from the host alone (no device, no launch; of p it reads the sizes, k, s, pad_lo, act and WHETHER bias is set): the
+// instance (strip = dw_strip_kernel, else dw_lds_kernel; its k, s and tile), its symbol as cf_op_last_kernel reports it after the launch, the channel
+// chunk, the chunks per image, the 16-byte groups per pixel of a chunk, threads per workgroup, dynamic LDS bytes, the tile grid and the number of
+// workgroups.  hipErrorInvalidValue where launch_dw refuses.  launch_dw launches exactly this (one function computes both: dw_plan, cf_dw.hip).
+struct DwChoice {
+    char tag[160];
+    int strip, k, s, th, tw;
+    int Cc, nchunk, cpp, threads, ntx, nty;
+    long long nwg;
+    size_t lds_bytes;
+};
+hipError_t dw_choose(int dtype, const DwParams& p, DwChoice& c);
 
 // ------------------------------------------------------------------ fused MBConv block
 // The kernel families.  The values are kernel arguments (MbParams::kind) and appear in tool output: they never change (3 is unused).

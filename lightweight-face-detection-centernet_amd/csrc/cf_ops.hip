@@ -337,23 +337,52 @@ int cf_host_unregister(void* hptr) {
     return CF_OK;
 }
 
+// What cf_op_dwconv and cf_op_dw_pick refuse before anything else, and the output size.  The padded input must hold one window: C's division
+// truncates, so (H + pad - k) / stride + 1 alone would call a 2-row input under a 3 x 3 stride-2 window one output row.
+static bool dw_args(int dtype, int C, int H, int W, int k, int stride, int pad_lo, int pad_hi, int act, int* Ho, int* Wo) {
+    if (bad_dtype(dtype) || (C % 8) || (k != 3 && k != 5) || (stride != 1 && stride != 2) || (act != 0 && act != 1)) return false;
+    if (H < 1 || W < 1 || (long long)H + pad_lo + pad_hi < k || (long long)W + pad_lo + pad_hi < k) return false;
+    *Ho = (H + pad_lo + pad_hi - k) / stride + 1; *Wo = (W + pad_lo + pad_hi - k) / stride + 1;
+    return true;
+}
+static DwParams dw_shape(int B, int C, int H, int W, int Ho, int Wo, int k, int stride, int pad_lo, int act) {
+    DwParams p{};
+    p.B = B; p.C = C; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.k = k; p.s = stride; p.pad_lo = pad_lo; p.act = act;
+    return p;
+}
 int cf_op_dwconv(int device, int dtype, const float* x, const float* w, const float* bias, float* y,
                  int B, int C, int H, int W, int k, int stride, int pad_lo, int pad_hi, int act) {
-    if (bad_dtype(dtype) || !x || !w || !y || (C % 8) || (k != 3 && k != 5) || (stride != 1 && stride != 2)) return CF_EINVAL;
-    const int Ho = (H + pad_lo + pad_hi - k) / stride + 1, Wo = (W + pad_lo + pad_hi - k) / stride + 1;
-    if (Ho < 1 || Wo < 1) return CF_EINVAL;
+    int Ho = 0, Wo = 0;
+    if (!x || !w || !y || !dw_args(dtype, C, H, W, k, stride, pad_lo, pad_hi, act, &Ho, &Wo)) return CF_EINVAL;
     Scope sc(device);
     std::vector<float> wp((size_t)k * k * C);
     dw_pack_weights(w, C, k, wp.data());
-    DwParams p{};
+    DwParams p = dw_shape(B, C, H, W, Ho, Wo, k, stride, pad_lo, act);
     p.x = sc.to_nhwc(dtype, x, B, C, H, W);
     p.w = sc.upv(wp);
     p.bias = bias ? sc.in(bias, C) : nullptr;
     p.y = sc.alloc_nan((size_t)B * Ho * Wo * C * elem_size(dtype));
-    p.B = B; p.C = C; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.k = k; p.s = stride; p.pad_lo = pad_lo; p.act = act;
     sc.run([&] { return launch_dw(sc.s, dtype, p); });
     sc.to_host_nchw(dtype, p.y, y, B, C, Ho, Wo);
     return sc.result("cf_op_dwconv");
+}
+// launch_dw's choice for the shape cf_op_dwconv would hand it (dw_choose: the host half of launch_dw, no device)
+int cf_op_dw_pick(int dtype, int B, int C, int H, int W, int k, int stride, int pad_lo, int pad_hi, int act, int has_bias,
+                  int out[16], char* tag, int tag_len) {
+    if (bad_dtype(dtype) || !out || B < 1 || (tag && tag_len < 1)) return CF_EINVAL;
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    if (tag) tag[0] = 0;
+    int Ho = 0, Wo = 0;
+    if (!dw_args(dtype, C, H, W, k, stride, pad_lo, pad_hi, act, &Ho, &Wo)) return CF_OK;
+    static const float some_bias = 0.0f;
+    DwParams p = dw_shape(B, C, H, W, Ho, Wo, k, stride, pad_lo, act);
+    p.bias = has_bias ? &some_bias : nullptr;                      // (dw_choose only asks whether there is one)
+    DwChoice c{};
+    if (dw_choose(dtype, p, c) != hipSuccess) return CF_OK;
+    const int v[16] = {1, c.strip, c.k, c.s, c.th, c.tw, c.Cc, c.nchunk, c.cpp, c.threads, (int)c.lds_bytes, c.ntx, c.nty, (int)c.nwg, Ho, Wo};
+    for (int i = 0; i < 16; ++i) out[i] = v[i];
+    if (tag) snprintf(tag, (size_t)tag_len, "%s", c.tag);
+    return CF_OK;
 }
 
 int cf_op_pwconv_ex(int device, int dtype, const float* x, const float* w, const float* bias,

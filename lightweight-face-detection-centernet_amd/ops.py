@@ -21,10 +21,29 @@ def conv_dw(x, w, k, stride, pad=None, act="swish", bias=None, dtype="fp32", dev
         pad = (p // 2, p - p // 2)
     Ho = (H + pad[0] + pad[1] - k) // stride + 1
     Wo = (W + pad[0] + pad[1] - k) // stride + 1
-    y = np.empty((B, Cc, Ho, Wo), np.float32)
+    y = np.empty((B, Cc, max(Ho, 0), max(Wo, 0)), np.float32)      # (no output: the library refuses the call)
     _lib.check(_lib.lib().cf_op_dwconv(device, _DT[dtype], ptr(x), ptr(w), ptr(f32(bias)), ptr(y), B, Cc, H, W,
                                        k, stride, pad[0], pad[1], {"none": 0, "swish": 1}[act]), op=True)
     return y
+
+
+_DW_PICK = ("ok", "strip", "k", "s", "TH", "TW", "Cc", "nchunk", "cpp", "threads", "lds_bytes", "ntx", "nty", "workgroups", "Ho", "Wo")
+
+
+def dw_pick(C_, H, W, k, stride, pad=None, dtype="fp32", B=1, act="swish", bias=False):
+    """What ``conv_dw`` would launch for a shape, from the host half of the launcher alone (cf_op_dw_pick: no GPU needed):
+    {ok, tag (the symbol ``last_kernel()`` reports after the launch), strip, k, s, TH, TW, Cc, nchunk, cpp, threads, lds_bytes,
+    ntx, nty, workgroups, Ho, Wo}; ok = False (tag None, zeros) for a shape ``conv_dw`` refuses.  ``pad`` as in ``conv_dw``."""
+    if pad is None:
+        p = max(k - stride, 0)
+        pad = (p // 2, p - p // 2)
+    out, tag = (C.c_int * 16)(), C.create_string_buffer(160)
+    _lib.check(_lib.lib().cf_op_dw_pick(_DT[dtype], int(B), int(C_), int(H), int(W), int(k), int(stride), int(pad[0]), int(pad[1]),
+                                        {"none": 0, "swish": 1}[act], 1 if bias else 0, out, tag, 160), op=True)
+    d = dict(zip(_DW_PICK, (int(v) for v in out)))
+    d["ok"] = bool(d["ok"])
+    d["tag"] = tag.value.decode() if d["ok"] else None
+    return d
 
 
 def last_kernel():

@@ -514,6 +514,65 @@ int cf_forward_fit(cf_ctx* ctx, const cf_fit_opts* opts, int format, const cf_yu
  * last forward was cf_forward_fit with a threshold decode behind it. */
 int cf_unfit_rows(cf_ctx* ctx, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device);
 
+/* ---- rotated sources: detect upright in frames stored a quarter or half turn away ------------
+ * Every forward above takes the stored frame for upright.  A corridor-mode camera (the sensor mounted a quarter turn, the stream still
+ * 1920 x 1080) and phone video (the turn kept in the container's display matrix, the hardware decoder handing out the surface as stored)
+ * break that: the network, trained on upright faces (the reference mirrors its training images and never turns them,
+ * dataset/dataset.py:125-128), sees sideways ones.  cf_forward_rot fills the canvases from the UPRIGHT view of the stored frames and
+ * cf_unfit_rows maps the decode's rows back into the STORED frame's pixels, so cover, draw and chip calls work in place on the
+ * decoder's surface as they do behind cf_forward_fit; cf_align_faces_frame fits a similarity to the landmarks, so its chips of a turned
+ * frame come out upright as they are:
+ *   cf_forward_rot -> cf_decode_threshold* (unchanged, per canvas) -> cf_unfit_rows [-> cf_track_update | cf_redact_faces | ...]
+ * No trained weights and no labelled set are on hand: no accuracy claim is made; the argument is geometric, as for the fit.
+ *
+ * rot in {0, 90, 180, 270} is the CLOCKWISE turn that makes the stored frame F (h x w) upright: a display-matrix rotation,
+ * cv2.ROTATE_90_CLOCKWISE for 90.  The upright view U has (hu, wu):
+ *   rot   0: (h, w)  U[y][x] = F[y][x]                    numpy: F
+ *   rot  90: (w, h)  U[y][x] = F[h-1-x][y]                numpy: np.rot90(F, -1)
+ *   rot 180: (h, w)  U[y][x] = F[h-1-y][w-1-x]            numpy: np.rot90(F, 2)
+ *   rot 270: (w, h)  U[y][x] = F[x][w-1-y]                numpy: np.rot90(F, 1)
+ * Canvas: canvas_b is what the statements above make of bgr(U_b), with bgr() the conversion of cf_forward_yuv applied to F, before the
+ * turn (the identity for CF_FRAME_BGR):
+ *   stretch == 0: the fit of cf_forward_fit with the geometry cf_fit_geometry(&fit, hu, wu, H, W): resize to (rh, rw), then pad;
+ *   stretch == 1: rw = W, rh = H, dx = dy = 0: the resize of cf_forward_resized from (hu, wu) to (H, W), no padding.
+ * Rows back (cf_unfit_rows behind cf_forward_rot): kept or dropped exactly as behind cf_forward_fit -- finite corners and the float32
+ * centre inside the content, in canvas coordinates.  With, in float64, in this order and without contraction,
+ *   ux(x) = ((double)x - dx) * ((double)wu / rw),   uy(y) = ((double)y - dy) * ((double)hu / rh),
+ * a point (x, y) of the canvas maps to (X, Y) of the stored frame; the difference is taken in float64 and rounded to float32 once:
+ *   rot   0: X = ux(x)            Y = uy(y)
+ *   rot  90: X = uy(y)            Y = (h-1) - ux(x)
+ *   rot 180: X = (w-1) - ux(x)    Y = (h-1) - uy(y)
+ *   rot 270: X = (w-1) - uy(y)    Y = ux(x)
+ * (h-1 and w-1 are the index map above; the decode's own "+1" widths treat coordinates as pixel indices).  The five landmarks are
+ * mapped point by point in their order: a rotation keeps handedness, left and right are not swapped.  The box is an ASSIGNMENT of
+ * mapped corners, never a min / max, so a signed zero or an inverted box of untrained weights cannot make the result ambiguous:
+ *   rot  90: X1 = X(., y1)  Y1 = Y(x2, .)  X2 = X(., y2)  Y2 = Y(x1, .)
+ *   rot 180: X1 = X(x2, .)  Y1 = Y(., y2)  X2 = X(x1, .)  Y2 = Y(., y1)
+ *   rot 270: X1 = X(., y2)  Y1 = Y(x1, .)  X2 = X(., y1)  Y2 = Y(x2, .)
+ * The score is copied; compaction, counts and flags as behind cf_forward_fit.  With rot == 0 and stretch == 0 the canvases and the rows
+ * are those of cf_forward_fit + cf_unfit_rows, bit for bit (the same kernels).
+ * Not covered: mirrored orientations (the other four EXIF codes; they need the landmark swap of the flip merge); a rot per frame within
+ * one call (one camera, one mount: group the frames per call); a rotated tiled forward; probing the orientation.  The labels
+ * cf_draw_faces paints are upright in the STORED frame, so a viewer of the upright video sees them turned. */
+typedef struct cf_rot_opts {
+    int32_t rot;                 /* 0 | 90 | 180 | 270: the clockwise turn that makes the stored frame upright */
+    int32_t stretch;             /* 1: the upright view is stretched to (H, W) and `fit` is only validated; 0: it is fitted by `fit` */
+    cf_fit_opts fit;
+} cf_rot_opts;                   /* 20 bytes */
+/* The geometry of the upright view in the canvas, as stated above; host only.  CF_EINVAL (cf_op_last_error names the value) for NULL
+ * opts or g, a rot outside the four, a stretch outside {0, 1}, and whatever cf_fit_geometry refuses; *g is written on success only. */
+int cf_rot_geometry(const cf_rot_opts* opts, int h, int w, int H, int W, cf_fit_geom* g);
+/* B stored frames of h x w in `format` -> the B canvases stated above -> forward.  Formats, planes, pitches, in_on_device, alignment and
+ * the staging of host frames exactly as for cf_forward_fit, and every check of it, plus CF_EINVAL before any GPU work, the value named
+ * in cf_last_error, for a rot outside the four or a stretch outside {0, 1} (ctx == NULL: the arguments are still checked first,
+ * cf_op_last_error names the cause).  A quarter turn is one launch (per 64 frames) whose taps coalesce along the stored rows; every tap
+ * lies inside the frame, pitch padding is never read; the frames are not modified.  The context remembers rot, the geometry and the
+ * stored frame's size for cf_unfit_rows until any other forward or upload; cf_unfit_rows then leaves "B frames of (h, w)" for the
+ * consumers with the same state rules and the same CF_ESTATE answers as behind cf_forward_fit.  cf_set_flip_test, cf_get_resized_input
+ * and cf_align_faces see the canvases; cf_merge_tiles behind it is CF_ESTATE. */
+int cf_forward_rot(cf_ctx* ctx, const cf_rot_opts* opts, int format, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w,
+                   int pitch0, int pitch1);
+
 /* ---- face tracks across video frames: cover faces through detection dropouts -----------------
  * Every entry point above treats a frame as if it were the only one: the frame in which a face scores just under the threshold goes out
  * uncovered.  A cf_tracker associates the rows of each frame with the tracks of the frames before, on the device, and hands the
@@ -1334,6 +1393,14 @@ int cf_op_fit(int device, const cf_fit_opts* opts, int format, const cf_yuv_plan
  * B * max(rows, max_out) <= 2^24; the option and size checks of cf_fit_geometry, before any device is touched; nothing is written on
  * refusal. */
 int cf_op_unfit(int device, const cf_fit_opts* opts, int B, int h, int w, int H, int W, const float* dets_net, const float* scores,
+                const float* lms_net, const int32_t* counts, int rows, int max_out, float* dets, float* lms, int32_t* out_counts,
+                int32_t* flags);
+/* The kernels of cf_forward_rot and of the cf_unfit_rows behind it alone, on host frames and host tables: cf_op_fit and cf_op_unfit with
+ * the turn and the stretch of `opts` (h x w is the STORED frame), the same shapes, limits and copies; the checks of cf_forward_rot and
+ * cf_rot_geometry before any device is touched; nothing is written on refusal. */
+int cf_op_rot(int device, const cf_rot_opts* opts, int format, const cf_yuv_planes* host_frames, int B, int h, int w, int pitch0,
+              int pitch1, int H, int W, uint8_t* canvas);
+int cf_op_unrot(int device, const cf_rot_opts* opts, int B, int h, int w, int H, int W, const float* dets_net, const float* scores,
                 const float* lms_net, const int32_t* counts, int rows, int max_out, float* dets, float* lms, int32_t* out_counts,
                 int32_t* flags);
 /* The mirror kernel of the flip test alone (cf_set_flip_test), on a host batch: x holds B network inputs of in_format (CF_IN_U8_HWC_BGR:

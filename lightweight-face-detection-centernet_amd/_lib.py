@@ -54,6 +54,7 @@ EXPORTS = (
     "cf_draw_faces", "cf_op_draw", "cf_draw_layout",
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
     "cf_fit_geometry", "cf_forward_fit", "cf_unfit_rows", "cf_op_fit", "cf_op_unfit",
+    "cf_rot_geometry", "cf_forward_rot", "cf_op_rot", "cf_op_unrot",
     "cf_set_flip_test", "cf_op_mirror", "cf_op_flip_heads",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_create_weak", "cf_op_track_weak",
@@ -238,6 +239,19 @@ def fit_opts(anchor="center", upscale=True, fill=(0, 0, 0)):
     if len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
         raise ValueError("fill must be three bytes B, G, R, got %r" % (fill,))
     return FitOpts(int(anchor), int(upscale), (C.c_uint8 * 4)(*fill, 0))
+
+
+class RotOpts(C.Structure):
+    """cf_rot_opts: the clockwise turn that makes the stored frame upright / stretch the upright view instead of fitting it / the fit."""
+    _fields_ = [("rot", C.c_int32), ("stretch", C.c_int32), ("fit", FitOpts)]
+
+
+def rot_opts(rot=0, fit=None):
+    """RotOpts for a turn of ``rot`` clockwise degrees (the library validates the value).  ``fit`` = None: the upright view is stretched
+    to the canvas; True: fitted with the default options; a dict: the keywords of ``fit_opts``."""
+    if fit is None or fit is False:
+        return RotOpts(int(rot), 1, fit_opts())
+    return RotOpts(int(rot), 0, fit_opts(**({} if fit is True else dict(fit))))
 
 
 class TrackOpts(C.Structure):
@@ -573,6 +587,10 @@ def lib():
         L.cf_unfit_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.cf_op_fit.argtypes = [C.c_int, C.POINTER(FitOpts), C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
         L.cf_op_unfit.argtypes = [C.c_int, C.POINTER(FitOpts)] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
+        L.cf_rot_geometry.argtypes = [C.POINTER(RotOpts)] + [C.c_int] * 4 + [C.POINTER(FitGeom)]
+        L.cf_forward_rot.argtypes = [C.c_void_p, C.POINTER(RotOpts), C.c_int, C.c_void_p] + [C.c_int] * 6
+        L.cf_op_rot.argtypes = [C.c_int, C.POINTER(RotOpts), C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+        L.cf_op_unrot.argtypes = [C.c_int, C.POINTER(RotOpts)] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
         L.cf_set_flip_test.argtypes = [C.c_void_p, C.c_int]
         L.cf_op_mirror.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]
         L.cf_op_flip_heads.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2

@@ -520,6 +520,24 @@ class Engine(object):
         self._chk(self._L.cf_forward_fit(self._h, C.byref(o), f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1))
         self.last_B = B
 
+    def forward_rot_enqueue(self, frames, fmt="bgr", rot=0, *, fit=None, on_device=False, h=None, w=None, pitch0=None, pitch1=None):
+        """Detect upright in frames that are STORED turned (a corridor-mode camera, phone video whose turn lives in the container's
+        display matrix): fill the network's canvases from the upright view of every frame and run them as one batch
+        (``cf_forward_rot``).  ``rot``: the clockwise turn -- 0, 90, 180 or 270 -- that makes the stored frame upright
+        (``cv2.ROTATE_90_CLOCKWISE`` for 90).  ``fit`` None: the upright view is stretched to (H, W) like ``forward_resized``; True, or a
+        dict with anchor, upscale and / or fill: it is fitted like ``forward_fit_enqueue``.  ``frames`` and the ``on_device`` form as
+        there; they are only read.  A ``decode_threshold`` then gives the rows in canvas coordinates and ``unfit_rows`` those in the
+        pixels of the STORED frame, where ``redact_faces``, ``draw_faces``, ``align_faces_frame`` and the tracker take them.  One ``rot``
+        per call; mirrored orientations and a rotated tiled forward are not covered.  No accuracy claim is made: the argument is geometric."""
+        f = _lib.frame_format(fmt)
+        o = _lib.rot_opts(rot, fit)
+        if on_device:
+            tab, B, h, w, pitch0, pitch1 = _lib.device_input_planes("forward_rot_enqueue", frames, f, h, w, pitch0, pitch1)
+        else:
+            tab, B, h, w, pitch0, pitch1, self._last.keep = _lib.frame_planes(frames, fmt, writable=False)
+        self._chk(self._L.cf_forward_rot(self._h, C.byref(o), f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1))
+        self.last_B = B
+
     def unfit_rows(self, max_out=1024):
         """Per-frame detections of the last fitted forward in frame pixels (``cf_unfit_rows``, host form): the rows the preceding
         ``decode_threshold`` kept -- in canvas coordinates, whatever ``set_rescale`` says -- whose corners are finite and whose centre
@@ -1400,17 +1418,18 @@ class CenterFace(object):
         return _Late(lookback, bool(flush), [[] for _ in range(n)])
 
     def _plan(self, frames, fmt, take, *, tiled=False, tile=None, overlap=None, with_full=True, merge=("ios", 0.5, 2.0), fit=None, tracker=None,
-              follow=None, detect=True, scenes=None, lookback=None, flush=False, cover=None, draw=None):
+              follow=None, detect=True, scenes=None, lookback=None, flush=False, cover=None, draw=None, rotate=0):
         """The plan of a public product method from the keyword arguments they share (``fit``: what ``_fit_options`` made of it;
-        ``cover`` / ``draw``: the options of that step).  ``fmt`` None: BGR images.  ``take`` says what the steps in frame space work on:
+        ``cover`` / ``draw``: the options of that step; ``rotate``: the clockwise turn that makes the stored frames upright, 0 = none).  ``fmt`` None: BGR images.  ``take`` says what the steps in frame space work on:
         'copy' -- a new array, which the call returns (the inputs stay untouched); 'array' -- the frames as one uint8 array of the size
         this instance was built for, unless they are fitted or tiled; 'given' -- the frames as they are (fitted or tiled only).  The
         forward reads that array too, except on the untiled path of 'copy', which takes the input in ``_input_form``.  Refuses, in this
         order and before any engine call: what ``_lookback`` refuses, frames of the wrong form, a source that cannot be had (the
         instance's size, ``max_batch`` below the tiles of a frame), what ``_follow`` and ``_scene`` refuse."""
+        rotate = self._rotation(rotate, tiled) if rotate else 0                  # (0: the plan of before, nothing of it is reached)
         eng = self.engine
         late = self._lookback(lookback, flush, tracker, len(frames))
-        fmt_, plain, per, rows = "bgr" if fmt is None else fmt, not tiled and fit is None, eng.max_batch, _RESCALE
+        fmt_, plain, per, rows = "bgr" if fmt is None else fmt, not tiled and fit is None and not rotate, eng.max_batch, _RESCALE
         if take == "copy" and plain and fmt is not None:                          # 4:2:0 frames of the instance's size go up as they are
             src, forward = self._input_form(eng, frames, fmt)
             array = np.stack([np.asarray(f) for f in src])                        # a new array: the inputs stay untouched
@@ -1426,7 +1445,9 @@ class CenterFace(object):
                 raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (array.shape,))
         else:
             array = frames
-        if fit is not None:
+        if rotate:                                                                # (fit None: the upright view is stretched)
+            src, forward, rows = array, lambda chunk: eng.forward_rot_enqueue(chunk, fmt_, rotate, fit=fit), _UNFIT
+        elif fit is not None:
             src, forward, rows = array, lambda chunk: eng.forward_fit_enqueue(chunk, fmt_, **fit), _UNFIT
         elif tiled:
             (forward, per), src, rows = self._tiled_form(array, fmt_, tile, overlap, with_full, cover is not None or draw is not None), array, _MERGE
@@ -1574,7 +1595,7 @@ class CenterFace(object):
             raise ValueError("detect_aligned needs the landmarks: construct CenterFace(..., landmarks=True)")
         return self._run(self._plain(imgs, chips=lambda i, j: self.engine.align_faces(size, **chip_options)))
 
-    def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, fit=None, **chip_options):
+    def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, fit=None, rotate=0, **chip_options):
         """Detection plus the aligned chip of every detection cut from the FRAME ITSELF (``Engine.align_faces_frame``), not from the
         network-sized batch: one (dets, lms, chips) per frame, dets / lms in frame pixels.  ``frames``: BGR uint8 [B,h,w,3]
         (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] ('nv12', 'nv21', 'i420', 'yv12') of the (height, width) this instance was
@@ -1582,11 +1603,12 @@ class CenterFace(object):
         ``detect_yuv`` (floor-divided to frame pixels).  ``tiled=True``: frames of any even size, detected by ``detect_tiled``'s path
         (``tile``, ``overlap``); the chips are those of the merged detections, which are in frame pixels and not floor-divided.
         ``fit``: True, or a dict with anchor, upscale and / or fill: frames of any size, detected by ``detect_fit``'s path instead
-        (frame pixels, not floor-divided); not together with ``tiled``.  ``chip_options``: out, rgb, mean, scale, template."""
+        (frame pixels, not floor-divided); not together with ``tiled``.  ``rotate``: as ``anonymize`` -- the similarity is fitted to the
+        landmarks, so the chips of a turned frame come out upright.  ``chip_options``: out, rgb, mean, scale, template."""
         fit = self._fit_options(fit, tiled)
         if not self.landmarks:
             raise ValueError("detect_aligned_frames needs the landmarks: construct CenterFace(..., landmarks=True)")
-        plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit)
+        plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit, rotate=rotate)
         return self._run(plan._replace(chips=lambda i, j: self.engine.align_faces_frame(plan.frames[i:j], fmt, size, **chip_options)))
 
     def _tiled_form(self, frames, fmt, tile, overlap, with_full, writable):
@@ -1602,6 +1624,17 @@ class CenterFace(object):
             raise ValueError("%d tiles per frame need max_batch >= %d (this instance has %d)" % (len(rects), len(rects), self.engine.max_batch))
         return lambda chunk: self.engine.forward_tiles_enqueue(chunk, rects, fmt), per
 
+    @staticmethod
+    def _rotation(rotate, tiled=False):
+        """The ``rotate`` argument of the product paths: the clockwise turn -- 0, 90, 180 or 270 -- that makes the STORED frames upright
+        (``Engine.forward_rot_enqueue``; the rows come back in the stored frame's pixels).  ``rotate`` and ``tiled=True`` exclude each
+        other."""
+        if rotate not in (0, 90, 180, 270):
+            raise ValueError("rotate must be 0, 90, 180 or 270 (clockwise degrees), got %r" % (rotate,))
+        if rotate and tiled:
+            raise ValueError("rotate= and tiled=True exclude each other: a rotated tiled forward is not covered")
+        return int(rotate)
+
     def _fit_options(self, fit, tiled=False):
         """The ``fit`` argument of the product paths -> None, or the options of ``Engine.forward_fit_enqueue``: ``fit`` None / False,
         True (the defaults) or a dict with anchor, upscale and / or fill.  ``fit`` and ``tiled=True`` exclude each other."""
@@ -1616,7 +1649,7 @@ class CenterFace(object):
         return o
 
     def detect_fit(self, frames, fmt="bgr", *, anchor="center", upscale=True, fill=(0, 0, 0), redact=None, tracker=None, follow=None, detect=True,
-                   scenes=None, lookback=None, flush=False):
+                   scenes=None, lookback=None, flush=False, rotate=0):
         """Detection of frames of another size -- or shape -- than the network input WITHOUT the stretch of ``detect_batch``: every frame
         is resized on the device with its aspect ratio kept and pasted into the network's canvas (``Engine.forward_fit_enqueue``:
         ``anchor``, ``upscale``, ``fill``), and the rows whose centre lies in the content are mapped back (``Engine.unfit_rows``).
@@ -1624,14 +1657,15 @@ class CenterFace(object):
         Returns (dets [n,5], lms [n,10]) per frame (``dets`` alone without landmarks), in FRAME pixels, not floor-divided.  No accuracy
         claim is made: there are no trained weights and no labelled set here; the reference's data pipeline fits and pads likewise
         (dataset/dataset.py:114-134).  ``redact``, ``tracker``, ``follow``, ``detect``, ``scenes``, ``lookback`` and ``flush``: as
-        ``detect_tiled``."""
+        ``detect_tiled``.  ``rotate``: 90, 180 or 270 -- the clockwise turn that makes the STORED frames upright: the upright view is
+        fitted (``Engine.forward_rot_enqueue``) and the rows come back in the stored frame's pixels; one turn per call."""
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         fit = self._fit_options(dict(anchor=anchor, upscale=upscale, fill=fill))
         if lookback is not None and redact is None:
             raise ValueError("lookback= needs redact=")                         # (without it there is nothing to delay)
         return self._run(self._plan(frames, fmt, "given", fit=fit, tracker=tracker, follow=follow, detect=detect, scenes=scenes, lookback=lookback,
-                                    flush=flush, cover=redact))
+                                    flush=flush, cover=redact, rotate=rotate))
 
     def detect_tiled(self, frames, tile=None, overlap=None, fmt="bgr", *, with_full=True, metric="ios", thresh=0.5, edge=2.0, redact=None,
                      tracker=None, follow=None, detect=True, scenes=None, lookback=None, flush=False):
@@ -1657,7 +1691,7 @@ class CenterFace(object):
                                     tracker=tracker, follow=follow, detect=detect, scenes=scenes, lookback=lookback, flush=flush, cover=redact))
 
     def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None,
-                  flush=False, **options):
+                  flush=False, rotate=0, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
         cell, scale, fill) or, with ``mode='blur'``, blurred (``Engine.blur_faces``; shape, radius, scale), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
@@ -1690,25 +1724,29 @@ class CenterFace(object):
         hits, misses) that became ready: empty while stream k warms up, one item in the steady state, and with ``flush=True`` (the end of
         the video: the stream is drained) up to ``depth + 1``; dets and lms are the covered rows, in the tracker's space, back-filled ones
         with hits 0 and misses = the distance.  The streams of a call must stand at one fill level (ValueError).  With the defaults every
-        call does what it did without them."""
+        call does what it did without them.  ``rotate``: 90, 180 or 270 -- the clockwise turn that makes the STORED frames upright (a
+        corridor-mode camera, phone video): the network sees the upright view (``Engine.forward_rot_enqueue``; stretched to the network
+        input, or fitted with ``fit``), frames of any size; detections and redaction are in the pixels of the stored frame, not
+        floor-divided; not together with ``tiled``; one turn per call; no accuracy claim is made."""
         return self._anonymize(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
-                               scenes=scenes, lookback=lookback, flush=flush)
+                               scenes=scenes, lookback=lookback, flush=flush, rotate=rotate)
 
     def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
-                      scenes=None, lookback=None, flush=False, **options):
+                      scenes=None, lookback=None, flush=False, rotate=0, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
         [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow``,
-        ``fit``, ``detect``, ``scenes``, ``lookback`` and ``flush``: as ``anonymize``."""
+        ``fit``, ``detect``, ``scenes``, ``lookback``, ``flush`` and ``rotate``: as ``anonymize``."""
         return self._anonymize(frames, fmt, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
-                               scenes=scenes, lookback=lookback, flush=flush)
+                               scenes=scenes, lookback=lookback, flush=flush, rotate=rotate)
 
-    def _anonymize(self, frames, fmt, options, *, tiled, fit, **shared):
+    def _anonymize(self, frames, fmt, options, *, tiled, fit, rotate=0, **shared):
         """The body of ``anonymize`` (``fmt`` None: BGR images) and ``anonymize_yuv``: the copy of the frames is covered."""
         _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
-        return self._run(self._plan(frames, fmt, "copy", tiled=tiled, fit=self._fit_options(fit, tiled), cover=options, **shared))
+        rotate = self._rotation(rotate, tiled) if rotate else 0
+        return self._run(self._plan(frames, fmt, "copy", tiled=tiled, fit=self._fit_options(fit, tiled), cover=options, rotate=rotate, **shared))
 
     def best_shots(self, frames, fmt="bgr", *, tracker, shots, tiled=False, tile=None, overlap=None, fit=None, follow=None, detect=True,
-                   flush=False, template=None, scenes=None):
+                   flush=False, template=None, scenes=None, rotate=0):
         """One chip per appearance of a person: detection, tracking and best-shot selection of ``frames`` -- BGR uint8 [B,h,w,3]
         (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] -- where image k of a call is the next frame of stream k of ``tracker`` (a
         ``Tracker``) and of ``shots`` (a ``BestShots``), as in ``anonymize(tracker=)``: a video is fed one call per frame, n cameras n
@@ -1718,13 +1756,14 @@ class CenterFace(object):
         after the last chunk the finished entries of the call's streams are collected -- ``flush=True`` finishes every live track first
         (the end of the video).  Returns, per stream, the list of finished shots in finishing order: dicts with ``id``, ``quality``,
         ``chip`` [size, size, 3], ``det`` [5], ``lms`` [10] (the row of the best frame, in the tracker's space) and ``record`` (the eight
-        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  ``fit``: as ``anonymize`` (``detect_fit``'s path).  The quality formula is this project's choice; no accuracy claim is made for it."""
+        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  ``fit``: as ``anonymize`` (``detect_fit``'s path).  ``rotate``: as ``anonymize``; the chips are fitted to the landmarks, so they come out upright.  The quality formula is this project's choice; no accuracy claim is made for it."""
         fit = self._fit_options(fit, tiled)
         if not self.landmarks:
             raise ValueError("best_shots needs the landmarks: construct CenterFace(..., landmarks=True)")
         if tracker is None or shots is None:
             raise ValueError("best_shots needs tracker= and shots=")
-        plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect, scenes=scenes)
+        plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect, scenes=scenes,
+                          rotate=rotate)
         sink = []
         self._run(plan._replace(best=_Best(shots, plan.frames, fmt, template, bool(flush), sink)))
         if not sink:
@@ -1748,29 +1787,31 @@ class CenterFace(object):
         return o
 
     def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None,
-                 flush=False, **options):
+                 flush=False, rotate=0, **options):
         """``detect_batch`` plus the drawing of every detection, what demo.py:15-23 does with cv2 on the host: (frames_out, [(dets, lms),
         ...]) -- frames_out a uint8 [B,h,w,3] COPY of ``imgs`` with box outlines, landmark dots and a label painted on the device
         (``Engine.draw_faces``; ``options`` as there, colours as BGR triples).  ``tiled``, ``tile``, ``overlap`` and ``tracker`` as
         ``anonymize``: with a tracker the label is the track id and the tracks held through a dropout are drawn too, dashed, in
         ``held_color``.  ``fit``, ``follow``, ``detect`` and ``scenes``: as ``anonymize``.  ``lookback`` and ``flush``: as ``anonymize`` --
-        the delayed frames are drawn, a back-filled row as a held one (dashed, in ``held_color``), and the return is the lists."""
+        the delayed frames are drawn, a back-filled row as a held one (dashed, in ``held_color``), and the return is the lists.
+        ``rotate``: as ``anonymize``; the labels are upright in the STORED frame, so a viewer of the upright video sees them turned."""
         return self._annotate(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
-                              scenes=scenes, lookback=lookback, flush=flush)
+                              scenes=scenes, lookback=lookback, flush=flush, rotate=rotate)
 
     def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
-                     scenes=None, lookback=None, flush=False, **options):
+                     scenes=None, lookback=None, flush=False, rotate=0, **options):
         """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
         in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``fit``, ``scenes``, ``lookback`` and
-        ``flush``: as ``annotate``."""
+        ``flush`` and ``rotate``: as ``annotate``."""
         return self._annotate(frames, fmt, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
-                              scenes=scenes, lookback=lookback, flush=flush)
+                              scenes=scenes, lookback=lookback, flush=flush, rotate=rotate)
 
-    def _annotate(self, frames, fmt, options, *, tiled, fit, tracker, **shared):
+    def _annotate(self, frames, fmt, options, *, tiled, fit, tracker, rotate=0, **shared):
         """The body of ``annotate`` (``fmt`` None: BGR images) and ``annotate_yuv``: the copy of the frames is drawn into."""
         fit = self._fit_options(fit, tiled)
+        rotate = self._rotation(rotate, tiled) if rotate else 0
         return self._run(self._plan(frames, fmt, "copy", tiled=tiled, fit=fit, tracker=tracker, draw=self._draw_options(options, tracker, fmt is not None),
-                                    **shared))
+                                    rotate=rotate, **shared))
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]

@@ -21,11 +21,13 @@
 //     kept iff dx <= cx < dx + rw and dy <= cy < dy + rh;
 //   * else X = (float)(((double)x - (double)dx) * ((double)w / (double)rw)), Y likewise with dy and h / rh, for the four corners and the
 //     ten landmark values (float64 in this order, no contraction: the file is built with -ffp-contract=off); the score is copied.
-// The compaction is a prefix sum, never an atomic: the order is the decode's.
+// The compaction is a prefix sum, never an atomic: the order is the decode's.  Behind a rotated forward (cf_rot.hip) the same kernel maps
+// through the turn as well: unfit_rows_kernel<ROT>, whose ROT == 0 instance is the map above.
 #include "cf_common.h"
 #include "cf_kernels.h"
 #include "cf_cvresize.h"
 #include "cf_yuvmath.h"
+#include "cf_fitpx.h"
 #include <string>
 
 namespace cf {
@@ -49,22 +51,7 @@ __device__ __forceinline__ uint32_t fit_tap(const uint8_t* p0, const uint8_t* p1
     }
 }
 
-// Three values 0..255 -> B | G << 8 | R << 16 by byte selection from whole dwords (two v_perm_b32).  Written as shifts and ORs, the
-// clamp of cv_linear_vpass next to the packing is selected as gfx950's v_ashr_pk_u8_i32, whose result came back from the device with
-// foreign bits above bit 15 in this kernel (they reach R and the next pixel's B); a byte selection takes bits 7:0 of each value and
-// nothing else.
-__device__ __forceinline__ uint32_t pack_bgr(uint32_t b, uint32_t g, uint32_t r) {
-    const uint32_t bg = __builtin_amdgcn_perm(g, b, 0x0c0c0400u);       // byte 0 = b[7:0], byte 1 = g[7:0], bytes 2, 3 = 0
-    return __builtin_amdgcn_perm(r, bg, 0x0c040100u);                   // bytes 0, 1 = bg[15:0], byte 2 = r[7:0], byte 3 = 0
-}
-
-__device__ __forceinline__ void fit_store(uint8_t* row, const uint32_t (&p)[4]) {
-    uint32_t* o = reinterpret_cast<uint32_t*>(row);
-    o[0] = p[0] | (p[1] << 24);
-    o[1] = (p[1] >> 8) | (p[2] << 16);
-    o[2] = (p[2] >> 16) | (p[3] << 8);
-}
-
+// (pack_bgr and fit_store: cf_fitpx.h, shared with cf_rot.hip)
 template <int SRC, bool VF>
 __global__ void __launch_bounds__(256) fit_frames_kernel(FitPtrs tab, uint8_t* dst, cf_fit_geom g, uint32_t fill, int h, int w, int pitch0,
                                                          int pitch1, int H, int W) {
@@ -120,14 +107,25 @@ __global__ void __launch_bounds__(256) fit_frames_kernel(FitPtrs tab, uint8_t* d
 }
 
 // One workgroup per image walks its rows in order, 1024 at a time: keep flag, ballot, the 16 wave counts through LDS, write at
-// base + prefix (as merge_collect_kernel).
+// base + prefix (as merge_collect_kernel).  ROT: the quarter turns of a rotated forward (cf_rot.hip has the statement); p.h x p.w is the
+// STORED frame, the content of the canvas its upright view of hu x wu.  ROT == 0 is the unfit above.
+template <int ROT>
 __global__ void __launch_bounds__(1024) unfit_rows_kernel(UnfitParams p) {
     __shared__ uint32_t wave_cnt[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int count = p.counts[b], n = min(max(count, 0), p.rows);
     const float xlo = (float)p.g.dx, xhi = (float)(p.g.dx + p.g.rw), ylo = (float)p.g.dy, yhi = (float)(p.g.dy + p.g.rh);
-    const double sx = (double)p.w / (double)p.g.rw, sy = (double)p.h / (double)p.g.rh;
+    const int hu = (ROT & 1) ? p.w : p.h, wu = (ROT & 1) ? p.h : p.w;
+    const double sx = (double)wu / (double)p.g.rw, sy = (double)hu / (double)p.g.rh;
     const double ox = (double)p.g.dx, oy = (double)p.g.dy;
+    // a point of the canvas -> the stored frame: the upright view's pixel first, then the index map of the turn; the difference is
+    // taken in float64 and rounded once
+    auto turn = [&](float x, float y, float& X, float& Y) {
+        const double ux = ((double)x - ox) * sx, uy = ((double)y - oy) * sy;
+        if constexpr (ROT == 1) { X = (float)uy; Y = (float)((double)(p.h - 1) - ux); }
+        else if constexpr (ROT == 2) { X = (float)((double)(p.w - 1) - ux); Y = (float)((double)(p.h - 1) - uy); }
+        else { X = (float)((double)(p.w - 1) - uy); Y = (float)ux; }
+    };
     uint32_t base = 0;
     for (int j0 = 0; j0 < n; j0 += 1024) {               // (n is uniform over the workgroup: so is the trip count)
         const int row = j0 + tid;
@@ -151,16 +149,29 @@ __global__ void __launch_bounds__(1024) unfit_rows_kernel(UnfitParams p) {
         if (keep && pos < (uint32_t)p.max_out) {
             const size_t d = (size_t)b * p.max_out + pos;
             float o[4];
+            if constexpr (ROT == 0) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = (float)(((double)c[k] - ((k & 1) ? oy : ox)) * ((k & 1) ? sy : sx));
+                for (int k = 0; k < 4; ++k) o[k] = (float)(((double)c[k] - ((k & 1) ? oy : ox)) * ((k & 1) ? sy : sx));
+            } else if constexpr (ROT == 2) {             // the box is an assignment of mapped corners, never a min / max
+                turn(c[2], c[3], o[0], o[1]); turn(c[0], c[1], o[2], o[3]);
+            } else if constexpr (ROT == 1) {
+                turn(c[2], c[1], o[0], o[1]); turn(c[0], c[3], o[2], o[3]);
+            } else {
+                turn(c[0], c[3], o[0], o[1]); turn(c[2], c[1], o[2], o[3]);
+            }
             *reinterpret_cast<float4*>(p.corners + d * 4) = make_float4(o[0], o[1], o[2], o[3]);
             float* dd = p.dets + d * 5;
             dd[0] = o[0]; dd[1] = o[1]; dd[2] = o[2]; dd[3] = o[3];
             dd[4] = p.scores[src * p.score_stride];
             const float* l = p.lms_net + src * 10;
             float* dl = p.lms + d * 10;
+            if constexpr (ROT == 0) {
 #pragma unroll
-            for (int k = 0; k < 10; ++k) dl[k] = (float)(((double)l[k] - ((k & 1) ? oy : ox)) * ((k & 1) ? sy : sx));
+                for (int k = 0; k < 10; ++k) dl[k] = (float)(((double)l[k] - ((k & 1) ? oy : ox)) * ((k & 1) ? sy : sx));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) turn(l[2 * k], l[2 * k + 1], dl[2 * k], dl[2 * k + 1]);      // point by point, order kept
+            }
         }
         base += total;
     }
@@ -220,11 +231,19 @@ hipError_t launch_fit_frames(hipStream_t s, int format, const void* const* plane
     return hipSuccess;
 }
 
-hipError_t launch_unfit_rows(hipStream_t s, const UnfitParams& p) {
-    if (p.B < 1 || p.rows < 1 || p.max_out < 1 || p.h < 1 || p.w < 1 || p.g.rw < 1 || p.g.rh < 1 || p.score_stride < 1 || !p.dets_net || !p.scores ||
-        !p.lms_net || !p.counts || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
+hipError_t launch_unfit_rows(hipStream_t s, const UnfitParams& p) { return launch_unrot_rows(s, p, 0); }
+
+// rot: 0, 90, 180, 270 (checked by the caller); p.g places the UPRIGHT view of the p.h x p.w frames
+hipError_t launch_unrot_rows(hipStream_t s, const UnfitParams& p, int rot) {
+    if ((rot != 0 && rot != 90 && rot != 180 && rot != 270) || p.B < 1 || p.rows < 1 || p.max_out < 1 || p.h < 1 || p.w < 1 || p.g.rw < 1 || p.g.rh < 1 ||
+        p.score_stride < 1 || !p.dets_net || !p.scores || !p.lms_net || !p.counts || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(unfit_rows_kernel, dim3(p.B), dim3(1024), 0, s, p);
+    switch (rot) {
+        case 90: hipLaunchKernelGGL(unfit_rows_kernel<1>, dim3(p.B), dim3(1024), 0, s, p); break;
+        case 180: hipLaunchKernelGGL(unfit_rows_kernel<2>, dim3(p.B), dim3(1024), 0, s, p); break;
+        case 270: hipLaunchKernelGGL(unfit_rows_kernel<3>, dim3(p.B), dim3(1024), 0, s, p); break;
+        default: hipLaunchKernelGGL(unfit_rows_kernel<0>, dim3(p.B), dim3(1024), 0, s, p); break;
+    }
     return hipGetLastError();
 }
 

@@ -504,6 +504,16 @@ struct UnfitParams {
 };
 hipError_t launch_unfit_rows(hipStream_t s, const UnfitParams& p);
 
+// Rotated sources (cf_rot.hip; the statement is in include/centerface_hip.h).  rot_geometry: the placement of the UPRIGHT view of an
+// h x w frame (host only; o has passed rot_check).  rot_check: nullptr, or what is wrong with the turn, the options and the frames.
+// launch_rot_frames: the fit of the upright views, dst [B][H][W][3] as launch_fit_frames; rot == 0 IS launch_fit_frames.
+// launch_unrot_rows (cf_fit.hip): the unfit behind it, p.g from rot_geometry, p.h x p.w the stored frame; rot == 0 is launch_unfit_rows.
+int rot_geometry(const cf_rot_opts* o, int h, int w, int H, int W, cf_fit_geom* g);
+const char* rot_check(std::string& why, const cf_rot_opts* o, int format, int B, int h, int w, int pitch0, int pitch1, int H, int W);
+hipError_t launch_rot_frames(hipStream_t s, int rot, int format, const void* const* planes, int B, int h, int w, int pitch0, int pitch1,
+                             const cf_fit_geom& g, const uint8_t* fill, uint8_t* dst, int H, int W);
+hipError_t launch_unrot_rows(hipStream_t s, const UnfitParams& p, int rot);
+
 // Flip test (cf_flip.hip; the statement is in include/centerface_hip.h).  mirror_check: nullptr, or what is wrong with the format and sizes
 // of a batch to mirror (the text lives in `why`; host only).  launch_mirror_batch: dst holds 2B network inputs of in_format (uint8
 // [.][H][W][3] or float32 [.][3][H][W]; 16-byte aligned); images B .. 2B-1 become images 0 .. B-1 of src with their columns reversed and,

@@ -1055,6 +1055,66 @@ int cf_op_unfit(int device, const cf_fit_opts* o, int B, int h, int w, int H, in
     return sc.result("cf_op_unfit");
 }
 
+// nullptr, or what is wrong with the turn, the options and the sizes of a rotated geometry (the text lives in `why`)
+static const char* rot_geometry_check(std::string& why, const cf_rot_opts* o, int h, int w, int H, int W) {
+    if (const char* bad = rot_check(why, o, CF_FRAME_BGR, 1, h, w, 3 * w, 0, 4, 4)) return bad;
+    if (H < 1 || W < 1) { why = "H=" + std::to_string(H) + ", W=" + std::to_string(W) + " must be at least 1"; return why.c_str(); }
+    return nullptr;
+}
+
+int cf_rot_geometry(const cf_rot_opts* o, int h, int w, int H, int W, cf_fit_geom* g) {
+    std::string why;
+    const char* bad = rot_geometry_check(why, o, h, w, H, W);
+    if (!bad && !g) bad = "null output";
+    if (bad) return fail("cf_rot_geometry", bad);
+    return rot_geometry(o, h, w, H, W, g);
+}
+
+// The kernel of cf_forward_rot on host frames.
+int cf_op_rot(int device, const cf_rot_opts* o, int format, const cf_yuv_planes* host_frames, int B, int h, int w, int pitch0, int pitch1,
+              int H, int W, uint8_t* canvas) {
+    const void* const* hp = reinterpret_cast<const void* const*>(host_frames);
+    std::string why;
+    const char* bad = rot_check(why, o, format, B, h, w, pitch0, pitch1, H, W);
+    if (!bad) bad = redact_check_planes(format, hp, B, 0, pitch0, pitch1);
+    if (!bad && !canvas) bad = "null output";
+    if (!bad && (long long)B * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
+    cf_fit_geom g{};
+    if (!bad && rot_geometry(o, h, w, H, W, &g)) bad = "no geometry";
+    if (bad) return fail("cf_op_rot", bad);
+    Scope sc(device);
+    const std::vector<const void*> dev = up_planes(sc, format, hp, B, h, pitch0, pitch1);
+    uint8_t* out = sc.out(canvas, (size_t)B * H * W * 3);
+    sc.run([&] { return launch_rot_frames(sc.s, o->rot, format, dev.data(), B, h, w, pitch0, pitch1, g, o->fit.fill, out, H, W); });
+    return sc.result("cf_op_rot");
+}
+
+int cf_op_unrot(int device, const cf_rot_opts* o, int B, int h, int w, int H, int W, const float* dets_net, const float* scores,
+                const float* lms_net, const int32_t* counts, int rows, int max_out, float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+    std::string why;
+    const char* bad = rot_geometry_check(why, o, h, w, H, W);
+    if (!bad && (!dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags)) bad = "null argument";
+    if (!bad && (B < 1 || rows < 1 || max_out < 1)) bad = "B, rows and max_out must be at least 1";
+    if (!bad && (long long)B * std::max(rows, max_out) > (1 << 24)) bad = "more than 2^24 rows";
+    cf_fit_geom g{};
+    if (!bad && rot_geometry(o, h, w, H, W, &g)) bad = "no geometry";
+    if (bad) return fail("cf_op_unrot", bad);
+    Scope sc(device);
+    const size_t n = (size_t)B * rows, mo = (size_t)B * max_out;
+    UnfitParams p{};
+    p.g = g; p.h = h; p.w = w; p.B = B;
+    p.dets_net = sc.in(dets_net, n * 4);
+    p.scores = sc.in(scores, n); p.score_stride = 1;
+    p.lms_net = sc.in(lms_net, n * 10);
+    p.counts = sc.in(counts, B); p.rows = rows;
+    p.max_out = max_out;
+    p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
+    p.corners = sc.make<float>(mo * 4);
+    p.out_counts = sc.out(out_counts, B); p.flags = sc.out(flags, B);
+    sc.run([&] { return launch_unrot_rows(sc.s, p, o->rot); });
+    return sc.result("cf_op_unrot");
+}
+
 // The mirror kernel of the flip test as the flip forward of a caller's tensor runs it: src -> a 2B batch, whose second half comes back.
 int cf_op_mirror(int device, int in_format, const void* x, int B, int H, int W, void* out) {
     std::string why;

@@ -168,6 +168,7 @@ struct cf_ctx {
     // cf_forward_fit: ft_on = the last forward was a fitted one, of tl_Bf frames of tl_h x tl_w placed by ft_g; cf_unfit_rows leaves its
     // rows where the merge leaves its own (tl, tl_maxout per frame)
     bool ft_on = false; cf_fit_geom ft_g = {0, 0, 0, 0};
+    int ft_rot = 0;                     // cf_forward_rot: the turn beside ft_g (ft_g then places the upright view of the tl_h x tl_w frames)
     struct { DevBuf cand, cand_count, order, mask, dets, lms, corners, counts, flags; } tl;
     struct { DevBuf dets, lms, info, corners, counts, flags; } tk; int tk_M = 0;      // cf_track_update: the tracked rows, tk_M per image
     // cf_track_follow: B > 0 = the rows in tk are the follow's, of B frames in the tracker's space (H x W network input, or -- tiled -- H x W
@@ -1181,7 +1182,7 @@ int forward_run(cf_ctx* c, const void* caller_in, int in_format, int Bcaller) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in.used;      // what cf_align_faces samples
-    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->fo.B = 0; c->lb.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
+    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->ft_rot = 0; c->fo.B = 0; c->lb.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -2121,6 +2122,33 @@ int cf_forward_fit(cf_ctx* c, const cf_fit_opts* o, int format, const cf_yuv_pla
     return CF_OK;
 }
 
+// Rotated forward: cf_forward_fit with the canvases filled from the upright view of the stored frames (cf_rot.hip); rot = 0 and
+// stretch = 0 launch the fit kernel itself.  The context remembers the turn beside the geometry: cf_unfit_rows maps through both.
+int cf_forward_rot(cf_ctx* c, const cf_rot_opts* o, int format, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w, int pitch0,
+                   int pitch1) {
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    std::string text;
+    const char* why = rot_check(text, o, format, B, h, w, pitch0, pitch1, c ? c->H : 4, c ? c->W : 4);
+    if (!why) why = redact_check_planes(format, planes, B, in_on_device, pitch0, pitch1);
+    if (!c) {                                                                // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_forward_rot: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_forward_rot: %s", why);
+    if (B > batch_cap(c))
+        return c->fail(CF_EINVAL, "cf_forward_rot: B=%d exceeds max_batch %d%s", B, batch_cap(c), c->flip ? " (flip test is on: half of max_batch)" : "");
+    cf_fit_geom g{};
+    if (rot_geometry(o, h, w, c->H, c->W, &g)) return c->fail(CF_EINVAL, "cf_forward_rot: no geometry for %d x %d (rot %d) in %d x %d", w, h, o->rot, c->W, c->H);
+    if (int r = forward_begin(c, "cf_forward_rot", B)) return r;
+    uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
+    auto rot = [&](const void* const* pl, int p0, int p1) { return launch_rot_frames(c->stream, o->rot, format, pl, B, h, w, p0, p1, g, o->fit.fill, dst, c->H, c->W); };
+    if (in_on_device) HIPCHK(c, rot(planes, pitch0, pitch1));
+    else if (int r = src_stage_frames(c, "cf_forward_rot", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, rot)) return r;
+    if (int r = forward_run(c, dst, CF_IN_U8_HWC_BGR, B)) return r;
+    c->ft_on = true; c->ft_g = g; c->ft_rot = o->rot; c->tl_Bf = B; c->tl_h = h; c->tl_w = w;
+    return CF_OK;
+}
+
 // The rows of the last threshold decode of a fitted forward, mapped back into frame pixels (cf_fit.hip) on the stream that carried the
 // decode; they land where the merge leaves its rows, and every consumer takes them from there.
 int cf_unfit_rows(cf_ctx* c, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
@@ -2146,7 +2174,7 @@ int cf_unfit_rows(cf_ctx* c, int max_out, float* dets, float* lms, int32_t* coun
     p.dets_net = in.corners; p.scores = in.dets + 4; p.score_stride = 5; p.lms_net = in.lms; p.counts = in.counts; p.rows = in.stride;
     p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
     p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
-    HIPCHK(c, launch_unfit_rows(c->stream, p));
+    HIPCHK(c, launch_unrot_rows(c->stream, p, c->ft_rot));               // (ft_rot == 0: launch_unfit_rows)
     c->stage = ROWS_MERGED; c->tl_maxout = max_out;
     return write_out(c, out_on_device, B, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }

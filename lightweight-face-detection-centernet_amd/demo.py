@@ -62,13 +62,20 @@ def _fit_detector(fit, dtype, flip=False):
     return CenterFace(fit, fit, dtype=dtype, flip_test=flip)
 
 
+def _upright_hw(frame, rotate):
+    """The (height, width) of the upright view of a stored frame that ``rotate`` clockwise degrees make upright."""
+    return (frame.shape[1], frame.shape[0]) if rotate in (90, 270) else (frame.shape[0], frame.shape[1])
+
+
 def anonymize_file(path, out_path, **options):
     """Read one image file, redact every detected face on the device (``CenterFace.anonymize``; ``options``: mode, shape, cell,
     scale, fill, or mode='blur' with shape, radius, scale) and write the result to ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``: sliced
     inference with N x N tiles at native resolution (``CenterFace.detect_tiled``; the image is cropped to even sides), for images much
     larger than N whose small faces a whole-frame resize would lose; the detections are then in image pixels.  ``fit=N``: the image
     goes letterboxed through an N x N context instead of one built for its size; not together with ``tiled``.  ``flip=True``: the
-    detector runs CenterNet's flip test (``CenterFace(flip_test=True)``: about twice the network time; no accuracy claim is made)."""
+    detector runs CenterNet's flip test (``CenterFace(flip_test=True)``: about twice the network time; no accuracy claim is made).
+    ``rotate=N`` (90, 180, 270): the image is STORED turned and N clockwise degrees make it upright -- the detector sees the upright
+    view (``CenterFace.anonymize(rotate=)``), the faces are redacted in the image as stored; not together with ``tiled``."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
@@ -76,6 +83,7 @@ def anonymize_file(path, out_path, **options):
     fit = int(options.pop("fit", 0) or 0)
     dtype = options.pop("dtype", "bf16")
     flip = bool(options.pop("flip", False))
+    rotate = options["rotate"] = int(options.pop("rotate", 0) or 0)
     if fit:
         detector = _fit_detector(fit, dtype, flip)
         options["fit"], options["tiled"] = True, bool(tiled)
@@ -86,7 +94,7 @@ def anonymize_file(path, out_path, **options):
         detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T, flip_test=flip)
         options["tiled"] = True
     else:
-        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype, flip_test=flip)
+        detector = CenterFace(*_upright_hw(frame, rotate), dtype=dtype, flip_test=flip)
     try:
         frames, results = detector.anonymize([frame], **options)
     finally:
@@ -98,7 +106,8 @@ def anonymize_file(path, out_path, **options):
 def annotate_file(path, out_path, **options):
     """demo.py:30-51 (``test_image`` with its drawing loop): read one image file, draw every detection on the device
     (``CenterFace.annotate``: green boxes, red landmark dots, the score as a label; ``options`` as there) and write the result to
-    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``, ``fit=N``, ``flip=True``: as ``anonymize_file``."""
+    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``, ``fit=N``, ``flip=True``, ``rotate=N``: as ``anonymize_file``
+    (the labels are upright in the image as stored)."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
@@ -106,6 +115,7 @@ def annotate_file(path, out_path, **options):
     fit = int(options.pop("fit", 0) or 0)
     dtype = options.pop("dtype", "bf16")
     flip = bool(options.pop("flip", False))
+    rotate = options["rotate"] = int(options.pop("rotate", 0) or 0)
     if fit:
         detector = _fit_detector(fit, dtype, flip)
         options["fit"], options["tiled"] = True, bool(tiled)
@@ -116,7 +126,7 @@ def annotate_file(path, out_path, **options):
         detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T, flip_test=flip)
         options["tiled"] = True
     else:
-        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype, flip_test=flip)
+        detector = CenterFace(*_upright_hw(frame, rotate), dtype=dtype, flip_test=flip)
     try:
         frames, results = detector.annotate([frame], **options)
     finally:
@@ -125,14 +135,15 @@ def annotate_file(path, out_path, **options):
     return results[0]
 
 
-def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False):
+def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False, rotate=0):
     """Read one image file and write the aligned chip of every detected face, cut from the image at its own resolution
     (``CenterFace.detect_aligned_frames``), to ``out_dir``/<image name>_<k>.png.  Returns (detections, the paths written).
-    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides).  ``fit=N``, ``flip=True``: as ``anonymize_file``."""
+    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides).  ``fit=N``, ``flip=True``, ``rotate=N``: as ``anonymize_file``
+    (the chips are fitted to the landmarks, so they come out upright)."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
-    tiled, fit = int(tiled or 0), int(fit or 0)
+    tiled, fit, rotate = int(tiled or 0), int(fit or 0), int(rotate or 0)
     if fit:
         detector = _fit_detector(fit, dtype, flip)
     elif tiled:
@@ -141,9 +152,9 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False
         T = len(ops.tile_grid(frame.shape[0], frame.shape[1], tiled, (tiled // 4) & ~1))
         detector = CenterFace(tiled, tiled, dtype=dtype, max_batch=T, flip_test=flip)
     else:
-        detector = CenterFace(frame.shape[0], frame.shape[1], dtype=dtype, flip_test=flip)
+        detector = CenterFace(*_upright_hw(frame, rotate), dtype=dtype, flip_test=flip)
     try:
-        dets, lms, chips = detector.detect_aligned_frames(frame[None], "bgr", size, tiled=bool(tiled), fit=bool(fit) or None)[0]
+        dets, lms, chips = detector.detect_aligned_frames(frame[None], "bgr", size, tiled=bool(tiled), fit=bool(fit) or None, rotate=rotate)[0]
     finally:
         detector.close()
     os.makedirs(out_dir, exist_ok=True)
@@ -155,7 +166,7 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False
 
 
 def main(argv=None):
-    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]] [--flip]``: print the detections of one image
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]] [--flip] [--rotate N]``: print the detections of one image
     file; with ``--draw`` also write the image with every detection drawn into it (boxes, landmark dots and, unless ``--label none``,
     the score); with
     ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``; or blurred: ``--blur [R]``, R = the
@@ -164,7 +175,9 @@ def main(argv=None):
     faces are found by sliced inference over N x N tiles at native resolution; with ``--fit [N]`` (default 640) the image goes through an
     N x N context letterboxed -- its aspect ratio kept, black padding, the detections mapped back into image pixels -- instead of a
     context built for its size (no accuracy claim is made for it); with ``--flip`` the detector runs CenterNet's flip test -- the image and
-    its mirror in one forward, the heads merged on the device -- at about twice the network time (no accuracy claim is made either)."""
+    its mirror in one forward, the heads merged on the device -- at about twice the network time (no accuracy claim is made either); with ``--rotate N``
+    (90, 180 or 270) the image is taken as STORED turned, N clockwise degrees making it upright: the detector sees the upright view and
+    the detections, the redaction and the drawing are in the pixels of the image as stored (not with ``--tiled``; no accuracy claim)."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("image")
@@ -179,6 +192,8 @@ def main(argv=None):
     ap.add_argument("--fit", type=int, nargs="?", const=640, default=0, metavar="N",
                     help="detect through an N x N context with the image letterboxed (N a multiple of 32; default 640)")
     ap.add_argument("--flip", action="store_true", help="flip test: run the image and its mirror and merge the heads on the device (about twice the network time)")
+    ap.add_argument("--rotate", type=int, default=0, choices=(0, 90, 180, 270), metavar="N",
+                    help="the image is stored turned: N clockwise degrees (90, 180, 270) make it upright; detect in the upright view")
     ap.add_argument("--chips", metavar="DIR", help="write the aligned chip of every detected face, cut from the image itself, into DIR")
     ap.add_argument("--size", type=int, default=112, help="with --chips: the chip side (a multiple of 4 in [16, 512])")
     ap.add_argument("--draw", metavar="OUT", help="write the image with every detection drawn into it to OUT")
@@ -188,6 +203,8 @@ def main(argv=None):
         ap.error("--tiled goes with --anonymize, --chips or --draw")
     if args.tiled and args.fit:
         ap.error("--tiled and --fit exclude each other")
+    if args.tiled and args.rotate:
+        ap.error("--tiled and --rotate exclude each other")
     if args.draw and (args.anonymize or args.chips):
         ap.error("--draw, --anonymize and --chips are separate runs")
     if args.blur is not None and not args.anonymize:
@@ -195,19 +212,22 @@ def main(argv=None):
     if args.anonymize and args.chips:
         ap.error("--anonymize and --chips are separate runs")
     if args.draw:
-        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit, flip=args.flip)
+        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate)
     elif args.chips:
-        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit, flip=args.flip)
+        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate)
     elif args.anonymize and args.blur is not None:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate)
     elif args.anonymize:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate)
     else:
         from .centerface import CenterFace
         frame = imread(args.image)
         if args.fit:
             detector = _fit_detector(args.fit, "bf16", args.flip)
-            dets, _ = detector.detect_fit(frame[None])[0]
+            dets, _ = detector.detect_fit(frame[None], rotate=args.rotate)[0]
+        elif args.rotate:
+            detector = CenterFace(*_upright_hw(frame, args.rotate), dtype="bf16", flip_test=args.flip)
+            dets, _ = detector.detect_fit(frame[None], rotate=args.rotate)[0]      # (a context of the upright view's size: the fit fills it)
         else:
             detector = CenterFace(frame.shape[0], frame.shape[1], dtype="bf16", flip_test=args.flip)
             dets, _ = detector(frame)

@@ -432,6 +432,48 @@ def unfit_rows(frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, anc
     return od, ol, oc, fl
 
 
+def rot_geometry(h, w, H, W, rot, fit=None):
+    """The placement of the UPRIGHT view of a stored h x w frame in an H x W canvas (``cf_rot_geometry``, host only): (rw, rh, dx, dy).
+    ``rot``: the clockwise turn (0, 90, 180, 270) that makes the frame upright; ``fit`` as ``_lib.rot_opts`` takes it (None: stretch)."""
+    o, g = _lib.rot_opts(rot, fit), _lib.FitGeom()
+    _lib.check(_lib.lib().cf_rot_geometry(C.byref(o), int(h), int(w), int(H), int(W), C.byref(g)), op=True)
+    return g.rw, g.rh, g.dx, g.dy
+
+
+def rot_frames(frames, size, fmt="bgr", rot=0, fit=None, device=0):
+    """The kernel of ``cf_forward_rot`` (``cf_op_rot``): uint8 [B, H, W, 3] BGR canvases of ``size`` = (H, W) from the upright view of the
+    stored ``frames`` (as ``fit_frames`` takes them; only read): frame b converted to BGR, turned ``rot`` degrees clockwise, then stretched
+    to the canvas (``fit`` = None) or fitted into it (True, or a dict of ``fit_opts`` keywords).  rot = 0 with a fit is ``fit_frames``."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    H, W = int(size[0]), int(size[1])
+    o = _lib.rot_opts(rot, fit)
+    out = np.empty((B, H, W, 3), np.uint8)
+    _lib.check(_lib.lib().cf_op_rot(device, C.byref(o), _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, H, W, ptr(out)), op=True)
+    del keep
+    return out
+
+
+def unrot_rows(frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, rot=0, fit=None, dets=None, lms=None, device=0):
+    """The mapping of decoded rows back into the pixels of the STORED frame (``cf_op_unrot``): ``unfit_rows`` behind a canvas that holds
+    the upright view of a ``frame_hw`` = (h, w) frame turned ``rot`` degrees clockwise, stretched (``fit`` = None) or fitted.  Boxes are
+    assigned from mapped corners (no min / max); landmarks keep their order."""
+    d = np.ascontiguousarray(dets_net, dtype=np.float32)
+    if d.ndim != 3 or d.shape[2] != 4:
+        raise ValueError("dets_net must be [B, rows, 4], got %s" % (d.shape,))
+    B, rows, _ = d.shape
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(B, rows)
+    lm = np.ascontiguousarray(lms_net, dtype=np.float32).reshape(B, rows, 10)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(B)
+    max_out = int(max_out)
+    od = np.zeros((B, max_out, 5), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(B, max_out, 5)
+    ol = np.zeros((B, max_out, 10), np.float32) if lms is None else np.ascontiguousarray(lms, dtype=np.float32).reshape(B, max_out, 10)
+    oc, fl = np.zeros((B,), np.int32), np.zeros((B,), np.int32)
+    o = _lib.rot_opts(rot, fit)
+    _lib.check(_lib.lib().cf_op_unrot(device, C.byref(o), B, int(frame_hw[0]), int(frame_hw[1]), int(net_hw[0]), int(net_hw[1]),
+                                      ptr(d), ptr(sc), ptr(lm), ptr(cn), rows, max_out, ptr(od), ptr(ol), ptr(oc), ptr(fl)), op=True)
+    return od, ol, oc, fl
+
+
 def mirror_batch(x, device=0):
     """The mirror kernel of the flip test (``cf_op_mirror``): ``x`` uint8 [B, H, W, 3] or float32 [B, 3, H, W] with W a multiple of 32 ->
     the same batch with the columns of every image reversed (whole pixels), written on the device as the flip forward writes the

@@ -573,6 +573,81 @@ int cf_rot_geometry(const cf_rot_opts* opts, int h, int w, int H, int W, cf_fit_
 int cf_forward_rot(cf_ctx* ctx, const cf_rot_opts* opts, int format, const cf_yuv_planes* frames, int in_on_device, int B, int h, int w,
                    int pitch0, int pitch1);
 
+/* ---- multi-scale detection: tiles and reduced frame copies, merged on the device -------------
+ * Every forward above shows the network each face at ONE size, set by how the frame is mapped into the canvas: the stretch or the fit of
+ * the whole frame, a turned whole frame, or tiles, which enlarge and cover the small end.  Nothing covers the large end: a face that fills
+ * a phone or video-call frame is about 300 network pixels wide after the fit into 640 x 640, where a stride-4 centre detector is known to
+ * break up.  CenterNet's test code answers with test_scales -- the frame run at several sizes, the results merged -- the other half of
+ * the test-time pair whose flip test is cf_set_flip_test.  Here ONE batch holds different VIEWS of the same frame -- enlarged tiles, the
+ * aspect-true whole frame, the whole frame at half and quarter size -- and ONE merge runs over it, all on the device:
+ *   cf_view_layout (host) -> cf_forward_views -> cf_decode_threshold* (unchanged, per view image) -> cf_merge_views [-> cf_track_update | ...]
+ * No trained weights and no labelled set are on hand: no accuracy claim is made; the argument is geometric, as for tiles and the fit.
+ * The layout defaults of the Python layer (levels 1.0 and 0.5) and its merge (IoS 0.5, edge 2) are this project's choices; nobody has
+ * measured them.
+ *
+ * A VIEW is a source rectangle of the frame and a content rectangle of the canvas.
+ * Canvas: image f * V + v is `fill` everywhere, except
+ *   canvas[dy : dy + dh, dx : dx + dw] = resize(bgr(frame f)[sy0 : sy0 + sh, sx0 : sx0 + sw], (dh, dw))
+ * with the conversion of cf_forward_yuv (the identity for CF_FRAME_BGR) and the fixed-point resize of cf_forward_resized applied to the
+ * crop: the taps clamp at the source rectangle's edges.  A view with (dx, dy, dw, dh) = (0, 0, W, H) is the tile of cf_forward_tiles,
+ * byte for byte; a view with the whole frame as source and the rectangle of cf_fit_geometry as content is the canvas of cf_forward_fit,
+ * byte for byte; a source of exactly the content's size reproduces the source bytes.
+ * Limits, plainly: one view per canvas -- a half-size level costs a whole forward for a quarter of a canvas, and packing several levels
+ * into one canvas is not built; no rotated views (cf_forward_rot stays a single-view path). */
+typedef struct cf_view {
+    int32_t sx0, sy0, sw, sh;    /* frame pixels; all even, sw, sh >= 2, inside the frame */
+    int32_t dx, dy, dw, dh;      /* canvas pixels; dw, dh >= 1, inside (H, W); may be odd */
+} cf_view;                       /* 32 bytes */
+typedef struct cf_view_opts {
+    int32_t tile_h, tile_w, overlap;   /* 0, 0: no tiles */
+    int32_t anchor;              /* CF_FIT_CENTER | CF_FIT_TOPLEFT, for the levels */
+    int32_t n_levels;            /* 0..8 */
+    int32_t scale_pm[8];         /* per mille of the fitted size, 1..1000 */
+} cf_view_opts;                  /* 52 bytes */
+/* The views of an h x w frame in an H x W canvas; host only.  Tiles first: the rectangles of cf_tile_grid(h, w, tile_h, tile_w, overlap,
+ * with_full = 0), each with the whole canvas (0, 0, W, H) as content, and only when there is more than one (tile_h = tile_w = 0: none,
+ * overlap is not looked at).  Then one view per level, in the order given: the whole frame (0, 0, w, h) as source and the content
+ *   dw = max(1, (rw * pm + 500) / 1000), dh = max(1, (rh * pm + 500) / 1000)      (integer division)
+ * with (rw, rh) of cf_fit_geometry with upscale = 1; CF_FIT_CENTER: dx = (W - dw) / 2, dy = (H - dh) / 2; CF_FIT_TOPLEFT: dx = dy = 0.
+ * 1080 x 1920 in 640 x 640, tile 640, overlap 128, levels 1000 and 500: 8 tiles, then 640 x 360 at y = 140, then 320 x 180 at
+ * (160, 230): V = 10.  *n = the number wanted; only the first `cap` are written.  CF_EINVAL (cf_op_last_error names the cause) for NULL
+ * opts or n, an anchor outside {0, 1}, n_levels outside 0..8, a scale outside 1..1000, when the result would be empty, and for whatever
+ * cf_tile_grid (tiles asked for) or cf_fit_geometry refuse.  A frame with an odd side gets levels with an odd source, which
+ * cf_forward_views refuses as it refuses the frame. */
+int cf_view_layout(const cf_view_opts* opts, int h, int w, int H, int W, cf_view* views, int cap, int* n);
+/* Bf frames of h x w in `format` and V views shared by the frames -> the network batch of Bf * V canvases stated above, fill = B, G, R
+ * of the padding (3 bytes) -> forward.  Frames, formats, pitches, the staging of host frames, the alignment of device planes and the
+ * even-sides rule exactly as for cf_forward_tiles; 1 <= V, Bf * V <= max_batch.  The cutter is one launch (per 64 frames); rows and
+ * columns of the padding are written without touching the source; every tap lies inside the source rectangle, pitch padding is never
+ * read; the frames are not modified.  CF_EINVAL before anything is enqueued, the offending view named by its index in cf_last_error,
+ * for: a source value that is odd, smaller than 2 or outside the frame, dw or dh below 1, a content outside (H, W), V < 1, NULL views
+ * or fill, a bad format, side, pitch or alignment, Bf * V > max_batch (ctx == NULL: the arguments are still checked first, the content
+ * only for dx, dy >= 0 and dw, dh >= 1 as there is no canvas, and cf_op_last_error names the cause).  The context remembers the views
+ * and the frame size for cf_merge_views until any other forward or upload.  Under cf_set_flip_test it behaves as cf_forward_tiles does
+ * (Bf * V <= max_batch / 2, the mirrors behind the batch).  cf_get_resized_input returns the view batch; cf_align_faces works per view
+ * image; cf_merge_tiles and cf_unfit_rows behind it are CF_ESTATE. */
+int cf_forward_views(cf_ctx* ctx, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0, int pitch1,
+                     const cf_view* views, int V, const uint8_t* fill);
+/* Merges the rows the LAST THRESHOLD DECODE kept for the Bf * V view images of the last cf_forward_views, per frame.  The candidates are
+ * the rows i < min(count, the decode's max_out) of each view image, walked in (view, row) order, in network coordinates whatever
+ * cf_set_rescale says.  A row is dropped when any of these holds:
+ *   * a corner is not finite;
+ *   * its float32 centre (x1 + x2) * 0.5f, (y1 + y2) * 0.5f lies outside [dx, dx + dw) x [dy, dy + dh) (the rule of cf_unfit_rows);
+ *   * its box comes within opts->edge of a content side whose SOURCE side is interior to the frame, four float32 compares:
+ *       x1 < (float)dx + edge  when sx0 > 0;   x2 > (float)(dx + dw) - edge  when sx0 + sw < w;   the same two in y
+ *     (for a tile view these are the compares of cf_merge_tiles, bit for bit; a whole-frame level has no interior side).
+ * A kept row is mapped, X = (float)(((double)x - (double)dx) * ((double)sw / (double)dw) + (double)sx0), Y likewise with dy, sh / dh
+ * and sy0 (the four corners and the ten landmark values; float64 in this order, no contraction; for a tile view the bits of
+ * cf_merge_tiles); the score is copied.  Then the greedy NMS of cf_merge_tiles over the frame's candidates: the same metric, threshold,
+ * order and ties, the same dets / lms / counts / flags (bit 0: a view image of the frame had more rows than the decode's max_out), the
+ * same out_on_device forms and the same CF_ENOMEM refusal above 256 MiB of suppression bits (Bf x (V * the decode's max_out)
+ * candidates).  The compaction is a prefix sum: deterministic.  Afterwards the context is in the state behind a merge: cf_track_update,
+ * cf_track_follow, cf_redact_faces, cf_blur_faces, cf_draw_faces, cf_align_faces_frame, the lookback and the best-shot offer take the
+ * rows with Bf frames of (h, w), unchanged; before cf_merge_views they return CF_ESTATE.  CF_ESTATE unless the last forward was
+ * cf_forward_views with a threshold decode behind it. */
+int cf_merge_views(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags,
+                   int out_on_device);
+
 /* ---- face tracks across video frames: cover faces through detection dropouts -----------------
  * Every entry point above treats a frame as if it were the only one: the frame in which a face scores just under the threshold goes out
  * uncovered.  A cf_tracker associates the rows of each frame with the tracks of the frames before, on the device, and hands the
@@ -1380,6 +1455,18 @@ int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, in
  * counts [Bf * T] -> dets [Bf][max_out][5], lms [Bf][max_out][10], out_counts [Bf], flags [Bf].  dets and lms are copied up first, so
  * rows the kernels do not write come back as the caller filled them. */
 int cf_op_merge_tiles(int device, const cf_merge_opts* opts, const cf_tile_rect* rects, int T, int Bf, int h, int w, int H, int W,
+                      const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                      float* dets, float* lms, int32_t* out_counts, int32_t* flags);
+/* The cutter of cf_forward_views alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up, so the padding
+ * bytes are on the device beside the pixels): canvases [Bf * V][H][W][3].  W % 4 == 0, Bf * V * H * W * 3 < 2^31.  The same validation,
+ * before any device is touched; nothing is written on refusal. */
+int cf_op_views(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1,
+                const cf_view* views, int V, const uint8_t* fill, int H, int W, uint8_t* canvases);
+/* The merge of cf_merge_views alone, on host tables: dets_net [Bf * V][rows][4], scores [Bf * V][rows], lms_net [Bf * V][rows][10],
+ * counts [Bf * V] -> dets [Bf][max_out][5], lms [Bf][max_out][10], out_counts [Bf], flags [Bf].  dets and lms are copied up first, so
+ * rows the kernels do not write come back as the caller filled them.  The views are checked against the h x w frame and the H x W
+ * canvas as cf_forward_views checks them. */
+int cf_op_merge_views(int device, const cf_merge_opts* opts, const cf_view* views, int V, int Bf, int h, int w, int H, int W,
                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
                       float* dets, float* lms, int32_t* out_counts, int32_t* flags);
 /* The fit kernel of cf_forward_fit alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up, so the

@@ -55,6 +55,7 @@ EXPORTS = (
     "cf_tile_grid", "cf_forward_tiles", "cf_merge_tiles", "cf_op_cut_tiles", "cf_op_merge_tiles",
     "cf_fit_geometry", "cf_forward_fit", "cf_unfit_rows", "cf_op_fit", "cf_op_unfit",
     "cf_rot_geometry", "cf_forward_rot", "cf_op_rot", "cf_op_unrot",
+    "cf_view_layout", "cf_forward_views", "cf_merge_views", "cf_op_views", "cf_op_merge_views",
     "cf_set_flip_test", "cf_op_mirror", "cf_op_flip_heads",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_create_weak", "cf_op_track_weak",
@@ -239,6 +240,58 @@ def fit_opts(anchor="center", upscale=True, fill=(0, 0, 0)):
     if len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
         raise ValueError("fill must be three bytes B, G, R, got %r" % (fill,))
     return FitOpts(int(anchor), int(upscale), (C.c_uint8 * 4)(*fill, 0))
+
+
+class View(C.Structure):
+    """cf_view: a source rectangle of the frame (even values) and a content rectangle of the canvas."""
+    _fields_ = [("sx0", C.c_int32), ("sy0", C.c_int32), ("sw", C.c_int32), ("sh", C.c_int32),
+                ("dx", C.c_int32), ("dy", C.c_int32), ("dw", C.c_int32), ("dh", C.c_int32)]
+
+
+class ViewOpts(C.Structure):
+    """cf_view_opts: the tile grid (0, 0: none) / the anchor of the levels / the levels in per mille of the fitted size."""
+    _fields_ = [("tile_h", C.c_int32), ("tile_w", C.c_int32), ("overlap", C.c_int32), ("anchor", C.c_int32), ("n_levels", C.c_int32),
+                ("scale_pm", C.c_int32 * 8)]
+
+
+def view_opts(tile=None, overlap=None, scales=(1.0,), anchor="center"):
+    """ViewOpts from a tile size (None: no tiles; an int or (tile_h, tile_w)), the tiles' overlap (None: a fifth of the smaller tile
+    side, rounded down to even), the levels as fractions of the fitted size (rounded to per mille; at most 8, each in 1..1000 per mille)
+    and an anchor name ('center' | 'topleft')."""
+    if isinstance(anchor, str):
+        if anchor.lower() not in FIT_ANCHORS:
+            raise ValueError("unknown anchor %r (one of %s)" % (anchor, sorted(FIT_ANCHORS)))
+        anchor = FIT_ANCHORS[anchor.lower()]
+    scales = [scales] if isinstance(scales, (int, float)) else list(scales)
+    if len(scales) > 8:
+        raise ValueError("at most 8 scales, got %d" % len(scales))
+    pm = [int(round(float(v) * 1000.0)) for v in scales]
+    for v, q in zip(scales, pm):
+        if q < 1 or q > 1000:
+            raise ValueError("scale %r is outside 0.001 .. 1.0" % (v,))
+    if tile is None:
+        th = tw = ov = 0
+    else:
+        th, tw = (int(tile), int(tile)) if isinstance(tile, int) else (int(tile[0]), int(tile[1]))
+        ov = (min(th, tw) // 5) & ~1 if overlap is None else int(overlap)
+    return ViewOpts(th, tw, ov, int(anchor), len(pm), (C.c_int32 * 8)(*pm))
+
+
+def view_table(views):
+    """(View table, V) of an int array-like [V][8] of (sx0, sy0, sw, sh, dx, dy, dw, dh) rows."""
+    r = np.ascontiguousarray(views, dtype=np.int32).reshape(-1, 8)
+    tab = (View * max(len(r), 1))()
+    for v, row in enumerate(r.tolist()):
+        (tab[v].sx0, tab[v].sy0, tab[v].sw, tab[v].sh, tab[v].dx, tab[v].dy, tab[v].dw, tab[v].dh) = row
+    return tab, len(r)
+
+
+def fill_bytes(fill):
+    """The three bytes B, G, R of a padding colour as a ctypes array."""
+    fill = [int(v) for v in fill]
+    if len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
+        raise ValueError("fill must be three bytes B, G, R, got %r" % (fill,))
+    return (C.c_uint8 * 4)(*fill, 0)
 
 
 class RotOpts(C.Structure):
@@ -587,6 +640,11 @@ def lib():
         L.cf_unfit_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.cf_op_fit.argtypes = [C.c_int, C.POINTER(FitOpts), C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
         L.cf_op_unfit.argtypes = [C.c_int, C.POINTER(FitOpts)] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
+        L.cf_view_layout.argtypes = [C.POINTER(ViewOpts)] + [C.c_int] * 4 + [C.POINTER(View), C.c_int, C.POINTER(C.c_int)]
+        L.cf_forward_views.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(View), C.c_int, C.c_void_p]
+        L.cf_merge_views.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.cf_op_views.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(View), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.cf_op_merge_views.argtypes = [C.c_int, C.POINTER(MergeOpts), C.POINTER(View)] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
         L.cf_rot_geometry.argtypes = [C.POINTER(RotOpts)] + [C.c_int] * 4 + [C.POINTER(FitGeom)]
         L.cf_forward_rot.argtypes = [C.c_void_p, C.POINTER(RotOpts), C.c_int, C.c_void_p] + [C.c_int] * 6
         L.cf_op_rot.argtypes = [C.c_int, C.POINTER(RotOpts), C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]

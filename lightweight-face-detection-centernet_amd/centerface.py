@@ -502,6 +502,43 @@ class Engine(object):
         o = _lib.merge_opts(metric, thresh, edge)
         self._chk(self._L.cf_merge_tiles(self._h, C.byref(o), int(max_out), _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(counts_ptr), _lib.vp(flags_ptr), 1))
 
+    # -- multi-scale detection: views of one frame --------------------------------------------------
+    def forward_views_enqueue(self, frames, views, fmt="bgr", *, fill=(0, 0, 0), on_device=False, h=None, w=None, pitch0=None, pitch1=None):
+        """Run ``views`` ([V][8] rows (sx0, sy0, sw, sh, dx, dy, dw, dh): a source rectangle of the frame, all even, and a content
+        rectangle of the canvas; ``ops.view_layout`` makes them) of every frame as one batch of Bf * V canvases (``cf_forward_views``);
+        image f * V + v is ``fill`` (B, G, R) with the source of view v of frame f resized into its content rectangle.  ``frames`` and the
+        ``on_device`` form as ``forward_tiles_enqueue`` takes them; they are only read.  A ``decode_threshold`` then gives the per-view
+        results and ``merge_views`` the per-frame ones.  One view per canvas: a half-size level costs a whole forward; packing several
+        levels into one canvas is not built, nor are rotated views.  No accuracy claim is made: the argument is geometric."""
+        f = _lib.frame_format(fmt)
+        vt, V = _lib.view_table(views)
+        fb = _lib.fill_bytes(fill)
+        if on_device:
+            tab, B, h, w, pitch0, pitch1 = _lib.device_input_planes("forward_views_enqueue", frames, f, h, w, pitch0, pitch1)
+        else:
+            tab, B, h, w, pitch0, pitch1, self._last.keep = _lib.frame_planes(frames, fmt, writable=False)
+        self._chk(self._L.cf_forward_views(self._h, f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, vt, V, fb))
+        self.last_B = B * V
+        self._last.tiles = (B, V)
+
+    def merge_views(self, metric="ios", thresh=0.5, edge=2.0, max_out=1024):
+        """Per-frame detections of the last views forward (``cf_merge_views``, host form): the rows the preceding ``decode_threshold``
+        kept for every view -- in canvas coordinates, whatever ``set_rescale`` says -- whose centre lies in the view's content and whose
+        box stays ``edge`` network pixels clear of a content side that is a seam inside the frame, mapped into frame pixels and
+        de-duplicated on the device by greedy NMS with ``metric`` 'ios' or 'iou' at ``thresh``.  Returns (results, flags) as
+        ``merge_tiles``.  IoS 0.5 and edge 2 are this project's defaults; nobody has measured them."""
+        Bf = (self._last.tiles or (1, 1))[0]                             # (without a views forward the library refuses: CF_ESTATE)
+        o = _lib.merge_opts(metric, thresh, edge)
+        flags = np.empty((Bf,), np.int32)
+        return self._rows(Bf, max_out, lambda cap, dets, lms, counts: self._L.cf_merge_views(
+            self._h, C.byref(o), cap, _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts), _lib.ptr(flags), 0)), flags
+
+    def merge_views_device(self, max_out, dets_ptr=None, lms_ptr=None, counts_ptr=None, flags_ptr=None, *, metric="ios", thresh=0.5, edge=2.0):
+        """Same, writing into caller-owned DEVICE buffers as ``merge_tiles_device``: asynchronous on the engine's main stream behind the
+        decode, no count is read on the host.  The context keeps the merged rows either way."""
+        o = _lib.merge_opts(metric, thresh, edge)
+        self._chk(self._L.cf_merge_views(self._h, C.byref(o), int(max_out), _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(counts_ptr), _lib.vp(flags_ptr), 1))
+
     # -- aspect-preserving (letterbox) input -------------------------------------------------------
     def forward_fit_enqueue(self, frames, fmt="bgr", *, anchor="center", upscale=True, fill=(0, 0, 0), on_device=False, h=None, w=None,
                             pitch0=None, pitch1=None):
@@ -1235,7 +1272,7 @@ class EngineRing(object):
             pass
 
 
-_RESCALE, _UNFIT, _MERGE = "rescale", "unfit", "merge"                 # how a plan's rows reach frame space: the three cases of ``_Plan.rows``
+_RESCALE, _UNFIT, _MERGE, _VIEWS = "rescale", "unfit", "merge", "views"      # how a plan's rows reach frame space: the four cases of ``_Plan.rows``
 _Frames = collections.namedtuple("_Frames", "array fmt options")        # the cover, draw and follow steps: the array a chunk's slice of which they work on
 _Scene = collections.namedtuple("_Scene", "scenes array fmt")           # the scene check: the ``SceneCuts`` and the array it looks at
 _Best = collections.namedtuple("_Best", "shots array fmt template flush sink")      # the best shots: where the chips are cut, where the collect goes
@@ -1244,8 +1281,8 @@ _Plan = collections.namedtuple("_Plan", (
     "frames",        # the source the forward reads, sliced per chunk: an array or a list of frames
     "forward",       # the enqueue that takes any slice of ``frames``
     "per",           # frames per chunk
-    "rows",          # how the rows reach frame space: _RESCALE (the decode rescales), _UNFIT (``Engine.unfit_rows``) or _MERGE
-    "merge",         # (metric, thresh, edge) of ``Engine.merge_tiles`` for _MERGE
+    "rows",          # how the rows reach frame space: _RESCALE (the decode rescales), _UNFIT (``Engine.unfit_rows``), _MERGE or _VIEWS
+    "merge",         # (metric, thresh, edge) of ``Engine.merge_tiles`` for _MERGE, of ``Engine.merge_views`` for _VIEWS
     "out",           # the output copy that is returned with the results, or None
     "tracker",       # the ``Tracker`` that every detected chunk advances, or None
     "scene",         # _Scene: every chunk is first checked for scene cuts, which frees the tracks of a cut stream
@@ -1418,8 +1455,9 @@ class CenterFace(object):
         return _Late(lookback, bool(flush), [[] for _ in range(n)])
 
     def _plan(self, frames, fmt, take, *, tiled=False, tile=None, overlap=None, with_full=True, merge=("ios", 0.5, 2.0), fit=None, tracker=None,
-              follow=None, detect=True, scenes=None, lookback=None, flush=False, cover=None, draw=None, rotate=0):
+              follow=None, detect=True, scenes=None, lookback=None, flush=False, cover=None, draw=None, rotate=0, views=None):
         """The plan of a public product method from the keyword arguments they share (``fit``: what ``_fit_options`` made of it;
+        ``views``: what ``_views_options`` made of it;
         ``cover`` / ``draw``: the options of that step; ``rotate``: the clockwise turn that makes the stored frames upright, 0 = none).  ``fmt`` None: BGR images.  ``take`` says what the steps in frame space work on:
         'copy' -- a new array, which the call returns (the inputs stay untouched); 'array' -- the frames as one uint8 array of the size
         this instance was built for, unless they are fitted or tiled; 'given' -- the frames as they are (fitted or tiled only).  The
@@ -1429,7 +1467,7 @@ class CenterFace(object):
         rotate = self._rotation(rotate, tiled) if rotate else 0                  # (0: the plan of before, nothing of it is reached)
         eng = self.engine
         late = self._lookback(lookback, flush, tracker, len(frames))
-        fmt_, plain, per, rows = "bgr" if fmt is None else fmt, not tiled and fit is None and not rotate, eng.max_batch, _RESCALE
+        fmt_, plain, per, rows = "bgr" if fmt is None else fmt, not tiled and fit is None and not rotate and views is None, eng.max_batch, _RESCALE
         if take == "copy" and plain and fmt is not None:                          # 4:2:0 frames of the instance's size go up as they are
             src, forward = self._input_form(eng, frames, fmt)
             array = np.stack([np.asarray(f) for f in src])                        # a new array: the inputs stay untouched
@@ -1445,7 +1483,10 @@ class CenterFace(object):
                 raise ValueError("frames must be uint8 [B,h,w,3] (bgr) or [B, h*3//2, w] (4:2:0), got %s" % (array.shape,))
         else:
             array = frames
-        if rotate:                                                                # (fit None: the upright view is stretched)
+        if views is not None:
+            (forward, per), src, rows = self._views_form(array, fmt_, views, cover is not None or draw is not None), array, _VIEWS
+            merge = (views["metric"], views["thresh"], views["edge"])
+        elif rotate:                                                              # (fit None: the upright view is stretched)
             src, forward, rows = array, lambda chunk: eng.forward_rot_enqueue(chunk, fmt_, rotate, fit=fit), _UNFIT
         elif fit is not None:
             src, forward, rows = array, lambda chunk: eng.forward_fit_enqueue(chunk, fmt_, **fit), _UNFIT
@@ -1510,7 +1551,8 @@ class CenterFace(object):
                 res = self._decode(eng, score)
             else:
                 eng.decode_threshold(score, self.nms_thresh, self.max_dets)
-                rows = eng.unfit_rows(self.max_dets) if plan.rows == _UNFIT else eng.merge_tiles(*plan.merge, self.max_dets)
+                rows = (eng.unfit_rows(self.max_dets) if plan.rows == _UNFIT else eng.merge_views(*plan.merge, self.max_dets) if plan.rows == _VIEWS
+                        else eng.merge_tiles(*plan.merge, self.max_dets))
                 res = self._postprocess_many(rows[0], rescaled=True)
             if plan.tracker is not None:
                 eng.track_update_device(plan.tracker, i)
@@ -1595,7 +1637,7 @@ class CenterFace(object):
             raise ValueError("detect_aligned needs the landmarks: construct CenterFace(..., landmarks=True)")
         return self._run(self._plain(imgs, chips=lambda i, j: self.engine.align_faces(size, **chip_options)))
 
-    def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, fit=None, rotate=0, **chip_options):
+    def detect_aligned_frames(self, frames, fmt="bgr", size=112, *, tiled=False, tile=None, overlap=None, fit=None, rotate=0, views=None, **chip_options):
         """Detection plus the aligned chip of every detection cut from the FRAME ITSELF (``Engine.align_faces_frame``), not from the
         network-sized batch: one (dets, lms, chips) per frame, dets / lms in frame pixels.  ``frames``: BGR uint8 [B,h,w,3]
         (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] ('nv12', 'nv21', 'i420', 'yv12') of the (height, width) this instance was
@@ -1604,11 +1646,12 @@ class CenterFace(object):
         (``tile``, ``overlap``); the chips are those of the merged detections, which are in frame pixels and not floor-divided.
         ``fit``: True, or a dict with anchor, upscale and / or fill: frames of any size, detected by ``detect_fit``'s path instead
         (frame pixels, not floor-divided); not together with ``tiled``.  ``rotate``: as ``anonymize`` -- the similarity is fitted to the
-        landmarks, so the chips of a turned frame come out upright.  ``chip_options``: out, rgb, mean, scale, template."""
+        landmarks, so the chips of a turned frame come out upright.  ``views``: as ``anonymize`` (``detect_views``'s path).  ``chip_options``: out, rgb, mean, scale, template."""
+        views = self._views_options(views, tiled, fit, rotate)
         fit = self._fit_options(fit, tiled)
         if not self.landmarks:
             raise ValueError("detect_aligned_frames needs the landmarks: construct CenterFace(..., landmarks=True)")
-        plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit, rotate=rotate)
+        plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit, rotate=rotate, views=views)
         return self._run(plan._replace(chips=lambda i, j: self.engine.align_faces_frame(plan.frames[i:j], fmt, size, **chip_options)))
 
     def _tiled_form(self, frames, fmt, tile, overlap, with_full, writable):
@@ -1623,6 +1666,57 @@ class CenterFace(object):
         if per < 1:
             raise ValueError("%d tiles per frame need max_batch >= %d (this instance has %d)" % (len(rects), len(rects), self.engine.max_batch))
         return lambda chunk: self.engine.forward_tiles_enqueue(chunk, rects, fmt), per
+
+    def _views_form(self, frames, fmt, views, writable):
+        """(forward, frames per chunk) of the views paths: the enqueue that makes the views of any slice of ``frames`` (their size's
+        layout, ``ops.view_layout``)."""
+        h, w = _lib.frame_planes(frames, fmt, writable=writable)[2:4]
+        from . import ops
+        table = ops.view_layout(h, w, self.img_h_new, self.img_w_new, views["tile"], views["overlap"], views["scales"], views["anchor"])
+        per = self.engine.max_batch // len(table)
+        if per < 1:
+            raise ValueError("%d views per frame need max_batch >= %d (this instance has %d)" % (len(table), len(table), self.engine.max_batch))
+        return lambda chunk: self.engine.forward_views_enqueue(chunk, table, fmt, fill=views["fill"]), per
+
+    @staticmethod
+    def _views_options(views, tiled=False, fit=None, rotate=0):
+        """The ``views`` argument of the product paths -> None, or the options of ``detect_views``' path with every default filled in:
+        ``views`` None / False, True (the defaults) or a dict with scales, tile, overlap, anchor, fill, metric, thresh and / or edge.
+        ``views`` excludes ``tiled=True``, ``fit`` and ``rotate``: the layout has its own tiles and its own fit, and no rotated views."""
+        if views is None or views is False:
+            return None
+        for name, on in (("tiled=True", tiled), ("fit=", fit is not None and fit is not False), ("rotate=", bool(rotate))):
+            if on:
+                raise ValueError("views= and %s exclude each other: the views have their own tiles and their own fit, and rotated views are not covered" % name)
+        o = dict(scales=(1.0, 0.5), tile=None, overlap=None, anchor="center", fill=(0, 0, 0), metric="ios", thresh=0.5, edge=2.0)
+        given = dict(views) if isinstance(views, dict) else {}
+        if set(given) - set(o):
+            raise ValueError("views takes %s, got %s" % (", ".join(sorted(o)), sorted(given)))
+        o.update(given)
+        _lib.view_opts(o["tile"], o["overlap"], o["scales"], o["anchor"])       # refuse bad names and numbers before any work
+        _lib.fill_bytes(o["fill"])
+        _lib.merge_opts(o["metric"], o["thresh"], o["edge"])
+        return o
+
+    def detect_views(self, frames, fmt="bgr", *, scales=(1.0, 0.5), tile=None, overlap=None, anchor="center", fill=(0, 0, 0), metric="ios",
+                     thresh=0.5, edge=2.0, redact=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None, flush=False):
+        """Multi-scale detection: every frame reaches the network as several VIEWS in one batch -- the aspect-true whole frame at each of
+        ``scales`` (fractions of the fitted size; 0.5 shows a face that fills the frame at half the size, where a stride-4 centre
+        detector holds together), placed by ``anchor`` on a canvas of ``fill``, and, with ``tile`` (``overlap``: default a fifth of the
+        tile, rounded down to even), enlarged tiles in front of them -- and the per-view detections are mapped back and de-duplicated on
+        the device (``Engine.merge_views``: ``metric``, ``thresh``, ``edge``).  ``frames`` as ``detect_tiled`` takes them, of any even
+        size; ``max_batch`` must hold the views of one frame.  Returns (dets [n,5], lms [n,10]) per frame (``dets`` alone without
+        landmarks), in FRAME pixels, not floor-divided.  One view per canvas: a half-size level costs a whole forward for a quarter of a
+        canvas, packing several levels into one canvas is not built, and there are no rotated views.  The layout defaults and the
+        IoS 0.5 / edge 2 merge are this project's choices and nobody has measured them; no accuracy claim is made.  ``redact``,
+        ``tracker``, ``follow``, ``detect``, ``scenes``, ``lookback`` and ``flush``: as ``detect_tiled``."""
+        views = self._views_options(dict(scales=scales, tile=tile, overlap=overlap, anchor=anchor, fill=fill, metric=metric, thresh=thresh, edge=edge))
+        if redact is not None:
+            _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
+        if lookback is not None and redact is None:
+            raise ValueError("lookback= needs redact=")                         # (without it there is nothing to delay)
+        return self._run(self._plan(frames, fmt, "given", views=views, tracker=tracker, follow=follow, detect=detect, scenes=scenes, lookback=lookback,
+                                    flush=flush, cover=redact))
 
     @staticmethod
     def _rotation(rotate, tiled=False):
@@ -1691,7 +1785,7 @@ class CenterFace(object):
                                     tracker=tracker, follow=follow, detect=detect, scenes=scenes, lookback=lookback, flush=flush, cover=redact))
 
     def anonymize(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None,
-                  flush=False, rotate=0, **options):
+                  flush=False, rotate=0, views=None, **options):
         """``detect_batch`` plus the redaction of every detection: (frames_out, [(dets, lms), ...]) -- frames_out a uint8 [B,h,w,3] COPY of
         ``imgs`` in which every detected face is pixelated or blanked on the device (``Engine.redact_faces``; ``options``: mode, shape,
         cell, scale, fill) or, with ``mode='blur'``, blurred (``Engine.blur_faces``; shape, radius, scale), the detections exactly those of ``detect_batch`` (rescale included).  ``imgs`` are left untouched; an image
@@ -1727,26 +1821,30 @@ class CenterFace(object):
         call does what it did without them.  ``rotate``: 90, 180 or 270 -- the clockwise turn that makes the STORED frames upright (a
         corridor-mode camera, phone video): the network sees the upright view (``Engine.forward_rot_enqueue``; stretched to the network
         input, or fitted with ``fit``), frames of any size; detections and redaction are in the pixels of the stored frame, not
-        floor-divided; not together with ``tiled``; one turn per call; no accuracy claim is made."""
+        floor-divided; not together with ``tiled``; one turn per call; no accuracy claim is made.  ``views``: True, or a dict with scales,
+        tile, overlap, anchor, fill, metric, thresh and / or edge: detection by ``detect_views`` -- several views of every frame in one
+        batch, merged on the device -- on frames of any even size, the rows in frame pixels; not together with ``tiled``, ``fit`` or
+        ``rotate``; no accuracy claim is made for it either."""
         return self._anonymize(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
-                               scenes=scenes, lookback=lookback, flush=flush, rotate=rotate)
+                               scenes=scenes, lookback=lookback, flush=flush, rotate=rotate, views=views)
 
     def anonymize_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
-                      scenes=None, lookback=None, flush=False, rotate=0, **options):
+                      scenes=None, lookback=None, flush=False, rotate=0, views=None, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
         [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow``,
-        ``fit``, ``detect``, ``scenes``, ``lookback``, ``flush`` and ``rotate``: as ``anonymize``."""
+        ``fit``, ``detect``, ``scenes``, ``lookback``, ``flush``, ``rotate`` and ``views``: as ``anonymize``."""
         return self._anonymize(frames, fmt, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
-                               scenes=scenes, lookback=lookback, flush=flush, rotate=rotate)
+                               scenes=scenes, lookback=lookback, flush=flush, rotate=rotate, views=views)
 
-    def _anonymize(self, frames, fmt, options, *, tiled, fit, rotate=0, **shared):
+    def _anonymize(self, frames, fmt, options, *, tiled, fit, rotate=0, views=None, **shared):
         """The body of ``anonymize`` (``fmt`` None: BGR images) and ``anonymize_yuv``: the copy of the frames is covered."""
         _lib.split_redact_options(options)                                    # refuse what blur does not take before any work
+        views = self._views_options(views, tiled, fit, rotate)
         rotate = self._rotation(rotate, tiled) if rotate else 0
-        return self._run(self._plan(frames, fmt, "copy", tiled=tiled, fit=self._fit_options(fit, tiled), cover=options, rotate=rotate, **shared))
+        return self._run(self._plan(frames, fmt, "copy", tiled=tiled, fit=self._fit_options(fit, tiled), cover=options, rotate=rotate, views=views, **shared))
 
     def best_shots(self, frames, fmt="bgr", *, tracker, shots, tiled=False, tile=None, overlap=None, fit=None, follow=None, detect=True,
-                   flush=False, template=None, scenes=None, rotate=0):
+                   flush=False, template=None, scenes=None, rotate=0, views=None):
         """One chip per appearance of a person: detection, tracking and best-shot selection of ``frames`` -- BGR uint8 [B,h,w,3]
         (``fmt='bgr'``) or dense 4:2:0 uint8 [B, h*3//2, w] -- where image k of a call is the next frame of stream k of ``tracker`` (a
         ``Tracker``) and of ``shots`` (a ``BestShots``), as in ``anonymize(tracker=)``: a video is fed one call per frame, n cameras n
@@ -1756,14 +1854,15 @@ class CenterFace(object):
         after the last chunk the finished entries of the call's streams are collected -- ``flush=True`` finishes every live track first
         (the end of the video).  Returns, per stream, the list of finished shots in finishing order: dicts with ``id``, ``quality``,
         ``chip`` [size, size, 3], ``det`` [5], ``lms`` [10] (the row of the best frame, in the tracker's space) and ``record`` (the eight
-        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  ``fit``: as ``anonymize`` (``detect_fit``'s path).  ``rotate``: as ``anonymize``; the chips are fitted to the landmarks, so they come out upright.  The quality formula is this project's choice; no accuracy claim is made for it."""
+        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  ``fit``: as ``anonymize`` (``detect_fit``'s path).  ``rotate``: as ``anonymize``; the chips are fitted to the landmarks, so they come out upright.  ``views``: as ``anonymize``.  The quality formula is this project's choice; no accuracy claim is made for it."""
+        views = self._views_options(views, tiled, fit, rotate)
         fit = self._fit_options(fit, tiled)
         if not self.landmarks:
             raise ValueError("best_shots needs the landmarks: construct CenterFace(..., landmarks=True)")
         if tracker is None or shots is None:
             raise ValueError("best_shots needs tracker= and shots=")
         plan = self._plan(frames, fmt, "array", tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect, scenes=scenes,
-                          rotate=rotate)
+                          rotate=rotate, views=views)
         sink = []
         self._run(plan._replace(best=_Best(shots, plan.frames, fmt, template, bool(flush), sink)))
         if not sink:
@@ -1787,31 +1886,33 @@ class CenterFace(object):
         return o
 
     def annotate(self, imgs, *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None,
-                 flush=False, rotate=0, **options):
+                 flush=False, rotate=0, views=None, **options):
         """``detect_batch`` plus the drawing of every detection, what demo.py:15-23 does with cv2 on the host: (frames_out, [(dets, lms),
         ...]) -- frames_out a uint8 [B,h,w,3] COPY of ``imgs`` with box outlines, landmark dots and a label painted on the device
         (``Engine.draw_faces``; ``options`` as there, colours as BGR triples).  ``tiled``, ``tile``, ``overlap`` and ``tracker`` as
         ``anonymize``: with a tracker the label is the track id and the tracks held through a dropout are drawn too, dashed, in
         ``held_color``.  ``fit``, ``follow``, ``detect`` and ``scenes``: as ``anonymize``.  ``lookback`` and ``flush``: as ``anonymize`` --
         the delayed frames are drawn, a back-filled row as a held one (dashed, in ``held_color``), and the return is the lists.
-        ``rotate``: as ``anonymize``; the labels are upright in the STORED frame, so a viewer of the upright video sees them turned."""
+        ``rotate``: as ``anonymize``; the labels are upright in the STORED frame, so a viewer of the upright video sees them turned.
+        ``views``: as ``anonymize``."""
         return self._annotate(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
-                              scenes=scenes, lookback=lookback, flush=flush, rotate=rotate)
+                              scenes=scenes, lookback=lookback, flush=flush, rotate=rotate, views=views)
 
     def annotate_yuv(self, frames, fmt="nv12", *, tiled=False, tile=None, overlap=None, fit=None, tracker=None, follow=None, detect=True,
-                     scenes=None, lookback=None, flush=False, rotate=0, **options):
+                     scenes=None, lookback=None, flush=False, rotate=0, views=None, **options):
         """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
         in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``fit``, ``scenes``, ``lookback`` and
-        ``flush`` and ``rotate``: as ``annotate``."""
+        ``flush``, ``rotate`` and ``views``: as ``annotate``."""
         return self._annotate(frames, fmt, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
-                              scenes=scenes, lookback=lookback, flush=flush, rotate=rotate)
+                              scenes=scenes, lookback=lookback, flush=flush, rotate=rotate, views=views)
 
-    def _annotate(self, frames, fmt, options, *, tiled, fit, tracker, rotate=0, **shared):
+    def _annotate(self, frames, fmt, options, *, tiled, fit, tracker, rotate=0, views=None, **shared):
         """The body of ``annotate`` (``fmt`` None: BGR images) and ``annotate_yuv``: the copy of the frames is drawn into."""
+        views = self._views_options(views, tiled, fit, rotate)
         fit = self._fit_options(fit, tiled)
         rotate = self._rotation(rotate, tiled) if rotate else 0
         return self._run(self._plan(frames, fmt, "copy", tiled=tiled, fit=fit, tracker=tracker, draw=self._draw_options(options, tracker, fmt is not None),
-                                    rotate=rotate, **shared))
+                                    rotate=rotate, views=views, **shared))
 
     def _yuv_frames(self, frames):
         """The frames of detect_yuv / detect_stream(fmt=...) checked against the instance's (height, width): a [B, height*3//2, width]

@@ -514,6 +514,30 @@ hipError_t launch_rot_frames(hipStream_t s, int rot, int format, const void* con
                              const cf_fit_geom& g, const uint8_t* fill, uint8_t* dst, int H, int W);
 hipError_t launch_unrot_rows(hipStream_t s, const UnfitParams& p, int rot);
 
+// Multi-scale views (cf_views.hip; the statement is in include/centerface_hip.h).  view_layout: the views of cf_view_layout (host only).
+// views_check: nullptr, or what is wrong with the frames and the view table (the text lives in `why` and names the view; host only);
+// views_table_check: its view-table part alone.  The cutter writes dst [Bf * V][H][W][3] uint8 BGR: image f * V + v = `fill` (B, G, R)
+// with the source rectangle of views[v] of frame f, converted (4:2:0) and resized, pasted at its content rectangle.  planes: HOST table
+// of Bf x {p0, p1, p2} DEVICE addresses (cf_frame.h; read only); views: V views on the DEVICE.
+int view_layout(const cf_view_opts* o, int h, int w, int H, int W, cf_view* views, int cap, int* n);
+const char* views_table_check(std::string& why, int h, int w, const cf_view* views, int V, int H, int W);
+const char* views_check(std::string& why, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_view* views, int V, int H, int W);
+hipError_t launch_cut_views(hipStream_t s, int format, const void* const* planes, int Bf, int pitch0, int pitch1, const cf_view* views, int V,
+                            const uint8_t* fill, uint8_t* dst, int H, int W);
+// The merge of the per-view results of a threshold decode over Bf * V images: MergeParams with a view table in the place of the
+// rectangles (the canvas size is in the views' content rectangles); workspace sizes as merge_mask_bytes(Bf, V, rows) and cap = V * rows.
+struct ViewMergeParams {
+    const cf_view* views;        // [V], device
+    int V, Bf, h, w;
+    const float* dets_net; const float* scores; int score_stride; const float* lms_net; const int* counts; int rows;
+    int metric; float thresh, edge;
+    float* cand; int* cand_count; int* order; unsigned long long* mask;
+    int max_out;
+    float* dets; float* lms; float* corners; int* out_counts;
+    int* flags;           // [Bf]: bit 0 = some view image of the frame had counts > rows
+};
+hipError_t launch_merge_views(hipStream_t s, const ViewMergeParams& p);
+
 // Flip test (cf_flip.hip; the statement is in include/centerface_hip.h).  mirror_check: nullptr, or what is wrong with the format and sizes
 // of a batch to mirror (the text lives in `why`; host only).  launch_mirror_batch: dst holds 2B network inputs of in_format (uint8
 // [.][H][W][3] or float32 [.][3][H][W]; 16-byte aligned); images B .. 2B-1 become images 0 .. B-1 of src with their columns reversed and,

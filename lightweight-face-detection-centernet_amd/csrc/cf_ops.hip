@@ -995,6 +995,66 @@ int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* re
     return sc.result("cf_op_merge_tiles");
 }
 
+int cf_view_layout(const cf_view_opts* o, int h, int w, int H, int W, cf_view* views, int cap, int* n) {
+    const int r = view_layout(o, h, w, H, W, views, cap, n);
+    if (r) g_op_error = "cf_view_layout: anchor 0 or 1, 0 <= n_levels <= 8, scales in 1..1000 per mille, h and w in 2..8192, H and W at least 1, tiles as cf_tile_grid "
+                        "takes them (or tile_h = tile_w = 0), and at least one view in the result; opts and n not null";
+    return r;
+}
+
+// The cutter of cf_forward_views on host frames.
+int cf_op_views(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1, const cf_view* views,
+                int V, const uint8_t* fill, int H, int W, uint8_t* canvases) {
+    std::string why;
+    const char* bad = views_check(why, format, Bf, h, w, pitch0, pitch1, views, V, H, W);
+    if (!bad) bad = redact_check_planes(format, reinterpret_cast<const void* const*>(host_frames), Bf, 0, pitch0, pitch1);
+    if (!bad && (!fill || !canvases)) bad = "null fill or output";
+    if (!bad && (long long)Bf * V * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
+    if (bad) return fail("cf_op_views", bad);
+    Scope sc(device);
+    const std::vector<const void*> dev = up_planes(sc, format, reinterpret_cast<const void* const*>(host_frames), Bf, h, pitch0, pitch1);
+    const cf_view* dviews = sc.in(views, V);
+    uint8_t* out = sc.out(canvases, (size_t)Bf * V * H * W * 3);
+    sc.run([&] { return launch_cut_views(sc.s, format, dev.data(), Bf, pitch0, pitch1, dviews, V, fill, out, H, W); });
+    return sc.result("cf_op_views");
+}
+
+int cf_op_merge_views(int device, const cf_merge_opts* o, const cf_view* views, int V, int Bf, int h, int w, int H, int W,
+                      const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                      float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+    std::string why;
+    const char* bad = nullptr;
+    if (!o || !dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags) bad = "null argument";
+    else if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) bad = "unknown metric (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)";
+    else if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) bad = "thresh and edge must be finite and not negative";
+    else if (rows < 1 || max_out < 1 || H < 1 || W < 1) bad = "rows, max_out, H and W must be at least 1";
+    else if (const char* geo = frame_geometry_check(FrameGeo{CF_FRAME_BGR, Bf, h, w, 3 * w, 0}, 2, true)) bad = geo;
+    else bad = views_table_check(why, h, w, views, V, H, W);
+    if (bad) return fail("cf_op_merge_views", bad);
+    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit) {
+        g_op_error = "cf_op_merge_views: the suppression bits of Bf x (V * rows) candidates exceed 256 MiB";
+        return CF_ENOMEM;
+    }
+    Scope sc(device);
+    const size_t n = (size_t)Bf * V * rows, cap = (size_t)V * rows, mo = (size_t)Bf * max_out;
+    ViewMergeParams p{};
+    p.views = sc.in(views, V);
+    p.V = V; p.Bf = Bf; p.h = h; p.w = w;
+    p.dets_net = sc.in(dets_net, n * 4);
+    p.scores = sc.in(scores, n); p.score_stride = 1;
+    p.lms_net = sc.in(lms_net, n * 10);
+    p.counts = sc.in(counts, (size_t)Bf * V); p.rows = rows;
+    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
+    p.cand = sc.make<float>(Bf * cap * 16); p.cand_count = sc.make<int>(Bf);
+    p.order = sc.make<int>(Bf * cap); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, V, rows));
+    p.max_out = max_out;
+    p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
+    p.corners = sc.make<float>(mo * 4);
+    p.out_counts = sc.out(out_counts, Bf); p.flags = sc.out(flags, Bf);
+    sc.run([&] { return launch_merge_views(sc.s, p); });
+    return sc.result("cf_op_merge_views");
+}
+
 // nullptr, or what is wrong with the options and sizes of a fit geometry (the text lives in `why`)
 static const char* fit_geometry_check(std::string& why, const cf_fit_opts* o, int h, int w, int H, int W) {
     if (const char* bad = fit_check(why, o, CF_FRAME_BGR, 1, h, w, 3 * w, 0, 4, 4)) return bad;      // the options and the frame's sides

@@ -62,6 +62,19 @@ def _fit_detector(fit, dtype, flip=False):
     return CenterFace(fit, fit, dtype=dtype, flip_test=flip)
 
 
+def _views_detector(frame, scales, tiled, dtype, flip=False, size=640):
+    """The detector, the frame and the ``views=`` options of ``scales=(1.0, 0.5)``: the image (cropped to even sides) goes through an
+    N x N context -- N = ``tiled`` when tiles are asked for, else ``size`` -- as several views in one batch: N x N tiles first when
+    ``tiled``, then the aspect-true whole image at each scale (``CenterFace.detect_views``; no accuracy claim is made for it)."""
+    from . import ops
+    from .centerface import CenterFace
+    frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
+    n = int(tiled) if tiled else int(size)
+    views = dict(scales=tuple(float(v) for v in scales), tile=int(tiled) if tiled else None)
+    V = len(ops.view_layout(frame.shape[0], frame.shape[1], n, n, **views))
+    return CenterFace(n, n, dtype=dtype, max_batch=V * (2 if flip else 1), flip_test=flip), frame, views
+
+
 def _upright_hw(frame, rotate):
     """The (height, width) of the upright view of a stored frame that ``rotate`` clockwise degrees make upright."""
     return (frame.shape[1], frame.shape[0]) if rotate in (90, 270) else (frame.shape[0], frame.shape[1])
@@ -75,7 +88,9 @@ def anonymize_file(path, out_path, **options):
     goes letterboxed through an N x N context instead of one built for its size; not together with ``tiled``.  ``flip=True``: the
     detector runs CenterNet's flip test (``CenterFace(flip_test=True)``: about twice the network time; no accuracy claim is made).
     ``rotate=N`` (90, 180, 270): the image is STORED turned and N clockwise degrees make it upright -- the detector sees the upright
-    view (``CenterFace.anonymize(rotate=)``), the faces are redacted in the image as stored; not together with ``tiled``."""
+    view (``CenterFace.anonymize(rotate=)``), the faces are redacted in the image as stored; not together with ``tiled``.
+    ``scales=(1.0, 0.5)``: multi-scale detection (``CenterFace.anonymize(views=)``) -- the whole image at each scale, behind the N x N
+    tiles of ``tiled=N`` if given, as one batch through a 640 x 640 (N x N) context; not together with ``fit`` or ``rotate``."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
@@ -84,7 +99,12 @@ def anonymize_file(path, out_path, **options):
     dtype = options.pop("dtype", "bf16")
     flip = bool(options.pop("flip", False))
     rotate = options["rotate"] = int(options.pop("rotate", 0) or 0)
-    if fit:
+    scales = options.pop("scales", None)
+    if scales:
+        if fit or rotate:
+            raise ValueError("scales= goes with tiled= only, not with fit= or rotate=")
+        detector, frame, options["views"] = _views_detector(frame, scales, tiled, dtype, flip)
+    elif fit:
         detector = _fit_detector(fit, dtype, flip)
         options["fit"], options["tiled"] = True, bool(tiled)
     elif tiled:
@@ -106,7 +126,7 @@ def anonymize_file(path, out_path, **options):
 def annotate_file(path, out_path, **options):
     """demo.py:30-51 (``test_image`` with its drawing loop): read one image file, draw every detection on the device
     (``CenterFace.annotate``: green boxes, red landmark dots, the score as a label; ``options`` as there) and write the result to
-    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``, ``fit=N``, ``flip=True``, ``rotate=N``: as ``anonymize_file``
+    ``out_path`` (format from its extension).  Returns the detections.  ``tiled=N``, ``fit=N``, ``flip=True``, ``rotate=N``, ``scales=``: as ``anonymize_file``
     (the labels are upright in the image as stored)."""
     from PIL import Image
     from .centerface import CenterFace
@@ -116,7 +136,12 @@ def annotate_file(path, out_path, **options):
     dtype = options.pop("dtype", "bf16")
     flip = bool(options.pop("flip", False))
     rotate = options["rotate"] = int(options.pop("rotate", 0) or 0)
-    if fit:
+    scales = options.pop("scales", None)
+    if scales:
+        if fit or rotate:
+            raise ValueError("scales= goes with tiled= only, not with fit= or rotate=")
+        detector, frame, options["views"] = _views_detector(frame, scales, tiled, dtype, flip)
+    elif fit:
         detector = _fit_detector(fit, dtype, flip)
         options["fit"], options["tiled"] = True, bool(tiled)
     elif tiled:
@@ -135,16 +160,21 @@ def annotate_file(path, out_path, **options):
     return results[0]
 
 
-def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False, rotate=0):
+def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False, rotate=0, scales=None):
     """Read one image file and write the aligned chip of every detected face, cut from the image at its own resolution
     (``CenterFace.detect_aligned_frames``), to ``out_dir``/<image name>_<k>.png.  Returns (detections, the paths written).
-    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides).  ``fit=N``, ``flip=True``, ``rotate=N``: as ``anonymize_file``
+    ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides).  ``fit=N``, ``flip=True``, ``rotate=N``, ``scales=``: as ``anonymize_file``
     (the chips are fitted to the landmarks, so they come out upright)."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
-    tiled, fit, rotate = int(tiled or 0), int(fit or 0), int(rotate or 0)
-    if fit:
+    tiled, fit, rotate, views = int(tiled or 0), int(fit or 0), int(rotate or 0), None
+    if scales:
+        if fit or rotate:
+            raise ValueError("scales= goes with tiled= only, not with fit= or rotate=")
+        detector, frame, views = _views_detector(frame, scales, tiled, dtype, flip)
+        tiled = 0
+    elif fit:
         detector = _fit_detector(fit, dtype, flip)
     elif tiled:
         from . import ops
@@ -154,7 +184,7 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False
     else:
         detector = CenterFace(*_upright_hw(frame, rotate), dtype=dtype, flip_test=flip)
     try:
-        dets, lms, chips = detector.detect_aligned_frames(frame[None], "bgr", size, tiled=bool(tiled), fit=bool(fit) or None, rotate=rotate)[0]
+        dets, lms, chips = detector.detect_aligned_frames(frame[None], "bgr", size, tiled=bool(tiled), fit=bool(fit) or None, rotate=rotate, views=views)[0]
     finally:
         detector.close()
     os.makedirs(out_dir, exist_ok=True)
@@ -166,7 +196,7 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False
 
 
 def main(argv=None):
-    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]] [--flip] [--rotate N]``: print the detections of one image
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]] [--scales S,S..] [--flip] [--rotate N]``: print the detections of one image
     file; with ``--draw`` also write the image with every detection drawn into it (boxes, landmark dots and, unless ``--label none``,
     the score); with
     ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``; or blurred: ``--blur [R]``, R = the
@@ -177,7 +207,10 @@ def main(argv=None):
     context built for its size (no accuracy claim is made for it); with ``--flip`` the detector runs CenterNet's flip test -- the image and
     its mirror in one forward, the heads merged on the device -- at about twice the network time (no accuracy claim is made either); with ``--rotate N``
     (90, 180 or 270) the image is taken as STORED turned, N clockwise degrees making it upright: the detector sees the upright view and
-    the detections, the redaction and the drawing are in the pixels of the image as stored (not with ``--tiled``; no accuracy claim)."""
+    the detections, the redaction and the drawing are in the pixels of the image as stored (not with ``--tiled``; no accuracy claim); with
+    ``--scales 1,0.5`` the image goes through a 640 x 640 context (``--tiled N``: N x N, behind N x N tiles) as one batch of views -- the
+    whole image, aspect ratio kept, at each scale -- whose detections are merged on the device (multi-scale detection; not with ``--fit``
+    or ``--rotate``; one view per canvas, no packing of levels; no accuracy claim is made)."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("image")
@@ -194,13 +227,17 @@ def main(argv=None):
     ap.add_argument("--flip", action="store_true", help="flip test: run the image and its mirror and merge the heads on the device (about twice the network time)")
     ap.add_argument("--rotate", type=int, default=0, choices=(0, 90, 180, 270), metavar="N",
                     help="the image is stored turned: N clockwise degrees (90, 180, 270) make it upright; detect in the upright view")
+    ap.add_argument("--scales", default=None, metavar="S,S..", type=lambda t: tuple(float(v) for v in t.split(",")),
+                    help="multi-scale detection: the whole image at each of these fractions of its fitted size (e.g. 1,0.5), merged on the device")
     ap.add_argument("--chips", metavar="DIR", help="write the aligned chip of every detected face, cut from the image itself, into DIR")
     ap.add_argument("--size", type=int, default=112, help="with --chips: the chip side (a multiple of 4 in [16, 512])")
     ap.add_argument("--draw", metavar="OUT", help="write the image with every detection drawn into it to OUT")
     ap.add_argument("--label", default="score", choices=("score", "none"), help="with --draw: the number above each box")
     args = ap.parse_args(argv)
-    if args.tiled and not (args.anonymize or args.chips or args.draw):
-        ap.error("--tiled goes with --anonymize, --chips or --draw")
+    if args.tiled and not (args.anonymize or args.chips or args.draw or args.scales):
+        ap.error("--tiled goes with --anonymize, --chips, --draw or --scales")
+    if args.scales and (args.fit or args.rotate):
+        ap.error("--scales goes with --tiled only, not with --fit or --rotate")
     if args.tiled and args.fit:
         ap.error("--tiled and --fit exclude each other")
     if args.tiled and args.rotate:
@@ -212,17 +249,20 @@ def main(argv=None):
     if args.anonymize and args.chips:
         ap.error("--anonymize and --chips are separate runs")
     if args.draw:
-        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate)
+        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales)
     elif args.chips:
-        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate)
+        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales)
     elif args.anonymize and args.blur is not None:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales)
     elif args.anonymize:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales)
     else:
         from .centerface import CenterFace
         frame = imread(args.image)
-        if args.fit:
+        if args.scales:
+            detector, frame, views = _views_detector(frame, args.scales, args.tiled, "bf16", args.flip)
+            dets, _ = detector.detect_views(frame[None], **views)[0]
+        elif args.fit:
             detector = _fit_detector(args.fit, "bf16", args.flip)
             dets, _ = detector.detect_fit(frame[None], rotate=args.rotate)[0]
         elif args.rotate:

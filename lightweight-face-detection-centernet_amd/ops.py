@@ -432,6 +432,61 @@ def unfit_rows(frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, anc
     return od, ol, oc, fl
 
 
+def view_layout(h, w, H, W, tile=None, overlap=None, scales=(1.0,), anchor="center"):
+    """The views of multi-scale detection (``cf_view_layout``; host only): int32 [V][8] rows (sx0, sy0, sw, sh, dx, dy, dw, dh) for an
+    h x w frame in an H x W canvas.  Tiles first (``tile`` = one int or (tile_h, tile_w), None: no tiles; only when there is more than
+    one), each filling the canvas; then one whole-frame level per entry of ``scales`` (fractions of the fitted size, rounded to per
+    mille, each within 0.001 .. 1.0), placed by ``anchor`` ('center' | 'topleft').  No accuracy claim is made for any layout."""
+    o = _lib.view_opts(tile, overlap, scales, anchor)
+    n = C.c_int(0)
+    L = _lib.lib()
+    _lib.check(L.cf_view_layout(C.byref(o), int(h), int(w), int(H), int(W), None, 0, C.byref(n)), op=True)
+    tab = (_lib.View * max(n.value, 1))()
+    _lib.check(L.cf_view_layout(C.byref(o), int(h), int(w), int(H), int(W), tab, n.value, C.byref(n)), op=True)
+    return np.array([[v.sx0, v.sy0, v.sw, v.sh, v.dx, v.dy, v.dw, v.dh] for v in tab[:n.value]], np.int32).reshape(-1, 8)
+
+
+def cut_views(frames, views, size, fmt="bgr", fill=(0, 0, 0), device=0):
+    """The views cutter (``cf_op_views``): uint8 [Bf, V, H, W, 3] BGR canvases of ``size`` = (H, W); canvas (f, v) is ``fill`` (B, G, R)
+    with the source rectangle of ``views[v]`` = (sx0, sy0, sw, sh, dx, dy, dw, dh) of frame f, converted to BGR (4:2:0 formats) and
+    resized to (dh, dw) with the taps clamped at the rectangle's edges, pasted at (dy, dx).  ``frames`` as ``cut_tiles`` takes them; they
+    are only read."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    vt, V = _lib.view_table(views)
+    H, W = int(size[0]), int(size[1])
+    fb = _lib.fill_bytes(fill)
+    out = np.empty((B, V, H, W, 3), np.uint8)
+    _lib.check(_lib.lib().cf_op_views(device, _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, vt, V, fb, H, W, ptr(out)), op=True)
+    del keep
+    return out
+
+
+def merge_views(views, frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, metric="ios", thresh=0.5, edge=2.0, dets=None, lms=None,
+                device=0):
+    """The merge of per-view detections (``cf_op_merge_views``): dets_net [Bf, V, rows, 4] box corners, scores [Bf, V, rows], lms_net
+    [Bf, V, rows, 10] in the coordinates of a ``net_hw`` = (H, W) canvas, counts [Bf, V]; per view the rows below min(count, rows) are
+    filtered (finite corners, centre inside the content, the edge rule at content sides whose source side is interior to the frame),
+    mapped into the ``frame_hw`` = (h, w) frame and de-duplicated per frame by greedy NMS with ``metric`` ('iou' | 'ios') and ``thresh``.
+    Returns (dets [Bf, max_out, 5], lms [Bf, max_out, 10], counts [Bf], flags [Bf]); rows at and past a frame's count keep the bytes of
+    the ``dets`` / ``lms`` arrays passed in (zeros by default)."""
+    vt, V = _lib.view_table(views)
+    d = np.ascontiguousarray(dets_net, dtype=np.float32)
+    if d.ndim != 4 or d.shape[1] != V or d.shape[3] != 4:
+        raise ValueError("dets_net must be [Bf, V=%d, rows, 4], got %s" % (V, d.shape))
+    Bf, _, rows, _ = d.shape
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(Bf, V, rows)
+    lm = np.ascontiguousarray(lms_net, dtype=np.float32).reshape(Bf, V, rows, 10)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(Bf, V)
+    max_out = int(max_out)
+    od = np.zeros((Bf, max_out, 5), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(Bf, max_out, 5)
+    ol = np.zeros((Bf, max_out, 10), np.float32) if lms is None else np.ascontiguousarray(lms, dtype=np.float32).reshape(Bf, max_out, 10)
+    oc, fl = np.zeros((Bf,), np.int32), np.zeros((Bf,), np.int32)
+    o = _lib.merge_opts(metric, thresh, edge)
+    _lib.check(_lib.lib().cf_op_merge_views(device, C.byref(o), vt, V, Bf, int(frame_hw[0]), int(frame_hw[1]), int(net_hw[0]), int(net_hw[1]),
+                                            ptr(d), ptr(sc), ptr(lm), ptr(cn), rows, max_out, ptr(od), ptr(ol), ptr(oc), ptr(fl)), op=True)
+    return od, ol, oc, fl
+
+
 def rot_geometry(h, w, H, W, rot, fit=None):
     """The placement of the UPRIGHT view of a stored h x w frame in an H x W canvas (``cf_rot_geometry``, host only): (rw, rh, dx, dy).
     ``rot``: the clockwise turn (0, 90, 180, 270) that makes the frame upright; ``fit`` as ``_lib.rot_opts`` takes it (None: stretch)."""

@@ -592,8 +592,8 @@ int cf_forward_rot(cf_ctx* ctx, const cf_rot_opts* opts, int format, const cf_yu
  * crop: the taps clamp at the source rectangle's edges.  A view with (dx, dy, dw, dh) = (0, 0, W, H) is the tile of cf_forward_tiles,
  * byte for byte; a view with the whole frame as source and the rectangle of cf_fit_geometry as content is the canvas of cf_forward_fit,
  * byte for byte; a source of exactly the content's size reproduces the source bytes.
- * Limits, plainly: one view per canvas -- a half-size level costs a whole forward for a quarter of a canvas, and packing several levels
- * into one canvas is not built; no rotated views (cf_forward_rot stays a single-view path). */
+ * Limits, plainly: cf_forward_views puts one view per canvas -- a half-size level costs a whole forward for a quarter of a canvas;
+ * the packing of several levels and frames into one canvas is cf_forward_packed below; no rotated views (cf_forward_rot stays a single-view path). */
 typedef struct cf_view {
     int32_t sx0, sy0, sw, sh;    /* frame pixels; all even, sw, sh >= 2, inside the frame */
     int32_t dx, dy, dw, dh;      /* canvas pixels; dw, dh >= 1, inside (H, W); may be odd */
@@ -647,6 +647,64 @@ int cf_forward_views(cf_ctx* ctx, int format, const cf_yuv_planes* frames, int i
  * cf_forward_views with a threshold decode behind it. */
 int cf_merge_views(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags,
                    int out_on_device);
+
+/* ---- packed views: several levels and frames share one canvas ---------------------------------
+ * cf_forward_views spends a whole canvas on every view: levels 1.0, 0.5 and 0.25 of a 1080p frame in 640 x 640 are three canvases per
+ * frame, the third one 1/16 full.  A PLACEMENT puts one view of one frame into one canvas, and a canvas may hold many:
+ *   cf_pack_views (host) -> cf_forward_packed -> cf_decode_threshold* (unchanged, per canvas) -> cf_merge_packed [-> cf_track_update | ...]
+ * Canvas n of a packed batch of N canvases is `fill` everywhere; inside the content rectangle of every placement with canvas == n it is
+ * the cf_forward_views image of that view of frame `frame`, byte for byte: the same conversion, the same fixed-point resize of the crop,
+ * taps clamped at the source rectangle.  The contents of one canvas must not overlap (sharing an edge is allowed); a canvas without a
+ * placement is all fill.  The placement list {f, f * V + v, views[v]} for f < Bf, v < V reproduces cf_forward_views byte for byte and
+ * cf_merge_views bit for bit.
+ * Limits, plainly: the threshold decode's own NMS and its max_out are per CANVAS, so they are shared by the frames on that canvas; boxes
+ * of two frames whose contents share an edge can suppress each other in that NMS when they overlap -- a gutter keeps them apart;
+ * cf_align_faces behind a packed forward works per canvas image; no rotated views; all frames of a call have one size.  The gutter
+ * default of the Python layer (0) is this project's choice; nobody has measured it (no trained weights, no labelled set). */
+typedef struct cf_place {
+    int32_t frame, canvas;       /* frame in [0, Bf), canvas in [0, N) */
+    cf_view view;                /* the source rectangle of the frame and the content rectangle in that canvas */
+} cf_place;                      /* 40 bytes */
+/* First-fit shelf packer; host only.  Items are the Bf * V (frame, view) pairs, frame-major (f ascending, then v ascending); an item
+ * carries its view's (dw, dh), the view's own dx, dy are replaced.  Canvases are kept in creation order; a canvas has shelves
+ * (y, height, x_next) in creation order and a y_next.  For each item, go through the canvases in order:
+ *   1. through the canvas's shelves in order: if dh <= height and x_next + dw <= W, place the item at (x_next, y), x_next += dw + gutter;
+ *   2. otherwise, if y_next + dh <= H, open a shelf y = y_next, height = dh, x_next = dw + gutter: the item at (0, y),
+ *      y_next = y + dh + gutter;
+ *   3. if no canvas takes the item, open a new canvas with the item at (0, 0) (its first shelf, by rule 2).
+ * A view whose content is the whole canvas (a tile view) therefore gets a canvas of its own.  places[k] is item k (frame = k / V, view
+ * k % V).  1080 x 1920 frames, 640 x 640 canvas, levels 1000, 500 and 250, Bf = 2, gutter 0, as (canvas, dx, dy):
+ *   frame 0: (0, 0, 0), (0, 0, 360), (0, 320, 360); frame 1: (1, 0, 0), (1, 0, 360), (0, 480, 360); two canvases;
+ *   gutter 16: (0, 0, 0), (0, 0, 376), (0, 336, 376), (1, 0, 0), (1, 0, 376), (1, 336, 376).
+ * *n_places = Bf * V and *n_canvases are the numbers wanted; only the first `cap` placements are written.  CF_EINVAL, cf_op_last_error
+ * naming the cause, for NULL views, n_places or n_canvases (or places with cap > 0), V < 1, Bf < 1, gutter < 0, cap < 0, H or W below 1,
+ * a view with dw > W or dh > H, dw or dh below 1.  gutter = fill between contents. */
+int cf_pack_views(const cf_view* views, int V, int Bf, int H, int W, int gutter, cf_place* places, int cap, int* n_places, int* n_canvases);
+/* Bf frames of h x w in `format` and P placements -> the network batch of N canvases stated above -> forward.  Frames, formats, pitches,
+ * the staging of host frames, the alignment of device planes and the even-sides rule exactly as for cf_forward_views; 1 <= N <=
+ * max_batch (half of it under the flip test), 1 <= P, frame in [0, Bf), canvas in [0, N); every view passes the checks of
+ * cf_forward_views' view table (the placement named by its index); two overlapping contents on one canvas are CF_EINVAL with both
+ * placement indices in cf_last_error.  Every refusal comes before anything is enqueued; with ctx == NULL the arguments are still checked
+ * (the content only for dx, dy >= 0 and dw, dh >= 1 as there is no canvas) and cf_op_last_error names the cause.  The cutter is ONE
+ * launch that writes all N canvases, one writer per byte; a canvas tile no placement touches is stored as fill without reading a frame;
+ * every tap lies inside its placement's source rectangle, pitch padding is never read; the frames are not modified.  The context
+ * remembers the placements for cf_merge_packed until any other forward or upload.  Under cf_set_flip_test it mirrors whole canvases, as
+ * cf_forward_views does.  cf_get_resized_input returns the N canvases.  cf_merge_views, cf_merge_tiles and cf_unfit_rows behind it are
+ * CF_ESTATE. */
+int cf_forward_packed(cf_ctx* ctx, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0, int pitch1,
+                      const cf_place* places, int P, int N, const uint8_t* fill);
+/* Merges the rows the LAST THRESHOLD DECODE kept for the N canvases of the last cf_forward_packed, per frame.  Frame f's candidates are
+ * the rows i < min(count, the decode's max_out) of the canvas of each of its placements, walked in (placement index ascending, row
+ * ascending) order.  Each row is tested against THAT placement's content with the three drop rules of cf_merge_views and mapped by the
+ * same float64 expression; the greedy NMS of cf_merge_tiles then runs unchanged.  A row whose centre lies in another frame's content
+ * fails this placement's centre rule and is picked up when that other placement is walked; a row whose centre lies in the fill belongs
+ * to nobody.  flags bit 0 of frame f: a canvas that holds one of its placements had more rows than the decode's max_out.  The
+ * compaction is a prefix sum: no atomics, deterministic.  The candidate capacity per frame is (most placements of any frame) x the
+ * decode's max_out, and the CF_ENOMEM bound of cf_merge_views applies to it.  Outputs and out_on_device forms as cf_merge_views.
+ * Afterwards the context is in the state behind a merge, with Bf frames of (h, w): every consumer takes the rows unchanged; before
+ * cf_merge_packed they return CF_ESTATE.  CF_ESTATE unless the last forward was cf_forward_packed with a threshold decode behind it. */
+int cf_merge_packed(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags,
+                    int out_on_device);
 
 /* ---- face tracks across video frames: cover faces through detection dropouts -----------------
  * Every entry point above treats a frame as if it were the only one: the frame in which a face scores just under the threshold goes out
@@ -1469,6 +1527,16 @@ int cf_op_views(int device, int format, const cf_yuv_planes* host_frames, int Bf
 int cf_op_merge_views(int device, const cf_merge_opts* opts, const cf_view* views, int V, int Bf, int h, int w, int H, int W,
                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
                       float* dets, float* lms, int32_t* out_counts, int32_t* flags);
+/* The cutter of cf_forward_packed alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up): canvases
+ * [N][H][W][3].  W % 4 == 0, N * H * W * 3 < 2^31.  The same validation, before any device is touched; nothing is written on refusal. */
+int cf_op_packed(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1,
+                 const cf_place* places, int P, int N, const uint8_t* fill, int H, int W, uint8_t* canvases);
+/* The merge of cf_merge_packed alone, on host tables: dets_net [N][rows][4], scores [N][rows], lms_net [N][rows][10], counts [N] ->
+ * dets [Bf][max_out][5], lms [Bf][max_out][10], out_counts [Bf], flags [Bf].  dets and lms are copied up first, so rows the kernels do
+ * not write come back as the caller filled them.  The placements are checked as cf_forward_packed checks them. */
+int cf_op_merge_packed(int device, const cf_merge_opts* opts, const cf_place* places, int P, int N, int Bf, int h, int w, int H, int W,
+                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                       float* dets, float* lms, int32_t* out_counts, int32_t* flags);
 /* The fit kernel of cf_forward_fit alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up, so the
  * padding bytes are on the device beside the pixels): canvas [B][H][W][3] uint8.  W % 4 == 0, B * H * W * 3 < 2^31.  The same
  * validation, before any device is touched; nothing is written on refusal. */

@@ -56,6 +56,7 @@ EXPORTS = (
     "cf_fit_geometry", "cf_forward_fit", "cf_unfit_rows", "cf_op_fit", "cf_op_unfit",
     "cf_rot_geometry", "cf_forward_rot", "cf_op_rot", "cf_op_unrot",
     "cf_view_layout", "cf_forward_views", "cf_merge_views", "cf_op_views", "cf_op_merge_views",
+    "cf_pack_views", "cf_forward_packed", "cf_merge_packed", "cf_op_packed", "cf_op_merge_packed",
     "cf_set_flip_test", "cf_op_mirror", "cf_op_flip_heads",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_create_weak", "cf_op_track_weak",
@@ -283,6 +284,20 @@ def view_table(views):
     tab = (View * max(len(r), 1))()
     for v, row in enumerate(r.tolist()):
         (tab[v].sx0, tab[v].sy0, tab[v].sw, tab[v].sh, tab[v].dx, tab[v].dy, tab[v].dw, tab[v].dh) = row
+    return tab, len(r)
+
+
+class Place(C.Structure):
+    """cf_place: one view of frame ``frame`` in canvas ``canvas`` (the view's content rectangle is its place in that canvas)."""
+    _fields_ = [("frame", C.c_int32), ("canvas", C.c_int32), ("view", View)]
+
+
+def place_table(places):
+    """(Place table, P) of an int array-like [P][10] of (frame, canvas, sx0, sy0, sw, sh, dx, dy, dw, dh) rows."""
+    r = np.ascontiguousarray(places, dtype=np.int32).reshape(-1, 10)
+    tab = (Place * max(len(r), 1))()
+    if len(r):
+        C.memmove(tab, r.ctypes.data, r.nbytes)
     return tab, len(r)
 
 
@@ -645,6 +660,11 @@ def lib():
         L.cf_merge_views.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.cf_op_views.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(View), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.cf_op_merge_views.argtypes = [C.c_int, C.POINTER(MergeOpts), C.POINTER(View)] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
+        L.cf_pack_views.argtypes = [C.POINTER(View)] + [C.c_int] * 5 + [C.POINTER(Place), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.cf_forward_packed.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(Place), C.c_int, C.c_int, C.c_void_p]
+        L.cf_merge_packed.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.cf_op_packed.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(Place), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.cf_op_merge_packed.argtypes = [C.c_int, C.POINTER(MergeOpts), C.POINTER(Place)] + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
         L.cf_rot_geometry.argtypes = [C.POINTER(RotOpts)] + [C.c_int] * 4 + [C.POINTER(FitGeom)]
         L.cf_forward_rot.argtypes = [C.c_void_p, C.POINTER(RotOpts), C.c_int, C.c_void_p] + [C.c_int] * 6
         L.cf_op_rot.argtypes = [C.c_int, C.POINTER(RotOpts), C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]

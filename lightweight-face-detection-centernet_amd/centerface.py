@@ -508,8 +508,8 @@ class Engine(object):
         rectangle of the canvas; ``ops.view_layout`` makes them) of every frame as one batch of Bf * V canvases (``cf_forward_views``);
         image f * V + v is ``fill`` (B, G, R) with the source of view v of frame f resized into its content rectangle.  ``frames`` and the
         ``on_device`` form as ``forward_tiles_enqueue`` takes them; they are only read.  A ``decode_threshold`` then gives the per-view
-        results and ``merge_views`` the per-frame ones.  One view per canvas: a half-size level costs a whole forward; packing several
-        levels into one canvas is not built, nor are rotated views.  No accuracy claim is made: the argument is geometric."""
+        results and ``merge_views`` the per-frame ones.  One view per canvas: a half-size level costs a whole forward; ``forward_packed_enqueue``
+        packs several levels and frames into one canvas; there are no rotated views.  No accuracy claim is made: the argument is geometric."""
         f = _lib.frame_format(fmt)
         vt, V = _lib.view_table(views)
         fb = _lib.fill_bytes(fill)
@@ -538,6 +538,46 @@ class Engine(object):
         decode, no count is read on the host.  The context keeps the merged rows either way."""
         o = _lib.merge_opts(metric, thresh, edge)
         self._chk(self._L.cf_merge_views(self._h, C.byref(o), int(max_out), _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(counts_ptr), _lib.vp(flags_ptr), 1))
+
+    # -- packed views: several levels and frames share one canvas -----------------------------------
+    def forward_packed_enqueue(self, frames, places, n_canvases, fmt="bgr", *, fill=(0, 0, 0), on_device=False, h=None, w=None, pitch0=None,
+                               pitch1=None):
+        """Run ``n_canvases`` canvases that hold the placements ``places`` ([P][10] rows (frame, canvas, sx0, sy0, sw, sh, dx, dy, dw, dh):
+        one view of one frame in one canvas; ``ops.pack_views`` makes them) as one batch (``cf_forward_packed``): canvas n is ``fill``
+        (B, G, R) and, inside the content of every placement with canvas == n, what ``forward_views_enqueue`` makes of that view of that
+        frame, byte for byte.  The contents of one canvas must not overlap (sharing an edge is allowed).  ``frames`` and the ``on_device``
+        form as ``forward_views_enqueue`` takes them; they are only read.  A ``decode_threshold`` then gives the per-CANVAS results --
+        its NMS and its max_out are shared by the frames on a canvas, and boxes of two frames whose contents share an edge can suppress
+        each other there; a gutter keeps them apart -- and ``merge_packed`` the per-frame ones.  No rotated views.  No accuracy claim is
+        made: the argument is geometric."""
+        f = _lib.frame_format(fmt)
+        pt, P = _lib.place_table(places)
+        fb = _lib.fill_bytes(fill)
+        if on_device:
+            tab, B, h, w, pitch0, pitch1 = _lib.device_input_planes("forward_packed_enqueue", frames, f, h, w, pitch0, pitch1)
+        else:
+            tab, B, h, w, pitch0, pitch1, self._last.keep = _lib.frame_planes(frames, fmt, writable=False)
+        self._chk(self._L.cf_forward_packed(self._h, f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, pt, P, int(n_canvases), fb))
+        self.last_B = int(n_canvases)
+        self._last.tiles = (B, 1)
+
+    def merge_packed(self, metric="ios", thresh=0.5, edge=2.0, max_out=1024):
+        """Per-frame detections of the last packed forward (``cf_merge_packed``, host form): per frame the rows the preceding
+        ``decode_threshold`` kept on the canvas of each of its placements whose centre lies in THAT placement's content (a row centred in
+        another frame's content comes out in that frame; one centred in the fill belongs to nobody), by the rules of ``merge_views``,
+        mapped into frame pixels and de-duplicated on the device.  Returns (results, flags) as ``merge_views``; flag bit 0: a canvas that
+        holds one of the frame's placements had more rows than the decode's max_out."""
+        Bf = (self._last.tiles or (1, 1))[0]                             # (without a packed forward the library refuses: CF_ESTATE)
+        o = _lib.merge_opts(metric, thresh, edge)
+        flags = np.empty((Bf,), np.int32)
+        return self._rows(Bf, max_out, lambda cap, dets, lms, counts: self._L.cf_merge_packed(
+            self._h, C.byref(o), cap, _lib.ptr(dets), _lib.ptr(lms), _lib.ptr(counts), _lib.ptr(flags), 0)), flags
+
+    def merge_packed_device(self, max_out, dets_ptr=None, lms_ptr=None, counts_ptr=None, flags_ptr=None, *, metric="ios", thresh=0.5, edge=2.0):
+        """Same, writing into caller-owned DEVICE buffers as ``merge_views_device``: asynchronous on the engine's main stream behind the
+        decode, no count is read on the host.  The context keeps the merged rows either way."""
+        o = _lib.merge_opts(metric, thresh, edge)
+        self._chk(self._L.cf_merge_packed(self._h, C.byref(o), int(max_out), _lib.vp(dets_ptr), _lib.vp(lms_ptr), _lib.vp(counts_ptr), _lib.vp(flags_ptr), 1))
 
     # -- aspect-preserving (letterbox) input -------------------------------------------------------
     def forward_fit_enqueue(self, frames, fmt="bgr", *, anchor="center", upscale=True, fill=(0, 0, 0), on_device=False, h=None, w=None,
@@ -1272,7 +1312,7 @@ class EngineRing(object):
             pass
 
 
-_RESCALE, _UNFIT, _MERGE, _VIEWS = "rescale", "unfit", "merge", "views"      # how a plan's rows reach frame space: the four cases of ``_Plan.rows``
+_RESCALE, _UNFIT, _MERGE, _VIEWS, _PACKED = "rescale", "unfit", "merge", "views", "packed"      # how a plan's rows reach frame space: the five cases of ``_Plan.rows``
 _Frames = collections.namedtuple("_Frames", "array fmt options")        # the cover, draw and follow steps: the array a chunk's slice of which they work on
 _Scene = collections.namedtuple("_Scene", "scenes array fmt")           # the scene check: the ``SceneCuts`` and the array it looks at
 _Best = collections.namedtuple("_Best", "shots array fmt template flush sink")      # the best shots: where the chips are cut, where the collect goes
@@ -1281,8 +1321,8 @@ _Plan = collections.namedtuple("_Plan", (
     "frames",        # the source the forward reads, sliced per chunk: an array or a list of frames
     "forward",       # the enqueue that takes any slice of ``frames``
     "per",           # frames per chunk
-    "rows",          # how the rows reach frame space: _RESCALE (the decode rescales), _UNFIT (``Engine.unfit_rows``), _MERGE or _VIEWS
-    "merge",         # (metric, thresh, edge) of ``Engine.merge_tiles`` for _MERGE, of ``Engine.merge_views`` for _VIEWS
+    "rows",          # how the rows reach frame space: _RESCALE (the decode rescales), _UNFIT (``Engine.unfit_rows``), _MERGE, _VIEWS or _PACKED
+    "merge",         # (metric, thresh, edge) of ``Engine.merge_tiles`` for _MERGE, of ``Engine.merge_views`` for _VIEWS, of ``Engine.merge_packed`` for _PACKED
     "out",           # the output copy that is returned with the results, or None
     "tracker",       # the ``Tracker`` that every detected chunk advances, or None
     "scene",         # _Scene: every chunk is first checked for scene cuts, which frees the tracks of a cut stream
@@ -1484,7 +1524,7 @@ class CenterFace(object):
         else:
             array = frames
         if views is not None:
-            (forward, per), src, rows = self._views_form(array, fmt_, views, cover is not None or draw is not None), array, _VIEWS
+            (forward, per), src, rows = self._views_form(array, fmt_, views, cover is not None or draw is not None), array, _PACKED if views.get("pack") else _VIEWS
             merge = (views["metric"], views["thresh"], views["edge"])
         elif rotate:                                                              # (fit None: the upright view is stretched)
             src, forward, rows = array, lambda chunk: eng.forward_rot_enqueue(chunk, fmt_, rotate, fit=fit), _UNFIT
@@ -1552,7 +1592,7 @@ class CenterFace(object):
             else:
                 eng.decode_threshold(score, self.nms_thresh, self.max_dets)
                 rows = (eng.unfit_rows(self.max_dets) if plan.rows == _UNFIT else eng.merge_views(*plan.merge, self.max_dets) if plan.rows == _VIEWS
-                        else eng.merge_tiles(*plan.merge, self.max_dets))
+                        else eng.merge_packed(*plan.merge, self.max_dets) if plan.rows == _PACKED else eng.merge_tiles(*plan.merge, self.max_dets))
                 res = self._postprocess_many(rows[0], rescaled=True)
             if plan.tracker is not None:
                 eng.track_update_device(plan.tracker, i)
@@ -1673,15 +1713,37 @@ class CenterFace(object):
         h, w = _lib.frame_planes(frames, fmt, writable=writable)[2:4]
         from . import ops
         table = ops.view_layout(h, w, self.img_h_new, self.img_w_new, views["tile"], views["overlap"], views["scales"], views["anchor"])
+        if views.get("pack"):
+            return self._packed_form(table, len(frames), fmt, views)
         per = self.engine.max_batch // len(table)
         if per < 1:
             raise ValueError("%d views per frame need max_batch >= %d (this instance has %d)" % (len(table), len(table), self.engine.max_batch))
         return lambda chunk: self.engine.forward_views_enqueue(chunk, table, fmt, fill=views["fill"]), per
 
+    def _packed_form(self, table, n_frames, fmt, views):
+        """(forward, frames per chunk) of the packed views paths: frames per chunk is the largest Bf whose packed canvas count
+        (``ops.pack_views``) fits ``max_batch`` -- the count is monotone in Bf, so the search goes upward -- and every chunk is packed for
+        its own length (the last one may be shorter), the layouts cached by length."""
+        from . import ops
+        size, cap, layouts = (self.img_h_new, self.img_w_new), self.engine.max_batch, {}
+
+        def layout(Bf):
+            if Bf not in layouts:
+                layouts[Bf] = ops.pack_views(table, Bf, size, views.get("gutter", 0))
+            return layouts[Bf]
+        if layout(1)[1] > cap:
+            raise ValueError("the %d views of one frame pack into %d canvases and need max_batch >= %d (this instance has %d)"
+                             % (len(table), layout(1)[1], layout(1)[1], cap))
+        per = 1
+        while per < n_frames and layout(per + 1)[1] <= cap:
+            per += 1
+        return lambda chunk: self.engine.forward_packed_enqueue(chunk, *layout(len(chunk)), fmt, fill=views["fill"]), per
+
     @staticmethod
     def _views_options(views, tiled=False, fit=None, rotate=0):
         """The ``views`` argument of the product paths -> None, or the options of ``detect_views``' path with every default filled in:
-        ``views`` None / False, True (the defaults) or a dict with scales, tile, overlap, anchor, fill, metric, thresh and / or edge.
+        ``views`` None / False, True (the defaults) or a dict with scales, tile, overlap, anchor, fill, metric, thresh, edge, pack and / or
+        gutter (``pack``: several views and frames share a canvas, ``ops.pack_views`` with ``gutter`` pixels of fill between them).
         ``views`` excludes ``tiled=True``, ``fit`` and ``rotate``: the layout has its own tiles and its own fit, and no rotated views."""
         if views is None or views is False:
             return None
@@ -1690,27 +1752,40 @@ class CenterFace(object):
                 raise ValueError("views= and %s exclude each other: the views have their own tiles and their own fit, and rotated views are not covered" % name)
         o = dict(scales=(1.0, 0.5), tile=None, overlap=None, anchor="center", fill=(0, 0, 0), metric="ios", thresh=0.5, edge=2.0)
         given = dict(views) if isinstance(views, dict) else {}
-        if set(given) - set(o):
-            raise ValueError("views takes %s, got %s" % (", ".join(sorted(o)), sorted(given)))
+        if set(given) - set(o) - {"pack", "gutter"}:                              # (pack and gutter: in the result only when given)
+            raise ValueError("views takes %s, got %s" % (", ".join(sorted(set(o) | {"pack", "gutter"})), sorted(given)))
         o.update(given)
         _lib.view_opts(o["tile"], o["overlap"], o["scales"], o["anchor"])       # refuse bad names and numbers before any work
         _lib.fill_bytes(o["fill"])
         _lib.merge_opts(o["metric"], o["thresh"], o["edge"])
+        if "gutter" in o:
+            o["gutter"] = int(o["gutter"])
+            if o["gutter"] < 0:
+                raise ValueError("gutter must not be negative, got %d" % o["gutter"])
+            if o["gutter"] and not o.get("pack"):
+                raise ValueError("gutter= goes with pack=True")
         return o
 
     def detect_views(self, frames, fmt="bgr", *, scales=(1.0, 0.5), tile=None, overlap=None, anchor="center", fill=(0, 0, 0), metric="ios",
-                     thresh=0.5, edge=2.0, redact=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None, flush=False):
+                     thresh=0.5, edge=2.0, redact=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None, flush=False,
+                     pack=False, gutter=0):
         """Multi-scale detection: every frame reaches the network as several VIEWS in one batch -- the aspect-true whole frame at each of
         ``scales`` (fractions of the fitted size; 0.5 shows a face that fills the frame at half the size, where a stride-4 centre
         detector holds together), placed by ``anchor`` on a canvas of ``fill``, and, with ``tile`` (``overlap``: default a fifth of the
         tile, rounded down to even), enlarged tiles in front of them -- and the per-view detections are mapped back and de-duplicated on
         the device (``Engine.merge_views``: ``metric``, ``thresh``, ``edge``).  ``frames`` as ``detect_tiled`` takes them, of any even
         size; ``max_batch`` must hold the views of one frame.  Returns (dets [n,5], lms [n,10]) per frame (``dets`` alone without
-        landmarks), in FRAME pixels, not floor-divided.  One view per canvas: a half-size level costs a whole forward for a quarter of a
-        canvas, packing several levels into one canvas is not built, and there are no rotated views.  The layout defaults and the
+        landmarks), in FRAME pixels, not floor-divided.  Without ``pack`` there is one view per canvas: a half-size level costs a whole
+        forward for a quarter of a canvas.  ``pack=True`` packs the views of the frames of a chunk into shared canvases
+        (``ops.pack_views``, first-fit shelves, ``gutter`` pixels of fill between contents; ``Engine.forward_packed_enqueue`` /
+        ``merge_packed``): levels 1.0, 0.5 and 0.25 of a 1080p frame then cost one 640 x 640 canvas per frame instead of three, and
+        ``max_batch`` must hold the canvases of one frame.  Packed, the threshold decode's NMS and ``max_dets`` are per canvas and so
+        shared by the frames on it, and boxes of two frames whose contents share an edge can suppress each other there: a gutter
+        keeps them apart.  There are no rotated views.  The layout defaults, ``gutter`` = 0 and the
         IoS 0.5 / edge 2 merge are this project's choices and nobody has measured them; no accuracy claim is made.  ``redact``,
         ``tracker``, ``follow``, ``detect``, ``scenes``, ``lookback`` and ``flush``: as ``detect_tiled``."""
-        views = self._views_options(dict(scales=scales, tile=tile, overlap=overlap, anchor=anchor, fill=fill, metric=metric, thresh=thresh, edge=edge))
+        views = self._views_options(dict(scales=scales, tile=tile, overlap=overlap, anchor=anchor, fill=fill, metric=metric, thresh=thresh, edge=edge,
+                                         **(dict(pack=True, gutter=gutter) if pack else dict(gutter=gutter) if gutter else {})))
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         if lookback is not None and redact is None:
@@ -1822,7 +1897,7 @@ class CenterFace(object):
         corridor-mode camera, phone video): the network sees the upright view (``Engine.forward_rot_enqueue``; stretched to the network
         input, or fitted with ``fit``), frames of any size; detections and redaction are in the pixels of the stored frame, not
         floor-divided; not together with ``tiled``; one turn per call; no accuracy claim is made.  ``views``: True, or a dict with scales,
-        tile, overlap, anchor, fill, metric, thresh and / or edge: detection by ``detect_views`` -- several views of every frame in one
+        tile, overlap, anchor, fill, metric, thresh, edge, pack and / or gutter: detection by ``detect_views`` -- several views of every frame in one
         batch, merged on the device -- on frames of any even size, the rows in frame pixels; not together with ``tiled``, ``fit`` or
         ``rotate``; no accuracy claim is made for it either."""
         return self._anonymize(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,

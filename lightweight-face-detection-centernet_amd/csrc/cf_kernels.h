@@ -538,6 +538,27 @@ struct ViewMergeParams {
 };
 hipError_t launch_merge_views(hipStream_t s, const ViewMergeParams& p);
 
+// Packed views (cf_views.hip; the statement is in include/centerface_hip.h).  pack_views: the shelf packer of cf_pack_views (host only;
+// the arguments have been checked).  pack_check: nullptr, or what is wrong with P placements of Bf frames of h x w in N canvases of
+// H x W -- ranges, every view by views_table_check's rules, two overlapping contents on one canvas (both indices named; host only).
+// pack_table: the ONE device blob of a packed batch, built on the host: the placements sorted by canvas (stable), the CSR of that order
+// by canvas [N + 1], the CSR by frame [Bf + 1] with, per frame, the sorted positions of its placements in placement-index order [P], and
+// the plane addresses 3 x Bf (YV12's chroma planes swapped: the I420 kernel serves both).  PackDev: the blob's parts on the device.
+int pack_views(const cf_view* views, int V, int Bf, int H, int W, int gutter, cf_place* places, int cap, int* n_canvases);
+const char* pack_check(std::string& why, int h, int w, const cf_place* places, int P, int N, int Bf, int H, int W);
+struct PackHost { std::vector<unsigned char> blob; size_t off_cv, off_fr, off_idx, off_planes; int most; };      // most: placements of any frame, at most
+PackHost pack_table(const cf_place* places, int P, int N, int Bf, const void* const* planes, int format);
+struct PackDev { const cf_place* places; const int* cv_off; const int* fr_off; const int* fr_idx; const uint8_t* const* planes; };
+inline PackDev pack_dev(const PackHost& t, const void* dev) {
+    const unsigned char* b = (const unsigned char*)dev;
+    return PackDev{(const cf_place*)b, (const int*)(b + t.off_cv), (const int*)(b + t.off_fr), (const int*)(b + t.off_idx), (const uint8_t* const*)(b + t.off_planes)};
+}
+// dst [N][H][W][3] uint8 BGR, every byte written once by one launch; the caller has run views_check's frame part and pack_check
+hipError_t launch_cut_packed(hipStream_t s, int format, const PackDev& t, int N, int pitch0, int pitch1, const uint8_t* fill, uint8_t* dst, int H, int W);
+// The merge of the per-canvas results of a threshold decode over N canvases: ViewMergeParams with the placements in the place of the
+// views (p.views unused, p.V = PackHost::most: cap = most * rows, workspace sizes as merge_mask_bytes(Bf, most, rows)).
+hipError_t launch_merge_packed(hipStream_t s, const ViewMergeParams& p, const PackDev& t);
+
 // Flip test (cf_flip.hip; the statement is in include/centerface_hip.h).  mirror_check: nullptr, or what is wrong with the format and sizes
 // of a batch to mirror (the text lives in `why`; host only).  launch_mirror_batch: dst holds 2B network inputs of in_format (uint8
 // [.][H][W][3] or float32 [.][3][H][W]; 16-byte aligned); images B .. 2B-1 become images 0 .. B-1 of src with their columns reversed and,

@@ -1055,6 +1055,91 @@ int cf_op_merge_views(int device, const cf_merge_opts* o, const cf_view* views, 
     return sc.result("cf_op_merge_views");
 }
 
+int cf_pack_views(const cf_view* views, int V, int Bf, int H, int W, int gutter, cf_place* places, int cap, int* n_places, int* n_canvases) {
+    char b[320];
+    const char* bad = nullptr;
+    if (!views || !n_places || !n_canvases || (cap > 0 && !places)) bad = "null views, places, n_places or n_canvases";
+    else if (V < 1) bad = "V must be at least 1";
+    else if (Bf < 1) bad = "Bf must be at least 1";
+    else if (gutter < 0) bad = "gutter must not be negative";
+    else if (cap < 0) bad = "cap must not be negative";
+    else if (H < 1 || W < 1) bad = "H and W must be at least 1";
+    else if ((long long)V * Bf > INT_MAX) bad = "more than 2^31 placements";
+    for (int v = 0; !bad && v < V; ++v) {
+        if (views[v].dw < 1 || views[v].dh < 1) { snprintf(b, sizeof b, "view %d has an empty content (dw = %d, dh = %d must be at least 1)", v, views[v].dw, views[v].dh); bad = b; }
+        else if (views[v].dw > W || views[v].dh > H) { snprintf(b, sizeof b, "view %d has a content of %d x %d, larger than the canvas %d x %d", v, views[v].dw, views[v].dh, W, H); bad = b; }
+    }
+    if (bad) return fail("cf_pack_views", bad);
+    *n_places = V * Bf;
+    return pack_views(views, V, Bf, H, W, gutter, places, cap, n_canvases);
+}
+
+// nullptr, or what is wrong with the frames and placements of a packed batch on host frames (the text lives in `why`)
+static const char* packed_check(std::string& why, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_place* places, int P, int N, int H, int W) {
+    if (Bf < 1) return "Bf must be at least 1";
+    if (H < 1 || W < 4 || (W & 3)) return "W must be a multiple of 4 and H at least 1";
+    if (const char* geo = frame_geometry_check(FrameGeo{format, Bf, h, w, pitch0, pitch1}, 2, true)) return geo;
+    return pack_check(why, h, w, places, P, N, Bf, H, W);
+}
+
+// The cutter of cf_forward_packed on host frames.
+int cf_op_packed(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1, const cf_place* places,
+                 int P, int N, const uint8_t* fill, int H, int W, uint8_t* canvases) {
+    std::string why;
+    const char* bad = packed_check(why, format, Bf, h, w, pitch0, pitch1, places, P, N, H, W);
+    if (!bad) bad = redact_check_planes(format, reinterpret_cast<const void* const*>(host_frames), Bf, 0, pitch0, pitch1);
+    if (!bad && (!fill || !canvases)) bad = "null fill or output";
+    if (!bad && N > 65535) bad = "more than 65535 canvases";
+    if (!bad && (long long)N * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
+    if (bad) return fail("cf_op_packed", bad);
+    Scope sc(device);
+    const std::vector<const void*> dev = up_planes(sc, format, reinterpret_cast<const void* const*>(host_frames), Bf, h, pitch0, pitch1);
+    const PackHost t = pack_table(places, P, N, Bf, dev.data(), format);
+    const unsigned char* blob = sc.in(t.blob.data(), t.blob.size());
+    uint8_t* out = sc.out(canvases, (size_t)N * H * W * 3);
+    sc.run([&] { return launch_cut_packed(sc.s, format, pack_dev(t, blob), N, pitch0, pitch1, fill, out, H, W); });
+    return sc.result("cf_op_packed");
+}
+
+int cf_op_merge_packed(int device, const cf_merge_opts* o, const cf_place* places, int P, int N, int Bf, int h, int w, int H, int W,
+                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                       float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+    std::string why;
+    const char* bad = nullptr;
+    if (!o || !dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags) bad = "null argument";
+    else if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) bad = "unknown metric (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)";
+    else if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) bad = "thresh and edge must be finite and not negative";
+    else if (rows < 1 || max_out < 1 || H < 1 || W < 1) bad = "rows, max_out, H and W must be at least 1";
+    else if (const char* geo = frame_geometry_check(FrameGeo{CF_FRAME_BGR, Bf, h, w, 3 * w, 0}, 2, true)) bad = geo;
+    else bad = pack_check(why, h, w, places, P, N, Bf, H, W);
+    if (bad) return fail("cf_op_merge_packed", bad);
+    const PackHost t = pack_table(places, P, N, Bf, nullptr, CF_FRAME_BGR);
+    const int V = t.most;
+    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit) {
+        g_op_error = "cf_op_merge_packed: the suppression bits of Bf x (most placements of a frame * rows) candidates exceed 256 MiB";
+        return CF_ENOMEM;
+    }
+    Scope sc(device);
+    const size_t n = (size_t)N * rows, cap = (size_t)V * rows, mo = (size_t)Bf * max_out;
+    const unsigned char* blob = sc.in(t.blob.data(), t.blob.size());
+    ViewMergeParams p{};
+    p.views = nullptr;
+    p.V = V; p.Bf = Bf; p.h = h; p.w = w;
+    p.dets_net = sc.in(dets_net, n * 4);
+    p.scores = sc.in(scores, n); p.score_stride = 1;
+    p.lms_net = sc.in(lms_net, n * 10);
+    p.counts = sc.in(counts, (size_t)N); p.rows = rows;
+    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
+    p.cand = sc.make<float>(Bf * cap * 16); p.cand_count = sc.make<int>(Bf);
+    p.order = sc.make<int>(Bf * cap); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, V, rows));
+    p.max_out = max_out;
+    p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
+    p.corners = sc.make<float>(mo * 4);
+    p.out_counts = sc.out(out_counts, Bf); p.flags = sc.out(flags, Bf);
+    sc.run([&] { return launch_merge_packed(sc.s, p, pack_dev(t, blob)); });
+    return sc.result("cf_op_merge_packed");
+}
+
 // nullptr, or what is wrong with the options and sizes of a fit geometry (the text lives in `why`)
 static const char* fit_geometry_check(std::string& why, const cf_fit_opts* o, int h, int w, int H, int W) {
     if (const char* bad = fit_check(why, o, CF_FRAME_BGR, 1, h, w, 3 * w, 0, 4, 4)) return bad;      // the options and the frame's sides

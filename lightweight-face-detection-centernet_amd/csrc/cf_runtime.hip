@@ -171,6 +171,10 @@ struct cf_ctx {
     // cf_forward_views: vw_V > 0 = the last forward was a views forward of tl_Bf frames of tl_h x tl_w (host copy of the views and the
     // device table, uploaded when they change); cf_merge_views leaves its rows where the tile merge leaves its own
     std::vector<cf_view> vw_views; DevBuf vw_dev; int vw_up = 0, vw_V = 0;
+    // cf_forward_packed: pk_P > 0 = the last forward was a packed one of tl_Bf frames of tl_h x tl_w in pk_N canvases (pk_tab: the host
+    // copy of the device blob pk_dev -- sorted placements, the two CSRs, the plane addresses -- uploaded when it changes); cf_merge_packed
+    // leaves its rows where the tile merge leaves its own
+    PackHost pk_tab; DevBuf pk_dev; int pk_up = 0, pk_P = 0, pk_N = 0;
     int ft_rot = 0;                     // cf_forward_rot: the turn beside ft_g (ft_g then places the upright view of the tl_h x tl_w frames)
     struct { DevBuf cand, cand_count, order, mask, dets, lms, corners, counts, flags; } tl;
     struct { DevBuf dets, lms, info, corners, counts, flags; } tk; int tk_M = 0;      // cf_track_update: the tracked rows, tk_M per image
@@ -678,7 +682,7 @@ int cf_destroy(cf_ctx* c) {
                     (void*)c->t_order, (void*)c->t_mask, (void*)(c->t_host ? nullptr : c->t_dets), (void*)(c->t_host ? nullptr : c->t_lms), (void*)c->t_counts, (void*)c->t_overflow,
                     (void*)c->t_lmsnet, (void*)c->al_off, (void*)c->t_detsnet})
         if (p) hipFree(p);
-    for (const DevBuf* b : {&c->src.buf, &c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->dr_recs, &c->tl_rects_dev, &c->vw_dev,
+    for (const DevBuf* b : {&c->src.buf, &c->al_chips, &c->al_mats, &c->rd_cells, &c->rd_stage, &c->bl_scratch, &c->dr_recs, &c->tl_rects_dev, &c->vw_dev, &c->pk_dev,
                             &c->tl.cand, &c->tl.cand_count, &c->tl.order, &c->tl.mask, &c->tl.dets, &c->tl.lms, &c->tl.corners, &c->tl.counts, &c->tl.flags,
                             &c->tk.dets, &c->tk.lms, &c->tk.info, &c->tk.corners, &c->tk.counts, &c->tk.flags, &c->fo.slot_moves, &c->fo.moves, &c->sn.part, &c->sn.out,
                             &c->bs.q, &c->bs.sc, &c->bs.jobs, &c->bs.flags, &c->bs.chips, &c->bs.off, &c->bs.out, &c->fl_in})
@@ -1185,7 +1189,7 @@ int forward_run(cf_ctx* c, const void* caller_in, int in_format, int Bcaller) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in.used;      // what cf_align_faces samples
-    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->ft_rot = 0; c->vw_V = 0; c->fo.B = 0; c->lb.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
+    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->ft_rot = 0; c->vw_V = 0; c->pk_P = 0; c->fo.B = 0; c->lb.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -1638,6 +1642,7 @@ enum RowsWanted {
     ROWS_OF_TILED_DECODE,    // the same, of a tiled forward (cf_merge_tiles)
     ROWS_OF_FIT_DECODE,      // the same, of a fitted forward (cf_unfit_rows)
     ROWS_OF_VIEWS_DECODE,    // the same, of a views forward (cf_merge_views)
+    ROWS_OF_PACKED_DECODE,   // the same, of a packed forward (cf_merge_packed)
     ROWS_UNTRACKED,          // the newest that no cf_track_update has consumed: the merged rows of a tiled forward, the mapped rows of a
                              // fitted one, else the decode's
     ROWS_UNSTEPPED,          // the tracked rows that no cf_lookback_step has consumed: the followed rows behind a follow, else the tracked rows
@@ -1662,13 +1667,14 @@ static int rows_for(cf_ctx* c, const char* who, RowsWanted want, RowSet& r) {
     if (want == ROWS_OF_TILED_DECODE && c->tl_T < 1) return c->fail(CF_ESTATE, "%s: the last forward was not cf_forward_tiles", who);
     if (want == ROWS_OF_FIT_DECODE && !c->ft_on) return c->fail(CF_ESTATE, "%s: the last forward was not cf_forward_fit", who);
     if (want == ROWS_OF_VIEWS_DECODE && c->vw_V < 1) return c->fail(CF_ESTATE, "%s: the last forward was not cf_forward_views", who);
+    if (want == ROWS_OF_PACKED_DECODE && c->pk_P < 1) return c->fail(CF_ESTATE, "%s: the last forward was not cf_forward_packed", who);
     if (!c->al_in) return c->fail(CF_ESTATE, "%s: an upload was started after the last forward, its input is gone", who);
     if (c->stage == ROWS_NONE || !c->t_detsnet || !c->t_dets || !c->t_lmsnet || !c->t_counts) return c->fail(CF_ESTATE, "%s without a threshold decode of the last forward", who);
     r = RowSet{c->t_detsnet, c->t_dets, c->t_lmsnet, c->t_counts, c->al_rows, c->last_B, c->H, c->W, false};
-    if (want == ROWS_OF_DECODE || want == ROWS_OF_TILED_DECODE || want == ROWS_OF_FIT_DECODE || want == ROWS_OF_VIEWS_DECODE) return CF_OK;
-    if (c->tl_T > 0 || c->ft_on || c->vw_V > 0) {
+    if (want == ROWS_OF_DECODE || want == ROWS_OF_TILED_DECODE || want == ROWS_OF_FIT_DECODE || want == ROWS_OF_VIEWS_DECODE || want == ROWS_OF_PACKED_DECODE) return CF_OK;
+    if (c->tl_T > 0 || c->ft_on || c->vw_V > 0 || c->pk_P > 0) {
         if (c->stage < ROWS_MERGED)
-            return c->fail(CF_ESTATE, c->vw_V > 0 ? "%s after cf_forward_views without a cf_merge_views of the last decode" : c->ft_on ? "%s after cf_forward_fit without a cf_unfit_rows of the last decode" : "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
+            return c->fail(CF_ESTATE, c->pk_P > 0 ? "%s after cf_forward_packed without a cf_merge_packed of the last decode" : c->vw_V > 0 ? "%s after cf_forward_views without a cf_merge_views of the last decode" : c->ft_on ? "%s after cf_forward_fit without a cf_unfit_rows of the last decode" : "%s after cf_forward_tiles without a cf_merge_tiles of the last decode", who);
         r = RowSet{(const float*)c->tl.corners.p, (const float*)c->tl.dets.p, (const float*)c->tl.lms.p, (const int*)c->tl.counts.p, c->tl_maxout, c->tl_Bf, c->tl_h, c->tl_w, true};
     }
     if (c->stage < ROWS_TRACKED) return want == ROWS_UNSTEPPED ? c->fail(CF_ESTATE, "%s without a cf_track_update or cf_track_follow behind the last decode", who) : CF_OK;
@@ -2172,6 +2178,95 @@ int cf_merge_views(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
     p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
     p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
     HIPCHK(c, launch_merge_views(c->stream, p));
+    c->stage = ROWS_MERGED; c->tl_maxout = max_out;
+    return write_out(c, out_on_device, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
+}
+
+// Packed forward: the packed cutter of cf_views.hip writes the N canvases to input_resized in one launch.  The device blob (sorted
+// placements, CSRs, plane addresses) is built per call -- the plane addresses are only known behind the staging -- and uploaded when it
+// differs from the one the device holds.
+int cf_forward_packed(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0, int pitch1,
+                      const cf_place* places, int P, int N, const uint8_t* fill) {
+    const void* const* planes = reinterpret_cast<const void* const*>(frames);
+    std::string text;
+    const int H = c ? c->H : 1 << 30, W = c ? c->W : 1 << 30;               // (no context, no canvas: as cf_forward_views)
+    const char* why = nullptr;
+    if (Bf < 1) why = "Bf must be at least 1";
+    else if (c && (W < 4 || (W & 3))) why = "W must be a multiple of 4";
+    else if (const char* geo = frame_geometry_check(FrameGeo{format, Bf, h, w, pitch0, pitch1}, 2, true)) why = geo;
+    else why = pack_check(text, h, w, places, P, N, Bf, H, W);
+    if (!why) why = redact_check_planes(format, planes, Bf, in_on_device, pitch0, pitch1);
+    if (!why && !fill) why = "null fill";
+    if (!c) {                                                                // the arguments are checked all the same (cf_op_last_error tells)
+        op_error_set((std::string("cf_forward_packed: ") + (why ? why : "null context")).c_str());
+        return CF_EINVAL;
+    }
+    if (why) return c->fail(CF_EINVAL, "cf_forward_packed: %s", why);
+    if (N > batch_cap(c))
+        return c->fail(CF_EINVAL, "cf_forward_packed: N = %d canvases exceed max_batch %d%s", N, batch_cap(c), c->flip ? " (flip test is on: half of max_batch)" : "");
+    if (int r = forward_begin(c, "cf_forward_packed", N)) return r;
+    uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
+    const uint8_t fv[3] = {fill[0], fill[1], fill[2]};
+    auto cut = [&](const void* const* pl, int p0, int p1) -> hipError_t {
+        PackHost t = pack_table(places, P, N, Bf, pl, format);
+        if (!c->pk_up || t.blob != c->pk_tab.blob) {
+            c->pk_up = 0;
+            if (c->pk_dev.bytes < t.blob.size()) {
+                hipError_t e = hipStreamSynchronize(c->stream);              // earlier launches may still read the table
+                if (e != hipSuccess) return e;
+                if (c->pk_dev.p) hipFree(c->pk_dev.p);
+                c->pk_dev = DevBuf{};
+                if ((e = hipMalloc(&c->pk_dev.p, t.blob.size())) != hipSuccess) { c->pk_dev.p = nullptr; return e; }
+                c->pk_dev.bytes = t.blob.size();
+            }
+            c->pk_tab = std::move(t);
+            hipError_t e = hipMemcpyAsync(c->pk_dev.p, c->pk_tab.blob.data(), c->pk_tab.blob.size(), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (only when the table changes: the host copy may be replaced next call)
+            if (e != hipSuccess) return e;
+            c->pk_up = 1;
+        }
+        return launch_cut_packed(c->stream, format, pack_dev(c->pk_tab, c->pk_dev.p), N, p0, p1, fv, dst, c->H, c->W);
+    };
+    if (in_on_device) HIPCHK(c, cut(planes, pitch0, pitch1));
+    else if (int r = src_stage_frames(c, "cf_forward_packed", FrameGeo{format, Bf, h, w, pitch0, pitch1}, planes, cut)) return r;
+    if (int r = forward_run(c, dst, CF_IN_U8_HWC_BGR, N)) return r;
+    c->pk_P = P; c->pk_N = N; c->tl_Bf = Bf; c->tl_h = h; c->tl_w = w;
+    return CF_OK;
+}
+
+// The merge of the last threshold decode's per-canvas rows by placement (cf_views.hip) on the stream that carried the decode; inputs,
+// workspace and outputs as cf_merge_views' with the most placements of any frame in the place of V.
+int cf_merge_packed(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
+    if (!c) return CF_EINVAL;
+    if (!o) return c->fail(CF_EINVAL, "cf_merge_packed: null options");
+    if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) return c->fail(CF_EINVAL, "cf_merge_packed: unknown metric %d (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)", o->metric);
+    if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge))
+        return c->fail(CF_EINVAL, "cf_merge_packed: thresh and edge must be finite and not negative");
+    if (max_out < 1) return c->fail(CF_EINVAL, "cf_merge_packed: max_out=%d must be at least 1", max_out);
+    RowSet in{};
+    if (int r = rows_for(c, "cf_merge_packed", ROWS_OF_PACKED_DECODE, in)) return r;
+    const int Bf = c->tl_Bf, V = c->pk_tab.most, rows = in.stride;
+    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit)
+        return c->fail(CF_ENOMEM, "cf_merge_packed: %d frames x %d placements x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
+                       Bf, V, rows, merge_mask_bytes(Bf, V, rows) / 1e6);
+    HIPCHK(c, hipSetDevice(c->device));
+    c->stage = ROWS_DECODED; c->fo.B = 0; c->lb.B = 0;    // the merged (and tracked, and followed) rows of an earlier call are gone from here on
+    const size_t cap = (size_t)V * rows, mo = (size_t)Bf * max_out, nb = (size_t)Bf * sizeof(int);
+    const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
+    auto& ws = c->tl;
+    const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
+        {ws.cand, Bf * cap * 16 * sizeof(float), "candidates"}, {ws.cand_count, nb, "candidate counts"}, {ws.order, Bf * cap * sizeof(int), "sort order"},
+        {ws.mask, merge_mask_bytes(Bf, V, rows), "suppression bits"}, {ws.dets, nd, "merged dets"}, {ws.lms, nl, "merged landmarks"},
+        {ws.corners, mo * 4 * sizeof(float), "merged corners"}, {ws.counts, nb, "merged counts"}, {ws.flags, nb, "flags"}};
+    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_merge_packed")) return r;
+    ViewMergeParams p{};
+    p.views = nullptr; p.V = V; p.Bf = Bf; p.h = c->tl_h; p.w = c->tl_w;
+    p.dets_net = in.corners; p.scores = in.dets + 4; p.score_stride = 5; p.lms_net = in.lms; p.counts = in.counts; p.rows = rows;
+    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
+    p.cand = (float*)ws.cand.p; p.cand_count = (int*)ws.cand_count.p; p.order = (int*)ws.order.p; p.mask = (unsigned long long*)ws.mask.p;
+    p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
+    p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
+    HIPCHK(c, launch_merge_packed(c->stream, p, pack_dev(c->pk_tab, c->pk_dev.p)));
     c->stage = ROWS_MERGED; c->tl_maxout = max_out;
     return write_out(c, out_on_device, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }

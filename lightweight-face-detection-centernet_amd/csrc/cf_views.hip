@@ -27,11 +27,17 @@
 //   * else X = (float)(((double)x - (double)dx) * ((double)sw / (double)dw) + (double)sx0), Y likewise, for the four corners and the
 //     ten landmark values (float64 in this order, no contraction: the file is built with -ffp-contract=off); the score is copied.
 // The compaction is a prefix sum over the flattened (view, row) items, never an atomic: the order is deterministic.
+//
+// PACKED VIEWS (further down).  A placement (cf_place) puts one view of one frame into one canvas, so several levels and frames share a
+// canvas: cut_packed_kernel writes all canvases in one launch, one writer per byte, and packed_collect_kernel walks a frame's placements;
+// the two kernels above are not touched by it.
 #include "cf_common.h"
 #include "cf_kernels.h"
 #include "cf_cvresize.h"
 #include "cf_yuvmath.h"
 #include "cf_fitpx.h"
+#include <algorithm>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -176,6 +182,168 @@ __global__ void __launch_bounds__(1024) views_collect_kernel(ViewMergeParams p) 
     if (tid == 0) { p.cand_count[f] = (int)base; p.flags[f] = truncated; }
 }
 
+// PACKED VIEWS.  A placement puts one view of one frame into one canvas; a canvas holds any number of them, disjoint.
+//
+// CUT.  One launch writes all N canvases, every byte once.  A workgroup owns a kPackTileW x kPackTileH tile of canvas blockIdx.y; its
+// lanes keep the shape of cut_views_kernel (four adjacent canvas columns, kViewRows rows, three dword stores per row), 32 lanes across
+// and 8 down.  The placements are sorted by canvas on the host (t.cv_off: the CSR).  In rounds of kPackList placements of its canvas,
+// every thread tests one against the tile and the hits are compacted into an LDS list (ballot, the four wave counts through LDS: no
+// atomic, the list is in placement order); a list can therefore not overflow, a canvas with more placements takes more rounds.  Every
+// lane then walks the list: a placement that reaches into its 4 x kViewRows pixels gets its column taps and coefficients computed once
+// and serves the lane's rows; the pixels live in registers from the first round to the stores at the end, `fill` where no placement
+// wrote.  A tile no placement touches stores fill and reads no frame.  Taps as view_tap: inside the placement's source rectangle.
+constexpr int kPackTileW = 128, kPackTileH = 8 * kViewRows;
+constexpr int kPackList = 256;
+
+template <int SRC, bool VF>
+__global__ void __launch_bounds__(256) cut_packed_kernel(PackDev t, uint8_t* dst, uint32_t fill, int pitch0, int pitch1, int H, int W, int tiles_x) {
+    __shared__ int s_list[kPackList];
+    __shared__ int s_cnt[4];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, n = (int)blockIdx.y;
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    const int tx0 = tx * kPackTileW, ty0 = ty * kPackTileH;
+    const int X0 = tx0 + 4 * (tid & 31), Y0 = ty0 + kViewRows * (tid >> 5);
+    const bool live = X0 < W && Y0 < H;                   // (W % 4 == 0: a live lane's four columns are inside)
+    uint32_t px[kViewRows][4];
+#pragma unroll
+    for (int i = 0; i < kViewRows; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) px[i][k] = fill;
+    const int k0 = t.cv_off[n], k1 = t.cv_off[n + 1];
+    for (int base = k0; base < k1; base += kPackList) {   // uniform trip count
+        const int cand = base + tid;
+        bool hit = false;
+        if (cand < k1) {
+            const cf_view r = t.places[cand].view;
+            hit = r.dx < tx0 + kPackTileW && r.dx + r.dw > tx0 && r.dy < ty0 + kPackTileH && r.dy + r.dh > ty0;
+        }
+        const unsigned long long m = __ballot(hit);
+        if (lane == 0) s_cnt[wave] = __popcll(m);
+        __syncthreads();
+        int at = 0, cnt = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < 4; ++w2) { if (w2 < wave) at += s_cnt[w2]; cnt += s_cnt[w2]; }
+        if (hit) s_list[at + __popcll(m & ((1ull << lane) - 1ull))] = cand;
+        __syncthreads();
+        if (live)
+            for (int j = 0; j < cnt; ++j) {
+                const cf_place& pl = t.places[__builtin_amdgcn_readfirstlane(s_list[j])];
+                const cf_view r = pl.view;
+                if (X0 + 4 <= r.dx || X0 >= r.dx + r.dw || Y0 + kViewRows <= r.dy || Y0 >= r.dy + r.dh) continue;      // not this lane's pixels
+                bool in[4];
+                int x0[4], x1[4], a0[4], a1[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int x = X0 + k - r.dx;
+                    in[k] = x >= 0 && x < r.dw;
+                    cv_linear_coeffs(min(max(x, 0), r.dw - 1), r.sw, r.dw, true, x0[k], x1[k], a0[k], a1[k]);      // a foreign column: the edge's taps, not used
+                    x0[k] += r.sx0; x1[k] += r.sx0;
+                }
+                const uint8_t* p0 = t.planes[3 * pl.frame];
+                const uint8_t* p1 = t.planes[3 * pl.frame + 1];
+                const uint8_t* p2 = t.planes[3 * pl.frame + 2];
+#pragma unroll
+                for (int i = 0; i < kViewRows; ++i) {
+                    const int y = Y0 + i - r.dy;
+                    if (y < 0 || y >= r.dh) continue;          // (inside the content, so inside the canvas)
+                    int y0, y1, b0, b1;
+                    cv_linear_coeffs(y, r.sh, r.dh, false, y0, y1, b0, b1);
+                    y0 += r.sy0; y1 += r.sy0;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t t00 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x0[k]);
+                        const uint32_t t01 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x1[k]);
+                        const uint32_t t10 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x0[k]);
+                        const uint32_t t11 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x1[k]);
+                        uint32_t ch[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const int s = 8 * c;
+                            const int h0 = (int)((t00 >> s) & 255) * a0[k] + (int)((t01 >> s) & 255) * a1[k];
+                            const int h1 = (int)((t10 >> s) & 255) * a0[k] + (int)((t11 >> s) & 255) * a1[k];
+                            ch[c] = (uint32_t)cv_linear_vpass(b0, b1, h0, h1);
+                        }
+                        if (in[k]) px[i][k] = pack_bgr(ch[0], ch[1], ch[2]);
+                    }
+                }
+            }
+        __syncthreads();                                      // s_list and s_cnt are rewritten by the next round
+    }
+    if (!live) return;
+    uint8_t* out = dst + (((size_t)n * H + Y0) * W + X0) * 3;
+#pragma unroll
+    for (int i = 0; i < kViewRows; ++i)
+        if (Y0 + i < H) fit_store(out + (size_t)i * W * 3, px[i]);
+}
+
+// views_collect_kernel over placements: one workgroup per frame walks the (placement, row) items of ITS placements (t.fr_off: the CSR by
+// frame; t.fr_idx: their positions in the sorted table, in placement-index order), 1024 at a time; the image of an item is its
+// placement's canvas.  The candidate table is [Bf][cap = p.V * rows][16] with p.V = the most placements of any frame.
+__global__ void __launch_bounds__(1024) packed_collect_kernel(ViewMergeParams p, PackDev t) {
+    __shared__ uint32_t wave_cnt[16];
+    __shared__ int truncated;
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q0 = t.fr_off[f], items = (t.fr_off[f + 1] - q0) * p.rows;
+    float* cand = p.cand + (size_t)f * p.V * p.rows * 16;
+    if (tid == 0) truncated = 0;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int j0 = 0; j0 < items; j0 += 1024) {
+        const int j = j0 + tid;
+        bool keep = false;
+        int img = 0, row = 0;
+        float c[4] = {0.f, 0.f, 0.f, 0.f};
+        cf_view r = {0, 0, 2, 2, 0, 0, 1, 1};
+        if (j < items) {
+            const int q = j / p.rows;
+            row = j - q * p.rows;
+            const cf_place& pl = t.places[t.fr_idx[q0 + q]];
+            img = pl.canvas;
+            const int n = p.counts[img];
+            if (row == 0 && n > p.rows) truncated = 1;                    // (every writer stores the same value)
+            if (row < min(n, p.rows)) {
+                r = pl.view;
+                const float4 b4 = *reinterpret_cast<const float4*>(p.dets_net + ((size_t)img * p.rows + row) * 4);
+                c[0] = b4.x; c[1] = b4.y; c[2] = b4.z; c[3] = b4.w;
+                keep = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]);
+                const float xlo = (float)r.dx, xhi = (float)(r.dx + r.dw), ylo = (float)r.dy, yhi = (float)(r.dy + r.dh);
+                const float cx = (c[0] + c[2]) * 0.5f, cy = (c[1] + c[3]) * 0.5f;
+                if (!(cx >= xlo && cx < xhi && cy >= ylo && cy < yhi)) keep = false;
+                if (r.sx0 > 0 && c[0] < xlo + p.edge) keep = false;
+                if (r.sx0 + r.sw < p.w && c[2] > xhi - p.edge) keep = false;
+                if (r.sy0 > 0 && c[1] < ylo + p.edge) keep = false;
+                if (r.sy0 + r.sh < p.h && c[3] > yhi - p.edge) keep = false;
+            }
+        }
+        const unsigned long long bal = __ballot(keep);
+        __syncthreads();                                                  // the counts of the round before have been read
+        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = 0, total = 0;
+        for (int w2 = 0; w2 < 16; ++w2) { if (w2 < wave) off += wave_cnt[w2]; total += wave_cnt[w2]; }
+        if (keep) {
+            const uint32_t pos = base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            const size_t src = (size_t)img * p.rows + row;
+            const double sx = (double)r.sw / (double)r.dw, sy = (double)r.sh / (double)r.dh;
+            const double dx = (double)r.dx, dy = (double)r.dy, ox = (double)r.sx0, oy = (double)r.sy0;
+            float o[16];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = (float)(((double)c[k] - ((k & 1) ? dy : dx)) * ((k & 1) ? sy : sx) + ((k & 1) ? oy : ox));
+            o[4] = p.scores[src * p.score_stride];
+            const float* l = p.lms_net + src * 10;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) o[5 + k] = (float)(((double)l[k] - ((k & 1) ? dy : dx)) * ((k & 1) ? sy : sx) + ((k & 1) ? oy : ox));
+            o[15] = 0.0f;
+            float4* d = reinterpret_cast<float4*>(cand + (size_t)pos * 16);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d[k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+        }
+        base += total;
+    }
+    __syncthreads();
+    if (tid == 0) { p.cand_count[f] = (int)base; p.flags[f] = truncated; }
+}
+
 }  // namespace
 
 int view_layout(const cf_view_opts* o, int h, int w, int H, int W, cf_view* views, int cap, int* n) {
@@ -270,6 +438,135 @@ hipError_t launch_merge_views(hipStream_t s, const ViewMergeParams& p) {
         !p.cand_count || !p.order || !p.mask || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(views_collect_kernel, dim3(p.Bf), dim3(1024), 0, s, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    ThreshParams q{};
+    q.B = p.Bf; q.cap = p.V * p.rows; q.nms_thresh = p.thresh; q.metric = p.metric;
+    q.cand = p.cand; q.cand_count = p.cand_count; q.order = p.order; q.mask = p.mask;
+    q.max_out = p.max_out; q.dets = p.dets; q.lms = p.lms; q.dets_net = p.corners; q.counts = p.out_counts;
+    return launch_nms_stages(s, q);
+}
+
+// The first-fit shelf packer of cf_pack_views (the rule is stated in include/centerface_hip.h and restated in tests/pack_cases.py).
+int pack_views(const cf_view* views, int V, int Bf, int H, int W, int gutter, cf_place* places, int cap, int* n_canvases) {
+    struct Shelf { long long y, height, x_next; };
+    struct Canvas { std::vector<Shelf> shelves; long long y_next; };
+    std::vector<Canvas> cvs;
+    long long k = 0;
+    for (int f = 0; f < Bf; ++f)
+        for (int v = 0; v < V; ++v, ++k) {
+            const long long dw = views[v].dw, dh = views[v].dh;
+            int at = -1;
+            long long x = 0, y = 0;
+            for (size_t c = 0; c < cvs.size() && at < 0; ++c) {
+                Canvas& cv = cvs[c];
+                for (Shelf& s : cv.shelves)
+                    if (dh <= s.height && s.x_next + dw <= W) { x = s.x_next; y = s.y; s.x_next += dw + gutter; at = (int)c; break; }
+                if (at < 0 && cv.y_next + dh <= H) {
+                    x = 0; y = cv.y_next;
+                    cv.shelves.push_back(Shelf{y, dh, dw + gutter});
+                    cv.y_next = y + dh + gutter;
+                    at = (int)c;
+                }
+            }
+            if (at < 0) {
+                cvs.push_back(Canvas{{Shelf{0, dh, dw + gutter}}, dh + gutter});
+                at = (int)cvs.size() - 1;
+            }
+            if (k < cap) {
+                cf_place& p = places[k];
+                p.frame = f; p.canvas = at; p.view = views[v];
+                p.view.dx = (int)x; p.view.dy = (int)y;
+            }
+        }
+    *n_canvases = (int)cvs.size();
+    return CF_OK;
+}
+
+const char* pack_check(std::string& why, int h, int w, const cf_place* places, int P, int N, int Bf, int H, int W) {
+    auto say = [&](const std::string& s) { why = s; return why.c_str(); };
+    char b[400];
+    if (P < 1) return say("P must be at least 1");
+    if (N < 1) return say("N must be at least 1");
+    if (!places) return say("null placement table");
+    for (int k = 0; k < P; ++k) {
+        const cf_place& p = places[k];
+        if (p.frame < 0 || p.frame >= Bf) { snprintf(b, sizeof b, "placement %d names frame %d outside [0, %d)", k, p.frame, Bf); return say(b); }
+        if (p.canvas < 0 || p.canvas >= N) { snprintf(b, sizeof b, "placement %d names canvas %d outside [0, %d)", k, p.canvas, N); return say(b); }
+        std::string text;
+        if (views_table_check(text, h, w, &p.view, 1, H, W)) { snprintf(b, sizeof b, "placement %d: %s", k, text.c_str()); return say(b); }
+    }
+    // overlaps: per canvas a sweep down the contents' top rows
+    std::vector<int> idx((size_t)P);
+    for (int k = 0; k < P; ++k) idx[k] = k;
+    std::sort(idx.begin(), idx.end(), [&](int a, int c) {
+        const cf_place &p = places[a], &q = places[c];
+        return p.canvas != q.canvas ? p.canvas < q.canvas : p.view.dy != q.view.dy ? p.view.dy < q.view.dy : a < c;
+    });
+    for (int i = 0; i < P; ++i) {
+        const cf_place& p = places[idx[i]];
+        for (int j = i + 1; j < P; ++j) {
+            const cf_place& q = places[idx[j]];
+            if (q.canvas != p.canvas || q.view.dy >= p.view.dy + p.view.dh) break;
+            if (q.view.dx < p.view.dx + p.view.dw && p.view.dx < q.view.dx + q.view.dw) {
+                snprintf(b, sizeof b, "the contents of placements %d and %d overlap on canvas %d", std::min(idx[i], idx[j]), std::max(idx[i], idx[j]), p.canvas);
+                return say(b);
+            }
+        }
+    }
+    return nullptr;
+}
+
+PackHost pack_table(const cf_place* places, int P, int N, int Bf, const void* const* planes, int format) {
+    PackHost t{};
+    std::vector<int> idx((size_t)P), pos((size_t)P);
+    for (int k = 0; k < P; ++k) idx[k] = k;
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int c) { return places[a].canvas < places[c].canvas; });
+    t.off_cv = (size_t)P * sizeof(cf_place);
+    t.off_fr = t.off_cv + (size_t)(N + 1) * sizeof(int);
+    t.off_idx = t.off_fr + (size_t)(Bf + 1) * sizeof(int);
+    t.off_planes = (t.off_idx + (size_t)P * sizeof(int) + 7) & ~(size_t)7;
+    t.blob.assign(t.off_planes + (size_t)3 * Bf * sizeof(void*), 0);
+    cf_place* sp = (cf_place*)t.blob.data();
+    int* cv = (int*)(t.blob.data() + t.off_cv);
+    int* fr = (int*)(t.blob.data() + t.off_fr);
+    int* fi = (int*)(t.blob.data() + t.off_idx);
+    const void** pl = (const void**)(t.blob.data() + t.off_planes);
+    for (int k = 0; k < P; ++k) { sp[k] = places[idx[k]]; pos[idx[k]] = k; ++cv[sp[k].canvas + 1]; ++fr[sp[k].frame + 1]; }
+    for (int n = 0; n < N; ++n) cv[n + 1] += cv[n];
+    for (int f = 0; f < Bf; ++f) { t.most = std::max(t.most, fr[f + 1]); fr[f + 1] += fr[f]; }
+    std::vector<int> next(fr, fr + Bf);
+    for (int k = 0; k < P; ++k) fi[next[places[k].frame]++] = pos[k];          // placement-index order inside a frame
+    const bool swap = format == CF_YUV_YV12;                                    // the I420 kernel on swapped planes (as launch_cut_views)
+    for (int f = 0; f < Bf && planes; ++f) {
+        pl[3 * f] = planes[3 * f];
+        pl[3 * f + 1] = planes[3 * f + (swap ? 2 : 1)];
+        pl[3 * f + 2] = planes[3 * f + (swap ? 1 : 2)];
+    }
+    return t;
+}
+
+hipError_t launch_cut_packed(hipStream_t s, int format, const PackDev& t, int N, int pitch0, int pitch1, const uint8_t* fill, uint8_t* dst, int H, int W) {
+    if (format < CF_YUV_NV12 || format > CF_FRAME_BGR || !t.places || !t.cv_off || !t.planes || !fill || !dst || N < 1 || N > 65535 || H < 1 || W < 4 || (W & 3))
+        return hipErrorInvalidValue;
+    const uint32_t fv = (uint32_t)fill[0] | ((uint32_t)fill[1] << 8) | ((uint32_t)fill[2] << 16);
+    const int tiles_x = (W + kPackTileW - 1) / kPackTileW, tiles_y = (H + kPackTileH - 1) / kPackTileH;
+    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N);
+    switch (format) {
+        case CF_YUV_NV12: hipLaunchKernelGGL((cut_packed_kernel<1, false>), grid, dim3(256), 0, s, t, dst, fv, pitch0, pitch1, H, W, tiles_x); break;
+        case CF_YUV_NV21: hipLaunchKernelGGL((cut_packed_kernel<1, true>), grid, dim3(256), 0, s, t, dst, fv, pitch0, pitch1, H, W, tiles_x); break;
+        case CF_YUV_I420: case CF_YUV_YV12: hipLaunchKernelGGL((cut_packed_kernel<2, false>), grid, dim3(256), 0, s, t, dst, fv, pitch0, pitch1, H, W, tiles_x); break;
+        default: hipLaunchKernelGGL((cut_packed_kernel<0, false>), grid, dim3(256), 0, s, t, dst, fv, pitch0, pitch1, H, W, tiles_x); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_packed(hipStream_t s, const ViewMergeParams& p, const PackDev& t) {
+    if (p.Bf < 1 || p.V < 1 || p.rows < 1 || p.max_out < 1 || (long long)p.V * p.rows > INT_MAX / 16 || p.h < 1 || p.w < 1 || p.score_stride < 1 ||
+        (p.metric != CF_MERGE_IOU && p.metric != CF_MERGE_IOS) || !t.places || !t.fr_off || !t.fr_idx || !p.dets_net || !p.scores || !p.lms_net || !p.counts ||
+        !p.cand || !p.cand_count || !p.order || !p.mask || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(packed_collect_kernel, dim3(p.Bf), dim3(1024), 0, s, p, t);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     ThreshParams q{};

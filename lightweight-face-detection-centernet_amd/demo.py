@@ -62,16 +62,20 @@ def _fit_detector(fit, dtype, flip=False):
     return CenterFace(fit, fit, dtype=dtype, flip_test=flip)
 
 
-def _views_detector(frame, scales, tiled, dtype, flip=False, size=640):
+def _views_detector(frame, scales, tiled, dtype, flip=False, size=640, pack=False, gutter=0):
     """The detector, the frame and the ``views=`` options of ``scales=(1.0, 0.5)``: the image (cropped to even sides) goes through an
     N x N context -- N = ``tiled`` when tiles are asked for, else ``size`` -- as several views in one batch: N x N tiles first when
-    ``tiled``, then the aspect-true whole image at each scale (``CenterFace.detect_views``; no accuracy claim is made for it)."""
+    ``tiled``, then the aspect-true whole image at each scale (``CenterFace.detect_views``; no accuracy claim is made for it).  ``pack``:
+    the views share canvases (``ops.pack_views`` with ``gutter`` pixels of fill between them) instead of taking one each."""
     from . import ops
     from .centerface import CenterFace
     frame = np.ascontiguousarray(frame[:frame.shape[0] & ~1, :frame.shape[1] & ~1])
     n = int(tiled) if tiled else int(size)
     views = dict(scales=tuple(float(v) for v in scales), tile=int(tiled) if tiled else None)
-    V = len(ops.view_layout(frame.shape[0], frame.shape[1], n, n, **views))
+    table = ops.view_layout(frame.shape[0], frame.shape[1], n, n, **views)
+    V = ops.pack_views(table, 1, (n, n), int(gutter))[1] if pack else len(table)
+    if pack:
+        views.update(pack=True, gutter=int(gutter))
     return CenterFace(n, n, dtype=dtype, max_batch=V * (2 if flip else 1), flip_test=flip), frame, views
 
 
@@ -90,7 +94,8 @@ def anonymize_file(path, out_path, **options):
     ``rotate=N`` (90, 180, 270): the image is STORED turned and N clockwise degrees make it upright -- the detector sees the upright
     view (``CenterFace.anonymize(rotate=)``), the faces are redacted in the image as stored; not together with ``tiled``.
     ``scales=(1.0, 0.5)``: multi-scale detection (``CenterFace.anonymize(views=)``) -- the whole image at each scale, behind the N x N
-    tiles of ``tiled=N`` if given, as one batch through a 640 x 640 (N x N) context; not together with ``fit`` or ``rotate``."""
+    tiles of ``tiled=N`` if given, as one batch through a 640 x 640 (N x N) context; not together with ``fit`` or ``rotate``.
+    ``pack=True`` (``gutter=N``) beside ``scales``: the views share canvases (``CenterFace.detect_views(pack=True)``)."""
     from PIL import Image
     from .centerface import CenterFace
     frame = imread(path)
@@ -99,11 +104,13 @@ def anonymize_file(path, out_path, **options):
     dtype = options.pop("dtype", "bf16")
     flip = bool(options.pop("flip", False))
     rotate = options["rotate"] = int(options.pop("rotate", 0) or 0)
-    scales = options.pop("scales", None)
+    scales, pack, gutter = options.pop("scales", None), options.pop("pack", False), options.pop("gutter", 0)
+    if pack and not scales:
+        raise ValueError("pack= goes with scales=")
     if scales:
         if fit or rotate:
             raise ValueError("scales= goes with tiled= only, not with fit= or rotate=")
-        detector, frame, options["views"] = _views_detector(frame, scales, tiled, dtype, flip)
+        detector, frame, options["views"] = _views_detector(frame, scales, tiled, dtype, flip, pack=pack, gutter=gutter)
     elif fit:
         detector = _fit_detector(fit, dtype, flip)
         options["fit"], options["tiled"] = True, bool(tiled)
@@ -136,11 +143,13 @@ def annotate_file(path, out_path, **options):
     dtype = options.pop("dtype", "bf16")
     flip = bool(options.pop("flip", False))
     rotate = options["rotate"] = int(options.pop("rotate", 0) or 0)
-    scales = options.pop("scales", None)
+    scales, pack, gutter = options.pop("scales", None), options.pop("pack", False), options.pop("gutter", 0)
+    if pack and not scales:
+        raise ValueError("pack= goes with scales=")
     if scales:
         if fit or rotate:
             raise ValueError("scales= goes with tiled= only, not with fit= or rotate=")
-        detector, frame, options["views"] = _views_detector(frame, scales, tiled, dtype, flip)
+        detector, frame, options["views"] = _views_detector(frame, scales, tiled, dtype, flip, pack=pack, gutter=gutter)
     elif fit:
         detector = _fit_detector(fit, dtype, flip)
         options["fit"], options["tiled"] = True, bool(tiled)
@@ -160,7 +169,7 @@ def annotate_file(path, out_path, **options):
     return results[0]
 
 
-def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False, rotate=0, scales=None):
+def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False, rotate=0, scales=None, pack=False, gutter=0):
     """Read one image file and write the aligned chip of every detected face, cut from the image at its own resolution
     (``CenterFace.detect_aligned_frames``), to ``out_dir``/<image name>_<k>.png.  Returns (detections, the paths written).
     ``tiled=N``: sliced inference with N x N tiles (the image is cropped to even sides).  ``fit=N``, ``flip=True``, ``rotate=N``, ``scales=``: as ``anonymize_file``
@@ -172,7 +181,7 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False
     if scales:
         if fit or rotate:
             raise ValueError("scales= goes with tiled= only, not with fit= or rotate=")
-        detector, frame, views = _views_detector(frame, scales, tiled, dtype, flip)
+        detector, frame, views = _views_detector(frame, scales, tiled, dtype, flip, pack=pack, gutter=gutter)
         tiled = 0
     elif fit:
         detector = _fit_detector(fit, dtype, flip)
@@ -196,7 +205,7 @@ def chips_file(path, out_dir, size=112, tiled=0, dtype="bf16", fit=0, flip=False
 
 
 def main(argv=None):
-    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]] [--scales S,S..] [--flip] [--rotate N]``: print the detections of one image
+    """``python -m centerface_amd.demo IMAGE [--anonymize OUT | --chips DIR | --draw OUT] [--tiled N | --fit [N]] [--scales S,S.. [--pack [--gutter N]]] [--flip] [--rotate N]``: print the detections of one image
     file; with ``--draw`` also write the image with every detection drawn into it (boxes, landmark dots and, unless ``--label none``,
     the score); with
     ``--anonymize`` also write the image with every face pixelated (or blanked: ``--mode solid``; or blurred: ``--blur [R]``, R = the
@@ -210,7 +219,9 @@ def main(argv=None):
     the detections, the redaction and the drawing are in the pixels of the image as stored (not with ``--tiled``; no accuracy claim); with
     ``--scales 1,0.5`` the image goes through a 640 x 640 context (``--tiled N``: N x N, behind N x N tiles) as one batch of views -- the
     whole image, aspect ratio kept, at each scale -- whose detections are merged on the device (multi-scale detection; not with ``--fit``
-    or ``--rotate``; one view per canvas, no packing of levels; no accuracy claim is made)."""
+    or ``--rotate``; one view per canvas; no accuracy claim is made); with ``--pack`` beside ``--scales`` the views are packed into shared
+    canvases, ``--gutter N`` pixels of fill between them (``--scales 1,0.5,0.25`` of a 1080p image: one 640 x 640 canvas instead of three;
+    the decode's NMS is then per canvas; the gutter default 0 is this project's choice, nobody has measured it)."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("image")
@@ -229,6 +240,8 @@ def main(argv=None):
                     help="the image is stored turned: N clockwise degrees (90, 180, 270) make it upright; detect in the upright view")
     ap.add_argument("--scales", default=None, metavar="S,S..", type=lambda t: tuple(float(v) for v in t.split(",")),
                     help="multi-scale detection: the whole image at each of these fractions of its fitted size (e.g. 1,0.5), merged on the device")
+    ap.add_argument("--pack", action="store_true", help="with --scales: pack the views into shared canvases instead of one canvas per view")
+    ap.add_argument("--gutter", type=int, default=0, metavar="N", help="with --pack: N pixels of fill between packed views (default 0)")
     ap.add_argument("--chips", metavar="DIR", help="write the aligned chip of every detected face, cut from the image itself, into DIR")
     ap.add_argument("--size", type=int, default=112, help="with --chips: the chip side (a multiple of 4 in [16, 512])")
     ap.add_argument("--draw", metavar="OUT", help="write the image with every detection drawn into it to OUT")
@@ -238,6 +251,12 @@ def main(argv=None):
         ap.error("--tiled goes with --anonymize, --chips, --draw or --scales")
     if args.scales and (args.fit or args.rotate):
         ap.error("--scales goes with --tiled only, not with --fit or --rotate")
+    if args.pack and not args.scales:
+        ap.error("--pack goes with --scales")
+    if args.gutter and not args.pack:
+        ap.error("--gutter goes with --pack")
+    if args.gutter < 0:
+        ap.error("--gutter must not be negative")
     if args.tiled and args.fit:
         ap.error("--tiled and --fit exclude each other")
     if args.tiled and args.rotate:
@@ -249,18 +268,18 @@ def main(argv=None):
     if args.anonymize and args.chips:
         ap.error("--anonymize and --chips are separate runs")
     if args.draw:
-        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales)
+        dets, _ = annotate_file(args.image, args.draw, label=args.label, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales, pack=args.pack, gutter=args.gutter)
     elif args.chips:
-        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales)
+        (dets, _), _ = chips_file(args.image, args.chips, size=args.size, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales, pack=args.pack, gutter=args.gutter)
     elif args.anonymize and args.blur is not None:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode="blur", shape=args.shape, radius=args.blur, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales, pack=args.pack, gutter=args.gutter)
     elif args.anonymize:
-        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales)
+        dets, _ = anonymize_file(args.image, args.anonymize, mode=args.mode, shape=args.shape, cell=args.cell, scale=args.scale, tiled=args.tiled, fit=args.fit, flip=args.flip, rotate=args.rotate, scales=args.scales, pack=args.pack, gutter=args.gutter)
     else:
         from .centerface import CenterFace
         frame = imread(args.image)
         if args.scales:
-            detector, frame, views = _views_detector(frame, args.scales, args.tiled, "bf16", args.flip)
+            detector, frame, views = _views_detector(frame, args.scales, args.tiled, "bf16", args.flip, pack=args.pack, gutter=args.gutter)
             dets, _ = detector.detect_views(frame[None], **views)[0]
         elif args.fit:
             detector = _fit_detector(args.fit, "bf16", args.flip)

@@ -487,6 +487,64 @@ def merge_views(views, frame_hw, net_hw, dets_net, scores, lms_net, counts, max_
     return od, ol, oc, fl
 
 
+def pack_views(views, Bf, size, gutter=0):
+    """The first-fit shelf packer (``cf_pack_views``; host only): the placements of the ``Bf * V`` (frame, view) pairs, frame-major, in
+    canvases of ``size`` = (H, W) with ``gutter`` pixels of fill between contents.  Each view keeps its source rectangle and its
+    (dw, dh); its dx, dy are replaced.  Returns (places int32 [Bf * V][10] rows (frame, canvas, sx0, sy0, sw, sh, dx, dy, dw, dh), the
+    number of canvases).  A view that fills the canvas gets a canvas of its own.  ``gutter`` = 0 is this project's default; nobody has
+    measured it (no trained weights, no labelled set): contents that share an edge share the threshold decode's NMS."""
+    vt, V = _lib.view_table(views)
+    H, W = int(size[0]), int(size[1])
+    n, nc = C.c_int(0), C.c_int(0)
+    L = _lib.lib()
+    _lib.check(L.cf_pack_views(vt, V, int(Bf), H, W, int(gutter), None, 0, C.byref(n), C.byref(nc)), op=True)
+    tab = (_lib.Place * max(n.value, 1))()
+    _lib.check(L.cf_pack_views(vt, V, int(Bf), H, W, int(gutter), tab, n.value, C.byref(n), C.byref(nc)), op=True)
+    return np.frombuffer(tab, np.int32).reshape(-1, 10)[:n.value].copy(), nc.value
+
+
+def cut_packed(frames, places, n_canvases, size, fmt="bgr", fill=(0, 0, 0), device=0):
+    """The packed cutter (``cf_op_packed``): uint8 [N, H, W, 3] BGR canvases of ``size`` = (H, W), N = ``n_canvases``; canvas n is
+    ``fill`` (B, G, R) and, inside the content rectangle of every row (frame, canvas, sx0, sy0, sw, sh, dx, dy, dw, dh) of ``places``
+    with canvas == n, what ``cut_views`` makes of that view of that frame.  The contents of one canvas must not overlap.  ``frames`` as
+    ``cut_views`` takes them; they are only read."""
+    tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
+    pt, P = _lib.place_table(places)
+    H, W, N = int(size[0]), int(size[1]), int(n_canvases)
+    fb = _lib.fill_bytes(fill)
+    out = np.empty((max(N, 0), H, W, 3), np.uint8)
+    _lib.check(_lib.lib().cf_op_packed(device, _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, pt, P, N, fb, H, W, ptr(out)), op=True)
+    del keep
+    return out
+
+
+def merge_packed(places, n_frames, frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, metric="ios", thresh=0.5, edge=2.0, dets=None,
+                 lms=None, device=0):
+    """The merge of per-canvas detections by placement (``cf_op_merge_packed``): dets_net [N, rows, 4] box corners, scores [N, rows],
+    lms_net [N, rows, 10] in the coordinates of a ``net_hw`` = (H, W) canvas, counts [N].  Frame f's candidates are the rows below
+    min(count, rows) of the canvas of each of its placements (placement order, then row order), filtered against that placement's
+    content by the rules of ``merge_views``, mapped into the ``frame_hw`` = (h, w) frame and de-duplicated per frame by greedy NMS.
+    Returns (dets [Bf, max_out, 5], lms [Bf, max_out, 10], counts [Bf], flags [Bf]) with Bf = ``n_frames``; rows at and past a frame's
+    count keep the bytes of the ``dets`` / ``lms`` arrays passed in (zeros by default)."""
+    pt, P = _lib.place_table(places)
+    d = np.ascontiguousarray(dets_net, dtype=np.float32)
+    if d.ndim != 3 or d.shape[2] != 4:
+        raise ValueError("dets_net must be [N, rows, 4], got %s" % (d.shape,))
+    N, rows, Bf = d.shape[0], d.shape[1], int(n_frames)
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(N, rows)
+    lm = np.ascontiguousarray(lms_net, dtype=np.float32).reshape(N, rows, 10)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(N)
+    max_out = int(max_out)
+    shape = (max(Bf, 0), max(max_out, 0))
+    od = np.zeros(shape + (5,), np.float32) if dets is None else np.ascontiguousarray(dets, dtype=np.float32).reshape(shape + (5,))
+    ol = np.zeros(shape + (10,), np.float32) if lms is None else np.ascontiguousarray(lms, dtype=np.float32).reshape(shape + (10,))
+    oc, fl = np.zeros((shape[0],), np.int32), np.zeros((shape[0],), np.int32)
+    o = _lib.merge_opts(metric, thresh, edge)
+    _lib.check(_lib.lib().cf_op_merge_packed(device, C.byref(o), pt, P, N, Bf, int(frame_hw[0]), int(frame_hw[1]), int(net_hw[0]), int(net_hw[1]),
+                                             ptr(d), ptr(sc), ptr(lm), ptr(cn), rows, max_out, ptr(od), ptr(ol), ptr(oc), ptr(fl)), op=True)
+    return od, ol, oc, fl
+
+
 def rot_geometry(h, w, H, W, rot, fit=None):
     """The placement of the UPRIGHT view of a stored h x w frame in an H x W canvas (``cf_rot_geometry``, host only): (rw, rh, dx, dy).
     ``rot``: the clockwise turn (0, 90, 180, 270) that makes the frame upright; ``fit`` as ``_lib.rot_opts`` takes it (None: stretch)."""

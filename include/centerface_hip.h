@@ -552,7 +552,8 @@ int cf_unfit_rows(cf_ctx* ctx, int max_out, float* dets, float* lms, int32_t* co
  * The score is copied; compaction, counts and flags as behind cf_forward_fit.  With rot == 0 and stretch == 0 the canvases and the rows
  * are those of cf_forward_fit + cf_unfit_rows, bit for bit (the same kernels).
  * Not covered: mirrored orientations (the other four EXIF codes; they need the landmark swap of the flip merge); a rot per frame within
- * one call (one camera, one mount: group the frames per call); a rotated tiled forward; probing the orientation.  The labels
+ * one call (one camera, one mount: group the frames per call); probing the orientation.  This call stays a single-view path: tiles
+ * and levels of a rotated source, a rotated tiled forward among them, live in cf_forward_packed_rot further down.  The labels
  * cf_draw_faces paints are upright in the STORED frame, so a viewer of the upright video sees them turned. */
 typedef struct cf_rot_opts {
     int32_t rot;                 /* 0 | 90 | 180 | 270: the clockwise turn that makes the stored frame upright */
@@ -593,7 +594,8 @@ int cf_forward_rot(cf_ctx* ctx, const cf_rot_opts* opts, int format, const cf_yu
  * byte for byte; a view with the whole frame as source and the rectangle of cf_fit_geometry as content is the canvas of cf_forward_fit,
  * byte for byte; a source of exactly the content's size reproduces the source bytes.
  * Limits, plainly: cf_forward_views puts one view per canvas -- a half-size level costs a whole forward for a quarter of a canvas;
- * the packing of several levels and frames into one canvas is cf_forward_packed below; no rotated views (cf_forward_rot stays a single-view path). */
+ * the packing of several levels and frames into one canvas is cf_forward_packed below; it takes the stored frame for upright: rotated
+ * views live in cf_forward_packed_rot (cf_forward_rot stays a single-view path). */
 typedef struct cf_view {
     int32_t sx0, sy0, sw, sh;    /* frame pixels; all even, sw, sh >= 2, inside the frame */
     int32_t dx, dy, dw, dh;      /* canvas pixels; dw, dh >= 1, inside (H, W); may be odd */
@@ -659,7 +661,8 @@ int cf_merge_views(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* d
  * cf_merge_views bit for bit.
  * Limits, plainly: the threshold decode's own NMS and its max_out are per CANVAS, so they are shared by the frames on that canvas; boxes
  * of two frames whose contents share an edge can suppress each other in that NMS when they overlap -- a gutter keeps them apart;
- * cf_align_faces behind a packed forward works per canvas image; no rotated views; all frames of a call have one size.  The gutter
+ * cf_align_faces behind a packed forward works per canvas image; the stored frame is taken for upright (rotated views live in
+ * cf_forward_packed_rot below); all frames of a call have one size.  The gutter
  * default of the Python layer (0) is this project's choice; nobody has measured it (no trained weights, no labelled set). */
 typedef struct cf_place {
     int32_t frame, canvas;       /* frame in [0, Bf), canvas in [0, N) */
@@ -705,6 +708,55 @@ int cf_forward_packed(cf_ctx* ctx, int format, const cf_yuv_planes* frames, int 
  * cf_merge_packed they return CF_ESTATE.  CF_ESTATE unless the last forward was cf_forward_packed with a threshold decode behind it. */
 int cf_merge_packed(cf_ctx* ctx, const cf_merge_opts* opts, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags,
                     int out_on_device);
+
+/* ---- rotated sources through views and packed canvases: tiles and levels of a turned frame ----
+ * cf_forward_rot puts ONE fitted or stretched whole frame on a canvas; cf_forward_views and cf_forward_packed take the stored frame for
+ * upright.  A corridor-mode camera stores 1920 x 1080 and means 1080 x 1920: fitted upright into 640 x 640 that is a 360 x 640 content,
+ * the faces down the corridor a handful of network pixels wide -- the case tiles and levels exist for.  cf_forward_packed_rot is
+ * cf_forward_packed whose placements cut the UPRIGHT view U of the stored frame F, so a turned source gets tiles, levels and packing in
+ * one batch, and the cf_merge_packed behind it returns the rows in the STORED frame's pixels: tracker, follower, redact, blur, draw,
+ * frame chips, lookback and best shots keep working in place on the decoder's surface, as they do behind cf_forward_rot:
+ *   cf_view_layout(hu, wu) + cf_pack_views (host, unchanged) -> cf_forward_packed_rot -> cf_decode_threshold* -> cf_merge_packed [-> ...]
+ * rot in {0, 90, 180, 270} is the clockwise turn that makes F (h x w) upright, U is (hu, wu) = (h, w) for 0 and 180, (w, h) for 90 and
+ * 270, and the index maps are those stated for cf_forward_rot.  Every placement's source rectangle is in pixels of U; the unpacked
+ * form is the placement list {f, f * V + v, views[v]}.
+ * Canvas: canvas n is `fill` everywhere, except inside each placement's content, where it is
+ *   resize(bgr(U_f)[sy0 : sy0 + sh, sx0 : sx0 + sw], (dh, dw))
+ * with bgr() taken per STORED pixel before the turn (a 4:2:0 pixel's chroma is that of its own 2 x 2 block in F) and the fixed-point
+ * resize of cf_forward_views, taps clamped at the source rectangle.  rot == 0 IS cf_forward_packed: the same launch, the same bytes.
+ * Merge: cf_merge_packed keeps its prototype and recognises a cf_forward_packed_rot behind the decode.  Per placement row it applies the
+ * three drop rules of cf_merge_views in canvas coordinates, unchanged, except that "source side interior to the frame" is tested against
+ * U: sx0 > 0, sx0 + sw < wu, sy0 > 0, sy0 + sh < hu.  A kept point (x, y) goes to the upright view first, in float64, in this order and
+ * without contraction,
+ *   ux(x) = ((double)x - dx) * ((double)sw / dw) + sx0,   uy(y) = ((double)y - dy) * ((double)sh / dh) + sy0,
+ * then to the stored frame by the table of cf_unfit_rows, the difference taken in float64 and rounded to float32 once:
+ *   rot  90: X = uy(y)            Y = (h-1) - ux(x)
+ *   rot 180: X = (w-1) - ux(x)    Y = (h-1) - uy(y)
+ *   rot 270: X = (w-1) - uy(y)    Y = ux(x)
+ * Landmarks are mapped point by point in their order (no left / right swap); the box is the ASSIGNMENT of mapped corners stated for
+ * cf_unfit_rows behind cf_forward_rot, never a min / max; the score is copied.  The greedy NMS of cf_merge_tiles then runs unchanged on
+ * the stored-frame boxes; counts, flags, the truncated-canvas rule, the out_on_device forms and the CF_ENOMEM bound are cf_merge_packed's.
+ * Afterwards the context is in the state behind a merge with Bf frames of (h, w) STORED.  rot 0 gives the bits of cf_merge_packed.
+ * A single whole-frame placement with the rectangle of cf_rot_geometry reproduces the canvas of cf_forward_rot byte for byte; its rows
+ * equal those of cf_unfit_rows behind cf_forward_rot in VALUE, not always in bits: the "+ sx0" adds + 0.0, which turns -0.0 into +0.0,
+ * and this merge runs an NMS that the unfit does not.
+ * Limits, plainly: no mirrored orientations (the other four EXIF codes); one rot per call (one camera, one mount: group the frames per
+ * call); no probing of the orientation; the labels cf_draw_faces paints stay upright in the STORED frame; the threshold decode's NMS and
+ * max_out are per canvas and so shared by the frames on it, as stated for packed views.  No trained weights and no labelled set are on hand: no accuracy
+ * claim is made.
+ *
+ * Bf stored frames of h x w and P placements whose sources lie in the upright view -> N canvases -> forward.  Every check of
+ * cf_forward_packed, with the source rectangles checked against (hu, wu), plus CF_EINVAL, the value named, for a rot outside the four;
+ * h and w must be even for every format (an even rectangle of U is then an even rectangle of F).  Every refusal comes before anything is
+ * enqueued; with ctx == NULL the arguments are still checked and cf_op_last_error names the cause.  rot 180 keeps the packed cutter's
+ * layout with mirrored taps; a quarter turn transposes on the output side (a wave's lanes run along canvas rows, so its taps run along
+ * stored rows and coalesce).  One launch writes all N canvases, one writer per byte; a canvas tile no placement touches is stored as
+ * fill without reading a frame; every tap lies inside its placement's source rectangle mapped into F, pitch padding is never read; the
+ * frames are not modified.  The context remembers rot, the placements and (h, w) until any other forward or upload; cf_merge_views,
+ * cf_merge_tiles and cf_unfit_rows behind it are CF_ESTATE.  Under cf_set_flip_test it mirrors whole canvases, as cf_forward_packed does
+ * (N <= max_batch / 2).  cf_get_resized_input returns the N canvases. */
+int cf_forward_packed_rot(cf_ctx* ctx, int rot, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w,
+                          int pitch0, int pitch1, const cf_place* places, int P, int N, const uint8_t* fill);
 
 /* ---- face tracks across video frames: cover faces through detection dropouts -----------------
  * Every entry point above treats a frame as if it were the only one: the frame in which a face scores just under the threshold goes out
@@ -1537,6 +1589,14 @@ int cf_op_packed(int device, int format, const cf_yuv_planes* host_frames, int B
 int cf_op_merge_packed(int device, const cf_merge_opts* opts, const cf_place* places, int P, int N, int Bf, int h, int w, int H, int W,
                        const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
                        float* dets, float* lms, int32_t* out_counts, int32_t* flags);
+/* The cutter of cf_forward_packed_rot and the merge behind it alone: cf_op_packed and cf_op_merge_packed with the turn `rot` (h x w is
+ * the STORED frame, the sources of the placements lie in its upright view, the rows come back in its pixels), the same shapes, limits
+ * and copies; the checks of cf_forward_packed_rot before any device is touched; nothing is written on refusal.  rot == 0: those two. */
+int cf_op_packed_rot(int device, int rot, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1,
+                     const cf_place* places, int P, int N, const uint8_t* fill, int H, int W, uint8_t* canvases);
+int cf_op_merge_packed_rot(int device, int rot, const cf_merge_opts* opts, const cf_place* places, int P, int N, int Bf, int h, int w,
+                           int H, int W, const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts,
+                           int rows, int max_out, float* dets, float* lms, int32_t* out_counts, int32_t* flags);
 /* The fit kernel of cf_forward_fit alone, on host frames (every plane holds rows x pitch bytes; all of them are copied up, so the
  * padding bytes are on the device beside the pixels): canvas [B][H][W][3] uint8.  W % 4 == 0, B * H * W * 3 < 2^31.  The same
  * validation, before any device is touched; nothing is written on refusal. */

@@ -57,6 +57,7 @@ EXPORTS = (
     "cf_rot_geometry", "cf_forward_rot", "cf_op_rot", "cf_op_unrot",
     "cf_view_layout", "cf_forward_views", "cf_merge_views", "cf_op_views", "cf_op_merge_views",
     "cf_pack_views", "cf_forward_packed", "cf_merge_packed", "cf_op_packed", "cf_op_merge_packed",
+    "cf_forward_packed_rot", "cf_op_packed_rot", "cf_op_merge_packed_rot",
     "cf_set_flip_test", "cf_op_mirror", "cf_op_flip_heads",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_create_weak", "cf_op_track_weak",
@@ -665,6 +666,9 @@ def lib():
         L.cf_merge_packed.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.cf_op_packed.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(Place), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.cf_op_merge_packed.argtypes = [C.c_int, C.POINTER(MergeOpts), C.POINTER(Place)] + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
+        L.cf_forward_packed_rot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(Place), C.c_int, C.c_int, C.c_void_p]
+        L.cf_op_packed_rot.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(Place), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.cf_op_merge_packed_rot.argtypes = [C.c_int, C.c_int, C.POINTER(MergeOpts), C.POINTER(Place)] + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
         L.cf_rot_geometry.argtypes = [C.POINTER(RotOpts)] + [C.c_int] * 4 + [C.POINTER(FitGeom)]
         L.cf_forward_rot.argtypes = [C.c_void_p, C.POINTER(RotOpts), C.c_int, C.c_void_p] + [C.c_int] * 6
         L.cf_op_rot.argtypes = [C.c_int, C.POINTER(RotOpts), C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]

@@ -509,7 +509,8 @@ class Engine(object):
         image f * V + v is ``fill`` (B, G, R) with the source of view v of frame f resized into its content rectangle.  ``frames`` and the
         ``on_device`` form as ``forward_tiles_enqueue`` takes them; they are only read.  A ``decode_threshold`` then gives the per-view
         results and ``merge_views`` the per-frame ones.  One view per canvas: a half-size level costs a whole forward; ``forward_packed_enqueue``
-        packs several levels and frames into one canvas; there are no rotated views.  No accuracy claim is made: the argument is geometric."""
+        packs several levels and frames into one canvas, and its ``rot=`` is where rotated views live.  No accuracy claim is made: the
+        argument is geometric."""
         f = _lib.frame_format(fmt)
         vt, V = _lib.view_table(views)
         fb = _lib.fill_bytes(fill)
@@ -541,15 +542,18 @@ class Engine(object):
 
     # -- packed views: several levels and frames share one canvas -----------------------------------
     def forward_packed_enqueue(self, frames, places, n_canvases, fmt="bgr", *, fill=(0, 0, 0), on_device=False, h=None, w=None, pitch0=None,
-                               pitch1=None):
+                               pitch1=None, rot=0):
         """Run ``n_canvases`` canvases that hold the placements ``places`` ([P][10] rows (frame, canvas, sx0, sy0, sw, sh, dx, dy, dw, dh):
         one view of one frame in one canvas; ``ops.pack_views`` makes them) as one batch (``cf_forward_packed``): canvas n is ``fill``
         (B, G, R) and, inside the content of every placement with canvas == n, what ``forward_views_enqueue`` makes of that view of that
         frame, byte for byte.  The contents of one canvas must not overlap (sharing an edge is allowed).  ``frames`` and the ``on_device``
         form as ``forward_views_enqueue`` takes them; they are only read.  A ``decode_threshold`` then gives the per-CANVAS results --
         its NMS and its max_out are shared by the frames on a canvas, and boxes of two frames whose contents share an edge can suppress
-        each other there; a gutter keeps them apart -- and ``merge_packed`` the per-frame ones.  No rotated views.  No accuracy claim is
-        made: the argument is geometric."""
+        each other there; a gutter keeps them apart -- and ``merge_packed`` the per-frame ones.  ``rot`` 90, 180 or 270
+        (``cf_forward_packed_rot``): rotated views -- the clockwise turn that makes the STORED frames upright; the source rectangles are
+        then in pixels of the upright view (lay them out with ``ops.view_layout(hu, wu, ...)``), and ``merge_packed`` returns the rows
+        in the stored frame's pixels.  One rot per call, no mirrored orientations.  No accuracy claim is made: the argument is
+        geometric."""
         f = _lib.frame_format(fmt)
         pt, P = _lib.place_table(places)
         fb = _lib.fill_bytes(fill)
@@ -557,7 +561,10 @@ class Engine(object):
             tab, B, h, w, pitch0, pitch1 = _lib.device_input_planes("forward_packed_enqueue", frames, f, h, w, pitch0, pitch1)
         else:
             tab, B, h, w, pitch0, pitch1, self._last.keep = _lib.frame_planes(frames, fmt, writable=False)
-        self._chk(self._L.cf_forward_packed(self._h, f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, pt, P, int(n_canvases), fb))
+        if rot:
+            self._chk(self._L.cf_forward_packed_rot(self._h, int(rot), f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, pt, P, int(n_canvases), fb))
+        else:
+            self._chk(self._L.cf_forward_packed(self._h, f, tab, 1 if on_device else 0, B, h, w, pitch0, pitch1, pt, P, int(n_canvases), fb))
         self.last_B = int(n_canvases)
         self._last.tiles = (B, 1)
 
@@ -605,7 +612,8 @@ class Engine(object):
         dict with anchor, upscale and / or fill: it is fitted like ``forward_fit_enqueue``.  ``frames`` and the ``on_device`` form as
         there; they are only read.  A ``decode_threshold`` then gives the rows in canvas coordinates and ``unfit_rows`` those in the
         pixels of the STORED frame, where ``redact_faces``, ``draw_faces``, ``align_faces_frame`` and the tracker take them.  One ``rot``
-        per call; mirrored orientations and a rotated tiled forward are not covered.  No accuracy claim is made: the argument is geometric."""
+        per call; mirrored orientations are not covered; a single-view path: tiles and levels of a rotated source, a rotated tiled forward
+        among them, live in ``forward_packed_enqueue(rot=)``.  No accuracy claim is made: the argument is geometric."""
         f = _lib.frame_format(fmt)
         o = _lib.rot_opts(rot, fit)
         if on_device:
@@ -1524,7 +1532,8 @@ class CenterFace(object):
         else:
             array = frames
         if views is not None:
-            (forward, per), src, rows = self._views_form(array, fmt_, views, cover is not None or draw is not None), array, _PACKED if views.get("pack") else _VIEWS
+            (forward, per), src = self._views_form(array, fmt_, views, cover is not None or draw is not None), array
+            rows = _PACKED if views.get("pack") or views.get("rotate") else _VIEWS      # (rotated views always go through the packed forward)
             merge = (views["metric"], views["thresh"], views["edge"])
         elif rotate:                                                              # (fit None: the upright view is stretched)
             src, forward, rows = array, lambda chunk: eng.forward_rot_enqueue(chunk, fmt_, rotate, fit=fit), _UNFIT
@@ -1709,15 +1718,25 @@ class CenterFace(object):
 
     def _views_form(self, frames, fmt, views, writable):
         """(forward, frames per chunk) of the views paths: the enqueue that makes the views of any slice of ``frames`` (their size's
-        layout, ``ops.view_layout``)."""
+        layout, ``ops.view_layout``).  With a turn (``views['rotate']``) the layout is that of the UPRIGHT view (hu, wu) and the forward
+        always the packed one: unpacked, the placement list {f, f * V + v, views[v]}."""
         h, w = _lib.frame_planes(frames, fmt, writable=writable)[2:4]
         from . import ops
-        table = ops.view_layout(h, w, self.img_h_new, self.img_w_new, views["tile"], views["overlap"], views["scales"], views["anchor"])
+        rot = views.get("rotate", 0)
+        hu, wu = (w, h) if rot in (90, 270) else (h, w)
+        table = ops.view_layout(hu, wu, self.img_h_new, self.img_w_new, views["tile"], views["overlap"], views["scales"], views["anchor"])
         if views.get("pack"):
             return self._packed_form(table, len(frames), fmt, views)
-        per = self.engine.max_batch // len(table)
+        V = len(table)
+        per = self.engine.max_batch // V
         if per < 1:
-            raise ValueError("%d views per frame need max_batch >= %d (this instance has %d)" % (len(table), len(table), self.engine.max_batch))
+            raise ValueError("%d views per frame need max_batch >= %d (this instance has %d)" % (V, V, self.engine.max_batch))
+        if rot:
+            def places(Bf):
+                t = np.empty((Bf, V, 10), np.int32)
+                t[:, :, 0], t[:, :, 1], t[:, :, 2:] = np.arange(Bf)[:, None], np.arange(Bf * V).reshape(Bf, V), table
+                return t.reshape(-1, 10)
+            return lambda chunk: self.engine.forward_packed_enqueue(chunk, places(len(chunk)), len(chunk) * V, fmt, fill=views["fill"], rot=rot), per
         return lambda chunk: self.engine.forward_views_enqueue(chunk, table, fmt, fill=views["fill"]), per
 
     def _packed_form(self, table, n_frames, fmt, views):
@@ -1737,24 +1756,32 @@ class CenterFace(object):
         per = 1
         while per < n_frames and layout(per + 1)[1] <= cap:
             per += 1
-        return lambda chunk: self.engine.forward_packed_enqueue(chunk, *layout(len(chunk)), fmt, fill=views["fill"]), per
+        return lambda chunk: self.engine.forward_packed_enqueue(chunk, *layout(len(chunk)), fmt, fill=views["fill"], rot=views.get("rotate", 0)), per
 
     @staticmethod
     def _views_options(views, tiled=False, fit=None, rotate=0):
         """The ``views`` argument of the product paths -> None, or the options of ``detect_views``' path with every default filled in:
-        ``views`` None / False, True (the defaults) or a dict with scales, tile, overlap, anchor, fill, metric, thresh, edge, pack and / or
-        gutter (``pack``: several views and frames share a canvas, ``ops.pack_views`` with ``gutter`` pixels of fill between them).
-        ``views`` excludes ``tiled=True``, ``fit`` and ``rotate``: the layout has its own tiles and its own fit, and no rotated views."""
+        ``views`` None / False, True (the defaults) or a dict with scales, tile, overlap, anchor, fill, metric, thresh, edge, pack, gutter
+        and / or rotate (``pack``: several views and frames share a canvas, ``ops.pack_views`` with ``gutter`` pixels of fill between
+        them; ``rotate``: 0, 90, 180 or 270, the clockwise turn that makes the STORED frames upright -- rotated views: the layout is that
+        of the upright view, ``Engine.forward_packed_enqueue(rot=)`` cuts it and the rows come back in the stored frame's pixels).
+        ``views`` excludes ``tiled=True``, ``fit`` and the top-level ``rotate``: the layout has its own tiles, its own fit and its own
+        ``rotate`` key."""
         if views is None or views is False:
             return None
         for name, on in (("tiled=True", tiled), ("fit=", fit is not None and fit is not False), ("rotate=", bool(rotate))):
             if on:
-                raise ValueError("views= and %s exclude each other: the views have their own tiles and their own fit, and rotated views are not covered" % name)
+                raise ValueError("views= and %s exclude each other: the views have their own tiles, their own fit and their own turn (rotated views: "
+                                 "the rotate key of the views dict)" % name)
         o = dict(scales=(1.0, 0.5), tile=None, overlap=None, anchor="center", fill=(0, 0, 0), metric="ios", thresh=0.5, edge=2.0)
-        given = dict(views) if isinstance(views, dict) else {}
-        if set(given) - set(o) - {"pack", "gutter"}:                              # (pack and gutter: in the result only when given)
-            raise ValueError("views takes %s, got %s" % (", ".join(sorted(set(o) | {"pack", "gutter"})), sorted(given)))
+        given, late = dict(views) if isinstance(views, dict) else {}, {"pack", "gutter", "rotate"}      # (late: in the result only when given)
+        if set(given) - set(o) - late:
+            raise ValueError("views takes %s, got %s" % (", ".join(sorted(set(o) | late)), sorted(given)))
         o.update(given)
+        if "rotate" in o:
+            if o["rotate"] not in (0, 90, 180, 270):
+                raise ValueError("the rotate key of views must be 0, 90, 180 or 270 (clockwise degrees), got %r" % (o["rotate"],))
+            o["rotate"] = int(o["rotate"])
         _lib.view_opts(o["tile"], o["overlap"], o["scales"], o["anchor"])       # refuse bad names and numbers before any work
         _lib.fill_bytes(o["fill"])
         _lib.merge_opts(o["metric"], o["thresh"], o["edge"])
@@ -1768,7 +1795,7 @@ class CenterFace(object):
 
     def detect_views(self, frames, fmt="bgr", *, scales=(1.0, 0.5), tile=None, overlap=None, anchor="center", fill=(0, 0, 0), metric="ios",
                      thresh=0.5, edge=2.0, redact=None, tracker=None, follow=None, detect=True, scenes=None, lookback=None, flush=False,
-                     pack=False, gutter=0):
+                     pack=False, gutter=0, rotate=0):
         """Multi-scale detection: every frame reaches the network as several VIEWS in one batch -- the aspect-true whole frame at each of
         ``scales`` (fractions of the fitted size; 0.5 shows a face that fills the frame at half the size, where a stride-4 centre
         detector holds together), placed by ``anchor`` on a canvas of ``fill``, and, with ``tile`` (``overlap``: default a fifth of the
@@ -1781,11 +1808,15 @@ class CenterFace(object):
         ``merge_packed``): levels 1.0, 0.5 and 0.25 of a 1080p frame then cost one 640 x 640 canvas per frame instead of three, and
         ``max_batch`` must hold the canvases of one frame.  Packed, the threshold decode's NMS and ``max_dets`` are per canvas and so
         shared by the frames on it, and boxes of two frames whose contents share an edge can suppress each other there: a gutter
-        keeps them apart.  There are no rotated views.  The layout defaults, ``gutter`` = 0 and the
+        keeps them apart.  ``rotate``: 90, 180 or 270 -- rotated views: the clockwise turn that makes the STORED frames upright; the
+        views are laid out in the upright view and cut from the stored frames in place (``Engine.forward_packed_enqueue(rot=)``, packed
+        or, without ``pack``, one view per canvas), and the rows come back in the STORED frame's pixels, as behind ``detect_rotated``.
+        One turn per call, no mirrored orientations, no probing.  The layout defaults, ``gutter`` = 0 and the
         IoS 0.5 / edge 2 merge are this project's choices and nobody has measured them; no accuracy claim is made.  ``redact``,
         ``tracker``, ``follow``, ``detect``, ``scenes``, ``lookback`` and ``flush``: as ``detect_tiled``."""
         views = self._views_options(dict(scales=scales, tile=tile, overlap=overlap, anchor=anchor, fill=fill, metric=metric, thresh=thresh, edge=edge,
-                                         **(dict(pack=True, gutter=gutter) if pack else dict(gutter=gutter) if gutter else {})))
+                                         **(dict(pack=True, gutter=gutter) if pack else dict(gutter=gutter) if gutter else {}),
+                                         **(dict(rotate=rotate) if rotate else {})))
         if redact is not None:
             _lib.split_redact_options(redact)                                   # refuse what blur does not take before any work
         if lookback is not None and redact is None:
@@ -1897,9 +1928,10 @@ class CenterFace(object):
         corridor-mode camera, phone video): the network sees the upright view (``Engine.forward_rot_enqueue``; stretched to the network
         input, or fitted with ``fit``), frames of any size; detections and redaction are in the pixels of the stored frame, not
         floor-divided; not together with ``tiled``; one turn per call; no accuracy claim is made.  ``views``: True, or a dict with scales,
-        tile, overlap, anchor, fill, metric, thresh, edge, pack and / or gutter: detection by ``detect_views`` -- several views of every frame in one
-        batch, merged on the device -- on frames of any even size, the rows in frame pixels; not together with ``tiled``, ``fit`` or
-        ``rotate``; no accuracy claim is made for it either."""
+        tile, overlap, anchor, fill, metric, thresh, edge, pack, gutter and / or rotate: detection by ``detect_views`` -- several views of every
+        frame in one batch, merged on the device -- on frames of any even size, the rows in frame pixels; not together with ``tiled``,
+        ``fit`` or the top-level ``rotate`` (rotated views: the ``rotate`` key of the dict, as ``detect_views(rotate=)``; the rows and the
+        redaction are then in the pixels of the STORED frame); no accuracy claim is made for it either."""
         return self._anonymize(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
                                scenes=scenes, lookback=lookback, flush=flush, rotate=rotate, views=views)
 

@@ -559,6 +559,16 @@ hipError_t launch_cut_packed(hipStream_t s, int format, const PackDev& t, int N,
 // views (p.views unused, p.V = PackHost::most: cap = most * rows, workspace sizes as merge_mask_bytes(Bf, most, rows)).
 hipError_t launch_merge_packed(hipStream_t s, const ViewMergeParams& p, const PackDev& t);
 
+// Rotated sources through packed views (cf_views_rot.hip; the statement is in include/centerface_hip.h).  rot: the clockwise turn (0, 90,
+// 180, 270) that makes the stored h x w frames upright; the placements' sources are rectangles of the upright view.  pack_rot_check:
+// nullptr, or what is wrong with the turn or with the placements (pack_check against the upright view's size; host only).
+// launch_cut_packed_rot / launch_merge_packed_rot: launch_cut_packed / launch_merge_packed through the turn, p.h x p.w the STORED frame,
+// the rows in its pixels; rot == 0 IS those two.
+const char* pack_rot_check(std::string& why, int rot, int h, int w, const cf_place* places, int P, int N, int Bf, int H, int W);
+hipError_t launch_cut_packed_rot(hipStream_t s, int rot, int format, const PackDev& t, int N, int h, int w, int pitch0, int pitch1, const uint8_t* fill,
+                                 uint8_t* dst, int H, int W);
+hipError_t launch_merge_packed_rot(hipStream_t s, int rot, const ViewMergeParams& p, const PackDev& t);
+
 // Flip test (cf_flip.hip; the statement is in include/centerface_hip.h).  mirror_check: nullptr, or what is wrong with the format and sizes
 // of a batch to mirror (the text lives in `why`; host only).  launch_mirror_batch: dst holds 2B network inputs of in_format (uint8
 // [.][H][W][3] or float32 [.][3][H][W]; 16-byte aligned); images B .. 2B-1 become images 0 .. B-1 of src with their columns reversed and,

@@ -1075,35 +1075,46 @@ int cf_pack_views(const cf_view* views, int V, int Bf, int H, int W, int gutter,
 }
 
 // nullptr, or what is wrong with the frames and placements of a packed batch on host frames (the text lives in `why`)
-static const char* packed_check(std::string& why, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_place* places, int P, int N, int H, int W) {
+// (rot: the turn of the _rot forms, 0 otherwise: pack_check)
+static const char* packed_check(std::string& why, int rot, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_place* places, int P, int N, int H,
+                                int W) {
     if (Bf < 1) return "Bf must be at least 1";
     if (H < 1 || W < 4 || (W & 3)) return "W must be a multiple of 4 and H at least 1";
     if (const char* geo = frame_geometry_check(FrameGeo{format, Bf, h, w, pitch0, pitch1}, 2, true)) return geo;
-    return pack_check(why, h, w, places, P, N, Bf, H, W);
+    return pack_rot_check(why, rot, h, w, places, P, N, Bf, H, W);
 }
 
 // The cutter of cf_forward_packed on host frames.
-int cf_op_packed(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1, const cf_place* places,
-                 int P, int N, const uint8_t* fill, int H, int W, uint8_t* canvases) {
+static int op_packed(const char* who, int device, int rot, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1,
+                     const cf_place* places, int P, int N, const uint8_t* fill, int H, int W, uint8_t* canvases) {
     std::string why;
-    const char* bad = packed_check(why, format, Bf, h, w, pitch0, pitch1, places, P, N, H, W);
+    const char* bad = packed_check(why, rot, format, Bf, h, w, pitch0, pitch1, places, P, N, H, W);
     if (!bad) bad = redact_check_planes(format, reinterpret_cast<const void* const*>(host_frames), Bf, 0, pitch0, pitch1);
     if (!bad && (!fill || !canvases)) bad = "null fill or output";
     if (!bad && N > 65535) bad = "more than 65535 canvases";
     if (!bad && (long long)N * H * W * 3 > INT_MAX) bad = "more than 2^31 output bytes";
-    if (bad) return fail("cf_op_packed", bad);
+    if (bad) return fail(who, bad);
     Scope sc(device);
     const std::vector<const void*> dev = up_planes(sc, format, reinterpret_cast<const void* const*>(host_frames), Bf, h, pitch0, pitch1);
     const PackHost t = pack_table(places, P, N, Bf, dev.data(), format);
     const unsigned char* blob = sc.in(t.blob.data(), t.blob.size());
     uint8_t* out = sc.out(canvases, (size_t)N * H * W * 3);
-    sc.run([&] { return launch_cut_packed(sc.s, format, pack_dev(t, blob), N, pitch0, pitch1, fill, out, H, W); });
-    return sc.result("cf_op_packed");
+    sc.run([&] { return launch_cut_packed_rot(sc.s, rot, format, pack_dev(t, blob), N, h, w, pitch0, pitch1, fill, out, H, W); });      // (rot 0: launch_cut_packed)
+    return sc.result(who);
+}
+int cf_op_packed(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1, const cf_place* places,
+                 int P, int N, const uint8_t* fill, int H, int W, uint8_t* canvases) {
+    return op_packed("cf_op_packed", device, 0, format, host_frames, Bf, h, w, pitch0, pitch1, places, P, N, fill, H, W, canvases);
+}
+// The cutter of cf_forward_packed_rot on host frames.
+int cf_op_packed_rot(int device, int rot, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1,
+                     const cf_place* places, int P, int N, const uint8_t* fill, int H, int W, uint8_t* canvases) {
+    return op_packed("cf_op_packed_rot", device, rot, format, host_frames, Bf, h, w, pitch0, pitch1, places, P, N, fill, H, W, canvases);
 }
 
-int cf_op_merge_packed(int device, const cf_merge_opts* o, const cf_place* places, int P, int N, int Bf, int h, int w, int H, int W,
-                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
-                       float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+static int op_merge_packed(const char* who, int device, int rot, const cf_merge_opts* o, const cf_place* places, int P, int N, int Bf, int h, int w, int H,
+                           int W, const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                           float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
     std::string why;
     const char* bad = nullptr;
     if (!o || !dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags) bad = "null argument";
@@ -1111,12 +1122,12 @@ int cf_op_merge_packed(int device, const cf_merge_opts* o, const cf_place* place
     else if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) bad = "thresh and edge must be finite and not negative";
     else if (rows < 1 || max_out < 1 || H < 1 || W < 1) bad = "rows, max_out, H and W must be at least 1";
     else if (const char* geo = frame_geometry_check(FrameGeo{CF_FRAME_BGR, Bf, h, w, 3 * w, 0}, 2, true)) bad = geo;
-    else bad = pack_check(why, h, w, places, P, N, Bf, H, W);
-    if (bad) return fail("cf_op_merge_packed", bad);
+    else bad = pack_rot_check(why, rot, h, w, places, P, N, Bf, H, W);      // (rot 0: pack_check)
+    if (bad) return fail(who, bad);
     const PackHost t = pack_table(places, P, N, Bf, nullptr, CF_FRAME_BGR);
     const int V = t.most;
     if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit) {
-        g_op_error = "cf_op_merge_packed: the suppression bits of Bf x (most placements of a frame * rows) candidates exceed 256 MiB";
+        g_op_error = std::string(who) + ": the suppression bits of Bf x (most placements of a frame * rows) candidates exceed 256 MiB";
         return CF_ENOMEM;
     }
     Scope sc(device);
@@ -1136,8 +1147,21 @@ int cf_op_merge_packed(int device, const cf_merge_opts* o, const cf_place* place
     p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
     p.corners = sc.make<float>(mo * 4);
     p.out_counts = sc.out(out_counts, Bf); p.flags = sc.out(flags, Bf);
-    sc.run([&] { return launch_merge_packed(sc.s, p, pack_dev(t, blob)); });
-    return sc.result("cf_op_merge_packed");
+    sc.run([&] { return launch_merge_packed_rot(sc.s, rot, p, pack_dev(t, blob)); });      // (rot 0: launch_merge_packed)
+    return sc.result(who);
+}
+int cf_op_merge_packed(int device, const cf_merge_opts* o, const cf_place* places, int P, int N, int Bf, int h, int w, int H, int W,
+                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                       float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+    return op_merge_packed("cf_op_merge_packed", device, 0, o, places, P, N, Bf, h, w, H, W, dets_net, scores, lms_net, counts, rows, max_out, dets, lms,
+                           out_counts, flags);
+}
+// The merge behind cf_forward_packed_rot on host tables: h x w is the STORED frame, the rows come back in its pixels.
+int cf_op_merge_packed_rot(int device, int rot, const cf_merge_opts* o, const cf_place* places, int P, int N, int Bf, int h, int w, int H, int W,
+                           const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                           float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+    return op_merge_packed("cf_op_merge_packed_rot", device, rot, o, places, P, N, Bf, h, w, H, W, dets_net, scores, lms_net, counts, rows, max_out, dets,
+                           lms, out_counts, flags);
 }
 
 // nullptr, or what is wrong with the options and sizes of a fit geometry (the text lives in `why`)

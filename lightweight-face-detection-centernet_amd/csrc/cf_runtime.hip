@@ -175,6 +175,7 @@ struct cf_ctx {
     // copy of the device blob pk_dev -- sorted placements, the two CSRs, the plane addresses -- uploaded when it changes); cf_merge_packed
     // leaves its rows where the tile merge leaves its own
     PackHost pk_tab; DevBuf pk_dev; int pk_up = 0, pk_P = 0, pk_N = 0;
+    int pk_rot = 0;                     // cf_forward_packed_rot: the turn beside the placements (their sources then lie in the upright view of the tl_h x tl_w frames)
     int ft_rot = 0;                     // cf_forward_rot: the turn beside ft_g (ft_g then places the upright view of the tl_h x tl_w frames)
     struct { DevBuf cand, cand_count, order, mask, dets, lms, corners, counts, flags; } tl;
     struct { DevBuf dets, lms, info, corners, counts, flags; } tk; int tk_M = 0;      // cf_track_update: the tracked rows, tk_M per image
@@ -1189,7 +1190,7 @@ int forward_run(cf_ctx* c, const void* caller_in, int in_format, int Bcaller) {
     c->thr_pending = false;                               // an enqueued threshold decode belongs to the forward before this one
     c->up.pending = false;                                // ... and so does an upload nobody asked to run
     c->al_in = net_in; c->al_fmt = in_format; c->al_slot = c->in.used;      // what cf_align_faces samples
-    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->ft_rot = 0; c->vw_V = 0; c->pk_P = 0; c->fo.B = 0; c->lb.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
+    c->stage = ROWS_NONE; c->tl_T = 0; c->ft_on = false; c->ft_rot = 0; c->vw_V = 0; c->pk_P = 0; c->pk_rot = 0; c->fo.B = 0; c->lb.B = 0;       // (cf_forward_tiles and cf_forward_fit set their state again behind this call)
     hipGraphExec_t exec = (c->flags & CF_FLAG_NO_GRAPH) ? nullptr : forward_graph(c, net_in, in_format, B);
     if (exec) HIPCHK(c, hipGraphLaunch(exec, c->stream));
     for (size_t i = 0; i < c->ops.size();) {
@@ -2185,8 +2186,9 @@ int cf_merge_views(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, 
 // Packed forward: the packed cutter of cf_views.hip writes the N canvases to input_resized in one launch.  The device blob (sorted
 // placements, CSRs, plane addresses) is built per call -- the plane addresses are only known behind the staging -- and uploaded when it
 // differs from the one the device holds.
-int cf_forward_packed(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0, int pitch1,
-                      const cf_place* places, int P, int N, const uint8_t* fill) {
+// (who: the entry point's name for the messages; rot: 0 from cf_forward_packed, whose checks, launch and bytes this then is)
+static int forward_packed(cf_ctx* c, const char* who, int rot, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0,
+                          int pitch1, const cf_place* places, int P, int N, const uint8_t* fill) {
     const void* const* planes = reinterpret_cast<const void* const*>(frames);
     std::string text;
     const int H = c ? c->H : 1 << 30, W = c ? c->W : 1 << 30;               // (no context, no canvas: as cf_forward_views)
@@ -2194,17 +2196,17 @@ int cf_forward_packed(cf_ctx* c, int format, const cf_yuv_planes* frames, int in
     if (Bf < 1) why = "Bf must be at least 1";
     else if (c && (W < 4 || (W & 3))) why = "W must be a multiple of 4";
     else if (const char* geo = frame_geometry_check(FrameGeo{format, Bf, h, w, pitch0, pitch1}, 2, true)) why = geo;
-    else why = pack_check(text, h, w, places, P, N, Bf, H, W);
+    else why = pack_rot_check(text, rot, h, w, places, P, N, Bf, H, W);     // (rot 0: pack_check)
     if (!why) why = redact_check_planes(format, planes, Bf, in_on_device, pitch0, pitch1);
     if (!why && !fill) why = "null fill";
     if (!c) {                                                                // the arguments are checked all the same (cf_op_last_error tells)
-        op_error_set((std::string("cf_forward_packed: ") + (why ? why : "null context")).c_str());
+        op_error_set((std::string(who) + ": " + (why ? why : "null context")).c_str());
         return CF_EINVAL;
     }
-    if (why) return c->fail(CF_EINVAL, "cf_forward_packed: %s", why);
+    if (why) return c->fail(CF_EINVAL, "%s: %s", who, why);
     if (N > batch_cap(c))
-        return c->fail(CF_EINVAL, "cf_forward_packed: N = %d canvases exceed max_batch %d%s", N, batch_cap(c), c->flip ? " (flip test is on: half of max_batch)" : "");
-    if (int r = forward_begin(c, "cf_forward_packed", N)) return r;
+        return c->fail(CF_EINVAL, "%s: N = %d canvases exceed max_batch %d%s", who, N, batch_cap(c), c->flip ? " (flip test is on: half of max_batch)" : "");
+    if (int r = forward_begin(c, who, N)) return r;
     uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
     const uint8_t fv[3] = {fill[0], fill[1], fill[2]};
     auto cut = [&](const void* const* pl, int p0, int p1) -> hipError_t {
@@ -2225,13 +2227,23 @@ int cf_forward_packed(cf_ctx* c, int format, const cf_yuv_planes* frames, int in
             if (e != hipSuccess) return e;
             c->pk_up = 1;
         }
-        return launch_cut_packed(c->stream, format, pack_dev(c->pk_tab, c->pk_dev.p), N, p0, p1, fv, dst, c->H, c->W);
+        return launch_cut_packed_rot(c->stream, rot, format, pack_dev(c->pk_tab, c->pk_dev.p), N, h, w, p0, p1, fv, dst, c->H, c->W);      // (rot 0: launch_cut_packed)
     };
     if (in_on_device) HIPCHK(c, cut(planes, pitch0, pitch1));
-    else if (int r = src_stage_frames(c, "cf_forward_packed", FrameGeo{format, Bf, h, w, pitch0, pitch1}, planes, cut)) return r;
+    else if (int r = src_stage_frames(c, who, FrameGeo{format, Bf, h, w, pitch0, pitch1}, planes, cut)) return r;
     if (int r = forward_run(c, dst, CF_IN_U8_HWC_BGR, N)) return r;
-    c->pk_P = P; c->pk_N = N; c->tl_Bf = Bf; c->tl_h = h; c->tl_w = w;
+    c->pk_P = P; c->pk_N = N; c->pk_rot = rot; c->tl_Bf = Bf; c->tl_h = h; c->tl_w = w;
     return CF_OK;
+}
+int cf_forward_packed(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0, int pitch1,
+                      const cf_place* places, int P, int N, const uint8_t* fill) {
+    return forward_packed(c, "cf_forward_packed", 0, format, frames, in_on_device, Bf, h, w, pitch0, pitch1, places, P, N, fill);
+}
+// Rotated packed forward: the placements' sources are rectangles of the UPRIGHT view of the stored frames (cf_views_rot.hip).  The
+// context remembers the turn beside the placements: cf_merge_packed maps through both, into the stored frame's pixels.
+int cf_forward_packed_rot(cf_ctx* c, int rot, int format, const cf_yuv_planes* frames, int in_on_device, int Bf, int h, int w, int pitch0, int pitch1,
+                          const cf_place* places, int P, int N, const uint8_t* fill) {
+    return forward_packed(c, "cf_forward_packed_rot", rot, format, frames, in_on_device, Bf, h, w, pitch0, pitch1, places, P, N, fill);
 }
 
 // The merge of the last threshold decode's per-canvas rows by placement (cf_views.hip) on the stream that carried the decode; inputs,
@@ -2266,7 +2278,7 @@ int cf_merge_packed(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets,
     p.cand = (float*)ws.cand.p; p.cand_count = (int*)ws.cand_count.p; p.order = (int*)ws.order.p; p.mask = (unsigned long long*)ws.mask.p;
     p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
     p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
-    HIPCHK(c, launch_merge_packed(c->stream, p, pack_dev(c->pk_tab, c->pk_dev.p)));
+    HIPCHK(c, launch_merge_packed_rot(c->stream, c->pk_rot, p, pack_dev(c->pk_tab, c->pk_dev.p)));      // (pk_rot == 0: launch_merge_packed)
     c->stage = ROWS_MERGED; c->tl_maxout = max_out;
     return write_out(c, out_on_device, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }

@@ -503,29 +503,35 @@ def pack_views(views, Bf, size, gutter=0):
     return np.frombuffer(tab, np.int32).reshape(-1, 10)[:n.value].copy(), nc.value
 
 
-def cut_packed(frames, places, n_canvases, size, fmt="bgr", fill=(0, 0, 0), device=0):
+def cut_packed(frames, places, n_canvases, size, fmt="bgr", fill=(0, 0, 0), device=0, rot=0):
     """The packed cutter (``cf_op_packed``): uint8 [N, H, W, 3] BGR canvases of ``size`` = (H, W), N = ``n_canvases``; canvas n is
     ``fill`` (B, G, R) and, inside the content rectangle of every row (frame, canvas, sx0, sy0, sw, sh, dx, dy, dw, dh) of ``places``
     with canvas == n, what ``cut_views`` makes of that view of that frame.  The contents of one canvas must not overlap.  ``frames`` as
-    ``cut_views`` takes them; they are only read."""
+    ``cut_views`` takes them; they are only read.  ``rot`` 90, 180 or 270 (``cf_op_packed_rot``): the clockwise turn that makes the
+    STORED frames upright; the source rectangles are then in pixels of the upright view (``np.rot90`` of the frame's BGR)."""
     tab, B, h, w, pitch0, pitch1, keep = _lib.frame_planes(frames, fmt, writable=False)
     pt, P = _lib.place_table(places)
     H, W, N = int(size[0]), int(size[1]), int(n_canvases)
     fb = _lib.fill_bytes(fill)
     out = np.empty((max(N, 0), H, W, 3), np.uint8)
-    _lib.check(_lib.lib().cf_op_packed(device, _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, pt, P, N, fb, H, W, ptr(out)), op=True)
+    if rot:
+        _lib.check(_lib.lib().cf_op_packed_rot(device, int(rot), _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, pt, P, N, fb, H, W, ptr(out)), op=True)
+    else:
+        _lib.check(_lib.lib().cf_op_packed(device, _lib.frame_format(fmt), tab, B, h, w, pitch0, pitch1, pt, P, N, fb, H, W, ptr(out)), op=True)
     del keep
     return out
 
 
 def merge_packed(places, n_frames, frame_hw, net_hw, dets_net, scores, lms_net, counts, max_out, metric="ios", thresh=0.5, edge=2.0, dets=None,
-                 lms=None, device=0):
+                 lms=None, device=0, rot=0):
     """The merge of per-canvas detections by placement (``cf_op_merge_packed``): dets_net [N, rows, 4] box corners, scores [N, rows],
     lms_net [N, rows, 10] in the coordinates of a ``net_hw`` = (H, W) canvas, counts [N].  Frame f's candidates are the rows below
     min(count, rows) of the canvas of each of its placements (placement order, then row order), filtered against that placement's
     content by the rules of ``merge_views``, mapped into the ``frame_hw`` = (h, w) frame and de-duplicated per frame by greedy NMS.
     Returns (dets [Bf, max_out, 5], lms [Bf, max_out, 10], counts [Bf], flags [Bf]) with Bf = ``n_frames``; rows at and past a frame's
-    count keep the bytes of the ``dets`` / ``lms`` arrays passed in (zeros by default)."""
+    count keep the bytes of the ``dets`` / ``lms`` arrays passed in (zeros by default).  ``rot`` 90, 180 or 270
+    (``cf_op_merge_packed_rot``): the placements' sources lie in the upright view of the STORED ``frame_hw`` frame, the edge rule tests
+    against that view, and the rows come back in the stored frame's pixels (boxes assigned from mapped corners, landmarks in order)."""
     pt, P = _lib.place_table(places)
     d = np.ascontiguousarray(dets_net, dtype=np.float32)
     if d.ndim != 3 or d.shape[2] != 4:
@@ -540,8 +546,12 @@ def merge_packed(places, n_frames, frame_hw, net_hw, dets_net, scores, lms_net, 
     ol = np.zeros(shape + (10,), np.float32) if lms is None else np.ascontiguousarray(lms, dtype=np.float32).reshape(shape + (10,))
     oc, fl = np.zeros((shape[0],), np.int32), np.zeros((shape[0],), np.int32)
     o = _lib.merge_opts(metric, thresh, edge)
-    _lib.check(_lib.lib().cf_op_merge_packed(device, C.byref(o), pt, P, N, Bf, int(frame_hw[0]), int(frame_hw[1]), int(net_hw[0]), int(net_hw[1]),
-                                             ptr(d), ptr(sc), ptr(lm), ptr(cn), rows, max_out, ptr(od), ptr(ol), ptr(oc), ptr(fl)), op=True)
+    args = (pt, P, N, Bf, int(frame_hw[0]), int(frame_hw[1]), int(net_hw[0]), int(net_hw[1]), ptr(d), ptr(sc), ptr(lm), ptr(cn), rows, max_out, ptr(od),
+            ptr(ol), ptr(oc), ptr(fl))
+    if rot:
+        _lib.check(_lib.lib().cf_op_merge_packed_rot(device, int(rot), C.byref(o), *args), op=True)
+    else:
+        _lib.check(_lib.lib().cf_op_merge_packed(device, C.byref(o), *args), op=True)
     return od, ol, oc, fl
 
 

@@ -249,6 +249,38 @@ template <int N> __device__ __forceinline__ void cf_sync_lds_dma_keep() {
     __syncthreads();
 }
 
+// v / DIV for every v < N as one 24-bit multiply and a shift (v_mul_u32_u24 + v_lshrrev), exact over that range: checked at compile
+// time.  For per-lane coordinates whose divisor is a template constant (halo pixel index -> halo row).
+template <int DIV, int N, int SH = 16>
+struct MulShiftDiv {
+    static constexpr unsigned MUL = ((1u << SH) + DIV - 1) / DIV;
+    static constexpr bool exact() {
+        for (unsigned v = 0; v < (unsigned)N; ++v) if (((v * MUL) >> SH) != v / DIV) return false;
+        return true;
+    }
+    static_assert((unsigned long long)N * MUL < (1ull << 32) && N < (1 << 24) && MUL < (1u << 24) && exact(), "24-bit multiply, exact quotient");
+    static __device__ __forceinline__ unsigned div(unsigned v) { return (v * MUL) >> SH; }
+};
+
+// Buffer access with the hardware range check as the predicate: a raw descriptor over a whole tensor, 32-bit byte offsets; an offset
+// at or past the descriptor's byte count reads zeros / stores nothing.  Tensors addressed this way are below 2 GiB (the launchers
+// check), so bit 31 of an offset (CF_OOB) is "no access".
+typedef __amdgpu_buffer_rsrc_t cf_rsrc_t;
+typedef __attribute__((ext_vector_type(4))) unsigned int cf_v4u;
+constexpr unsigned CF_OOB = 0x80000000u;
+__device__ __forceinline__ cf_rsrc_t cf_rsrc(const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);      // flags: 32-bit raw data format
+}
+__device__ __forceinline__ u32x4 cf_bload16(cf_rsrc_t r, unsigned off) {
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+}
+__device__ __forceinline__ uint32_t cf_bload4(cf_rsrc_t r, unsigned off) {
+    return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0);
+}
+__device__ __forceinline__ void cf_bstore16(const u32x4& v, cf_rsrc_t r, unsigned off) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cf_v4u, v), r, (int)off, 0, 0);
+}
+
 // Lane -> output pixel map of the depthwise phase (pixel-pair tile kernels: cf_mbconv2.hip, cf_stem0.hip).
 //
 // A lane reads its pixel's pixel-pair rows from the LDS tile with ds_read_b128 at  e * PITCH + const, PITCH / 16 odd,

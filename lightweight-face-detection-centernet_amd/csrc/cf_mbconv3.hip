@@ -298,6 +298,14 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
 
 #include CF_EXP_INC(cf_mbconv3_0)   // rounds-persistent variant: measured slower (profiles/r03_mfma_depthwise.md), experiments build only
 
+// ---- MODE != 0 of the fused kernels below (profiles/r09_front_overhead.md; layer1.1 and layer2.0): the X loads of the rounds (bit 0)
+// and of the 16-channel tail round (bit 1) take a 32-bit byte offset into a buffer descriptor (cf_uphead.hip: an offset at or past
+// the descriptor's byte count reads zeros): ZeroPad2d, a pixel block past the halo and the Cin chunk past a pixel's row are all "bit 31
+// of the offset" -- no clamps, no data selects, no 64-bit address arithmetic; the halo row of a pixel index is one 24-bit multiply
+// and a shift, exact over the index range (checked at compile time; a table in memory was measured slower on layer1.0 and the stem).
+// The launcher checks: x below 2 GiB, a row of x below 16 MiB.  MODE 0 is the kernel for any size.  The launchers take MODE 3 for the
+// measured instance alone; each bit was measured by itself too.
+
 // ================================================================== fully fused block: expand -> depthwise -> project (+residual)
 // One workgroup per output tile; the hidden channels go through the tile in rounds of 32 (+ an optional last round of 16:
 // hid = 144): expand the halo for the round -> quad cells in LDS -> matrix-core depthwise -> Swish -> the lane's eight (four)
@@ -320,9 +328,10 @@ struct Fx {
     static_assert(!TAIL16 || JX <= 2, "16-channel round: one 16x16x32 expand MFMA, Cin <= 32");
 };
 
-template <int KS, int JX, int NMB, bool RESID, int TOH, int TOW, int NW, bool TAIL16, bool XRELOAD, bool ALDS, bool SB = false>
+template <int KS, int JX, int NMB, bool RESID, int TOH, int TOW, int NW, bool TAIL16, bool XRELOAD, bool ALDS, bool SB = false, int MODE = 0>
 __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
     typedef Fx<KS, JX, NMB, TOH, TOW, NW, TAIL16, ALDS> G;
+    constexpr bool FAST_LD = (MODE & 1) != 0, FAST_TL = (MODE & 2) != 0;
     constexpr int IWQ = G::IWQ, IWP = G::IWP, IPX = G::IPX, NIB = G::NIB, MAXI = G::MAXI, CP8 = G::CP8, CP4 = G::CP4;
     constexpr int SPW = G::SPW, WXB = G::WXB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -355,7 +364,31 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
     // X fragments of this wave's halo pixel blocks (MFMA A operand: lane = pixel, 8 contiguous Cin per half): resident, or
     // (XRELOAD) fetched again from L2 at the top of every round; clamped address + zero select = ZeroPad2d
     u32x4 xf[MAXI][JX];
+    // MODE != 0: byte offset of halo pixel ip for a lane whose chunk starts at lbase = tile0 + its chunk offset (tile0: halo pixel (0, 0)
+    // over the batch; it wraps below zero at the top / left edge, and only pixels inside the map are addressed with it); a pixel past
+    // the halo (ip >= IPX) lies at iy >= IH: folded into the row test
+    typedef MulShiftDiv<IWP, (MAXI * NW * 32 > NIB * 32 ? MAXI * NW * 32 : NIB * 32)> HD;
+    const int gy0 = oy0 - p.pad_lo, gx0h = ox0 - p.pad_lo;
+    const unsigned hlim = (unsigned)min(p.Hin, gy0 + G::IH);
+    const unsigned rowb24 = rowbytes & 0xffffffu, pitch24 = ((unsigned)p.Win * rowbytes) & 0xffffffu;
+    const unsigned tile0 = (((unsigned)b * (unsigned)p.Hin + (unsigned)gy0) * (unsigned)p.Win + (unsigned)gx0h) * rowbytes;
+    const cf_rsrc_t xr = cf_rsrc(p.x, MODE ? (unsigned)p.B * (unsigned)p.Hin * (unsigned)p.Win * rowbytes : 0u);
+    auto halo_off = [&](unsigned ip, unsigned lbase) -> unsigned {
+        const unsigned iy = HD::div(ip), ix = ip - iy * (unsigned)IWP;
+        const bool valid = (unsigned)(gy0 + (int)iy) < hlim && (unsigned)(gx0h + (int)ix) < (unsigned)p.Win;
+        return valid ? iy * pitch24 + (ix * rowb24 + lbase) : CF_OOB;         // factors below 2^24 by their masks: two v_mad_u32_u24
+    };
     auto load_x = [&]() {
+    if constexpr (FAST_LD) {
+        const unsigned oobh = (h && (p.Cin & 8)) ? CF_OOB : 0u;      // an odd chunk count: the upper half's last chunk lies past the pixel's row
+#pragma unroll
+        for (int t = 0; t < MAXI; ++t) {
+            const unsigned off = halo_off((unsigned)(wave * 32 + pl + t * NW * 32), tile0 + (unsigned)(h * JX * 16));
+#pragma unroll
+            for (int j = 0; j < JX; ++j) xf[t][j] = cf_bload16(xr, (j == JX - 1 ? (off | oobh) : off) + j * 16);
+        }
+        return;
+    }
 #pragma unroll
     for (int t = 0; t < MAXI; ++t) {
         const int ib = wave + NW * t;
@@ -510,6 +543,29 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
         for (int mb = 0; mb < NMB; ++mb)
             wp4[mb] = *reinterpret_cast<const u32x2*>((const char*)p.wproj + (size_t)nq * NMB * 1024 + ((size_t)mb * 64 + lane) * 8);
         __syncthreads();
+        if constexpr (FAST_TL) {
+            // every wave runs the same NSB sub-blocks: unrolled, the loads of all of them requested before the first MFMA; a Cin chunk
+            // past the pixel's row (kc = 3 at Cin = 24) is bit 31 of the lane's base
+            static_assert((NIB * 2) % NW == 0, "whole sub-block rounds");
+            constexpr int NSB = NIB * 2 / NW;
+            const int kc = lane >> 4;
+            const unsigned lb = tile0 + (unsigned)(kc * 16) + (kc * 8 < p.Cin ? 0u : CF_OOB);
+            u32x4 xv[NSB];
+#pragma unroll
+            for (int i = 0; i < NSB; ++i) xv[i] = cf_bload16(xr, halo_off((unsigned)((wave + NW * i) * 16 + (lane & 15)), lb));
+            char* ecell = E + (unsigned)(wave * 4 + kc) * (unsigned)CP4 + (lane & 15) * 8;
+#pragma unroll
+            for (int i = 0; i < NSB; ++i) {
+                f32x4 a4 = {0.0f, 0.0f, 0.0f, 0.0f};
+                a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xv[i]), __builtin_bit_cast(mfma_bf16x8, wv), a4, 0, 0, 0);
+                f32x2 u0, u1; u0.x = a4[0]; u0.y = a4[1]; u1.x = a4[2]; u1.y = a4[3];
+                const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
+                u32x2 d;
+                d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
+                d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
+                *reinterpret_cast<u32x2*>(ecell + i * (NW * 4 * CP4)) = d;
+            }
+        } else
         for (int sb = wave; sb < NIB * 2; sb += NW) {               // 16-pixel sub-blocks = 4 quads each
             const int ip = sb * 16 + (lane & 15), kc = lane >> 4;   // A operand: lane (pixel, Cin chunk)
             const int ipc = ip < IPX ? ip : IPX - 1;
@@ -619,9 +675,10 @@ struct Fs {
     static_assert(!TAIL16 || JX <= 2, "16-channel round: one 16x16x32 expand MFMA, Cin <= 32");
 };
 
-template <int KS, int JX, int NMB, int TOH, int TOW, bool TAIL16, bool XRELOAD, bool ALDS>
+template <int KS, int JX, int NMB, int TOH, int TOW, bool TAIL16, bool XRELOAD, bool ALDS, int MODE = 0>
 __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
     typedef Fs<KS, JX, NMB, TOH, TOW, TAIL16, ALDS> G;
+    constexpr bool FAST_LD = (MODE & 1) != 0, FAST_TL = (MODE & 2) != 0;
     constexpr int IWQ = G::IWQ, IWP = G::IWP, IPX = G::IPX, NIB = G::NIB, MAXI = G::MAXI, CP8 = G::CP8, CP4 = G::CP4;
     constexpr int WXB = G::WXB, NW = 4, KSTEPS = 3, NSTEP = G::NSTEP, HQ = (IWQ + 1) / 2;
     typedef __attribute__((ext_vector_type(4))) __bf16 mfma_bf16x4;
@@ -648,7 +705,31 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
                                              (__attribute__((address_space(3))) void*)(dst + c * 1024), 16, 0, 0);
     };
     u32x4 xf[MAXI][JX];
+    // MODE != 0: byte offset of halo pixel ip (cell order: a row's even x-quads first, then the odd ones) for a lane whose chunk starts at
+    // lbase = tile0 + its chunk offset, as in mbconv_mx_kernel; a pixel past the halo lies at iy >= IH: folded into the row test
+    typedef MulShiftDiv<IWQ, (MAXI * NW * 8 > NIB * 8 ? MAXI * NW * 8 : NIB * 8)> HD;
+    const int gy0 = oy0 * 2 - p.pad_lo, gx0h = ox0 * 2 - p.pad_lo;
+    const unsigned hlim = (unsigned)min(p.Hin, gy0 + G::IH);
+    const unsigned rowb24 = rowbytes & 0xffffffu, pitch24 = ((unsigned)p.Win * rowbytes) & 0xffffffu;
+    const unsigned tile0 = (((unsigned)b * (unsigned)p.Hin + (unsigned)gy0) * (unsigned)p.Win + (unsigned)gx0h) * rowbytes;
+    const cf_rsrc_t xr = cf_rsrc(p.x, MODE ? (unsigned)p.B * (unsigned)p.Hin * (unsigned)p.Win * rowbytes : 0u);
+    auto halo_off = [&](unsigned ip, unsigned lbase) -> unsigned {
+        const unsigned cc = ip >> 2, iy = HD::div(cc), pos = cc - iy * (unsigned)IWQ;
+        const unsigned ix = 4u * (pos < (unsigned)HQ ? 2u * pos : 2u * pos - (unsigned)(2 * HQ - 1)) + (ip & 3u);
+        const bool valid = (unsigned)(gy0 + (int)iy) < hlim && (unsigned)(gx0h + (int)ix) < (unsigned)p.Win;
+        return valid ? iy * pitch24 + (ix * rowb24 + lbase) : CF_OOB;         // factors below 2^24 by their masks: two v_mad_u32_u24
+    };
     auto load_x = [&]() {
+    if constexpr (FAST_LD) {
+        const unsigned oobh = (h && (p.Cin & 8)) ? CF_OOB : 0u;      // an odd chunk count: the upper half's last chunk lies past the pixel's row
+#pragma unroll
+        for (int t = 0; t < MAXI; ++t) {
+            const unsigned off = halo_off((unsigned)(wave * 32 + pl + t * NW * 32), tile0 + (unsigned)(h * JX * 16));
+#pragma unroll
+            for (int j = 0; j < JX; ++j) xf[t][j] = cf_bload16(xr, (j == JX - 1 ? (off | oobh) : off) + j * 16);
+        }
+        return;
+    }
 #pragma unroll
     for (int t = 0; t < MAXI; ++t) {
         const int ib = wave + NW * t;
@@ -782,6 +863,34 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
         for (int mb = 0; mb < NMB; ++mb)
             wp4[mb] = *reinterpret_cast<const u32x2*>((const char*)p.wproj + (size_t)nq * 2 * NMB * 512 + ((size_t)mb * 64 + lane) * 8);
         __syncthreads();
+        if constexpr (FAST_TL) {
+            // every wave runs the same NSB sub-blocks, in groups of UB: the loads of a group requested before its first MFMA; a Cin
+            // chunk past the pixel's row (kc = 3 at Cin = 24) is bit 31 of the lane's base
+            static_assert((NIB * 2) % NW == 0, "whole sub-block rounds");
+            constexpr int NSB = NIB * 2 / NW, UB = 4;
+            const int kc = lane >> 4;
+            const unsigned lb = tile0 + (unsigned)(kc * 16) + (kc * 8 < p.Cin ? 0u : CF_OOB);
+            char* ecell = E + (unsigned)(wave * 4 + kc) * (unsigned)CP4 + (lane & 15) * 8;
+#pragma unroll
+            for (int i0 = 0; i0 < NSB; i0 += UB) {
+                u32x4 xv[UB];
+#pragma unroll
+                for (int u = 0; u < UB; ++u)
+                    if (i0 + u < NSB) xv[u] = cf_bload16(xr, halo_off((unsigned)((wave + NW * (i0 + u)) * 16 + (lane & 15)), lb));
+#pragma unroll
+                for (int u = 0; u < UB; ++u) {
+                    if (i0 + u >= NSB) break;
+                    f32x4 a4 = {0.0f, 0.0f, 0.0f, 0.0f};
+                    a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xv[u]), __builtin_bit_cast(mfma_bf16x8, wv), a4, 0, 0, 0);
+                    f32x2 u0, u1; u0.x = a4[0]; u0.y = a4[1]; u1.x = a4[2]; u1.y = a4[3];
+                    const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
+                    u32x2 d;
+                    d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
+                    d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
+                    *reinterpret_cast<u32x2*>(ecell + (i0 + u) * (NW * 4 * CP4)) = d;
+                }
+            }
+        } else
         for (int sb = wave; sb < NIB * 2; sb += NW) {               // 16-pixel sub-blocks = 4 quads each
             const int ip = sb * 16 + (lane & 15), kc = lane >> 4;
             const int ipc = ip < IPX ? ip : IPX - 1;
@@ -998,6 +1107,14 @@ hipError_t fx_launch_t(hipStream_t s, const MbParams& p) {
     set_kernel_tag(SB ? "void cf::mbconv_mx_kernel<%d, %d, %d, %s, %d, %d, %d, %s, %s, %s, true>(cf::MbParams)"
                       : "void cf::mbconv_mx_kernel<%d, %d, %d, %s, %d, %d, %d, %s, %s, %s, false>(cf::MbParams)", KS, JX, NMB, RESID ? "true" : "false",
                    TOH, TOW, NW, TAIL16 ? "true" : "false", XRELOAD ? "true" : "false", ALDS ? "true" : "false");
+    // MODE 3 for layer1.1's instance alone (the one measured and digest-tested, profiles/r09_front_overhead.md; its tail round needs whole
+    // sub-block rounds): 32-bit offsets with bit 31 as "no access" and 24-bit multiplies by the row pitch -- x below 2 GiB, a row of it below
+    // 16 MiB; the timing experiments stay on the general kernel, as does CF_FRONT_MODE=0 (experiments build: A/B runs, digests of MODE 0)
+    if constexpr (KS == 3 && JX == 2 && NMB == 2 && RESID && TOH == 16 && TOW == 16 && NW == 4 && TAIL16 && !XRELOAD && ALDS && !SB && (G::NIB * 2) % NW == 0) {
+        static const bool fast_on = cf_ab_int("CF_FRONT_MODE", 1) != 0;
+        const bool small = fast_on && abl == 0 && (size_t)p.B * p.Hin * p.Win * p.Cin * 2 < ((size_t)1 << 31) && (size_t)p.Win * p.Cin * 2 < ((size_t)1 << 24);
+        if (small) return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB, 3>>(grid, blk, G::LDS, s, q);
+    }
     return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB>>(grid, blk, G::LDS, s, q);
 }
 // layer2.1 is compiled in its own translation unit (cf_mbconv3_ilp.hip = this file with CF_ILP_TU defined) under
@@ -1128,6 +1245,13 @@ static hipError_t fs_launch_t(hipStream_t s, const MbParams& p) {
     dim3 grid((p.Wout + TOW - 1) / TOW, (p.Hout + TOH - 1) / TOH, p.B), blk(256);
     set_kernel_tag("void cf::mbconv_mx2_kernel<%d, %d, %d, %d, %d, %s, %s, %s>(cf::MbParams)", KS, JX, NMB, TOH, TOW,
                    TAIL16 ? "true" : "false", XRELOAD ? "true" : "false", ALDS ? "true" : "false");
+    // MODE 3 for layer2.0's instance alone (the one measured and digest-tested, profiles/r09_front_overhead.md): x below 2 GiB, a row of it
+    // below 16 MiB; CF_FRONT_MODE=0 (experiments build) keeps the general kernel
+    if constexpr (KS == 5 && JX == 2 && NMB == 2 && TOH == 8 && TOW == 16 && TAIL16 && !XRELOAD && !ALDS && (G::NIB * 2) % 4 == 0) {
+        static const bool fast_on = cf_ab_int("CF_FRONT_MODE", 1) != 0;
+        const bool small = fast_on && (size_t)p.B * p.Hin * p.Win * p.Cin * 2 < ((size_t)1 << 31) && (size_t)p.Win * p.Cin * 2 < ((size_t)1 << 24);
+        if (small) return launch_lds<mbconv_mx2_kernel<KS, JX, NMB, TOH, TOW, TAIL16, XRELOAD, ALDS, 3>>(grid, blk, G::LDS, s, p);
+    }
     return launch_lds<mbconv_mx2_kernel<KS, JX, NMB, TOH, TOW, TAIL16, XRELOAD, ALDS>>(grid, blk, G::LDS, s, p);
 }
 #define FSE(V, KS, JX, NMB, TAIL, TOH, TOW, XR, AL) \

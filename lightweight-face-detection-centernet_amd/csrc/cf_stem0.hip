@@ -501,6 +501,9 @@ __global__ __launch_bounds__(S0P_NT) void stem0_px_kernel(Stem0Params p) {
             const int r = r0 + it * RSTEP;
             if (tact && r < S0_PH) Xs[r * S0P_PROW + 2 + e] = (T)(pack_bf16x2(v[it], 0.0f) & 0xffffu);
         }
+        // element 2 + ECOLS of a row is read too, by the last halo column's second chunk (a k-slot whose stem weight is zero): it must
+        // not be whatever the workgroup before left in LDS (0 * NaN is NaN)
+        if (tid < S0_PH) Xs[tid * S0P_PROW + 2 + ECOLS] = (T)0;
     }
     __syncthreads();
 
@@ -665,8 +668,28 @@ void stem0mx_pack(const float* ws, const float* wd, const float* wp, void* wstem
     }
 }
 
-template <int FMT>
+// ---- MODE 1 of stem0_mx_kernel (profiles/r09_front_overhead.md), the staging of the uint8 image: one 32-bit offset per thread into a
+// buffer descriptor (cf_uphead.hip: an offset at or past the descriptor's byte count reads zeros), advanced by the row stride, and the
+// normalisation constants from a compile-time table.  MODE 0 is the kernel for any size: 64-bit addresses, a clamp per row, the
+// constants by select chains.  (The same treatment of the operand gather -- offsets from a table -- and of the stores measured
+// slower / neutral and is not here.)  The staging thread's first row tid / ND and (dword column + 1) / 3 by MulShiftDiv: a table in
+// memory for these was measured, its load sits in front of the image loads and cost more than the divisions.
+// normalisation of the four bytes of a dword by channel phase: {scale[4], shift[4]}; centerface.py:12-15 (BGR): mean 0.408 0.447 0.470,
+// std 0.289 0.274 0.278
+struct S0NormTab {
+    alignas(32) float v[3][8];                                      // a phase's row is read as two 16-byte vectors
+    constexpr S0NormTab() : v() {
+        for (int ph = 0; ph < 3; ++ph)
+            for (int i = 0; i < 4; ++i) {
+                const int ci = (ph + i) % 3;
+                v[ph][i] = ci == 0 ? 1.0f / (255.0f * 0.289f) : ci == 1 ? 1.0f / (255.0f * 0.274f) : 1.0f / (255.0f * 0.278f);
+                v[ph][4 + i] = ci == 0 ? -0.408f / 0.289f : ci == 1 ? -0.447f / 0.274f : -0.470f / 0.278f;
+            }
+    }
+};
+template <int FMT, int MODE = 0>
 __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
+    constexpr bool FAST = MODE != 0;
     typedef bf16_t T;
     // The normalised patch Xs is dead once every wave has gathered its MFMA operands, so it shares the
     // LDS bytes of the tile E that phase 1 then writes: 25 KB per workgroup instead of 34 (6 instead of 4
@@ -693,12 +716,23 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
         // normalisation is (u/255 - mean)/std as one fma per byte (1 ulp from the reference's two
         // divisions, far below the bf16 rounding that follows); outside the image: exact 0 (ZeroPad2d).
         constexpr int ND = S0P_ND, RG = S0P_NT / ND, NITD = (S0_PH + RG - 1) / RG;
-        const int d = tid % ND, rg = tid / ND;
+        static constexpr S0NormTab kNorm{};
+        const int rg = FAST ? (int)MulShiftDiv<ND, S0P_NT>::div((unsigned)tid) : tid / ND, d = FAST ? tid - rg * ND : tid % ND;
         const bool tact = rg < RG;
         const int boff = ix0 * 3 - 2 + 4 * d;
         const bool din = tact && boff >= 0 && boff + 4 <= p.W * 3;
         const int cboff = min(max(boff, 0), p.W * 3 - 4);
         float sc[4], sh[4]; bool bok[4];
+        if constexpr (FAST) {
+            // channel phase of the dword's first byte, element 4 d - 2 of the patch row: (4 d + 1) % 3 = (d + 1) % 3
+            const unsigned d1 = (unsigned)d + 1u, ph = d1 - 3u * MulShiftDiv<3, ND + 1>::div(d1);
+            const u32x4* nt = reinterpret_cast<const u32x4*>(kNorm.v[ph]);
+            const u32x4 a = nt[0], c = nt[1];
+            sc[0] = __uint_as_float(a.x); sc[1] = __uint_as_float(a.y); sc[2] = __uint_as_float(a.z); sc[3] = __uint_as_float(a.w);
+            sh[0] = __uint_as_float(c.x); sh[1] = __uint_as_float(c.y); sh[2] = __uint_as_float(c.z); sh[3] = __uint_as_float(c.w);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bok[i] = din && 4 * d - 2 + i >= 0 && 4 * d - 2 + i < S0_PW * 3;
+        } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int e = 4 * d - 2 + i;                         // element of the patch row, e = col*3 + ci
@@ -708,11 +742,23 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
             sc[i] = ci == 0 ? 1.0f / (255.0f * 0.289f) : ci == 1 ? 1.0f / (255.0f * 0.274f) : 1.0f / (255.0f * 0.278f);
             sh[i] = ci == 0 ? -0.408f / 0.289f : ci == 1 ? -0.447f / 0.274f : -0.470f / 0.278f;
         }
+        }
         uint32_t v[NITD];
+        if constexpr (FAST) {
+            // one 32-bit offset per thread, advanced by RG image rows.  No row clamp: a row above the first image wraps to an offset past
+            // the descriptor and reads zeros, as a row below the last image does; a row of the neighbouring image is inside the tensor.
+            // Neither is used: the border path of convert() replaces every byte of a row outside the image.
+            const cf_rsrc_t xr = cf_rsrc(p.x, (unsigned)p.B * (unsigned)p.H * (unsigned)p.W * 3u);
+            const unsigned rowb = (unsigned)p.W * 3u;
+            const unsigned off0 = ((unsigned)b * (unsigned)p.H + (unsigned)(iy0 + rg)) * rowb + (unsigned)cboff;
+#pragma unroll
+            for (int it = 0; it < NITD; ++it) v[it] = cf_bload4(xr, off0 + (unsigned)(it * RG) * rowb);
+        } else {
 #pragma unroll
         for (int it = 0; it < NITD; ++it) {
             const int cy = min(max(iy0 + rg + it * RG, 0), p.H - 1);
             v[it] = *reinterpret_cast<const uint32_t*>((const uint8_t*)p.x + ((size_t)b * p.H + cy) * p.W * 3 + cboff);
+        }
         }
         // Interior tiles (81 % at 640x640: the whole patch inside the image) need no zero-padding selects.  Elements of the
         // dword columns that lie outside the PATCH then hold neighbouring pixels instead of 0: nothing reads them except
@@ -760,6 +806,9 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
             const int r = r0 + it * RSTEP;
             if (tact && r < S0_PH) Xs[r * S0P_PROW + 2 + e] = (T)(pack_bf16x2(v[it], 0.0f) & 0xffffu);
         }
+        // element 2 + ECOLS of a row is read too, by the last halo column's second chunk (a k-slot whose stem weight is zero): it must
+        // not be whatever the workgroup before left in LDS (0 * NaN is NaN)
+        if (tid < S0_PH) Xs[tid * S0P_PROW + 2 + ECOLS] = (T)0;
     }
     __syncthreads();
 
@@ -876,8 +925,13 @@ hipError_t launch_stem0(hipStream_t s, int dtype, const Stem0Params& p) {
         if (dtype != 1) return hipErrorInvalidValue;
         dim3 grid((Wo + S0_TOW - 1) / S0_TOW, (Ho + S0_TOH - 1) / S0_TOH, p.B), blk(S0P_NT);
         set_kernel_tag("void cf::stem0_mx_kernel<%d>(cf::Stem0Params)", p.in_format);
-        if (p.in_format == CF_IN_U8_HWC_BGR) hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_U8_HWC_BGR>), grid, blk, 0, s, p);
-        else hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_F32_NCHW>), grid, blk, 0, s, p);
+        // MODE 1: 32-bit byte offsets into the image, below 2 GiB (the offset of a row above the first image wraps far past it)
+        static const bool fast_on = cf_ab_int("CF_FRONT_MODE", 1) != 0;        // experiments build: 0 keeps the general kernel
+        const bool small = fast_on && (size_t)p.B * p.H * p.W * 3 < ((size_t)1 << 31);
+        if (p.in_format == CF_IN_U8_HWC_BGR) {
+            if (small) hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_U8_HWC_BGR, 1>), grid, blk, 0, s, p);
+            else hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_U8_HWC_BGR>), grid, blk, 0, s, p);
+        } else hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_F32_NCHW>), grid, blk, 0, s, p);
         return hipGetLastError();
     }
     if (p.kind & STEM0_PX) {

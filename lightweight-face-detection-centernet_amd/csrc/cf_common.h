@@ -281,6 +281,49 @@ __device__ __forceinline__ void cf_bstore16(const u32x4& v, cf_rsrc_t r, unsigne
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cf_v4u, v), r, (int)off, 0, 0);
 }
 
+// Expand deal by row pair (profiles/r10_halo_deal.md): which halo pixel lane pl of expand block t of wave w loads, for the matrix-core
+// kernels with a 16-wide tile (halo rows of five x-quads = 20 columns), four waves and an even halo height IH = 16 + KS - 1.  Pixel pl
+// of a 32-pixel block is MFMA row pl, so register quad tq = pl >> 3 of lane half hh = (pl >> 2) & 1 holds the four x = pl & 3 of ONE
+// quad cell, and the deal makes "this cell does not exist" a statement about (w, t, tq), never about a lane:
+//   blocks 0, 1 (KS = 5: block 2 of waves 0, 1 too)   row pair 4 t + w (rows 2 rp + hh), main quads tq = 0 .. 3
+//   KS = 3, block 2, waves 0, 1    row pair 8, main quads 2 w + tq, tq < 2
+//   KS = 3, block 2, waves 2, 3    the live half (columns 16, 17; 18 and 19 meet only zero Toeplitz entries) of quad 4 of all nine row
+//                                  pairs, two per register quad: x = 0, 1 row pair 4 (w - 2) + 2 tq, x = 2, 3 the next; four on wave
+//                                  2, five on wave 3
+//   KS = 5, waves 2, 3             quad 4 (all four columns live) of row pair 4 (w - 2) + tq in block 2, of row pair 6 + w in tq = 0
+//                                  of block 3
+// Shifts and constants only: w is wave-uniform and t a constant after unrolling.  The cell stores that go with it: cf_mx.h.
+template <int KS>
+struct HaloDeal {
+    static_assert(KS == 3 || KS == 5, "an even halo height");
+    static constexpr int IH = 16 + KS - 1, IWQ = 5, NRP = IH / 2, NBLK = KS == 3 ? 3 : 4;
+    // row pairs whose quad-4 half wave w (2 or 3) activates in block 2 of the 3x3 deal
+    static __device__ __forceinline__ int side_pairs(int w) { return w == 2 ? 4 : NRP - 4; }
+    // false: the lane has no pixel (ty = tx = 0 then)
+    static __device__ __forceinline__ bool pixel(int w, int t, int pl, int& ty, int& tx) {
+        const int tq = pl >> 3, hh = (pl >> 2) & 1, x = pl & 3;
+        bool live = true;
+        if (t < 2) {
+            ty = 2 * (4 * t + w) + hh; tx = 4 * tq + x;
+        } else if constexpr (KS == 3) {
+            const bool side = w >= 2;
+            const int lp = 2 * tq + (x >> 1);
+            live = side ? lp < side_pairs(w) : tq < 2;
+            ty = (side ? 2 * (4 * (w - 2) + lp) : 16) + hh;
+            tx = side ? 16 + (x & 1) : 8 * w + 4 * tq + x;
+        } else if (t == 2) {
+            const bool side = w >= 2;
+            ty = 2 * (side ? 4 * (w - 2) + tq : 8 + w) + hh;
+            tx = side ? 16 + x : 4 * tq + x;
+        } else {
+            live = w >= 2 && tq == 0;
+            ty = 2 * (6 + w) + hh; tx = 16 + x;
+        }
+        ty = live ? ty : 0; tx = live ? tx : 0;
+        return live;
+    }
+};
+
 // Lane -> output pixel map of the depthwise phase (pixel-pair tile kernels: cf_mbconv2.hip, cf_stem0.hip).
 //
 // A lane reads its pixel's pixel-pair rows from the LDS tile with ds_read_b128 at  e * PITCH + const, PITCH / 16 odd,

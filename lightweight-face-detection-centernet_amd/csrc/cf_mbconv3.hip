@@ -305,6 +305,11 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
 // and a shift, exact over the index range (checked at compile time; a table in memory was measured slower on layer1.0 and the stem).
 // The launcher checks: x below 2 GiB, a row of x below 16 MiB.  MODE 0 is the kernel for any size.  The launchers take MODE 3 for the
 // measured instance alone; each bit was measured by itself too.
+// Bit 2 of mbconv_mx_kernel's MODE (profiles/r10_halo_deal.md; layer1.1 and layer2.1, on top of bit 0): the rounds' expand blocks are
+// dealt to the waves by halo ROW PAIR (HaloDeal in cf_common.h, halo_deal_store in cf_mx.h) instead of in linear pixel order, so that a
+// register quad is one quad cell for both lane halves and a cell that nothing reads costs no Swish: per round 20 / 20 / 20 / 21
+// swish2_pre per wave instead of 24 each (3x3), 24 / 24 / 26 / 26 instead of 32 / 24 / 24 / 24 (5x5).  The cell layout, the depthwise,
+// the tail round and the epilogue are untouched: only who writes which cell changes.
 
 // ================================================================== fully fused block: expand -> depthwise -> project (+residual)
 // One workgroup per output tile; the hidden channels go through the tile in rounds of 32 (+ an optional last round of 16:
@@ -331,9 +336,13 @@ struct Fx {
 template <int KS, int JX, int NMB, bool RESID, int TOH, int TOW, int NW, bool TAIL16, bool XRELOAD, bool ALDS, bool SB = false, int MODE = 0>
 __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
     typedef Fx<KS, JX, NMB, TOH, TOW, NW, TAIL16, ALDS> G;
-    constexpr bool FAST_LD = (MODE & 1) != 0, FAST_TL = (MODE & 2) != 0;
+    constexpr bool FAST_LD = (MODE & 1) != 0, FAST_TL = (MODE & 2) != 0, DEAL = (MODE & 4) != 0;
     constexpr int IWQ = G::IWQ, IWP = G::IWP, IPX = G::IPX, NIB = G::NIB, MAXI = G::MAXI, CP8 = G::CP8, CP4 = G::CP4;
     constexpr int SPW = G::SPW, WXB = G::WXB;
+    constexpr int DKS = KS == 5 ? 5 : 3;                            // (HaloDeal exists for 3 and 5: other kernel sizes never have DEAL)
+    typedef HaloDeal<DKS> HDL;
+    static_assert(!DEAL || (FAST_LD && (KS == 3 || KS == 5) && TOH == 16 && TOW == 16 && NW == 4 && MAXI == HDL::NBLK && G::IH == HDL::IH && IWQ == HDL::IWQ),
+                  "the row-pair deal: 16x16 tile, four waves, loads through the descriptor");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* E = smem;
     char* Wst = smem + G::EBYTES;
@@ -383,7 +392,15 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
         const unsigned oobh = (h && (p.Cin & 8)) ? CF_OOB : 0u;      // an odd chunk count: the upper half's last chunk lies past the pixel's row
 #pragma unroll
         for (int t = 0; t < MAXI; ++t) {
-            const unsigned off = halo_off((unsigned)(wave * 32 + pl + t * NW * 32), tile0 + (unsigned)(h * JX * 16));
+            unsigned off;
+            if constexpr (DEAL) {
+                // the lane's halo pixel by row pair (HaloDeal, cf_common.h); a lane without a pixel reads zeros, like a padded one.  Every
+                // wave issues every block's loads
+                int ty, tx;
+                const bool live = HDL::pixel(wave, t, pl, ty, tx);
+                const bool valid = live && (unsigned)(gy0 + ty) < hlim && (unsigned)(gx0h + tx) < (unsigned)p.Win;
+                off = valid ? (unsigned)ty * pitch24 + ((unsigned)tx * rowb24 + (tile0 + (unsigned)(h * JX * 16))) : CF_OOB;
+            } else off = halo_off((unsigned)(wave * 32 + pl + t * NW * 32), tile0 + (unsigned)(h * JX * 16));
 #pragma unroll
             for (int j = 0; j < JX; ++j) xf[t][j] = cf_bload16(xr, (j == JX - 1 ? (off | oobh) : off) + j * 16);
         }
@@ -464,7 +481,7 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
 #pragma unroll
         for (int t = 0; t < MAXI; ++t) {
             const int ib = wave + NW * t;
-            if (ib >= NIB) break;
+            if (DEAL ? (KS == 5 && t == 3 && wave < 2) : ib >= NIB) break;      // DEAL: the 5x5 deal's fourth block exists on waves 2, 3
             f32x16 a;
 #pragma unroll
             for (int r = 0; r < 16; ++r) a[r] = 0.0f;
@@ -474,6 +491,7 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
                 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mfma_bf16x8, xf[t][j]),
                                                             __builtin_bit_cast(mfma_bf16x8, wv), a, 0, 0, 0);
             }
+            if constexpr (DEAL) { halo_deal_store<DKS, CP8>(E, wave, t, h, pl, a); continue; }
             char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)CP8 + pl * 8;
 #pragma unroll
             for (int tq = 0; tq < 4; ++tq) {
@@ -1107,13 +1125,24 @@ hipError_t fx_launch_t(hipStream_t s, const MbParams& p) {
     set_kernel_tag(SB ? "void cf::mbconv_mx_kernel<%d, %d, %d, %s, %d, %d, %d, %s, %s, %s, true>(cf::MbParams)"
                       : "void cf::mbconv_mx_kernel<%d, %d, %d, %s, %d, %d, %d, %s, %s, %s, false>(cf::MbParams)", KS, JX, NMB, RESID ? "true" : "false",
                    TOH, TOW, NW, TAIL16 ? "true" : "false", XRELOAD ? "true" : "false", ALDS ? "true" : "false");
-    // MODE 3 for layer1.1's instance alone (the one measured and digest-tested, profiles/r09_front_overhead.md; its tail round needs whole
-    // sub-block rounds): 32-bit offsets with bit 31 as "no access" and 24-bit multiplies by the row pitch -- x below 2 GiB, a row of it below
+    // MODE 7 = 3 + the expand deal by row pair (bit 2, below) for layer1.1's instance alone (the one measured and digest-tested,
+    // profiles/r09_front_overhead.md; its tail round needs whole sub-block rounds): 32-bit offsets with bit 31 as "no access" and 24-bit multiplies by the row pitch -- x below 2 GiB, a row of it below
     // 16 MiB; the timing experiments stay on the general kernel, as does CF_FRONT_MODE=0 (experiments build: A/B runs, digests of MODE 0)
     if constexpr (KS == 3 && JX == 2 && NMB == 2 && RESID && TOH == 16 && TOW == 16 && NW == 4 && TAIL16 && !XRELOAD && ALDS && !SB && (G::NIB * 2) % NW == 0) {
-        static const bool fast_on = cf_ab_int("CF_FRONT_MODE", 1) != 0;
-        const bool small = fast_on && abl == 0 && (size_t)p.B * p.Hin * p.Win * p.Cin * 2 < ((size_t)1 << 31) && (size_t)p.Win * p.Cin * 2 < ((size_t)1 << 24);
-        if (small) return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB, 3>>(grid, blk, G::LDS, s, q);
+        static const int front = cf_ab_int("CF_FRONT_MODE", 1);
+        const bool small = front != 0 && abl == 0 && (size_t)p.B * p.Hin * p.Win * p.Cin * 2 < ((size_t)1 << 31) && (size_t)p.Win * p.Cin * 2 < ((size_t)1 << 24);
+#ifdef CF_EXPERIMENTS
+        if (small && front == 2) return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB, 3>>(grid, blk, G::LDS, s, q);
+#endif
+        if (small) return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB, 7>>(grid, blk, G::LDS, s, q);
+    }
+    // MODE 5 for layer2.1's instance alone (no tail round): bit 0 as above and bit 2, the expand deal by row pair (HaloDeal in cf_common.h,
+    // profiles/r10_halo_deal.md) -- layer1.1's MODE 7 has the same bit.  Same preconditions.  CF_FRONT_MODE=2 (experiments build) launches
+    // what ran before that deal, for A/B runs: layer1.1 on MODE 3, layer2.1 on the general kernel.
+    if constexpr (KS == 5 && JX == 2 && NMB == 2 && RESID && TOH == 16 && TOW == 16 && NW == 4 && !TAIL16 && !XRELOAD && ALDS && !SB) {
+        static const int front = cf_ab_int("CF_FRONT_MODE", 1);
+        const bool small = front != 0 && front != 2 && abl == 0 && (size_t)p.B * p.Hin * p.Win * p.Cin * 2 < ((size_t)1 << 31) && (size_t)p.Win * p.Cin * 2 < ((size_t)1 << 24);
+        if (small) return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB, 5>>(grid, blk, G::LDS, s, q);
     }
     return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB>>(grid, blk, G::LDS, s, q);
 }

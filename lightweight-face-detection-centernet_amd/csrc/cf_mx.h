@@ -29,6 +29,61 @@ __device__ __forceinline__ f32x2 swish2_pre(f32x2 u) {      // u = -log2(e) x  -
     return u * r;
 }
 
+// Swish + cell stores of expand block t of wave w under HaloDeal<KS> (cf_common.h); a = the block's 32x32 expand accumulators (lane =
+// channel pl of lane half h, register quad tq = rows 8 tq + 4 h ..).  Every cell the depthwise reads is written, every round: the dead
+// column pair of a 3x3 halo's quad 4 as ZERO, never left to what the workgroup before had in those bytes (the depthwise multiplies it
+// by a zero weight, and 0 * NaN is NaN).  Register quads without a cell are neither activated nor stored; every test is on w, t, tq.
+template <int KS, int CP>
+__device__ __forceinline__ void halo_deal_store(char* E, int w, int t, int h, int pl, const f32x16& a) {
+    typedef HaloDeal<KS> D;
+    constexpr int RP = 2 * D::IWQ * CP;                             // bytes from a row pair to the next
+    auto full = [&](int tq, char* dst) {
+        f32x2 u0, u1; u0.x = a[4 * tq]; u0.y = a[4 * tq + 1]; u1.x = a[4 * tq + 2]; u1.y = a[4 * tq + 3];
+        const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
+        u32x2 d;
+        d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
+        d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
+        *reinterpret_cast<u32x2*>(dst) = d;
+    };
+    auto half = [&](float ux, float uy, char* dst) {
+        f32x2 u; u.x = ux; u.y = uy;
+        const f32x2 y = swish2_pre(u);
+        u32x2 d;
+        d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y.x, y.y));
+        d.y = 0u;
+        *reinterpret_cast<u32x2*>(dst) = d;
+    };
+    // ONE vector base for all blocks (row h of row pair 0, quad 0, the lane's channel) + the block's wave-uniform byte offset, added
+    // where it is used: a base per block, hoisted out of the round loop, costs the fused kernels their occupancy step
+    char* const lane0 = E + h * (D::IWQ * CP) + pl * 8;
+    auto at = [&](int so) -> char* { asm volatile("" : "+s"(so)); return lane0 + so; };
+    if (t < 2 || (KS == 5 && t == 2 && w < 2)) {
+        char* e = at((4 * t + w) * RP);
+#pragma unroll
+        for (int tq = 0; tq < 4; ++tq) full(tq, e + tq * CP);
+    } else if constexpr (KS == 3) {
+        if (w < 2) {
+            char* e = at(8 * RP + 2 * w * CP);
+            full(0, e); full(1, e + CP);
+        } else {
+            const int np = D::side_pairs(w);
+            char* e = at(4 * (w - 2) * RP + 4 * CP);
+#pragma unroll
+            for (int tq = 0; tq < 4; ++tq) {
+                if (2 * tq >= np) break;
+                half(a[4 * tq], a[4 * tq + 1], e + 2 * tq * RP);
+                if (2 * tq + 1 < np) half(a[4 * tq + 2], a[4 * tq + 3], e + (2 * tq + 1) * RP);
+            }
+        }
+    } else if (t == 2) {
+        char* e = at(4 * (w - 2) * RP + 4 * CP);
+#pragma unroll
+        for (int tq = 0; tq < 4; ++tq) full(tq, e + tq * RP);
+    } else if (w >= 2) {
+        full(0, at((6 + w) * RP + 4 * CP));
+    }
+}
+
 static inline uint16_t host_f32_to_f16_3(float f) {       // round-to-nearest-even, saturating (= cf_mbconv2.hip)
     uint32_t u; __builtin_memcpy(&u, &f, 4);
     const uint32_t sign = (u >> 16) & 0x8000u;

@@ -674,6 +674,10 @@ void stem0mx_pack(const float* ws, const float* wd, const float* wp, void* wstem
 // constants by select chains.  (The same treatment of the operand gather -- offsets from a table -- and of the stores measured
 // slower / neutral and is not here.)  The staging thread's first row tid / ND and (dword column + 1) / 3 by MulShiftDiv: a table in
 // memory for these was measured, its load sits in front of the image loads and cost more than the divisions.
+// ---- bit 1 of MODE (profiles/r10_halo_deal.md), both input formats: the expand blocks are dealt to the waves by halo row pair
+// (HaloDeal in cf_common.h, halo_deal_store in cf_mx.h) instead of in linear pixel order: 20 / 20 / 20 / 21 swish2_pre per wave instead
+// of 24 each, no Swish on halo columns 18, 19 (written as zero) or on the six quad slots past the halo.  Only who writes which cell of E
+// changes; the gather takes the same (ty, tx).
 // normalisation of the four bytes of a dword by channel phase: {scale[4], shift[4]}; centerface.py:12-15 (BGR): mean 0.408 0.447 0.470,
 // std 0.289 0.274 0.278
 struct S0NormTab {
@@ -689,7 +693,8 @@ struct S0NormTab {
 };
 template <int FMT, int MODE = 0>
 __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
-    constexpr bool FAST = MODE != 0;
+    constexpr bool FAST = (MODE & 1) != 0, DEAL = (MODE & 2) != 0;
+    static_assert(!DEAL || (S0_TOH == 16 && S0_TOW == 16 && S0P_NW == 4 && S0M_IWQ == HaloDeal<3>::IWQ && S0_IH == HaloDeal<3>::IH), "the row-pair deal");
     typedef bf16_t T;
     // The normalised patch Xs is dead once every wave has gathered its MFMA operands, so it shares the
     // LDS bytes of the tile E that phase 1 then writes: 25 KB per workgroup instead of 34 (6 instead of 4
@@ -839,10 +844,15 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
         const int ip = ib * 32 + pl;
         // halo rows of 5 x-quads = 20 columns: columns 18, 19 lie past the 18-wide halo (no output reads them) and repeat column 17
         const int ipc = ip < S0M_IPX ? ip : S0M_IPX - 1;
-        const int ty = ipc / S0M_IWP, txq = ipc - ty * S0M_IWP, tx = txq < S0_IW ? txq : S0_IW - 1;
+        int ty = ipc / S0M_IWP, tx = ipc - ty * S0M_IWP;
+        bool live = ip < S0M_IPX;
+        // DEAL: the lane's halo pixel by row pair (HaloDeal, cf_common.h): tx <= 17, and a lane without a pixel gathers patch pixel
+        // (0, 0), whose results are never activated or stored
+        if constexpr (DEAL) live = HaloDeal<3>::pixel(wave, t, pl, ty, tx);
+        else tx = tx < S0_IW ? tx : S0_IW - 1;
         const int y = oy0 - 1 + ty, x = ox0 - 1 + tx;
         // a halo pixel outside the map is the depthwise conv's zero padding: zero operand row -> swish(0) = 0
-        const bool inmap = decltype(inside)::value || (ip < S0M_IPX && (unsigned)y < (unsigned)Ho && (unsigned)x < (unsigned)Wo);
+        const bool inmap = decltype(inside)::value || (live && (unsigned)y < (unsigned)Ho && (unsigned)x < (unsigned)Wo);
         // eight aligned dword reads per lane, already in operand order (see stem0px_pack): no packing ops
         const char* xp = reinterpret_cast<const char*>(Xs) + ((2 * ty) * S0P_PROW + (2 * tx) * 3 + 2) * 2;
 #pragma unroll
@@ -872,6 +882,7 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
         for (int c = 0; c < 2; ++c)
             a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mfma_bf16x8, xg[t][c]),
                                                         __builtin_bit_cast(mfma_bf16x8, ws[c]), a, 0, 0, 0);
+        if constexpr (DEAL) { halo_deal_store<3, S0M_CP>(E, wave, t, h, pl, a); continue; }
         // D rows (r & 3) + 8 (r >> 2) + 4 h: register quad tq = halo quad ib * 8 + 2 tq + h -> one 8-byte cell of lane channel pl
         char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)S0M_CP + pl * 8;
 #pragma unroll
@@ -926,12 +937,19 @@ hipError_t launch_stem0(hipStream_t s, int dtype, const Stem0Params& p) {
         dim3 grid((Wo + S0_TOW - 1) / S0_TOW, (Ho + S0_TOH - 1) / S0_TOH, p.B), blk(S0P_NT);
         set_kernel_tag("void cf::stem0_mx_kernel<%d>(cf::Stem0Params)", p.in_format);
         // MODE 1: 32-bit byte offsets into the image, below 2 GiB (the offset of a row above the first image wraps far past it)
-        static const bool fast_on = cf_ab_int("CF_FRONT_MODE", 1) != 0;        // experiments build: 0 keeps the general kernel
-        const bool small = fast_on && (size_t)p.B * p.H * p.W * 3 < ((size_t)1 << 31);
+        // Bit 1 (MODE 3; MODE 2 for float input, whose staging has no bit 0): the expand deal by row pair, which lives in LDS and
+        // registers alone and has no precondition.  Experiments build: CF_FRONT_MODE=0 keeps the general kernels, 2 what ran before that deal
+        static const int front = cf_ab_int("CF_FRONT_MODE", 1);
+        const bool small = front != 0 && (size_t)p.B * p.H * p.W * 3 < ((size_t)1 << 31);
         if (p.in_format == CF_IN_U8_HWC_BGR) {
-            if (small) hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_U8_HWC_BGR, 1>), grid, blk, 0, s, p);
+#ifdef CF_EXPERIMENTS
+            if (small && front == 2) hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_U8_HWC_BGR, 1>), grid, blk, 0, s, p);
+            else
+#endif
+            if (small) hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_U8_HWC_BGR, 3>), grid, blk, 0, s, p);
             else hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_U8_HWC_BGR>), grid, blk, 0, s, p);
-        } else hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_F32_NCHW>), grid, blk, 0, s, p);
+        } else if (front != 0 && front != 2) hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_F32_NCHW, 2>), grid, blk, 0, s, p);
+        else hipLaunchKernelGGL((stem0_mx_kernel<CF_IN_F32_NCHW>), grid, blk, 0, s, p);
         return hipGetLastError();
     }
     if (p.kind & STEM0_PX) {

@@ -10,7 +10,8 @@
 //   canvas_b[dy : dy + rh, dx : dx + rw] = resize(bgr(frame_b), (rh, rw)),   every other pixel = fill
 // with bgr() the fixed-point BT.601 conversion of cf_yuvmath.h (the identity for BGR frames) and resize the fixed-point INTER_LINEAR of
 // cf_cvresize.h from (h, w) to (rh, rw): "resize, then pad".  rw == w and rh == h give the coefficients 2048 / 0: the source bytes.
-// A lane owns four adjacent CANVAS columns -- each of them content or padding on its own, dx and dx + rw are no multiples of 4 -- whose
+// fit_frames_kernel<SRC, VF, ROT> runs the padded lane of cf_cutpx.h on this one geometry (ROT 2: the rot 180 of cf_rot.hip, mirrored
+// taps): a lane owns four adjacent CANVAS columns -- each of them content or padding on its own, dx and dx + rw are no multiples of 4 -- whose
 // taps and coefficients are computed once and serve kFitRows canvas rows, each row going out as three dword stores (W % 4 == 0),
 // lane-contiguous.  Rows wholly in the padding, and lanes whose four columns are, are written as fill without touching the source; a
 // padding column beside content computes the edge column's taps and drops them.  The taps are byte loads; every tap lies inside the
@@ -21,111 +22,48 @@
 //     kept iff dx <= cx < dx + rw and dy <= cy < dy + rh;
 //   * else X = (float)(((double)x - (double)dx) * ((double)w / (double)rw)), Y likewise with dy and h / rh, for the four corners and the
 //     ten landmark values (float64 in this order, no contraction: the file is built with -ffp-contract=off); the score is copied.
-// The compaction is a prefix sum, never an atomic: the order is the decode's.  Behind a rotated forward (cf_rot.hip) the same kernel maps
+// The compaction (compact_pos, cf_collect.h) is a prefix sum, never an atomic: the order is the decode's.  Behind a rotated forward (cf_rot.hip) the same kernel maps
 // through the turn as well: unfit_rows_kernel<ROT>, whose ROT == 0 instance is the map above.
 #include "cf_common.h"
 #include "cf_kernels.h"
-#include "cf_cvresize.h"
-#include "cf_yuvmath.h"
-#include "cf_fitpx.h"
+#include "cf_cutpx.h"
+#include "cf_collect.h"
 #include <string>
 
 namespace cf {
 namespace {
 
-constexpr int kFitFrames = 64;                       // frames per launch: 3 x 64 pointers = 1.5 KB of kernel arguments
 // canvas rows per lane (one set of column coefficients).  The cutter's 8 left 16 frames of 1080p with 3 waves per SIMD, 44 % of them
 // storing fill only: 35 / 55 us (NV12 / BGR) against 23 / 32 us with 4; 2 and 1 measured the same as 4 (profiles/fit.md)
 constexpr int kFitRows = 4;
 using FitPtrs = FramePtrs<kFitFrames>;
 
-// SRC: 0 = BGR rows, 1 = one interleaved chroma plane (NV12 / NV21), 2 = two chroma planes (I420; YV12 on a swapped table);
-// VF: V first in the interleaved pairs (NV21).  One source pixel -> B | G << 8 | R << 16
-template <int SRC, bool VF>
-__device__ __forceinline__ uint32_t fit_tap(const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, int pitch0, int pitch1, int y, int x) {
-    if constexpr (SRC == 0) {
-        const uint8_t* q = p0 + (size_t)y * pitch0 + 3 * x;
-        return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
-    } else {
-        return yuv_px(p0[(size_t)y * pitch0 + x], chroma_at<SRC == 1, VF>(p1, p2, pitch1, y >> 1, x >> 1));
-    }
-}
-
-// (pack_bgr and fit_store: cf_fitpx.h, shared with cf_rot.hip)
-template <int SRC, bool VF>
+// The padded lane of cf_cutpx.h on one geometry: the whole upright view is the source, g its content.  ROT: 0 = as stored, 2 = rot 180,
+// the same lane layout on mirrored taps (adjacent canvas columns are still adjacent stored columns; hu = h, wu = w).
+template <int SRC, bool VF, int ROT>
 __global__ void __launch_bounds__(256) fit_frames_kernel(FitPtrs tab, uint8_t* dst, cf_fit_geom g, uint32_t fill, int h, int w, int pitch0,
                                                          int pitch1, int H, int W) {
     const int f = blockIdx.y;
     const int gw = W >> 2, ng = (H + kFitRows - 1) / kFitRows;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= ng * gw) return;
-    const int grp = i / gw, X0 = (i - grp * gw) << 2;
-    uint8_t* out = dst + ((size_t)f * H * W + X0) * 3;
-    const int Y0 = grp * kFitRows, Yend = min(H, Y0 + kFitRows);
-    const uint32_t pad[4] = {fill, fill, fill, fill};
-    bool in[4];
-    int x0[4], x1[4], a0[4], a1[4];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int x = X0 + k - g.dx;
-        in[k] = x >= 0 && x < g.rw;
-        cv_linear_coeffs(min(max(x, 0), g.rw - 1), w, g.rw, true, x0[k], x1[k], a0[k], a1[k]);      // a padding column beside content: the edge's taps, not used
-        any = any || in[k];
-    }
-    if (!any || Yend <= g.dy || Y0 >= g.dy + g.rh) {     // the lane's columns, or all of its rows, are padding: the source is not touched
-        for (int Y = Y0; Y < Yend; ++Y) fit_store(out + (size_t)Y * W * 3, pad);
-        return;
-    }
-    const uint8_t* p0 = tab.p0[f];
-    const uint8_t* p1 = tab.p1[f];
-    const uint8_t* p2 = tab.p2[f];
-    for (int Y = Y0; Y < Yend; ++Y) {
-        const int y = Y - g.dy;
-        if (y < 0 || y >= g.rh) { fit_store(out + (size_t)Y * W * 3, pad); continue; }
-        int y0, y1, b0, b1;
-        cv_linear_coeffs(y, h, g.rh, false, y0, y1, b0, b1);
-        uint32_t p[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t t00 = fit_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x0[k]);
-            const uint32_t t01 = fit_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x1[k]);
-            const uint32_t t10 = fit_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x0[k]);
-            const uint32_t t11 = fit_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x1[k]);
-            uint32_t ch[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int s = 8 * c;
-                const int h0 = (int)((t00 >> s) & 255) * a0[k] + (int)((t01 >> s) & 255) * a1[k];
-                const int h1 = (int)((t10 >> s) & 255) * a0[k] + (int)((t11 >> s) & 255) * a1[k];
-                ch[c] = (uint32_t)cv_linear_vpass(b0, b1, h0, h1);
-            }
-            p[k] = in[k] ? pack_bgr(ch[0], ch[1], ch[2]) : fill;
-        }
-        fit_store(out + (size_t)Y * W * 3, p);
-    }
+    const int grp = i / gw, X0 = (i - grp * gw) << 2, Y0 = grp * kFitRows;
+    padded_lane<SRC, VF, ROT>(cf_view{0, 0, w, h, g.dx, g.dy, g.rw, g.rh}, SrcPlanes{tab.p0[f], tab.p1[f], tab.p2[f], pitch0, pitch1, h, w},
+                              dst + (size_t)f * H * W * 3, W, X0, Y0, min(H, Y0 + kFitRows), fill);
 }
 
-// One workgroup per image walks its rows in order, 1024 at a time: keep flag, ballot, the 16 wave counts through LDS, write at
-// base + prefix (as merge_collect_kernel).  ROT: the quarter turns of a rotated forward (cf_rot.hip has the statement); p.h x p.w is the
-// STORED frame, the content of the canvas its upright view of hu x wu.  ROT == 0 is the unfit above.
+// One workgroup per image walks its rows in order, 1024 at a time, and compacts the kept ones (compact_pos).  ROT: the quarter turns of a
+// rotated forward (cf_rot.hip has the statement); p.h x p.w is the STORED frame, the content of the canvas its upright view of hu x wu.
+// ROT == 0 is the unfit above.  (The upright point has no source offset to add: a sum with 0.0 would turn a -0.0 into +0.0.)
 template <int ROT>
 __global__ void __launch_bounds__(1024) unfit_rows_kernel(UnfitParams p) {
-    __shared__ uint32_t wave_cnt[16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int count = p.counts[b], n = min(max(count, 0), p.rows);
     const float xlo = (float)p.g.dx, xhi = (float)(p.g.dx + p.g.rw), ylo = (float)p.g.dy, yhi = (float)(p.g.dy + p.g.rh);
     const int hu = (ROT & 1) ? p.w : p.h, wu = (ROT & 1) ? p.h : p.w;
     const double sx = (double)wu / (double)p.g.rw, sy = (double)hu / (double)p.g.rh;
     const double ox = (double)p.g.dx, oy = (double)p.g.dy;
-    // a point of the canvas -> the stored frame: the upright view's pixel first, then the index map of the turn; the difference is
-    // taken in float64 and rounded once
-    auto turn = [&](float x, float y, float& X, float& Y) {
-        const double ux = ((double)x - ox) * sx, uy = ((double)y - oy) * sy;
-        if constexpr (ROT == 1) { X = (float)uy; Y = (float)((double)(p.h - 1) - ux); }
-        else if constexpr (ROT == 2) { X = (float)((double)(p.w - 1) - ux); Y = (float)((double)(p.h - 1) - uy); }
-        else { X = (float)((double)(p.w - 1) - uy); Y = (float)ux; }
-    };
+    auto map = [&](float x, float y, float& X, float& Y) { turn_point<ROT>(((double)x - ox) * sx, ((double)y - oy) * sy, p.h, p.w, X, Y); };
     uint32_t base = 0;
     for (int j0 = 0; j0 < n; j0 += 1024) {               // (n is uniform over the workgroup: so is the trip count)
         const int row = j0 + tid;
@@ -139,41 +77,17 @@ __global__ void __launch_bounds__(1024) unfit_rows_kernel(UnfitParams p) {
             const float cx = (c[0] + c[2]) * 0.5f, cy = (c[1] + c[3]) * 0.5f;
             if (!(cx >= xlo && cx < xhi && cy >= ylo && cy < yhi)) keep = false;
         }
-        const unsigned long long bal = __ballot(keep);
-        __syncthreads();                                                  // the counts of the round before have been read
-        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = 0, total = 0;
-        for (int w2 = 0; w2 < 16; ++w2) { if (w2 < wave) off += wave_cnt[w2]; total += wave_cnt[w2]; }
-        const uint32_t pos = base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        const uint32_t pos = compact_pos(keep, base);
         if (keep && pos < (uint32_t)p.max_out) {
             const size_t d = (size_t)b * p.max_out + pos;
             float o[4];
-            if constexpr (ROT == 0) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = (float)(((double)c[k] - ((k & 1) ? oy : ox)) * ((k & 1) ? sy : sx));
-            } else if constexpr (ROT == 2) {             // the box is an assignment of mapped corners, never a min / max
-                turn(c[2], c[3], o[0], o[1]); turn(c[0], c[1], o[2], o[3]);
-            } else if constexpr (ROT == 1) {
-                turn(c[2], c[1], o[0], o[1]); turn(c[0], c[3], o[2], o[3]);
-            } else {
-                turn(c[0], c[3], o[0], o[1]); turn(c[2], c[1], o[2], o[3]);
-            }
+            turn_box<ROT>(c, map, o);
             *reinterpret_cast<float4*>(p.corners + d * 4) = make_float4(o[0], o[1], o[2], o[3]);
             float* dd = p.dets + d * 5;
             dd[0] = o[0]; dd[1] = o[1]; dd[2] = o[2]; dd[3] = o[3];
             dd[4] = p.scores[src * p.score_stride];
-            const float* l = p.lms_net + src * 10;
-            float* dl = p.lms + d * 10;
-            if constexpr (ROT == 0) {
-#pragma unroll
-                for (int k = 0; k < 10; ++k) dl[k] = (float)(((double)l[k] - ((k & 1) ? oy : ox)) * ((k & 1) ? sy : sx));
-            } else {
-#pragma unroll
-                for (int k = 0; k < 5; ++k) turn(l[2 * k], l[2 * k + 1], dl[2 * k], dl[2 * k + 1]);      // point by point, order kept
-            }
+            turn_landmarks(p.lms_net + src * 10, map, p.lms + d * 10);
         }
-        base += total;
     }
     if (tid == 0) { p.out_counts[b] = (int)base; p.flags[b] = count > p.rows ? 1 : 0; }
 }
@@ -206,11 +120,11 @@ const char* fit_check(std::string& why, const cf_fit_opts* o, int format, int B,
     return nullptr;
 }
 
-// planes: B x {p0, p1, p2} device addresses (HOST table); the caller has run fit_check and fit_geometry
-hipError_t launch_fit_frames(hipStream_t s, int format, const void* const* planes, int B, int h, int w, int pitch0, int pitch1, const cf_fit_geom& g,
-                             const uint8_t* fill, uint8_t* dst, int H, int W) {
-    if (format < CF_YUV_NV12 || format > CF_FRAME_BGR || !planes || !dst || !fill || B < 1 || H < 1 || W < 4 || (W & 3) || h < 1 || w < 1 ||
-        g.rw < 1 || g.rh < 1 || g.dx < 0 || g.dy < 0 || g.dx > W - g.rw || g.dy > H - g.rh)
+// planes: B x {p0, p1, p2} device addresses (HOST table); the caller has run fit_check / rot_check and fit_geometry / rot_geometry
+hipError_t launch_fit_frames(hipStream_t s, int rot, int format, const void* const* planes, int B, int h, int w, int pitch0, int pitch1,
+                             const cf_fit_geom& g, const uint8_t* fill, uint8_t* dst, int H, int W) {
+    if ((rot != 0 && rot != 90 && rot != 180 && rot != 270) || format < CF_YUV_NV12 || format > CF_FRAME_BGR || !planes || !dst || !fill || B < 1 || H < 1 ||
+        W < 4 || (W & 3) || h < 1 || w < 1 || g.rw < 1 || g.rh < 1 || g.dx < 0 || g.dy < 0 || g.dx > W - g.rw || g.dy > H - g.rh)
         return hipErrorInvalidValue;
     const uint32_t fv = (uint32_t)fill[0] | ((uint32_t)fill[1] << 8) | ((uint32_t)fill[2] << 16);
     const long long n = (long long)((H + kFitRows - 1) / kFitRows) * (W >> 2);
@@ -219,12 +133,11 @@ hipError_t launch_fit_frames(hipStream_t s, int format, const void* const* plane
         const FitPtrs tab = frame_ptrs<kFitFrames>(planes, format, f0, nb, true);      // YV12: the I420 kernel on swapped planes (as launch_cut_tiles)
         const dim3 grid((unsigned)((n + 255) / 256), (unsigned)nb);
         uint8_t* out = dst + (size_t)f0 * H * W * 3;
-        switch (format) {
-            case CF_YUV_NV12: hipLaunchKernelGGL((fit_frames_kernel<1, false>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W); break;
-            case CF_YUV_NV21: hipLaunchKernelGGL((fit_frames_kernel<1, true>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W); break;
-            case CF_YUV_I420: case CF_YUV_YV12: hipLaunchKernelGGL((fit_frames_kernel<2, false>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W); break;
-            default: hipLaunchKernelGGL((fit_frames_kernel<0, false>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W); break;
-        }
+        if (rot == 90 || rot == 270) launch_rot_quarter(s, rot, format, tab, nb, out, g, fv, h, w, pitch0, pitch1, H, W);
+        else with_format(format, [&](auto SRC, auto VF) {
+            if (rot == 0) hipLaunchKernelGGL((fit_frames_kernel<SRC, VF, 0>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W);
+            else hipLaunchKernelGGL((fit_frames_kernel<SRC, VF, 2>), grid, dim3(256), 0, s, tab, out, g, fv, h, w, pitch0, pitch1, H, W);
+        });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

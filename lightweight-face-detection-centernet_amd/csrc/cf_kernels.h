@@ -454,30 +454,6 @@ int tile_grid(int h, int w, int tile_h, int tile_w, int overlap, int with_full, 
 const char* tiles_check(std::string& why, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_tile_rect* rects, int T, int H, int W);
 hipError_t launch_cut_tiles(hipStream_t s, int format, const void* const* planes, int Bf, int pitch0, int pitch1, const cf_tile_rect* rects,
                             int T, uint8_t* dst, int H, int W);
-// The merge of the per-tile results of a threshold decode over Bf * T images of H x W: rows i < min(counts[img], rows) of dets_net
-// [Bf * T][rows][4], scores[(img * rows + i) * score_stride], lms_net [Bf * T][rows][10] are filtered (edge rule, non-finite corners),
-// mapped into the h x w frame and collected per frame in (tile, row) order; then rank / mask / sweep with `metric` and `thresh`.
-struct MergeParams {
-    const cf_tile_rect* rects;   // [T], device
-    int T, Bf, h, w, H, W;
-    const float* dets_net; const float* scores; int score_stride; const float* lms_net; const int* counts; int rows;
-    int metric; float thresh, edge;
-    // workspace (device), cap = T * rows candidates per frame
-    float* cand;          // [Bf][cap][16]
-    int* cand_count;      // [Bf]
-    int* order;           // [Bf][cap]
-    unsigned long long* mask;    // [Bf][cap][ceil(cap / 64)]: merge_mask_bytes
-    // outputs (device), frame pixels
-    int max_out;
-    float* dets;          // [Bf][max_out][5]
-    float* lms;           // [Bf][max_out][10]
-    float* corners;       // [Bf][max_out][4]: the box rows FaceList::boxes takes with (H, W) = (h, w)
-    int* out_counts;      // [Bf], may exceed max_out
-    int* flags;           // [Bf]: bit 0 = some tile of the frame had counts > rows
-};
-size_t merge_mask_bytes(int Bf, int T, int rows);
-constexpr size_t kMergeMaskLimit = (size_t)256 << 20;      // refused with CF_ENOMEM above this, before any launch
-hipError_t launch_merge_tiles(hipStream_t s, const MergeParams& p);
 
 // Aspect-preserving input (cf_fit.hip; the statement is that file's header).  fit_geometry: the placement of an h x w frame in an H x W
 // canvas (host only; CF_EINVAL for an unknown anchor / upscale, a null g or a size below 1).  fit_check: nullptr, or what is wrong with the
@@ -486,8 +462,13 @@ hipError_t launch_merge_tiles(hipStream_t s, const MergeParams& p);
 // (cf_frame.h; read only).
 int fit_geometry(int anchor, int upscale, int h, int w, int H, int W, cf_fit_geom* g);
 const char* fit_check(std::string& why, const cf_fit_opts* o, int format, int B, int h, int w, int pitch0, int pitch1, int H, int W);
-hipError_t launch_fit_frames(hipStream_t s, int format, const void* const* planes, int B, int h, int w, int pitch0, int pitch1, const cf_fit_geom& g,
-                             const uint8_t* fill, uint8_t* dst, int H, int W);
+// rot: the clockwise turn (0, 90, 180, 270) that makes the stored h x w frames upright; g then places the UPRIGHT view (rot_geometry).
+// 90 and 270 go to the quarter-turn kernel of cf_rot.hip (launch_rot_quarter: one launch over nb <= kFitFrames checked frames).
+constexpr int kFitFrames = 64;                       // frames per launch: 3 x 64 pointers = 1.5 KB of kernel arguments
+hipError_t launch_fit_frames(hipStream_t s, int rot, int format, const void* const* planes, int B, int h, int w, int pitch0, int pitch1,
+                             const cf_fit_geom& g, const uint8_t* fill, uint8_t* dst, int H, int W);
+void launch_rot_quarter(hipStream_t s, int rot, int format, const FramePtrs<kFitFrames>& tab, int nb, uint8_t* dst, const cf_fit_geom& g, uint32_t fill,
+                        int h, int w, int pitch0, int pitch1, int H, int W);
 // The rows of a threshold decode over B fitted images mapped back into the h x w frames: rows i < min(counts[b], rows) of dets_net
 // [B][rows][4], scores[(b * rows + i) * score_stride], lms_net [B][rows][10] are filtered (non-finite corners, centre outside the
 // content), mapped and compacted per image in order.
@@ -506,12 +487,10 @@ hipError_t launch_unfit_rows(hipStream_t s, const UnfitParams& p);
 
 // Rotated sources (cf_rot.hip; the statement is in include/centerface_hip.h).  rot_geometry: the placement of the UPRIGHT view of an
 // h x w frame (host only; o has passed rot_check).  rot_check: nullptr, or what is wrong with the turn, the options and the frames.
-// launch_rot_frames: the fit of the upright views, dst [B][H][W][3] as launch_fit_frames; rot == 0 IS launch_fit_frames.
+// The fit of the upright views is launch_fit_frames with the turn.
 // launch_unrot_rows (cf_fit.hip): the unfit behind it, p.g from rot_geometry, p.h x p.w the stored frame; rot == 0 is launch_unfit_rows.
 int rot_geometry(const cf_rot_opts* o, int h, int w, int H, int W, cf_fit_geom* g);
 const char* rot_check(std::string& why, const cf_rot_opts* o, int format, int B, int h, int w, int pitch0, int pitch1, int H, int W);
-hipError_t launch_rot_frames(hipStream_t s, int rot, int format, const void* const* planes, int B, int h, int w, int pitch0, int pitch1,
-                             const cf_fit_geom& g, const uint8_t* fill, uint8_t* dst, int H, int W);
 hipError_t launch_unrot_rows(hipStream_t s, const UnfitParams& p, int rot);
 
 // Multi-scale views (cf_views.hip; the statement is in include/centerface_hip.h).  view_layout: the views of cf_view_layout (host only).
@@ -524,19 +503,6 @@ const char* views_table_check(std::string& why, int h, int w, const cf_view* vie
 const char* views_check(std::string& why, int format, int Bf, int h, int w, int pitch0, int pitch1, const cf_view* views, int V, int H, int W);
 hipError_t launch_cut_views(hipStream_t s, int format, const void* const* planes, int Bf, int pitch0, int pitch1, const cf_view* views, int V,
                             const uint8_t* fill, uint8_t* dst, int H, int W);
-// The merge of the per-view results of a threshold decode over Bf * V images: MergeParams with a view table in the place of the
-// rectangles (the canvas size is in the views' content rectangles); workspace sizes as merge_mask_bytes(Bf, V, rows) and cap = V * rows.
-struct ViewMergeParams {
-    const cf_view* views;        // [V], device
-    int V, Bf, h, w;
-    const float* dets_net; const float* scores; int score_stride; const float* lms_net; const int* counts; int rows;
-    int metric; float thresh, edge;
-    float* cand; int* cand_count; int* order; unsigned long long* mask;
-    int max_out;
-    float* dets; float* lms; float* corners; int* out_counts;
-    int* flags;           // [Bf]: bit 0 = some view image of the frame had counts > rows
-};
-hipError_t launch_merge_views(hipStream_t s, const ViewMergeParams& p);
 
 // Packed views (cf_views.hip; the statement is in include/centerface_hip.h).  pack_views: the shelf packer of cf_pack_views (host only;
 // the arguments have been checked).  pack_check: nullptr, or what is wrong with P placements of Bf frames of h x w in N canvases of
@@ -554,20 +520,52 @@ inline PackDev pack_dev(const PackHost& t, const void* dev) {
     return PackDev{(const cf_place*)b, (const int*)(b + t.off_cv), (const int*)(b + t.off_fr), (const int*)(b + t.off_idx), (const uint8_t* const*)(b + t.off_planes)};
 }
 // dst [N][H][W][3] uint8 BGR, every byte written once by one launch; the caller has run views_check's frame part and pack_check
-hipError_t launch_cut_packed(hipStream_t s, int format, const PackDev& t, int N, int pitch0, int pitch1, const uint8_t* fill, uint8_t* dst, int H, int W);
-// The merge of the per-canvas results of a threshold decode over N canvases: ViewMergeParams with the placements in the place of the
-// views (p.views unused, p.V = PackHost::most: cap = most * rows, workspace sizes as merge_mask_bytes(Bf, most, rows)).
-hipError_t launch_merge_packed(hipStream_t s, const ViewMergeParams& p, const PackDev& t);
+// rot: the clockwise turn (0, 90, 180, 270) that makes the stored h x w frames upright (the placements' sources are then rectangles of
+// the upright view, cf_views_rot.hip)
+hipError_t launch_cut_packed(hipStream_t s, int rot, int format, const PackDev& t, int N, int h, int w, int pitch0, int pitch1, const uint8_t* fill,
+                             uint8_t* dst, int H, int W);
 
 // Rotated sources through packed views (cf_views_rot.hip; the statement is in include/centerface_hip.h).  rot: the clockwise turn (0, 90,
 // 180, 270) that makes the stored h x w frames upright; the placements' sources are rectangles of the upright view.  pack_rot_check:
 // nullptr, or what is wrong with the turn or with the placements (pack_check against the upright view's size; host only).
-// launch_cut_packed_rot / launch_merge_packed_rot: launch_cut_packed / launch_merge_packed through the turn, p.h x p.w the STORED frame,
-// the rows in its pixels; rot == 0 IS those two.
+// launch_cut_packed_quarter: launch_cut_packed's rot 90 / 270 (the arguments have been checked).
 const char* pack_rot_check(std::string& why, int rot, int h, int w, const cf_place* places, int P, int N, int Bf, int H, int W);
-hipError_t launch_cut_packed_rot(hipStream_t s, int rot, int format, const PackDev& t, int N, int h, int w, int pitch0, int pitch1, const uint8_t* fill,
-                                 uint8_t* dst, int H, int W);
-hipError_t launch_merge_packed_rot(hipStream_t s, int rot, const ViewMergeParams& p, const PackDev& t);
+void launch_cut_packed_quarter(hipStream_t s, int rot, int format, const PackDev& t, int N, uint8_t* dst, uint32_t fill, int h, int w, int pitch0, int pitch1,
+                               int H, int W);
+
+// The merge of the rows of a threshold decode over the images of a tiled, views or packed forward (cf_tiles.hip, cf_collect.h): rows
+// i < min(counts[img], rows) of dets_net [.][rows][4], scores[(img * rows + i) * score_stride], lms_net [.][rows][10] are filtered
+// (non-finite corners; the edge rule; behind views and placements the centre rule), mapped into the STORED h x w frame and collected per
+// frame in (source, row) order; then rank / mask / sweep with `metric` and `thresh`.  kind names the sources of a frame:
+//   MERGE_TILES   rects [V]: image f * V + t is rectangle t stretched over the H x W canvas
+//   MERGE_VIEWS   views [V]: image f * V + v is view v
+//   MERGE_PLACED  pack: the placements of the frame, image = the placement's canvas; V = PackHost::most; rot = the turn (0, 90, 180, 270)
+//                 that makes the stored frames upright, the placements' sources being rectangles of the upright view
+enum { MERGE_TILES = 0, MERGE_VIEWS = 1, MERGE_PLACED = 2 };
+struct MergeParams {
+    int kind;
+    const cf_tile_rect* rects;   // device
+    const cf_view* views;        // device
+    PackDev pack;
+    int V, Bf, h, w, H, W, rot;  // (H, W: MERGE_TILES only; rot: MERGE_PLACED only, else 0)
+    const float* dets_net; const float* scores; int score_stride; const float* lms_net; const int* counts; int rows;
+    int metric; float thresh, edge;
+    // workspace (device), cap = V * rows candidates per frame
+    float* cand;          // [Bf][cap][16]
+    int* cand_count;      // [Bf]
+    int* order;           // [Bf][cap]
+    unsigned long long* mask;    // [Bf][cap][ceil(cap / 64)]: merge_mask_bytes
+    // outputs (device), frame pixels
+    int max_out;
+    float* dets;          // [Bf][max_out][5]
+    float* lms;           // [Bf][max_out][10]
+    float* corners;       // [Bf][max_out][4]: the box rows FaceList::boxes takes with (H, W) = (h, w)
+    int* out_counts;      // [Bf], may exceed max_out
+    int* flags;           // [Bf]: bit 0 = some image of the frame had counts > rows
+};
+size_t merge_mask_bytes(int Bf, int V, int rows);
+constexpr size_t kMergeMaskLimit = (size_t)256 << 20;      // refused with CF_ENOMEM above this, before any launch
+hipError_t launch_merge(hipStream_t s, const MergeParams& p);
 
 // Flip test (cf_flip.hip; the statement is in include/centerface_hip.h).  mirror_check: nullptr, or what is wrong with the format and sizes
 // of a batch to mirror (the text lives in `why`; host only).  launch_mirror_batch: dst holds 2B network inputs of in_format (uint8

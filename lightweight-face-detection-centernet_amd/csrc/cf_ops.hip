@@ -960,39 +960,57 @@ int cf_op_cut_tiles(int device, int format, const cf_yuv_planes* host_frames, in
     return sc.result("cf_op_cut_tiles");
 }
 
-int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* rects, int T, int Bf, int h, int w, int H, int W,
-                      const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
-                      float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
-    std::string why;
-    const char* bad = nullptr;
-    if (!o || !dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags) bad = "null argument";
-    else if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) bad = "unknown metric (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)";
-    else if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) bad = "thresh and edge must be finite and not negative";
-    else if (rows < 1 || max_out < 1 || H < 1 || W < 1) bad = "rows, max_out, H and W must be at least 1";
-    else bad = tiles_check(why, CF_FRAME_BGR, Bf, h, w, 3 * w, 0, rects, T, H, 4);      // the geometry part: frame and rectangles
-    if (bad) return fail("cf_op_merge_tiles", bad);
-    if ((long long)T * rows > (1 << 24) || merge_mask_bytes(Bf, T, rows) > kMergeMaskLimit) {
-        g_op_error = "cf_op_merge_tiles: the suppression bits of Bf x (T * rows) candidates exceed 256 MiB";
+// The merges on host tables.  merge_opts_check: the argument checks the three families share, in their order (nullptr: go on with the
+// geometry).  op_merge: the out-of-memory guard, the staging and the launch; p carries the kind, V, Bf, the sizes and the turn, table the
+// kind's host table (rectangles, views, or the blob of `pack`), n_img = the number of decoded images, what = the guard's words for V.
+static const char* merge_opts_check(const cf_merge_opts* o, const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows,
+                                    int max_out, int H, int W, const float* dets, const float* lms, const int32_t* out_counts, const int32_t* flags) {
+    if (!o || !dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags) return "null argument";
+    if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) return "unknown metric (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)";
+    if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) return "thresh and edge must be finite and not negative";
+    if (rows < 1 || max_out < 1 || H < 1 || W < 1) return "rows, max_out, H and W must be at least 1";
+    return nullptr;
+}
+static int op_merge(const char* who, int device, MergeParams p, const void* table, size_t table_bytes, const PackHost* pack, size_t n_img, const char* what, const cf_merge_opts* o,
+                    const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out, float* dets, float* lms,
+                    int32_t* out_counts, int32_t* flags) {
+    const int Bf = p.Bf, V = p.V;
+    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit) {
+        g_op_error = std::string(who) + ": the suppression bits of Bf x (" + what + " * rows) candidates exceed 256 MiB";
         return CF_ENOMEM;
     }
     Scope sc(device);
-    const size_t n = (size_t)Bf * T * rows, cap = (size_t)T * rows, mo = (size_t)Bf * max_out;
-    MergeParams p{};
-    p.rects = sc.in(rects, T);
-    p.T = T; p.Bf = Bf; p.h = h; p.w = w; p.H = H; p.W = W;
+    const size_t n = n_img * rows, cap = (size_t)V * rows, mo = (size_t)Bf * max_out;
+    const unsigned char* tab = sc.in((const unsigned char*)table, table_bytes);
+    if (p.kind == MERGE_TILES) p.rects = (const cf_tile_rect*)tab;
+    else if (p.kind == MERGE_VIEWS) p.views = (const cf_view*)tab;
+    else p.pack = pack_dev(*pack, tab);
     p.dets_net = sc.in(dets_net, n * 4);
     p.scores = sc.in(scores, n); p.score_stride = 1;
     p.lms_net = sc.in(lms_net, n * 10);
-    p.counts = sc.in(counts, (size_t)Bf * T); p.rows = rows;
+    p.counts = sc.in(counts, n_img); p.rows = rows;
     p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
     p.cand = sc.make<float>(Bf * cap * 16); p.cand_count = sc.make<int>(Bf);
-    p.order = sc.make<int>(Bf * cap); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, T, rows));
+    p.order = sc.make<int>(Bf * cap); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, V, rows));
     p.max_out = max_out;
     p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
     p.corners = sc.make<float>(mo * 4);
     p.out_counts = sc.out(out_counts, Bf); p.flags = sc.out(flags, Bf);
-    sc.run([&] { return launch_merge_tiles(sc.s, p); });
-    return sc.result("cf_op_merge_tiles");
+    sc.run([&] { return launch_merge(sc.s, p); });
+    return sc.result(who);
+}
+
+int cf_op_merge_tiles(int device, const cf_merge_opts* o, const cf_tile_rect* rects, int T, int Bf, int h, int w, int H, int W,
+                      const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
+                      float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
+    std::string why;
+    const char* bad = merge_opts_check(o, dets_net, scores, lms_net, counts, rows, max_out, H, W, dets, lms, out_counts, flags);
+    if (!bad) bad = tiles_check(why, CF_FRAME_BGR, Bf, h, w, 3 * w, 0, rects, T, H, 4);      // the geometry part: frame and rectangles
+    if (bad) return fail("cf_op_merge_tiles", bad);
+    MergeParams p{};
+    p.kind = MERGE_TILES; p.V = T; p.Bf = Bf; p.h = h; p.w = w; p.H = H; p.W = W;
+    return op_merge("cf_op_merge_tiles", device, p, rects, (size_t)T * sizeof(cf_tile_rect), nullptr, (size_t)Bf * T, "T", o, dets_net, scores,
+                    lms_net, counts, rows, max_out, dets, lms, out_counts, flags);
 }
 
 int cf_view_layout(const cf_view_opts* o, int h, int w, int H, int W, cf_view* views, int cap, int* n) {
@@ -1023,36 +1041,14 @@ int cf_op_merge_views(int device, const cf_merge_opts* o, const cf_view* views, 
                       const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
                       float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
     std::string why;
-    const char* bad = nullptr;
-    if (!o || !dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags) bad = "null argument";
-    else if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) bad = "unknown metric (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)";
-    else if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) bad = "thresh and edge must be finite and not negative";
-    else if (rows < 1 || max_out < 1 || H < 1 || W < 1) bad = "rows, max_out, H and W must be at least 1";
-    else if (const char* geo = frame_geometry_check(FrameGeo{CF_FRAME_BGR, Bf, h, w, 3 * w, 0}, 2, true)) bad = geo;
-    else bad = views_table_check(why, h, w, views, V, H, W);
+    const char* bad = merge_opts_check(o, dets_net, scores, lms_net, counts, rows, max_out, H, W, dets, lms, out_counts, flags);
+    if (!bad) bad = frame_geometry_check(FrameGeo{CF_FRAME_BGR, Bf, h, w, 3 * w, 0}, 2, true);
+    if (!bad) bad = views_table_check(why, h, w, views, V, H, W);
     if (bad) return fail("cf_op_merge_views", bad);
-    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit) {
-        g_op_error = "cf_op_merge_views: the suppression bits of Bf x (V * rows) candidates exceed 256 MiB";
-        return CF_ENOMEM;
-    }
-    Scope sc(device);
-    const size_t n = (size_t)Bf * V * rows, cap = (size_t)V * rows, mo = (size_t)Bf * max_out;
-    ViewMergeParams p{};
-    p.views = sc.in(views, V);
-    p.V = V; p.Bf = Bf; p.h = h; p.w = w;
-    p.dets_net = sc.in(dets_net, n * 4);
-    p.scores = sc.in(scores, n); p.score_stride = 1;
-    p.lms_net = sc.in(lms_net, n * 10);
-    p.counts = sc.in(counts, (size_t)Bf * V); p.rows = rows;
-    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
-    p.cand = sc.make<float>(Bf * cap * 16); p.cand_count = sc.make<int>(Bf);
-    p.order = sc.make<int>(Bf * cap); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, V, rows));
-    p.max_out = max_out;
-    p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
-    p.corners = sc.make<float>(mo * 4);
-    p.out_counts = sc.out(out_counts, Bf); p.flags = sc.out(flags, Bf);
-    sc.run([&] { return launch_merge_views(sc.s, p); });
-    return sc.result("cf_op_merge_views");
+    MergeParams p{};
+    p.kind = MERGE_VIEWS; p.V = V; p.Bf = Bf; p.h = h; p.w = w; p.H = H; p.W = W;
+    return op_merge("cf_op_merge_views", device, p, views, (size_t)V * sizeof(cf_view), nullptr, (size_t)Bf * V, "V", o, dets_net, scores,
+                    lms_net, counts, rows, max_out, dets, lms, out_counts, flags);
 }
 
 int cf_pack_views(const cf_view* views, int V, int Bf, int H, int W, int gutter, cf_place* places, int cap, int* n_places, int* n_canvases) {
@@ -1099,7 +1095,7 @@ static int op_packed(const char* who, int device, int rot, int format, const cf_
     const PackHost t = pack_table(places, P, N, Bf, dev.data(), format);
     const unsigned char* blob = sc.in(t.blob.data(), t.blob.size());
     uint8_t* out = sc.out(canvases, (size_t)N * H * W * 3);
-    sc.run([&] { return launch_cut_packed_rot(sc.s, rot, format, pack_dev(t, blob), N, h, w, pitch0, pitch1, fill, out, H, W); });      // (rot 0: launch_cut_packed)
+    sc.run([&] { return launch_cut_packed(sc.s, rot, format, pack_dev(t, blob), N, h, w, pitch0, pitch1, fill, out, H, W); });
     return sc.result(who);
 }
 int cf_op_packed(int device, int format, const cf_yuv_planes* host_frames, int Bf, int h, int w, int pitch0, int pitch1, const cf_place* places,
@@ -1116,39 +1112,15 @@ static int op_merge_packed(const char* who, int device, int rot, const cf_merge_
                            int W, const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
                            float* dets, float* lms, int32_t* out_counts, int32_t* flags) {
     std::string why;
-    const char* bad = nullptr;
-    if (!o || !dets_net || !scores || !lms_net || !counts || !dets || !lms || !out_counts || !flags) bad = "null argument";
-    else if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) bad = "unknown metric (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)";
-    else if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge)) bad = "thresh and edge must be finite and not negative";
-    else if (rows < 1 || max_out < 1 || H < 1 || W < 1) bad = "rows, max_out, H and W must be at least 1";
-    else if (const char* geo = frame_geometry_check(FrameGeo{CF_FRAME_BGR, Bf, h, w, 3 * w, 0}, 2, true)) bad = geo;
-    else bad = pack_rot_check(why, rot, h, w, places, P, N, Bf, H, W);      // (rot 0: pack_check)
+    const char* bad = merge_opts_check(o, dets_net, scores, lms_net, counts, rows, max_out, H, W, dets, lms, out_counts, flags);
+    if (!bad) bad = frame_geometry_check(FrameGeo{CF_FRAME_BGR, Bf, h, w, 3 * w, 0}, 2, true);
+    if (!bad) bad = pack_rot_check(why, rot, h, w, places, P, N, Bf, H, W);      // (rot 0: pack_check)
     if (bad) return fail(who, bad);
     const PackHost t = pack_table(places, P, N, Bf, nullptr, CF_FRAME_BGR);
-    const int V = t.most;
-    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit) {
-        g_op_error = std::string(who) + ": the suppression bits of Bf x (most placements of a frame * rows) candidates exceed 256 MiB";
-        return CF_ENOMEM;
-    }
-    Scope sc(device);
-    const size_t n = (size_t)N * rows, cap = (size_t)V * rows, mo = (size_t)Bf * max_out;
-    const unsigned char* blob = sc.in(t.blob.data(), t.blob.size());
-    ViewMergeParams p{};
-    p.views = nullptr;
-    p.V = V; p.Bf = Bf; p.h = h; p.w = w;
-    p.dets_net = sc.in(dets_net, n * 4);
-    p.scores = sc.in(scores, n); p.score_stride = 1;
-    p.lms_net = sc.in(lms_net, n * 10);
-    p.counts = sc.in(counts, (size_t)N); p.rows = rows;
-    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
-    p.cand = sc.make<float>(Bf * cap * 16); p.cand_count = sc.make<int>(Bf);
-    p.order = sc.make<int>(Bf * cap); p.mask = (unsigned long long*)sc.alloc(merge_mask_bytes(Bf, V, rows));
-    p.max_out = max_out;
-    p.dets = sc.inout(dets, mo * 5); p.lms = sc.inout(lms, mo * 10);
-    p.corners = sc.make<float>(mo * 4);
-    p.out_counts = sc.out(out_counts, Bf); p.flags = sc.out(flags, Bf);
-    sc.run([&] { return launch_merge_packed_rot(sc.s, rot, p, pack_dev(t, blob)); });      // (rot 0: launch_merge_packed)
-    return sc.result(who);
+    MergeParams p{};
+    p.kind = MERGE_PLACED; p.V = t.most; p.Bf = Bf; p.h = h; p.w = w; p.H = H; p.W = W; p.rot = rot;
+    return op_merge(who, device, p, t.blob.data(), t.blob.size(), &t, (size_t)N,
+                    "most placements of a frame", o, dets_net, scores, lms_net, counts, rows, max_out, dets, lms, out_counts, flags);
 }
 int cf_op_merge_packed(int device, const cf_merge_opts* o, const cf_place* places, int P, int N, int Bf, int h, int w, int H, int W,
                        const float* dets_net, const float* scores, const float* lms_net, const int32_t* counts, int rows, int max_out,
@@ -1194,7 +1166,7 @@ int cf_op_fit(int device, const cf_fit_opts* o, int format, const cf_yuv_planes*
     Scope sc(device);
     const std::vector<const void*> dev = up_planes(sc, format, hp, B, h, pitch0, pitch1);
     uint8_t* out = sc.out(canvas, (size_t)B * H * W * 3);
-    sc.run([&] { return launch_fit_frames(sc.s, format, dev.data(), B, h, w, pitch0, pitch1, g, o->fill, out, H, W); });
+    sc.run([&] { return launch_fit_frames(sc.s, 0, format, dev.data(), B, h, w, pitch0, pitch1, g, o->fill, out, H, W); });
     return sc.result("cf_op_fit");
 }
 
@@ -1254,7 +1226,7 @@ int cf_op_rot(int device, const cf_rot_opts* o, int format, const cf_yuv_planes*
     Scope sc(device);
     const std::vector<const void*> dev = up_planes(sc, format, hp, B, h, pitch0, pitch1);
     uint8_t* out = sc.out(canvas, (size_t)B * H * W * 3);
-    sc.run([&] { return launch_rot_frames(sc.s, o->rot, format, dev.data(), B, h, w, pitch0, pitch1, g, o->fit.fill, out, H, W); });
+    sc.run([&] { return launch_fit_frames(sc.s, o->rot, format, dev.data(), B, h, w, pitch0, pitch1, g, o->fit.fill, out, H, W); });
     return sc.result("cf_op_rot");
 }
 

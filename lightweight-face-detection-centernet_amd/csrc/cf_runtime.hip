@@ -2069,40 +2069,45 @@ int cf_forward_tiles(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_
     return CF_OK;
 }
 
-// The merge of the last threshold decode's per-tile rows (cf_tiles.hip) on the stream that carried the decode: it reads the decode's
+// The merge of the last threshold decode's rows (launch_merge, cf_tiles.hip) on the stream that carried the decode: it reads the decode's
 // device-side counts, network-coordinate corners and landmarks and the score column of its dets (device memory, or the page-locked
-// host rows the sweep kernel wrote: device-visible either way).
-int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
-    if (!c) return CF_EINVAL;
-    if (!o) return c->fail(CF_EINVAL, "cf_merge_tiles: null options");
-    if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) return c->fail(CF_EINVAL, "cf_merge_tiles: unknown metric %d (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)", o->metric);
+// host rows the sweep kernel wrote: device-visible either way).  who: the entry point; rows_kind: the decode it needs; kind: MERGE_*,
+// whose sources and V the context remembers from the forward; noun: what V counts, for the out-of-memory message.
+static int merge_rows(cf_ctx* c, const char* who, RowsWanted rows_kind, int kind, const char* noun, const cf_merge_opts* o, int max_out, float* dets, float* lms,
+                      int32_t* counts, int32_t* flags, int out_on_device) {
+    if (!o) return c->fail(CF_EINVAL, "%s: null options", who);
+    if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) return c->fail(CF_EINVAL, "%s: unknown metric %d (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)", who, o->metric);
     if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge))
-        return c->fail(CF_EINVAL, "cf_merge_tiles: thresh and edge must be finite and not negative");
-    if (max_out < 1) return c->fail(CF_EINVAL, "cf_merge_tiles: max_out=%d must be at least 1", max_out);
+        return c->fail(CF_EINVAL, "%s: thresh and edge must be finite and not negative", who);
+    if (max_out < 1) return c->fail(CF_EINVAL, "%s: max_out=%d must be at least 1", who, max_out);
     RowSet in{};
-    if (int r = rows_for(c, "cf_merge_tiles", ROWS_OF_TILED_DECODE, in)) return r;
-    const int Bf = c->tl_Bf, T = c->tl_T, rows = in.stride;
-    if ((long long)T * rows > (1 << 24) || merge_mask_bytes(Bf, T, rows) > kMergeMaskLimit)
-        return c->fail(CF_ENOMEM, "cf_merge_tiles: %d frames x %d tiles x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
-                       Bf, T, rows, merge_mask_bytes(Bf, T, rows) / 1e6);
+    if (int r = rows_for(c, who, rows_kind, in)) return r;
+    const int Bf = c->tl_Bf, V = kind == MERGE_TILES ? c->tl_T : kind == MERGE_VIEWS ? c->vw_V : c->pk_tab.most, rows = in.stride;
+    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit)
+        return c->fail(CF_ENOMEM, "%s: %d frames x %d %s x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out", who, Bf, V,
+                       noun, rows, merge_mask_bytes(Bf, V, rows) / 1e6);
     HIPCHK(c, hipSetDevice(c->device));
     c->stage = ROWS_DECODED; c->fo.B = 0; c->lb.B = 0;    // the merged (and tracked, and followed) rows of an earlier call are gone from here on
-    const size_t cap = (size_t)T * rows, mo = (size_t)Bf * max_out, nb = (size_t)Bf * sizeof(int);
+    const size_t cap = (size_t)V * rows, mo = (size_t)Bf * max_out, nb = (size_t)Bf * sizeof(int);
     const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
     auto& ws = c->tl;
     const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
         {ws.cand, Bf * cap * 16 * sizeof(float), "candidates"}, {ws.cand_count, nb, "candidate counts"}, {ws.order, Bf * cap * sizeof(int), "sort order"},
-        {ws.mask, merge_mask_bytes(Bf, T, rows), "suppression bits"}, {ws.dets, nd, "merged dets"}, {ws.lms, nl, "merged landmarks"},
+        {ws.mask, merge_mask_bytes(Bf, V, rows), "suppression bits"}, {ws.dets, nd, "merged dets"}, {ws.lms, nl, "merged landmarks"},
         {ws.corners, mo * 4 * sizeof(float), "merged corners"}, {ws.counts, nb, "merged counts"}, {ws.flags, nb, "flags"}};
-    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_merge_tiles")) return r;
+    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, who)) return r;
     MergeParams p{};
-    p.rects = (const cf_tile_rect*)c->tl_rects_dev.p; p.T = T; p.Bf = Bf; p.h = c->tl_h; p.w = c->tl_w; p.H = in.H; p.W = in.W;
+    p.kind = kind;
+    if (kind == MERGE_TILES) p.rects = (const cf_tile_rect*)c->tl_rects_dev.p;
+    else if (kind == MERGE_VIEWS) p.views = (const cf_view*)c->vw_dev.p;
+    else { p.pack = pack_dev(c->pk_tab, c->pk_dev.p); p.rot = c->pk_rot; }
+    p.V = V; p.Bf = Bf; p.h = c->tl_h; p.w = c->tl_w; p.H = in.H; p.W = in.W;
     p.dets_net = in.corners; p.scores = in.dets + 4; p.score_stride = 5; p.lms_net = in.lms; p.counts = in.counts; p.rows = rows;
     p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
     p.cand = (float*)ws.cand.p; p.cand_count = (int*)ws.cand_count.p; p.order = (int*)ws.order.p; p.mask = (unsigned long long*)ws.mask.p;
     p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
     p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
-    HIPCHK(c, launch_merge_tiles(c->stream, p));
+    HIPCHK(c, launch_merge(c->stream, p));
     c->stage = ROWS_MERGED; c->tl_maxout = max_out;
     return write_out(c, out_on_device, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }
@@ -2144,43 +2149,6 @@ int cf_forward_views(cf_ctx* c, int format, const cf_yuv_planes* frames, int in_
     if (int r = forward_run(c, dst, CF_IN_U8_HWC_BGR, Bf * V)) return r;
     c->vw_V = V; c->tl_Bf = Bf; c->tl_h = h; c->tl_w = w;
     return CF_OK;
-}
-
-// The merge of the last threshold decode's per-view rows (cf_views.hip) on the stream that carried the decode; inputs, workspace and
-// outputs as cf_merge_tiles'.
-int cf_merge_views(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
-    if (!c) return CF_EINVAL;
-    if (!o) return c->fail(CF_EINVAL, "cf_merge_views: null options");
-    if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) return c->fail(CF_EINVAL, "cf_merge_views: unknown metric %d (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)", o->metric);
-    if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge))
-        return c->fail(CF_EINVAL, "cf_merge_views: thresh and edge must be finite and not negative");
-    if (max_out < 1) return c->fail(CF_EINVAL, "cf_merge_views: max_out=%d must be at least 1", max_out);
-    RowSet in{};
-    if (int r = rows_for(c, "cf_merge_views", ROWS_OF_VIEWS_DECODE, in)) return r;
-    const int Bf = c->tl_Bf, V = c->vw_V, rows = in.stride;
-    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit)
-        return c->fail(CF_ENOMEM, "cf_merge_views: %d frames x %d views x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
-                       Bf, V, rows, merge_mask_bytes(Bf, V, rows) / 1e6);
-    HIPCHK(c, hipSetDevice(c->device));
-    c->stage = ROWS_DECODED; c->fo.B = 0; c->lb.B = 0;    // the merged (and tracked, and followed) rows of an earlier call are gone from here on
-    const size_t cap = (size_t)V * rows, mo = (size_t)Bf * max_out, nb = (size_t)Bf * sizeof(int);
-    const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
-    auto& ws = c->tl;
-    const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
-        {ws.cand, Bf * cap * 16 * sizeof(float), "candidates"}, {ws.cand_count, nb, "candidate counts"}, {ws.order, Bf * cap * sizeof(int), "sort order"},
-        {ws.mask, merge_mask_bytes(Bf, V, rows), "suppression bits"}, {ws.dets, nd, "merged dets"}, {ws.lms, nl, "merged landmarks"},
-        {ws.corners, mo * 4 * sizeof(float), "merged corners"}, {ws.counts, nb, "merged counts"}, {ws.flags, nb, "flags"}};
-    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_merge_views")) return r;
-    ViewMergeParams p{};
-    p.views = (const cf_view*)c->vw_dev.p; p.V = V; p.Bf = Bf; p.h = c->tl_h; p.w = c->tl_w;
-    p.dets_net = in.corners; p.scores = in.dets + 4; p.score_stride = 5; p.lms_net = in.lms; p.counts = in.counts; p.rows = rows;
-    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
-    p.cand = (float*)ws.cand.p; p.cand_count = (int*)ws.cand_count.p; p.order = (int*)ws.order.p; p.mask = (unsigned long long*)ws.mask.p;
-    p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
-    p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
-    HIPCHK(c, launch_merge_views(c->stream, p));
-    c->stage = ROWS_MERGED; c->tl_maxout = max_out;
-    return write_out(c, out_on_device, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
 }
 
 // Packed forward: the packed cutter of cf_views.hip writes the N canvases to input_resized in one launch.  The device blob (sorted
@@ -2227,7 +2195,7 @@ static int forward_packed(cf_ctx* c, const char* who, int rot, int format, const
             if (e != hipSuccess) return e;
             c->pk_up = 1;
         }
-        return launch_cut_packed_rot(c->stream, rot, format, pack_dev(c->pk_tab, c->pk_dev.p), N, h, w, p0, p1, fv, dst, c->H, c->W);      // (rot 0: launch_cut_packed)
+        return launch_cut_packed(c->stream, rot, format, pack_dev(c->pk_tab, c->pk_dev.p), N, h, w, p0, p1, fv, dst, c->H, c->W);
     };
     if (in_on_device) HIPCHK(c, cut(planes, pitch0, pitch1));
     else if (int r = src_stage_frames(c, who, FrameGeo{format, Bf, h, w, pitch0, pitch1}, planes, cut)) return r;
@@ -2246,41 +2214,19 @@ int cf_forward_packed_rot(cf_ctx* c, int rot, int format, const cf_yuv_planes* f
     return forward_packed(c, "cf_forward_packed_rot", rot, format, frames, in_on_device, Bf, h, w, pitch0, pitch1, places, P, N, fill);
 }
 
-// The merge of the last threshold decode's per-canvas rows by placement (cf_views.hip) on the stream that carried the decode; inputs,
-// workspace and outputs as cf_merge_views' with the most placements of any frame in the place of V.
+// The three merges: the rows of a tiled, a views or a packed decode through merge_rows (cf_merge_packed maps through the turn the
+// packed forward remembered).
+int cf_merge_tiles(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
+    if (!c) return CF_EINVAL;
+    return merge_rows(c, "cf_merge_tiles", ROWS_OF_TILED_DECODE, MERGE_TILES, "tiles", o, max_out, dets, lms, counts, flags, out_on_device);
+}
+int cf_merge_views(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
+    if (!c) return CF_EINVAL;
+    return merge_rows(c, "cf_merge_views", ROWS_OF_VIEWS_DECODE, MERGE_VIEWS, "views", o, max_out, dets, lms, counts, flags, out_on_device);
+}
 int cf_merge_packed(cf_ctx* c, const cf_merge_opts* o, int max_out, float* dets, float* lms, int32_t* counts, int32_t* flags, int out_on_device) {
     if (!c) return CF_EINVAL;
-    if (!o) return c->fail(CF_EINVAL, "cf_merge_packed: null options");
-    if (o->metric != CF_MERGE_IOU && o->metric != CF_MERGE_IOS) return c->fail(CF_EINVAL, "cf_merge_packed: unknown metric %d (0 = CF_MERGE_IOU, 1 = CF_MERGE_IOS)", o->metric);
-    if (!(o->thresh >= 0.f) || !(o->edge >= 0.f) || !std::isfinite(o->thresh) || !std::isfinite(o->edge))
-        return c->fail(CF_EINVAL, "cf_merge_packed: thresh and edge must be finite and not negative");
-    if (max_out < 1) return c->fail(CF_EINVAL, "cf_merge_packed: max_out=%d must be at least 1", max_out);
-    RowSet in{};
-    if (int r = rows_for(c, "cf_merge_packed", ROWS_OF_PACKED_DECODE, in)) return r;
-    const int Bf = c->tl_Bf, V = c->pk_tab.most, rows = in.stride;
-    if ((long long)V * rows > (1 << 24) || merge_mask_bytes(Bf, V, rows) > kMergeMaskLimit)
-        return c->fail(CF_ENOMEM, "cf_merge_packed: %d frames x %d placements x %d rows need %.1f MB of suppression bits (limit 256 MiB): decode with a smaller max_out",
-                       Bf, V, rows, merge_mask_bytes(Bf, V, rows) / 1e6);
-    HIPCHK(c, hipSetDevice(c->device));
-    c->stage = ROWS_DECODED; c->fo.B = 0; c->lb.B = 0;    // the merged (and tracked, and followed) rows of an earlier call are gone from here on
-    const size_t cap = (size_t)V * rows, mo = (size_t)Bf * max_out, nb = (size_t)Bf * sizeof(int);
-    const size_t nd = mo * 5 * sizeof(float), nl = mo * 10 * sizeof(float);
-    auto& ws = c->tl;
-    const struct { DevBuf& b; size_t need; const char* what; } bufs[] = {
-        {ws.cand, Bf * cap * 16 * sizeof(float), "candidates"}, {ws.cand_count, nb, "candidate counts"}, {ws.order, Bf * cap * sizeof(int), "sort order"},
-        {ws.mask, merge_mask_bytes(Bf, V, rows), "suppression bits"}, {ws.dets, nd, "merged dets"}, {ws.lms, nl, "merged landmarks"},
-        {ws.corners, mo * 4 * sizeof(float), "merged corners"}, {ws.counts, nb, "merged counts"}, {ws.flags, nb, "flags"}};
-    for (const auto& b : bufs) if (int r = grow(c, b.b, b.need, b.what, "cf_merge_packed")) return r;
-    ViewMergeParams p{};
-    p.views = nullptr; p.V = V; p.Bf = Bf; p.h = c->tl_h; p.w = c->tl_w;
-    p.dets_net = in.corners; p.scores = in.dets + 4; p.score_stride = 5; p.lms_net = in.lms; p.counts = in.counts; p.rows = rows;
-    p.metric = o->metric; p.thresh = o->thresh; p.edge = o->edge;
-    p.cand = (float*)ws.cand.p; p.cand_count = (int*)ws.cand_count.p; p.order = (int*)ws.order.p; p.mask = (unsigned long long*)ws.mask.p;
-    p.max_out = max_out; p.dets = (float*)ws.dets.p; p.lms = (float*)ws.lms.p; p.corners = (float*)ws.corners.p;
-    p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
-    HIPCHK(c, launch_merge_packed_rot(c->stream, c->pk_rot, p, pack_dev(c->pk_tab, c->pk_dev.p)));      // (pk_rot == 0: launch_merge_packed)
-    c->stage = ROWS_MERGED; c->tl_maxout = max_out;
-    return write_out(c, out_on_device, Bf, max_out, p.out_counts, p.flags, counts, flags, {{dets, p.dets, 5 * sizeof(float)}, {lms, p.lms, 10 * sizeof(float)}});
+    return merge_rows(c, "cf_merge_packed", ROWS_OF_PACKED_DECODE, MERGE_PLACED, "placements", o, max_out, dets, lms, counts, flags, out_on_device);
 }
 
 // Fitted forward: the fit kernel (cf_fit.hip) writes the B padded canvases to input_resized, so the plan and its graphs are those of
@@ -2302,7 +2248,7 @@ int cf_forward_fit(cf_ctx* c, const cf_fit_opts* o, int format, const cf_yuv_pla
     if (fit_geometry(o->anchor, o->upscale, h, w, c->H, c->W, &g)) return c->fail(CF_EINVAL, "cf_forward_fit: no geometry for %d x %d in %d x %d", w, h, c->W, c->H);
     if (int r = forward_begin(c, "cf_forward_fit", B)) return r;
     uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
-    auto fit = [&](const void* const* pl, int p0, int p1) { return launch_fit_frames(c->stream, format, pl, B, h, w, p0, p1, g, o->fill, dst, c->H, c->W); };
+    auto fit = [&](const void* const* pl, int p0, int p1) { return launch_fit_frames(c->stream, 0, format, pl, B, h, w, p0, p1, g, o->fill, dst, c->H, c->W); };
     if (in_on_device) HIPCHK(c, fit(planes, pitch0, pitch1));
     else if (int r = src_stage_frames(c, "cf_forward_fit", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, fit)) return r;
     if (int r = forward_run(c, dst, CF_IN_U8_HWC_BGR, B)) return r;
@@ -2329,7 +2275,7 @@ int cf_forward_rot(cf_ctx* c, const cf_rot_opts* o, int format, const cf_yuv_pla
     if (rot_geometry(o, h, w, c->H, c->W, &g)) return c->fail(CF_EINVAL, "cf_forward_rot: no geometry for %d x %d (rot %d) in %d x %d", w, h, o->rot, c->W, c->H);
     if (int r = forward_begin(c, "cf_forward_rot", B)) return r;
     uint8_t* dst = (uint8_t*)c->bufs[c->buf_resized].p;
-    auto rot = [&](const void* const* pl, int p0, int p1) { return launch_rot_frames(c->stream, o->rot, format, pl, B, h, w, p0, p1, g, o->fit.fill, dst, c->H, c->W); };
+    auto rot = [&](const void* const* pl, int p0, int p1) { return launch_fit_frames(c->stream, o->rot, format, pl, B, h, w, p0, p1, g, o->fit.fill, dst, c->H, c->W); };
     if (in_on_device) HIPCHK(c, rot(planes, pitch0, pitch1));
     else if (int r = src_stage_frames(c, "cf_forward_rot", FrameGeo{format, B, h, w, pitch0, pitch1}, planes, rot)) return r;
     if (int r = forward_run(c, dst, CF_IN_U8_HWC_BGR, B)) return r;

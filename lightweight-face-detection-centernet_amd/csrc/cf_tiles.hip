@@ -11,9 +11,9 @@
 // going out as three dword stores (W % 4 == 0), lane-contiguous.  Source rows start at arbitrary even offsets: the taps are byte loads.
 // Every tap lies inside the rectangle, hence inside the row extents of the planes; pitch padding is never read.
 //
-// MERGE.  A collect kernel fills the per-frame candidate table [Bf][cap = T * rows][16] (the record of ThreshParams::cand) from the
-// per-tile results of a threshold decode, in order (tile ascending, keep position ascending), and the NMS stages of cf_decode.hip run
-// on it.  Per row of tile (x0, y0, rw, rh), i < min(counts, rows):
+// MERGE (launch_merge: here for the tiles, the views and the placements alike; its kernel, collect_rows_kernel<Items, ROT>, is
+// cf_collect.h's).  It fills the per-frame candidate table [Bf][cap = T * rows][16] (the record of ThreshParams::cand) from the per-tile
+// results of a threshold decode, in order (tile ascending, keep position ascending), and the NMS stages of cf_decode.hip run on it.  Per row of tile (x0, y0, rw, rh), i < min(counts, rows):
 //   * dropped when a corner is not finite, or when its network-coordinate box comes within `edge` pixels of an INTERIOR side of the
 //     rectangle (one that is not on the frame border): x1 < edge, x2 > W - edge, y1 < edge, y2 > H - edge (float32 compares);
 //   * else X = (float)((double)x * ((double)rw / (double)W) + (double)x0), Y likewise with rh / H and y0, for the four corners and the
@@ -21,8 +21,8 @@
 // The compaction is a prefix sum over the flattened (tile, row) items, never an atomic: the order is deterministic.
 #include "cf_common.h"
 #include "cf_kernels.h"
-#include "cf_cvresize.h"
-#include "cf_yuvmath.h"
+#include "cf_cutpx.h"
+#include "cf_collect.h"
 #include <string>
 
 namespace cf {
@@ -32,18 +32,7 @@ constexpr int kCutFrames = 64;                       // frames per launch: 3 x 6
 constexpr int kCutRows = 8;                          // output rows per lane (one set of column coefficients)
 using CutPtrs = FramePtrs<kCutFrames>;
 
-// SRC: 0 = BGR rows, 1 = one interleaved chroma plane (NV12 / NV21), 2 = two chroma planes (I420; YV12 on a swapped table);
-// VF: V first in the interleaved pairs (NV21).  One source pixel -> B | G << 8 | R << 16
-template <int SRC, bool VF>
-__device__ __forceinline__ uint32_t cut_tap(const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, int pitch0, int pitch1, int y, int x) {
-    if constexpr (SRC == 0) {
-        const uint8_t* q = p0 + (size_t)y * pitch0 + 3 * x;
-        return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
-    } else {
-        return yuv_px(p0[(size_t)y * pitch0 + x], chroma_at<SRC == 1, VF>(p1, p2, pitch1, y >> 1, x >> 1));
-    }
-}
-
+// (a loop of its own, not the padded lane of cf_cutpx.h: a tile has no padding, so no lane tests for it)
 template <int SRC, bool VF>
 __global__ void __launch_bounds__(256) cut_tiles_kernel(CutPtrs tab, const cf_tile_rect* __restrict__ rects, uint8_t* dst, int T, int pitch0,
                                                         int pitch1, int H, int W) {
@@ -53,9 +42,7 @@ __global__ void __launch_bounds__(256) cut_tiles_kernel(CutPtrs tab, const cf_ti
     if (i >= ng * gw) return;
     const int g = i / gw, X0 = (i - g * gw) << 2;
     const cf_tile_rect r = rects[t];
-    const uint8_t* p0 = tab.p0[f];
-    const uint8_t* p1 = tab.p1[f];
-    const uint8_t* p2 = tab.p2[f];
+    const SrcPlanes src{tab.p0[f], tab.p1[f], tab.p2[f], pitch0, pitch1, 0, 0};
     int x0[4], x1[4], a0[4], a1[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -70,89 +57,9 @@ __global__ void __launch_bounds__(256) cut_tiles_kernel(CutPtrs tab, const cf_ti
         y0 += r.y0; y1 += r.y0;
         uint32_t p[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t t00 = cut_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x0[k]);
-            const uint32_t t01 = cut_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x1[k]);
-            const uint32_t t10 = cut_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x0[k]);
-            const uint32_t t11 = cut_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x1[k]);
-            uint32_t v = 0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int s = 8 * c;
-                const int h0 = (int)((t00 >> s) & 255) * a0[k] + (int)((t01 >> s) & 255) * a1[k];
-                const int h1 = (int)((t10 >> s) & 255) * a0[k] + (int)((t11 >> s) & 255) * a1[k];
-                v |= (uint32_t)cv_linear_vpass(b0, b1, h0, h1) << s;
-            }
-            p[k] = v;
-        }
-        uint32_t* o = reinterpret_cast<uint32_t*>(out + (size_t)Y * W * 3);
-        o[0] = p[0] | (p[1] << 24);
-        o[1] = (p[1] >> 8) | (p[2] << 16);
-        o[2] = (p[2] >> 16) | (p[3] << 8);
+        for (int k = 0; k < 4; ++k) p[k] = bilinear_px<SRC, VF>(src, y0, y1, b0, b1, x0[k], x1[k], a0[k], a1[k]);
+        quad_store(out + (size_t)Y * W * 3, p);
     }
-}
-
-// One workgroup per frame walks the T * rows (tile, row) items in order, 1024 at a time: keep flag, ballot, the 16 wave counts through
-// LDS, write at base + prefix.
-__global__ void __launch_bounds__(1024) merge_collect_kernel(MergeParams p) {
-    __shared__ uint32_t wave_cnt[16];
-    __shared__ int truncated;
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cap = p.T * p.rows;
-    float* cand = p.cand + (size_t)f * cap * 16;
-    if (tid == 0) truncated = 0;
-    __syncthreads();
-    const float W = (float)p.W, H = (float)p.H;
-    uint32_t base = 0;
-    for (int j0 = 0; j0 < cap; j0 += 1024) {
-        const int j = j0 + tid;
-        bool keep = false;
-        int t = 0, row = 0;
-        float c[4] = {0.f, 0.f, 0.f, 0.f};
-        cf_tile_rect r = {0, 0, 2, 2};
-        if (j < cap) {
-            t = j / p.rows; row = j - t * p.rows;
-            const int img = f * p.T + t;
-            const int n = p.counts[img];
-            if (row == 0 && n > p.rows) truncated = 1;                    // (every writer stores the same value)
-            if (row < min(n, p.rows)) {
-                r = p.rects[t];
-                const float4 q = *reinterpret_cast<const float4*>(p.dets_net + ((size_t)img * p.rows + row) * 4);
-                c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w;
-                keep = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]);
-                if (r.x0 > 0 && c[0] < p.edge) keep = false;
-                if (r.x0 + r.w < p.w && c[2] > W - p.edge) keep = false;
-                if (r.y0 > 0 && c[1] < p.edge) keep = false;
-                if (r.y0 + r.h < p.h && c[3] > H - p.edge) keep = false;
-            }
-        }
-        const unsigned long long bal = __ballot(keep);
-        __syncthreads();                                                  // the counts of the round before have been read
-        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = 0, total = 0;
-        for (int w2 = 0; w2 < 16; ++w2) { if (w2 < wave) off += wave_cnt[w2]; total += wave_cnt[w2]; }
-        if (keep) {
-            const uint32_t pos = base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            const size_t src = (size_t)(f * p.T + t) * p.rows + row;
-            const double sx = (double)r.w / (double)p.W, sy = (double)r.h / (double)p.H;
-            const double ox = (double)r.x0, oy = (double)r.y0;
-            float o[16];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = (float)((double)c[k] * ((k & 1) ? sy : sx) + ((k & 1) ? oy : ox));
-            o[4] = p.scores[src * p.score_stride];
-            const float* l = p.lms_net + src * 10;
-#pragma unroll
-            for (int k = 0; k < 10; ++k) o[5 + k] = (float)((double)l[k] * ((k & 1) ? sy : sx) + ((k & 1) ? oy : ox));
-            o[15] = 0.0f;
-            float4* d = reinterpret_cast<float4*>(cand + (size_t)pos * 16);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) d[k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
-        }
-        base += total;
-    }
-    __syncthreads();
-    if (tid == 0) { p.cand_count[f] = (int)base; p.flags[f] = truncated; }
 }
 
 }  // namespace
@@ -209,33 +116,39 @@ hipError_t launch_cut_tiles(hipStream_t s, int format, const void* const* planes
         const CutPtrs tab = frame_ptrs<kCutFrames>(planes, format, f0, nb, true);      // YV12: the I420 kernel on swapped planes (as launch_yuv_to_bgr)
         const dim3 grid((unsigned)((n + 255) / 256), (unsigned)T, (unsigned)nb);
         uint8_t* out = dst + (size_t)f0 * T * H * W * 3;
-        switch (format) {
-            case CF_YUV_NV12: hipLaunchKernelGGL((cut_tiles_kernel<1, false>), grid, dim3(256), 0, s, tab, rects, out, T, pitch0, pitch1, H, W); break;
-            case CF_YUV_NV21: hipLaunchKernelGGL((cut_tiles_kernel<1, true>), grid, dim3(256), 0, s, tab, rects, out, T, pitch0, pitch1, H, W); break;
-            case CF_YUV_I420: case CF_YUV_YV12: hipLaunchKernelGGL((cut_tiles_kernel<2, false>), grid, dim3(256), 0, s, tab, rects, out, T, pitch0, pitch1, H, W); break;
-            default: hipLaunchKernelGGL((cut_tiles_kernel<0, false>), grid, dim3(256), 0, s, tab, rects, out, T, pitch0, pitch1, H, W); break;
-        }
+        with_format(format, [&](auto SRC, auto VF) {
+            hipLaunchKernelGGL((cut_tiles_kernel<SRC, VF>), grid, dim3(256), 0, s, tab, rects, out, T, pitch0, pitch1, H, W);
+        });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-size_t merge_mask_bytes(int Bf, int T, int rows) {
-    const size_t cap = (size_t)T * rows;
+size_t merge_mask_bytes(int Bf, int V, int rows) {
+    const size_t cap = (size_t)V * rows;
     return (size_t)Bf * cap * ((cap + 63) / 64) * sizeof(unsigned long long);
 }
 
-hipError_t launch_merge_tiles(hipStream_t s, const MergeParams& p) {
-    if (p.Bf < 1 || p.T < 1 || p.rows < 1 || p.max_out < 1 || (long long)p.T * p.rows > INT_MAX / 16 || p.H < 1 || p.W < 1 || p.score_stride < 1 ||
-        (p.metric != CF_MERGE_IOU && p.metric != CF_MERGE_IOS) || !p.rects || !p.dets_net || !p.scores || !p.lms_net || !p.counts || !p.cand ||
-        !p.cand_count || !p.order || !p.mask || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
+hipError_t launch_merge(hipStream_t s, const MergeParams& p) {
+    const bool sources = p.kind == MERGE_TILES ? p.rects && p.H >= 1 && p.W >= 1 && p.rot == 0
+                       : p.kind == MERGE_VIEWS ? p.views && p.rot == 0
+                       : p.kind == MERGE_PLACED && p.pack.places && p.pack.fr_off && p.pack.fr_idx && (p.rot == 0 || p.rot == 90 || p.rot == 180 || p.rot == 270);
+    if (!sources || p.Bf < 1 || p.V < 1 || p.rows < 1 || p.max_out < 1 || (long long)p.V * p.rows > INT_MAX / 16 || p.h < 1 || p.w < 1 || p.score_stride < 1 ||
+        (p.metric != CF_MERGE_IOU && p.metric != CF_MERGE_IOS) || !p.dets_net || !p.scores || !p.lms_net || !p.counts || !p.cand || !p.cand_count ||
+        !p.order || !p.mask || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(merge_collect_kernel, dim3(p.Bf), dim3(1024), 0, s, p);
+    const dim3 grid(p.Bf), block(1024);
+    if (p.kind == MERGE_TILES) hipLaunchKernelGGL((collect_rows_kernel<TileItems, 0>), grid, block, 0, s, p);
+    else if (p.kind == MERGE_VIEWS) hipLaunchKernelGGL((collect_rows_kernel<ViewItems, 0>), grid, block, 0, s, p);
+    else if (p.rot == 0) hipLaunchKernelGGL((collect_rows_kernel<PlacedItems, 0>), grid, block, 0, s, p);
+    else if (p.rot == 90) hipLaunchKernelGGL((collect_rows_kernel<PlacedItems, 1>), grid, block, 0, s, p);
+    else if (p.rot == 180) hipLaunchKernelGGL((collect_rows_kernel<PlacedItems, 2>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((collect_rows_kernel<PlacedItems, 3>), grid, block, 0, s, p);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     ThreshParams q{};
-    q.B = p.Bf; q.cap = p.T * p.rows; q.nms_thresh = p.thresh; q.metric = p.metric;
+    q.B = p.Bf; q.cap = p.V * p.rows; q.nms_thresh = p.thresh; q.metric = p.metric;
     q.cand = p.cand; q.cand_count = p.cand_count; q.order = p.order; q.mask = p.mask;
     q.max_out = p.max_out; q.dets = p.dets; q.lms = p.lms; q.dets_net = p.corners; q.counts = p.out_counts;
     return launch_nms_stages(s, q);

@@ -16,7 +16,7 @@
 // canvas); a padding column beside content computes the edge column's taps and drops them.  The taps are byte loads; every tap lies
 // inside the source rectangle, pitch padding is never read.
 //
-// MERGE.  A collect kernel fills the per-frame candidate table [Bf][cap = V * rows][16] (the record of ThreshParams::cand) from the
+// MERGE (collect_rows_kernel<ViewItems, 0> of cf_collect.h, launched by cf_tiles.hip's launch_merge).  It fills the candidate table [Bf][cap = V * rows][16] (the record of ThreshParams::cand) from the
 // per-view results of a threshold decode, in order (view ascending, keep position ascending), and the NMS stages of cf_decode.hip run
 // on it.  Per row of view v, i < min(counts, rows), dropped when
 //   * a corner is not finite, or
@@ -29,13 +29,11 @@
 // The compaction is a prefix sum over the flattened (view, row) items, never an atomic: the order is deterministic.
 //
 // PACKED VIEWS (further down).  A placement (cf_place) puts one view of one frame into one canvas, so several levels and frames share a
-// canvas: cut_packed_kernel writes all canvases in one launch, one writer per byte, and packed_collect_kernel walks a frame's placements;
-// the two kernels above are not touched by it.
+// canvas: cut_packed_kernel writes all canvases in one launch, one writer per byte, and the collect kernel walks a frame's placements
+// (PlacedItems).
 #include "cf_common.h"
 #include "cf_kernels.h"
-#include "cf_cvresize.h"
-#include "cf_yuvmath.h"
-#include "cf_fitpx.h"
+#include "cf_cutpx.h"
 #include <algorithm>
 #include <cstdio>
 #include <string>
@@ -48,18 +46,7 @@ constexpr int kViewFrames = 64;                      // frames per launch: 3 x 6
 constexpr int kViewRows = 4;                         // canvas rows per lane (one set of column coefficients): the fit's figure, cf_fit.hip says why not 8
 using ViewPtrs = FramePtrs<kViewFrames>;
 
-// SRC: 0 = BGR rows, 1 = one interleaved chroma plane (NV12 / NV21), 2 = two chroma planes (I420; YV12 on a swapped table);
-// VF: V first in the interleaved pairs (NV21).  One source pixel -> B | G << 8 | R << 16
-template <int SRC, bool VF>
-__device__ __forceinline__ uint32_t view_tap(const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, int pitch0, int pitch1, int y, int x) {
-    if constexpr (SRC == 0) {
-        const uint8_t* q = p0 + (size_t)y * pitch0 + 3 * x;
-        return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
-    } else {
-        return yuv_px(p0[(size_t)y * pitch0 + x], chroma_at<SRC == 1, VF>(p1, p2, pitch1, y >> 1, x >> 1));
-    }
-}
-
+// the padded lane of cf_cutpx.h on view blockIdx.y of the device's table
 template <int SRC, bool VF>
 __global__ void __launch_bounds__(256) cut_views_kernel(ViewPtrs tab, const cf_view* __restrict__ views, uint8_t* dst, int V, uint32_t fill,
                                                         int pitch0, int pitch1, int H, int W) {
@@ -67,119 +54,9 @@ __global__ void __launch_bounds__(256) cut_views_kernel(ViewPtrs tab, const cf_v
     const int gw = W >> 2, ng = (H + kViewRows - 1) / kViewRows;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= ng * gw) return;
-    const int grp = i / gw, X0 = (i - grp * gw) << 2;
-    const cf_view r = views[v];
-    uint8_t* out = dst + (((size_t)f * V + v) * H * W + X0) * 3;
-    const int Y0 = grp * kViewRows, Yend = min(H, Y0 + kViewRows);
-    const uint32_t pad[4] = {fill, fill, fill, fill};
-    bool in[4];
-    int x0[4], x1[4], a0[4], a1[4];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int x = X0 + k - r.dx;
-        in[k] = x >= 0 && x < r.dw;
-        cv_linear_coeffs(min(max(x, 0), r.dw - 1), r.sw, r.dw, true, x0[k], x1[k], a0[k], a1[k]);      // a padding column beside content: the edge's taps, not used
-        x0[k] += r.sx0; x1[k] += r.sx0;
-        any = any || in[k];
-    }
-    if (!any || Yend <= r.dy || Y0 >= r.dy + r.dh) {     // the lane's columns, or all of its rows, are padding: the source is not touched
-        for (int Y = Y0; Y < Yend; ++Y) fit_store(out + (size_t)Y * W * 3, pad);
-        return;
-    }
-    const uint8_t* p0 = tab.p0[f];
-    const uint8_t* p1 = tab.p1[f];
-    const uint8_t* p2 = tab.p2[f];
-    for (int Y = Y0; Y < Yend; ++Y) {
-        const int y = Y - r.dy;
-        if (y < 0 || y >= r.dh) { fit_store(out + (size_t)Y * W * 3, pad); continue; }
-        int y0, y1, b0, b1;
-        cv_linear_coeffs(y, r.sh, r.dh, false, y0, y1, b0, b1);
-        y0 += r.sy0; y1 += r.sy0;
-        uint32_t p[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t t00 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x0[k]);
-            const uint32_t t01 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x1[k]);
-            const uint32_t t10 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x0[k]);
-            const uint32_t t11 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x1[k]);
-            uint32_t ch[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int s = 8 * c;
-                const int h0 = (int)((t00 >> s) & 255) * a0[k] + (int)((t01 >> s) & 255) * a1[k];
-                const int h1 = (int)((t10 >> s) & 255) * a0[k] + (int)((t11 >> s) & 255) * a1[k];
-                ch[c] = (uint32_t)cv_linear_vpass(b0, b1, h0, h1);
-            }
-            p[k] = in[k] ? pack_bgr(ch[0], ch[1], ch[2]) : fill;
-        }
-        fit_store(out + (size_t)Y * W * 3, p);
-    }
-}
-
-// One workgroup per frame walks the V * rows (view, row) items in order, 1024 at a time: keep flag, ballot, the 16 wave counts through
-// LDS, write at base + prefix (as merge_collect_kernel).
-__global__ void __launch_bounds__(1024) views_collect_kernel(ViewMergeParams p) {
-    __shared__ uint32_t wave_cnt[16];
-    __shared__ int truncated;
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cap = p.V * p.rows;
-    float* cand = p.cand + (size_t)f * cap * 16;
-    if (tid == 0) truncated = 0;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int j0 = 0; j0 < cap; j0 += 1024) {
-        const int j = j0 + tid;
-        bool keep = false;
-        int v = 0, row = 0;
-        float c[4] = {0.f, 0.f, 0.f, 0.f};
-        cf_view r = {0, 0, 2, 2, 0, 0, 1, 1};
-        if (j < cap) {
-            v = j / p.rows; row = j - v * p.rows;
-            const int img = f * p.V + v;
-            const int n = p.counts[img];
-            if (row == 0 && n > p.rows) truncated = 1;                    // (every writer stores the same value)
-            if (row < min(n, p.rows)) {
-                r = p.views[v];
-                const float4 q = *reinterpret_cast<const float4*>(p.dets_net + ((size_t)img * p.rows + row) * 4);
-                c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w;
-                keep = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]);
-                const float xlo = (float)r.dx, xhi = (float)(r.dx + r.dw), ylo = (float)r.dy, yhi = (float)(r.dy + r.dh);
-                const float cx = (c[0] + c[2]) * 0.5f, cy = (c[1] + c[3]) * 0.5f;
-                if (!(cx >= xlo && cx < xhi && cy >= ylo && cy < yhi)) keep = false;
-                if (r.sx0 > 0 && c[0] < xlo + p.edge) keep = false;
-                if (r.sx0 + r.sw < p.w && c[2] > xhi - p.edge) keep = false;
-                if (r.sy0 > 0 && c[1] < ylo + p.edge) keep = false;
-                if (r.sy0 + r.sh < p.h && c[3] > yhi - p.edge) keep = false;
-            }
-        }
-        const unsigned long long bal = __ballot(keep);
-        __syncthreads();                                                  // the counts of the round before have been read
-        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = 0, total = 0;
-        for (int w2 = 0; w2 < 16; ++w2) { if (w2 < wave) off += wave_cnt[w2]; total += wave_cnt[w2]; }
-        if (keep) {
-            const uint32_t pos = base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            const size_t src = (size_t)(f * p.V + v) * p.rows + row;
-            const double sx = (double)r.sw / (double)r.dw, sy = (double)r.sh / (double)r.dh;
-            const double dx = (double)r.dx, dy = (double)r.dy, ox = (double)r.sx0, oy = (double)r.sy0;
-            float o[16];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = (float)(((double)c[k] - ((k & 1) ? dy : dx)) * ((k & 1) ? sy : sx) + ((k & 1) ? oy : ox));
-            o[4] = p.scores[src * p.score_stride];
-            const float* l = p.lms_net + src * 10;
-#pragma unroll
-            for (int k = 0; k < 10; ++k) o[5 + k] = (float)(((double)l[k] - ((k & 1) ? dy : dx)) * ((k & 1) ? sy : sx) + ((k & 1) ? oy : ox));
-            o[15] = 0.0f;
-            float4* d = reinterpret_cast<float4*>(cand + (size_t)pos * 16);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) d[k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
-        }
-        base += total;
-    }
-    __syncthreads();
-    if (tid == 0) { p.cand_count[f] = (int)base; p.flags[f] = truncated; }
+    const int grp = i / gw, X0 = (i - grp * gw) << 2, Y0 = grp * kViewRows;
+    padded_lane<SRC, VF, 0>(views[v], SrcPlanes{tab.p0[f], tab.p1[f], tab.p2[f], pitch0, pitch1, 0, 0}, dst + ((size_t)f * V + v) * H * W * 3, W, X0, Y0,
+                            min(H, Y0 + kViewRows), fill);
 }
 
 // PACKED VIEWS.  A placement puts one view of one frame into one canvas; a canvas holds any number of them, disjoint.
@@ -187,19 +64,20 @@ __global__ void __launch_bounds__(1024) views_collect_kernel(ViewMergeParams p) 
 // CUT.  One launch writes all N canvases, every byte once.  A workgroup owns a kPackTileW x kPackTileH tile of canvas blockIdx.y; its
 // lanes keep the shape of cut_views_kernel (four adjacent canvas columns, kViewRows rows, three dword stores per row), 32 lanes across
 // and 8 down.  The placements are sorted by canvas on the host (t.cv_off: the CSR).  In rounds of kPackList placements of its canvas,
-// every thread tests one against the tile and the hits are compacted into an LDS list (ballot, the four wave counts through LDS: no
-// atomic, the list is in placement order); a list can therefore not overflow, a canvas with more placements takes more rounds.  Every
-// lane then walks the list: a placement that reaches into its 4 x kViewRows pixels gets its column taps and coefficients computed once
-// and serves the lane's rows; the pixels live in registers from the first round to the stores at the end, `fill` where no placement
-// wrote.  A tile no placement touches stores fill and reads no frame.  Taps as view_tap: inside the placement's source rectangle.
+// every thread tests one against the tile and the hits are compacted into an LDS list (list_round, cf_cutpx.h); a list can therefore
+// not overflow, a canvas with more placements takes more rounds.  Every lane then walks the list: a placement that reaches into its
+// 4 x kViewRows pixels gets its column taps and coefficients computed once (col_coeffs) and serves the lane's rows (bilinear_px); the
+// pixels live in registers from the first round to the stores at the end, `fill` where no placement wrote.  A tile no placement touches
+// stores fill and reads no frame.  Taps inside the placement's source rectangle.  ROT: 0 = frames as stored; 2 = rot 180 (h x w the
+// stored frame), the same layout on mirrored taps: adjacent canvas columns are still adjacent stored columns.
 constexpr int kPackTileW = 128, kPackTileH = 8 * kViewRows;
-constexpr int kPackList = 256;
 
-template <int SRC, bool VF>
-__global__ void __launch_bounds__(256) cut_packed_kernel(PackDev t, uint8_t* dst, uint32_t fill, int pitch0, int pitch1, int H, int W, int tiles_x) {
+template <int SRC, bool VF, int ROT>
+__global__ void __launch_bounds__(256) cut_packed_kernel(PackDev t, uint8_t* dst, uint32_t fill, int h, int w, int pitch0, int pitch1, int H, int W,
+                                                         int tiles_x) {
     __shared__ int s_list[kPackList];
     __shared__ int s_cnt[4];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, n = (int)blockIdx.y;
+    const int tid = (int)threadIdx.x, n = (int)blockIdx.y;
     const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
     const int tx0 = tx * kPackTileW, ty0 = ty * kPackTileH;
     const int X0 = tx0 + 4 * (tid & 31), Y0 = ty0 + kViewRows * (tid >> 5);
@@ -211,20 +89,7 @@ __global__ void __launch_bounds__(256) cut_packed_kernel(PackDev t, uint8_t* dst
         for (int k = 0; k < 4; ++k) px[i][k] = fill;
     const int k0 = t.cv_off[n], k1 = t.cv_off[n + 1];
     for (int base = k0; base < k1; base += kPackList) {   // uniform trip count
-        const int cand = base + tid;
-        bool hit = false;
-        if (cand < k1) {
-            const cf_view r = t.places[cand].view;
-            hit = r.dx < tx0 + kPackTileW && r.dx + r.dw > tx0 && r.dy < ty0 + kPackTileH && r.dy + r.dh > ty0;
-        }
-        const unsigned long long m = __ballot(hit);
-        if (lane == 0) s_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int at = 0, cnt = 0;
-#pragma unroll
-        for (int w2 = 0; w2 < 4; ++w2) { if (w2 < wave) at += s_cnt[w2]; cnt += s_cnt[w2]; }
-        if (hit) s_list[at + __popcll(m & ((1ull << lane) - 1ull))] = cand;
-        __syncthreads();
+        const int cnt = list_round(t, base, k1, tx0, ty0, kPackTileW, kPackTileH, s_list, s_cnt);
         if (live)
             for (int j = 0; j < cnt; ++j) {
                 const cf_place& pl = t.places[__builtin_amdgcn_readfirstlane(s_list[j])];
@@ -232,16 +97,8 @@ __global__ void __launch_bounds__(256) cut_packed_kernel(PackDev t, uint8_t* dst
                 if (X0 + 4 <= r.dx || X0 >= r.dx + r.dw || Y0 + kViewRows <= r.dy || Y0 >= r.dy + r.dh) continue;      // not this lane's pixels
                 bool in[4];
                 int x0[4], x1[4], a0[4], a1[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int x = X0 + k - r.dx;
-                    in[k] = x >= 0 && x < r.dw;
-                    cv_linear_coeffs(min(max(x, 0), r.dw - 1), r.sw, r.dw, true, x0[k], x1[k], a0[k], a1[k]);      // a foreign column: the edge's taps, not used
-                    x0[k] += r.sx0; x1[k] += r.sx0;
-                }
-                const uint8_t* p0 = t.planes[3 * pl.frame];
-                const uint8_t* p1 = t.planes[3 * pl.frame + 1];
-                const uint8_t* p2 = t.planes[3 * pl.frame + 2];
+                col_coeffs(r, X0, in, x0, x1, a0, a1);
+                const SrcPlanes src{t.planes[3 * pl.frame], t.planes[3 * pl.frame + 1], t.planes[3 * pl.frame + 2], pitch0, pitch1, h, w};
 #pragma unroll
                 for (int i = 0; i < kViewRows; ++i) {
                     const int y = Y0 + i - r.dy;
@@ -251,19 +108,8 @@ __global__ void __launch_bounds__(256) cut_packed_kernel(PackDev t, uint8_t* dst
                     y0 += r.sy0; y1 += r.sy0;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const uint32_t t00 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x0[k]);
-                        const uint32_t t01 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y0, x1[k]);
-                        const uint32_t t10 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x0[k]);
-                        const uint32_t t11 = view_tap<SRC, VF>(p0, p1, p2, pitch0, pitch1, y1, x1[k]);
-                        uint32_t ch[3];
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const int s = 8 * c;
-                            const int h0 = (int)((t00 >> s) & 255) * a0[k] + (int)((t01 >> s) & 255) * a1[k];
-                            const int h1 = (int)((t10 >> s) & 255) * a0[k] + (int)((t11 >> s) & 255) * a1[k];
-                            ch[c] = (uint32_t)cv_linear_vpass(b0, b1, h0, h1);
-                        }
-                        if (in[k]) px[i][k] = pack_bgr(ch[0], ch[1], ch[2]);
+                        const uint32_t v = bilinear_px<SRC, VF, ROT>(src, y0, y1, b0, b1, x0[k], x1[k], a0[k], a1[k]);
+                        if (in[k]) px[i][k] = v;
                     }
                 }
             }
@@ -273,75 +119,7 @@ __global__ void __launch_bounds__(256) cut_packed_kernel(PackDev t, uint8_t* dst
     uint8_t* out = dst + (((size_t)n * H + Y0) * W + X0) * 3;
 #pragma unroll
     for (int i = 0; i < kViewRows; ++i)
-        if (Y0 + i < H) fit_store(out + (size_t)i * W * 3, px[i]);
-}
-
-// views_collect_kernel over placements: one workgroup per frame walks the (placement, row) items of ITS placements (t.fr_off: the CSR by
-// frame; t.fr_idx: their positions in the sorted table, in placement-index order), 1024 at a time; the image of an item is its
-// placement's canvas.  The candidate table is [Bf][cap = p.V * rows][16] with p.V = the most placements of any frame.
-__global__ void __launch_bounds__(1024) packed_collect_kernel(ViewMergeParams p, PackDev t) {
-    __shared__ uint32_t wave_cnt[16];
-    __shared__ int truncated;
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q0 = t.fr_off[f], items = (t.fr_off[f + 1] - q0) * p.rows;
-    float* cand = p.cand + (size_t)f * p.V * p.rows * 16;
-    if (tid == 0) truncated = 0;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int j0 = 0; j0 < items; j0 += 1024) {
-        const int j = j0 + tid;
-        bool keep = false;
-        int img = 0, row = 0;
-        float c[4] = {0.f, 0.f, 0.f, 0.f};
-        cf_view r = {0, 0, 2, 2, 0, 0, 1, 1};
-        if (j < items) {
-            const int q = j / p.rows;
-            row = j - q * p.rows;
-            const cf_place& pl = t.places[t.fr_idx[q0 + q]];
-            img = pl.canvas;
-            const int n = p.counts[img];
-            if (row == 0 && n > p.rows) truncated = 1;                    // (every writer stores the same value)
-            if (row < min(n, p.rows)) {
-                r = pl.view;
-                const float4 b4 = *reinterpret_cast<const float4*>(p.dets_net + ((size_t)img * p.rows + row) * 4);
-                c[0] = b4.x; c[1] = b4.y; c[2] = b4.z; c[3] = b4.w;
-                keep = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(c[3]);
-                const float xlo = (float)r.dx, xhi = (float)(r.dx + r.dw), ylo = (float)r.dy, yhi = (float)(r.dy + r.dh);
-                const float cx = (c[0] + c[2]) * 0.5f, cy = (c[1] + c[3]) * 0.5f;
-                if (!(cx >= xlo && cx < xhi && cy >= ylo && cy < yhi)) keep = false;
-                if (r.sx0 > 0 && c[0] < xlo + p.edge) keep = false;
-                if (r.sx0 + r.sw < p.w && c[2] > xhi - p.edge) keep = false;
-                if (r.sy0 > 0 && c[1] < ylo + p.edge) keep = false;
-                if (r.sy0 + r.sh < p.h && c[3] > yhi - p.edge) keep = false;
-            }
-        }
-        const unsigned long long bal = __ballot(keep);
-        __syncthreads();                                                  // the counts of the round before have been read
-        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = 0, total = 0;
-        for (int w2 = 0; w2 < 16; ++w2) { if (w2 < wave) off += wave_cnt[w2]; total += wave_cnt[w2]; }
-        if (keep) {
-            const uint32_t pos = base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            const size_t src = (size_t)img * p.rows + row;
-            const double sx = (double)r.sw / (double)r.dw, sy = (double)r.sh / (double)r.dh;
-            const double dx = (double)r.dx, dy = (double)r.dy, ox = (double)r.sx0, oy = (double)r.sy0;
-            float o[16];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = (float)(((double)c[k] - ((k & 1) ? dy : dx)) * ((k & 1) ? sy : sx) + ((k & 1) ? oy : ox));
-            o[4] = p.scores[src * p.score_stride];
-            const float* l = p.lms_net + src * 10;
-#pragma unroll
-            for (int k = 0; k < 10; ++k) o[5 + k] = (float)(((double)l[k] - ((k & 1) ? dy : dx)) * ((k & 1) ? sy : sx) + ((k & 1) ? oy : ox));
-            o[15] = 0.0f;
-            float4* d = reinterpret_cast<float4*>(cand + (size_t)pos * 16);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) d[k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
-        }
-        base += total;
-    }
-    __syncthreads();
-    if (tid == 0) { p.cand_count[f] = (int)base; p.flags[f] = truncated; }
+        if (Y0 + i < H) quad_store(out + (size_t)i * W * 3, px[i]);
 }
 
 }  // namespace
@@ -420,31 +198,13 @@ hipError_t launch_cut_views(hipStream_t s, int format, const void* const* planes
         const ViewPtrs tab = frame_ptrs<kViewFrames>(planes, format, f0, nb, true);      // YV12: the I420 kernel on swapped planes (as launch_cut_tiles)
         const dim3 grid((unsigned)((n + 255) / 256), (unsigned)V, (unsigned)nb);
         uint8_t* out = dst + (size_t)f0 * V * H * W * 3;
-        switch (format) {
-            case CF_YUV_NV12: hipLaunchKernelGGL((cut_views_kernel<1, false>), grid, dim3(256), 0, s, tab, views, out, V, fv, pitch0, pitch1, H, W); break;
-            case CF_YUV_NV21: hipLaunchKernelGGL((cut_views_kernel<1, true>), grid, dim3(256), 0, s, tab, views, out, V, fv, pitch0, pitch1, H, W); break;
-            case CF_YUV_I420: case CF_YUV_YV12: hipLaunchKernelGGL((cut_views_kernel<2, false>), grid, dim3(256), 0, s, tab, views, out, V, fv, pitch0, pitch1, H, W); break;
-            default: hipLaunchKernelGGL((cut_views_kernel<0, false>), grid, dim3(256), 0, s, tab, views, out, V, fv, pitch0, pitch1, H, W); break;
-        }
+        with_format(format, [&](auto SRC, auto VF) {
+            hipLaunchKernelGGL((cut_views_kernel<SRC, VF>), grid, dim3(256), 0, s, tab, views, out, V, fv, pitch0, pitch1, H, W);
+        });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-hipError_t launch_merge_views(hipStream_t s, const ViewMergeParams& p) {
-    if (p.Bf < 1 || p.V < 1 || p.rows < 1 || p.max_out < 1 || (long long)p.V * p.rows > INT_MAX / 16 || p.h < 1 || p.w < 1 || p.score_stride < 1 ||
-        (p.metric != CF_MERGE_IOU && p.metric != CF_MERGE_IOS) || !p.views || !p.dets_net || !p.scores || !p.lms_net || !p.counts || !p.cand ||
-        !p.cand_count || !p.order || !p.mask || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(views_collect_kernel, dim3(p.Bf), dim3(1024), 0, s, p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    ThreshParams q{};
-    q.B = p.Bf; q.cap = p.V * p.rows; q.nms_thresh = p.thresh; q.metric = p.metric;
-    q.cand = p.cand; q.cand_count = p.cand_count; q.order = p.order; q.mask = p.mask;
-    q.max_out = p.max_out; q.dets = p.dets; q.lms = p.lms; q.dets_net = p.corners; q.counts = p.out_counts;
-    return launch_nms_stages(s, q);
 }
 
 // The first-fit shelf packer of cf_pack_views (the rule is stated in include/centerface_hip.h and restated in tests/pack_cases.py).
@@ -546,34 +306,23 @@ PackHost pack_table(const cf_place* places, int P, int N, int Bf, const void* co
     return t;
 }
 
-hipError_t launch_cut_packed(hipStream_t s, int format, const PackDev& t, int N, int pitch0, int pitch1, const uint8_t* fill, uint8_t* dst, int H, int W) {
-    if (format < CF_YUV_NV12 || format > CF_FRAME_BGR || !t.places || !t.cv_off || !t.planes || !fill || !dst || N < 1 || N > 65535 || H < 1 || W < 4 || (W & 3))
+// rot 90 / 270 go to the quarter-turn kernel of cf_views_rot.hip
+hipError_t launch_cut_packed(hipStream_t s, int rot, int format, const PackDev& t, int N, int h, int w, int pitch0, int pitch1, const uint8_t* fill,
+                             uint8_t* dst, int H, int W) {
+    if ((rot != 0 && rot != 90 && rot != 180 && rot != 270) || format < CF_YUV_NV12 || format > CF_FRAME_BGR || !t.places || !t.cv_off || !t.planes || !fill ||
+        !dst || N < 1 || N > 65535 || H < 1 || W < 4 || (W & 3) || (rot != 0 && (h < 2 || w < 2 || ((h | w) & 1))))
         return hipErrorInvalidValue;
     const uint32_t fv = (uint32_t)fill[0] | ((uint32_t)fill[1] << 8) | ((uint32_t)fill[2] << 16);
-    const int tiles_x = (W + kPackTileW - 1) / kPackTileW, tiles_y = (H + kPackTileH - 1) / kPackTileH;
-    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N);
-    switch (format) {
-        case CF_YUV_NV12: hipLaunchKernelGGL((cut_packed_kernel<1, false>), grid, dim3(256), 0, s, t, dst, fv, pitch0, pitch1, H, W, tiles_x); break;
-        case CF_YUV_NV21: hipLaunchKernelGGL((cut_packed_kernel<1, true>), grid, dim3(256), 0, s, t, dst, fv, pitch0, pitch1, H, W, tiles_x); break;
-        case CF_YUV_I420: case CF_YUV_YV12: hipLaunchKernelGGL((cut_packed_kernel<2, false>), grid, dim3(256), 0, s, t, dst, fv, pitch0, pitch1, H, W, tiles_x); break;
-        default: hipLaunchKernelGGL((cut_packed_kernel<0, false>), grid, dim3(256), 0, s, t, dst, fv, pitch0, pitch1, H, W, tiles_x); break;
+    if (rot == 90 || rot == 270) launch_cut_packed_quarter(s, rot, format, t, N, dst, fv, h, w, pitch0, pitch1, H, W);
+    else {
+        const int tiles_x = (W + kPackTileW - 1) / kPackTileW, tiles_y = (H + kPackTileH - 1) / kPackTileH;
+        const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N);
+        with_format(format, [&](auto SRC, auto VF) {
+            if (rot == 0) hipLaunchKernelGGL((cut_packed_kernel<SRC, VF, 0>), grid, dim3(256), 0, s, t, dst, fv, h, w, pitch0, pitch1, H, W, tiles_x);
+            else hipLaunchKernelGGL((cut_packed_kernel<SRC, VF, 2>), grid, dim3(256), 0, s, t, dst, fv, h, w, pitch0, pitch1, H, W, tiles_x);
+        });
     }
     return hipGetLastError();
-}
-
-hipError_t launch_merge_packed(hipStream_t s, const ViewMergeParams& p, const PackDev& t) {
-    if (p.Bf < 1 || p.V < 1 || p.rows < 1 || p.max_out < 1 || (long long)p.V * p.rows > INT_MAX / 16 || p.h < 1 || p.w < 1 || p.score_stride < 1 ||
-        (p.metric != CF_MERGE_IOU && p.metric != CF_MERGE_IOS) || !t.places || !t.fr_off || !t.fr_idx || !p.dets_net || !p.scores || !p.lms_net || !p.counts ||
-        !p.cand || !p.cand_count || !p.order || !p.mask || !p.dets || !p.lms || !p.corners || !p.out_counts || !p.flags)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(packed_collect_kernel, dim3(p.Bf), dim3(1024), 0, s, p, t);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    ThreshParams q{};
-    q.B = p.Bf; q.cap = p.V * p.rows; q.nms_thresh = p.thresh; q.metric = p.metric;
-    q.cand = p.cand; q.cand_count = p.cand_count; q.order = p.order; q.mask = p.mask;
-    q.max_out = p.max_out; q.dets = p.dets; q.lms = p.lms; q.dets_net = p.corners; q.counts = p.out_counts;
-    return launch_nms_stages(s, q);
 }
 
 }  // namespace cf

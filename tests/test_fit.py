@@ -212,6 +212,16 @@ def test_op_unfit_bit_exact_on_constructed_tables():
     assert gc.tolist() == [1] and want[0][0][0].tolist() == [10, 4, 30, 24, 0.5]
 
 
+def test_op_unfit_keeps_the_sign_of_a_negative_zero():
+    """Top-left anchor, dx = dy = 0: X = float32((float64(x) - 0) * sx) and nothing is added, so a -0.0 corner and a -0.0 landmark come
+    back as -0.0, bit for bit (a map that added a source offset of 0.0 would return +0.0)."""
+    d = np.float32([[(-0.0, -0.0, 8, 6)]])
+    l = np.zeros((1, 1, 10), np.float32)
+    l[0, 0, :2] = -0.0
+    want, gc, _ = check_unfit((32, 96), NET, d, np.float32([[0.5]]), l, [1], 2, anchor="topleft")
+    assert gc.tolist() == [1] and np.signbit(want[0][0][0, :2]).all() and np.signbit(want[0][1][0, :2]).all()
+
+
 # ------------------------------------------------------------------------------------------ the engine
 def fitted_engine(hw, fmt="bgr", seed=0, need=2, **opts):
     """A 64 x 96 context with the default (synthetic) weights and two frames of ``hw`` whose fitted forward, decoded at a score threshold

@@ -12,6 +12,7 @@ import pytest
 
 import centerface_amd as cfa
 from centerface_amd import ops
+import csrc_text
 from fit_cases import WORKED, fit_geometry_ref, fit_ref, unfit_ref
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,11 +55,10 @@ def test_fit_symbols_constants_and_structs_match_the_header():
         with pytest.raises(ValueError):
             L.fit_opts(**bad)
     # the fit includes the one statement of the resize and of the conversion, and is built without FMA contraction (so is the map)
-    src = open(os.path.join(REPO, "lightweight-face-detection-centernet_amd", "csrc", "cf_fit.hip")).read()
-    assert '#include "cf_cvresize.h"' in src and '#include "cf_yuvmath.h"' in src
-    assert "cv_linear_coeffs(" in src and "cv_linear_vpass(" in src and "yuv_px(" in src
-    assert "1220542" not in src and not re.search(r"\brintf\b", src)       # no second statement of either
-    assert not re.search(r"atomic\w*\s*\(", src, flags=re.I)               # the compaction is a prefix sum: no atomic call
+    # (the statements are in the shared headers cf_fit.hip includes: required of the union, refused in every file of it)
+    texts = csrc_text.unit("cf_fit.hip")
+    assert '#include "cf_cutpx.h"' in texts["cf_fit.hip"] and '#include "cf_collect.h"' in texts["cf_fit.hip"]
+    csrc_text.assert_one_statement(texts, ('#include "cf_cvresize.h"', '#include "cf_yuvmath.h"', "cv_linear_coeffs(", "cv_linear_vpass(", "yuv_px("))
     mk = open(os.path.join(REPO, "lightweight-face-detection-centernet_amd", "csrc", "Makefile")).read()
     srcs = re.search(r"^SRCS\s*=(.*)$", mk, flags=re.M).group(1).split()
     assert "cf_fit.hip" in srcs and re.search(r"EXTRA_cf_fit\s*=\s*-ffp-contract=off", mk)

@@ -273,6 +273,16 @@ def test_merge_packed_rows_in_the_neighbour_in_the_fill_and_on_a_shared_edge():
     assert check_merge(SHARED[:1], 2, frame, net, d, s, l, c, 8)[1].tolist() == [1, 0]
 
 
+def test_merge_packed_negative_zero_unturned():
+    """rot 0: a -0.0 corner and a -0.0 landmark in a content at the canvas's origin map as float32((float64(-0.0) - 0) * sx + sx0) = +0.0,
+    bit for bit (the turned merges have this case in tests/test_packrot.py)."""
+    d, s, l, c = canvas_table(1, 4, {0: [(-0.0, -0.0, 8, 6, 0.7)]})
+    l[0, 0, :2] = -0.0
+    want, gc, _ = check_merge(SHARED, 2, (64, 96), (64, 64), d, s, l, c, 4)
+    assert gc.tolist() == [1, 0] and want[0][0][0].tolist() == [0, 0, 24, np.float32(6 * (64 / 22)), np.float32(0.7)]
+    assert not np.signbit(want[0][0][0, :2]).any() and not np.signbit(want[0][1][0, :2]).any()
+
+
 def test_merge_packed_truncated_canvas_flags_every_frame_on_it():
     frame, net = (64, 96), (64, 64)
     places = SHARED + [(2, 1, 0, 0, 96, 64, 0, 0, 32, 22), (3, 1, 0, 0, 96, 64, 32, 22, 32, 22), (3, 2, 0, 0, 96, 64, 0, 0, 64, 43)]

@@ -14,6 +14,7 @@ import pytest
 
 import centerface_amd as cfa
 from centerface_amd import ops
+import csrc_text
 from pack_cases import WORKED_GUTTER_0, WORKED_GUTTER_16, WORKED_VIEWS, pack_views_ref, unpacked_places
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,10 +51,14 @@ def test_pack_symbols_and_struct_match_the_header():
 
 
 def test_the_packed_kernels_stand_beside_the_old_ones():
-    src = open(os.path.join(CSRC, "cf_views.hip")).read()
-    assert "cut_packed_kernel" in src and "packed_collect_kernel" in src and "cut_views_kernel" in src and "views_collect_kernel" in src
-    assert src.count("launch_nms_stages(") == 2                                  # the NMS stages run unchanged behind either collect
-    assert not re.search(r"\batomic\w*\s*\(", src, flags=re.I) and "__hip_atomic" not in src      # the compactions are prefix sums
+    texts = csrc_text.unit("cf_views.hip")
+    src = texts["cf_views.hip"]
+    assert "cut_packed_kernel" in src and "cut_views_kernel" in src
+    # the rows of either go through the one collect kernel (an Items type each) and the one launch of the NMS stages, unchanged
+    merge = csrc_text.unit("cf_tiles.hip")
+    csrc_text.assert_one_statement(merge, ("collect_rows_kernel<PlacedItems, 0>", "collect_rows_kernel<ViewItems, 0>", "struct PlacedItems", "struct ViewItems"))
+    assert merge["cf_tiles.hip"].count("launch_nms_stages(") == 1 and "launch_nms_stages(" not in src
+    csrc_text.assert_one_statement(texts, ())                                    # the list and the compactions are prefix sums
 
 
 def test_the_documents_state_what_is_built_and_its_limits():

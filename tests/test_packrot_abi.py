@@ -11,6 +11,7 @@ import pytest
 
 import centerface_amd as cfa
 from centerface_amd import ops
+import csrc_text
 from packrot_cases import ROTS, merge_packed_rot_ref, packed_rot_canvases_ref, upright_hw
 from rot_cases import rot_geometry_ref, rot_ref, unrot_ref
 
@@ -43,10 +44,19 @@ def test_packrot_symbols_match_the_header():
 
 
 def test_the_rotated_kernels_have_a_file_of_their_own():
-    src = open(os.path.join(CSRC, "cf_views_rot.hip")).read()
-    assert "cut_packed_half_kernel" in src and "cut_packed_quarter_kernel" in src and "packed_collect_rot_kernel" in src
-    assert src.count("launch_nms_stages(") == 1                                  # the NMS stages run unchanged behind the collect
+    texts = csrc_text.unit("cf_views_rot.hip")
+    src = texts["cf_views_rot.hip"]
+    assert "cut_packed_quarter_kernel" in src and "launch_cut_packed_quarter(" in src
+    # rot 180 is the packed cutter's own kernel on mirrored taps; the turned rows go through the one collect kernel, the NMS stages unchanged
+    views = open(os.path.join(CSRC, "cf_views.hip")).read()
+    assert "cut_packed_kernel<SRC, VF, 2>" in views and "launch_cut_packed_quarter(" in views
+    merge = csrc_text.unit("cf_tiles.hip")
+    for rot in (1, 2, 3):
+        assert "collect_rows_kernel<PlacedItems, %d>" % rot in merge["cf_tiles.hip"]
+    assert "turn_point<ROT>" in merge["cf_collect.h"] and merge["cf_tiles.hip"].count("launch_nms_stages(") == 1
     assert not re.search(r"atomic", src, flags=re.I)                             # the list and the compaction are prefix sums
+    csrc_text.assert_one_statement(texts, ())
+    csrc_text.assert_one_statement(merge, ())
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^SRCS\s*=.*\bcf_views_rot\.hip\b", mk, flags=re.M)
     assert re.search(r"^EXTRA_cf_views_rot\s*=.*-ffp-contract=off", mk, flags=re.M)

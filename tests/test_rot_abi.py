@@ -10,6 +10,7 @@ import pytest
 
 import centerface_amd as cfa
 from centerface_amd import ops
+import csrc_text
 from fit_cases import WORKED, fit_geometry_ref
 from rot_cases import ROTS, rot_geometry_ref, rot_ref, unrot_ref, upright
 
@@ -40,11 +41,16 @@ def test_rot_symbols_and_struct_match_the_header():
     assert (o.rot, o.stretch, o.fit.anchor, o.fit.upscale, list(o.fit.fill)) == (180, 0, 1, 0, [1, 2, 3, 0])
     assert L.rot_opts(0, {}).stretch == 0                                   # an empty dict is a fit with the defaults, not a stretch
     # the new file shares the one statement of the resize and of the conversion and is built without contraction
-    src = open(os.path.join(CSRC, "cf_rot.hip")).read()
-    assert '#include "cf_cvresize.h"' in src and '#include "cf_yuvmath.h"' in src and '#include "cf_fitpx.h"' in src
-    assert "cv_linear_coeffs(" in src and "cv_linear_vpass(" in src and "yuv_px(" in src and "pack_bgr(" in src
-    assert "1220542" not in src and not re.search(r"\brintf\b", src) and "__builtin_amdgcn_perm" not in src
-    assert "launch_fit_frames(" in src                                      # rot 0 is the fit's own launch
+    # (through the cutters' shared header: required of the union, refused in every file of it)
+    texts = csrc_text.unit("cf_rot.hip")
+    src = texts["cf_rot.hip"]
+    assert '#include "cf_cutpx.h"' in src
+    csrc_text.assert_one_statement(texts, ('#include "cf_cvresize.h"', '#include "cf_yuvmath.h"', "cv_linear_coeffs(", "cv_linear_vpass(", "yuv_px(", "pack_bgr("))
+    assert "__builtin_amdgcn_perm" not in src                               # the byte-selecting pack is stated once, in the header
+    # rot 0 and rot 180 are the fit's own kernel and launch; the fit's launch hands the quarter turns to this file
+    fit = open(os.path.join(CSRC, "cf_fit.hip")).read()
+    assert "fit_frames_kernel<SRC, VF, 0>" in fit and "fit_frames_kernel<SRC, VF, 2>" in fit and "launch_rot_quarter(" in fit
+    assert "launch_rot_quarter(" in src and "rot_quarter_kernel" in src and "rot_half_kernel" not in src
     mk = open(os.path.join(CSRC, "Makefile")).read()
     srcs = re.search(r"^SRCS\s*=(.*)$", mk, flags=re.M).group(1).split()
     assert "cf_rot.hip" in srcs and re.search(r"EXTRA_cf_rot\s*=\s*-ffp-contract=off", mk)

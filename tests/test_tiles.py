@@ -225,6 +225,19 @@ def test_merge_duplicates_ties_and_the_edge_rule():
     assert check_merge(TWO, frame, net, d, s, l, c, 4)[1].tolist() == [1]
 
 
+def test_merge_has_no_centre_rule_and_maps_a_negative_zero():
+    """The tile merge drops by the edge rule alone: a row of tile 0 whose centre lies left of the canvas (x1 = -40, x2 = 10) has the
+    frame's left side beside it and stays, where the views merge would drop it.  A -0.0 corner and a -0.0 landmark map as
+    float32(float64(-0.0) * sx + x0): +0.0 in tile 0 (x0 = 0), bit for bit."""
+    frame, net = (64, 96), (64, 64)
+    d, s, l, c = table(1, 2, 4, {(0, 0): [(-40, 10, 10, 30, 0.9), (-0.0, 40, 20, 60, 0.8)]})
+    l[0, 0, 1, :2] = -0.0
+    assert np.signbit(d[0, 0, 1, 0]) and np.signbit(l[0, 0, 1, 0])
+    want, gc, _ = check_merge(TWO, frame, net, d, s, l, c, 4)
+    assert gc.tolist() == [2] and want[0][0][0].tolist() == [-40, 10, 10, 30, np.float32(0.9)]
+    assert want[0][0][1, 0] == 0 and not np.signbit(want[0][0][1, 0]) and not np.signbit(want[0][1][1, :2]).any()
+
+
 def test_merge_ios_against_iou_flags_and_truncation():
     frame, net = (256, 384), (256, 256)
     rects = [(0, 0, 256, 256), (128, 0, 256, 256)]

@@ -259,6 +259,18 @@ def test_merge_views_centre_rule_non_finite_corners_and_flags():
     assert gc.tolist() == [1, 3] and gf.tolist() == [0, 1]
 
 
+def test_merge_views_negative_zero_and_a_centre_outside_the_canvas():
+    """Unturned: a -0.0 corner and a -0.0 landmark of a view whose content starts at the canvas's origin map as
+    float32((float64(-0.0) - 0) * sx + sx0) = +0.0, bit for bit; a row whose centre lies left of the canvas is dropped by the centre
+    rule (the tile merge, which has none, keeps that row)."""
+    frame, net = (64, 96), (64, 64)
+    d, s, l, c = table(1, 2, 4, {(0, 0): [(-0.0, -0.0, 8, 6, 0.7), (-40, 10, 10, 30, 0.9)]})
+    l[0, 0, 0, :2] = -0.0
+    want, gc, _ = check_merge(TILES, frame, net, d, s, l, c, 4)
+    assert gc.tolist() == [1] and want[0][0][0].tolist() == [0, 0, 8, 6, np.float32(0.7)]
+    assert not np.signbit(want[0][0][0, :2]).any() and not np.signbit(want[0][1][0, :2]).any()
+
+
 def test_merge_views_across_scales_ties_and_truncation():
     frame, net = (64, 96), (64, 64)
     views = TILES[:1] + LEVELS[1:]

@@ -13,6 +13,7 @@ import pytest
 
 import centerface_amd as cfa
 from centerface_amd import ops
+import csrc_text
 from view_cases import WORKED, view_layout_ref
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,12 +64,16 @@ def test_view_symbols_and_structs_match_the_header():
 
 
 def test_the_cutter_holds_one_statement_of_resize_and_conversion_and_no_atomic():
-    src = open(os.path.join(CSRC, "cf_views.hip")).read()
-    assert '#include "cf_cvresize.h"' in src and '#include "cf_yuvmath.h"' in src
-    assert "cv_linear_coeffs(" in src and "cv_linear_vpass(" in src and "yuv_px(" in src
-    assert "1220542" not in src and not re.search(r"\brintf\b", src) and "2048" not in src       # no second statement of either
-    assert not re.search(r"\batomic\w*\s*\(", src, flags=re.I) and "__hip_atomic" not in src
-    assert "cut_views_kernel" in src and "views_collect_kernel" in src and "launch_nms_stages(" in src
+    # (through the cutters' shared header: required of the union, refused in every file of it)
+    texts = csrc_text.unit("cf_views.hip")
+    src = texts["cf_views.hip"]
+    assert '#include "cf_cutpx.h"' in src
+    csrc_text.assert_one_statement(texts, ('#include "cf_cvresize.h"', '#include "cf_yuvmath.h"', "cv_linear_coeffs(", "cv_linear_vpass(", "yuv_px("))
+    assert all("2048" not in text for text in texts.values())
+    # the views' rows go through the one collect kernel and the one launch of the NMS stages, which live with the tile merge
+    merge = csrc_text.unit("cf_tiles.hip")
+    csrc_text.assert_one_statement(merge, ("collect_rows_kernel<ViewItems, 0>", "struct ViewItems", "launch_nms_stages("))
+    assert "cut_views_kernel" in src and "launch_nms_stages(" not in src
     # the tile cutter and the fit kernel were not edited into it: they still stand where they stood
     assert "cut_tiles_kernel" in open(os.path.join(CSRC, "cf_tiles.hip")).read() and "fit_frames_kernel" in open(os.path.join(CSRC, "cf_fit.hip")).read()
     mk = open(os.path.join(CSRC, "Makefile")).read()

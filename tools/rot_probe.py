@@ -12,7 +12,7 @@ What is timed, after warming up every launch involved, with HIP events on the en
   ratio_90_to_0_<fmt>         rot90_<fmt>_us / rot0_<fmt>_us (medians)
   unfit_rot<R>_us             cf_unfit_rows (device form) alone behind a rot = R forward and a threshold decode with max_out = 64
 A kernel-level cross-check is a `rocprofv3 --kernel-trace --stats` run of `rot_probe.py --short` (kernels: fit_frames_kernel,
-rot_half_kernel, rot_quarter_kernel, unfit_rows_kernel).  One JSON line."""
+fit_frames_kernel, rot_quarter_kernel, unfit_rows_kernel).  One JSON line."""
 import json
 import os
 import sys

@@ -16,7 +16,7 @@ and with HIP events on the engine's main stream around REP back-to-back calls:
   decode_us         the threshold decode alone (collect + rank + mask + sweep over 63 images), the yardstick for the merge
 The cutter and the convert + resize kernel have no entry point of their own: their kernel times come from a
 `rocprofv3 --kernel-trace --stats` run of `tile_probe.py --short` (kernels: cut_tiles_kernel, yuv_bgr_resize_kernel,
-merge_collect_kernel).  One JSON line."""
+collect_rows_kernel).  One JSON line."""
 import json
 import os
 import sys

@@ -14,7 +14,7 @@ batch, per window:
   decode_us           that threshold decode of the 160 canvases alone, for scale
 The network at batch 160 takes milliseconds and the cutters tens of microseconds, so the spread of the differences is printed beside
 every median: read the two together.  No threshold is set here.  A kernel-level cross-check is a kernel-trace run of
-`view_probe.py --short` (kernels: cut_views_kernel, cut_tiles_kernel, fit_frames_kernel, views_collect_kernel, merge_collect_kernel).
+`view_probe.py --short` (kernels: cut_views_kernel, cut_tiles_kernel, fit_frames_kernel, collect_rows_kernel).
 One JSON line; `--md` prints the table of profiles/views.md instead."""
 import json
 import os

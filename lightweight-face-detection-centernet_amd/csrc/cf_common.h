@@ -271,6 +271,11 @@ constexpr unsigned CF_OOB = 0x80000000u;
 __device__ __forceinline__ cf_rsrc_t cf_rsrc(const void* base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);      // flags: 32-bit raw data format
 }
+// the launcher's side of that: a tensor of `pixels` rows of `rowbytes` may be addressed through a descriptor with CF_OOB offsets and
+// 24-bit multiplies by the pitch of a map row (`width` pixels) when it is below 2 GiB and a map row of it below 16 MiB
+static inline bool cf_rsrc_fits(size_t pixels, size_t width, size_t rowbytes) {
+    return pixels * rowbytes < ((size_t)1 << 31) && width * rowbytes < ((size_t)1 << 24);
+}
 __device__ __forceinline__ u32x4 cf_bload16(cf_rsrc_t r, unsigned off) {
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
 }
@@ -448,6 +453,36 @@ static inline uint16_t host_f32_to_bf16(float f) {
 }
 static inline float host_bf16_to_f32(uint16_t b) {
     uint32_t u = (uint32_t)b << 16; float f; __builtin_memcpy(&f, &u, 4); return f;
+}
+// host-side fp32 -> fp16: the depthwise taps of the v_dot2c and matrix-core families (cf_mbconv2.hip, cf_mbconv3.hip, cf_stem0.hip)
+static inline uint16_t host_f32_to_f16(float f) {         // round-to-nearest-even, saturating
+    uint32_t u; __builtin_memcpy(&u, &f, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    const int32_t exp = (int32_t)((u >> 23) & 0xff) - 127 + 15;
+    uint32_t man = u & 0x7fffffu;
+    if (((u >> 23) & 0xff) == 0xff) return (uint16_t)(sign | 0x7c00u | (man ? 0x200u : 0));
+    if (exp >= 31) return (uint16_t)(sign | 0x7bffu);
+    if (exp <= 0) {
+        if (exp < -10) return (uint16_t)sign;
+        man |= 0x800000u;
+        const int shift = 14 - exp;
+        uint32_t half = man >> shift;
+        const uint32_t rem = man & ((1u << shift) - 1), mid = 1u << (shift - 1);
+        if (rem > mid || (rem == mid && (half & 1))) ++half;
+        return (uint16_t)(sign | half);
+    }
+    uint32_t half = ((uint32_t)exp << 10) | (man >> 13);
+    const uint32_t rem = man & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (half & 1))) ++half;
+    if (half >= 0x7c00u) half = 0x7bffu;
+    return (uint16_t)(sign | half);
+}
+// channel held by MFMA row-slot i of n-block nb of a 32x32 accumulator block: lane (pixel, h) accumulator register r  <->  row
+// i = (r & 3) + 8 (r >> 2) + 4 h  <->  channel nb * 32 + h * 16 + r (the weight packers of every 32x32 GEMM family)
+static inline int slot_channel(int nb, int i) {
+    int h = (i >> 2) & 1;
+    int r = (i & 3) + 4 * (i >> 3);
+    return nb * 32 + h * 16 + r;
 }
 // host: four fp32 weights -> one 16-byte split fragment [hi0..3 | lo0..3] (CfMma<sp32_t>)
 static inline void pack_split4(const float* src, void* dst16) {

@@ -20,11 +20,6 @@ namespace cf {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 mfma_bf16x8;
 
-static inline int slot_channel(int nb, int i) {
-    int h = (i >> 2) & 1;
-    int r = (i & 3) + 4 * (i >> 3);
-    return nb * 32 + h * 16 + r;
-}
 // chunks per kernel row (3 pixels x 24 ch) and MFMA steps per kernel row
 static inline int cpd(int dtype) { return dtype != 1 ? 18 : 9; }
 static inline int spd(int dtype) { return dtype != 1 ? 9 : 5; }

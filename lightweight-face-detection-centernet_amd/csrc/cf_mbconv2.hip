@@ -36,34 +36,6 @@ typedef __attribute__((ext_vector_type(8))) uint32_t u32x8;
 typedef __attribute__((ext_vector_type(2))) __fp16 f16x2;
 #define CF_AS4 __attribute__((address_space(4)))
 
-static inline int slot_channel2(int nb, int i) {
-    int h = (i >> 2) & 1;
-    int r = (i & 3) + 4 * (i >> 3);
-    return nb * 32 + h * 16 + r;
-}
-
-static inline uint16_t host_f32_to_f16(float f) {       // round-to-nearest-even, saturating
-    uint32_t u; __builtin_memcpy(&u, &f, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const int32_t exp = (int32_t)((u >> 23) & 0xff) - 127 + 15;
-    uint32_t man = u & 0x7fffffu;
-    if (((u >> 23) & 0xff) == 0xff) return (uint16_t)(sign | 0x7c00u | (man ? 0x200u : 0));
-    if (exp >= 31) return (uint16_t)(sign | 0x7bffu);
-    if (exp <= 0) {
-        if (exp < -10) return (uint16_t)sign;
-        man |= 0x800000u;
-        const int shift = 14 - exp;
-        uint32_t half = man >> shift;
-        const uint32_t rem = man & ((1u << shift) - 1), mid = 1u << (shift - 1);
-        if (rem > mid || (rem == mid && (half & 1))) ++half;
-        return (uint16_t)(sign | half);
-    }
-    uint32_t half = ((uint32_t)exp << 10) | (man >> 13);
-    const uint32_t rem = man & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (half & 1))) ++half;
-    if (half >= 0x7c00u) half = 0x7bffu;
-    return (uint16_t)(sign | half);
-}
 
 // acc += w.lo * e.lo + w.hi * e.hi (fp16 inputs, fp32 accumulate); w is wave-uniform (SGPR)
 // (the builtin, not inline asm: DOT results have read-after-write wait states the compiler must see)
@@ -895,7 +867,7 @@ void mb2_pack_weights(int, const MbGeom& g, int Cin, int hid, int Cout, int k, c
             for (int j = 0; j < g.HALF; ++j)
                 for (int lane = 0; lane < 64; ++lane) {
                     const int i = lane & 31, hh = lane >> 5;
-                    const int co = slot_channel2(nbo, i);
+                    const int co = slot_channel(nbo, i);
                     if (co >= Cout) continue;
                     const int hc = q * g.HC + (hh * g.HALF + j) * 8;
                     uint16_t* dst = (uint16_t*)((char*)wproj_host + ((((size_t)nbo * g.nq + q) * g.HALF + j) * 64 + lane) * 16);

@@ -82,31 +82,14 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
     const int ox0 = txi * TOW, oy0 = tyi * TOH, b = blockIdx.z;
     const int grp = blockIdx.y;
 
-    {
-        const char* srcx = (const char*)p.wexp + (size_t)grp * WXB;
-        for (int c = wave; c < WXB / 1024; c += NW)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcx + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(Wst + c * 1024), 16, 0, 0);
-    }
+    CF_MX_STAGE((const char*)p.wexp + (size_t)grp * WXB, Wst, WXB);
     asm volatile("" ::: "memory");        // the loads below stay behind the DMAs in program order (cf_sync_lds_dma_keep counts on it)
     // Toeplitz A operands of this round ([2 channel quads][KS][2 k-steps][lane] x 8 B): an LDS copy next to the expand
     // weights (ALDS: 81-110 VGPRs, + 6 / 10 KB of LDS) or resident register pairs (132-148 VGPRs)
     char* Ats = Wst + WXB;
     u32x2 A[ALDS ? 1 : 2][ALDS ? 1 : KS][2];
-    if constexpr (ALDS) {
-        const char* srca = (const char*)p.wdw + (size_t)grp * G::ATB;
-        for (int c = wave; c < G::ATB / 1024; c += NW)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srca + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(Ats + c * 1024), 16, 0, 0);
-    } else {
-        const u32x2* at = reinterpret_cast<const u32x2*>(p.wdw) + (size_t)grp * (2 * KS * 2) * 64 + lane;
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int ky = 0; ky < KS; ++ky)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) A[q][ky][ks] = at[((q * KS + ky) * 2 + ks) * 64];
-    }
+    if constexpr (ALDS) CF_MX_STAGE((const char*)p.wdw + (size_t)grp * G::ATB, Ats, G::ATB);
+    else mx_load_taps<2 * KS * 2>(&A[0][0][0], reinterpret_cast<const u32x2*>(p.wdw) + (size_t)grp * (2 * KS * 2) * 64 + lane);
     asm volatile("" ::: "memory");
     const char* xbase = (const char*)p.x + (size_t)b * p.Hin * p.Win * p.Cin * 2;
     const unsigned rowbytes = (unsigned)p.Cin * 2;
@@ -193,6 +176,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
         const bool more = it + 1 < MAXI && ib + NW < NIB;
         bool vn = false;
         if (more) { if (abl & 8) { for (int j = 0; j < JX; ++j) xn[j] = xa[j]; vn = va; } else vn = load_x(ib + NW, xn); }
+        // (written out, like every expand block: cf_mx.h says what a shared function cost)
         f32x16 a;
 #pragma unroll
         for (int r = 0; r < 16; ++r) a[r] = 0.0f;
@@ -203,17 +187,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
             a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mfma_bf16x8, xa[j]),
                                                         __builtin_bit_cast(mfma_bf16x8, wv), a, 0, 0, 0);
         }
-        char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)CP + pl * 8;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x2 u0, u1; u0.x = a[4 * t]; u0.y = a[4 * t + 1]; u1.x = a[4 * t + 2]; u1.y = a[4 * t + 3];
-            f32x2 y0 = u0, y1 = u1;
-            if (!(abl & 4)) { y0 = swish2_pre(u0); y1 = swish2_pre(u1); }
-            u32x2 d;
-            d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-            d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-            *reinterpret_cast<u32x2*>(ecell + 2 * t * CP) = d;
-        }
+        mx_block_store<CP>(E, ib, h, pl, a, !(abl & 4));
         if (more) mask_x(xn, vn);
     }
     __syncthreads();
@@ -235,7 +209,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
         else mx_depthwise<KS, IWQ, CP>(bb, reinterpret_cast<const u32x2 (*)[KS][2]>(A), acc);
         }
         // a = -log2(e) * depthwise output -> Swish, leftover factor out again (the project GEMM has plain weights)
-        if (!(abl & 2))
+        if (!(abl & 2))         // (mx_swish_acc<8, true> of cf_mx.h: its own text here, other assembly for all 36 instances through the function)
 #pragma unroll
         for (int g = 0; g < 8; ++g)
 #pragma unroll
@@ -259,9 +233,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
                 const unsigned off = __umul24(opix0 >> 5, yblk) + ((opix0 & 31u) << 4) + (unsigned)chunk * 512u;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    u32x4 o;
-                    o.x = packb(acc[0][i], acc[1][i]); o.y = packb(acc[2][i], acc[3][i]);
-                    o.z = packb(acc[4][i], acc[5][i]); o.w = packb(acc[6][i], acc[7][i]);
+                    const u32x4 o = mx_pack8(acc, i);
                     st16(yb + off + 16 * i, o);
                 }
             } else {
@@ -269,9 +241,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     if (!q4 && gx0 + i >= p.Wout) break;
-                    u32x4 o;
-                    o.x = packb(acc[0][i], acc[1][i]); o.y = packb(acc[2][i], acc[3][i]);
-                    o.z = packb(acc[4][i], acc[5][i]); o.w = packb(acc[6][i], acc[7][i]);
+                    const u32x4 o = mx_pack8(acc, i);
                     const unsigned opix = opix0 + i;
                     st16(yb + (YB ? off0 + __umul24(opix >> 5, yblk) + ((opix & 31u) << 4) : off0 + (unsigned)i * yrow), o);
                 }
@@ -281,9 +251,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mx_kernel(MbParams p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (gx0 + i >= p.Wout) break;
-            u32x4 o;
-            o.x = packb(acc[0][i], acc[1][i]); o.y = packb(acc[2][i], acc[3][i]);
-            o.z = packb(acc[4][i], acc[5][i]); o.w = packb(acc[6][i], acc[7][i]);
+            const u32x4 o = mx_pack8(acc, i);
             const size_t opix = opix0 + i;
             if (abl & 32) {         // timing experiment (results invalid): the same bytes, 1 KB of consecutive addresses per store instruction
                 const size_t region = (((size_t)b * gridDim.x + blockIdx.x) * gridDim.y + grp) * (size_t)(TOH * TOW * 64);
@@ -362,13 +330,7 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
     const char* xbase = (const char*)p.x + (size_t)b * p.Hin * p.Win * p.Cin * 2;
     const unsigned rowbytes = (unsigned)p.Cin * 2;
 
-    auto stage_weights = [&](int q) {
-        char* dst = Wst + (q & 1) * WXB;
-        const char* srcx = (const char*)p.wexp + (size_t)q * WXB;
-        for (int c = wave; c < WXB / 1024; c += NW)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcx + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(dst + c * 1024), 16, 0, 0);
-    };
+    auto stage_weights = [&](int q) { CF_MX_STAGE((const char*)p.wexp + (size_t)q * WXB, Wst + (q & 1) * WXB, WXB); };
 
     // X fragments of this wave's halo pixel blocks (MFMA A operand: lane = pixel, 8 contiguous Cin per half): resident, or
     // (XRELOAD) fetched again from L2 at the top of every round; clamped address + zero select = ZeroPad2d
@@ -453,15 +415,7 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
         // Toeplitz operands + project fragments of this round (and the X fragments when reloaded): requested before the barrier,
         // used after it -- they stay in flight across it, only the older expand-weight DMA is drained
         u32x2 A[ALDS ? 1 : 2][ALDS ? 1 : KS][2];
-        if constexpr (!ALDS) {
-            const u32x2* at = reinterpret_cast<const u32x2*>(p.wdw) + (size_t)q * (2 * KS * 2) * 64 + lane;
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int ky = 0; ky < KS; ++ky)
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) A[a][ky][ks] = at[((a * KS + ky) * 2 + ks) * 64];
-        }
+        if constexpr (!ALDS) mx_load_taps<2 * KS * 2>(&A[0][0][0], reinterpret_cast<const u32x2*>(p.wdw) + (size_t)q * (2 * KS * 2) * 64 + lane);
         u32x4 wpc[NMB];
 #pragma unroll
         for (int mb = 0; mb < NMB; ++mb) wpc[mb] = ld16((const char*)p.wproj + (((size_t)q * NMB + mb) * 64 + lane) * 16);
@@ -469,12 +423,7 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
         cf_sync_lds_dma_keep<(ALDS ? 0 : 2 * KS * 2) + NMB + (XRELOAD ? MAXI * JX : 0)>();   // previous round's depthwise done with E / the table; expand weights landed
         // this round's Toeplitz table -> LDS under the expand phase (drained before the next barrier).  Staging it one round
         // ahead in a second buffer was measured: no gain (0.192 vs 0.189 ms on layer1.1), 6-10 KB more LDS
-        if constexpr (ALDS) {
-            const char* srca = (const char*)p.wdw + (size_t)q * G::ATB;
-            for (int c = wave; c < G::ATB / 1024; c += NW)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srca + c * 1024 + lane * 16),
-                                                 (__attribute__((address_space(3))) void*)(Ats + c * 1024), 16, 0, 0);
-        }
+        if constexpr (ALDS) CF_MX_STAGE((const char*)p.wdw + (size_t)q * G::ATB, Ats, G::ATB);
         const char* Atq = Ats;
 
         // ---- phase 1: expand + Swish -> quad cells
@@ -491,18 +440,8 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
                 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mfma_bf16x8, xf[t][j]),
                                                             __builtin_bit_cast(mfma_bf16x8, wv), a, 0, 0, 0);
             }
-            if constexpr (DEAL) { halo_deal_store<DKS, CP8>(E, wave, t, h, pl, a); continue; }
-            char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)CP8 + pl * 8;
-#pragma unroll
-            for (int tq = 0; tq < 4; ++tq) {
-                f32x2 u0, u1; u0.x = a[4 * tq]; u0.y = a[4 * tq + 1]; u1.x = a[4 * tq + 2]; u1.y = a[4 * tq + 3];
-                f32x2 y0 = u0, y1 = u1;
-                if (!(abl & 4)) { y0 = swish2_pre(u0); y1 = swish2_pre(u1); }
-                u32x2 d;
-                d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-                d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-                *reinterpret_cast<u32x2*>(ecell + 2 * tq * CP8) = d;
-            }
+            if constexpr (DEAL) halo_deal_store<DKS, CP8>(E, wave, t, h, pl, a);
+            else mx_block_store<CP8>(E, ib, h, pl, a, !(abl & 4));
         }
         cf_sync_lds_dma();          // E complete; the operand table (DMA) landed
         if (q + 1 < nq) stage_weights(q + 1);
@@ -520,20 +459,10 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
             else if constexpr (ALDS) mx_depthwise_lds<KS, IWQ, CP8>(E + qcell[sw] * (unsigned)CP8 + kg * 64, Atq + lane * 8, acc);
             else mx_depthwise<KS, IWQ, CP8>(E + qcell[sw] * (unsigned)CP8 + kg * 64, reinterpret_cast<const u32x2 (*)[KS][2]>(A), acc);
             }
-            if (!(abl & 2))
-#pragma unroll
-            for (int g = 0; g < 8; ++g)
-#pragma unroll
-                for (int i = 0; i < 4; i += 2) {
-                    f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-                    const f32x2 y = swish2_pre(u);
-                    acc[g][i] = y.x; acc[g][i + 1] = y.y;
-                }
+            if (!(abl & 2)) mx_swish_acc<8>(acc);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                u32x4 d;
-                d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
-                d.z = packb(acc[4][i], acc[5][i]); d.w = packb(acc[6][i], acc[7][i]);
+                const u32x4 d = mx_pack8(acc, i);
                 if (abl & 8) { pacc[sw][i][0][0] += __uint_as_float(d.x ^ d.y ^ d.z ^ d.w); continue; }
 #pragma unroll
                 for (int mb = 0; mb < NMB; ++mb)
@@ -549,13 +478,7 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
         typedef __attribute__((ext_vector_type(4))) __bf16 mfma_bf16x4;
         const u32x4 wv = ld16((const char*)p.wexp + (size_t)nq * WXB + lane * 16);
         u32x2 A4[KS][2];
-        {
-            const u32x2* at = reinterpret_cast<const u32x2*>(p.wdw) + (size_t)nq * (2 * KS * 2) * 64 + lane;
-#pragma unroll
-            for (int ky = 0; ky < KS; ++ky)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) A4[ky][ks] = at[(ky * 2 + ks) * 64];
-        }
+        mx_load_taps<KS * 2>(&A4[0][0], reinterpret_cast<const u32x2*>(p.wdw) + (size_t)nq * (2 * KS * 2) * 64 + lane);
         u32x2 wp4[NMB];
 #pragma unroll
         for (int mb = 0; mb < NMB; ++mb)
@@ -576,12 +499,7 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
             for (int i = 0; i < NSB; ++i) {
                 f32x4 a4 = {0.0f, 0.0f, 0.0f, 0.0f};
                 a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xv[i]), __builtin_bit_cast(mfma_bf16x8, wv), a4, 0, 0, 0);
-                f32x2 u0, u1; u0.x = a4[0]; u0.y = a4[1]; u1.x = a4[2]; u1.y = a4[3];
-                const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-                u32x2 d;
-                d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-                d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-                *reinterpret_cast<u32x2*>(ecell + i * (NW * 4 * CP4)) = d;
+                mx_cell_store(ecell + i * (NW * 4 * CP4), a4[0], a4[1], a4[2], a4[3]);
             }
         } else
         for (int sb = wave; sb < NIB * 2; sb += NW) {               // 16-pixel sub-blocks = 4 quads each
@@ -595,12 +513,7 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
             xv.x = valid ? xv.x : 0u; xv.y = valid ? xv.y : 0u; xv.z = valid ? xv.z : 0u; xv.w = valid ? xv.w : 0u;
             f32x4 a4 = {0.0f, 0.0f, 0.0f, 0.0f};
             a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xv), __builtin_bit_cast(mfma_bf16x8, wv), a4, 0, 0, 0);
-            f32x2 u0, u1; u0.x = a4[0]; u0.y = a4[1]; u1.x = a4[2]; u1.y = a4[3];
-            const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-            u32x2 d;
-            d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-            d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-            *reinterpret_cast<u32x2*>(E + (unsigned)(sb * 4 + kc) * (unsigned)CP4 + (lane & 15) * 8) = d;
+            mx_cell_store(E + (unsigned)(sb * 4 + kc) * (unsigned)CP4 + (lane & 15) * 8, a4[0], a4[1], a4[2], a4[3]);
         }
         __syncthreads();
 #pragma unroll
@@ -613,24 +526,12 @@ __global__ __launch_bounds__(NW * 64) void mbconv_mx_kernel(MbParams p) {
             for (int st = 0; st < KS * 2; ++st) {
                 const char* bs = bb + ((st >> 1) * IWQ + (st & 1)) * CP4;
                 const u32x4 b0 = ld16(bs), b1 = ld16(bs + 16);
-                const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, A4[st >> 1][st & 1]);
-                u32x2 t0, t1, t2, t3; t0.x = b0.x; t0.y = b0.y; t1.x = b0.z; t1.y = b0.w; t2.x = b1.x; t2.y = b1.y; t3.x = b1.z; t3.y = b1.w;
-                CF_MX_MFMA(acc[0], av, __builtin_bit_cast(mfma_f16x4, t0), 0);
-                CF_MX_MFMA(acc[1], av, __builtin_bit_cast(mfma_f16x4, t1), 1);
-                CF_MX_MFMA(acc[2], av, __builtin_bit_cast(mfma_f16x4, t2), 2);
-                CF_MX_MFMA(acc[3], av, __builtin_bit_cast(mfma_f16x4, t3), 3);
+                mx_mfma4(acc, A4[st >> 1][st & 1], b0, b1);
             }
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int i = 0; i < 4; i += 2) {
-                    f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-                    const f32x2 y = swish2_pre(u);
-                    acc[g][i] = y.x; acc[g][i + 1] = y.y;
-                }
+            mx_swish_acc<4>(acc);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                u32x2 d; d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
+                const u32x2 d = mx_pack4(acc, i);
 #pragma unroll
                 for (int mb = 0; mb < NMB; ++mb)
                     pacc[sw][i][mb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(mfma_bf16x4, wp4[mb]),
@@ -715,13 +616,7 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
     const char* xbase = (const char*)p.x + (size_t)b * p.Hin * p.Win * p.Cin * 2;
     const unsigned rowbytes = (unsigned)p.Cin * 2;
 
-    auto stage_weights = [&](int q) {
-        char* dst = Wst + (q & 1) * WXB;
-        const char* srcx = (const char*)p.wexp + (size_t)q * WXB;
-        for (int c = wave; c < WXB / 1024; c += NW)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcx + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(dst + c * 1024), 16, 0, 0);
-    };
+    auto stage_weights = [&](int q) { CF_MX_STAGE((const char*)p.wexp + (size_t)q * WXB, Wst + (q & 1) * WXB, WXB); };
     u32x4 xf[MAXI][JX];
     // MODE != 0: byte offset of halo pixel ip (cell order: a row's even x-quads first, then the odd ones) for a lane whose chunk starts at
     // lbase = tile0 + its chunk offset, as in mbconv_mx_kernel; a pixel past the halo lies at iy >= IH: folded into the row test
@@ -792,7 +687,7 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
         const char* wx = Wst + (q & 1) * WXB;
         // this half's Toeplitz operands + project fragments (+ X fragments when reloaded): requested before the barrier, in flight across it
         u32x2 Ah[ALDS ? 1 : KS][KSTEPS];
-        if constexpr (!ALDS) {
+        if constexpr (!ALDS) {       // (mx_load_taps, its own text: through the function the MODE 0 instance gains an instruction)
             const u32x2* at = reinterpret_cast<const u32x2*>(p.wdw) + ((size_t)q * 2 + half) * NSTEP * 64 + lane;
 #pragma unroll
             for (int ky = 0; ky < KS; ++ky)
@@ -805,12 +700,7 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
             wp4[mb] = *reinterpret_cast<const u32x2*>((const char*)p.wproj + ((((size_t)q * 2 + half) * NMB + mb) * 64 + lane) * 8);
         if constexpr (XRELOAD) load_x();
         cf_sync_lds_dma_keep<(ALDS ? 0 : NSTEP) + NMB + (XRELOAD ? MAXI * JX : 0)>();   // previous round's depthwise done with E / the table; expand weights landed
-        if constexpr (ALDS) {
-            const char* srca = (const char*)p.wdw + (size_t)q * G::ATB;
-            for (int c = wave; c < G::ATB / 1024; c += NW)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srca + c * 1024 + lane * 16),
-                                                 (__attribute__((address_space(3))) void*)(Ats + c * 1024), 16, 0, 0);
-        }
+        if constexpr (ALDS) CF_MX_STAGE((const char*)p.wdw + (size_t)q * G::ATB, Ats, G::ATB);
 
         // ---- phase 1: expand + Swish -> quad cells
 #pragma unroll
@@ -826,16 +716,7 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
                 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mfma_bf16x8, xf[t][j]),
                                                             __builtin_bit_cast(mfma_bf16x8, wv), a, 0, 0, 0);
             }
-            char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)CP8 + pl * 8;
-#pragma unroll
-            for (int tq = 0; tq < 4; ++tq) {
-                f32x2 u0, u1; u0.x = a[4 * tq]; u0.y = a[4 * tq + 1]; u1.x = a[4 * tq + 2]; u1.y = a[4 * tq + 3];
-                const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-                u32x2 d;
-                d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-                d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-                *reinterpret_cast<u32x2*>(ecell + 2 * tq * CP8) = d;
-            }
+            mx_block_store<CP8>(E, ib, h, pl, a);
         }
         cf_sync_lds_dma();          // E complete; the operand table landed
         if (q + 1 < nq) stage_weights(q + 1);
@@ -846,17 +727,10 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
             f32x4 acc[4];
             if constexpr (ALDS) mx_depthwise_half<KS, KSTEPS, IWQ, CP8>(E + qcell * (unsigned)CP8 + kg * 64 + half * 32, Ats + half * (NSTEP * 512) + lane * 8, acc);
             else mx_depthwise_half_reg<KS, KSTEPS, IWQ, CP8>(E + qcell * (unsigned)CP8 + kg * 64 + half * 32, reinterpret_cast<const u32x2 (*)[KSTEPS]>(Ah), acc);
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int i = 0; i < 4; i += 2) {
-                    f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-                    const f32x2 y = swish2_pre(u);
-                    acc[g][i] = y.x; acc[g][i + 1] = y.y;
-                }
+            mx_swish_acc<4>(acc);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                u32x2 d; d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
+                const u32x2 d = mx_pack4(acc, i);
 #pragma unroll
                 for (int mb = 0; mb < NMB; ++mb)
                     pacc[i][mb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(mfma_bf16x4, wp4[mb]),
@@ -869,13 +743,7 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
         // ---- last round: 16 hidden channels (4 groups x 4), done by the half-0 wave of each set (1 / 9 of the work at hid = 144)
         const u32x4 wv = ld16((const char*)p.wexp + (size_t)nq * WXB + lane * 16);
         u32x2 A4[KS][KSTEPS];
-        {
-            const u32x2* at = reinterpret_cast<const u32x2*>(p.wdw) + (size_t)nq * (2 * NSTEP) * 64 + lane;
-#pragma unroll
-            for (int ky = 0; ky < KS; ++ky)
-#pragma unroll
-                for (int ks = 0; ks < KSTEPS; ++ks) A4[ky][ks] = at[(ky * KSTEPS + ks) * 64];
-        }
+        mx_load_taps<NSTEP>(&A4[0][0], reinterpret_cast<const u32x2*>(p.wdw) + (size_t)nq * (2 * NSTEP) * 64 + lane);
         u32x2 wp4[NMB];
 #pragma unroll
         for (int mb = 0; mb < NMB; ++mb)
@@ -900,12 +768,7 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
                     if (i0 + u >= NSB) break;
                     f32x4 a4 = {0.0f, 0.0f, 0.0f, 0.0f};
                     a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xv[u]), __builtin_bit_cast(mfma_bf16x8, wv), a4, 0, 0, 0);
-                    f32x2 u0, u1; u0.x = a4[0]; u0.y = a4[1]; u1.x = a4[2]; u1.y = a4[3];
-                    const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-                    u32x2 d;
-                    d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-                    d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-                    *reinterpret_cast<u32x2*>(ecell + (i0 + u) * (NW * 4 * CP4)) = d;
+                    mx_cell_store(ecell + (i0 + u) * (NW * 4 * CP4), a4[0], a4[1], a4[2], a4[3]);
                 }
             }
         } else
@@ -921,12 +784,7 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
             xv.x = valid ? xv.x : 0u; xv.y = valid ? xv.y : 0u; xv.z = valid ? xv.z : 0u; xv.w = valid ? xv.w : 0u;
             f32x4 a4 = {0.0f, 0.0f, 0.0f, 0.0f};
             a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xv), __builtin_bit_cast(mfma_bf16x8, wv), a4, 0, 0, 0);
-            f32x2 u0, u1; u0.x = a4[0]; u0.y = a4[1]; u1.x = a4[2]; u1.y = a4[3];
-            const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-            u32x2 d;
-            d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-            d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-            *reinterpret_cast<u32x2*>(E + (unsigned)(sb * 4 + kc) * (unsigned)CP4 + (lane & 15) * 8) = d;
+            mx_cell_store(E + (unsigned)(sb * 4 + kc) * (unsigned)CP4 + (lane & 15) * 8, a4[0], a4[1], a4[2], a4[3]);
         }
         __syncthreads();
         if (half == 0) {
@@ -938,24 +796,12 @@ __global__ __launch_bounds__(256) void mbconv_mx2_kernel(MbParams p) {
             for (int st = 0; st < NSTEP; ++st) {
                 const char* bs = bb + ((st / KSTEPS) * IWQ + ((st % KSTEPS) & 1) * HQ + ((st % KSTEPS) >> 1)) * CP4;
                 const u32x4 b0 = ld16(bs), b1 = ld16(bs + 16);
-                const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, A4[st / KSTEPS][st % KSTEPS]);
-                u32x2 t0, t1, t2, t3; t0.x = b0.x; t0.y = b0.y; t1.x = b0.z; t1.y = b0.w; t2.x = b1.x; t2.y = b1.y; t3.x = b1.z; t3.y = b1.w;
-                CF_MX_MFMA(acc[0], av, __builtin_bit_cast(mfma_f16x4, t0), 0);
-                CF_MX_MFMA(acc[1], av, __builtin_bit_cast(mfma_f16x4, t1), 1);
-                CF_MX_MFMA(acc[2], av, __builtin_bit_cast(mfma_f16x4, t2), 2);
-                CF_MX_MFMA(acc[3], av, __builtin_bit_cast(mfma_f16x4, t3), 3);
+                mx_mfma4(acc, A4[st / KSTEPS][st % KSTEPS], b0, b1);
             }
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int i = 0; i < 4; i += 2) {
-                    f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-                    const f32x2 y = swish2_pre(u);
-                    acc[g][i] = y.x; acc[g][i + 1] = y.y;
-                }
+            mx_swish_acc<4>(acc);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                u32x2 d; d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
+                const u32x2 d = mx_pack4(acc, i);
 #pragma unroll
                 for (int mb = 0; mb < NMB; ++mb)
                     pacc[i][mb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(mfma_bf16x4, wp4[mb]),
@@ -1078,7 +924,7 @@ void mx_pack_taps(int nq, int k, const float* wd /*[hid][k*k]*/, uint32_t* out, 
                         uint16_t v[4];
                         for (int kk = 0; kk < 4; ++kk) {
                             const int kx = 4 * ks + kk - stride * i;
-                            v[kk] = (kx >= 0 && kx < k) ? host_f32_to_f16_3(wrow[kx]) : 0;
+                            v[kk] = (kx >= 0 && kx < k) ? host_f32_to_f16(wrow[kx]) : 0;
                         }
                         uint32_t* dst = out + ((((size_t)(r * 2 + q) * k + ky) * ksteps + ks) * 64 + lane) * 2;
                         dst[0] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);
@@ -1130,7 +976,7 @@ hipError_t fx_launch_t(hipStream_t s, const MbParams& p) {
     // 16 MiB; the timing experiments stay on the general kernel, as does CF_FRONT_MODE=0 (experiments build: A/B runs, digests of MODE 0)
     if constexpr (KS == 3 && JX == 2 && NMB == 2 && RESID && TOH == 16 && TOW == 16 && NW == 4 && TAIL16 && !XRELOAD && ALDS && !SB && (G::NIB * 2) % NW == 0) {
         static const int front = cf_ab_int("CF_FRONT_MODE", 1);
-        const bool small = front != 0 && abl == 0 && (size_t)p.B * p.Hin * p.Win * p.Cin * 2 < ((size_t)1 << 31) && (size_t)p.Win * p.Cin * 2 < ((size_t)1 << 24);
+        const bool small = front != 0 && abl == 0 && cf_rsrc_fits((size_t)p.B * p.Hin * p.Win, p.Win, (size_t)p.Cin * 2);
 #ifdef CF_EXPERIMENTS
         if (small && front == 2) return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB, 3>>(grid, blk, G::LDS, s, q);
 #endif
@@ -1141,7 +987,7 @@ hipError_t fx_launch_t(hipStream_t s, const MbParams& p) {
     // what ran before that deal, for A/B runs: layer1.1 on MODE 3, layer2.1 on the general kernel.
     if constexpr (KS == 5 && JX == 2 && NMB == 2 && RESID && TOH == 16 && TOW == 16 && NW == 4 && !TAIL16 && !XRELOAD && ALDS && !SB) {
         static const int front = cf_ab_int("CF_FRONT_MODE", 1);
-        const bool small = front != 0 && front != 2 && abl == 0 && (size_t)p.B * p.Hin * p.Win * p.Cin * 2 < ((size_t)1 << 31) && (size_t)p.Win * p.Cin * 2 < ((size_t)1 << 24);
+        const bool small = front != 0 && front != 2 && abl == 0 && cf_rsrc_fits((size_t)p.B * p.Hin * p.Win, p.Win, (size_t)p.Cin * 2);
         if (small) return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB, 5>>(grid, blk, G::LDS, s, q);
     }
     return launch_lds<mbconv_mx_kernel<KS, JX, NMB, RESID, TOH, TOW, NW, TAIL16, XRELOAD, ALDS, SB>>(grid, blk, G::LDS, s, q);
@@ -1240,7 +1086,7 @@ void mx_fused_pack_weights(int, const MbGeom& g, int Cin, int hid, int Cout, int
                     uint16_t v[4];
                     for (int kk = 0; kk < 4; ++kk) {
                         const int kx = 4 * ks + kk - i;
-                        v[kk] = (kx >= 0 && kx < k) ? host_f32_to_f16_3(wrow[kx]) : 0;
+                        v[kk] = (kx >= 0 && kx < k) ? host_f32_to_f16(wrow[kx]) : 0;
                     }
                     uint32_t* dst = tt + (((size_t)ky * 2 + ks) * 64 + lane) * 2;
                     dst[0] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);
@@ -1278,7 +1124,7 @@ static hipError_t fs_launch_t(hipStream_t s, const MbParams& p) {
     // below 16 MiB; CF_FRONT_MODE=0 (experiments build) keeps the general kernel
     if constexpr (KS == 5 && JX == 2 && NMB == 2 && TOH == 8 && TOW == 16 && TAIL16 && !XRELOAD && !ALDS && (G::NIB * 2) % 4 == 0) {
         static const bool fast_on = cf_ab_int("CF_FRONT_MODE", 1) != 0;
-        const bool small = fast_on && (size_t)p.B * p.Hin * p.Win * p.Cin * 2 < ((size_t)1 << 31) && (size_t)p.Win * p.Cin * 2 < ((size_t)1 << 24);
+        const bool small = fast_on && cf_rsrc_fits((size_t)p.B * p.Hin * p.Win, p.Win, (size_t)p.Cin * 2);
         if (small) return launch_lds<mbconv_mx2_kernel<KS, JX, NMB, TOH, TOW, TAIL16, XRELOAD, ALDS, 3>>(grid, blk, G::LDS, s, p);
     }
     return launch_lds<mbconv_mx2_kernel<KS, JX, NMB, TOH, TOW, TAIL16, XRELOAD, ALDS>>(grid, blk, G::LDS, s, p);
@@ -1359,7 +1205,7 @@ void mx_fused2_pack_weights(int, const MbGeom& g, int Cin, int hid, int Cout, in
                     uint16_t v[4];
                     for (int kk = 0; kk < 4; ++kk) {
                         const int kx = 4 * ks + kk - 2 * i;
-                        v[kk] = (kx >= 0 && kx < k) ? host_f32_to_f16_3(wrow[kx]) : 0;
+                        v[kk] = (kx >= 0 && kx < k) ? host_f32_to_f16(wrow[kx]) : 0;
                     }
                     uint32_t* dst = tt + (((size_t)ky * 3 + ks) * 64 + lane) * 2;
                     dst[0] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);

@@ -436,8 +436,7 @@ void mb4_repack(int dtype, const MbGeom& g, int hid, int Cout, int k, const floa
             for (int jp = 0; jp < g.HALF; ++jp)
                 for (int lane = 0; lane < 64; ++lane) {
                     const int i = lane & 31, h = lane >> 5;
-                    const int hh = (i >> 2) & 1, rr = (i & 3) + 4 * (i >> 3);
-                    const int co = nbo * 32 + hh * 16 + rr;                     // = slot_channel(nbo, i) of cf_mbconv.hip
+                    const int co = slot_channel(nbo, i);
                     if (co >= Cout) continue;
                     char* dst = (char*)wproj_host + ((((size_t)nbo * g.nq + q) * g.HALF + jp) * 64 + lane) * 16;
                     pack_chunk(dtype, wp + (size_t)co * hid + q * g.HC + 8 * jp + 4 * h, dst);

@@ -365,7 +365,7 @@ void mb6_pack(int, const MbGeom& g, int Cin, int hid, int Cout, int k, const flo
             for (int j = 0; j < g.JX; ++j)
                 for (int lane = 0; lane < 64; ++lane) {
                     const int i = lane & 31, h = lane >> 5;
-                    int cl = (nbl * 32 + ((i >> 2) & 1) * 16 + (i & 3) + 4 * (i >> 3));          // slot_channel(nbl, i)
+                    int cl = slot_channel(nbl, i);
                     if (nbl == g.NBE - 1 && g.HC % 32 == 16) {
                         const int hh = (i >> 2) & 1, rr = (i & 3) + 4 * (i >> 3);
                         cl = rr < 8 ? nbl * 32 + hh * 8 + rr : g.HC;
@@ -389,7 +389,7 @@ void mb6_pack(int, const MbGeom& g, int Cin, int hid, int Cout, int k, const flo
             for (int js = 0; js < JS; ++js)
                 for (int lane = 0; lane < 64; ++lane) {
                     const int i = lane & 31, h = lane >> 5;
-                    const int co = ((i >> 2) & 1) * 16 + (i & 3) + 4 * (i >> 3);                 // slot_channel(0, i)
+                    const int co = slot_channel(0, i);
                     if (co >= Cout) continue;
                     float v[4];
                     for (int e = 0; e < 4; ++e) v[e] = kCfNegLn2 * wp[(size_t)co * hid + q * g.HC + (h * g.HALF + kg * JS + js) * 4 + e];

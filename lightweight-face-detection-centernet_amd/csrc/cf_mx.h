@@ -29,6 +29,78 @@ __device__ __forceinline__ f32x2 swish2_pre(f32x2 u) {      // u = -log2(e) x  -
     return u * r;
 }
 
+// ---- the vocabulary of the matrix-core kernels (expdw_mx_kernel, mbconv_mx_kernel, mbconv_mx2_kernel, stem0_mx_kernel and the
+// experiments variants): every block is the text its callers used to carry, inlined; profiles/mx_vocab_refactor.md compares the assembly
+
+// one quad cell: four fp32 (= -log2(e) x) -> Swish -> fp16 round-toward-zero -> one 8-byte LDS store; swish = false only under CF_ABLATION
+__device__ __forceinline__ void mx_cell_store(char* dst, float a0, float a1, float a2, float a3, bool swish = true) {
+    f32x2 y0, y1; y0.x = a0; y0.y = a1; y1.x = a2; y1.y = a3;
+    if (swish) { y0 = swish2_pre(y0); y1 = swish2_pre(y1); }
+    u32x2 d;
+    d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
+    d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
+    *reinterpret_cast<u32x2*>(dst) = d;
+}
+// the four cells of expand block ib in linear pixel order: D rows (r & 3) + 8 (r >> 2) + 4 h, so register quad tq of lane (channel pl,
+// half h) is halo quad ib * 8 + 2 tq + h
+template <int CP>
+__device__ __forceinline__ void mx_block_store(char* E, int ib, int h, int pl, const f32x16& a, bool swish = true) {
+    char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)CP + pl * 8;
+#pragma unroll
+    for (int tq = 0; tq < 4; ++tq) mx_cell_store(ecell + 2 * tq * CP, a[4 * tq], a[4 * tq + 1], a[4 * tq + 2], a[4 * tq + 3], swish);
+}
+
+// Swish over the depthwise accumulators acc[NG][4] (= -log2(e) x); SCALE: the leftover factor out again (a consumer with plain weights).
+// expdw_mx_kernel keeps its own text of the SCALE form: through this function all 36 of its instances come out with other assembly
+template <int NG, bool SCALE = false>
+__device__ __forceinline__ void mx_swish_acc(f32x4* acc) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+        for (int i = 0; i < 4; i += 2) {
+            f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
+            f32x2 y = swish2_pre(u);
+            if constexpr (SCALE) y = y * kNegLn23;
+            acc[g][i] = y.x; acc[g][i + 1] = y.y;
+        }
+}
+
+// the lane's eight (four) channels of output pixel i as bf16: a 16-byte store or a project MFMA B fragment
+__device__ __forceinline__ u32x4 mx_pack8(const f32x4* acc, int i) {
+    u32x4 d;
+    d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
+    d.z = packb(acc[4][i], acc[5][i]); d.w = packb(acc[6][i], acc[7][i]);
+    return d;
+}
+__device__ __forceinline__ u32x2 mx_pack4(const f32x4* acc, int i) {
+    u32x2 d; d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
+    return d;
+}
+
+// BYTES (whole KiB) from global memory straight into LDS, the KiB chunks dealt over the caller's NW waves (global_load_lds, 16 bytes
+// per lane; uses the caller's wave and lane).  A macro: as a function the loop is canonicalised before it is inlined, without the
+// caller's ranges of wave and lane, and all 40 kernels of cf_mbconv3.hip come out with other assembly (the fused ones two lines longer)
+#define CF_MX_STAGE(SRC, DST, BYTES)                                                                                              \
+    do {                                                                                                                          \
+        char* stage_dst = (DST);                                                                                                  \
+        const char* stage_src = (SRC);                                                                                            \
+        for (int c = wave; c < (BYTES) / 1024; c += NW)                                                                           \
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(stage_src + c * 1024 + lane * 16),   \
+                                             (__attribute__((address_space(3))) void*)(stage_dst + c * 1024), 16, 0, 0);          \
+    } while (0)
+
+// (The expand block -- a zeroed f32x16 and the JX-long chain of v_mfma_f32_32x32x16_bf16 against weight fragments in LDS -- stays
+// written out in every kernel: as a function, with either form of the fragment address or a callable for it, the nine
+// expdw_mx_kernel<5, 4, 10, 40, 8> instances gain 24 to 46 instructions and both layer1.1 instances of mbconv_mx_kernel come out with
+// other assembly, the general ones included, which no test at small shapes can reach: profiles/mx_vocab_refactor.md.)
+
+// N register-resident Toeplitz operand pairs (a [2][KS][2], [KS][2] or [KS][KSTEPS] array, flat), 64 lanes apart; at = table + lane
+template <int N>
+__device__ __forceinline__ void mx_load_taps(u32x2* A, const u32x2* at) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) A[n] = at[n * 64];
+}
+
 // Swish + cell stores of expand block t of wave w under HaloDeal<KS> (cf_common.h); a = the block's 32x32 expand accumulators (lane =
 // channel pl of lane half h, register quad tq = rows 8 tq + 4 h ..).  Every cell the depthwise reads is written, every round: the dead
 // column pair of a 3x3 halo's quad 4 as ZERO, never left to what the workgroup before had in those bytes (the depthwise multiplies it
@@ -37,14 +109,7 @@ template <int KS, int CP>
 __device__ __forceinline__ void halo_deal_store(char* E, int w, int t, int h, int pl, const f32x16& a) {
     typedef HaloDeal<KS> D;
     constexpr int RP = 2 * D::IWQ * CP;                             // bytes from a row pair to the next
-    auto full = [&](int tq, char* dst) {
-        f32x2 u0, u1; u0.x = a[4 * tq]; u0.y = a[4 * tq + 1]; u1.x = a[4 * tq + 2]; u1.y = a[4 * tq + 3];
-        const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-        u32x2 d;
-        d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-        d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-        *reinterpret_cast<u32x2*>(dst) = d;
-    };
+    auto full = [&](int tq, char* dst) { mx_cell_store(dst, a[4 * tq], a[4 * tq + 1], a[4 * tq + 2], a[4 * tq + 3]); };
     auto half = [&](float ux, float uy, char* dst) {
         f32x2 u; u.x = ux; u.y = uy;
         const f32x2 y = swish2_pre(u);
@@ -84,29 +149,6 @@ __device__ __forceinline__ void halo_deal_store(char* E, int w, int t, int h, in
     }
 }
 
-static inline uint16_t host_f32_to_f16_3(float f) {       // round-to-nearest-even, saturating (= cf_mbconv2.hip)
-    uint32_t u; __builtin_memcpy(&u, &f, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const int32_t exp = (int32_t)((u >> 23) & 0xff) - 127 + 15;
-    uint32_t man = u & 0x7fffffu;
-    if (((u >> 23) & 0xff) == 0xff) return (uint16_t)(sign | 0x7c00u | (man ? 0x200u : 0));
-    if (exp >= 31) return (uint16_t)(sign | 0x7bffu);
-    if (exp <= 0) {
-        if (exp < -10) return (uint16_t)sign;
-        man |= 0x800000u;
-        const int shift = 14 - exp;
-        uint32_t half = man >> shift;
-        const uint32_t rem = man & ((1u << shift) - 1), mid = 1u << (shift - 1);
-        if (rem > mid || (rem == mid && (half & 1))) ++half;
-        return (uint16_t)(sign | half);
-    }
-    uint32_t half = ((uint32_t)exp << 10) | (man >> 13);
-    const uint32_t rem = man & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (half & 1))) ++half;
-    if (half >= 0x7c00u) half = 0x7bffu;
-    return (uint16_t)(sign | half);
-}
-
 // lane & 15 -> output quad of a set (entry: bit 15 = no quad, bits 6.. = oy, bits 0-5 = x-quad)
 template <int TOH, int TOW, int IWQ, int S = 1>
 struct SetMap {
@@ -136,6 +178,34 @@ struct SetMap {
 
 #define CF_MX_MFMA(ACC, AV, BV, ABID) ACC = __builtin_amdgcn_mfma_f32_4x4x4f16(AV, BV, ACC, 2, ABID, 0)
 
+// one k-step of channel g of a lane's eight: bq = its 64 contiguous bytes of a cell row (channel g = dwords 2 g, 2 g + 1), a = the
+// Toeplitz operands of channel quad g >> 2 (abid = g & 3 picks the channel inside the quad).  The callers keep the loop over g and
+// pick the operand pair there: with the loop in here (both pairs as arguments) the LDS forms issue the table reads behind the cell
+// reads and wait for all of them at once -- other assembly for all 29 instances that hold the table in LDS
+__device__ __forceinline__ void mx_mfma8(f32x4* acc, int g, u32x2 a, const u32x4* bq) {
+    const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, a);
+    u32x2 b2;
+    b2.x = (g & 1) ? bq[g >> 1].z : bq[g >> 1].x;
+    b2.y = (g & 1) ? bq[g >> 1].w : bq[g >> 1].y;
+    const mfma_f16x4 bv = __builtin_bit_cast(mfma_f16x4, b2);
+    switch (g & 3) {
+        case 0: CF_MX_MFMA(acc[g], av, bv, 0); break;
+        case 1: CF_MX_MFMA(acc[g], av, bv, 1); break;
+        case 2: CF_MX_MFMA(acc[g], av, bv, 2); break;
+        default: CF_MX_MFMA(acc[g], av, bv, 3); break;
+    }
+}
+// the same for four channels: b0, b1 = the lane's 32 contiguous bytes
+__device__ __forceinline__ void mx_mfma4(f32x4* acc, u32x2 a, u32x4 b0, u32x4 b1) {
+    const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, a);
+    u32x2 t0, t1, t2, t3;
+    t0.x = b0.x; t0.y = b0.y; t1.x = b0.z; t1.y = b0.w; t2.x = b1.x; t2.y = b1.y; t3.x = b1.z; t3.y = b1.w;
+    CF_MX_MFMA(acc[0], av, __builtin_bit_cast(mfma_f16x4, t0), 0);
+    CF_MX_MFMA(acc[1], av, __builtin_bit_cast(mfma_f16x4, t1), 1);
+    CF_MX_MFMA(acc[2], av, __builtin_bit_cast(mfma_f16x4, t2), 2);
+    CF_MX_MFMA(acc[3], av, __builtin_bit_cast(mfma_f16x4, t3), 3);
+}
+
 // depthwise of one set (16 output quads x 32 channels): acc[g][i] = output pixel i of this lane's quad, channel kg*8 + g
 template <int KS, int IWQ, int CP>
 __device__ __forceinline__ void mx_depthwise(const char* bb, const u32x2 (*A)[KS][2], f32x4* acc) {
@@ -154,19 +224,7 @@ __device__ __forceinline__ void mx_depthwise(const char* bb, const u32x2 (*A)[KS
         }
         __builtin_amdgcn_sched_barrier(0);        // keep the next group's reads in flight under this group's MFMAs
 #pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, A[g >> 2][st >> 1][st & 1]);
-            u32x2 b2;
-            b2.x = (g & 1) ? bq[st & 1][g >> 1].z : bq[st & 1][g >> 1].x;
-            b2.y = (g & 1) ? bq[st & 1][g >> 1].w : bq[st & 1][g >> 1].y;
-            const mfma_f16x4 bv = __builtin_bit_cast(mfma_f16x4, b2);
-            switch (g & 3) {
-                case 0: CF_MX_MFMA(acc[g], av, bv, 0); break;
-                case 1: CF_MX_MFMA(acc[g], av, bv, 1); break;
-                case 2: CF_MX_MFMA(acc[g], av, bv, 2); break;
-                default: CF_MX_MFMA(acc[g], av, bv, 3); break;
-            }
-        }
+        for (int g = 0; g < 8; ++g) mx_mfma8(acc, g, A[g >> 2][st >> 1][st & 1], bq[st & 1]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -195,19 +253,7 @@ __device__ __forceinline__ void mx_depthwise_lds(const char* bb, const char* at 
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, aq[st & 1][g >> 2]);
-            u32x2 b2;
-            b2.x = (g & 1) ? bq[st & 1][g >> 1].z : bq[st & 1][g >> 1].x;
-            b2.y = (g & 1) ? bq[st & 1][g >> 1].w : bq[st & 1][g >> 1].y;
-            const mfma_f16x4 bv = __builtin_bit_cast(mfma_f16x4, b2);
-            switch (g & 3) {
-                case 0: CF_MX_MFMA(acc[g], av, bv, 0); break;
-                case 1: CF_MX_MFMA(acc[g], av, bv, 1); break;
-                case 2: CF_MX_MFMA(acc[g], av, bv, 2); break;
-                default: CF_MX_MFMA(acc[g], av, bv, 3); break;
-            }
-        }
+        for (int g = 0; g < 8; ++g) mx_mfma8(acc, g, aq[st & 1][g >> 2], bq[st & 1]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -229,19 +275,7 @@ __device__ __forceinline__ void mx_depthwise_lds1(const char* bb, const char* at
         aq[0] = *reinterpret_cast<const u32x2*>(at + st * 512);
         aq[1] = *reinterpret_cast<const u32x2*>(at + (NSTEP + st) * 512);
 #pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, aq[g >> 2]);
-            u32x2 b2;
-            b2.x = (g & 1) ? bq[g >> 1].z : bq[g >> 1].x;
-            b2.y = (g & 1) ? bq[g >> 1].w : bq[g >> 1].y;
-            const mfma_f16x4 bv = __builtin_bit_cast(mfma_f16x4, b2);
-            switch (g & 3) {
-                case 0: CF_MX_MFMA(acc[g], av, bv, 0); break;
-                case 1: CF_MX_MFMA(acc[g], av, bv, 1); break;
-                case 2: CF_MX_MFMA(acc[g], av, bv, 2); break;
-                default: CF_MX_MFMA(acc[g], av, bv, 3); break;
-            }
-        }
+        for (int g = 0; g < 8; ++g) mx_mfma8(acc, g, aq[g >> 2], bq);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -268,14 +302,7 @@ __device__ __forceinline__ void mx_depthwise_half(const char* bb, const char* at
             aq[(st + 1) & 1] = *reinterpret_cast<const u32x2*>(at + (st + 1) * 512);
         }
         __builtin_amdgcn_sched_barrier(0);
-        const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, aq[st & 1]);
-        u32x2 t0, t1, t2, t3;
-        t0.x = bq[st & 1][0].x; t0.y = bq[st & 1][0].y; t1.x = bq[st & 1][0].z; t1.y = bq[st & 1][0].w;
-        t2.x = bq[st & 1][1].x; t2.y = bq[st & 1][1].y; t3.x = bq[st & 1][1].z; t3.y = bq[st & 1][1].w;
-        CF_MX_MFMA(acc[0], av, __builtin_bit_cast(mfma_f16x4, t0), 0);
-        CF_MX_MFMA(acc[1], av, __builtin_bit_cast(mfma_f16x4, t1), 1);
-        CF_MX_MFMA(acc[2], av, __builtin_bit_cast(mfma_f16x4, t2), 2);
-        CF_MX_MFMA(acc[3], av, __builtin_bit_cast(mfma_f16x4, t3), 3);
+        mx_mfma4(acc, aq[st & 1], bq[st & 1][0], bq[st & 1][1]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -297,14 +324,7 @@ __device__ __forceinline__ void mx_depthwise_half_reg(const char* bb, const u32x
             bq[(st + 1) & 1][1] = ld16(bb + (ky * IWQ + (ks & 1) * HQ + (ks >> 1)) * CP + 16);
         }
         __builtin_amdgcn_sched_barrier(0);
-        const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, A[st / KSTEPS][st % KSTEPS]);
-        u32x2 t0, t1, t2, t3;
-        t0.x = bq[st & 1][0].x; t0.y = bq[st & 1][0].y; t1.x = bq[st & 1][0].z; t1.y = bq[st & 1][0].w;
-        t2.x = bq[st & 1][1].x; t2.y = bq[st & 1][1].y; t3.x = bq[st & 1][1].z; t3.y = bq[st & 1][1].w;
-        CF_MX_MFMA(acc[0], av, __builtin_bit_cast(mfma_f16x4, t0), 0);
-        CF_MX_MFMA(acc[1], av, __builtin_bit_cast(mfma_f16x4, t1), 1);
-        CF_MX_MFMA(acc[2], av, __builtin_bit_cast(mfma_f16x4, t2), 2);
-        CF_MX_MFMA(acc[3], av, __builtin_bit_cast(mfma_f16x4, t3), 3);
+        mx_mfma4(acc, A[st / KSTEPS][st % KSTEPS], bq[st & 1][0], bq[st & 1][1]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }

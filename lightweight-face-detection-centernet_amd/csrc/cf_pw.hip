@@ -26,13 +26,7 @@ namespace cf {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 mfma_bf16x8;
 
-// channel held by MFMA row-slot i of n-block nb (see header comment): lane (pixel, h) accumulator
-// register r  <->  row i = (r&3) + 8*(r>>2) + 4*h  <->  channel nb*32 + h*16 + r
-static inline int slot_channel(int nb, int i) {
-    int h = (i >> 2) & 1;
-    int r = (i & 3) + 4 * (i >> 3);
-    return nb * 32 + h * 16 + r;
-}
+// (slot_channel, cf_common.h: the channel held by MFMA row-slot i of n-block nb, see the header comment)
 
 static inline int pw_chunks(int dtype, int K) { return (int)((size_t)K * elem_size(dtype) / 16); }
 

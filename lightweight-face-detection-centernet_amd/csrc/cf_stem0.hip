@@ -27,11 +27,6 @@ namespace cf {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 mfma_bf16x8;
 
-static inline int slot_channel(int nb, int i) {
-    int h = (i >> 2) & 1;
-    int r = (i & 3) + 4 * (i >> 3);
-    return nb * 32 + h * 16 + r;
-}
 
 constexpr int S0_TOH = 16, S0_TOW = 16;                 // 8 waves: one 32-pixel block (2 rows) each
 constexpr int S0_NT = (S0_TOH * S0_TOW / 32) * 64;      // 512 threads
@@ -327,29 +322,6 @@ constexpr int S0P_PITCH = 32 * 4 + 16;                             // one pixel 
 constexpr int S0P_NIB = (S0_IPX + 31) / 32;                        // 11 halo pixel blocks
 static constexpr float kS0NegLog2e = -1.44269504088896341f, kS0NegLn2 = -0.69314718055994531f;
 
-static inline uint16_t s0_f32_to_f16(float f) {                    // RNE, saturating
-    uint32_t u; __builtin_memcpy(&u, &f, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const int32_t exp = (int32_t)((u >> 23) & 0xff) - 127 + 15;
-    uint32_t man = u & 0x7fffffu;
-    if (((u >> 23) & 0xff) == 0xff) return (uint16_t)(sign | 0x7c00u | (man ? 0x200u : 0));
-    if (exp >= 31) return (uint16_t)(sign | 0x7bffu);
-    if (exp <= 0) {
-        if (exp < -10) return (uint16_t)sign;
-        man |= 0x800000u;
-        const int shift = 14 - exp;
-        uint32_t half = man >> shift;
-        const uint32_t rem = man & ((1u << shift) - 1), mid = 1u << (shift - 1);
-        if (rem > mid || (rem == mid && (half & 1))) ++half;
-        return (uint16_t)(sign | half);
-    }
-    uint32_t half = ((uint32_t)exp << 10) | (man >> 13);
-    const uint32_t rem = man & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (half & 1))) ++half;
-    if (half >= 0x7c00u) half = 0x7bffu;
-    return (uint16_t)(sign | half);
-}
-
 size_t stem0px_wstem_bytes() { return 2 * 64 * 16; }
 size_t stem0px_wdw_dwords() { return 2 * 4 * 3 * 2 * 8; }
 // ws [32][3][3][3] (co, ci, ky, kx), wd [32][9], wp [16][32]
@@ -381,8 +353,8 @@ void stem0px_pack(const float* ws, const float* wd, const float* wp, void* wstem
                     for (int i = 0; i < 8; ++i) {
                         const float* wrow = wd + (c * 8 + i) * 9 + ky * 3;
                         const int k0 = 2 * t - par, k1 = k0 + 1;
-                        const uint16_t lo = (k0 >= 0 && k0 < 3) ? s0_f32_to_f16(wrow[k0]) : 0;
-                        const uint16_t hi = (k1 >= 0 && k1 < 3) ? s0_f32_to_f16(wrow[k1]) : 0;
+                        const uint16_t lo = (k0 >= 0 && k0 < 3) ? host_f32_to_f16(wrow[k0]) : 0;
+                        const uint16_t hi = (k1 >= 0 && k1 < 3) ? host_f32_to_f16(wrow[k1]) : 0;
                         wdw_out[((((par * 4 + c) * 3 + ky) * 2 + t) * 8) + i] = (uint32_t)lo | ((uint32_t)hi << 16);
                     }
     // project (A operand, as stem0_pack_proj) x -ln 2
@@ -823,7 +795,7 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
     for (int c = 0; c < 2; ++c) ws[c] = ld16((const char*)p.wstem + ((size_t)c * 64 + lane) * 16);
     // Toeplitz operands of the 32 stem channels: [2 channel quads][3 rows][2 k-steps] register pairs (mx_pack_taps)
     u32x2 A[2][3][2];
-    {
+    {   // (mx_load_taps of cf_mx.h, its own text: through the function the general float-input instance <1, 0> comes out with other assembly)
         const u32x2* at = reinterpret_cast<const u32x2*>(p.wdw) + lane;
 #pragma unroll
         for (int q = 0; q < 2; ++q)
@@ -884,16 +856,10 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
                                                         __builtin_bit_cast(mfma_bf16x8, ws[c]), a, 0, 0, 0);
         if constexpr (DEAL) { halo_deal_store<3, S0M_CP>(E, wave, t, h, pl, a); continue; }
         // D rows (r & 3) + 8 (r >> 2) + 4 h: register quad tq = halo quad ib * 8 + 2 tq + h -> one 8-byte cell of lane channel pl
+        // (mx_block_store with its loop written out: through that function the two general instances come out with other assembly)
         char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)S0M_CP + pl * 8;
 #pragma unroll
-        for (int tq = 0; tq < 4; ++tq) {
-            f32x2 u0, u1; u0.x = a[4 * tq]; u0.y = a[4 * tq + 1]; u1.x = a[4 * tq + 2]; u1.y = a[4 * tq + 3];
-            const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-            u32x2 d;
-            d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-            d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-            *reinterpret_cast<u32x2*>(ecell + 2 * tq * S0M_CP) = d;
-        }
+        for (int tq = 0; tq < 4; ++tq) mx_cell_store(ecell + 2 * tq * S0M_CP, a[4 * tq], a[4 * tq + 1], a[4 * tq + 2], a[4 * tq + 3]);
     }
     __syncthreads();
 
@@ -905,21 +871,12 @@ __global__ __launch_bounds__(S0P_NT) void stem0_mx_kernel(Stem0Params p) {
     f32x4 acc[8];
     mx_depthwise<3, S0M_IWQ, S0M_CP>(E + (unsigned)(soy * S0M_IWQ + soxq) * (unsigned)S0M_CP + kg * 64,
                                       reinterpret_cast<const u32x2 (*)[3][2]>(A), acc);
-#pragma unroll
-    for (int g = 0; g < 8; ++g)
-#pragma unroll
-        for (int i = 0; i < 4; i += 2) {
-            f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-            const f32x2 yv = swish2_pre(u);
-            acc[g][i] = yv.x; acc[g][i + 1] = yv.y;
-        }
+    mx_swish_acc<8>(acc);
     const u32x4 wpc = ld16((const char*)p.wproj + (size_t)lane * 16);
     const int gy = oy0 + soy, gx0 = ox0 + 4 * soxq;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        u32x4 d;
-        d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
-        d.z = packb(acc[4][i], acc[5][i]); d.w = packb(acc[6][i], acc[7][i]);
+        const u32x4 d = mx_pack8(acc, i);
         f32x4 o = {0.0f, 0.0f, 0.0f, 0.0f};
         o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, wpc), __builtin_bit_cast(mfma_bf16x8, d), o, 0, 0, 0);
         if (gy < Ho && gx0 + i < Wo) {                             // rows 4 kg .. 4 kg + 3 = output channels of pixel (quad, i)

@@ -24,13 +24,9 @@ __global__ __launch_bounds__(NW * 64) void expdw_mxr_kernel(MbParams p) {
     auto stage = [&](int r) {
         char* dst = Wst + (r & 1) * STG;
         const char* srcx = (const char*)p.wexp + (size_t)(grp * R + r) * WXB;
-        for (int c = wave; c < WXB / 1024; c += NW)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcx + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(dst + c * 1024), 16, 0, 0);
+        CF_MX_STAGE(srcx, dst, WXB);
         const char* srca = (const char*)p.wdw + (size_t)(grp * R + r) * G::ATB;
-        for (int c = wave; c < G::ATB / 1024; c += NW)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srca + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(dst + WXB + c * 1024), 16, 0, 0);
+        CF_MX_STAGE(srca, dst + WXB, G::ATB);
         asm volatile("" ::: "memory");
     };
     stage(0);
@@ -90,17 +86,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mxr_kernel(MbParams p) {
             a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mfma_bf16x8, xa[j]),
                                                         __builtin_bit_cast(mfma_bf16x8, wv), a, 0, 0, 0);
         }
-        char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)CP + pl * 8;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x2 u0, u1; u0.x = a[4 * t]; u0.y = a[4 * t + 1]; u1.x = a[4 * t + 2]; u1.y = a[4 * t + 3];
-            f32x2 y0 = u0, y1 = u1;
-            if (!(abl & 4)) { y0 = swish2_pre(u0); y1 = swish2_pre(u1); }
-            u32x2 d;
-            d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-            d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-            *reinterpret_cast<u32x2*>(ecell + 2 * t * CP) = d;
-        }
+        mx_block_store<CP>(E, ib, h, pl, a, !(abl & 4));
         if (more) {
 #pragma unroll
             for (int j = 0; j < JX; ++j) xa[j] = xn[j];
@@ -124,15 +110,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mxr_kernel(MbParams p) {
         mx_depthwise_lds<KS, IWQ, CP>(bb, Ats + lane * 8, acc);
         }
         // a = -log2(e) * depthwise output -> Swish, leftover factor out again (the project GEMM has plain weights)
-        if (!(abl & 2))
-#pragma unroll
-        for (int g = 0; g < 8; ++g)
-#pragma unroll
-            for (int i = 0; i < 4; i += 2) {
-                f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-                const f32x2 y = swish2_pre(u) * kNegLn23;
-                acc[g][i] = y.x; acc[g][i + 1] = y.y;
-            }
+        if (!(abl & 2)) mx_swish_acc<8, true>(acc);
         const int gy = oy0 + oy, gx0 = ox0 + 4 * oxq;
         if (!live || gy >= p.Hout || ((abl & 16) && acc[0][0] != 123.0f)) continue;
         const size_t opix0 = ((size_t)b * p.Hout + gy) * p.Wout + gx0;
@@ -140,9 +118,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mxr_kernel(MbParams p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (gx0 + i >= p.Wout) break;
-            u32x4 o;
-            o.x = packb(acc[0][i], acc[1][i]); o.y = packb(acc[2][i], acc[3][i]);
-            o.z = packb(acc[4][i], acc[5][i]); o.w = packb(acc[6][i], acc[7][i]);
+            const u32x4 o = mx_pack8(acc, i);
             const size_t opix = opix0 + i;
             st16((char*)p.y + (p.yblock ? blk_off(opix, p.hid / 8, chunk) : (opix * p.hid + (size_t)chunk * 8) * 2), o);
         }
@@ -171,13 +147,9 @@ __global__ __launch_bounds__(NW * 64) void expdw_mxt_kernel(MbParams p) {
     const int unit0 = blockIdx.x * T;
     {
         const char* srcx = (const char*)p.wexp + (size_t)grp * WXB;
-        for (int c = wave; c < WXB / 1024; c += NW)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcx + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(Wst + c * 1024), 16, 0, 0);
+        CF_MX_STAGE(srcx, Wst, WXB);
         const char* srca = (const char*)p.wdw + (size_t)grp * G::ATB;
-        for (int c = wave; c < G::ATB / 1024; c += NW)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srca + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(Ats + c * 1024), 16, 0, 0);
+        CF_MX_STAGE(srca, Ats, G::ATB);
     }
     asm volatile("" ::: "memory");
     auto load_x = [&](int b, int oy0, int ox0, int ib, u32x4* xf) -> bool {
@@ -242,16 +214,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mxt_kernel(MbParams p) {
                 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mfma_bf16x8, xa[j]),
                                                             __builtin_bit_cast(mfma_bf16x8, wv), a, 0, 0, 0);
             }
-            char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)CP + pl * 8;
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) {
-                f32x2 u0, u1; u0.x = a[4 * tt]; u0.y = a[4 * tt + 1]; u1.x = a[4 * tt + 2]; u1.y = a[4 * tt + 3];
-                const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-                u32x2 d;
-                d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-                d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-                *reinterpret_cast<u32x2*>(ecell + 2 * tt * CP) = d;
-            }
+            mx_block_store<CP>(E, ib, h, pl, a);
             if (more) {
 #pragma unroll
                 for (int j = 0; j < JX; ++j) xa[j] = xn[j];
@@ -273,14 +236,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mxt_kernel(MbParams p) {
             f32x4 acc[8];
             const char* bb = E + (unsigned)(oy * IWQ + oxq) * (unsigned)CP + kg * 64;
             mx_depthwise_lds<KS, IWQ, CP>(bb, Ats + lane * 8, acc);
-#pragma unroll
-            for (int g = 0; g < 8; ++g)
-#pragma unroll
-                for (int i = 0; i < 4; i += 2) {
-                    f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-                    const f32x2 y = swish2_pre(u) * kNegLn23;
-                    acc[g][i] = y.x; acc[g][i + 1] = y.y;
-                }
+            mx_swish_acc<8, true>(acc);
             const int gy = oyc + oy, gx0 = oxc + 4 * oxq;
             if (!live || gy >= p.Hout) continue;
             const size_t opix0 = ((size_t)bc * p.Hout + gy) * p.Wout + gx0;
@@ -288,9 +244,7 @@ __global__ __launch_bounds__(NW * 64) void expdw_mxt_kernel(MbParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (gx0 + i >= p.Wout) break;
-                u32x4 o;
-                o.x = packb(acc[0][i], acc[1][i]); o.y = packb(acc[2][i], acc[3][i]);
-                o.z = packb(acc[4][i], acc[5][i]); o.w = packb(acc[6][i], acc[7][i]);
+                const u32x4 o = mx_pack8(acc, i);
                 const size_t opix = opix0 + i;
                 st16((char*)p.y + (p.yblock ? blk_off(opix, p.hid / 8, chunk) : (opix * p.hid + (size_t)chunk * 8) * 2), o);
             }

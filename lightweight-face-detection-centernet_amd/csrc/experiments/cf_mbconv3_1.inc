@@ -27,7 +27,7 @@ template <int KS, int JX, int NMB, bool RESID, int TOH, int TOW, bool TAIL16>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void mbconv_mxs_kernel(MbParams p) {
     typedef Fz<KS, JX, NMB, TOH, TOW, TAIL16> G;
     constexpr int IWQ = G::IWQ, IWP = G::IWP, IPX = G::IPX, NIB = G::NIB, MAXI = G::MAXI, CP8 = G::CP8, CP4 = G::CP4;
-    constexpr int WXB = G::WXB, NR = G::NR;
+    constexpr int WXB = G::WXB, NR = G::NR, NW = NR;                 // (NW: the waves CF_MX_STAGE deals chunks to = one role)
     typedef __attribute__((ext_vector_type(4))) __bf16 mfma_bf16x4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Wst = smem + 2 * G::EBYTES;
@@ -71,16 +71,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     auto stage_w = [&](int q) {                 // expand role: expand weights of round q -> stage q & 1
         char* dst = Wst + (q & 1) * WXB;
         const char* srcx = (const char*)p.wexp + (size_t)q * WXB;
-        for (int c = wave; c < WXB / 1024; c += NR)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcx + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(dst + c * 1024), 16, 0, 0);
+        CF_MX_STAGE(srcx, dst, WXB);
     };
     auto stage_a = [&](int q) {                 // depthwise role: Toeplitz table of round q -> stage q & 1
         char* dst = Ats + (q & 1) * G::ATB;
         const char* srca = (const char*)p.wdw + (size_t)q * G::ATB;
-        for (int c = wave; c < G::ATB / 1024; c += NR)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srca + c * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(dst + c * 1024), 16, 0, 0);
+        CF_MX_STAGE(srca, dst, G::ATB);
     };
     auto expand_round = [&](int q) {            // full round q (32 channels) -> E[q & 1]
         char* E = smem + (q & 1) * G::EBYTES;
@@ -98,16 +94,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mfma_bf16x8, xf(t, j)),
                                                             __builtin_bit_cast(mfma_bf16x8, wv), a, 0, 0, 0);
             }
-            char* ecell = E + (unsigned)(ib * 8 + h) * (unsigned)CP8 + pl * 8;
-#pragma unroll
-            for (int tq = 0; tq < 4; ++tq) {
-                f32x2 u0, u1; u0.x = a[4 * tq]; u0.y = a[4 * tq + 1]; u1.x = a[4 * tq + 2]; u1.y = a[4 * tq + 3];
-                const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-                u32x2 d;
-                d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-                d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-                *reinterpret_cast<u32x2*>(ecell + 2 * tq * CP8) = d;
-            }
+            mx_block_store<CP8>(E, ib, h, pl, a);
         }
     };
     auto expand_tail = [&]() {                  // last round: 16 channels on 16x16x32 MFMAs -> E[nq & 1], cell row 144 B
@@ -124,12 +111,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             xv.x = valid ? xv.x : 0u; xv.y = valid ? xv.y : 0u; xv.z = valid ? xv.z : 0u; xv.w = valid ? xv.w : 0u;
             f32x4 a4 = {0.0f, 0.0f, 0.0f, 0.0f};
             a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xv), __builtin_bit_cast(mfma_bf16x8, wv), a4, 0, 0, 0);
-            f32x2 u0, u1; u0.x = a4[0]; u0.y = a4[1]; u1.x = a4[2]; u1.y = a4[3];
-            const f32x2 y0 = swish2_pre(u0), y1 = swish2_pre(u1);
-            u32x2 d;
-            d.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y0.x, y0.y));
-            d.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(y1.x, y1.y));
-            *reinterpret_cast<u32x2*>(E + (unsigned)(sb * 4 + kc) * (unsigned)CP4 + (lane & 15) * 8) = d;
+            mx_cell_store(E + (unsigned)(sb * 4 + kc) * (unsigned)CP4 + (lane & 15) * 8, a4[0], a4[1], a4[2], a4[3]);
         }
     };
 
@@ -150,19 +132,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         const char* E = smem + (q & 1) * G::EBYTES;
         f32x4 acc[8];
         mx_depthwise_lds1<KS, IWQ, CP8>(E + qcell * (unsigned)CP8 + kg * 64, Ats + (q & 1) * G::ATB + lane * 8, acc);
-#pragma unroll
-        for (int g = 0; g < 8; ++g)
-#pragma unroll
-            for (int i = 0; i < 4; i += 2) {
-                f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-                const f32x2 y = swish2_pre(u);
-                acc[g][i] = y.x; acc[g][i + 1] = y.y;
-            }
+        mx_swish_acc<8>(acc);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            u32x4 d;
-            d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
-            d.z = packb(acc[4][i], acc[5][i]); d.w = packb(acc[6][i], acc[7][i]);
+            const u32x4 d = mx_pack8(acc, i);
 #pragma unroll
             for (int mb = 0; mb < NMB; ++mb)
                 st[i * NMB + mb] = __builtin_bit_cast(u32x4, __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, wpc[mb]), __builtin_bit_cast(mfma_bf16x8, d),
@@ -172,13 +145,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     auto dw_tail = [&]() {                      // the 16-channel round from E[nq & 1] (cell row 144 B)
         const char* E = smem + (nq & 1) * G::EBYTES;
         u32x2 A4[KS][2];
-        {
-            const u32x2* at = reinterpret_cast<const u32x2*>(p.wdw) + (size_t)nq * (2 * KS * 2) * 64 + lane;
-#pragma unroll
-            for (int ky = 0; ky < KS; ++ky)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) A4[ky][ks] = at[(ky * 2 + ks) * 64];
-        }
+        mx_load_taps<KS * 2>(&A4[0][0], reinterpret_cast<const u32x2*>(p.wdw) + (size_t)nq * (2 * KS * 2) * 64 + lane);
         u32x2 wp4[NMB];
 #pragma unroll
         for (int mb = 0; mb < NMB; ++mb)
@@ -191,24 +158,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         for (int st = 0; st < KS * 2; ++st) {
             const char* bs = bb + ((st >> 1) * IWQ + (st & 1)) * CP4;
             const u32x4 b0 = ld16(bs), b1 = ld16(bs + 16);
-            const mfma_f16x4 av = __builtin_bit_cast(mfma_f16x4, A4[st >> 1][st & 1]);
-            u32x2 t0, t1, t2, t3; t0.x = b0.x; t0.y = b0.y; t1.x = b0.z; t1.y = b0.w; t2.x = b1.x; t2.y = b1.y; t3.x = b1.z; t3.y = b1.w;
-            CF_MX_MFMA(acc[0], av, __builtin_bit_cast(mfma_f16x4, t0), 0);
-            CF_MX_MFMA(acc[1], av, __builtin_bit_cast(mfma_f16x4, t1), 1);
-            CF_MX_MFMA(acc[2], av, __builtin_bit_cast(mfma_f16x4, t2), 2);
-            CF_MX_MFMA(acc[3], av, __builtin_bit_cast(mfma_f16x4, t3), 3);
+            mx_mfma4(acc, A4[st >> 1][st & 1], b0, b1);
         }
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int i = 0; i < 4; i += 2) {
-                f32x2 u; u.x = acc[g][i]; u.y = acc[g][i + 1];
-                const f32x2 y = swish2_pre(u);
-                acc[g][i] = y.x; acc[g][i + 1] = y.y;
-            }
+        mx_swish_acc<4>(acc);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            u32x2 d; d.x = packb(acc[0][i], acc[1][i]); d.y = packb(acc[2][i], acc[3][i]);
+            const u32x2 d = mx_pack4(acc, i);
 #pragma unroll
             for (int mb = 0; mb < NMB; ++mb)
                 st[i * NMB + mb] = __builtin_bit_cast(u32x4, __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(mfma_bf16x4, wp4[mb]), __builtin_bit_cast(mfma_bf16x4, d),

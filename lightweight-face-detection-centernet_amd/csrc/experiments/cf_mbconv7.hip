@@ -370,7 +370,7 @@ void mb7_pack(int dtype, const MbGeom& g, int Cin, int hid, int Cout, int k, con
         for (int gp = 0; gp < NGP; ++gp)
             for (int lane = 0; lane < 64; ++lane) {
                 const int i = lane & 31, h = lane >> 5;
-                const int co = ((i >> 2) & 1) * 16 + (i & 3) + 4 * (i >> 3);                 // slot_channel(0, i)
+                const int co = slot_channel(0, i);
                 if (co >= Cout) continue;
                 float v[4];
                 for (int e = 0; e < 4; ++e) v[e] = kCfNegLn2 * wp[(size_t)co * hid + q * g.HC + (2 * gp + h) * 4 + e];

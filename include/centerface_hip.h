@@ -855,6 +855,55 @@ typedef struct cf_track_weak_opts {
  * cf_last_error (ctx == NULL: the arguments are still checked first, cf_op_last_error names the cause). */
 int cf_track_create_weak(cf_ctx* ctx, int n_streams, const cf_track_opts* opts, const cf_track_weak_opts* weak, cf_tracker** out);
 
+/* ---- constant velocity: tracks are matched where the face is expected, held boxes coast with it ----
+ * A track above does not know that its face is moving: a held box stands where the face WAS, and the next detection is measured against
+ * last frame's box, so a fast face that drops out for one frame comes back under a new id while the old track covers an empty place.  A
+ * tracker created with cf_track_motion_opts keeps, per slot, vel = (vx, vy) in float32 beside the record (the motion model that SORT and
+ * ByteTrack put in front of the association, reduced to the centre):
+ *   gain: float32, finite, in (0, 1];   damp: float32, finite, in [0, 1].
+ * All new arithmetic is float32, every operation rounded, no FMA contraction.  One update of a stream becomes:
+ *   1'. Skip.  Step 1 as it is; in addition a row with a corner of magnitude above 16777216 (2^24) is skipped too.  This keeps every
+ *       later quantity finite.
+ *   P.  Predict.  For every slot alive when the update began, with stored box o and velocity v:
+ *       P = (o.x1 + vx, o.y1 + vy, o.x2 + vx, o.y2 + vy).
+ *   2'. Match.  Steps 2, 2a and 2b measure the IoU of P and the row, not of the stored box and the row.  The measure, the arg-max, the
+ *       tie rule, the NaN rule, the thresholds and the eligibility (including "confirmed when the update began") are unchanged.  A winner
+ *       takes the row's box d, score and landmarks as they are, as before.  Its velocity is updated from the values BEFORE the take --
+ *       the stored box o, g = misses, hb = hits:
+ *         cdx = (d.x1 + d.x2) * 0.5f;  cox = (o.x1 + o.x2) * 0.5f;  rx = (cdx - cox) - vx;
+ *         a = hb == 1 ? 1.0f : gain;   vx' = vx + a * (rx / (float)(g + 1));        y likewise.
+ *       hb == 1 is the track's second sighting: its velocity is still the 0 of birth, so the first measured displacement is taken whole.
+ *   3'. Age.  Freeing tentative tracks and counting misses are unchanged.  A slot that stays alive unmatched (a held track) COASTS: every
+ *       x of its box and of its ten landmarks becomes x + vx, every y becomes y + vy; then vel = (vx * damp, vy * damp).  If a coasted
+ *       corner's magnitude exceeds 2^24 the slot is freed instead.
+ *       Follower records: if the tracker has follower records, and the slot's tpl_id == id, and tpl_box equals the box before the coast bit
+ *       for bit, then tpl_box takes the coasted box.  The next cf_track_follow then FOLLOWS from the coasted place with the template of
+ *       the last detection; without this write it would LEARN whatever stands there.
+ *   4'. Birth.  As it is, with vel = (0, 0): a reused slot never inherits a velocity.
+ *   5.  Output.  Unchanged: the held row is the coasted box, grown by hold_grow, with its landmarks coasted with it.
+ * What follows for the other objects:
+ *   * cf_track_follow leaves vel alone.  It still LEARNS behind any match, because the box changed; behind a coast it now follows about
+ *     the predicted centre.
+ *   * With the follower running between updates, v is the motion per update that the follower has not already put into the box.
+ *   * Lookback, best shots, redact, blur, draw and chips take the rows unchanged.
+ *   * cf_track_reset and a scene cut need no word about velocities, because birth zeroes them.
+ *   * Device state per slot becomes 88 bytes for a motion tracker.
+ * THE LIMITS.  The model cannot bootstrap: a face so fast that its SECOND sighting misses iou_thresh against the unpredicted box is reborn
+ * every frame, as before.  Only the centre moves; size is not predicted.  A wrong match yields a wrong velocity for a few frames.
+ * Coasting at damp = 1 carries a held box max_age * v away.  gain = 0.5 and damp = 1.0 (SORT's coast) are this project's choices: there
+ * is no labelled video here, nobody has measured them, and no accuracy claim is made.
+ * A tracker created without these options runs the update it ran before, bit for bit. */
+typedef struct cf_track_motion_opts {
+    float gain;           /* finite, in (0, 1]: the share of a measured residual that the velocity takes from the third sighting on */
+    float damp;           /* finite, in [0, 1]: what is left of the velocity after each coasted frame */
+} cf_track_motion_opts;
+/* cf_track_create with the weak and the motion options, each of which may be NULL; motion == NULL is cf_track_create_weak (with its
+ * refusals, under its name).  CF_EINVAL for a bad value before any GPU work, after the plain and the weak checks: "gain must be finite
+ * and in (0, 1]", "damp must be finite and in [0, 1]" (ctx == NULL: the arguments are still checked first, cf_op_last_error names the
+ * cause). */
+int cf_track_create_ex(cf_ctx* ctx, int n_streams, const cf_track_opts* opts, const cf_track_weak_opts* weak,
+                       const cf_track_motion_opts* motion, cf_tracker** out);
+
 /* ---- follow tracked faces between detections: block matching in the frame, on the device -----
  * cf_track_update leaves two holes: a held track does not move (hold_grow only inflates its box blindly, and its landmarks stay where
  * the face was), and every frame needs a forward, because the tracker advances only behind a decode.  cf_track_follow measures, from
@@ -1655,6 +1704,21 @@ int cf_op_follow(int device, const cf_track_opts* opts, const cf_follow_opts* fo
                  const float* boxes, const float* scores, const float* lms_in, const int32_t* counts_in, const uint8_t* detect,
                  int format, const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h, int space_w, int tiled,
                  float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, int32_t* moves);
+/* cf_op_track_weak with the tracker of cf_track_create_ex ("constant velocity"): the same tables, limits and checks, plus the motion option
+ * checks, before any device is touched and after the plain and the weak ones.  weak and motion may each be NULL; motion == NULL is
+ * cf_op_track_weak (vel is then left alone).  vel: NULL, or [F][S][max_tracks][2] = vx, vy of the output rows, in output-row order,
+ * after every frame; copied up first like dets, so rows at and past the count keep the caller's bytes. */
+int cf_op_track_ex(int device, const cf_track_opts* opts, const cf_track_weak_opts* weak, const cf_track_motion_opts* motion,
+                   int n_streams, int n_frames, int rows, const float* boxes, const float* scores, const float* lms_in,
+                   const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, float* vel);
+/* cf_op_follow with the tracker of cf_track_create_ex: the update of every detect frame is that tracker's, and a coast moves the follower
+ * records' tpl_box along.  The option checks come in the order plain, weak, motion, follow.  weak == NULL and motion == NULL is
+ * cf_op_follow. */
+int cf_op_follow_ex(int device, const cf_track_opts* opts, const cf_track_weak_opts* weak, const cf_track_motion_opts* motion,
+                    const cf_follow_opts* fopts, int n_streams, int n_frames, int rows,
+                    const float* boxes, const float* scores, const float* lms_in, const int32_t* counts_in, const uint8_t* detect,
+                    int format, const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h, int space_w, int tiled,
+                    float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, int32_t* moves);
 /* The kernels of cf_scene_check over a whole sequence of host frames, with a fresh cf_scene of n_streams streams and no tracker: frame
  * f of stream s is frames[f * S + s] (F * S host frames of h x w in `format`, pitches as cf_redact_faces; only read).  out [F][S][4] =
  * code, hist, grid, run of every check; sigs [F][S][128] (or NULL) = the signature of every frame.  The option and count checks of

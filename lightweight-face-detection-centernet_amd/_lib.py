@@ -61,6 +61,7 @@ EXPORTS = (
     "cf_set_flip_test", "cf_op_mirror", "cf_op_flip_heads",
     "cf_track_create", "cf_track_destroy", "cf_track_reset", "cf_track_update", "cf_op_track",
     "cf_track_create_weak", "cf_op_track_weak",
+    "cf_track_create_ex", "cf_op_track_ex", "cf_op_follow_ex",
     "cf_track_follow", "cf_op_follow",
     "cf_scene_create", "cf_scene_destroy", "cf_scene_forget", "cf_scene_check", "cf_op_scene",
     "cf_lookback_create", "cf_lookback_destroy", "cf_lookback_forget", "cf_lookback_step", "cf_op_lookback",
@@ -346,6 +347,32 @@ def track_weak_opts(birth_score=0.3, weak_iou=0.5):
     """TrackWeakOpts (the library validates the numbers).  0.5 is ByteTrack's customary value and this project's choice: nobody has
     measured it here, and no accuracy claim is made."""
     return TrackWeakOpts(float(birth_score), float(weak_iou))
+
+
+class TrackMotionOpts(C.Structure):
+    """cf_track_motion_opts: the share of a measured residual the velocity takes / what is left of the velocity after a coasted frame."""
+    _fields_ = [("gain", C.c_float), ("damp", C.c_float)]
+
+
+def track_motion_opts(gain=0.5, damp=1.0):
+    """TrackMotionOpts (the library validates the numbers).  0.5 and 1.0 (SORT's coast) are this project's choices: there is no labelled
+    video here, nobody has measured them, and no accuracy claim is made."""
+    return TrackMotionOpts(float(gain), float(damp))
+
+
+def track_motion_of(motion):
+    """The ``motion=`` argument of ``Tracker`` and the sequence ops: None (or False) -> None, True -> the defaults, a dict with ``gain``
+    and / or ``damp`` -> those.  ValueError for anything else and for unknown keys; the library validates the numbers."""
+    if motion is None or motion is False:
+        return None
+    if motion is True:
+        return track_motion_opts()
+    if not isinstance(motion, dict):
+        raise ValueError("motion must be None, True or a dict with gain and / or damp, got %r" % (motion,))
+    unknown = sorted(set(motion) - {"gain", "damp"})
+    if unknown:
+        raise ValueError("motion: unknown keys %s (gain, damp)" % (unknown,))
+    return track_motion_opts(**motion)
 
 
 class FollowOpts(C.Structure):
@@ -683,6 +710,10 @@ def lib():
         L.cf_op_track.argtypes = [C.c_int, C.POINTER(TrackOpts)] + [C.c_int] * 3 + [C.c_void_p] * 9
         L.cf_track_create_weak.argtypes = [C.c_void_p, C.c_int, C.POINTER(TrackOpts), C.POINTER(TrackWeakOpts), C.POINTER(C.c_void_p)]
         L.cf_op_track_weak.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(TrackWeakOpts)] + [C.c_int] * 3 + [C.c_void_p] * 9
+        L.cf_track_create_ex.argtypes = [C.c_void_p, C.c_int, C.POINTER(TrackOpts), C.POINTER(TrackWeakOpts), C.POINTER(TrackMotionOpts), C.POINTER(C.c_void_p)]
+        L.cf_op_track_ex.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(TrackWeakOpts), C.POINTER(TrackMotionOpts)] + [C.c_int] * 3 + [C.c_void_p] * 10
+        L.cf_op_follow_ex.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(TrackWeakOpts), C.POINTER(TrackMotionOpts), C.POINTER(FollowOpts)] + \
+            [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 7 + [C.c_void_p] * 6
         L.cf_track_follow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(FollowOpts), C.c_int, C.POINTER(PlanesRW)] + [C.c_int] * 5 + \
             [C.c_void_p] * 5 + [C.c_int]
         L.cf_op_follow.argtypes = [C.c_int, C.POINTER(TrackOpts), C.POINTER(FollowOpts)] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int, C.POINTER(PlanesRW)] + \

@@ -1057,13 +1057,29 @@ class Tracker(_StreamState):
     only match a track that was already confirmed (``min_hits``), at IoU >= ``weak_iou``, and are otherwise discarded: the frame in
     which a face scores 0.29 keeps its track alive with the box and the landmarks of THAT frame instead of a held, stale box (flag
     bit 1 of the update says that it happened).  0.1 and 0.5 are ByteTrack's customary values and this project's choice: nobody has
-    measured them here, and no accuracy claim is made."""
+    measured them here, and no accuracy claim is made.
+
+    ``motion`` (default None: no motion model): True, or a dict with ``gain`` and / or ``damp`` -- constant-velocity prediction
+    (``include/centerface_hip.h``, "constant velocity").  Every slot keeps a velocity; rows are matched against the box where the face
+    is EXPECTED, and a held box coasts with its landmarks by the velocity per missed frame (times ``damp`` after each).  The model cannot
+    bootstrap (the second sighting must still match the unpredicted box), only the centre moves, and a coast at ``damp = 1`` carries
+    a held box ``max_age * v`` away.  ``gain = 0.5`` and ``damp = 1.0`` (SORT's coast) are this project's choices: there is no labelled
+    video here, nobody has measured them, and no accuracy claim is made.  ``Tracker.motion`` is None or the dict of the two numbers;
+    every product path reads the model from the tracker it is given."""
 
     _create, _destroy, _clear, _noun = "cf_track_create", "cf_track_destroy", "cf_track_reset", "tracker"
 
     def __init__(self, engine_or_device, streams, iou=0.3, max_age=15, min_hits=2, max_tracks=256, hold_grow=0.0, weak_score=None, birth_score=0.3,
-                 weak_iou=0.5):
+                 weak_iou=0.5, motion=None):
         self.max_tracks = int(max_tracks)
+        self.motion, self._mo = None, _lib.track_motion_of(motion)
+        if self._mo is not None:
+            gain, damp = float(self._mo.gain), float(self._mo.damp)
+            if not 0.0 < gain <= 1.0:                                                # (a NaN fails every comparison)
+                raise ValueError("gain must be finite and in (0, 1], got %r" % (gain,))
+            if not 0.0 <= damp <= 1.0:
+                raise ValueError("damp must be finite and in [0, 1], got %r" % (damp,))
+            self.motion = dict(gain=gain, damp=damp)
         self.weak_score, self.birth_score, self._wo = None, None, None
         if weak_score is not None:
             weak_score, birth_score, weak_iou = float(weak_score), float(birth_score), float(weak_iou)
@@ -1075,6 +1091,9 @@ class Tracker(_StreamState):
         self._open(engine_or_device, streams, _lib.track_opts(iou, max_age, min_hits, max_tracks, hold_grow))
 
     def _make(self, ctx, out):
+        if self._mo is not None:
+            return self._L.cf_track_create_ex(ctx, self.streams, C.byref(self._o), None if self._wo is None else C.byref(self._wo), C.byref(self._mo),
+                                              C.byref(out))
         if self._wo is None:
             return _StreamState._make(self, ctx, out)
         return self._L.cf_track_create_weak(ctx, self.streams, C.byref(self._o), C.byref(self._wo), C.byref(out))
@@ -1880,7 +1899,7 @@ class CenterFace(object):
         ``Engine.blur_faces``; the frames are then redacted IN PLACE with the merged boxes.  ``tracker``: a ``Tracker`` whose
         stream k the k-th frame of this call continues (frame pixels): it is advanced behind the merge, and the redaction then covers
         the tracked rows -- the merged detections plus the tracks held through a dropout; the detections returned stay the frame's
-        own.  ``follow``, ``detect`` and ``scenes``: as ``anonymize`` (``redact=`` only; the frames are checked and followed as they are before the
+        own.  A ``Tracker(motion=)`` carries its motion model itself: no argument here, the held rows are the coasted ones.  ``follow``, ``detect`` and ``scenes``: as ``anonymize`` (``redact=`` only; the frames are checked and followed as they are before the
         redaction).  ``lookback`` and ``flush`` (``redact=`` and an array of frames only): as ``anonymize`` -- the frames are then NOT
         redacted in place, the return is the lists of ``anonymize(lookback=)``."""
         if redact is not None:
@@ -1901,7 +1920,9 @@ class CenterFace(object):
         call; it is advanced between the decode (the merge) and the redaction, which then covers the detections of this frame AND the
         tracks held through a dropout.  The detections returned stay the frame's own.  A tracker with two thresholds
         (``Tracker(weak_score=)``): every product path decodes at its ``weak_score`` instead of 0.3, so that the rows between the
-        thresholds reach the update, and returns the rows above its ``birth_score``.  ``follow`` (needs ``tracker``): True, or a dict with
+        thresholds reach the update, and returns the rows above its ``birth_score``.  A tracker with a motion model
+        (``Tracker(motion=)``) needs no argument here, in ``anonymize_yuv``, ``annotate*``, ``best_shots`` or ``detect_tiled(redact=)``:
+        the tracker object carries it, and the held rows that are covered, drawn or cut are then the coasted ones.  ``follow`` (needs ``tracker``): True, or a dict with
         ``search`` and / or ``max_sad`` (``Engine.track_follow``; the defaults 4 and 4096 are this project's choices, no accuracy claim is
         made): right behind the update the tracker's faces are followed in the frame by block matching, so a track held through a dropout
         moves with its face instead of staying where it was last detected.  ``detect=False`` (needs ``tracker``, which a call with
@@ -1939,7 +1960,8 @@ class CenterFace(object):
                       scenes=None, lookback=None, flush=False, rotate=0, views=None, **options):
         """``detect_yuv`` plus the redaction, for 4:2:0 video frames: (frames_out, [(dets, lms), ...]), frames_out a uint8
         [B, height*3//2, width] copy of ``frames`` in the same format with every detected face redacted in the luma and chroma planes.  ``tiled=True``, ``tracker``, ``follow``,
-        ``fit``, ``detect``, ``scenes``, ``lookback``, ``flush``, ``rotate`` and ``views``: as ``anonymize``."""
+        ``fit``, ``detect``, ``scenes``, ``lookback``, ``flush``, ``rotate`` and ``views``: as ``anonymize``; a ``Tracker(motion=)`` carries its
+        motion model itself, as there."""
         return self._anonymize(frames, fmt, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
                                scenes=scenes, lookback=lookback, flush=flush, rotate=rotate, views=views)
 
@@ -1961,7 +1983,7 @@ class CenterFace(object):
         after the last chunk the finished entries of the call's streams are collected -- ``flush=True`` finishes every live track first
         (the end of the video).  Returns, per stream, the list of finished shots in finishing order: dicts with ``id``, ``quality``,
         ``chip`` [size, size, 3], ``det`` [5], ``lms`` [10] (the row of the best frame, in the tracker's space) and ``record`` (the eight
-        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  ``fit``: as ``anonymize`` (``detect_fit``'s path).  ``rotate``: as ``anonymize``; the chips are fitted to the landmarks, so they come out upright.  ``views``: as ``anonymize``.  The quality formula is this project's choice; no accuracy claim is made for it."""
+        int32 of ``Engine.bestshot_collect``).  ``scenes``: as ``anonymize`` -- a cut frees the stream's tracks, so their entries finish.  ``fit``: as ``anonymize`` (``detect_fit``'s path).  ``rotate``: as ``anonymize``; the chips are fitted to the landmarks, so they come out upright.  ``views``: as ``anonymize``.  A ``Tracker(motion=)`` carries its motion model itself (no argument here).  The quality formula is this project's choice; no accuracy claim is made for it."""
         views = self._views_options(views, tiled, fit, rotate)
         fit = self._fit_options(fit, tiled)
         if not self.landmarks:
@@ -2001,7 +2023,8 @@ class CenterFace(object):
         ``held_color``.  ``fit``, ``follow``, ``detect`` and ``scenes``: as ``anonymize``.  ``lookback`` and ``flush``: as ``anonymize`` --
         the delayed frames are drawn, a back-filled row as a held one (dashed, in ``held_color``), and the return is the lists.
         ``rotate``: as ``anonymize``; the labels are upright in the STORED frame, so a viewer of the upright video sees them turned.
-        ``views``: as ``anonymize``."""
+        ``views``: as ``anonymize``.  A ``Tracker(motion=)`` carries its motion model itself (no argument here): the held tracks are
+        drawn where they coasted to."""
         return self._annotate(imgs, None, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
                               scenes=scenes, lookback=lookback, flush=flush, rotate=rotate, views=views)
 
@@ -2009,7 +2032,7 @@ class CenterFace(object):
                      scenes=None, lookback=None, flush=False, rotate=0, views=None, **options):
         """``annotate`` for 4:2:0 video frames: frames_out a uint8 [B, height*3//2, width] copy of ``frames`` in the same format, drawn
         in the luma and chroma planes; the BGR colours are converted with ``ops.bgr_to_yuv_color``.  ``fit``, ``scenes``, ``lookback`` and
-        ``flush``, ``rotate`` and ``views``: as ``annotate``."""
+        ``flush``, ``rotate`` and ``views``: as ``annotate``; a ``Tracker(motion=)`` likewise."""
         return self._annotate(frames, fmt, options, tiled=tiled, tile=tile, overlap=overlap, fit=fit, tracker=tracker, follow=follow, detect=detect,
                               scenes=scenes, lookback=lookback, flush=flush, rotate=rotate, views=views)
 

@@ -599,10 +599,18 @@ struct TrackParams {
     float* corners;       // [B][max_tracks][4]: the box rows FaceList::boxes takes, as MergeParams::corners
     int* out_counts;      // [B], <= max_tracks
     int* flags;           // [B]: bit 0 = a new row found no free slot and was dropped; bit 1 = a weak row matched
+    // constant velocity (cf_track_create_ex), behind everything else so that the kernel arguments of the other trackers lie where they lay:
+    // motion != 0 matches against the predicted boxes, learns `vel` from every match and coasts the held slots
+    int motion; float gain, damp;
+    void set_motion(const cf_track_motion_opts* m) { motion = m ? 1 : 0; gain = m ? m->gain : 0.f; damp = m ? m->damp : 0.f; }
+    float* vel;           // state [S][max_tracks][2]: vx, vy -- motion trackers only, else nullptr (never read)
+    int* tmeta;           // the follower's FollowParams::tmeta [S][max_tracks][6], or nullptr before the first follow: a coast moves tpl_box along
+    float* vel_out;       // output [B][max_tracks][2] in output-row order, or nullptr (motion trackers only)
 };
-// nullptr, or what is wrong with the options / the number of streams (host only); the weak options may be null (a plain tracker)
+// nullptr, or what is wrong with the options / the number of streams (host only); the weak and the motion options may be null (a plain tracker)
 const char* track_check(const cf_track_opts* o, int n_streams);
 const char* track_weak_check(const cf_track_weak_opts* w);
+const char* track_motion_check(const cf_track_motion_opts* m);
 hipError_t launch_track_update(hipStream_t s, const TrackParams& p);
 
 // The follower (cf_follow.hip; the statement is in include/centerface_hip.h): block matching of every alive slot of the streams

@@ -1301,9 +1301,10 @@ struct OpFollow {
 // followed in its host frames, staged as cf_op_redact stages them.
 int op_track_sequence(const char* who, int device, const cf_track_opts* o, int n_streams, int n_frames, int rows, const float* boxes, const float* scores,
                       const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, const OpFollow* fw,
-                      const cf_track_weak_opts* wo = nullptr) {
+                      const cf_track_weak_opts* wo = nullptr, const cf_track_motion_opts* mo = nullptr, float* vel = nullptr) {
     const char* bad = track_check(o, n_streams);
     if (!bad) bad = track_weak_check(wo);
+    if (!bad) bad = track_motion_check(mo);
     if (!bad && fw) bad = follow_check(fw->o, fw->format, n_streams, fw->h, fw->w, fw->pitch0, fw->pitch1);
     if (!bad && (!boxes || !scores || !lms_in || !counts_in || !dets || !lms || !info || !counts || !flags || (fw && (!fw->detect || !fw->moves)))) bad = "null argument";
     if (!bad && (n_frames < 1 || rows < 1)) bad = "n_frames and rows must be at least 1";
@@ -1324,7 +1325,9 @@ int op_track_sequence(const char* who, int device, const cf_track_opts* o, int n
     p.rows = rows; p.B = n_streams; p.stream0 = 0;
     p.iou_thresh = o->iou_thresh; p.max_age = o->max_age; p.min_hits = o->min_hits; p.max_tracks = o->max_tracks; p.hold_grow = o->hold_grow;
     p.set_weak(wo);
+    p.set_motion(mo);
     p.meta = sc.make<int>(S * M * 4); p.rec = sc.make<float>(S * M * 16);
+    if (mo) { p.vel = sc.make<float>(S * M * 2); p.vel_out = vel ? sc.inout(vel, nout * 2) : nullptr; }
     const std::vector<int> ones(S, 1);
     p.next_id = sc.upv(ones);
     p.dets = sc.inout(dets, nout * 5); p.lms_out = sc.inout(lms, nout * 10); p.info = sc.inout(info, nout * 3);
@@ -1339,6 +1342,7 @@ int op_track_sequence(const char* who, int device, const cf_track_opts* o, int n
         q.stream0 = 0; q.max_tracks = o->max_tracks; q.hold_grow = o->hold_grow; q.meta = p.meta; q.rec = p.rec; q.corners = p.corners;
         q.tpl = (uint8_t*)sc.alloc(S * M * kFollowSlotBytes); q.tmeta = (int*)(q.tpl + S * M * kFollowSide * kFollowSide);
         q.slot_moves = sc.make<int>(S * M * 4);
+        if (mo) p.tmeta = q.tmeta;
         moves_dev = sc.inout(fw->moves, nout * 4);
         fr = sc.stage(fw->format, fw->host_planes, (int)(F * S), fw->h, fw->w, fw->pitch0, fw->pitch1);      // read only: nothing to copy back
         q.g = fr.geo(n_streams);
@@ -1349,6 +1353,7 @@ int op_track_sequence(const char* who, int device, const cf_track_opts* o, int n
         p.counts = first.counts + f * S;
         p.dets = first.dets + f * S * M * 5; p.lms_out = first.lms_out + f * S * M * 10; p.info = first.info + f * S * M * 3;
         p.out_counts = first.out_counts + f * S; p.flags = first.flags + f * S;
+        if (first.vel_out) p.vel_out = first.vel_out + f * S * M * 2;
         if (!fw || fw->detect[f]) sc.run([&] { return launch_track_update(sc.s, p); });
         if (!fw) continue;
         q.planes = fr.planes(f * S);
@@ -1379,6 +1384,26 @@ int cf_op_follow(int device, const cf_track_opts* o, const cf_follow_opts* fo, i
                  float* lms, int32_t* info, int32_t* counts, int32_t* flags, int32_t* moves) {
     const OpFollow fw{fo, detect, format, reinterpret_cast<const void* const*>(frames), h, w, pitch0, pitch1, space_h, space_w, tiled, moves};
     return op_track_sequence("cf_op_follow", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, &fw);
+}
+
+int cf_op_track_ex(int device, const cf_track_opts* o, const cf_track_weak_opts* weak, const cf_track_motion_opts* motion, int n_streams, int n_frames,
+                   int rows, const float* boxes, const float* scores, const float* lms_in, const int32_t* counts_in, float* dets, float* lms, int32_t* info,
+                   int32_t* counts, int32_t* flags, float* vel) {
+    if (!motion) return cf_op_track_weak(device, o, weak, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags);
+    return op_track_sequence("cf_op_track_ex", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, nullptr,
+                             weak, motion, vel);
+}
+
+int cf_op_follow_ex(int device, const cf_track_opts* o, const cf_track_weak_opts* weak, const cf_track_motion_opts* motion, const cf_follow_opts* fo,
+                    int n_streams, int n_frames, int rows, const float* boxes, const float* scores, const float* lms_in, const int32_t* counts_in,
+                    const uint8_t* detect, int format, const cf_planes_rw* frames, int h, int w, int pitch0, int pitch1, int space_h, int space_w, int tiled,
+                    float* dets, float* lms, int32_t* info, int32_t* counts, int32_t* flags, int32_t* moves) {
+    if (!weak && !motion)
+        return cf_op_follow(device, o, fo, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, detect, format, frames, h, w, pitch0, pitch1, space_h,
+                            space_w, tiled, dets, lms, info, counts, flags, moves);
+    const OpFollow fw{fo, detect, format, reinterpret_cast<const void* const*>(frames), h, w, pitch0, pitch1, space_h, space_w, tiled, moves};
+    return op_track_sequence("cf_op_follow_ex", device, o, n_streams, n_frames, rows, boxes, scores, lms_in, counts_in, dets, lms, info, counts, flags, &fw,
+                             weak, motion);
 }
 
 // The kernels of cf_scene_check over a sequence of host frames, with the state of a fresh cf_scene (nothing valid) and no tracker.

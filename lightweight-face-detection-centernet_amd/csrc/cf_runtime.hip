@@ -2339,7 +2339,9 @@ struct cf_tracker : StreamState {
     static constexpr const char* noun = "tracker";
     cf_track_opts o{};
     bool weak = false; cf_track_weak_opts wo{};                         // cf_track_create_weak: the second pass of the update
+    bool motion = false; cf_track_motion_opts mo{};                     // cf_track_create_ex: prediction, velocities, coasting
     int* meta = nullptr; float* rec = nullptr; int* next_id = nullptr;
+    float* vel = nullptr;                                               // [S][max_tracks][2], motion trackers only
     uint8_t* fol = nullptr;                                             // the follower records (cf_track_follow), allocated by the first follow
     RowSpace sp;                                                        // the coordinate space of the first update
 };
@@ -2463,13 +2465,21 @@ extern "C" {
 // ---- face tracks across frames (cf_track.hip)
 int cf_track_destroy(cf_tracker* t) { return state_destroy(t); }
 
-static int track_create(const char* who, cf_ctx* c, int n_streams, const cf_track_opts* o, const cf_track_weak_opts* w, cf_tracker** out) {
+static int track_create(const char* who, cf_ctx* c, int n_streams, const cf_track_opts* o, const cf_track_weak_opts* w, cf_tracker** out,
+                        const cf_track_motion_opts* m = nullptr) {
     const char* why = track_check(o, n_streams);
-    if (int r = state_create_check(c, who, why ? why : track_weak_check(w), out)) return r;
+    if (!why) why = track_weak_check(w);
+    if (int r = state_create_check(c, who, why ? why : track_motion_check(m), out)) return r;
     cf_tracker* t = new cf_tracker();
     t->o = *o;
     if (w) { t->weak = true; t->wo = *w; }
     const size_t slots = (size_t)n_streams * o->max_tracks;
+    if (m) {                                                            // (birth zeroes a slot's velocity: no initial value is needed, zero all the same)
+        t->motion = true; t->mo = *m;
+        return state_create(c, t, n_streams, {{(void**)&t->meta, slots * 4 * sizeof(int), 0}, {(void**)&t->rec, slots * 16 * sizeof(float), 0},
+                                              {(void**)&t->next_id, (size_t)n_streams * sizeof(int), 1}, {(void**)&t->vel, slots * 2 * sizeof(float), 0}},
+                            out, "%s: %d streams x %d tracks: %s", who, n_streams, o->max_tracks);
+    }
     return state_create(c, t, n_streams, {{(void**)&t->meta, slots * 4 * sizeof(int), 0}, {(void**)&t->rec, slots * 16 * sizeof(float), 0},
                                           {(void**)&t->next_id, (size_t)n_streams * sizeof(int), 1}},
                         out, "%s: %d streams x %d tracks: %s", who, n_streams, o->max_tracks);
@@ -2481,6 +2491,10 @@ int cf_track_create(cf_ctx* c, int n_streams, const cf_track_opts* o, cf_tracker
 
 int cf_track_create_weak(cf_ctx* c, int n_streams, const cf_track_opts* o, const cf_track_weak_opts* w, cf_tracker** out) {
     return w ? track_create("cf_track_create_weak", c, n_streams, o, w, out) : cf_track_create(c, n_streams, o, out);
+}
+
+int cf_track_create_ex(cf_ctx* c, int n_streams, const cf_track_opts* o, const cf_track_weak_opts* w, const cf_track_motion_opts* m, cf_tracker** out) {
+    return m ? track_create("cf_track_create_ex", c, n_streams, o, w, out, m) : cf_track_create_weak(c, n_streams, o, w, out);
 }
 
 int cf_track_reset(cf_tracker* t, int stream) {
@@ -2509,7 +2523,9 @@ int cf_track_update(cf_ctx* c, cf_tracker* t, int stream0, float* dets, float* l
     p.B = B; p.stream0 = stream0;
     p.iou_thresh = t->o.iou_thresh; p.max_age = t->o.max_age; p.min_hits = t->o.min_hits; p.max_tracks = M; p.hold_grow = t->o.hold_grow;
     p.set_weak(t->weak ? &t->wo : nullptr);
+    p.set_motion(t->motion ? &t->mo : nullptr);
     p.meta = t->meta; p.rec = t->rec; p.next_id = t->next_id;
+    if (t->motion) { p.vel = t->vel; p.tmeta = t->fol ? (int*)(t->fol + (size_t)t->S * M * kFollowSide * kFollowSide) : nullptr; }
     p.dets = (float*)ws.dets.p; p.lms_out = (float*)ws.lms.p; p.info = (int*)ws.info.p; p.corners = (float*)ws.corners.p;
     p.out_counts = (int*)ws.counts.p; p.flags = (int*)ws.flags.p;
     HIPCHK(c, ordered(c, t, [&] { return launch_track_update(c->stream, p); }));

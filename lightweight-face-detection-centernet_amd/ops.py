@@ -631,18 +631,24 @@ def flip_heads(records, B, device=0):
     return out, plane
 
 
-def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=None, device=0, birth_score=None, weak_iou=None, **opts):
+def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=None, device=0, birth_score=None, weak_iou=None, motion=None, vel=False,
+                   **opts):
     """The tracker's update over a whole sequence (``cf_op_track``) with a fresh tracker: boxes [F, S, rows, 4], scores [F, S, rows], lms
     [F, S, rows, 10], counts [F, S] -- frame f of stream s has the rows below min(count, rows), in whatever coordinates they are.
     ``opts``: iou, max_age, min_hits, max_tracks, hold_grow (``_lib.track_opts``).  ``birth_score``: the tracker with two thresholds
     (``cf_op_track_weak``) -- rows with score > birth_score associate as before, the others may only match a confirmed track, at IoU >=
     ``weak_iou`` (0.5 unless given), and are never born; flag bit 1 says that one did.  Returns (dets [F, S, max_tracks, 5], lms
     [F, S, max_tracks, 10], info [F, S, max_tracks, 3] = id, hits, misses, counts [F, S], flags [F, S]) after every frame; rows at and
-    past a count keep the bytes of the ``dets`` / ``lms_out`` / ``info`` arrays passed in (zeros by default)."""
+    past a count keep the bytes of the ``dets`` / ``lms_out`` / ``info`` arrays passed in (zeros by default).
+    ``motion``: None, True or dict(gain=, damp=) -- the tracker with constant-velocity prediction (``cf_op_track_ex``; include/centerface_hip.h
+    "constant velocity"): rows are matched against the predicted boxes and held boxes coast.  gain 0.5 and damp 1.0 are this project's
+    choices; nobody has measured them and no accuracy claim is made.  ``vel=True``: the velocities [F, S, max_tracks, 2] of the output rows
+    are returned as a sixth item (an array: it is also the initial content; all zero without ``motion``)."""
     o = _lib.track_opts(**opts)
     if birth_score is None and weak_iou is not None:
         raise ValueError("weak_iou needs birth_score")
     wo = None if birth_score is None else _lib.track_weak_opts(birth_score, 0.5 if weak_iou is None else weak_iou)
+    mo = _lib.track_motion_of(motion)
     b = np.ascontiguousarray(boxes, dtype=np.float32)
     if b.ndim != 4 or b.shape[3] != 4:
         raise ValueError("boxes must be [F, S, rows, 4], got %s" % (b.shape,))
@@ -656,15 +662,22 @@ def track_sequence(boxes, scores, lms, counts, dets=None, lms_out=None, info=Non
     oi = np.zeros((F, S, M, 3), np.int32) if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(F, S, M, 3)
     oc, fl = np.zeros((F, S), np.int32), np.zeros((F, S), np.int32)
     tabs = (ptr(b), ptr(sc), ptr(lm), ptr(cn), ptr(od), ptr(ol), ptr(oi), ptr(oc), ptr(fl))
-    if wo is None:
+    want_vel = vel is not None and vel is not False
+    ov = None
+    if want_vel:
+        ov = np.zeros((F, S, M, 2), np.float32) if vel is True else np.ascontiguousarray(vel, dtype=np.float32).reshape(F, S, M, 2)
+    if mo is not None:
+        _lib.check(_lib.lib().cf_op_track_ex(device, C.byref(o), None if wo is None else C.byref(wo), C.byref(mo), S, F, rows, *tabs,
+                                             None if ov is None else ptr(ov)), op=True)
+    elif wo is None:
         _lib.check(_lib.lib().cf_op_track(device, C.byref(o), S, F, rows, *tabs), op=True)
     else:
         _lib.check(_lib.lib().cf_op_track_weak(device, C.byref(o), C.byref(wo), S, F, rows, *tabs), op=True)
-    return od, ol, oi, oc, fl
+    return (od, ol, oi, oc, fl, ov) if want_vel else (od, ol, oi, oc, fl)
 
 
 def follow_sequence(boxes, scores, lms, counts, frames, fmt="bgr", space_hw=None, detect=None, *, tiled=False, search=4, max_sad=4096,
-                    dets=None, lms_out=None, info=None, moves=None, device=0, **opts):
+                    dets=None, lms_out=None, info=None, moves=None, device=0, motion=None, birth_score=None, weak_iou=None, **opts):
     """``track_sequence`` with the follower behind every frame (``cf_op_follow``): frame f of stream s is ``frames[f * S + s]`` -- F * S host
     frames of one size as ``redact_faces`` takes them (BGR uint8 [F*S,h,w,3], dense 4:2:0 uint8 [F*S, h*3//2, w], or per-frame plane
     tuples of pitched rows), only read.  ``detect`` [F] (default: all): where it is set the update with the frame's rows runs first,
@@ -672,8 +685,14 @@ def follow_sequence(boxes, scores, lms, counts, frames, fmt="bgr", space_hw=None
     ``max_sad`` moves nothing; the two defaults are this project's choices, no accuracy claim is made for them.  ``space_hw``: the (H, W)
     the rows are in, mapped to the frame by w / W, h / H; ``tiled=True``: the rows are in frame pixels (``space_hw`` is the frame's size).
     ``opts`` as ``track_sequence``.  Returns (dets, lms, info, counts, flags, moves [F, S, max_tracks, 4] = px, py, SAD, code
-    (``_lib.CF_FOLLOW_*``)) after every frame; rows at and past a count keep the bytes of the arrays passed in (zeros by default)."""
+    (``_lib.CF_FOLLOW_*``)) after every frame; rows at and past a count keep the bytes of the arrays passed in (zeros by default).
+    ``motion`` (and ``birth_score`` / ``weak_iou``) as ``track_sequence``: the updates are those of that tracker (``cf_op_follow_ex``), and a
+    coasted slot is FOLLOWED from its coasted place with the template of its last detection."""
     o, fo = _lib.track_opts(**opts), _lib.follow_opts(search, max_sad)
+    if birth_score is None and weak_iou is not None:
+        raise ValueError("weak_iou needs birth_score")
+    wo = None if birth_score is None else _lib.track_weak_opts(birth_score, 0.5 if weak_iou is None else weak_iou)
+    mo = _lib.track_motion_of(motion)
     b = np.ascontiguousarray(boxes, dtype=np.float32)
     if b.ndim != 4 or b.shape[3] != 4:
         raise ValueError("boxes must be [F, S, rows, 4], got %s" % (b.shape,))
@@ -692,8 +711,13 @@ def follow_sequence(boxes, scores, lms, counts, frames, fmt="bgr", space_hw=None
     oi = np.zeros((F, S, M, 3), np.int32) if info is None else np.ascontiguousarray(info, dtype=np.int32).reshape(F, S, M, 3)
     om = np.zeros((F, S, M, 4), np.int32) if moves is None else np.ascontiguousarray(moves, dtype=np.int32).reshape(F, S, M, 4)
     oc, fl = np.zeros((F, S), np.int32), np.zeros((F, S), np.int32)
-    _lib.check(_lib.lib().cf_op_follow(device, C.byref(o), C.byref(fo), S, F, rows, ptr(b), ptr(sc), ptr(lm), ptr(cn), ptr(dt), _lib.frame_format(fmt), tab,
-                                       h, w, pitch0, pitch1, H, W, 1 if tiled else 0, ptr(od), ptr(ol), ptr(oi), ptr(oc), ptr(fl), ptr(om)), op=True)
+    if wo is None and mo is None:
+        _lib.check(_lib.lib().cf_op_follow(device, C.byref(o), C.byref(fo), S, F, rows, ptr(b), ptr(sc), ptr(lm), ptr(cn), ptr(dt), _lib.frame_format(fmt), tab,
+                                           h, w, pitch0, pitch1, H, W, 1 if tiled else 0, ptr(od), ptr(ol), ptr(oi), ptr(oc), ptr(fl), ptr(om)), op=True)
+    else:
+        _lib.check(_lib.lib().cf_op_follow_ex(device, C.byref(o), None if wo is None else C.byref(wo), None if mo is None else C.byref(mo), C.byref(fo), S, F,
+                                              rows, ptr(b), ptr(sc), ptr(lm), ptr(cn), ptr(dt), _lib.frame_format(fmt), tab, h, w, pitch0, pitch1, H, W,
+                                              1 if tiled else 0, ptr(od), ptr(ol), ptr(oi), ptr(oc), ptr(fl), ptr(om)), op=True)
     del keep
     return od, ol, oi, oc, fl, om
 

@@ -20,7 +20,14 @@ and three on a LARGER row count, a decode at a threshold lowered further until e
   decode60_us, decode60_update_us (a plain tracker: every row associates and is born), decode60_update_weak_us (birth_score = the
   median over the images of the 21st row's score, so about 20 rows per image are strong and 40 weak: the weak rows only look for a
   confirmed track, find none -- a weak row is never born -- and are discarded in every update)
-update_*_us are the differences to the decode of the same rows."""
+update_*_us are the differences to the decode of the same rows.
+
+--motion: the tracker with constant-velocity prediction (cf_track_create_ex) beside the plain one, in the same run and the same
+alternation, on the SAME 20 rows:
+  decode_update_motion_us       10 x (the same decode + cf_track_update of a motion tracker, gain 0.5, damp 1.0)
+update_motion_us is the difference to decode_us, to be read beside update_us of this run.  The faces stand still, so every velocity is 0
+and every row matches its predicted box at IoU 1: what is timed is the motion instance's extra loads and stores (vel, the stored box of a
+winner), not a different association.  No threshold is attached to the figure."""
 import json
 import os
 import sys
@@ -30,7 +37,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import centerface_amd as cfa
 
-short, weak = "--short" in sys.argv, "--weak" in sys.argv
+short, weak, motion = "--short" in sys.argv, "--weak" in sys.argv, "--motion" in sys.argv
 B, H, W, MAXF, MAXW, REP, WIN = 16, 544, 960, 20, 60, 10, 7
 rng = np.random.default_rng(0)
 eng = cfa.Engine(H, W, max_batch=B, dtype="bf16", decode_stream=False)
@@ -87,6 +94,17 @@ if weak:
               ("decode60_update", update_of(plain60, thr_w, MAXW)), ("decode60_update_weak", update_of(weak60, thr_w, MAXW))]
     out.update(weak_score_thresh=thr_w, birth_score60=birth60, rows60_per_image=[int(c) for c in n_w], strong_rows60_per_image=strong)
 
+if motion:
+    moving = cfa.Tracker(eng, B, max_tracks=256, motion=True)
+    trackers.append(moving)
+
+    def decode_update_motion():
+        eng.decode_threshold_enqueue(thr, 0.3, MAXF)
+        eng.track_update_device(moving, 0, counts_ptr=d_counts)
+
+    calls.append(("decode_update_motion", decode_update_motion))
+    out.update(motion=moving.motion)
+
 for _ in range(3):                                                              # warm-up: code objects, the context's tracked rows
     for _, call in calls:
         call()
@@ -115,6 +133,8 @@ if not short:
         out["update_weak_us"] = round(out["decode_update_weak_us"] - out["decode_us"], 2)
         out["update60_us"] = round(out["decode60_update_us"] - out["decode60_us"], 2)
         out["update60_weak_us"] = round(out["decode60_update_weak_us"] - out["decode60_us"], 2)
+    if motion:
+        out["update_motion_us"] = round(out["decode_update_motion_us"] - out["decode_us"], 2)
 eng.synchronize()
 eng.device_free(d_counts)
 for t in trackers:
